@@ -10,7 +10,7 @@ mode.  `value` is env-steps (env-cycles) per second in every mode: N envs x cycl
 Inputs are resident in HBM before the timed region; nothing is copied to the host inside it.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--task reach_ball|match]
-                  [--mode rollout|step|graph] [--fuse T] [--noise] [--league-exchange]
+                  [--mode rollout|step|graph] [--fuse T] [--noise] [--league-exchange] [--dump-outputs DIR]
 
 Workload naming (BASELINE.json `configs`): --envs 65536 = configs[2] (default; kwargs of
 dqn_stable_baselines3.py:18-31, uniform random policy drawn in-kernel, reset distribution of
@@ -33,6 +33,14 @@ a box with fewer than N GPUs the same entry point runs a REHEARSAL (ranks share 
 says so in `config.rehearsal`.  --league-exchange adds the one collective the path has: the
 all-gather of every rank's rollout slab (RCCL over xGMI) on a side stream, overlapped with the
 next rollout (BASELINE.json configs[4]).
+
+--dump-outputs DIR: after the timed regions, rank 0 writes what the LAST timed step computed -- the arrays a caller of the
+timed path receives (rollout mode: obs, action, reward, done, result of the last launch; step / graph mode: obs, reward, done,
+result of the last cycle; --task match: its rollout record / reward_left, done) -- as DIR/<name>.npy, float32 for float arrays
+and float64 (exact) for integer ones.  Every array keeps the same fixed, seeded sample of envs (all of them when they fit in
+DUMP_BYTES).  The settle and warm-up phases run for a time, not a count, so with this flag the engine's state is put back to
+its seeded post-reset state before the last timed region: the dumped step has the same inputs on every run with the same
+arguments, whatever build computes it.
 """
 import argparse
 import json
@@ -64,6 +72,8 @@ DDPG_KWARGS = dict(change_ball_position=False, change_ball_velocity=False, ball_
                    ball_direction=0, min_distance_to_ball=5.0, max_steps=200, action_space_size=16, use_continuous_action=True,
                    use_turning=False)
 REPEATS = 5
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes of array data in all
+DUMP_SEED = 0x5EED             # --dump-outputs: which envs the sample keeps
 
 
 def parse(argv=None):
@@ -96,6 +106,9 @@ def parse(argv=None):
     ap.add_argument('--eager', action='store_true', help='issue the timed launches eagerly from Python instead of replaying one hipGraph')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample-steps', type=int, default=0, help='0 = auto (about 10-20 s of CPU work)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (a fixed, seeded sample of envs, '
+                         f'at most {DUMP_BYTES >> 20} MiB); its inputs are the same on every run with the same arguments')
     args = ap.parse_args(argv)
     per_cycle = args.mode == 'step'
     if args.steps is None:
@@ -106,6 +119,8 @@ def parse(argv=None):
         args.envs = 8192 if args.task == 'match' else 65536
     if args.steps < 1 or args.warmup < 0 or args.fuse < 1 or args.repeats < 1 or args.envs < 1:
         ap.error('--steps, --fuse, --repeats, --envs must be >= 1, --warmup >= 0')
+    if args.dump_outputs and args.league_exchange:
+        ap.error('--dump-outputs covers the rollout, step and graph modes and --task match, not --league-exchange')
     if args.mode == 'graph':
         args.eager = True          # that mode replays its own graph of single-cycle launches
     args.cycles_per_step = 1 if per_cycle else args.fuse
@@ -317,9 +332,10 @@ WARM_REGIONS = 3
 WARM_MS = 100.0
 
 
-def timed_regions(run, repeats, stream, dist, dev, warm_regions=WARM_REGIONS):
+def timed_regions(run, repeats, stream, dist, dev, warm_regions=WARM_REGIONS, before_last=None):
     """`repeats` timed regions of one `run()` each: barrier + synchronize on both sides, wall clock and ONE HIP event pair on the
     launch stream per region.  Returns (wall seconds per region, max over ranks; event seconds per region, this rank).
+    `before_last()` (--dump-outputs) runs before the last region, outside its timing.
     `warm_regions` untimed runs come first: capturing the graph leaves the device idle for tens of milliseconds and its clock ramps
     up again over the next ~10 ms of load -- round 3's five timed regions of every line rose monotonically (87 -> 102 G) because the
     first two were that ramp, not the kernel."""
@@ -334,7 +350,9 @@ def timed_regions(run, repeats, stream, dist, dev, warm_regions=WARM_REGIONS):
             run()
             torch.cuda.synchronize()
             done += 1
-    for _ in range(repeats):
+    for i in range(repeats):
+        if before_last is not None and i == repeats - 1:
+            before_last()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         if dist is not None:
             dist.barrier()
@@ -354,6 +372,50 @@ def timed_regions(run, repeats, stream, dist, dev, warm_regions=WARM_REGIONS):
 
 def median_of(xs):
     return float(statistics.median(xs))
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# --------------------------------------------------------------------------------------------------------------------
+def restorer(eng, snapshot):
+    """before_last hook of timed_regions(): copy `snapshot` (a clone of the engine's arena taken right after its seeded reset;
+    the arena is the whole state, the Philox counter included) back into the engine, keeping the episode counters of the run."""
+    if snapshot is None:
+        return None
+
+    def restore():
+        import torch
+        stats = eng.stats_striped.clone()
+        eng.arena.copy_(snapshot)
+        eng.stats_striped.copy_(stats)
+        torch.cuda.synchronize()
+    return restore
+
+
+def output_sample(arrays, env_axis, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Host copies of `arrays` (name -> tensor; envs along `env_axis`) for --dump-outputs: float32 stays float32, everything else
+    becomes float64 (exact for the engine's integer types).  Every array keeps the same envs: all of them if they fit in `budget`
+    bytes, otherwise a fixed sample (sorted) drawn with `seed`."""
+    import numpy as np
+    import torch
+    n = next(iter(arrays.values())).shape[env_axis]
+    per_env = sum(a.numel() // n * (4 if a.dtype == torch.float32 else 8) for a in arrays.values())
+    k = min(n, budget // per_env)
+    if k < 1:
+        raise ValueError(f'--dump-outputs: one env of this run takes {per_env} bytes, more than the {budget} of the dump')
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    out = {}
+    for name, a in arrays.items():
+        s = a.index_select(env_axis, torch.as_tensor(idx, device=a.device)).cpu().numpy()
+        out[name] = s if s.dtype == np.float32 else s.astype(np.float64)
+    return out
+
+
+def write_outputs(dirname, arrays, env_axis):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in output_sample(arrays, env_axis).items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def load_traffic(mode, fuse, n_envs):
@@ -416,9 +478,11 @@ def n_rotating(per_buf_bytes):
     return max(2, -(-(600 << 20) // per_buf_bytes))
 
 
-def measure_rollout(eng, T, launches, nbuf, repeats, stream, settle_ms, dist=None, dev=None, warm=4, warm_regions=WARM_REGIONS):
+def measure_rollout(eng, T, launches, nbuf, repeats, stream, settle_ms, dist=None, dev=None, warm=4, warm_regions=WARM_REGIONS,
+                    snapshot=None):
     """`repeats` regions of `launches` rollout launches of T cycles each, cycling through nbuf record buffers.
-    Returns dict(value-free raw figures): median wall / event seconds per launch, the per-region figures."""
+    Returns dict(value-free raw figures): median wall / event seconds per launch, the per-region figures.  With a `snapshot`
+    (--dump-outputs) the engine restarts from it before the last region, and 'last' is the record of the last launch."""
     n = eng.num_envs
     bufs = [eng.alloc_rollout(T) for _ in range(nbuf)]
     k = [0]
@@ -431,11 +495,15 @@ def measure_rollout(eng, T, launches, nbuf, repeats, stream, settle_ms, dist=Non
     import torch
     torch.cuda.synchronize()
     g = graph_of(lambda: issue(launches))
-    wall, evs = timed_regions(g.replay, repeats, stream, dist, dev, warm_regions)
+    wall, evs = timed_regions(g.replay, repeats, stream, dist, dev, warm_regions, restorer(eng, snapshot))
     rec = RECORD_BYTES + (12 if (eng.cfg.task.use_continuous_action and eng.cfg.task.use_turning) else 0)   # float[4] actions
     alg = n * (2 * STATE_BYTES + T * rec)
-    return {'wall': wall, 'events': evs, 'launch_s': median_of(wall) / launches, 'launch_s_events': median_of(evs) / launches,
-            'alg_bytes_launch': alg, 'launches': launches, 'buffers': nbuf, 'bytes_in_flight': nbuf * T * n * rec}
+    m = {'wall': wall, 'events': evs, 'launch_s': median_of(wall) / launches, 'launch_s_events': median_of(evs) / launches,
+         'alg_bytes_launch': alg, 'launches': launches, 'buffers': nbuf, 'bytes_in_flight': nbuf * T * n * rec}
+    if snapshot is not None:
+        last = bufs[(k[0] - 1) % nbuf]                       # the buffer the graph's last launch writes
+        m['last'] = {name: v for name, v in last.items() if v is not None}
+    return m
 
 
 def rollout_entry(m, n, T, kernel, traffic_key):
@@ -498,8 +566,11 @@ def measure_step_k(eng, k, launches, repeats, stream, settle_ms):
             'record': 'obs, action, reward, done, result of every cycle ([k][N]); caller actions int32 [k][N]'}
 
 
-def measure_match(n, dev, rank, T, launches, repeats, stream, settle_ms, noise=False, phase='spread', mode='rollout', dist=None, match_kw=None):
-    """11v11 engine: `launches` rollout launches of T cycles (or single-cycle launches in step mode) per region."""
+def measure_match(n, dev, rank, T, launches, repeats, stream, settle_ms, noise=False, phase='spread', mode='rollout', dist=None, match_kw=None,
+                  dump=False):
+    """11v11 engine: `launches` rollout launches of T cycles (or single-cycle launches in step mode) per region.  dump=True
+    (--dump-outputs): the engine restarts from its seeded initial state before the last region, and 'last' holds what the last
+    launch returned."""
     import torch
     from soccer2d_amd.match import MatchEngine, make_match_config
     extra = dict(match_kw or {})
@@ -511,6 +582,7 @@ def measure_match(n, dev, rank, T, launches, repeats, stream, settle_ms, noise=F
         # cycles after each -- do not coincide across the batch, as in any batch that has run for a while
         g = torch.Generator(device='cpu').manual_seed(1234 + rank)
         eng.cycle += (2 * torch.randint(0, 1500, (n,), generator=g, dtype=torch.int32)).to(dev)
+    snapshot = eng.arena.clone() if dump else None
     ro = eng.alloc_rollout(T) if mode == 'rollout' else None
     per_launch = T if mode == 'rollout' else 1
 
@@ -524,7 +596,7 @@ def measure_match(n, dev, rank, T, launches, repeats, stream, settle_ms, noise=F
     issue(2)
     torch.cuda.synchronize()
     gr = graph_of(lambda: issue(launches))
-    wall, evs = timed_regions(gr.replay, repeats, stream, dist, dev)
+    wall, evs = timed_regions(gr.replay, repeats, stream, dist, dev, before_last=restorer(eng, snapshot))
     ls, le = median_of(wall) / launches, median_of(evs) / launches
     alg = n * (2 * MATCH_STATE_BYTES + (per_launch * MATCH_RECORD_BYTES if mode == 'rollout' else 5))
     st = eng.stats.cpu().tolist()
@@ -548,11 +620,15 @@ def measure_match(n, dev, rank, T, launches, repeats, stream, settle_ms, noise=F
     if valu_per_wave_cycle:
         roof['issue_model']['achieved'] = waves * per_launch * valu_per_wave_cycle / ls / 1e9
         roof['issue_model']['frac'] = roof['issue_model']['achieved'] / VALU_PEAK_GINSTR
-    return {'value': n * per_launch / ls, 'unit': 'env-steps/s', 'launches_per_region': launches, 'cycles_per_launch': per_launch,
-            'phase': phase, 'repeats': [n * per_launch * launches / w for w in wall], 'wall': wall,
-            'player_steps_per_s': 22 * n * per_launch / ls, 'roofline': roof,
-            'events': {'goals_left': st[1], 'goals_right': st[2], 'matches': st[3], 'kicks': st[4], 'tackles': st[5],
-                       'offsides': st[6], 'ball_outs': st[7]}}
+    mm = {'value': n * per_launch / ls, 'unit': 'env-steps/s', 'launches_per_region': launches, 'cycles_per_launch': per_launch,
+          'phase': phase, 'repeats': [n * per_launch * launches / w for w in wall], 'wall': wall,
+          'player_steps_per_s': 22 * n * per_launch / ls, 'roofline': roof,
+          'events': {'goals_left': st[1], 'goals_right': st[2], 'matches': st[3], 'kicks': st[4], 'tackles': st[5],
+                     'offsides': st[6], 'ball_outs': st[7]}}
+    if dump:
+        mm['last'] = ({name: v for name, v in ro.items() if v is not None} if mode == 'rollout'
+                      else {'reward_left': eng.reward_left, 'done': eng.done})
+    return mm
 
 
 def match_valu_per_wave_cycle():
@@ -653,6 +729,8 @@ def run_reach(args, dev, dist, rank, world):
     metric, workload = workload_of('reach_ball', n, world, args.league_exchange)
     default_line = world == 1 and not args.no_secondary and args.mode == 'rollout' and args.variant == 'dqn' and not args.league_exchange
     eng = reach_engine(n, dev, rank, args.noise, args.variant)
+    snapshot = eng.arena.clone() if args.dump_outputs else None        # the seeded post-reset state (--dump-outputs)
+    dumped = None
     per_buf = T * n * RECORD_BYTES
     nbuf = args.rotate_buffers if args.rotate_buffers > 0 else n_rotating(per_buf)
     K = args.steps
@@ -666,7 +744,8 @@ def run_reach(args, dev, dist, rank, world):
 
     league = None
     if args.mode == 'rollout' and not args.league_exchange:
-        m = measure_rollout(eng, T, K, nbuf, args.repeats, stream, args.settle_ms, dist, dev, warm=args.warmup)
+        m = measure_rollout(eng, T, K, nbuf, args.repeats, stream, args.settle_ms, dist, dev, warm=args.warmup, snapshot=snapshot)
+        dumped = (m.pop('last', None), 1)
         wall, launch_s, launch_ev = m['wall'], m['launch_s'], m['launch_s_events']
         steps_per_launch, alg = T, m['alg_bytes_launch']
         traffic_key = ('rollout' if nbuf == 1 else 'rollout-rotate') + ('-noise' if args.noise else '')
@@ -704,9 +783,13 @@ def run_reach(args, dev, dist, rank, world):
         settle(lambda c: [eng.step(None) for _ in range(c)], 2048, args.settle_ms)
         for _ in range(args.warmup * args.cycles_per_step):
             eng.step(None)
-        wall, evs = timed_regions(run, args.repeats, stream, dist, dev)
+        wall, evs = timed_regions(run, args.repeats, stream, dist, dev, before_last=restorer(eng, snapshot))
+        dumped = ({'obs': eng.obs, 'reward': eng.reward, 'done': eng.done, 'result': eng.result}, 0)    # what step() returns
         launch_s, launch_ev = median_of(wall) / k_cycles, median_of(evs) / k_cycles
         steps_per_launch, alg, traffic_key, n_launches = 1, n * (2 * STATE_BYTES + 4 + RECORD_BYTES - 4), 'step', k_cycles
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, *dumped)
+    dumped = snapshot = None
     kernel = eng.kernel_name()
     elapsed = median_of(wall)
     cycles_per_region = K * args.cycles_per_step
@@ -858,9 +941,13 @@ def run_match(args, dev, dist, rank, world):
     stream = torch.cuda.current_stream(dev)
     metric, workload = workload_of('match', n, world, False)
     mm = measure_match(n, dev, rank, T, args.steps, args.repeats, stream, args.settle_ms, noise=args.noise,
-                       phase=args.match_phase, mode='rollout' if args.mode == 'rollout' else 'step', dist=dist)
+                       phase=args.match_phase, mode='rollout' if args.mode == 'rollout' else 'step', dist=dist,
+                       dump=bool(args.dump_outputs))
+    last = mm.pop('last', None)
     if rank != 0:
         return None
+    if last is not None:
+        write_outputs(args.dump_outputs, last, 1 if args.mode == 'rollout' else 0)
     elapsed = median_of(mm['wall'])
     per_launch = mm['cycles_per_launch']
     line = {'metric': metric, 'value': world * n * per_launch * args.steps / elapsed, 'unit': 'env-steps/s', 'n_gpus': world,

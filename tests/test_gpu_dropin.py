@@ -535,6 +535,46 @@ def test_bench_self_launches_its_ranks(tmp_path):
         assert le['backend'] == 'gloo' and le['rccl_ranks'] == 0 and 'NOT a multi-GPU measurement' in d['config']['rehearsal']
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last timed step computed, from the same inputs on every run -- runs with different
+    settle phases write the same files, and they equal the CPU oracle's last launch (rollout) / last cycle (step mode) of K steps
+    from the seeded reset (2 048 envs fit the sample budget whole)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def dump(tag, *args):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--repeats', '2', '--no-secondary', '--no-cpu-baseline',
+                            '--dump-outputs', str(d)] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    n, T, K = 2048, 64, 3
+    roll = ['--envs', str(n), '--fuse', str(T), '--steps', str(K), '--warmup', '1']
+    a, b = dump('roll_a', *roll, '--settle-ms', '0'), dump('roll_b', *roll, '--settle-ms', '30')
+    assert sorted(a) == ['action', 'done', 'obs', 'result', 'reward']
+    orc = O.OracleEngine(O.make_config(noise=0, **O.DQN_KWARGS), n, 'f32')
+    orc.reset()
+    ref = orc.rollout(K * T)
+    for name in a:
+        assert a[name].dtype == (np.float32 if name in ('obs', 'reward') else np.float64), name
+        assert a[name].shape == ref[name][-T:].shape, name
+        assert np.array_equal(a[name], b[name]), name
+        assert np.array_equal(a[name], ref[name][-T:].astype(a[name].dtype)), name
+    s = dump('step', '--mode', 'step', '--envs', str(n), '--steps', '5', '--warmup', '2', '--settle-ms', '10')
+    orc = O.OracleEngine(O.make_config(noise=0, **O.DQN_KWARGS), n, 'f32')      # reset() of a used engine starts later episodes
+    orc.reset()
+    for _ in range(5):
+        last = orc.step(None)
+    for name, want in zip(('obs', 'reward', 'done', 'result'), last):
+        assert np.array_equal(s[name], want.astype(s[name].dtype)), name
+    match = ['--task', 'match', '--envs', '256', '--fuse', '16', '--steps', '2', '--warmup', '1']
+    ma, mb = dump('match_a', *match, '--settle-ms', '0'), dump('match_b', *match, '--settle-ms', '30')
+    assert sorted(ma) == ['done', 'mode', 'obs', 'reward'] and ma['obs'].shape[:2] == (16, 256)
+    assert all(np.array_equal(ma[k], mb[k]) for k in ma)
+
+
 def test_command_action_kind_equals_the_oracle():
     """S2D_ACT_COMMAND (the boundary of the reference's action_to_rpc_actions hook): a decoded body command per env -- dash with any
     power / direction, turn, none, and S2D_CMD_FREEZE (the env sits the cycle out) -- executed as it is; GPU == oracle bit for bit,

@@ -263,6 +263,42 @@ def test_bench_names_the_workload_it_runs():
     assert 'custom' in w and 'configs[' not in w
 
 
+def test_bench_output_sample(tmp_path):
+    """--dump-outputs: float32 arrays stay float32, integer arrays become float64 with the same values; every array keeps the
+    same envs -- all of them when they fit, else the same seeded sample on every call -- within the byte budget."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    assert bench.parse(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(['--dump-outputs', str(tmp_path), '--league-exchange'])
+    T, n = 8, 1000
+    g = torch.Generator().manual_seed(1)
+    env_id = torch.arange(n, dtype=torch.float32)
+    arrays = {'obs': env_id[None, :, None] + torch.rand(T, n, 10, generator=g),
+              'action': torch.arange(n, dtype=torch.int32).expand(T, n).contiguous(),
+              'done': torch.randint(0, 2, (T, n), generator=g, dtype=torch.uint8)}
+    full = bench.output_sample(arrays, 1)
+    assert full['obs'].dtype == np.float32 and full['action'].dtype == np.float64 and full['done'].dtype == np.float64
+    for name, a in arrays.items():
+        assert np.array_equal(full[name], a.numpy().astype(full[name].dtype))
+    per_env = T * (10 * 4 + 8 + 8)
+    small = bench.output_sample(arrays, 1, budget=100 * per_env + 7)
+    assert sum(a.nbytes for a in small.values()) <= 100 * per_env + 7 and small['action'].shape == (T, 100)
+    idx = small['action'][0].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(np.floor(small['obs'][0, :, 0]), idx)
+    assert np.array_equal(small['done'], arrays['done'].numpy()[:, idx])
+    again = bench.output_sample(arrays, 1, budget=100 * per_env + 7)
+    assert all(np.array_equal(again[k], small[k]) for k in small)
+    step = bench.output_sample({'obs': arrays['obs'][0], 'done': arrays['done'][0]}, 0, budget=50 * (40 + 8))
+    assert step['obs'].shape == (50, 10) and step['done'].shape == (50,)
+    with pytest.raises(ValueError):
+        bench.output_sample(arrays, 1, budget=per_env - 1)
+    bench.write_outputs(str(tmp_path / 'd'), arrays, 1)
+    assert sorted(os.listdir(tmp_path / 'd')) == ['action.npy', 'done.npy', 'obs.npy']
+    assert np.array_equal(np.load(tmp_path / 'd' / 'obs.npy'), full['obs'])
+
+
 def test_bench_self_launch_builds_the_torchrun_command(monkeypatch, capsys):
     """`python bench.py --gpus N` without WORLD_SIZE: the parent counts GPUs in a child, starts
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same args>` as a child
