@@ -450,6 +450,26 @@ S2D_DEV NoiseIn noise_prepare(const S2DHot& p, uint32_t gid_lo, uint32_t gid_hi,
   n.tu = w.tu;
   return n;
 }
+// Noise kind (template parameter of the reach-ball kernels): 0 off, 1 the lattice above (default), 2 rcssserver's MPObject::noise() --
+// (drand(-m, m), drand(-m, m)) with m = rand * |v|, a uniform square.  Its draw: block 2 of the stream at counter k (one block per
+// cycle; block 0 is the lattice's, block 1 the turn uniform), words x, y -> the player's (dvx, dvy) units, z, w -> the ball's, each
+// c = (w >> 8) * 2^-24 * 2 - 1: exact, in [-1, 1) on the 2^-23 grid.  It is served through the same NoiseIn as the lattice, with
+// magnitude uniform 1 (the multiply by 1 is exact) and c_y / c_x in the sine / cosine slots: add_noise then adds c * (rand * |v|).
+enum { S2D_NK_OFF = 0, S2D_NK_LATTICE = 1, S2D_NK_SQUARE = 2 };
+S2D_DEV float noise_unit(uint32_t w) { return rnd_u01(w) * 2.0f - 1.0f; }
+S2D_DEV NoiseIn noise_from_square(const U4& b, float tu) {
+  return NoiseIn{1.0f, noise_unit(b.y), noise_unit(b.x), 1.0f, noise_unit(b.w), noise_unit(b.z), tu};
+}
+S2D_DEV NoiseIn noise_prepare_square(const S2DHot& p, uint32_t gid_lo, uint32_t gid_hi, uint32_t ctr, uint32_t stream, bool turn) {
+  const float tu = turn ? rnd_u01(s2d_draw(p, gid_lo, gid_hi, ctr, stream, 1).x) : 0.0f;
+  return noise_from_square(s2d_draw(p, gid_lo, gid_hi, ctr, stream, 2), tu);
+}
+template <int NK>
+S2D_DEV NoiseIn noise_prepare_kind(const S2DHot& p, uint32_t gid_lo, uint32_t gid_hi, uint32_t ctr, uint32_t stream, bool turn) {
+  static_assert(NK == S2D_NK_LATTICE || NK == S2D_NK_SQUARE, "noise kind");
+  if constexpr (NK == S2D_NK_SQUARE) return noise_prepare_square(p, gid_lo, gid_hi, ctr, stream, turn);
+  else return noise_prepare(p, gid_lo, gid_hi, ctr, stream, turn);
+}
 S2D_DEV void add_noise(float& vx, float& vy, float rnd, float u_mag, float sn, float cs) {
   float s = hypot2(vx, vy);
   float mag = u_mag * (rnd * s);
@@ -736,7 +756,7 @@ S2D_DEV ResetSample reset_sample_coop(const S2DHot& p, const S2DRare& r, uint32_
   return o;
 }
 // trainer (move ball) (move player) (recover), then the command-less cycle (soccer_2d_env.py:186-197)
-template <bool NOISE>
+template <int NK>
 S2D_DEV float reset_apply(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, uint32_t gid_lo, uint32_t gid_hi,
                           const ResetSample& o, float recover_init, uint32_t key) {
   e.step_number = 0;                                     // :172
@@ -745,27 +765,27 @@ S2D_DEV float reset_apply(const S2DHot& p, const S2DRare* __restrict__ rp, Env& 
   e.stamina = p.stamina_max; e.recovery = recover_init;
   e.effort = p.effort_init; e.capacity = p.stamina_capacity;
   NoiseIn nz{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if (NOISE) nz = noise_prepare(p, gid_lo, gid_hi, key, S2D_ST_NOISE_RESET, false);   // keyed like the sample itself
-  return sim_cycle<NOISE, false>(p, rp, e, S2D_CMD_NONE, CmdPrep{0.0f, 0.0f, 0.0f}, nz);
+  if constexpr (NK != S2D_NK_OFF) nz = noise_prepare_kind<NK>(p, gid_lo, gid_hi, key, S2D_ST_NOISE_RESET, false);   // keyed like the sample itself
+  return sim_cycle<NK != S2D_NK_OFF, false>(p, rp, e, S2D_CMD_NONE, CmdPrep{0.0f, 0.0f, 0.0f}, nz);
 }
 // The env a reset leaves behind -- trainer moves + recover + the command-less cycle, whose noise is keyed by the
 // reset's own key -- is a pure function of (env id, key), so it can be prepared together with the sample (batched,
 // off the critical path) and a reset becomes a register copy plus the cycle's tick.  NextEpisode = that prepared state.
 struct NextEpisode { float px, py, vx, vy, body, stamina, effort, recovery, capacity, bx, by, bvx, bvy; };
-template <bool NOISE>
+template <int NK>
 S2D_DEV NextEpisode episode_prepare(const S2DHot& p, const S2DRare* __restrict__ rp, const S2DRare& r, uint32_t gid_lo,
                                     uint32_t gid_hi, uint32_t key) {
   const ResetSample o = reset_sample(p, r, gid_lo, gid_hi, key);
   Env t{};
-  reset_apply<NOISE>(p, rp, t, gid_lo, gid_hi, o, r.recover_init, key);
+  reset_apply<NK>(p, rp, t, gid_lo, gid_hi, o, r.recover_init, key);
   return NextEpisode{t.px, t.py, t.vx, t.vy, t.body, t.stamina, t.effort, t.recovery, t.capacity, t.bx, t.by, t.bvx, t.bvy};
 }
-template <bool NOISE>
+template <int NK>
 S2D_DEV NextEpisode episode_prepare_coop(const S2DHot& p, const S2DRare* __restrict__ rp, const S2DRare& r, uint32_t gid_lo,
                                          uint32_t gid_hi, uint32_t key, bool need, int lane, uint32_t* scratch) {
   const ResetSample o = reset_sample_coop(p, r, gid_lo, gid_hi, key, need, lane, scratch);
   Env t{};
-  reset_apply<NOISE>(p, rp, t, gid_lo, gid_hi, o, r.recover_init, key);
+  reset_apply<NK>(p, rp, t, gid_lo, gid_hi, o, r.recover_init, key);
   return NextEpisode{t.px, t.py, t.vx, t.vy, t.body, t.stamina, t.effort, t.recovery, t.capacity, t.bx, t.by, t.bvx, t.bvy};
 }
 S2D_DEV void episode_begin(Env& e, const NextEpisode& q) {
@@ -786,12 +806,12 @@ S2D_DEV FirstObs first_obs(const S2DHot& p, const NextEpisode& q) {
   f.dist = hypot2(q.bx - q.px, q.by - q.py);
   return f;
 }
-template <bool NOISE>
+template <int NK>
 S2D_DEV float env_reset(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, uint32_t gid_lo,
                         uint32_t gid_hi) {
   const S2DRare r = *rp;                                 // one bulk scalar load for the whole path
   const uint32_t key = reset_key(e);
   ResetSample o = reset_sample(p, r, gid_lo, gid_hi, key);
   e.episode = (int)key;
-  return reset_apply<NOISE>(p, rp, e, gid_lo, gid_hi, o, r.recover_init, key);
+  return reset_apply<NK>(p, rp, e, gid_lo, gid_hi, o, r.recover_init, key);
 }

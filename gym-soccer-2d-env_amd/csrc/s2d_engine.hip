@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void s2d_init_kernel(S2DHot p, const S2DRar
   S[F_CAPACITY * stride + i] = p.stamina_capacity;
 }
 
-template <bool NOISE>
+template <int NK>
 __global__ __launch_bounds__(kBlock) void s2d_reach_reset_kernel(S2DHot p, const S2DRare* __restrict__ rp,
                                                                  float* __restrict__ S, int64_t stride, int64_t n,
                                                                  const uint8_t* __restrict__ mask, StepOut o) {
@@ -56,14 +56,14 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_reset_kernel(S2DHot p, const
     env_load(e, S, stride, i);
     if (active) {
       uint64_t gid = (((uint64_t)p.gid_hi << 32) | p.gid_lo) + (uint64_t)i;
-      float d2 = env_reset<NOISE>(p, rp, e, (uint32_t)gid, (uint32_t)(gid >> 32));
+      float d2 = env_reset<NK>(p, rp, e, (uint32_t)gid, (uint32_t)(gid >> 32));
       int d, r; float w;
       observe_and_check(p, e, d2, ob, d, w, r);
       env_store(e, S, stride, i);
       o.reward[i] = 0.0f; o.done[i] = 0; o.result[i] = 0;
       if (p.auto_reset) {                                // the per-step API's prepared episodes (see StepOut::prep)
-        prep_store<NOISE>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)e.episode + 1u);
-        prep_store<NOISE>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)e.episode + 2u);
+        prep_store<NK>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)e.episode + 1u);
+        prep_store<NK>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)e.episode + 2u);
       }
     } else {                                             // keep the row this env already has
 #pragma unroll
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_reset_kernel(S2DHot p, const
 
 // The refill workgroups of s2d_step / s2d_step_k (see StepOut::prep): episode e + 2 into slot e & 1 where it is missing -- never the
 // slot that holds episode e + 1, the only one a main wave of the same launch takes a reset from.
-template <bool NOISE>
+template <int NK>
 S2D_DEV void refill_prepared_slots(const S2DHot& p, const S2DRare* __restrict__ rp, float* __restrict__ S, int64_t stride, int64_t n,
                                    const StepOut& o, int lane, uint32_t* scratch) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -90,18 +90,19 @@ S2D_DEV void refill_prepared_slots(const S2DHot& p, const S2DRare* __restrict__ 
   }
   if (__ballot(need) == 0ull) return;                      // wave-uniform
   const uint64_t gid = (((uint64_t)p.gid_hi << 32) | p.gid_lo) + (uint64_t)i;
-  prep_store_coop<NOISE>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), e2, need, lane, scratch);   // the wave draws together
+  prep_store_coop<NK>(p, rp, o.prep, stride, i, (uint32_t)gid, (uint32_t)(gid >> 32), e2, need, lane, scratch);   // the wave draws together
 }
 
-template <int MODE, bool NOISE>
+template <int MODE, int NK>
 __global__ __launch_bounds__(kBlock) void s2d_reach_step_kernel(S2DHot p, const S2DRare* __restrict__ rp,
                                                                 float* __restrict__ S, int64_t stride, int64_t n,
                                                                 const void* __restrict__ actions, int kind,
                                                                 StepOut o, int refill_blocks) {
+  constexpr bool NOISE = NK != S2D_NK_OFF;
   __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][kObsTile];
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   if ((int)blockIdx.x < refill_blocks) {                   // the FIRST blocks of the grid, so that they start first
-    refill_prepared_slots<NOISE>(p, rp, S, stride, n, o, lane, reinterpret_cast<uint32_t*>(&lds[wv][0]));
+    refill_prepared_slots<NK>(p, rp, S, stride, n, o, lane, reinterpret_cast<uint32_t*>(&lds[wv][0]));
     return;
   }
   const int main_block = (int)blockIdx.x - refill_blocks;
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_kernel(S2DHot p, const 
       // A1: one Soccer2DEnv.step (soccer_2d_env.py:226-269), as step_env(), with the reset served from the prefetched slot
       e.step_number += 1;                                  // reach_ball_env.py:55
       NoiseIn nz{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (NOISE) nz = noise_prepare(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
+      if constexpr (NOISE) nz = noise_prepare_kind<NK>(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
       float d2 = sim_cycle<NOISE, true>(p, rp, e, cmd, c, nz);   // trainer forces PlayOn each cycle (:242)
       observe_and_check(p, e, d2, ob, done, reward, res);
       if (done && p.auto_reset) {                          // SB3 VecEnv convention
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_kernel(S2DHot p, const 
           for (int w = 0; w < S2D_OBS_DIM; ++w) ob.o[w] = f.o[w];
           e.prev_dist = f.dist; e.prev_angle = f.rel;      // reach_ball_env.py:166: carry seeded
         } else {                                           // slot not (yet) valid: draw it here
-          d2 = env_reset<NOISE>(p, rp, e, gl, gh);
+          d2 = env_reset<NK>(p, rp, e, gl, gh);
           int dn2, r2; float w2;
           observe_and_check(p, e, d2, ob, dn2, w2, r2);    // reach_ball_env.py:166: carry seeded, outputs dropped
         }
@@ -189,15 +190,16 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_kernel(S2DHot p, const 
 // envs, no prologue, resets served from the persistent prepared slots (refill workgroups in front of the grid) -- at most ONE per env
 // and launch from a slot (the slot of episode e + 2 may be rewritten by this launch's refill workgroups while it is read), later
 // ones are drawn inline.  Per-step outputs go to the caller's record [K][N] (any array may be NULL), the last step's also to the arena.
-template <int MODE, bool NOISE>
+template <int MODE, int NK>
 __global__ __launch_bounds__(kBlock) void s2d_reach_step_k_kernel(S2DHot p, const S2DRare* __restrict__ rp,
                                                                   float* __restrict__ S, int64_t stride, int64_t n, int n_steps,
                                                                   const void* __restrict__ actions, int kind, RolloutOut ro,
                                                                   StepOut o, int refill_blocks) {
+  constexpr bool NOISE = NK != S2D_NK_OFF;
   __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][kObsTile];
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   if ((int)blockIdx.x < refill_blocks) {
-    refill_prepared_slots<NOISE>(p, rp, S, stride, n, o, lane, reinterpret_cast<uint32_t*>(&lds[wv][0]));
+    refill_prepared_slots<NK>(p, rp, S, stride, n, o, lane, reinterpret_cast<uint32_t*>(&lds[wv][0]));
     return;
   }
   const int64_t i = (int64_t)((int)blockIdx.x - refill_blocks) * kBlock + threadIdx.x;
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_k_kernel(S2DHot p, cons
       const CmdPrep c = decide<MODE>(p, actions, kind, row + i, gl, gh, k, t == 0 || (k & 3u) == 0u, quad, squad, ro.action, cmd, dir);
       e.step_number += 1;                                  // reach_ball_env.py:55
       NoiseIn nz{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (NOISE) nz = noise_prepare(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
+      if constexpr (NOISE) nz = noise_prepare_kind<NK>(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
       float d2 = sim_cycle<NOISE, true>(p, rp, e, cmd, c, nz);   // trainer forces PlayOn each cycle (soccer_2d_env.py:242)
       observe_and_check(p, e, d2, ob, done, reward, res);
       if (done && p.auto_reset) {                          // SB3 VecEnv convention
@@ -265,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_k_kernel(S2DHot p, cons
           for (int w = 0; w < S2D_OBS_DIM; ++w) ob.o[w] = f.o[w];
           e.prev_dist = f.dist; e.prev_angle = f.rel;      // reach_ball_env.py:166: carry seeded
         } else {                                           // no valid slot (left): draw it here
-          d2 = env_reset<NOISE>(p, rp, e, gl, gh);
+          d2 = env_reset<NK>(p, rp, e, gl, gh);
           int dn2, r2; float w2;
           observe_and_check(p, e, d2, ob, dn2, w2, r2);    // reach_ball_env.py:166: carry seeded, outputs dropped
         }
@@ -288,11 +290,12 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_step_k_kernel(S2DHot p, cons
   stats_store(srow, lane, sold, wave_first == 0 ? (unsigned long long)n * (unsigned long long)n_steps : 0ull, c1, c2, c3);
 }
 
-template <int MODE, bool NOISE>
+template <int MODE, int NK>
 __global__ __launch_bounds__(kBlock) void s2d_reach_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
                                                                    float* __restrict__ S, int64_t stride, int64_t n,
                                                                    int n_steps, const void* __restrict__ actions,
                                                                    int kind, RolloutOut ro, StepOut o) {
+  constexpr bool NOISE = NK != S2D_NK_OFF;
   __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][kObsTile];
   __shared__ PrepTile prep[kWavesPerBlock];
   __shared__ float4 act_lut[kWavesPerBlock][kWave];        // decoded commands of a small discrete action space (per wave)
@@ -354,7 +357,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_rollout_kernel(S2DHot p_sgpr
   bool have_prep = false;
   uint32_t* const coop_scratch = reinterpret_cast<uint32_t*>(&lds[wv][0]);   // the observation tile is idle between cycles
   if (p.auto_reset) {                                      // full wave, drawn together (reset_sample_coop)
-    prep_fill_coop<NOISE>(p, rp, prep[wv], lane, active ? reset_key(e) : 0u, gl, gh, active, coop_scratch);
+    prep_fill_coop<NK>(p, rp, prep[wv], lane, active ? reset_key(e) : 0u, gl, gh, active, coop_scratch);
     have_prep = active;
   }
   int n_missing = 0;                                       // wave-uniform: lanes whose prepared sample is used up
@@ -373,7 +376,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_rollout_kernel(S2DHot p_sgpr
     if (n_missing >= kRefillMin) {                         // batched refill (wave-uniform counter: no ballot per cycle)
       // (sequential draw: with ~8-20 lanes to serve, the cooperative loop's three rounds cost what their ~4 tries cost, and its
       // registers cost the 1 M-env launch 3 %)
-      if (active && !have_prep) { prep_fill<NOISE>(p, rp, prep[wv], lane, e, gl, gh); have_prep = true; }
+      if (active && !have_prep) { prep_fill<NK>(p, rp, prep[wv], lane, e, gl, gh); have_prep = true; }
       n_missing = 0;
     }
     if (active) {
@@ -388,8 +391,8 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_rollout_kernel(S2DHot p_sgpr
       } else {
         c = decide<MODE>(p, actions, kind, row + i, gl, gh, k, t == 0 || (k & 3u) == 0u, quad, squad, ro.action, cmd, dir);
       }
-      if (fast) step_env<NOISE, true>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, &prep[wv], lane, have_prep, ep_lds, sc_lut);
-      else step_env<NOISE, false>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, &prep[wv], lane, have_prep);
+      if (fast) step_env<NK, true>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, &prep[wv], lane, have_prep, ep_lds, sc_lut);
+      else step_env<NK, false>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, &prep[wv], lane, have_prep);
       if (ro.reward) ro.reward[row + i] = reward;
       if (ro.done) ro.done[row + i] = (uint8_t)done;
       if (ro.result) ro.result[row + i] = (uint8_t)res;
@@ -503,12 +506,13 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_rollout_kernel(S2DHot p_sgpr
 // wave-uniform branches, eleven of them per cycle in the two waves that store -- and those are the long waves when noise is off:
 // with them compiled out the slowest workgroup of a 256-cycle launch counts 296 k clocks instead of 321 k
 // (profiles/r03/ws_static_record.txt).  Instantiated for the discrete-action, noise-off configuration (the DQN script's).
-template <int MODE, bool NOISE, int REC = 0>
+template <int MODE, int NK, int REC = 0>
 __global__ __launch_bounds__(kWsBlock, 4) void s2d_reach_rollout_ws_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
                                                                         float* __restrict__ S, int64_t stride,
                                                                         int64_t n, int n_steps,
                                                                         const void* __restrict__ actions, int kind,
                                                                         RolloutOut ro, StepOut o) {
+  constexpr bool NOISE = NK != S2D_NK_OFF;
   constexpr int kActWords = NOISE ? (int)WA_WORDS : (int)WA_NPM;
   // decoded command (+ prepared noise) of step t in slot t mod 3: the policy wave runs TWO steps ahead of the simulating wave, which
   // fetches the command of its NEXT step at the start of an iteration and, at the iteration's end -- when the body angle after a
@@ -539,7 +543,7 @@ __global__ __launch_bounds__(kWsBlock, 4) void s2d_reach_rollout_ws_kernel(S2DHo
     uint32_t ep0 = 0u;
     if (active) ep0 = reinterpret_cast<const uint32_t*>(S + F_EPISODE * stride)[i];
     const int k = role == 0 ? 0 : role - 1;
-    slot_fill_coop<NOISE>(p_sgpr, rp, slots[k], lane, (uint32_t)gid, (uint32_t)(gid >> 32), ep0 + 1u + (uint32_t)k, active,
+    slot_fill_coop<NK>(p_sgpr, rp, slots[k], lane, (uint32_t)gid, (uint32_t)(gid >> 32), ep0 + 1u + (uint32_t)k, active,
                           reinterpret_cast<uint32_t*>(&tile[0][0]) + role * kWave);   // the observation tiles are idle before the loop
   }
 
@@ -588,7 +592,12 @@ __global__ __launch_bounds__(kWsBlock, 4) void s2d_reach_rollout_ws_kernel(S2DHo
         if (MODE == S2D_MODE_TURN4) act[b][WA_CMD][lane] = __int_as_float(cmd);
         act[b][WA_POWER][lane] = c.power;
         act[b][WA_DIR][lane] = c.dir; act[b][WA_RATE][lane] = c.dir_rate;
-        if constexpr (NOISE) {                             // the state-independent half of this cycle's noise; the sine / cosine of
+        if constexpr (NK == S2D_NK_SQUARE) {              // rcssserver's square: one block per cycle, the six words as NoiseIn carries them
+          const NoiseIn nz = noise_prepare_square(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
+          act[b][WA_NPM][lane] = nz.pm; act[b][WA_NPS][lane] = nz.ps; act[b][WA_NPC][lane] = nz.pc;
+          act[b][WA_NBM][lane] = nz.bm; act[b][WA_NBS][lane] = nz.bs; act[b][WA_NBC][lane] = nz.bc;
+          if (MODE == S2D_MODE_TURN4) act[b][WA_NTU][lane] = nz.tu;
+        } else if constexpr (NOISE) {                      // the state-independent half of this cycle's noise; the sine / cosine of
           // the whole-degree directions are entries of the table the simulating wave built before the first barrier
           const NoiseWords nw = noise_words(p, gl, gh, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN, nblk, t == 0 || (k & 1u) == 0u);
           const float2 ps = sc_lut[noise_dir_index(nw.wp)], bs = sc_lut[noise_dir_index(nw.wb)];
@@ -645,7 +654,7 @@ __global__ __launch_bounds__(kWsBlock, 4) void s2d_reach_rollout_ws_kernel(S2DHo
       if (fast)
         for (int k = lane; k < tab_len; k += kWave) ep_lds[k] = tb->ep[k];
     }
-    if (fast || NOISE) {                                   // (sin, cos) of the whole degrees: dash directions and noise directions
+    if (fast || NK == S2D_NK_LATTICE) {                    // (sin, cos) of the whole degrees: dash directions and noise directions
       for (int k = lane; k <= 360; k += kWave) {
         float sn, cs;
         sincos_deg((float)(k - 180), sn, cs);
@@ -711,7 +720,7 @@ __global__ __launch_bounds__(kWsBlock, 4) void s2d_reach_rollout_ws_kernel(S2DHo
           snap[b][WS_FLAGS][lane] = __int_as_float(flags | (j << 8));   // bits 8..: the slot holding the next episode
           if (took) {                                      // rare: the prepared episode is a copy
             if (nth >= kSlots)                             // more than kSlots episodes ended in this launch: prepare inline
-              slot_fill<NOISE>(p, rp, slots[j], lane, gl, gh, (uint32_t)e.episode + 1u);
+              slot_fill<NK>(p, rp, slots[j], lane, gl, gh, (uint32_t)e.episode + 1u);
             episode_begin(e, slot_take<kWave>(slots[j], lane, rst));
             nth += 1; j = (j + 1 == kSlots) ? 0 : j + 1;
           }
@@ -952,6 +961,15 @@ __global__ void s2d_debug_eval_kernel(int op, const float* __restrict__ in, floa
       q[0] = nz.pm; q[1] = nz.ps; q[2] = nz.pc; q[3] = nz.bm; q[4] = nz.bs; q[5] = nz.bc;
       break;
     }
+    case 11:                                             // rcssserver's square noise (s2d_device.h: noise_prepare_square), commanded cycle
+    case 12: {                                           // the same on the command-less cycle of a reset (stream NOISE_RESET)
+      const uint32_t* u = reinterpret_cast<const uint32_t*>(in) + 4 * i;   // gid_lo, gid_hi, counter, seed_lo (seed_hi = 0)
+      S2DHot p{}; p.seed_lo = u[3]; p.seed_hi = 0u;
+      const NoiseIn nz = noise_prepare_square(p, u[0], u[1], u[2], op == 11 ? S2D_ST_NOISE : S2D_ST_NOISE_RESET, false);
+      float* q = out + 4 * i;
+      q[0] = nz.pc; q[1] = nz.ps; q[2] = nz.bc; q[3] = nz.bs;   // c_px, c_py, c_bx, c_by
+      break;
+    }
     case 0: { float s, c; sincos_deg(in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break; }
     case 1: out[i] = atan2_deg(in[2 * i], in[2 * i + 1]); break;
     case 2: out[i] = exp_spec(in[i]); break;
@@ -1025,6 +1043,7 @@ struct S2DEngine {
   const S2DRare* rare_dev;
   int mode;      // S2D_MODE_*
   bool noise;
+  int nk;        // noise kind of the kernels: S2D_NK_OFF, S2D_NK_LATTICE or S2D_NK_SQUARE (s2d_device.h)
   int rollout_ws;  // -1 auto (by batch size), 0 unified kernel, 1 wave-specialised kernel
   int rollout_e;   // envs per lane of the wave-specialised rollout: 2 (s2d_rollout2.hip, where the batch and the record allow it) or 1
   int rollout_nt;  // -1 by record size, 0 / 1: plain / non-temporal record stores (experiments)
@@ -1118,6 +1137,10 @@ S2D_API int s2d_validate_config(const S2DConfig* c) {
   if (t.max_steps < 0) return fail(S2D_EINVAL, "max_steps must be >= 0");
   if (!(t.reset_ball_decay > 0 && t.reset_ball_decay < 1)) return fail(S2D_EINVAL, "reset_ball_decay must be in (0,1)");
   if (c->env_id_offset < 0) return fail(S2D_EINVAL, "env_id_offset must be >= 0");
+  if (c->noise_model != S2D_NOISE_LATTICE && c->noise_model != S2D_NOISE_RCSSSERVER)
+    return fail(S2D_EINVAL, "noise_model must be S2D_NOISE_LATTICE (0) or S2D_NOISE_RCSSSERVER (1)");
+  if (c->noise_model == S2D_NOISE_RCSSSERVER && !c->noise)
+    return fail(S2D_EINVAL, "noise_model = S2D_NOISE_RCSSSERVER needs noise = 1 (with noise = 0 there is no noise to shape)");
   return S2D_OK;
 }
 
@@ -1218,6 +1241,7 @@ S2D_API int s2d_create(const S2DConfig* cfg, int64_t n_envs, int device, void* a
   h->mode = !cfg->task.use_continuous_action ? S2D_MODE_DISCRETE
                                              : (cfg->task.use_turning ? S2D_MODE_TURN4 : S2D_MODE_CONT1);
   h->noise = cfg->noise != 0;
+  h->nk = !h->noise ? S2D_NK_OFF : (cfg->noise_model == S2D_NOISE_RCSSSERVER ? S2D_NK_SQUARE : S2D_NK_LATTICE);
   h->rollout_ws = -1;
   if (const char* v = std::getenv("S2D_ROLLOUT_WS")) h->rollout_ws = std::atoi(v) != 0 ? 1 : 0;
   // envs per lane of the wave-specialised rollout: 1 (default).  2 = s2d_rollout2.hip: bit-identical, whole-line record stores,
@@ -1336,7 +1360,10 @@ static int check_action_kind(const S2DEngine* h, const void* actions, int kind) 
 S2D_API int s2d_reset(S2DHandle h, const uint8_t* mask_dev, void* stream) {
   if (!h) return fail(S2D_EINVAL, "NULL handle");
   DeviceGuard guard(h->device);
-  auto k = h->noise ? s2d_reach_reset_kernel<true> : s2d_reach_reset_kernel<false>;
+  using ResetK = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, const uint8_t*, StepOut);
+  static const ResetK table[3] = {s2d_reach_reset_kernel<S2D_NK_OFF>, s2d_reach_reset_kernel<S2D_NK_LATTICE>,
+                                  s2d_reach_reset_kernel<S2D_NK_SQUARE>};
+  const ResetK k = table[h->nk];
   hipLaunchKernelGGL(k, dim3(grid_for(h->n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->hot,
                      h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n, mask_dev, h->out);
   HIP_TRY(hipGetLastError());
@@ -1350,13 +1377,16 @@ S2D_API int s2d_step(S2DHandle h, const void* actions_dev, int action_kind, void
   if (rc != S2D_OK) return rc;
   DeviceGuard guard(h->device);
   using StepK = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, const void*, int, StepOut, int);
-  static const StepK table[3][2] = {
-      {s2d_reach_step_kernel<S2D_MODE_DISCRETE, false>, s2d_reach_step_kernel<S2D_MODE_DISCRETE, true>},
-      {s2d_reach_step_kernel<S2D_MODE_CONT1, false>, s2d_reach_step_kernel<S2D_MODE_CONT1, true>},
-      {s2d_reach_step_kernel<S2D_MODE_TURN4, false>, s2d_reach_step_kernel<S2D_MODE_TURN4, true>}};
+  static const StepK table[3][3] = {
+      {s2d_reach_step_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF>, s2d_reach_step_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE>,
+       s2d_reach_step_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE>},
+      {s2d_reach_step_kernel<S2D_MODE_CONT1, S2D_NK_OFF>, s2d_reach_step_kernel<S2D_MODE_CONT1, S2D_NK_LATTICE>,
+       s2d_reach_step_kernel<S2D_MODE_CONT1, S2D_NK_SQUARE>},
+      {s2d_reach_step_kernel<S2D_MODE_TURN4, S2D_NK_OFF>, s2d_reach_step_kernel<S2D_MODE_TURN4, S2D_NK_LATTICE>,
+       s2d_reach_step_kernel<S2D_MODE_TURN4, S2D_NK_SQUARE>}};
   // main workgroups + (with auto-reset) as many refill workgroups: they keep the prepared episodes of StepOut::prep topped up
   const int main_blocks = grid_for(h->n), refill_blocks = h->cfg.auto_reset ? main_blocks : 0;
-  hipLaunchKernelGGL(table[h->mode][h->noise ? 1 : 0], dim3(main_blocks + refill_blocks), dim3(kBlock), 0,
+  hipLaunchKernelGGL(table[h->mode][h->nk], dim3(main_blocks + refill_blocks), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), h->hot, h->rare_dev,
                      reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n, actions_dev, action_kind, h->out,
                      refill_blocks);
@@ -1380,12 +1410,15 @@ S2D_API int s2d_step_k(S2DHandle h, int k, const void* actions_dev, int action_k
   }
   DeviceGuard guard(h->device);
   using StepK = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, const void*, int, RolloutOut, StepOut, int);
-  static const StepK table[3][2] = {
-      {s2d_reach_step_k_kernel<S2D_MODE_DISCRETE, false>, s2d_reach_step_k_kernel<S2D_MODE_DISCRETE, true>},
-      {s2d_reach_step_k_kernel<S2D_MODE_CONT1, false>, s2d_reach_step_k_kernel<S2D_MODE_CONT1, true>},
-      {s2d_reach_step_k_kernel<S2D_MODE_TURN4, false>, s2d_reach_step_k_kernel<S2D_MODE_TURN4, true>}};
+  static const StepK table[3][3] = {
+      {s2d_reach_step_k_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF>, s2d_reach_step_k_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE>,
+       s2d_reach_step_k_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE>},
+      {s2d_reach_step_k_kernel<S2D_MODE_CONT1, S2D_NK_OFF>, s2d_reach_step_k_kernel<S2D_MODE_CONT1, S2D_NK_LATTICE>,
+       s2d_reach_step_k_kernel<S2D_MODE_CONT1, S2D_NK_SQUARE>},
+      {s2d_reach_step_k_kernel<S2D_MODE_TURN4, S2D_NK_OFF>, s2d_reach_step_k_kernel<S2D_MODE_TURN4, S2D_NK_LATTICE>,
+       s2d_reach_step_k_kernel<S2D_MODE_TURN4, S2D_NK_SQUARE>}};
   const int main_blocks = grid_for(h->n), refill_blocks = h->cfg.auto_reset ? main_blocks : 0;
-  hipLaunchKernelGGL(table[h->mode][h->noise ? 1 : 0], dim3(main_blocks + refill_blocks), dim3(kBlock), 0,
+  hipLaunchKernelGGL(table[h->mode][h->nk], dim3(main_blocks + refill_blocks), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
                      k, actions_dev, action_kind, ro, h->out, refill_blocks);
   HIP_TRY(hipGetLastError());
@@ -1413,29 +1446,36 @@ S2D_API int s2d_rollout(S2DHandle h, int n_steps, const void* actions_dev, int a
   }
   DeviceGuard guard(h->device);
   using RollK = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, const void*, int, RolloutOut, StepOut);
-  static const RollK table[3][2] = {
-      {s2d_reach_rollout_kernel<S2D_MODE_DISCRETE, false>, s2d_reach_rollout_kernel<S2D_MODE_DISCRETE, true>},
-      {s2d_reach_rollout_kernel<S2D_MODE_CONT1, false>, s2d_reach_rollout_kernel<S2D_MODE_CONT1, true>},
-      {s2d_reach_rollout_kernel<S2D_MODE_TURN4, false>, s2d_reach_rollout_kernel<S2D_MODE_TURN4, true>}};
-  static const RollK table_ws[3][2] = {
-      {s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, false>, s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, true>},
-      {s2d_reach_rollout_ws_kernel<S2D_MODE_CONT1, false>, s2d_reach_rollout_ws_kernel<S2D_MODE_CONT1, true>},
-      {s2d_reach_rollout_ws_kernel<S2D_MODE_TURN4, false>, s2d_reach_rollout_ws_kernel<S2D_MODE_TURN4, true>}};
+  static const RollK table[3][3] = {
+      {s2d_reach_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF>, s2d_reach_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE>,
+       s2d_reach_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE>},
+      {s2d_reach_rollout_kernel<S2D_MODE_CONT1, S2D_NK_OFF>, s2d_reach_rollout_kernel<S2D_MODE_CONT1, S2D_NK_LATTICE>,
+       s2d_reach_rollout_kernel<S2D_MODE_CONT1, S2D_NK_SQUARE>},
+      {s2d_reach_rollout_kernel<S2D_MODE_TURN4, S2D_NK_OFF>, s2d_reach_rollout_kernel<S2D_MODE_TURN4, S2D_NK_LATTICE>,
+       s2d_reach_rollout_kernel<S2D_MODE_TURN4, S2D_NK_SQUARE>}};
+  static const RollK table_ws[3][3] = {
+      {s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF>, s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE>,
+       s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE>},
+      {s2d_reach_rollout_ws_kernel<S2D_MODE_CONT1, S2D_NK_OFF>, s2d_reach_rollout_ws_kernel<S2D_MODE_CONT1, S2D_NK_LATTICE>,
+       s2d_reach_rollout_ws_kernel<S2D_MODE_CONT1, S2D_NK_SQUARE>},
+      {s2d_reach_rollout_ws_kernel<S2D_MODE_TURN4, S2D_NK_OFF>, s2d_reach_rollout_ws_kernel<S2D_MODE_TURN4, S2D_NK_LATTICE>,
+       s2d_reach_rollout_ws_kernel<S2D_MODE_TURN4, S2D_NK_SQUARE>}};
   // small batches: four waves per env group (policy | simulate | agent | ball)
   const bool ws = h->rollout_ws < 0 ? (h->n <= kWsMaxEnvs) : (h->rollout_ws != 0);
   static const char* const mode_names[3] = {"discrete", "continuous", "turning"};
   if (ws) {
     // two envs per lane (s2d_rollout2.hip) where the batch is a multiple of 128 envs and the record is complete and aligned
-    if (h->rollout_e == 2 && s2d_internal_rollout2(h->mode, h->noise ? 1 : 0, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
+    // (it has no rcssserver noise model: with that one the four-wave kernel runs, and kernel_name says so)
+    if (h->rollout_e == 2 && h->nk != S2D_NK_SQUARE && s2d_internal_rollout2(h->mode, h->noise ? 1 : 0, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
                                                    h->stride, h->n, n_steps, actions_dev, action_kind, &ro, &h->out, stream, h->kernel_name)) {
       HIP_TRY(hipGetLastError());
       h->last_kernel = h->kernel_name;
       return S2D_OK;
     }
-    RollK kern_ws = table_ws[h->mode][h->noise ? 1 : 0];
+    RollK kern_ws = table_ws[h->mode][h->nk];
     int rec = 0;
     if (h->mode == S2D_MODE_DISCRETE && !h->noise && ro.obs && ro.action && ro.reward && ro.done && ro.result) {
-      kern_ws = ro.nt ? s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, false, 2> : s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, false, 1>;
+      kern_ws = ro.nt ? s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, 2> : s2d_reach_rollout_ws_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, 1>;
       rec = ro.nt ? 2 : 1;
     }
     hipLaunchKernelGGL(kern_ws, dim3((unsigned)((h->n + kWave - 1) / kWave)),
@@ -1444,16 +1484,16 @@ S2D_API int s2d_rollout(S2DHandle h, int n_steps, const void* actions_dev, int a
                        ro, h->out);
     HIP_TRY(hipGetLastError());
     std::snprintf(h->kernel_name, sizeof h->kernel_name, "s2d_reach_rollout_ws_kernel<%s,noise=%d,rec=%d,nt=%d>", mode_names[h->mode],
-                  h->noise ? 1 : 0, rec, ro.nt ? 1 : 0);
+                  h->nk, rec, ro.nt ? 1 : 0);
     h->last_kernel = h->kernel_name;
     return S2D_OK;
   }
-  hipLaunchKernelGGL(table[h->mode][h->noise ? 1 : 0], dim3(grid_for(h->n)), dim3(kBlock), 0,
+  hipLaunchKernelGGL(table[h->mode][h->nk], dim3(grid_for(h->n)), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), h->hot, h->rare_dev,
                      reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n, n_steps, actions_dev, action_kind,
                      ro, h->out);
   HIP_TRY(hipGetLastError());
-  std::snprintf(h->kernel_name, sizeof h->kernel_name, "s2d_reach_rollout_kernel<%s,noise=%d>", mode_names[h->mode], h->noise ? 1 : 0);
+  std::snprintf(h->kernel_name, sizeof h->kernel_name, "s2d_reach_rollout_kernel<%s,noise=%d>", mode_names[h->mode], h->nk);
   h->last_kernel = h->kernel_name;
   return S2D_OK;
 }
@@ -1504,7 +1544,7 @@ S2D_API int s2d_set_seed(S2DHandle h, uint64_t seed, void* stream) {
 }
 
 S2D_API int s2d_debug_eval(int op, const void* in_dev, void* out_dev, int64_t n, void* stream) {
-  if (!in_dev || !out_dev || n <= 0 || op < 0 || op > 10 || (op == 9 && n % 256 != 0)) return fail(S2D_EINVAL, "bad s2d_debug_eval argument");
+  if (!in_dev || !out_dev || n <= 0 || op < 0 || op > 12 || (op == 9 && n % 256 != 0)) return fail(S2D_EINVAL, "bad s2d_debug_eval argument");
   hipLaunchKernelGGL(s2d_debug_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), op, static_cast<const float*>(in_dev),
                      static_cast<float*>(out_dev), n);

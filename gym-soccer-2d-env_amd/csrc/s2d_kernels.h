@@ -229,11 +229,11 @@ struct PrepTile { float v[13 + S2D_OBS_DIM + 2][kWave]; };   // NextEpisode + Fi
 #endif
 static constexpr int kRefillMin = S2D_REFILL_MIN;
 
-template <bool NOISE>
+template <int NK>
 S2D_DEV void prep_fill(const S2DHot& p, const S2DRare* __restrict__ rp, PrepTile& t, int lane, const Env& e,
                        uint32_t gid_lo, uint32_t gid_hi) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare<NOISE>(p, rp, r, gid_lo, gid_hi, reset_key(e));
+  const NextEpisode q = episode_prepare<NK>(p, rp, r, gid_lo, gid_hi, reset_key(e));
   t.v[0][lane] = q.px; t.v[1][lane] = q.py; t.v[2][lane] = q.vx; t.v[3][lane] = q.vy; t.v[4][lane] = q.body;
   t.v[5][lane] = q.stamina; t.v[6][lane] = q.effort; t.v[7][lane] = q.recovery; t.v[8][lane] = q.capacity;
   t.v[9][lane] = q.bx; t.v[10][lane] = q.by; t.v[11][lane] = q.bvx; t.v[12][lane] = q.bvy;
@@ -244,11 +244,11 @@ S2D_DEV void prep_fill(const S2DHot& p, const S2DRare* __restrict__ rp, PrepTile
 }
 // the same by the whole wave together (reset_sample_coop; wave-uniform call, `need` = this lane's tile entry is to be drawn;
 // `scratch` = 64 wave-private LDS words)
-template <bool NOISE>
+template <int NK>
 S2D_DEV void prep_fill_coop(const S2DHot& p, const S2DRare* __restrict__ rp, PrepTile& t, int lane, uint32_t key,
                             uint32_t gid_lo, uint32_t gid_hi, bool need, uint32_t* scratch) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare_coop<NOISE>(p, rp, r, gid_lo, gid_hi, key, need, lane, scratch);
+  const NextEpisode q = episode_prepare_coop<NK>(p, rp, r, gid_lo, gid_hi, key, need, lane, scratch);
   const FirstObs f = first_obs(p, q);
   if (need) {
     t.v[0][lane] = q.px; t.v[1][lane] = q.py; t.v[2][lane] = q.vx; t.v[3][lane] = q.vy; t.v[4][lane] = q.body;
@@ -273,13 +273,14 @@ S2D_DEV const S2DTables* tables_of(const S2DRare* rp) {
 // prep == nullptr: the reset sample is drawn on the spot (per-step API).
 // FAST: the dash-only fast path (s2d_device.h, S2DTables): ep_lds = effort * power by step number, sc_lut = (sin, cos) of the
 // whole degrees -180 .. 180; the caller has checked that the env sits on the table.
-template <bool NOISE, bool FAST = false>
+template <int NK, bool FAST = false>
 S2D_DEV void step_env(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, uint32_t gid_lo, uint32_t gid_hi,
                       uint32_t k, int cmd, const CmdPrep& c, ObsOut& ob, float& reward, int& done, int& result,
                       float* __restrict__ terminal_row, PrepTile* prep, int lane, bool& have_prep,
                       const float* ep_lds = nullptr, const float2* sc_lut = nullptr) {
+  constexpr bool NOISE = NK != S2D_NK_OFF;
   NoiseIn nz{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if (NOISE) nz = noise_prepare(p, gid_lo, gid_hi, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
+  if constexpr (NOISE) nz = noise_prepare_kind<NK>(p, gid_lo, gid_hi, k, S2D_ST_NOISE, cmd == S2D_CMD_TURN);
   float d2;
   if constexpr (FAST) {
     const float ep = ep_lds[e.step_number];
@@ -295,7 +296,7 @@ S2D_DEV void step_env(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, u
 #pragma unroll
     for (int k = 0; k < S2D_OBS_DIM; ++k) terminal_row[k] = ob.o[k];
     if (prep) {
-      if (!have_prep) prep_fill<NOISE>(p, rp, *prep, lane, e, gid_lo, gid_hi);   // episode shorter than the refill cadence
+      if (!have_prep) prep_fill<NK>(p, rp, *prep, lane, e, gid_lo, gid_hi);   // episode shorter than the refill cadence
       have_prep = false;
       episode_begin(e, prep_take_episode(*prep, lane));    // state, first observation and carry were prepared together
 #pragma unroll
@@ -303,7 +304,7 @@ S2D_DEV void step_env(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, u
       e.prev_dist = prep->v[13 + S2D_OBS_DIM][lane]; e.prev_angle = prep->v[14 + S2D_OBS_DIM][lane];
       return;
     } else {
-      d2 = env_reset<NOISE>(p, rp, e, gid_lo, gid_hi);
+      d2 = env_reset<NK>(p, rp, e, gid_lo, gid_hi);
     }
     int dn2, r2; float w2;
     observe_and_check(p, e, d2, ob, dn2, w2, r2);        // reach_ball_env.py:166: carry seeded, outputs dropped
@@ -311,11 +312,11 @@ S2D_DEV void step_env(const S2DHot& p, const S2DRare* __restrict__ rp, Env& e, u
 }
 
 // prepare episode `episode` of the env and store it in its persistent slot (episode & 1), tag last
-template <bool NOISE>
+template <int NK>
 S2D_DEV void prep_store(const S2DHot& p, const S2DRare* __restrict__ rp, float* __restrict__ prep, int64_t stride, int64_t i,
                         uint32_t gl, uint32_t gh, uint32_t episode) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare<NOISE>(p, rp, r, gl, gh, episode);
+  const NextEpisode q = episode_prepare<NK>(p, rp, r, gl, gh, episode);
   float* d = prep + (int64_t)(episode & 1u) * PS_WORDS * stride + i;
   const float w[PS_WORDS] = {q.px, q.py, q.body, q.bx, q.by, q.bvx, q.bvy};
 #pragma unroll
@@ -323,11 +324,11 @@ S2D_DEV void prep_store(const S2DHot& p, const S2DRare* __restrict__ rp, float* 
   prep_tags(prep, stride)[(int64_t)(episode & 1u) * stride + i] = prep_tag_of(episode, q);
 }
 // the refill workgroups' form: the whole wave draws together (reset_sample_coop; `need` = this lane's slot is to be drawn)
-template <bool NOISE>
+template <int NK>
 S2D_DEV void prep_store_coop(const S2DHot& p, const S2DRare* __restrict__ rp, float* __restrict__ prep, int64_t stride, int64_t i,
                              uint32_t gl, uint32_t gh, uint32_t episode, bool need, int lane, uint32_t* scratch) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare_coop<NOISE>(p, rp, r, gl, gh, episode, need, lane, scratch);
+  const NextEpisode q = episode_prepare_coop<NK>(p, rp, r, gl, gh, episode, need, lane, scratch);
   if (need) {
     float* d = prep + (int64_t)(episode & 1u) * PS_WORDS * stride + i;
     const float w[PS_WORDS] = {q.px, q.py, q.body, q.bx, q.by, q.bvx, q.bvy};
@@ -388,19 +389,19 @@ S2D_DEV NextEpisode slot_take(const float (*slot)[W], int col, const ResetStamin
                      slot[SL_BX][col], slot[SL_BX + 1][col], slot[SL_BX + 2][col], slot[SL_BX + 3][col]};
 }
 // one prepared episode of this lane's env -> LDS slot
-template <bool NOISE>
+template <int NK>
 S2D_DEV void slot_fill(const S2DHot& p, const S2DRare* __restrict__ rp, float (*slot)[kWave], int lane, uint32_t gl,
                        uint32_t gh, uint32_t episode) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare<NOISE>(p, rp, r, gl, gh, episode);
+  const NextEpisode q = episode_prepare<NK>(p, rp, r, gl, gh, episode);
   slot_put<kWave>(slot, lane, q, first_obs(p, q));
 }
 // the prologue's form: the whole wave draws together (reset_sample_coop; `need` = this lane has an env)
-template <bool NOISE>
+template <int NK>
 S2D_DEV void slot_fill_coop(const S2DHot& p, const S2DRare* __restrict__ rp, float (*slot)[kWave], int lane, uint32_t gl,
                             uint32_t gh, uint32_t episode, bool need, uint32_t* scratch) {
   const S2DRare r = *rp;
-  const NextEpisode q = episode_prepare_coop<NOISE>(p, rp, r, gl, gh, episode, need, lane, scratch);
+  const NextEpisode q = episode_prepare_coop<NK>(p, rp, r, gl, gh, episode, need, lane, scratch);
   const FirstObs f = first_obs(p, q);
   if (need) slot_put<kWave>(slot, lane, q, f);
 }

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kWsBlock) void s2d_reach_rollout_ws2_kernel(S2DHot 
 #pragma unroll
     for (int e = 0; e < kE; ++e) {
       const uint64_t gid = gid0 + (uint64_t)e;
-      const NextEpisode q = episode_prepare_coop<NOISE>(p_sgpr, rp, r, (uint32_t)gid, (uint32_t)(gid >> 32),
+      const NextEpisode q = episode_prepare_coop<NOISE ? S2D_NK_LATTICE : S2D_NK_OFF>(p_sgpr, rp, r, (uint32_t)gid, (uint32_t)(gid >> 32),
                                                         (e ? ep0.y : ep0.x) + 1u + (uint32_t)k, true, lane, scratch);
       slot_put<kGroup>(slots[k], col + e, q, first_obs(p_sgpr, q));
     }
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kWsBlock) void s2d_reach_rollout_ws2_kernel(S2DHot 
             if (fl[q] && p.auto_reset) {                   // rare: the prepared episode is a copy
               if (nth[q] >= kSlots) {                      // more than kSlots episodes ended in this launch: prepare inline
                 const S2DRare r = *rp;
-                const NextEpisode ne = episode_prepare<NOISE>(p, rp, r, gl[q], gh[q], (uint32_t)e[q].episode + 1u);
+                const NextEpisode ne = episode_prepare<NOISE ? S2D_NK_LATTICE : S2D_NK_OFF>(p, rp, r, gl[q], gh[q], (uint32_t)e[q].episode + 1u);
                 slot_put<kGroup>(slots[j[q]], col + q, ne, first_obs(p, ne));
               }
               episode_begin(e[q], slot_take<kGroup>(slots[j[q]], col + q, rst));

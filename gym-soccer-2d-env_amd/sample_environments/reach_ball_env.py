@@ -11,7 +11,7 @@ from soccer2d_amd.vec_env import Soccer2DVecEnv
 
 class ReachBallEnv(Soccer2DEnv):
     def __init__(self, render_mode=None, logger=None, log_dir=None, **kwargs):
-        unknown = [k for k in kwargs if k not in TASK_KWARGS and k not in ('device', 'seed', 'noise', 'server_params')]
+        unknown = [k for k in kwargs if k not in TASK_KWARGS and k not in ('device', 'seed', 'noise', 'noise_model', 'server_params')]
         # the reference silently ignores unknown kwargs (kwargs.get with defaults); keep that
         for k in unknown:
             kwargs.pop(k)

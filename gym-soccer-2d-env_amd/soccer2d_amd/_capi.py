@@ -23,6 +23,8 @@ RESULT_NONE, RESULT_GOAL, RESULT_OUT, RESULT_TIMEOUT = 0, 1, 2, 3
 RESULT_NAMES = (None, 'Goal', 'Out', 'Timeout')   # info['result'], reach_ball_env.py:126-150
 CMD_NONE, CMD_DASH, CMD_TURN, CMD_FREEZE = 0, 1, 2, -1
 ACT_DISCRETE_I32, ACT_DISCRETE_I64, ACT_CONTINUOUS, ACT_TURNING, ACT_RANDOM, ACT_COMMAND = 0, 1, 2, 3, 4, 5
+NOISE_LATTICE, NOISE_RCSSSERVER = 0, 1
+NOISE_MODELS = {'lattice': NOISE_LATTICE, 'rcssserver': NOISE_RCSSSERVER}   # S2DConfig.noise_model by name
 
 
 class S2DLibraryError(RuntimeError):
@@ -60,7 +62,7 @@ class S2DConfig(C.Structure):
         ('abi_version', C.c_uint32), ('struct_bytes', C.c_uint32),
         ('sp', S2DServerParams), ('task', S2DReachBallParams),
         ('seed', C.c_uint64), ('env_id_offset', C.c_int64),
-        ('auto_reset', C.c_int32), ('noise', C.c_int32), ('reserved', C.c_int32 * 4)]
+        ('auto_reset', C.c_int32), ('noise', C.c_int32), ('noise_model', C.c_int32), ('reserved', C.c_int32 * 3)]
 
 
 _F = C.POINTER(C.c_float)

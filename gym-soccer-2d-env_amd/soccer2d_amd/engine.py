@@ -21,11 +21,16 @@ TASK_KWARGS = dict(change_ball_position=True, change_ball_velocity=False, ball_p
                    use_continuous_action=True, action_space_size=16, use_turning=False)
 
 
-def make_config(seed=0x5EED, env_id_offset=0, auto_reset=True, noise=True, server_params=None, **kwargs):
+def make_config(seed=0x5EED, env_id_offset=0, auto_reset=True, noise=True, server_params=None, noise_model='lattice', **kwargs):
     """S2DConfig from ReachBallEnv-style kwargs (+ optional ServerParam overrides by
     idl/service.proto field name).  Unknown names raise ValueError.  noise=True (player_rand / ball_rand on) is the
     default because the reference's rcssserver runs with its stock noise (soccer_2d_env.py:363-368); noise=False is the
-    explicit opt-in for deterministic dynamics."""
+    explicit opt-in for deterministic dynamics.  noise_model picks the form of the velocity noise: 'lattice' (default,
+    DESIGN.md section 5) or 'rcssserver' (MPObject::noise()'s uniform square; needs noise=True)."""
+    if not isinstance(noise_model, str) or noise_model not in _capi.NOISE_MODELS:
+        raise ValueError(f"noise_model must be one of {sorted(_capi.NOISE_MODELS)}, got {noise_model!r}")
+    if noise_model != 'lattice' and not noise:
+        raise ValueError(f"noise_model={noise_model!r} needs noise=True")
     lib = _capi.load_library()
     cfg = _capi.S2DConfig()
     lib.s2d_default_config(C.byref(cfg))
@@ -41,6 +46,7 @@ def make_config(seed=0x5EED, env_id_offset=0, auto_reset=True, noise=True, serve
     cfg.env_id_offset = int(env_id_offset)
     cfg.auto_reset = int(bool(auto_reset))
     cfg.noise = int(bool(noise))
+    cfg.noise_model = _capi.NOISE_MODELS[noise_model]
     _capi.check(lib, lib.s2d_validate_config(C.byref(cfg)), 's2d_validate_config')
     return cfg
 

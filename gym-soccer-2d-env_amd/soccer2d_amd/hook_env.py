@@ -52,14 +52,14 @@ def command_of(action):
 class HookRuntime:
     """1..64 hook-based env instances on one engine."""
 
-    def __init__(self, envs, device='cuda:0', seed=0x5EED, noise=True, server_params=None):
+    def __init__(self, envs, device='cuda:0', seed=0x5EED, noise=True, server_params=None, noise_model='lattice'):
         self.envs = list(envs)
         n = len(self.envs)
         if not 1 <= n <= MAX_HOOK_ENVS:
             raise ValueError(f"the hook path runs 1..{MAX_HOOK_ENVS} envs, got {n}")
         # the engine's own task logic is not used: no auto-reset, no episode end of its own making
-        cfg = make_config(seed=seed, auto_reset=False, noise=noise, server_params=server_params, use_continuous_action=False,
-                          action_space_size=16, max_steps=2000000000, min_distance_to_ball=0.0)
+        cfg = make_config(seed=seed, auto_reset=False, noise=noise, server_params=server_params, noise_model=noise_model,
+                          use_continuous_action=False, action_space_size=16, max_steps=2000000000, min_distance_to_ball=0.0)
         self.engine = Engine(n, device, cfg=cfg)
         # Connect state of every instance = what s2d_create leaves behind (s2d_init_kernel): a player that has just joined -- full
         # stamina, effort / recovery / capacity at their initial values (rcssserver's state after a (recover)), at rest at the
@@ -143,7 +143,8 @@ class HookVecEnv:
     """N instances of a hook-based env class behind a list-style vector surface (``reset() -> [obs]``,
     ``step([a]) -> ([obs], [reward], [done], [info])``, auto-reset with ``info['terminal_observation']``)."""
 
-    def __init__(self, env_cls, num_envs, device='cuda:0', seed=0x5EED, noise=True, server_params=None, **kwargs):
+    def __init__(self, env_cls, num_envs, device='cuda:0', seed=0x5EED, noise=True, server_params=None, noise_model='lattice',
+                 **kwargs):
         if not 1 <= int(num_envs) <= MAX_HOOK_ENVS:
             raise ValueError(f"the hook path runs 1..{MAX_HOOK_ENVS} envs, got {num_envs}")
         import soccer_2d_env
@@ -154,7 +155,7 @@ class HookVecEnv:
             self.envs = [env_cls(**kwargs) for _ in range(int(num_envs))]
         finally:
             soccer_2d_env._defer_hook_runtime[0] = False
-        self.runtime = HookRuntime(self.envs, device, seed, noise, server_params)
+        self.runtime = HookRuntime(self.envs, device, seed, noise, server_params, noise_model)
         for i, e in enumerate(self.envs):
             e._hooks, e._hook_index = self.runtime, i
         self.num_envs = len(self.envs)

@@ -24,9 +24,9 @@ class Soccer2DVecEnv:
     metadata = {'render.modes': ['human']}
 
     def __init__(self, num_envs, device='cuda:0', seed=0x5EED, env_id_offset=0, auto_reset=True, noise=True,
-                 server_params=None, clone_outputs=False, **kwargs):
+                 server_params=None, clone_outputs=False, noise_model='lattice', **kwargs):
         cfg = make_config(seed=seed, env_id_offset=env_id_offset, auto_reset=auto_reset, noise=noise,
-                          server_params=server_params, **kwargs)
+                          server_params=server_params, noise_model=noise_model, **kwargs)
         self.engine = Engine(num_envs, device, cfg=cfg)
         self.num_envs = self.engine.num_envs
         self.device = self.engine.device

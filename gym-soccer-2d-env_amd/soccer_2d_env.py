@@ -44,7 +44,7 @@ class Soccer2DEnv(_Base):
 
     def __init__(self, render_mode=None, run_grpc_server=True, run_rcssserver=True, run_trainer_player=True,
                  logger=None, log_dir=None, device='cuda:0', seed=0x5EED, noise=True, server_params=None,
-                 **kwargs):
+                 noise_model='lattice', **kwargs):
         # run_* switches are accepted for signature compatibility; there is nothing to spawn.
         self.render_mode = render_mode
         self.log_dir = log_dir
@@ -58,13 +58,14 @@ class Soccer2DEnv(_Base):
                 raise TypeError(f"unexpected keyword arguments for a hook-based env: {sorted(kwargs)}")
             if not _defer_hook_runtime[0]:
                 from soccer2d_amd.hook_env import HookRuntime
-                self._hooks = HookRuntime([self], device=device, seed=seed, noise=noise, server_params=server_params)
+                self._hooks = HookRuntime([self], device=device, seed=seed, noise=noise, server_params=server_params,
+                                          noise_model=noise_model)
             return
         kw = dict(self.task_kwargs)
         kw.update(kwargs)
         # reference flow: the caller resets after done (dqn_stable_baselines3.py:52-56)
         self.vec = Soccer2DVecEnv(1, device=device, seed=seed, auto_reset=False, noise=noise,
-                                  server_params=server_params, **kw)
+                                  server_params=server_params, noise_model=noise_model, **kw)
         self.action_space = self.vec.action_space
         self.observation_space = self.vec.observation_space
 

@@ -74,6 +74,13 @@ enum {
                          * S2D_CMD_NONE */
 };
 
+/* velocity noise of MPObject::_inc (S2DConfig.noise_model) */
+enum {
+  S2D_NOISE_LATTICE = 0,    /* default: polar(U(0, m) on a 2^-16 grid, a whole degree), m = rand |v|; E|dv|^2 = m^2 / 3 */
+  S2D_NOISE_RCSSSERVER = 1  /* rcssserver's MPObject::noise(): (drand(-m, m), drand(-m, m)); E|dv|^2 = 2 m^2 / 3.  Needs
+                             * noise = 1.  The two-envs-per-lane rollout (S2D_ROLLOUT_E=2) does not have it and falls back. */
+};
+
 /* ---- configuration -------------------------------------------------------------------- */
 /* Physics parameters.  Field names follow ServerParam / PlayerType of idl/service.proto:
  * 1435-1732.  The reference never holds their VALUES (rcssserver sends them at run time,
@@ -119,7 +126,9 @@ typedef struct S2DConfig {
   int32_t auto_reset;     /* 1: a done env is reset inside the same step (SB3 VecEnv
                              convention); 0: caller resets (reference single-env flow)   */
   int32_t noise;          /* 0: player_rand/ball_rand ignored (parity mode); 1: Philox noise */
-  int32_t reserved[4];
+  int32_t noise_model;    /* S2D_NOISE_*: form of the velocity noise when noise = 1 (was reserved[0], which older
+                             callers zero: they get the lattice) */
+  int32_t reserved[3];
 } S2DConfig;
 
 /* ---- device buffers --------------------------------------------------------------------
@@ -254,7 +263,11 @@ int s2d_set_seed(S2DHandle h, uint64_t seed, void *stream);
 /* 9 reset_sample_coop against reset_sample (in = uint32[n][4], n a multiple of 256; out[n][14]);
  * 10 the movement-noise draw of one commanded cycle (one Philox word per object and cycle -- magnitude uniform
  *   k / 65536 from its high half, direction a WHOLE degree from its low half): in = uint32[n][4] = global env id lo, hi, policy step k,
- *   seed (low word) -> out[n][6] = player magnitude uniform, sin, cos; ball magnitude uniform, sin, cos. */
+ *   seed (low word) -> out[n][6] = player magnitude uniform, sin, cos; ball magnitude uniform, sin, cos.
+ * 11 the S2D_NOISE_RCSSSERVER draw of one commanded cycle (Philox block 2 of stream 3 at counter k; each word w ->
+ *   (w >> 8) * 2^-24 * 2 - 1, in [-1, 1)): in = uint32[n][4] = global env id lo, hi, counter k, seed (low word)
+ *   -> out[n][4] = player c_x, c_y, ball c_x, c_y (the velocity gains c * rand * |v| per axis);
+ * 12 the same for the command-less cycle of a reset (block 2 of stream 5, counter = the reset's episode key). */
 int s2d_debug_eval(int op, const void *in_dev, void *out_dev, int64_t n, void *stream);
 
 #ifdef __cplusplus
