@@ -132,6 +132,8 @@ struct MStock {
 // run-time test on an LDS word in front of the quick exit it cost the general kernel 4 %).  Same layout as MParams: no data members.
 struct MParamsNoIll : MParams { static constexpr int illegal_defense_number = 0; };
 static_assert(sizeof(MParamsNoIll) == sizeof(MParams), "MParamsNoIll adds no data");
+template <class B> struct MParamsCtl : B {};   // the general parameter block as the controller kernels read it (see the kernel)
+static_assert(sizeof(MParamsCtl<MParamsNoIll>) == sizeof(MParams), "MParamsCtl adds no data");
 // The same physics and rules with the SCHEDULE of the match -- how long things last, how many there are of them -- as per-engine
 // words: a learner's engine with short halves, no extra time or other waits differs from the stock configuration in these words
 // only and would otherwise run the general instantiation (1.79 G against 2.00 G, profiles/r04/match_schedule_words.txt).  They sit in
@@ -1085,18 +1087,25 @@ template <class P, class TY> S2D_DEV void match_cycle(const P& p, const TY& pt, 
 // (bits(d2) << 8 | index); d2 >= 0, so its bit pattern orders like the value and the key orders like (d2, index) -- the same
 // winner as a scan in index order.  Outputs only (nothing in the dynamics reads them): evaluated once per launch, after its
 // last cycle.
-S2D_DEV void match_nearest(const MObj& o, MGame& g, int l) {
-  const bool is_player = l < NP;
-  float bxn = hbcast(o.x, BALL), byn = hbcast(o.y, BALL);
-  float d2 = sq2(o.x - bxn, o.y - byn);
-  const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 8) | (unsigned long long)l;
-  unsigned long long kl = (is_player && l < 11) ? key : ~0ull;
-  unsigned long long kr = (is_player && l >= 11) ? key : ~0ull;
+// The key of one lane and the reduction, shared with the scripted controller's per-cycle team search (m_scripted_action).
+S2D_DEV unsigned long long nearest_key(float d2, int l) {
+  return ((unsigned long long)__float_as_uint(d2) << 8) | (unsigned long long)l;
+}
+S2D_DEV void half_min_keys(unsigned long long& kl, unsigned long long& kr) {   // all 64 lanes; min of each key over the half
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1) {
     unsigned long long ol = __shfl_xor(kl, off, kHalf), orr = __shfl_xor(kr, off, kHalf);
     kl = ol < kl ? ol : kl; kr = orr < kr ? orr : kr;
   }
+}
+S2D_DEV void match_nearest(const MObj& o, MGame& g, int l) {
+  const bool is_player = l < NP;
+  float bxn = hbcast(o.x, BALL), byn = hbcast(o.y, BALL);
+  float d2 = sq2(o.x - bxn, o.y - byn);
+  const unsigned long long key = nearest_key(d2, l);
+  unsigned long long kl = (is_player && l < 11) ? key : ~0ull;
+  unsigned long long kr = (is_player && l >= 11) ? key : ~0ull;
+  half_min_keys(kl, kr);
   g.nearest_l = (int)(kl & 0xFFull); g.nearest_r = (int)(kr & 0xFFull);
 }
 
@@ -1116,6 +1125,84 @@ template <class P> S2D_DEV void m_random_action(const P& p, uint32_t gl, uint32_
   const float ang = s * 180.0f;
   a = two ? u * 100.0f : ang;
   b = two ? ang : 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-slot controllers (S2D_CTL_*, include/s2d_match.h): the caller's row, the random policy above, or the scripted team below
+// ------------------------------------------------------------------------------------------
+struct MCtl {                          // kernel argument of the CTL instantiations
+  uint32_t random_mask, script_mask;   // bit i: slot i is random / scripted; neither: the caller's row (read for those slots only)
+  float* actions_out;                  // [T][N][22][3] each slot's (cmd, a, b) before the engine's gating, or NULL
+};
+// The scripted team's constants (documented with the rule table in include/s2d_match.h)
+constexpr float kTurnTol = S2D_SCRIPT_TURN_TOL, kArrive = S2D_SCRIPT_ARRIVE, kArrive2 = kArrive * kArrive;
+constexpr float kScriptDash = S2D_SCRIPT_DASH_POWER;
+constexpr float kGoalieX = S2D_SCRIPT_GOALIE_X, kGoalieYGain = S2D_SCRIPT_GOALIE_Y_GAIN, kGoalieYMax = S2D_SCRIPT_GOALIE_Y_MAX;
+constexpr float kHomeGainX = S2D_SCRIPT_HOME_GAIN_X, kHomeGainY = S2D_SCRIPT_HOME_GAIN_Y;
+S2D_DEV void turn_or_dash(float ang, int& cmd, float& a, float& b) {   // ang: the target's bearing relative to the body
+  const bool turn = fabsf(ang) > kTurnTol;
+  cmd = turn ? S2D_MCMD_TURN : S2D_MCMD_DASH;
+  a = turn ? ang : kScriptDash;
+  b = 0.0f;
+}
+// The scripted team (the project's own baseline; rules 1-8 of include/s2d_match.h, first match wins), from the start-of-cycle state
+// of the match.  Called by every lane of the wave in uniform control flow (ball broadcast, team search); lanes >= 22 get NONE.
+// Every distance is compared squared; -ffp-contract=off keeps the arithmetic what tests/scripted_policy_ref.c restates.
+template <class P, class TY>
+S2D_DEV void m_scripted_action(const P& p, const TY& pt, const MObj& o, const MGame& g, const MRare& r, int l, int half,
+                               int& cmd, float& a, float& b) {
+  const float bx = hbcast_c<BALL>(o.x, half), by = hbcast_c<BALL>(o.y, half);
+  const float d2 = sq2(bx - o.x, by - o.y);
+  // each team's chaser: its nearest non-goalie to the ball, ties to the lower index, sent-off players excluded
+  const bool field = l < NP && l != S2D_MATCH_GOALIE_LEFT && l != S2D_MATCH_GOALIE_RIGHT && o.card < S2D_CARD_RED;
+  unsigned long long kl = (field && l < 11) ? nearest_key(d2, l) : ~0ull;
+  unsigned long long kr = (field && l >= 11) ? nearest_key(d2, l) : ~0ull;
+  half_min_keys(kl, kr);
+  const int chaser = (int)((l < 11 ? kl : kr) & 0xFFull);
+  cmd = S2D_MCMD_NONE; a = 0.0f; b = 0.0f;
+  if (l >= NP) return;
+  const int mode = g.mode, side = side_of(l), mside = g.mode_side;
+  // 1. nothing to do: a halted or dead-ball mode (which takes in the shoot-out's modes other than Ready / Taken), tackling, sent off
+  if (is_halted(mode) || ball_dead(mode) || o.tackle > 0 || o.card >= S2D_CARD_RED) return;
+  const bool pen = is_penalty(mode);
+  const bool goalie = l == S2D_MATCH_GOALIE_LEFT || l == S2D_MATCH_GOALIE_RIGHT;
+  // 8. the shoot-out: the current taker, and in PenaltyTaken_ the defending goalie; nobody else
+  const bool taker = pen && l == (r.taker & 0xff) - 1;
+  const bool keeper = mode == S2D_GM_PENALTY_TAKEN && l == (mside == SIDE_LEFT ? S2D_MATCH_GOALIE_RIGHT : S2D_MATCH_GOALIE_LEFT);
+  if (pen && !taker && !keeper) return;
+  const float att = pen ? 1.0f : (side == SIDE_LEFT ? 1.0f : -1.0f);   // x sign of the goal he attacks (shoot-out: the right one)
+  const float def = pen ? 1.0f : -att;                                  // ... and of the one he defends
+  const float ang_ball = norm_deg_any(atan2_deg(by - o.y, bx - o.x) - o.body);
+  const float shot = norm_deg_any(atan2_deg(0.0f - o.y, att * p.half_l - o.x) - o.body);
+  // 2. a goalie holding a caught ball clears it
+  if (mode == S2D_GM_FREE_KICK && r.holder == l + 1) { cmd = S2D_MCMD_KICK; a = p.max_power; b = shot; return; }
+  // 3. goalie catch: the ball within reach and catch angle, inside his own penalty area, last played by the other side
+  if (goalie && (mode == S2D_GM_PLAY_ON || keeper) && o.catch_ban == 0 && g.last_touch == other_side(side)) {
+    const float cl = pt[PT_CATCH_LEN][l];
+    if (d2 <= cl * cl && ang_ball <= p.max_catch_angle && ang_ball >= p.min_catch_angle && fabsf(by) <= p.pen_half_w &&
+        def * bx >= p.pen_x) {
+      cmd = S2D_MCMD_CATCH; a = ang_ball; return;
+    }
+  }
+  // 4. kick a kickable ball at the goal; 5. the chaser goes to the ball -- in PlayOn and the team's own restarts (shoot-out: the taker)
+  const bool may_play = pen ? taker : (mode == S2D_GM_PLAY_ON || mside == side);
+  if (may_play && d2 <= pt[PT_KICKABLE_AREA2][l]) { cmd = S2D_MCMD_KICK; a = p.max_power; b = shot; return; }
+  if (may_play && (taker || chaser == l)) { turn_or_dash(ang_ball, cmd, a, b); return; }
+  // 6. the goalie guards his goal line; 7. everybody else keeps his formation place, shifted toward the ball
+  float tx, ty;
+  if (goalie) {
+    tx = def * kGoalieX; ty = clampf(by * kGoalieYGain, -kGoalieYMax, kGoalieYMax);
+  } else {
+    const int k = l % 11;
+    tx = clampf(att * kFormX[k] + kHomeGainX * bx, -p.half_l, p.half_l);
+    ty = clampf(kFormY[k] + kHomeGainY * by, -p.half_w, p.half_w);
+  }
+  const float dx = tx - o.x, dy = ty - o.y;
+  if (sq2(dx, dy) <= kArrive2) {                           // arrived: face the ball
+    if (fabsf(ang_ball) > kTurnTol) { cmd = S2D_MCMD_TURN; a = ang_ball; }
+    return;
+  }
+  turn_or_dash(norm_deg_any(atan2_deg(dy, dx) - o.body), cmd, a, b);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1195,9 +1282,11 @@ struct MRoll { float* obs; float* reward; int32_t* mode; uint8_t* done; };
 struct MShared {                                      // the workgroup's LDS (declared by the kernel)
   float4 (*pos_tile)[kTileSlots]; PTab* pt; unsigned int* lds_cnt; MRare* rare; float (*obs_tile)[2 * SLOTS * S2D_MATCH_OBJ_WORDS];
 };
-template <class P, class TY>
+// CTL: the slots' controllers come from `ctl` (per-slot: caller's row, random, scripted) and the record of what they chose is written
+// when ctl.actions_out is set; otherwise every slot takes the caller's row, or the random policy when actions == NULL.
+template <bool CTL, class P, class TY>
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
-                                const float* __restrict__ actions, const MRoll& ro) {
+                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl) {
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
@@ -1224,6 +1313,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   const int64_t eb = (int64_t)blockIdx.x * kEnvsPerBlock;  // the workgroup's first match
   char* obs_row = reinterpret_cast<char*>(ro.obs) + eb * (int64_t)(kVecPerMatch * 16);
   float* reward_row = ro.reward + eb; int32_t* mode_row = ro.mode + eb; uint8_t* done_row = ro.done + eb;
+  float* act_row = CTL ? ctl.actions_out + eb * (NP * 3) : nullptr;   // the action record: [T][N][22][3], same scheme
   const uint32_t lane = threadIdx.x & 63u, m_in_wg = threadIdx.x / kHalf;
   const uint32_t obs_off = ((threadIdx.x >> 6) * 2u * kVecPerMatch + lane) * 16u;
   const int64_t e0 = e - half;                             // first match of this wave (matches of a wave: e0, e0 + 1)
@@ -1252,7 +1342,28 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
     int l = l_launch, half = half_launch;
     asm volatile("" : "+v"(l), "+v"(half));
     int cmd = S2D_MCMD_NONE; float a = 0.0f, b = 0.0f;
-    if (l < NP) {
+    if constexpr (CTL) {
+      int scmd = S2D_MCMD_NONE; float sa = 0.0f, sb = 0.0f;
+      if (ctl.script_mask != 0u) m_scripted_action(p, pt, o, g, r, l, half, scmd, sa, sb);   // (uniform: a kernel argument)
+      if (l < NP) {
+        const uint32_t bit = 1u << l;
+        if (ctl.script_mask & bit) {
+          cmd = scmd; a = sa; b = sb;
+        } else if (ctl.random_mask & bit) {
+          m_random_action(p, gl, gh, (uint32_t)g.tick, l, t == 0, pol, cmd, a, b);
+        } else {
+          const float* ap = actions + (((int64_t)t * n + ec) * NP + l) * 3;
+          cmd = (int)ap[0]; a = ap[1]; b = ap[2];
+        }
+      }
+      if (ctl.actions_out) {                               // wave-uniform
+        if (valid && l < NP) {
+          float* w = act_row + (m_in_wg * NP + l) * 3;
+          w[0] = (float)cmd; w[1] = a; w[2] = b;
+        }
+        act_row += n * (NP * 3);
+      }
+    } else if (l < NP) {
       if (actions) {
         const float* ap = actions + (((int64_t)t * n + ec) * NP + l) * 3;
         cmd = (int)ap[0]; a = ap[1]; b = ap[2];
@@ -1291,9 +1402,14 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // STOCK_TYPES (with STOCK): all 22 players of the stock PlayerType, the table's entries are constants too.
 // SCHED (with STOCK and STOCK_TYPES): the schedule words are the engine's own (MStockSched).  ILL (general only): the engine has
 // IllegalDefense_ switched on.
-template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false>
+// CTL: per-slot controllers (MCtl, the one extra argument: the instantiations without it keep their argument list and code).
+S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
+S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
+template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, class... CtlArg>
 __global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
-                                                                     const float* __restrict__ actions, MRoll ro) {
+                                                                     const float* __restrict__ actions, MRoll ro, CtlArg... ctl_arg) {
+  static_assert(sizeof...(CtlArg) == (CTL ? 1 : 0), "the CTL instantiations take an MCtl, the others nothing more");
+  const MCtl ctl = m_ctl_arg(ctl_arg...);
   __shared__ float4 pos_tile[kEnvsPerBlock][kTileSlots];
   __shared__ PTab pt[PT_WORDS];                       // per-slot PlayerType parameters, shared by the 8 matches
   __shared__ unsigned int lds_cnt[8];
@@ -1314,28 +1430,31 @@ __global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p
     const MStockSched p{p_arg.auto_reset, p_arg.noise, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi M_SCHEDULE_INTS(X)};
 #undef X
     const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-    match_rollout_body(p, types, sh, q, n, n_steps, actions, ro);
+    match_rollout_body<CTL>(p, types, sh, q, n, n_steps, actions, ro, ctl);
   } else if constexpr (STOCK) {
     __syncthreads();
     const MStock p{p_arg.auto_reset, p_arg.noise, p_arg.penalty_shoot_outs, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi};
     if constexpr (STOCK_TYPES) {
       const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-      match_rollout_body(p, types, sh, q, n, n_steps, actions, ro);
+      match_rollout_body<CTL>(p, types, sh, q, n, n_steps, actions, ro, ctl);
     } else {
-      match_rollout_body(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro);
+      match_rollout_body<CTL>(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl);
     }
   } else {
     // The ~70 uniform parameters are read from LDS (broadcast reads) where they are used instead of
     // occupying SGPRs for the whole kernel: as kernargs they cost 142 SGPR spills and 48 B of scratch at
     // the 128-VGPR cap (26 spills / 12 B this way, +14 % throughput).
     static_assert(!ILL || !STOCK, "the stock configurations have the rule off");
-    using PBlock = std::conditional_t<ILL, MParams, MParamsNoIll>;
+    // The CTL kernels read the block through a type of their own (no data added): every helper templated on it is then an
+    // instantiation of theirs.  Helpers shared with the CTL kernels were optimised differently in the kernels without them.
+    using PBase = std::conditional_t<ILL, MParams, MParamsNoIll>;
+    using PBlock = std::conditional_t<CTL, MParamsCtl<PBase>, PBase>;
     __shared__ PBlock p_lds;
     static_assert(sizeof(MParams) / 4 <= kMBlock, "one thread per parameter word");
     if (threadIdx.x < sizeof(MParams) / 4)
       reinterpret_cast<uint32_t*>(&p_lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&p_arg)[threadIdx.x];
     __syncthreads();
-    match_rollout_body(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro);
+    match_rollout_body<CTL>(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl);
   }
 }
 
@@ -1373,6 +1492,8 @@ struct S2DMatchEngine {
   bool stock = false;                                  // mp's configuration words equal MStock: launches use the constant-folded kernels
   bool stock_types = false;                            // ... and every player is of the stock PlayerType (ptab's entries equal MStockTypes)
   bool stock_sched = false;                            // stock rules, physics and types, the engine's own schedule (MStockSched)
+  bool has_ctl = false;                                // s2d_match_set_controllers installed a table: launches use the CTL kernels
+  uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   char* arena; size_t arena_bytes; bool owns_arena;
   S2DMatchBuffers buf; MPtrs ptrs;
 };
@@ -1789,30 +1910,52 @@ S2D_API int s2d_match_buffer_offsets(S2DMatchHandle h, int64_t* offsets, int n_o
   return S2D_OK;
 }
 
-static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream) {
-  MRoll ro{nullptr, nullptr, nullptr, nullptr};
-  if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
+// One launch of the instantiation this engine runs; CTL (with one MCtl in `extra`): the controller variant of the same one.
+template <bool CTL, class... X>
+static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, X... extra) {
   MDeviceGuard guard(h->device);
+  const dim3 grid(m_grid(h->n)), block(kMBlock);
   if (h->stock_sched)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, true>), dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->mp,
-                       h->ptrs, h->n, n_steps, actions, ro);
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, true, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+                       actions, ro, extra...);
   else if (h->stock_types)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true>), dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->mp,
-                       h->ptrs, h->n, n_steps, actions, ro);
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+                       actions, ro, extra...);
   else if (h->stock)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, false>), dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->mp,
-                       h->ptrs, h->n, n_steps, actions, ro);
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, false, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+                       actions, ro, extra...);
   else if (h->mp.illegal_defense_number > 0)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, true>), dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream),
-                       h->mp, h->ptrs, h->n, n_steps, actions, ro);
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, true, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+                       actions, ro, extra...);
   else
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false>), dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->mp,
-                       h->ptrs, h->n, n_steps, actions, ro);
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+                       actions, ro, extra...);
   MHIP_TRY(hipGetLastError());
   return S2D_OK;
 }
+// actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL)
+static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
+                    float* actions_out = nullptr) {
+  MRoll ro{nullptr, nullptr, nullptr, nullptr};
+  if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  constexpr uint32_t kAll = (1u << NP) - 1u;
+  if (h->has_ctl) {
+    if (!actions && ((h->ctl_random | h->ctl_script) & kAll) != kAll)
+      return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
+    return m_dispatch<true>(h, n_steps, actions, ro, st, MCtl{h->ctl_random, h->ctl_script, actions_out});
+  }
+  if (actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, MCtl{actions ? 0u : kAll, 0u, actions_out});
+  return m_dispatch<false>(h, n_steps, actions, ro, st);
+}
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
+  if (h->has_ctl) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, controllers>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, controllers>" : h->stock ? "s2d_match_rollout_kernel<stock, controllers>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, controllers>" :
+                                              "s2d_match_rollout_kernel<general, controllers>";
+  }
   if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule>";
   return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types>" : h->stock ? "s2d_match_rollout_kernel<stock>" :
          h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense>" : "s2d_match_rollout_kernel<general>";
@@ -1835,4 +1978,28 @@ S2D_API int s2d_match_rollout(S2DMatchHandle h, int n_steps, const float* action
   if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
   if (n_steps == 0) return S2D_OK;
   return m_launch(h, n_steps, actions_dev, out, stream);
+}
+S2D_API int s2d_match_set_controllers(S2DMatchHandle h, const uint8_t* ctl) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!ctl) { h->has_ctl = false; h->ctl_random = 0u; h->ctl_script = 0u; return S2D_OK; }
+  uint32_t rnd = 0u, scr = 0u;
+  for (int i = 0; i < NP; ++i) {
+    if (ctl[i] > S2D_CTL_SCRIPTED)
+      return mfail(S2D_EINVAL, "controller code of slot " + std::to_string(i) + " is " + std::to_string((int)ctl[i]) +
+                               " (S2D_CTL_EXTERNAL / RANDOM / SCRIPTED = 0 / 1 / 2)");
+    if (ctl[i] == S2D_CTL_RANDOM) rnd |= 1u << i;
+    if (ctl[i] == S2D_CTL_SCRIPTED) scr |= 1u << i;
+  }
+  h->has_ctl = true; h->ctl_random = rnd; h->ctl_script = scr;
+  return S2D_OK;
+}
+S2D_API int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
+                                 float* actions_out_dev, void* stream) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
+  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
+  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
+  if (n_steps == 0) return S2D_OK;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev);
 }

@@ -19,6 +19,8 @@ GM_NAMES = {0: 'BeforeKickOff', 1: 'TimeOver', 2: 'PlayOn', 3: 'KickOff_', 4: 'K
             20: 'CatchFault_', 21: 'IndFreeKick_', 22: 'PenaltySetup_', 23: 'PenaltyReady_', 24: 'PenaltyTaken_',
             25: 'PenaltyMiss_', 26: 'PenaltyScore_', 27: 'IllegalDefense_', 28: 'PenaltyOnfield_', 29: 'PenaltyFoul_', 30: 'GoalieCatch_', 31: 'ExtendHalf'}
 CARD_NONE, CARD_YELLOW, CARD_RED = 0, 1, 2
+CTL_EXTERNAL, CTL_RANDOM, CTL_SCRIPTED = 0, 1, 2          # per-slot controllers (s2d_match_set_controllers)
+CTL_CODES = {'external': CTL_EXTERNAL, 'random': CTL_RANDOM, 'scripted': CTL_SCRIPTED}
 
 
 class S2DMatchParams(C.Structure):
@@ -108,6 +110,8 @@ MATCH_PROTOTYPES = (
     ('s2d_match_rollout', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p)),
     ('s2d_match_relative', C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_match_kernel_name', C.c_char_p, (C.c_void_p,)),
+    ('s2d_match_set_controllers', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_ex', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p)),
 )
 
 
@@ -118,3 +122,29 @@ def bind(lib):
         fn.restype = res
         fn.argtypes = list(args)
     return lib
+
+
+def controller_codes(spec):
+    """22 controller codes (bytes) from `spec`: 22 codes (ints or names), or {'left': c, 'right': c} with c a code or a name
+    ('external' | 'random' | 'scripted'; a missing side is external).  None stays None (no table)."""
+    if spec is None:
+        return None
+
+    def code(v):
+        if isinstance(v, str):
+            if v not in CTL_CODES:
+                raise ValueError(f"unknown controller {v!r} (use one of {sorted(CTL_CODES)})")
+            return CTL_CODES[v]
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 2:
+            raise ValueError(f"controller code {v!r} is not 0 (external), 1 (random) or 2 (scripted)")
+        return int(v)
+    if isinstance(spec, dict):
+        extra = set(spec) - {'left', 'right'}
+        if extra:
+            raise ValueError(f"controller spec keys must be 'left' / 'right', got {sorted(extra)}")
+        codes = [code(spec.get('left', CTL_EXTERNAL))] * 11 + [code(spec.get('right', CTL_EXTERNAL))] * 11
+    else:
+        codes = [code(v) for v in spec]
+        if len(codes) != MATCH_PLAYERS:
+            raise ValueError(f"controller spec needs {MATCH_PLAYERS} codes, got {len(codes)}")
+    return bytes(codes)

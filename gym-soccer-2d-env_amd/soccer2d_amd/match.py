@@ -67,6 +67,7 @@ def make_match_config(seed=0x5EED, env_id_offset=0, auto_reset=True, noise=False
 class MatchEngine:
     def __init__(self, num_envs, device='cuda:0', cfg=None, **kwargs):
         self.lib = M.bind(_capi.load_library())
+        self.controllers = None                         # no per-slot table (set_controllers)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device(device)
@@ -117,6 +118,15 @@ class MatchEngine:
         except Exception:
             pass
 
+    def set_controllers(self, spec):
+        """Per-slot controllers: `spec` = 22 codes, or {'left': ..., 'right': ...}, with 'external' (0: the caller's actions),
+        'random' (1: the in-kernel random policy) or 'scripted' (2: the in-kernel scripted team, include/s2d_match.h).  Rows of
+        non-external slots in the caller's actions are never read.  None restores the behaviour without a table."""
+        codes = M.controller_codes(spec)
+        buf = None if codes is None else (C.c_uint8 * M.MATCH_PLAYERS).from_buffer_copy(codes)
+        _capi.check(self.lib, self.lib.s2d_match_set_controllers(self._h, buf), 's2d_match_set_controllers')
+        self.controllers = None if codes is None else list(codes)
+
     def _actions(self, actions, T=None):
         if actions is None:
             return None, None
@@ -143,18 +153,25 @@ class MatchEngine:
         self._keep = keep
         return self.reward_left, self.done
 
-    def alloc_rollout(self, T, with_obs=True):
+    def alloc_rollout(self, T, with_obs=True, record_actions=False):
         n, dev = self.num_envs, self.device
-        return dict(obs=torch.empty((T, n, M.MATCH_SLOTS, M.MATCH_OBJ_WORDS), dtype=torch.float32, device=dev) if with_obs else None,
-                    reward=torch.empty((T, n), dtype=torch.float32, device=dev),
-                    mode=torch.empty((T, n), dtype=torch.int32, device=dev),
-                    done=torch.empty((T, n), dtype=torch.uint8, device=dev))
+        out = dict(obs=torch.empty((T, n, M.MATCH_SLOTS, M.MATCH_OBJ_WORDS), dtype=torch.float32, device=dev) if with_obs else None,
+                   reward=torch.empty((T, n), dtype=torch.float32, device=dev),
+                   mode=torch.empty((T, n), dtype=torch.int32, device=dev),
+                   done=torch.empty((T, n), dtype=torch.uint8, device=dev))
+        if record_actions:
+            out['actions'] = torch.empty((T, n, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=dev)
+        return out
 
-    def rollout(self, n_steps, actions=None, out=None, with_obs=True):
+    def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False):
+        """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
+        each cycle, before the engine's own gating (caller slots: the caller's row)."""
         T = int(n_steps)
         keep, ptr = self._actions(actions, T)
         if out is None:
-            out = self.alloc_rollout(T, with_obs)
+            out = self.alloc_rollout(T, with_obs, record_actions)
+        elif record_actions and out.get('actions') is None:
+            out['actions'] = torch.empty((T, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
         ro = M.S2DMatchRollout()
         for name in ('obs', 'reward', 'mode', 'done'):
             v = out.get(name)
@@ -162,7 +179,14 @@ class MatchEngine:
                 if not v.is_contiguous() or v.shape[0] < T or v.shape[1] != self.num_envs:
                     raise ValueError(f"rollout buffer {name!r} must be contiguous [T>={T},{self.num_envs},...]")
                 setattr(ro, name, v.data_ptr())
-        _capi.check(self.lib, self.lib.s2d_match_rollout(self._h, T, ptr, C.byref(ro), self._stream()), 's2d_match_rollout')
+        rec = out.get('actions') if record_actions else None
+        if rec is not None:
+            if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or tuple(rec.shape[1:]) != (self.num_envs, M.MATCH_PLAYERS, 3):
+                raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{self.num_envs},22,3]")
+            _capi.check(self.lib, self.lib.s2d_match_rollout_ex(self._h, T, ptr, C.byref(ro), C.c_void_p(rec.data_ptr()), self._stream()),
+                        's2d_match_rollout_ex')
+        else:
+            _capi.check(self.lib, self.lib.s2d_match_rollout(self._h, T, ptr, C.byref(ro), self._stream()), 's2d_match_rollout')
         self._keep = (keep, out)
         return out
 
@@ -236,16 +260,32 @@ class Soccer2DMatchVecEnv:
             (zero-sum: the right team's reward is the negative).
     done    uint8 [N]           1 when a match reached TimeOver (auto-restart follows the VecEnv convention).
     info    dict of tensors     game_mode_type, game_mode_side, scores, cycle, nearest player per team.
+
+    opponent = 'random' | 'scripted': the learner controls the left team only -- actions float32 [N, 11, 3] -- and the right
+    team is played inside the cycle kernel (the random policy, or the scripted team of include/s2d_match.h).  None: both teams
+    come from the caller, as above.
     """
 
-    def __init__(self, num_envs, device='cuda:0', **kwargs):
+    @staticmethod
+    def spaces(opponent=None):
+        """(observation_space, action_space) of an env with this opponent (no engine needed)."""
         import numpy as np
         from .spaces import Box
+        if opponent not in (None, 'random', 'scripted'):
+            raise ValueError(f"opponent must be None, 'random' or 'scripted', got {opponent!r}")
+        return (Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32),
+                Box(low=-180.0, high=180.0, shape=(22 if opponent is None else 11, 3), dtype=np.float32))
+
+    def __init__(self, num_envs, device='cuda:0', opponent=None, **kwargs):
+        self.observation_space, self.action_space = self.spaces(opponent)
         self.engine = MatchEngine(num_envs, device, **kwargs)
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
-        self.observation_space = Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32)
-        self.action_space = Box(low=-180.0, high=180.0, shape=(22, 3), dtype=np.float32)
+        self.opponent = opponent
         self._ro = self.engine.alloc_rollout(1)
+        if opponent is not None:
+            self.engine.set_controllers({'left': 'external', 'right': opponent})
+            # the caller's half of the action rows; the right team's rows are never read
+            self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
 
     def _obs(self):
         e = self.engine
@@ -256,7 +296,16 @@ class Soccer2DMatchVecEnv:
         return self._obs()
 
     def step(self, actions=None):
-        a = None if actions is None else torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(1, self.num_envs, 22, 3)
+        if self.opponent is None:
+            a = None if actions is None else torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(1, self.num_envs, 22, 3)
+        else:
+            if actions is None:
+                raise ValueError("with an in-kernel opponent, step() needs the left team's actions [N, 11, 3]")
+            a = torch.as_tensor(actions, device=self.device).to(torch.float32)
+            if tuple(a.shape) != (self.num_envs, 11, 3):
+                raise ValueError(f"actions must have shape ({self.num_envs}, 11, 3) (the left team), got {tuple(a.shape)}")
+            self._act[0, :, :11] = a
+            a = self._act
         self.engine.rollout(1, actions=a, out=self._ro)
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,

@@ -230,6 +230,57 @@ int s2d_match_step(S2DMatchHandle h, const float *actions_dev, void *stream);
 int s2d_match_rollout(S2DMatchHandle h, int n_steps, const float *actions_dev /* [T][N][22][3] or NULL */,
                       const S2DMatchRollout *out, void *stream);
 
+/* Per-slot controllers.  Without a table (the default, and after s2d_match_set_controllers(h, NULL)) every slot takes the caller's
+ * row, or the random policy when actions_dev is NULL: the behaviour above.  With a table, each of the 22 slots has its own code:
+ *   S2D_CTL_EXTERNAL  the caller's row of actions_dev (rows of the other slots are never read: they may hold anything),
+ *   S2D_CTL_RANDOM    the random policy's draw (the same Philox stream and counters as with actions_dev == NULL),
+ *   S2D_CTL_SCRIPTED  the scripted team below, evaluated in the cycle kernel from the start-of-cycle state of the match.
+ * s2d_match_step / s2d_match_rollout use the table when one is set.
+ *
+ * The scripted team is this project's own rule-based baseline, written to give a learner an opponent that plays and to label
+ * expert actions.  It is not the behaviour of any published team (helios or other) and claims no parity with a reference.  For
+ * player l of side s, the first rule that applies wins (ball = the ball at the start of the cycle; "goal" = the centre of a goal
+ * line; every direction is relative to the body, norm(atan2_deg(dy, dx) - body), every distance is compared squared):
+ *   1. NONE in the halted modes (TimeOver, Pause, Human), the dead-ball modes (announcements, AfterGoal_, BeforeKickOff,
+ *      FirstHalfOver, ExtendHalf, GoalieCatch_, the shoot-out modes other than PenaltyReady_ / PenaltyTaken_), and for a player
+ *      who is tackling or sent off.
+ *   2. A goalie holding a caught ball (FreeKick_, ball_holder == l + 1): KICK(max_power, toward the opponents' goal).
+ *   3. Goalie catch: the goalie in PlayOn (or defending in PenaltyTaken_) with catch_ban == 0, the ball within his catch length
+ *      (catchable_area_l * stretch) and catch angle, inside his own penalty area, last touched by the other side (no back pass):
+ *      CATCH(direction of the ball).
+ *   4. The ball kickable (his PlayerType's kickable area) and his team may play it (PlayOn or its own restart):
+ *      KICK(max_power, toward the opponents' goal).
+ *   5. Chaser: his team's nearest non-goalie to the ball (ties to the lower index, sent-off players excluded), in PlayOn and his
+ *      team's own restarts: with ang = direction of the ball, TURN(ang) if |ang| > S2D_SCRIPT_TURN_TOL, else
+ *      DASH(S2D_SCRIPT_DASH_POWER, 0).
+ *   6. The goalie otherwise: goes to (-+S2D_SCRIPT_GOALIE_X, clamp(ball_y * S2D_SCRIPT_GOALIE_Y_GAIN, +-S2D_SCRIPT_GOALIE_Y_MAX)) on
+ *      his own goal's side with the same turn / dash rule; within S2D_SCRIPT_ARRIVE of it he turns toward the ball instead (TURN if
+ *      |ang| > S2D_SCRIPT_TURN_TOL, else NONE).
+ *   7. Everybody else: the same toward his home position -- the kick-off formation's place (x mirrored for the right team) plus
+ *      S2D_SCRIPT_HOME_GAIN_X * ball_x, S2D_SCRIPT_HOME_GAIN_Y * ball_y, clamped to the pitch.  This also covers the other team's
+ *      restarts: nobody chases a ball the other side is to play.
+ *   8. The shoot-out: in PenaltyReady_ / PenaltyTaken_ the current taker uses rules 4 and 5 (he is his team's chaser), the
+ *      defending goalie in PenaltyTaken_ rules 3 and 6; both aim at / guard the goal the kicks are taken at (the right one).
+ *      Everybody else: NONE.
+ * The constants: */
+enum { S2D_CTL_EXTERNAL = 0, S2D_CTL_RANDOM = 1, S2D_CTL_SCRIPTED = 2 };
+#define S2D_SCRIPT_TURN_TOL 10.0f       /* degrees: a target further off the body axis is turned to, not dashed to */
+#define S2D_SCRIPT_ARRIVE 1.0f          /* m: a goalie / home position this close is reached */
+#define S2D_SCRIPT_DASH_POWER 100.0f    /* power of every scripted dash */
+#define S2D_SCRIPT_GOALIE_X 50.0f       /* |x| of the goalie's guard point (2.5 m in front of his goal line) */
+#define S2D_SCRIPT_GOALIE_Y_GAIN 0.25f  /* guard point y = this * ball y ... */
+#define S2D_SCRIPT_GOALIE_Y_MAX 5.0f    /* ... clamped to +- this (inside the goal mouth, half width 7.01) */
+#define S2D_SCRIPT_HOME_GAIN_X 0.5f     /* home position = formation place + these gains * ball position */
+#define S2D_SCRIPT_HOME_GAIN_Y 0.25f
+/* ctl: host array of 22 codes, or NULL = no table (the behaviour without one).  Error: a code outside 0..2. */
+int s2d_match_set_controllers(S2DMatchHandle h, const uint8_t *ctl);
+/* s2d_match_rollout plus the action record: actions_out_dev = float[T][N][22][3] (4-byte aligned) or NULL receives the (command, a, b)
+ * each slot's controller produced in each cycle, before the engine's own gating (halted modes, tackling, red cards); caller slots
+ * hold the caller's row.  Without a table the record shows the behaviour without one.  Errors: an unaligned actions_out_dev; a table
+ * with an S2D_CTL_EXTERNAL slot while actions_dev is NULL (that error also applies to s2d_match_step / s2d_match_rollout). */
+int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float *actions_dev, const S2DMatchRollout *out,
+                         float *actions_out_dev, void *stream);
+
 /* Per-agent relative tables of the WorldModel every player receives: for agent p (0..21) and object
  * j (0..21 players, 22 = ball) dist[N][22][23] = Player.dist_from_self / Ball.dist_from_self and
  * angle[N][22][23] = Player.angle_from_self / Ball.angle_from_self (absolute direction of j seen from
