@@ -1484,6 +1484,196 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_relative_kernel(MPtrs q, in
   }
 }
 
+// Per-agent observations (include/s2d_match.h, s2d_match_agent_obs).  Per-slot words the cycle kernels do not keep (the PT table
+// stays as it is): built on the host at create time, passed by value.
+struct MAgentTab {
+  float ka[kHalf], ka2[kHalf], speed_max[kHalf], kick_rate[kHalf], inv_margin[kHalf], size[kHalf], type_id[kHalf];
+  float ball_size, ball_decay;
+};
+constexpr int kAObsVec = S2D_AGENT_OBS_DIM / 4;                       // 56 float4 per row
+static_assert(S2D_AGENT_OBS_DIM % 4 == 0 && kAObsVec <= 2 * kHalf, "a half-wave stores a row as two float4 per lane");
+static_assert(S2D_AGENT_OBS_TEAMMATES == 48 && S2D_AGENT_OBS_OPPONENTS == 136 && S2D_AGENT_OBS_ROW_WORDS == 8, "row layout");
+constexpr uint32_t kOurSetPlayModes = (1u << S2D_GM_KICK_OFF) | (1u << S2D_GM_KICK_IN) | (1u << S2D_GM_FREE_KICK) |
+                                      (1u << S2D_GM_CORNER_KICK) | (1u << S2D_GM_GOAL_KICK) | (1u << S2D_GM_IND_FREE_KICK) |
+                                      (1u << S2D_GM_GOALIE_CATCH) | (1u << S2D_GM_PENALTY_KICK);
+struct MAObsShared {                                   // one match (half-wave): the lanes' facts, then the row being assembled
+  float x[kHalf], y[kHalf], vx[kHalf], vy[kHalf], reach[kHalf], catch_ban[kHalf];
+  int rank_slot[2][3];                                 // per team: slots of the three smallest (reach, slot) keys, -1 = none
+  float4 row[kAObsVec];
+};
+S2D_DEV float m_own_body(float b, bool right) { return right ? (b > 0.0f ? b - 180.0f : b + 180.0f) : b; }
+S2D_DEV float m_side_word(int side, int ours) { return side == ours ? 1.0f : (side == SIDE_NONE ? 0.0f : -1.0f); }
+
+// Mapping as the relative kernel: a half-wave per match, lane l = slot (22 = the ball).  Each lane derives its object's facts once
+// (kickable, reach steps, rank among its team); per-side lines once per match.  Then, for each agent of the mask in slot order,
+// every lane writes its part of the agent's row into an LDS row (objects: their 8 words; the agent's lane: the self block; the
+// ball's lane: ball words and the kick rate; lanes 23..28: the game block) and the half-wave stores the 896-byte row as two
+// contiguous float4 stores (512 + 384 B), every line written whole by one instruction.
+__global__ __launch_bounds__(kMBlock) void s2d_match_agent_obs_kernel(MParams p, MAgentTab tab, MPtrs q, int64_t n, uint32_t mask,
+                                                                       float* __restrict__ obs) {
+  __shared__ MAObsShared sh_all[kEnvsPerBlock];
+  MAObsShared& sh = sh_all[threadIdx.x / kHalf];
+  const int l = threadIdx.x & (kHalf - 1);
+  const int half = (threadIdx.x >> 5) & 1;
+  const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
+  const bool valid = e < n;
+  const int64_t ec = valid ? e : n - 1;
+  const bool is_player = l < NP;
+  float x = 0.0f, y = 0.0f, vx = 0.0f, vy = 0.0f, body = 0.0f, stamina = 0.0f, effort = 0.0f, recovery = 0.0f, capacity = 0.0f;
+  int tackle = 0, card = 0, catch_ban = 0;
+  if (l <= BALL) {
+    const int64_t k = ec * SLOTS + l;
+    x = q.obj[MF_X * q.obj_stride + k]; y = q.obj[MF_Y * q.obj_stride + k];
+    vx = q.obj[MF_VX * q.obj_stride + k]; vy = q.obj[MF_VY * q.obj_stride + k];
+  }
+  if (is_player) {
+    const int64_t k = ec * SLOTS + l;
+    body = q.obj[MF_BODY * q.obj_stride + k];
+    stamina = q.obj[MF_STAMINA * q.obj_stride + k]; effort = q.obj[MF_EFFORT * q.obj_stride + k];
+    recovery = q.obj[MF_RECOVERY * q.obj_stride + k]; capacity = q.obj[MF_CAPACITY * q.obj_stride + k];
+    tackle = __float_as_int(q.obj[MF_TACKLE * q.obj_stride + k]); card = __float_as_int(q.obj[MF_CARD * q.obj_stride + k]);
+    catch_ban = __float_as_int(q.obj[MF_CATCH_BAN * q.obj_stride + k]);
+  }
+  const int cycle = q.env[ME_CYCLE * q.env_stride + ec], mode = q.env[ME_MODE * q.env_stride + ec];
+  const int mode_side = q.env[ME_MODE_SIDE * q.env_stride + ec], last_touch = q.env[ME_LAST_TOUCH * q.env_stride + ec];
+  const int score_l = q.env[ME_SCORE_L * q.env_stride + ec], score_r = q.env[ME_SCORE_R * q.env_stride + ec];
+  const int holder = q.env[ME_HOLDER * q.env_stride + ec], stopped = q.env[ME_STOPPED * q.env_stride + ec];
+  const bool active = is_player && card < S2D_CARD_RED;
+  sh.x[l] = x; sh.y[l] = y; sh.vx[l] = vx; sh.vy[l] = vy; sh.catch_ban[l] = (float)catch_ban;
+  wave_fence();
+  const float bx = sh.x[BALL], by = sh.y[BALL], bvx = sh.vx[BALL], bvy = sh.vy[BALL];
+  // object facts (frame-free: negating every input negates every difference exactly)
+  const int lc = is_player ? l : 0;
+  const float ka2 = tab.ka2[lc];
+  const bool kickable = active && sq2(bx - x, by - y) <= ka2;
+  int reach = S2D_AGENT_REACH_NONE;
+  if (active) {
+    if (sq2(bx - x, by - y) <= ka2) {
+      reach = 0;
+    } else {
+      const float ka = tab.ka[lc], smax = tab.speed_max[lc], decay = tab.ball_decay;
+      float cx = bx, cy = by, cvx = bvx, cvy = bvy;
+      for (int t = 1; t <= S2D_AGENT_REACH_MAX; ++t) {
+        cx = cx + cvx; cy = cy + cvy; cvx = cvx * decay; cvy = cvy * decay;
+        const float r = ka + (float)t * smax;
+        if (sq2(cx - x, cy - y) <= r * r) { reach = t; break; }
+      }
+    }
+  }
+  sh.reach[l] = (float)reach;
+  const uint32_t kick_mask = hballot(kickable, half) & 0x3FFFFFu, act_mask = hballot(active, half) & 0x3FFFFFu;
+  if (l < 6) sh.rank_slot[l / 3][l % 3] = -1;
+  wave_fence();
+  if (active) {                                        // rank of (reach, slot) among the active players of the team
+    const int t0 = l < 11 ? 0 : 11;
+    int rank = 0;
+    for (int j = t0; j < t0 + 11; ++j) {
+      const int rj = (int)sh.reach[j];
+      rank += (((act_mask >> j) & 1u) != 0u && (rj < reach || (rj == reach && j < l))) ? 1 : 0;
+    }
+    if (rank < 3) sh.rank_slot[l < 11 ? 0 : 1][rank] = l;
+  }
+  // per-side lines, in the frame of side S (index 0 = left, 1 = right); every lane the same value
+  float offside_line[2], def_ours[2], def_theirs[2];
+  for (int S = 0; S < 2; ++S) {
+    const float sg = S == 0 ? 1.0f : -1.0f;
+    const int us = S == 0 ? 0 : 11, them = S == 0 ? 11 : 0;
+    const float obx = sg * bx;
+    float first = -1.0e9f, second = -1.0e9f;
+    for (int j = 0; j < 11; ++j) {
+      const float v = sg * sh.x[them + j];
+      if (v > first) { second = first; first = v; } else if (v > second) second = v;
+    }
+    float line = 0.0f;
+    if (second > line) line = second;
+    if (obx > line) line = obx;
+    float mn = obx, mx = obx;
+    for (int j = 1; j < 11; ++j) {                     // (slot 0 of each team is the goalie)
+      const bool act_us = ((act_mask >> (us + j)) & 1u) != 0u, act_them = ((act_mask >> (them + j)) & 1u) != 0u;
+      const float vu = sg * sh.x[us + j], vt = sg * sh.x[them + j];
+      if (act_us && vu < mn) mn = vu;
+      if (act_them && vt > mx) mx = vt;
+    }
+    offside_line[S] = line; def_ours[S] = mn; def_theirs[S] = mx;
+  }
+  wave_fence();
+  const int nrows = __builtin_popcount(mask);
+  float* out = obs + (e * (int64_t)nrows) * S2D_AGENT_OBS_DIM;
+  uint32_t rest = mask;
+  for (int r = 0; r < nrows; ++r) {
+    const int pa = __builtin_ctz(rest);                // the agent (uniform: the mask is a kernel argument)
+    rest &= rest - 1u;
+    const bool right = pa >= 11;
+    const int ours = right ? SIDE_RIGHT : SIDE_LEFT, S = right ? 1 : 0;
+    const float sg = right ? -1.0f : 1.0f;
+    const float ax = sg * sh.x[pa], ay = sg * sh.y[pa];
+    const float abody = m_own_body(__shfl(body, pa, kHalf), right);
+    // this lane's object in the agent's frame
+    const float ox = sg * x, oy = sg * y, ovx = sg * vx, ovy = sg * vy, obody = m_own_body(body, right);
+    const float dx = ox - ax, dy = oy - ay;
+    float dist = hypot2(dx, dy);
+    float bearing = norm_deg_any(atan2_deg(dy, dx) - abody);
+    if (l == pa) { dist = 0.0f; bearing = 0.0f; }
+    if (is_player) {
+      const int idx = ((l < 11) == !right ? S2D_AGENT_OBS_TEAMMATES : S2D_AGENT_OBS_OPPONENTS) / 4 + 2 * (l % 11);
+      sh.row[idx] = active ? make_float4(ox, oy, ovx, ovy) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      sh.row[idx + 1] = active ? make_float4(obody, dist, bearing, (float)reach) : make_float4(0.0f, 0.0f, 0.0f, (float)reach);
+      if (l == pa) {                                   // self block, words 0..11
+        sh.row[0] = make_float4(ox, oy, ovx, ovy);
+        sh.row[1] = make_float4(obody, stamina, effort, recovery);
+        sh.row[2] = make_float4(capacity, (l == S2D_MATCH_GOALIE_LEFT || l == S2D_MATCH_GOALIE_RIGHT) ? 1.0f : 0.0f, (float)tackle,
+                                (float)card);
+      }
+    } else if (l == BALL) {                            // ball words; self words 12..15 (they need the ball's distance and bearing)
+      const bool akick = ((kick_mask >> pa) & 1u) != 0u;
+      float rate = 0.0f;
+      if (akick) {
+        const float dir_diff = fabsf(bearing);
+        const float dist_ball = dist - tab.size[pa] - tab.ball_size;    // (hypot2 == sqrtf of the same square)
+        rate = tab.kick_rate[pa] * (1.0f - 0.25f * (dir_diff * 0.005555555555555556f) - 0.25f * (dist_ball * tab.inv_margin[pa]));
+      }
+      sh.row[3] = make_float4(akick ? 1.0f : 0.0f, rate, sh.catch_ban[pa], tab.type_id[pa]);
+      sh.row[4] = make_float4(ox, oy, ovx, ovy);
+      const int hside = holder > 0 ? side_of(holder - 1) : SIDE_NONE;
+      sh.row[5] = make_float4(dist, bearing, m_side_word(last_touch, ours), m_side_word(hside, ours));
+    } else if (l <= BALL + 6) {                        // game block: lane 23 + g writes words 4g..4g+3
+      const int g = l - (BALL + 1);
+      const uint32_t team = right ? 0x3FF800u : 0x7FFu;
+      const uint32_t km_tm = kick_mask & team & ~(1u << pa), km_op = kick_mask & (0x3FFFFFu ^ team);
+      const float k_tm = km_tm ? (float)(__builtin_ctz(km_tm) % 11 + 1) : 0.0f;
+      const float k_op = km_op ? (float)(__builtin_ctz(km_op) % 11 + 1) : 0.0f;
+      const int* rs = sh.rank_slot[S];
+      const int t1 = rs[0] == pa ? rs[1] : rs[0];
+      const int t2 = (rs[0] == pa || rs[1] == pa) ? rs[2] : rs[1];
+      const int* ro = sh.rank_slot[1 - S];
+      const float t1r = t1 >= 0 ? sh.reach[t1] : (float)S2D_AGENT_REACH_NONE, t1u = t1 >= 0 ? (float)(t1 % 11 + 1) : 0.0f;
+      const float t2r = t2 >= 0 ? sh.reach[t2] : (float)S2D_AGENT_REACH_NONE, t2u = t2 >= 0 ? (float)(t2 % 11 + 1) : 0.0f;
+      const float o1r = ro[0] >= 0 ? sh.reach[ro[0]] : (float)S2D_AGENT_REACH_NONE, o1u = ro[0] >= 0 ? (float)(ro[0] % 11 + 1) : 0.0f;
+      const float o2r = ro[1] >= 0 ? sh.reach[ro[1]] : (float)S2D_AGENT_REACH_NONE, o2u = ro[1] >= 0 ? (float)(ro[1] % 11 + 1) : 0.0f;
+      const float sp = in_modes(mode, kOurSetPlayModes) ? 1.0f : 0.0f;
+      const float side_w = m_side_word(mode_side, ours);
+      float4 w;
+      switch (g) {
+        case 0: w = make_float4((float)mode, side_w, (float)(right ? score_r : score_l), (float)(right ? score_l : score_r)); break;
+        case 1: w = make_float4((float)cycle, (float)stopped, (float)cycles_to_period_end(p, cycle),
+                                in_modes(mode, kPenaltyModes) ? 1.0f : 0.0f); break;
+        case 2: w = make_float4(offside_line[S], def_ours[S], def_theirs[S], k_tm); break;
+        case 3: w = make_float4(k_op, sh.reach[pa], t1r, t1u); break;
+        case 4: w = make_float4(t2r, t2u, o1r, o1u); break;
+        default: w = make_float4(o2r, o2u, side_w > 0.0f ? sp : 0.0f, side_w < 0.0f ? sp : 0.0f); break;
+      }
+      sh.row[S2D_AGENT_OBS_GAME / 4 + g] = w;
+    }
+    wave_fence();
+    if (valid) {
+      float4* dst = reinterpret_cast<float4*>(out + (int64_t)r * S2D_AGENT_OBS_DIM);
+      dst[l] = sh.row[l];
+      if (l + kHalf < kAObsVec) dst[l + kHalf] = sh.row[l + kHalf];
+    }
+    wave_fence();
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -1494,6 +1684,7 @@ struct S2DMatchEngine {
   bool stock_sched = false;                            // stock rules, physics and types, the engine's own schedule (MStockSched)
   bool has_ctl = false;                                // s2d_match_set_controllers installed a table: launches use the CTL kernels
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
+  MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
   char* arena; size_t arena_bytes; bool owns_arena;
   S2DMatchBuffers buf; MPtrs ptrs;
 };
@@ -1829,6 +2020,15 @@ S2D_API int s2d_match_create(const S2DMatchConfig* cfg, int64_t n_envs, int devi
   if (!h) return mfail(S2D_ENOMEM, "host allocation failed");
   h->cfg = *cfg; h->n = n_envs; h->stride = L.stride; h->device = device;
   mparams_from_config(*cfg, h->mp, h->ptab);
+  std::memset(&h->atab, 0, sizeof h->atab);
+  for (int i = 0; i < NP; ++i) {
+    const S2DPlayerType& t = cfg->player_types[cfg->player_type_id[i]];
+    h->atab.ka[i] = (float)t.player_size + h->mp.ball_size + (float)t.kickable_margin;   // as the kickable bound is derived
+    h->atab.ka2[i] = h->ptab[PT_KICKABLE_AREA2][i]; h->atab.speed_max[i] = h->ptab[PT_SPEED_MAX][i];
+    h->atab.kick_rate[i] = h->ptab[PT_KICK_RATE][i]; h->atab.inv_margin[i] = h->ptab[PT_INV_KICK_MARGIN][i];
+    h->atab.size[i] = h->ptab[PT_SIZE][i]; h->atab.type_id[i] = (float)cfg->player_type_id[i];
+  }
+  h->atab.ball_size = h->mp.ball_size; h->atab.ball_decay = h->ptab[PT_DECAY][BALL];
   {                                                     // S2D_MATCH_GENERAL_KERNEL=1: the general instantiation whatever the configuration (tests, A/B)
     const char* general = std::getenv("S2D_MATCH_GENERAL_KERNEL");
     h->stock = m_is_stock(h->mp) && !(general && general[0] == '1');
@@ -1965,6 +2165,17 @@ S2D_API int s2d_match_relative(S2DMatchHandle h, float* dist_dev, float* angle_d
   MDeviceGuard guard(h->device);
   hipLaunchKernelGGL(s2d_match_relative_kernel, dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->ptrs,
                      h->n, dist_dev, angle_dev);
+  MHIP_TRY(hipGetLastError());
+  return S2D_OK;
+}
+S2D_API int s2d_match_agent_obs(S2DMatchHandle h, uint32_t slot_mask, float* obs_dev, void* stream) {
+  if (!h || !obs_dev) return mfail(S2D_EINVAL, "NULL argument");
+  if (slot_mask == 0u || (slot_mask >> NP) != 0u)
+    return mfail(S2D_EINVAL, "slot_mask must be a non-empty set of bits 0..21 (0x3FFFFF = all agents)");
+  if (reinterpret_cast<uintptr_t>(obs_dev) & 15u) return mfail(S2D_EINVAL, "agent observation buffer must be 16-byte aligned");
+  MDeviceGuard guard(h->device);
+  hipLaunchKernelGGL(s2d_match_agent_obs_kernel, dim3(m_grid(h->n)), dim3(kMBlock), 0, static_cast<hipStream_t>(stream), h->mp,
+                     h->atab, h->ptrs, h->n, slot_mask, obs_dev);
   MHIP_TRY(hipGetLastError());
   return S2D_OK;
 }

@@ -21,6 +21,28 @@ GM_NAMES = {0: 'BeforeKickOff', 1: 'TimeOver', 2: 'PlayOn', 3: 'KickOff_', 4: 'K
 CARD_NONE, CARD_YELLOW, CARD_RED = 0, 1, 2
 CTL_EXTERNAL, CTL_RANDOM, CTL_SCRIPTED = 0, 1, 2          # per-slot controllers (s2d_match_set_controllers)
 CTL_CODES = {'external': CTL_EXTERNAL, 'random': CTL_RANDOM, 'scripted': CTL_SCRIPTED}
+# per-agent observations in each team's own frame (s2d_match_agent_obs; the words are specified in include/s2d_match.h)
+AGENT_OBS_DIM, AGENT_REACH_MAX, REACH_NONE = 224, 50, 51
+AGENT_OBS_BLOCKS = {'self': slice(0, 16), 'ball': slice(16, 24), 'game': slice(24, 48), 'teammates': slice(48, 136),
+                    'opponents': slice(136, 224)}
+AGENT_ROW_FIELDS = ('x', 'y', 'vx', 'vy', 'body', 'dist', 'bearing', 'reach_steps')    # one teammate / opponent row
+AGENT_OBS_FIELDS = dict(AGENT_OBS_BLOCKS)
+for _i, _n in enumerate(('x', 'y', 'vx', 'vy', 'body', 'stamina', 'effort', 'recovery', 'stamina_capacity', 'is_goalie',
+                         'tackle_cycles', 'card', 'is_kickable', 'kick_rate', 'catch_ban', 'type_id')):
+    AGENT_OBS_FIELDS['self.' + _n] = 0 + _i
+for _i, _n in enumerate(('x', 'y', 'vx', 'vy', 'dist_from_self', 'bearing', 'last_touch', 'holder')):
+    AGENT_OBS_FIELDS['ball.' + _n] = 16 + _i
+for _i, _n in enumerate(('game_mode_type', 'mode_side', 'our_score', 'their_score', 'cycle', 'stopped_cycle', 'cycles_to_period_end',
+                         'is_penalty_kick_mode', 'offside_line_x', 'our_defense_line_x', 'their_defense_line_x',
+                         'kickable_teammate_unum', 'kickable_opponent_unum', 'self_reach_steps',
+                         'first_teammate_reach_steps', 'first_teammate_unum', 'second_teammate_reach_steps', 'second_teammate_unum',
+                         'first_opponent_reach_steps', 'first_opponent_unum', 'second_opponent_reach_steps', 'second_opponent_unum',
+                         'is_our_set_play', 'is_their_set_play')):
+    AGENT_OBS_FIELDS['game.' + _n] = 24 + _i
+for _t, _base in (('teammates', 48), ('opponents', 136)):       # [..., 11 rows] with a stride of 8 words
+    for _i, _n in enumerate(AGENT_ROW_FIELDS):
+        AGENT_OBS_FIELDS[f'{_t}.{_n}'] = slice(_base + _i, _base + 88, 8)
+AGENT_SLOT_MASKS = {'all': 0x3FFFFF, 'left': 0x7FF, 'right': 0x3FF800}
 
 
 class S2DMatchParams(C.Structure):
@@ -112,6 +134,7 @@ MATCH_PROTOTYPES = (
     ('s2d_match_kernel_name', C.c_char_p, (C.c_void_p,)),
     ('s2d_match_set_controllers', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_ex', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_match_agent_obs', C.c_int, (C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
 )
 
 
@@ -148,3 +171,14 @@ def controller_codes(spec):
         if len(codes) != MATCH_PLAYERS:
             raise ValueError(f"controller spec needs {MATCH_PLAYERS} codes, got {len(codes)}")
     return bytes(codes)
+
+
+def agent_slot_mask(slots):
+    """slot mask of s2d_match_agent_obs from 'all' | 'left' | 'right' | an int mask of bits 0..21"""
+    if isinstance(slots, str):
+        if slots not in AGENT_SLOT_MASKS:
+            raise ValueError(f"slots must be one of {sorted(AGENT_SLOT_MASKS)} or a mask, got {slots!r}")
+        return AGENT_SLOT_MASKS[slots]
+    if isinstance(slots, bool) or int(slots) != slots or not 0 < int(slots) <= 0x3FFFFF:
+        raise ValueError(f"slot mask must be a non-empty set of bits 0..21, got {slots!r}")
+    return int(slots)

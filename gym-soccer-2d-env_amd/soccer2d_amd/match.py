@@ -222,6 +222,21 @@ class MatchEngine:
         teammate[:, M.MATCH_BALL] = False
         return {'dist': d, 'bearing': bearing, 'teammate': teammate}
 
+    def agent_observations(self, slots='all', out=None):
+        """float32 [N, k, 224]: each selected agent's observation in its own team's frame (include/s2d_match.h, "Per-agent
+        observations"), rows in ascending slot order.  slots = 'all' (22) | 'left' (slots 0..10) | 'right' (11..21) | a mask of
+        bits 0..21.  Computed from the current state by one kernel on torch's current stream; `out` (contiguous, float32, 16-byte
+        aligned, [N, k, 224]) is written in place and returned."""
+        mask = M.agent_slot_mask(slots)
+        shape = (self.num_envs, bin(mask).count('1'), M.AGENT_OBS_DIM)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        _capi.check(self.lib, self.lib.s2d_match_agent_obs(self._h, mask, C.c_void_p(out.data_ptr()), self._stream()),
+                    's2d_match_agent_obs')
+        return out
+
     def world_model(self):
         """dict proto-path -> device tensor (left team's point of view = absolute coordinates)."""
         P = M.MATCH_PLAYERS
@@ -264,31 +279,49 @@ class Soccer2DMatchVecEnv:
     opponent = 'random' | 'scripted': the learner controls the left team only -- actions float32 [N, 11, 3] -- and the right
     team is played inside the cycle kernel (the random policy, or the scripted team of include/s2d_match.h).  None: both teams
     come from the caller, as above.
+
+    obs = 'agent': every controlled agent observes in its own team's frame (MatchEngine.agent_observations), so that one policy
+    can play either side.  opponent None is self-play: obs float32 [N, 22, 224], actions [N, 22, 3], reward [N, 22] (+reward
+    for slots 0..10, its negative for 11..21).  With an in-kernel opponent: obs [N, 11, 224] (the left team only), actions
+    [N, 11, 3], reward [N, 11].  The obs tensor is one buffer, rewritten by every reset() / step().
     """
 
     @staticmethod
-    def spaces(opponent=None):
-        """(observation_space, action_space) of an env with this opponent (no engine needed)."""
+    def spaces(opponent=None, obs='state'):
+        """(observation_space, action_space) of an env with this opponent and observation (no engine needed)."""
         import numpy as np
         from .spaces import Box
         if opponent not in (None, 'random', 'scripted'):
             raise ValueError(f"opponent must be None, 'random' or 'scripted', got {opponent!r}")
-        return (Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32),
-                Box(low=-180.0, high=180.0, shape=(22 if opponent is None else 11, 3), dtype=np.float32))
+        if obs not in ('state', 'agent'):
+            raise ValueError(f"obs must be 'state' or 'agent', got {obs!r}")
+        agents = 22 if opponent is None else 11
+        if obs == 'agent':
+            ospace = Box(low=-1.0e6, high=1.0e6, shape=(agents, M.AGENT_OBS_DIM), dtype=np.float32)
+        else:
+            ospace = Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32)
+        return ospace, Box(low=-180.0, high=180.0, shape=(agents, 3), dtype=np.float32)
 
-    def __init__(self, num_envs, device='cuda:0', opponent=None, **kwargs):
-        self.observation_space, self.action_space = self.spaces(opponent)
+    def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', **kwargs):
+        self.observation_space, self.action_space = self.spaces(opponent, obs)
         self.engine = MatchEngine(num_envs, device, **kwargs)
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
-        self.opponent = opponent
+        self.opponent, self.obs_kind = opponent, obs
         self._ro = self.engine.alloc_rollout(1)
         if opponent is not None:
             self.engine.set_controllers({'left': 'external', 'right': opponent})
             # the caller's half of the action rows; the right team's rows are never read
             self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
+        if obs == 'agent':
+            self._slots = 'all' if opponent is None else 'left'
+            self._aobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
+            # reward sign per agent: the left team's reward for slots 0..10, its negative for 11..21
+            self._rsign = torch.tensor([1.0] * 11 + ([-1.0] * 11 if opponent is None else []), dtype=torch.float32, device=self.device)
 
     def _obs(self):
         e = self.engine
+        if self.obs_kind == 'agent':
+            return e.agent_observations(self._slots, out=self._aobs)
         return torch.stack([e.x[:, :23], e.y[:, :23], e.vx[:, :23], e.vy[:, :23], e.body[:, :23]], dim=2)
 
     def reset(self, mask=None):
@@ -310,6 +343,8 @@ class Soccer2DMatchVecEnv:
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,
                 'right_team_score': e.score_right, 'cycle': e.cycle, 'nearest_left': e.nearest_left, 'nearest_right': e.nearest_right}
+        if self.obs_kind == 'agent':
+            return self._obs(), e.reward_left[:, None] * self._rsign, e.done, info
         return self._ro['obs'][0, :, :23], e.reward_left, e.done, info
 
     def close(self):

@@ -287,6 +287,70 @@ int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float *actions_dev
  * p, degrees; idl/service.proto:84-85, 155-156).  The diagonal (j = p) is 0. */
 int s2d_match_relative(S2DMatchHandle h, float *dist_dev, float *angle_dev, void *stream);
 
+/* Per-agent observations in each team's own frame (the WorldModel / Self / InterceptTable / Player messages every agent reads,
+ * idl/service.proto:144-265, 306-349), from the current state.  A full-state observation: no vision model, no see-message
+ * quantisation.  One row of S2D_AGENT_OBS_DIM float32 words per agent; integers and flags are stored as their float values.
+ *
+ * Own frame.  For agent p of side s (left = slots 0..10, right = 11..21), sgn = +1 left, -1 right:
+ *   every position and velocity is multiplied by sgn (exact); every body direction b becomes
+ *   s == left ? b : (b > 0 ? b - 180 : b + 180); all further arithmetic uses only these own-frame values, so for a mirrored state
+ *   (teams swapped, positions and velocities negated, bodies turned by 180) the rows are bitwise those of the original.
+ *   Distances are hypot2(dx, dy), bearings norm_deg_any(atan2_deg(dy, dx) - body) with the fp32 spec functions (DESIGN.md
+ *   section 4); sq2(x, y) = fmaf(x, x, y * y).  Unum = slot index within the team + 1.  "Active" = card < S2D_CARD_RED.
+ *   "Ours" / "theirs": sides as seen from s; a side word is +1 ours, -1 theirs, 0 none.
+ *
+ * Words (offsets below):
+ *   self [0, 16)       x, y, vx, vy, body, stamina, effort, recovery, stamina_capacity, is_goalie (slot 0 / 11), tackle_cycles,
+ *                      card, is_kickable, kick_rate, catch_ban, PlayerType id
+ *   ball [16, 24)      x, y, vx, vy, dist_from_self, bearing, last_touch (side word), holder (+1 our goalie holds a caught ball,
+ *                      -1 theirs, 0 nobody: S2DMatchBuffers.ball_holder)
+ *   game [24, 48)      game_mode_type, mode side (side word), our_score, their_score, cycle, stopped_cycle,
+ *                      cycles_to_period_end (cycles until the clock reaches the end of the current half or extra half, the
+ *                      engine's countdown), is_penalty_kick_mode, offside_line_x, our_defense_line_x, their_defense_line_x,
+ *                      kickable teammate unum, kickable opponent unum, self reach steps, first teammate reach / unum, second
+ *                      teammate reach / unum, first opponent reach / unum, second opponent reach / unum, is_our_set_play,
+ *                      is_their_set_play
+ *   teammates [48, 136)  11 rows of 8 words in slot order, self included: x, y, vx, vy, body, dist, bearing, reach_steps
+ *   opponents [136, 224) 11 rows of 8 words in slot order, the same words
+ * Definitions:
+ *   is_kickable   sq2(ball - self) <= the slot's kickable bound (the largest float whose root does not exceed its PlayerType's
+ *                 kickable area: the engine's own test); 0 for an inactive agent.
+ *   kick_rate     when kickable: kick_power_rate * (1 - 0.25 * (dir_diff * (1/180)) - 0.25 * (dist_ball / kickable_margin)), in the
+ *                 operation order of the engine's kick (dir_diff = |ball bearing|, dist_ball = sqrtf(sq2) - player_size -
+ *                 ball_size, the division a multiplication by the float of 1/kickable_margin); otherwise 0.
+ *   reach_steps   this project's own estimate, not librcsc's InterceptSimulator (no parity claimed).  The ball runs noise-free,
+ *                 pos += vel; vel *= ball_decay; the player stands still at t = 0 and gains his type's player_speed_max per
+ *                 cycle.  t = 0 hits if sq2(ball - pos) <= the kickable bound; t >= 1 if sq2(ball_t - pos) <= r * r with
+ *                 r = ka + (float)t * speed_max, ka = (float)((float)player_size + (float)ball_size) + (float)kickable_margin.
+ *                 The first t in 0..S2D_AGENT_REACH_MAX, else S2D_AGENT_REACH_NONE; inactive players: NONE.
+ *   first / second teammate / opponent   the two smallest (reach, slot) keys among the active players of that team, self
+ *                 excluded from the teammates; missing ones: reach NONE, unum 0.
+ *   kickable teammate / opponent   unum of the lowest-slot active kickable player of that team other than self; 0 if none.
+ *   offside_line_x  max(0, ball x, second-largest x among the 11 opponents), own frame: the line of the engine's offside rule.
+ *                 As there, the scan covers all 11 opponents, sent-off ones included at their parked place (x = 0 beside the
+ *                 halfway line), and "second-largest" counts equal values twice.
+ *   our_defense_line_x    min(ball x, x of our active non-goalies); their_defense_line_x = max(ball x, x of their active
+ *                 non-goalies); own frame.  (The proto's comment says "minimum" for both; the maximum for theirs is a deliberate
+ *                 choice: in the own frame their last defender is the one with the largest x.)
+ *   is_penalty_kick_mode  the mode is a shoot-out mode: 22, 23, 24, 25, 26, 28 or 29 (IllegalDefense_, 27, is not one).
+ *   is_our_set_play       the mode is KickOff_, KickIn_, FreeKick_, CornerKick_, GoalKick_, IndFreeKick_, GoalieCatch_ or
+ *                 PenaltyKick_ and its side is ours; is_their_set_play: the same with theirs.
+ *   rows of inactive teammates / opponents: 0 except reach = NONE (this includes the agent's own row when he is sent off).
+ *   the agent's own row: dist = 0 and bearing = 0. */
+#define S2D_AGENT_OBS_DIM 224          /* float32 words per agent: 896 B, 14 lines of 64 B */
+#define S2D_AGENT_OBS_SELF 0
+#define S2D_AGENT_OBS_BALL 16
+#define S2D_AGENT_OBS_GAME 24
+#define S2D_AGENT_OBS_TEAMMATES 48
+#define S2D_AGENT_OBS_OPPONENTS 136
+#define S2D_AGENT_OBS_ROW_WORDS 8     /* words of one teammate / opponent row */
+#define S2D_AGENT_REACH_MAX 50
+#define S2D_AGENT_REACH_NONE 51
+/* obs_dev: float[N][popcount(slot_mask)][S2D_AGENT_OBS_DIM], rows in ascending slot order, 16-byte aligned.
+ * slot_mask: bits 0..21 (0x3FFFFF all, 0x7FF the left team).  Reads the current state; writes nothing else.
+ * Errors: a mask with bits above 21, an empty mask, a NULL or unaligned obs_dev. */
+int s2d_match_agent_obs(S2DMatchHandle h, uint32_t slot_mask, float *obs_dev, void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
