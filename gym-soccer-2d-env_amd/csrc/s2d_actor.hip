@@ -1,0 +1,317 @@
+// s2d_actor.hip -- the fused epsilon-greedy Q-network actor (s2d_rollout_qnet, include/s2d.h; DESIGN.md sections 4, 5).
+//
+// The plain rollout kernel (one env per lane, the whole cycle in one wave, T cycles per launch) with the action of every cycle
+// chosen in-kernel from the caller's network  q = W3 relu(W2 relu(W1 x + b1) + b2) + b3  on the env's current observation, and
+// per-env epsilon-greedy exploration.  Reference: DQN("MlpPolicy").predict inside SB3's collect_rollouts,
+// dqn_stable_baselines3.py:36-49.
+//
+// The network runs on the f32-input matrix cores: v_mfma_f32_16x16x4_f32 is bit for bit the k-ordered fmaf chain
+// acc = fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1, fma(a_k0, b_k0, C)))), so a chain of them that starts from C = bias
+// and is fed its k-steps in ascending order is exactly the spec's  acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc).
+// Orientation: A = the weights (rows = output units j, lane l holds W[16 jt + (l & 15)][4 s + (l >> 4)] for k-step s), B = the
+// activations (lane l holds in[env 16 nt + (l & 15)][4 s + (l >> 4)]), D: lane l, register r = unit 16 jt + 4 (l >> 4) + r of env
+// 16 nt + (l & 15).  D is not the next layer's B fragment (that would permute k), so every layer's output goes through LDS:
+// each lane writes its four units as one 16-byte store into [env][unit] rows and the next layer reads single words in k order.
+// A wave works through its 64 envs as four tiles of 16.  Layer 1 reads the observation tile ([64][10], k = 10, 11 read as
+// zero against zero weights: fmaf(0, 0, acc) can only turn -0 into +0, which relu maps to +0 anyway).
+// The weights are repacked once per launch into fragment order in LDS (each fragment = 64 consecutive words, conflict-free
+// reads); the parameter buffer and epsilon are read when the kernel runs, so a captured graph acts with what they hold at replay.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <mutex>
+
+#include "s2d_kernels.h"
+
+// experiment build (-DS2D_QNET_STAMPS, profiles/experiments/qnet_actor_clocks.py): per wave, the shader clocks (s_memtime) of the
+// network (observation tile + three layers + argmax), of the rest of the cycle (action draw, simulation, record stores) and of the
+// prologue, summed over the launch; lane 0 writes them as floats into terminal_obs row wave_first of the arena
+#ifdef S2D_QNET_STAMPS
+#define QS_DECL uint64_t qs_net = 0, qs_rest = 0, qs_t = __builtin_amdgcn_s_memtime(); const uint64_t qs_begin = qs_t; uint64_t qs_pro = 0
+#define QS_MARK(acc) do { const uint64_t qs_now = __builtin_amdgcn_s_memtime(); acc += qs_now - qs_t; qs_t = qs_now; } while (0)
+#define QS_STORE() do { if (lane == 0) { float* q_ = o.terminal_obs + wave_first * S2D_OBS_DIM; q_[0] = (float)qs_net; \
+    q_[1] = (float)qs_rest; q_[2] = (float)qs_pro; q_[3] = (float)(__builtin_amdgcn_s_memtime() - qs_begin); } } while (0)
+#else
+#define QS_DECL do {} while (0)
+#define QS_MARK(acc) do {} while (0)
+#define QS_STORE() do {} while (0)
+#endif
+
+typedef float v4f_t __attribute__((ext_vector_type(4)));
+
+struct QNetDims {
+  int h1, h2, na;        // hidden widths (multiples of 16, 16 .. 128), actions (1 .. 64)
+  int na16;              // actions rounded up to 16 (rows of layer 3's tiles; the padding rows have zero weights and bias)
+  int pitch;             // LDS row pitch of the hidden-activation images (words): max width rounded up to 64, + 4
+  int qpitch;            // LDS row pitch of the Q-value image: na16 + 4
+};
+// LDS layout, in floats: [W1 frags | W2 frags | W3 frags | b1 | b2 | b3 (na16)] shared by the block, then per wave
+// [hA 16 x pitch | hB 16 x pitch | q 64 x qpitch | obs tile 640 | PrepTile]
+S2D_DEV int w1_frags(const QNetDims& d) { return (d.h1 / 16) * 3; }
+S2D_DEV int w2_frags(const QNetDims& d) { return (d.h2 / 16) * (d.h1 / 4); }
+S2D_DEV int w3_frags(const QNetDims& d) { return (d.na16 / 16) * (d.h2 / 4); }
+
+// J output tiles (jt0 .. jt0 + J - 1) of one layer for one 16-env tile: out[c][j] (LDS, pitch `op`) = (relu)(b[j] + sum_k W[j][k]
+// in[k]) for the tile's 16 envs c.  in_frag(s) = this lane's B word of k-step s.  J independent accumulators keep the matrix pipe
+// issuing (dependent latency 40 cycles against a 32-cycle issue); the k-steps go in groups of KU whose LDS reads are issued together.
+// All 64 lanes take part (MFMA).
+template <bool RELU, int J, int KU, typename InFrag>
+S2D_DEV void layer_group(const float* __restrict__ wf, const float* __restrict__ bias, int jt0, int ksteps, InFrag in_frag,
+                         float* __restrict__ out, int op, int lane) {
+  const int g = lane >> 4, c = lane & 15;
+  v4f_t acc[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const float4 b4 = *reinterpret_cast<const float4*>(bias + 16 * (jt0 + j) + 4 * g);
+    acc[j] = v4f_t{b4.x, b4.y, b4.z, b4.w};
+  }
+  for (int s0 = 0; s0 < ksteps; s0 += KU) {
+    float b[KU], w[J][KU];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      b[u] = in_frag(s0 + u);
+#pragma unroll
+      for (int j = 0; j < J; ++j) w[j][u] = wf[((jt0 + j) * ksteps + s0 + u) * kWave + lane];
+    }
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+#pragma unroll
+      for (int j = 0; j < J; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u], b[u], acc[j], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    if (RELU) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[j][r] = acc[j][r] > 0.0f ? acc[j][r] : 0.0f;   // relu: NaN and -0 -> +0
+    }
+    *reinterpret_cast<float4*>(out + c * op + 16 * (jt0 + j) + 4 * g) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+  }
+}
+// all m16 output tiles of one layer, four (then two, then one) at a time
+template <bool RELU, int KU, typename InFrag>
+S2D_DEV void layer_tile(const float* __restrict__ wf, const float* __restrict__ bias, int m16, int ksteps, InFrag in_frag,
+                        float* __restrict__ out, int op, int lane) {
+  int jt = 0;
+  for (; jt + 4 <= m16; jt += 4) layer_group<RELU, 4, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
+  if (jt + 2 <= m16) { layer_group<RELU, 2, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane); jt += 2; }
+  if (jt < m16) layer_group<RELU, 1, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
+}
+
+// greedy action of every env of the wave (lane = env): the network on the observation tile, then the spec's argmax scan
+S2D_DEV int qnet_greedy(const QNetDims& d, const float* __restrict__ wl, float* __restrict__ ha, float* __restrict__ hb,
+                        float* __restrict__ qv, const float* __restrict__ obs_tile, int lane) {
+  const int g = lane >> 4, c = lane & 15;
+  const float* w1 = wl;
+  const float* w2 = w1 + w1_frags(d) * kWave;
+  const float* w3 = w2 + w2_frags(d) * kWave;
+  const float* b1 = w3 + w3_frags(d) * kWave;
+  const float* b2 = b1 + d.h1;
+  const float* b3 = b2 + d.h2;
+  for (int nt = 0; nt < 4; ++nt) {
+    const float* x = obs_tile + (16 * nt + c) * S2D_OBS_DIM;
+    layer_tile<true, 3>(w1, b1, d.h1 / 16, 3, [&](int s) { const int k = 4 * s + g; return k < S2D_OBS_DIM ? x[k] : 0.0f; },
+                     ha, d.pitch, lane);
+    wave_lds_fence();
+    layer_tile<true, 4>(w2, b2, d.h2 / 16, d.h1 / 4, [&](int s) { return ha[c * d.pitch + 4 * s + g]; }, hb, d.pitch, lane);
+    wave_lds_fence();
+    layer_tile<false, 4>(w3, b3, d.na16 / 16, d.h2 / 4, [&](int s) { return hb[c * d.pitch + 4 * s + g]; },
+                      qv + 16 * nt * d.qpitch, d.qpitch, lane);
+    wave_lds_fence();
+  }
+  // best = 0; for a = 1 .. A-1: if (q[a] > q[best]) best = a   (ties: lowest index; a NaN never replaces the best)
+  const float* q = qv + lane * d.qpitch;
+  int best = 0;
+  float bv = q[0];
+  for (int a = 1; a < d.na; ++a) {
+    const float v = q[a];
+    if (v > bv) { bv = v; best = a; }
+  }
+  wave_lds_fence();
+  return best;
+}
+
+// exploration threshold of a device epsilon: eps >= 1 -> 2^32, eps > 0 -> (uint64)(eps 2^32), else (0, -x, NaN) 0
+S2D_DEV uint64_t explore_threshold(float eps) {
+  return eps >= 1.0f ? (1ull << 32) : eps > 0.0f ? (uint64_t)(eps * 4294967296.0f) : 0ull;
+}
+
+template <int NK>
+__global__ __launch_bounds__(kBlock) void s2d_reach_qnet_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
+                                                                        float* __restrict__ S, int64_t stride, int64_t n,
+                                                                        int n_steps, QNetDims d, const float* __restrict__ params,
+                                                                        const float* __restrict__ eps_dev, RolloutOut ro,
+                                                                        float* __restrict__ term_rec, StepOut o, int wave_words) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  QS_DECL;
+  const S2DHot p = hot_in_vgprs(p_sgpr);
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+
+  // ---- the network in fragment order (block-wide, once per launch)
+  const int f1 = w1_frags(d), f2 = w2_frags(d), f3 = w3_frags(d);
+  const int nfrag = f1 + f2 + f3;
+  const int o_b1 = 10 * d.h1, o_w2 = o_b1 + d.h1, o_b2 = o_w2 + d.h2 * d.h1, o_w3 = o_b2 + d.h2, o_b3 = o_w3 + d.na * d.h2;
+  for (int idx = threadIdx.x; idx < nfrag * kWave; idx += blockDim.x) {
+    const int f = idx / kWave, l = idx & (kWave - 1);
+    const int row = l & 15, kk = l >> 4;
+    float v = 0.0f;
+    if (f < f1) {
+      const int jt = f / 3, s = f - 3 * jt, k = 4 * s + kk;
+      if (k < S2D_OBS_DIM) v = params[(16 * jt + row) * S2D_OBS_DIM + k];
+    } else if (f < f1 + f2) {
+      const int g2 = f - f1, ks = d.h1 / 4, jt = g2 / ks, s = g2 - jt * ks;
+      v = params[o_w2 + (16 * jt + row) * d.h1 + 4 * s + kk];
+    } else {
+      const int g3 = f - f1 - f2, ks = d.h2 / 4, jt = g3 / ks, s = g3 - jt * ks, j = 16 * jt + row;
+      if (j < d.na) v = params[o_w3 + j * d.h2 + 4 * s + kk];
+    }
+    smem[idx] = v;
+  }
+  float* const bias = smem + nfrag * kWave;
+  for (int j = threadIdx.x; j < d.h1 + d.h2 + d.na16; j += blockDim.x) {
+    float v;
+    if (j < d.h1) v = params[o_b1 + j];
+    else if (j < d.h1 + d.h2) v = params[o_b2 + j - d.h1];
+    else v = (j - d.h1 - d.h2 < d.na) ? params[o_b3 + j - d.h1 - d.h2] : 0.0f;
+    bias[j] = v;
+  }
+  const int shared_words = (nfrag * kWave + d.h1 + d.h2 + d.na16 + 3) & ~3;
+  float* const wbase = smem + shared_words + wv * wave_words;
+  float* const ha = wbase;
+  float* const hb = ha + 16 * d.pitch;
+  float* const qv = hb + 16 * d.pitch;
+  float* const tile = qv + kWave * d.qpitch;
+  PrepTile* const prep = reinterpret_cast<PrepTile*>(tile + kObsTile);
+  __syncthreads();
+  if (wave_first >= n) return;
+
+  const bool active = i < n;
+  int64_t rows = n - wave_first; if (rows > kWave) rows = kWave;
+  const int valid = (int)rows * S2D_OBS_DIM;
+  const uint64_t thr = explore_threshold(*eps_dev);
+  uint32_t* const kplane = reinterpret_cast<uint32_t*>(S + F_POLICY * stride);
+  Env e;
+  uint32_t gl = 0, gh = 0, k0 = 0;
+  ObsOut ob;
+#pragma unroll
+  for (int k = 0; k < S2D_OBS_DIM; ++k) ob.o[k] = 0.0f;
+  if (active) {
+    env_load(e, S, stride, i);
+    k0 = kplane[i];
+    uint64_t gid = (((uint64_t)p.gid_hi << 32) | p.gid_lo) + (uint64_t)i;
+    gl = (uint32_t)gid; gh = (uint32_t)(gid >> 32);
+    observe(p, e.px, e.py, e.body, e.bx, e.by, e.bvx, e.bvy, ob);   // what the last step / reset returned for this state
+  }
+  float reward = 0.0f, dir = 0.0f; int done = 0, res = 0, cmd = 0;
+  unsigned int cnt1 = 0, cnt2 = 0, cnt3 = 0;
+  float* const term_row = o.terminal_obs + i * S2D_OBS_DIM;
+  U4 quad{0, 0, 0, 0}, equad{0, 0, 0, 0}, squad{0, 0, 0, 0};
+  bool have_prep = false;
+  uint32_t* const coop_scratch = reinterpret_cast<uint32_t*>(tile);
+  if (p.auto_reset) {
+    prep_fill_coop<NK>(p, rp, *prep, lane, active ? reset_key(e) : 0u, gl, gh, active, coop_scratch);
+    have_prep = active;
+  }
+  int n_missing = 0;
+  int64_t row = 0;
+  QS_MARK(qs_pro);
+  for (int t = 0; t < n_steps; ++t, row += n) {
+    res = 0;
+    if (n_missing >= kRefillMin) {
+      if (active && !have_prep) { prep_fill<NK>(p, rp, *prep, lane, e, gl, gh); have_prep = true; }
+      n_missing = 0;
+    }
+    // the action of step t from the observation returned by step t - 1 (the launch's start state at t = 0)
+    wave_lds_fence();
+    tile_write(tile, ob, lane, active);
+    wave_lds_fence();
+    const int greedy = qnet_greedy(d, smem, ha, hb, qv, tile, lane);
+    QS_MARK(qs_net);
+    if (active) {
+      const uint32_t k = k0 + (uint32_t)t;
+      if (t == 0 || (k & 3u) == 0u) {
+        quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);                      // block 0: S2D_ACT_RANDOM's draw
+        equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
+      }
+      const bool explore = (uint64_t)quad_word(equad, k) < thr;
+      const int a = explore ? rnd_below(quad_word(quad, k), (uint32_t)p.n_actions) : greedy;
+      if (ro.action) static_cast<int32_t*>(ro.action)[row + i] = a;
+      const CmdPrep c = decode_action<S2D_MODE_DISCRETE>(p, Action4{(float)a, 0.0f, 0.0f, 0.0f}, gl, gh, k, false, squad, cmd, dir);
+      step_env<NK, false>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, prep, lane, have_prep);
+      if (ro.reward) ro.reward[row + i] = reward;
+      if (ro.done) ro.done[row + i] = (uint8_t)done;
+      if (ro.result) ro.result[row + i] = (uint8_t)res;
+      if (term_rec && done) {                              // the observation the finished episode ended on
+        float* const dst = term_rec + (row + i) * S2D_OBS_DIM;
+#pragma unroll
+        for (int k2 = 0; k2 < S2D_OBS_DIM; ++k2) dst[k2] = p.auto_reset ? term_row[k2] : ob.o[k2];
+      }
+      cnt1 += res == S2D_RESULT_GOAL; cnt2 += res == S2D_RESULT_OUT; cnt3 += res == S2D_RESULT_TIMEOUT;
+    }
+    if (p.auto_reset) n_missing += __popcll(__ballot(active && done != 0));
+    if (ro.obs) store_obs_tile(tile, ob, lane, active, ro.obs + (row + wave_first) * S2D_OBS_DIM, valid);
+    QS_MARK(qs_rest);
+  }
+  if (active) {
+    env_store(e, S, stride, i);
+    kplane[i] = k0 + (uint32_t)n_steps;
+    o.reward[i] = reward; o.done[i] = (uint8_t)done; o.result[i] = (uint8_t)res;
+    o.action_dir[i] = dir; o.action_cmd[i] = (uint8_t)cmd;
+  }
+  store_obs_tile(tile, ob, lane, active, o.obs + wave_first * S2D_OBS_DIM, valid);
+  if (!active) { cnt1 = cnt2 = cnt3 = 0; }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt1 += __shfl_xor(cnt1, off); cnt2 += __shfl_xor(cnt2, off); cnt3 += __shfl_xor(cnt3, off);
+  }
+  unsigned long long* const srow = stats_row(o.stats, wave_first);
+  stats_store(srow, lane, stats_load(srow, lane), wave_first == 0 ? (unsigned long long)n * (unsigned long long)n_steps : 0ull, cnt1, cnt2, cnt3);
+  QS_STORE();
+}
+
+// host side (same library, hidden symbol; the C entry point and its argument checks are in s2d_engine.hip)
+static constexpr size_t kLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all of it available to one workgroup
+static constexpr int kMaxDevices = 64;
+extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
+                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
+                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name) {
+  QNetDims d;
+  d.h1 = h1; d.h2 = h2; d.na = na; d.na16 = (na + 15) / 16 * 16;
+  const int wmax = h1 > h2 ? h1 : h2;
+  d.pitch = (wmax + 63) / 64 * 64 + 4;
+  d.qpitch = d.na16 + 4;
+  const int nfrag = (h1 / 16) * 3 + (h2 / 16) * (h1 / 4) + (d.na16 / 16) * (h2 / 4);
+  const size_t shared_words = ((size_t)nfrag * kWave + h1 + h2 + d.na16 + 3) & ~(size_t)3;
+  const int wave_words = 2 * 16 * d.pitch + kWave * d.qpitch + kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
+  int waves = kWavesPerBlock;                              // as many waves per workgroup as the LDS holds (4 for 10-64-64-16)
+  while (waves > 1 && (shared_words + (size_t)waves * wave_words) * sizeof(float) > kLdsMax) waves /= 2;
+  const size_t lds = (shared_words + (size_t)waves * wave_words) * sizeof(float);
+  if (lds > kLdsMax) return -1;
+  using K = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut, float*,
+                     StepOut, int);
+  static const K table[3] = {s2d_reach_qnet_rollout_kernel<S2D_NK_OFF>, s2d_reach_qnet_rollout_kernel<S2D_NK_LATTICE>,
+                             s2d_reach_qnet_rollout_kernel<S2D_NK_SQUARE>};
+  // the dynamic-LDS limit is a per-device property of the function: set it once per (device, noise kind), under a lock (engines on
+  // several devices may be driven from several threads); the caller has made the engine's device current
+  static std::mutex attr_mu;
+  static bool attr_set[kMaxDevices][3] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -2;
+  {
+    std::lock_guard<std::mutex> lock(attr_mu);
+    if (!attr_set[dev][nk]) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(table[nk]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) !=
+          hipSuccess)
+        return -2;
+      attr_set[dev][nk] = true;
+    }
+  }
+  const int threads = waves * kWave;
+  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
+  hipLaunchKernelGGL(table[nk], dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n,
+                     n_steps, d, params, eps, *ro, term_rec, *o, wave_words);
+  if (name) std::snprintf(name, 96, "s2d_reach_qnet_rollout_kernel<noise=%d,h1=%d,h2=%d,a=%d,waves=%d>", nk, h1, h2, na, waves);
+  return 0;
+}

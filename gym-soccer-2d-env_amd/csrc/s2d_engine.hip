@@ -7,7 +7,8 @@
 // wave-private LDS tile and stores 2560 contiguous bytes with 16-byte-per-lane stores.
 // One thread = one env; there is no cross-env communication, so the only cross-lane work is
 // the LDS transposition and the ballot/popcount reduction of the episode counters.
-// No MFMA: the path has no dense contraction (arithmetic intensity ~0.5 flop/byte).
+// No MFMA in the simulation: it has no dense contraction (arithmetic intensity ~0.5 flop/byte); the optional policy network
+// of s2d_rollout_qnet (s2d_actor.hip) uses f32 MFMA.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -1036,6 +1037,11 @@ extern "C" int s2d_internal_rollout2(int mode, int noise, const S2DHot* hot, con
                                      int64_t n, int n_steps, const void* actions_dev, int kind, const RolloutOut* ro,
                                      const StepOut* o, void* stream, char* name);
 
+// s2d_actor.hip (same library, hidden symbol): launches the Q-network actor rollout (0, or < 0 if the network does not fit LDS)
+extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
+                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
+                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name);
+
 struct S2DEngine {
   S2DConfig cfg;
   S2DHot hot;
@@ -1494,6 +1500,40 @@ S2D_API int s2d_rollout(S2DHandle h, int n_steps, const void* actions_dev, int a
                      ro, h->out);
   HIP_TRY(hipGetLastError());
   std::snprintf(h->kernel_name, sizeof h->kernel_name, "s2d_reach_rollout_kernel<%s,noise=%d>", mode_names[h->mode], h->nk);
+  h->last_kernel = h->kernel_name;
+  return S2D_OK;
+}
+
+S2D_API int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet* net, const S2DRollout* out, float* terminal_obs,
+                             void* stream) {
+  if (!h) return fail(S2D_EINVAL, "NULL handle");
+  if (!net) return fail(S2D_EINVAL, "s2d_rollout_qnet: net is NULL");
+  const S2DReachBallParams& t = h->cfg.task;
+  if (t.use_continuous_action) return fail(S2D_EINVAL, "s2d_rollout_qnet needs a discrete-action engine (use_continuous_action = 0)");
+  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_qnet: n_steps must be >= 1");
+  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
+  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: hidden widths must be multiples of 16 in [16, 128]");
+  if (net->n_actions < 1 || net->n_actions > 64 || net->n_actions != t.action_space_size)
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: n_actions must equal action_space_size and be in [1, 64]");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: epsilon must be a non-NULL, 4-byte aligned device pointer");
+  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_qnet: terminal_obs must be 4-byte aligned");
+  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (out) {
+    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
+    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->action) & 3u) return fail(S2D_EINVAL, "rollout action buffer must be 4-byte aligned");
+  }
+  DeviceGuard guard(h->device);
+  const int rc = s2d_internal_rollout_qnet(h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
+                                           n_steps, net->hidden1, net->hidden2, net->n_actions, net->params, net->epsilon, &ro,
+                                           terminal_obs, &h->out, stream, h->kernel_name);
+  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_qnet: the network does not fit the LDS of a workgroup");
+  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_qnet: hipGetDevice or hipFuncSetAttribute failed");
+  HIP_TRY(hipGetLastError());
   h->last_kernel = h->kernel_name;
   return S2D_OK;
 }

@@ -8,6 +8,10 @@ directly: observations never leave HBM, the replay buffer is a device tensor, on
 feeds N transitions.
 
     python examples/dqn_reach_ball.py --envs 4096 --iters 10 --train-steps 200 --test-steps 250
+
+--fused-actor T collects T x N transitions per launch: the engine evaluates the learner's own network in-kernel
+(Engine.rollout_qnet with a soccer2d_amd.actor.QNetActor), epsilon-greedy per env; the actor's packed weights are refreshed
+with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal observations.
 """
 import argparse
 import copy
@@ -114,6 +118,46 @@ class DeviceDQN:
             if self.steps % self.target_every == 0:
                 self.q_target.load_state_dict(self.q.state_dict())
 
+    def optimise(self, n_updates):
+        for _g in range(n_updates):
+            o, a, r, no, t = self.rb.sample(self.batch)
+            with torch.no_grad():
+                tgt = r + self.gamma * (1 - t) * self.q_target(no).max(dim=1).values
+            loss = nn.functional.smooth_l1_loss(self.q(o).gather(1, a.unsqueeze(1)).squeeze(1), tgt)
+            self.opt.zero_grad(set_to_none=True)
+            loss.backward()
+            nn.utils.clip_grad_norm_(self.q.parameters(), 10.0)
+            self.opt.step()
+
+    def learn_fused(self, vec_steps, T, on_result=None):
+        """The same DQN, experience collected T steps per launch by the fused actor (the learner's own network in-kernel):
+        per launch T x N transitions into the replay buffer, then grad_steps updates per collected vector step, then sync()."""
+        from soccer2d_amd.actor import QNetActor
+        if not hasattr(self, 'actor'):
+            self.actor = QNetActor.from_module(self.q, device=self.dev, epsilon=self.epsilon())
+            self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
+        eng, rec = self.env.engine, self.rec
+        for _ in range((vec_steps + T - 1) // T):
+            self.actor.epsilon = self.epsilon()
+            obs0 = eng.obs.clone()                               # the observation the first action is chosen from
+            self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
+            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
+            done = rec['done'].bool()
+            next_obs = torch.where(done.unsqueeze(-1), rec['terminal_obs'], rec['obs'])   # bootstrap through Timeouts
+            term = ((rec['result'] == 1) | (rec['result'] == 2)).float()                 # Goal / Out are true terminations
+            self.rb.add(obs_t.reshape(-1, obs_t.shape[-1]), rec['action'].reshape(-1).long(), rec['reward'].reshape(-1),
+                        next_obs.reshape(-1, next_obs.shape[-1]), term.reshape(-1))
+            if on_result is not None:
+                on_result(rec['result'].reshape(-1))
+            for _t in range(T):
+                self.steps += 1
+                if self.steps % self.target_every == 0:
+                    self.q_target.load_state_dict(self.q.state_dict())
+            if self.rb.full or self.rb.pos >= self.batch:
+                self.optimise(self.grad_steps * T)
+                self.actor.sync()                                # the next launch acts with the new weights
+        self.obs = eng.obs.clone()
+
 
 def test(env, model, vec_steps):
     """dqn_stable_baselines3.py:44-62 -- greedy policy, count info['result'] of finished episodes."""
@@ -142,6 +186,8 @@ def main():
     ap.add_argument('--train-steps', type=int, default=200)
     ap.add_argument('--test-steps', type=int, default=250)
     ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
+                    help='collect T steps per launch with the in-kernel epsilon-greedy actor (0: one torch forward per step)')
     args = ap.parse_args()
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
@@ -149,7 +195,10 @@ def main():
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()
-        model.learn(args.train_steps)
+        if args.fused_actor > 0:
+            model.learn_fused(args.train_steps, args.fused_actor)
+        else:
+            model.learn(args.train_steps)
         torch.cuda.synchronize()
         dt = time.time() - t0
         r = test(test_env, model, args.test_steps)

@@ -99,6 +99,12 @@ class S2DRollout(C.Structure):
                 ('done', C.c_void_p), ('result', C.c_void_p)]
 
 
+class S2DQNet(C.Structure):
+    """the caller's Q-network of s2d_rollout_qnet (widths, device pointers of the packed parameters and of epsilon)"""
+    _fields_ = [('hidden1', C.c_int32), ('hidden2', C.c_int32), ('n_actions', C.c_int32), ('reserved', C.c_int32),
+                ('params', C.c_void_p), ('epsilon', C.c_void_p)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -126,6 +132,7 @@ PROTOTYPES = (
     ('s2d_step', C.c_int, (C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)),
     ('s2d_rollout', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
     ('s2d_step_k', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
+    ('s2d_rollout_qnet', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DQNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

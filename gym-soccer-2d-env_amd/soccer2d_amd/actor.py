@@ -1,0 +1,115 @@
+"""QNetActor: the device-side state of the fused epsilon-greedy actor (Engine.rollout_qnet, s2d_rollout_qnet in include/s2d.h).
+
+It owns ONE packed fp32 parameter buffer in torch's ``nn.Sequential(Linear, ReLU, Linear, ReLU, Linear).parameters()`` order
+(W1[H1][10], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A]) and a device epsilon scalar.  The kernel reads both when it runs, so a
+learner updates them in place (``sync()`` after an optimiser phase, ``epsilon = ...``) and a captured graph acts with the new
+values at its next replay.  SB3's ``DQN.q_net.q_net`` (an nn.Sequential of that shape) qualifies as the source module.
+"""
+import ctypes as C
+
+import torch
+
+from . import _capi
+
+OBS_DIM = _capi.S2D_OBS_DIM
+WIDTHS = tuple(range(16, 129, 16))
+MAX_ACTIONS = 64
+
+
+_NO_OPS = (torch.nn.Identity, torch.nn.Flatten)   # SB3's features extractor of a flat Box observation is a Flatten
+
+
+def _linears(module):
+    """The three nn.Linear layers of a Linear-ReLU-Linear-ReLU-Linear module (the form the kernel evaluates), in order.
+    Leaf modules are read in registration order; Identity / Flatten are skipped; anything else (another activation, a missing
+    ReLU, a fourth layer) is rejected: the kernel would silently act with a different function."""
+    leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
+    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU) else type(m).__name__
+             for m in leaves]
+    if kinds != ['Linear', 'ReLU', 'Linear', 'ReLU', 'Linear']:
+        raise ValueError(f'the Q-network must be Linear-ReLU-Linear-ReLU-Linear (10 -> H1 -> H2 -> A), got {"-".join(kinds) or "nothing"}')
+    return [leaves[0], leaves[2], leaves[4]]
+
+
+def param_count(hidden1, hidden2, n_actions):
+    return OBS_DIM * hidden1 + hidden1 + hidden1 * hidden2 + hidden2 + n_actions * hidden2 + n_actions
+
+
+class QNetActor:
+    """Packed parameters + device epsilon of a 10-H1-H2-A ReLU MLP for Engine.rollout_qnet."""
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05):
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in WIDTHS:
+                raise ValueError(f'{name} must be a multiple of 16 in [16, 128], got {w}')
+        if not 1 <= int(n_actions) <= MAX_ACTIONS:
+            raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
+        self.hidden1, self.hidden2, self.n_actions = int(hidden1), int(hidden2), int(n_actions)
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        # torch's device allocations are 256-byte aligned (the ABI asks for 16)
+        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32, device=self.device)
+        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._eps_value = None
+        self.epsilon = epsilon
+        self._module = None
+
+    @classmethod
+    def from_module(cls, module, device=None, epsilon=0.05):
+        """An actor shaped like `module` (three nn.Linear layers 10 -> H1 -> H2 -> A), loaded from it."""
+        l1, l2, l3 = _linears(module)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon)
+        actor.load_from(module)
+        return actor
+
+    def shapes(self):
+        h1, h2, a = self.hidden1, self.hidden2, self.n_actions
+        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
+
+    def load_from(self, module):
+        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
+        layers = _linears(module)
+        got = []
+        for lin in layers:
+            if lin.bias is None:
+                raise ValueError('every nn.Linear of the Q-network needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if tuple(got) != self.shapes():
+            raise ValueError(f'Q-network shapes {got} do not match the actor {list(self.shapes())}')
+        self._module = module
+        self.sync()
+        return self
+
+    def sync(self):
+        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
+        if self._module is None:
+            raise ValueError('no module loaded (load_from)')
+        srcs = []
+        for lin in _linears(self._module):
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+        return self
+
+    @property
+    def epsilon(self):
+        return self._eps_value
+
+    @epsilon.setter
+    def epsilon(self, value):
+        """Written in place into the device scalar the kernel reads (stream-ordered on torch's current stream)."""
+        self._eps_value = float(value)
+        self._eps.fill_(self._eps_value)
+
+    @property
+    def epsilon_tensor(self):
+        return self._eps
+
+    def c_struct(self):
+        net = _capi.S2DQNet()
+        net.hidden1, net.hidden2, net.n_actions, net.reserved = self.hidden1, self.hidden2, self.n_actions, 0
+        net.params = self.params.data_ptr()
+        net.epsilon = self._eps.data_ptr()
+        return net

@@ -213,6 +213,52 @@ class Engine:
         self._keep = (keep, out)
         return out
 
+    _QNET_RECORD = {'obs': (torch.float32, (S2D_OBS_DIM,)), 'action': (torch.int32, ()), 'reward': (torch.float32, ()),
+                    'done': (torch.uint8, ()), 'result': (torch.uint8, ()), 'terminal_obs': (torch.float32, (S2D_OBS_DIM,))}
+
+    def rollout_qnet(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
+        """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.QNetActor) epsilon-greedy choices on
+        the envs' own observations, evaluated in-kernel (s2d_rollout_qnet; discrete-action engines).  Returns the record dict of
+        rollout() (action int32 [T,N]); with terminal_obs=True (or a caller `out` holding 'terminal_obs') also float32 [T,N,10],
+        written only where done.  The actor's buffers are read when the kernel runs: a captured graph acts with the weights and
+        epsilon they hold at replay.  `out` pointer blocks are cached as in rollout()."""
+        T, n = int(n_steps), self.num_envs
+        if T < 1:
+            raise ValueError('rollout_qnet needs n_steps >= 1')
+        net = actor.c_struct()
+        if actor.device != self.device:
+            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        fresh = out is None
+        if fresh:
+            out = self.alloc_rollout(T, with_obs=with_obs, terminal_obs=terminal_obs)
+        names = ('obs', 'action', 'reward', 'done', 'result', 'terminal_obs')
+        cached = None if fresh else self._ro_cache.get(('qnet', id(out)))
+        key = tuple(None if out.get(k) is None else out[k].data_ptr() for k in names)
+        if cached is None or cached[0] != key or cached[1] < T:
+            ro = _capi.S2DRollout()
+            t_min = None
+            for name in names:
+                v = out.get(name)
+                if v is not None:
+                    dt, trail = self._QNET_RECORD[name]
+                    if (v.dtype != dt or not v.is_contiguous() or v.device != self.device or v.dim() != 2 + len(trail)
+                            or v.shape[0] < T or v.shape[1] != n or tuple(v.shape[2:]) != trail):
+                        raise ValueError(f"rollout_qnet buffer {name!r} must be a contiguous {dt} [T>={T},{n}"
+                                         f"{''.join(',' + str(d) for d in trail)}] tensor on {self.device}")
+                    if name != 'terminal_obs':
+                        setattr(ro, name, v.data_ptr())
+                    t_min = v.shape[0] if t_min is None else min(t_min, v.shape[0])
+            term = out.get('terminal_obs')
+            cached = (key, T if t_min is None else t_min, ro, out, None if term is None else C.c_void_p(term.data_ptr()))
+            if not fresh:
+                if len(self._ro_cache) >= 16:
+                    self._ro_cache.clear()
+                self._ro_cache[('qnet', id(out))] = cached
+        rc = self.lib.s2d_rollout_qnet(self._h, T, C.byref(net), C.byref(cached[2]), cached[4], self._stream())
+        _capi.check(self.lib, rc, 's2d_rollout_qnet')
+        self._keep = (actor, out)
+        return out
+
     def step_k(self, k, actions=None, out=None):
         """k cycles of the per-step API in ONE launch (s2d_step_k; 1 <= k <= 64): for a learner that holds its actions for k steps
         ahead (action repeat, open-loop chunks).  actions [k, N, ...] as for rollout() (None = in-kernel random policy); returns the
@@ -232,11 +278,12 @@ class Engine:
         self._keep = (keep, out)
         return out
 
-    def alloc_rollout(self, T, with_obs=True, slab=False, fields=None):
+    def alloc_rollout(self, T, with_obs=True, slab=False, fields=None, terminal_obs=False):
         """Caller-owned rollout buffers for `rollout(..., out=)`.  slab=True carves the fields out of ONE contiguous
         uint8 tensor (256-byte aligned fields; returned under the key '_slab'), so that a rollout record travels in a
         single collective (dist.all_gather_rollout) without a packing copy: the kernel writes straight into the slab.
-        fields (with slab=True): the names that go into the slab -- what travels --; the others are plain local tensors."""
+        fields (with slab=True): the names that go into the slab -- what travels --; the others are plain local tensors.
+        terminal_obs=True adds float32 [T,N,10] 'terminal_obs' (rollout_qnet's record of the observations episodes ended on)."""
         n, t, dev = self.num_envs, self.cfg.task, self.device
         slab_fields = None if fields is None else set(fields)
         if slab_fields is not None and not slab:
@@ -244,6 +291,8 @@ class Engine:
         act_dt, act_trail = (torch.int32, ()) if not t.use_continuous_action else (torch.float32, (4 if t.use_turning else 1,))
         fields = [('obs', torch.float32, (S2D_OBS_DIM,))] if with_obs else []
         fields += [('action', act_dt, act_trail), ('reward', torch.float32, ()), ('done', torch.uint8, ()), ('result', torch.uint8, ())]
+        if terminal_obs:
+            fields.append(('terminal_obs', torch.float32, (S2D_OBS_DIM,)))
         if not slab:
             out = {name: torch.empty((T, n) + trail, dtype=dt, device=dev) for name, dt, trail in fields}
             out.setdefault('obs', None)

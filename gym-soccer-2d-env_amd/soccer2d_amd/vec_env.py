@@ -54,7 +54,15 @@ class Soccer2DVecEnv:
             info = {k: v.clone() for k, v in info.items()}
         return obs, reward, done, info
 
-    def rollout(self, n_steps, actions=None, out=None, with_obs=True):
+    def rollout(self, n_steps, actions=None, out=None, with_obs=True, policy=None, terminal_obs=False):
+        """T fused steps.  policy=None: `actions` (or the in-kernel random policy); policy=QNetActor: the actor's epsilon-greedy
+        actions, evaluated in-kernel (Engine.rollout_qnet; terminal_obs=True records the observations episodes ended on)."""
+        if policy is not None:
+            if actions is not None:
+                raise ValueError('give either actions or policy, not both')
+            return self.engine.rollout_qnet(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
+        if terminal_obs:
+            raise ValueError('terminal_obs=True records the fused actor\'s terminal observations: it needs policy=QNetActor')
         return self.engine.rollout(n_steps, actions=actions, out=out, with_obs=with_obs)
 
     def render(self, mode='human'):      # soccer_2d_env.py:271-278: no-op

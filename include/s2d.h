@@ -14,6 +14,8 @@
  *                              + ReachBallEnv hooks              reach_ball_env.py:53-161
  *   s2d_rollout                SB3 collect_rollouts loop over step()  dqn_stable_baselines3.py:41-55
  *                              (T fused steps, random policy or caller actions)
+ *   s2d_rollout_qnet           DQN("MlpPolicy").predict inside SB3's collect_rollouts  dqn_stable_baselines3.py:36-49
+ *                              (T fused steps, epsilon-greedy actions of the caller's Q-network, in-kernel)
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -179,6 +181,17 @@ typedef struct S2DRollout {
   uint8_t *result;   /* [T][N] */
 } S2DRollout;
 
+/* The caller's Q-network for s2d_rollout_qnet (DESIGN.md sections 4, 5): q = W3 relu(W2 relu(W1 x + b1) + b2) + b3 on the
+ * env's 10-word observation x.  hidden1 / hidden2 in {16, 32, ..., 128}; n_actions = task.action_space_size, 1 .. 64.
+ * params: ONE contiguous fp32 device buffer, 16-byte aligned, in torch's nn.Sequential(Linear, ReLU, Linear, ReLU, Linear)
+ * .parameters() order: W1[H1][10], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A].  epsilon: one fp32 device word.  Both are
+ * read when the kernel runs (a captured graph acts with what they hold at replay).  reserved: 0.                          */
+typedef struct S2DQNet {
+  int32_t hidden1, hidden2, n_actions, reserved;
+  const float *params;
+  const float *epsilon;
+} S2DQNet;
+
 /* Derived protobuf-mirroring fields that are not plain state words (row T1).  Each array
  * is [N]; NULL pointers are skipped.                                                       */
 typedef struct S2DWorldModel {
@@ -231,6 +244,18 @@ int s2d_step_k(S2DHandle h, int k, const void *actions_dev, int action_kind, con
  * [T][N] in `action_kind` layout, or NULL with S2D_ACT_RANDOM. */
 int s2d_rollout(S2DHandle h, int n_steps, const void *actions_dev, int action_kind,
                 const S2DRollout *out, void *stream);
+/* n_steps >= 1 cycles fused in ONE launch (discrete-action engines only) whose action at every cycle is the caller's
+ * Q-network, epsilon-greedy per env:
+ *   greedy  = the first index of the largest q (ties: lowest index; a NaN never replaces the current best), every output
+ *             an fmaf chain from its bias in ascending k, relu(v) = v > 0 ? v : +0;
+ *   explore = word k & 3 of Philox block 2 of stream POLICY at counter k >> 2 < thr, k = the env's policy_step (advanced by
+ *             one every step), thr = eps >= 1 ? 2^32 : eps > 0 ? (uint64)(eps 2^32) : 0 (NaN: 0);
+ *   the random action is S2D_ACT_RANDOM's draw, so eps = 1 is s2d_rollout(NULL, S2D_ACT_RANDOM) bit for bit.
+ * The action of step t is chosen from the observation step t - 1 returned (t = 0: the observation of the launch's start
+ * state).  `out` as for s2d_rollout (action = int32[T][N]); terminal_obs (may be NULL) = float[T][N][10], written only where
+ * done[t][i] (the observation the episode ended on).  Rejected without a launch: continuous / turning engines, widths not in
+ * {16, ..., 128} step 16, n_actions != action_space_size or > 64, NULL or misaligned params / epsilon, n_steps < 1. */
+int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
