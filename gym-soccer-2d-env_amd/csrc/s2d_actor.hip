@@ -1,9 +1,11 @@
-// s2d_actor.hip -- the fused epsilon-greedy Q-network actor (s2d_rollout_qnet, include/s2d.h; DESIGN.md sections 4, 5).
+// s2d_actor.hip -- the fused actors: the epsilon-greedy Q-network (s2d_rollout_qnet) and the deterministic tanh policy with
+// Gaussian action noise (s2d_rollout_actor); include/s2d.h, DESIGN.md sections 4, 5.
 //
 // The plain rollout kernel (one env per lane, the whole cycle in one wave, T cycles per launch) with the action of every cycle
-// chosen in-kernel from the caller's network  q = W3 relu(W2 relu(W1 x + b1) + b2) + b3  on the env's current observation, and
-// per-env epsilon-greedy exploration.  Reference: DQN("MlpPolicy").predict inside SB3's collect_rollouts,
-// dqn_stable_baselines3.py:36-49.
+// chosen in-kernel from the caller's network  y = W3 relu(W2 relu(W1 x + b1) + b2) + b3  on the env's current observation, and
+// per-env epsilon exploration.  Head by mode: discrete engines take the argmax of y (DQN("MlpPolicy").predict inside SB3's
+// collect_rollouts, dqn_stable_baselines3.py:36-49); continuous (A = 1) and turning (A = 4) engines take a_j = tanh_spec(y_j),
+// optionally plus clipped Gaussian noise (SB3's DDPG / TD3 actor.mu with NormalActionNoise, ddpg_stable_baselines3.py).
 //
 // The network runs on the f32-input matrix cores: v_mfma_f32_16x16x4_f32 is bit for bit the k-ordered fmaf chain
 // acc = fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1, fma(a_k0, b_k0, C)))), so a chain of them that starts from C = bias
@@ -98,8 +100,10 @@ S2D_DEV void layer_tile(const float* __restrict__ wf, const float* __restrict__ 
   if (jt < m16) layer_group<RELU, 1, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
 }
 
-// greedy action of every env of the wave (lane = env): the network on the observation tile, then the spec's argmax scan
-S2D_DEV int qnet_greedy(const QNetDims& d, const float* __restrict__ wl, float* __restrict__ ha, float* __restrict__ hb,
+// the network on the observation tile of the wave (lane = env): qv[env][j] (pitch d.qpitch) = the output layer's
+// pre-activations y_j; ARGMAX: then the spec's argmax scan, whose result is returned (the Q-actor's greedy action)
+template <bool ARGMAX>
+S2D_DEV int net_forward(const QNetDims& d, const float* __restrict__ wl, float* __restrict__ ha, float* __restrict__ hb,
                         float* __restrict__ qv, const float* __restrict__ obs_tile, int lane) {
   const int g = lane >> 4, c = lane & 15;
   const float* w1 = wl;
@@ -119,6 +123,7 @@ S2D_DEV int qnet_greedy(const QNetDims& d, const float* __restrict__ wl, float* 
                       qv + 16 * nt * d.qpitch, d.qpitch, lane);
     wave_lds_fence();
   }
+  if constexpr (!ARGMAX) return 0;
   // best = 0; for a = 1 .. A-1: if (q[a] > q[best]) best = a   (ties: lowest index; a NaN never replaces the best)
   const float* q = qv + lane * d.qpitch;
   int best = 0;
@@ -136,12 +141,53 @@ S2D_DEV uint64_t explore_threshold(float eps) {
   return eps >= 1.0f ? (1ull << 32) : eps > 0.0f ? (uint64_t)(eps * 4294967296.0f) : 0ull;
 }
 
-template <int NK>
-__global__ __launch_bounds__(kBlock) void s2d_reach_qnet_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
-                                                                        float* __restrict__ S, int64_t stride, int64_t n,
-                                                                        int n_steps, QNetDims d, const float* __restrict__ params,
-                                                                        const float* __restrict__ eps_dev, RolloutOut ro,
-                                                                        float* __restrict__ term_rec, StepOut o, int wave_words) {
+// the deterministic policy's action of one env (lane = env), not exploring: a_j = tanh_spec(y_j), with GAUSS + clip(mu_j +
+// sigma_j z_j), z from Box-Muller on POLICY block 3 (TURN4: z0..z3 of the block at counter k; CONT1: z_{k & 3} of the block at
+// counter k >> 2, cached in gquad).  noise = [2][A] (mu, sigma) in device memory.
+template <int MODE, bool GAUSS>
+S2D_DEV Action4 tanh_action(const S2DHot& p, const float* __restrict__ y, const float* __restrict__ noise, uint32_t gl, uint32_t gh,
+                            uint32_t k, const U4& gquad) {
+  constexpr int A = MODE == S2D_MODE_TURN4 ? 4 : 1;
+  float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < A; ++j) a[j] = tanh_spec(y[j]);
+  if constexpr (GAUSS) {
+    float z[4];
+    if constexpr (MODE == S2D_MODE_TURN4) {
+      const U4 w = s2d_draw(p, gl, gh, k, S2D_ST_POLICY, 3);
+      box_muller(w.x, w.y, z[0], z[1]);
+      box_muller(w.z, w.w, z[2], z[3]);
+    } else {
+      const bool hi = (k & 2u) != 0u;
+      float zc, zs;
+      box_muller(hi ? gquad.z : gquad.x, hi ? gquad.w : gquad.y, zc, zs);
+      z[0] = (k & 1u) ? zs : zc;
+    }
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+      const float v = a[j] + fmaf(noise[A + j], z[j], noise[j]);
+      a[j] = v < -1.0f ? -1.0f : v > 1.0f ? 1.0f : v;
+    }
+  }
+  return Action4{a[0], a[1], a[2], a[3]};
+}
+
+// the noise buffer of the tanh-head instantiations (Noise = const float*); the Q-actor's have no such argument
+S2D_DEV const float* actor_noise() { return nullptr; }
+S2D_DEV const float* actor_noise(const float* p) { return p; }
+
+// The fused rollout of both actors.  MODE = S2D_MODE_DISCRETE: the Q-network's epsilon-greedy argmax (s2d_rollout_qnet);
+// CONT1 / TURN4: the deterministic tanh policy with epsilon-random exploration and optional Gaussian action noise (GAUSS,
+// s2d_rollout_actor).  One body, so that both share the prologue, the simulation, the records and the epilogue.  The noise
+// buffer is a trailing argument pack, empty for the Q-actor, so that its kernel arguments, and its code, stay as they were.
+template <int MODE, int NK, bool GAUSS, typename... Noise>
+__global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
+                                                                         float* __restrict__ S, int64_t stride, int64_t n,
+                                                                         int n_steps, QNetDims d, const float* __restrict__ params,
+                                                                         const float* __restrict__ eps_dev, RolloutOut ro,
+                                                                         float* __restrict__ term_rec, StepOut o, int wave_words,
+                                                                         Noise... noise_arg) {
+  const float* __restrict__ noise = actor_noise(noise_arg...);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   QS_DECL;
   const S2DHot p = hot_in_vgprs(p_sgpr);
@@ -207,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_qnet_rollout_kernel(S2DHot p
   float reward = 0.0f, dir = 0.0f; int done = 0, res = 0, cmd = 0;
   unsigned int cnt1 = 0, cnt2 = 0, cnt3 = 0;
   float* const term_row = o.terminal_obs + i * S2D_OBS_DIM;
-  U4 quad{0, 0, 0, 0}, equad{0, 0, 0, 0}, squad{0, 0, 0, 0};
+  U4 quad{0, 0, 0, 0}, equad{0, 0, 0, 0}, squad{0, 0, 0, 0}, gquad{0, 0, 0, 0};
   bool have_prep = false;
   uint32_t* const coop_scratch = reinterpret_cast<uint32_t*>(tile);
   if (p.auto_reset) {
@@ -227,18 +273,41 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_qnet_rollout_kernel(S2DHot p
     wave_lds_fence();
     tile_write(tile, ob, lane, active);
     wave_lds_fence();
-    const int greedy = qnet_greedy(d, smem, ha, hb, qv, tile, lane);
+    int greedy = 0;
+    float y[4];
+    if constexpr (MODE == S2D_MODE_DISCRETE) {
+      greedy = net_forward<true>(d, smem, ha, hb, qv, tile, lane);
+    } else {
+      net_forward<false>(d, smem, ha, hb, qv, tile, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[j] = qv[lane * d.qpitch + j];   // A <= 4 of the 16 rows of the one output tile
+      wave_lds_fence();
+    }
     QS_MARK(qs_net);
     if (active) {
       const uint32_t k = k0 + (uint32_t)t;
-      if (t == 0 || (k & 3u) == 0u) {
-        quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);                      // block 0: S2D_ACT_RANDOM's draw
-        equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
+      CmdPrep c;
+      if constexpr (MODE == S2D_MODE_DISCRETE) {
+        if (t == 0 || (k & 3u) == 0u) {
+          quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);                      // block 0: S2D_ACT_RANDOM's draw
+          equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
+        }
+        const bool explore = (uint64_t)quad_word(equad, k) < thr;
+        const int a = explore ? rnd_below(quad_word(quad, k), (uint32_t)p.n_actions) : greedy;
+        if (ro.action) static_cast<int32_t*>(ro.action)[row + i] = a;
+        c = decode_action<S2D_MODE_DISCRETE>(p, Action4{(float)a, 0.0f, 0.0f, 0.0f}, gl, gh, k, false, squad, cmd, dir);
+      } else {
+        const bool refresh = t == 0 || (k & 3u) == 0u;
+        if (refresh) {
+          equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
+          if (MODE == S2D_MODE_CONT1) quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);              // block 0: the random action
+          if (GAUSS && MODE == S2D_MODE_CONT1) gquad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 3);   // block 3: noise
+        }
+        const bool explore = (uint64_t)quad_word(equad, k) < thr;
+        const Action4 a = explore ? random_action<MODE>(p, gl, gh, k, quad, false) : tanh_action<MODE, GAUSS>(p, y, noise, gl, gh, k, gquad);
+        if (ro.action) store_rollout_action<MODE>(ro.action, row + i, a);
+        c = decode_action<MODE>(p, a, gl, gh, k, refresh, squad, cmd, dir);
       }
-      const bool explore = (uint64_t)quad_word(equad, k) < thr;
-      const int a = explore ? rnd_below(quad_word(quad, k), (uint32_t)p.n_actions) : greedy;
-      if (ro.action) static_cast<int32_t*>(ro.action)[row + i] = a;
-      const CmdPrep c = decode_action<S2D_MODE_DISCRETE>(p, Action4{(float)a, 0.0f, 0.0f, 0.0f}, gl, gh, k, false, squad, cmd, dir);
       step_env<NK, false>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, prep, lane, have_prep);
       if (ro.reward) ro.reward[row + i] = reward;
       if (ro.done) ro.done[row + i] = (uint8_t)done;
@@ -274,44 +343,86 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_qnet_rollout_kernel(S2DHot p
 // host side (same library, hidden symbol; the C entry point and its argument checks are in s2d_engine.hip)
 static constexpr size_t kLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all of it available to one workgroup
 static constexpr int kMaxDevices = 64;
-extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
-                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name) {
-  QNetDims d;
+using QNetKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut,
+                            float*, StepOut, int);
+using TanhKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut,
+                            float*, StepOut, int, const float*);
+
+// the LDS plan of a 10-h1-h2-na network: dims, per-wave words and the wave count per workgroup (as many as the LDS holds, 4 for
+// 10-64-64-16); false if one wave does not fit
+static bool plan_lds(int h1, int h2, int na, QNetDims& d, int& wave_words, int& waves, size_t& lds) {
   d.h1 = h1; d.h2 = h2; d.na = na; d.na16 = (na + 15) / 16 * 16;
   const int wmax = h1 > h2 ? h1 : h2;
   d.pitch = (wmax + 63) / 64 * 64 + 4;
   d.qpitch = d.na16 + 4;
   const int nfrag = (h1 / 16) * 3 + (h2 / 16) * (h1 / 4) + (d.na16 / 16) * (h2 / 4);
   const size_t shared_words = ((size_t)nfrag * kWave + h1 + h2 + d.na16 + 3) & ~(size_t)3;
-  const int wave_words = 2 * 16 * d.pitch + kWave * d.qpitch + kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
-  int waves = kWavesPerBlock;                              // as many waves per workgroup as the LDS holds (4 for 10-64-64-16)
+  wave_words = 2 * 16 * d.pitch + kWave * d.qpitch + kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
+  waves = kWavesPerBlock;
   while (waves > 1 && (shared_words + (size_t)waves * wave_words) * sizeof(float) > kLdsMax) waves /= 2;
-  const size_t lds = (shared_words + (size_t)waves * wave_words) * sizeof(float);
-  if (lds > kLdsMax) return -1;
-  using K = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut, float*,
-                     StepOut, int);
-  static const K table[3] = {s2d_reach_qnet_rollout_kernel<S2D_NK_OFF>, s2d_reach_qnet_rollout_kernel<S2D_NK_LATTICE>,
-                             s2d_reach_qnet_rollout_kernel<S2D_NK_SQUARE>};
-  // the dynamic-LDS limit is a per-device property of the function: set it once per (device, noise kind), under a lock (engines on
-  // several devices may be driven from several threads); the caller has made the engine's device current
+  lds = (shared_words + (size_t)waves * wave_words) * sizeof(float);
+  return lds <= kLdsMax;
+}
+
+// the dynamic-LDS limit is a per-device property of the function: set it once per (device, instantiation `slot`), under a lock
+// (engines on several devices may be driven from several threads); the caller has made the engine's device current
+static constexpr int kActorSlots = 3 + 2 * 3 * 2;
+static bool allow_lds(const void* fn, int slot) {
   static std::mutex attr_mu;
-  static bool attr_set[kMaxDevices][3] = {};
+  static bool attr_set[kMaxDevices][kActorSlots] = {};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -2;
-  {
-    std::lock_guard<std::mutex> lock(attr_mu);
-    if (!attr_set[dev][nk]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(table[nk]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) !=
-          hipSuccess)
-        return -2;
-      attr_set[dev][nk] = true;
-    }
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lock(attr_mu);
+  if (!attr_set[dev][slot]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
+    attr_set[dev][slot] = true;
   }
+  return true;
+}
+
+extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
+                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
+                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name) {
+  QNetDims d;
+  int wave_words, waves;
+  size_t lds;
+  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
+  static const QNetKernel table[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false>,
+                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false>,
+                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false>};
+  if (!allow_lds(reinterpret_cast<const void*>(table[nk]), nk)) return -2;
   const int threads = waves * kWave;
   const unsigned blocks = (unsigned)((n + threads - 1) / threads);
   hipLaunchKernelGGL(table[nk], dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n,
                      n_steps, d, params, eps, *ro, term_rec, *o, wave_words);
   if (name) std::snprintf(name, 96, "s2d_reach_qnet_rollout_kernel<noise=%d,h1=%d,h2=%d,a=%d,waves=%d>", nk, h1, h2, na, waves);
+  return 0;
+}
+
+// mode = S2D_MODE_CONT1 | S2D_MODE_TURN4 (na = 1 | 4), gauss = 0 | 1
+extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2DHot* hot, const S2DRare* rare_dev, float* S,
+                                          int64_t stride, int64_t n, int n_steps, int h1, int h2, int na, const float* params,
+                                          const float* eps, const float* noise, const RolloutOut* ro, float* term_rec,
+                                          const StepOut* o, void* stream, char* name) {
+  QNetDims d;
+  int wave_words, waves;
+  size_t lds;
+  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
+#define S2D_DDPG_ROW(M)                                                                                                          \
+  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, const float*>,                 \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, const float*>,                   \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, const float*>}
+  static const TanhKernel table[2][6] = {S2D_DDPG_ROW(S2D_MODE_CONT1), S2D_DDPG_ROW(S2D_MODE_TURN4)};
+#undef S2D_DDPG_ROW
+  const int m = mode == S2D_MODE_TURN4 ? 1 : 0, v = 3 * gauss + nk;
+  const TanhKernel k = table[m][v];
+  if (!allow_lds(reinterpret_cast<const void*>(k), 3 + 6 * m + v)) return -2;
+  const int threads = waves * kWave;
+  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n, n_steps, d,
+                     params, eps, *ro, term_rec, *o, wave_words, noise);
+  if (name)
+    std::snprintf(name, 96, "s2d_reach_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,h1=%d,h2=%d,a=%d,waves=%d>",
+                  m ? "turn4" : "cont1", nk, gauss, h1, h2, na, waves);
   return 0;
 }

@@ -202,6 +202,58 @@ S2D_DEV float exp_spec(float x) {
   float y = fmaf(p, z, r) + 1.0f;
   return ldexpf(y, (int)k);
 }
+// Cephes logf: m in [sqrt(1/2), sqrt(2)) and e from a frexp split, x = m - 1, the 9-term polynomial, ln 2
+// split as exp_spec's.  0 -> -inf, negative and NaN -> NaN, +inf -> +inf.  Every step is one fixed fp32 operation.
+S2D_DEV float log_spec(float v) {
+  int e;
+  float m = frexpf(v, &e);                               // v = m 2^e, m in [0.5, 1)
+  const bool lo = m < 0.70710678118654752f;
+  e = lo ? e - 1 : e;
+  const float x = lo ? (m + m) - 1.0f : m - 1.0f;
+  const float z = x * x;
+  float p = 7.0376836292e-2f;
+  p = fmaf(p, x, -1.1514610310e-1f);
+  p = fmaf(p, x, 1.1676998740e-1f);
+  p = fmaf(p, x, -1.2420140846e-1f);
+  p = fmaf(p, x, 1.4249322787e-1f);
+  p = fmaf(p, x, -1.6668057665e-1f);
+  p = fmaf(p, x, 2.0000714765e-1f);
+  p = fmaf(p, x, -2.4999993993e-1f);
+  p = fmaf(p, x, 3.3333331174e-1f);
+  const float fe = (float)e;
+  float y = (p * x) * z;
+  y = fmaf(fe, -2.12194440e-4f, y);
+  y = fmaf(-0.5f, z, y);
+  float r = fmaf(fe, 0.693359375f, x + y);
+  r = v == 0.0f ? -__builtin_inff() : r;
+  r = v == __builtin_inff() ? v : r;
+  return (v < 0.0f || v != v) ? __builtin_nanf("") : r;
+}
+// Cephes tanhf on a = |y|, sign restored at the end (odd by construction, -0 -> -0, NaN passes):
+// a < 0.625: a + (z P(z)) a with z = a^2; else 1 - 2 / (exp_spec(2a) + 1); a > 9: exactly 1.
+S2D_DEV float tanh_spec(float y) {
+  const float a = fabsf(y);
+  const float z = a * a;
+  float p = -5.70498872745e-3f;
+  p = fmaf(p, z, 2.06390887954e-2f);
+  p = fmaf(p, z, -5.37397155531e-2f);
+  p = fmaf(p, z, 1.33314422036e-1f);
+  p = fmaf(p, z, -3.33332819422e-1f);
+  const float small = fmaf(z * p, a, a);
+  const float big = 1.0f - 2.0f / (exp_spec(a + a) + 1.0f);
+  float r = a < 0.625f ? small : big;
+  r = a > 9.0f ? 1.0f : r;
+  return copysignf(r, y);
+}
+// Box-Muller on two Philox words: u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], angle = (wb >> 8) 45 2^-21
+// degrees (360 u2); z_cos = r cos, z_sin = r sin with r = sqrt(-2 log_spec(u1)), so |z| <= sqrt(48 ln 2) = 5.768.
+S2D_DEV void box_muller(uint32_t wa, uint32_t wb, float& zc, float& zs) {
+  const float u1 = (float)((wa >> 8) + 1u) * 5.9604644775390625e-8f;
+  const float r = sqrt_cr(-2.0f * log_spec(u1));
+  float s, c;
+  sincos_deg((float)(wb >> 8) * 2.1457672119140625e-5f, s, c);
+  zc = r * c; zs = r * s;
+}
 // pyrusgeom AngleDeg normalisation for |d| <= 540 (every angle the engine forms: sums and
 // differences of two angles in [-180,180], plus 180 for a back dash); general form with
 // fmod kept for the diagnostic entry point.

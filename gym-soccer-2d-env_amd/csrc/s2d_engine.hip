@@ -971,6 +971,17 @@ __global__ void s2d_debug_eval_kernel(int op, const float* __restrict__ in, floa
       q[0] = nz.pc; q[1] = nz.ps; q[2] = nz.bc; q[3] = nz.bs;   // c_px, c_py, c_bx, c_by
       break;
     }
+    case 13: out[i] = tanh_spec(in[i]); break;
+    case 14: out[i] = log_spec(in[i]); break;
+    case 15: {                                           // Gaussian block of the actor's action noise (POLICY block 3, Box-Muller)
+      const uint32_t* u = reinterpret_cast<const uint32_t*>(in) + 4 * i;   // gid_lo, gid_hi, counter, seed_lo (seed_hi = 0)
+      S2DHot p{}; p.seed_lo = u[3]; p.seed_hi = 0u;
+      const U4 w = s2d_draw(p, u[0], u[1], u[2], S2D_ST_POLICY, 3);
+      float* q = out + 4 * i;
+      box_muller(w.x, w.y, q[0], q[1]);
+      box_muller(w.z, w.w, q[2], q[3]);
+      break;
+    }
     case 0: { float s, c; sincos_deg(in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break; }
     case 1: out[i] = atan2_deg(in[2 * i], in[2 * i + 1]); break;
     case 2: out[i] = exp_spec(in[i]); break;
@@ -1041,6 +1052,11 @@ extern "C" int s2d_internal_rollout2(int mode, int noise, const S2DHot* hot, con
 extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
                                          int n_steps, int h1, int h2, int na, const float* params, const float* eps,
                                          const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name);
+// s2d_actor.hip: launches the deterministic (tanh) actor rollout of a continuous or turning engine (same return codes)
+extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2DHot* hot, const S2DRare* rare_dev, float* S,
+                                          int64_t stride, int64_t n, int n_steps, int h1, int h2, int na, const float* params,
+                                          const float* eps, const float* noise, const RolloutOut* ro, float* term_rec,
+                                          const StepOut* o, void* stream, char* name);
 
 struct S2DEngine {
   S2DConfig cfg;
@@ -1538,6 +1554,47 @@ S2D_API int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet* net, const
   return S2D_OK;
 }
 
+S2D_API int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet* net, const S2DRollout* out, float* terminal_obs,
+                              void* stream) {
+  if (!h) return fail(S2D_EINVAL, "NULL handle");
+  if (!net) return fail(S2D_EINVAL, "s2d_rollout_actor: net is NULL");
+  if (h->mode == S2D_MODE_DISCRETE)
+    return fail(S2D_EINVAL, "s2d_rollout_actor needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet");
+  const int na = h->mode == S2D_MODE_TURN4 ? 4 : 1;
+  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_actor: n_steps must be >= 1");
+  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
+  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
+    return fail(S2D_EINVAL, "s2d_rollout_actor: hidden widths must be multiples of 16 in [16, 128] (the weights live in LDS); "
+                            "SB3's default net_arch=[400, 300] does not fit: use policy_kwargs=dict(net_arch=[64, 64])");
+  if (net->n_out != na)
+    return fail(S2D_EINVAL, h->mode == S2D_MODE_TURN4 ? "s2d_rollout_actor: n_out must be 4 on a turning engine"
+                                                      : "s2d_rollout_actor: n_out must be 1 on a continuous (non-turning) engine");
+  if (net->noise_kind != 0 && net->noise_kind != 1) return fail(S2D_EINVAL, "s2d_rollout_actor: noise_kind must be 0 (none) or 1 (Gaussian)");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return fail(S2D_EINVAL, "s2d_rollout_actor: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_actor: epsilon must be a non-NULL, 4-byte aligned device pointer");
+  if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
+    return fail(S2D_EINVAL, "s2d_rollout_actor: Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
+  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_actor: terminal_obs must be 4-byte aligned");
+  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (out) {
+    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
+    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
+      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
+  }
+  DeviceGuard guard(h->device);
+  const int rc = s2d_internal_rollout_actor(h->mode, h->nk, net->noise_kind, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
+                                            h->stride, h->n, n_steps, net->hidden1, net->hidden2, na, net->params, net->epsilon,
+                                            net->noise_kind ? net->noise : nullptr, &ro, terminal_obs, &h->out, stream, h->kernel_name);
+  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_actor: the network does not fit the LDS of a workgroup");
+  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor: hipGetDevice or hipFuncSetAttribute failed");
+  HIP_TRY(hipGetLastError());
+  h->last_kernel = h->kernel_name;
+  return S2D_OK;
+}
+
 S2D_API int s2d_world_model(S2DHandle h, const S2DWorldModel* out, void* stream) {
   if (!h || !out) return fail(S2D_EINVAL, "NULL argument");
   DeviceGuard guard(h->device);
@@ -1584,7 +1641,7 @@ S2D_API int s2d_set_seed(S2DHandle h, uint64_t seed, void* stream) {
 }
 
 S2D_API int s2d_debug_eval(int op, const void* in_dev, void* out_dev, int64_t n, void* stream) {
-  if (!in_dev || !out_dev || n <= 0 || op < 0 || op > 12 || (op == 9 && n % 256 != 0)) return fail(S2D_EINVAL, "bad s2d_debug_eval argument");
+  if (!in_dev || !out_dev || n <= 0 || op < 0 || op > 15 || (op == 9 && n % 256 != 0)) return fail(S2D_EINVAL, "bad s2d_debug_eval argument");
   hipLaunchKernelGGL(s2d_debug_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), op, static_cast<const float*>(in_dev),
                      static_cast<float*>(out_dev), n);

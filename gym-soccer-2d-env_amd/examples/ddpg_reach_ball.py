@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""DDPG on N vectorised reach_ball envs with a continuous action, everything on the GPU.
+
+Mirror of the reference's ddpg_stable_baselines3.py (use_continuous_action=True, use_turning=False; --turning for the 4-D
+variant) with stable-baselines3 -- which cannot be installed offline -- replaced by a small plain-torch DDPG: actor
+Linear-ReLU-Linear-ReLU-Linear-Tanh (SB3's actor.mu with policy_kwargs=dict(net_arch=[64, 64])), critic Q(s, a), target nets
+with Polyak averaging, Gaussian action noise, a replay buffer in device memory.
+
+    python examples/ddpg_reach_ball.py --envs 4096 --iters 10 --train-steps 200 --test-steps 250 --fused-actor 32
+
+--fused-actor T collects T x N transitions per launch: the engine evaluates the learner's own actor in-kernel
+(Engine.rollout_actor with a soccer2d_amd.actor.DeterministicActor), with epsilon-random exploration for the first launches
+(SB3's learning_starts) and Gaussian action noise; the actor's packed weights are refreshed with sync() after every optimiser
+phase and Timeouts bootstrap from the recorded terminal observations.  0: one torch forward per step.
+"""
+import argparse
+import copy
+import os
+import sys
+import time
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sample_environments.environment_factory import EnvironmentFactory  # noqa: E402
+
+kewargs = {
+    'change_ball_position': True, 'change_ball_velocity': True,
+    'ball_position_x': 0, 'ball_position_y': 0, 'ball_speed': 0, 'ball_direction': 0,
+    'min_distance_to_ball': 5.0, 'max_steps': 200,
+    'use_continuous_action': True, 'action_space_size': 16, 'use_turning': False,
+}
+
+
+def mlp(n_in, n_out, hidden=64, tanh=False):
+    layers = [nn.Linear(n_in, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, n_out)]
+    return nn.Sequential(*(layers + ([nn.Tanh()] if tanh else [])))
+
+
+class DeviceReplay:
+    def __init__(self, capacity, n_obs, n_act, device):
+        self.cap, self.pos, self.full = capacity, 0, False
+        self.obs = torch.empty((capacity, n_obs), device=device)
+        self.next_obs = torch.empty((capacity, n_obs), device=device)
+        self.act = torch.empty((capacity, n_act), device=device)
+        self.rew = torch.empty((capacity,), device=device)
+        self.term = torch.empty((capacity,), device=device)
+
+    def add(self, obs, act, rew, next_obs, term):
+        n = obs.shape[0]
+        idx = (torch.arange(n, device=obs.device) + self.pos) % self.cap
+        self.obs[idx], self.act[idx], self.rew[idx], self.next_obs[idx], self.term[idx] = obs, act, rew, next_obs, term
+        self.full |= self.pos + n >= self.cap
+        self.pos = (self.pos + n) % self.cap
+
+    def sample(self, batch):
+        hi = self.cap if self.full else self.pos
+        i = torch.randint(0, hi, (batch,), device=self.obs.device)
+        return self.obs[i], self.act[i], self.rew[i], self.next_obs[i], self.term[i]
+
+
+class DeviceDDPG:
+    def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
+                 learning_starts=2, seed=0):
+        torch.manual_seed(seed)
+        self.env, self.dev = env, env.device
+        n_obs, self.n_act = env.observation_space.shape[0], env.action_space.shape[0]
+        self.mu = mlp(n_obs, self.n_act, tanh=True).to(self.dev)
+        self.q = mlp(n_obs + self.n_act, 1).to(self.dev)
+        self.mu_target, self.q_target = copy.deepcopy(self.mu), copy.deepcopy(self.q)
+        self.opt_mu = torch.optim.Adam(self.mu.parameters(), lr=lr)
+        self.opt_q = torch.optim.Adam(self.q.parameters(), lr=lr)
+        self.rb = DeviceReplay(buffer, n_obs, self.n_act, self.dev)
+        self.gamma, self.tau, self.batch, self.grad_steps, self.sigma = gamma, tau, batch, grad_steps, sigma
+        self.learning_starts, self.launches = learning_starts, 0
+        self.obs = env.reset().clone()
+
+    @torch.no_grad()
+    def predict(self, obs, noise=False):
+        a = self.mu(obs)
+        if noise:
+            a = (a + self.sigma * torch.randn_like(a)).clamp(-1, 1)
+        return a
+
+    def optimise(self, n_updates):
+        for _g in range(n_updates):
+            o, a, r, no, t = self.rb.sample(self.batch)
+            with torch.no_grad():
+                tgt = r + self.gamma * (1 - t) * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
+            loss_q = nn.functional.mse_loss(self.q(torch.cat([o, a], 1)).squeeze(1), tgt)
+            self.opt_q.zero_grad(set_to_none=True)
+            loss_q.backward()
+            self.opt_q.step()
+            loss_mu = -self.q(torch.cat([o, self.mu(o)], 1)).mean()
+            self.opt_mu.zero_grad(set_to_none=True)
+            loss_mu.backward()
+            self.opt_mu.step()
+            with torch.no_grad():
+                for net, tgt_net in ((self.mu, self.mu_target), (self.q, self.q_target)):
+                    for p, pt in zip(net.parameters(), tgt_net.parameters()):
+                        pt.mul_(1 - self.tau).add_(p, alpha=self.tau)
+
+    def _store(self, obs_t, act, rec_obs, rew, done, res, term_obs):
+        next_obs = torch.where(done.bool().unsqueeze(-1), term_obs, rec_obs)            # bootstrap through Timeouts
+        term = ((res == 1) | (res == 2)).float()                                          # Goal / Out are true terminations
+        d = obs_t.shape[-1]
+        self.rb.add(obs_t.reshape(-1, d), act.reshape(-1, self.n_act), rew.reshape(-1), next_obs.reshape(-1, d), term.reshape(-1))
+
+    def learn(self, vec_steps):
+        """one torch forward per vector step (the torch-in-the-loop path)"""
+        for _ in range(vec_steps):
+            if self.launches < self.learning_starts:
+                act = torch.rand((self.env.num_envs, self.n_act), device=self.dev) * 2 - 1
+            else:
+                act = self.predict(self.obs, noise=True)
+            nobs, rew, done, info = self.env.step(act)
+            self._store(self.obs, act, nobs, rew, done, info['result'], info['terminal_observation'])
+            self.obs = nobs.clone()
+            if self.rb.full or self.rb.pos >= self.batch:
+                self.optimise(self.grad_steps)
+        self.launches += 1
+
+    def learn_fused(self, vec_steps, T):
+        """The same DDPG, experience collected T steps per launch by the fused actor (the learner's own actor in-kernel):
+        epsilon = 1 (uniform random actions) for the first learning_starts launches, then the noisy actor."""
+        from soccer2d_amd.actor import DeterministicActor
+        if not hasattr(self, 'actor'):
+            self.actor = DeterministicActor.from_module(self.mu, device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
+            self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
+        eng, rec = self.env.engine, self.rec
+        for _ in range((vec_steps + T - 1) // T):
+            self.actor.epsilon = 1.0 if self.launches < self.learning_starts else 0.0
+            obs0 = eng.obs.clone()                               # the observation the first action is chosen from
+            self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
+            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
+            self._store(obs_t, rec['action'], rec['obs'], rec['reward'], rec['done'], rec['result'], rec['terminal_obs'])
+            self.launches += 1
+            if self.rb.full or self.rb.pos >= self.batch:
+                self.optimise(self.grad_steps * T)
+                self.actor.sync()                                # the next launch acts with the new weights
+        self.obs = eng.obs.clone()
+
+
+def test(env, model, vec_steps):
+    """deterministic policy (no noise), count info['result'] of finished episodes"""
+    obs = env.reset()
+    counts = torch.zeros(4, dtype=torch.int64, device=env.device)
+    for _ in range(vec_steps):
+        act = model.predict(obs) if model is not None else None
+        obs, rew, done, info = env.step(act)
+        counts += torch.bincount(info['result'].long(), minlength=4)
+    c = counts.cpu().tolist()
+    n = max(1, c[1] + c[2] + c[3])
+    return {'Goal': c[1] / n, 'Out': c[2] / n, 'Timeout': c[3] / n, 'episodes': n}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--envs', type=int, default=4096)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--train-steps', type=int, default=200)
+    ap.add_argument('--test-steps', type=int, default=250)
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--turning', action='store_true', help='use_turning=True: the 4-D action')
+    ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
+                    help='collect T steps per launch with the in-kernel actor (0: one torch forward per step)')
+    args = ap.parse_args()
+    kw = dict(kewargs, use_turning=args.turning)
+    env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
+    test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
+    model = DeviceDDPG(env)
+    r0 = test(test_env, model, args.test_steps)
+    print('untrained actor:', r0)
+    r = r0
+    for i in range(args.iters):
+        t0 = time.time()
+        if args.fused_actor > 0:
+            model.learn_fused(args.train_steps, args.fused_actor)
+        else:
+            model.learn(args.train_steps)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        r = test(test_env, model, args.test_steps)
+        print(f'iter {i}: {args.train_steps * args.envs / dt / 1e6:.2f} M env-steps/s incl. learning  {r}')
+    print(f"goal share: {r0['Goal']:.4f} before, {r['Goal']:.4f} after {args.iters} iterations")
+    env.close(); test_env.close()
+
+
+if __name__ == '__main__':
+    main()

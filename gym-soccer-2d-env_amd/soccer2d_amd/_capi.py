@@ -105,6 +105,13 @@ class S2DQNet(C.Structure):
                 ('params', C.c_void_p), ('epsilon', C.c_void_p)]
 
 
+class S2DActorNet(C.Structure):
+    """the caller's deterministic actor of s2d_rollout_actor (widths, outputs, noise kind; device pointers of the packed
+    parameters, of epsilon and of the [2][n_out] (mu, sigma) noise buffer)"""
+    _fields_ = [('hidden1', C.c_int32), ('hidden2', C.c_int32), ('n_out', C.c_int32), ('noise_kind', C.c_int32),
+                ('params', C.c_void_p), ('epsilon', C.c_void_p), ('noise', C.c_void_p)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -133,6 +140,7 @@ PROTOTYPES = (
     ('s2d_rollout', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
     ('s2d_step_k', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
     ('s2d_rollout_qnet', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DQNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_rollout_actor', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DActorNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

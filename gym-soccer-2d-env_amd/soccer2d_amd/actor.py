@@ -1,4 +1,6 @@
 """QNetActor: the device-side state of the fused epsilon-greedy actor (Engine.rollout_qnet, s2d_rollout_qnet in include/s2d.h).
+DeterministicActor: the same for the fused tanh actor of continuous and turning engines (Engine.rollout_actor,
+s2d_rollout_actor), SB3's DDPG / TD3 ``actor.mu`` with optional Gaussian action noise.
 
 It owns ONE packed fp32 parameter buffer in torch's ``nn.Sequential(Linear, ReLU, Linear, ReLU, Linear).parameters()`` order
 (W1[H1][10], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A]) and a device epsilon scalar.  The kernel reads both when it runs, so a
@@ -19,15 +21,18 @@ MAX_ACTIONS = 64
 _NO_OPS = (torch.nn.Identity, torch.nn.Flatten)   # SB3's features extractor of a flat Box observation is a Flatten
 
 
-def _linears(module):
-    """The three nn.Linear layers of a Linear-ReLU-Linear-ReLU-Linear module (the form the kernel evaluates), in order.
-    Leaf modules are read in registration order; Identity / Flatten are skipped; anything else (another activation, a missing
-    ReLU, a fourth layer) is rejected: the kernel would silently act with a different function."""
+def _linears(module, tanh=False):
+    """The three nn.Linear layers of a Linear-ReLU-Linear-ReLU-Linear module (the form the kernel evaluates), in order; with
+    tanh=True the module must end in a Tanh (the deterministic actor's head).  Leaf modules are read in registration order;
+    Identity / Flatten are skipped; anything else (another activation, a missing ReLU or Tanh, a fourth layer) is rejected:
+    the kernel would silently act with a different function."""
     leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
-    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU) else type(m).__name__
-             for m in leaves]
-    if kinds != ['Linear', 'ReLU', 'Linear', 'ReLU', 'Linear']:
-        raise ValueError(f'the Q-network must be Linear-ReLU-Linear-ReLU-Linear (10 -> H1 -> H2 -> A), got {"-".join(kinds) or "nothing"}')
+    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU)
+             else 'Tanh' if isinstance(m, torch.nn.Tanh) else type(m).__name__ for m in leaves]
+    want = ['Linear', 'ReLU', 'Linear', 'ReLU', 'Linear'] + (['Tanh'] if tanh else [])
+    if kinds != want:
+        what = 'actor' if tanh else 'Q-network'
+        raise ValueError(f'the {what} must be {"-".join(want)} (10 -> H1 -> H2 -> A), got {"-".join(kinds) or "nothing"}')
     return [leaves[0], leaves[2], leaves[4]]
 
 
@@ -112,4 +117,131 @@ class QNetActor:
         net.hidden1, net.hidden2, net.n_actions, net.reserved = self.hidden1, self.hidden2, self.n_actions, 0
         net.params = self.params.data_ptr()
         net.epsilon = self._eps.data_ptr()
+        return net
+
+
+ACTOR_OUTPUTS = (1, 4)   # use_continuous_action without / with use_turning
+
+
+class DeterministicActor:
+    """Packed parameters, device epsilon and Gaussian action noise of a 10-H1-H2-A tanh actor for Engine.rollout_actor.
+
+    a = tanh(W3 relu(W2 relu(W1 x + b1) + b2) + b3), SB3's DDPG / TD3 ``model.actor.mu``; A = 1 on a continuous engine, 4 on a
+    turning one.  noise_sigma=None: no action noise (kind 0); otherwise the kernel adds mu + sigma z, z ~ N(0, 1) per output
+    (truncated at |z| <= 5.77), and clips to [-1, 1], as SB3's NormalActionNoise does.  The parameter, epsilon and (mu, sigma)
+    buffers are written in place and read when the kernel runs, so a captured graph acts with what they hold at replay; the
+    noise kind (None or not) selects the kernel and is fixed at capture."""
+
+    def __init__(self, hidden1=64, hidden2=64, n_out=1, device='cuda:0', epsilon=0.0, noise_mean=None, noise_sigma=None):
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in WIDTHS:
+                raise ValueError(f'{name} must be a multiple of 16 in [16, 128] (the weights live in LDS), got {w}; SB3\'s '
+                                 f'default DDPG net_arch=[400, 300] does not fit: use policy_kwargs=dict(net_arch=[64, 64])')
+        if int(n_out) not in ACTOR_OUTPUTS:
+            raise ValueError(f'n_out must be 1 (continuous engine) or 4 (turning engine), got {n_out}')
+        self.hidden1, self.hidden2, self.n_out = int(hidden1), int(hidden2), int(n_out)
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_out), dtype=torch.float32, device=self.device)
+        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._noise = torch.zeros(2, self.n_out, dtype=torch.float32, device=self.device)   # [mu; sigma]
+        self._eps_value = None
+        self._sigma = None
+        self.epsilon = epsilon
+        self.noise_mean = 0.0 if noise_mean is None else noise_mean
+        self.noise_sigma = noise_sigma
+        self._module = None
+
+    @classmethod
+    def from_module(cls, module, device=None, epsilon=0.0, noise_mean=None, noise_sigma=None):
+        """An actor shaped like `module` (SB3's actor.mu: Linear-ReLU-Linear-ReLU-Linear-Tanh, optionally behind a Flatten or
+        Identity), loaded from it."""
+        l1, l2, l3 = _linears(module, tanh=True)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon, noise_mean=noise_mean,
+                    noise_sigma=noise_sigma)
+        actor.load_from(module)
+        return actor
+
+    def shapes(self):
+        h1, h2, a = self.hidden1, self.hidden2, self.n_out
+        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
+
+    def load_from(self, module):
+        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
+        got = []
+        for lin in _linears(module, tanh=True):
+            if lin.bias is None:
+                raise ValueError('every nn.Linear of the actor needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if tuple(got) != self.shapes():
+            raise ValueError(f'actor shapes {got} do not match {list(self.shapes())}')
+        self._module = module
+        self.sync()
+        return self
+
+    def sync(self):
+        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
+        if self._module is None:
+            raise ValueError('no module loaded (load_from)')
+        srcs = []
+        for lin in _linears(self._module, tanh=True):
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+        return self
+
+    @property
+    def epsilon(self):
+        return self._eps_value
+
+    @epsilon.setter
+    def epsilon(self, value):
+        """Written in place into the device scalar the kernel reads (stream-ordered on torch's current stream)."""
+        self._eps_value = float(value)
+        self._eps.fill_(self._eps_value)
+
+    def _set_row(self, row, value):
+        v = torch.as_tensor(value, dtype=torch.float32).reshape(-1)
+        if v.numel() not in (1, self.n_out):
+            raise ValueError(f'expected a scalar or {self.n_out} values, got {v.numel()}')
+        self._noise[row].copy_(v.expand(self.n_out))
+
+    @property
+    def noise_mean(self):
+        return self._noise[0]
+
+    @noise_mean.setter
+    def noise_mean(self, value):
+        """mu of the Gaussian action noise (scalar or [A]), written in place."""
+        self._set_row(0, value)
+
+    @property
+    def noise_sigma(self):
+        """sigma of the Gaussian action noise ([A] device tensor), or None: no action noise."""
+        return None if self._sigma is None else self._noise[1]
+
+    @noise_sigma.setter
+    def noise_sigma(self, value):
+        if value is None:
+            self._sigma = None
+            return
+        self._set_row(1, value)
+        self._sigma = True
+
+    @property
+    def noise_kind(self):
+        return 0 if self._sigma is None else 1
+
+    @property
+    def epsilon_tensor(self):
+        return self._eps
+
+    def c_struct(self):
+        net = _capi.S2DActorNet()
+        net.hidden1, net.hidden2, net.n_out, net.noise_kind = self.hidden1, self.hidden2, self.n_out, self.noise_kind
+        net.params = self.params.data_ptr()
+        net.epsilon = self._eps.data_ptr()
+        net.noise = self._noise.data_ptr()
         return net

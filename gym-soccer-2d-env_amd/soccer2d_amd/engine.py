@@ -216,23 +216,15 @@ class Engine:
     _QNET_RECORD = {'obs': (torch.float32, (S2D_OBS_DIM,)), 'action': (torch.int32, ()), 'reward': (torch.float32, ()),
                     'done': (torch.uint8, ()), 'result': (torch.uint8, ()), 'terminal_obs': (torch.float32, (S2D_OBS_DIM,))}
 
-    def rollout_qnet(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
-        """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.QNetActor) epsilon-greedy choices on
-        the envs' own observations, evaluated in-kernel (s2d_rollout_qnet; discrete-action engines).  Returns the record dict of
-        rollout() (action int32 [T,N]); with terminal_obs=True (or a caller `out` holding 'terminal_obs') also float32 [T,N,10],
-        written only where done.  The actor's buffers are read when the kernel runs: a captured graph acts with the weights and
-        epsilon they hold at replay.  `out` pointer blocks are cached as in rollout()."""
-        T, n = int(n_steps), self.num_envs
-        if T < 1:
-            raise ValueError('rollout_qnet needs n_steps >= 1')
-        net = actor.c_struct()
-        if actor.device != self.device:
-            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+    def _actor_record(self, entry, record, T, out, with_obs, terminal_obs):
+        """The checked, cached record of a fused-actor launch (rollout_qnet / rollout_actor): (out, S2DRollout, terminal_obs
+        pointer).  `record` = {name: (dtype, trailing shape)}; `out` pointer blocks are cached as in rollout()."""
+        n = self.num_envs
         fresh = out is None
         if fresh:
             out = self.alloc_rollout(T, with_obs=with_obs, terminal_obs=terminal_obs)
         names = ('obs', 'action', 'reward', 'done', 'result', 'terminal_obs')
-        cached = None if fresh else self._ro_cache.get(('qnet', id(out)))
+        cached = None if fresh else self._ro_cache.get((entry, id(out)))
         key = tuple(None if out.get(k) is None else out[k].data_ptr() for k in names)
         if cached is None or cached[0] != key or cached[1] < T:
             ro = _capi.S2DRollout()
@@ -240,10 +232,10 @@ class Engine:
             for name in names:
                 v = out.get(name)
                 if v is not None:
-                    dt, trail = self._QNET_RECORD[name]
+                    dt, trail = record[name]
                     if (v.dtype != dt or not v.is_contiguous() or v.device != self.device or v.dim() != 2 + len(trail)
                             or v.shape[0] < T or v.shape[1] != n or tuple(v.shape[2:]) != trail):
-                        raise ValueError(f"rollout_qnet buffer {name!r} must be a contiguous {dt} [T>={T},{n}"
+                        raise ValueError(f"{entry} buffer {name!r} must be a contiguous {dt} [T>={T},{n}"
                                          f"{''.join(',' + str(d) for d in trail)}] tensor on {self.device}")
                     if name != 'terminal_obs':
                         setattr(ro, name, v.data_ptr())
@@ -253,9 +245,48 @@ class Engine:
             if not fresh:
                 if len(self._ro_cache) >= 16:
                     self._ro_cache.clear()
-                self._ro_cache[('qnet', id(out))] = cached
-        rc = self.lib.s2d_rollout_qnet(self._h, T, C.byref(net), C.byref(cached[2]), cached[4], self._stream())
+                self._ro_cache[(entry, id(out))] = cached
+        return out, cached[2], cached[4]
+
+    def rollout_qnet(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
+        """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.QNetActor) epsilon-greedy choices on
+        the envs' own observations, evaluated in-kernel (s2d_rollout_qnet; discrete-action engines).  Returns the record dict of
+        rollout() (action int32 [T,N]); with terminal_obs=True (or a caller `out` holding 'terminal_obs') also float32 [T,N,10],
+        written only where done.  The actor's buffers are read when the kernel runs: a captured graph acts with the weights and
+        epsilon they hold at replay.  `out` pointer blocks are cached as in rollout()."""
+        T = int(n_steps)
+        if T < 1:
+            raise ValueError('rollout_qnet needs n_steps >= 1')
+        net = actor.c_struct()
+        if actor.device != self.device:
+            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        out, ro, term = self._actor_record('rollout_qnet', self._QNET_RECORD, T, out, with_obs, terminal_obs)
+        rc = self.lib.s2d_rollout_qnet(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
         _capi.check(self.lib, rc, 's2d_rollout_qnet')
+        self._keep = (actor, out)
+        return out
+
+    def rollout_actor(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
+        """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.DeterministicActor) tanh policy on
+        the envs' own observations, with epsilon-random exploration and optional Gaussian action noise, evaluated in-kernel
+        (s2d_rollout_actor; continuous and turning engines).  Returns the record dict of rollout() (action float32 [T,N,1] or
+        [T,N,4]: the noisy, clipped action); terminal_obs, graph capture and `out` caching as in rollout_qnet()."""
+        T = int(n_steps)
+        if T < 1:
+            raise ValueError('rollout_actor needs n_steps >= 1')
+        net = actor.c_struct()
+        if actor.device != self.device:
+            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        t = self.cfg.task
+        if not t.use_continuous_action:
+            raise ValueError('rollout_actor needs a continuous-action engine (use_continuous_action=True); use rollout_qnet')
+        a = 4 if t.use_turning else 1
+        if actor.n_out != a:
+            raise ValueError(f'a {"turning" if t.use_turning else "continuous"} engine needs an actor with n_out = {a}, got {actor.n_out}')
+        record = dict(self._QNET_RECORD, action=(torch.float32, (a,)))
+        out, ro, term = self._actor_record('rollout_actor', record, T, out, with_obs, terminal_obs)
+        rc = self.lib.s2d_rollout_actor(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
+        _capi.check(self.lib, rc, 's2d_rollout_actor')
         self._keep = (actor, out)
         return out
 

@@ -13,6 +13,7 @@ first observation of its next episode; the last one of the old episode is in
 import torch
 
 from . import _capi
+from .actor import DeterministicActor
 from .engine import Engine, make_config
 from .spaces import reach_ball_spaces
 from .state_view import StateView, world_model_tensors
@@ -56,10 +57,13 @@ class Soccer2DVecEnv:
 
     def rollout(self, n_steps, actions=None, out=None, with_obs=True, policy=None, terminal_obs=False):
         """T fused steps.  policy=None: `actions` (or the in-kernel random policy); policy=QNetActor: the actor's epsilon-greedy
-        actions, evaluated in-kernel (Engine.rollout_qnet; terminal_obs=True records the observations episodes ended on)."""
+        actions, evaluated in-kernel (Engine.rollout_qnet; terminal_obs=True records the observations episodes ended on);
+        policy=DeterministicActor: its tanh policy with exploration and action noise (Engine.rollout_actor)."""
         if policy is not None:
             if actions is not None:
                 raise ValueError('give either actions or policy, not both')
+            if isinstance(policy, DeterministicActor):
+                return self.engine.rollout_actor(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
             return self.engine.rollout_qnet(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
         if terminal_obs:
             raise ValueError('terminal_obs=True records the fused actor\'s terminal observations: it needs policy=QNetActor')

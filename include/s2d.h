@@ -16,6 +16,8 @@
  *                              (T fused steps, random policy or caller actions)
  *   s2d_rollout_qnet           DQN("MlpPolicy").predict inside SB3's collect_rollouts  dqn_stable_baselines3.py:36-49
  *                              (T fused steps, epsilon-greedy actions of the caller's Q-network, in-kernel)
+ *   s2d_rollout_actor          DDPG / TD3 actor.mu + NormalActionNoise inside SB3's collect_rollouts
+ *                              ddpg_stable_baselines3.py (T fused steps, the caller's tanh policy, in-kernel)
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -192,6 +194,19 @@ typedef struct S2DQNet {
   const float *epsilon;
 } S2DQNet;
 
+/* The caller's deterministic actor for s2d_rollout_actor (DESIGN.md sections 4, 5): a = tanh(W3 relu(W2 relu(W1 x + b1) + b2)
+ * + b3), SB3's DDPG / TD3 actor.mu.  hidden1 / hidden2 in {16, 32, ..., 128} (the weights live in LDS; SB3's default
+ * net_arch=[400, 300] does not fit: policy_kwargs=dict(net_arch=[64, 64])); n_out = 1 (use_continuous_action, not turning) or
+ * 4 (use_turning).  params as S2DQNet's (W3[n_out][H2], b3[n_out]), 16-byte aligned; epsilon: one fp32 device word; noise:
+ * fp32 device buffer [2][n_out] = (mu, sigma) of the Gaussian action noise, required when noise_kind = 1 (0: no action noise,
+ * noise may be NULL).  params, epsilon and noise are read when the kernel runs; noise_kind selects the instantiation.  */
+typedef struct S2DActorNet {
+  int32_t hidden1, hidden2, n_out, noise_kind;
+  const float *params;
+  const float *epsilon;
+  const float *noise;
+} S2DActorNet;
+
 /* Derived protobuf-mirroring fields that are not plain state words (row T1).  Each array
  * is [N]; NULL pointers are skipped.                                                       */
 typedef struct S2DWorldModel {
@@ -256,6 +271,19 @@ int s2d_rollout(S2DHandle h, int n_steps, const void *actions_dev, int action_ki
  * done[t][i] (the observation the episode ended on).  Rejected without a launch: continuous / turning engines, widths not in
  * {16, ..., 128} step 16, n_actions != action_space_size or > 64, NULL or misaligned params / epsilon, n_steps < 1. */
 int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+/* n_steps >= 1 cycles fused in ONE launch (continuous or turning engines) whose action at every cycle is the caller's tanh
+ * policy on the env's observation, per env and step at its policy_step k (advanced by one every step):
+ *   explore (as s2d_rollout_qnet's) -> S2D_ACT_RANDOM's draw for the mode, without action noise (eps = 1 is
+ *             s2d_rollout(NULL, S2D_ACT_RANDOM) bit for bit);
+ *   else      a_j = tanh_spec(y_j), with noise_kind = 1 clip(tanh_spec(y_j) + (mu_j + sigma_j z_j)) (one fmaf), clip to [-1, 1],
+ *             z from Box-Muller on Philox block 3 of stream POLICY: turning z0..z3 of the block at counter k, continuous
+ *             z_{k & 3} of the block at counter k >> 2.
+ * The action then goes through the mode's action map (turning: the softmax and the SELECT draw).  `out` as for s2d_rollout
+ * (action = float[T][N][1] | float[T][N][4]: the noisy, clipped action, what SB3's replay buffer stores); terminal_obs as for
+ * s2d_rollout_qnet.  Rejected without a launch: discrete engines, n_out != the mode's A, widths not in {16, ..., 128} step
+ * 16, noise_kind not in {0, 1}, NULL or misaligned params / epsilon / noise (noise only with kind 1), n_steps < 1, a network
+ * that does not fit the LDS. */
+int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
@@ -292,7 +320,10 @@ int s2d_set_seed(S2DHandle h, uint64_t seed, void *stream);
  * 11 the S2D_NOISE_RCSSSERVER draw of one commanded cycle (Philox block 2 of stream 3 at counter k; each word w ->
  *   (w >> 8) * 2^-24 * 2 - 1, in [-1, 1)): in = uint32[n][4] = global env id lo, hi, counter k, seed (low word)
  *   -> out[n][4] = player c_x, c_y, ball c_x, c_y (the velocity gains c * rand * |v| per axis);
- * 12 the same for the command-less cycle of a reset (block 2 of stream 5, counter = the reset's episode key). */
+ * 12 the same for the command-less cycle of a reset (block 2 of stream 5, counter = the reset's episode key).
+ * The primitives of s2d_rollout_actor (DESIGN.md sections 4, 5): 13 tanh_spec (in[n] -> out[n]), 14 log_spec (in[n] -> out[n]),
+ * 15 the Gaussian block of its action noise (Box-Muller on Philox block 3 of stream POLICY): in = uint32[n][4] = global env id
+ *   lo, hi, counter, seed (low word) -> out[n][4] = z0..z3. */
 int s2d_debug_eval(int op, const void *in_dev, void *out_dev, int64_t n, void *stream);
 
 #ifdef __cplusplus
