@@ -20,8 +20,10 @@
 // reads); the parameter buffer and epsilon are read when the kernel runs, so a captured graph acts with what they hold at replay.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <mutex>
+#include <string>
 
 #include "s2d_kernels.h"
 
@@ -176,26 +178,9 @@ S2D_DEV Action4 tanh_action(const S2DHot& p, const float* __restrict__ y, const 
 S2D_DEV const float* actor_noise() { return nullptr; }
 S2D_DEV const float* actor_noise(const float* p) { return p; }
 
-// The fused rollout of both actors.  MODE = S2D_MODE_DISCRETE: the Q-network's epsilon-greedy argmax (s2d_rollout_qnet);
-// CONT1 / TURN4: the deterministic tanh policy with epsilon-random exploration and optional Gaussian action noise (GAUSS,
-// s2d_rollout_actor).  One body, so that both share the prologue, the simulation, the records and the epilogue.  The noise
-// buffer is a trailing argument pack, empty for the Q-actor, so that its kernel arguments, and its code, stay as they were.
-template <int MODE, int NK, bool GAUSS, typename... Noise>
-__global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
-                                                                         float* __restrict__ S, int64_t stride, int64_t n,
-                                                                         int n_steps, QNetDims d, const float* __restrict__ params,
-                                                                         const float* __restrict__ eps_dev, RolloutOut ro,
-                                                                         float* __restrict__ term_rec, StepOut o, int wave_words,
-                                                                         Noise... noise_arg) {
-  const float* __restrict__ noise = actor_noise(noise_arg...);
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  QS_DECL;
-  const S2DHot p = hot_in_vgprs(p_sgpr);
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t wave_first = i - lane;
-
-  // ---- the network in fragment order (block-wide, once per launch)
+// the caller's parameters (nn.Sequential order: W1 [h1][10], b1, W2 [h2][h1], b2, W3 [na][h2], b3) into the block's LDS in
+// fragment order, then b1 | b2 | b3 padded with zeros to na16 (block-wide: every thread of the block takes part)
+S2D_DEV void net_pack(const QNetDims& d, const float* __restrict__ params, float* __restrict__ smem) {
   const int f1 = w1_frags(d), f2 = w2_frags(d), f3 = w3_frags(d);
   const int nfrag = f1 + f2 + f3;
   const int o_b1 = 10 * d.h1, o_w2 = o_b1 + d.h1, o_b2 = o_w2 + d.h2 * d.h1, o_w3 = o_b2 + d.h2, o_b3 = o_w3 + d.na * d.h2;
@@ -223,8 +208,34 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot 
     else v = (j - d.h1 - d.h2 < d.na) ? params[o_b3 + j - d.h1 - d.h2] : 0.0f;
     bias[j] = v;
   }
-  const int shared_words = (nfrag * kWave + d.h1 + d.h2 + d.na16 + 3) & ~3;
-  float* const wbase = smem + shared_words + wv * wave_words;
+}
+// words of the block-shared part of the LDS (fragments and biases, rounded up to 16 bytes); the waves' parts follow
+S2D_DEV int net_shared_words(const QNetDims& d) {
+  return ((w1_frags(d) + w2_frags(d) + w3_frags(d)) * kWave + d.h1 + d.h2 + d.na16 + 3) & ~3;
+}
+
+// The fused rollout of both actors.  MODE = S2D_MODE_DISCRETE: the Q-network's epsilon-greedy argmax (s2d_rollout_qnet);
+// CONT1 / TURN4: the deterministic tanh policy with epsilon-random exploration and optional Gaussian action noise (GAUSS,
+// s2d_rollout_actor).  One body, so that both share the prologue, the simulation, the records and the epilogue.  The noise
+// buffer is a trailing argument pack, empty for the Q-actor, so that its kernel arguments, and its code, stay as they were.
+template <int MODE, int NK, bool GAUSS, typename... Noise>
+__global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
+                                                                         float* __restrict__ S, int64_t stride, int64_t n,
+                                                                         int n_steps, QNetDims d, const float* __restrict__ params,
+                                                                         const float* __restrict__ eps_dev, RolloutOut ro,
+                                                                         float* __restrict__ term_rec, StepOut o, int wave_words,
+                                                                         Noise... noise_arg) {
+  const float* __restrict__ noise = actor_noise(noise_arg...);
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  QS_DECL;
+  const S2DHot p = hot_in_vgprs(p_sgpr);
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+
+  // ---- the network in fragment order (block-wide, once per launch)
+  net_pack(d, params, smem);
+  float* const wbase = smem + net_shared_words(d) + wv * wave_words;
   float* const ha = wbase;
   float* const hb = ha + 16 * d.pitch;
   float* const qv = hb + 16 * d.pitch;
@@ -340,7 +351,36 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot 
   QS_STORE();
 }
 
-// host side (same library, hidden symbol; the C entry point and its argument checks are in s2d_engine.hip)
+// diagnostic (s2d_debug_net_forward): the rollout's network on caller observations.  The same packing, LDS layout and
+// net_forward as s2d_reach_actor_rollout_kernel; the observation tile holds obs[i] for the wave's envs i < n and zero rows past
+// n; y[i][0 .. na-1] = the output layer's pre-activations, greedy[i] = their argmax.
+__global__ __launch_bounds__(kBlock) void s2d_debug_net_forward_kernel(QNetDims d, const float* __restrict__ params,
+                                                                       const float* __restrict__ obs, int64_t n, float* __restrict__ y,
+                                                                       int32_t* __restrict__ greedy, int wave_words) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+  net_pack(d, params, smem);
+  float* const ha = smem + net_shared_words(d) + wv * wave_words;
+  float* const hb = ha + 16 * d.pitch;
+  float* const qv = hb + 16 * d.pitch;
+  float* const tile = qv + kWave * d.qpitch;
+  __syncthreads();
+  if (wave_first >= n) return;
+  const bool active = i < n;
+#pragma unroll
+  for (int k = 0; k < S2D_OBS_DIM; ++k) tile[lane * S2D_OBS_DIM + k] = active ? obs[i * S2D_OBS_DIM + k] : 0.0f;
+  wave_lds_fence();
+  const int best = net_forward<true>(d, smem, ha, hb, qv, tile, lane);
+  if (active) {
+    for (int a = 0; a < d.na; ++a) y[i * d.na + a] = qv[lane * d.qpitch + a];
+    greedy[i] = best;
+  }
+}
+
+// host side (same library, hidden symbol; the rollouts' C entry points and their argument checks are in s2d_engine.hip,
+// s2d_debug_net_forward is at the end of this file)
 static constexpr size_t kLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all of it available to one workgroup
 static constexpr int kMaxDevices = 64;
 using QNetKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut,
@@ -365,8 +405,9 @@ static bool plan_lds(int h1, int h2, int na, QNetDims& d, int& wave_words, int& 
 }
 
 // the dynamic-LDS limit is a per-device property of the function: set it once per (device, instantiation `slot`), under a lock
-// (engines on several devices may be driven from several threads); the caller has made the engine's device current
-static constexpr int kActorSlots = 3 + 2 * 3 * 2;
+// (engines on several devices may be driven from several threads); the caller has made the engine's device current.  Slots:
+// the Q-actor's 3, the tanh actor's 2 x 3 x 2, then s2d_debug_net_forward's
+static constexpr int kActorSlots = 3 + 2 * 3 * 2 + 1;
 static bool allow_lds(const void* fn, int slot) {
   static std::mutex attr_mu;
   static bool attr_set[kMaxDevices][kActorSlots] = {};
@@ -425,4 +466,45 @@ extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2D
     std::snprintf(name, 96, "s2d_reach_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,h1=%d,h2=%d,a=%d,waves=%d>",
                   m ? "turn4" : "cont1", nk, gauss, h1, h2, na, waves);
   return 0;
+}
+
+// errors share the thread-local text of s2d_last_error() (defined in s2d_engine.hip)
+extern "C" void s2d_internal_set_error(const char* msg);
+
+S2D_API int s2d_debug_net_forward(int h1, int h2, int na, const void* params_dev, const void* obs_dev, int64_t n, void* y_dev,
+                                  void* greedy_dev, char* name, void* stream) {
+  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
+  const char* err = nullptr;
+  if (!width_ok(h1) || !width_ok(h2)) err = "s2d_debug_net_forward: hidden widths must be multiples of 16 in [16, 128]";
+  else if (na < 1 || na > 64) err = "s2d_debug_net_forward: na must be in [1, 64]";
+  else if (n < 1 || n > INT32_MAX) err = "s2d_debug_net_forward: n must be in [1, 2^31 - 1]";
+  else if (!params_dev || (reinterpret_cast<uintptr_t>(params_dev) & 15u))
+    err = "s2d_debug_net_forward: params must be a non-NULL, 16-byte aligned device pointer";
+  else if (!obs_dev || !y_dev || !greedy_dev ||
+           ((reinterpret_cast<uintptr_t>(obs_dev) | reinterpret_cast<uintptr_t>(y_dev) | reinterpret_cast<uintptr_t>(greedy_dev)) & 3u))
+    err = "s2d_debug_net_forward: obs, y and greedy must be non-NULL, 4-byte aligned device pointers";
+  if (err) { s2d_internal_set_error(err); return S2D_EINVAL; }
+  QNetDims d;
+  int wave_words, waves;
+  size_t lds;
+  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) {
+    s2d_internal_set_error("s2d_debug_net_forward: the network does not fit the LDS of a workgroup");
+    return S2D_EINVAL;
+  }
+  if (!allow_lds(reinterpret_cast<const void*>(s2d_debug_net_forward_kernel), kActorSlots - 1)) {
+    s2d_internal_set_error("s2d_debug_net_forward: hipGetDevice or hipFuncSetAttribute failed");
+    return S2D_EHIP;
+  }
+  const int threads = waves * kWave;
+  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
+  hipLaunchKernelGGL(s2d_debug_net_forward_kernel, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), d,
+                     static_cast<const float*>(params_dev), static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev),
+                     static_cast<int32_t*>(greedy_dev), wave_words);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    s2d_internal_set_error((std::string("s2d_debug_net_forward: launch: ") + hipGetErrorString(e)).c_str());
+    return S2D_EHIP;
+  }
+  if (name) std::snprintf(name, 96, "s2d_debug_net_forward_kernel<h1=%d,h2=%d,a=%d,waves=%d>", h1, h2, na, waves);
+  return S2D_OK;
 }

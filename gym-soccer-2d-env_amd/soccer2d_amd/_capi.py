@@ -147,6 +147,8 @@ PROTOTYPES = (
     ('s2d_validate_state', C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_set_seed', C.c_int, (C.c_void_p, C.c_uint64, C.c_void_p)),
     ('s2d_debug_eval', C.c_int, (C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)),
+    ('s2d_debug_net_forward', C.c_int, (C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_char_p, C.c_void_p)),
 )
 
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

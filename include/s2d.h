@@ -325,6 +325,15 @@ int s2d_set_seed(S2DHandle h, uint64_t seed, void *stream);
  * 15 the Gaussian block of its action noise (Box-Muller on Philox block 3 of stream POLICY): in = uint32[n][4] = global env id
  *   lo, hi, counter, seed (low word) -> out[n][4] = z0..z3. */
 int s2d_debug_eval(int op, const void *in_dev, void *out_dev, int64_t n, void *stream);
+/* diagnostic: the fused actors' network (s2d_rollout_qnet / s2d_rollout_actor) on caller observations, with the rollout
+ * kernels' weight packing, LDS plan and matrix-core layers, so that tests can compare its output bit for bit with the fmaf
+ * spec (DESIGN.md sections 4, 5).  params_dev = the network of S2DQNet.params (10-h1-h2-na, nn.Sequential order, 16-byte
+ * aligned); obs_dev = float[n][10]; y_dev = float[n][na] <- the output layer's pre-activations; greedy_dev = int32[n] <- their
+ * argmax (ties: lowest index; a NaN never replaces the best).  name = NULL or >= 96 bytes <- the kernel's name with its waves
+ * per workgroup.  S2D_EINVAL without a launch: widths not in {16, ..., 128} step 16, na not in 1..64, n not in 1..2^31 - 1,
+ * NULL or misaligned pointers. */
+int s2d_debug_net_forward(int h1, int h2, int na, const void *params_dev, const void *obs_dev, int64_t n, void *y_dev,
+                          void *greedy_dev, char *name, void *stream);
 
 #ifdef __cplusplus
 }

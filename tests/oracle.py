@@ -198,6 +198,7 @@ def reset_from_draws(cfg, draws, precision='f64'):
 
 
 STATE_FIELDS = _capi.STATE_FIELDS
+UINT32_FIELDS = (STATE_FIELDS.index('policy_step'), STATE_FIELDS.index('episode'))   # uint32 in the engine, int32 planes
 
 
 class OracleEngine:
@@ -303,6 +304,8 @@ class OracleEngine:
         idx = STATE_FIELDS.index(field) if isinstance(field, str) else int(field)
         out = np.zeros(self.n)
         assert self.L.s2do_get_state(self.h, idx, _dp(out)) == 0
+        if idx in UINT32_FIELDS:          # uint32 counters: exact, in the engine's int32 view (2^31 .. 2^32 - 1 are negative)
+            return out.astype(np.int64).astype(np.uint32).view(np.int32)
         if idx >= 15:
             return out.astype(np.int32)
         return out.astype(self.L._np_real)
@@ -315,9 +318,26 @@ class OracleEngine:
         self.L.s2do_last_tries(self.h, out.ctypes.data)
         return out
 
+    @staticmethod
+    def _row(vals):
+        """19 state words for s2do_set_env: the uint32 counters as their non-negative value (taken modulo 2^32)"""
+        a = np.asarray(vals, dtype=np.float64).copy()
+        for f in UINT32_FIELDS:
+            a[f] = float(int(vals[f]) & 0xFFFFFFFF)
+        return a
+
     def set_env(self, i, **kw):
         cur = [float(self.state(f)[i]) for f in STATE_FIELDS]
         for k, v in kw.items():
             cur[STATE_FIELDS.index(k)] = float(v)
-        a = np.asarray(cur, dtype=np.float64)
+        a = self._row(cur)
         assert self.L.s2do_set_env(self.h, int(i), _dp(a)) == 0
+
+    def set_state(self, field, values):
+        """overwrite one state field of every env (values[n]; uint32 counters modulo 2^32)"""
+        rows = np.stack([self.state(f).astype(np.float64) for f in STATE_FIELDS], axis=1)
+        idx = STATE_FIELDS.index(field)
+        v = np.broadcast_to(np.asarray(values), (self.n,))
+        rows[:, idx] = (v.astype(np.int64) & 0xFFFFFFFF) if idx in UINT32_FIELDS else v
+        for i in range(self.n):
+            assert self.L.s2do_set_env(self.h, i, _dp(self._row(rows[i]))) == 0

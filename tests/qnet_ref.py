@@ -73,9 +73,10 @@ def philox(c0, c1, c2, c3, k0, k1):
 
 
 def policy_word(seed, gid, k, block):
-    """word k & 3 of Philox block `block` of stream POLICY at counter k >> 2, per env (gid, k: int arrays)"""
+    """word k & 3 of Philox block `block` of stream POLICY at counter k >> 2, per env (gid, k: int arrays; k is the uint32
+    policy counter, taken modulo 2^32, so the engine's int32 view and k0 + t past 2^32 both give the device's counter)"""
     gid = np.asarray(gid, dtype=np.uint64)
-    k = np.asarray(k, dtype=np.uint64)
+    k = (np.asarray(k).astype(np.int64) & 0xFFFFFFFF).astype(np.uint64)
     ctr = np.broadcast_to(k >> np.uint64(2), gid.shape)
     w = philox(gid & np.uint64(0xFFFFFFFF), gid >> np.uint64(32), ctr, np.full(gid.shape, (ST_POLICY << 16) | block, np.uint64),
                seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)

@@ -123,13 +123,25 @@ def _noise_of(actor):
     return None if actor.noise_kind == 0 else torch.stack([actor.noise_mean, actor.noise_sigma]).cpu().numpy()
 
 
-def _closed_loop_parity(ref, n, T, mode, eps, noise, sigma, warm=5, seed=0x5EED, h1=64, h2=64):
+def int32_view(k):
+    """uint32 counters (taken modulo 2^32) as the engine's int32 plane holds them"""
+    return (np.asarray(k, dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def _closed_loop_parity(ref, n, T, mode, eps, noise, sigma, warm=5, seed=0x5EED, h1=64, h2=64, k_set=None):
     na = NA[mode]
     eng = _engine(n, mode, noise, seed=seed)
     orc = _oracle(n, mode, noise, seed=seed)
     eng.reset(); orc.reset()
     if warm:
         eng.rollout(warm); orc.rollout(warm)
+    if k_set is not None:
+        eng.policy_step.copy_(torch.from_numpy(int32_view(k_set)).to('cuda:0'))
+        if isinstance(orc, _StepEngine):
+            orc.e.policy_step.copy_(torch.from_numpy(int32_view(k_set)).to('cuda:0'))
+        else:
+            orc.set_state('policy_step', k_set)
+        same(eng.policy_step, orc.state('policy_step'), 'policy_step set')
     actor = _actor(_mu(h1, h2, na, seed=n + T + na), eps, sigma)
     params = actor.params.cpu().numpy()
     k0 = eng.policy_step.cpu().numpy().astype(np.int64)
@@ -153,7 +165,7 @@ def _closed_loop_parity(ref, n, T, mode, eps, noise, sigma, warm=5, seed=0x5EED,
     for f in O.STATE_FIELDS:
         if f != 'policy_step':
             same(getattr(eng, f), orc.state(f), f'state.{f}')
-    same(eng.policy_step, (k0 + T).astype(np.int32), 'policy_step = k0 + T')
+    same(eng.policy_step, int32_view(k0 + T), 'policy_step = k0 + T (mod 2^32)')
     same(eng.obs, orc.obs(), 'obs'); same(eng.done, orc.done(), 'done'); same(eng.result, orc.result(), 'result')
     same(eng.stats[:4], orc.stats()[:4].astype(np.int64), 'stats')
     return out
@@ -168,6 +180,16 @@ def test_closed_loop_parity(ref, mode, noise, eps, sigma):
     assert int(out['done'].sum()) > 0
     a = out['action'].cpu().numpy()
     assert len(np.unique(a)) > 100 and (np.abs(a) <= 1).all()
+
+
+@pytest.mark.parametrize('mode,noise', [('cont1', 'lattice'), ('cont1', 'off'), ('turn4', 'lattice')])
+def test_policy_counter_wraps_past_2_31_and_2_32(ref, mode, noise):
+    """policy_step keys the exploration, the random action and the Gaussian noise (cont1: the block at k >> 2, cached over
+    four cycles): a launch that carries it across 2^31 (the int32 view turns negative) and 2^32 (the counter wraps, and with
+    it the cached block's counter) acts exactly as R.actions"""
+    n = 600
+    k = np.array([2 ** 32 - 1 - (i % 7) if i % 3 == 0 else 2 ** 31 - 2 for i in range(n)], dtype=np.int64)
+    _closed_loop_parity(ref, n, 40, mode, 0.1, noise, 0.3, warm=3, k_set=k)
 
 
 @pytest.mark.parametrize('mode', ['cont1', 'turn4'])
@@ -339,7 +361,7 @@ def test_ragged_sizes(ref, n):
     _closed_loop_parity(ref, n, 9, 'turn4', 0.1, 'lattice', 0.3, warm=3)
 
 
-@pytest.mark.parametrize('h1,h2', [(16, 16), (128, 128), (64, 32)])
+@pytest.mark.parametrize('h1,h2', [(16, 16), (128, 128), (64, 32), (48, 80), (112, 96)])
 @pytest.mark.parametrize('mode', ['cont1', 'turn4'])
 def test_other_shapes(ref, mode, h1, h2):
     _closed_loop_parity(ref, 1000, 6, mode, 0.1, 'lattice', 0.3, warm=2, h1=h1, h2=h2)

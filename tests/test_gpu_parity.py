@@ -547,6 +547,37 @@ def test_cycle_counter_wraps_past_int32():
 
 
 @pytest.mark.parametrize('ws', ['0', '1'])
+@pytest.mark.parametrize('name', ['noise-on', 'turning4'])
+def test_policy_counter_wraps_past_2_31_and_2_32(name, ws, monkeypatch):
+    """`policy_step` is a uint32 (an int32 plane) that keys every POLICY and noise draw; a 65 536-env actor run passes 2^31
+    in hours.  Across 2^31 (the int32 view turns negative) and 2^32 (the counter wraps) the random-policy rollout with noise
+    keeps matching the oracle bit for bit."""
+    monkeypatch.setenv('S2D_ROLLOUT_WS', ws)
+    kw = dict(CONFIGS[name]); kw['noise'] = True
+    n, T = 300, 40
+    eng, stepper, orc = _engine(n, **dict(kw)), _engine(n, **dict(kw)), _oracle(n, **dict(kw))
+    eng.reset(); stepper.reset(); orc.reset()
+    k = np.array([2 ** 32 - 1 - (i % 7) if i % 3 == 0 else 2 ** 31 - 2 for i in range(n)], dtype=np.int64)
+    view = (k & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    eng.policy_step.copy_(torch.from_numpy(view).to('cuda:0'))
+    stepper.policy_step.copy_(torch.from_numpy(view).to('cuda:0'))
+    orc.set_state('policy_step', k)
+    assert_state_same(eng, orc, 'set')
+    out, ref = eng.rollout(T), orc.rollout(T)
+    torch.cuda.synchronize()
+    for f in ('obs', 'action', 'reward', 'done', 'result'):
+        assert_same(out[f], ref[f], f'wrap {f}')
+    assert_state_same(eng, orc, 'wrap')
+    for t in range(T):                                   # the per-step API (s2d_step) across the same points
+        obs, _, done, _ = stepper.step(None)
+        assert_same(obs, ref['obs'][t], f'step t={t} obs')
+        assert_same(done, ref['done'][t], f'step t={t} done')
+    assert_state_same(stepper, orc, 'wrap stepwise')
+    assert_same(eng.policy_step, ((k + T) & 0xFFFFFFFF).astype(np.uint32).view(np.int32), 'policy_step = k0 + T (mod 2^32)')
+    assert int(eng.policy_step.min()) < 0 and int(eng.policy_step.max()) >= 0
+
+
+@pytest.mark.parametrize('ws', ['0', '1'])
 @pytest.mark.parametrize('seed', list(range(6)))
 def test_random_server_parameters_parity(seed, ws, monkeypatch):
     """Parity must not hinge on the stock parameter values: random ServerParam / task settings (speeds and

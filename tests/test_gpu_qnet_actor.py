@@ -118,7 +118,17 @@ def _record(eng, T, terminal=True):
     return out
 
 
-def _closed_loop_parity(ref, n, T, eps, noise, warm=5, seed=0x5EED, auto_reset=True, with_obs=True):
+def wrap_counters(n):
+    """policy_step values that cross 2^32 (every third env) and 2^31 (the others) within a 40-cycle launch"""
+    return np.array([2 ** 32 - 1 - (i % 7) if i % 3 == 0 else 2 ** 31 - 2 for i in range(n)], dtype=np.int64)
+
+
+def int32_view(k):
+    """uint32 counters (taken modulo 2^32) as the engine's int32 plane holds them"""
+    return (np.asarray(k, dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def _closed_loop_parity(ref, n, T, eps, noise, warm=5, seed=0x5EED, auto_reset=True, with_obs=True, k_set=None):
     kw = dict(seed=seed)
     eng = _engine(n, noise, auto_reset=auto_reset, **kw)
     orc = _oracle(n, noise, **kw) if auto_reset else O.OracleEngine(
@@ -126,6 +136,12 @@ def _closed_loop_parity(ref, n, T, eps, noise, warm=5, seed=0x5EED, auto_reset=T
     eng.reset(); orc.reset()
     if warm:
         eng.rollout(warm); orc.rollout(warm)
+    if k_set is not None:
+        eng.policy_step.copy_(torch.from_numpy(int32_view(k_set)).to('cuda:0'))
+        if isinstance(orc, _StepEngine):
+            orc.e.policy_step.copy_(torch.from_numpy(int32_view(k_set)).to('cuda:0'))
+        else:
+            orc.set_state('policy_step', k_set)
     net = _net(seed=n + T)
     actor = _actor(net, eps)
     params = actor.params.cpu().numpy()
@@ -156,10 +172,19 @@ def _closed_loop_parity(ref, n, T, eps, noise, warm=5, seed=0x5EED, auto_reset=T
         if f == 'policy_step':
             continue
         same(getattr(eng, f), orc.state(f), f'state.{f}')
-    same(eng.policy_step, (k0 + T).astype(np.int32), 'policy_step = k0 + T')
+    same(eng.policy_step, int32_view(k0 + T), 'policy_step = k0 + T (mod 2^32)')
     same(eng.obs, orc.obs(), 'obs'); same(eng.done, orc.done(), 'done'); same(eng.result, orc.result(), 'result')
     same(eng.stats[:4], orc.stats()[:4].astype(np.int64), 'stats')
     return out
+
+
+@pytest.mark.parametrize('noise', ['lattice', 'square'])
+@pytest.mark.parametrize('eps', [0.1, 0.5])
+def test_policy_counter_wraps_past_2_31_and_2_32(ref, noise, eps):
+    """policy_step is a uint32 keying every POLICY and noise draw: an actor launch that carries it across 2^31 (the int32
+    view turns negative) and 2^32 (the counter wraps) acts and moves exactly as the oracle driven by Q.actions"""
+    n, T = 600, 40
+    _closed_loop_parity(ref, n, T, eps, noise, warm=3, k_set=wrap_counters(n))
 
 
 @pytest.mark.parametrize('noise', ['off', 'lattice', 'square'])
@@ -298,8 +323,8 @@ def test_greedy_agrees_with_a_float64_torch_forward():
     assert float(clear.float().mean()) > 0.9
 
 
-@pytest.mark.parametrize('h1,h2', [(16, 16), (128, 128), (64, 32)])
-@pytest.mark.parametrize('na', [1, 2, 64])
+@pytest.mark.parametrize('h1,h2', [(16, 16), (128, 128), (64, 32), (48, 80), (112, 96), (80, 112)])
+@pytest.mark.parametrize('na', [1, 2, 17, 33, 48, 64])
 def test_other_shapes(ref, h1, h2, na):
     n, T = 1000, 6
     eng = _engine(n, 'lattice', action_space_size=na)
@@ -350,3 +375,24 @@ def test_rejections_leave_the_state_unchanged():
         eng.rollout_qnet(4, QNetActor(64, 64, 8))
     torch.cuda.synchronize()
     assert torch.equal(before, eng.arena)
+
+
+@pytest.mark.parametrize('eps', [2.0 ** -33, 2.0 ** -32, 1 - 2.0 ** -24, 1.0, 1.5, -0.0, float('nan'), float('inf')],
+                         ids=['2^-33', '2^-32', '1-2^-24', '1', '1.5', '-0', 'nan', 'inf'])
+def test_epsilon_edges(ref, eps):
+    """the device threshold of epsilons at the edges (rounding to 0 or 1 in 2^32 units, 1 - ulp, >= 1, -0, NaN, inf): the
+    actions equal Q.actions bit for bit"""
+    n, T = 4096, 6
+    eng = _engine(n, 'lattice')
+    eng.reset()
+    actor = _actor(_net(seed=21), eps)
+    params = actor.params.cpu().numpy()
+    k0 = eng.policy_step.cpu().numpy().astype(np.int64)
+    obs = eng.obs.cpu().numpy()
+    r = eng.rollout_qnet(T, actor)
+    torch.cuda.synchronize()
+    gid = np.arange(n, dtype=np.int64)
+    for t in range(T):
+        want = Q.actions(ref, obs, params, 64, 64, 16, eps, eng.cfg.seed, gid, k0 + t)
+        same(r['action'][t], want, f'action[{t}]')
+        obs = r['obs'][t].cpu().numpy()

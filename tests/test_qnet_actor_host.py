@@ -175,3 +175,56 @@ def test_qnet_struct_and_export_match_the_header():
         import subprocess
         syms = subprocess.run(['nm', '-D', '--defined-only', lib], stdout=subprocess.PIPE, text=True).stdout
         assert re.search(r'\bs2d_rollout_qnet\b', syms)
+
+
+def test_policy_counter_helpers_wrap_modulo_2_32(ref):
+    """policy_step is a uint32 on the device, seen through an int32 plane: the helpers take every counter modulo 2^32, so
+    the int32 view (negative past 2^31), the uint32 value and k0 + t past 2^32 all name the same Philox words"""
+    seed, gid = 0x5EED, np.arange(6, dtype=np.int64)
+    k = np.array([2 ** 31 - 2, 2 ** 31, 2 ** 32 - 4, 2 ** 32 - 1, 0, 3], dtype=np.int64)
+    view = k.astype(np.uint32).view(np.int32).astype(np.int64)
+    assert (view[1:4] < 0).all()
+    for block in (0, 2):
+        w = Q.policy_word(seed, gid, k, block)
+        assert np.array_equal(w, Q.policy_word(seed, gid, view, block))
+        assert np.array_equal(w, Q.policy_word(seed, gid, k + 2 ** 32, block))
+        for i in range(k.size):
+            kk = int(k[i])
+            want = O.philox([int(gid[i]), 0, kk >> 2, (1 << 16) | block], [seed & 0xFFFFFFFF, seed >> 32])
+            assert int(w[i]) == want[kk & 3]
+    rs = np.random.RandomState(3)
+    p = _params(rs, 16, 16, 5)
+    x = rs.uniform(-1, 1, (6, 10)).astype(np.float32)
+    a = Q.actions(ref, x, p, 16, 16, 5, 0.5, seed, gid, k)
+    assert np.array_equal(a, Q.actions(ref, x, p, 16, 16, 5, 0.5, seed, gid, view))
+    assert np.array_equal(a, Q.actions(ref, x, p, 16, 16, 5, 0.5, seed, gid, k + 2 ** 32))
+
+
+def test_oracle_uint32_counters_are_exact_past_2_31():
+    """OracleEngine.state returns the uint32 counters exactly in the engine's int32 view, set_env / set_state pass them
+    to the oracle as non-negative values, and a rollout across 2^32 wraps policy_step modulo 2^32"""
+    n, T = 12, 9
+    orc = O.OracleEngine(O.make_config(**O.DQN_KWARGS), n, 'f32')
+    orc.reset()
+    k = np.array([2 ** 32 - 1 - (i % 7) if i % 3 == 0 else 2 ** 31 - 2 for i in range(n)], dtype=np.int64)
+    orc.set_state('policy_step', k)
+    want = k.astype(np.uint32).view(np.int32)
+    assert np.array_equal(orc.state('policy_step'), want)
+    orc.set_env(1, episode=int(want[0]))                                 # an int32 view round-trips too
+    orc.set_env(2, episode=2 ** 32 - 2)
+    ep = orc.state('episode')
+    assert ep[1] == want[0] and ep[2] == -2
+    orc.set_env(4, cycle=5)                                              # rewrites every field from state(): unchanged
+    assert np.array_equal(orc.state('policy_step'), want)
+    orc.rollout(T)
+    assert np.array_equal(orc.state('policy_step'), (k + T).astype(np.uint32).view(np.int32))
+    assert orc.state('episode')[2] in (-2, -1)
+
+
+def test_debug_net_forward_is_declared_and_bound():
+    from soccer2d_amd import _capi
+    hdr = open(os.path.join(ROOT, 'include', 's2d.h')).read()
+    assert re.search(r'int s2d_debug_net_forward\(int h1, int h2, int na, const void \*params_dev, const void \*obs_dev, '
+                     r'int64_t n, void \*y_dev,\s+void \*greedy_dev, char \*name, void \*stream\);', hdr)
+    protos = {p[0]: p for p in _capi.PROTOTYPES}
+    assert len(protos['s2d_debug_net_forward'][2]) == 10
