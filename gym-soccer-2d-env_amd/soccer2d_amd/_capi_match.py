@@ -12,6 +12,8 @@ GM_FIRST_HALF_OVER, GM_FOUL_CHARGE, GM_CATCH_FAULT, GM_IND_FREE_KICK, GM_GOALIE_
 GM_PENALTY_SETUP, GM_PENALTY_READY, GM_PENALTY_TAKEN, GM_PENALTY_MISS, GM_PENALTY_SCORE, GM_PENALTY_ONFIELD, GM_PENALTY_FOUL = 22, 23, 24, 25, 26, 28, 29   # :290-297
 GM_FOUL_PUSH, GM_FOUL_MULTIPLE_ATTACKER, GM_FOUL_BALL_OUT = 15, 16, 17   # :283-285 (an operator's calls: played like FoulCharge_)
 GM_PAUSE, GM_HUMAN = 12, 13                            # :280-281 (an operator's: written into eng.mode to hold a match)
+PENALTY_MODES = (GM_PENALTY_SETUP, GM_PENALTY_READY, GM_PENALTY_TAKEN, GM_PENALTY_MISS, GM_PENALTY_SCORE, GM_PENALTY_ONFIELD,
+                 GM_PENALTY_FOUL)                      # the shoot-out's modes (the kernel's set)
 GM_ILLEGAL_DEFENSE = 27                                # :295 (off in the stock server)
 GM_PENALTY_KICK = 10                                   # :278 (a foul inside the offender's own penalty area; the shoot-out modes are not built)
 GM_NAMES = {0: 'BeforeKickOff', 1: 'TimeOver', 2: 'PlayOn', 3: 'KickOff_', 4: 'KickIn_', 5: 'FreeKick_', 6: 'CornerKick_', 7: 'GoalKick_',

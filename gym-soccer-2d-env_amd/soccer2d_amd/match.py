@@ -248,7 +248,7 @@ class MatchEngine:
               'world_model.ball.velocity.x': self.vx[:, M.MATCH_BALL], 'world_model.ball.velocity.y': self.vy[:, M.MATCH_BALL]}
         # the penalty shoot-out (WorldModel.is_penalty_kick_mode, PenaltyKickState: idl/service.proto:336, 130-138), decoded from the
         # set-play word the engine keeps it in (include/s2d_match.h); "our" = the left team
-        pen = (self.mode >= M.GM_PENALTY_SETUP) & (self.mode <= 29)
+        pen = torch.isin(self.mode, torch.tensor(M.PENALTY_MODES, dtype=self.mode.dtype, device=self.mode.device))   # (27 = IllegalDefense_ is not one)
         w = torch.where(pen, self.set_play_taker, torch.zeros_like(self.set_play_taker))
         wm.update({'world_model.is_penalty_kick_mode': pen,
                    'world_model.penalty_kick_state.on_field_side': torch.where(pen, 2, 0),

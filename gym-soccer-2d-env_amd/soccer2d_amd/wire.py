@@ -10,6 +10,8 @@ order (what the reference's generated code emits), floats are 32-bit little-endi
 """
 import struct
 
+from ._capi_match import PENALTY_MODES
+
 # ---- field numbers (idl/service.proto) ---------------------------------------------------
 VEC = {'x': 1, 'y': 2, 'dist': 3, 'angle': 4}                                   # RpcVector2D :22-27
 BALL = {'position': 1, 'relative_position': 2, 'velocity': 5, 'dist_from_self': 16, 'angle_from_self': 17}   # :68-86
@@ -267,7 +269,7 @@ def match_state_bytes(engine, index, player):
     ball = dict(x=x[22], y=y[22], vx=vx[22], vy=vy[22], rel_x=x[22] - x[player], rel_y=y[22] - y[player])
     sl, sr = int(engine.score_left[index]), int(engine.score_right[index])
     mode, side, w = int(engine.mode[index]), int(engine.mode_side[index]), int(engine.set_play_taker[index])
-    pen = 22 <= mode <= 29                                 # the shoot-out: its state is in the set-play word (include/s2d_match.h)
+    pen = mode in PENALTY_MODES                            # the shoot-out (27 = IllegalDefense_ is not one): its state is in the set-play word (include/s2d_match.h)
     pk = None
     if pen:
         kicks, goals = ((w >> 12) & 15, (w >> 16) & 15), ((w >> 20) & 15, (w >> 24) & 15)

@@ -381,8 +381,11 @@ static int pen_over(const MP *p, int w) {
 
 typedef struct MatchStats { unsigned long long v[8]; } MatchStats;
 
+/* what happened in a cycle (s2dmo_events; test coverage only, nothing of the match depends on it) */
+enum { EV_KICK = 1, EV_TACKLE = 2, EV_CATCH = 4, EV_COLLIDE = 8, EV_BALL_COLLIDE = 16, EV_GOAL = 32 };
+
 /* one cycle of one match; act = [22][3] {cmd, a, b} */
-static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, MatchStats *st) {
+static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, MatchStats *st, uint32_t *ev) {
   const uint32_t cyc = (uint32_t)m->tick;                /* Philox counter: cycles since the reset, stopped ones included */
   const int mode0 = m->mode, side0 = m->mode_side;
   Obj *b = &m->o[BALL];
@@ -475,7 +478,7 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
     if (p->noise) add_noise(&o->vx, &o->vy, p->player_rand, rnd_u01(nz[0]), rnd_u01(nz[1]));
     o->x += o->vx; o->y += o->vy;
   }
-  if (caught_by >= 0) st->v[4]++;
+  if (caught_by >= 0) { st->v[4]++; *ev |= EV_CATCH; }
   if (caught_by >= 0 || hold_move >= 0)                    /* a catch / a move with the ball wins the cycle: kicks are dropped */
     for (int i = 0; i < NP; ++i) { kicked[i] = 0; by_kick[i] = 0; kx[i] = ky[i] = R(0.0); }
   if (foul_by >= 0) {                                      /* the victim goes down; a foul the referee saw is a card */
@@ -488,6 +491,7 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
   int any_kick = 0, last_kicker = -1, last_kick_cmd = -1, other_touch = 0;
   const int taker0 = m->set_play_taker & 0xff;            /* who may not touch the ball twice in a row (bit 8: his set play was an INDIRECT free kick) */
   for (int i = 0; i < NP; ++i) if (kicked[i]) {
+    *ev |= by_kick[i] ? EV_KICK : EV_TACKLE;
     bax += kx[i]; bay += ky[i]; any_kick = 1; last_kicker = i;
     if (by_kick[i]) last_kick_cmd = i;
     if (i + 1 != taker0) other_touch = 1;
@@ -550,6 +554,8 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
       m->o[i].x = sx[i] / (REAL)cnt[i]; m->o[i].y = sy[i] / (REAL)cnt[i]; collided[i] = 1;
     }
   }
+  for (int i = 0; i < NP; ++i) if (collided[i]) *ev |= EV_COLLIDE;
+  if (collided[BALL]) *ev |= EV_BALL_COLLIDE;
   for (int i = 0; i < NOBJ; ++i) if (collided[i]) { m->o[i].vx *= p->collision_vel_rate; m->o[i].vy *= p->collision_vel_rate; }
   int coll_touch_side = SIDE_NONE;
   if (touch_player >= 0 && (!is_setplay(mode0) || side_of(touch_player) == side0)) {
@@ -685,12 +691,12 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
       /* no goal directly from an indirect free kick (IndFreeKick_, idl/service.proto:289): while nobody but its taker has touched the
        * ball, a ball in the net is a ball over the goal line -- a goal kick for the defenders, by the branch below */
       } else if (!(m->set_play_taker & 0x100) && bx > p->half_l && R(fabs)(by) < p->goal_half_width) {       /* goal for the left team */
-        m->score_left += 1; m->reward_left = R(1.0); st->v[1]++;
+        m->score_left += 1; m->reward_left = R(1.0); st->v[1]++; *ev |= EV_GOAL;
         if (p->after_goal_wait > 0) restart(m, S2D_GM_AFTER_GOAL, SIDE_LEFT, bx, by);   /* the ball rests in the net */
         else { place_formation(m, SIDE_RIGHT); restart(m, S2D_GM_KICK_OFF, SIDE_RIGHT, R(0.0), R(0.0)); }
         m->last_touch_side = SIDE_NONE;
       } else if (!(m->set_play_taker & 0x100) && bx < -p->half_l && R(fabs)(by) < p->goal_half_width) {      /* goal for the right team */
-        m->score_right += 1; m->reward_left = R(-1.0); st->v[2]++;
+        m->score_right += 1; m->reward_left = R(-1.0); st->v[2]++; *ev |= EV_GOAL;
         if (p->after_goal_wait > 0) restart(m, S2D_GM_AFTER_GOAL, SIDE_RIGHT, bx, by);
         else { place_formation(m, SIDE_LEFT); restart(m, S2D_GM_KICK_OFF, SIDE_LEFT, R(0.0), R(0.0)); }
         m->last_touch_side = SIDE_NONE;
@@ -813,17 +819,21 @@ static void random_actions(const MP *p, uint64_t gid, uint32_t cyc, float *act) 
 }
 
 /* ------------------------------------------------------------------ vectorised engine */
-typedef struct S2DMOEngine { MP p; int64_t n; Match *m; MatchStats st; } S2DMOEngine;
+/* env_id: each env's Philox id (NULL: env_id_offset + e) -- a batch of states taken from different matches keeps their draws;
+ * ev: what happened in each env in the last cycle (EV_* bits) */
+typedef struct S2DMOEngine { MP p; int64_t n; Match *m; MatchStats st; int64_t *env_id; uint32_t *ev; } S2DMOEngine;
+static uint64_t env_gid(const S2DMOEngine *h, int64_t e) { return (uint64_t)(h->env_id ? h->env_id[e] : h->p.env_id_offset + e); }
 
 API S2DMOEngine *s2dmo_create(const S2DMatchConfig *cfg, int64_t n) {
   if (!cfg || n <= 0) return NULL;
   S2DMOEngine *h = (S2DMOEngine *)calloc(1, sizeof *h);
   mp_from_config(cfg, &h->p); h->n = n;
   h->m = (Match *)calloc((size_t)n, sizeof(Match));
+  h->ev = (uint32_t *)calloc((size_t)n, sizeof(uint32_t));
   for (int64_t e = 0; e < n; ++e) match_reset(&h->p, &h->m[e]);
   return h;
 }
-API void s2dmo_destroy(S2DMOEngine *h) { if (h) { free(h->m); free(h); } }
+API void s2dmo_destroy(S2DMOEngine *h) { if (h) { free(h->m); free(h->env_id); free(h->ev); free(h); } }
 API void s2dmo_reset(S2DMOEngine *h, const uint8_t *mask) {
   for (int64_t e = 0; e < h->n; ++e) if (!mask || mask[e]) match_reset(&h->p, &h->m[e]);
 }
@@ -836,8 +846,9 @@ API void s2dmo_step(S2DMOEngine *h, const float *actions) {
     for (int64_t e = 0; e < h->n; ++e) {
       float buf[NP * 3];
       const float *a = actions ? actions + (size_t)e * NP * 3 : buf;
-      if (!actions) random_actions(&h->p, (uint64_t)(h->p.env_id_offset + e), (uint32_t)h->m[e].tick, buf);
-      match_step(&h->p, &h->m[e], (uint64_t)(h->p.env_id_offset + e), a, &loc);
+      if (!actions) random_actions(&h->p, env_gid(h, e), (uint32_t)h->m[e].tick, buf);
+      h->ev[e] = 0;
+      match_step(&h->p, &h->m[e], env_gid(h, e), a, &loc, &h->ev[e]);
     }
 #pragma omp critical
     for (int k = 0; k < 8; ++k) tot.v[k] += loc.v[k];
@@ -920,5 +931,46 @@ API void s2dmo_relative(const S2DMOEngine *h, float *dist, float *angle) {
 }
 API void s2dmo_random_actions(const S2DMOEngine *h, float *out) {
   for (int64_t e = 0; e < h->n; ++e)
-    random_actions(&h->p, (uint64_t)(h->p.env_id_offset + e), (uint32_t)h->m[e].tick, out + (size_t)e * NP * 3);
+    random_actions(&h->p, env_gid(h, e), (uint32_t)h->m[e].tick, out + (size_t)e * NP * 3);
 }
+/* Load every Match word of envs e0 .. e0 + count - 1 from planes laid out like the device buffers (MATCH_BUFFER_FIELDS of
+ * soccer2d_amd/_capi_match.py, stats left out), so that a device snapshot goes straight in:
+ *   0-8   x y vx vy body stamina effort recovery stamina_capacity   float [count][24]
+ *   9-10  tackle_cycles catch_ban                                    int32 [count][24]
+ *   11-24 cycle mode mode_side score_left score_right last_touch_side setplay_timer offside_mask ball_holder goalie_moves
+ *         set_play_taker last_kicker stopped_cycle tick               int32 [count]
+ *   25    card int32 [count][24];  26 reward_left float [count];  27 done uint8 [count];  28-29 nearest_left nearest_right int32 [count]
+ * Slot 23 of the object planes is padding and is not read. */
+enum { LOAD_PLANES = 30 };
+API int s2dmo_load(S2DMOEngine *h, int64_t e0, int64_t count, const void *const *planes) {
+  if (e0 < 0 || count < 0 || e0 + count > h->n) return -1;
+  for (int k = 0; k < LOAD_PLANES; ++k) if (!planes[k]) return -2;
+  for (int64_t j = 0; j < count; ++j) {
+    Match *m = &h->m[e0 + j];
+    for (int s = 0; s < NOBJ; ++s) {
+      const size_t q = (size_t)j * S2D_MATCH_SLOTS + (size_t)s;
+      Obj *o = &m->o[s];
+      o->x = (REAL)((const float *)planes[0])[q]; o->y = (REAL)((const float *)planes[1])[q];
+      o->vx = (REAL)((const float *)planes[2])[q]; o->vy = (REAL)((const float *)planes[3])[q];
+      o->body = (REAL)((const float *)planes[4])[q]; o->stamina = (REAL)((const float *)planes[5])[q];
+      o->effort = (REAL)((const float *)planes[6])[q]; o->recovery = (REAL)((const float *)planes[7])[q];
+      o->capacity = (REAL)((const float *)planes[8])[q];
+      o->tackle = ((const int32_t *)planes[9])[q]; o->catch_ban = ((const int32_t *)planes[10])[q];
+      o->card = ((const int32_t *)planes[25])[q];
+    }
+    int32_t w[14];
+    for (int k = 0; k < 14; ++k) w[k] = ((const int32_t *)planes[11 + k])[j];
+    m->cycle = w[0]; m->mode = w[1]; m->mode_side = w[2]; m->score_left = w[3]; m->score_right = w[4]; m->last_touch_side = w[5];
+    m->setplay_timer = w[6]; m->offside_mask = w[7]; m->ball_holder = w[8]; m->goalie_moves = w[9]; m->set_play_taker = w[10];
+    m->last_kicker = w[11]; m->stopped_cycle = w[12]; m->tick = w[13];
+    m->reward_left = (REAL)((const float *)planes[26])[j]; m->done = ((const uint8_t *)planes[27])[j];
+    m->nearest_left = ((const int32_t *)planes[28])[j]; m->nearest_right = ((const int32_t *)planes[29])[j];
+  }
+  return 0;
+}
+/* the Philox id of every env (n of them; NULL: env_id_offset + e again) */
+API void s2dmo_set_env_ids(S2DMOEngine *h, const int64_t *ids) {
+  free(h->env_id); h->env_id = NULL;
+  if (ids) { h->env_id = (int64_t *)malloc((size_t)h->n * sizeof(int64_t)); memcpy(h->env_id, ids, (size_t)h->n * sizeof(int64_t)); }
+}
+API const uint32_t *s2dmo_events(const S2DMOEngine *h) { return h->ev; }

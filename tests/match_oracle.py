@@ -68,38 +68,45 @@ def make_match_config(seed=0x5EED, env_id_offset=0, auto_reset=1, noise=0, serve
     return cfg
 
 
-_lib = None
+# the per-env words of MATCH_BUFFER_FIELDS (soccer2d_amd/_capi_match.py) in their order, stats left out: what s2dmo_load reads
+STATE_FIELDS = tuple(name for (name, _t, _d, trail) in M.MATCH_BUFFER_FIELDS if trail is not None)
+FLOAT_FIELDS = tuple(name for (name, _t, d, trail) in M.MATCH_BUFFER_FIELDS if d == 'float32')
+EV_KICK, EV_TACKLE, EV_CATCH, EV_COLLIDE, EV_BALL_COLLIDE, EV_GOAL = 1, 2, 4, 8, 16, 32    # s2dmo_events bits
+
+_libs = {}
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        O.build_oracle()
-        path = os.path.join(O.ORACLE_DIR, '_build', 'libs2d_match_oracle_f32.so')
-        if not os.path.exists(path):
-            import subprocess
-            subprocess.run(['make', '-C', O.ORACLE_DIR], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-        L = C.CDLL(path)
-        cfgp = C.POINTER(M.S2DMatchConfig)
-        L.s2dmo_create.argtypes = [cfgp, C.c_int64]; L.s2dmo_create.restype = C.c_void_p
-        L.s2dmo_destroy.argtypes = [C.c_void_p]; L.s2dmo_destroy.restype = None
-        L.s2dmo_reset.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_reset.restype = None
-        L.s2dmo_step.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_step.restype = None
-        L.s2dmo_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]; L.s2dmo_get.restype = C.c_int
-        L.s2dmo_set_obj.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)]; L.s2dmo_set_obj.restype = C.c_int
-        L.s2dmo_set_game.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]; L.s2dmo_set_game.restype = C.c_int
-        L.s2dmo_set_touch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int]; L.s2dmo_set_touch.restype = C.c_int
-        L.s2dmo_set_card.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int]; L.s2dmo_set_card.restype = C.c_int
-        L.s2dmo_stats.argtypes = [C.c_void_p]; L.s2dmo_stats.restype = C.POINTER(C.c_ulonglong)
-        L.s2dmo_random_actions.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_random_actions.restype = None
-        L.s2dmo_relative.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; L.s2dmo_relative.restype = None
-        _lib = L
-    return _lib
+def lib(precision='f32'):
+    """the fp32 spec build ('f32': the kernels' parity target) or the fp64 libm build ('f64') of s2d_match_oracle.c"""
+    if precision in _libs:
+        return _libs[precision]
+    if precision not in ('f32', 'f64'):
+        raise ValueError(precision)
+    O.build_oracle()                       # rebuilds when s2d_match_oracle.c, the common header or the headers changed
+    L = C.CDLL(os.path.join(O.ORACLE_DIR, '_build', f'libs2d_match_oracle_{precision}.so'))
+    cfgp = C.POINTER(M.S2DMatchConfig)
+    L.s2dmo_create.argtypes = [cfgp, C.c_int64]; L.s2dmo_create.restype = C.c_void_p
+    L.s2dmo_destroy.argtypes = [C.c_void_p]; L.s2dmo_destroy.restype = None
+    L.s2dmo_reset.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_reset.restype = None
+    L.s2dmo_step.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_step.restype = None
+    L.s2dmo_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]; L.s2dmo_get.restype = C.c_int
+    L.s2dmo_set_obj.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)]; L.s2dmo_set_obj.restype = C.c_int
+    L.s2dmo_set_game.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]; L.s2dmo_set_game.restype = C.c_int
+    L.s2dmo_set_touch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int]; L.s2dmo_set_touch.restype = C.c_int
+    L.s2dmo_set_card.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int]; L.s2dmo_set_card.restype = C.c_int
+    L.s2dmo_stats.argtypes = [C.c_void_p]; L.s2dmo_stats.restype = C.POINTER(C.c_ulonglong)
+    L.s2dmo_random_actions.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_random_actions.restype = None
+    L.s2dmo_relative.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; L.s2dmo_relative.restype = None
+    L.s2dmo_load.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]; L.s2dmo_load.restype = C.c_int
+    L.s2dmo_set_env_ids.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_set_env_ids.restype = None
+    L.s2dmo_events.argtypes = [C.c_void_p]; L.s2dmo_events.restype = C.POINTER(C.c_uint32)
+    _libs[precision] = L
+    return L
 
 
 class MatchOracle:
-    def __init__(self, cfg, n):
-        self.L, self.cfg, self.n = lib(), cfg, int(n)
+    def __init__(self, cfg, n, prec='f32'):
+        self.L, self.cfg, self.n, self.prec = lib(prec), cfg, int(n), prec
         self.h = self.L.s2dmo_create(C.byref(cfg), self.n)
         assert self.h
 
@@ -145,6 +152,51 @@ class MatchOracle:
         if name == 'done':
             return out.astype(np.uint8)
         return out.astype(np.int32)
+
+    def snapshot(self):
+        """every Match word as {MATCH_BUFFER_FIELDS name: array [n, 24] or [n]} in the device dtypes (the fp64 build's floats as
+        float64: its state is not rounded to fp32)"""
+        fdt = np.float32 if self.prec == 'f32' else np.float64
+        out = {}
+        for name, _t, dt, trail in M.MATCH_BUFFER_FIELDS:
+            if trail is None:
+                continue
+            if trail:
+                idx = OBJ_FIELDS.index(name) if name in OBJ_FIELDS else EXTRA_OBJ_FIELDS[name]
+                v = np.zeros((self.n, 24))
+            else:
+                idx = EXTRA_ENV_FIELDS[name] if name in EXTRA_ENV_FIELDS else 10 + ENV_FIELDS.index(name)
+                v = np.zeros(self.n)
+            assert self.L.s2dmo_get(self.h, idx, v.ctypes.data_as(C.POINTER(C.c_double))) == 0
+            out[name] = v.astype(fdt if dt == 'float32' else np.dtype(dt))
+        return out
+
+    def load(self, state, e0=0):
+        """write every Match word of envs e0 .. e0 + k - 1 from `state` ({name: array [k, 24] or [k]} as snapshot() or the device
+        buffers give it; floats are taken as fp32)"""
+        keep = []
+        for name, _t, dt, trail in M.MATCH_BUFFER_FIELDS:
+            if trail is None:
+                continue
+            a = np.ascontiguousarray(state[name], dtype=np.dtype(dt))
+            keep.append(a)
+        k = keep[0].shape[0]
+        assert all(a.shape == ((k,) + ((24,) if a.ndim == 2 else ())) for a in keep), [a.shape for a in keep]
+        ptrs = (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+        assert self.L.s2dmo_load(self.h, int(e0), k, ptrs) == 0
+
+    def set_env_ids(self, ids=None):
+        """the Philox id of each env (None: env_id_offset + e): a batch of states from different matches keeps its draws"""
+        if ids is None:
+            self.L.s2dmo_set_env_ids(self.h, None)
+        else:
+            self._ids = np.ascontiguousarray(ids, dtype=np.int64)
+            assert self._ids.shape == (self.n,)
+            self.L.s2dmo_set_env_ids(self.h, self._ids.ctypes.data)
+
+    def events(self):
+        """uint32 [n]: EV_* bits of what happened in each env in the last step"""
+        return np.ctypeslib.as_array(self.L.s2dmo_events(self.h), shape=(self.n,)).copy()
 
     def stats(self):
         return np.ctypeslib.as_array(self.L.s2dmo_stats(self.h), shape=(8,)).astype(np.int64)

@@ -64,11 +64,18 @@ def make_config(seed=0x5EED, env_id_offset=0, auto_reset=1, noise=1, server=None
     return cfg
 
 
+# every library of `make -C oracle` (target all) and every file one of them is compiled from
+ORACLE_LIBS = tuple(f'libs2d_{k}_{p}.so' for k in ('oracle', 'match_oracle', 'gtc_oracle') for p in ('f32', 'f64'))
+ORACLE_SOURCES = ('s2d_oracle.c', 's2d_match_oracle.c', 's2d_gtc_oracle.c', 's2d_oracle_common.h', 'Makefile',
+                  '../include/s2d.h', '../include/s2d_match.h', '../include/s2d_gtc.h')
+
+
 def build_oracle(force=False):
+    """make -C oracle when a library is missing or older than any source (make itself rebuilds only what is stale)"""
     out = os.path.join(ORACLE_DIR, '_build')
-    libs = [os.path.join(out, f'libs2d_oracle_{p}.so') for p in ('f32', 'f64')]
-    src = os.path.join(ORACLE_DIR, 's2d_oracle.c')
-    stale = force or any((not os.path.exists(l)) or os.path.getmtime(l) < os.path.getmtime(src) for l in libs)
+    libs = [os.path.join(out, l) for l in ORACLE_LIBS]
+    newest = max(os.path.getmtime(os.path.join(ORACLE_DIR, s)) for s in ORACLE_SOURCES)
+    stale = force or any((not os.path.exists(l)) or os.path.getmtime(l) < newest for l in libs)
     if stale:
         subprocess.run(['make', '-C', ORACLE_DIR] + (['-B'] if force else []), check=True,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)

@@ -805,10 +805,22 @@ def test_illegal_defense_on_device():
                 put(e, i, x=-20.0, y=10.0 + i)
         put(e, 22, x=0.0, y=30.0, vx=0.0, vy=0.0)
     seen = []
+    from soccer2d_amd import wire
     for t in range(10):
         eng.step(torch.as_tensor(a, device='cuda:0')); orc.step(a)
         assert_match_same(eng, orc, f'illegal defense t={t}')
         seen.append([int(v) for v in orc.get('mode')])
+        if t == 4:
+            # during the announcement the world model and the State bytes report no shoot-out (27 is not one of its modes)
+            wm = eng.world_model()
+            assert not bool(wm['world_model.is_penalty_kick_mode'][:4].any())
+            for k in ('on_field_side', 'current_taker_side', 'our_taker_counter', 'their_taker_counter', 'our_score', 'their_score'):
+                assert int(wm['world_model.penalty_kick_state.' + k][:4].abs().max()) == 0, k
+            for e in range(4):
+                for player in (0, 10, 11):
+                    msg = dict((f[0], f[2]) for f in wire.decode(wire.match_state_bytes(eng, e, player)))[2]
+                    fields = [f[0] for f in wire.decode(msg)]
+                    assert 30 not in fields and 38 not in fields, (e, player)
     assert seen[3] == [GM_PLAY_ON] * n and seen[4][:4] == [GM_ILLEGAL_DEFENSE] * 4 and seen[4][4:] == [GM_PLAY_ON] * 2
     assert [int(v) for v in orc.get('mode_side')[:4]] == [2, 2, 2, 1] and seen[7][:4] == [GM_FREE_KICK] * 4      # the others restart
     assert seen[9][4:] == [GM_PLAY_ON] * 2 and int(orc.get('setplay_timer')[4]) == 0 and int(orc.get('setplay_timer')[5]) == 0

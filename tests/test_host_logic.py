@@ -147,7 +147,9 @@ def _league_worker(rank, world, port, q):
         gl, gr = torch.randint(0, 4, (n_local,), generator=g), torch.randint(0, 4, (n_local,), generator=g)
         L, R, GL, GR = exchange_results(left, right, gl, gr)
         lg.update(L, R, GL, GR)
-    q.put((rank, lg.elo.clone(), lg.games.clone()))
+    # by value (numpy), not as shared-memory tensors: the parent must not have to reach this process's descriptor sharer, which is
+    # gone once this process exits
+    q.put((rank, lg.elo.numpy().copy(), lg.games.numpy().copy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -164,6 +166,7 @@ def test_league_table_stays_replicated_over_two_ranks():
     for p in procs:
         p.start()
     got = sorted([q.get(timeout=120) for _ in range(world)], key=lambda t: t[0])
+    got = [(r, torch.from_numpy(e), torch.from_numpy(g)) for r, e, g in got]
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

@@ -66,6 +66,22 @@ def test_penalty_kick_state_on_the_wire():
     assert 30 not in [x[0] for x in wire.decode(wire.encode_world_model(dict(cycle=5, game_mode_type=2)))]
 
 
+def test_illegal_defense_is_not_a_shoot_out_mode_on_the_wire():
+    """IllegalDefense_ (27) lies between the shoot-out's modes (22..26, 28, 29) but is not one: the State bytes of a match in it carry
+    no is_penalty_kick_mode and no PenaltyKickState, those of a match in PenaltyTaken_ do"""
+    from types import SimpleNamespace
+    z = lambda v=0.0: np.full((1, 24), v, dtype=np.float32)          # noqa: E731
+    for mode, want in ((27, False), (24, True), (28, True), (29, True), (21, False)):
+        eng = SimpleNamespace(x=z(), y=z(), vx=z(), vy=z(), body=z(), stamina=z(8000.0), effort=z(1.0), recovery=z(1.0),
+                              stamina_capacity=z(130600.0), tackle_cycles=np.zeros((1, 24), np.int32), cfg=SimpleNamespace(player_type_id=[0] * 24),
+                              score_left=np.zeros(1, np.int32), score_right=np.zeros(1, np.int32), mode=np.array([mode], np.int32),
+                              mode_side=np.array([1], np.int32), set_play_taker=np.array([(1 << 12) | 11], np.int32),
+                              stopped_cycle=np.zeros(1, np.int32), cycle=np.array([500], np.int32))
+        for player in (0, 10, 11):
+            wm = dict((f[0], f[2]) for f in wire.decode(dict((f[0], f[2]) for f in wire.decode(wire.match_state_bytes(eng, 0, player)))[2]))
+            assert (30 in wm) == want and (38 in wm) == want, (mode, player, sorted(wm))
+
+
 def test_rcg_round_trip(tmp_path):
     path = tmp_path / 'm.rcg'
     rs = np.random.RandomState(0)
