@@ -26,6 +26,7 @@
 #include <string>
 
 #include "s2d_kernels.h"
+#include "s2d_net.h"
 
 // experiment build (-DS2D_QNET_STAMPS, profiles/experiments/qnet_actor_clocks.py): per wave, the shader clocks (s_memtime) of the
 // network (observation tile + three layers + argmax), of the rest of the cycle (action draw, simulation, record stores) and of the
@@ -41,8 +42,6 @@
 #define QS_STORE() do {} while (0)
 #endif
 
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-
 struct QNetDims {
   int h1, h2, na;        // hidden widths (multiples of 16, 16 .. 128), actions (1 .. 64)
   int na16;              // actions rounded up to 16 (rows of layer 3's tiles; the padding rows have zero weights and bias)
@@ -54,53 +53,6 @@ struct QNetDims {
 S2D_DEV int w1_frags(const QNetDims& d) { return (d.h1 / 16) * 3; }
 S2D_DEV int w2_frags(const QNetDims& d) { return (d.h2 / 16) * (d.h1 / 4); }
 S2D_DEV int w3_frags(const QNetDims& d) { return (d.na16 / 16) * (d.h2 / 4); }
-
-// J output tiles (jt0 .. jt0 + J - 1) of one layer for one 16-env tile: out[c][j] (LDS, pitch `op`) = (relu)(b[j] + sum_k W[j][k]
-// in[k]) for the tile's 16 envs c.  in_frag(s) = this lane's B word of k-step s.  J independent accumulators keep the matrix pipe
-// issuing (dependent latency 40 cycles against a 32-cycle issue); the k-steps go in groups of KU whose LDS reads are issued together.
-// All 64 lanes take part (MFMA).
-template <bool RELU, int J, int KU, typename InFrag>
-S2D_DEV void layer_group(const float* __restrict__ wf, const float* __restrict__ bias, int jt0, int ksteps, InFrag in_frag,
-                         float* __restrict__ out, int op, int lane) {
-  const int g = lane >> 4, c = lane & 15;
-  v4f_t acc[J];
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const float4 b4 = *reinterpret_cast<const float4*>(bias + 16 * (jt0 + j) + 4 * g);
-    acc[j] = v4f_t{b4.x, b4.y, b4.z, b4.w};
-  }
-  for (int s0 = 0; s0 < ksteps; s0 += KU) {
-    float b[KU], w[J][KU];
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-      b[u] = in_frag(s0 + u);
-#pragma unroll
-      for (int j = 0; j < J; ++j) w[j][u] = wf[((jt0 + j) * ksteps + s0 + u) * kWave + lane];
-    }
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-#pragma unroll
-      for (int j = 0; j < J; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u], b[u], acc[j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    if (RELU) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[j][r] = acc[j][r] > 0.0f ? acc[j][r] : 0.0f;   // relu: NaN and -0 -> +0
-    }
-    *reinterpret_cast<float4*>(out + c * op + 16 * (jt0 + j) + 4 * g) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
-  }
-}
-// all m16 output tiles of one layer, four (then two, then one) at a time
-template <bool RELU, int KU, typename InFrag>
-S2D_DEV void layer_tile(const float* __restrict__ wf, const float* __restrict__ bias, int m16, int ksteps, InFrag in_frag,
-                        float* __restrict__ out, int op, int lane) {
-  int jt = 0;
-  for (; jt + 4 <= m16; jt += 4) layer_group<RELU, 4, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
-  if (jt + 2 <= m16) { layer_group<RELU, 2, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane); jt += 2; }
-  if (jt < m16) layer_group<RELU, 1, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
-}
 
 // the network on the observation tile of the wave (lane = env): qv[env][j] (pitch d.qpitch) = the output layer's
 // pre-activations y_j; ARGMAX: then the spec's argmax scan, whose result is returned (the Q-actor's greedy action)
@@ -136,11 +88,6 @@ S2D_DEV int net_forward(const QNetDims& d, const float* __restrict__ wl, float* 
   }
   wave_lds_fence();
   return best;
-}
-
-// exploration threshold of a device epsilon: eps >= 1 -> 2^32, eps > 0 -> (uint64)(eps 2^32), else (0, -x, NaN) 0
-S2D_DEV uint64_t explore_threshold(float eps) {
-  return eps >= 1.0f ? (1ull << 32) : eps > 0.0f ? (uint64_t)(eps * 4294967296.0f) : 0ull;
 }
 
 // the deterministic policy's action of one env (lane = env), not exploring: a_j = tanh_spec(y_j), with GAUSS + clip(mu_j +

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "s2d_device.h"
+#include "s2d_net.h"
 
 #define S2D_API extern "C" __attribute__((visibility("default")))
 
@@ -14,7 +15,6 @@
 #define S2D_BLOCK 256
 #endif
 static constexpr int kBlock = S2D_BLOCK;
-static constexpr int kWave = 64;
 static constexpr int kWavesPerBlock = kBlock / kWave;
 static constexpr int kObsTile = kWave * S2D_OBS_DIM;  // 640 floats per wave
 static constexpr int64_t kWsMaxEnvs = 524288;         // the wave-specialised rollout wins or ties up to here at steady clocks (profiles/r01/ws_vs_unified_sweep.txt)

@@ -23,11 +23,14 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <tuple>
 #include <string>
 #include <type_traits>
 
 #include "s2d_device.h"
+#include "s2d_net.h"
 #include "../../include/s2d_match.h"
 
 #define S2D_API extern "C" __attribute__((visibility("default")))
@@ -39,7 +42,7 @@ static constexpr int NP = S2D_MATCH_PLAYERS;
 static constexpr int BALL = S2D_MATCH_BALL;
 static constexpr int SLOTS = S2D_MATCH_SLOTS;
 
-enum { S2D_ST_TACKLE = 4, S2D_ST_CATCH = 5, S2D_ST_TYPES = 6 };
+enum { S2D_ST_TACKLE = 4, S2D_ST_CATCH = 5, S2D_ST_TYPES = 6, S2D_ST_NET = S2D_MATCH_ST_NET };
 enum { SIDE_NONE = 0, SIDE_LEFT = 1, SIDE_RIGHT = 2 };
 enum { MF_X, MF_Y, MF_VX, MF_VY, MF_BODY, MF_STAMINA, MF_EFFORT, MF_RECOVERY, MF_CAPACITY, MF_TACKLE, MF_CATCH_BAN, MF_CARD, MF_OBJ_PLANES };
 // Per-slot parameters (heterogeneous PlayerTypes, idl/service.proto:1697-1732): a [PT_WORDS][32] table,
@@ -134,6 +137,8 @@ struct MParamsNoIll : MParams { static constexpr int illegal_defense_number = 0;
 static_assert(sizeof(MParamsNoIll) == sizeof(MParams), "MParamsNoIll adds no data");
 template <class B> struct MParamsCtl : B {};   // the general parameter block as the controller kernels read it (see the kernel)
 static_assert(sizeof(MParamsCtl<MParamsNoIll>) == sizeof(MParams), "MParamsCtl adds no data");
+template <class B> struct MParamsNet : B {};   // ... and as the network kernels read it
+static_assert(sizeof(MParamsNet<MParamsNoIll>) == sizeof(MParams), "MParamsNet adds no data");
 // The same physics and rules with the SCHEDULE of the match -- how long things last, how many there are of them -- as per-engine
 // words: a learner's engine with short halves, no extra time or other waits differs from the stock configuration in these words
 // only and would otherwise run the general instantiation (1.79 G against 2.00 G, profiles/r04/match_schedule_words.txt).  They sit in
@@ -1276,6 +1281,306 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_reset_kernel(MParams p, MPt
   m_store(q, e, l, o, g, r);
 }
 
+// Per-agent observations (include/s2d_match.h, s2d_match_agent_obs).  Per-slot words the cycle kernels do not keep (the PT table
+// stays as it is): built on the host at create time, passed by value.
+struct MAgentTab {
+  float ka[kHalf], ka2[kHalf], speed_max[kHalf], kick_rate[kHalf], inv_margin[kHalf], size[kHalf], type_id[kHalf];
+  float ball_size, ball_decay;
+};
+constexpr int kAObsVec = S2D_AGENT_OBS_DIM / 4;                       // 56 float4 per row
+static_assert(S2D_AGENT_OBS_DIM % 4 == 0 && kAObsVec <= 2 * kHalf, "a half-wave stores a row as two float4 per lane");
+static_assert(S2D_AGENT_OBS_TEAMMATES == 48 && S2D_AGENT_OBS_OPPONENTS == 136 && S2D_AGENT_OBS_ROW_WORDS == 8, "row layout");
+constexpr uint32_t kOurSetPlayModes = (1u << S2D_GM_KICK_OFF) | (1u << S2D_GM_KICK_IN) | (1u << S2D_GM_FREE_KICK) |
+                                      (1u << S2D_GM_CORNER_KICK) | (1u << S2D_GM_GOAL_KICK) | (1u << S2D_GM_IND_FREE_KICK) |
+                                      (1u << S2D_GM_GOALIE_CATCH) | (1u << S2D_GM_PENALTY_KICK);
+struct MAObsFacts {                                    // one match (half-wave): the lanes' facts
+  float x[kHalf], y[kHalf], vx[kHalf], vy[kHalf], reach[kHalf], catch_ban[kHalf];
+  int rank_slot[2][3];                                 // per team: slots of the three smallest (reach, slot) keys, -1 = none
+};
+struct MAObsShared : MAObsFacts {                      // ... then the row being assembled
+  float4 row[kAObsVec];
+};
+S2D_DEV float m_own_body(float b, bool right) { return right ? (b > 0.0f ? b - 180.0f : b + 180.0f) : b; }
+S2D_DEV float m_side_word(int side, int ours) { return side == ours ? 1.0f : (side == SIDE_NONE ? 0.0f : -1.0f); }
+
+// What the rows read of one lane's object and of its match: the state words, zero where the lane has no such word (x .. vy up to
+// the ball, the rest for players only).  s2d_match_agent_obs_kernel loads them from memory, the network rollout takes them from
+// its registers at the start of a cycle.
+struct MAgentIn {
+  float x, y, vx, vy, body, stamina, effort, recovery, capacity;
+  int tackle, card, catch_ban;
+  int cycle, mode, mode_side, last_touch, score_l, score_r, holder, stopped;
+};
+// ... and what m_agent_facts derives from them once per match: the lane's kickable / active / reach facts, the match's masks and
+// the per-side lines (index 0 = left, 1 = right; every lane the same value)
+struct MAgentDerived {
+  bool is_player, active;
+  int reach;
+  uint32_t kick_mask;
+  float offside_line[2], def_ours[2], def_theirs[2];
+};
+
+// Mapping as the relative kernel: a half-wave per match, lane l = slot (22 = the ball).  Each lane derives its object's facts once
+// (kickable, reach steps, rank among its team); per-side lines once per match.  Called by all 64 lanes; ends with a wave fence.
+S2D_DEV MAgentDerived m_agent_facts(const MAgentTab& tab, MAObsFacts& sh, const MAgentIn& in, int l, int half) {
+  MAgentDerived f;
+  f.is_player = l < NP;
+  f.active = f.is_player && in.card < S2D_CARD_RED;
+  const float x = in.x, y = in.y;
+  const bool active = f.active;
+  sh.x[l] = x; sh.y[l] = y; sh.vx[l] = in.vx; sh.vy[l] = in.vy; sh.catch_ban[l] = (float)in.catch_ban;
+  wave_fence();
+  const float bx = sh.x[BALL], by = sh.y[BALL], bvx = sh.vx[BALL], bvy = sh.vy[BALL];
+  // object facts (frame-free: negating every input negates every difference exactly)
+  const int lc = f.is_player ? l : 0;
+  const float ka2 = tab.ka2[lc];
+  const bool kickable = active && sq2(bx - x, by - y) <= ka2;
+  int reach = S2D_AGENT_REACH_NONE;
+  if (active) {
+    if (sq2(bx - x, by - y) <= ka2) {
+      reach = 0;
+    } else {
+      const float ka = tab.ka[lc], smax = tab.speed_max[lc], decay = tab.ball_decay;
+      float cx = bx, cy = by, cvx = bvx, cvy = bvy;
+      for (int t = 1; t <= S2D_AGENT_REACH_MAX; ++t) {
+        cx = cx + cvx; cy = cy + cvy; cvx = cvx * decay; cvy = cvy * decay;
+        const float r = ka + (float)t * smax;
+        if (sq2(cx - x, cy - y) <= r * r) { reach = t; break; }
+      }
+    }
+  }
+  f.reach = reach;
+  sh.reach[l] = (float)reach;
+  f.kick_mask = hballot(kickable, half) & 0x3FFFFFu;
+  const uint32_t act_mask = hballot(active, half) & 0x3FFFFFu;
+  if (l < 6) sh.rank_slot[l / 3][l % 3] = -1;
+  wave_fence();
+  if (active) {                                        // rank of (reach, slot) among the active players of the team
+    const int t0 = l < 11 ? 0 : 11;
+    int rank = 0;
+    for (int j = t0; j < t0 + 11; ++j) {
+      const int rj = (int)sh.reach[j];
+      rank += (((act_mask >> j) & 1u) != 0u && (rj < reach || (rj == reach && j < l))) ? 1 : 0;
+    }
+    if (rank < 3) sh.rank_slot[l < 11 ? 0 : 1][rank] = l;
+  }
+  // per-side lines, in the frame of side S
+  for (int S = 0; S < 2; ++S) {
+    const float sg = S == 0 ? 1.0f : -1.0f;
+    const int us = S == 0 ? 0 : 11, them = S == 0 ? 11 : 0;
+    const float obx = sg * bx;
+    float first = -1.0e9f, second = -1.0e9f;
+    for (int j = 0; j < 11; ++j) {
+      const float v = sg * sh.x[them + j];
+      if (v > first) { second = first; first = v; } else if (v > second) second = v;
+    }
+    float line = 0.0f;
+    if (second > line) line = second;
+    if (obx > line) line = obx;
+    float mn = obx, mx = obx;
+    for (int j = 1; j < 11; ++j) {                     // (slot 0 of each team is the goalie)
+      const bool act_us = ((act_mask >> (us + j)) & 1u) != 0u, act_them = ((act_mask >> (them + j)) & 1u) != 0u;
+      const float vu = sg * sh.x[us + j], vt = sg * sh.x[them + j];
+      if (act_us && vu < mn) mn = vu;
+      if (act_them && vt > mx) mx = vt;
+    }
+    f.offside_line[S] = line; f.def_ours[S] = mn; f.def_theirs[S] = mx;
+  }
+  wave_fence();
+  return f;
+}
+
+// The row of agent pa (uniform within the half-wave) into `row` (LDS, 56 float4): every lane writes its part (objects: their 8
+// words; the agent's lane: the self block; the ball's lane: ball words and the kick rate; lanes 23..28: the game block), so that
+// after a wave fence all 56 float4 hold the row.  This is THE definition of a row: s2d_match_agent_obs_kernel and the network
+// rollout both call it.
+template <class P>
+S2D_DEV void m_agent_row(const P& p, const MAgentTab& tab, const MAObsFacts& sh, const MAgentIn& in, const MAgentDerived& f, int l,
+                         int pa, float4* row) {
+  const float x = in.x, y = in.y, vx = in.vx, vy = in.vy, body = in.body;
+  const bool is_player = f.is_player, active = f.active;
+  const bool right = pa >= 11;
+  const int ours = right ? SIDE_RIGHT : SIDE_LEFT, S = right ? 1 : 0;
+  const float sg = right ? -1.0f : 1.0f;
+  const float ax = sg * sh.x[pa], ay = sg * sh.y[pa];
+  const float abody = m_own_body(__shfl(body, pa, kHalf), right);
+  // this lane's object in the agent's frame
+  const float ox = sg * x, oy = sg * y, ovx = sg * vx, ovy = sg * vy, obody = m_own_body(body, right);
+  const float dx = ox - ax, dy = oy - ay;
+  float dist = hypot2(dx, dy);
+  float bearing = norm_deg_any(atan2_deg(dy, dx) - abody);
+  if (l == pa) { dist = 0.0f; bearing = 0.0f; }
+  if (is_player) {
+    const int idx = ((l < 11) == !right ? S2D_AGENT_OBS_TEAMMATES : S2D_AGENT_OBS_OPPONENTS) / 4 + 2 * (l % 11);
+    row[idx] = active ? make_float4(ox, oy, ovx, ovy) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    row[idx + 1] = active ? make_float4(obody, dist, bearing, (float)f.reach) : make_float4(0.0f, 0.0f, 0.0f, (float)f.reach);
+    if (l == pa) {                                   // self block, words 0..11
+      row[0] = make_float4(ox, oy, ovx, ovy);
+      row[1] = make_float4(obody, in.stamina, in.effort, in.recovery);
+      row[2] = make_float4(in.capacity, (l == S2D_MATCH_GOALIE_LEFT || l == S2D_MATCH_GOALIE_RIGHT) ? 1.0f : 0.0f, (float)in.tackle,
+                           (float)in.card);
+    }
+  } else if (l == BALL) {                            // ball words; self words 12..15 (they need the ball's distance and bearing)
+    const bool akick = ((f.kick_mask >> pa) & 1u) != 0u;
+    float rate = 0.0f;
+    if (akick) {
+      const float dir_diff = fabsf(bearing);
+      const float dist_ball = dist - tab.size[pa] - tab.ball_size;    // (hypot2 == sqrtf of the same square)
+      rate = tab.kick_rate[pa] * (1.0f - 0.25f * (dir_diff * 0.005555555555555556f) - 0.25f * (dist_ball * tab.inv_margin[pa]));
+    }
+    row[3] = make_float4(akick ? 1.0f : 0.0f, rate, sh.catch_ban[pa], tab.type_id[pa]);
+    row[4] = make_float4(ox, oy, ovx, ovy);
+    const int hside = in.holder > 0 ? side_of(in.holder - 1) : SIDE_NONE;
+    row[5] = make_float4(dist, bearing, m_side_word(in.last_touch, ours), m_side_word(hside, ours));
+  } else if (l <= BALL + 6) {                        // game block: lane 23 + g writes words 4g..4g+3
+    const int g = l - (BALL + 1);
+    const uint32_t team = right ? 0x3FF800u : 0x7FFu;
+    const uint32_t km_tm = f.kick_mask & team & ~(1u << pa), km_op = f.kick_mask & (0x3FFFFFu ^ team);
+    const float k_tm = km_tm ? (float)(__builtin_ctz(km_tm) % 11 + 1) : 0.0f;
+    const float k_op = km_op ? (float)(__builtin_ctz(km_op) % 11 + 1) : 0.0f;
+    const int* rs = sh.rank_slot[S];
+    const int t1 = rs[0] == pa ? rs[1] : rs[0];
+    const int t2 = (rs[0] == pa || rs[1] == pa) ? rs[2] : rs[1];
+    const int* ro = sh.rank_slot[1 - S];
+    const float t1r = t1 >= 0 ? sh.reach[t1] : (float)S2D_AGENT_REACH_NONE, t1u = t1 >= 0 ? (float)(t1 % 11 + 1) : 0.0f;
+    const float t2r = t2 >= 0 ? sh.reach[t2] : (float)S2D_AGENT_REACH_NONE, t2u = t2 >= 0 ? (float)(t2 % 11 + 1) : 0.0f;
+    const float o1r = ro[0] >= 0 ? sh.reach[ro[0]] : (float)S2D_AGENT_REACH_NONE, o1u = ro[0] >= 0 ? (float)(ro[0] % 11 + 1) : 0.0f;
+    const float o2r = ro[1] >= 0 ? sh.reach[ro[1]] : (float)S2D_AGENT_REACH_NONE, o2u = ro[1] >= 0 ? (float)(ro[1] % 11 + 1) : 0.0f;
+    const int mode = in.mode, cycle = in.cycle;
+    const float sp = in_modes(mode, kOurSetPlayModes) ? 1.0f : 0.0f;
+    const float side_w = m_side_word(in.mode_side, ours);
+    float4 w;
+    switch (g) {
+      case 0: w = make_float4((float)mode, side_w, (float)(right ? in.score_r : in.score_l), (float)(right ? in.score_l : in.score_r)); break;
+      case 1: w = make_float4((float)cycle, (float)in.stopped, (float)cycles_to_period_end(p, cycle),
+                              in_modes(mode, kPenaltyModes) ? 1.0f : 0.0f); break;
+      case 2: w = make_float4(f.offside_line[S], f.def_ours[S], f.def_theirs[S], k_tm); break;
+      case 3: w = make_float4(k_op, sh.reach[pa], t1r, t1u); break;
+      case 4: w = make_float4(t2r, t2u, o1r, o1u); break;
+      default: w = make_float4(o2r, o2u, side_w > 0.0f ? sp : 0.0f, side_w < 0.0f ? sp : 0.0f); break;
+    }
+    row[S2D_AGENT_OBS_GAME / 4 + g] = w;
+  }
+}
+
+// The half-wave stores a row assembled in LDS as two contiguous float4 stores (512 + 384 B), every line written whole by one instruction.
+S2D_DEV void m_agent_row_store(float* __restrict__ dst, const float4* row, int l) {
+  float4* d = reinterpret_cast<float4*>(dst);
+  d[l] = row[l];
+  if (l + kHalf < kAObsVec) d[l + kHalf] = row[l + kHalf];
+}
+
+
+// ------------------------------------------------------------------------------------------
+// network slots (s2d_match_set_network, include/s2d_match.h): the caller's Q-network on each network slot's agent row
+// ------------------------------------------------------------------------------------------
+// A wave holds two matches; the rows built in a cycle are those of the row mask (network slots, plus the recorded ones) in slot
+// order, interleaved by match: tile row 2 j + half = the j-th agent of the tile's eight.  Each 16-row tile is built in LDS, then
+// pushed through the three layers (s2d_net.h: layer 1's 56 k-steps read W1's fragments from memory, layers 2 and 3 theirs from
+// LDS), and the argmax of each row is kept; pad rows of the last tile are zero and their results are never read.
+constexpr int kNetK1 = S2D_AGENT_OBS_DIM / 4;          // 56 k-steps of layer 1
+constexpr int kNetRowPitch = S2D_AGENT_OBS_DIM + 4;    // LDS pitch of a row (228: the 16 rows of a B fragment hit 64 banks)
+constexpr int kNetHidPitch = 64 + 4;                   // ... of the hidden and Q images
+constexpr int kNetMaxRows = 48;                        // 2 matches x 22 agents, in tiles of 16
+struct MNet {
+  uint32_t net_mask, row_mask, obs_mask;   // network slots; slots whose rows are built (net | obs); slots recorded in agent_obs
+  int h1, h2, na, na16;
+  const float* frags;                      // the engine's fragment-order copy: W1 (read from memory), then W2 | W3 | b1 | b2 | b3
+  int shared_words;                        // words of W2 .. b3 (staged into LDS)
+  const float* epsilon;                    // device float, read once per launch
+  const float* table;                      // device float[na][3]
+  int32_t* net_index;                      // [T][N][22] or NULL
+  float* agent_obs;                        // [T][N][popcount(obs_mask)][224] or NULL
+};
+struct MNetArg { MNet net; MAgentTab tab; };   // kernel argument of the NET instantiations (with their MCtl)
+constexpr int kNetWaveWords = 16 * kNetRowPitch + 16 * kNetHidPitch + 2 * (int)(sizeof(MAObsFacts) / 4) + kNetMaxRows;
+static_assert((2 * sizeof(MAObsFacts)) % 16 == 0 && (16 * kNetRowPitch + 16 * kNetHidPitch) % 4 == 0, "16-byte aligned LDS parts");
+
+S2D_DEV float* m_net_lds() {                           // dynamic LDS: [W2 | W3 | b1 | b2 | b3] then kNetWaveWords per wave
+  extern __shared__ __attribute__((aligned(16))) float net_smem[];
+  return net_smem;
+}
+// the block-shared part of the network into LDS (every thread of the block; the kernel's barrier follows)
+S2D_DEV void m_net_stage(const MNet& net) {
+  const float4* src = reinterpret_cast<const float4*>(net.frags + net.h1 / 16 * kNetK1 * 64);
+  float4* dst = reinterpret_cast<float4*>(m_net_lds());
+  for (int i = threadIdx.x; i < net.shared_words / 4; i += kMBlock) dst[i] = src[i];
+}
+
+// One cycle's network step of the wave, from the start-of-cycle state (o, g, r): the rows, their record, the forward pass and
+// the argmax.  Returns the greedy index of this lane's slot (meaningful for network slots).  All 64 lanes, uniform control flow.
+template <class P>
+S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGame& g, const MRare& r, int l, int half, bool valid,
+                         int64_t rec_row) {
+  const MNet& net = na.net;
+  const int lane = threadIdx.x & 63, gq = lane >> 4, c = lane & 15;
+  float* const shared = m_net_lds();
+  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * kNetWaveWords;
+  float* const hid = tile + 16 * kNetRowPitch;
+  MAObsFacts* const facts = reinterpret_cast<MAObsFacts*>(hid + 16 * kNetHidPitch);
+  int* const gidx = reinterpret_cast<int*>(facts + 2);
+  MAgentIn in{};
+  if (l <= BALL) { in.x = o.x; in.y = o.y; in.vx = o.vx; in.vy = o.vy; }
+  if (l < NP) {
+    in.body = o.body; in.stamina = o.stamina; in.effort = o.effort; in.recovery = o.recovery; in.capacity = o.capacity;
+    in.tackle = o.tackle; in.card = o.card; in.catch_ban = o.catch_ban;
+  }
+  in.cycle = g.cycle; in.mode = g.mode; in.mode_side = g.mode_side; in.last_touch = g.last_touch;
+  in.score_l = r.score_l; in.score_r = r.score_r; in.holder = r.holder; in.stopped = r.stopped;
+  MAObsFacts& fs = facts[half];
+  const MAgentDerived f = m_agent_facts(na.tab, fs, in, l, half);
+  const int nrows = __builtin_popcount(net.row_mask), nobs = __builtin_popcount(net.obs_mask);
+  const float* const w2 = shared;
+  const float* const w3 = w2 + (net.h2 / 16) * (net.h1 / 4) * 64;
+  const float* const b1 = w3 + (net.na16 / 16) * (net.h2 / 4) * 64;
+  const float* const b2 = b1 + net.h1;
+  const float* const b3 = b2 + net.h2;
+  uint32_t rest = net.row_mask;
+  for (int nt = 0; 8 * nt < nrows; ++nt) {
+    const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
+    for (int i = lane; i < (16 - 2 * rn) * (kNetRowPitch / 4); i += 64)   // pad rows of the last tile
+      reinterpret_cast<float4*>(tile + 2 * rn * kNetRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int j = 0; j < rn; ++j) {
+      const int pa = __builtin_ctz(rest);              // the agent (uniform: the mask is a kernel argument)
+      rest &= rest - 1u;
+      float4* const row = reinterpret_cast<float4*>(tile + (2 * j + half) * kNetRowPitch);
+      m_agent_row(p, na.tab, fs, in, f, l, pa, row);
+      if (net.agent_obs && ((net.obs_mask >> pa) & 1u)) {
+        wave_fence();
+        const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
+        if (valid) m_agent_row_store(net.agent_obs + (rec_row * nobs + k) * S2D_AGENT_OBS_DIM, row, l);
+      }
+    }
+    wave_fence();
+    if (net.net_mask != 0u) {
+      const float* const x = tile + c * kNetRowPitch;
+      layer_tile<true, 4>(net.frags, b1, net.h1 / 16, kNetK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
+      wave_fence();
+      layer_tile<true, 4>(w2, b2, net.h2 / 16, net.h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile,
+                          kNetHidPitch, lane);
+      wave_fence();
+      layer_tile<false, 4>(w3, b3, net.na16 / 16, net.h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid,
+                           kNetHidPitch, lane);
+      wave_fence();
+      if (lane < 16) {   // best = 0; for a = 1 .. K-1: if (q[a] > q[best]) best = a  (ties: lowest index; a NaN never replaces the best)
+        const float* q = hid + lane * kNetHidPitch;
+        int best = 0;
+        float bv = q[0];
+        for (int a = 1; a < net.na; ++a) {
+          const float v = q[a];
+          if (v > bv) { bv = v; best = a; }
+        }
+        gidx[16 * nt + lane] = best;
+      }
+      wave_fence();
+    }
+  }
+  int greedy = 0;
+  if (l < NP && ((net.net_mask >> l) & 1u)) greedy = gidx[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+  wave_fence();
+  return greedy;
+}
+
 struct MRoll { float* obs; float* reward; int32_t* mode; uint8_t* done; };
 
 // n_steps cycles; actions = [T][N][22][3] or NULL (random policy).  n_steps = 1 with ro = {} is the per-step API.
@@ -1284,9 +1589,10 @@ struct MShared {                                      // the workgroup's LDS (de
 };
 // CTL: the slots' controllers come from `ctl` (per-slot: caller's row, random, scripted) and the record of what they chose is written
 // when ctl.actions_out is set; otherwise every slot takes the caller's row, or the random policy when actions == NULL.
-template <bool CTL, class P, class TY>
+// NET (with CTL): the network slots of `nin` override the table: the action of the caller's network on the slot's agent row.
+template <bool CTL, bool NET = false, class P, class TY>
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
-                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl) {
+                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const MNetArg* nin = nullptr) {
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
@@ -1326,6 +1632,8 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   // cycles, starting from their slot number on the SIMD (HW_ID.wave_id): at any time the four hold four different levels, and over
   // a launch every wave spends the same time at each.
   const int simd_slot = (int)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4);   // HW_REG_HW_ID bits 3:0
+  uint64_t net_thr = 0;
+  if constexpr (NET) net_thr = nin->net.net_mask ? explore_threshold(*nin->net.epsilon) : 0;   // (records only: no network)
   for (int t = 0; t < n_steps; ++t) {
     if ((t & 3) == 0) {
       switch ((simd_slot + (t >> 2)) & 3) {
@@ -1345,9 +1653,21 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
     if constexpr (CTL) {
       int scmd = S2D_MCMD_NONE; float sa = 0.0f, sb = 0.0f;
       if (ctl.script_mask != 0u) m_scripted_action(p, pt, o, g, r, l, half, scmd, sa, sb);   // (uniform: a kernel argument)
+      int nidx = -1;                                       // NET: the network's index of this slot, -1 = not a network slot
+      if constexpr (NET) {
+        const int greedy = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec);
+        if (l < NP && ((nin->net.net_mask >> l) & 1u)) {   // explore: word x < thr, then the index is word y's draw below K
+          const U4 w = m_draw(p, gl, gh, (uint32_t)g.tick, S2D_ST_NET, (uint32_t)l);
+          nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, (uint32_t)nin->net.na) : greedy;
+        }
+        if (nin->net.net_index && valid && l < NP) nin->net.net_index[((int64_t)t * n + e) * NP + l] = nidx;
+      }
       if (l < NP) {
         const uint32_t bit = 1u << l;
-        if (ctl.script_mask & bit) {
+        if (NET && nidx >= 0) {
+          const float* tr = nin->net.table + 3 * nidx;
+          cmd = (int)tr[0]; a = tr[1]; b = tr[2];
+        } else if (ctl.script_mask & bit) {
           cmd = scmd; a = sa; b = sb;
         } else if (ctl.random_mask & bit) {
           m_random_action(p, gl, gh, (uint32_t)g.tick, l, t == 0, pol, cmd, a, b);
@@ -1403,13 +1723,20 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // SCHED (with STOCK and STOCK_TYPES): the schedule words are the engine's own (MStockSched).  ILL (general only): the engine has
 // IllegalDefense_ switched on.
 // CTL: per-slot controllers (MCtl, the one extra argument: the instantiations without it keep their argument list and code).
+// NET (with CTL): network slots (MNetArg, a second extra argument), the network's LDS in dynamic shared memory; one workgroup per CU
+// holds it, so these instantiations have the register file of one wave per SIMD.
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
-template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, class... CtlArg>
-__global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
+S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
+S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
+template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, bool NET = false, class... CtlArg>
+__global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
                                                                      const float* __restrict__ actions, MRoll ro, CtlArg... ctl_arg) {
-  static_assert(sizeof...(CtlArg) == (CTL ? 1 : 0), "the CTL instantiations take an MCtl, the others nothing more");
+  static_assert(sizeof...(CtlArg) == (NET ? 2 : CTL ? 1 : 0), "the CTL instantiations take an MCtl, NET ones an MNetArg too, the others nothing more");
+  static_assert(!NET || CTL, "network slots come with the controller table");
   const MCtl ctl = m_ctl_arg(ctl_arg...);
+  const MNetArg* nin = nullptr;
+  if constexpr (NET) nin = m_net_arg(ctl_arg...);
   __shared__ float4 pos_tile[kEnvsPerBlock][kTileSlots];
   __shared__ PTab pt[PT_WORDS];                       // per-slot PlayerType parameters, shared by the 8 matches
   __shared__ unsigned int lds_cnt[8];
@@ -1423,6 +1750,7 @@ __global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p
   if constexpr (!STOCK_TYPES)
     for (int k = threadIdx.x; k < PT_WORDS * kHalf; k += kMBlock) (&pt[0][0])[k] = q.ptab[k];
   if (threadIdx.x < 8) lds_cnt[threadIdx.x] = 0u;
+  if constexpr (NET) m_net_stage(nin->net);              // (the barrier of every branch below covers it)
   static_assert(!SCHED || (STOCK && STOCK_TYPES), "the engine's own schedule comes with constant rules and types");
   if constexpr (SCHED) {
     __syncthreads();
@@ -1430,15 +1758,15 @@ __global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p
     const MStockSched p{p_arg.auto_reset, p_arg.noise, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi M_SCHEDULE_INTS(X)};
 #undef X
     const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-    match_rollout_body<CTL>(p, types, sh, q, n, n_steps, actions, ro, ctl);
+    match_rollout_body<CTL, NET>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin);
   } else if constexpr (STOCK) {
     __syncthreads();
     const MStock p{p_arg.auto_reset, p_arg.noise, p_arg.penalty_shoot_outs, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi};
     if constexpr (STOCK_TYPES) {
       const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-      match_rollout_body<CTL>(p, types, sh, q, n, n_steps, actions, ro, ctl);
+      match_rollout_body<CTL, NET>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin);
     } else {
-      match_rollout_body<CTL>(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl);
+      match_rollout_body<CTL, NET>(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin);
     }
   } else {
     // The ~70 uniform parameters are read from LDS (broadcast reads) where they are used instead of
@@ -1447,14 +1775,15 @@ __global__ __launch_bounds__(kMBlock, 4) void s2d_match_rollout_kernel(MParams p
     static_assert(!ILL || !STOCK, "the stock configurations have the rule off");
     // The CTL kernels read the block through a type of their own (no data added): every helper templated on it is then an
     // instantiation of theirs.  Helpers shared with the CTL kernels were optimised differently in the kernels without them.
+    // The NET kernels likewise (sharing the CTL kernels' type changed those kernels' code).
     using PBase = std::conditional_t<ILL, MParams, MParamsNoIll>;
-    using PBlock = std::conditional_t<CTL, MParamsCtl<PBase>, PBase>;
+    using PBlock = std::conditional_t<NET, MParamsNet<PBase>, std::conditional_t<CTL, MParamsCtl<PBase>, PBase>>;
     __shared__ PBlock p_lds;
     static_assert(sizeof(MParams) / 4 <= kMBlock, "one thread per parameter word");
     if (threadIdx.x < sizeof(MParams) / 4)
       reinterpret_cast<uint32_t*>(&p_lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&p_arg)[threadIdx.x];
     __syncthreads();
-    match_rollout_body<CTL>(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl);
+    match_rollout_body<CTL, NET>(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin);
   }
 }
 
@@ -1484,31 +1813,7 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_relative_kernel(MPtrs q, in
   }
 }
 
-// Per-agent observations (include/s2d_match.h, s2d_match_agent_obs).  Per-slot words the cycle kernels do not keep (the PT table
-// stays as it is): built on the host at create time, passed by value.
-struct MAgentTab {
-  float ka[kHalf], ka2[kHalf], speed_max[kHalf], kick_rate[kHalf], inv_margin[kHalf], size[kHalf], type_id[kHalf];
-  float ball_size, ball_decay;
-};
-constexpr int kAObsVec = S2D_AGENT_OBS_DIM / 4;                       // 56 float4 per row
-static_assert(S2D_AGENT_OBS_DIM % 4 == 0 && kAObsVec <= 2 * kHalf, "a half-wave stores a row as two float4 per lane");
-static_assert(S2D_AGENT_OBS_TEAMMATES == 48 && S2D_AGENT_OBS_OPPONENTS == 136 && S2D_AGENT_OBS_ROW_WORDS == 8, "row layout");
-constexpr uint32_t kOurSetPlayModes = (1u << S2D_GM_KICK_OFF) | (1u << S2D_GM_KICK_IN) | (1u << S2D_GM_FREE_KICK) |
-                                      (1u << S2D_GM_CORNER_KICK) | (1u << S2D_GM_GOAL_KICK) | (1u << S2D_GM_IND_FREE_KICK) |
-                                      (1u << S2D_GM_GOALIE_CATCH) | (1u << S2D_GM_PENALTY_KICK);
-struct MAObsShared {                                   // one match (half-wave): the lanes' facts, then the row being assembled
-  float x[kHalf], y[kHalf], vx[kHalf], vy[kHalf], reach[kHalf], catch_ban[kHalf];
-  int rank_slot[2][3];                                 // per team: slots of the three smallest (reach, slot) keys, -1 = none
-  float4 row[kAObsVec];
-};
-S2D_DEV float m_own_body(float b, bool right) { return right ? (b > 0.0f ? b - 180.0f : b + 180.0f) : b; }
-S2D_DEV float m_side_word(int side, int ours) { return side == ours ? 1.0f : (side == SIDE_NONE ? 0.0f : -1.0f); }
-
-// Mapping as the relative kernel: a half-wave per match, lane l = slot (22 = the ball).  Each lane derives its object's facts once
-// (kickable, reach steps, rank among its team); per-side lines once per match.  Then, for each agent of the mask in slot order,
-// every lane writes its part of the agent's row into an LDS row (objects: their 8 words; the agent's lane: the self block; the
-// ball's lane: ball words and the kick rate; lanes 23..28: the game block) and the half-wave stores the 896-byte row as two
-// contiguous float4 stores (512 + 384 B), every line written whole by one instruction.
+// One match per half-wave: the facts, then for each agent of the mask in slot order its row into LDS and out to memory.
 __global__ __launch_bounds__(kMBlock) void s2d_match_agent_obs_kernel(MParams p, MAgentTab tab, MPtrs q, int64_t n, uint32_t mask,
                                                                        float* __restrict__ obs) {
   __shared__ MAObsShared sh_all[kEnvsPerBlock];
@@ -1518,158 +1823,34 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_agent_obs_kernel(MParams p,
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
   const bool valid = e < n;
   const int64_t ec = valid ? e : n - 1;
-  const bool is_player = l < NP;
-  float x = 0.0f, y = 0.0f, vx = 0.0f, vy = 0.0f, body = 0.0f, stamina = 0.0f, effort = 0.0f, recovery = 0.0f, capacity = 0.0f;
-  int tackle = 0, card = 0, catch_ban = 0;
+  MAgentIn in{};
   if (l <= BALL) {
     const int64_t k = ec * SLOTS + l;
-    x = q.obj[MF_X * q.obj_stride + k]; y = q.obj[MF_Y * q.obj_stride + k];
-    vx = q.obj[MF_VX * q.obj_stride + k]; vy = q.obj[MF_VY * q.obj_stride + k];
+    in.x = q.obj[MF_X * q.obj_stride + k]; in.y = q.obj[MF_Y * q.obj_stride + k];
+    in.vx = q.obj[MF_VX * q.obj_stride + k]; in.vy = q.obj[MF_VY * q.obj_stride + k];
   }
-  if (is_player) {
+  if (l < NP) {
     const int64_t k = ec * SLOTS + l;
-    body = q.obj[MF_BODY * q.obj_stride + k];
-    stamina = q.obj[MF_STAMINA * q.obj_stride + k]; effort = q.obj[MF_EFFORT * q.obj_stride + k];
-    recovery = q.obj[MF_RECOVERY * q.obj_stride + k]; capacity = q.obj[MF_CAPACITY * q.obj_stride + k];
-    tackle = __float_as_int(q.obj[MF_TACKLE * q.obj_stride + k]); card = __float_as_int(q.obj[MF_CARD * q.obj_stride + k]);
-    catch_ban = __float_as_int(q.obj[MF_CATCH_BAN * q.obj_stride + k]);
+    in.body = q.obj[MF_BODY * q.obj_stride + k];
+    in.stamina = q.obj[MF_STAMINA * q.obj_stride + k]; in.effort = q.obj[MF_EFFORT * q.obj_stride + k];
+    in.recovery = q.obj[MF_RECOVERY * q.obj_stride + k]; in.capacity = q.obj[MF_CAPACITY * q.obj_stride + k];
+    in.tackle = __float_as_int(q.obj[MF_TACKLE * q.obj_stride + k]); in.card = __float_as_int(q.obj[MF_CARD * q.obj_stride + k]);
+    in.catch_ban = __float_as_int(q.obj[MF_CATCH_BAN * q.obj_stride + k]);
   }
-  const int cycle = q.env[ME_CYCLE * q.env_stride + ec], mode = q.env[ME_MODE * q.env_stride + ec];
-  const int mode_side = q.env[ME_MODE_SIDE * q.env_stride + ec], last_touch = q.env[ME_LAST_TOUCH * q.env_stride + ec];
-  const int score_l = q.env[ME_SCORE_L * q.env_stride + ec], score_r = q.env[ME_SCORE_R * q.env_stride + ec];
-  const int holder = q.env[ME_HOLDER * q.env_stride + ec], stopped = q.env[ME_STOPPED * q.env_stride + ec];
-  const bool active = is_player && card < S2D_CARD_RED;
-  sh.x[l] = x; sh.y[l] = y; sh.vx[l] = vx; sh.vy[l] = vy; sh.catch_ban[l] = (float)catch_ban;
-  wave_fence();
-  const float bx = sh.x[BALL], by = sh.y[BALL], bvx = sh.vx[BALL], bvy = sh.vy[BALL];
-  // object facts (frame-free: negating every input negates every difference exactly)
-  const int lc = is_player ? l : 0;
-  const float ka2 = tab.ka2[lc];
-  const bool kickable = active && sq2(bx - x, by - y) <= ka2;
-  int reach = S2D_AGENT_REACH_NONE;
-  if (active) {
-    if (sq2(bx - x, by - y) <= ka2) {
-      reach = 0;
-    } else {
-      const float ka = tab.ka[lc], smax = tab.speed_max[lc], decay = tab.ball_decay;
-      float cx = bx, cy = by, cvx = bvx, cvy = bvy;
-      for (int t = 1; t <= S2D_AGENT_REACH_MAX; ++t) {
-        cx = cx + cvx; cy = cy + cvy; cvx = cvx * decay; cvy = cvy * decay;
-        const float r = ka + (float)t * smax;
-        if (sq2(cx - x, cy - y) <= r * r) { reach = t; break; }
-      }
-    }
-  }
-  sh.reach[l] = (float)reach;
-  const uint32_t kick_mask = hballot(kickable, half) & 0x3FFFFFu, act_mask = hballot(active, half) & 0x3FFFFFu;
-  if (l < 6) sh.rank_slot[l / 3][l % 3] = -1;
-  wave_fence();
-  if (active) {                                        // rank of (reach, slot) among the active players of the team
-    const int t0 = l < 11 ? 0 : 11;
-    int rank = 0;
-    for (int j = t0; j < t0 + 11; ++j) {
-      const int rj = (int)sh.reach[j];
-      rank += (((act_mask >> j) & 1u) != 0u && (rj < reach || (rj == reach && j < l))) ? 1 : 0;
-    }
-    if (rank < 3) sh.rank_slot[l < 11 ? 0 : 1][rank] = l;
-  }
-  // per-side lines, in the frame of side S (index 0 = left, 1 = right); every lane the same value
-  float offside_line[2], def_ours[2], def_theirs[2];
-  for (int S = 0; S < 2; ++S) {
-    const float sg = S == 0 ? 1.0f : -1.0f;
-    const int us = S == 0 ? 0 : 11, them = S == 0 ? 11 : 0;
-    const float obx = sg * bx;
-    float first = -1.0e9f, second = -1.0e9f;
-    for (int j = 0; j < 11; ++j) {
-      const float v = sg * sh.x[them + j];
-      if (v > first) { second = first; first = v; } else if (v > second) second = v;
-    }
-    float line = 0.0f;
-    if (second > line) line = second;
-    if (obx > line) line = obx;
-    float mn = obx, mx = obx;
-    for (int j = 1; j < 11; ++j) {                     // (slot 0 of each team is the goalie)
-      const bool act_us = ((act_mask >> (us + j)) & 1u) != 0u, act_them = ((act_mask >> (them + j)) & 1u) != 0u;
-      const float vu = sg * sh.x[us + j], vt = sg * sh.x[them + j];
-      if (act_us && vu < mn) mn = vu;
-      if (act_them && vt > mx) mx = vt;
-    }
-    offside_line[S] = line; def_ours[S] = mn; def_theirs[S] = mx;
-  }
-  wave_fence();
+  in.cycle = q.env[ME_CYCLE * q.env_stride + ec]; in.mode = q.env[ME_MODE * q.env_stride + ec];
+  in.mode_side = q.env[ME_MODE_SIDE * q.env_stride + ec]; in.last_touch = q.env[ME_LAST_TOUCH * q.env_stride + ec];
+  in.score_l = q.env[ME_SCORE_L * q.env_stride + ec]; in.score_r = q.env[ME_SCORE_R * q.env_stride + ec];
+  in.holder = q.env[ME_HOLDER * q.env_stride + ec]; in.stopped = q.env[ME_STOPPED * q.env_stride + ec];
+  const MAgentDerived f = m_agent_facts(tab, sh, in, l, half);
   const int nrows = __builtin_popcount(mask);
   float* out = obs + (e * (int64_t)nrows) * S2D_AGENT_OBS_DIM;
   uint32_t rest = mask;
   for (int r = 0; r < nrows; ++r) {
     const int pa = __builtin_ctz(rest);                // the agent (uniform: the mask is a kernel argument)
     rest &= rest - 1u;
-    const bool right = pa >= 11;
-    const int ours = right ? SIDE_RIGHT : SIDE_LEFT, S = right ? 1 : 0;
-    const float sg = right ? -1.0f : 1.0f;
-    const float ax = sg * sh.x[pa], ay = sg * sh.y[pa];
-    const float abody = m_own_body(__shfl(body, pa, kHalf), right);
-    // this lane's object in the agent's frame
-    const float ox = sg * x, oy = sg * y, ovx = sg * vx, ovy = sg * vy, obody = m_own_body(body, right);
-    const float dx = ox - ax, dy = oy - ay;
-    float dist = hypot2(dx, dy);
-    float bearing = norm_deg_any(atan2_deg(dy, dx) - abody);
-    if (l == pa) { dist = 0.0f; bearing = 0.0f; }
-    if (is_player) {
-      const int idx = ((l < 11) == !right ? S2D_AGENT_OBS_TEAMMATES : S2D_AGENT_OBS_OPPONENTS) / 4 + 2 * (l % 11);
-      sh.row[idx] = active ? make_float4(ox, oy, ovx, ovy) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      sh.row[idx + 1] = active ? make_float4(obody, dist, bearing, (float)reach) : make_float4(0.0f, 0.0f, 0.0f, (float)reach);
-      if (l == pa) {                                   // self block, words 0..11
-        sh.row[0] = make_float4(ox, oy, ovx, ovy);
-        sh.row[1] = make_float4(obody, stamina, effort, recovery);
-        sh.row[2] = make_float4(capacity, (l == S2D_MATCH_GOALIE_LEFT || l == S2D_MATCH_GOALIE_RIGHT) ? 1.0f : 0.0f, (float)tackle,
-                                (float)card);
-      }
-    } else if (l == BALL) {                            // ball words; self words 12..15 (they need the ball's distance and bearing)
-      const bool akick = ((kick_mask >> pa) & 1u) != 0u;
-      float rate = 0.0f;
-      if (akick) {
-        const float dir_diff = fabsf(bearing);
-        const float dist_ball = dist - tab.size[pa] - tab.ball_size;    // (hypot2 == sqrtf of the same square)
-        rate = tab.kick_rate[pa] * (1.0f - 0.25f * (dir_diff * 0.005555555555555556f) - 0.25f * (dist_ball * tab.inv_margin[pa]));
-      }
-      sh.row[3] = make_float4(akick ? 1.0f : 0.0f, rate, sh.catch_ban[pa], tab.type_id[pa]);
-      sh.row[4] = make_float4(ox, oy, ovx, ovy);
-      const int hside = holder > 0 ? side_of(holder - 1) : SIDE_NONE;
-      sh.row[5] = make_float4(dist, bearing, m_side_word(last_touch, ours), m_side_word(hside, ours));
-    } else if (l <= BALL + 6) {                        // game block: lane 23 + g writes words 4g..4g+3
-      const int g = l - (BALL + 1);
-      const uint32_t team = right ? 0x3FF800u : 0x7FFu;
-      const uint32_t km_tm = kick_mask & team & ~(1u << pa), km_op = kick_mask & (0x3FFFFFu ^ team);
-      const float k_tm = km_tm ? (float)(__builtin_ctz(km_tm) % 11 + 1) : 0.0f;
-      const float k_op = km_op ? (float)(__builtin_ctz(km_op) % 11 + 1) : 0.0f;
-      const int* rs = sh.rank_slot[S];
-      const int t1 = rs[0] == pa ? rs[1] : rs[0];
-      const int t2 = (rs[0] == pa || rs[1] == pa) ? rs[2] : rs[1];
-      const int* ro = sh.rank_slot[1 - S];
-      const float t1r = t1 >= 0 ? sh.reach[t1] : (float)S2D_AGENT_REACH_NONE, t1u = t1 >= 0 ? (float)(t1 % 11 + 1) : 0.0f;
-      const float t2r = t2 >= 0 ? sh.reach[t2] : (float)S2D_AGENT_REACH_NONE, t2u = t2 >= 0 ? (float)(t2 % 11 + 1) : 0.0f;
-      const float o1r = ro[0] >= 0 ? sh.reach[ro[0]] : (float)S2D_AGENT_REACH_NONE, o1u = ro[0] >= 0 ? (float)(ro[0] % 11 + 1) : 0.0f;
-      const float o2r = ro[1] >= 0 ? sh.reach[ro[1]] : (float)S2D_AGENT_REACH_NONE, o2u = ro[1] >= 0 ? (float)(ro[1] % 11 + 1) : 0.0f;
-      const float sp = in_modes(mode, kOurSetPlayModes) ? 1.0f : 0.0f;
-      const float side_w = m_side_word(mode_side, ours);
-      float4 w;
-      switch (g) {
-        case 0: w = make_float4((float)mode, side_w, (float)(right ? score_r : score_l), (float)(right ? score_l : score_r)); break;
-        case 1: w = make_float4((float)cycle, (float)stopped, (float)cycles_to_period_end(p, cycle),
-                                in_modes(mode, kPenaltyModes) ? 1.0f : 0.0f); break;
-        case 2: w = make_float4(offside_line[S], def_ours[S], def_theirs[S], k_tm); break;
-        case 3: w = make_float4(k_op, sh.reach[pa], t1r, t1u); break;
-        case 4: w = make_float4(t2r, t2u, o1r, o1u); break;
-        default: w = make_float4(o2r, o2u, side_w > 0.0f ? sp : 0.0f, side_w < 0.0f ? sp : 0.0f); break;
-      }
-      sh.row[S2D_AGENT_OBS_GAME / 4 + g] = w;
-    }
+    m_agent_row(p, tab, sh, in, f, l, pa, sh.row);
     wave_fence();
-    if (valid) {
-      float4* dst = reinterpret_cast<float4*>(out + (int64_t)r * S2D_AGENT_OBS_DIM);
-      dst[l] = sh.row[l];
-      if (l + kHalf < kAObsVec) dst[l + kHalf] = sh.row[l + kHalf];
-    }
+    if (valid) m_agent_row_store(out + (int64_t)r * S2D_AGENT_OBS_DIM, sh.row, l);
     wave_fence();
   }
 }
@@ -1683,6 +1864,9 @@ struct S2DMatchEngine {
   bool stock_types = false;                            // ... and every player is of the stock PlayerType (ptab's entries equal MStockTypes)
   bool stock_sched = false;                            // stock rules, physics and types, the engine's own schedule (MStockSched)
   bool has_ctl = false;                                // s2d_match_set_controllers installed a table: launches use the CTL kernels
+  bool has_net = false;                                // s2d_match_set_network installed a network: launches use the NET kernels
+  S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time)
+  float* net_frags = nullptr;                          // the fragment-order copy the pack kernel writes (kNetFragsMax words)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
   char* arena; size_t arena_bytes; bool owns_arena;
@@ -2089,6 +2273,7 @@ S2D_API int s2d_match_create(const S2DMatchConfig* cfg, int64_t n_envs, int devi
 S2D_API void s2d_match_destroy(S2DMatchHandle h) {
   if (!h) return;
   if (h->owns_arena && h->arena) { MDeviceGuard guard(h->device); (void)hipFree(h->arena); }
+  if (h->net_frags) { MDeviceGuard guard(h->device); (void)hipFree(h->net_frags); }
   delete h;
 }
 S2D_API int s2d_match_buffers(S2DMatchHandle h, S2DMatchBuffers* out) {
@@ -2110,46 +2295,155 @@ S2D_API int s2d_match_buffer_offsets(S2DMatchHandle h, int64_t* offsets, int n_o
   return S2D_OK;
 }
 
-// One launch of the instantiation this engine runs; CTL (with one MCtl in `extra`): the controller variant of the same one.
-template <bool CTL, class... X>
+// NET instantiations: the dynamic LDS limit is a per-device property of the function; raise it once per (device, instantiation) to
+// what the CU leaves beside the kernel's static LDS, under a lock (engines on several devices may be driven from several threads)
+static constexpr size_t kNetLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all of it available to one workgroup
+static constexpr int kNetMaxDevices = 64;
+static bool m_net_allow_lds(const void* fn, int slot, size_t dyn) {
+  static std::mutex mu;
+  static size_t limit[kNetMaxDevices][5] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kNetMaxDevices) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!limit[dev][slot]) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.sharedSizeBytes >= kNetLdsMax) return false;
+    const size_t room = kNetLdsMax - fa.sharedSizeBytes;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) != hipSuccess) return false;
+    limit[dev][slot] = room;
+  }
+  return dyn <= limit[dev][slot];
+}
+template <class K> static int m_net_launch(K kernel, int slot, size_t dyn, dim3 grid, dim3 block, hipStream_t st, const MParams& mp,
+                                           const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
+                                           const MCtl& ctl, const MNetArg& na) {
+  if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn))
+    return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
+  hipLaunchKernelGGL(kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
+  return S2D_OK;
+}
+
+// One launch of the instantiation this engine runs; CTL (with one MCtl in `extra`): the controller variant of the same one;
+// NET (with an MCtl and an MNetArg): the network variant, with `dyn` bytes of dynamic LDS.
+template <bool CTL, bool NET = false, class... X>
 static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, X... extra) {
   MDeviceGuard guard(h->device);
   const dim3 grid(m_grid(h->n)), block(kMBlock);
-  if (h->stock_sched)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, true, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+  if constexpr (NET) {
+    const MNetArg& na = std::get<1>(std::tie(extra...));
+    const size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * kNetWaveWords) * sizeof(float);
+    int rc;
+    if (h->stock_sched)
+      rc = m_net_launch(s2d_match_rollout_kernel<true, true, true, false, true, true, X...>, 0, dyn, grid, block, st, h->mp, h->ptrs,
+                        h->n, n_steps, actions, ro, extra...);
+    else if (h->stock_types)
+      rc = m_net_launch(s2d_match_rollout_kernel<true, true, false, false, true, true, X...>, 1, dyn, grid, block, st, h->mp, h->ptrs,
+                        h->n, n_steps, actions, ro, extra...);
+    else if (h->stock)
+      rc = m_net_launch(s2d_match_rollout_kernel<true, false, false, false, true, true, X...>, 2, dyn, grid, block, st, h->mp, h->ptrs,
+                        h->n, n_steps, actions, ro, extra...);
+    else if (h->mp.illegal_defense_number > 0)
+      rc = m_net_launch(s2d_match_rollout_kernel<false, false, false, true, true, true, X...>, 3, dyn, grid, block, st, h->mp, h->ptrs,
+                        h->n, n_steps, actions, ro, extra...);
+    else
+      rc = m_net_launch(s2d_match_rollout_kernel<false, false, false, false, true, true, X...>, 4, dyn, grid, block, st, h->mp, h->ptrs,
+                        h->n, n_steps, actions, ro, extra...);
+    if (rc != S2D_OK) return rc;
+  } else if (h->stock_sched)
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, true, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
                        actions, ro, extra...);
   else if (h->stock_types)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
                        actions, ro, extra...);
   else if (h->stock)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, false, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, false, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
                        actions, ro, extra...);
   else if (h->mp.illegal_defense_number > 0)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, true, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, true, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
                        actions, ro, extra...);
   else
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, false, CTL, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
+    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
                        actions, ro, extra...);
   MHIP_TRY(hipGetLastError());
   return S2D_OK;
 }
-// actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL)
+
+// The caller's parameters (torch order: W1 [h1][224], b1, W2 [h2][h1], b2, W3 [na][h2], b3) into the engine's fragment-order copy:
+// W1's fragments [h1/16][56][64], W2's [h2/16][h1/4][64], W3's [na16/16][h2/4][64] (rows past na zero), b1 | b2 | b3 (zero past na).
+// Enqueued by every network launch, so that a captured graph repacks what the parameter buffer holds at replay.
+__global__ __launch_bounds__(256) void s2d_match_net_pack_kernel(const float* __restrict__ params, int h1, int h2, int na, int na16,
+                                                                 float* __restrict__ frags, int total) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int f1 = h1 / 16 * kNetK1, f2 = h2 / 16 * (h1 / 4), f3 = na16 / 16 * (h2 / 4);
+  const int o_b1 = S2D_AGENT_OBS_DIM * h1, o_w2 = o_b1 + h1, o_b2 = o_w2 + h2 * h1, o_w3 = o_b2 + h2, o_b3 = o_w3 + na * h2;
+  float v = 0.0f;
+  if (idx < (f1 + f2 + f3) * 64) {
+    const int f = idx / 64, l = idx & 63, row = l & 15, kk = l >> 4;
+    if (f < f1) {
+      const int jt = f / kNetK1, s = f - kNetK1 * jt;
+      v = params[(16 * jt + row) * S2D_AGENT_OBS_DIM + 4 * s + kk];
+    } else if (f < f1 + f2) {
+      const int g2 = f - f1, ks = h1 / 4, jt = g2 / ks, s = g2 - jt * ks;
+      v = params[o_w2 + (16 * jt + row) * h1 + 4 * s + kk];
+    } else {
+      const int g3 = f - f1 - f2, ks = h2 / 4, jt = g3 / ks, s = g3 - jt * ks, j = 16 * jt + row;
+      if (j < na) v = params[o_w3 + j * h2 + 4 * s + kk];
+    }
+  } else {
+    const int j = idx - (f1 + f2 + f3) * 64;
+    if (j < h1) v = params[o_b1 + j];
+    else if (j < h1 + h2) v = params[o_b2 + j - h1];
+    else if (j - h1 - h2 < na) v = params[o_b3 + j - h1 - h2];
+  }
+  frags[idx] = v;
+}
+static constexpr int kNetFragsMax = (64 / 16 * kNetK1 + 64 / 16 * (64 / 4) + 64 / 16 * (64 / 4)) * 64 + 64 + 64 + 64;
+
+// actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL).
+// With a network set, or a row record asked for (obs_mask), the NET instantiation runs (after the pack kernel, when there is a network).
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
-                    float* actions_out = nullptr) {
+                    float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
+                    float* agent_obs_out = nullptr) {
   MRoll ro{nullptr, nullptr, nullptr, nullptr};
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr uint32_t kAll = (1u << NP) - 1u;
-  if (h->has_ctl) {
-    if (!actions && ((h->ctl_random | h->ctl_script) & kAll) != kAll)
-      return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
-    return m_dispatch<true>(h, n_steps, actions, ro, st, MCtl{h->ctl_random, h->ctl_script, actions_out});
+  const uint32_t net_mask = h->has_net ? h->net.slot_mask : 0u;
+  if (!agent_obs_out) obs_mask = 0u;
+  if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
+    return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
+  const MCtl ctl = h->has_ctl ? MCtl{h->ctl_random, h->ctl_script, actions_out} : MCtl{actions ? 0u : kAll, 0u, actions_out};
+  if (net_mask || obs_mask || net_index_out) {
+    MNetArg na;
+    std::memset(&na, 0, sizeof na);
+    MNet& nt = na.net;
+    nt.net_mask = net_mask; nt.obs_mask = obs_mask; nt.row_mask = net_mask | obs_mask;
+    nt.net_index = net_index_out; nt.agent_obs = agent_obs_out;
+    na.tab = h->atab;
+    if (net_mask) {
+      nt.h1 = h->net.h1; nt.h2 = h->net.h2; nt.na = h->net.n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
+      nt.frags = h->net_frags; nt.epsilon = h->net.epsilon; nt.table = h->net.table;
+      nt.shared_words = (nt.h2 / 16 * (nt.h1 / 4) + nt.na16 / 16 * (nt.h2 / 4)) * 64 + nt.h1 + nt.h2 + nt.na16;
+      const int total = (nt.h1 / 16 * kNetK1) * 64 + nt.shared_words;
+      MDeviceGuard guard(h->device);
+      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->net.params, nt.h1, nt.h2, nt.na,
+                         nt.na16, h->net_frags, total);
+      MHIP_TRY(hipGetLastError());
+    }
+    return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
   }
-  if (actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, MCtl{actions ? 0u : kAll, 0u, actions_out});
+  if (h->has_ctl || actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, ctl);
   return m_dispatch<false>(h, n_steps, actions, ro, st);
 }
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
+  if (h->has_net) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, network>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, network>" : h->stock ? "s2d_match_rollout_kernel<stock, network>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, network>" :
+                                              "s2d_match_rollout_kernel<general, network>";
+  }
   if (h->has_ctl) {
     if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, controllers>";
     return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, controllers>" : h->stock ? "s2d_match_rollout_kernel<stock, controllers>" :
@@ -2213,4 +2507,43 @@ S2D_API int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float* act
     return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
   if (n_steps == 0) return S2D_OK;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev);
+}
+S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { h->has_net = false; h->net = S2DMatchNet{}; return S2D_OK; }
+  const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
+  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "network hidden widths must be 16, 32, 48 or 64");
+  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "network n_actions must be in [1, 64]");
+  if (net->slot_mask == 0u || (net->slot_mask >> NP) != 0u)
+    return mfail(S2D_EINVAL, "network slot_mask must be a non-empty set of bits 0..21");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return mfail(S2D_EINVAL, "network params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->epsilon || !net->table || ((reinterpret_cast<uintptr_t>(net->epsilon) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
+    return mfail(S2D_EINVAL, "network epsilon and table must be non-NULL, 4-byte aligned device pointers");
+  if (!h->net_frags) {
+    MDeviceGuard guard(h->device);
+    void* pmem = nullptr;
+    if (hipMalloc(&pmem, (size_t)kNetFragsMax * sizeof(float)) != hipSuccess) return mfail(S2D_ENOMEM, "hipMalloc of the network copy failed");
+    h->net_frags = static_cast<float*>(pmem);
+  }
+  h->net = *net; h->has_net = true;
+  return S2D_OK;
+}
+S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
+                                  float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask, float* agent_obs_out_dev,
+                                  void* stream) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
+  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
+  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
+  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
+  if (agent_obs_out_dev) {
+    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
+      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when agent_obs_out is given");
+    if (reinterpret_cast<uintptr_t>(agent_obs_out_dev) & 15u) return mfail(S2D_EINVAL, "agent_obs_out must be 16-byte aligned");
+  }
+  if (n_steps == 0) return S2D_OK;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev);
 }

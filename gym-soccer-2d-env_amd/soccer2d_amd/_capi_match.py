@@ -118,6 +118,16 @@ class S2DMatchRollout(C.Structure):
     _fields_ = [('obs', C.c_void_p), ('reward', C.c_void_p), ('mode', C.c_void_p), ('done', C.c_void_p)]
 
 
+class S2DMatchNet(C.Structure):             # include/s2d_match.h: network slots
+    _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
+                ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p)]
+
+
+MATCH_NET_WIDTHS = (16, 32, 48, 64)
+MATCH_NET_MAX_ACTIONS = 64
+MATCH_ST_NET = 7                           # S2D_MATCH_ST_NET: Philox stream of the network slots' exploration
+
+
 MATCH_PROTOTYPES = (
     ('s2d_match_default_config', None, (C.POINTER(S2DMatchConfig),)),
     ('s2d_match_default_player_params', None, (C.POINTER(S2DPlayerParams),)),
@@ -137,6 +147,9 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_controllers', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_ex', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p)),
     ('s2d_match_agent_obs', C.c_int, (C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_network', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_net', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_void_p)),
 )
 
 

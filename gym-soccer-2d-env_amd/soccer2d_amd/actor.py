@@ -245,3 +245,110 @@ class DeterministicActor:
         net.epsilon = self._eps.data_ptr()
         net.noise = self._noise.data_ptr()
         return net
+
+
+def match_param_count(h1, h2, k):
+    """words of a 224-H1-H2-K network in nn.Sequential order"""
+    return h1 * MATCH_OBS_DIM + h1 + h2 * h1 + h2 + k * h2 + k
+
+
+MATCH_OBS_DIM = 224                  # S2D_AGENT_OBS_DIM: the 11v11 engine's per-agent row
+MATCH_WIDTHS = (16, 32, 48, 64)
+MATCH_MAX_ACTIONS = 64
+
+
+class MatchQNetActor:
+    """Packed parameters, device epsilon and action table of a 224-H1-H2-K ReLU Q-network for the 11v11 engine's network slots
+    (MatchEngine.set_network, s2d_match_set_network in include/s2d_match.h).
+
+    The network sees one agent's own-frame row (MatchEngine.agent_observations); its index chooses a row of `table`, float32
+    [K, 3] = (command, a, b).  params, epsilon and table are device buffers written in place (``sync()``, ``epsilon = ...``,
+    ``set_table()``) and read when the kernel runs, so a captured graph acts with what they hold at replay."""
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05, table=None):
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in MATCH_WIDTHS:
+                raise ValueError(f'{name} must be one of {MATCH_WIDTHS}, got {w}')
+        if not 1 <= int(n_actions) <= MATCH_MAX_ACTIONS:
+            raise ValueError(f'n_actions must be in [1, {MATCH_MAX_ACTIONS}], got {n_actions}')
+        self.hidden1, self.hidden2, self.n_actions = int(hidden1), int(hidden2), int(n_actions)
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.params = torch.zeros(match_param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32,
+                                  device=self.device)
+        self.table = torch.zeros((self.n_actions, 3), dtype=torch.float32, device=self.device)
+        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._eps_value = None
+        self.epsilon = epsilon
+        self._module = None
+        if table is not None:
+            self.set_table(table)
+
+    @classmethod
+    def from_module(cls, module, table, device=None, epsilon=0.05):
+        """An actor shaped like `module` (three nn.Linear layers 224 -> H1 -> H2 -> K), loaded from it, with action table
+        `table` [K, 3]."""
+        l1, l2, l3 = _linears(module)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon)
+        actor.load_from(module)
+        actor.set_table(table)
+        return actor
+
+    def shapes(self):
+        h1, h2, k = self.hidden1, self.hidden2, self.n_actions
+        return ((h1, MATCH_OBS_DIM), (h1,), (h2, h1), (h2,), (k, h2), (k,))
+
+    def load_from(self, module):
+        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
+        got = []
+        for lin in _linears(module):
+            if lin.bias is None:
+                raise ValueError('every nn.Linear of the Q-network needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if tuple(got) != self.shapes():
+            raise ValueError(f'Q-network shapes {got} do not match the actor {list(self.shapes())}')
+        self._module = module
+        self.sync()
+        return self
+
+    def sync(self):
+        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
+        if self._module is None:
+            raise ValueError('no module loaded (load_from)')
+        srcs = []
+        for lin in _linears(self._module):
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+        return self
+
+    def set_table(self, table):
+        """Write the action table (float [K, 3] = command, a, b per index) in place."""
+        t = torch.as_tensor(table, dtype=torch.float32)
+        if tuple(t.shape) != (self.n_actions, 3):
+            raise ValueError(f'action table must have shape ({self.n_actions}, 3), got {tuple(t.shape)}')
+        self.table.copy_(t.to(self.device))
+        return self
+
+    @property
+    def epsilon(self):
+        return self._eps_value
+
+    @epsilon.setter
+    def epsilon(self, value):
+        """Written in place into the device scalar the kernel reads (stream-ordered on torch's current stream)."""
+        self._eps_value = float(value)
+        self._eps.fill_(self._eps_value)
+
+    @property
+    def epsilon_tensor(self):
+        return self._eps
+
+    def c_struct(self, slot_mask):
+        from . import _capi_match as M
+        net = M.S2DMatchNet()
+        net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
+        net.params, net.epsilon, net.table = self.params.data_ptr(), self._eps.data_ptr(), self.table.data_ptr()
+        return net

@@ -68,6 +68,7 @@ class MatchEngine:
     def __init__(self, num_envs, device='cuda:0', cfg=None, **kwargs):
         self.lib = M.bind(_capi.load_library())
         self.controllers = None                         # no per-slot table (set_controllers)
+        self.network, self.network_mask = None, 0       # no network slots (set_network)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device(device)
@@ -127,6 +128,22 @@ class MatchEngine:
         _capi.check(self.lib, self.lib.s2d_match_set_controllers(self._h, buf), 's2d_match_set_controllers')
         self.controllers = None if codes is None else list(codes)
 
+    def set_network(self, actor, slots='all'):
+        """Network slots: `actor` (a MatchQNetActor) chooses the action of every slot in `slots` ('all' | 'left' | 'right' | a
+        mask of bits 0..21) inside the cycle kernel, on the slot's agent row (include/s2d_match.h).  It overrides the controller
+        table for those slots; the engine keeps the actor's buffers, so sync() / epsilon / set_table() act at the next launch (or
+        graph replay).  None clears the network."""
+        if actor is None:
+            _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, None), 's2d_match_set_network')
+            self.network, self.network_mask = None, 0
+            return
+        mask = M.agent_slot_mask(slots)
+        if actor.device != self.device:
+            raise ValueError(f"the actor's buffers are on {actor.device}, the engine on {self.device}")
+        net = actor.c_struct(mask)
+        _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
+        self.network, self.network_mask = actor, mask
+
     def _actions(self, actions, T=None):
         if actions is None:
             return None, None
@@ -163,9 +180,11 @@ class MatchEngine:
             out['actions'] = torch.empty((T, n, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=dev)
         return out
 
-    def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False):
+    def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None):
         """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
-        each cycle, before the engine's own gating (caller slots: the caller's row)."""
+        each cycle, before the engine's own gating (caller slots: the caller's row).  net_index: out['net_index'] int32
+        [T, N, 22] receives each network slot's index (-1 for the other slots).  agent_obs = 'all' | 'left' | 'right' | a mask:
+        out['agent_obs'] float32 [T, N, k, 224] receives those slots' start-of-cycle agent rows (the learner's obs_t)."""
         T = int(n_steps)
         keep, ptr = self._actions(actions, T)
         if out is None:
@@ -180,6 +199,8 @@ class MatchEngine:
                     raise ValueError(f"rollout buffer {name!r} must be contiguous [T>={T},{self.num_envs},...]")
                 setattr(ro, name, v.data_ptr())
         rec = out.get('actions') if record_actions else None
+        if net_index or agent_obs is not None:
+            return self._rollout_net(T, ptr, ro, rec, out, keep, net_index, agent_obs)
         if rec is not None:
             if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or tuple(rec.shape[1:]) != (self.num_envs, M.MATCH_PLAYERS, 3):
                 raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{self.num_envs},22,3]")
@@ -187,6 +208,33 @@ class MatchEngine:
                         's2d_match_rollout_ex')
         else:
             _capi.check(self.lib, self.lib.s2d_match_rollout(self._h, T, ptr, C.byref(ro), self._stream()), 's2d_match_rollout')
+        self._keep = (keep, out)
+        return out
+
+    def _rollout_net(self, T, ptr, ro, rec, out, keep, net_index, agent_obs):
+        n, dev = self.num_envs, self.device
+        if rec is not None and (rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or
+                                tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
+            raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{n},22,3]")
+        idx = None
+        if net_index:
+            idx = out.get('net_index')
+            if idx is None:
+                idx = out['net_index'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.int32, device=dev)
+            elif idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape[0] < T or tuple(idx.shape[1:]) != (n, M.MATCH_PLAYERS):
+                raise ValueError(f"rollout buffer 'net_index' must be contiguous int32 [T>={T},{n},22]")
+        obs, mask = None, 0
+        if agent_obs is not None:
+            mask = M.agent_slot_mask(agent_obs)
+            shape = (n, bin(mask).count('1'), M.AGENT_OBS_DIM)
+            obs = out.get('agent_obs')
+            if obs is None:
+                obs = out['agent_obs'] = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
+            elif obs.dtype != torch.float32 or not obs.is_contiguous() or obs.shape[0] < T or tuple(obs.shape[1:]) != shape:
+                raise ValueError(f"rollout buffer 'agent_obs' must be contiguous float32 [T>={T},{n},{shape[1]},224]")
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _capi.check(self.lib, self.lib.s2d_match_rollout_net(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), mask, vp(obs),
+                                                              self._stream()), 's2d_match_rollout_net')
         self._keep = (keep, out)
         return out
 
@@ -264,6 +312,11 @@ class MatchEngine:
         return wm
 
 
+def _is_match_actor(obj):
+    from .actor import MatchQNetActor
+    return isinstance(obj, MatchQNetActor)
+
+
 class Soccer2DMatchVecEnv:
     """gym-style surface over MatchEngine for BASELINE.json configs[3] ("11v11 full-match env"):
     ``reset() -> obs``, ``step(actions) -> (obs, reward, done, info)`` with device tensors.
@@ -276,8 +329,9 @@ class Soccer2DMatchVecEnv:
     done    uint8 [N]           1 when a match reached TimeOver (auto-restart follows the VecEnv convention).
     info    dict of tensors     game_mode_type, game_mode_side, scores, cycle, nearest player per team.
 
-    opponent = 'random' | 'scripted': the learner controls the left team only -- actions float32 [N, 11, 3] -- and the right
-    team is played inside the cycle kernel (the random policy, or the scripted team of include/s2d_match.h).  None: both teams
+    opponent = 'random' | 'scripted' | a MatchQNetActor: the learner controls the left team only -- actions float32 [N, 11, 3] --
+    and the right team is played inside the cycle kernel (the random policy, the scripted team of include/s2d_match.h, or the
+    actor's network on each right slot's agent row: a frozen past copy of the learner).  None: both teams
     come from the caller, as above.
 
     obs = 'agent': every controlled agent observes in its own team's frame (MatchEngine.agent_observations), so that one policy
@@ -291,8 +345,8 @@ class Soccer2DMatchVecEnv:
         """(observation_space, action_space) of an env with this opponent and observation (no engine needed)."""
         import numpy as np
         from .spaces import Box
-        if opponent not in (None, 'random', 'scripted'):
-            raise ValueError(f"opponent must be None, 'random' or 'scripted', got {opponent!r}")
+        if not (opponent in (None, 'random', 'scripted') or _is_match_actor(opponent)):
+            raise ValueError(f"opponent must be None, 'random', 'scripted' or a MatchQNetActor, got {opponent!r}")
         if obs not in ('state', 'agent'):
             raise ValueError(f"obs must be 'state' or 'agent', got {obs!r}")
         agents = 22 if opponent is None else 11
@@ -308,8 +362,13 @@ class Soccer2DMatchVecEnv:
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
         self.opponent, self.obs_kind = opponent, obs
         self._ro = self.engine.alloc_rollout(1)
-        if opponent is not None:
+        if _is_match_actor(opponent):
+            # the right team on a frozen network (a past copy of the learner): its slots' controller is the network
+            self.engine.set_controllers({'left': 'external', 'right': 'random'})
+            self.engine.set_network(opponent, 'right')
+        elif opponent is not None:
             self.engine.set_controllers({'left': 'external', 'right': opponent})
+        if opponent is not None:
             # the caller's half of the action rows; the right team's rows are never read
             self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
         if obs == 'agent':

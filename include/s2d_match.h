@@ -351,6 +351,45 @@ int s2d_match_relative(S2DMatchHandle h, float *dist_dev, float *angle_dev, void
  * Errors: a mask with bits above 21, an empty mask, a NULL or unaligned obs_dev. */
 int s2d_match_agent_obs(S2DMatchHandle h, uint32_t slot_mask, float *obs_dev, void *stream);
 
+/* Network slots: the caller's epsilon-greedy Q-network chooses the action of every slot in slot_mask inside the cycle kernel, on
+ * that slot's own-frame agent row.  One network serves all its slots (both teams: self-play); the other slots keep their
+ * controllers (the table of s2d_match_set_controllers, or the caller's rows / the random policy without one).  For network slot l
+ * of match e in a cycle:
+ *   1. x = the slot's S2D_AGENT_OBS_DIM-word row of the START-of-cycle state: bitwise what s2d_match_agent_obs returns for it (the
+ *      two share one device function).
+ *   2. y = W3 relu(W2 relu(W1 x + b1) + b2) + b3, each unit acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc); relu maps
+ *      NaN and -0 to +0.  params (device, 16-byte aligned, torch nn.Sequential(...).parameters() order):
+ *      W1[h1][224], b1[h1], W2[h2][h1], b2[h2], W3[K][h2], b3[K]; h1, h2 in {16, 32, 48, 64}, 1 <= K <= 64.
+ *   3. greedy = the first index of the maximum of y (best = 0; for a = 1 .. K-1: if (y[a] > y[best]) best = a: a NaN never
+ *      replaces the best).
+ *   4. exploration: w = Philox block (counter = the match's tick, stream S2D_MATCH_ST_NET, block = l), the random policy's keys;
+ *      thr = *epsilon >= 1 ? 2^32 : *epsilon > 0 ? (uint64)(*epsilon * 2^32) : 0 (epsilon read when the kernel runs);
+ *      index = w.x < thr ? (w.y * K) >> 32 : greedy.
+ *   5. (cmd, a, b) = table[index] (device float[K][3], read at run time; cmd = (int)table[index][0]), then the engine's usual
+ *      gating, exactly as for a scripted slot.  Bodies are relative and Move is in own-frame coordinates: no per-side conversion.
+ * The engine keeps the pointers, not copies: a launch (or a captured graph's replay) acts with what params, epsilon and table
+ * hold when it runs; every launch first repacks params into an engine-owned copy in the kernel's fragment order. */
+#define S2D_MATCH_ST_NET 7   /* Philox stream id of the network slots' exploration (no other match draw uses it) */
+typedef struct S2DMatchNet {
+  int32_t h1, h2, n_actions;   /* hidden widths, K */
+  uint32_t slot_mask;          /* bits 0..21 */
+  const float *params;         /* device, 16-byte aligned, layout above */
+  const float *epsilon;        /* device float */
+  const float *table;          /* device float[K][3] */
+} S2DMatchNet;
+/* net == NULL: no network (the behaviour above).  Errors (S2D_EINVAL, the engine unchanged): h1 / h2 not in {16, 32, 48, 64},
+ * n_actions outside [1, 64], an empty slot_mask or bits above 21, NULL or unaligned pointers.  s2d_match_step, s2d_match_rollout and
+ * s2d_match_rollout_ex use the network when one is set; a caller row of a network slot is never read. */
+int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet *net);
+/* s2d_match_rollout_ex plus two records (either may be NULL):
+ *   net_index_out_dev  int32[T][N][22]: the index each network slot chose, -1 for the other slots (4-byte aligned);
+ *   agent_obs_out_dev  float[T][N][popcount(obs_mask)][S2D_AGENT_OBS_DIM]: the start-of-cycle rows of the slots in obs_mask, in
+ *                      ascending slot order (the learner's obs_t; 16-byte aligned; written as whole 64-byte lines).
+ * Errors: as s2d_match_rollout_ex; unaligned records; agent_obs_out_dev with an empty obs_mask or bits above 21. */
+int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float *actions_dev, const S2DMatchRollout *out,
+                          float *actions_out_dev, int32_t *net_index_out_dev, uint32_t obs_mask, float *agent_obs_out_dev,
+                          void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
