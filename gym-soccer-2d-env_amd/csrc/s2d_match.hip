@@ -2547,3 +2547,12 @@ S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* ac
   if (n_steps == 0) return S2D_OK;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev);
 }
+
+// What the vision layer (s2d_see.hip, a translation unit of its own) needs of an engine beyond s2d_match_buffers(): the Philox key
+// and id words of its draws and its device.  Library-internal (hidden visibility): not part of the C ABI.
+extern "C" int s2d_match_internal_keys(S2DMatchHandle h, uint32_t keys[4], int* device) {
+  if (!h) return S2D_EINVAL;
+  keys[0] = h->mp.seed_lo; keys[1] = h->mp.seed_hi; keys[2] = h->mp.gid_lo; keys[3] = h->mp.gid_hi;
+  *device = h->device;
+  return S2D_OK;
+}

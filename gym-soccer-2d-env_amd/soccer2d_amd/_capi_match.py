@@ -46,6 +46,22 @@ for _t, _base in (('teammates', 48), ('opponents', 136)):       # [..., 11 rows]
         AGENT_OBS_FIELDS[f'{_t}.{_n}'] = slice(_base + _i, _base + 88, 8)
 AGENT_SLOT_MASKS = {'all': 0x3FFFFF, 'left': 0x7FF, 'right': 0x3FF800}
 
+# the vision layer (s2d_match_see; the words are specified in include/s2d_match.h, "Vision")
+SEE_DIM, MATCH_ST_SEE = 192, 8
+VIEW_KEEP, VIEW_NARROW, VIEW_NORMAL, VIEW_WIDE = 0, 1, 2, 3
+VIEW_CODES = {'keep': VIEW_KEEP, 'narrow': VIEW_NARROW, 'normal': VIEW_NORMAL, 'wide': VIEW_WIDE}
+SEE_LEVEL_UNSEEN, SEE_LEVEL_FELT, SEE_LEVEL_NO_TEAM, SEE_LEVEL_TEAM, SEE_LEVEL_FULL = 0, 1, 2, 3, 4
+SEE_BLOCKS = {'self': slice(0, 16), 'ball': slice(16, 24), 'players': slice(24, 192)}
+SEE_ROW_FIELDS = ('level', 'team', 'unum', 'dist', 'dir', 'dist_chg', 'dir_chg', 'body_rel')     # one player row
+SEE_FIELDS = {}                                        # every word 0..191 exactly once: name -> index, or a slice over the 21 rows
+for _i, _n in enumerate(('x', 'y', 'vx', 'vy', 'body', 'neck', 'face', 'view_width', 'fresh', 'see_wait', 'stamina', 'effort',
+                         'recovery', 'stamina_capacity', 'is_goalie', 'card')):
+    SEE_FIELDS['self.' + _n] = 0 + _i
+for _i, _n in enumerate(('level', 'dist', 'dir', 'dist_chg', 'dir_chg', 'game_mode_type', 'mode_side', 'cycle')):
+    SEE_FIELDS['ball.' + _n] = 16 + _i
+for _i, _n in enumerate(SEE_ROW_FIELDS):
+    SEE_FIELDS['players.' + _n] = slice(24 + _i, 192, 8)
+
 
 class S2DMatchParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
@@ -123,6 +139,19 @@ class S2DMatchNet(C.Structure):             # include/s2d_match.h: network slots
                 ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p)]
 
 
+VISION_PARAM_FIELDS = ('visible_distance', 'dist_quantize_step', 'dist_round', 'dist_chg_quantize', 'dir_chg_quantize',
+                       'unum_far_length', 'unum_too_far_length', 'team_far_length', 'team_too_far_length',
+                       'min_neck_moment', 'max_neck_moment', 'min_neck_angle', 'max_neck_angle')
+
+
+class S2DVisionParams(C.Structure):         # include/s2d_match.h: Vision
+    _fields_ = [('view_angle', C.c_double * 3), ('see_interval', C.c_double * 3)] + [(n, C.c_double) for n in VISION_PARAM_FIELDS]
+
+
+class S2DMatchVision(C.Structure):          # the caller-owned vision planes, [N][24] each
+    _fields_ = [('neck', C.c_void_p), ('view_width', C.c_void_p), ('see_wait', C.c_void_p)]
+
+
 MATCH_NET_WIDTHS = (16, 32, 48, 64)
 MATCH_NET_MAX_ACTIONS = 64
 MATCH_ST_NET = 7                           # S2D_MATCH_ST_NET: Philox stream of the network slots' exploration
@@ -150,6 +179,13 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_net', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_vision_default_params', None, (C.POINTER(S2DVisionParams),)),
+    ('s2d_match_vision_validate', C.c_int, (C.POINTER(S2DVisionParams),)),
+    ('s2d_match_vision_reset', C.c_int, (C.c_void_p, C.POINTER(S2DMatchVision), C.c_void_p, C.c_void_p)),
+    ('s2d_match_vision_step', C.c_int, (C.c_void_p, C.POINTER(S2DVisionParams), C.POINTER(S2DMatchVision), C.c_void_p, C.c_void_p,
+                                        C.c_void_p)),
+    ('s2d_match_see', C.c_int, (C.c_void_p, C.POINTER(S2DVisionParams), C.POINTER(S2DMatchVision), C.c_uint32, C.c_void_p,
+                                C.c_void_p)),
 )
 
 
@@ -197,3 +233,24 @@ def agent_slot_mask(slots):
     if isinstance(slots, bool) or int(slots) != slots or not 0 < int(slots) <= 0x3FFFFF:
         raise ValueError(f"slot mask must be a non-empty set of bits 0..21, got {slots!r}")
     return int(slots)
+
+
+def vision_params(lib, **params):
+    """S2DVisionParams: the defaults of s2d_match_vision_default_params with `params` written over them (view_angle and
+    see_interval: three values, narrow / normal / wide), validated by s2d_match_vision_validate."""
+    from . import _capi
+    prm = S2DVisionParams()
+    lib.s2d_match_vision_default_params(C.byref(prm))
+    for k, v in params.items():
+        if k in ('view_angle', 'see_interval'):
+            vals = [float(x) for x in v]
+            if len(vals) != 3:
+                raise ValueError(f"{k} needs three values (narrow, normal, wide)")
+            for i, x in enumerate(vals):
+                getattr(prm, k)[i] = x
+        elif k in VISION_PARAM_FIELDS:
+            setattr(prm, k, float(v))
+        else:
+            raise ValueError(f"unknown vision parameter {k!r}")
+    _capi.check(lib, lib.s2d_match_vision_validate(C.byref(prm)), 's2d_match_vision_validate')
+    return prm

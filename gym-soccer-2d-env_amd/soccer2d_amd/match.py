@@ -69,6 +69,7 @@ class MatchEngine:
         self.lib = M.bind(_capi.load_library())
         self.controllers = None                         # no per-slot table (set_controllers)
         self.network, self.network_mask = None, 0       # no network slots (set_network)
+        self.vision = None                              # no vision layer (enable_vision)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device(device)
@@ -161,6 +162,9 @@ class MatchEngine:
                 raise ValueError(f"mask must have shape ({self.num_envs},)")
             ptr = C.c_void_p(mask.data_ptr())
         _capi.check(self.lib, self.lib.s2d_match_reset(self._h, ptr, self._stream()), 's2d_match_reset')
+        if self.vision is not None:
+            _capi.check(self.lib, self.lib.s2d_match_vision_reset(self._h, C.byref(self.vision), ptr, self._stream()),
+                        's2d_match_vision_reset')
         self._keep = mask
 
     def step(self, actions=None):
@@ -285,6 +289,60 @@ class MatchEngine:
                     's2d_match_agent_obs')
         return out
 
+    def enable_vision(self, **params):
+        """Switch the vision layer on (include/s2d_match.h, "Vision"): allocates the three state planes -- `neck` float32,
+        `view_width` int32, `see_wait` int32, each [N, 24] -- and resets them; from now on reset() resets them with the engine.
+        `params`: S2DVisionParams fields over the defaults (view_angle / see_interval: three values, narrow / normal / wide).
+        The engine itself does not change: the body step never reads these planes."""
+        self.vision_params = M.vision_params(self.lib, **params)
+        shape = (self.num_envs, M.MATCH_SLOTS)
+        self.neck = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.view_width = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.see_wait = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.vision = M.S2DMatchVision(self.neck.data_ptr(), self.view_width.data_ptr(), self.see_wait.data_ptr())
+        _capi.check(self.lib, self.lib.s2d_match_vision_reset(self._h, C.byref(self.vision), None, self._stream()),
+                    's2d_match_vision_reset')
+
+    def _need_vision(self):
+        if self.vision is None:
+            raise RuntimeError("the vision layer is off: call enable_vision() first")
+
+    def vision_step(self, view_actions=None, done=None):
+        """One cycle of the vision state; call it once after each body step.  view_actions float32 [N, 22, 2] = (TurnNeck
+        moment, ChangeView code 0 keep / 1 narrow / 2 normal / 3 wide) per player, None = nobody turns or changes.  done: None, True
+        (the engine's own `done` of the last step) or a uint8 [N] tensor: those matches' vision state is reset instead."""
+        self._need_vision()
+        a, aptr = None, None
+        if view_actions is not None:
+            a = torch.as_tensor(view_actions, device=self.device).to(torch.float32).contiguous()
+            if tuple(a.shape) != (self.num_envs, M.MATCH_PLAYERS, 2):
+                raise ValueError(f"view_actions must have shape ({self.num_envs}, {M.MATCH_PLAYERS}, 2), got {tuple(a.shape)}")
+            aptr = C.c_void_p(a.data_ptr())
+        d, dptr = None, None
+        if done is not None and done is not False:
+            d = self.done if done is True else torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
+            if tuple(d.shape) != (self.num_envs,):
+                raise ValueError(f"done must have shape ({self.num_envs},)")
+            dptr = C.c_void_p(d.data_ptr())
+        _capi.check(self.lib, self.lib.s2d_match_vision_step(self._h, C.byref(self.vision_params), C.byref(self.vision), aptr, dptr,
+                                                              self._stream()), 's2d_match_vision_step')
+        self._keep_vision = (a, d)
+
+    def see(self, slots='all', out=None):
+        """float32 [N, k, 192]: each selected agent's see row in its own team's frame (include/s2d_match.h, "Vision"; the words:
+        _capi_match.SEE_FIELDS), rows in ascending slot order; slots and `out` as for agent_observations.  A pure function of
+        the current state, the vision planes and the tick."""
+        self._need_vision()
+        mask = M.agent_slot_mask(slots)
+        shape = (self.num_envs, bin(mask).count('1'), M.SEE_DIM)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        _capi.check(self.lib, self.lib.s2d_match_see(self._h, C.byref(self.vision_params), C.byref(self.vision), mask,
+                                                      C.c_void_p(out.data_ptr()), self._stream()), 's2d_match_see')
+        return out
+
     def world_model(self):
         """dict proto-path -> device tensor (left team's point of view = absolute coordinates)."""
         P = M.MATCH_PLAYERS
@@ -338,6 +396,12 @@ class Soccer2DMatchVecEnv:
     can play either side.  opponent None is self-play: obs float32 [N, 22, 224], actions [N, 22, 3], reward [N, 22] (+reward
     for slots 0..10, its negative for 11..21).  With an in-kernel opponent: obs [N, 11, 224] (the left team only), actions
     [N, 11, 3], reward [N, 11].  The obs tensor is one buffer, rewritten by every reset() / step().
+
+    obs = 'see': partial observability -- every controlled agent gets its see row (MatchEngine.see: view cone, quantised
+    distances, identities lost with distance, see timing).  Shapes and rewards as for 'agent' with 192 words per agent, and
+    actions float32 [N, 22 or 11, 5] = (command, a, b, TurnNeck moment, ChangeView code).  A step is the body step, then
+    vision_step with the engine's done (a restarted match restarts its vision state), then see.  `vision` = a dict of
+    S2DVisionParams fields.  The row returned by reset() is not fresh (self and game words only); the first step's is.
     """
 
     @staticmethod
@@ -347,17 +411,22 @@ class Soccer2DMatchVecEnv:
         from .spaces import Box
         if not (opponent in (None, 'random', 'scripted') or _is_match_actor(opponent)):
             raise ValueError(f"opponent must be None, 'random', 'scripted' or a MatchQNetActor, got {opponent!r}")
-        if obs not in ('state', 'agent'):
-            raise ValueError(f"obs must be 'state' or 'agent', got {obs!r}")
+        if obs not in ('state', 'agent', 'see'):
+            raise ValueError(f"obs must be 'state', 'agent' or 'see', got {obs!r}")
         agents = 22 if opponent is None else 11
+        if obs == 'see':
+            return (Box(low=-1.0e6, high=1.0e6, shape=(agents, M.SEE_DIM), dtype=np.float32),
+                    Box(low=-180.0, high=180.0, shape=(agents, 5), dtype=np.float32))
         if obs == 'agent':
             ospace = Box(low=-1.0e6, high=1.0e6, shape=(agents, M.AGENT_OBS_DIM), dtype=np.float32)
         else:
             ospace = Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32)
         return ospace, Box(low=-180.0, high=180.0, shape=(agents, 3), dtype=np.float32)
 
-    def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', **kwargs):
+    def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, **kwargs):
         self.observation_space, self.action_space = self.spaces(opponent, obs)
+        if vision is not None and obs != 'see':
+            raise ValueError("vision parameters need obs='see'")
         self.engine = MatchEngine(num_envs, device, **kwargs)
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
         self.opponent, self.obs_kind = opponent, obs
@@ -371,7 +440,11 @@ class Soccer2DMatchVecEnv:
         if opponent is not None:
             # the caller's half of the action rows; the right team's rows are never read
             self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
-        if obs == 'agent':
+        if obs == 'see':
+            self.engine.enable_vision(**(vision or {}))
+            # the view half of the action rows; an in-kernel opponent's players never turn their necks or change their view
+            self._view = torch.zeros((self.num_envs, M.MATCH_PLAYERS, 2), dtype=torch.float32, device=self.device)
+        if obs in ('agent', 'see'):
             self._slots = 'all' if opponent is None else 'left'
             self._aobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
             # reward sign per agent: the left team's reward for slots 0..10, its negative for 11..21
@@ -381,13 +454,27 @@ class Soccer2DMatchVecEnv:
         e = self.engine
         if self.obs_kind == 'agent':
             return e.agent_observations(self._slots, out=self._aobs)
+        if self.obs_kind == 'see':
+            return e.see(self._slots, out=self._aobs)
         return torch.stack([e.x[:, :23], e.y[:, :23], e.vx[:, :23], e.vy[:, :23], e.body[:, :23]], dim=2)
 
     def reset(self, mask=None):
         self.engine.reset(mask)
         return self._obs()
 
+    def _step_see(self, actions):
+        agents = 22 if self.opponent is None else 11
+        if actions is None:
+            raise ValueError(f"with obs='see', step() needs actions [N, {agents}, 5]")
+        a = torch.as_tensor(actions, device=self.device).to(torch.float32)
+        if tuple(a.shape) != (self.num_envs, agents, 5):
+            raise ValueError(f"actions must have shape ({self.num_envs}, {agents}, 5), got {tuple(a.shape)}")
+        self._view[:, :agents] = a[..., 3:]
+        return a[..., :3].contiguous()
+
     def step(self, actions=None):
+        if self.obs_kind == 'see':
+            actions = self._step_see(actions)
         if self.opponent is None:
             a = None if actions is None else torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(1, self.num_envs, 22, 3)
         else:
@@ -402,7 +489,9 @@ class Soccer2DMatchVecEnv:
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,
                 'right_team_score': e.score_right, 'cycle': e.cycle, 'nearest_left': e.nearest_left, 'nearest_right': e.nearest_right}
-        if self.obs_kind == 'agent':
+        if self.obs_kind == 'see':
+            e.vision_step(self._view, done=True)
+        if self.obs_kind in ('agent', 'see'):
             return self._obs(), e.reward_left[:, None] * self._rsign, e.done, info
         return self._ro['obs'][0, :, :23], e.reward_left, e.done, info
 

@@ -32,7 +32,8 @@ extern "C" {
 #define S2D_MATCH_GOALIE_RIGHT 11
 
 /* body commands = the PlayerAction oneof members 1..6 (idl/service.proto:380-411, 1291-1298).  TurnNeck and
- * ChangeView only steer the vision model, which a full-state engine does not have: send S2D_MCMD_NONE. */
+ * ChangeView (:413-419) are no body commands: they steer the opt-in vision layer below ("Vision": s2d_match_vision_step
+ * takes them as a row of their own); in an action row of the body step send S2D_MCMD_NONE. */
 enum { S2D_MCMD_NONE = 0, S2D_MCMD_DASH = 1, S2D_MCMD_TURN = 2, S2D_MCMD_KICK = 3, S2D_MCMD_TACKLE = 4,
        S2D_MCMD_CATCH = 5, S2D_MCMD_MOVE = 6 };
 /* GameModeType values used (idl/service.proto:267-301).  mode_side: for the restarts (KickOff_, KickIn_, FreeKick_, CornerKick_,
@@ -288,8 +289,9 @@ int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float *actions_dev
 int s2d_match_relative(S2DMatchHandle h, float *dist_dev, float *angle_dev, void *stream);
 
 /* Per-agent observations in each team's own frame (the WorldModel / Self / InterceptTable / Player messages every agent reads,
- * idl/service.proto:144-265, 306-349), from the current state.  A full-state observation: no vision model, no see-message
- * quantisation.  One row of S2D_AGENT_OBS_DIM float32 words per agent; integers and flags are stored as their float values.
+ * idl/service.proto:144-265, 306-349), from the current state.  A full-state observation: the view cone, the see-message
+ * quantisation and the see timing are the vision layer's ("Vision" below, s2d_match_see), not this row's.  One row of
+ * S2D_AGENT_OBS_DIM float32 words per agent; integers and flags are stored as their float values.
  *
  * Own frame.  For agent p of side s (left = slots 0..10, right = 11..21), sgn = +1 left, -1 right:
  *   every position and velocity is multiplied by sgn (exact); every body direction b becomes
@@ -389,6 +391,110 @@ int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet *net);
 int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float *actions_dev, const S2DMatchRollout *out,
                           float *actions_out_dev, int32_t *net_index_out_dev, uint32_t obs_mask, float *agent_obs_out_dev,
                           void *stream);
+
+/* Vision: an opt-in layer beside the engine -- view cone, neck, see-message quantisation, see timing.  Restated from the published
+ * behaviour of rcssserver's synchronous see mode; like every 11v11 rule it is this project's own restatement: PARITY TO RCSSSERVER
+ * UNPINNED.  The fp32 words below are the contract (the device equals tests/see_ref.c bit for bit).  The engine handle stores
+ * nothing of it: the three state planes are the caller's, an engine that never calls these functions is byte for byte the engine
+ * without them.  Deviations: the self words are exact (self-localisation from flags and lines is not modelled: they are what
+ * sense_body plus a perfect localiser would give); no landmark flags or lines; no gaussian_see; nothing is heard but the referee
+ * (the game words); synchronous timing only.
+ *
+ * Parameters (ServerParam names; doubles, each rounded to fp32 once; a reciprocal inv(v) is the float of the double 1 / v):
+ *   view_angle[3]       60, 120, 180 degrees for narrow, normal, wide (rcssserver: visible_angle 90 scaled by 2/3, 4/3 and 2 in
+ *                       synchronous mode; the comment at idl/service.proto:12-14 names 60 / 90 / 180)
+ *   see_interval[3]     1, 2, 3 cycles between two see messages (whole numbers)
+ *   visible_distance    3: closer objects outside the cone are felt
+ *   dist_quantize_step 0.1, dist_round 0.1, dist_chg_quantize 0.02, dir_chg_quantize 0.1
+ *   unum_far_length 20, unum_too_far_length 40, team_far_length 40, team_too_far_length 60 (idl/service.proto:1713-1716)
+ *   min / max_neck_moment -+180, min / max_neck_angle -+90 (:1477-1480) */
+typedef struct S2DVisionParams {
+  double view_angle[3], see_interval[3];
+  double visible_distance;
+  double dist_quantize_step, dist_round, dist_chg_quantize, dir_chg_quantize;
+  double unum_far_length, unum_too_far_length, team_far_length, team_too_far_length;
+  double min_neck_moment, max_neck_moment, min_neck_angle, max_neck_angle;
+} S2DVisionParams;
+void s2d_match_vision_default_params(S2DVisionParams *prm);
+/* Errors: non-finite values; view angles outside (0, 360]; intervals < 1 (or not whole, or > 1e6); quantisation steps <= 0; negative
+ * distances; a far length above its too_far length; a minimum above its maximum. */
+int s2d_match_vision_validate(const S2DVisionParams *prm);
+
+/* The vision state: caller-owned device planes [N][24] (slot = player; slots 22, 23 are padding), 4-byte aligned. */
+typedef struct S2DMatchVision {
+  float *neck;          /* neck angle relative to the body, degrees */
+  int32_t *view_width;  /* S2D_VIEW_NARROW / NORMAL / WIDE; any other value reads as normal */
+  int32_t *see_wait;    /* cycles until the next see message; right after a step, see_wait == see_interval[width] says "fresh" */
+} S2DMatchVision;
+enum { S2D_VIEW_KEEP = 0, S2D_VIEW_NARROW = 1, S2D_VIEW_NORMAL = 2, S2D_VIEW_WIDE = 3 };
+/* neck = +0, width = normal, wait = 0 in every slot of the masked matches (mask_dev NULL = all).  A reset state is not fresh: the
+ * first s2d_match_vision_step makes every player see. */
+int s2d_match_vision_reset(S2DMatchHandle h, const S2DMatchVision *vis, const uint8_t *mask_dev, void *stream);
+/* One cycle of the vision state; call it once after each body step.  view_actions_dev: float[N][22][2] = (TurnNeck moment,
+ * ChangeView code) per player, or NULL = nobody turns or changes.  Codes: S2D_VIEW_*; any other value (NaN included) keeps the width.
+ * done_dev: uint8[N] or NULL.  For player l of match e:
+ *   1. done_dev[e] != 0: neck = +0, width = normal, wait = 0 (the match has just restarted; the actions are not read).
+ *   2. otherwise a sent-off player (card == S2D_CARD_RED) keeps all three words and nothing below happens to him.
+ *   3. otherwise, with actions: m = moment is NaN ? 0 : clamp(moment, min_neck_moment, max_neck_moment);
+ *      neck = clamp(norm_deg_any(neck + m), min_neck_angle, max_neck_angle)   (clamp(v, lo, hi) = v < lo ? lo : v > hi ? hi : v);
+ *      with a code 1..3: width = code and wait = min(wait, see_interval[code]) -- a pending wait never exceeds the new width's
+ *      interval, so switching to a narrower view shortens the wait and "fresh" below stays unambiguous.
+ *   4. the timer (cases 1 and 3): wait = max(wait - 1, 0); fresh = (wait == 0); if fresh: wait = see_interval[width].
+ * fresh is not stored: after the step it is see_wait == see_interval[width].  What a ChangeView does, with the default intervals:
+ *   - to a width whose interval is not below the pending wait (any change to a wider view, for one): the running timer goes on;
+ *     the new cone is first used at its next expiry, the new interval from then on.
+ *   - to a narrower width with a longer wait pending: the wait is cut in the same step, so the next see message comes EARLIER than
+ *     the running timer would have sent it.  To narrow (interval 1) that is this very cycle: wait = min(wait, 1) = 1, the timer
+ *     takes it to 0, the player is fresh in the step of the ChangeView and in every cycle after it.  Wide (wait 3) -> normal gives
+ *     wait 2 -> 1: fresh in the next cycle, one cycle before the wide timer would have expired.  Without the cut that step would
+ *     leave wait == 2 == see_interval[normal], which reads as fresh although no see message is due.
+ * Reads the card plane of the engine; writes the three planes only. */
+int s2d_match_vision_step(S2DMatchHandle h, const S2DVisionParams *prm, const S2DMatchVision *vis, const float *view_actions_dev,
+                          const uint8_t *done_dev, void *stream);
+
+/* The see row of agent p: S2D_SEE_DIM float32 words in p's team's own frame, exactly as in the agent rows above (positions and
+ * velocities times sgn, bodies turned by 180 degrees for the right team, all arithmetic on own-frame values: a mirrored state gives
+ * the mirrored agent bitwise the same row when no distance lies inside a probabilistic band).  Integers and flags are stored as
+ * their float values.
+ *   self [0, 16)     x, y, vx, vy, body, neck, face, view width code (1..3), fresh (0 / 1), see_wait, stamina, effort, recovery,
+ *                    stamina_capacity, is_goalie, card.                   face = norm_deg_any(body + neck)
+ *   ball [16, 24)    level, dist, dir, dist_chg, dir_chg | game_mode_type, mode side (side word), cycle (the referee is heard)
+ *   players [24, 192)  21 rows of 8 words: level, team (+1 ours, -1 theirs, 0 unknown), unum (0 unknown), dist, dir, dist_chg,
+ *                    dir_chg, body_rel
+ * The self words and the three game words are always delivered.  When the cycle is not fresh for p, or p is sent off, the five ball
+ * words and all player rows are +0.  Otherwise, for every other ACTIVE object j (card < S2D_CARD_RED; the ball is always active), in
+ * this order of fp32 operations (quant(v, q) = rintf(v * inv(q)) * q):
+ *   dx = x_j - x_p, dy = y_j - y_p;  d = hypot2(dx, dy)
+ *   rel = d == 0 ? 0 : norm_deg_any(atan2_deg(dy, dx) - face)
+ *   in_cone = fabsf(rel) <= 0.5f * view_angle[width];   felt = d <= visible_distance
+ *   level = in_cone ? (ball: 4; player: by distance, below) : felt ? 1 : 0
+ *   level >= 1:  dist = d == 0 ? 0 : quant(exp_spec(quant(log_spec(d), dist_quantize_step)), dist_round);  dir = rintf(rel)
+ *   level == 4, d != 0:  ex = dx / d, ey = dy / d, rvx = vx_j - vx_p, rvy = vy_j - vy_p
+ *                dist_chg = dist * quant(fmaf(rvx, ex, rvy * ey) / d, dist_chg_quantize)
+ *                dir_chg = quant((fmaf(rvy, ex, -(rvx * ey)) / d) * 57.29577951308232f, dir_chg_quantize)
+ *   level == 4, players:  body_rel = rintf(norm_deg_any(body_j - face))
+ *   every word a level does not carry is +0: level 1 (felt, outside the cone) and level 2 carry dist and dir only, level 3 adds the
+ *   team word, level 4 the unum, the two changes and body_rel.  (A quantised word may be -0.)
+ * A player in the cone:  d <= unum_far_length: 4;  else if d < unum_too_far_length and u1 >= (d - unum_far_length) *
+ * inv(unum_too_far_length - unum_far_length): 4;  else if d <= team_far_length: 3;  else if d < team_too_far_length and
+ * u2 >= (d - team_far_length) * inv(team_too_far_length - team_far_length): 3;  else 2.   u1, u2 = (w.x >> 8) * 2^-24,
+ * (w.y >> 8) * 2^-24 of the Philox block with counter = the match's tick, stream S2D_MATCH_ST_SEE, block = p * 24 + j, the random
+ * policy's keys: the row is a pure function of state, vision state and tick.
+ * Order of the player rows: the seen ones (level >= 1) first, ascending by (dir, dist, slot) -- left to right across the view --
+ * then the others, all +0.  The slot is the own-frame one (p's team 0..10, the other team 11..21: the raw slot for the left
+ * team, (slot + 11) % 22 for the right team), so that mirrored states order alike; as the last tie-break it is a named, negligible
+ * identity leak. */
+#define S2D_SEE_DIM 192            /* float32 words per agent: 768 B, 12 lines of 64 B */
+#define S2D_SEE_SELF 0
+#define S2D_SEE_BALL 16
+#define S2D_SEE_PLAYERS 24
+#define S2D_SEE_ROW_WORDS 8        /* words of one player row */
+#define S2D_MATCH_ST_SEE 8         /* Philox stream id of the identity draws (streams 0..7 belong to the engine) */
+/* see_dev: float[N][popcount(slot_mask)][S2D_SEE_DIM], rows in ascending slot order, 16-byte aligned; slot_mask as for
+ * s2d_match_agent_obs.  Reads the current state and the vision planes; writes nothing else.
+ * Errors: a mask with bits above 21, an empty mask, a NULL or unaligned see_dev, invalid parameters, NULL or unaligned planes. */
+int s2d_match_see(S2DMatchHandle h, const S2DVisionParams *prm, const S2DMatchVision *vis, uint32_t slot_mask, float *see_dev,
+                  void *stream);
 
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
