@@ -31,6 +31,7 @@
 
 #include "s2d_device.h"
 #include "s2d_net.h"
+#include "s2d_see_row.h"
 #include "../../include/s2d_match.h"
 
 #define S2D_API extern "C" __attribute__((visibility("default")))
@@ -139,6 +140,8 @@ template <class B> struct MParamsCtl : B {};   // the general parameter block as
 static_assert(sizeof(MParamsCtl<MParamsNoIll>) == sizeof(MParams), "MParamsCtl adds no data");
 template <class B> struct MParamsNet : B {};   // ... and as the network kernels read it
 static_assert(sizeof(MParamsNet<MParamsNoIll>) == sizeof(MParams), "MParamsNet adds no data");
+template <class B> struct MParamsSee : B {};   // ... and as the see-network kernels read it
+static_assert(sizeof(MParamsSee<MParamsNoIll>) == sizeof(MParams), "MParamsSee adds no data");
 // The same physics and rules with the SCHEDULE of the match -- how long things last, how many there are of them -- as per-engine
 // words: a learner's engine with short halves, no extra time or other waits differs from the stock configuration in these words
 // only and would otherwise run the general instantiation (1.79 G against 2.00 G, profiles/r04/match_schedule_words.txt).  They sit in
@@ -1581,6 +1584,111 @@ S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGa
   return greedy;
 }
 
+// ------------------------------------------------------------------------------------------
+// see network (s2d_match_set_see_network, include/s2d_match.h): the Q-network on each slot's SEE row, the vision state stepped here
+// ------------------------------------------------------------------------------------------
+// The scheme of the network slots above with the 192-word see row in the place of the agent row: 8 agents per match per tile,
+// zeroed pad rows, the three layers on f32 MFMA (layer 1: 48 k-steps), hidden and Q images at pitch 68.  The row is s2d_see_row.h's
+// see_row(), the function s2d_match_see_kernel runs.  Neck, view width and see wait of the lane's player live in registers across
+// the launch's cycles (like MObj); each cycle they go into the half-wave's facts for the row builder.
+constexpr int kSeeK1 = S2D_SEE_DIM / 4;                // 48 k-steps of layer 1
+constexpr int kSeeRowPitch = S2D_SEE_DIM + 4;          // LDS pitch of a row (196: 16-byte aligned, the 16 rows of a B fragment hit 64 banks)
+struct MSee {
+  uint32_t net_mask, row_mask, obs_mask;   // network slots; slots whose rows are built (net | obs); slots recorded in see_out
+  int h1, h2, na, na16;
+  const float* frags;                      // the engine's fragment-order copy: W1 (read from memory), then W2 | W3 | b1 | b2 | b3
+  int shared_words;                        // words of W2 .. b3 (staged into LDS)
+  const float* epsilon;                    // device float, read once per launch
+  const float* table;                      // device float[na][5]: command, a, b, TurnNeck moment, ChangeView code
+  int32_t* net_index;                      // [T][N][22] or NULL
+  float* see_out;                          // [T][N][popcount(obs_mask)][192] or NULL
+  const float* view_actions;               // [T][N][22][2] or NULL: the view actions of the slots without the network
+};
+struct MSeeArg { MSee net; s2d_see::SeeParams sp; S2DMatchVision vis; };   // kernel argument of the SEE instantiations (with their MCtl)
+constexpr int kSeeWaveWords = 16 * kSeeRowPitch + 16 * kNetHidPitch + 2 * (int)(sizeof(s2d_see::SeeFacts) / 4) + kNetMaxRows;
+static_assert((2 * sizeof(s2d_see::SeeFacts)) % 16 == 0 && (16 * kSeeRowPitch + 16 * kNetHidPitch) % 4 == 0 && kSeeRowPitch % 4 == 0,
+              "16-byte aligned LDS parts");
+static_assert(16 * kSeeRowPitch >= 16 * kNetHidPitch, "layer 2's image fits where the rows were");
+
+// the block-shared part of the network into LDS (every thread of the block; the kernel's barrier follows)
+S2D_DEV void m_see_stage(const MSee& net) {
+  const float4* src = reinterpret_cast<const float4*>(net.frags + net.h1 / 16 * kSeeK1 * 64);
+  float4* dst = reinterpret_cast<float4*>(m_net_lds());
+  for (int i = threadIdx.x; i < net.shared_words / 4; i += kMBlock) dst[i] = src[i];
+}
+
+// One cycle's see-network step of the wave, from the start-of-cycle state (o, g), the lane's vision words and the match's tick: the
+// see rows, their record, the forward pass and the argmax.  Returns the greedy index of this lane's slot (meaningful for network
+// slots).  All 64 lanes, uniform control flow.
+S2D_DEV int m_see_greedy(const MSeeArg& sa, const MObj& o, const MGame& g, float vneck, int vwidth, int vwait, int l, int half,
+                         bool valid, uint64_t gid, int64_t rec_row) {
+  const MSee& net = sa.net;
+  const int lane = threadIdx.x & 63, gq = lane >> 4, c = lane & 15;
+  float* const shared = m_net_lds();
+  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * kSeeWaveWords;
+  float* const hid = tile + 16 * kSeeRowPitch;
+  s2d_see::SeeFacts* const facts = reinterpret_cast<s2d_see::SeeFacts*>(hid + 16 * kNetHidPitch);
+  int* const gidx = reinterpret_cast<int*>(facts + 2);
+  s2d_see::SeeIn in{};
+  if (l <= BALL) { in.x = o.x; in.y = o.y; in.vx = o.vx; in.vy = o.vy; }
+  if (l < NP) {
+    in.body = o.body; in.stamina = o.stamina; in.effort = o.effort; in.recovery = o.recovery; in.capacity = o.capacity;
+    in.card = o.card; in.neck = vneck; in.width = vwidth; in.wait = vwait;
+  }
+  in.mode = g.mode; in.mode_side = g.mode_side; in.cycle = g.cycle; in.tick = (uint32_t)g.tick;
+  s2d_see::SeeFacts& fs = facts[half];
+  s2d_see::see_facts(fs, in, l);                         // (ends with a wave fence)
+  const int nrows = __builtin_popcount(net.row_mask), nobs = __builtin_popcount(net.obs_mask);
+  const float* const w2 = shared;
+  const float* const w3 = w2 + (net.h2 / 16) * (net.h1 / 4) * 64;
+  const float* const b1 = w3 + (net.na16 / 16) * (net.h2 / 4) * 64;
+  const float* const b2 = b1 + net.h1;
+  const float* const b3 = b2 + net.h2;
+  uint32_t rest = net.row_mask;
+  for (int nt = 0; 8 * nt < nrows; ++nt) {
+    const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
+    for (int i = lane; i < (16 - 2 * rn) * (kSeeRowPitch / 4); i += 64)   // pad rows of the last tile
+      reinterpret_cast<float4*>(tile + 2 * rn * kSeeRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int j = 0; j < rn; ++j) {
+      const int pa = __builtin_ctz(rest);              // the agent (uniform: the mask is a kernel argument)
+      rest &= rest - 1u;
+      float4* const row = reinterpret_cast<float4*>(tile + (2 * j + half) * kSeeRowPitch);
+      s2d_see::see_row(sa.sp, fs, in, l, half, pa, gid, row);   // (ends with a wave fence: the row is whole)
+      if (net.see_out && ((net.obs_mask >> pa) & 1u)) {
+        const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
+        if (valid) s2d_see::see_row_store(net.see_out + (rec_row * nobs + k) * S2D_SEE_DIM, row, l);
+      }
+    }
+    wave_fence();
+    if (net.net_mask != 0u) {
+      const float* const x = tile + c * kSeeRowPitch;
+      layer_tile<true, 4>(net.frags, b1, net.h1 / 16, kSeeK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
+      wave_fence();
+      layer_tile<true, 4>(w2, b2, net.h2 / 16, net.h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile,
+                          kNetHidPitch, lane);
+      wave_fence();
+      layer_tile<false, 4>(w3, b3, net.na16 / 16, net.h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid,
+                           kNetHidPitch, lane);
+      wave_fence();
+      if (lane < 16) {   // best = 0; for a = 1 .. K-1: if (q[a] > q[best]) best = a  (ties: lowest index; a NaN never replaces the best)
+        const float* q = hid + lane * kNetHidPitch;
+        int best = 0;
+        float bv = q[0];
+        for (int a = 1; a < net.na; ++a) {
+          const float v = q[a];
+          if (v > bv) { bv = v; best = a; }
+        }
+        gidx[16 * nt + lane] = best;
+      }
+      wave_fence();
+    }
+  }
+  int greedy = 0;
+  if (l < NP && ((net.net_mask >> l) & 1u)) greedy = gidx[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+  wave_fence();
+  return greedy;
+}
+
 struct MRoll { float* obs; float* reward; int32_t* mode; uint8_t* done; };
 
 // n_steps cycles; actions = [T][N][22][3] or NULL (random policy).  n_steps = 1 with ro = {} is the per-step API.
@@ -1590,9 +1698,12 @@ struct MShared {                                      // the workgroup's LDS (de
 // CTL: the slots' controllers come from `ctl` (per-slot: caller's row, random, scripted) and the record of what they chose is written
 // when ctl.actions_out is set; otherwise every slot takes the caller's row, or the random policy when actions == NULL.
 // NET (with CTL): the network slots of `nin` override the table: the action of the caller's network on the slot's agent row.
-template <bool CTL, bool NET = false, class P, class TY>
+// NA = MSeeArg (with NET): the see network -- the network acts on the slot's see row and chooses the view action too; the vision
+// state of all 22 players is stepped here, once per cycle, after the body cycle.
+template <bool CTL, bool NET = false, class P, class TY, class NA = MNetArg>
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
-                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const MNetArg* nin = nullptr) {
+                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr) {
+  constexpr bool SEE = NET && std::is_same<NA, MSeeArg>::value;
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
@@ -1601,6 +1712,13 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   MObj o; MGame g;
   MRare& r = sh.rare[threadIdx.x / kHalf];
   m_load(q, ec, l, o, g, r);
+  float vneck = 0.0f; int vwidth = 0, vwait = 0;          // SEE: the vision state of this lane's player, in registers for the launch
+  if constexpr (SEE) {
+    if (l < NP) {
+      const int64_t k = ec * SLOTS + l;
+      vneck = nin->vis.neck[k]; vwidth = nin->vis.view_width[k]; vwait = nin->vis.see_wait[k];
+    }
+  }
   m_derive(p, g);
   tile_init(sh.pos_tile[threadIdx.x / kHalf], l, pt[PT_SIZE][l]);
   const uint64_t gid = (((uint64_t)p.gid_hi << 32) | p.gid_lo) + (uint64_t)ec;
@@ -1650,12 +1768,16 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
     int l = l_launch, half = half_launch;
     asm volatile("" : "+v"(l), "+v"(half));
     int cmd = S2D_MCMD_NONE; float a = 0.0f, b = 0.0f;
+    float view_m = 0.0f, view_c = 0.0f;                    // SEE: this slot's view action (TurnNeck moment, ChangeView code) ...
+    bool view_act = false;                                 // ... and whether it has one
     if constexpr (CTL) {
       int scmd = S2D_MCMD_NONE; float sa = 0.0f, sb = 0.0f;
       if (ctl.script_mask != 0u) m_scripted_action(p, pt, o, g, r, l, half, scmd, sa, sb);   // (uniform: a kernel argument)
       int nidx = -1;                                       // NET: the network's index of this slot, -1 = not a network slot
       if constexpr (NET) {
-        const int greedy = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec);
+        int greedy;
+        if constexpr (SEE) greedy = m_see_greedy(*nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec);
+        else greedy = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec);
         if (l < NP && ((nin->net.net_mask >> l) & 1u)) {   // explore: word x < thr, then the index is word y's draw below K
           const U4 w = m_draw(p, gl, gh, (uint32_t)g.tick, S2D_ST_NET, (uint32_t)l);
           nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, (uint32_t)nin->net.na) : greedy;
@@ -1665,8 +1787,13 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       if (l < NP) {
         const uint32_t bit = 1u << l;
         if (NET && nidx >= 0) {
-          const float* tr = nin->net.table + 3 * nidx;
-          cmd = (int)tr[0]; a = tr[1]; b = tr[2];
+          if constexpr (SEE) {
+            const float* tr = nin->net.table + 5 * nidx;
+            cmd = (int)tr[0]; a = tr[1]; b = tr[2]; view_m = tr[3]; view_c = tr[4]; view_act = true;
+          } else {
+            const float* tr = nin->net.table + 3 * nidx;
+            cmd = (int)tr[0]; a = tr[1]; b = tr[2];
+          }
         } else if (ctl.script_mask & bit) {
           cmd = scmd; a = sa; b = sb;
         } else if (ctl.random_mask & bit) {
@@ -1674,6 +1801,12 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
         } else {
           const float* ap = actions + (((int64_t)t * n + ec) * NP + l) * 3;
           cmd = (int)ap[0]; a = ap[1]; b = ap[2];
+        }
+        if constexpr (SEE) {
+          if (nidx < 0 && nin->net.view_actions) {         // (the pointer: wave-uniform)
+            const float* vp = nin->net.view_actions + (((int64_t)t * n + ec) * NP + l) * 2;
+            view_m = vp[0]; view_c = vp[1]; view_act = true;
+          }
         }
       }
       if (ctl.actions_out) {                               // wave-uniform
@@ -1692,6 +1825,9 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       }
     }
     match_cycle(p, pt, o, g, r, l, half, gl, gh, cmd, a, b, cnt, sh.pos_tile[threadIdx.x / kHalf]);
+    if constexpr (SEE) {                                   // the vision step: this cycle's done, the card after the body cycle
+      if (l < NP) s2d_see::vision_advance(nin->sp, vneck, vwidth, vwait, g.done != 0, o.card >= S2D_CARD_RED, view_act, view_m, view_c);
+    }
     if (ro.obs) {                                          // wave-uniform
       if (l < SLOTS) { obs_slot[0] = o.x; obs_slot[1] = o.y; obs_slot[2] = o.vx; obs_slot[3] = o.vy; obs_slot[4] = o.body; }
       wave_fence();
@@ -1708,6 +1844,12 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   }
   match_nearest(o, g, l);
   if (valid) m_store(q, e, l, o, g, r);
+  if constexpr (SEE) {
+    if (valid && l < NP) {
+      const int64_t k = e * SLOTS + l;
+      nin->vis.neck[k] = vneck; nin->vis.view_width[k] = vwidth; nin->vis.see_wait[k] = vwait;
+    }
+  }
   {                                                     // tackles: per-lane counters -> wave sum -> LDS
     unsigned int tk = valid ? cnt.tackles : 0u;
 #pragma unroll
@@ -1725,18 +1867,26 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // CTL: per-slot controllers (MCtl, the one extra argument: the instantiations without it keep their argument list and code).
 // NET (with CTL): network slots (MNetArg, a second extra argument), the network's LDS in dynamic shared memory; one workgroup per CU
 // holds it, so these instantiations have the register file of one wave per SIMD.
+// SEE: the NET instantiations whose second extra argument is an MSeeArg -- the see network, a family of its own (the existing
+// instantiations keep their template and kernel arguments).
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
+S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeeArg&) { return c; }
+S2D_DEV const MNetArg* m_net_arg() { return nullptr; }
+S2D_DEV const MNetArg* m_net_arg(const MCtl&) { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
+S2D_DEV const MSeeArg* m_net_arg(const MCtl&, const MSeeArg& a) { return &a; }
+template <class... A> struct MIsSee : std::false_type {};
+template <> struct MIsSee<MCtl, MSeeArg> : std::true_type {};
 template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, bool NET = false, class... CtlArg>
 __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
                                                                      const float* __restrict__ actions, MRoll ro, CtlArg... ctl_arg) {
   static_assert(sizeof...(CtlArg) == (NET ? 2 : CTL ? 1 : 0), "the CTL instantiations take an MCtl, NET ones an MNetArg too, the others nothing more");
   static_assert(!NET || CTL, "network slots come with the controller table");
+  constexpr bool SEE = MIsSee<CtlArg...>::value;
   const MCtl ctl = m_ctl_arg(ctl_arg...);
-  const MNetArg* nin = nullptr;
-  if constexpr (NET) nin = m_net_arg(ctl_arg...);
+  const auto* const nin = m_net_arg(ctl_arg...);
   __shared__ float4 pos_tile[kEnvsPerBlock][kTileSlots];
   __shared__ PTab pt[PT_WORDS];                       // per-slot PlayerType parameters, shared by the 8 matches
   __shared__ unsigned int lds_cnt[8];
@@ -1750,7 +1900,8 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
   if constexpr (!STOCK_TYPES)
     for (int k = threadIdx.x; k < PT_WORDS * kHalf; k += kMBlock) (&pt[0][0])[k] = q.ptab[k];
   if (threadIdx.x < 8) lds_cnt[threadIdx.x] = 0u;
-  if constexpr (NET) m_net_stage(nin->net);              // (the barrier of every branch below covers it)
+  if constexpr (SEE) m_see_stage(nin->net);              // (the barrier of every branch below covers it)
+  else if constexpr (NET) m_net_stage(nin->net);
   static_assert(!SCHED || (STOCK && STOCK_TYPES), "the engine's own schedule comes with constant rules and types");
   if constexpr (SCHED) {
     __syncthreads();
@@ -1775,9 +1926,10 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
     static_assert(!ILL || !STOCK, "the stock configurations have the rule off");
     // The CTL kernels read the block through a type of their own (no data added): every helper templated on it is then an
     // instantiation of theirs.  Helpers shared with the CTL kernels were optimised differently in the kernels without them.
-    // The NET kernels likewise (sharing the CTL kernels' type changed those kernels' code).
+    // The NET kernels likewise (sharing the CTL kernels' type changed those kernels' code), and the SEE kernels.
     using PBase = std::conditional_t<ILL, MParams, MParamsNoIll>;
-    using PBlock = std::conditional_t<NET, MParamsNet<PBase>, std::conditional_t<CTL, MParamsCtl<PBase>, PBase>>;
+    using PBlock = std::conditional_t<SEE, MParamsSee<PBase>,
+                                      std::conditional_t<NET, MParamsNet<PBase>, std::conditional_t<CTL, MParamsCtl<PBase>, PBase>>>;
     __shared__ PBlock p_lds;
     static_assert(sizeof(MParams) / 4 <= kMBlock, "one thread per parameter word");
     if (threadIdx.x < sizeof(MParams) / 4)
@@ -1867,6 +2019,8 @@ struct S2DMatchEngine {
   bool has_net = false;                                // s2d_match_set_network installed a network: launches use the NET kernels
   S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time)
   float* net_frags = nullptr;                          // the fragment-order copy the pack kernel writes (kNetFragsMax words)
+  bool has_see = false;                                // s2d_match_set_see_network installed a see network: launches use the SEE kernels
+  S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
   char* arena; size_t arena_bytes; bool owns_arena;
@@ -2301,7 +2455,7 @@ static constexpr size_t kNetLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all o
 static constexpr int kNetMaxDevices = 64;
 static bool m_net_allow_lds(const void* fn, int slot, size_t dyn) {
   static std::mutex mu;
-  static size_t limit[kNetMaxDevices][5] = {};
+  static size_t limit[kNetMaxDevices][10] = {};        // slots 0..4: the NET instantiations, 5..9: the SEE ones
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kNetMaxDevices) return false;
   std::lock_guard<std::mutex> lock(mu);
@@ -2314,9 +2468,10 @@ static bool m_net_allow_lds(const void* fn, int slot, size_t dyn) {
   }
   return dyn <= limit[dev][slot];
 }
-template <class K> static int m_net_launch(K kernel, int slot, size_t dyn, dim3 grid, dim3 block, hipStream_t st, const MParams& mp,
-                                           const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
-                                           const MCtl& ctl, const MNetArg& na) {
+template <class K, class NA> static int m_net_launch(K kernel, int slot, size_t dyn, dim3 grid, dim3 block, hipStream_t st, const MParams& mp,
+                                                     const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
+                                                     const MCtl& ctl, const NA& na) {
+  if (std::is_same<NA, MSeeArg>::value) slot += 5;
   if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn))
     return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
   hipLaunchKernelGGL(kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
@@ -2330,8 +2485,9 @@ static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const
   MDeviceGuard guard(h->device);
   const dim3 grid(m_grid(h->n)), block(kMBlock);
   if constexpr (NET) {
-    const MNetArg& na = std::get<1>(std::tie(extra...));
-    const size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * kNetWaveWords) * sizeof(float);
+    const auto& na = std::get<1>(std::tie(extra...));    // an MNetArg, or the see network's MSeeArg
+    constexpr int wave_words = std::is_same<std::decay_t<decltype(na)>, MSeeArg>::value ? kSeeWaveWords : kNetWaveWords;
+    const size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
     int rc;
     if (h->stock_sched)
       rc = m_net_launch(s2d_match_rollout_kernel<true, true, true, false, true, true, X...>, 0, dyn, grid, block, st, h->mp, h->ptrs,
@@ -2368,21 +2524,23 @@ static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const
   return S2D_OK;
 }
 
-// The caller's parameters (torch order: W1 [h1][224], b1, W2 [h2][h1], b2, W3 [na][h2], b3) into the engine's fragment-order copy:
-// W1's fragments [h1/16][56][64], W2's [h2/16][h1/4][64], W3's [na16/16][h2/4][64] (rows past na zero), b1 | b2 | b3 (zero past na).
+// The caller's parameters (torch order: W1 [h1][in_dim], b1, W2 [h2][h1], b2, W3 [na][h2], b3; in_dim = 224 for the agent-row
+// network, 192 for the see network) into the engine's fragment-order copy:
+// W1's fragments [h1/16][in_dim/4][64], W2's [h2/16][h1/4][64], W3's [na16/16][h2/4][64] (rows past na zero), b1 | b2 | b3 (zero past na).
 // Enqueued by every network launch, so that a captured graph repacks what the parameter buffer holds at replay.
-__global__ __launch_bounds__(256) void s2d_match_net_pack_kernel(const float* __restrict__ params, int h1, int h2, int na, int na16,
-                                                                 float* __restrict__ frags, int total) {
+__global__ __launch_bounds__(256) void s2d_match_net_pack_kernel(const float* __restrict__ params, int in_dim, int h1, int h2, int na,
+                                                                 int na16, float* __restrict__ frags, int total) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
-  const int f1 = h1 / 16 * kNetK1, f2 = h2 / 16 * (h1 / 4), f3 = na16 / 16 * (h2 / 4);
-  const int o_b1 = S2D_AGENT_OBS_DIM * h1, o_w2 = o_b1 + h1, o_b2 = o_w2 + h2 * h1, o_w3 = o_b2 + h2, o_b3 = o_w3 + na * h2;
+  const int k1 = in_dim / 4;
+  const int f1 = h1 / 16 * k1, f2 = h2 / 16 * (h1 / 4), f3 = na16 / 16 * (h2 / 4);
+  const int o_b1 = in_dim * h1, o_w2 = o_b1 + h1, o_b2 = o_w2 + h2 * h1, o_w3 = o_b2 + h2, o_b3 = o_w3 + na * h2;
   float v = 0.0f;
   if (idx < (f1 + f2 + f3) * 64) {
     const int f = idx / 64, l = idx & 63, row = l & 15, kk = l >> 4;
     if (f < f1) {
-      const int jt = f / kNetK1, s = f - kNetK1 * jt;
-      v = params[(16 * jt + row) * S2D_AGENT_OBS_DIM + 4 * s + kk];
+      const int jt = f / k1, s = f - k1 * jt;
+      v = params[(16 * jt + row) * in_dim + 4 * s + kk];
     } else if (f < f1 + f2) {
       const int g2 = f - f1, ks = h1 / 4, jt = g2 / ks, s = g2 - jt * ks;
       v = params[o_w2 + (16 * jt + row) * h1 + 4 * s + kk];
@@ -2399,21 +2557,44 @@ __global__ __launch_bounds__(256) void s2d_match_net_pack_kernel(const float* __
   frags[idx] = v;
 }
 static constexpr int kNetFragsMax = (64 / 16 * kNetK1 + 64 / 16 * (64 / 4) + 64 / 16 * (64 / 4)) * 64 + 64 + 64 + 64;
+static_assert(kSeeK1 <= kNetK1, "the see network's copy fits the agent-row network's");
 
 // actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL).
 // With a network set, or a row record asked for (obs_mask), the NET instantiation runs (after the pack kernel, when there is a network).
+// With a see network set the SEE instantiation runs (agent_obs_out is then the see record, view_actions the other slots' view actions).
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
                     float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
-                    float* agent_obs_out = nullptr) {
+                    float* agent_obs_out = nullptr, const float* view_actions = nullptr) {
   MRoll ro{nullptr, nullptr, nullptr, nullptr};
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr uint32_t kAll = (1u << NP) - 1u;
-  const uint32_t net_mask = h->has_net ? h->net.slot_mask : 0u;
+  const uint32_t net_mask = h->has_see ? h->see.slot_mask : h->has_net ? h->net.slot_mask : 0u;
   if (!agent_obs_out) obs_mask = 0u;
   if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
     return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
   const MCtl ctl = h->has_ctl ? MCtl{h->ctl_random, h->ctl_script, actions_out} : MCtl{actions ? 0u : kAll, 0u, actions_out};
+  if (h->has_see) {
+    MSeeArg sa;
+    std::memset(&sa, 0, sizeof sa);
+    MSee& nt = sa.net;
+    nt.net_mask = net_mask; nt.obs_mask = obs_mask; nt.row_mask = net_mask | obs_mask;
+    nt.net_index = net_index_out; nt.see_out = agent_obs_out; nt.view_actions = view_actions;
+    const uint32_t keys[4] = {h->mp.seed_lo, h->mp.seed_hi, h->mp.gid_lo, h->mp.gid_hi};
+    sa.sp = s2d_see::see_params(h->see.prm, keys);
+    sa.vis = h->see.vis;
+    if (net_mask) {
+      nt.h1 = h->see.h1; nt.h2 = h->see.h2; nt.na = h->see.n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
+      nt.frags = h->net_frags; nt.epsilon = h->see.epsilon; nt.table = h->see.table;
+      nt.shared_words = (nt.h2 / 16 * (nt.h1 / 4) + nt.na16 / 16 * (nt.h2 / 4)) * 64 + nt.h1 + nt.h2 + nt.na16;
+      const int total = (nt.h1 / 16 * kSeeK1) * 64 + nt.shared_words;
+      MDeviceGuard guard(h->device);
+      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->see.params, (int)S2D_SEE_DIM, nt.h1,
+                         nt.h2, nt.na, nt.na16, h->net_frags, total);
+      MHIP_TRY(hipGetLastError());
+    }
+    return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, sa);
+  }
   if (net_mask || obs_mask || net_index_out) {
     MNetArg na;
     std::memset(&na, 0, sizeof na);
@@ -2427,8 +2608,8 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       nt.shared_words = (nt.h2 / 16 * (nt.h1 / 4) + nt.na16 / 16 * (nt.h2 / 4)) * 64 + nt.h1 + nt.h2 + nt.na16;
       const int total = (nt.h1 / 16 * kNetK1) * 64 + nt.shared_words;
       MDeviceGuard guard(h->device);
-      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->net.params, nt.h1, nt.h2, nt.na,
-                         nt.na16, h->net_frags, total);
+      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->net.params, (int)S2D_AGENT_OBS_DIM,
+                         nt.h1, nt.h2, nt.na, nt.na16, h->net_frags, total);
       MHIP_TRY(hipGetLastError());
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
@@ -2438,6 +2619,12 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
 }
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
+  if (h->has_see) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, see network>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, see network>" : h->stock ? "s2d_match_rollout_kernel<stock, see network>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, see network>" :
+                                              "s2d_match_rollout_kernel<general, see network>";
+  }
   if (h->has_net) {
     if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, network>";
     return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, network>" : h->stock ? "s2d_match_rollout_kernel<stock, network>" :
@@ -2527,12 +2714,67 @@ S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
     h->net_frags = static_cast<float*>(pmem);
   }
   h->net = *net; h->has_net = true;
+  h->has_see = false; h->see = S2DMatchSeeNet{};       // one network per engine
   return S2D_OK;
+}
+static int m_net_frags_alloc(S2DMatchHandle h) {
+  if (h->net_frags) return S2D_OK;
+  MDeviceGuard guard(h->device);
+  void* pmem = nullptr;
+  if (hipMalloc(&pmem, (size_t)kNetFragsMax * sizeof(float)) != hipSuccess) return mfail(S2D_ENOMEM, "hipMalloc of the network copy failed");
+  h->net_frags = static_cast<float*>(pmem);
+  return S2D_OK;
+}
+S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { h->has_see = false; h->see = S2DMatchSeeNet{}; return S2D_OK; }
+  const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
+  if ((net->slot_mask >> NP) != 0u) return mfail(S2D_EINVAL, "see network slot_mask must be a set of bits 0..21");
+  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "see network hidden widths must be 16, 32, 48 or 64");
+  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "see network n_actions must be in [1, 64]");
+  if (net->slot_mask != 0u) {
+    if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+      return mfail(S2D_EINVAL, "see network params must be a non-NULL, 16-byte aligned device pointer");
+    if (!net->epsilon || !net->table || ((reinterpret_cast<uintptr_t>(net->epsilon) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
+      return mfail(S2D_EINVAL, "see network epsilon and table must be non-NULL, 4-byte aligned device pointers");
+  }
+  if (!net->vis.neck || !net->vis.view_width || !net->vis.see_wait) return mfail(S2D_EINVAL, "NULL vision plane");
+  if ((reinterpret_cast<uintptr_t>(net->vis.neck) | reinterpret_cast<uintptr_t>(net->vis.view_width) |
+       reinterpret_cast<uintptr_t>(net->vis.see_wait)) & 3u)
+    return mfail(S2D_EINVAL, "the vision planes must be 4-byte aligned");
+  if (int rc = s2d_match_vision_validate(&net->prm); rc != S2D_OK) return rc;
+  if (net->slot_mask != 0u)
+    if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  h->see = *net; h->has_see = true;
+  h->has_net = false; h->net = S2DMatchNet{};          // one network per engine
+  return S2D_OK;
+}
+S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
+                                  const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask,
+                                  float* see_out_dev, void* stream) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!h->has_see) return mfail(S2D_EINVAL, "s2d_match_rollout_see needs a see network (s2d_match_set_see_network)");
+  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
+  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
+  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
+  if (view_actions_dev && (reinterpret_cast<uintptr_t>(view_actions_dev) & 3u))
+    return mfail(S2D_EINVAL, "view_actions must be 4-byte aligned (float)");
+  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
+  if (see_out_dev) {
+    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
+      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when see_out is given");
+    if (reinterpret_cast<uintptr_t>(see_out_dev) & 15u) return mfail(S2D_EINVAL, "see_out must be 16-byte aligned");
+  }
+  if (n_steps == 0) return S2D_OK;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, see_out_dev, view_actions_dev);
 }
 S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                   float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask, float* agent_obs_out_dev,
                                   void* stream) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the agent-row record is not built)");
   if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
   if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
   if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))

@@ -152,6 +152,12 @@ class S2DMatchVision(C.Structure):          # the caller-owned vision planes, [N
     _fields_ = [('neck', C.c_void_p), ('view_width', C.c_void_p), ('see_wait', C.c_void_p)]
 
 
+class S2DMatchSeeNet(C.Structure):          # include/s2d_match.h: see network
+    _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
+                ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p),
+                ('prm', S2DVisionParams), ('vis', S2DMatchVision)]
+
+
 MATCH_NET_WIDTHS = (16, 32, 48, 64)
 MATCH_NET_MAX_ACTIONS = 64
 MATCH_ST_NET = 7                           # S2D_MATCH_ST_NET: Philox stream of the network slots' exploration
@@ -186,6 +192,9 @@ MATCH_PROTOTYPES = (
                                         C.c_void_p)),
     ('s2d_match_see', C.c_int, (C.c_void_p, C.POINTER(S2DVisionParams), C.POINTER(S2DMatchVision), C.c_uint32, C.c_void_p,
                                 C.c_void_p)),
+    ('s2d_match_set_see_network', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_see', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
 )
 
 

@@ -253,6 +253,7 @@ def match_param_count(h1, h2, k):
 
 
 MATCH_OBS_DIM = 224                  # S2D_AGENT_OBS_DIM: the 11v11 engine's per-agent row
+MATCH_SEE_DIM = 192                  # S2D_SEE_DIM: its see row (the vision layer)
 MATCH_WIDTHS = (16, 32, 48, 64)
 MATCH_MAX_ACTIONS = 64
 
@@ -263,9 +264,18 @@ class MatchQNetActor:
 
     The network sees one agent's own-frame row (MatchEngine.agent_observations); its index chooses a row of `table`, float32
     [K, 3] = (command, a, b).  params, epsilon and table are device buffers written in place (``sync()``, ``epsilon = ...``,
-    ``set_table()``) and read when the kernel runs, so a captured graph acts with what they hold at replay."""
+    ``set_table()``) and read when the kernel runs, so a captured graph acts with what they hold at replay.
 
-    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05, table=None):
+    obs='see': a 192-H1-H2-K network on the agent's see row (MatchEngine.see: partial observability) with a table float32
+    [K, 5] = (command, a, b, TurnNeck moment, ChangeView code) -- the see network of include/s2d_match.h
+    (s2d_match_set_see_network): the index chooses the body command and the view action."""
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05, table=None, obs='agent'):
+        if obs not in ('agent', 'see'):
+            raise ValueError(f"obs must be 'agent' or 'see', got {obs!r}")
+        self.obs = obs
+        self.in_dim = MATCH_SEE_DIM if obs == 'see' else MATCH_OBS_DIM
+        self.table_width = 5 if obs == 'see' else 3
         for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
             if int(w) not in MATCH_WIDTHS:
                 raise ValueError(f'{name} must be one of {MATCH_WIDTHS}, got {w}')
@@ -275,9 +285,9 @@ class MatchQNetActor:
         self.device = torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        self.params = torch.zeros(match_param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32,
-                                  device=self.device)
-        self.table = torch.zeros((self.n_actions, 3), dtype=torch.float32, device=self.device)
+        count = match_param_count(self.hidden1, self.hidden2, self.n_actions) + (self.in_dim - MATCH_OBS_DIM) * self.hidden1
+        self.params = torch.zeros(count, dtype=torch.float32, device=self.device)
+        self.table = torch.zeros((self.n_actions, self.table_width), dtype=torch.float32, device=self.device)
         self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._eps_value = None
         self.epsilon = epsilon
@@ -286,19 +296,19 @@ class MatchQNetActor:
             self.set_table(table)
 
     @classmethod
-    def from_module(cls, module, table, device=None, epsilon=0.05):
+    def from_module(cls, module, table, device=None, epsilon=0.05, obs='agent'):
         """An actor shaped like `module` (three nn.Linear layers 224 -> H1 -> H2 -> K), loaded from it, with action table
-        `table` [K, 3]."""
+        `table` [K, 3]; obs='see': 192 -> H1 -> H2 -> K and a table [K, 5]."""
         l1, l2, l3 = _linears(module)
         dev = device if device is not None else l1.weight.device
-        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon)
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon, obs=obs)
         actor.load_from(module)
         actor.set_table(table)
         return actor
 
     def shapes(self):
         h1, h2, k = self.hidden1, self.hidden2, self.n_actions
-        return ((h1, MATCH_OBS_DIM), (h1,), (h2, h1), (h2,), (k, h2), (k,))
+        return ((h1, self.in_dim), (h1,), (h2, h1), (h2,), (k, h2), (k,))
 
     def load_from(self, module):
         """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
@@ -325,10 +335,11 @@ class MatchQNetActor:
         return self
 
     def set_table(self, table):
-        """Write the action table (float [K, 3] = command, a, b per index) in place."""
+        """Write the action table (float [K, 3] = command, a, b per index; obs='see': [K, 5], with the TurnNeck moment and the
+        ChangeView code) in place."""
         t = torch.as_tensor(table, dtype=torch.float32)
-        if tuple(t.shape) != (self.n_actions, 3):
-            raise ValueError(f'action table must have shape ({self.n_actions}, 3), got {tuple(t.shape)}')
+        if tuple(t.shape) != (self.n_actions, self.table_width):
+            raise ValueError(f'action table must have shape ({self.n_actions}, {self.table_width}), got {tuple(t.shape)}')
         self.table.copy_(t.to(self.device))
         return self
 
@@ -346,9 +357,16 @@ class MatchQNetActor:
     def epsilon_tensor(self):
         return self._eps
 
-    def c_struct(self, slot_mask):
+    def c_struct(self, slot_mask, vision_params=None, vision=None):
+        """S2DMatchNet; obs='see': S2DMatchSeeNet, which needs the engine's vision parameters and planes."""
         from . import _capi_match as M
-        net = M.S2DMatchNet()
+        if self.obs == 'see':
+            if vision_params is None or vision is None:
+                raise ValueError("a see actor's struct needs the engine's vision parameters and planes (enable_vision)")
+            net = M.S2DMatchSeeNet()
+            net.prm, net.vis = vision_params, vision
+        else:
+            net = M.S2DMatchNet()
         net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
         net.params, net.epsilon, net.table = self.params.data_ptr(), self._eps.data_ptr(), self.table.data_ptr()
         return net

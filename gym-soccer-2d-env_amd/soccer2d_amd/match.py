@@ -133,17 +133,30 @@ class MatchEngine:
         """Network slots: `actor` (a MatchQNetActor) chooses the action of every slot in `slots` ('all' | 'left' | 'right' | a
         mask of bits 0..21) inside the cycle kernel, on the slot's agent row (include/s2d_match.h).  It overrides the controller
         table for those slots; the engine keeps the actor's buffers, so sync() / epsilon / set_table() act at the next launch (or
-        graph replay).  None clears the network."""
+        graph replay).  None clears the network.
+
+        A see actor (MatchQNetActor(obs='see')) is the see network: it acts on the slot's see row, its table also chooses the
+        slot's TurnNeck / ChangeView, and from now on the cycle kernel steps the vision state itself -- do not call vision_step()
+        for cycles it runs.  It needs enable_vision() first.  One network per engine: either kind replaces the other."""
         if actor is None:
             _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, None), 's2d_match_set_network')
+            _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, None), 's2d_match_set_see_network')
             self.network, self.network_mask = None, 0
             return
         mask = M.agent_slot_mask(slots)
         if actor.device != self.device:
             raise ValueError(f"the actor's buffers are on {actor.device}, the engine on {self.device}")
-        net = actor.c_struct(mask)
-        _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
+        if getattr(actor, 'obs', 'agent') == 'see':
+            self._need_vision()
+            net = actor.c_struct(mask, self.vision_params, self.vision)
+            _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
+        else:
+            net = actor.c_struct(mask)
+            _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
         self.network, self.network_mask = actor, mask
+
+    def _see_network_set(self):
+        return self.network is not None and getattr(self.network, 'obs', 'agent') == 'see'
 
     def _actions(self, actions, T=None):
         if actions is None:
@@ -184,11 +197,16 @@ class MatchEngine:
             out['actions'] = torch.empty((T, n, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=dev)
         return out
 
-    def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None):
+    def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None,
+                see_obs=None, view_actions=None):
         """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
         each cycle, before the engine's own gating (caller slots: the caller's row).  net_index: out['net_index'] int32
         [T, N, 22] receives each network slot's index (-1 for the other slots).  agent_obs = 'all' | 'left' | 'right' | a mask:
-        out['agent_obs'] float32 [T, N, k, 224] receives those slots' start-of-cycle agent rows (the learner's obs_t)."""
+        out['agent_obs'] float32 [T, N, k, 224] receives those slots' start-of-cycle agent rows (the learner's obs_t).
+        see_obs = 'all' | 'left' | 'right' | a mask: out['see'] float32 [T, N, k, 192] receives those slots' start-of-cycle see
+        rows, built in the cycle kernel, which then also steps the vision state (s2d_match_rollout_see): with a see network set,
+        beside its slots; without a network, as a record-only see network for this call.  view_actions float32 [T, N, 22, 2] =
+        (TurnNeck moment, ChangeView code) of the slots the see network does not play (None: they neither turn nor change)."""
         T = int(n_steps)
         keep, ptr = self._actions(actions, T)
         if out is None:
@@ -203,6 +221,10 @@ class MatchEngine:
                     raise ValueError(f"rollout buffer {name!r} must be contiguous [T>={T},{self.num_envs},...]")
                 setattr(ro, name, v.data_ptr())
         rec = out.get('actions') if record_actions else None
+        if see_obs is not None or view_actions is not None or (net_index and self._see_network_set()):
+            if agent_obs is not None:
+                raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
+            return self._rollout_see(T, ptr, ro, rec, out, keep, net_index, see_obs, view_actions)
         if net_index or agent_obs is not None:
             return self._rollout_net(T, ptr, ro, rec, out, keep, net_index, agent_obs)
         if rec is not None:
@@ -240,6 +262,51 @@ class MatchEngine:
         _capi.check(self.lib, self.lib.s2d_match_rollout_net(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), mask, vp(obs),
                                                               self._stream()), 's2d_match_rollout_net')
         self._keep = (keep, out)
+        return out
+
+    def _rollout_see(self, T, ptr, ro, rec, out, keep, net_index, see_obs, view_actions):
+        n, dev = self.num_envs, self.device
+        self._need_vision()
+        if rec is not None and (rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or
+                                tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
+            raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{n},22,3]")
+        record_only = not self._see_network_set()
+        if record_only and self.network is not None:
+            raise ValueError("see_obs / view_actions need a see network or no network (the engine has an agent-row network set)")
+        idx = None
+        if net_index:
+            idx = out.get('net_index')
+            if idx is None:
+                idx = out['net_index'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.int32, device=dev)
+            elif idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape[0] < T or tuple(idx.shape[1:]) != (n, M.MATCH_PLAYERS):
+                raise ValueError(f"rollout buffer 'net_index' must be contiguous int32 [T>={T},{n},22]")
+        va = None
+        if view_actions is not None:
+            va = torch.as_tensor(view_actions, device=dev).to(torch.float32).contiguous()
+            if tuple(va.shape) != (T, n, M.MATCH_PLAYERS, 2):
+                raise ValueError(f"view_actions must have shape ({T}, {n}, {M.MATCH_PLAYERS}, 2), got {tuple(va.shape)}")
+        see, mask = None, 0
+        if see_obs is not None:
+            mask = M.agent_slot_mask(see_obs)
+            shape = (n, bin(mask).count('1'), M.SEE_DIM)
+            see = out.get('see')
+            if see is None:
+                see = out['see'] = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
+            elif see.dtype != torch.float32 or not see.is_contiguous() or see.shape[0] < T or tuple(see.shape[1:]) != shape:
+                raise ValueError(f"rollout buffer 'see' must be contiguous float32 [T>={T},{n},{shape[1]},192]")
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        if record_only:                                  # no network: the vision state stepped and recorded in-kernel for this call
+            net = M.S2DMatchSeeNet()
+            net.h1, net.h2, net.n_actions, net.slot_mask = 16, 16, 1, 0
+            net.prm, net.vis = self.vision_params, self.vision
+            _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
+        try:
+            _capi.check(self.lib, self.lib.s2d_match_rollout_see(self._h, T, ptr, vp(va), C.byref(ro), vp(rec), vp(idx), mask, vp(see),
+                                                                  self._stream()), 's2d_match_rollout_see')
+        finally:
+            if record_only:
+                _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, None), 's2d_match_set_see_network')
+        self._keep = (keep, out, va)
         return out
 
     def kernel_name(self):
@@ -293,7 +360,9 @@ class MatchEngine:
         """Switch the vision layer on (include/s2d_match.h, "Vision"): allocates the three state planes -- `neck` float32,
         `view_width` int32, `see_wait` int32, each [N, 24] -- and resets them; from now on reset() resets them with the engine.
         `params`: S2DVisionParams fields over the defaults (view_angle / see_interval: three values, narrow / normal / wide).
-        The engine itself does not change: the body step never reads these planes."""
+        The engine itself does not change: the body step never reads these planes -- unless a see network is set
+        (set_network with a see actor), whose cycle kernel steps them.  The engine then holds these planes' addresses and a copy
+        of the parameters: a second enable_vision() sets the see network again, on the new planes and parameters."""
         self.vision_params = M.vision_params(self.lib, **params)
         shape = (self.num_envs, M.MATCH_SLOTS)
         self.neck = torch.zeros(shape, dtype=torch.float32, device=self.device)
@@ -302,6 +371,8 @@ class MatchEngine:
         self.vision = M.S2DMatchVision(self.neck.data_ptr(), self.view_width.data_ptr(), self.see_wait.data_ptr())
         _capi.check(self.lib, self.lib.s2d_match_vision_reset(self._h, C.byref(self.vision), None, self._stream()),
                     's2d_match_vision_reset')
+        if self._see_network_set():                      # the engine kept the old planes' addresses and the old parameters
+            self.set_network(self.network, self.network_mask)
 
     def _need_vision(self):
         if self.vision is None:
@@ -402,6 +473,9 @@ class Soccer2DMatchVecEnv:
     actions float32 [N, 22 or 11, 5] = (command, a, b, TurnNeck moment, ChangeView code).  A step is the body step, then
     vision_step with the engine's done (a restarted match restarts its vision state), then see.  `vision` = a dict of
     S2DVisionParams fields.  The row returned by reset() is not fresh (self and game words only); the first step's is.
+    With opponent = a see actor (MatchQNetActor(obs='see')) the right team plays on its own see rows and turns its necks and
+    changes its view as the actor's table says; the cycle kernel then steps the vision state of all 22 players itself (the left
+    team's from the caller's TurnNeck / ChangeView words), so a step is one launch plus see.  A see actor needs obs='see'.
     """
 
     @staticmethod
@@ -431,7 +505,14 @@ class Soccer2DMatchVecEnv:
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
         self.opponent, self.obs_kind = opponent, obs
         self._ro = self.engine.alloc_rollout(1)
-        if _is_match_actor(opponent):
+        self._see_opponent = _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'see'
+        if self._see_opponent:
+            if obs != 'see':
+                raise ValueError("a see actor as the opponent needs obs='see'")
+            self.engine.set_controllers({'left': 'external', 'right': 'random'})
+            self.engine.enable_vision(**(vision or {}))
+            self.engine.set_network(opponent, 'right')
+        elif _is_match_actor(opponent):
             # the right team on a frozen network (a past copy of the learner): its slots' controller is the network
             self.engine.set_controllers({'left': 'external', 'right': 'random'})
             self.engine.set_network(opponent, 'right')
@@ -441,7 +522,8 @@ class Soccer2DMatchVecEnv:
             # the caller's half of the action rows; the right team's rows are never read
             self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
         if obs == 'see':
-            self.engine.enable_vision(**(vision or {}))
+            if not self._see_opponent:
+                self.engine.enable_vision(**(vision or {}))
             # the view half of the action rows; an in-kernel opponent's players never turn their necks or change their view
             self._view = torch.zeros((self.num_envs, M.MATCH_PLAYERS, 2), dtype=torch.float32, device=self.device)
         if obs in ('agent', 'see'):
@@ -485,11 +567,14 @@ class Soccer2DMatchVecEnv:
                 raise ValueError(f"actions must have shape ({self.num_envs}, 11, 3) (the left team), got {tuple(a.shape)}")
             self._act[0, :, :11] = a
             a = self._act
-        self.engine.rollout(1, actions=a, out=self._ro)
+        if self._see_opponent:                            # one launch: the body cycle and the vision step of all 22 players
+            self.engine.rollout(1, actions=a, out=self._ro, view_actions=self._view.unsqueeze(0))
+        else:
+            self.engine.rollout(1, actions=a, out=self._ro)
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,
                 'right_team_score': e.score_right, 'cycle': e.cycle, 'nearest_left': e.nearest_left, 'nearest_right': e.nearest_right}
-        if self.obs_kind == 'see':
+        if self.obs_kind == 'see' and not self._see_opponent:
             e.vision_step(self._view, done=True)
         if self.obs_kind in ('agent', 'see'):
             return self._obs(), e.reward_left[:, None] * self._rsign, e.done, info

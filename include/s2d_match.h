@@ -448,7 +448,8 @@ int s2d_match_vision_reset(S2DMatchHandle h, const S2DMatchVision *vis, const ui
  *     takes it to 0, the player is fresh in the step of the ChangeView and in every cycle after it.  Wide (wait 3) -> normal gives
  *     wait 2 -> 1: fresh in the next cycle, one cycle before the wide timer would have expired.  Without the cut that step would
  *     leave wait == 2 == see_interval[normal], which reads as fresh although no see message is due.
- * Reads the card plane of the engine; writes the three planes only. */
+ * Reads the card plane of the engine; writes the three planes only.  While a see network is set ("See network" below) the cycle
+ * kernel runs this step itself, once per cycle: do not call it for those cycles as well. */
 int s2d_match_vision_step(S2DMatchHandle h, const S2DVisionParams *prm, const S2DMatchVision *vis, const float *view_actions_dev,
                           const uint8_t *done_dev, void *stream);
 
@@ -496,10 +497,62 @@ int s2d_match_vision_step(S2DMatchHandle h, const S2DVisionParams *prm, const S2
 int s2d_match_see(S2DMatchHandle h, const S2DVisionParams *prm, const S2DMatchVision *vis, uint32_t slot_mask, float *see_dev,
                   void *stream);
 
+/* See network: the network slots of "Network slots" above under partial observability.  The Q-network acts on each slot's SEE row
+ * (S2D_SEE_DIM words) instead of its full-state agent row, it also chooses the slot's view action (TurnNeck, ChangeView), and the
+ * vision state of all 22 players is stepped inside the cycle kernel: T cycles of self-play under the vision model are one launch.
+ * One network per engine: setting a see network clears an s2d_match_set_network one, and the reverse.  For every cycle of a launch
+ * and every match:
+ *   1. For every slot in slot_mask | obs_mask: x = the slot's see row, built from the START-of-cycle engine state, the current
+ *      vision state and the match's tick: bitwise what s2d_match_see returns at that moment (the two share one device function).
+ *      Slots of obs_mask are recorded (s2d_match_rollout_see), as whole 64-byte lines.
+ *   2. For every slot of slot_mask: steps 2 to 4 of "Network slots" on the 192 words -- params = W1[h1][192], b1[h1], W2[h2][h1],
+ *      b2[h2], W3[K][h2], b3[K]; the same k-ascending fmaf order, the same relu and first-maximum argmax, the same Philox stream
+ *      S2D_MATCH_ST_NET with block = slot, epsilon read when the kernel runs.
+ *   3. (cmd, a, b) = table[index][0..2] (device float[K][5]), then the engine's usual gating and the body cycle.
+ *   4. One vision step per player, exactly as s2d_match_vision_step specifies (the order done / sent-off / action / timer): done =
+ *      this cycle's done of the match; the card is the one after the body cycle; the view action (TurnNeck moment, ChangeView
+ *      code) is table[index][3..4] for a network slot, for any other slot its row of view_actions_dev, or "nobody turns or
+ *      changes" when view_actions_dev is NULL.
+ * One launch of T cycles therefore equals T rounds of s2d_match_see, the host-side choice, s2d_match_rollout_ex for one step and
+ * s2d_match_vision_step with the engine's done.
+ * The vision planes are read once at the start of a launch and written once at its end, for valid matches and slots 0..21 only.
+ * While a see network is set the cycle kernel OWNS the vision step: the caller must not also call s2d_match_vision_step for those
+ * cycles (s2d_match_see and s2d_match_vision_reset between launches are fine).  The engine keeps the pointers (params, epsilon,
+ * table, the three planes), not copies; prm is copied at the call.
+ * slot_mask == 0 is the record-only see network: no forward pass (params, epsilon and table are not read and may be NULL), the
+ * vision state is stepped in the kernel and see rows can be recorded. */
+typedef struct S2DMatchSeeNet {
+  int32_t h1, h2, n_actions;   /* h1, h2 in {16, 32, 48, 64}; 1 <= K <= 64 */
+  uint32_t slot_mask;          /* bits 0..21; 0 = no network: vision stepped and recorded in-kernel only */
+  const float *params;         /* W1[h1][192], b1, W2[h2][h1], b2, W3[K][h2], b3; device, 16-byte aligned */
+  const float *epsilon;        /* device float */
+  const float *table;          /* device float[K][5]: command, a, b, TurnNeck moment, ChangeView code */
+  S2DVisionParams prm;         /* copied at the call */
+  S2DMatchVision vis;          /* the caller's three planes; the engine keeps the pointers */
+} S2DMatchSeeNet;
+/* net == NULL: clears the see network.  Errors (S2D_EINVAL, the engine unchanged): h1 / h2 not in {16, 32, 48, 64}, n_actions outside
+ * [1, 64], bits above 21 in slot_mask; with slot_mask != 0, NULL or unaligned params (16 bytes), epsilon or table (4 bytes); NULL or
+ * unaligned vision planes; parameters s2d_match_vision_validate rejects.  s2d_match_step, s2d_match_rollout and s2d_match_rollout_ex
+ * use the see network when one is set, with no view actions for the other slots; s2d_match_rollout_net then returns S2D_EINVAL (the
+ * agent rows are not built). */
+int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet *net);
+/* s2d_match_rollout_ex with the see network, plus:
+ *   view_actions_dev   float[T][N][22][2] or NULL: (TurnNeck moment, ChangeView code) of the slots outside slot_mask; rows of
+ *                      network slots are never read (nor are their rows of actions_dev);
+ *   net_index_out_dev  int32[T][N][22] or NULL: the index each network slot chose, -1 for the other slots;
+ *   see_out_dev        float[T][N][popcount(obs_mask)][S2D_SEE_DIM] or NULL: the start-of-cycle see rows of the slots in obs_mask,
+ *                      in ascending slot order (the learner's obs_t; 16-byte aligned).
+ * Errors: no see network set; as s2d_match_rollout_ex; unaligned records or view actions; see_out_dev with an empty obs_mask or
+ * bits above 21. */
+int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float *actions_dev, const float *view_actions_dev,
+                          const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev, uint32_t obs_mask,
+                          float *see_out_dev, void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
- * env_id_offset, auto_reset, noise and the PlayerTypes do not matter for the choice. */
+ * env_id_offset, auto_reset, noise and the PlayerTypes do not matter for the choice.  With a controller table, a network or a see
+ * network set the name ends in "controllers>", "network>" or "see network>". */
 const char *s2d_match_kernel_name(S2DMatchHandle h);
 
 #ifdef __cplusplus
