@@ -9,8 +9,15 @@ issues it: ONE LAUNCH of T = 256 fused cycles (--fuse) in the default rollout mo
 mode.  `value` is env-steps (env-cycles) per second in every mode: N envs x cycles / seconds.
 Inputs are resident in HBM before the timed region; nothing is copied to the host inside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--task reach_ball|match]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--task reach_ball|match] [--full]
                   [--mode rollout|step|graph] [--fuse T] [--noise] [--league-exchange] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing else: set-up, settle and warm-up, the timed regions, the dump if one
+is asked for, the result line (metric, value, ms_per_step, the roofline of the same regions, episode counts).  --full adds every
+other measurement to the same line: the cold figure (`secondary.rollout_cold`, taken before the headline), `noise_on`, the
+`secondary` entries (other action modes, T = 64, the per-step API, configs[1] and configs[3]), the league all-gather beside a
+multi-rank metric, and `cpu_baseline` (the CPU oracle and its NumPy restatement on the host cores, ~20 s); --no-secondary and
+--no-cpu-baseline take single parts of that away again.  The headline is measured in the same way with and without --full.
 
 Workload naming (BASELINE.json `configs`): --envs 65536 = configs[2] (default; kwargs of
 dqn_stable_baselines3.py:18-31, uniform random policy drawn in-kernel, reset distribution of
@@ -23,7 +30,7 @@ back: profiles/r04/clock_trajectory.txt), then R = 5 timed regions of EXACTLY
 K steps each (one hipGraph replay per region, bracketed by barrier + synchronize on both sides, max
 over ranks); `value` is the MEDIAN region, the five figures are kept in `repeats`.  The default record
 is written into ROTATING buffers (> 512 MiB in flight, so no line of it can live in the 256 MiB
-Infinity Cache): the headline is the pure-HBM figure; the one-buffer figure is in `secondary`.
+Infinity Cache): the headline is the pure-HBM figure; the one-buffer figure is in `secondary` (--full).
 
 Multi-GPU: one process per GPU, contiguous global env-id ranges, NO data-path collective (envs
 are independent) -> weak scaling; only the timing max is all-reduced.  `python bench.py --gpus N`
@@ -102,9 +109,12 @@ def parse(argv=None):
     ap.add_argument('--league-payload', choices=('record', 'league'), default='record',
                     help='what the league all-gather carries: record = all five arrays (50 B per env-step), league = action, reward, '
                          'done, result (10 B per env-step; observations stay on the rank that trains on them)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need, in the same line: rollout_cold, noise_on, the secondary '
+                         'entries, the league all-gather beside a multi-rank metric, cpu_baseline (off by default)')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary measurements')
     ap.add_argument('--eager', action='store_true', help='issue the timed launches eagerly from Python instead of replaying one hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-sample-steps', type=int, default=0, help='0 = auto (about 10-20 s of CPU work)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed to DIR/<name>.npy (a fixed, seeded sample of envs, '
@@ -727,7 +737,8 @@ def run_reach(args, dev, dist, rank, world):
     n, T = args.envs, max(1, args.fuse)
     stream = torch.cuda.current_stream(dev)
     metric, workload = workload_of('reach_ball', n, world, args.league_exchange)
-    default_line = world == 1 and not args.no_secondary and args.mode == 'rollout' and args.variant == 'dqn' and not args.league_exchange
+    default_shape = world == 1 and not args.no_secondary and args.mode == 'rollout' and args.variant == 'dqn' and not args.league_exchange
+    default_line = args.full and default_shape
     eng = reach_engine(n, dev, rank, args.noise, args.variant)
     snapshot = eng.arena.clone() if args.dump_outputs else None        # the seeded post-reset state (--dump-outputs)
     dumped = None
@@ -735,12 +746,18 @@ def run_reach(args, dev, dist, rank, world):
     nbuf = args.rotate_buffers if args.rotate_buffers > 0 else n_rotating(per_buf)
     K = args.steps
 
-    cold = None
+    cold = placeholder = None
     if default_line:
         # the cold figure: the first GPU work of this process -- 4 warm-up launches, one region of 20, no settle phase
         m = measure_rollout(eng, T, 20, 1, 1, stream, 0.0, warm_regions=0)
         cold = rollout_entry(m, n, T, eng.kernel_name(), None)
         cold['settle_ms'] = 0
+    elif default_shape:
+        # The cold measurement leaves its record buffer allocated (the engine's pointer-block cache holds it), so the headline's
+        # rotating buffers are the allocations that follow it -- and where the record lies in HBM moves the rate of this kernel by
+        # up to a fifth (profiles/r03/alloc_sensitivity_*.txt).  A plain run makes the same allocation without the measurement:
+        # its headline buffers lie where those of a --full run lie.
+        placeholder = eng.alloc_rollout(T)
 
     league = None
     if args.mode == 'rollout' and not args.league_exchange:
@@ -789,7 +806,7 @@ def run_reach(args, dev, dist, rank, world):
         steps_per_launch, alg, traffic_key, n_launches = 1, n * (2 * STATE_BYTES + 4 + RECORD_BYTES - 4), 'step', k_cycles
     if args.dump_outputs and rank == 0:
         write_outputs(args.dump_outputs, *dumped)
-    dumped = snapshot = None
+    dumped = snapshot = placeholder = None
     kernel = eng.kernel_name()
     elapsed = median_of(wall)
     cycles_per_region = K * args.cycles_per_step
@@ -807,7 +824,7 @@ def run_reach(args, dev, dist, rank, world):
             'config': {'workload': workload + ('; noise on (player_rand 0.1, ball_rand 0.05)' if args.noise else '; noise off (SURVEY 8d)'),
                        'envs_per_gpu': n, 'global_envs': world * n, 'mode': args.mode, 'variant': args.variant,
                        'cycles_per_launch': steps_per_launch if args.mode != 'graph' else f'1 ({T} per graph replay)',
-                       'settle_ms': args.settle_ms, 'rollout_buffers': nbuf,
+                       'settle_ms': args.settle_ms, 'rollout_buffers': nbuf, 'full': bool(args.full),
                        'record_bytes_in_flight': nbuf * per_buf if args.mode == 'rollout' else 0,
                        'issue': 'eager' if (args.eager or args.league_exchange) else 'one hipGraph replay per timed region',
                        'noise': bool(args.noise),
@@ -823,7 +840,7 @@ def run_reach(args, dev, dist, rank, world):
         if league is not None:
             line['league_exchange'] = league
     # world > 1, default mode: the league all-gather measured beside the metric (short; RCCL on a real node), under a deadline
-    if world > 1 and not args.league_exchange and not args.no_secondary and args.mode == 'rollout':
+    if args.full and world > 1 and not args.league_exchange and not args.no_secondary and args.mode == 'rollout':
         def give_up():
             # a collective that never completes is a finding, not a success: the line (without this measurement) is on stdout,
             # the exit code says that the run did not finish
@@ -849,7 +866,7 @@ def run_reach(args, dev, dist, rank, world):
         except Exception as ex:
             sec['error'] = repr(ex)
         sec['rollout_cold'] = cold
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             line['cpu_baseline'] = cpu_baseline(n, args.cpu_sample_steps, bool(args.noise))
         except Exception as ex:     # the baseline is a report, never the product
@@ -954,11 +971,11 @@ def run_match(args, dev, dist, rank, world):
             'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': {'workload': workload, 'envs_per_gpu': n, 'mode': args.mode, 'cycles_per_launch': per_launch,
-                       'settle_ms': args.settle_ms, 'match_phase': args.match_phase, 'noise': bool(args.noise),
+                       'settle_ms': args.settle_ms, 'match_phase': args.match_phase, 'noise': bool(args.noise), 'full': bool(args.full),
                        'player_steps_per_s': world * mm['player_steps_per_s'], 'timed_regions': len(mm['wall']), 'value_is': 'median region',
                        'parallelism': f'match-shard x{world} (no collective)'},
             'repeats': [world * v for v in mm['repeats']], 'roofline': mm['roofline'], 'events': mm['events']}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             line['cpu_baseline'] = match_cpu_baseline(n)
         except Exception as ex:

@@ -7,13 +7,13 @@ TAG=${1:-r04}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python bench.py --fuse 64 --steps 64 --no-secondary --no-cpu-baseline > $OUT/bench_rollout_T64.json 2> /dev/null
 python bench.py --noise --no-secondary --no-cpu-baseline > $OUT/bench_rollout_noise.json 2> /dev/null
 python bench.py --mode step --no-cpu-baseline > $OUT/bench_step.json 2> /dev/null
 python bench.py --envs 4096 --no-secondary --no-cpu-baseline > $OUT/bench_rollout_4096.json 2> /dev/null
 python bench.py --envs 1048576 --fuse 64 --steps 16 --no-secondary --no-cpu-baseline > $OUT/bench_rollout_1M.json 2> /dev/null
-python bench.py --task match --steps 16 > $OUT/bench_match_rollout.json 2> /dev/null
+python bench.py --full --task match --steps 16 > $OUT/bench_match_rollout.json 2> /dev/null
 python bench.py --task match --mode step --steps 512 --no-cpu-baseline > $OUT/bench_match_step.json 2> /dev/null
 # kernel stats of the same commands (no PMC in these runs)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_rollout -- python3 bench.py --no-cpu-baseline --no-secondary > $OUT/prof_rollout.log 2>&1

@@ -575,6 +575,25 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     assert all(np.array_equal(ma[k], mb[k]) for k in ma)
 
 
+def test_bench_plain_run_prints_the_headline_line_only():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the headline fields and the roofline of the same
+    regions, and none of the measurements that --full adds (cold figure, noise_on, secondary entries, CPU baseline)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--envs', '2048',
+                        '--fuse', '16', '--repeats', '2', '--settle-ms', '0'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['unit'] == 'env-steps/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and d['n_gpus'] == 1
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] > 0 and len(d['repeats']) == 2
+    assert d['value'] == pytest.approx(2048 * 16 / (d['ms_per_step'] * 1e-3)) and d['roofline']['launch_us'] == pytest.approx(d['ms_per_step'] * 1e3)
+    assert d['config']['full'] is False and not {'secondary', 'noise_on', 'cpu_baseline'} & set(d)
+
+
 def test_command_action_kind_equals_the_oracle():
     """S2D_ACT_COMMAND (the boundary of the reference's action_to_rpc_actions hook): a decoded body command per env -- dash with any
     power / direction, turn, none, and S2D_CMD_FREEZE (the env sits the cycle out) -- executed as it is; GPU == oracle bit for bit,

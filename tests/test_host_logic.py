@@ -249,6 +249,60 @@ def test_bench_step_units(monkeypatch):
     assert bench.n_rotating(64 * 65536 * 50) == 3 and bench.n_rotating(64 * 65536 * 50) * 64 * 65536 * 50 > (512 << 20)
 
 
+def test_bench_plain_run_measures_the_headline_only(monkeypatch):
+    """bench.py without --full measures its headline and nothing else -- one measure_rollout() call with the caller's steps and
+    warm-up, no cold figure, no secondary entries, no CPU baseline -- and allocates the record buffer that the cold measurement of a
+    --full run leaves behind, so that the headline's buffers are the same allocations in both.  With --full the same headline call
+    is made, after the cold one, and the line carries all of it.  (The measurements themselves are replaced here: no GPU.)"""
+    import torch
+    import bench
+    assert bench.parse([]).full is False and bench.parse(['--full']).full is True
+
+    class FakeEngine:
+        num_envs, arena = 65536, torch.zeros(4)
+        stats = torch.zeros(8, dtype=torch.int64)
+        allocs = 0
+
+        def alloc_rollout(self, T):
+            self.allocs += 1
+            return {}
+
+        def kernel_name(self):
+            return 'fake'
+    calls = []
+
+    def fake_measure_rollout(eng, T, launches, nbuf, repeats, stream, settle_ms, dist=None, dev=None, warm=4, warm_regions=3, snapshot=None):
+        calls.append(('rollout', launches, warm, nbuf, repeats, settle_ms, eng.allocs))
+        return {'wall': [1e-3 * launches] * repeats, 'events': [1e-3 * launches] * repeats, 'launch_s': 1e-3, 'launch_s_events': 1e-3,
+                'alg_bytes_launch': 1, 'launches': launches, 'buffers': nbuf, 'bytes_in_flight': 1}
+    engines = []
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda dev=None: None)
+    monkeypatch.setattr(bench, 'reach_engine', lambda *a, **k: engines.append(FakeEngine()) or engines[-1])
+    monkeypatch.setattr(bench, 'measure_rollout', fake_measure_rollout)
+    monkeypatch.setattr(bench, 'secondary_measurements', lambda *a: calls.append(('secondary',)))
+    monkeypatch.setattr(bench, 'cpu_baseline', lambda *a: calls.append(('cpu',)) or {'value': 1.0})
+    monkeypatch.setattr(bench, 'match_cpu_baseline', lambda *a: calls.append(('cpu',)) or {'value': 1.0})
+    headline = ('rollout', 7, 3, 2, 5, 200.0, 1)          # --steps 7 --warmup 3, two rotating buffers, after one earlier allocation
+    plain = bench.run_reach(bench.parse(['--steps', '7', '--warmup', '3']), 'cpu', None, 0, 1)
+    assert calls == [headline] and engines[0].allocs == 1
+    assert not {'secondary', 'noise_on', 'cpu_baseline'} & set(plain) and plain['config']['full'] is False
+    assert plain['steps'] == 7 and plain['warmup'] == 3 and plain['ms_per_step'] == pytest.approx(1.0)
+    assert plain['value'] == pytest.approx(65536 * 256 / 1e-3) and plain['unit'] == 'env-steps/s' and plain['higher_is_better'] is True
+    del calls[:], engines[:]
+    full = bench.run_reach(bench.parse(['--steps', '7', '--warmup', '3', '--full']), 'cpu', None, 0, 1)
+    assert calls == [('rollout', 20, 4, 1, 1, 0.0, 0), headline[:-1] + (0,), ('secondary',), ('cpu',)]
+    assert full['secondary']['rollout_cold']['settle_ms'] == 0 and full['cpu_baseline'] == {'value': 1.0} and full['config']['full'] is True
+    assert {k: full[k] for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step')} == \
+           {k: plain[k] for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step')}
+    # what --full adds can be taken away piece by piece, and without --full those flags change nothing
+    del calls[:]
+    bench.run_reach(bench.parse(['--steps', '7', '--warmup', '3', '--full', '--no-cpu-baseline']), 'cpu', None, 0, 1)
+    assert calls[-1] == ('secondary',) and ('cpu',) not in calls
+    del calls[:]
+    bench.run_reach(bench.parse(['--steps', '7', '--warmup', '3', '--no-cpu-baseline']), 'cpu', None, 0, 1)
+    assert calls == [headline]
+
+
 def test_bench_names_the_workload_it_runs():
     """metric / config.workload follow --envs / --task / --league-exchange (BASELINE.json configs[1..4]); other sizes are 'custom'."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
