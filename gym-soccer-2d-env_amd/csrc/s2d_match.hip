@@ -1481,12 +1481,25 @@ S2D_DEV void m_agent_row_store(float* __restrict__ dst, const float4* row, int l
 // order, interleaved by match: tile row 2 j + half = the j-th agent of the tile's eight.  Each 16-row tile is built in LDS, then
 // pushed through the three layers (s2d_net.h: layer 1's 56 k-steps read W1's fragments from memory, layers 2 and 3 theirs from
 // LDS), and the argmax of each row is kept; pad rows of the last tile are zero and their results are never read.
+// Two networks (s2d_match_set_opponent_network): a tile never mixes networks -- the rows go in two passes, each over one network's
+// slots in slot order with that network's fragments, widths, LDS block and K; rows that are only recorded go with the first pass.
+// The passes' argmax tiles follow each other in the wave's index words (at most four tiles: ceil(a / 8) + ceil(b / 8), a + b <= 22).
 constexpr int kNetK1 = S2D_AGENT_OBS_DIM / 4;          // 56 k-steps of layer 1
 constexpr int kNetRowPitch = S2D_AGENT_OBS_DIM + 4;    // LDS pitch of a row (228: the 16 rows of a B fragment hit 64 banks)
 constexpr int kNetHidPitch = 64 + 4;                   // ... of the hidden and Q images
 constexpr int kNetMaxRows = 48;                        // 2 matches x 22 agents, in tiles of 16
+constexpr int kNetIdxWords = 64;                       // ... and of two passes: at most four tiles of 16
+struct MNetOpp {                           // the second network (empty mask: none): the words of its own pass
+  uint32_t mask;                           // its slots (disjoint from net_mask)
+  int h1, h2, na, na16;
+  const float* frags;                      // its fragment-order copy, laid out as the first one's
+  int shared_words;                        // words of its W2 .. b3 staged into LDS behind the first network's; 0: the two do not fit the
+                                           // CU's LDS, and its pass reads them from frags, as both read W1
+  const float* epsilon;
+  const float* table;
+};
 struct MNet {
-  uint32_t net_mask, row_mask, obs_mask;   // network slots; slots whose rows are built (net | obs); slots recorded in agent_obs
+  uint32_t net_mask, row_mask, obs_mask;   // first network's slots; slots whose rows are built (both networks' | obs); slots recorded in agent_obs
   int h1, h2, na, na16;
   const float* frags;                      // the engine's fragment-order copy: W1 (read from memory), then W2 | W3 | b1 | b2 | b3
   int shared_words;                        // words of W2 .. b3 (staged into LDS)
@@ -1494,12 +1507,13 @@ struct MNet {
   const float* table;                      // device float[na][3]
   int32_t* net_index;                      // [T][N][22] or NULL
   float* agent_obs;                        // [T][N][popcount(obs_mask)][224] or NULL
+  MNetOpp opp;
 };
 struct MNetArg { MNet net; MAgentTab tab; };   // kernel argument of the NET instantiations (with their MCtl)
-constexpr int kNetWaveWords = 16 * kNetRowPitch + 16 * kNetHidPitch + 2 * (int)(sizeof(MAObsFacts) / 4) + kNetMaxRows;
+constexpr int kNetWaveWords = 16 * kNetRowPitch + 16 * kNetHidPitch + 2 * (int)(sizeof(MAObsFacts) / 4) + kNetIdxWords;
 static_assert((2 * sizeof(MAObsFacts)) % 16 == 0 && (16 * kNetRowPitch + 16 * kNetHidPitch) % 4 == 0, "16-byte aligned LDS parts");
 
-S2D_DEV float* m_net_lds() {                           // dynamic LDS: [W2 | W3 | b1 | b2 | b3] then kNetWaveWords per wave
+S2D_DEV float* m_net_lds() {                           // dynamic LDS: [W2 | W3 | b1 | b2 | b3] of each network, then kNetWaveWords per wave
   extern __shared__ __attribute__((aligned(16))) float net_smem[];
   return net_smem;
 }
@@ -1508,6 +1522,41 @@ S2D_DEV void m_net_stage(const MNet& net) {
   const float4* src = reinterpret_cast<const float4*>(net.frags + net.h1 / 16 * kNetK1 * 64);
   float4* dst = reinterpret_cast<float4*>(m_net_lds());
   for (int i = threadIdx.x; i < net.shared_words / 4; i += kMBlock) dst[i] = src[i];
+  if (net.opp.shared_words != 0) {
+    const float4* src2 = reinterpret_cast<const float4*>(net.opp.frags + net.opp.h1 / 16 * kNetK1 * 64);
+    dst += net.shared_words / 4;
+    for (int i = threadIdx.x; i < net.opp.shared_words / 4; i += kMBlock) dst[i] = src2[i];
+  }
+}
+
+// One 16-row tile (LDS, `tile`) through the three layers of one network and the argmax of each row into idx[0..15].  w1: W1's
+// fragments (memory); w2s: W2 | W3 | b1 | b2 | b3, in LDS (staged) or in memory -- one inlined copy of this function per kind.
+S2D_DEV void m_net_tile_forward(const float* __restrict__ w1, const float* __restrict__ w2s, int h1, int h2, int nact, int na16,
+                                float* tile, float* hid, int* idx, int lane) {
+  const int gq = lane >> 4, c = lane & 15;
+  const float* const w2 = w2s;
+  const float* const w3 = w2 + (h2 / 16) * (h1 / 4) * 64;
+  const float* const b1 = w3 + (na16 / 16) * (h2 / 4) * 64;
+  const float* const b2 = b1 + h1;
+  const float* const b3 = b2 + h2;
+  const float* const x = tile + c * kNetRowPitch;
+  layer_tile<true, 4>(w1, b1, h1 / 16, kNetK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<true, 4>(w2, b2, h2 / 16, h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<false, 4>(w3, b3, na16 / 16, h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid, kNetHidPitch, lane);
+  wave_fence();
+  if (lane < 16) {   // best = 0; for a = 1 .. K-1: if (q[a] > q[best]) best = a  (ties: lowest index; a NaN never replaces the best)
+    const float* q = hid + lane * kNetHidPitch;
+    int best = 0;
+    float bv = q[0];
+    for (int a = 1; a < nact; ++a) {
+      const float v = q[a];
+      if (v > bv) { bv = v; best = a; }
+    }
+    idx[lane] = best;
+  }
+  wave_fence();
 }
 
 // One cycle's network step of the wave, from the start-of-cycle state (o, g, r): the rows, their record, the forward pass and
@@ -1516,9 +1565,9 @@ template <class P>
 S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGame& g, const MRare& r, int l, int half, bool valid,
                          int64_t rec_row) {
   const MNet& net = na.net;
-  const int lane = threadIdx.x & 63, gq = lane >> 4, c = lane & 15;
+  const int lane = threadIdx.x & 63;
   float* const shared = m_net_lds();
-  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * kNetWaveWords;
+  float* const tile = shared + net.shared_words + net.opp.shared_words + (threadIdx.x >> 6) * kNetWaveWords;
   float* const hid = tile + 16 * kNetRowPitch;
   MAObsFacts* const facts = reinterpret_cast<MAObsFacts*>(hid + 16 * kNetHidPitch);
   int* const gidx = reinterpret_cast<int*>(facts + 2);
@@ -1532,54 +1581,49 @@ S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGa
   in.score_l = r.score_l; in.score_r = r.score_r; in.holder = r.holder; in.stopped = r.stopped;
   MAObsFacts& fs = facts[half];
   const MAgentDerived f = m_agent_facts(na.tab, fs, in, l, half);
-  const int nrows = __builtin_popcount(net.row_mask), nobs = __builtin_popcount(net.obs_mask);
-  const float* const w2 = shared;
-  const float* const w3 = w2 + (net.h2 / 16) * (net.h1 / 4) * 64;
-  const float* const b1 = w3 + (net.na16 / 16) * (net.h2 / 4) * 64;
-  const float* const b2 = b1 + net.h1;
-  const float* const b3 = b2 + net.h2;
-  uint32_t rest = net.row_mask;
-  for (int nt = 0; 8 * nt < nrows; ++nt) {
-    const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
-    for (int i = lane; i < (16 - 2 * rn) * (kNetRowPitch / 4); i += 64)   // pad rows of the last tile
-      reinterpret_cast<float4*>(tile + 2 * rn * kNetRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int j = 0; j < rn; ++j) {
-      const int pa = __builtin_ctz(rest);              // the agent (uniform: the mask is a kernel argument)
-      rest &= rest - 1u;
-      float4* const row = reinterpret_cast<float4*>(tile + (2 * j + half) * kNetRowPitch);
-      m_agent_row(p, na.tab, fs, in, f, l, pa, row);
-      if (net.agent_obs && ((net.obs_mask >> pa) & 1u)) {
-        wave_fence();
-        const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
-        if (valid) m_agent_row_store(net.agent_obs + (rec_row * nobs + k) * S2D_AGENT_OBS_DIM, row, l);
-      }
-    }
-    wave_fence();
-    if (net.net_mask != 0u) {
-      const float* const x = tile + c * kNetRowPitch;
-      layer_tile<true, 4>(net.frags, b1, net.h1 / 16, kNetK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
-      wave_fence();
-      layer_tile<true, 4>(w2, b2, net.h2 / 16, net.h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile,
-                          kNetHidPitch, lane);
-      wave_fence();
-      layer_tile<false, 4>(w3, b3, net.na16 / 16, net.h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid,
-                           kNetHidPitch, lane);
-      wave_fence();
-      if (lane < 16) {   // best = 0; for a = 1 .. K-1: if (q[a] > q[best]) best = a  (ties: lowest index; a NaN never replaces the best)
-        const float* q = hid + lane * kNetHidPitch;
-        int best = 0;
-        float bv = q[0];
-        for (int a = 1; a < net.na; ++a) {
-          const float v = q[a];
-          if (v > bv) { bv = v; best = a; }
+  const int nobs = __builtin_popcount(net.obs_mask);
+  const uint32_t first_rows = net.row_mask & ~net.opp.mask;   // the first pass: the first network's slots and the only-recorded ones
+  const int first_tiles = (__builtin_popcount(first_rows) + 7) >> 3;
+#pragma nounroll
+  for (int pass = 0; pass < 2; ++pass) {                 // (every word of a pass is a kernel argument: uniform)
+    const bool second = pass != 0;
+    uint32_t rest = second ? net.opp.mask : first_rows;
+    if (rest == 0u) continue;
+    const bool forward = second || net.net_mask != 0u;   // (first pass without a network: records only)
+    const int h1 = second ? net.opp.h1 : net.h1, h2 = second ? net.opp.h2 : net.h2;
+    const int nact = second ? net.opp.na : net.na, na16 = second ? net.opp.na16 : net.na16;
+    const float* const w1 = second ? net.opp.frags : net.frags;
+    const bool staged = !second || net.opp.shared_words != 0;
+    int* const pidx = gidx + (second ? 16 * first_tiles : 0);
+    const int nrows = __builtin_popcount(rest);
+    for (int nt = 0; 8 * nt < nrows; ++nt) {
+      const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
+      for (int i = lane; i < (16 - 2 * rn) * (kNetRowPitch / 4); i += 64)   // pad rows of the last tile
+        reinterpret_cast<float4*>(tile + 2 * rn * kNetRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      for (int j = 0; j < rn; ++j) {
+        const int pa = __builtin_ctz(rest);              // the agent (uniform: the mask is a kernel argument)
+        rest &= rest - 1u;
+        float4* const row = reinterpret_cast<float4*>(tile + (2 * j + half) * kNetRowPitch);
+        m_agent_row(p, na.tab, fs, in, f, l, pa, row);
+        if (net.agent_obs && ((net.obs_mask >> pa) & 1u)) {
+          wave_fence();
+          const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
+          if (valid) m_agent_row_store(net.agent_obs + (rec_row * nobs + k) * S2D_AGENT_OBS_DIM, row, l);
         }
-        gidx[16 * nt + lane] = best;
       }
       wave_fence();
+      if (forward) {
+        if (staged) m_net_tile_forward(w1, shared + (second ? net.shared_words : 0), h1, h2, nact, na16, tile, hid, pidx + 16 * nt, lane);
+        else m_net_tile_forward(w1, w1 + h1 / 16 * kNetK1 * 64, h1, h2, nact, na16, tile, hid, pidx + 16 * nt, lane);
+      }
     }
   }
   int greedy = 0;
-  if (l < NP && ((net.net_mask >> l) & 1u)) greedy = gidx[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+  if (l < NP) {                                          // the slot's place among its own pass's rows
+    const uint32_t below = (1u << l) - 1u;
+    if ((net.net_mask >> l) & 1u) greedy = gidx[2 * __builtin_popcount(first_rows & below) + half];
+    else if ((net.opp.mask >> l) & 1u) greedy = gidx[16 * first_tiles + 2 * __builtin_popcount(net.opp.mask & below) + half];
+  }
   wave_fence();
   return greedy;
 }
@@ -1751,7 +1795,19 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   // a launch every wave spends the same time at each.
   const int simd_slot = (int)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4);   // HW_REG_HW_ID bits 3:0
   uint64_t net_thr = 0;
-  if constexpr (NET) net_thr = nin->net.net_mask ? explore_threshold(*nin->net.epsilon) : 0;   // (records only: no network)
+  uint32_t net_slots = 0u, net_k = 0u;                     // NET: the slots on a network; this lane's network: its K and table
+  const float* net_tab = nullptr;
+  if constexpr (NET) {
+    net_thr = nin->net.net_mask ? explore_threshold(*nin->net.epsilon) : 0;   // (records only: no network)
+    net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
+    if constexpr (!SEE) {
+      if (nin->net.opp.mask != 0u) {                       // the second network: its slots take its threshold, K and table
+        const uint64_t thr2 = explore_threshold(*nin->net.opp.epsilon);
+        net_slots |= nin->net.opp.mask;
+        if ((nin->net.opp.mask >> l) & 1u) { net_thr = thr2; net_k = (uint32_t)nin->net.opp.na; net_tab = nin->net.opp.table; }
+      }
+    }
+  }
   for (int t = 0; t < n_steps; ++t) {
     if ((t & 3) == 0) {
       switch ((simd_slot + (t >> 2)) & 3) {
@@ -1778,9 +1834,9 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
         int greedy;
         if constexpr (SEE) greedy = m_see_greedy(*nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec);
         else greedy = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec);
-        if (l < NP && ((nin->net.net_mask >> l) & 1u)) {   // explore: word x < thr, then the index is word y's draw below K
+        if (l < NP && ((net_slots >> l) & 1u)) {           // explore: word x < thr, then the index is word y's draw below K
           const U4 w = m_draw(p, gl, gh, (uint32_t)g.tick, S2D_ST_NET, (uint32_t)l);
-          nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, (uint32_t)nin->net.na) : greedy;
+          nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, net_k) : greedy;
         }
         if (nin->net.net_index && valid && l < NP) nin->net.net_index[((int64_t)t * n + e) * NP + l] = nidx;
       }
@@ -1788,10 +1844,10 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
         const uint32_t bit = 1u << l;
         if (NET && nidx >= 0) {
           if constexpr (SEE) {
-            const float* tr = nin->net.table + 5 * nidx;
+            const float* tr = net_tab + 5 * nidx;
             cmd = (int)tr[0]; a = tr[1]; b = tr[2]; view_m = tr[3]; view_c = tr[4]; view_act = true;
           } else {
-            const float* tr = nin->net.table + 3 * nidx;
+            const float* tr = net_tab + 3 * nidx;
             cmd = (int)tr[0]; a = tr[1]; b = tr[2];
           }
         } else if (ctl.script_mask & bit) {
@@ -2018,7 +2074,9 @@ struct S2DMatchEngine {
   bool has_ctl = false;                                // s2d_match_set_controllers installed a table: launches use the CTL kernels
   bool has_net = false;                                // s2d_match_set_network installed a network: launches use the NET kernels
   S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time)
-  float* net_frags = nullptr;                          // the fragment-order copy the pack kernel writes (kNetFragsMax words)
+  bool has_opp = false;                                // s2d_match_set_opponent_network installed a second network (NET kernels, a pass of its own)
+  S2DMatchNet opp{};                                   // ... its pointers
+  float* net_frags = nullptr;                          // the fragment-order copies the pack kernel writes (2 x kNetFragsMax words: network, opponent)
   bool has_see = false;                                // s2d_match_set_see_network installed a see network: launches use the SEE kernels
   S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
@@ -2472,6 +2530,22 @@ template <class K, class NA> static int m_net_launch(K kernel, int slot, size_t 
                                                      const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
                                                      const MCtl& ctl, const NA& na) {
   if (std::is_same<NA, MSeeArg>::value) slot += 5;
+  if constexpr (std::is_same<NA, MNetArg>::value) {
+    // The budget: a 64-64-64 network's W2 .. b3 are 33 536 B, a wave's tile, facts and index words 20 784 B, so two widest
+    // networks ask for 2 x 33 536 + 4 x 20 784 = 150 208 B.  Beside the stock kernels' 12 288 B of static LDS the CU leaves
+    // 151 552 B: they fit.  Beside the general kernels' 14 208 / 14 576 B (their parameter block) it leaves 149 632 / 149 264 B:
+    // there two networks of 64-64-(49..64) do not fit, and the second one's W2 .. b3 stay in memory (the kernel reads them
+    // there, the same words in the same order).  Every other pair fits every kernel.
+    const size_t second = (size_t)na.net.opp.shared_words * sizeof(float);
+    if (second != 0 && !m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn)) {
+      MNetArg unstaged = na;
+      unstaged.net.opp.shared_words = 0;
+      if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn - second))
+        return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn - second) + " B) does not fit beside the cycle kernel's");
+      hipLaunchKernelGGL(kernel, grid, block, dyn - second, st, mp, ptrs, n, n_steps, actions, ro, ctl, unstaged);
+      return S2D_OK;
+    }
+  }
   if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn))
     return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
   hipLaunchKernelGGL(kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
@@ -2487,7 +2561,8 @@ static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const
   if constexpr (NET) {
     const auto& na = std::get<1>(std::tie(extra...));    // an MNetArg, or the see network's MSeeArg
     constexpr int wave_words = std::is_same<std::decay_t<decltype(na)>, MSeeArg>::value ? kSeeWaveWords : kNetWaveWords;
-    const size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
+    size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
+    if constexpr (std::is_same<std::decay_t<decltype(na)>, MNetArg>::value) dyn += (size_t)na.net.opp.shared_words * sizeof(float);
     int rc;
     if (h->stock_sched)
       rc = m_net_launch(s2d_match_rollout_kernel<true, true, true, false, true, true, X...>, 0, dyn, grid, block, st, h->mp, h->ptrs,
@@ -2569,7 +2644,7 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr uint32_t kAll = (1u << NP) - 1u;
-  const uint32_t net_mask = h->has_see ? h->see.slot_mask : h->has_net ? h->net.slot_mask : 0u;
+  const uint32_t net_mask = h->has_see ? h->see.slot_mask : (h->has_net ? h->net.slot_mask : 0u) | (h->has_opp ? h->opp.slot_mask : 0u);
   if (!agent_obs_out) obs_mask = 0u;
   if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
     return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
@@ -2599,17 +2674,36 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
     MNetArg na;
     std::memset(&na, 0, sizeof na);
     MNet& nt = na.net;
-    nt.net_mask = net_mask; nt.obs_mask = obs_mask; nt.row_mask = net_mask | obs_mask;
+    nt.obs_mask = obs_mask; nt.row_mask = net_mask | obs_mask;
     nt.net_index = net_index_out; nt.agent_obs = agent_obs_out;
     na.tab = h->atab;
-    if (net_mask) {
-      nt.h1 = h->net.h1; nt.h2 = h->net.h2; nt.na = h->net.n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
-      nt.frags = h->net_frags; nt.epsilon = h->net.epsilon; nt.table = h->net.table;
-      nt.shared_words = (nt.h2 / 16 * (nt.h1 / 4) + nt.na16 / 16 * (nt.h2 / 4)) * 64 + nt.h1 + nt.h2 + nt.na16;
-      const int total = (nt.h1 / 16 * kNetK1) * 64 + nt.shared_words;
-      MDeviceGuard guard(h->device);
-      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->net.params, (int)S2D_AGENT_OBS_DIM,
-                         nt.h1, nt.h2, nt.na, nt.na16, h->net_frags, total);
+    // The kernel's first pass is the network when one is set, else the opponent; its second pass the opponent beside a network.
+    // Each keeps its own half of the fragment copy, so which pass a network runs in changes no word it reads.
+    const S2DMatchNet* const first = h->has_net ? &h->net : h->has_opp ? &h->opp : nullptr;
+    const S2DMatchNet* const second = h->has_net && h->has_opp ? &h->opp : nullptr;
+    const auto shared_words = [](int h1, int h2, int na16) { return (h2 / 16 * (h1 / 4) + na16 / 16 * (h2 / 4)) * 64 + h1 + h2 + na16; };
+    const auto pack = [&](const S2DMatchNet* net, float* frags, int words) {
+      const int na16 = (net->n_actions + 15) / 16 * 16;
+      const int total = (net->h1 / 16 * kNetK1) * 64 + words;
+      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, net->params, (int)S2D_AGENT_OBS_DIM,
+                         net->h1, net->h2, net->n_actions, na16, frags, total);
+    };
+    MDeviceGuard guard(h->device);
+    if (first) {
+      nt.net_mask = first->slot_mask;
+      nt.h1 = first->h1; nt.h2 = first->h2; nt.na = first->n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
+      nt.frags = h->net_frags + (first == &h->opp ? kNetFragsMax : 0); nt.epsilon = first->epsilon; nt.table = first->table;
+      nt.shared_words = shared_words(nt.h1, nt.h2, nt.na16);
+      pack(first, const_cast<float*>(nt.frags), nt.shared_words);
+      MHIP_TRY(hipGetLastError());
+    }
+    if (second) {
+      MNetOpp& op = nt.opp;
+      op.mask = second->slot_mask;
+      op.h1 = second->h1; op.h2 = second->h2; op.na = second->n_actions; op.na16 = (op.na + 15) / 16 * 16;
+      op.frags = h->net_frags + kNetFragsMax; op.epsilon = second->epsilon; op.table = second->table;
+      op.shared_words = shared_words(op.h1, op.h2, op.na16);
+      pack(second, const_cast<float*>(op.frags), op.shared_words);
       MHIP_TRY(hipGetLastError());
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
@@ -2625,7 +2719,13 @@ S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
            h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, see network>" :
                                               "s2d_match_rollout_kernel<general, see network>";
   }
-  if (h->has_net) {
+  if (h->has_net && h->has_opp) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, two networks>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, two networks>" : h->stock ? "s2d_match_rollout_kernel<stock, two networks>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, two networks>" :
+                                              "s2d_match_rollout_kernel<general, two networks>";
+  }
+  if (h->has_net || h->has_opp) {
     if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, network>";
     return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, network>" : h->stock ? "s2d_match_rollout_kernel<stock, network>" :
            h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, network>" :
@@ -2695,34 +2795,45 @@ S2D_API int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float* act
   if (n_steps == 0) return S2D_OK;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev);
 }
-S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { h->has_net = false; h->net = S2DMatchNet{}; return S2D_OK; }
+static int m_net_frags_alloc(S2DMatchHandle h) {
+  if (h->net_frags) return S2D_OK;
+  MDeviceGuard guard(h->device);
+  void* pmem = nullptr;
+  if (hipMalloc(&pmem, 2 * (size_t)kNetFragsMax * sizeof(float)) != hipSuccess) return mfail(S2D_ENOMEM, "hipMalloc of the network copy failed");
+  h->net_frags = static_cast<float*>(pmem);
+  return S2D_OK;
+}
+// what both agent-row network setters reject; other_mask: the slots of the engine's other agent-row network (0: none set)
+static int m_net_validate(const S2DMatchNet* net, uint32_t other_mask) {
   const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
   if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "network hidden widths must be 16, 32, 48 or 64");
   if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "network n_actions must be in [1, 64]");
   if (net->slot_mask == 0u || (net->slot_mask >> NP) != 0u)
     return mfail(S2D_EINVAL, "network slot_mask must be a non-empty set of bits 0..21");
+  if (net->slot_mask & other_mask)
+    return mfail(S2D_EINVAL, "network slot_mask overlaps the engine's other network (a slot belongs to one network)");
   if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
     return mfail(S2D_EINVAL, "network params must be a non-NULL, 16-byte aligned device pointer");
   if (!net->epsilon || !net->table || ((reinterpret_cast<uintptr_t>(net->epsilon) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
     return mfail(S2D_EINVAL, "network epsilon and table must be non-NULL, 4-byte aligned device pointers");
-  if (!h->net_frags) {
-    MDeviceGuard guard(h->device);
-    void* pmem = nullptr;
-    if (hipMalloc(&pmem, (size_t)kNetFragsMax * sizeof(float)) != hipSuccess) return mfail(S2D_ENOMEM, "hipMalloc of the network copy failed");
-    h->net_frags = static_cast<float*>(pmem);
-  }
-  h->net = *net; h->has_net = true;
-  h->has_see = false; h->see = S2DMatchSeeNet{};       // one network per engine
   return S2D_OK;
 }
-static int m_net_frags_alloc(S2DMatchHandle h) {
-  if (h->net_frags) return S2D_OK;
-  MDeviceGuard guard(h->device);
-  void* pmem = nullptr;
-  if (hipMalloc(&pmem, (size_t)kNetFragsMax * sizeof(float)) != hipSuccess) return mfail(S2D_ENOMEM, "hipMalloc of the network copy failed");
-  h->net_frags = static_cast<float*>(pmem);
+S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { h->has_net = false; h->net = S2DMatchNet{}; return S2D_OK; }
+  if (int rc = m_net_validate(net, h->has_opp ? h->opp.slot_mask : 0u); rc != S2D_OK) return rc;
+  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  h->net = *net; h->has_net = true;
+  h->has_see = false; h->see = S2DMatchSeeNet{};       // the see network and the agent-row ones exclude each other
+  return S2D_OK;
+}
+S2D_API int s2d_match_set_opponent_network(S2DMatchHandle h, const S2DMatchNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { h->has_opp = false; h->opp = S2DMatchNet{}; return S2D_OK; }
+  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
+  if (int rc = m_net_validate(net, h->has_net ? h->net.slot_mask : 0u); rc != S2D_OK) return rc;
+  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  h->opp = *net; h->has_opp = true;
   return S2D_OK;
 }
 S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
@@ -2746,7 +2857,8 @@ S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* ne
   if (net->slot_mask != 0u)
     if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
   h->see = *net; h->has_see = true;
-  h->has_net = false; h->net = S2DMatchNet{};          // one network per engine
+  h->has_net = false; h->net = S2DMatchNet{};          // the see network is the engine's only one: both agent-row networks go
+  h->has_opp = false; h->opp = S2DMatchNet{};
   return S2D_OK;
 }
 S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,

@@ -183,6 +183,7 @@ MATCH_PROTOTYPES = (
     ('s2d_match_rollout_ex', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p)),
     ('s2d_match_agent_obs', C.c_int, (C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
     ('s2d_match_set_network', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_opponent_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_net', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p)),
     ('s2d_match_vision_default_params', None, (C.POINTER(S2DVisionParams),)),

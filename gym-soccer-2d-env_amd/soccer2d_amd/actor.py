@@ -357,6 +357,15 @@ class MatchQNetActor:
     def epsilon_tensor(self):
         return self._eps
 
+    def snapshot(self, epsilon=0.0):
+        """A frozen copy: a new actor of the same shape with its own copies of the packed parameters and the action table and
+        its own epsilon -- the league member a learner plays against (MatchEngine.set_opponent_network).  It has no module:
+        later sync() calls of the original do not touch it."""
+        snap = type(self)(self.hidden1, self.hidden2, self.n_actions, device=self.device, epsilon=epsilon, obs=self.obs)
+        snap.params.copy_(self.params)
+        snap.table.copy_(self.table)
+        return snap
+
     def c_struct(self, slot_mask, vision_params=None, vision=None):
         """S2DMatchNet; obs='see': S2DMatchSeeNet, which needs the engine's vision parameters and planes."""
         from . import _capi_match as M

@@ -128,6 +128,38 @@ def play_round(engine, policies, left_ids, right_ids, n_cycles):
     return (engine.score_left - s0l).to(torch.int64), (engine.score_right - s0r).to(torch.int64)
 
 
+def play_networks(engine, left_actor, right_actor, n_cycles, chunk=64):
+    """One round of learner versus frozen opponent inside the cycle kernel: `left_actor` plays the left team and `right_actor`
+    (typically ``left_actor.snapshot()``) the right one, each MatchQNetActor on its own weights, epsilon and table
+    (MatchEngine.set_network / set_opponent_network), `n_cycles` cycles in launches of at most `chunk`.  Resets the engine first,
+    like play_round, and returns (goals_left, goals_right) int64[N] for League.update; the engine's previous networks are
+    restored."""
+    n_cycles, chunk = int(n_cycles), int(chunk)
+    if n_cycles < 0 or chunk < 1:
+        raise ValueError(f"n_cycles must be >= 0 and chunk >= 1, got {n_cycles} and {chunk}")
+    prev = (engine.network, engine.network_mask, engine.opponent_network, engine.opponent_mask)
+    engine.set_network(None)
+    try:
+        engine.set_network(left_actor, 'left')
+        engine.set_opponent_network(right_actor, 'right')
+        engine.reset()
+        s0l, s0r = engine.score_left.clone(), engine.score_right.clone()
+        out = engine.alloc_rollout(min(chunk, max(n_cycles, 1)), with_obs=False)
+        done = 0
+        while done < n_cycles:
+            t = min(chunk, n_cycles - done)
+            engine.rollout(t, out=out, with_obs=False)
+            done += t
+        goals = (engine.score_left - s0l).to(torch.int64), (engine.score_right - s0r).to(torch.int64)
+    finally:
+        engine.set_network(None)
+        if prev[0] is not None:
+            engine.set_network(prev[0], prev[1])
+        if prev[2] is not None:
+            engine.set_opponent_network(prev[2], prev[3])
+    return goals
+
+
 def exchange_results(left, right, goals_left, goals_right, group=None):
     """All-gather one round's results so that every rank can apply the same Elo update.
     Inputs are per-rank tensors of equal length; output tensors are ordered by rank."""

@@ -69,6 +69,7 @@ class MatchEngine:
         self.lib = M.bind(_capi.load_library())
         self.controllers = None                         # no per-slot table (set_controllers)
         self.network, self.network_mask = None, 0       # no network slots (set_network)
+        self.opponent_network, self.opponent_mask = None, 0   # no second network (set_opponent_network)
         self.vision = None                              # no vision layer (enable_vision)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -133,15 +134,18 @@ class MatchEngine:
         """Network slots: `actor` (a MatchQNetActor) chooses the action of every slot in `slots` ('all' | 'left' | 'right' | a
         mask of bits 0..21) inside the cycle kernel, on the slot's agent row (include/s2d_match.h).  It overrides the controller
         table for those slots; the engine keeps the actor's buffers, so sync() / epsilon / set_table() act at the next launch (or
-        graph replay).  None clears the network.
+        graph replay).  None clears every network, the opponent network (set_opponent_network) included.
 
         A see actor (MatchQNetActor(obs='see')) is the see network: it acts on the slot's see row, its table also chooses the
         slot's TurnNeck / ChangeView, and from now on the cycle kernel steps the vision state itself -- do not call vision_step()
-        for cycles it runs.  It needs enable_vision() first.  One network per engine: either kind replaces the other."""
+        for cycles it runs.  It needs enable_vision() first.  Either kind replaces the other, and the see network also clears
+        the opponent network: it stays the engine's only one."""
         if actor is None:
             _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, None), 's2d_match_set_network')
+            _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, None), 's2d_match_set_opponent_network')
             _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, None), 's2d_match_set_see_network')
             self.network, self.network_mask = None, 0
+            self.opponent_network, self.opponent_mask = None, 0
             return
         mask = M.agent_slot_mask(slots)
         if actor.device != self.device:
@@ -150,10 +154,33 @@ class MatchEngine:
             self._need_vision()
             net = actor.c_struct(mask, self.vision_params, self.vision)
             _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
+            self.opponent_network, self.opponent_mask = None, 0
         else:
             net = actor.c_struct(mask)
             _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
         self.network, self.network_mask = actor, mask
+
+    def set_opponent_network(self, actor, slots='right'):
+        """A second, independent network beside set_network's: `actor` (a MatchQNetActor on agent rows, typically a frozen
+        ``snapshot()`` of the learner) plays the slots in `slots` on its own weights, epsilon and action table, in the same launch
+        (s2d_match_set_opponent_network in include/s2d_match.h).  The two masks must be disjoint; either network may be set
+        without the other.  None clears the opponent only.  A see actor is refused: the see network stays single."""
+        if actor is None:
+            _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, None), 's2d_match_set_opponent_network')
+            self.opponent_network, self.opponent_mask = None, 0
+            return
+        mask = M.agent_slot_mask(slots)
+        if getattr(actor, 'obs', 'agent') == 'see':
+            raise ValueError("the opponent network acts on agent rows: a see actor cannot be one (the see network stays single)")
+        if actor.device != self.device:
+            raise ValueError(f"the actor's buffers are on {actor.device}, the engine on {self.device}")
+        if self._see_network_set():
+            raise ValueError("a see network is set: it is the engine's only network (set_network(None) first)")
+        if mask & self.network_mask:
+            raise ValueError(f"opponent slots {mask:#x} overlap the network's slots {self.network_mask:#x}")
+        net = actor.c_struct(mask)
+        _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, C.byref(net)), 's2d_match_set_opponent_network')
+        self.opponent_network, self.opponent_mask = actor, mask
 
     def _see_network_set(self):
         return self.network is not None and getattr(self.network, 'obs', 'agent') == 'see'
@@ -271,7 +298,7 @@ class MatchEngine:
                                 tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
             raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{n},22,3]")
         record_only = not self._see_network_set()
-        if record_only and self.network is not None:
+        if record_only and (self.network is not None or self.opponent_network is not None):
             raise ValueError("see_obs / view_actions need a see network or no network (the engine has an agent-row network set)")
         idx = None
         if net_index:

@@ -383,6 +383,23 @@ typedef struct S2DMatchNet {
  * n_actions outside [1, 64], an empty slot_mask or bits above 21, NULL or unaligned pointers.  s2d_match_step, s2d_match_rollout and
  * s2d_match_rollout_ex use the network when one is set; a caller row of a network slot is never read. */
 int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet *net);
+/* Opponent network: a second, independent network of the same kind, so that a learner plays a frozen snapshot of itself (or another
+ * league member) inside one launch.  It takes the same S2DMatchNet -- its own h1, h2, n_actions, slot_mask, params, epsilon and
+ * table -- and the engine keeps its pointers and repacks its params before every launch, as for the first network.
+ *   - Steps 1 to 5 of "Network slots" hold for each slot with the network that slot belongs to: the same start-of-cycle row, the
+ *     same k-ascending fmaf order, relu and first-maximum argmax, the same Philox stream S2D_MATCH_ST_NET with block = the slot; the
+ *     threshold from that network's own *epsilon, the random index below that network's own K, the action from its own table.
+ *   - The two slot masks must be disjoint: a slot's index is a function of its own network only.
+ *   - The two are symmetric and either may be set without the other: (network A on mask a, opponent B on mask b) and (network B on
+ *     b, opponent A on a) are bitwise the same launch; with one of them set the launch is the single-network one.
+ *   - s2d_match_step, s2d_match_rollout, s2d_match_rollout_ex and s2d_match_rollout_net use both.  net_index_out holds the index of
+ *     the slots of either network, -1 elsewhere (the masks tell which network a slot belongs to); agent_obs_out is unchanged.
+ *   - s2d_match_kernel_name ends in "two networks>" when both are set.
+ * net == NULL clears the opponent only, and s2d_match_set_network(h, NULL) the first network only.  Errors (S2D_EINVAL, the engine
+ * unchanged): everything s2d_match_set_network rejects; a slot_mask that overlaps the other network's (s2d_match_set_network
+ * rejects the same against a set opponent); a see network is set -- the see network stays single, and s2d_match_set_see_network
+ * clears both agent-row networks. */
+int s2d_match_set_opponent_network(S2DMatchHandle h, const S2DMatchNet *net);
 /* s2d_match_rollout_ex plus two records (either may be NULL):
  *   net_index_out_dev  int32[T][N][22]: the index each network slot chose, -1 for the other slots (4-byte aligned);
  *   agent_obs_out_dev  float[T][N][popcount(obs_mask)][S2D_AGENT_OBS_DIM]: the start-of-cycle rows of the slots in obs_mask, in
@@ -500,7 +517,8 @@ int s2d_match_see(S2DMatchHandle h, const S2DVisionParams *prm, const S2DMatchVi
 /* See network: the network slots of "Network slots" above under partial observability.  The Q-network acts on each slot's SEE row
  * (S2D_SEE_DIM words) instead of its full-state agent row, it also chooses the slot's view action (TurnNeck, ChangeView), and the
  * vision state of all 22 players is stepped inside the cycle kernel: T cycles of self-play under the vision model are one launch.
- * One network per engine: setting a see network clears an s2d_match_set_network one, and the reverse.  For every cycle of a launch
+ * One see network per engine, and no agent-row network beside it: setting a see network clears the s2d_match_set_network and
+ * s2d_match_set_opponent_network ones, s2d_match_set_network clears the see network.  For every cycle of a launch
  * and every match:
  *   1. For every slot in slot_mask | obs_mask: x = the slot's see row, built from the START-of-cycle engine state, the current
  *      vision state and the match's tick: bitwise what s2d_match_see returns at that moment (the two share one device function).
