@@ -219,17 +219,51 @@ def test_noise_is_bounded_and_seeded():
     assert (sp <= 1.05 * 1.1 + 1e-6).all()
 
 
-def test_f32_tracks_f64_over_an_episode():
-    """Stated tolerance: fp32 engine vs fp64 engine, same formulas: <= 1e-3 m over
-    a 201-step episode."""
+# what the fp32 engine may drift from the fp64 engine by over a 201-step episode.  Positions: the stated 1e-3 m.  Stamina
+# and body: 4x the maximum the fp32 oracle shows over the four configurations below (measured: stamina 9.8e-4 of 8000, two fp32 ulps,
+# from the recovery decrement 0.002 that is no fp32 number; body 1.5e-4 deg in the turning mode, 0 elsewhere: nothing else turns).
+TRACK_BOUNDS = dict(player_x=1e-3, player_y=1e-3, ball_x=1e-3, ball_y=1e-3, stamina=3.9e-3, player_body=6e-4)
+TRACK_CONFIGS = {
+    'discrete-free-angle': dict(server=dict(dash_angle_step=0.0)),
+    'continuous': dict(use_continuous_action=True),
+    'turning': dict(use_continuous_action=True, use_turning=True),
+    'noise-on': dict(noise=1),
+}
+
+
+@pytest.mark.parametrize('name', list(TRACK_CONFIGS))
+def test_f32_tracks_f64_over_an_episode(name):
+    """Stated tolerance: fp32 engine vs fp64 engine, same formulas, same actions: <= 1e-3 m over a 201-step episode, in
+    every action mode and with noise on, stamina and body angle included.  An env leaves the comparison at the first cycle in which
+    it collides (either build) or the one-cycle rule of tests/reach_f64.py flags it ill-conditioned: what follows a flipped
+    threshold is drift, not error.  The others are compared after every cycle."""
+    import reach_f64 as R
     n = 128
-    kw = dict(auto_reset=0, change_ball_velocity=True, server=dict(dash_angle_step=0.0))
-    a, b = fresh(n=n, prec='f32', **kw), fresh(n=n, prec='f64', **kw)
+    kw = dict(auto_reset=0, change_ball_velocity=True, **TRACK_CONFIGS[name])
+    a, b = fresh(n=n, prec='f32', **dict(kw)), fresh(n=n, prec='f64', **dict(kw))
     a.reset(); b.reset()
     rs = np.random.RandomState(5)
+    alive = np.ones(n, bool)
+    rsum = a.cfg.sp.player_size + a.cfg.sp.ball_size
+    worst = {f: 0.0 for f in TRACK_BOUNDS}
     for t in range(201):
-        act = rs.randint(0, 16, n).astype(np.int32)
+        act = R.random_actions(rs, a.cfg, n)
+        if not a.cfg.task.use_continuous_action:
+            act = act.astype(np.int32)
+        _, ill, _, _ = R.probe(a.cfg, R.read_rows(a), act)
         a.step(act); b.step(act)
-    for f in ('player_x', 'player_y', 'ball_x', 'ball_y'):
-        assert np.abs(a.state(f) - b.state(f)).max() < 1e-3, f
+        touch = np.zeros(n, bool)
+        for e in (a, b):
+            d = np.hypot(e.state('ball_x').astype(np.float64) - e.state('player_x'), e.state('ball_y').astype(np.float64) - e.state('player_y'))
+            touch |= d <= rsum * (1 + 1e-6)                # a collision leaves the pair in exact contact
+        alive &= ~ill & ~touch
+        for f in TRACK_BOUNDS:
+            d = np.abs(a.state(f).astype(np.float64) - b.state(f))
+            if f == 'player_body':
+                d = np.minimum(d, 360.0 - d)
+            worst[f] = max(worst[f], float(d[alive].max()))
+    print(name, int(alive.sum()), 'envs compared to the end;', worst)
+    assert alive.sum() >= n * 3 // 4, int(alive.sum())
+    for f, bound in TRACK_BOUNDS.items():
+        assert worst[f] < bound, (f, worst[f], bound)
     assert (a.state('cycle') == b.state('cycle')).all() and (a.state('cycle') == 202).all()
