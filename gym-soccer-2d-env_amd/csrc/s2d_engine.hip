@@ -1058,6 +1058,12 @@ extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2D
                                           const float* eps, const float* noise, const RolloutOut* ro, float* term_rec,
                                           const StepOut* o, void* stream, char* name);
 
+// s2d_policy.hip: launches the stochastic policy rollout of any action mode (same return codes)
+extern "C" int s2d_internal_rollout_policy(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
+                                           int64_t n, int n_steps, int h1, int h2, int na, int act_fn, const float* params,
+                                           const float* log_std, const uint32_t* det, const RolloutOut* ro, float* term_rec,
+                                           float* logp, const StepOut* o, void* stream, char* name);
+
 struct S2DEngine {
   S2DConfig cfg;
   S2DHot hot;
@@ -1590,6 +1596,47 @@ S2D_API int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet* net, 
                                             net->noise_kind ? net->noise : nullptr, &ro, terminal_obs, &h->out, stream, h->kernel_name);
   if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_actor: the network does not fit the LDS of a workgroup");
   if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor: hipGetDevice or hipFuncSetAttribute failed");
+  HIP_TRY(hipGetLastError());
+  h->last_kernel = h->kernel_name;
+  return S2D_OK;
+}
+
+S2D_API int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet* net, const S2DRollout* out, float* terminal_obs,
+                               float* logp, void* stream) {
+  if (!h) return fail(S2D_EINVAL, "NULL handle");
+  if (!net) return fail(S2D_EINVAL, "s2d_rollout_policy: net is NULL");
+  const int na = h->mode == S2D_MODE_DISCRETE ? h->cfg.task.action_space_size : h->mode == S2D_MODE_TURN4 ? 4 : 1;
+  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_policy: n_steps must be >= 1");
+  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
+  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: hidden widths must be multiples of 16 in [16, 128] (the weights live in LDS)");
+  if (net->n_out != na || na < 1 || na > 64)
+    return fail(S2D_EINVAL, h->mode == S2D_MODE_DISCRETE ? "s2d_rollout_policy: n_out must equal action_space_size and be in [1, 64]"
+                            : h->mode == S2D_MODE_TURN4  ? "s2d_rollout_policy: n_out must be 4 on a turning engine"
+                                                         : "s2d_rollout_policy: n_out must be 1 on a continuous (non-turning) engine");
+  if (net->activation != 0 && net->activation != 1) return fail(S2D_EINVAL, "s2d_rollout_policy: activation must be 0 (ReLU) or 1 (Tanh)");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->deterministic || (reinterpret_cast<uintptr_t>(net->deterministic) & 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: deterministic must be a non-NULL, 4-byte aligned device pointer");
+  if (h->mode != S2D_MODE_DISCRETE && (!net->log_std || (reinterpret_cast<uintptr_t>(net->log_std) & 3u)))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: a continuous engine needs a non-NULL, 4-byte aligned log_std buffer [n_out]");
+  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_policy: terminal_obs must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(logp) & 3u) return fail(S2D_EINVAL, "s2d_rollout_policy: logp must be 4-byte aligned");
+  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (out) {
+    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
+    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
+      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
+  }
+  DeviceGuard guard(h->device);
+  const int rc = s2d_internal_rollout_policy(h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride,
+                                             h->n, n_steps, net->hidden1, net->hidden2, na, net->activation, net->params,
+                                             h->mode == S2D_MODE_DISCRETE ? nullptr : net->log_std, net->deterministic, &ro,
+                                             terminal_obs, logp, &h->out, stream, h->kernel_name);
+  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_policy: the network does not fit the LDS of a workgroup");
+  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_policy: hipGetDevice or hipFuncSetAttribute failed");
   HIP_TRY(hipGetLastError());
   h->last_kernel = h->kernel_name;
   return S2D_OK;

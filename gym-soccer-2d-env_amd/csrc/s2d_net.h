@@ -17,11 +17,13 @@
 static constexpr int kWave = 64;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
-// J output tiles (jt0 .. jt0 + J - 1) of one layer for one 16-env tile: out[c][j] (LDS, pitch `op`) = (relu)(b[j] + sum_k W[j][k]
+// J output tiles (jt0 .. jt0 + J - 1) of one layer for one 16-env tile: out[c][j] (LDS, pitch `op`) = (act)(b[j] + sum_k W[j][k]
 // in[k]) for the tile's 16 envs c.  in_frag(s) = this lane's B word of k-step s.  J independent accumulators keep the matrix pipe
 // issuing (dependent latency 40 cycles against a 32-cycle issue); the k-steps go in groups of KU whose LDS reads are issued together.
-// All 64 lanes take part (MFMA).
-template <bool RELU, int J, int KU, typename InFrag>
+// All 64 lanes take part (MFMA).  ACT: the activation on the accumulators, S2D_ACT_FN_* (the callers that say true / false get
+// relu / none, as before; tanh_spec is the stochastic policy's, s2d_policy.hip).
+enum { S2D_ACT_FN_NONE = 0, S2D_ACT_FN_RELU = 1, S2D_ACT_FN_TANH = 2 };
+template <int ACT, int J, int KU, typename InFrag>
 S2D_DEV void layer_group(const float* __restrict__ wf, const float* __restrict__ bias, int jt0, int ksteps, InFrag in_frag,
                          float* __restrict__ out, int op, int lane) {
   const int g = lane >> 4, c = lane & 15;
@@ -47,21 +49,24 @@ S2D_DEV void layer_group(const float* __restrict__ wf, const float* __restrict__
   }
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    if (RELU) {
+    if (ACT == S2D_ACT_FN_RELU) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[j][r] = acc[j][r] > 0.0f ? acc[j][r] : 0.0f;   // relu: NaN and -0 -> +0
+    } else if (ACT == S2D_ACT_FN_TANH) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[j][r] = tanh_spec(acc[j][r]);
     }
     *reinterpret_cast<float4*>(out + c * op + 16 * (jt0 + j) + 4 * g) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
   }
 }
 // all m16 output tiles of one layer, four (then two, then one) at a time
-template <bool RELU, int KU, typename InFrag>
+template <int ACT, int KU, typename InFrag>
 S2D_DEV void layer_tile(const float* __restrict__ wf, const float* __restrict__ bias, int m16, int ksteps, InFrag in_frag,
                         float* __restrict__ out, int op, int lane) {
   int jt = 0;
-  for (; jt + 4 <= m16; jt += 4) layer_group<RELU, 4, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
-  if (jt + 2 <= m16) { layer_group<RELU, 2, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane); jt += 2; }
-  if (jt < m16) layer_group<RELU, 1, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
+  for (; jt + 4 <= m16; jt += 4) layer_group<ACT, 4, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
+  if (jt + 2 <= m16) { layer_group<ACT, 2, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane); jt += 2; }
+  if (jt < m16) layer_group<ACT, 1, KU>(wf, bias, jt, ksteps, in_frag, out, op, lane);
 }
 
 // exploration threshold of a device epsilon: eps >= 1 -> 2^32, eps > 0 -> (uint64)(eps 2^32), else (0, -x, NaN) 0

@@ -112,6 +112,13 @@ class S2DActorNet(C.Structure):
                 ('params', C.c_void_p), ('epsilon', C.c_void_p), ('noise', C.c_void_p)]
 
 
+class S2DPolicyNet(C.Structure):
+    """the caller's stochastic policy of s2d_rollout_policy (widths, outputs, activation 0 ReLU / 1 Tanh; device pointers of the
+    packed parameters, of log_std[n_out] (NULL on a discrete engine) and of the deterministic word)"""
+    _fields_ = [('hidden1', C.c_int32), ('hidden2', C.c_int32), ('n_out', C.c_int32), ('activation', C.c_int32),
+                ('params', C.c_void_p), ('log_std', C.c_void_p), ('deterministic', C.c_void_p)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -141,6 +148,10 @@ PROTOTYPES = (
     ('s2d_step_k', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
     ('s2d_rollout_qnet', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DQNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_actor', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DActorNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DPolicyNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p,
+                                     C.c_void_p)),
+    ('s2d_gae', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),
@@ -149,6 +160,8 @@ PROTOTYPES = (
     ('s2d_debug_eval', C.c_int, (C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)),
     ('s2d_debug_net_forward', C.c_int, (C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_char_p, C.c_void_p)),
+    ('s2d_debug_policy_head', C.c_int, (C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)),
 )
 
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,6 +1,7 @@
 """QNetActor: the device-side state of the fused epsilon-greedy actor (Engine.rollout_qnet, s2d_rollout_qnet in include/s2d.h).
 DeterministicActor: the same for the fused tanh actor of continuous and turning engines (Engine.rollout_actor,
-s2d_rollout_actor), SB3's DDPG / TD3 ``actor.mu`` with optional Gaussian action noise.
+s2d_rollout_actor), SB3's DDPG / TD3 ``actor.mu`` with optional Gaussian action noise.  StochasticActor: the sampled policy of
+on-policy collection (Engine.rollout_policy, s2d_rollout_policy): a categorical or diagonal-Gaussian head with log-probabilities.
 
 It owns ONE packed fp32 parameter buffer in torch's ``nn.Sequential(Linear, ReLU, Linear, ReLU, Linear).parameters()`` order
 (W1[H1][10], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A]) and a device epsilon scalar.  The kernel reads both when it runs, so a
@@ -244,6 +245,156 @@ class DeterministicActor:
         net.params = self.params.data_ptr()
         net.epsilon = self._eps.data_ptr()
         net.noise = self._noise.data_ptr()
+        return net
+
+
+def _policy_layers(module):
+    """(the three nn.Linear layers, activation 0 ReLU / 1 Tanh) of a stochastic policy: Linear-F-Linear-F-Linear with F = ReLU
+    or Tanh, both the same.  `module` is one nn.Module, or a list / tuple of modules read one after the other -- SB3's pair
+    ``[policy.mlp_extractor.policy_net, policy.action_net]``.  Identity / Flatten are skipped; mixed activations, any other
+    activation, a missing one or a fourth layer are refused: the kernel would silently act with a different function."""
+    mods = list(module) if isinstance(module, (list, tuple)) else [module]
+    leaves = [m for mod in mods for m in mod.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
+    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU)
+             else 'Tanh' if isinstance(m, torch.nn.Tanh) else type(m).__name__ for m in leaves]
+    for act, name in enumerate(('ReLU', 'Tanh')):
+        if kinds == ['Linear', name, 'Linear', name, 'Linear']:
+            return [leaves[0], leaves[2], leaves[4]], act
+    raise ValueError('the policy must be Linear-F-Linear-F-Linear (10 -> H1 -> H2 -> A) with F = ReLU or Tanh, the same twice, '
+                     f'got {"-".join(kinds) or "nothing"}')
+
+
+class StochasticActor:
+    """Packed parameters, device log_std and the deterministic word of a 10-H1-H2-A stochastic policy for Engine.rollout_policy
+    (s2d_rollout_policy): on-policy collection for PPO / A2C.
+
+    y = W3 f(W2 f(W1 x + b1) + b2) + b3 with f = ReLU or Tanh (``activation`` 'relu' / 'tanh'; Tanh is SB3's default for PPO's
+    MlpPolicy).  On a discrete engine y are the logits of a categorical policy (A = action_space_size <= 64); on a continuous
+    (A = 1) or turning (A = 4) engine the means of a diagonal Gaussian with the state-independent ``log_std`` [A] (SB3's
+    ``policy.log_std``).  The kernel samples, records the unclipped action and its log-probability, and hands the env the
+    clipped action.  ``deterministic = True`` switches to greedy actions (argmax / clipped mean).  The parameter buffer,
+    log_std and the deterministic word are device buffers written in place and read when the kernel runs, so a captured graph
+    acts with what they hold at replay: an evaluation pass is the collection graph with ``deterministic = True``."""
+
+    def __init__(self, hidden1=64, hidden2=64, n_out=16, activation='tanh', device='cuda:0', log_std=0.0, deterministic=False):
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in WIDTHS:
+                raise ValueError(f'{name} must be a multiple of 16 in [16, 128] (the weights live in LDS), got {w}')
+        if not 1 <= int(n_out) <= MAX_ACTIONS:
+            raise ValueError(f'n_out must be in [1, {MAX_ACTIONS}], got {n_out}')
+        if activation not in ('relu', 'tanh'):
+            raise ValueError(f"activation must be 'relu' or 'tanh', got {activation!r}")
+        self.hidden1, self.hidden2, self.n_out, self.activation = int(hidden1), int(hidden2), int(n_out), activation
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_out), dtype=torch.float32, device=self.device)
+        self._log_std = torch.zeros(self.n_out, dtype=torch.float32, device=self.device)
+        self._det = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._det_value = False
+        self.log_std = log_std
+        self.deterministic = deterministic
+        self._module = None
+        self._log_std_src = None
+
+    @classmethod
+    def from_module(cls, policy_net, log_std=None, device=None, deterministic=False):
+        """An actor shaped like `policy_net`, loaded from it.  Accepted: an nn.Module whose leaves are Linear-F-Linear-F-Linear
+        with F = ReLU or Tanh (a leading Flatten / Identity is skipped), or a list / tuple of modules that read so one after the
+        other: SB3's ``[model.policy.mlp_extractor.policy_net, model.policy.action_net]``.  log_std: None (zeros), a scalar,
+        [A] values, or a tensor / nn.Parameter that sync() reads again (SB3's ``model.policy.log_std``)."""
+        (l1, l2, l3), act = _policy_layers(policy_net)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=('relu', 'tanh')[act], device=dev,
+                    deterministic=deterministic)
+        actor.load_from(policy_net, log_std=log_std)
+        return actor
+
+    def shapes(self):
+        h1, h2, a = self.hidden1, self.hidden2, self.n_out
+        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
+
+    def load_from(self, policy_net, log_std=None):
+        """Validate `policy_net` against this actor (shapes and activation), remember it and `log_std` (if a tensor), and pack
+        them (sync())."""
+        layers, act = _policy_layers(policy_net)
+        if ('relu', 'tanh')[act] != self.activation:
+            raise ValueError(f'the policy\'s activation is {("relu", "tanh")[act]}, the actor\'s {self.activation}')
+        got = []
+        for lin in layers:
+            if lin.bias is None:
+                raise ValueError('every nn.Linear of the policy needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if tuple(got) != self.shapes():
+            raise ValueError(f'policy shapes {got} do not match the actor {list(self.shapes())}')
+        if log_std is not None:
+            if torch.is_tensor(log_std):
+                if log_std.numel() != self.n_out:
+                    raise ValueError(f'log_std must have {self.n_out} values, got {log_std.numel()}')
+                self._log_std_src = log_std
+            else:
+                self.log_std = log_std
+        self._module = policy_net
+        self.sync()
+        return self
+
+    def sync(self):
+        """Copy the loaded module's current parameters (and the remembered log_std tensor) into the device buffers: device
+        copies, no allocation of the buffers the kernel reads (capturable)."""
+        if self._module is None:
+            raise ValueError('no module loaded (load_from)')
+        srcs = []
+        for lin in _policy_layers(self._module)[0]:
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+            if self._log_std_src is not None:
+                self._log_std.copy_(self._log_std_src.detach().reshape(-1))
+        return self
+
+    @property
+    def log_std(self):
+        """the device log_std [A] the kernel reads"""
+        return self._log_std
+
+    @log_std.setter
+    def log_std(self, value):
+        """a scalar or [A] values, written in place"""
+        v = torch.as_tensor(value, dtype=torch.float32).detach().reshape(-1)
+        if v.numel() not in (1, self.n_out):
+            raise ValueError(f'expected a scalar or {self.n_out} values, got {v.numel()}')
+        self._log_std.copy_(v.expand(self.n_out))
+
+    @property
+    def deterministic(self):
+        return self._det_value
+
+    @deterministic.setter
+    def deterministic(self, value):
+        """Written in place into the device word the kernel reads (stream-ordered on torch's current stream)."""
+        self._det_value = bool(value)
+        self._det.fill_(int(self._det_value))
+
+    @property
+    def deterministic_tensor(self):
+        return self._det
+
+    def snapshot(self, deterministic=None):
+        """A frozen copy: a new actor of the same shape with its own parameters, log_std and deterministic word (the old policy
+        of a PPO update, an evaluation copy).  It has no module: later sync() calls of the original do not touch it."""
+        snap = type(self)(self.hidden1, self.hidden2, self.n_out, activation=self.activation, device=self.device,
+                          deterministic=self._det_value if deterministic is None else deterministic)
+        snap.params.copy_(self.params)
+        snap._log_std.copy_(self._log_std)
+        return snap
+
+    def c_struct(self):
+        net = _capi.S2DPolicyNet()
+        net.hidden1, net.hidden2, net.n_out = self.hidden1, self.hidden2, self.n_out
+        net.activation = 1 if self.activation == 'tanh' else 0
+        net.params = self.params.data_ptr()
+        net.log_std = self._log_std.data_ptr()
+        net.deterministic = self._det.data_ptr()
         return net
 
 

@@ -216,14 +216,14 @@ class Engine:
     _QNET_RECORD = {'obs': (torch.float32, (S2D_OBS_DIM,)), 'action': (torch.int32, ()), 'reward': (torch.float32, ()),
                     'done': (torch.uint8, ()), 'result': (torch.uint8, ()), 'terminal_obs': (torch.float32, (S2D_OBS_DIM,))}
 
-    def _actor_record(self, entry, record, T, out, with_obs, terminal_obs):
-        """The checked, cached record of a fused-actor launch (rollout_qnet / rollout_actor): (out, S2DRollout, terminal_obs
-        pointer).  `record` = {name: (dtype, trailing shape)}; `out` pointer blocks are cached as in rollout()."""
+    def _actor_record(self, entry, record, T, out, with_obs, terminal_obs, logp=False):
+        """The checked, cached record of a fused-actor launch (rollout_qnet / rollout_actor / rollout_policy): (out, S2DRollout,
+        terminal_obs pointer).  `record` = {name: (dtype, trailing shape)}; `out` pointer blocks are cached as in rollout()."""
         n = self.num_envs
         fresh = out is None
         if fresh:
-            out = self.alloc_rollout(T, with_obs=with_obs, terminal_obs=terminal_obs)
-        names = ('obs', 'action', 'reward', 'done', 'result', 'terminal_obs')
+            out = self.alloc_rollout(T, with_obs=with_obs, terminal_obs=terminal_obs, logp=logp)
+        names = tuple(k for k in ('obs', 'action', 'reward', 'done', 'result', 'terminal_obs', 'logp') if k in record)
         cached = None if fresh else self._ro_cache.get((entry, id(out)))
         key = tuple(None if out.get(k) is None else out[k].data_ptr() for k in names)
         if cached is None or cached[0] != key or cached[1] < T:
@@ -237,7 +237,7 @@ class Engine:
                             or v.shape[0] < T or v.shape[1] != n or tuple(v.shape[2:]) != trail):
                         raise ValueError(f"{entry} buffer {name!r} must be a contiguous {dt} [T>={T},{n}"
                                          f"{''.join(',' + str(d) for d in trail)}] tensor on {self.device}")
-                    if name != 'terminal_obs':
+                    if name not in ('terminal_obs', 'logp'):
                         setattr(ro, name, v.data_ptr())
                     t_min = v.shape[0] if t_min is None else min(t_min, v.shape[0])
             term = out.get('terminal_obs')
@@ -290,6 +290,35 @@ class Engine:
         self._keep = (actor, out)
         return out
 
+    def rollout_policy(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False, logp=True):
+        """n_steps fused cycles in one launch whose actions are SAMPLED in-kernel from `actor`'s (soccer2d_amd.actor.
+        StochasticActor) policy on the envs' own observations: categorical on a discrete engine, diagonal Gaussian on a continuous
+        or turning one (s2d_rollout_policy; on-policy collection for PPO / A2C).  Returns the record dict of rollout() -- action
+        int32 [T,N], or float32 [T,N,1] / [T,N,4]: the UNCLIPPED sample (the env received it clipped to [-1, 1]) -- plus 'logp'
+        float32 [T,N], the log-probability of the recorded action (logp=True, or a caller `out` holding 'logp').
+        actor.deterministic = True acts greedily in the same launch.  terminal_obs, graph capture and `out` caching as in
+        rollout_qnet()."""
+        T = int(n_steps)
+        if T < 1:
+            raise ValueError('rollout_policy needs n_steps >= 1')
+        net = actor.c_struct()
+        if actor.device != self.device:
+            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        t = self.cfg.task
+        a = int(t.action_space_size) if not t.use_continuous_action else 4 if t.use_turning else 1
+        if actor.n_out != a:
+            raise ValueError(f'this engine needs a policy with n_out = {a}, got {actor.n_out}')
+        record = dict(self._QNET_RECORD, logp=(torch.float32, ()))
+        if t.use_continuous_action:
+            record['action'] = (torch.float32, (a,))
+        out, ro, term = self._actor_record('rollout_policy', record, T, out, with_obs, terminal_obs, logp=logp)
+        lp = out.get('logp')
+        rc = self.lib.s2d_rollout_policy(self._h, T, C.byref(net), C.byref(ro), term, None if lp is None else C.c_void_p(lp.data_ptr()),
+                                         self._stream())
+        _capi.check(self.lib, rc, 's2d_rollout_policy')
+        self._keep = (actor, out)
+        return out
+
     def step_k(self, k, actions=None, out=None):
         """k cycles of the per-step API in ONE launch (s2d_step_k; 1 <= k <= 64): for a learner that holds its actions for k steps
         ahead (action repeat, open-loop chunks).  actions [k, N, ...] as for rollout() (None = in-kernel random policy); returns the
@@ -309,12 +338,13 @@ class Engine:
         self._keep = (keep, out)
         return out
 
-    def alloc_rollout(self, T, with_obs=True, slab=False, fields=None, terminal_obs=False):
+    def alloc_rollout(self, T, with_obs=True, slab=False, fields=None, terminal_obs=False, logp=False):
         """Caller-owned rollout buffers for `rollout(..., out=)`.  slab=True carves the fields out of ONE contiguous
         uint8 tensor (256-byte aligned fields; returned under the key '_slab'), so that a rollout record travels in a
         single collective (dist.all_gather_rollout) without a packing copy: the kernel writes straight into the slab.
         fields (with slab=True): the names that go into the slab -- what travels --; the others are plain local tensors.
-        terminal_obs=True adds float32 [T,N,10] 'terminal_obs' (rollout_qnet's record of the observations episodes ended on)."""
+        terminal_obs=True adds float32 [T,N,10] 'terminal_obs' (rollout_qnet's record of the observations episodes ended on);
+        logp=True adds float32 [T,N] 'logp' (rollout_policy's log-probabilities)."""
         n, t, dev = self.num_envs, self.cfg.task, self.device
         slab_fields = None if fields is None else set(fields)
         if slab_fields is not None and not slab:
@@ -324,6 +354,8 @@ class Engine:
         fields += [('action', act_dt, act_trail), ('reward', torch.float32, ()), ('done', torch.uint8, ()), ('result', torch.uint8, ())]
         if terminal_obs:
             fields.append(('terminal_obs', torch.float32, (S2D_OBS_DIM,)))
+        if logp:
+            fields.append(('logp', torch.float32, ()))
         if not slab:
             out = {name: torch.empty((T, n) + trail, dtype=dt, device=dev) for name, dt, trail in fields}
             out.setdefault('obs', None)

@@ -13,7 +13,7 @@ first observation of its next episode; the last one of the old episode is in
 import torch
 
 from . import _capi
-from .actor import DeterministicActor
+from .actor import DeterministicActor, StochasticActor
 from .engine import Engine, make_config
 from .spaces import reach_ball_spaces
 from .state_view import StateView, world_model_tensors
@@ -58,10 +58,13 @@ class Soccer2DVecEnv:
     def rollout(self, n_steps, actions=None, out=None, with_obs=True, policy=None, terminal_obs=False):
         """T fused steps.  policy=None: `actions` (or the in-kernel random policy); policy=QNetActor: the actor's epsilon-greedy
         actions, evaluated in-kernel (Engine.rollout_qnet; terminal_obs=True records the observations episodes ended on);
-        policy=DeterministicActor: its tanh policy with exploration and action noise (Engine.rollout_actor)."""
+        policy=DeterministicActor: its tanh policy with exploration and action noise (Engine.rollout_actor);
+        policy=StochasticActor: actions sampled from its categorical / Gaussian policy, with 'logp' (Engine.rollout_policy)."""
         if policy is not None:
             if actions is not None:
                 raise ValueError('give either actions or policy, not both')
+            if isinstance(policy, StochasticActor):
+                return self.engine.rollout_policy(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
             if isinstance(policy, DeterministicActor):
                 return self.engine.rollout_actor(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
             return self.engine.rollout_qnet(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)

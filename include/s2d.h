@@ -18,6 +18,8 @@
  *                              (T fused steps, epsilon-greedy actions of the caller's Q-network, in-kernel)
  *   s2d_rollout_actor          DDPG / TD3 actor.mu + NormalActionNoise inside SB3's collect_rollouts
  *                              ddpg_stable_baselines3.py (T fused steps, the caller's tanh policy, in-kernel)
+ *   s2d_rollout_policy         PPO / A2C: sampling from the policy's distribution + log_prob inside collect_rollouts
+ *   s2d_gae                    RolloutBuffer.compute_returns_and_advantage
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -207,6 +209,20 @@ typedef struct S2DActorNet {
   const float *noise;
 } S2DActorNet;
 
+/* The caller's stochastic policy for s2d_rollout_policy (DESIGN.md sections 4, 5): y = W3 f(W2 f(W1 x + b1) + b2) + b3, f =
+ * relu (activation = 0) or tanh_spec (1, SB3's default for PPO's MlpPolicy); y = the logits of a categorical policy on a discrete
+ * engine (n_out = action_space_size, 1 .. 64), the means of a diagonal Gaussian on a continuous (n_out = 1) or turning (4) one.
+ * hidden1 / hidden2 in {16, 32, ..., 128}.  params as S2DQNet's (W3[n_out][H2], b3[n_out]), 16-byte aligned.  log_std: fp32
+ * device buffer [n_out], SB3's state-independent log_std parameter (may be NULL on a discrete engine).  deterministic: one
+ * uint32 device word, 0 = sample, non-zero = act greedily.  params, log_std and deterministic are read when the kernel runs (a
+ * captured graph acts with what they hold at replay: an evaluation pass is the collection graph with the word set).  */
+typedef struct S2DPolicyNet {
+  int32_t hidden1, hidden2, n_out, activation;
+  const float *params;
+  const float *log_std;
+  const uint32_t *deterministic;
+} S2DPolicyNet;
+
 /* Derived protobuf-mirroring fields that are not plain state words (row T1).  Each array
  * is [N]; NULL pointers are skipped.                                                       */
 typedef struct S2DWorldModel {
@@ -284,6 +300,47 @@ int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet *net, const S2DRoll
  * 16, noise_kind not in {0, 1}, NULL or misaligned params / epsilon / noise (noise only with kind 1), n_steps < 1, a network
  * that does not fit the LDS. */
 int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+/* n_steps >= 1 cycles fused in ONE launch (every action mode) whose action at every cycle is SAMPLED from the caller's policy
+ * on the env's observation, with the log-probability of the action taken recorded: on-policy collection (PPO / A2C).  Per env
+ * and step at its policy_step k (advanced by one every step); every line one fixed fp32 operation:
+ *   network   every unit an fmaf chain from its bias in ascending k; hidden units then relu(v) = v > 0 ? v : +0 or
+ *             tanh_spec(v); layer 1 runs over k = 0 .. 11 with x_10 = x_11 = 0 against zero weights (two fmaf(0, 0, acc): an
+ *             accumulator of -0 becomes +0, visible only through tanh_spec); the output layer is linear.
+ *   discrete  m = max of y[0 .. A-1] by the argmax scan of s2d_rollout_qnet (ascending; a NaN never replaces the best), g = its
+ *             index; e_a = exp_spec(y_a - m); S = e_0, S += e_a for ascending a; u = (w >> 8) 2^-24 with w = word k & 3 of
+ *             Philox block 4 of stream POLICY at counter k >> 2; target = u * S; c = 0, the action is the first a with
+ *             (c += e_a) > target, or g if there is none (u * S rounds up to S; non-finite logits);
+ *             logp = (y_a - m) - log_spec(S).  The action is in [0, A) for every input; non-finite logits are otherwise out
+ *             of contract.
+ *   continuous / turning   sigma_j = exp_spec(log_std_j); z from Box-Muller on Philox block 3 of stream POLICY, laid out as
+ *             s2d_rollout_actor's (turning: z0..z3 of the block at counter k; continuous: z_{k & 3} of the block at counter
+ *             k >> 2; s2d_debug_eval op 15); a_j = fmaf(sigma_j, z_j, y_j), RECORDED UNCLIPPED (what SB3's rollout buffer
+ *             stores); the env receives clip(a_j, -1, 1) = a < -1 ? -1 : a > 1 ? 1 : a through the mode's action map;
+ *             logp = t_0 (+ t_1 + t_2 + t_3 in ascending j), t_j = fmaf(-0.5f * z_j, z_j, -log_std_j) - 0.91893853f.
+ *   deterministic != 0   greedy: the action is g (discrete) or a_j = clip(y_j, -1, 1) (recorded so), logp as above with
+ *             z_j = 0; no Philox draw.  There is no epsilon in this path.
+ * `out` as for s2d_rollout (action = int32[T][N] | float[T][N][1] | float[T][N][4]); terminal_obs as for s2d_rollout_qnet;
+ * logp (may be NULL) = float[T][N].  policy_step advances by n_steps; the state, the statistics and the per-step outputs
+ * are left as s2d_rollout_actor leaves them.  A discrete engine with deterministic != 0 and activation 0 is
+ * s2d_rollout_qnet with epsilon = 0 bit for bit.  Rejected without a launch, the state untouched: n_out that is not the
+ * engine's (action_space_size | 1 | 4) or > 64, widths not in {16, ..., 128} step 16, activation not in {0, 1}, NULL or
+ * misaligned params / deterministic, log_std NULL or misaligned on a continuous or turning engine, n_steps < 1, a network that
+ * does not fit the LDS. */
+int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet *net, const S2DRollout *out, float *terminal_obs, float *logp,
+                       void *stream);
+/* Generalised advantage estimation over a time-major record, one backward scan per env (no engine handle: raw device
+ * pointers, any stream of the current device).  ENGINE-INDEPENDENT: it assumes nothing of reach-ball; the 11v11 records have
+ * the same [T][N] layout (N = envs, or envs x agents flattened).  Inputs: reward[T][N], done[T][N] (uint8), value[T][N] = V of
+ * the observation action t was chosen from, last_value[N] = V of the observation after step T - 1; optionally result[T][N]
+ * (uint8) with terminal_value[T][N] = V of the terminal observation (both or neither).  Outputs advantage[T][N], ret[T][N]
+ * (they must not overlap the inputs).  fp32, in this order, next_v = last_value, gae = 0, for t = T-1 .. 0:
+ *   r = reward[t]; where result[t] == S2D_RESULT_TIMEOUT (and terminal values are given) r = fmaf(gamma, terminal_value[t], r)
+ *   (SB3's time-limit bootstrap); nt = done[t] ? 0 : 1; delta = fmaf(gamma * nt, next_v, r) - value[t];
+ *   gae = fmaf((gamma * lam) * nt, gae, delta); advantage[t] = gae; ret[t] = gae + value[t]; next_v = value[t].
+ * S2D_EINVAL without a launch: n_steps < 1, n_envs < 1, result without terminal_value or the reverse, non-finite gamma / lam,
+ * NULL or misaligned arrays. */
+int s2d_gae(int n_steps, int64_t n_envs, const float *reward, const uint8_t *done, const float *value, const float *last_value,
+            const uint8_t *result, const float *terminal_value, float gamma, float lam, float *advantage, float *ret, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
@@ -334,6 +391,14 @@ int s2d_debug_eval(int op, const void *in_dev, void *out_dev, int64_t n, void *s
  * NULL or misaligned pointers. */
 int s2d_debug_net_forward(int h1, int h2, int na, const void *params_dev, const void *obs_dev, int64_t n, void *y_dev,
                           void *greedy_dev, char *name, void *stream);
+/* diagnostic: the head of s2d_rollout_policy alone, on caller logits or means, so that its edge cases can be compared bit for
+ * bit with the spec without running a rollout.  mode: 0 discrete (n_out = A in 1..64), 1 continuous (n_out = 1), 2 turning
+ * (n_out = 4).  y_dev = float[n][n_out]; log_std_dev = float[n_out] (may be NULL with mode 0); gid_dev = uint64[n] global env
+ * ids; k_dev = uint32[n] policy steps; seed = the Philox key; deterministic as the device word of S2DPolicyNet.  action_dev =
+ * int32[n] (mode 0) or float[n][n_out] <- the recorded action; logp_dev = float[n].  S2D_EINVAL without a launch: a mode or
+ * n_out outside the above, n not in 1..2^31 - 1, NULL or misaligned pointers. */
+int s2d_debug_policy_head(int mode, int n_out, const void *y_dev, const void *log_std_dev, const void *gid_dev, const void *k_dev,
+                          uint64_t seed, int deterministic, int64_t n, void *action_dev, void *logp_dev, void *stream);
 
 #ifdef __cplusplus
 }
