@@ -31,6 +31,7 @@
 
 #include "s2d_device.h"
 #include "s2d_net.h"
+#include "s2d_head.h"
 #include "s2d_see_row.h"
 #include "../../include/s2d_match.h"
 
@@ -141,6 +142,7 @@ static_assert(sizeof(MParamsCtl<MParamsNoIll>) == sizeof(MParams), "MParamsCtl a
 template <class B> struct MParamsNet : B {};   // ... and as the network kernels read it
 static_assert(sizeof(MParamsNet<MParamsNoIll>) == sizeof(MParams), "MParamsNet adds no data");
 template <class B> struct MParamsSee : B {};   // ... and as the see-network kernels read it
+template <class B> struct MParamsPol : B {};   // ... and as the policy-network kernels read it
 static_assert(sizeof(MParamsSee<MParamsNoIll>) == sizeof(MParams), "MParamsSee adds no data");
 // The same physics and rules with the SCHEDULE of the match -- how long things last, how many there are of them -- as per-engine
 // words: a learner's engine with short halves, no extra time or other waits differs from the stock configuration in these words
@@ -1510,8 +1512,19 @@ struct MNet {
   MNetOpp opp;
 };
 struct MNetArg { MNet net; MAgentTab tab; };   // kernel argument of the NET instantiations (with their MCtl)
+// Policy slots (s2d_match_set_policy_network): the words a pass needs beyond MNet's, [0] the first pass, [1] the second.
+struct MPol {
+  int kind[2];                             // 0: a Q-network (argmax here, epsilon in the body), 1: a stochastic policy (the head below)
+  int act[2];                              // hidden activation of the pass: 0 relu, 1 tanh_spec
+  const uint32_t* det[2];                  // a policy's device word (read once per launch): != 0 -> greedy
+  float* logp;                             // [T][N][22] or NULL
+};
+struct MPolArg { MNet net; MAgentTab tab; MPol pol; };   // kernel argument of the POL instantiations: an MNetArg, then the policy words
 constexpr int kNetWaveWords = 16 * kNetRowPitch + 16 * kNetHidPitch + 2 * (int)(sizeof(MAObsFacts) / 4) + kNetIdxWords;
 static_assert((2 * sizeof(MAObsFacts)) % 16 == 0 && (16 * kNetRowPitch + 16 * kNetHidPitch) % 4 == 0, "16-byte aligned LDS parts");
+// POL: one log-probability word beside each index word.  4 waves x 64 words = 1 024 B of the 1 344 B that two 64-64-64 networks
+// leave beside the stock kernels: that pair stays staged there.
+constexpr int kPolWaveWords = kNetWaveWords + kNetIdxWords;
 
 S2D_DEV float* m_net_lds() {                           // dynamic LDS: [W2 | W3 | b1 | b2 | b3] of each network, then kNetWaveWords per wave
   extern __shared__ __attribute__((aligned(16))) float net_smem[];
@@ -1559,18 +1572,81 @@ S2D_DEV void m_net_tile_forward(const float* __restrict__ w1, const float* __res
   wave_fence();
 }
 
+// The same tile through the three layers of a network of a POL instantiation, hidden activation ACT (both are compiled in, the
+// pass says which); the logits stay in `hid`.  ACT relu is m_net_tile_forward's forward word for word.
+template <int ACT>
+S2D_DEV void m_pol_tile_layers(const float* __restrict__ w1, const float* __restrict__ w2s, int h1, int h2, int na16, float* tile,
+                               float* hid, int lane) {
+  const int gq = lane >> 4, c = lane & 15;
+  const float* const w2 = w2s;
+  const float* const w3 = w2 + (h2 / 16) * (h1 / 4) * 64;
+  const float* const b1 = w3 + (na16 / 16) * (h2 / 4) * 64;
+  const float* const b2 = b1 + h1;
+  const float* const b3 = b2 + h2;
+  const float* const x = tile + c * kNetRowPitch;
+  layer_tile<ACT, 4>(w1, b1, h1 / 16, kNetK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<ACT, 4>(w2, b2, h2 / 16, h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<S2D_ACT_FN_NONE, 4>(w3, b3, na16 / 16, h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid, kNetHidPitch, lane);
+  wave_fence();
+}
+// The pass's head on the tile's logits.  A Q-network pass (pol == false): m_net_tile_forward's argmax.  A policy pass: the head is
+// categorical_head (s2d_head.h), run by the tile's 16 head lanes, one row each, on the logits where layer 3 left them -- the next
+// tile overwrites them, and the slot's own lane is in another part of the wave.  So the head lane derives whose row it holds:
+// tile row r = 2 j + half is the j-th slot of `tile_mask` (the tile's slots, a uniform word) of the match in that half, whose id
+// and tick it takes from that half's first lane (gl, gh, tick: every lane's own match; shuffled here, not once per cycle, so
+// that they are not live across the layers).  It draws the slot's ST_NET block itself and takes word z; the sums stay the
+// sequential ones of the spec.  Rows past `rn` pairs are pads: no head.
+template <class P>
+S2D_DEV void m_pol_tile_head(const P& p, int nact, const float* hid, int* idx, float* lp, int lane, bool pol, bool det,
+                             uint32_t tile_mask, int rn, uint32_t gl, uint32_t gh, uint32_t tick) {
+  uint32_t hgl = 0u, hgh = 0u, htick = 0u;
+  if (pol) {                                               // (uniform; all 64 lanes shuffle)
+    const int src = (lane & 1) * kHalf;
+    hgl = (uint32_t)__shfl((int)gl, src, 64); hgh = (uint32_t)__shfl((int)gh, src, 64); htick = (uint32_t)__shfl((int)tick, src, 64);
+  }
+  if (lane < 16) {
+    const float* q = hid + lane * kNetHidPitch;
+    if (!pol) {          // best = 0; for a = 1 .. K-1: if (q[a] > q[best]) best = a  (ties: lowest index; a NaN never replaces the best)
+      int best = 0;
+      float bv = q[0];
+      for (int a = 1; a < nact; ++a) {
+        const float v = q[a];
+        if (v > bv) { bv = v; best = a; }
+      }
+      idx[lane] = best;
+    } else if ((lane >> 1) < rn) {
+      uint32_t m = tile_mask;
+      for (int j = 0; j < (lane >> 1); ++j) m &= m - 1u;
+      const int slot = __builtin_ctz(m);
+      uint32_t w = 0u;
+      if (!det) w = m_draw(p, hgl, hgh, htick, S2D_ST_NET, (uint32_t)slot).z;
+      float logp;
+      idx[lane] = categorical_head(q, nact, det, w, logp);
+      lp[lane] = logp;
+    }
+  }
+  wave_fence();
+}
+
 // One cycle's network step of the wave, from the start-of-cycle state (o, g, r): the rows, their record, the forward pass and
 // the argmax.  Returns the greedy index of this lane's slot (meaningful for network slots).  All 64 lanes, uniform control flow.
-template <class P>
-S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGame& g, const MRare& r, int l, int half, bool valid,
-                         int64_t rec_row) {
+// POL (NA = MPolArg): the pass's kind, activation and `det` bit (bit 0 the first pass, bit 1 the second) pick the forward above;
+// gl, gh: this lane's match id; returns an MPick: the index and its log-probability (policy slots; 0 elsewhere).
+struct MPick { int idx; float logp; };
+template <class P, class NA>
+S2D_DEV auto m_net_greedy(const P& p, const NA& na, const MObj& o, const MGame& g, const MRare& r, int l, int half, bool valid,
+                          int64_t rec_row, uint32_t det = 0u, uint32_t gl = 0u, uint32_t gh = 0u) {
+  constexpr bool POL = std::is_same<NA, MPolArg>::value;
   const MNet& net = na.net;
   const int lane = threadIdx.x & 63;
   float* const shared = m_net_lds();
-  float* const tile = shared + net.shared_words + net.opp.shared_words + (threadIdx.x >> 6) * kNetWaveWords;
+  float* const tile = shared + net.shared_words + net.opp.shared_words + (threadIdx.x >> 6) * (POL ? kPolWaveWords : kNetWaveWords);
   float* const hid = tile + 16 * kNetRowPitch;
   MAObsFacts* const facts = reinterpret_cast<MAObsFacts*>(hid + 16 * kNetHidPitch);
   int* const gidx = reinterpret_cast<int*>(facts + 2);
+  float* const glp = reinterpret_cast<float*>(gidx + kNetIdxWords);   // (POL only: the words kPolWaveWords adds)
   MAgentIn in{};
   if (l <= BALL) { in.x = o.x; in.y = o.y; in.vx = o.vx; in.vy = o.vy; }
   if (l < NP) {
@@ -1598,6 +1674,7 @@ S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGa
     const int nrows = __builtin_popcount(rest);
     for (int nt = 0; 8 * nt < nrows; ++nt) {
       const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
+      [[maybe_unused]] const uint32_t tile_mask = rest;    // (POL: its lowest rn bits are this tile's slots)
       for (int i = lane; i < (16 - 2 * rn) * (kNetRowPitch / 4); i += 64)   // pad rows of the last tile
         reinterpret_cast<float4*>(tile + 2 * rn * kNetRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       for (int j = 0; j < rn; ++j) {
@@ -1612,20 +1689,39 @@ S2D_DEV int m_net_greedy(const P& p, const MNetArg& na, const MObj& o, const MGa
         }
       }
       wave_fence();
-      if (forward) {
+      if constexpr (POL) {
+        if (forward) {
+          const bool pol = (second ? na.pol.kind[1] : na.pol.kind[0]) != 0, pdet = ((second ? det >> 1 : det) & 1u) != 0u;
+          const bool tanh_act = (second ? na.pol.act[1] : na.pol.act[0]) != 0;
+          const auto run = [&](const float* __restrict__ w2s) __attribute__((always_inline)) {   // (inlined per address space, as below)
+            if (tanh_act) m_pol_tile_layers<S2D_ACT_FN_TANH>(w1, w2s, h1, h2, na16, tile, hid, lane);
+            else m_pol_tile_layers<S2D_ACT_FN_RELU>(w1, w2s, h1, h2, na16, tile, hid, lane);
+          };
+          if (staged) run(shared + (second ? net.shared_words : 0));
+          else run(w1 + h1 / 16 * kNetK1 * 64);
+          m_pol_tile_head(p, nact, hid, pidx + 16 * nt, glp + (pidx - gidx) + 16 * nt, lane, pol, pdet, tile_mask, rn, gl, gh,
+                          (uint32_t)g.tick);
+        }
+      } else if (forward) {
         if (staged) m_net_tile_forward(w1, shared + (second ? net.shared_words : 0), h1, h2, nact, na16, tile, hid, pidx + 16 * nt, lane);
         else m_net_tile_forward(w1, w1 + h1 / 16 * kNetK1 * 64, h1, h2, nact, na16, tile, hid, pidx + 16 * nt, lane);
       }
     }
   }
   int greedy = 0;
+  [[maybe_unused]] float lp = 0.0f;
   if (l < NP) {                                          // the slot's place among its own pass's rows
     const uint32_t below = (1u << l) - 1u;
     if ((net.net_mask >> l) & 1u) greedy = gidx[2 * __builtin_popcount(first_rows & below) + half];
     else if ((net.opp.mask >> l) & 1u) greedy = gidx[16 * first_tiles + 2 * __builtin_popcount(net.opp.mask & below) + half];
+    if constexpr (POL) {
+      if (((net.net_mask >> l) & 1u) && na.pol.kind[0]) lp = glp[2 * __builtin_popcount(first_rows & below) + half];
+      else if (((net.opp.mask >> l) & 1u) && na.pol.kind[1]) lp = glp[16 * first_tiles + 2 * __builtin_popcount(net.opp.mask & below) + half];
+    }
   }
   wave_fence();
-  return greedy;
+  if constexpr (POL) return MPick{greedy, lp};
+  else return greedy;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1748,6 +1844,7 @@ template <bool CTL, bool NET = false, class P, class TY, class NA = MNetArg>
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
                                 const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr) {
   constexpr bool SEE = NET && std::is_same<NA, MSeeArg>::value;
+  constexpr bool POL = NET && std::is_same<NA, MPolArg>::value;   // policy slots: an instantiation of its own (the NET ones keep their code)
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
@@ -1797,7 +1894,20 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   uint64_t net_thr = 0;
   uint32_t net_slots = 0u, net_k = 0u;                     // NET: the slots on a network; this lane's network: its K and table
   const float* net_tab = nullptr;
-  if constexpr (NET) {
+  [[maybe_unused]] uint32_t pol_det = 0u;                  // POL: the passes' deterministic words, read once per launch like epsilon
+  if constexpr (POL) {
+    const MPol& pl = nin->pol;
+    if (pl.kind[0]) pol_det |= *pl.det[0] != 0u ? 1u : 0u;
+    if (pl.kind[1]) pol_det |= *pl.det[1] != 0u ? 2u : 0u;
+    // a policy has no epsilon (its pointer is NULL): the thresholds below are read for the Q-network passes only
+    net_thr = nin->net.net_mask && !pl.kind[0] ? explore_threshold(*nin->net.epsilon) : 0;
+    net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
+    if (nin->net.opp.mask != 0u) {
+      const uint64_t thr2 = pl.kind[1] ? 0 : explore_threshold(*nin->net.opp.epsilon);
+      net_slots |= nin->net.opp.mask;
+      if ((nin->net.opp.mask >> l) & 1u) { net_thr = thr2; net_k = (uint32_t)nin->net.opp.na; net_tab = nin->net.opp.table; }
+    }
+  } else if constexpr (NET) {
     net_thr = nin->net.net_mask ? explore_threshold(*nin->net.epsilon) : 0;   // (records only: no network)
     net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
     if constexpr (!SEE) {
@@ -1832,11 +1942,27 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       int nidx = -1;                                       // NET: the network's index of this slot, -1 = not a network slot
       if constexpr (NET) {
         int greedy;
+        [[maybe_unused]] float lp = 0.0f;
         if constexpr (SEE) greedy = m_see_greedy(*nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec);
+        else if constexpr (POL) {
+          const MPick pick = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec, pol_det, gl, gh);
+          greedy = pick.idx; lp = pick.logp;
+        }
         else greedy = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec);
         if (l < NP && ((net_slots >> l) & 1u)) {           // explore: word x < thr, then the index is word y's draw below K
-          const U4 w = m_draw(p, gl, gh, (uint32_t)g.tick, S2D_ST_NET, (uint32_t)l);
-          nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, net_k) : greedy;
+          bool pol_lane = false;                           // POL: the slot is on a policy: its head has sampled (word z of this block)
+          if constexpr (POL)
+            pol_lane = (nin->pol.kind[0] && ((nin->net.net_mask >> l) & 1u)) || (nin->pol.kind[1] && ((nin->net.opp.mask >> l) & 1u));
+          if (pol_lane) {
+            nidx = greedy;
+          } else {
+            const U4 w = m_draw(p, gl, gh, (uint32_t)g.tick, S2D_ST_NET, (uint32_t)l);
+            nidx = (uint64_t)w.x < net_thr ? rnd_below(w.y, net_k) : greedy;
+          }
+        }
+        if constexpr (POL) {
+          // (wave-uniform pointer; 0.0f for every slot that is not on a policy)
+          if (nin->pol.logp && valid && l < NP) nin->pol.logp[((int64_t)t * n + e) * NP + l] = lp;
         }
         if (nin->net.net_index && valid && l < NP) nin->net.net_index[((int64_t)t * n + e) * NP + l] = nidx;
       }
@@ -1925,22 +2051,29 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // holds it, so these instantiations have the register file of one wave per SIMD.
 // SEE: the NET instantiations whose second extra argument is an MSeeArg -- the see network, a family of its own (the existing
 // instantiations keep their template and kernel arguments).
+// POL: the NET instantiations whose second extra argument is an MPolArg -- policy slots, likewise a family of its own: a launch
+// takes one only when a role holds a policy network, so the NET kernels and their LDS plan are what they were.
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeeArg&) { return c; }
+S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MPolArg&) { return c; }
 S2D_DEV const MNetArg* m_net_arg() { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&) { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
 S2D_DEV const MSeeArg* m_net_arg(const MCtl&, const MSeeArg& a) { return &a; }
+S2D_DEV const MPolArg* m_net_arg(const MCtl&, const MPolArg& a) { return &a; }
 template <class... A> struct MIsSee : std::false_type {};
 template <> struct MIsSee<MCtl, MSeeArg> : std::true_type {};
+template <class... A> struct MIsPol : std::false_type {};
+template <> struct MIsPol<MCtl, MPolArg> : std::true_type {};
 template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, bool NET = false, class... CtlArg>
 __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
                                                                      const float* __restrict__ actions, MRoll ro, CtlArg... ctl_arg) {
   static_assert(sizeof...(CtlArg) == (NET ? 2 : CTL ? 1 : 0), "the CTL instantiations take an MCtl, NET ones an MNetArg too, the others nothing more");
   static_assert(!NET || CTL, "network slots come with the controller table");
   constexpr bool SEE = MIsSee<CtlArg...>::value;
+  constexpr bool POL = MIsPol<CtlArg...>::value;
   const MCtl ctl = m_ctl_arg(ctl_arg...);
   const auto* const nin = m_net_arg(ctl_arg...);
   __shared__ float4 pos_tile[kEnvsPerBlock][kTileSlots];
@@ -1984,8 +2117,9 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
     // instantiation of theirs.  Helpers shared with the CTL kernels were optimised differently in the kernels without them.
     // The NET kernels likewise (sharing the CTL kernels' type changed those kernels' code), and the SEE kernels.
     using PBase = std::conditional_t<ILL, MParams, MParamsNoIll>;
+    using PBlockNet = std::conditional_t<POL, MParamsPol<PBase>, MParamsNet<PBase>>;
     using PBlock = std::conditional_t<SEE, MParamsSee<PBase>,
-                                      std::conditional_t<NET, MParamsNet<PBase>, std::conditional_t<CTL, MParamsCtl<PBase>, PBase>>>;
+                                      std::conditional_t<NET, PBlockNet, std::conditional_t<CTL, MParamsCtl<PBase>, PBase>>>;
     __shared__ PBlock p_lds;
     static_assert(sizeof(MParams) / 4 <= kMBlock, "one thread per parameter word");
     if (threadIdx.x < sizeof(MParams) / 4)
@@ -2076,6 +2210,10 @@ struct S2DMatchEngine {
   S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time)
   bool has_opp = false;                                // s2d_match_set_opponent_network installed a second network (NET kernels, a pass of its own)
   S2DMatchNet opp{};                                   // ... its pointers
+  // s2d_match_set_policy_network: a role that holds a stochastic policy keeps it in the same S2DMatchNet (epsilon NULL), plus:
+  bool net_pol = false, opp_pol = false;               // the role's network is a policy: launches use the POL kernels
+  int net_act = 0, opp_act = 0;                        // ... its hidden activation (0 relu, 1 tanh)
+  const uint32_t* net_det = nullptr; const uint32_t* opp_det = nullptr;   // ... its deterministic word (the caller's, read at run time)
   float* net_frags = nullptr;                          // the fragment-order copies the pack kernel writes (2 x kNetFragsMax words: network, opponent)
   bool has_see = false;                                // s2d_match_set_see_network installed a see network: launches use the SEE kernels
   S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
@@ -2513,7 +2651,7 @@ static constexpr size_t kNetLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all o
 static constexpr int kNetMaxDevices = 64;
 static bool m_net_allow_lds(const void* fn, int slot, size_t dyn) {
   static std::mutex mu;
-  static size_t limit[kNetMaxDevices][10] = {};        // slots 0..4: the NET instantiations, 5..9: the SEE ones
+  static size_t limit[kNetMaxDevices][15] = {};        // slots 0..4: the NET instantiations, 5..9: the SEE ones, 10..14: the POL ones
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kNetMaxDevices) return false;
   std::lock_guard<std::mutex> lock(mu);
@@ -2530,15 +2668,18 @@ template <class K, class NA> static int m_net_launch(K kernel, int slot, size_t 
                                                      const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
                                                      const MCtl& ctl, const NA& na) {
   if (std::is_same<NA, MSeeArg>::value) slot += 5;
-  if constexpr (std::is_same<NA, MNetArg>::value) {
+  if (std::is_same<NA, MPolArg>::value) slot += 10;
+  if constexpr (!std::is_same<NA, MSeeArg>::value) {
     // The budget: a 64-64-64 network's W2 .. b3 are 33 536 B, a wave's tile, facts and index words 20 784 B, so two widest
     // networks ask for 2 x 33 536 + 4 x 20 784 = 150 208 B.  Beside the stock kernels' 12 288 B of static LDS the CU leaves
     // 151 552 B: they fit.  Beside the general kernels' 14 208 / 14 576 B (their parameter block) it leaves 149 632 / 149 264 B:
     // there two networks of 64-64-(49..64) do not fit, and the second one's W2 .. b3 stay in memory (the kernel reads them
     // there, the same words in the same order).  Every other pair fits every kernel.
+    // The POL kernels' waves hold 64 more words each (kPolWaveWords): 151 232 B for the widest pair, which the stock kernels
+    // still stage; the general ones fall back as above.
     const size_t second = (size_t)na.net.opp.shared_words * sizeof(float);
     if (second != 0 && !m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn)) {
-      MNetArg unstaged = na;
+      NA unstaged = na;
       unstaged.net.opp.shared_words = 0;
       if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn - second))
         return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn - second) + " B) does not fit beside the cycle kernel's");
@@ -2560,9 +2701,10 @@ static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const
   const dim3 grid(m_grid(h->n)), block(kMBlock);
   if constexpr (NET) {
     const auto& na = std::get<1>(std::tie(extra...));    // an MNetArg, or the see network's MSeeArg
-    constexpr int wave_words = std::is_same<std::decay_t<decltype(na)>, MSeeArg>::value ? kSeeWaveWords : kNetWaveWords;
+    using NA = std::decay_t<decltype(na)>;
+    constexpr int wave_words = std::is_same<NA, MSeeArg>::value ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
     size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
-    if constexpr (std::is_same<std::decay_t<decltype(na)>, MNetArg>::value) dyn += (size_t)na.net.opp.shared_words * sizeof(float);
+    if constexpr (!std::is_same<NA, MSeeArg>::value) dyn += (size_t)na.net.opp.shared_words * sizeof(float);
     int rc;
     if (h->stock_sched)
       rc = m_net_launch(s2d_match_rollout_kernel<true, true, true, false, true, true, X...>, 0, dyn, grid, block, st, h->mp, h->ptrs,
@@ -2639,7 +2781,7 @@ static_assert(kSeeK1 <= kNetK1, "the see network's copy fits the agent-row netwo
 // With a see network set the SEE instantiation runs (agent_obs_out is then the see record, view_actions the other slots' view actions).
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
                     float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
-                    float* agent_obs_out = nullptr, const float* view_actions = nullptr) {
+                    float* agent_obs_out = nullptr, const float* view_actions = nullptr, float* logp_out = nullptr) {
   MRoll ro{nullptr, nullptr, nullptr, nullptr};
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2669,6 +2811,10 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       MHIP_TRY(hipGetLastError());
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, sa);
+  }
+  if (logp_out && !((h->has_net && h->net_pol) || (h->has_opp && h->opp_pol))) {   // no policy network: the record is all zero
+    MDeviceGuard guard(h->device);
+    MHIP_TRY(hipMemsetAsync(logp_out, 0, (size_t)n_steps * (size_t)h->n * NP * sizeof(float), st));
   }
   if (net_mask || obs_mask || net_index_out) {
     MNetArg na;
@@ -2706,6 +2852,20 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       pack(second, const_cast<float*>(op.frags), op.shared_words);
       MHIP_TRY(hipGetLastError());
     }
+    // A role on a stochastic policy: the POL instantiation, the same MNetArg plus each pass's kind, activation and word.
+    const bool first_pol = first && (first == &h->net ? h->net_pol : h->opp_pol), second_pol = second && h->opp_pol;
+    if (first_pol || second_pol) {
+      MPolArg pa;
+      std::memset(&pa, 0, sizeof pa);
+      pa.net = na.net; pa.tab = na.tab;
+      pa.pol.logp = logp_out;
+      if (first_pol) {
+        pa.pol.kind[0] = 1;
+        pa.pol.act[0] = first == &h->net ? h->net_act : h->opp_act; pa.pol.det[0] = first == &h->net ? h->net_det : h->opp_det;
+      }
+      if (second_pol) { pa.pol.kind[1] = 1; pa.pol.act[1] = h->opp_act; pa.pol.det[1] = h->opp_det; }
+      return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, pa);
+    }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
   }
   if (h->has_ctl || actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, ctl);
@@ -2718,6 +2878,20 @@ S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
     return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, see network>" : h->stock ? "s2d_match_rollout_kernel<stock, see network>" :
            h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, see network>" :
                                               "s2d_match_rollout_kernel<general, see network>";
+  }
+  if (h->has_net && h->has_opp && (h->net_pol || h->opp_pol)) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, two networks, policy>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, two networks, policy>" :
+           h->stock       ? "s2d_match_rollout_kernel<stock, two networks, policy>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, two networks, policy>" :
+                                              "s2d_match_rollout_kernel<general, two networks, policy>";
+  }
+  if ((h->has_net && h->net_pol) || (h->has_opp && h->opp_pol)) {
+    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, policy network>";
+    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, policy network>" :
+           h->stock       ? "s2d_match_rollout_kernel<stock, policy network>" :
+           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, policy network>" :
+                                              "s2d_match_rollout_kernel<general, policy network>";
   }
   if (h->has_net && h->has_opp) {
     if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, two networks>";
@@ -2803,6 +2977,11 @@ static int m_net_frags_alloc(S2DMatchHandle h) {
   h->net_frags = static_cast<float*>(pmem);
   return S2D_OK;
 }
+// a role without a network, whatever kind it held
+static void m_role_clear(S2DMatchHandle h, int role) {
+  if (role == S2D_MATCH_ROLE_OPPONENT) { h->has_opp = false; h->opp = S2DMatchNet{}; h->opp_pol = false; h->opp_act = 0; h->opp_det = nullptr; }
+  else { h->has_net = false; h->net = S2DMatchNet{}; h->net_pol = false; h->net_act = 0; h->net_det = nullptr; }
+}
 // what both agent-row network setters reject; other_mask: the slots of the engine's other agent-row network (0: none set)
 static int m_net_validate(const S2DMatchNet* net, uint32_t other_mask) {
   const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
@@ -2820,20 +2999,53 @@ static int m_net_validate(const S2DMatchNet* net, uint32_t other_mask) {
 }
 S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { h->has_net = false; h->net = S2DMatchNet{}; return S2D_OK; }
+  if (!net) { m_role_clear(h, S2D_MATCH_ROLE_NETWORK); return S2D_OK; }
   if (int rc = m_net_validate(net, h->has_opp ? h->opp.slot_mask : 0u); rc != S2D_OK) return rc;
   if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  m_role_clear(h, S2D_MATCH_ROLE_NETWORK);               // (a policy network in this role goes)
   h->net = *net; h->has_net = true;
   h->has_see = false; h->see = S2DMatchSeeNet{};       // the see network and the agent-row ones exclude each other
   return S2D_OK;
 }
 S2D_API int s2d_match_set_opponent_network(S2DMatchHandle h, const S2DMatchNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { h->has_opp = false; h->opp = S2DMatchNet{}; return S2D_OK; }
+  if (!net) { m_role_clear(h, S2D_MATCH_ROLE_OPPONENT); return S2D_OK; }
   if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
   if (int rc = m_net_validate(net, h->has_net ? h->net.slot_mask : 0u); rc != S2D_OK) return rc;
   if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  m_role_clear(h, S2D_MATCH_ROLE_OPPONENT);
   h->opp = *net; h->has_opp = true;
+  return S2D_OK;
+}
+S2D_API int s2d_match_set_policy_network(S2DMatchHandle h, int role, const S2DMatchPolicyNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (role != S2D_MATCH_ROLE_NETWORK && role != S2D_MATCH_ROLE_OPPONENT)
+    return mfail(S2D_EINVAL, "policy network role must be S2D_MATCH_ROLE_NETWORK (0) or S2D_MATCH_ROLE_OPPONENT (1)");
+  const bool opp = role == S2D_MATCH_ROLE_OPPONENT;
+  if (!net) { m_role_clear(h, role); return S2D_OK; }
+  if (opp && h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
+  if (net->activation != 0 && net->activation != 1) return mfail(S2D_EINVAL, "policy network activation must be 0 (relu) or 1 (tanh)");
+  const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
+  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "policy network hidden widths must be 16, 32, 48 or 64");
+  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "policy network n_actions must be in [1, 64]");
+  if (net->slot_mask == 0u || (net->slot_mask >> NP) != 0u)
+    return mfail(S2D_EINVAL, "policy network slot_mask must be a non-empty set of bits 0..21");
+  const uint32_t other_mask = opp ? (h->has_net ? h->net.slot_mask : 0u) : (h->has_opp ? h->opp.slot_mask : 0u);
+  if (net->slot_mask & other_mask)
+    return mfail(S2D_EINVAL, "policy network slot_mask overlaps the network of the engine's other role (a slot belongs to one network)");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return mfail(S2D_EINVAL, "policy network params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->deterministic || !net->table ||
+      ((reinterpret_cast<uintptr_t>(net->deterministic) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
+    return mfail(S2D_EINVAL, "policy network deterministic and table must be non-NULL, 4-byte aligned device pointers");
+  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  m_role_clear(h, role);
+  const S2DMatchNet as_net{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, nullptr, net->table};
+  if (opp) { h->opp = as_net; h->has_opp = true; h->opp_pol = true; h->opp_act = net->activation; h->opp_det = net->deterministic; }
+  else {
+    h->net = as_net; h->has_net = true; h->net_pol = true; h->net_act = net->activation; h->net_det = net->deterministic;
+    h->has_see = false; h->see = S2DMatchSeeNet{};     // as s2d_match_set_network: the see network and the agent-row ones exclude each other
+  }
   return S2D_OK;
 }
 S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
@@ -2857,8 +3069,8 @@ S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* ne
   if (net->slot_mask != 0u)
     if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
   h->see = *net; h->has_see = true;
-  h->has_net = false; h->net = S2DMatchNet{};          // the see network is the engine's only one: both agent-row networks go
-  h->has_opp = false; h->opp = S2DMatchNet{};
+  m_role_clear(h, S2D_MATCH_ROLE_NETWORK);               // the see network is the engine's only one: both agent-row networks go,
+  m_role_clear(h, S2D_MATCH_ROLE_OPPONENT);              // policy networks too
   return S2D_OK;
 }
 S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
@@ -2900,6 +3112,28 @@ S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* ac
   }
   if (n_steps == 0) return S2D_OK;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev);
+}
+
+S2D_API int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
+                                     float* actions_out_dev, int32_t* net_index_out_dev, float* logp_out_dev, uint32_t obs_mask,
+                                     float* agent_obs_out_dev, void* stream) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the see network has no policy head)");
+  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
+  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
+  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
+  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
+    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
+  if (logp_out_dev && (reinterpret_cast<uintptr_t>(logp_out_dev) & 3u)) return mfail(S2D_EINVAL, "logp_out must be 4-byte aligned (float)");
+  if (agent_obs_out_dev) {
+    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
+      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when agent_obs_out is given");
+    if (reinterpret_cast<uintptr_t>(agent_obs_out_dev) & 15u) return mfail(S2D_EINVAL, "agent_obs_out must be 16-byte aligned");
+  }
+  if (n_steps == 0) return S2D_OK;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev, nullptr,
+                  logp_out_dev);
 }
 
 // What the vision layer (s2d_see.hip, a translation unit of its own) needs of an engine beyond s2d_match_buffers(): the Philox key

@@ -23,6 +23,7 @@
 #include <string>
 
 #include "s2d_actor_net.h"
+#include "s2d_head.h"
 
 // ------------------------------------------------------------------------------------------ network
 // the three layers on the wave's observation tile with hidden activation ACT (1 relu, 2 tanh_spec): net_forward<false> of
@@ -57,28 +58,7 @@ S2D_DEV void policy_forward(const QNetDims& d, int act, const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------ heads (include/s2d.h: the spec)
-// categorical head on the logits q[0 .. A-1] of one env; w = the env's uniform word of this step; returns the action
-S2D_DEV int categorical_head(const float* __restrict__ q, int A, bool det, uint32_t w, float& logp) {
-  int g = 0;
-  float m = q[0];
-  for (int a = 1; a < A; ++a) {
-    const float v = q[a];
-    if (v > m) { m = v; g = a; }
-  }
-  float S = exp_spec(q[0] - m);
-  for (int a = 1; a < A; ++a) S += exp_spec(q[a] - m);
-  int act = g;
-  if (!det) {
-    const float target = rnd_u01(w) * S;
-    float c = 0.0f;
-    for (int a = 0; a < A; ++a) {
-      c += exp_spec(q[a] - m);
-      if (c > target) { act = a; break; }
-    }
-  }
-  logp = (q[act] - m) - log_spec(S);
-  return act;
-}
+// (the categorical head: s2d_head.h, shared with the 11v11 policy slots)
 
 // z0 .. z(A-1) of the Gaussian block (POLICY block 3) at policy step k: the tanh actor's layout (turning: the four of the block
 // at counter k; continuous: z_{k & 3} of the block at counter k >> 2, cached in gquad)

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Self-play PPO on the 11v11 engine: one shared policy on all 22 slots, collected inside the cycle kernel.
+
+    python examples/ppo_match_selfplay.py --num-matches 1024 --steps 64 --iterations 20
+
+Per iteration:
+  1. ONE launch collects T cycles of N matches: MatchEngine.rollout(T, logp=True, net_index=True, agent_obs='all') with a
+     soccer2d_amd.actor.MatchPolicyActor on every slot -- the kernel builds each agent's own-frame row, runs the policy net,
+     samples from its categorical distribution and records the row, the index and its log-probability.
+  2. The critic stays in torch: one batched forward over the recorded [T, N, 22, 224] rows and the rows after the last cycle.
+  3. The per-agent reward is the engine's left-team reward with the sign by side (+ for slots 0..10, - for 11..21); agents are
+     flattened into the env axis, [T, N * 22], for soccer2d_amd.gae.gae().
+  4. Clipped-surrogate epochs whose logp_old is the kernel's record; sync() hands the new weights to the next launch.
+  5. Every --eval-every iterations the learner plays a frozen snapshot() of an earlier self on an evaluation engine of half the
+     matches (league.play_networks: learner left, snapshot right, both in-kernel), then the snapshot is renewed.
+
+stable-baselines3 cannot be installed offline; the PPO here is a small plain-torch one of the same shape (Tanh MlpPolicy)."""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+DASH, TURN, KICK, TACKLE = 1.0, 2.0, 3.0, 4.0   # S2D_MCMD_* (include/s2d_match.h)
+# 16 actions, (command, a, b): dashes in eight directions, turns, kicks ahead and to the sides, a tackle
+ACTION_TABLE = ([[DASH, 100.0, float(d)] for d in (0, 45, 90, 135, 180, -135, -90, -45)] +
+                [[TURN, float(m), 0.0] for m in (-60, -15, 15, 60)] +
+                [[KICK, 100.0, float(d)] for d in (-45, 0, 45)] + [[TACKLE, 0.0, 0.0]])
+
+
+def mlp(n_in, n_out, hidden, act):
+    return nn.Sequential(nn.Linear(n_in, hidden), act(), nn.Linear(hidden, hidden), act(), nn.Linear(hidden, n_out))
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--num-matches', type=int, default=1024)
+    ap.add_argument('--steps', type=int, default=64, help='cycles per launch (T)')
+    ap.add_argument('--iterations', type=int, default=10)
+    ap.add_argument('--epochs', type=int, default=4)
+    ap.add_argument('--minibatches', type=int, default=8)
+    ap.add_argument('--hidden', type=int, default=64, choices=(16, 32, 48, 64))
+    ap.add_argument('--relu', action='store_true', help='ReLU hidden activations instead of Tanh (SB3\'s MlpPolicy default)')
+    ap.add_argument('--lr', type=float, default=3e-4)
+    ap.add_argument('--gamma', type=float, default=0.99)
+    ap.add_argument('--lam', type=float, default=0.95)
+    ap.add_argument('--clip', type=float, default=0.2)
+    ap.add_argument('--vf-coef', type=float, default=0.5)
+    ap.add_argument('--ent-coef', type=float, default=0.01)
+    ap.add_argument('--eval-every', type=int, default=5, help='iterations between evaluation rounds against the snapshot')
+    ap.add_argument('--eval-cycles', type=int, default=600)
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--seed', type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse(argv)
+    from soccer2d_amd import league
+    from soccer2d_amd.actor import MatchPolicyActor
+    from soccer2d_amd.gae import gae
+    from soccer2d_amd.match import MatchEngine
+    torch.manual_seed(args.seed)
+    dev = torch.device(args.device)
+    N, T, K = args.num_matches, args.steps, len(ACTION_TABLE)
+    act = nn.ReLU if args.relu else nn.Tanh
+    pi, vf = mlp(224, K, args.hidden, act).to(dev), mlp(224, 1, args.hidden, act).to(dev)
+    opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()), lr=args.lr)
+    actor = MatchPolicyActor.from_module(pi, ACTION_TABLE, device=dev)
+    eng = MatchEngine(N, dev, noise=True, seed=args.seed)
+    eng.set_network(actor, 'all')
+    eng.reset()
+    rec = eng.alloc_rollout(T, with_obs=False)
+    eval_eng = MatchEngine(max(1, N // 2), dev, noise=True, seed=args.seed + 1)
+    frozen = actor.snapshot()
+    sign = torch.tensor([1.0] * 11 + [-1.0] * 11, device=dev)
+    stats = []
+    for it in range(args.iterations):
+        eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all')
+        rows, idx, logp_old = rec['agent_obs'], rec['net_index'], rec['logp']
+        with torch.no_grad():
+            value = vf(rows.reshape(-1, 224)).reshape(T, N * 22)
+            last_value = vf(eng.agent_observations('all').reshape(-1, 224)).reshape(N * 22)
+        reward = (rec['reward'][:, :, None] * sign).reshape(T, N * 22).contiguous()
+        done = rec['done'][:, :, None].expand(T, N, 22).reshape(T, N * 22).contiguous()
+        adv, ret = gae(reward, done, value.contiguous(), last_value.contiguous(), args.gamma, args.lam)
+        obs_b, act_b = rows.reshape(-1, 224), idx.reshape(-1).long()
+        lp_b, adv_b, ret_b = logp_old.reshape(-1), adv.reshape(-1), ret.reshape(-1)
+        B = obs_b.shape[0]
+        mb = (B + args.minibatches - 1) // args.minibatches
+        for _epoch in range(args.epochs):
+            perm = torch.randperm(B, device=dev)
+            for s in range(0, B, mb):
+                i = perm[s:s + mb]
+                d = torch.distributions.Categorical(logits=pi(obs_b[i]))
+                lp = d.log_prob(act_b[i])
+                a = adv_b[i]
+                a = (a - a.mean()) / (a.std() + 1e-8)
+                ratio = (lp - lp_b[i]).exp()
+                pg = -torch.min(ratio * a, ratio.clamp(1 - args.clip, 1 + args.clip) * a).mean()
+                v_loss = nn.functional.mse_loss(vf(obs_b[i]).squeeze(-1), ret_b[i])
+                ent = d.entropy().mean()
+                loss = pg + args.vf_coef * v_loss - args.ent_coef * ent
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+        actor.sync()                                       # the next launch samples from the new policy
+        row = dict(iteration=it, policy_loss=float(pg.detach()), value_loss=float(v_loss.detach()), entropy=float(ent.detach()),
+                   approx_kl=float((lp_b[i] - lp.detach()).mean()), mean_reward=float(rec['reward'].mean()))
+        if (it + 1) % args.eval_every == 0:
+            gl, gr = league.play_networks(eval_eng, actor, frozen, args.eval_cycles)
+            row.update(eval_goals_learner=int(gl.sum()), eval_goals_snapshot=int(gr.sum()))
+            frozen = actor.snapshot()                      # the next rounds' opponent: the learner as it is now
+        stats.append(row)
+        print('  '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}' for k, v in row.items()))
+    eng.close(); eval_eng.close()
+    return stats
+
+
+if __name__ == '__main__':
+    main()

@@ -139,6 +139,15 @@ class S2DMatchNet(C.Structure):             # include/s2d_match.h: network slots
                 ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p)]
 
 
+class S2DMatchPolicyNet(C.Structure):       # include/s2d_match.h: policy slots
+    _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
+                ('activation', C.c_int32), ('params', C.c_void_p), ('deterministic', C.c_void_p), ('table', C.c_void_p)]
+
+
+MATCH_ROLE_NETWORK = 0                     # S2D_MATCH_ROLE_NETWORK: the role s2d_match_set_network fills
+MATCH_ROLE_OPPONENT = 1                    # S2D_MATCH_ROLE_OPPONENT: the role s2d_match_set_opponent_network fills
+
+
 VISION_PARAM_FIELDS = ('visible_distance', 'dist_quantize_step', 'dist_round', 'dist_chg_quantize', 'dir_chg_quantize',
                        'unum_far_length', 'unum_too_far_length', 'team_far_length', 'team_too_far_length',
                        'min_neck_moment', 'max_neck_moment', 'min_neck_angle', 'max_neck_angle')
@@ -196,6 +205,9 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_see_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_see', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_policy_network', C.c_int, (C.c_void_p, C.c_int, C.c_void_p)),
+    ('s2d_match_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
 )
 
 

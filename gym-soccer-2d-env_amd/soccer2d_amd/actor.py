@@ -530,3 +530,127 @@ class MatchQNetActor:
         net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
         net.params, net.epsilon, net.table = self.params.data_ptr(), self._eps.data_ptr(), self.table.data_ptr()
         return net
+
+
+class MatchPolicyActor:
+    """Packed parameters, the device deterministic word and the action table of a 224-H1-H2-K stochastic policy for the 11v11
+    engine's policy slots (MatchEngine.set_network / set_opponent_network, s2d_match_set_policy_network in include/s2d_match.h):
+    on-policy self-play (PPO / A2C with shared parameters) collected inside the cycle kernel.
+
+    y = W3 f(W2 f(W1 x + b1) + b2) + b3 with f = ReLU or Tanh (``activation``; Tanh is SB3's default for PPO's MlpPolicy) are the
+    logits of a categorical policy over the K rows of `table`, float32 [K, 3] = (command, a, b).  The kernel samples the index,
+    records it (``net_index``) and its log-probability (``MatchEngine.rollout(logp=True)``); ``deterministic = True`` switches to
+    the first maximum.  params, the deterministic word and table are device buffers written in place and read when the kernel
+    runs, so a captured graph acts with what they hold at replay.  The see network has no policy head: obs='see' is refused."""
+
+    kind = 'policy'
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None,
+                 obs='agent'):
+        if obs != 'agent':
+            raise ValueError(f"a policy actor acts on agent rows only (obs='agent'): the see network has no policy head, got obs={obs!r}")
+        self.obs, self.in_dim, self.table_width = 'agent', MATCH_OBS_DIM, 3
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in MATCH_WIDTHS:
+                raise ValueError(f'{name} must be one of {MATCH_WIDTHS}, got {w}')
+        if not 1 <= int(n_actions) <= MATCH_MAX_ACTIONS:
+            raise ValueError(f'n_actions must be in [1, {MATCH_MAX_ACTIONS}], got {n_actions}')
+        if activation not in ('relu', 'tanh'):
+            raise ValueError(f"activation must be 'relu' or 'tanh', got {activation!r}")
+        self.hidden1, self.hidden2, self.n_actions, self.activation = int(hidden1), int(hidden2), int(n_actions), activation
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.params = torch.zeros(match_param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32,
+                                  device=self.device)
+        self.table = torch.zeros((self.n_actions, 3), dtype=torch.float32, device=self.device)
+        self._det = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._det_value = False
+        self.deterministic = deterministic
+        self._module = None
+        if table is not None:
+            self.set_table(table)
+
+    @classmethod
+    def from_module(cls, policy_net, table, device=None, deterministic=False, obs='agent'):
+        """An actor shaped like `policy_net` (224 -> H1 -> H2 -> K; the module forms StochasticActor.from_module accepts, SB3's
+        ``[policy.mlp_extractor.policy_net, policy.action_net]`` among them), loaded from it, with action table `table` [K, 3].
+        The activation is the module's."""
+        (l1, l2, l3), act = _policy_layers(policy_net)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=('relu', 'tanh')[act], device=dev,
+                    deterministic=deterministic, obs=obs)
+        actor.load_from(policy_net)
+        actor.set_table(table)
+        return actor
+
+    def shapes(self):
+        h1, h2, k = self.hidden1, self.hidden2, self.n_actions
+        return ((h1, MATCH_OBS_DIM), (h1,), (h2, h1), (h2,), (k, h2), (k,))
+
+    def load_from(self, policy_net):
+        """Validate `policy_net` against this actor (shapes and activation), remember it, and pack its parameters (sync())."""
+        layers, act = _policy_layers(policy_net)
+        if ('relu', 'tanh')[act] != self.activation:
+            raise ValueError(f'the policy\'s activation is {("relu", "tanh")[act]}, the actor\'s {self.activation}')
+        got = []
+        for lin in layers:
+            if lin.bias is None:
+                raise ValueError('every nn.Linear of the policy needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if tuple(got) != self.shapes():
+            raise ValueError(f'policy shapes {got} do not match the actor {list(self.shapes())}')
+        self._module = policy_net
+        self.sync()
+        return self
+
+    def sync(self):
+        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
+        if self._module is None:
+            raise ValueError('no module loaded (load_from)')
+        srcs = []
+        for lin in _policy_layers(self._module)[0]:
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+        return self
+
+    def set_table(self, table):
+        """Write the action table (float [K, 3] = command, a, b per index) in place."""
+        t = torch.as_tensor(table, dtype=torch.float32)
+        if tuple(t.shape) != (self.n_actions, 3):
+            raise ValueError(f'action table must have shape ({self.n_actions}, 3), got {tuple(t.shape)}')
+        self.table.copy_(t.to(self.device))
+        return self
+
+    @property
+    def deterministic(self):
+        return self._det_value
+
+    @deterministic.setter
+    def deterministic(self, value):
+        """Written in place into the device word the kernel reads (stream-ordered on torch's current stream)."""
+        self._det_value = bool(value)
+        self._det.fill_(int(self._det_value))
+
+    @property
+    def deterministic_tensor(self):
+        return self._det
+
+    def snapshot(self, deterministic=None):
+        """A frozen copy: a new actor of the same shape with its own parameters, table and deterministic word -- the league
+        member a learner plays against, or an evaluation copy.  It has no module: later sync() calls do not touch it."""
+        snap = type(self)(self.hidden1, self.hidden2, self.n_actions, activation=self.activation, device=self.device,
+                          deterministic=self._det_value if deterministic is None else deterministic)
+        snap.params.copy_(self.params)
+        snap.table.copy_(self.table)
+        return snap
+
+    def c_struct(self, slot_mask):
+        """S2DMatchPolicyNet for s2d_match_set_policy_network"""
+        from . import _capi_match as M
+        net = M.S2DMatchPolicyNet()
+        net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
+        net.activation = 1 if self.activation == 'tanh' else 0
+        net.params, net.deterministic, net.table = self.params.data_ptr(), self._det.data_ptr(), self.table.data_ptr()
+        return net

@@ -130,9 +130,9 @@ def play_round(engine, policies, left_ids, right_ids, n_cycles):
 
 def play_networks(engine, left_actor, right_actor, n_cycles, chunk=64):
     """One round of learner versus frozen opponent inside the cycle kernel: `left_actor` plays the left team and `right_actor`
-    (typically ``left_actor.snapshot()``) the right one, each MatchQNetActor on its own weights, epsilon and table
-    (MatchEngine.set_network / set_opponent_network), `n_cycles` cycles in launches of at most `chunk`.  Resets the engine first,
-    like play_round, and returns (goals_left, goals_right) int64[N] for League.update; the engine's previous networks are
+    (typically ``left_actor.snapshot()``) the right one, each a MatchQNetActor on its own weights, epsilon and table or a MatchPolicyActor on
+    its own weights, deterministic word and table, in any combination (MatchEngine.set_network / set_opponent_network), `n_cycles` cycles in launches of at most `chunk`.  Resets the engine first,
+    like play_round, and returns (goals_left, goals_right) int64[N] for League.update; the engine's previous networks, of either kind, are
     restored."""
     n_cycles, chunk = int(n_cycles), int(chunk)
     if n_cycles < 0 or chunk < 1:

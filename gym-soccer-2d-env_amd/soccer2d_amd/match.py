@@ -64,6 +64,11 @@ def make_match_config(seed=0x5EED, env_id_offset=0, auto_reset=True, noise=False
     return cfg
 
 
+def _is_policy(actor):
+    """a MatchPolicyActor (policy slots) rather than a MatchQNetActor"""
+    return getattr(actor, 'kind', 'qnet') == 'policy'
+
+
 class MatchEngine:
     def __init__(self, num_envs, device='cuda:0', cfg=None, **kwargs):
         self.lib = M.bind(_capi.load_library())
@@ -131,7 +136,8 @@ class MatchEngine:
         self.controllers = None if codes is None else list(codes)
 
     def set_network(self, actor, slots='all'):
-        """Network slots: `actor` (a MatchQNetActor) chooses the action of every slot in `slots` ('all' | 'left' | 'right' | a
+        """Network slots: `actor` (a MatchQNetActor, or a MatchPolicyActor: policy slots, sampled from the policy's own
+        distribution, s2d_match_set_policy_network) chooses the action of every slot in `slots` ('all' | 'left' | 'right' | a
         mask of bits 0..21) inside the cycle kernel, on the slot's agent row (include/s2d_match.h).  It overrides the controller
         table for those slots; the engine keeps the actor's buffers, so sync() / epsilon / set_table() act at the next launch (or
         graph replay).  None clears every network, the opponent network (set_opponent_network) included.
@@ -156,13 +162,19 @@ class MatchEngine:
             _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
             self.opponent_network, self.opponent_mask = None, 0
         else:
+            if mask & self.opponent_mask:
+                raise ValueError(f"network slots {mask:#x} overlap the opponent network's slots {self.opponent_mask:#x}")
             net = actor.c_struct(mask)
-            _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
+            if _is_policy(actor):
+                _capi.check(self.lib, self.lib.s2d_match_set_policy_network(self._h, M.MATCH_ROLE_NETWORK, C.byref(net)),
+                            's2d_match_set_policy_network')
+            else:
+                _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
         self.network, self.network_mask = actor, mask
 
     def set_opponent_network(self, actor, slots='right'):
-        """A second, independent network beside set_network's: `actor` (a MatchQNetActor on agent rows, typically a frozen
-        ``snapshot()`` of the learner) plays the slots in `slots` on its own weights, epsilon and action table, in the same launch
+        """A second, independent network beside set_network's: `actor` (a MatchQNetActor on agent rows or a MatchPolicyActor,
+        of either kind whatever set_network's is; typically a frozen ``snapshot()`` of the learner) plays the slots in `slots` on its own weights, epsilon and action table, in the same launch
         (s2d_match_set_opponent_network in include/s2d_match.h).  The two masks must be disjoint; either network may be set
         without the other.  None clears the opponent only.  A see actor is refused: the see network stays single."""
         if actor is None:
@@ -179,7 +191,11 @@ class MatchEngine:
         if mask & self.network_mask:
             raise ValueError(f"opponent slots {mask:#x} overlap the network's slots {self.network_mask:#x}")
         net = actor.c_struct(mask)
-        _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, C.byref(net)), 's2d_match_set_opponent_network')
+        if _is_policy(actor):
+            _capi.check(self.lib, self.lib.s2d_match_set_policy_network(self._h, M.MATCH_ROLE_OPPONENT, C.byref(net)),
+                        's2d_match_set_policy_network')
+        else:
+            _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, C.byref(net)), 's2d_match_set_opponent_network')
         self.opponent_network, self.opponent_mask = actor, mask
 
     def _see_network_set(self):
@@ -225,7 +241,7 @@ class MatchEngine:
         return out
 
     def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None,
-                see_obs=None, view_actions=None):
+                see_obs=None, view_actions=None, logp=False):
         """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
         each cycle, before the engine's own gating (caller slots: the caller's row).  net_index: out['net_index'] int32
         [T, N, 22] receives each network slot's index (-1 for the other slots).  agent_obs = 'all' | 'left' | 'right' | a mask:
@@ -233,7 +249,9 @@ class MatchEngine:
         see_obs = 'all' | 'left' | 'right' | a mask: out['see'] float32 [T, N, k, 192] receives those slots' start-of-cycle see
         rows, built in the cycle kernel, which then also steps the vision state (s2d_match_rollout_see): with a see network set,
         beside its slots; without a network, as a record-only see network for this call.  view_actions float32 [T, N, 22, 2] =
-        (TurnNeck moment, ChangeView code) of the slots the see network does not play (None: they neither turn nor change)."""
+        (TurnNeck moment, ChangeView code) of the slots the see network does not play (None: they neither turn nor change).
+        logp: out['logp'] float32 [T, N, 22] receives the log-probability of the index each policy slot took (MatchPolicyActor;
+        0 for every other slot, Q-network slots included): s2d_match_rollout_policy, with net_index and agent_obs as above."""
         T = int(n_steps)
         keep, ptr = self._actions(actions, T)
         if out is None:
@@ -252,8 +270,10 @@ class MatchEngine:
             if agent_obs is not None:
                 raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
             return self._rollout_see(T, ptr, ro, rec, out, keep, net_index, see_obs, view_actions)
-        if net_index or agent_obs is not None:
-            return self._rollout_net(T, ptr, ro, rec, out, keep, net_index, agent_obs)
+        if logp and self._see_network_set():
+            raise ValueError("logp is the policy slots' record: the see network has no policy head")
+        if net_index or agent_obs is not None or logp:
+            return self._rollout_net(T, ptr, ro, rec, out, keep, net_index, agent_obs, logp)
         if rec is not None:
             if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or tuple(rec.shape[1:]) != (self.num_envs, M.MATCH_PLAYERS, 3):
                 raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{self.num_envs},22,3]")
@@ -264,7 +284,7 @@ class MatchEngine:
         self._keep = (keep, out)
         return out
 
-    def _rollout_net(self, T, ptr, ro, rec, out, keep, net_index, agent_obs):
+    def _rollout_net(self, T, ptr, ro, rec, out, keep, net_index, agent_obs, logp=False):
         n, dev = self.num_envs, self.device
         if rec is not None and (rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or
                                 tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
@@ -286,6 +306,16 @@ class MatchEngine:
             elif obs.dtype != torch.float32 or not obs.is_contiguous() or obs.shape[0] < T or tuple(obs.shape[1:]) != shape:
                 raise ValueError(f"rollout buffer 'agent_obs' must be contiguous float32 [T>={T},{n},{shape[1]},224]")
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        if logp:
+            lp = out.get('logp')
+            if lp is None:
+                lp = out['logp'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.float32, device=dev)
+            elif lp.dtype != torch.float32 or not lp.is_contiguous() or lp.shape[0] < T or tuple(lp.shape[1:]) != (n, M.MATCH_PLAYERS):
+                raise ValueError(f"rollout buffer 'logp' must be contiguous float32 [T>={T},{n},22]")
+            _capi.check(self.lib, self.lib.s2d_match_rollout_policy(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), vp(lp), mask,
+                                                                     vp(obs), self._stream()), 's2d_match_rollout_policy')
+            self._keep = (keep, out)
+            return out
         _capi.check(self.lib, self.lib.s2d_match_rollout_net(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), mask, vp(obs),
                                                               self._stream()), 's2d_match_rollout_net')
         self._keep = (keep, out)
@@ -469,8 +499,8 @@ class MatchEngine:
 
 
 def _is_match_actor(obj):
-    from .actor import MatchQNetActor
-    return isinstance(obj, MatchQNetActor)
+    from .actor import MatchPolicyActor, MatchQNetActor
+    return isinstance(obj, (MatchQNetActor, MatchPolicyActor))
 
 
 class Soccer2DMatchVecEnv:
@@ -485,9 +515,10 @@ class Soccer2DMatchVecEnv:
     done    uint8 [N]           1 when a match reached TimeOver (auto-restart follows the VecEnv convention).
     info    dict of tensors     game_mode_type, game_mode_side, scores, cycle, nearest player per team.
 
-    opponent = 'random' | 'scripted' | a MatchQNetActor: the learner controls the left team only -- actions float32 [N, 11, 3] --
+    opponent = 'random' | 'scripted' | a MatchQNetActor | a MatchPolicyActor: the learner controls the left team only -- actions float32 [N, 11, 3] --
     and the right team is played inside the cycle kernel (the random policy, the scripted team of include/s2d_match.h, or the
-    actor's network on each right slot's agent row: a frozen past copy of the learner).  None: both teams
+    actor's network on each right slot's agent row: a frozen past copy of the learner; a MatchPolicyActor samples from its
+    own distribution, or plays its first maximum with deterministic = True).  None: both teams
     come from the caller, as above.
 
     obs = 'agent': every controlled agent observes in its own team's frame (MatchEngine.agent_observations), so that one policy
@@ -511,7 +542,7 @@ class Soccer2DMatchVecEnv:
         import numpy as np
         from .spaces import Box
         if not (opponent in (None, 'random', 'scripted') or _is_match_actor(opponent)):
-            raise ValueError(f"opponent must be None, 'random', 'scripted' or a MatchQNetActor, got {opponent!r}")
+            raise ValueError(f"opponent must be None, 'random', 'scripted' a MatchQNetActor or a MatchPolicyActor, got {opponent!r}")
         if obs not in ('state', 'agent', 'see'):
             raise ValueError(f"obs must be 'state', 'agent' or 'see', got {obs!r}")
         agents = 22 if opponent is None else 11

@@ -409,6 +409,54 @@ int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float *actions_de
                           float *actions_out_dev, int32_t *net_index_out_dev, uint32_t obs_mask, float *agent_obs_out_dev,
                           void *stream);
 
+/* Policy slots: a stochastic policy (PPO / A2C with shared parameters) in the place of the epsilon-greedy Q-network of "Network
+ * slots" -- the slot's action is sampled from the policy's own categorical distribution and its log-probability is recorded.
+ * Either role (the one s2d_match_set_network fills, the one s2d_match_set_opponent_network fills) may hold one.  For a policy slot
+ * l of match e in a cycle:
+ *   1. x = the row of step 1 of "Network slots", unchanged (the device function of s2d_match_agent_obs).
+ *   2. logits y = W3 f(W2 f(W1 x + b1) + b2) + b3 in the same k-ascending fmaf order, params in the S2DMatchNet layout;
+ *      f = relu (NaN and -0 -> +0) or tanh_spec (include/s2d.h), the same on both hidden layers; the output layer is linear.
+ *   3. The head is the categorical head of s2d_rollout_policy (include/s2d.h; tests/policy_ref.c::categorical restates it): m = the
+ *      first maximum of y, at index g; S = sum over a ascending of exp_spec(y[a] - m).  Not deterministic: target = rnd_u01(w) * S,
+ *      index = the first a whose running sum c (c = 0; c += exp_spec(y[a] - m), a ascending) exceeds target, g if none does.
+ *      Deterministic (*deterministic != 0, read when the kernel runs): index = g.  Both: logp = (y[index] - m) - log_spec(S).
+ *   4. w = word z of the Philox block of step 4 of "Network slots" (counter = the match's tick, stream S2D_MATCH_ST_NET, block = l).
+ *      The epsilon-greedy head uses words x and y of that block: its draws and the keys are what they were.
+ *   5. (cmd, a, b) = table[index], then the engine's usual gating, as in step 5.
+ * Roles: each role holds at most one network, of either kind -- setting a policy network replaces a Q-network there and the
+ * reverse; s2d_match_set_network(h, NULL) and s2d_match_set_opponent_network(h, NULL) clear their role whatever it holds, and so
+ * does net == NULL here.  All four combinations of kinds are legal; the two masks must be disjoint whatever the kinds; the symmetry
+ * of the opponent network holds: (A in role 0 on mask a, B in role 1 on b) is bitwise the launch (B in role 0 on b, A in role 1 on
+ * a).  Setting role 0 clears a see network (as s2d_match_set_network does), setting role 1 while a see network is set is
+ * S2D_EINVAL, and s2d_match_set_see_network clears policy networks too.  Not offered: a policy head for the see network, a
+ * Gaussian head (11v11 actions go through the table), a value head (the critic runs on the recorded rows), action masking.
+ * The engine keeps the pointers, not copies, as for S2DMatchNet.
+ * Errors (S2D_EINVAL, the engine unchanged): a role other than 0 or 1; an activation other than 0 or 1; h1 / h2 not in {16, 32, 48,
+ * 64}; n_actions outside [1, 64]; an empty slot_mask or bits above 21; NULL or unaligned pointers (params 16 bytes, deterministic
+ * and table 4); a slot_mask that overlaps the other role's.
+ * s2d_match_kernel_name ends in "policy network>" when one role is set and holds a policy network, in "two networks, policy>" when
+ * both roles are set and at least one holds a policy network. */
+#define S2D_MATCH_ROLE_NETWORK  0   /* the role s2d_match_set_network fills */
+#define S2D_MATCH_ROLE_OPPONENT 1   /* the role s2d_match_set_opponent_network fills */
+typedef struct S2DMatchPolicyNet {
+  int32_t h1, h2, n_actions;      /* {16,32,48,64}, {16,32,48,64}, 1..64 */
+  uint32_t slot_mask;             /* bits 0..21, not empty */
+  int32_t activation;             /* 0 relu, 1 tanh (tanh_spec) on both hidden layers */
+  const float *params;            /* device, 16-byte aligned, the S2DMatchNet layout */
+  const uint32_t *deterministic;  /* device word, read when the kernel runs: != 0 -> greedy */
+  const float *table;             /* device float[K][3] */
+} S2DMatchPolicyNet;
+int s2d_match_set_policy_network(S2DMatchHandle h, int role, const S2DMatchPolicyNet *net);
+/* s2d_match_step, s2d_match_rollout, s2d_match_rollout_ex and s2d_match_rollout_net use a policy network when one is set
+ * (s2d_match_rollout_net then records the index alone).  This is s2d_match_rollout_net plus
+ *   logp_out_dev  float[T][N][22] (4-byte aligned, or NULL): a policy slot receives the log-probability of the index it took (in
+ *                 deterministic mode: of the greedy index); every other slot, Q-network slots included, receives 0.0f.
+ * With no policy network set it behaves as s2d_match_rollout_net and logp_out_dev is all zeros.
+ * Errors: as s2d_match_rollout_net; an unaligned logp_out_dev. */
+int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float *actions_dev, const S2DMatchRollout *out,
+                             float *actions_out_dev, int32_t *net_index_out_dev, float *logp_out_dev,
+                             uint32_t obs_mask, float *agent_obs_out_dev, void *stream);
+
 /* Vision: an opt-in layer beside the engine -- view cone, neck, see-message quantisation, see timing.  Restated from the published
  * behaviour of rcssserver's synchronous see mode; like every 11v11 rule it is this project's own restatement: PARITY TO RCSSSERVER
  * UNPINNED.  The fp32 words below are the contract (the device equals tests/see_ref.c bit for bit).  The engine handle stores
