@@ -20,12 +20,13 @@
 // beyond N only skip their loads and stores.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
-#include <tuple>
 #include <string>
 #include <type_traits>
 
@@ -2200,21 +2201,23 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_agent_obs_kernel(MParams p,
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// One agent-row network of an engine.  A role that is not set equals MRole{} (an empty slot mask).
+struct MRole {
+  bool set = false;                                    // a setter installed a network here: launches use the NET kernels (both roles: two passes)
+  S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time); a policy's epsilon is NULL
+  bool pol = false;                                    // s2d_match_set_policy_network: a stochastic policy, launches use the POL kernels
+  int act = 0;                                         // ... its hidden activation (0 relu, 1 tanh)
+  const uint32_t* det = nullptr;                       // ... its deterministic word (the caller's, read at run time)
+};
+static_assert(S2D_MATCH_ROLE_NETWORK == 0 && S2D_MATCH_ROLE_OPPONENT == 1, "the roles index S2DMatchEngine::role, the other role is role ^ 1");
 struct S2DMatchEngine {
   S2DMatchConfig cfg; MParams mp; float ptab[PT_WORDS][kHalf]; int64_t n, stride; int device;
   bool stock = false;                                  // mp's configuration words equal MStock: launches use the constant-folded kernels
   bool stock_types = false;                            // ... and every player is of the stock PlayerType (ptab's entries equal MStockTypes)
   bool stock_sched = false;                            // stock rules, physics and types, the engine's own schedule (MStockSched)
   bool has_ctl = false;                                // s2d_match_set_controllers installed a table: launches use the CTL kernels
-  bool has_net = false;                                // s2d_match_set_network installed a network: launches use the NET kernels
-  S2DMatchNet net{};                                   // ... its pointers (the caller's buffers, read at run time)
-  bool has_opp = false;                                // s2d_match_set_opponent_network installed a second network (NET kernels, a pass of its own)
-  S2DMatchNet opp{};                                   // ... its pointers
-  // s2d_match_set_policy_network: a role that holds a stochastic policy keeps it in the same S2DMatchNet (epsilon NULL), plus:
-  bool net_pol = false, opp_pol = false;               // the role's network is a policy: launches use the POL kernels
-  int net_act = 0, opp_act = 0;                        // ... its hidden activation (0 relu, 1 tanh)
-  const uint32_t* net_det = nullptr; const uint32_t* opp_det = nullptr;   // ... its deterministic word (the caller's, read at run time)
-  float* net_frags = nullptr;                          // the fragment-order copies the pack kernel writes (2 x kNetFragsMax words: network, opponent)
+  MRole role[2];                                       // the agent-row networks, by S2D_MATCH_ROLE_NETWORK / S2D_MATCH_ROLE_OPPONENT
+  float* net_frags = nullptr;                          // the fragment-order copies the pack kernel writes (2 x kNetFragsMax words, one half per role)
   bool has_see = false;                                // s2d_match_set_see_network installed a see network: launches use the SEE kernels
   S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
@@ -2645,31 +2648,53 @@ S2D_API int s2d_match_buffer_offsets(S2DMatchHandle h, int64_t* offsets, int n_o
   return S2D_OK;
 }
 
+// The five variants of the cycle kernel, in the order an engine is tried against them, and the one this engine runs.
+struct MVariant { bool stock, stock_types, sched, ill; const char* text; };
+static constexpr MVariant kVariant[5] = {{true, true, true, false, "stock rules, own schedule"},
+                                         {true, true, false, false, "stock, stock types"},
+                                         {true, false, false, false, "stock"},
+                                         {false, false, false, true, "general, illegal defense"},
+                                         {false, false, false, false, "general"}};
+static int m_variant(const S2DMatchEngine* h) {
+  return h->stock_sched ? 0 : h->stock_types ? 1 : h->stock ? 2 : h->mp.illegal_defense_number > 0 ? 3 : 4;
+}
+// f(std::integral_constant<int, v>{}) for the run-time v: the variant as a compile-time index
+template <class F> static int m_with_variant(int v, F&& f) {
+  switch (v) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
 // NET instantiations: the dynamic LDS limit is a per-device property of the function; raise it once per (device, instantiation) to
 // what the CU leaves beside the kernel's static LDS, under a lock (engines on several devices may be driven from several threads)
 static constexpr size_t kNetLdsMax = 160 * 1024;   // gfx950: LDS of a CU, all of it available to one workgroup
 static constexpr int kNetMaxDevices = 64;
-static bool m_net_allow_lds(const void* fn, int slot, size_t dyn) {
-  static std::mutex mu;
-  static size_t limit[kNetMaxDevices][15] = {};        // slots 0..4: the NET instantiations, 5..9: the SEE ones, 10..14: the POL ones
+static std::mutex m_net_lds_mutex;
+template <auto Kernel> static bool m_net_allow_lds(size_t dyn) {
+  static size_t limit[kNetMaxDevices] = {};            // of this instantiation, per device
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kNetMaxDevices) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!limit[dev][slot]) {
+  std::lock_guard<std::mutex> lock(m_net_lds_mutex);
+  if (!limit[dev]) {
+    const void* const fn = reinterpret_cast<const void*>(Kernel);
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.sharedSizeBytes >= kNetLdsMax) return false;
     const size_t room = kNetLdsMax - fa.sharedSizeBytes;
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) != hipSuccess) return false;
-    limit[dev][slot] = room;
+    limit[dev] = room;
   }
-  return dyn <= limit[dev][slot];
+  return dyn <= limit[dev];
 }
-template <class K, class NA> static int m_net_launch(K kernel, int slot, size_t dyn, dim3 grid, dim3 block, hipStream_t st, const MParams& mp,
-                                                     const MPtrs& ptrs, int64_t n, int n_steps, const float* actions, const MRoll& ro,
-                                                     const MCtl& ctl, const NA& na) {
-  if (std::is_same<NA, MSeeArg>::value) slot += 5;
-  if (std::is_same<NA, MPolArg>::value) slot += 10;
-  if constexpr (!std::is_same<NA, MSeeArg>::value) {
+template <auto Kernel, class NA> static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp, const MPtrs& ptrs, int64_t n,
+                                                         int n_steps, const float* actions, const MRoll& ro, const MCtl& ctl, const NA& na) {
+  constexpr bool SEE = std::is_same<NA, MSeeArg>::value;
+  constexpr int wave_words = SEE ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
+  size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
+  if constexpr (!SEE) {
     // The budget: a 64-64-64 network's W2 .. b3 are 33 536 B, a wave's tile, facts and index words 20 784 B, so two widest
     // networks ask for 2 x 33 536 + 4 x 20 784 = 150 208 B.  Beside the stock kernels' 12 288 B of static LDS the CU leaves
     // 151 552 B: they fit.  Beside the general kernels' 14 208 / 14 576 B (their parameter block) it leaves 149 632 / 149 264 B:
@@ -2678,65 +2703,36 @@ template <class K, class NA> static int m_net_launch(K kernel, int slot, size_t 
     // The POL kernels' waves hold 64 more words each (kPolWaveWords): 151 232 B for the widest pair, which the stock kernels
     // still stage; the general ones fall back as above.
     const size_t second = (size_t)na.net.opp.shared_words * sizeof(float);
-    if (second != 0 && !m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn)) {
+    dyn += second;
+    if (second != 0 && !m_net_allow_lds<Kernel>(dyn)) {
       NA unstaged = na;
       unstaged.net.opp.shared_words = 0;
-      if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn - second))
+      if (!m_net_allow_lds<Kernel>(dyn - second))
         return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn - second) + " B) does not fit beside the cycle kernel's");
-      hipLaunchKernelGGL(kernel, grid, block, dyn - second, st, mp, ptrs, n, n_steps, actions, ro, ctl, unstaged);
+      hipLaunchKernelGGL(Kernel, grid, block, dyn - second, st, mp, ptrs, n, n_steps, actions, ro, ctl, unstaged);
       return S2D_OK;
     }
   }
-  if (!m_net_allow_lds(reinterpret_cast<const void*>(kernel), slot, dyn))
+  if (!m_net_allow_lds<Kernel>(dyn))
     return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
-  hipLaunchKernelGGL(kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
+  hipLaunchKernelGGL(Kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
   return S2D_OK;
 }
 
 // One launch of the instantiation this engine runs; CTL (with one MCtl in `extra`): the controller variant of the same one;
-// NET (with an MCtl and an MNetArg): the network variant, with `dyn` bytes of dynamic LDS.
+// NET (with an MCtl and an MNetArg, MPolArg or MSeeArg): the network variant, with its dynamic LDS.
 template <bool CTL, bool NET = false, class... X>
 static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, X... extra) {
   MDeviceGuard guard(h->device);
   const dim3 grid(m_grid(h->n)), block(kMBlock);
-  if constexpr (NET) {
-    const auto& na = std::get<1>(std::tie(extra...));    // an MNetArg, or the see network's MSeeArg
-    using NA = std::decay_t<decltype(na)>;
-    constexpr int wave_words = std::is_same<NA, MSeeArg>::value ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
-    size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
-    if constexpr (!std::is_same<NA, MSeeArg>::value) dyn += (size_t)na.net.opp.shared_words * sizeof(float);
-    int rc;
-    if (h->stock_sched)
-      rc = m_net_launch(s2d_match_rollout_kernel<true, true, true, false, true, true, X...>, 0, dyn, grid, block, st, h->mp, h->ptrs,
-                        h->n, n_steps, actions, ro, extra...);
-    else if (h->stock_types)
-      rc = m_net_launch(s2d_match_rollout_kernel<true, true, false, false, true, true, X...>, 1, dyn, grid, block, st, h->mp, h->ptrs,
-                        h->n, n_steps, actions, ro, extra...);
-    else if (h->stock)
-      rc = m_net_launch(s2d_match_rollout_kernel<true, false, false, false, true, true, X...>, 2, dyn, grid, block, st, h->mp, h->ptrs,
-                        h->n, n_steps, actions, ro, extra...);
-    else if (h->mp.illegal_defense_number > 0)
-      rc = m_net_launch(s2d_match_rollout_kernel<false, false, false, true, true, true, X...>, 3, dyn, grid, block, st, h->mp, h->ptrs,
-                        h->n, n_steps, actions, ro, extra...);
-    else
-      rc = m_net_launch(s2d_match_rollout_kernel<false, false, false, false, true, true, X...>, 4, dyn, grid, block, st, h->mp, h->ptrs,
-                        h->n, n_steps, actions, ro, extra...);
-    if (rc != S2D_OK) return rc;
-  } else if (h->stock_sched)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, true, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
-                       actions, ro, extra...);
-  else if (h->stock_types)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, true, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
-                       actions, ro, extra...);
-  else if (h->stock)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<true, false, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
-                       actions, ro, extra...);
-  else if (h->mp.illegal_defense_number > 0)
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, true, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
-                       actions, ro, extra...);
-  else
-    hipLaunchKernelGGL((s2d_match_rollout_kernel<false, false, false, false, CTL, false, X...>), grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps,
-                       actions, ro, extra...);
+  const int rc = m_with_variant(m_variant(h), [&](auto v) -> int {
+    constexpr MVariant V = kVariant[decltype(v)::value];
+    constexpr auto kernel = s2d_match_rollout_kernel<V.stock, V.stock_types, V.sched, V.ill, CTL, NET, X...>;
+    if constexpr (NET) return m_net_launch<kernel>(grid, block, st, h->mp, h->ptrs, h->n, n_steps, actions, ro, extra...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, h->mp, h->ptrs, h->n, n_steps, actions, ro, extra...);
+    return S2D_OK;
+  });
+  if (rc != S2D_OK) return rc;
   MHIP_TRY(hipGetLastError());
   return S2D_OK;
 }
@@ -2776,6 +2772,20 @@ __global__ __launch_bounds__(256) void s2d_match_net_pack_kernel(const float* __
 static constexpr int kNetFragsMax = (64 / 16 * kNetK1 + 64 / 16 * (64 / 4) + 64 / 16 * (64 / 4)) * 64 + 64 + 64 + 64;
 static_assert(kSeeK1 <= kNetK1, "the see network's copy fits the agent-row network's");
 
+// words of W2 .. b3 in fragment order: what a pass stages into LDS
+static int m_net_shared_words(int h1, int h2, int na16) { return (h2 / 16 * (h1 / 4) + na16 / 16 * (h2 / 4)) * 64 + h1 + h2 + na16; }
+// One pass's network words (D = MNet, MNetOpp or MSee) from the caller's network, and the pack kernel that fills its copy `frags`.
+template <class D> static void m_net_pass(D& d, const S2DMatchNet& net, int in_dim, float* frags, hipStream_t st) {
+  d.h1 = net.h1; d.h2 = net.h2; d.na = net.n_actions; d.na16 = (d.na + 15) / 16 * 16;
+  d.frags = frags; d.epsilon = net.epsilon; d.table = net.table;
+  d.shared_words = m_net_shared_words(d.h1, d.h2, d.na16);
+  const int total = (d.h1 / 16 * (in_dim / 4)) * 64 + d.shared_words;
+  hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, net.params, in_dim, d.h1, d.h2, d.na, d.na16,
+                     frags, total);
+}
+// the fields the see network shares with the agent-row ones
+static S2DMatchNet m_see_as_net(const S2DMatchSeeNet& s) { return S2DMatchNet{s.h1, s.h2, s.n_actions, s.slot_mask, s.params, s.epsilon, s.table}; }
+
 // actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL).
 // With a network set, or a row record asked for (obs_mask), the NET instantiation runs (after the pack kernel, when there is a network).
 // With a see network set the SEE instantiation runs (agent_obs_out is then the see record, view_actions the other slots' view actions).
@@ -2786,7 +2796,8 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr uint32_t kAll = (1u << NP) - 1u;
-  const uint32_t net_mask = h->has_see ? h->see.slot_mask : (h->has_net ? h->net.slot_mask : 0u) | (h->has_opp ? h->opp.slot_mask : 0u);
+  const MRole* const role = h->role;
+  const uint32_t net_mask = h->has_see ? h->see.slot_mask : role[0].net.slot_mask | role[1].net.slot_mask;
   if (!agent_obs_out) obs_mask = 0u;
   if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
     return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
@@ -2801,18 +2812,13 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
     sa.sp = s2d_see::see_params(h->see.prm, keys);
     sa.vis = h->see.vis;
     if (net_mask) {
-      nt.h1 = h->see.h1; nt.h2 = h->see.h2; nt.na = h->see.n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
-      nt.frags = h->net_frags; nt.epsilon = h->see.epsilon; nt.table = h->see.table;
-      nt.shared_words = (nt.h2 / 16 * (nt.h1 / 4) + nt.na16 / 16 * (nt.h2 / 4)) * 64 + nt.h1 + nt.h2 + nt.na16;
-      const int total = (nt.h1 / 16 * kSeeK1) * 64 + nt.shared_words;
       MDeviceGuard guard(h->device);
-      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->see.params, (int)S2D_SEE_DIM, nt.h1,
-                         nt.h2, nt.na, nt.na16, h->net_frags, total);
+      m_net_pass(nt, m_see_as_net(h->see), S2D_SEE_DIM, h->net_frags, st);
       MHIP_TRY(hipGetLastError());
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, sa);
   }
-  if (logp_out && !((h->has_net && h->net_pol) || (h->has_opp && h->opp_pol))) {   // no policy network: the record is all zero
+  if (logp_out && !(role[0].pol || role[1].pol)) {       // no policy network: the record is all zero
     MDeviceGuard guard(h->device);
     MHIP_TRY(hipMemsetAsync(logp_out, 0, (size_t)n_steps * (size_t)h->n * NP * sizeof(float), st));
   }
@@ -2823,47 +2829,26 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
     nt.obs_mask = obs_mask; nt.row_mask = net_mask | obs_mask;
     nt.net_index = net_index_out; nt.agent_obs = agent_obs_out;
     na.tab = h->atab;
+    MPol pol;                                              // a role on a stochastic policy: each pass's kind, activation and word
+    std::memset(&pol, 0, sizeof pol);
+    pol.logp = logp_out;
     // The kernel's first pass is the network when one is set, else the opponent; its second pass the opponent beside a network.
-    // Each keeps its own half of the fragment copy, so which pass a network runs in changes no word it reads.
-    const S2DMatchNet* const first = h->has_net ? &h->net : h->has_opp ? &h->opp : nullptr;
-    const S2DMatchNet* const second = h->has_net && h->has_opp ? &h->opp : nullptr;
-    const auto shared_words = [](int h1, int h2, int na16) { return (h2 / 16 * (h1 / 4) + na16 / 16 * (h2 / 4)) * 64 + h1 + h2 + na16; };
-    const auto pack = [&](const S2DMatchNet* net, float* frags, int words) {
-      const int na16 = (net->n_actions + 15) / 16 * 16;
-      const int total = (net->h1 / 16 * kNetK1) * 64 + words;
-      hipLaunchKernelGGL(s2d_match_net_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, net->params, (int)S2D_AGENT_OBS_DIM,
-                         net->h1, net->h2, net->n_actions, na16, frags, total);
-    };
+    // Each role keeps its own half of the fragment copy, so which pass a network runs in changes no word it reads.
+    const int first = role[S2D_MATCH_ROLE_NETWORK].set ? S2D_MATCH_ROLE_NETWORK : S2D_MATCH_ROLE_OPPONENT;
+    const int passes = role[0].set + role[1].set;
     MDeviceGuard guard(h->device);
-    if (first) {
-      nt.net_mask = first->slot_mask;
-      nt.h1 = first->h1; nt.h2 = first->h2; nt.na = first->n_actions; nt.na16 = (nt.na + 15) / 16 * 16;
-      nt.frags = h->net_frags + (first == &h->opp ? kNetFragsMax : 0); nt.epsilon = first->epsilon; nt.table = first->table;
-      nt.shared_words = shared_words(nt.h1, nt.h2, nt.na16);
-      pack(first, const_cast<float*>(nt.frags), nt.shared_words);
+    for (int k = 0; k < passes; ++k) {
+      const MRole& r = role[first + k];
+      float* const frags = h->net_frags + (first + k) * kNetFragsMax;
+      if (k == 0) { nt.net_mask = r.net.slot_mask; m_net_pass(nt, r.net, S2D_AGENT_OBS_DIM, frags, st); }
+      else { nt.opp.mask = r.net.slot_mask; m_net_pass(nt.opp, r.net, S2D_AGENT_OBS_DIM, frags, st); }
       MHIP_TRY(hipGetLastError());
+      if (r.pol) { pol.kind[k] = 1; pol.act[k] = r.act; pol.det[k] = r.det; }
     }
-    if (second) {
-      MNetOpp& op = nt.opp;
-      op.mask = second->slot_mask;
-      op.h1 = second->h1; op.h2 = second->h2; op.na = second->n_actions; op.na16 = (op.na + 15) / 16 * 16;
-      op.frags = h->net_frags + kNetFragsMax; op.epsilon = second->epsilon; op.table = second->table;
-      op.shared_words = shared_words(op.h1, op.h2, op.na16);
-      pack(second, const_cast<float*>(op.frags), op.shared_words);
-      MHIP_TRY(hipGetLastError());
-    }
-    // A role on a stochastic policy: the POL instantiation, the same MNetArg plus each pass's kind, activation and word.
-    const bool first_pol = first && (first == &h->net ? h->net_pol : h->opp_pol), second_pol = second && h->opp_pol;
-    if (first_pol || second_pol) {
+    if (pol.kind[0] || pol.kind[1]) {                      // the POL instantiation: the same MNetArg plus the policy words
       MPolArg pa;
       std::memset(&pa, 0, sizeof pa);
-      pa.net = na.net; pa.tab = na.tab;
-      pa.pol.logp = logp_out;
-      if (first_pol) {
-        pa.pol.kind[0] = 1;
-        pa.pol.act[0] = first == &h->net ? h->net_act : h->opp_act; pa.pol.det[0] = first == &h->net ? h->net_det : h->opp_det;
-      }
-      if (second_pol) { pa.pol.kind[1] = 1; pa.pol.act[1] = h->opp_act; pa.pol.det[1] = h->opp_det; }
+      pa.net = na.net; pa.tab = na.tab; pa.pol = pol;
       return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, pa);
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
@@ -2871,49 +2856,22 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
   if (h->has_ctl || actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, ctl);
   return m_dispatch<false>(h, n_steps, actions, ro, st);
 }
+// "s2d_match_rollout_kernel<" variant [", " slot kind] ">"
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
-  if (h->has_see) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, see network>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, see network>" : h->stock ? "s2d_match_rollout_kernel<stock, see network>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, see network>" :
-                                              "s2d_match_rollout_kernel<general, see network>";
-  }
-  if (h->has_net && h->has_opp && (h->net_pol || h->opp_pol)) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, two networks, policy>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, two networks, policy>" :
-           h->stock       ? "s2d_match_rollout_kernel<stock, two networks, policy>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, two networks, policy>" :
-                                              "s2d_match_rollout_kernel<general, two networks, policy>";
-  }
-  if ((h->has_net && h->net_pol) || (h->has_opp && h->opp_pol)) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, policy network>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, policy network>" :
-           h->stock       ? "s2d_match_rollout_kernel<stock, policy network>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, policy network>" :
-                                              "s2d_match_rollout_kernel<general, policy network>";
-  }
-  if (h->has_net && h->has_opp) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, two networks>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, two networks>" : h->stock ? "s2d_match_rollout_kernel<stock, two networks>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, two networks>" :
-                                              "s2d_match_rollout_kernel<general, two networks>";
-  }
-  if (h->has_net || h->has_opp) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, network>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, network>" : h->stock ? "s2d_match_rollout_kernel<stock, network>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, network>" :
-                                              "s2d_match_rollout_kernel<general, network>";
-  }
-  if (h->has_ctl) {
-    if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule, controllers>";
-    return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types, controllers>" : h->stock ? "s2d_match_rollout_kernel<stock, controllers>" :
-           h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense, controllers>" :
-                                              "s2d_match_rollout_kernel<general, controllers>";
-  }
-  if (h->stock_sched) return "s2d_match_rollout_kernel<stock rules, own schedule>";
-  return h->stock_types ? "s2d_match_rollout_kernel<stock, stock types>" : h->stock ? "s2d_match_rollout_kernel<stock>" :
-         h->mp.illegal_defense_number > 0 ? "s2d_match_rollout_kernel<general, illegal defense>" : "s2d_match_rollout_kernel<general>";
+  constexpr int kKinds = 7;
+  static const char* const kind_text[kKinds] = {"", ", controllers", ", network", ", two networks", ", policy network",
+                                                ", two networks, policy", ", see network"};
+  static const std::array<std::string, 5 * kKinds> names = [] {
+    std::array<std::string, 5 * kKinds> t;
+    for (int v = 0; v < 5; ++v)
+      for (int k = 0; k < kKinds; ++k) t[v * kKinds + k] = std::string("s2d_match_rollout_kernel<") + kVariant[v].text + kind_text[k] + ">";
+    return t;
+  }();
+  const int nets = h->role[0].set + h->role[1].set;
+  const bool pol = h->role[0].pol || h->role[1].pol;
+  const int kind = h->has_see ? 6 : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
+  return names[m_variant(h) * kKinds + kind].c_str();
 }
 S2D_API int s2d_match_relative(S2DMatchHandle h, float* dist_dev, float* angle_dev, void* stream) {
   if (!h || !dist_dev || !angle_dev) return mfail(S2D_EINVAL, "NULL argument");
@@ -2938,11 +2896,29 @@ S2D_API int s2d_match_step(S2DMatchHandle h, const float* actions_dev, void* str
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
   return m_launch(h, 1, actions_dev, nullptr, stream);
 }
+// What the rollout entry points check alike, in the order they report it: the handle, n_steps, the obs buffer, the optional records
+// `recs` (4-byte aligned), then the row record `rows` (agent_obs_out or see_out: 16-byte aligned, with a proper obs_mask).
+// true: launch.  false: return *rc (an error, or S2D_OK for n_steps == 0).
+struct MRecord { const void* ptr; const char* name; const char* type; };
+static bool m_rollout_args(int* rc, S2DMatchHandle h, int n_steps, const S2DMatchRollout* out, std::initializer_list<MRecord> recs = {},
+                           const void* rows = nullptr, const char* rows_name = "", uint32_t obs_mask = 0u) {
+  const auto fail = [rc](const std::string& msg) { *rc = mfail(S2D_EINVAL, msg); return false; };
+  if (!h) return fail("NULL handle");
+  if (n_steps < 0) return fail("n_steps must be >= 0");
+  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return fail("rollout obs buffer must be 16-byte aligned");
+  for (const MRecord& r : recs)
+    if (reinterpret_cast<uintptr_t>(r.ptr) & 3u) return fail(std::string(r.name) + " must be 4-byte aligned (" + r.type + ")");
+  if (rows) {
+    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
+      return fail(std::string("obs_mask must be a non-empty set of bits 0..21 when ") + rows_name + " is given");
+    if (reinterpret_cast<uintptr_t>(rows) & 15u) return fail(std::string(rows_name) + " must be 16-byte aligned");
+  }
+  *rc = S2D_OK;
+  return n_steps != 0;
+}
 S2D_API int s2d_match_rollout(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out, void* stream) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
-  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
-  if (n_steps == 0) return S2D_OK;
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out)) return rc;
   return m_launch(h, n_steps, actions_dev, out, stream);
 }
 S2D_API int s2d_match_set_controllers(S2DMatchHandle h, const uint8_t* ctl) {
@@ -2961,14 +2937,11 @@ S2D_API int s2d_match_set_controllers(S2DMatchHandle h, const uint8_t* ctl) {
 }
 S2D_API int s2d_match_rollout_ex(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                  float* actions_out_dev, void* stream) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
-  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
-  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
-  if (n_steps == 0) return S2D_OK;
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}})) return rc;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev);
 }
+
 static int m_net_frags_alloc(S2DMatchHandle h) {
   if (h->net_frags) return S2D_OK;
   MDeviceGuard guard(h->device);
@@ -2977,90 +2950,78 @@ static int m_net_frags_alloc(S2DMatchHandle h) {
   h->net_frags = static_cast<float*>(pmem);
   return S2D_OK;
 }
-// a role without a network, whatever kind it held
-static void m_role_clear(S2DMatchHandle h, int role) {
-  if (role == S2D_MATCH_ROLE_OPPONENT) { h->has_opp = false; h->opp = S2DMatchNet{}; h->opp_pol = false; h->opp_act = 0; h->opp_det = nullptr; }
-  else { h->has_net = false; h->net = S2DMatchNet{}; h->net_pol = false; h->net_act = 0; h->net_det = nullptr; }
-}
-// what both agent-row network setters reject; other_mask: the slots of the engine's other agent-row network (0: none set)
-static int m_net_validate(const S2DMatchNet* net, uint32_t other_mask) {
+// What every network setter rejects.  what: "network", "policy network" or "see network"; word / word_name: the network's device
+// word beside the table (epsilon or deterministic); other_mask: the slots of the engine's other agent-row network (0: none set).
+// empty_ok (the see network): an empty slot_mask is a record-only network, whose pointers are not read.
+static int m_net_validate(const std::string& what, const S2DMatchNet& net, const void* word, const char* word_name, bool empty_ok,
+                          uint32_t other_mask) {
   const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
-  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "network hidden widths must be 16, 32, 48 or 64");
-  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "network n_actions must be in [1, 64]");
-  if (net->slot_mask == 0u || (net->slot_mask >> NP) != 0u)
-    return mfail(S2D_EINVAL, "network slot_mask must be a non-empty set of bits 0..21");
-  if (net->slot_mask & other_mask)
-    return mfail(S2D_EINVAL, "network slot_mask overlaps the engine's other network (a slot belongs to one network)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return mfail(S2D_EINVAL, "network params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || !net->table || ((reinterpret_cast<uintptr_t>(net->epsilon) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
-    return mfail(S2D_EINVAL, "network epsilon and table must be non-NULL, 4-byte aligned device pointers");
+  if (!width_ok(net.h1) || !width_ok(net.h2)) return mfail(S2D_EINVAL, what + " hidden widths must be 16, 32, 48 or 64");
+  if (net.n_actions < 1 || net.n_actions > 64) return mfail(S2D_EINVAL, what + " n_actions must be in [1, 64]");
+  if ((net.slot_mask == 0u && !empty_ok) || (net.slot_mask >> NP) != 0u)
+    return mfail(S2D_EINVAL, what + " slot_mask must be a " + (empty_ok ? "" : "non-empty ") + "set of bits 0..21");
+  if (net.slot_mask & other_mask)
+    return mfail(S2D_EINVAL, what + " slot_mask overlaps the network of the engine's other role (a slot belongs to one network)");
+  if (net.slot_mask == 0u) return S2D_OK;
+  if (!net.params || (reinterpret_cast<uintptr_t>(net.params) & 15u))
+    return mfail(S2D_EINVAL, what + " params must be a non-NULL, 16-byte aligned device pointer");
+  if (!word || !net.table || ((reinterpret_cast<uintptr_t>(word) | reinterpret_cast<uintptr_t>(net.table)) & 3u))
+    return mfail(S2D_EINVAL, what + " " + word_name + " and table must be non-NULL, 4-byte aligned device pointers");
+  return S2D_OK;
+}
+// Who excludes whom, for all four setters.  `slot`: a role, or kSlotSee.  The see network is the engine's only one: the opponent role
+// refuses beside it, the network role replaces it, and setting it clears both roles (policy networks too).
+static constexpr int kSlotSee = 2;
+static int m_slot_admit(S2DMatchHandle h, int slot) {
+  if (slot == S2D_MATCH_ROLE_OPPONENT && h->has_see)
+    return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
+  return S2D_OK;
+}
+static void m_slot_clear(S2DMatchHandle h, int slot) {   // a slot without a network, whatever kind it held
+  if (slot == kSlotSee) { h->has_see = false; h->see = S2DMatchSeeNet{}; }
+  else h->role[slot] = MRole{};
+}
+static void m_slot_displace(S2DMatchHandle h, int slot) {
+  if (slot == kSlotSee) { m_slot_clear(h, S2D_MATCH_ROLE_NETWORK); m_slot_clear(h, S2D_MATCH_ROLE_OPPONENT); }
+  if (slot == S2D_MATCH_ROLE_NETWORK) m_slot_clear(h, kSlotSee);
+}
+// an agent-row network into a role: r = the role's new state (set, with the caller's pointers)
+static int m_role_set(S2DMatchHandle h, int role, const MRole& r) {
+  if (int rc = m_slot_admit(h, role); rc != S2D_OK) return rc;
+  if (r.pol && r.act != 0 && r.act != 1) return mfail(S2D_EINVAL, "policy network activation must be 0 (relu) or 1 (tanh)");
+  const void* const word = r.pol ? static_cast<const void*>(r.det) : r.net.epsilon;
+  const uint32_t other_mask = h->role[role ^ 1].net.slot_mask;
+  if (int rc = m_net_validate(r.pol ? "policy network" : "network", r.net, word, r.pol ? "deterministic" : "epsilon", false, other_mask);
+      rc != S2D_OK)
+    return rc;
+  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  h->role[role] = r;                                   // (whatever kind the role held goes)
+  m_slot_displace(h, role);
   return S2D_OK;
 }
 S2D_API int s2d_match_set_network(S2DMatchHandle h, const S2DMatchNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { m_role_clear(h, S2D_MATCH_ROLE_NETWORK); return S2D_OK; }
-  if (int rc = m_net_validate(net, h->has_opp ? h->opp.slot_mask : 0u); rc != S2D_OK) return rc;
-  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
-  m_role_clear(h, S2D_MATCH_ROLE_NETWORK);               // (a policy network in this role goes)
-  h->net = *net; h->has_net = true;
-  h->has_see = false; h->see = S2DMatchSeeNet{};       // the see network and the agent-row ones exclude each other
-  return S2D_OK;
+  if (!net) { m_slot_clear(h, S2D_MATCH_ROLE_NETWORK); return S2D_OK; }
+  return m_role_set(h, S2D_MATCH_ROLE_NETWORK, MRole{true, *net});
 }
 S2D_API int s2d_match_set_opponent_network(S2DMatchHandle h, const S2DMatchNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { m_role_clear(h, S2D_MATCH_ROLE_OPPONENT); return S2D_OK; }
-  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
-  if (int rc = m_net_validate(net, h->has_net ? h->net.slot_mask : 0u); rc != S2D_OK) return rc;
-  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
-  m_role_clear(h, S2D_MATCH_ROLE_OPPONENT);
-  h->opp = *net; h->has_opp = true;
-  return S2D_OK;
+  if (!net) { m_slot_clear(h, S2D_MATCH_ROLE_OPPONENT); return S2D_OK; }
+  return m_role_set(h, S2D_MATCH_ROLE_OPPONENT, MRole{true, *net});
 }
 S2D_API int s2d_match_set_policy_network(S2DMatchHandle h, int role, const S2DMatchPolicyNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
   if (role != S2D_MATCH_ROLE_NETWORK && role != S2D_MATCH_ROLE_OPPONENT)
     return mfail(S2D_EINVAL, "policy network role must be S2D_MATCH_ROLE_NETWORK (0) or S2D_MATCH_ROLE_OPPONENT (1)");
-  const bool opp = role == S2D_MATCH_ROLE_OPPONENT;
-  if (!net) { m_role_clear(h, role); return S2D_OK; }
-  if (opp && h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network stays single (clear it first)");
-  if (net->activation != 0 && net->activation != 1) return mfail(S2D_EINVAL, "policy network activation must be 0 (relu) or 1 (tanh)");
-  const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
-  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "policy network hidden widths must be 16, 32, 48 or 64");
-  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "policy network n_actions must be in [1, 64]");
-  if (net->slot_mask == 0u || (net->slot_mask >> NP) != 0u)
-    return mfail(S2D_EINVAL, "policy network slot_mask must be a non-empty set of bits 0..21");
-  const uint32_t other_mask = opp ? (h->has_net ? h->net.slot_mask : 0u) : (h->has_opp ? h->opp.slot_mask : 0u);
-  if (net->slot_mask & other_mask)
-    return mfail(S2D_EINVAL, "policy network slot_mask overlaps the network of the engine's other role (a slot belongs to one network)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return mfail(S2D_EINVAL, "policy network params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->deterministic || !net->table ||
-      ((reinterpret_cast<uintptr_t>(net->deterministic) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
-    return mfail(S2D_EINVAL, "policy network deterministic and table must be non-NULL, 4-byte aligned device pointers");
-  if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
-  m_role_clear(h, role);
+  if (!net) { m_slot_clear(h, role); return S2D_OK; }
+  // a policy keeps its words in the same S2DMatchNet, epsilon NULL
   const S2DMatchNet as_net{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, nullptr, net->table};
-  if (opp) { h->opp = as_net; h->has_opp = true; h->opp_pol = true; h->opp_act = net->activation; h->opp_det = net->deterministic; }
-  else {
-    h->net = as_net; h->has_net = true; h->net_pol = true; h->net_act = net->activation; h->net_det = net->deterministic;
-    h->has_see = false; h->see = S2DMatchSeeNet{};     // as s2d_match_set_network: the see network and the agent-row ones exclude each other
-  }
-  return S2D_OK;
+  return m_role_set(h, role, MRole{true, as_net, true, net->activation, net->deterministic});
 }
 S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { h->has_see = false; h->see = S2DMatchSeeNet{}; return S2D_OK; }
-  const auto width_ok = [](int w) { return w == 16 || w == 32 || w == 48 || w == 64; };
-  if ((net->slot_mask >> NP) != 0u) return mfail(S2D_EINVAL, "see network slot_mask must be a set of bits 0..21");
-  if (!width_ok(net->h1) || !width_ok(net->h2)) return mfail(S2D_EINVAL, "see network hidden widths must be 16, 32, 48 or 64");
-  if (net->n_actions < 1 || net->n_actions > 64) return mfail(S2D_EINVAL, "see network n_actions must be in [1, 64]");
-  if (net->slot_mask != 0u) {
-    if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-      return mfail(S2D_EINVAL, "see network params must be a non-NULL, 16-byte aligned device pointer");
-    if (!net->epsilon || !net->table || ((reinterpret_cast<uintptr_t>(net->epsilon) | reinterpret_cast<uintptr_t>(net->table)) & 3u))
-      return mfail(S2D_EINVAL, "see network epsilon and table must be non-NULL, 4-byte aligned device pointers");
-  }
+  if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+  if (int rc = m_net_validate("see network", m_see_as_net(*net), net->epsilon, "epsilon", true, 0u); rc != S2D_OK) return rc;
   if (!net->vis.neck || !net->vis.view_width || !net->vis.see_wait) return mfail(S2D_EINVAL, "NULL vision plane");
   if ((reinterpret_cast<uintptr_t>(net->vis.neck) | reinterpret_cast<uintptr_t>(net->vis.view_width) |
        reinterpret_cast<uintptr_t>(net->vis.see_wait)) & 3u)
@@ -3069,69 +3030,37 @@ S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* ne
   if (net->slot_mask != 0u)
     if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
   h->see = *net; h->has_see = true;
-  m_role_clear(h, S2D_MATCH_ROLE_NETWORK);               // the see network is the engine's only one: both agent-row networks go,
-  m_role_clear(h, S2D_MATCH_ROLE_OPPONENT);              // policy networks too
+  m_slot_displace(h, kSlotSee);
   return S2D_OK;
 }
 S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
                                   const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask,
                                   float* see_out_dev, void* stream) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!h->has_see) return mfail(S2D_EINVAL, "s2d_match_rollout_see needs a see network (s2d_match_set_see_network)");
-  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
-  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
-  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
-  if (view_actions_dev && (reinterpret_cast<uintptr_t>(view_actions_dev) & 3u))
-    return mfail(S2D_EINVAL, "view_actions must be 4-byte aligned (float)");
-  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
-  if (see_out_dev) {
-    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
-      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when see_out is given");
-    if (reinterpret_cast<uintptr_t>(see_out_dev) & 15u) return mfail(S2D_EINVAL, "see_out must be 16-byte aligned");
-  }
-  if (n_steps == 0) return S2D_OK;
+  if (h && !h->has_see) return mfail(S2D_EINVAL, "s2d_match_rollout_see needs a see network (s2d_match_set_see_network)");
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {view_actions_dev, "view_actions", "float"},
+                                             {net_index_out_dev, "net_index_out", "int32"}}, see_out_dev, "see_out", obs_mask))
+    return rc;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, see_out_dev, view_actions_dev);
 }
 S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                   float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask, float* agent_obs_out_dev,
                                   void* stream) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the agent-row record is not built)");
-  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
-  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
-  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
-  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
-  if (agent_obs_out_dev) {
-    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
-      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when agent_obs_out is given");
-    if (reinterpret_cast<uintptr_t>(agent_obs_out_dev) & 15u) return mfail(S2D_EINVAL, "agent_obs_out must be 16-byte aligned");
-  }
-  if (n_steps == 0) return S2D_OK;
+  if (h && h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the agent-row record is not built)");
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {net_index_out_dev, "net_index_out", "int32"}},
+                      agent_obs_out_dev, "agent_obs_out", obs_mask))
+    return rc;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev);
 }
-
 S2D_API int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                      float* actions_out_dev, int32_t* net_index_out_dev, float* logp_out_dev, uint32_t obs_mask,
                                      float* agent_obs_out_dev, void* stream) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the see network has no policy head)");
-  if (n_steps < 0) return mfail(S2D_EINVAL, "n_steps must be >= 0");
-  if (out && out->obs && (reinterpret_cast<uintptr_t>(out->obs) & 15u)) return mfail(S2D_EINVAL, "rollout obs buffer must be 16-byte aligned");
-  if (actions_out_dev && (reinterpret_cast<uintptr_t>(actions_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "actions_out must be 4-byte aligned (float)");
-  if (net_index_out_dev && (reinterpret_cast<uintptr_t>(net_index_out_dev) & 3u))
-    return mfail(S2D_EINVAL, "net_index_out must be 4-byte aligned (int32)");
-  if (logp_out_dev && (reinterpret_cast<uintptr_t>(logp_out_dev) & 3u)) return mfail(S2D_EINVAL, "logp_out must be 4-byte aligned (float)");
-  if (agent_obs_out_dev) {
-    if (obs_mask == 0u || (obs_mask >> NP) != 0u)
-      return mfail(S2D_EINVAL, "obs_mask must be a non-empty set of bits 0..21 when agent_obs_out is given");
-    if (reinterpret_cast<uintptr_t>(agent_obs_out_dev) & 15u) return mfail(S2D_EINVAL, "agent_obs_out must be 16-byte aligned");
-  }
-  if (n_steps == 0) return S2D_OK;
+  if (h && h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the see network has no policy head)");
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {net_index_out_dev, "net_index_out", "int32"},
+                                             {logp_out_dev, "logp_out", "float"}}, agent_obs_out_dev, "agent_obs_out", obs_mask))
+    return rc;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev, nullptr,
                   logp_out_dev);
 }

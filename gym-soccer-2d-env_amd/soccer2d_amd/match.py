@@ -69,6 +69,10 @@ def _is_policy(actor):
     return getattr(actor, 'kind', 'qnet') == 'policy'
 
 
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class MatchEngine:
     def __init__(self, num_envs, device='cuda:0', cfg=None, **kwargs):
         self.lib = M.bind(_capi.load_library())
@@ -164,13 +168,20 @@ class MatchEngine:
         else:
             if mask & self.opponent_mask:
                 raise ValueError(f"network slots {mask:#x} overlap the opponent network's slots {self.opponent_mask:#x}")
-            net = actor.c_struct(mask)
-            if _is_policy(actor):
-                _capi.check(self.lib, self.lib.s2d_match_set_policy_network(self._h, M.MATCH_ROLE_NETWORK, C.byref(net)),
-                            's2d_match_set_policy_network')
-            else:
-                _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network')
+            self._set_role(M.MATCH_ROLE_NETWORK, actor, mask)
         self.network, self.network_mask = actor, mask
+
+    def _set_role(self, role, actor, mask):
+        """an agent-row actor into a role of the engine: a policy through s2d_match_set_policy_network, a Q-network through the
+        role's own setter"""
+        net = actor.c_struct(mask)
+        if _is_policy(actor):
+            rc, fn = self.lib.s2d_match_set_policy_network(self._h, role, C.byref(net)), 's2d_match_set_policy_network'
+        elif role == M.MATCH_ROLE_OPPONENT:
+            rc, fn = self.lib.s2d_match_set_opponent_network(self._h, C.byref(net)), 's2d_match_set_opponent_network'
+        else:
+            rc, fn = self.lib.s2d_match_set_network(self._h, C.byref(net)), 's2d_match_set_network'
+        _capi.check(self.lib, rc, fn)
 
     def set_opponent_network(self, actor, slots='right'):
         """A second, independent network beside set_network's: `actor` (a MatchQNetActor on agent rows or a MatchPolicyActor,
@@ -190,13 +201,19 @@ class MatchEngine:
             raise ValueError("a see network is set: it is the engine's only network (set_network(None) first)")
         if mask & self.network_mask:
             raise ValueError(f"opponent slots {mask:#x} overlap the network's slots {self.network_mask:#x}")
-        net = actor.c_struct(mask)
-        if _is_policy(actor):
-            _capi.check(self.lib, self.lib.s2d_match_set_policy_network(self._h, M.MATCH_ROLE_OPPONENT, C.byref(net)),
-                        's2d_match_set_policy_network')
-        else:
-            _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, C.byref(net)), 's2d_match_set_opponent_network')
+        self._set_role(M.MATCH_ROLE_OPPONENT, actor, mask)
         self.opponent_network, self.opponent_mask = actor, mask
+
+    def _record(self, out, name, T, tail_shape, dtype):
+        """out[name], a rollout record [T, *tail_shape]: allocated when absent, else checked (dtype, contiguous, at least T
+        steps, the tail)"""
+        t = out.get(name)
+        if t is None:
+            t = out[name] = torch.empty((T,) + tuple(tail_shape), dtype=dtype, device=self.device)
+        elif t.dtype != dtype or not t.is_contiguous() or t.shape[0] < T or tuple(t.shape[1:]) != tuple(tail_shape):
+            kind, tail = str(dtype).replace('torch.', ''), ','.join(str(d) for d in tail_shape)
+            raise ValueError(f"rollout buffer {name!r} must be contiguous {kind} [T>={T},{tail}]")
+        return t
 
     def _see_network_set(self):
         return self.network is not None and getattr(self.network, 'obs', 'agent') == 'see'
@@ -256,8 +273,6 @@ class MatchEngine:
         keep, ptr = self._actions(actions, T)
         if out is None:
             out = self.alloc_rollout(T, with_obs, record_actions)
-        elif record_actions and out.get('actions') is None:
-            out['actions'] = torch.empty((T, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
         ro = M.S2DMatchRollout()
         for name in ('obs', 'reward', 'mode', 'done'):
             v = out.get(name)
@@ -265,78 +280,43 @@ class MatchEngine:
                 if not v.is_contiguous() or v.shape[0] < T or v.shape[1] != self.num_envs:
                     raise ValueError(f"rollout buffer {name!r} must be contiguous [T>={T},{self.num_envs},...]")
                 setattr(ro, name, v.data_ptr())
-        rec = out.get('actions') if record_actions else None
+        n, st = self.num_envs, self._stream()
+        rec = self._record(out, 'actions', T, (n, M.MATCH_PLAYERS, 3), torch.float32) if record_actions else None
+        va = None
         if see_obs is not None or view_actions is not None or (net_index and self._see_network_set()):
             if agent_obs is not None:
                 raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
-            return self._rollout_see(T, ptr, ro, rec, out, keep, net_index, see_obs, view_actions)
-        if logp and self._see_network_set():
+            va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions)
+        elif logp and self._see_network_set():
             raise ValueError("logp is the policy slots' record: the see network has no policy head")
-        if net_index or agent_obs is not None or logp:
-            return self._rollout_net(T, ptr, ro, rec, out, keep, net_index, agent_obs, logp)
-        if rec is not None:
-            if rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or tuple(rec.shape[1:]) != (self.num_envs, M.MATCH_PLAYERS, 3):
-                raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{self.num_envs},22,3]")
-            _capi.check(self.lib, self.lib.s2d_match_rollout_ex(self._h, T, ptr, C.byref(ro), C.c_void_p(rec.data_ptr()), self._stream()),
-                        's2d_match_rollout_ex')
+        elif net_index or agent_obs is not None or logp:
+            idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
+            obs, mask = None, 0
+            if agent_obs is not None:
+                mask = M.agent_slot_mask(agent_obs)
+                obs = self._record(out, 'agent_obs', T, (n, bin(mask).count('1'), M.AGENT_OBS_DIM), torch.float32)
+            if logp:
+                lp = self._record(out, 'logp', T, (n, M.MATCH_PLAYERS), torch.float32)
+                _capi.check(self.lib, self.lib.s2d_match_rollout_policy(self._h, T, ptr, C.byref(ro), _ptr(rec), _ptr(idx), _ptr(lp),
+                                                                         mask, _ptr(obs), st), 's2d_match_rollout_policy')
+            else:
+                _capi.check(self.lib, self.lib.s2d_match_rollout_net(self._h, T, ptr, C.byref(ro), _ptr(rec), _ptr(idx), mask,
+                                                                      _ptr(obs), st), 's2d_match_rollout_net')
+        elif rec is not None:
+            _capi.check(self.lib, self.lib.s2d_match_rollout_ex(self._h, T, ptr, C.byref(ro), _ptr(rec), st), 's2d_match_rollout_ex')
         else:
-            _capi.check(self.lib, self.lib.s2d_match_rollout(self._h, T, ptr, C.byref(ro), self._stream()), 's2d_match_rollout')
-        self._keep = (keep, out)
+            _capi.check(self.lib, self.lib.s2d_match_rollout(self._h, T, ptr, C.byref(ro), st), 's2d_match_rollout')
+        self._keep = (keep, out, va)
         return out
 
-    def _rollout_net(self, T, ptr, ro, rec, out, keep, net_index, agent_obs, logp=False):
-        n, dev = self.num_envs, self.device
-        if rec is not None and (rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or
-                                tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
-            raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{n},22,3]")
-        idx = None
-        if net_index:
-            idx = out.get('net_index')
-            if idx is None:
-                idx = out['net_index'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.int32, device=dev)
-            elif idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape[0] < T or tuple(idx.shape[1:]) != (n, M.MATCH_PLAYERS):
-                raise ValueError(f"rollout buffer 'net_index' must be contiguous int32 [T>={T},{n},22]")
-        obs, mask = None, 0
-        if agent_obs is not None:
-            mask = M.agent_slot_mask(agent_obs)
-            shape = (n, bin(mask).count('1'), M.AGENT_OBS_DIM)
-            obs = out.get('agent_obs')
-            if obs is None:
-                obs = out['agent_obs'] = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
-            elif obs.dtype != torch.float32 or not obs.is_contiguous() or obs.shape[0] < T or tuple(obs.shape[1:]) != shape:
-                raise ValueError(f"rollout buffer 'agent_obs' must be contiguous float32 [T>={T},{n},{shape[1]},224]")
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        if logp:
-            lp = out.get('logp')
-            if lp is None:
-                lp = out['logp'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.float32, device=dev)
-            elif lp.dtype != torch.float32 or not lp.is_contiguous() or lp.shape[0] < T or tuple(lp.shape[1:]) != (n, M.MATCH_PLAYERS):
-                raise ValueError(f"rollout buffer 'logp' must be contiguous float32 [T>={T},{n},22]")
-            _capi.check(self.lib, self.lib.s2d_match_rollout_policy(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), vp(lp), mask,
-                                                                     vp(obs), self._stream()), 's2d_match_rollout_policy')
-            self._keep = (keep, out)
-            return out
-        _capi.check(self.lib, self.lib.s2d_match_rollout_net(self._h, T, ptr, C.byref(ro), vp(rec), vp(idx), mask, vp(obs),
-                                                              self._stream()), 's2d_match_rollout_net')
-        self._keep = (keep, out)
-        return out
-
-    def _rollout_see(self, T, ptr, ro, rec, out, keep, net_index, see_obs, view_actions):
+    def _rollout_see(self, T, ptr, ro, rec, out, net_index, see_obs, view_actions):
+        """the see network's rollout, or the record-only one; returns the view actions' tensor (for the caller to keep alive)"""
         n, dev = self.num_envs, self.device
         self._need_vision()
-        if rec is not None and (rec.dtype != torch.float32 or not rec.is_contiguous() or rec.shape[0] < T or
-                                tuple(rec.shape[1:]) != (n, M.MATCH_PLAYERS, 3)):
-            raise ValueError(f"rollout buffer 'actions' must be contiguous float32 [T>={T},{n},22,3]")
         record_only = not self._see_network_set()
         if record_only and (self.network is not None or self.opponent_network is not None):
             raise ValueError("see_obs / view_actions need a see network or no network (the engine has an agent-row network set)")
-        idx = None
-        if net_index:
-            idx = out.get('net_index')
-            if idx is None:
-                idx = out['net_index'] = torch.empty((T, n, M.MATCH_PLAYERS), dtype=torch.int32, device=dev)
-            elif idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape[0] < T or tuple(idx.shape[1:]) != (n, M.MATCH_PLAYERS):
-                raise ValueError(f"rollout buffer 'net_index' must be contiguous int32 [T>={T},{n},22]")
+        idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
         va = None
         if view_actions is not None:
             va = torch.as_tensor(view_actions, device=dev).to(torch.float32).contiguous()
@@ -345,26 +325,19 @@ class MatchEngine:
         see, mask = None, 0
         if see_obs is not None:
             mask = M.agent_slot_mask(see_obs)
-            shape = (n, bin(mask).count('1'), M.SEE_DIM)
-            see = out.get('see')
-            if see is None:
-                see = out['see'] = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
-            elif see.dtype != torch.float32 or not see.is_contiguous() or see.shape[0] < T or tuple(see.shape[1:]) != shape:
-                raise ValueError(f"rollout buffer 'see' must be contiguous float32 [T>={T},{n},{shape[1]},192]")
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            see = self._record(out, 'see', T, (n, bin(mask).count('1'), M.SEE_DIM), torch.float32)
         if record_only:                                  # no network: the vision state stepped and recorded in-kernel for this call
             net = M.S2DMatchSeeNet()
             net.h1, net.h2, net.n_actions, net.slot_mask = 16, 16, 1, 0
             net.prm, net.vis = self.vision_params, self.vision
             _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
         try:
-            _capi.check(self.lib, self.lib.s2d_match_rollout_see(self._h, T, ptr, vp(va), C.byref(ro), vp(rec), vp(idx), mask, vp(see),
-                                                                  self._stream()), 's2d_match_rollout_see')
+            _capi.check(self.lib, self.lib.s2d_match_rollout_see(self._h, T, ptr, _ptr(va), C.byref(ro), _ptr(rec), _ptr(idx), mask,
+                                                                  _ptr(see), self._stream()), 's2d_match_rollout_see')
         finally:
             if record_only:
                 _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, None), 's2d_match_set_see_network')
-        self._keep = (keep, out, va)
-        return out
+        return va
 
     def kernel_name(self):
         """which instantiation of the cycle kernel this engine launches (`<stock>`: rules and physics folded into the code)"""

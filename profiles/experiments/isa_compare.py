@@ -1,6 +1,6 @@
 """Compare the device code of two source trees kernel by kernel (the method of profiles/r05/qnet_actor_isa.txt).
 
-Every unit of gym-soccer-2d-env_amd/csrc is compiled in both trees with the flags of the Makefile plus --cuda-device-only,
+Every unit of gym-soccer-2d-env_amd/csrc (SRCS of the new tree's Makefile) is compiled in both trees with the flags of the Makefile plus --cuda-device-only,
 llvm-objdump -d splits the code object into kernel symbols, and each kernel's instructions are compared one by one:
 comments, <symbol> targets, s_nop 0 and end-of-function padding stripped, PC-relative literals masked.  No GPU needed.
 
@@ -16,9 +16,17 @@ import tempfile
 ROCM = os.environ.get('ROCM_PATH', '/opt/rocm')
 HIPCC = os.path.join(ROCM, 'bin', 'hipcc')
 OBJDUMP = os.path.join(ROCM, 'llvm', 'bin', 'llvm-objdump')
-UNITS = ('s2d_engine.hip', 's2d_rollout2.hip', 's2d_match.hip', 's2d_gtc.hip', 's2d_actor.hip')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC', '-fvisibility=hidden', '--cuda-device-only',
          '--no-gpu-bundle-output']
+
+
+def units(tree):
+    """the translation units of the library: SRCS of the tree's csrc/Makefile"""
+    with open(os.path.join(tree, 'gym-soccer-2d-env_amd', 'csrc', 'Makefile')) as f:
+        m = re.search(r'^SRCS\s*:?=\s*((?:.*\\\n)*.*)$', f.read(), re.M)
+    if not m:
+        sys.exit(f'no SRCS in the Makefile of {tree}')
+    return tuple(m.group(1).replace('\\\n', ' ').split())
 
 
 def disasm(tree, unit, out):
@@ -55,7 +63,7 @@ def main():
     ren = dict(r.split('=', 1) for r in a.rename)
     differ = 0
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in UNITS:
+        for unit in units(a.new):
             os.makedirs(os.path.join(tmp, 'old'), exist_ok=True)
             os.makedirs(os.path.join(tmp, 'new'), exist_ok=True)
             old, new = disasm(a.old, unit, os.path.join(tmp, 'old')), disasm(a.new, unit, os.path.join(tmp, 'new'))
