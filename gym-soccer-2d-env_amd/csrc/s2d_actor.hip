@@ -26,192 +26,10 @@
 #include <string>
 
 #include "s2d_actor_net.h"
+#include "s2d_actor_rollout.h"
 
-// experiment build (-DS2D_QNET_STAMPS, profiles/experiments/qnet_actor_clocks.py): per wave, the shader clocks (s_memtime) of the
-// network (observation tile + three layers + argmax), of the rest of the cycle (action draw, simulation, record stores) and of the
-// prologue, summed over the launch; lane 0 writes them as floats into terminal_obs row wave_first of the arena
-#ifdef S2D_QNET_STAMPS
-#define QS_DECL uint64_t qs_net = 0, qs_rest = 0, qs_t = __builtin_amdgcn_s_memtime(); const uint64_t qs_begin = qs_t; uint64_t qs_pro = 0
-#define QS_MARK(acc) do { const uint64_t qs_now = __builtin_amdgcn_s_memtime(); acc += qs_now - qs_t; qs_t = qs_now; } while (0)
-#define QS_STORE() do { if (lane == 0) { float* q_ = o.terminal_obs + wave_first * S2D_OBS_DIM; q_[0] = (float)qs_net; \
-    q_[1] = (float)qs_rest; q_[2] = (float)qs_pro; q_[3] = (float)(__builtin_amdgcn_s_memtime() - qs_begin); } } while (0)
-#else
-#define QS_DECL do {} while (0)
-#define QS_MARK(acc) do {} while (0)
-#define QS_STORE() do {} while (0)
-#endif
-
-// the deterministic policy's action of one env (lane = env), not exploring: a_j = tanh_spec(y_j), with GAUSS + clip(mu_j +
-// sigma_j z_j), z from Box-Muller on POLICY block 3 (TURN4: z0..z3 of the block at counter k; CONT1: z_{k & 3} of the block at
-// counter k >> 2, cached in gquad).  noise = [2][A] (mu, sigma) in device memory.
-template <int MODE, bool GAUSS>
-S2D_DEV Action4 tanh_action(const S2DHot& p, const float* __restrict__ y, const float* __restrict__ noise, uint32_t gl, uint32_t gh,
-                            uint32_t k, const U4& gquad) {
-  constexpr int A = MODE == S2D_MODE_TURN4 ? 4 : 1;
-  float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int j = 0; j < A; ++j) a[j] = tanh_spec(y[j]);
-  if constexpr (GAUSS) {
-    float z[4];
-    if constexpr (MODE == S2D_MODE_TURN4) {
-      const U4 w = s2d_draw(p, gl, gh, k, S2D_ST_POLICY, 3);
-      box_muller(w.x, w.y, z[0], z[1]);
-      box_muller(w.z, w.w, z[2], z[3]);
-    } else {
-      const bool hi = (k & 2u) != 0u;
-      float zc, zs;
-      box_muller(hi ? gquad.z : gquad.x, hi ? gquad.w : gquad.y, zc, zs);
-      z[0] = (k & 1u) ? zs : zc;
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-      const float v = a[j] + fmaf(noise[A + j], z[j], noise[j]);
-      a[j] = v < -1.0f ? -1.0f : v > 1.0f ? 1.0f : v;
-    }
-  }
-  return Action4{a[0], a[1], a[2], a[3]};
-}
-
-// the noise buffer of the tanh-head instantiations (Noise = const float*); the Q-actor's have no such argument
-S2D_DEV const float* actor_noise() { return nullptr; }
-S2D_DEV const float* actor_noise(const float* p) { return p; }
-
-// The fused rollout of both actors.  MODE = S2D_MODE_DISCRETE: the Q-network's epsilon-greedy argmax (s2d_rollout_qnet);
-// CONT1 / TURN4: the deterministic tanh policy with epsilon-random exploration and optional Gaussian action noise (GAUSS,
-// s2d_rollout_actor).  One body, so that both share the prologue, the simulation, the records and the epilogue.  The noise
-// buffer is a trailing argument pack, empty for the Q-actor, so that its kernel arguments, and its code, stay as they were.
-template <int MODE, int NK, bool GAUSS, typename... Noise>
-__global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot p_sgpr, const S2DRare* __restrict__ rp,
-                                                                         float* __restrict__ S, int64_t stride, int64_t n,
-                                                                         int n_steps, QNetDims d, const float* __restrict__ params,
-                                                                         const float* __restrict__ eps_dev, RolloutOut ro,
-                                                                         float* __restrict__ term_rec, StepOut o, int wave_words,
-                                                                         Noise... noise_arg) {
-  const float* __restrict__ noise = actor_noise(noise_arg...);
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  QS_DECL;
-  const S2DHot p = hot_in_vgprs(p_sgpr);
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t wave_first = i - lane;
-
-  // ---- the network in fragment order (block-wide, once per launch)
-  net_pack(d, params, smem);
-  float* const wbase = smem + net_shared_words(d) + wv * wave_words;
-  float* const ha = wbase;
-  float* const hb = ha + 16 * d.pitch;
-  float* const qv = hb + 16 * d.pitch;
-  float* const tile = qv + kWave * d.qpitch;
-  PrepTile* const prep = reinterpret_cast<PrepTile*>(tile + kObsTile);
-  __syncthreads();
-  if (wave_first >= n) return;
-
-  const bool active = i < n;
-  int64_t rows = n - wave_first; if (rows > kWave) rows = kWave;
-  const int valid = (int)rows * S2D_OBS_DIM;
-  const uint64_t thr = explore_threshold(*eps_dev);
-  uint32_t* const kplane = reinterpret_cast<uint32_t*>(S + F_POLICY * stride);
-  Env e;
-  uint32_t gl = 0, gh = 0, k0 = 0;
-  ObsOut ob;
-#pragma unroll
-  for (int k = 0; k < S2D_OBS_DIM; ++k) ob.o[k] = 0.0f;
-  if (active) {
-    env_load(e, S, stride, i);
-    k0 = kplane[i];
-    uint64_t gid = (((uint64_t)p.gid_hi << 32) | p.gid_lo) + (uint64_t)i;
-    gl = (uint32_t)gid; gh = (uint32_t)(gid >> 32);
-    observe(p, e.px, e.py, e.body, e.bx, e.by, e.bvx, e.bvy, ob);   // what the last step / reset returned for this state
-  }
-  float reward = 0.0f, dir = 0.0f; int done = 0, res = 0, cmd = 0;
-  unsigned int cnt1 = 0, cnt2 = 0, cnt3 = 0;
-  float* const term_row = o.terminal_obs + i * S2D_OBS_DIM;
-  U4 quad{0, 0, 0, 0}, equad{0, 0, 0, 0}, squad{0, 0, 0, 0}, gquad{0, 0, 0, 0};
-  bool have_prep = false;
-  uint32_t* const coop_scratch = reinterpret_cast<uint32_t*>(tile);
-  if (p.auto_reset) {
-    prep_fill_coop<NK>(p, rp, *prep, lane, active ? reset_key(e) : 0u, gl, gh, active, coop_scratch);
-    have_prep = active;
-  }
-  int n_missing = 0;
-  int64_t row = 0;
-  QS_MARK(qs_pro);
-  for (int t = 0; t < n_steps; ++t, row += n) {
-    res = 0;
-    if (n_missing >= kRefillMin) {
-      if (active && !have_prep) { prep_fill<NK>(p, rp, *prep, lane, e, gl, gh); have_prep = true; }
-      n_missing = 0;
-    }
-    // the action of step t from the observation returned by step t - 1 (the launch's start state at t = 0)
-    wave_lds_fence();
-    tile_write(tile, ob, lane, active);
-    wave_lds_fence();
-    int greedy = 0;
-    float y[4];
-    if constexpr (MODE == S2D_MODE_DISCRETE) {
-      greedy = net_forward<true>(d, smem, ha, hb, qv, tile, lane);
-    } else {
-      net_forward<false>(d, smem, ha, hb, qv, tile, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = qv[lane * d.qpitch + j];   // A <= 4 of the 16 rows of the one output tile
-      wave_lds_fence();
-    }
-    QS_MARK(qs_net);
-    if (active) {
-      const uint32_t k = k0 + (uint32_t)t;
-      CmdPrep c;
-      if constexpr (MODE == S2D_MODE_DISCRETE) {
-        if (t == 0 || (k & 3u) == 0u) {
-          quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);                      // block 0: S2D_ACT_RANDOM's draw
-          equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
-        }
-        const bool explore = (uint64_t)quad_word(equad, k) < thr;
-        const int a = explore ? rnd_below(quad_word(quad, k), (uint32_t)p.n_actions) : greedy;
-        if (ro.action) static_cast<int32_t*>(ro.action)[row + i] = a;
-        c = decode_action<S2D_MODE_DISCRETE>(p, Action4{(float)a, 0.0f, 0.0f, 0.0f}, gl, gh, k, false, squad, cmd, dir);
-      } else {
-        const bool refresh = t == 0 || (k & 3u) == 0u;
-        if (refresh) {
-          equad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 2);                // block 2: explore or not
-          if (MODE == S2D_MODE_CONT1) quad = policy_quad(p, gl, gh, k, S2D_ST_POLICY);              // block 0: the random action
-          if (GAUSS && MODE == S2D_MODE_CONT1) gquad = s2d_draw(p, gl, gh, k >> 2, S2D_ST_POLICY, 3);   // block 3: noise
-        }
-        const bool explore = (uint64_t)quad_word(equad, k) < thr;
-        const Action4 a = explore ? random_action<MODE>(p, gl, gh, k, quad, false) : tanh_action<MODE, GAUSS>(p, y, noise, gl, gh, k, gquad);
-        if (ro.action) store_rollout_action<MODE>(ro.action, row + i, a);
-        c = decode_action<MODE>(p, a, gl, gh, k, refresh, squad, cmd, dir);
-      }
-      step_env<NK, false>(p, rp, e, gl, gh, k, cmd, c, ob, reward, done, res, term_row, prep, lane, have_prep);
-      if (ro.reward) ro.reward[row + i] = reward;
-      if (ro.done) ro.done[row + i] = (uint8_t)done;
-      if (ro.result) ro.result[row + i] = (uint8_t)res;
-      if (term_rec && done) {                              // the observation the finished episode ended on
-        float* const dst = term_rec + (row + i) * S2D_OBS_DIM;
-#pragma unroll
-        for (int k2 = 0; k2 < S2D_OBS_DIM; ++k2) dst[k2] = p.auto_reset ? term_row[k2] : ob.o[k2];
-      }
-      cnt1 += res == S2D_RESULT_GOAL; cnt2 += res == S2D_RESULT_OUT; cnt3 += res == S2D_RESULT_TIMEOUT;
-    }
-    if (p.auto_reset) n_missing += __popcll(__ballot(active && done != 0));
-    if (ro.obs) store_obs_tile(tile, ob, lane, active, ro.obs + (row + wave_first) * S2D_OBS_DIM, valid);
-    QS_MARK(qs_rest);
-  }
-  if (active) {
-    env_store(e, S, stride, i);
-    kplane[i] = k0 + (uint32_t)n_steps;
-    o.reward[i] = reward; o.done[i] = (uint8_t)done; o.result[i] = (uint8_t)res;
-    o.action_dir[i] = dir; o.action_cmd[i] = (uint8_t)cmd;
-  }
-  store_obs_tile(tile, ob, lane, active, o.obs + wave_first * S2D_OBS_DIM, valid);
-  if (!active) { cnt1 = cnt2 = cnt3 = 0; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt1 += __shfl_xor(cnt1, off); cnt2 += __shfl_xor(cnt2, off); cnt3 += __shfl_xor(cnt3, off);
-  }
-  unsigned long long* const srow = stats_row(o.stats, wave_first);
-  stats_store(srow, lane, stats_load(srow, lane), wave_first == 0 ? (unsigned long long)n * (unsigned long long)n_steps : 0ull, cnt1, cnt2, cnt3);
-  QS_STORE();
-}
+// The fused rollout of both actors is s2d_reach_actor_rollout_kernel<MODE, NK, GAUSS, Dims, Noise...> of s2d_actor_rollout.h, here
+// with Dims = QNetDims (net_pack, net_shared_words and net_forward of s2d_actor_net.h).
 
 // diagnostic (s2d_debug_net_forward): the rollout's network on caller observations.  The same packing, LDS layout and
 // net_forward as s2d_reach_actor_rollout_kernel; the observation tile holds obs[i] for the wave's envs i < n and zero rows past
@@ -259,9 +77,9 @@ extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRar
   int wave_words, waves;
   size_t lds;
   if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
-  static const QNetKernel table[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false>,
-                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false>,
-                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false>};
+  static const QNetKernel table[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false, QNetDims>,
+                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false, QNetDims>,
+                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false, QNetDims>};
   if (!allow_lds(reinterpret_cast<const void*>(table[nk]), nk)) return -2;
   const int threads = waves * kWave;
   const unsigned blocks = (unsigned)((n + threads - 1) / threads);
@@ -281,9 +99,9 @@ extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2D
   size_t lds;
   if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
 #define S2D_DDPG_ROW(M)                                                                                                          \
-  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, const float*>,                 \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, const float*>,                   \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, const float*>}
+  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, QNetDims, const float*>,                 \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, QNetDims, const float*>,                   \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, QNetDims, const float*>}
   static const TanhKernel table[2][6] = {S2D_DDPG_ROW(S2D_MODE_CONT1), S2D_DDPG_ROW(S2D_MODE_TURN4)};
 #undef S2D_DDPG_ROW
   const int m = mode == S2D_MODE_TURN4 ? 1 : 0, v = 3 * gauss + nk;

@@ -101,7 +101,7 @@ static constexpr int kMaxDevices = 64;
 
 // the LDS plan of a 10-h1-h2-na network: dims, per-wave words and the wave count per workgroup (as many as the LDS holds, 4 for
 // 10-64-64-16); false if one wave does not fit
-static bool plan_lds(int h1, int h2, int na, QNetDims& d, int& wave_words, int& waves, size_t& lds) {
+static inline bool plan_lds(int h1, int h2, int na, QNetDims& d, int& wave_words, int& waves, size_t& lds) {
   d.h1 = h1; d.h2 = h2; d.na = na; d.na16 = (na + 15) / 16 * 16;
   const int wmax = h1 > h2 ? h1 : h2;
   d.pitch = (wmax + 63) / 64 * 64 + 4;

@@ -33,8 +33,14 @@ kewargs = {
 }
 
 
-def mlp(n_in, n_out, hidden=64, tanh=False):
-    layers = [nn.Linear(n_in, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, n_out)]
+def mlp(n_in, n_out, hidden=64, tanh=False, net_arch=None, activation='relu'):
+    """net_arch / activation: SB3's policy_kwargs=dict(net_arch=dict(pi=[16, 8], qf=[...]), activation_fn=nn.Tanh)"""
+    act = nn.Tanh if activation == 'tanh' else nn.ReLU
+    layers = []
+    for w in (net_arch or (hidden, hidden)):
+        layers += [nn.Linear(n_in, w), act()]
+        n_in = w
+    layers.append(nn.Linear(n_in, n_out))
     return nn.Sequential(*(layers + ([nn.Tanh()] if tanh else [])))
 
 
@@ -62,11 +68,12 @@ class DeviceReplay:
 
 class DeviceDDPG:
     def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
-                 learning_starts=2, seed=0):
+                 learning_starts=2, seed=0, net_arch=None, activation='relu'):
         torch.manual_seed(seed)
         self.env, self.dev = env, env.device
         n_obs, self.n_act = env.observation_space.shape[0], env.action_space.shape[0]
-        self.mu = mlp(n_obs, self.n_act, tanh=True).to(self.dev)
+        self.general = net_arch is not None or activation != 'relu'      # an actor only the general fused actor takes
+        self.mu = mlp(n_obs, self.n_act, tanh=True, net_arch=net_arch, activation=activation).to(self.dev)
         self.q = mlp(n_obs + self.n_act, 1).to(self.dev)
         self.mu_target, self.q_target = copy.deepcopy(self.mu), copy.deepcopy(self.q)
         self.opt_mu = torch.optim.Adam(self.mu.parameters(), lr=lr)
@@ -125,8 +132,10 @@ class DeviceDDPG:
         """The same DDPG, experience collected T steps per launch by the fused actor (the learner's own actor in-kernel):
         epsilon = 1 (uniform random actions) for the first learning_starts launches, then the noisy actor."""
         from soccer2d_amd.actor import DeterministicActor
+        from soccer2d_amd.mlp_actor import MlpDeterministicActor
         if not hasattr(self, 'actor'):
-            self.actor = DeterministicActor.from_module(self.mu, device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
+            cls = MlpDeterministicActor if self.general else DeterministicActor
+            self.actor = cls.from_module(self.mu, device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
         for _ in range((vec_steps + T - 1) // T):
@@ -165,11 +174,15 @@ def main():
     ap.add_argument('--turning', action='store_true', help='use_turning=True: the 4-D action')
     ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
                     help='collect T steps per launch with the in-kernel actor (0: one torch forward per step)')
+    ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
+                    help="the actor's hidden widths, e.g. 16,8 (1 to 4 multiples of 8 up to 128; default: 64,64)")
+    ap.add_argument('--activation', choices=('relu', 'tanh'), default='relu')
     args = ap.parse_args()
+    net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
-    model = DeviceDDPG(env)
+    model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -34,10 +34,15 @@ kewargs = {                      # dqn_stable_baselines3.py:18-31
 
 
 class QNet(nn.Module):           # SB3 DQN "MlpPolicy" default: two hidden layers of 64
-    def __init__(self, n_obs=10, n_act=16, hidden=64):
+    def __init__(self, n_obs=10, n_act=16, hidden=64, net_arch=None, activation='relu'):
+        """net_arch / activation: SB3's policy_kwargs=dict(net_arch=[128, 64, 32, 16], activation_fn=nn.Tanh)"""
         super().__init__()
-        self.net = nn.Sequential(nn.Linear(n_obs, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(),
-                                 nn.Linear(hidden, n_act))
+        act = nn.Tanh if activation == 'tanh' else nn.ReLU
+        layers, n_in = [], n_obs
+        for w in (net_arch or (hidden, hidden)):
+            layers += [nn.Linear(n_in, w), act()]
+            n_in = w
+        self.net = nn.Sequential(*layers, nn.Linear(n_in, n_act))
 
     def forward(self, x):
         return self.net(x)
@@ -67,11 +72,12 @@ class DeviceReplay:
 
 class DeviceDQN:
     def __init__(self, env, lr=1e-3, gamma=0.99, buffer=1 << 20, batch=4096, target_every=50, grad_steps=4,
-                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0):
+                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu'):
         torch.manual_seed(seed)
         self.env, self.dev = env, env.device
         self.n_act = env.action_space.n
-        self.q = QNet(env.observation_space.shape[0], self.n_act).to(self.dev)
+        self.general = net_arch is not None or activation != 'relu'      # a network only the general fused actor takes
+        self.q = QNet(env.observation_space.shape[0], self.n_act, net_arch=net_arch, activation=activation).to(self.dev)
         self.q_target = copy.deepcopy(self.q)
         self.opt = torch.optim.Adam(self.q.parameters(), lr=lr)
         self.rb = DeviceReplay(buffer, env.observation_space.shape[0], self.dev)
@@ -133,8 +139,10 @@ class DeviceDQN:
         """The same DQN, experience collected T steps per launch by the fused actor (the learner's own network in-kernel):
         per launch T x N transitions into the replay buffer, then grad_steps updates per collected vector step, then sync()."""
         from soccer2d_amd.actor import QNetActor
+        from soccer2d_amd.mlp_actor import MlpQNetActor
         if not hasattr(self, 'actor'):
-            self.actor = QNetActor.from_module(self.q, device=self.dev, epsilon=self.epsilon())
+            cls = MlpQNetActor if self.general else QNetActor
+            self.actor = cls.from_module(self.q, device=self.dev, epsilon=self.epsilon())
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
         for _ in range((vec_steps + T - 1) // T):
@@ -188,10 +196,14 @@ def main():
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
                     help='collect T steps per launch with the in-kernel epsilon-greedy actor (0: one torch forward per step)')
+    ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
+                    help='hidden widths, e.g. 128,64,32,16 (1 to 4 multiples of 8 up to 128; default: 64,64)')
+    ap.add_argument('--activation', choices=('relu', 'tanh'), default='relu')
     args = ap.parse_args()
+    net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
-    model = DeviceDQN(env)
+    model = DeviceDQN(env, net_arch=net_arch, activation=args.activation)
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

@@ -119,6 +119,13 @@ class S2DPolicyNet(C.Structure):
                 ('params', C.c_void_p), ('log_std', C.c_void_p), ('deterministic', C.c_void_p)]
 
 
+class S2DMlpNet(C.Structure):
+    """the caller's general MLP of s2d_rollout_qnet_mlp / s2d_rollout_actor_mlp (1 .. 4 hidden widths, outputs, activation 0 ReLU
+    / 1 Tanh, noise kind; device pointers as S2DQNet's / S2DActorNet's)"""
+    _fields_ = [('n_hidden', C.c_int32), ('hidden', C.c_int32 * 4), ('n_out', C.c_int32), ('activation', C.c_int32),
+                ('noise_kind', C.c_int32), ('params', C.c_void_p), ('epsilon', C.c_void_p), ('noise', C.c_void_p)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -148,6 +155,8 @@ PROTOTYPES = (
     ('s2d_step_k', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(S2DRollout), C.c_void_p)),
     ('s2d_rollout_qnet', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DQNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_actor', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DActorNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_rollout_qnet_mlp', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DMlpNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_rollout_actor_mlp', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DMlpNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DPolicyNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p,
                                      C.c_void_p)),
     ('s2d_gae', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
@@ -160,6 +169,7 @@ PROTOTYPES = (
     ('s2d_debug_eval', C.c_int, (C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)),
     ('s2d_debug_net_forward', C.c_int, (C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_char_p, C.c_void_p)),
+    ('s2d_debug_mlp_forward', C.c_int, (C.POINTER(S2DMlpNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p)),
     ('s2d_debug_policy_head', C.c_int, (C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)),
 )

@@ -223,6 +223,34 @@ typedef struct S2DPolicyNet {
   const uint32_t *deterministic;
 } S2DPolicyNet;
 
+/* The caller's network for s2d_rollout_qnet_mlp / s2d_rollout_actor_mlp: a general MLP 10 -> h_1 -> ... -> h_L -> n_out (DESIGN.md
+ * section 4), for the networks SB3's policy_kwargs=dict(net_arch=[...], activation_fn=...) build.  One to four hidden layers;
+ * every hidden width a multiple of 8 in [8, 128] (the weights live in LDS); one hidden activation for the whole network, relu or
+ * tanh_spec; the output layer is linear.  The observation is x[0..9], h_0 = 10:
+ *   params    torch's nn.Sequential(Linear, F, ..., Linear).parameters() order: W_1[h_1][10], b_1, ..., W_L[h_L][h_(L-1)], b_L,
+ *             W_out[n_out][h_L], b_out, in one contiguous, 16-byte aligned fp32 device buffer;
+ *   units     every unit is acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc);
+ *   layer 1   runs over k = 0 .. 11 with x_10 = x_11 = 0 against zero weights: two more fmaf(0, 0, acc), which turn an
+ *             accumulator of -0 into +0 (invisible behind relu, visible behind tanh_spec; part of the spec);
+ *   layers 2 .. L and the output layer run over exactly k = 0 .. h_(l-1) - 1 (a width that is a multiple of 8 but not of 16
+ *             pads the output rows of its tile; no padded unit is ever read and no extra fmaf enters a chain);
+ *   hidden    relu(v) = v > 0 ? v : +0, or tanh_spec(v);
+ *   heads     s2d_rollout_qnet's (the argmax scan, epsilon-greedy at policy_step k, Philox blocks 0 and 2) and
+ *             s2d_rollout_actor's (tanh_spec(y_j), optional Gaussian noise from block 3, clip, epsilon-random exploration),
+ *             unchanged: no draw, key or counter differs.
+ * With n_hidden = 2, both widths multiples of 16 and activation 0 the result is s2d_rollout_qnet's / s2d_rollout_actor's bit
+ * for bit.  epsilon and noise as S2DQNet's / S2DActorNet's; params, epsilon and noise are read when the kernel runs.  A
+ * network whose fragments and biases plus one wave's images exceed the 160 KiB LDS of a workgroup is refused
+ * ([128, 64, 32, 16] with 16 outputs runs with 2 waves per workgroup; [128, 128, 128] does not fit). */
+typedef struct S2DMlpNet {
+  int32_t n_hidden;        /* 1 .. 4 */
+  int32_t hidden[4];       /* multiples of 8 in [8, 128]; entries past n_hidden are 0 */
+  int32_t n_out;           /* Q: action_space_size, 1 .. 64; tanh actor: 1 | 4 */
+  int32_t activation;      /* 0 relu, 1 tanh_spec */
+  int32_t noise_kind;      /* tanh actor only: 0 | 1; must be 0 for the Q actor */
+  const float *params, *epsilon, *noise;   /* as S2DQNet / S2DActorNet */
+} S2DMlpNet;
+
 /* Derived protobuf-mirroring fields that are not plain state words (row T1).  Each array
  * is [N]; NULL pointers are skipped.                                                       */
 typedef struct S2DWorldModel {
@@ -300,6 +328,16 @@ int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet *net, const S2DRoll
  * 16, noise_kind not in {0, 1}, NULL or misaligned params / epsilon / noise (noise only with kind 1), n_steps < 1, a network
  * that does not fit the LDS. */
 int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+/* s2d_rollout_qnet (discrete engines) and s2d_rollout_actor (continuous and turning engines) with the general MLP of S2DMlpNet.
+ * Records, terminal_obs, graph capture, policy_step, statistics and the per-step outputs behave as their two-layer
+ * counterparts'; s2d_kernel_name() names the instantiation with its shape and waves per workgroup
+ * (...<noise=0,act=tanh,h=128-64-32-16,a=16,waves=2>).  Rejected with S2D_EINVAL, without a launch and with the state untouched:
+ * n_hidden outside 1..4, a width that is not a multiple of 8 in [8, 128], a non-zero hidden[] entry past n_hidden, activation
+ * outside {0, 1}, the wrong engine mode or an n_out that is not the engine's (action_space_size <= 64 | 1 | 4), noise_kind set
+ * on the Q path or outside {0, 1}, NULL or misaligned params / epsilon / noise (noise only with kind 1), n_steps < 1, and a
+ * network that does not fit the LDS (the error text says how many bytes it needs). */
+int s2d_rollout_qnet_mlp(S2DHandle h, int n_steps, const S2DMlpNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+int s2d_rollout_actor_mlp(S2DHandle h, int n_steps, const S2DMlpNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
 /* n_steps >= 1 cycles fused in ONE launch (every action mode) whose action at every cycle is SAMPLED from the caller's policy
  * on the env's observation, with the log-probability of the action taken recorded: on-policy collection (PPO / A2C).  Per env
  * and step at its policy_step k (advanced by one every step); every line one fixed fp32 operation:
@@ -391,6 +429,12 @@ int s2d_debug_eval(int op, const void *in_dev, void *out_dev, int64_t n, void *s
  * NULL or misaligned pointers. */
 int s2d_debug_net_forward(int h1, int h2, int na, const void *params_dev, const void *obs_dev, int64_t n, void *y_dev,
                           void *greedy_dev, char *name, void *stream);
+/* diagnostic: the same for the general MLP of s2d_rollout_qnet_mlp / s2d_rollout_actor_mlp, with their packing, LDS plan and
+ * layer loop.  shape: n_hidden, hidden, n_out (1 .. 64), activation and params are used, epsilon / noise / noise_kind ignored;
+ * obs_dev, y_dev = float[n][n_out], greedy_dev and name as above.  S2D_EINVAL without a launch: a shape s2d_rollout_qnet_mlp
+ * refuses, n not in 1..2^31 - 1, NULL or misaligned pointers. */
+int s2d_debug_mlp_forward(const S2DMlpNet *shape, const void *obs_dev, int64_t n, void *y_dev, void *greedy_dev, char *name,
+                          void *stream);
 /* diagnostic: the head of s2d_rollout_policy alone, on caller logits or means, so that its edge cases can be compared bit for
  * bit with the spec without running a rollout.  mode: 0 discrete (n_out = A in 1..64), 1 continuous (n_out = 1), 2 turning
  * (n_out = 4).  y_dev = float[n][n_out]; log_std_dev = float[n_out] (may be NULL with mode 0); gid_dev = uint64[n] global env

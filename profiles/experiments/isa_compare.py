@@ -4,7 +4,10 @@ Every unit of gym-soccer-2d-env_amd/csrc (SRCS of the new tree's Makefile) is co
 llvm-objdump -d splits the code object into kernel symbols, and each kernel's instructions are compared one by one:
 comments, <symbol> targets, s_nop 0 and end-of-function padding stripped, PC-relative literals masked.  No GPU needed.
 
-    python profiles/experiments/isa_compare.py OLD_TREE NEW_TREE [--rename OLD_SYM=NEW_SYM ...]
+    python profiles/experiments/isa_compare.py OLD_TREE NEW_TREE [--rename OLD_SYM=NEW_SYM ...] [--new-template-arg TEXT ...]
+
+--new-template-arg 'QNetDims, ': a kernel template of the new tree has gained the template argument TEXT; an old symbol is compared
+with the new symbol whose demangled name is the old one's once the first TEXT is taken out.  A unit that only the new tree has is listed as new.
 """
 import argparse
 import os
@@ -54,11 +57,17 @@ def disasm(tree, unit, out):
     return {k: v for k, v in funcs.items() if v}
 
 
+def demangled(syms):
+    out = subprocess.run(['c++filt'] + list(syms), check=True, capture_output=True, text=True).stdout
+    return dict(zip(syms, out.splitlines()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('old')
     ap.add_argument('new')
     ap.add_argument('--rename', action='append', default=[], help='OLD_SYM=NEW_SYM')
+    ap.add_argument('--new-template-arg', action='append', default=[], help='text of a template argument only the new symbols have')
     a = ap.parse_args()
     ren = dict(r.split('=', 1) for r in a.rename)
     differ = 0
@@ -66,7 +75,17 @@ def main():
         for unit in units(a.new):
             os.makedirs(os.path.join(tmp, 'old'), exist_ok=True)
             os.makedirs(os.path.join(tmp, 'new'), exist_ok=True)
-            old, new = disasm(a.old, unit, os.path.join(tmp, 'old')), disasm(a.new, unit, os.path.join(tmp, 'new'))
+            in_old = os.path.exists(os.path.join(a.old, 'gym-soccer-2d-env_amd', 'csrc', unit))   # a unit the new tree adds
+            old = disasm(a.old, unit, os.path.join(tmp, 'old')) if in_old else {}
+            new = disasm(a.new, unit, os.path.join(tmp, 'new'))
+            if a.new_template_arg and old and new:
+                dold, dnew = demangled(sorted(old)), demangled(sorted(new))
+                for nsym, name in dnew.items():
+                    for text in a.new_template_arg:
+                        name = name.replace(text, '', 1)                # its first occurrence: the template argument list
+                    for osym, oname in dold.items():
+                        if oname == name and osym not in new:
+                            ren[osym] = nsym
             for sym in sorted(old):
                 nsym = ren.get(sym, sym)
                 if nsym not in new:
