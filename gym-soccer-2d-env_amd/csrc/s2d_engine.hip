@@ -1073,6 +1073,14 @@ extern "C" int s2d_internal_rollout_qnet_mlp(int nk, const S2DHot* hot, const S2
 extern "C" int s2d_internal_rollout_actor_mlp(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
                                               int64_t n, int n_steps, const S2DMlpNet* net, const RolloutOut* ro, float* term_rec,
                                               const StepOut* o, void* stream, char* name, size_t name_bytes);
+// s2d_wide_actor.hip: the same for the streamed-weight network (the launches check the workspace before they enqueue anything)
+extern "C" int s2d_internal_wide_check(const char* who, const S2DWideNet* net);
+extern "C" int s2d_internal_rollout_qnet_wide(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
+                                              int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
+                                              const StepOut* o, void* stream, char* name, size_t name_bytes);
+extern "C" int s2d_internal_rollout_actor_wide(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
+                                               int64_t n, int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
+                                               const StepOut* o, void* stream, char* name, size_t name_bytes);
 
 struct S2DEngine {
   S2DConfig cfg;
@@ -1085,7 +1093,7 @@ struct S2DEngine {
   int rollout_ws;  // -1 auto (by batch size), 0 unified kernel, 1 wave-specialised kernel
   int rollout_e;   // envs per lane of the wave-specialised rollout: 2 (s2d_rollout2.hip, where the batch and the record allow it) or 1
   int rollout_nt;  // -1 by record size, 0 / 1: plain / non-temporal record stores (experiments)
-  char kernel_name[96];   // full instantiation of the last rollout launch
+  char kernel_name[160];   // full instantiation of the last rollout launch
   int64_t n, stride;
   int device;
   char* arena;
@@ -1678,6 +1686,78 @@ S2D_API int s2d_rollout_actor_mlp(S2DHandle h, int n_steps, const S2DMlpNet* net
                                                 sizeof h->kernel_name);
   if (rc == S2D_EINVAL) return S2D_EINVAL;
   if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor_mlp: hipGetDevice or hipFuncSetAttribute failed");
+  HIP_TRY(hipGetLastError());
+  h->last_kernel = h->kernel_name;
+  return S2D_OK;
+}
+
+S2D_API int s2d_rollout_qnet_wide(S2DHandle h, int n_steps, const S2DWideNet* net, const S2DRollout* out, float* terminal_obs,
+                                 void* stream) {
+  if (!h) return fail(S2D_EINVAL, "NULL handle");
+  if (!net) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: net is NULL");
+  const S2DReachBallParams& t = h->cfg.task;
+  if (t.use_continuous_action)
+    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide needs a discrete-action engine (use_continuous_action = 0); use s2d_rollout_actor_wide");
+  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: n_steps must be >= 1");
+  if (s2d_internal_wide_check("s2d_rollout_qnet_wide", net) != S2D_OK) return S2D_EINVAL;
+  if (net->n_out != t.action_space_size)
+    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: n_out must equal action_space_size and be in [1, 64]");
+  if (net->noise_kind != 0) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: noise_kind must be 0 (the Q actor has no action noise)");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: epsilon must be a non-NULL, 4-byte aligned device pointer");
+  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: terminal_obs must be 4-byte aligned");
+  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (out) {
+    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
+    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->action) & 3u) return fail(S2D_EINVAL, "rollout action buffer must be 4-byte aligned");
+  }
+  DeviceGuard guard(h->device);
+  const int rc = s2d_internal_rollout_qnet_wide(h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
+                                               n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name, sizeof h->kernel_name);
+  if (rc == S2D_EINVAL) return S2D_EINVAL;
+  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_qnet_wide: hipGetDevice or hipFuncSetAttribute failed");
+  HIP_TRY(hipGetLastError());
+  h->last_kernel = h->kernel_name;
+  return S2D_OK;
+}
+
+S2D_API int s2d_rollout_actor_wide(S2DHandle h, int n_steps, const S2DWideNet* net, const S2DRollout* out, float* terminal_obs,
+                                  void* stream) {
+  if (!h) return fail(S2D_EINVAL, "NULL handle");
+  if (!net) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: net is NULL");
+  if (h->mode == S2D_MODE_DISCRETE)
+    return fail(S2D_EINVAL, "s2d_rollout_actor_wide needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet_wide");
+  const int na = h->mode == S2D_MODE_TURN4 ? 4 : 1;
+  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: n_steps must be >= 1");
+  if (s2d_internal_wide_check("s2d_rollout_actor_wide", net) != S2D_OK) return S2D_EINVAL;
+  if (net->n_out != na)
+    return fail(S2D_EINVAL, h->mode == S2D_MODE_TURN4 ? "s2d_rollout_actor_wide: n_out must be 4 on a turning engine"
+                                                      : "s2d_rollout_actor_wide: n_out must be 1 on a continuous (non-turning) engine");
+  if (net->noise_kind != 0 && net->noise_kind != 1)
+    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: noise_kind must be 0 (none) or 1 (Gaussian)");
+  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
+    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: epsilon must be a non-NULL, 4-byte aligned device pointer");
+  if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
+    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
+  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: terminal_obs must be 4-byte aligned");
+  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (out) {
+    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
+    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
+      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
+  }
+  DeviceGuard guard(h->device);
+  const int rc = s2d_internal_rollout_actor_wide(h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
+                                                h->stride, h->n, n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name,
+                                                sizeof h->kernel_name);
+  if (rc == S2D_EINVAL) return S2D_EINVAL;
+  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor_wide: hipGetDevice or hipFuncSetAttribute failed");
   HIP_TRY(hipGetLastError());
   h->last_kernel = h->kernel_name;
   return S2D_OK;

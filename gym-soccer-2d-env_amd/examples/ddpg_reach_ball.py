@@ -35,7 +35,7 @@ kewargs = {
 
 def mlp(n_in, n_out, hidden=64, tanh=False, net_arch=None, activation='relu'):
     """net_arch / activation: SB3's policy_kwargs=dict(net_arch=dict(pi=[16, 8], qf=[...]), activation_fn=nn.Tanh)"""
-    act = nn.Tanh if activation == 'tanh' else nn.ReLU
+    act = {'relu': nn.ReLU, 'tanh': nn.Tanh, 'sigmoid': nn.Sigmoid}[activation]
     layers = []
     for w in (net_arch or (hidden, hidden)):
         layers += [nn.Linear(n_in, w), act()]
@@ -133,9 +133,17 @@ class DeviceDDPG:
         epsilon = 1 (uniform random actions) for the first learning_starts launches, then the noisy actor."""
         from soccer2d_amd.actor import DeterministicActor
         from soccer2d_amd.mlp_actor import MlpDeterministicActor
+        from soccer2d_amd.wide_actor import WideDeterministicActor
         if not hasattr(self, 'actor'):
-            cls = MlpDeterministicActor if self.general else DeterministicActor
-            self.actor = cls.from_module(self.mu, device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
+            kw = dict(device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
+            if not self.general:
+                self.actor = DeterministicActor.from_module(self.mu, **kw)
+            else:
+                try:
+                    self.actor = MlpDeterministicActor.from_module(self.mu, **kw)
+                except ValueError:      # SB3's default [400, 300], five layers, Sigmoid, or too large for the LDS: streamed weights
+                    self.actor = WideDeterministicActor.from_module(self.mu, **kw)
+            print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
         for _ in range((vec_steps + T - 1) // T):
@@ -175,8 +183,8 @@ def main():
     ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
                     help='collect T steps per launch with the in-kernel actor (0: one torch forward per step)')
     ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
-                    help="the actor's hidden widths, e.g. 16,8 (1 to 4 multiples of 8 up to 128; default: 64,64)")
-    ap.add_argument('--activation', choices=('relu', 'tanh'), default='relu')
+                    help="the actor's hidden widths, e.g. 16,8 or 400,300 (1 to 5 multiples of 4 up to 400; default: 64,64)")
+    ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)

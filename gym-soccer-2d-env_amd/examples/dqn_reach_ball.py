@@ -37,7 +37,7 @@ class QNet(nn.Module):           # SB3 DQN "MlpPolicy" default: two hidden layer
     def __init__(self, n_obs=10, n_act=16, hidden=64, net_arch=None, activation='relu'):
         """net_arch / activation: SB3's policy_kwargs=dict(net_arch=[128, 64, 32, 16], activation_fn=nn.Tanh)"""
         super().__init__()
-        act = nn.Tanh if activation == 'tanh' else nn.ReLU
+        act = {'relu': nn.ReLU, 'tanh': nn.Tanh, 'sigmoid': nn.Sigmoid}[activation]
         layers, n_in = [], n_obs
         for w in (net_arch or (hidden, hidden)):
             layers += [nn.Linear(n_in, w), act()]
@@ -140,9 +140,17 @@ class DeviceDQN:
         per launch T x N transitions into the replay buffer, then grad_steps updates per collected vector step, then sync()."""
         from soccer2d_amd.actor import QNetActor
         from soccer2d_amd.mlp_actor import MlpQNetActor
+        from soccer2d_amd.wide_actor import WideQNetActor
         if not hasattr(self, 'actor'):
-            cls = MlpQNetActor if self.general else QNetActor
-            self.actor = cls.from_module(self.q, device=self.dev, epsilon=self.epsilon())
+            kw = dict(device=self.dev, epsilon=self.epsilon())
+            if not self.general:
+                self.actor = QNetActor.from_module(self.q, **kw)
+            else:
+                try:
+                    self.actor = MlpQNetActor.from_module(self.q, **kw)
+                except ValueError:      # wider than 128, five layers, Sigmoid, or too large for the LDS: streamed weights
+                    self.actor = WideQNetActor.from_module(self.q, **kw)
+            print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
         for _ in range((vec_steps + T - 1) // T):
@@ -197,8 +205,8 @@ def main():
     ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
                     help='collect T steps per launch with the in-kernel epsilon-greedy actor (0: one torch forward per step)')
     ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
-                    help='hidden widths, e.g. 128,64,32,16 (1 to 4 multiples of 8 up to 128; default: 64,64)')
-    ap.add_argument('--activation', choices=('relu', 'tanh'), default='relu')
+                    help='hidden widths, e.g. 128,64,32,16 (1 to 5 multiples of 4 up to 400; default: 64,64)')
+    ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)

@@ -126,6 +126,14 @@ class S2DMlpNet(C.Structure):
                 ('noise_kind', C.c_int32), ('params', C.c_void_p), ('epsilon', C.c_void_p), ('noise', C.c_void_p)]
 
 
+class S2DWideNet(C.Structure):
+    """the caller's streamed-weight MLP of s2d_rollout_qnet_wide / s2d_rollout_actor_wide (1 .. 5 hidden widths up to 400, outputs,
+    activation 0 ReLU / 1 Tanh / 2 Sigmoid, noise kind; device pointers as S2DMlpNet's, and the workspace the pack kernel writes)"""
+    _fields_ = [('n_hidden', C.c_int32), ('hidden', C.c_int32 * 5), ('n_out', C.c_int32), ('activation', C.c_int32),
+                ('noise_kind', C.c_int32), ('params', C.c_void_p), ('epsilon', C.c_void_p), ('noise', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -157,6 +165,9 @@ PROTOTYPES = (
     ('s2d_rollout_actor', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DActorNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_qnet_mlp', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DMlpNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_actor_mlp', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DMlpNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_wide_workspace_bytes', C.c_size_t, (C.POINTER(S2DWideNet),)),
+    ('s2d_rollout_qnet_wide', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DWideNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_rollout_actor_wide', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DWideNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DPolicyNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p,
                                      C.c_void_p)),
     ('s2d_gae', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
@@ -170,6 +181,7 @@ PROTOTYPES = (
     ('s2d_debug_net_forward', C.c_int, (C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_char_p, C.c_void_p)),
     ('s2d_debug_mlp_forward', C.c_int, (C.POINTER(S2DMlpNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p)),
+    ('s2d_debug_wide_forward', C.c_int, (C.POINTER(S2DWideNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p)),
     ('s2d_debug_policy_head', C.c_int, (C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)),
 )

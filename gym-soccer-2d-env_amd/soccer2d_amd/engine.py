@@ -254,9 +254,16 @@ class Engine:
         from .mlp_actor import MlpDeterministicActor, MlpQNetActor
         return isinstance(actor, (MlpQNetActor, MlpDeterministicActor))
 
+    @staticmethod
+    def _is_wide(actor):
+        """does `actor` carry the streamed-weight MLP (soccer2d_amd.wide_actor), which goes to the _wide entry points"""
+        from .wide_actor import WideDeterministicActor, WideQNetActor
+        return isinstance(actor, (WideQNetActor, WideDeterministicActor))
+
     def rollout_qnet(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
         """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.QNetActor, or a
-        soccer2d_amd.mlp_actor.MlpQNetActor with one to four hidden layers: s2d_rollout_qnet_mlp) epsilon-greedy choices on
+        soccer2d_amd.mlp_actor.MlpQNetActor with one to four hidden layers: s2d_rollout_qnet_mlp, or a
+        soccer2d_amd.wide_actor.WideQNetActor with up to five layers of up to 400 units: s2d_rollout_qnet_wide) epsilon-greedy choices on
         the envs' own observations, evaluated in-kernel (s2d_rollout_qnet; discrete-action engines).  Returns the record dict of
         rollout() (action int32 [T,N]); with terminal_obs=True (or a caller `out` holding 'terminal_obs') also float32 [T,N,10],
         written only where done.  The actor's buffers are read when the kernel runs: a captured graph acts with the weights and
@@ -268,7 +275,8 @@ class Engine:
         if actor.device != self.device:
             raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
         out, ro, term = self._actor_record('rollout_qnet', self._QNET_RECORD, T, out, with_obs, terminal_obs)
-        entry = 's2d_rollout_qnet_mlp' if self._is_mlp(actor) else 's2d_rollout_qnet'
+        entry = ('s2d_rollout_qnet_wide' if self._is_wide(actor) else
+                 's2d_rollout_qnet_mlp' if self._is_mlp(actor) else 's2d_rollout_qnet')
         rc = getattr(self.lib, entry)(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
         _capi.check(self.lib, rc, entry)
         self._keep = (actor, out)
@@ -276,7 +284,8 @@ class Engine:
 
     def rollout_actor(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
         """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.DeterministicActor, or a
-        soccer2d_amd.mlp_actor.MlpDeterministicActor with one to four hidden layers: s2d_rollout_actor_mlp) tanh policy on
+        soccer2d_amd.mlp_actor.MlpDeterministicActor with one to four hidden layers: s2d_rollout_actor_mlp, or a
+        soccer2d_amd.wide_actor.WideDeterministicActor with up to five layers of up to 400 units: s2d_rollout_actor_wide) tanh policy on
         the envs' own observations, with epsilon-random exploration and optional Gaussian action noise, evaluated in-kernel
         (s2d_rollout_actor; continuous and turning engines).  Returns the record dict of rollout() (action float32 [T,N,1] or
         [T,N,4]: the noisy, clipped action); terminal_obs, graph capture and `out` caching as in rollout_qnet()."""
@@ -294,7 +303,8 @@ class Engine:
             raise ValueError(f'a {"turning" if t.use_turning else "continuous"} engine needs an actor with n_out = {a}, got {actor.n_out}')
         record = dict(self._QNET_RECORD, action=(torch.float32, (a,)))
         out, ro, term = self._actor_record('rollout_actor', record, T, out, with_obs, terminal_obs)
-        entry = 's2d_rollout_actor_mlp' if self._is_mlp(actor) else 's2d_rollout_actor'
+        entry = ('s2d_rollout_actor_wide' if self._is_wide(actor) else
+                 's2d_rollout_actor_mlp' if self._is_mlp(actor) else 's2d_rollout_actor')
         rc = getattr(self.lib, entry)(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
         _capi.check(self.lib, rc, entry)
         self._keep = (actor, out)

@@ -116,6 +116,7 @@ class _MlpShape:
 
     _tanh_head = False
     _what = 'Q-network'
+    _layers = staticmethod(_mlp_layers)     # how a module is read: the grid of layers and activations (wide_actor has another)
 
     def _init_shape(self, hidden, n_out, activation, device):
         self.hidden = _check_shape(hidden, n_out, activation)
@@ -147,7 +148,7 @@ class _MlpShape:
 
     def load_from(self, module):
         """Validate `module`'s shapes and activation against this actor, remember it, and pack its parameters (sync())."""
-        linears, act = _mlp_layers(module, self._tanh_head)
+        linears, act = self._layers(module, self._tanh_head)
         if act != self.activation:
             raise ValueError(f'the {self._what}\'s activation is {act}, the actor\'s {self.activation}')
         got = []
@@ -164,7 +165,7 @@ class _MlpShape:
         if self._module is None:
             raise ValueError('no module loaded (load_from)')
         srcs = []
-        for lin in _mlp_layers(self._module, self._tanh_head)[0]:
+        for lin in self._layers(self._module, self._tanh_head)[0]:
             srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
         with torch.no_grad():
             torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)

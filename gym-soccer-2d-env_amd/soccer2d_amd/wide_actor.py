@@ -1,0 +1,199 @@
+"""WideQNetActor / WideDeterministicActor: the fused actors of Engine.rollout_qnet / Engine.rollout_actor on the streamed-weight
+MLP (s2d_rollout_qnet_wide / s2d_rollout_actor_wide, S2DWideNet in include/s2d.h): 10 -> h_1 -> ... -> h_L -> A with one to five
+hidden layers, every hidden width a multiple of 4 in [8, 400] and one hidden activation, ReLU, Tanh or Sigmoid.  These are the
+networks the reference's scripts build by default or search over: SB3's ``DDPG("MlpPolicy", env)`` actor ``[400, 300]``, and
+``layer_size in {8, ..., 400} x n_layers in 1..5 x {ReLU, Tanh, Sigmoid}`` of its Optuna samples.
+
+They are MlpQNetActor / MlpDeterministicActor (soccer2d_amd.mlp_actor) on a wider grid.  The weights do not have to fit the
+LDS: every launch first rewrites them in the matrix cores' fragment order into a workspace tensor the actor owns, and the rollout
+kernel streams them from there.  The workspace belongs to one launch at a time: an actor is for one engine and one stream.  On
+every shape the Mlp classes take both paths give the same bits.
+"""
+import torch
+
+from . import _capi
+from .actor import _NO_OPS, ACTOR_OUTPUTS, MAX_ACTIONS, OBS_DIM, DeterministicActor, QNetActor
+from .mlp_actor import _MlpShape, param_count
+
+MAX_HIDDEN = 5
+WIDE_WIDTHS = tuple(range(8, 401, 4))
+ACTIVATIONS = ('relu', 'tanh', 'sigmoid')
+_KINDS = {torch.nn.ReLU: 'ReLU', torch.nn.Tanh: 'Tanh', torch.nn.Sigmoid: 'Sigmoid'}
+
+# the plan of csrc/s2d_wide_net.h (wide_plan_lds), in 4-byte words
+LDS_BYTES = 160 * 1024
+_WAVE = 64
+_OBS_TILE = _WAVE * OBS_DIM
+_PREP_TILE = (13 + OBS_DIM + 2) * _WAVE
+
+
+def wide_plan(hidden, n_out):
+    """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of a 10-hidden...-n_out network, by the arithmetic of
+    the C plan.  The workspace holds every layer's fragments (ceil(h / 16) tiles x its k-steps, 3 for layer 1, h_(l-1) / 4 after
+    it, 64 words each) and the biases padded to their tiles.  The LDS holds the biases and per wave two images of `tiles` x 16 rows
+    (pitch: the widest padded layer rounded up to 64, + 4), the output image, the observation tile and the prepared-episode tile.
+    More waves go before more tiles: the first of (4, 4), (4, 2), (4, 1), (2, 4), ..., (1, 1) that 160 KiB hold."""
+    na16 = (n_out + 15) // 16 * 16
+    nfrag = nbias = wmax = 0
+    ksteps = 3
+    for w in hidden:
+        m16 = (w + 15) // 16
+        nfrag += m16 * ksteps
+        nbias += 16 * m16
+        wmax = max(wmax, 16 * m16)
+        ksteps = w // 4
+    nfrag += (na16 // 16) * ksteps
+    nbias += na16
+    rpitch = (wmax + 63) // 64 * 64 + 4
+    shared = (nbias + 3) & ~3
+    for waves in (4, 2, 1):
+        for tiles in (4, 2, 1):
+            wave_words = 2 * tiles * 16 * rpitch + _WAVE * (na16 + 4) + _OBS_TILE + _PREP_TILE
+            nbytes = (shared + waves * wave_words) * 4
+            if nbytes <= LDS_BYTES:
+                return waves, tiles, nbytes, (nfrag * _WAVE + nbias) * 4
+    raise AssertionError('one wave with one tile fits for every shape on the grid')
+
+
+def _check_shape(hidden, n_out, activation):
+    hidden = tuple(int(w) for w in hidden)
+    if not 1 <= len(hidden) <= MAX_HIDDEN:
+        raise ValueError(f'the streamed MLP has 1 to {MAX_HIDDEN} hidden layers, got {len(hidden)}')
+    for w in hidden:
+        if w not in WIDE_WIDTHS:
+            raise ValueError(f'every hidden width must be a multiple of 4 in [8, 400], got {w} in {list(hidden)}')
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be 'relu', 'tanh' or 'sigmoid', got {activation!r}")
+    return hidden
+
+
+def _wide_layers(module, tanh_head=False):
+    """(the nn.Linear layers in order, activation name) of a Linear-(F-Linear) x L module, F = ReLU, Tanh or Sigmoid, the same
+    throughout; with tanh_head=True the module must end in one more Tanh (the deterministic actor's head).  Leaf modules are read
+    in registration order; Identity / Flatten are skipped; anything else is refused: the kernel would silently act with a
+    different function."""
+    leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
+    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else _KINDS.get(type(m), type(m).__name__) for m in leaves]
+    what = 'actor' if tanh_head else 'Q-network'
+    form = ('Linear-(F-Linear) x L' + ('-Tanh' if tanh_head else '') +
+            f', L = 1 .. {MAX_HIDDEN} hidden layers, F = ReLU, Tanh or Sigmoid')
+    got = '-'.join(kinds) or 'nothing'
+    body = kinds
+    if tanh_head:
+        if not kinds or kinds[-1] != 'Tanh':
+            raise ValueError(f'the actor must end in a Tanh ({form}), got {got}')
+        body = kinds[:-1]
+    if len(body) % 2 == 0 or any(k != 'Linear' for k in body[0::2]):
+        raise ValueError(f'the {what} must be {form}, got {got}')
+    acts = set(body[1::2])
+    n_hidden = len(body) // 2
+    if not 1 <= n_hidden <= MAX_HIDDEN:
+        raise ValueError(f'the {what} must have 1 to {MAX_HIDDEN} hidden layers ({form}), got {n_hidden}: {got}')
+    allowed = set(_KINDS.values())
+    if len(acts) > 1 and acts <= allowed:
+        raise ValueError(f'the {what} must use one activation throughout, ReLU, Tanh or Sigmoid, not a mix ({form}), got {got}')
+    if not acts <= allowed:
+        raise ValueError(f'the hidden activation must be ReLU, Tanh or Sigmoid ({form}), got {got}')
+    linears = leaves[0:len(body):2]
+    for lin in linears:
+        if lin.bias is None:
+            raise ValueError(f'every nn.Linear of the {what} needs a bias')
+    return linears, acts.pop().lower()
+
+
+class _WideShape(_MlpShape):
+    """_MlpShape on the wide grid, and the workspace the pack kernel writes"""
+
+    _layers = staticmethod(_wide_layers)
+
+    def _init_shape(self, hidden, n_out, activation, device):
+        hidden = _check_shape(hidden, n_out, activation)
+        self.activation = activation
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.hidden = hidden
+        # torch's device allocations are 256-byte aligned (the ABI asks for 16, and for 256 of the workspace)
+        self.params = torch.zeros(param_count(hidden, n_out), dtype=torch.float32, device=self.device)
+        self.workspace = torch.zeros(wide_plan(hidden, n_out)[3] // 4, dtype=torch.float32, device=self.device)
+        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._eps_value = None
+        self._module = None
+
+    @property
+    def plan(self):
+        """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of the kernel's plan for this shape"""
+        return wide_plan(self.hidden, self._outputs)
+
+    @property
+    def waves(self):
+        return self.plan[0]
+
+    def c_struct(self):
+        net = _capi.S2DWideNet()
+        net.n_hidden = len(self.hidden)
+        for l in range(MAX_HIDDEN):
+            net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
+        net.n_out = self._outputs
+        net.activation = ACTIVATIONS.index(self.activation)
+        net.noise_kind = self.noise_kind if self._tanh_head else 0
+        net.params = self.params.data_ptr()
+        net.epsilon = self._eps.data_ptr()
+        net.noise = self._noise.data_ptr() if self._tanh_head else None
+        net.workspace = self.workspace.data_ptr()
+        net.workspace_bytes = self.workspace.numel() * 4
+        return net
+
+
+class WideQNetActor(_WideShape, QNetActor):
+    """Packed parameters, device epsilon and workspace of a 10-h_1-...-h_L-A Q-network (L = 1 .. 5, widths up to 400, ReLU, Tanh or
+    Sigmoid) for Engine.rollout_qnet.  epsilon / epsilon_tensor are QNetActor's."""
+
+    def __init__(self, hidden=(256, 256), n_actions=16, activation='relu', device='cuda:0', epsilon=0.05):
+        if not 1 <= int(n_actions) <= MAX_ACTIONS:
+            raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
+        self.n_actions = int(n_actions)
+        self._init_shape(hidden, self.n_actions, activation, device)
+        self.epsilon = epsilon
+
+    @classmethod
+    def from_module(cls, module, device=None, epsilon=0.05):
+        """An actor shaped like `module` (Linear-(F-Linear) x L, F = ReLU, Tanh or Sigmoid throughout, optionally behind a
+        Flatten or Identity: SB3's ``model.q_net.q_net``), loaded from it."""
+        linears, act = _wide_layers(module)
+        dev = device if device is not None else linears[0].weight.device
+        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
+                    epsilon=epsilon)
+        actor.load_from(module)
+        return actor
+
+
+class WideDeterministicActor(_WideShape, DeterministicActor):
+    """Packed parameters, device epsilon, Gaussian action noise and workspace of a 10-h_1-...-h_L-A tanh actor (L = 1 .. 5, widths
+    up to 400: SB3's default [400, 300]) for Engine.rollout_actor.  epsilon and the noise properties are DeterministicActor's."""
+
+    _tanh_head = True
+    _what = 'actor'
+
+    def __init__(self, hidden=(400, 300), n_out=1, activation='relu', device='cuda:0', epsilon=0.0, noise_mean=None,
+                 noise_sigma=None):
+        if int(n_out) not in ACTOR_OUTPUTS:
+            raise ValueError(f'n_out must be 1 (continuous engine) or 4 (turning engine), got {n_out}')
+        self.n_out = int(n_out)
+        self._init_shape(hidden, self.n_out, activation, device)
+        self._noise = torch.zeros(2, self.n_out, dtype=torch.float32, device=self.device)   # [mu; sigma]
+        self._sigma = None
+        self.epsilon = epsilon
+        self.noise_mean = 0.0 if noise_mean is None else noise_mean
+        self.noise_sigma = noise_sigma
+
+    @classmethod
+    def from_module(cls, module, device=None, epsilon=0.0, noise_mean=None, noise_sigma=None):
+        """An actor shaped like `module` (SB3's ``model.actor.mu``: Linear-(F-Linear) x L-Tanh, F = ReLU, Tanh or Sigmoid
+        throughout, optionally behind a Flatten or Identity), loaded from it."""
+        linears, act = _wide_layers(module, tanh_head=True)
+        dev = device if device is not None else linears[0].weight.device
+        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
+                    epsilon=epsilon, noise_mean=noise_mean, noise_sigma=noise_sigma)
+        actor.load_from(module)
+        return actor

@@ -18,6 +18,9 @@
  *                              (T fused steps, epsilon-greedy actions of the caller's Q-network, in-kernel)
  *   s2d_rollout_actor          DDPG / TD3 actor.mu + NormalActionNoise inside SB3's collect_rollouts
  *                              ddpg_stable_baselines3.py (T fused steps, the caller's tanh policy, in-kernel)
+ *   s2d_rollout_qnet_wide / s2d_rollout_actor_wide   the same with the networks the reference's scripts build by default or
+ *                              search over: SB3's DDPG("MlpPolicy") actor [400, 300] (ddpg_stable_baselines3.py), the Optuna
+ *                              grids of best_python_sample_soccer_env*.py (up to five layers of 400, Sigmoid)
  *   s2d_rollout_policy         PPO / A2C: sampling from the policy's distribution + log_prob inside collect_rollouts
  *   s2d_gae                    RolloutBuffer.compute_returns_and_advantage
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
@@ -198,7 +201,7 @@ typedef struct S2DQNet {
 
 /* The caller's deterministic actor for s2d_rollout_actor (DESIGN.md sections 4, 5): a = tanh(W3 relu(W2 relu(W1 x + b1) + b2)
  * + b3), SB3's DDPG / TD3 actor.mu.  hidden1 / hidden2 in {16, 32, ..., 128} (the weights live in LDS; SB3's default
- * net_arch=[400, 300] does not fit: policy_kwargs=dict(net_arch=[64, 64])); n_out = 1 (use_continuous_action, not turning) or
+ * net_arch=[400, 300] does not fit there: s2d_rollout_actor_wide streams it, S2DWideNet); n_out = 1 (use_continuous_action, not turning) or
  * 4 (use_turning).  params as S2DQNet's (W3[n_out][H2], b3[n_out]), 16-byte aligned; epsilon: one fp32 device word; noise:
  * fp32 device buffer [2][n_out] = (mu, sigma) of the Gaussian action noise, required when noise_kind = 1 (0: no action noise,
  * noise may be NULL).  params, epsilon and noise are read when the kernel runs; noise_kind selects the instantiation.  */
@@ -250,6 +253,37 @@ typedef struct S2DMlpNet {
   int32_t noise_kind;      /* tanh actor only: 0 | 1; must be 0 for the Q actor */
   const float *params, *epsilon, *noise;   /* as S2DQNet / S2DActorNet */
 } S2DMlpNet;
+
+/* The caller's network for s2d_rollout_qnet_wide / s2d_rollout_actor_wide: S2DMlpNet's MLP on a wider grid, with the weights
+ * streamed from memory instead of living in LDS (DESIGN.md sections 4, 7): every network the reference's scripts can build --
+ * SB3's default DDPG actor [400, 300], the Optuna grids layer_size in {8, ..., 400} x n_layers in 1..5 x {ReLU, Tanh, Sigmoid}.
+ *   shape     10 -> h_1 -> ... -> h_L -> n_out, L in 1..5; every hidden width a multiple of 4 (the MFMA's k-step) in [8, 400];
+ *             one hidden activation for the whole network; the output layer is linear;
+ *   params    as S2DMlpNet's: nn.Sequential(...).parameters() order in one contiguous, 16-byte aligned fp32 device buffer;
+ *   units     acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc); layer 1 over k = 0 .. 11 (x_10 = x_11 = 0 against zero
+ *             weights: an accumulator of -0 becomes +0), later layers over exactly h_(l-1) terms (a width that is no multiple
+ *             of 16 pads the output rows of its last tile; no padded unit is ever read);
+ *   hidden    relu(v) = v > 0 ? v : +0, tanh_spec(v), or sigmoid_spec(v): a = min(|v|, 87) (NaN: 87), t = exp_spec(-a),
+ *             d = 1 + t, v >= 0 ? 1 / d : t / d (correctly rounded), NaN passes; +-0 -> 0.5, +inf -> 1, v <= -87 ->
+ *             exp_spec(-87) = 1.6458115e-38 rather than 0;
+ *   heads     s2d_rollout_qnet's and s2d_rollout_actor's, unchanged: no draw, key or counter differs.
+ * On every shape S2DMlpNet takes (L <= 4, widths multiples of 8 up to 128, relu or tanh, fitting the LDS) the result is the
+ * _mlp entry points' bit for bit.
+ *   workspace a 256-byte aligned device buffer of at least s2d_wide_workspace_bytes() bytes, where every call first writes
+ *             the parameters in the matrix cores' fragment order (a pack kernel on the caller's stream) and the rollout kernel
+ *             then reads them: params, epsilon and noise are still read when the kernels run, and a captured graph holds both
+ *             nodes and acts with what the buffers hold at replay.  A workspace belongs to ONE launch at a time: two launches
+ *             that may overlap (two streams, two engines) need a workspace each. */
+typedef struct S2DWideNet {
+  int32_t n_hidden;        /* 1 .. 5 */
+  int32_t hidden[5];       /* multiples of 4 in [8, 400]; entries past n_hidden are 0 */
+  int32_t n_out;           /* Q: action_space_size, 1 .. 64; tanh actor: 1 | 4 */
+  int32_t activation;      /* 0 relu, 1 tanh_spec, 2 sigmoid_spec */
+  int32_t noise_kind;      /* tanh actor only: 0 | 1; must be 0 for the Q actor */
+  const float *params, *epsilon, *noise;   /* as S2DMlpNet */
+  void *workspace;         /* 256-byte aligned device memory, written by every call */
+  size_t workspace_bytes;  /* >= s2d_wide_workspace_bytes(this shape) */
+} S2DWideNet;
 
 /* Derived protobuf-mirroring fields that are not plain state words (row T1).  Each array
  * is [N]; NULL pointers are skipped.                                                       */
@@ -338,6 +372,21 @@ int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet *net, const S2
  * network that does not fit the LDS (the error text says how many bytes it needs). */
 int s2d_rollout_qnet_mlp(S2DHandle h, int n_steps, const S2DMlpNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
 int s2d_rollout_actor_mlp(S2DHandle h, int n_steps, const S2DMlpNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+/* bytes of the workspace of S2DWideNet for `shape` (n_hidden, hidden and n_out are read): the fragment-order copy of the
+ * parameters, every layer's weights in tile-major fragments of 64 words with zero padding, then the biases padded to their tiles.
+ * 0 for a shape off the grid. */
+size_t s2d_wide_workspace_bytes(const S2DWideNet *shape);
+/* s2d_rollout_qnet_mlp / s2d_rollout_actor_mlp with the streamed-weight network of S2DWideNet.  A call enqueues two kernels on
+ * `stream`: the pack kernel (params -> workspace) and the rollout.  Records, terminal_obs, policy_step, statistics and the
+ * per-step outputs behave as the _mlp pair's; s2d_kernel_name() names the instantiation with its shape, its waves per workgroup
+ * and its env tiles per pass (...<noise=0,act=sigmoid,h=400-300,a=16,waves=2,tiles=1>); neither enters the result.  Rejected with
+ * S2D_EINVAL, without a launch and with the state untouched, the error text naming the field: n_hidden outside 1..5, a width
+ * that is not a multiple of 4 in [8, 400], a non-zero hidden[] entry past n_hidden, activation outside {0, 1, 2}, the wrong
+ * engine mode or an n_out that is not the engine's, noise_kind set on the Q path or outside {0, 1}, NULL or misaligned params /
+ * epsilon / noise / workspace, workspace_bytes too small (the text says how many bytes are needed), n_steps < 1.  (The
+ * environment variable S2D_WIDE_PLAN=waves,tiles, read at every launch, overrides the plan for testing.) */
+int s2d_rollout_qnet_wide(S2DHandle h, int n_steps, const S2DWideNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
+int s2d_rollout_actor_wide(S2DHandle h, int n_steps, const S2DWideNet *net, const S2DRollout *out, float *terminal_obs, void *stream);
 /* n_steps >= 1 cycles fused in ONE launch (every action mode) whose action at every cycle is SAMPLED from the caller's policy
  * on the env's observation, with the log-probability of the action taken recorded: on-policy collection (PPO / A2C).  Per env
  * and step at its policy_step k (advanced by one every step); every line one fixed fp32 operation:
@@ -435,6 +484,12 @@ int s2d_debug_net_forward(int h1, int h2, int na, const void *params_dev, const 
  * refuses, n not in 1..2^31 - 1, NULL or misaligned pointers. */
 int s2d_debug_mlp_forward(const S2DMlpNet *shape, const void *obs_dev, int64_t n, void *y_dev, void *greedy_dev, char *name,
                           void *stream);
+/* diagnostic: the same for the streamed-weight network of s2d_rollout_qnet_wide / s2d_rollout_actor_wide, with their pack kernel,
+ * LDS plan and layer loop.  shape: n_hidden, hidden, n_out (1 .. 64), activation, params, workspace and workspace_bytes are used.
+ * S2D_EINVAL without a launch: a shape or workspace s2d_rollout_qnet_wide refuses, n not in 1..2^31 - 1, NULL or misaligned
+ * pointers. */
+int s2d_debug_wide_forward(const S2DWideNet *shape, const void *obs_dev, int64_t n, void *y_dev, void *greedy_dev, char *name,
+                           void *stream);
 /* diagnostic: the head of s2d_rollout_policy alone, on caller logits or means, so that its edge cases can be compared bit for
  * bit with the spec without running a rollout.  mode: 0 discrete (n_out = A in 1..64), 1 continuous (n_out = 1), 2 turning
  * (n_out = 4).  y_dev = float[n][n_out]; log_std_dev = float[n_out] (may be NULL with mode 0); gid_dev = uint64[n] global env
