@@ -22,8 +22,6 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <mutex>
-#include <string>
 
 #include "s2d_actor_net.h"
 #include "s2d_actor_rollout.h"
@@ -59,101 +57,47 @@ __global__ __launch_bounds__(kBlock) void s2d_debug_net_forward_kernel(QNetDims 
   }
 }
 
-// host side (same library, hidden symbol; the rollouts' C entry points and their argument checks are in s2d_engine.hip,
-// s2d_debug_net_forward is at the end of this file; the LDS plan is in s2d_actor_net.h)
-using QNetKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut,
-                            float*, StepOut, int);
-using TanhKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, const float*, const float*, RolloutOut,
-                            float*, StepOut, int, const float*);
-
-// slots of allow_lds_slot (s2d_actor_net.h): the Q-actor's 3, the tanh actor's 2 x 3 x 2, then s2d_debug_net_forward's
-static constexpr int kActorSlots = 3 + 2 * 3 * 2 + 1;
-static bool allow_lds(const void* fn, int slot) { return allow_lds_slot<kActorSlots>(fn, slot); }
-
-extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
-                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name) {
-  QNetDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
-  static const QNetKernel table[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false, QNetDims>,
-                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false, QNetDims>,
-                                       s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false, QNetDims>};
-  if (!allow_lds(reinterpret_cast<const void*>(table[nk]), nk)) return -2;
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(table[nk], dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n,
-                     n_steps, d, params, eps, *ro, term_rec, *o, wave_words);
-  if (name) std::snprintf(name, 96, "s2d_reach_qnet_rollout_kernel<noise=%d,h1=%d,h2=%d,a=%d,waves=%d>", nk, h1, h2, na, waves);
-  return 0;
+// host side (same library, hidden symbol; the rollouts' C entry points and their argument checks are in s2d_engine.hip, the
+// tables and the launch in s2d_actor_rollout.h, s2d_debug_net_forward is at the end of this file; the LDS plan is in
+// s2d_actor_net.h)
+bool s2d_internal_net_plan(int h1, int h2, int na, ActorPlanBuf* buf) {
+  ActorPlan<QNetDims>& pl = plan_in<QNetDims>(buf);
+  return plan_lds(h1, h2, na, pl.d, pl.wave_words, pl.waves, pl.lds);
 }
 
-// mode = S2D_MODE_CONT1 | S2D_MODE_TURN4 (na = 1 | 4), gauss = 0 | 1
-extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2DHot* hot, const S2DRare* rare_dev, float* S,
-                                          int64_t stride, int64_t n, int n_steps, int h1, int h2, int na, const float* params,
-                                          const float* eps, const float* noise, const RolloutOut* ro, float* term_rec,
-                                          const StepOut* o, void* stream, char* name) {
-  QNetDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
-#define S2D_DDPG_ROW(M)                                                                                                          \
-  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, QNetDims, const float*>,                 \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, QNetDims, const float*>,                   \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, QNetDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, QNetDims, const float*>}
-  static const TanhKernel table[2][6] = {S2D_DDPG_ROW(S2D_MODE_CONT1), S2D_DDPG_ROW(S2D_MODE_TURN4)};
-#undef S2D_DDPG_ROW
-  const int m = mode == S2D_MODE_TURN4 ? 1 : 0, v = 3 * gauss + nk;
-  const TanhKernel k = table[m][v];
-  if (!allow_lds(reinterpret_cast<const void*>(k), 3 + 6 * m + v)) return -2;
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n, n_steps, d,
-                     params, eps, *ro, term_rec, *o, wave_words, noise);
-  if (name)
-    std::snprintf(name, 96, "s2d_reach_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,h1=%d,h2=%d,a=%d,waves=%d>",
-                  m ? "turn4" : "cont1", nk, gauss, h1, h2, na, waves);
+int s2d_internal_rollout_net(const ActorRollout& a, const ActorPlanBuf& buf, const float* params, const float* eps, const float* noise) {
+  const ActorPlan<QNetDims>& pl = plan_of<QNetDims>(buf);
+  const int h1 = pl.d.h1, h2 = pl.d.h2, na = pl.d.na;
+  if (!launch_actor_rollout(a, pl, params, eps, noise, [] {})) return -2;
+  if (a.mode == S2D_MODE_DISCRETE)
+    std::snprintf(a.name, a.name_bytes, "s2d_reach_qnet_rollout_kernel<noise=%d,h1=%d,h2=%d,a=%d,waves=%d>", a.nk, h1, h2, na, pl.waves);
+  else
+    std::snprintf(a.name, a.name_bytes, "s2d_reach_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,h1=%d,h2=%d,a=%d,waves=%d>",
+                  a.mode == S2D_MODE_TURN4 ? "turn4" : "cont1", a.nk, noise ? 1 : 0, h1, h2, na, pl.waves);
   return 0;
 }
-
-// errors share the thread-local text of s2d_last_error() (defined in s2d_engine.hip)
-extern "C" void s2d_internal_set_error(const char* msg);
 
 S2D_API int s2d_debug_net_forward(int h1, int h2, int na, const void* params_dev, const void* obs_dev, int64_t n, void* y_dev,
                                   void* greedy_dev, char* name, void* stream) {
+  static const char who[] = "s2d_debug_net_forward";
   const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
   const char* err = nullptr;
   if (!width_ok(h1) || !width_ok(h2)) err = "s2d_debug_net_forward: hidden widths must be multiples of 16 in [16, 128]";
   else if (na < 1 || na > 64) err = "s2d_debug_net_forward: na must be in [1, 64]";
-  else if (n < 1 || n > INT32_MAX) err = "s2d_debug_net_forward: n must be in [1, 2^31 - 1]";
-  else if (!params_dev || (reinterpret_cast<uintptr_t>(params_dev) & 15u))
-    err = "s2d_debug_net_forward: params must be a non-NULL, 16-byte aligned device pointer";
-  else if (!obs_dev || !y_dev || !greedy_dev ||
-           ((reinterpret_cast<uintptr_t>(obs_dev) | reinterpret_cast<uintptr_t>(y_dev) | reinterpret_cast<uintptr_t>(greedy_dev)) & 3u))
-    err = "s2d_debug_net_forward: obs, y and greedy must be non-NULL, 4-byte aligned device pointers";
   if (err) { s2d_internal_set_error(err); return S2D_EINVAL; }
-  QNetDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) {
+  int rc = debug_forward_args(who, params_dev, obs_dev, n, y_dev, greedy_dev);
+  if (rc != S2D_OK) return rc;
+  ActorPlanBuf buf;
+  if (!s2d_internal_net_plan(h1, h2, na, &buf)) {
     s2d_internal_set_error("s2d_debug_net_forward: the network does not fit the LDS of a workgroup");
     return S2D_EINVAL;
   }
-  if (!allow_lds(reinterpret_cast<const void*>(s2d_debug_net_forward_kernel), kActorSlots - 1)) {
-    s2d_internal_set_error("s2d_debug_net_forward: hipGetDevice or hipFuncSetAttribute failed");
-    return S2D_EHIP;
-  }
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(s2d_debug_net_forward_kernel, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), d,
-                     static_cast<const float*>(params_dev), static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev),
-                     static_cast<int32_t*>(greedy_dev), wave_words);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    s2d_internal_set_error((std::string("s2d_debug_net_forward: launch: ") + hipGetErrorString(e)).c_str());
-    return S2D_EHIP;
-  }
-  if (name) std::snprintf(name, 96, "s2d_debug_net_forward_kernel<h1=%d,h2=%d,a=%d,waves=%d>", h1, h2, na, waves);
-  return S2D_OK;
+  const ActorPlan<QNetDims>& pl = plan_of<QNetDims>(buf);
+  rc = debug_forward_launch(who, reinterpret_cast<const void*>(s2d_debug_net_forward_kernel), pl, n, [&](unsigned blocks, int threads) {
+    hipLaunchKernelGGL(s2d_debug_net_forward_kernel, dim3(blocks), dim3(threads), pl.lds, static_cast<hipStream_t>(stream), pl.d,
+                       static_cast<const float*>(params_dev), static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev),
+                       static_cast<int32_t*>(greedy_dev), pl.wave_words);
+  });
+  if (rc == S2D_OK && name) std::snprintf(name, 96, "s2d_debug_net_forward_kernel<h1=%d,h2=%d,a=%d,waves=%d>", h1, h2, na, pl.waves);
+  return rc;
 }

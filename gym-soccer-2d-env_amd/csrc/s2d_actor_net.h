@@ -1,12 +1,10 @@
 // s2d_actor_net.h -- the 10-H1-H2-A network of the reach-ball engine's fused actors, shared by s2d_actor.hip (the Q-network and
 // the tanh actor) and s2d_policy.hip (the stochastic policy heads): its dimensions, the repacking of the caller's parameters
-// into fragment order, the forward pass on the wave's observation tile, the LDS plan and the dynamic-LDS attribute.
-// (Moved out of s2d_actor.hip unchanged; allow_lds takes the size of the including unit's slot table as a template argument.)
+// into fragment order, the forward pass on the wave's observation tile and the LDS plan.  (Moved out of s2d_actor.hip unchanged.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 #include "s2d_kernels.h"
 #include "s2d_net.h"
@@ -113,21 +111,4 @@ static inline bool plan_lds(int h1, int h2, int na, QNetDims& d, int& wave_words
   while (waves > 1 && (shared_words + (size_t)waves * wave_words) * sizeof(float) > kLdsMax) waves /= 2;
   lds = (shared_words + (size_t)waves * wave_words) * sizeof(float);
   return lds <= kLdsMax;
-}
-
-// the dynamic-LDS limit is a per-device property of the function: set it once per (device, instantiation `slot`), under a lock
-// (engines on several devices may be driven from several threads); the caller has made the engine's device current.  SLOTS =
-// the number of instantiations of the including unit
-template <int SLOTS>
-static bool allow_lds_slot(const void* fn, int slot) {
-  static std::mutex attr_mu;
-  static bool attr_set[kMaxDevices][SLOTS] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
-  std::lock_guard<std::mutex> lock(attr_mu);
-  if (!attr_set[dev][slot]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
-    attr_set[dev][slot] = true;
-  }
-  return true;
 }

@@ -1,8 +1,10 @@
 // s2d_actor_rollout.h -- the rollout kernel of the reach-ball engine's fused actors, as one template over the network it acts
-// with, shared by s2d_actor.hip (Dims = QNetDims, the 10-H1-H2-A network of s2d_actor_net.h) and s2d_mlp_actor.hip (Dims =
-// MlpDims, the general MLP of s2d_mlp_net.h): the prologue, the heads (epsilon-greedy argmax; tanh with optional Gaussian action
-// noise), the simulation, the records and the statistics.  (Moved out of s2d_actor.hip; the text of the kernel is unchanged but
-// for the type of `d`, so that the QNetDims instantiations keep their instructions: profiles/r05/mlp_actor_isa.txt.)
+// with, shared by s2d_actor.hip (Dims = QNetDims, the 10-H1-H2-A network of s2d_actor_net.h), s2d_mlp_actor.hip (Dims =
+// MlpDims, the general MLP of s2d_mlp_net.h) and s2d_wide_actor.hip (Dims = WideDims, the streamed-weight MLP of s2d_wide_net.h):
+// the prologue, the heads (epsilon-greedy argmax; tanh with optional Gaussian action noise), the simulation, the records and the
+// statistics.  (Moved out of s2d_actor.hip; the text of the kernel is unchanged but for the type of `d`, so that the QNetDims
+// instantiations keep their instructions: profiles/r05/mlp_actor_isa.txt.)  At the end of the file, the kernel's host side as
+// one template over the same Dims: the launch tables, the dynamic-LDS attribute and the launch.
 //
 // Dims: the kernel argument that describes the network.  Beside its fields pitch and qpitch (the row pitches of the wave's two
 // hidden images [16] and of its output image [64]) the kernel asks for three overloads on it:
@@ -13,7 +15,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
+#include <new>
+#include <string>
 
+#include "s2d_actor_launch.h"
 #include "s2d_actor_net.h"
 
 // experiment build (-DS2D_QNET_STAMPS, profiles/experiments/qnet_actor_clocks.py): per wave, the shader clocks (s_memtime) of the
@@ -200,4 +206,118 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot 
   unsigned long long* const srow = stats_row(o.stats, wave_first);
   stats_store(srow, lane, stats_load(srow, lane), wave_first == 0 ? (unsigned long long)n * (unsigned long long)n_steps : 0ull, cnt1, cnt2, cnt3);
   QS_STORE();
+}
+
+// ------------------------------------------------------------------------------------------ host side
+// The dynamic-LDS limit is a per-device property of the function: set it once per (device, instantiation `slot`), under a lock
+// (engines on several devices may be driven from several threads); the caller has made the engine's device current.  One table
+// per Owner: every back end numbers its instantiations from 0 (Owner = its Dims; s2d_policy.hip has a tag of its own).
+// kLdsSlots: the most instantiations an Owner has -- a back end's 16 (the Q head's 3, the tanh head's 2 x 3 x 2, then its
+// diagnostic kernel in the last slot); s2d_policy.hip uses 9 (3 modes x 3 noise kinds)
+static constexpr int kLdsSlots = 16;
+template <typename Owner>
+static bool allow_lds_slot(const void* fn, int slot) {
+  static std::mutex attr_mu;
+  static bool attr_set[kMaxDevices][kLdsSlots] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lock(attr_mu);
+  if (!attr_set[dev][slot]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
+    attr_set[dev][slot] = true;
+  }
+  return true;
+}
+
+// a back end's plan for one network: its kernel argument, the LDS words of a wave, the waves of a workgroup, the LDS bytes; and
+// its place in the buffer the entry points carry
+template <typename Dims>
+struct ActorPlan {
+  Dims d;
+  int wave_words, waves;
+  size_t lds;
+};
+template <typename Dims>
+static ActorPlan<Dims>& plan_in(ActorPlanBuf* buf) {
+  static_assert(sizeof(ActorPlan<Dims>) <= sizeof buf->bytes && alignof(ActorPlan<Dims>) <= alignof(ActorPlanBuf), "ActorPlanBuf");
+  return *new (buf->bytes) ActorPlan<Dims>;
+}
+template <typename Dims>
+static const ActorPlan<Dims>& plan_of(const ActorPlanBuf& buf) { return *reinterpret_cast<const ActorPlan<Dims>*>(buf.bytes); }
+
+// "128-64-32-16" (Net = S2DMlpNet | S2DWideNet)
+template <typename Net>
+static std::string widths_text(const Net* net) {
+  std::string s;
+  for (int l = 0; l < net->n_hidden; ++l) s += (l ? "-" : "") + std::to_string(net->hidden[l]);
+  return s;
+}
+
+// The rollout of a planned network with the head of the engine's mode: the Q head on a discrete engine, the tanh head on a
+// continuous or turning one (`noise` non-NULL: with Gaussian action noise).  `before()` enqueues what has to run ahead of the
+// rollout on the same stream (the wide back end's pack kernel); it is called once nothing can fail any more.  false, with
+// nothing enqueued, if hipGetDevice or hipFuncSetAttribute failed.
+template <typename Dims, typename Before>
+static bool launch_actor_rollout(const ActorRollout& a, const ActorPlan<Dims>& pl, const float* params, const float* eps,
+                                 const float* noise, Before before) {
+  using QKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, Dims, const float*, const float*, RolloutOut, float*,
+                           StepOut, int);
+  using TanhKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, Dims, const float*, const float*, RolloutOut,
+                              float*, StepOut, int, const float*);
+  static const QKernel qtable[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false, Dims>,
+                                    s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false, Dims>,
+                                    s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false, Dims>};
+#define S2D_TANH_ROW(M)                                                                                                                            \
+  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, Dims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, Dims, const float*>, \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, Dims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, Dims, const float*>,   \
+   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, Dims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, Dims, const float*>}
+  static const TanhKernel ttable[2][6] = {S2D_TANH_ROW(S2D_MODE_CONT1), S2D_TANH_ROW(S2D_MODE_TURN4)};
+#undef S2D_TANH_ROW
+  const hipStream_t stream = static_cast<hipStream_t>(a.stream);
+  const int threads = pl.waves * kWave;
+  const unsigned blocks = (unsigned)((a.n + threads - 1) / threads);
+  if (a.mode == S2D_MODE_DISCRETE) {
+    const QKernel k = qtable[a.nk];
+    if (!allow_lds_slot<Dims>(reinterpret_cast<const void*>(k), a.nk)) return false;
+    before();
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), pl.lds, stream, *a.hot, a.rare_dev, a.S, a.stride, a.n, a.n_steps, pl.d, params,
+                       eps, *a.ro, a.term_rec, *a.o, pl.wave_words);
+    return true;
+  }
+  const int m = a.mode == S2D_MODE_TURN4 ? 1 : 0, v = 3 * (noise ? 1 : 0) + a.nk;
+  const TanhKernel k = ttable[m][v];
+  if (!allow_lds_slot<Dims>(reinterpret_cast<const void*>(k), 3 + 6 * m + v)) return false;
+  before();
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), pl.lds, stream, *a.hot, a.rare_dev, a.S, a.stride, a.n, a.n_steps, pl.d, params, eps,
+                     *a.ro, a.term_rec, *a.o, pl.wave_words, noise);
+  return true;
+}
+
+// The host half of s2d_debug_{net,mlp,wide}_forward (`who`).  Its arguments beside the shape: S2D_OK, or S2D_EINVAL with the text set
+static inline int debug_forward_args(const std::string& who, const void* params, const void* obs, int64_t n, const void* y, const void* greedy) {
+  std::string err;
+  if (n < 1 || n > INT32_MAX) err = ": n must be in [1, 2^31 - 1]";
+  else if (!params || (reinterpret_cast<uintptr_t>(params) & 15u)) err = ": params must be a non-NULL, 16-byte aligned device pointer";
+  else if (!obs || !y || !greedy ||
+           ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(greedy)) & 3u))
+    err = ": obs, y and greedy must be non-NULL, 4-byte aligned device pointers";
+  if (err.empty()) return S2D_OK;
+  s2d_internal_set_error((who + err).c_str());
+  return S2D_EINVAL;
+}
+
+// and its launch: the dynamic-LDS limit of `kernel` (the last slot of Dims' table), then enqueue(blocks, threads), which launches
+// the kernel (and whatever goes ahead of it), then the launch's error
+template <typename Dims, typename Enqueue>
+static int debug_forward_launch(const std::string& who, const void* kernel, const ActorPlan<Dims>& pl, int64_t n, Enqueue enqueue) {
+  if (!allow_lds_slot<Dims>(kernel, kLdsSlots - 1)) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  const int threads = pl.waves * kWave;
+  enqueue((unsigned)((n + threads - 1) / threads), threads);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return S2D_OK;
+  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
+  return S2D_EHIP;
 }

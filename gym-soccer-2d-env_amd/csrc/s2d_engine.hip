@@ -21,6 +21,7 @@
 
 #include "s2d_device.h"
 
+#include "s2d_actor_launch.h"
 #include "s2d_kernels.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1034,7 +1035,7 @@ __global__ void s2d_debug_eval_kernel(int op, const float* __restrict__ in, floa
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-// shared with s2d_match.hip (same library, hidden symbol)
+// shared with the other units (same library, hidden symbol)
 extern "C" void s2d_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -1048,39 +1049,7 @@ extern "C" int s2d_internal_rollout2(int mode, int noise, const S2DHot* hot, con
                                      int64_t n, int n_steps, const void* actions_dev, int kind, const RolloutOut* ro,
                                      const StepOut* o, void* stream, char* name);
 
-// s2d_actor.hip (same library, hidden symbol): launches the Q-network actor rollout (0, or < 0 if the network does not fit LDS)
-extern "C" int s2d_internal_rollout_qnet(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                         int n_steps, int h1, int h2, int na, const float* params, const float* eps,
-                                         const RolloutOut* ro, float* term_rec, const StepOut* o, void* stream, char* name);
-// s2d_actor.hip: launches the deterministic (tanh) actor rollout of a continuous or turning engine (same return codes)
-extern "C" int s2d_internal_rollout_actor(int mode, int nk, int gauss, const S2DHot* hot, const S2DRare* rare_dev, float* S,
-                                          int64_t stride, int64_t n, int n_steps, int h1, int h2, int na, const float* params,
-                                          const float* eps, const float* noise, const RolloutOut* ro, float* term_rec,
-                                          const StepOut* o, void* stream, char* name);
-
-// s2d_policy.hip: launches the stochastic policy rollout of any action mode (same return codes)
-extern "C" int s2d_internal_rollout_policy(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
-                                           int64_t n, int n_steps, int h1, int h2, int na, int act_fn, const float* params,
-                                           const float* log_std, const uint32_t* det, const RolloutOut* ro, float* term_rec,
-                                           float* logp, const StepOut* o, void* stream, char* name);
-
-// s2d_mlp_actor.hip: the shape check of a general MLP (S2D_OK, or S2D_EINVAL with the error text set) and the launches of its
-// two actors (0, S2D_EINVAL with the text set, or -2 on a HIP failure)
-extern "C" int s2d_internal_mlp_check(const char* who, const S2DMlpNet* net);
-extern "C" int s2d_internal_rollout_qnet_mlp(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                             int n_steps, const S2DMlpNet* net, const RolloutOut* ro, float* term_rec,
-                                             const StepOut* o, void* stream, char* name, size_t name_bytes);
-extern "C" int s2d_internal_rollout_actor_mlp(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
-                                              int64_t n, int n_steps, const S2DMlpNet* net, const RolloutOut* ro, float* term_rec,
-                                              const StepOut* o, void* stream, char* name, size_t name_bytes);
-// s2d_wide_actor.hip: the same for the streamed-weight network (the launches check the workspace before they enqueue anything)
-extern "C" int s2d_internal_wide_check(const char* who, const S2DWideNet* net);
-extern "C" int s2d_internal_rollout_qnet_wide(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                              int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
-                                              const StepOut* o, void* stream, char* name, size_t name_bytes);
-extern "C" int s2d_internal_rollout_actor_wide(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
-                                               int64_t n, int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
-                                               const StepOut* o, void* stream, char* name, size_t name_bytes);
+// the launches of the fused actors (three network back ends and the stochastic policy): s2d_actor_launch.h
 
 struct S2DEngine {
   S2DConfig cfg;
@@ -1544,264 +1513,218 @@ S2D_API int s2d_rollout(S2DHandle h, int n_steps, const void* actions_dev, int a
   return S2D_OK;
 }
 
-S2D_API int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet* net, const S2DRollout* out, float* terminal_obs,
-                             void* stream) {
+// ---- the fused actors: seven entry points on one checked prologue and epilogue.  An entry keeps what is its own: the engine
+// modes it takes, its n_out rule, its shape check and its launcher.
+
+// S2D_EINVAL with the text `who` + `what`: built on the failing branch only, a launch that passes allocates nothing
+static int actor_fail(const char* who, const char* what) { return fail(S2D_EINVAL, std::string(who) + what); }
+
+// What every entry checks alike before its own rules, and the record as the kernels take it.  `modes`: bit S2D_MODE_* set for the
+// engine modes the entry takes, `wrong_mode`: its refusal of the others.  `logp`: the policy entry's.
+static int actor_begin(const char* who, S2DEngine* h, const void* net, unsigned modes, const char* wrong_mode, int n_steps,
+                       const S2DRollout* out, const float* terminal_obs, const float* logp, RolloutOut& ro) {
+  const auto misaligned = [](const void* q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
   if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_qnet: net is NULL");
-  const S2DReachBallParams& t = h->cfg.task;
-  if (t.use_continuous_action) return fail(S2D_EINVAL, "s2d_rollout_qnet needs a discrete-action engine (use_continuous_action = 0)");
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_qnet: n_steps must be >= 1");
-  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
-  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet: hidden widths must be multiples of 16 in [16, 128]");
-  if (net->n_actions < 1 || net->n_actions > 64 || net->n_actions != t.action_space_size)
-    return fail(S2D_EINVAL, "s2d_rollout_qnet: n_actions must equal action_space_size and be in [1, 64]");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_qnet: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (!net) return actor_fail(who, ": net is NULL");
+  if (!(modes >> h->mode & 1u)) return fail(S2D_EINVAL, wrong_mode);
+  if (n_steps < 1) return actor_fail(who, ": n_steps must be >= 1");
+  if (misaligned(terminal_obs, 3u)) return actor_fail(who, ": terminal_obs must be 4-byte aligned");
+  if (misaligned(logp, 3u)) return actor_fail(who, ": logp must be 4-byte aligned");
+  ro = RolloutOut{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   if (out) {
     ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & 3u) return fail(S2D_EINVAL, "rollout action buffer must be 4-byte aligned");
+    if (misaligned(out->obs, 3u)) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
+    if (misaligned(out->action, h->mode == S2D_MODE_TURN4 ? 15u : 3u))
+      return fail(S2D_EINVAL, modes >> S2D_MODE_TURN4 & 1u ? "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned"
+                                                         : "rollout action buffer must be 4-byte aligned");
   }
+  return S2D_OK;
+}
+
+// The pointer rules of the six epsilon actors.  max_noise_kind: 1 for a tanh entry (0 none | 1 Gaussian, which needs `noise`), 0
+// for a Q entry (the MLP structs carry the field: it must be 0)
+static int actor_pointers(const char* who, const float* params, const float* epsilon, const float* noise, int noise_kind,
+                          int max_noise_kind) {
+  const auto bad = [](const void* q, unsigned m) { return !q || (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  if (noise_kind < 0 || noise_kind > max_noise_kind)
+    return actor_fail(who, max_noise_kind ? ": noise_kind must be 0 (none) or 1 (Gaussian)"
+                                          : ": noise_kind must be 0 (the Q actor has no action noise)");
+  if (bad(params, 15u)) return actor_fail(who, ": params must be a non-NULL, 16-byte aligned device pointer");
+  if (bad(epsilon, 3u)) return actor_fail(who, ": epsilon must be a non-NULL, 4-byte aligned device pointer");
+  if (noise_kind == 1 && bad(noise, 3u)) return actor_fail(who, ": Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
+  return S2D_OK;
+}
+
+// n_out of a tanh entry: 4 on a turning engine, 1 on a continuous one
+static int actor_n_out(const char* who, const S2DEngine* h, int n_out) {
+  const bool turn = h->mode == S2D_MODE_TURN4;
+  if (n_out == (turn ? 4 : 1)) return S2D_OK;
+  return actor_fail(who, turn ? ": n_out must be 4 on a turning engine" : ": n_out must be 1 on a continuous (non-turning) engine");
+}
+
+static bool actor_width_ok(int h1, int h2) {
+  const auto ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
+  return ok(h1) && ok(h2);
+}
+
+// the plan of a two-layer network
+static int actor_net_plan(const char* who, int h1, int h2, int na, ActorPlanBuf& pl) {
+  if (s2d_internal_net_plan(h1, h2, na, &pl)) return S2D_OK;
+  return actor_fail(who, ": the network does not fit the LDS of a workgroup");
+}
+
+// The launch of a checked call and what follows it.  launch(a) is the entry's launcher: 0, S2D_EINVAL with the text set by the
+// back end, or another value for a failed HIP call; it enqueues nothing unless it returns 0.
+template <typename Launch>
+static int actor_launch(const char* who, S2DEngine* h, int n_steps, const RolloutOut& ro, float* terminal_obs, void* stream, Launch launch) {
   DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_qnet(h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
-                                           n_steps, net->hidden1, net->hidden2, net->n_actions, net->params, net->epsilon, &ro,
-                                           terminal_obs, &h->out, stream, h->kernel_name);
-  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_qnet: the network does not fit the LDS of a workgroup");
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_qnet: hipGetDevice or hipFuncSetAttribute failed");
+  const ActorRollout a{h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n, n_steps, &ro,
+                       terminal_obs, &h->out, stream, h->kernel_name, sizeof h->kernel_name};
+  const int rc = launch(a);
+  if (rc == S2D_EINVAL) return S2D_EINVAL;
+  if (rc != 0) return fail(S2D_EHIP, std::string(who) + ": hipGetDevice or hipFuncSetAttribute failed");
   HIP_TRY(hipGetLastError());
   h->last_kernel = h->kernel_name;
   return S2D_OK;
+}
+
+static constexpr unsigned kDiscreteEngine = 1u << S2D_MODE_DISCRETE, kContinuousEngines = 1u << S2D_MODE_CONT1 | 1u << S2D_MODE_TURN4;
+
+S2D_API int s2d_rollout_qnet(S2DHandle h, int n_steps, const S2DQNet* net, const S2DRollout* out, float* terminal_obs,
+                             void* stream) {
+  static const char who[] = "s2d_rollout_qnet";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kDiscreteEngine, "s2d_rollout_qnet needs a discrete-action engine (use_continuous_action = 0)", n_steps,
+                       out, terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  if (!actor_width_ok(net->hidden1, net->hidden2))
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: hidden widths must be multiples of 16 in [16, 128]");
+  if (net->n_actions < 1 || net->n_actions > 64 || net->n_actions != h->cfg.task.action_space_size)
+    return fail(S2D_EINVAL, "s2d_rollout_qnet: n_actions must equal action_space_size and be in [1, 64]");
+  ActorPlanBuf pl;
+  if ((rc = actor_pointers(who, net->params, net->epsilon, nullptr, 0, 0)) != S2D_OK ||
+      (rc = actor_net_plan(who, net->hidden1, net->hidden2, net->n_actions, pl)) != S2D_OK)
+    return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_net(a, pl, net->params, net->epsilon, nullptr); });
 }
 
 S2D_API int s2d_rollout_actor(S2DHandle h, int n_steps, const S2DActorNet* net, const S2DRollout* out, float* terminal_obs,
                               void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_actor: net is NULL");
-  if (h->mode == S2D_MODE_DISCRETE)
-    return fail(S2D_EINVAL, "s2d_rollout_actor needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet");
-  const int na = h->mode == S2D_MODE_TURN4 ? 4 : 1;
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_actor: n_steps must be >= 1");
-  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
-  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
+  static const char who[] = "s2d_rollout_actor";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kContinuousEngines,
+                       "s2d_rollout_actor needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet", n_steps, out,
+                       terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  if (!actor_width_ok(net->hidden1, net->hidden2))
     return fail(S2D_EINVAL, "s2d_rollout_actor: hidden widths must be multiples of 16 in [16, 128] (the weights live in LDS); "
                             "SB3's default net_arch=[400, 300] does not fit: use policy_kwargs=dict(net_arch=[64, 64])");
-  if (net->n_out != na)
-    return fail(S2D_EINVAL, h->mode == S2D_MODE_TURN4 ? "s2d_rollout_actor: n_out must be 4 on a turning engine"
-                                                      : "s2d_rollout_actor: n_out must be 1 on a continuous (non-turning) engine");
-  if (net->noise_kind != 0 && net->noise_kind != 1) return fail(S2D_EINVAL, "s2d_rollout_actor: noise_kind must be 0 (none) or 1 (Gaussian)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
-    return fail(S2D_EINVAL, "s2d_rollout_actor: Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_actor: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
-      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
-  }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_actor(h->mode, h->nk, net->noise_kind, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
-                                            h->stride, h->n, n_steps, net->hidden1, net->hidden2, na, net->params, net->epsilon,
-                                            net->noise_kind ? net->noise : nullptr, &ro, terminal_obs, &h->out, stream, h->kernel_name);
-  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_actor: the network does not fit the LDS of a workgroup");
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  ActorPlanBuf pl;
+  if ((rc = actor_n_out(who, h, net->n_out)) != S2D_OK ||
+      (rc = actor_pointers(who, net->params, net->epsilon, net->noise, net->noise_kind, 1)) != S2D_OK ||
+      (rc = actor_net_plan(who, net->hidden1, net->hidden2, net->n_out, pl)) != S2D_OK)
+    return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream, [&](const ActorRollout& a) {
+    return s2d_internal_rollout_net(a, pl, net->params, net->epsilon, net->noise_kind ? net->noise : nullptr);
+  });
 }
 
 S2D_API int s2d_rollout_qnet_mlp(S2DHandle h, int n_steps, const S2DMlpNet* net, const S2DRollout* out, float* terminal_obs,
                                  void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: net is NULL");
-  const S2DReachBallParams& t = h->cfg.task;
-  if (t.use_continuous_action)
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp needs a discrete-action engine (use_continuous_action = 0); use s2d_rollout_actor_mlp");
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: n_steps must be >= 1");
-  if (s2d_internal_mlp_check("s2d_rollout_qnet_mlp", net) != S2D_OK) return S2D_EINVAL;
-  if (net->n_out != t.action_space_size)
+  static const char who[] = "s2d_rollout_qnet_mlp";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kDiscreteEngine,
+                       "s2d_rollout_qnet_mlp needs a discrete-action engine (use_continuous_action = 0); use s2d_rollout_actor_mlp", n_steps,
+                       out, terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  ActorPlanBuf pl;
+  if (s2d_internal_mlp_plan(who, net, &pl) != S2D_OK) return S2D_EINVAL;
+  if (net->n_out != h->cfg.task.action_space_size)
     return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: n_out must equal action_space_size and be in [1, 64]");
-  if (net->noise_kind != 0) return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: noise_kind must be 0 (the Q actor has no action noise)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_qnet_mlp: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & 3u) return fail(S2D_EINVAL, "rollout action buffer must be 4-byte aligned");
-  }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_qnet_mlp(h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
-                                               n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name, sizeof h->kernel_name);
-  if (rc == S2D_EINVAL) return S2D_EINVAL;
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_qnet_mlp: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  if ((rc = actor_pointers(who, net->params, net->epsilon, nullptr, net->noise_kind, 0)) != S2D_OK) return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_mlp(a, who, net, pl); });
 }
 
 S2D_API int s2d_rollout_actor_mlp(S2DHandle h, int n_steps, const S2DMlpNet* net, const S2DRollout* out, float* terminal_obs,
                                   void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: net is NULL");
-  if (h->mode == S2D_MODE_DISCRETE)
-    return fail(S2D_EINVAL, "s2d_rollout_actor_mlp needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet_mlp");
-  const int na = h->mode == S2D_MODE_TURN4 ? 4 : 1;
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: n_steps must be >= 1");
-  if (s2d_internal_mlp_check("s2d_rollout_actor_mlp", net) != S2D_OK) return S2D_EINVAL;
-  if (net->n_out != na)
-    return fail(S2D_EINVAL, h->mode == S2D_MODE_TURN4 ? "s2d_rollout_actor_mlp: n_out must be 4 on a turning engine"
-                                                      : "s2d_rollout_actor_mlp: n_out must be 1 on a continuous (non-turning) engine");
-  if (net->noise_kind != 0 && net->noise_kind != 1)
-    return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: noise_kind must be 0 (none) or 1 (Gaussian)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_actor_mlp: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
-      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
-  }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_actor_mlp(h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
-                                                h->stride, h->n, n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name,
-                                                sizeof h->kernel_name);
-  if (rc == S2D_EINVAL) return S2D_EINVAL;
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor_mlp: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  static const char who[] = "s2d_rollout_actor_mlp";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kContinuousEngines,
+                       "s2d_rollout_actor_mlp needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet_mlp", n_steps,
+                       out, terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  ActorPlanBuf pl;
+  if (s2d_internal_mlp_plan(who, net, &pl) != S2D_OK) return S2D_EINVAL;
+  if ((rc = actor_n_out(who, h, net->n_out)) != S2D_OK ||
+      (rc = actor_pointers(who, net->params, net->epsilon, net->noise, net->noise_kind, 1)) != S2D_OK)
+    return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_mlp(a, who, net, pl); });
 }
 
 S2D_API int s2d_rollout_qnet_wide(S2DHandle h, int n_steps, const S2DWideNet* net, const S2DRollout* out, float* terminal_obs,
                                  void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: net is NULL");
-  const S2DReachBallParams& t = h->cfg.task;
-  if (t.use_continuous_action)
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide needs a discrete-action engine (use_continuous_action = 0); use s2d_rollout_actor_wide");
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: n_steps must be >= 1");
-  if (s2d_internal_wide_check("s2d_rollout_qnet_wide", net) != S2D_OK) return S2D_EINVAL;
-  if (net->n_out != t.action_space_size)
+  static const char who[] = "s2d_rollout_qnet_wide";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kDiscreteEngine,
+                       "s2d_rollout_qnet_wide needs a discrete-action engine (use_continuous_action = 0); use s2d_rollout_actor_wide", n_steps,
+                       out, terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  ActorPlanBuf pl;
+  if (s2d_internal_wide_plan(who, net, &pl) != S2D_OK) return S2D_EINVAL;
+  if (net->n_out != h->cfg.task.action_space_size)
     return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: n_out must equal action_space_size and be in [1, 64]");
-  if (net->noise_kind != 0) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: noise_kind must be 0 (the Q actor has no action noise)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_qnet_wide: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & 3u) return fail(S2D_EINVAL, "rollout action buffer must be 4-byte aligned");
-  }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_qnet_wide(h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride, h->n,
-                                               n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name, sizeof h->kernel_name);
-  if (rc == S2D_EINVAL) return S2D_EINVAL;
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_qnet_wide: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  if ((rc = actor_pointers(who, net->params, net->epsilon, nullptr, net->noise_kind, 0)) != S2D_OK) return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_wide(a, who, net, pl); });
 }
 
 S2D_API int s2d_rollout_actor_wide(S2DHandle h, int n_steps, const S2DWideNet* net, const S2DRollout* out, float* terminal_obs,
                                   void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: net is NULL");
-  if (h->mode == S2D_MODE_DISCRETE)
-    return fail(S2D_EINVAL, "s2d_rollout_actor_wide needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet_wide");
-  const int na = h->mode == S2D_MODE_TURN4 ? 4 : 1;
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: n_steps must be >= 1");
-  if (s2d_internal_wide_check("s2d_rollout_actor_wide", net) != S2D_OK) return S2D_EINVAL;
-  if (net->n_out != na)
-    return fail(S2D_EINVAL, h->mode == S2D_MODE_TURN4 ? "s2d_rollout_actor_wide: n_out must be 4 on a turning engine"
-                                                      : "s2d_rollout_actor_wide: n_out must be 1 on a continuous (non-turning) engine");
-  if (net->noise_kind != 0 && net->noise_kind != 1)
-    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: noise_kind must be 0 (none) or 1 (Gaussian)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
-    return fail(S2D_EINVAL, "s2d_rollout_actor_wide: Gaussian noise needs a non-NULL, 4-byte aligned noise buffer [2][n_out]");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_actor_wide: terminal_obs must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
-      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
-  }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_actor_wide(h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x),
-                                                h->stride, h->n, n_steps, net, &ro, terminal_obs, &h->out, stream, h->kernel_name,
-                                                sizeof h->kernel_name);
-  if (rc == S2D_EINVAL) return S2D_EINVAL;
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_actor_wide: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  static const char who[] = "s2d_rollout_actor_wide";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kContinuousEngines,
+                       "s2d_rollout_actor_wide needs a continuous-action engine (use_continuous_action = 1); use s2d_rollout_qnet_wide", n_steps,
+                       out, terminal_obs, nullptr, ro);
+  if (rc != S2D_OK) return rc;
+  ActorPlanBuf pl;
+  if (s2d_internal_wide_plan(who, net, &pl) != S2D_OK) return S2D_EINVAL;
+  if ((rc = actor_n_out(who, h, net->n_out)) != S2D_OK ||
+      (rc = actor_pointers(who, net->params, net->epsilon, net->noise, net->noise_kind, 1)) != S2D_OK)
+    return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_wide(a, who, net, pl); });
 }
 
 S2D_API int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet* net, const S2DRollout* out, float* terminal_obs,
                                float* logp, void* stream) {
-  if (!h) return fail(S2D_EINVAL, "NULL handle");
-  if (!net) return fail(S2D_EINVAL, "s2d_rollout_policy: net is NULL");
-  const int na = h->mode == S2D_MODE_DISCRETE ? h->cfg.task.action_space_size : h->mode == S2D_MODE_TURN4 ? 4 : 1;
-  if (n_steps < 1) return fail(S2D_EINVAL, "s2d_rollout_policy: n_steps must be >= 1");
-  const auto width_ok = [](int w) { return w >= 16 && w <= 128 && w % 16 == 0; };
-  if (!width_ok(net->hidden1) || !width_ok(net->hidden2))
+  static const char who[] = "s2d_rollout_policy";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kDiscreteEngine | kContinuousEngines, "", n_steps, out, terminal_obs, logp, ro);
+  if (rc != S2D_OK) return rc;
+  const bool discrete = h->mode == S2D_MODE_DISCRETE;
+  const auto bad = [](const void* q, unsigned m) { return !q || (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  if (!actor_width_ok(net->hidden1, net->hidden2))
     return fail(S2D_EINVAL, "s2d_rollout_policy: hidden widths must be multiples of 16 in [16, 128] (the weights live in LDS)");
-  if (net->n_out != na || na < 1 || na > 64)
-    return fail(S2D_EINVAL, h->mode == S2D_MODE_DISCRETE ? "s2d_rollout_policy: n_out must equal action_space_size and be in [1, 64]"
-                            : h->mode == S2D_MODE_TURN4  ? "s2d_rollout_policy: n_out must be 4 on a turning engine"
-                                                         : "s2d_rollout_policy: n_out must be 1 on a continuous (non-turning) engine");
-  if (net->activation != 0 && net->activation != 1) return fail(S2D_EINVAL, "s2d_rollout_policy: activation must be 0 (ReLU) or 1 (Tanh)");
-  if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return fail(S2D_EINVAL, "s2d_rollout_policy: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->deterministic || (reinterpret_cast<uintptr_t>(net->deterministic) & 3u))
-    return fail(S2D_EINVAL, "s2d_rollout_policy: deterministic must be a non-NULL, 4-byte aligned device pointer");
-  if (h->mode != S2D_MODE_DISCRETE && (!net->log_std || (reinterpret_cast<uintptr_t>(net->log_std) & 3u)))
-    return fail(S2D_EINVAL, "s2d_rollout_policy: a continuous engine needs a non-NULL, 4-byte aligned log_std buffer [n_out]");
-  if (reinterpret_cast<uintptr_t>(terminal_obs) & 3u) return fail(S2D_EINVAL, "s2d_rollout_policy: terminal_obs must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(logp) & 3u) return fail(S2D_EINVAL, "s2d_rollout_policy: logp must be 4-byte aligned");
-  RolloutOut ro{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (out) {
-    ro = RolloutOut{out->obs, out->action, out->reward, out->done, out->result, 0};
-    if (reinterpret_cast<uintptr_t>(out->obs) & 3u) return fail(S2D_EINVAL, "rollout obs buffer must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->action) & (h->mode == S2D_MODE_TURN4 ? 15u : 3u))
-      return fail(S2D_EINVAL, "rollout action buffer must be 4-byte (16-byte on a turning engine) aligned");
+  if (discrete) {
+    if (net->n_out != h->cfg.task.action_space_size || net->n_out < 1 || net->n_out > 64)
+      return fail(S2D_EINVAL, "s2d_rollout_policy: n_out must equal action_space_size and be in [1, 64]");
+  } else if ((rc = actor_n_out(who, h, net->n_out)) != S2D_OK) {
+    return rc;
   }
-  DeviceGuard guard(h->device);
-  const int rc = s2d_internal_rollout_policy(h->mode, h->nk, &h->hot, h->rare_dev, reinterpret_cast<float*>(h->buf.player_x), h->stride,
-                                             h->n, n_steps, net->hidden1, net->hidden2, na, net->activation, net->params,
-                                             h->mode == S2D_MODE_DISCRETE ? nullptr : net->log_std, net->deterministic, &ro,
-                                             terminal_obs, logp, &h->out, stream, h->kernel_name);
-  if (rc == -1) return fail(S2D_EINVAL, "s2d_rollout_policy: the network does not fit the LDS of a workgroup");
-  if (rc != 0) return fail(S2D_EHIP, "s2d_rollout_policy: hipGetDevice or hipFuncSetAttribute failed");
-  HIP_TRY(hipGetLastError());
-  h->last_kernel = h->kernel_name;
-  return S2D_OK;
+  if (net->activation != 0 && net->activation != 1) return fail(S2D_EINVAL, "s2d_rollout_policy: activation must be 0 (ReLU) or 1 (Tanh)");
+  if (bad(net->params, 15u)) return fail(S2D_EINVAL, "s2d_rollout_policy: params must be a non-NULL, 16-byte aligned device pointer");
+  if (bad(net->deterministic, 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: deterministic must be a non-NULL, 4-byte aligned device pointer");
+  if (!discrete && bad(net->log_std, 3u))
+    return fail(S2D_EINVAL, "s2d_rollout_policy: a continuous engine needs a non-NULL, 4-byte aligned log_std buffer [n_out]");
+  ActorPlanBuf pl;
+  if ((rc = actor_net_plan(who, net->hidden1, net->hidden2, net->n_out, pl)) != S2D_OK) return rc;
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream, [&](const ActorRollout& a) {
+    return s2d_internal_rollout_policy(a, pl, net->activation, net->params, discrete ? nullptr : net->log_std, net->deterministic, logp);
+  });
 }
 
 S2D_API int s2d_world_model(S2DHandle h, const S2DWorldModel* out, void* stream) {

@@ -22,7 +22,7 @@
 #include <cstdio>
 #include <string>
 
-#include "s2d_actor_net.h"
+#include "s2d_actor_rollout.h"
 #include "s2d_head.h"
 
 // ------------------------------------------------------------------------------------------ network
@@ -222,38 +222,29 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_policy_rollout_kernel(S2DHot
 
 using PolicyKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, QNetDims, int, const float*, const float*,
                               const uint32_t*, RolloutOut, float*, float*, StepOut, int);
-static constexpr int kPolicySlots = 3 * 3;
+struct PolicySlots {};   // the table of allow_lds_slot (s2d_actor_rollout.h) of this unit: 3 x 3 instantiations
 
-// mode = S2D_MODE_*, nk = S2D_NK_*, act_fn = 0 relu | 1 tanh; 0, -1 if the network does not fit the LDS, -2 on a HIP failure
-extern "C" int s2d_internal_rollout_policy(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
-                                           int64_t n, int n_steps, int h1, int h2, int na, int act_fn, const float* params,
-                                           const float* log_std, const uint32_t* det, const RolloutOut* ro, float* term_rec,
-                                           float* logp, const StepOut* o, void* stream, char* name) {
-  QNetDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (!plan_lds(h1, h2, na, d, wave_words, waves, lds)) return -1;
+// act_fn = 0 relu | 1 tanh; 0, or -2 on a HIP failure
+int s2d_internal_rollout_policy(const ActorRollout& a, const ActorPlanBuf& buf, int act_fn, const float* params, const float* log_std,
+                                const uint32_t* det, float* logp) {
+  const ActorPlan<QNetDims>& pl = plan_of<QNetDims>(buf);
 #define S2D_POLICY_ROW(M)                                                                                                \
   {s2d_reach_policy_rollout_kernel<M, S2D_NK_OFF>, s2d_reach_policy_rollout_kernel<M, S2D_NK_LATTICE>,                   \
    s2d_reach_policy_rollout_kernel<M, S2D_NK_SQUARE>}
   static const PolicyKernel table[3][3] = {S2D_POLICY_ROW(S2D_MODE_DISCRETE), S2D_POLICY_ROW(S2D_MODE_CONT1),
                                            S2D_POLICY_ROW(S2D_MODE_TURN4)};
 #undef S2D_POLICY_ROW
-  const PolicyKernel k = table[mode][nk];
-  if (!allow_lds_slot<kPolicySlots>(reinterpret_cast<const void*>(k), 3 * mode + nk)) return -2;
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n, n_steps, d,
-                     act_fn, params, log_std, det, *ro, term_rec, logp, *o, wave_words);
+  const PolicyKernel k = table[a.mode][a.nk];
+  if (!allow_lds_slot<PolicySlots>(reinterpret_cast<const void*>(k), 3 * a.mode + a.nk)) return -2;
+  const int threads = pl.waves * kWave;
+  const unsigned blocks = (unsigned)((a.n + threads - 1) / threads);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), pl.lds, static_cast<hipStream_t>(a.stream), *a.hot, a.rare_dev, a.S, a.stride, a.n,
+                     a.n_steps, pl.d, act_fn, params, log_std, det, *a.ro, a.term_rec, logp, *a.o, pl.wave_words);
   static const char* const mode_names[3] = {"discrete", "cont1", "turn4"};
-  if (name)
-    std::snprintf(name, 96, "s2d_reach_policy_rollout_kernel<mode=%s,noise=%d,act=%s,h1=%d,h2=%d,a=%d,waves=%d>", mode_names[mode],
-                  nk, act_fn ? "tanh" : "relu", h1, h2, na, waves);
+  std::snprintf(a.name, a.name_bytes, "s2d_reach_policy_rollout_kernel<mode=%s,noise=%d,act=%s,h1=%d,h2=%d,a=%d,waves=%d>",
+                mode_names[a.mode], a.nk, act_fn ? "tanh" : "relu", pl.d.h1, pl.d.h2, pl.d.na, pl.waves);
   return 0;
 }
-
-// errors share the thread-local text of s2d_last_error() (defined in s2d_engine.hip)
-extern "C" void s2d_internal_set_error(const char* msg);
 
 // ------------------------------------------------------------------------------------------ the head alone
 __global__ void s2d_debug_policy_head_kernel(int mode, int A, const float* __restrict__ y, const float* __restrict__ log_std_dev,

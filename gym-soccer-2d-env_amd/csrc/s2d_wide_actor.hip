@@ -44,27 +44,9 @@ __global__ __launch_bounds__(kBlock) void s2d_debug_wide_forward_kernel(WideDims
   }
 }
 
-// host side (same library, hidden symbols; the rollouts' C entry points are in s2d_engine.hip, s2d_wide_workspace_bytes and
-// s2d_debug_wide_forward at the end of this file; the plan is in s2d_wide_net.h)
-using WideQNetKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, WideDims, const float*, const float*,
-                                RolloutOut, float*, StepOut, int);
-using WideTanhKernel = void (*)(S2DHot, const S2DRare*, float*, int64_t, int64_t, int, WideDims, const float*, const float*,
-                                RolloutOut, float*, StepOut, int, const float*);
-
-// slots of allow_lds_slot (s2d_actor_net.h): the Q-actor's 3, the tanh actor's 2 x 3 x 2, then s2d_debug_wide_forward's
-static constexpr int kWideSlots = 3 + 2 * 3 * 2 + 1;
-static bool allow_lds(const void* fn, int slot) { return allow_lds_slot<kWideSlots>(fn, slot); }
-
-extern "C" void s2d_internal_set_error(const char* msg);
-
+// host side (same library, hidden symbols; the rollouts' C entry points are in s2d_engine.hip, the tables and the launch in
+// s2d_actor_rollout.h, s2d_wide_workspace_bytes and s2d_debug_wide_forward at the end of this file; the plan is in s2d_wide_net.h)
 static const char* const kActName[3] = {"relu", "tanh", "sigmoid"};
-
-// "400-300"
-static std::string widths_text(const S2DWideNet* net) {
-  std::string s;
-  for (int l = 0; l < net->n_hidden; ++l) s += (l ? "-" : "") + std::to_string(net->hidden[l]);
-  return s;
-}
 
 static size_t workspace_bytes(const WideDims& d) { return ((size_t)d.nfrag * kWave + d.nbias) * sizeof(float); }
 
@@ -72,7 +54,8 @@ static size_t workspace_bytes(const WideDims& d) { return ((size_t)d.nfrag * kWa
 // error text set (`who` = the entry point's name).  S2D_WIDE_PLAN=waves,tiles in the environment, read at every launch, overrides
 // the plan's choice of waves per workgroup and env tiles per pass (testing: the results do not depend on them); a pair that is
 // not of {4, 2, 1} or does not fit the LDS is refused.
-static int wide_plan(const char* who, const S2DWideNet* net, WideDims* d, int* wave_words, int* waves, size_t* lds) {
+int s2d_internal_wide_plan(const char* who, const S2DWideNet* net, ActorPlanBuf* buf) {
+  ActorPlan<WideDims>* const pl = &plan_in<WideDims>(buf);
   const std::string w(who);
   if (net->n_hidden < 1 || net->n_hidden > kWideMaxHidden) {
     s2d_internal_set_error((w + ": n_hidden must be in [1, 5]").c_str());
@@ -93,7 +76,7 @@ static int wide_plan(const char* who, const S2DWideNet* net, WideDims* d, int* w
   int fw = 0, ft = 0;
   const char* const env = std::getenv("S2D_WIDE_PLAN");
   if (env && *env && std::sscanf(env, "%d,%d", &fw, &ft) != 2) fw = ft = -1;
-  if (!wide_plan_lds(net->n_hidden, net->hidden, net->n_out, net->activation, fw, ft, *d, *wave_words, *waves, *lds)) {
+  if (!wide_plan_lds(net->n_hidden, net->hidden, net->n_out, net->activation, fw, ft, pl->d, pl->wave_words, pl->waves, pl->lds)) {
     s2d_internal_set_error((w + ": S2D_WIDE_PLAN=" + (env ? env : "") + " is not waves,tiles of {4, 2, 1} that fit the LDS for 10-" +
                             widths_text(net) + "-" + std::to_string(net->n_out)).c_str());
     return S2D_EINVAL;
@@ -101,7 +84,7 @@ static int wide_plan(const char* who, const S2DWideNet* net, WideDims* d, int* w
   return S2D_OK;
 }
 
-// the workspace of a checked shape: S2D_EINVAL with the text set if it is NULL, misaligned or too small
+// the workspace of a planned shape: S2D_EINVAL with the text set if it is NULL, misaligned or too small
 static int wide_workspace(const char* who, const S2DWideNet* net, const WideDims& d) {
   const std::string w(who);
   if (!net->workspace || (reinterpret_cast<uintptr_t>(net->workspace) & 255u)) {
@@ -117,75 +100,28 @@ static int wide_workspace(const char* who, const S2DWideNet* net, const WideDims
   return S2D_OK;
 }
 
-// the shape check alone, for the entry points of s2d_engine.hip (they check their engine's side and the other pointers
-// themselves; the workspace is checked by the launch functions below, before anything is enqueued)
-extern "C" int s2d_internal_wide_check(const char* who, const S2DWideNet* net) {
-  WideDims d;
-  int wave_words, waves;
-  size_t lds;
-  return wide_plan(who, net, &d, &wave_words, &waves, &lds);
-}
-
 // params -> workspace in fragment order, on `stream`
-static void launch_pack(WideDims& d, const S2DWideNet* net, hipStream_t stream) {
-  d.wf = static_cast<const float*>(net->workspace);
+static void launch_pack(const WideDims& d, const S2DWideNet* net, hipStream_t stream) {
   const int words = d.nfrag * kWave + d.nbias;
   hipLaunchKernelGGL(s2d_wide_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, net->params,
                      static_cast<float*>(net->workspace));
 }
 
-// launches the pack kernel and the Q-network actor rollout of a checked network: 0, S2D_EINVAL (the error text set), or -2 on a
-// HIP failure
-extern "C" int s2d_internal_rollout_qnet_wide(int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride, int64_t n,
-                                              int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
-                                              const StepOut* o, void* stream, char* name, size_t name_bytes) {
-  WideDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (wide_plan("s2d_rollout_qnet_wide", net, &d, &wave_words, &waves, &lds) != S2D_OK) return S2D_EINVAL;
-  if (wide_workspace("s2d_rollout_qnet_wide", net, d) != S2D_OK) return S2D_EINVAL;
-  static const WideQNetKernel table[3] = {s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_OFF, false, WideDims>,
-                                           s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_LATTICE, false, WideDims>,
-                                           s2d_reach_actor_rollout_kernel<S2D_MODE_DISCRETE, S2D_NK_SQUARE, false, WideDims>};
-  if (!allow_lds(reinterpret_cast<const void*>(table[nk]), nk)) return -2;
-  launch_pack(d, net, static_cast<hipStream_t>(stream));
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(table[nk], dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n,
-                     n_steps, d, net->params, net->epsilon, *ro, term_rec, *o, wave_words);
-  if (name)
-    std::snprintf(name, name_bytes, "s2d_wide_qnet_rollout_kernel<noise=%d,act=%s,h=%s,a=%d,waves=%d,tiles=%d>", nk,
-                  kActName[net->activation], widths_text(net).c_str(), net->n_out, waves, d.tiles);
-  return 0;
-}
-
-// mode = S2D_MODE_CONT1 | S2D_MODE_TURN4 (n_out = 1 | 4), the noise kind is net's
-extern "C" int s2d_internal_rollout_actor_wide(int mode, int nk, const S2DHot* hot, const S2DRare* rare_dev, float* S, int64_t stride,
-                                               int64_t n, int n_steps, const S2DWideNet* net, const RolloutOut* ro, float* term_rec,
-                                               const StepOut* o, void* stream, char* name, size_t name_bytes) {
-  WideDims d;
-  int wave_words, waves;
-  size_t lds;
-  if (wide_plan("s2d_rollout_actor_wide", net, &d, &wave_words, &waves, &lds) != S2D_OK) return S2D_EINVAL;
-  if (wide_workspace("s2d_rollout_actor_wide", net, d) != S2D_OK) return S2D_EINVAL;
-#define S2D_WIDE_ROW(M)                                                                                                       \
-  {s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, false, WideDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, false, WideDims, const float*>, \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, false, WideDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_OFF, true, WideDims, const float*>,   \
-   s2d_reach_actor_rollout_kernel<M, S2D_NK_LATTICE, true, WideDims, const float*>, s2d_reach_actor_rollout_kernel<M, S2D_NK_SQUARE, true, WideDims, const float*>}
-  static const WideTanhKernel table[2][6] = {S2D_WIDE_ROW(S2D_MODE_CONT1), S2D_WIDE_ROW(S2D_MODE_TURN4)};
-#undef S2D_WIDE_ROW
-  const int gauss = net->noise_kind ? 1 : 0;
-  const int m = mode == S2D_MODE_TURN4 ? 1 : 0, v = 3 * gauss + nk;
-  const WideTanhKernel k = table[m][v];
-  if (!allow_lds(reinterpret_cast<const void*>(k), 3 + 6 * m + v)) return -2;
-  launch_pack(d, net, static_cast<hipStream_t>(stream));
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), *hot, rare_dev, S, stride, n, n_steps, d,
-                     net->params, net->epsilon, *ro, term_rec, *o, wave_words, gauss ? net->noise : nullptr);
-  if (name)
-    std::snprintf(name, name_bytes, "s2d_wide_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,act=%s,h=%s,a=%d,waves=%d,tiles=%d>",
-                  m ? "turn4" : "cont1", nk, gauss, kActName[net->activation], widths_text(net).c_str(), net->n_out, waves, d.tiles);
+// the workspace check, then the pack kernel and the rollout
+int s2d_internal_rollout_wide(const ActorRollout& a, const char* who, const S2DWideNet* net, const ActorPlanBuf& buf) {
+  ActorPlan<WideDims> pl = plan_of<WideDims>(buf);
+  if (wide_workspace(who, net, pl.d) != S2D_OK) return S2D_EINVAL;
+  pl.d.wf = static_cast<const float*>(net->workspace);
+  const float* const noise = net->noise_kind ? net->noise : nullptr;
+  if (!launch_actor_rollout(a, pl, net->params, net->epsilon, noise, [&] { launch_pack(pl.d, net, static_cast<hipStream_t>(a.stream)); }))
+    return -2;
+  if (a.mode == S2D_MODE_DISCRETE)
+    std::snprintf(a.name, a.name_bytes, "s2d_wide_qnet_rollout_kernel<noise=%d,act=%s,h=%s,a=%d,waves=%d,tiles=%d>", a.nk,
+                  kActName[net->activation], widths_text(net).c_str(), net->n_out, pl.waves, pl.d.tiles);
+  else
+    std::snprintf(a.name, a.name_bytes, "s2d_wide_actor_rollout_kernel<mode=%s,noise=%d,gauss=%d,act=%s,h=%s,a=%d,waves=%d,tiles=%d>",
+                  a.mode == S2D_MODE_TURN4 ? "turn4" : "cont1", a.nk, noise ? 1 : 0, kActName[net->activation], widths_text(net).c_str(),
+                  net->n_out, pl.waves, pl.d.tiles);
   return 0;
 }
 
@@ -200,38 +136,22 @@ S2D_API size_t s2d_wide_workspace_bytes(const S2DWideNet* shape) {
 
 S2D_API int s2d_debug_wide_forward(const S2DWideNet* shape, const void* obs_dev, int64_t n, void* y_dev, void* greedy_dev, char* name,
                                    void* stream) {
+  static const char who[] = "s2d_debug_wide_forward";
   if (!shape) { s2d_internal_set_error("s2d_debug_wide_forward: shape is NULL"); return S2D_EINVAL; }
-  WideDims d;
-  int wave_words, waves;
-  size_t lds;
-  int rc = wide_plan("s2d_debug_wide_forward", shape, &d, &wave_words, &waves, &lds);
+  ActorPlanBuf buf;
+  int rc = s2d_internal_wide_plan(who, shape, &buf);
+  if (rc == S2D_OK) rc = debug_forward_args(who, shape->params, obs_dev, n, y_dev, greedy_dev);
+  if (rc == S2D_OK) rc = wide_workspace(who, shape, plan_of<WideDims>(buf).d);
   if (rc != S2D_OK) return rc;
-  const char* err = nullptr;
-  if (n < 1 || n > INT32_MAX) err = "s2d_debug_wide_forward: n must be in [1, 2^31 - 1]";
-  else if (!shape->params || (reinterpret_cast<uintptr_t>(shape->params) & 15u))
-    err = "s2d_debug_wide_forward: params must be a non-NULL, 16-byte aligned device pointer";
-  else if (!obs_dev || !y_dev || !greedy_dev ||
-           ((reinterpret_cast<uintptr_t>(obs_dev) | reinterpret_cast<uintptr_t>(y_dev) | reinterpret_cast<uintptr_t>(greedy_dev)) & 3u))
-    err = "s2d_debug_wide_forward: obs, y and greedy must be non-NULL, 4-byte aligned device pointers";
-  if (err) { s2d_internal_set_error(err); return S2D_EINVAL; }
-  rc = wide_workspace("s2d_debug_wide_forward", shape, d);
-  if (rc != S2D_OK) return rc;
-  if (!allow_lds(reinterpret_cast<const void*>(s2d_debug_wide_forward_kernel), kWideSlots - 1)) {
-    s2d_internal_set_error("s2d_debug_wide_forward: hipGetDevice or hipFuncSetAttribute failed");
-    return S2D_EHIP;
-  }
-  launch_pack(d, shape, static_cast<hipStream_t>(stream));
-  const int threads = waves * kWave;
-  const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  hipLaunchKernelGGL(s2d_debug_wide_forward_kernel, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), d,
-                     static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev), static_cast<int32_t*>(greedy_dev), wave_words);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    s2d_internal_set_error((std::string("s2d_debug_wide_forward: launch: ") + hipGetErrorString(e)).c_str());
-    return S2D_EHIP;
-  }
-  if (name)
+  ActorPlan<WideDims> pl = plan_of<WideDims>(buf);
+  pl.d.wf = static_cast<const float*>(shape->workspace);
+  rc = debug_forward_launch(who, reinterpret_cast<const void*>(s2d_debug_wide_forward_kernel), pl, n, [&](unsigned blocks, int threads) {
+    launch_pack(pl.d, shape, static_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(s2d_debug_wide_forward_kernel, dim3(blocks), dim3(threads), pl.lds, static_cast<hipStream_t>(stream), pl.d,
+                       static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev), static_cast<int32_t*>(greedy_dev), pl.wave_words);
+  });
+  if (rc == S2D_OK && name)
     std::snprintf(name, 96, "s2d_debug_wide_forward_kernel<act=%s,h=%s,a=%d,waves=%d,tiles=%d>", kActName[shape->activation],
-                  widths_text(shape).c_str(), shape->n_out, waves, d.tiles);
-  return S2D_OK;
+                  widths_text(shape).c_str(), shape->n_out, pl.waves, pl.d.tiles);
+  return rc;
 }

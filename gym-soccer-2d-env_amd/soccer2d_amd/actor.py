@@ -8,7 +8,7 @@ It owns ONE packed fp32 parameter buffer in torch's ``nn.Sequential(Linear, ReLU
 learner updates them in place (``sync()`` after an optimiser phase, ``epsilon = ...``) and a captured graph acts with the new
 values at its next replay.  SB3's ``DQN.q_net.q_net`` (an nn.Sequential of that shape) qualifies as the source module.
 """
-import ctypes as C
+import math
 
 import torch
 
@@ -20,84 +20,138 @@ MAX_ACTIONS = 64
 
 
 _NO_OPS = (torch.nn.Identity, torch.nn.Flatten)   # SB3's features extractor of a flat Box observation is a Flatten
+_ACT_KINDS = {torch.nn.ReLU: 'ReLU', torch.nn.Tanh: 'Tanh', torch.nn.Sigmoid: 'Sigmoid'}
 
 
-def _linears(module, tanh=False):
-    """The three nn.Linear layers of a Linear-ReLU-Linear-ReLU-Linear module (the form the kernel evaluates), in order; with
-    tanh=True the module must end in a Tanh (the deterministic actor's head).  Leaf modules are read in registration order;
-    Identity / Flatten are skipped; anything else (another activation, a missing ReLU or Tanh, a fourth layer) is rejected:
+def _read_layers(module, acts=('ReLU',), hidden=(2, 2), tanh_head=False, many=False):
+    """(the nn.Linear layers in order, the hidden activation's name in lower case) of a module of the form the kernels evaluate:
+    Linear-(F-Linear) x L with L in hidden = (fewest, most) hidden layers and one F of `acts` throughout; with tanh_head the module
+    must end in one more Tanh (the deterministic actors' head); with many, `module` may be a list / tuple of modules read one
+    after the other (SB3's ``[policy.mlp_extractor.policy_net, policy.action_net]``).  Leaf modules are read in registration
+    order; Identity / Flatten are skipped; anything else (another activation, a mix, a missing one, a layer too many) is refused:
     the kernel would silently act with a different function."""
-    leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
-    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU)
-             else 'Tanh' if isinstance(m, torch.nn.Tanh) else type(m).__name__ for m in leaves]
-    want = ['Linear', 'ReLU', 'Linear', 'ReLU', 'Linear'] + (['Tanh'] if tanh else [])
-    if kinds != want:
-        what = 'actor' if tanh else 'Q-network'
-        raise ValueError(f'the {what} must be {"-".join(want)} (10 -> H1 -> H2 -> A), got {"-".join(kinds) or "nothing"}')
-    return [leaves[0], leaves[2], leaves[4]]
+    mods = list(module) if many and isinstance(module, (list, tuple)) else [module]
+    leaves = [m for mod in mods for m in mod.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
+    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else _ACT_KINDS.get(type(m), type(m).__name__) for m in leaves]
+    what = 'actor' if tanh_head else 'Q-network'
+    got = '-'.join(kinds) or 'nothing'
+    fewest, most = hidden
+    if fewest == most:                  # one depth: the module is one of len(acts) forms
+        for name in acts:
+            want = ['Linear'] + [name, 'Linear'] * most + (['Tanh'] if tanh_head else [])
+            if kinds == want:
+                return leaves[0:2 * most + 1:2], name.lower()
+        if len(acts) == 1:
+            raise ValueError(f'the {what} must be {"-".join(want)} (10 -> H1 -> H2 -> A), got {got}')
+        raise ValueError('the policy must be Linear-F-Linear-F-Linear (10 -> H1 -> H2 -> A) with F = ReLU or Tanh, the same twice, '
+                         f'got {got}')
+    names = ', '.join(acts[:-1]) + ' or ' + acts[-1]
+    form = 'Linear-(F-Linear) x L' + ('-Tanh' if tanh_head else '') + f', L = {fewest} .. {most} hidden layers, F = {names}'
+    body = kinds
+    if tanh_head:
+        if not kinds or kinds[-1] != 'Tanh':
+            raise ValueError(f'the actor must end in a Tanh ({form}), got {got}')
+        body = kinds[:-1]
+    if len(body) % 2 == 0 or any(k != 'Linear' for k in body[0::2]):
+        raise ValueError(f'the {what} must be {form}, got {got}')
+    used = set(body[1::2])
+    n_hidden = len(body) // 2
+    if not fewest <= n_hidden <= most:
+        raise ValueError(f'the {what} must have {fewest} to {most} hidden layers ({form}), got {n_hidden}: {got}')
+    if len(used) > 1 and used <= set(acts):
+        raise ValueError(f'the {what} must use one activation throughout, {names}, not a mix ({form}), got {got}')
+    if not used <= set(acts):
+        raise ValueError(f'the hidden activation must be {names} ({form}), got {got}')
+    return leaves[0:len(body):2], used.pop().lower()
 
 
-def param_count(hidden1, hidden2, n_actions):
-    return OBS_DIM * hidden1 + hidden1 + hidden1 * hidden2 + hidden2 + n_actions * hidden2 + n_actions
+class _PackedActor:
+    """What every actor does alike: ONE packed fp32 parameter buffer on a resolved device, sized from shapes(), loaded from a
+    module the class's reader accepts (load_from) and refreshed from it in place (sync).  A class says how its modules read
+    (`_grid`, the arguments of _read_layers), what its texts call the network (`_what`), which C entry point of the reach-ball
+    engine launches it (`_entry`; Engine.rollout_qnet / rollout_actor read it), and its layers' widths (`_widths`)."""
 
+    _grid = {}
+    _what = 'Q-network'
+    _shape_error = '{what} shapes {got} do not match the actor {want}'
+    _entry = None
+    in_dim = OBS_DIM
+    activation = None               # the hidden activation's name, where the class has a choice
+    _buffers = ('params',)          # the device buffers a snapshot() copies
+    _has_noise = False              # the Gaussian action-noise rows of the deterministic actors
 
-class QNetActor:
-    """Packed parameters + device epsilon of a 10-H1-H2-A ReLU MLP for Engine.rollout_qnet."""
-
-    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05):
-        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
-            if int(w) not in WIDTHS:
-                raise ValueError(f'{name} must be a multiple of 16 in [16, 128], got {w}')
-        if not 1 <= int(n_actions) <= MAX_ACTIONS:
-            raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
-        self.hidden1, self.hidden2, self.n_actions = int(hidden1), int(hidden2), int(n_actions)
+    def _init_packed(self, device):
         self.device = torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         # torch's device allocations are 256-byte aligned (the ABI asks for 16)
-        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32, device=self.device)
-        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._eps_value = None
-        self.epsilon = epsilon
+        self.params = torch.zeros(sum(math.prod(shape) for shape in self.shapes()), dtype=torch.float32, device=self.device)
         self._module = None
 
     @classmethod
-    def from_module(cls, module, device=None, epsilon=0.05):
-        """An actor shaped like `module` (three nn.Linear layers 10 -> H1 -> H2 -> A), loaded from it."""
-        l1, l2, l3 = _linears(module)
-        dev = device if device is not None else l1.weight.device
-        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon)
-        actor.load_from(module)
-        return actor
+    def _read(cls, module):
+        return _read_layers(module, **cls._grid)
+
+    @property
+    def _outputs(self):
+        """the output layer's width: n_actions, or n_out in the classes that call it so"""
+        return self.n_actions
+
+    def _widths(self):
+        return (self.hidden1, self.hidden2, self._outputs)
 
     def shapes(self):
-        h1, h2, a = self.hidden1, self.hidden2, self.n_actions
-        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
+        out, win = [], self.in_dim
+        for w in self._widths():
+            out += [(w, win), (w,)]
+            win = w
+        return tuple(out)
+
+    def _validate(self, module):
+        linears, act = self._read(module)
+        got = []
+        for lin in linears:
+            if lin.bias is None:
+                raise ValueError(f'every nn.Linear of the {self._what} needs a bias')
+            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
+        if self.activation is not None and act != self.activation:
+            raise ValueError(f'the {self._what}\'s activation is {act}, the actor\'s {self.activation}')
+        if tuple(got) != self.shapes():
+            raise ValueError(self._shape_error.format(what=self._what, got=got, want=list(self.shapes())))
 
     def load_from(self, module):
-        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
-        layers = _linears(module)
-        got = []
-        for lin in layers:
-            if lin.bias is None:
-                raise ValueError('every nn.Linear of the Q-network needs a bias')
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'Q-network shapes {got} do not match the actor {list(self.shapes())}')
+        """Validate `module` against this actor (shapes, and the activation where there is a choice), remember it, and pack its
+        parameters (sync())."""
+        self._validate(module)
         self._module = module
-        self.sync()
-        return self
+        return self.sync()
 
     def sync(self):
-        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
+        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation of the buffers the
+        kernel reads (capturable)."""
         if self._module is None:
             raise ValueError('no module loaded (load_from)')
         srcs = []
-        for lin in _linears(self._module):
+        for lin in self._read(self._module)[0]:
             srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
         with torch.no_grad():
             torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
         return self
+
+    def _frozen(self, snap):
+        """`snap`, a new actor of this shape, with copies of this one's buffers (snapshot())"""
+        for name in self._buffers:
+            getattr(snap, name).copy_(getattr(self, name))
+        return snap
+
+
+class _Epsilon:
+    """the device epsilon scalar of the epsilon actors"""
+
+    def _init_epsilon(self, epsilon):
+        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._eps_value = None
+        self.epsilon = epsilon
 
     @property
     def epsilon(self):
@@ -113,6 +167,58 @@ class QNetActor:
     def epsilon_tensor(self):
         return self._eps
 
+
+class _Deterministic:
+    """the device `deterministic` word of the stochastic policies"""
+
+    def _init_deterministic(self, deterministic):
+        self._det = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._det_value = False
+        self.deterministic = deterministic
+
+    @property
+    def deterministic(self):
+        return self._det_value
+
+    @deterministic.setter
+    def deterministic(self, value):
+        """Written in place into the device word the kernel reads (stream-ordered on torch's current stream)."""
+        self._det_value = bool(value)
+        self._det.fill_(int(self._det_value))
+
+    @property
+    def deterministic_tensor(self):
+        return self._det
+
+
+def param_count(hidden1, hidden2, n_actions):
+    return OBS_DIM * hidden1 + hidden1 + hidden1 * hidden2 + hidden2 + n_actions * hidden2 + n_actions
+
+
+class QNetActor(_Epsilon, _PackedActor):
+    """Packed parameters + device epsilon of a 10-H1-H2-A ReLU MLP for Engine.rollout_qnet."""
+
+    _entry = 's2d_rollout_qnet'
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05):
+        for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
+            if int(w) not in WIDTHS:
+                raise ValueError(f'{name} must be a multiple of 16 in [16, 128], got {w}')
+        if not 1 <= int(n_actions) <= MAX_ACTIONS:
+            raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
+        self.hidden1, self.hidden2, self.n_actions = int(hidden1), int(hidden2), int(n_actions)
+        self._init_packed(device)
+        self._init_epsilon(epsilon)
+
+    @classmethod
+    def from_module(cls, module, device=None, epsilon=0.05):
+        """An actor shaped like `module` (three nn.Linear layers 10 -> H1 -> H2 -> A), loaded from it."""
+        (l1, l2, l3), _ = cls._read(module)
+        dev = device if device is not None else l1.weight.device
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon)
+        actor.load_from(module)
+        return actor
+
     def c_struct(self):
         net = _capi.S2DQNet()
         net.hidden1, net.hidden2, net.n_actions, net.reserved = self.hidden1, self.hidden2, self.n_actions, 0
@@ -124,7 +230,7 @@ class QNetActor:
 ACTOR_OUTPUTS = (1, 4)   # use_continuous_action without / with use_turning
 
 
-class DeterministicActor:
+class DeterministicActor(_Epsilon, _PackedActor):
     """Packed parameters, device epsilon and Gaussian action noise of a 10-H1-H2-A tanh actor for Engine.rollout_actor.
 
     a = tanh(W3 relu(W2 relu(W1 x + b1) + b2) + b3), SB3's DDPG / TD3 ``model.actor.mu``; A = 1 on a continuous engine, 4 on a
@@ -132,6 +238,13 @@ class DeterministicActor:
     (truncated at |z| <= 5.77), and clips to [-1, 1], as SB3's NormalActionNoise does.  The parameter, epsilon and (mu, sigma)
     buffers are written in place and read when the kernel runs, so a captured graph acts with what they hold at replay; the
     noise kind (None or not) selects the kernel and is fixed at capture."""
+
+    _grid = dict(tanh_head=True)
+    _what = 'actor'
+    _shape_error = '{what} shapes {got} do not match {want}'
+    _entry = 's2d_rollout_actor'
+    _has_noise = True
+    _outputs = property(lambda self: self.n_out)
 
     def __init__(self, hidden1=64, hidden2=64, n_out=1, device='cuda:0', epsilon=0.0, noise_mean=None, noise_sigma=None):
         for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
@@ -141,67 +254,26 @@ class DeterministicActor:
         if int(n_out) not in ACTOR_OUTPUTS:
             raise ValueError(f'n_out must be 1 (continuous engine) or 4 (turning engine), got {n_out}')
         self.hidden1, self.hidden2, self.n_out = int(hidden1), int(hidden2), int(n_out)
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_out), dtype=torch.float32, device=self.device)
-        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._init_packed(device)
+        self._init_epsilon(epsilon)
+        self._init_noise(noise_mean, noise_sigma)
+
+    def _init_noise(self, noise_mean, noise_sigma):
         self._noise = torch.zeros(2, self.n_out, dtype=torch.float32, device=self.device)   # [mu; sigma]
-        self._eps_value = None
         self._sigma = None
-        self.epsilon = epsilon
         self.noise_mean = 0.0 if noise_mean is None else noise_mean
         self.noise_sigma = noise_sigma
-        self._module = None
 
     @classmethod
     def from_module(cls, module, device=None, epsilon=0.0, noise_mean=None, noise_sigma=None):
         """An actor shaped like `module` (SB3's actor.mu: Linear-ReLU-Linear-ReLU-Linear-Tanh, optionally behind a Flatten or
         Identity), loaded from it."""
-        l1, l2, l3 = _linears(module, tanh=True)
+        (l1, l2, l3), _ = cls._read(module)
         dev = device if device is not None else l1.weight.device
         actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon, noise_mean=noise_mean,
                     noise_sigma=noise_sigma)
         actor.load_from(module)
         return actor
-
-    def shapes(self):
-        h1, h2, a = self.hidden1, self.hidden2, self.n_out
-        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
-
-    def load_from(self, module):
-        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
-        got = []
-        for lin in _linears(module, tanh=True):
-            if lin.bias is None:
-                raise ValueError('every nn.Linear of the actor needs a bias')
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'actor shapes {got} do not match {list(self.shapes())}')
-        self._module = module
-        self.sync()
-        return self
-
-    def sync(self):
-        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
-        if self._module is None:
-            raise ValueError('no module loaded (load_from)')
-        srcs = []
-        for lin in _linears(self._module, tanh=True):
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
-        with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
-        return self
-
-    @property
-    def epsilon(self):
-        return self._eps_value
-
-    @epsilon.setter
-    def epsilon(self, value):
-        """Written in place into the device scalar the kernel reads (stream-ordered on torch's current stream)."""
-        self._eps_value = float(value)
-        self._eps.fill_(self._eps_value)
 
     def _set_row(self, row, value):
         v = torch.as_tensor(value, dtype=torch.float32).reshape(-1)
@@ -235,10 +307,6 @@ class DeterministicActor:
     def noise_kind(self):
         return 0 if self._sigma is None else 1
 
-    @property
-    def epsilon_tensor(self):
-        return self._eps
-
     def c_struct(self):
         net = _capi.S2DActorNet()
         net.hidden1, net.hidden2, net.n_out, net.noise_kind = self.hidden1, self.hidden2, self.n_out, self.noise_kind
@@ -248,23 +316,10 @@ class DeterministicActor:
         return net
 
 
-def _policy_layers(module):
-    """(the three nn.Linear layers, activation 0 ReLU / 1 Tanh) of a stochastic policy: Linear-F-Linear-F-Linear with F = ReLU
-    or Tanh, both the same.  `module` is one nn.Module, or a list / tuple of modules read one after the other -- SB3's pair
-    ``[policy.mlp_extractor.policy_net, policy.action_net]``.  Identity / Flatten are skipped; mixed activations, any other
-    activation, a missing one or a fourth layer are refused: the kernel would silently act with a different function."""
-    mods = list(module) if isinstance(module, (list, tuple)) else [module]
-    leaves = [m for mod in mods for m in mod.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
-    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU)
-             else 'Tanh' if isinstance(m, torch.nn.Tanh) else type(m).__name__ for m in leaves]
-    for act, name in enumerate(('ReLU', 'Tanh')):
-        if kinds == ['Linear', name, 'Linear', name, 'Linear']:
-            return [leaves[0], leaves[2], leaves[4]], act
-    raise ValueError('the policy must be Linear-F-Linear-F-Linear (10 -> H1 -> H2 -> A) with F = ReLU or Tanh, the same twice, '
-                     f'got {"-".join(kinds) or "nothing"}')
+_POLICY_GRID = dict(acts=('ReLU', 'Tanh'), many=True)
 
 
-class StochasticActor:
+class StochasticActor(_Deterministic, _PackedActor):
     """Packed parameters, device log_std and the deterministic word of a 10-H1-H2-A stochastic policy for Engine.rollout_policy
     (s2d_rollout_policy): on-policy collection for PPO / A2C.
 
@@ -276,6 +331,11 @@ class StochasticActor:
     log_std and the deterministic word are device buffers written in place and read when the kernel runs, so a captured graph
     acts with what they hold at replay: an evaluation pass is the collection graph with ``deterministic = True``."""
 
+    _grid = _POLICY_GRID
+    _what = 'policy'
+    _buffers = ('params', '_log_std')
+    _outputs = property(lambda self: self.n_out)
+
     def __init__(self, hidden1=64, hidden2=64, n_out=16, activation='tanh', device='cuda:0', log_std=0.0, deterministic=False):
         for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
             if int(w) not in WIDTHS:
@@ -285,16 +345,10 @@ class StochasticActor:
         if activation not in ('relu', 'tanh'):
             raise ValueError(f"activation must be 'relu' or 'tanh', got {activation!r}")
         self.hidden1, self.hidden2, self.n_out, self.activation = int(hidden1), int(hidden2), int(n_out), activation
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self.params = torch.zeros(param_count(self.hidden1, self.hidden2, self.n_out), dtype=torch.float32, device=self.device)
+        self._init_packed(device)
+        self._init_deterministic(deterministic)
         self._log_std = torch.zeros(self.n_out, dtype=torch.float32, device=self.device)
-        self._det = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._det_value = False
         self.log_std = log_std
-        self.deterministic = deterministic
-        self._module = None
         self._log_std_src = None
 
     @classmethod
@@ -303,30 +357,16 @@ class StochasticActor:
         with F = ReLU or Tanh (a leading Flatten / Identity is skipped), or a list / tuple of modules that read so one after the
         other: SB3's ``[model.policy.mlp_extractor.policy_net, model.policy.action_net]``.  log_std: None (zeros), a scalar,
         [A] values, or a tensor / nn.Parameter that sync() reads again (SB3's ``model.policy.log_std``)."""
-        (l1, l2, l3), act = _policy_layers(policy_net)
+        (l1, l2, l3), act = cls._read(policy_net)
         dev = device if device is not None else l1.weight.device
-        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=('relu', 'tanh')[act], device=dev,
-                    deterministic=deterministic)
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=act, device=dev, deterministic=deterministic)
         actor.load_from(policy_net, log_std=log_std)
         return actor
-
-    def shapes(self):
-        h1, h2, a = self.hidden1, self.hidden2, self.n_out
-        return ((h1, OBS_DIM), (h1,), (h2, h1), (h2,), (a, h2), (a,))
 
     def load_from(self, policy_net, log_std=None):
         """Validate `policy_net` against this actor (shapes and activation), remember it and `log_std` (if a tensor), and pack
         them (sync())."""
-        layers, act = _policy_layers(policy_net)
-        if ('relu', 'tanh')[act] != self.activation:
-            raise ValueError(f'the policy\'s activation is {("relu", "tanh")[act]}, the actor\'s {self.activation}')
-        got = []
-        for lin in layers:
-            if lin.bias is None:
-                raise ValueError('every nn.Linear of the policy needs a bias')
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'policy shapes {got} do not match the actor {list(self.shapes())}')
+        self._validate(policy_net)
         if log_std is not None:
             if torch.is_tensor(log_std):
                 if log_std.numel() != self.n_out:
@@ -335,20 +375,14 @@ class StochasticActor:
             else:
                 self.log_std = log_std
         self._module = policy_net
-        self.sync()
-        return self
+        return self.sync()
 
     def sync(self):
         """Copy the loaded module's current parameters (and the remembered log_std tensor) into the device buffers: device
         copies, no allocation of the buffers the kernel reads (capturable)."""
-        if self._module is None:
-            raise ValueError('no module loaded (load_from)')
-        srcs = []
-        for lin in _policy_layers(self._module)[0]:
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
-        with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
-            if self._log_std_src is not None:
+        super().sync()
+        if self._log_std_src is not None:
+            with torch.no_grad():
                 self._log_std.copy_(self._log_std_src.detach().reshape(-1))
         return self
 
@@ -365,28 +399,11 @@ class StochasticActor:
             raise ValueError(f'expected a scalar or {self.n_out} values, got {v.numel()}')
         self._log_std.copy_(v.expand(self.n_out))
 
-    @property
-    def deterministic(self):
-        return self._det_value
-
-    @deterministic.setter
-    def deterministic(self, value):
-        """Written in place into the device word the kernel reads (stream-ordered on torch's current stream)."""
-        self._det_value = bool(value)
-        self._det.fill_(int(self._det_value))
-
-    @property
-    def deterministic_tensor(self):
-        return self._det
-
     def snapshot(self, deterministic=None):
         """A frozen copy: a new actor of the same shape with its own parameters, log_std and deterministic word (the old policy
         of a PPO update, an evaluation copy).  It has no module: later sync() calls of the original do not touch it."""
-        snap = type(self)(self.hidden1, self.hidden2, self.n_out, activation=self.activation, device=self.device,
-                          deterministic=self._det_value if deterministic is None else deterministic)
-        snap.params.copy_(self.params)
-        snap._log_std.copy_(self._log_std)
-        return snap
+        return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_out, activation=self.activation, device=self.device,
+                                       deterministic=self._det_value if deterministic is None else deterministic))
 
     def c_struct(self):
         net = _capi.S2DPolicyNet()
@@ -409,7 +426,27 @@ MATCH_WIDTHS = (16, 32, 48, 64)
 MATCH_MAX_ACTIONS = 64
 
 
-class MatchQNetActor:
+class _ActionTable:
+    """the device action table of the 11v11 actors: float32 [K, table_width]"""
+
+    _buffers = ('params', 'table')
+
+    def _init_table(self, table):
+        self.table = torch.zeros((self.n_actions, self.table_width), dtype=torch.float32, device=self.device)
+        if table is not None:
+            self.set_table(table)
+
+    def set_table(self, table):
+        """Write the action table (float [K, 3] = command, a, b per index; obs='see': [K, 5], with the TurnNeck moment and the
+        ChangeView code) in place."""
+        t = torch.as_tensor(table, dtype=torch.float32)
+        if tuple(t.shape) != (self.n_actions, self.table_width):
+            raise ValueError(f'action table must have shape ({self.n_actions}, {self.table_width}), got {tuple(t.shape)}')
+        self.table.copy_(t.to(self.device))
+        return self
+
+
+class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
     """Packed parameters, device epsilon and action table of a 224-H1-H2-K ReLU Q-network for the 11v11 engine's network slots
     (MatchEngine.set_network, s2d_match_set_network in include/s2d_match.h).
 
@@ -433,89 +470,26 @@ class MatchQNetActor:
         if not 1 <= int(n_actions) <= MATCH_MAX_ACTIONS:
             raise ValueError(f'n_actions must be in [1, {MATCH_MAX_ACTIONS}], got {n_actions}')
         self.hidden1, self.hidden2, self.n_actions = int(hidden1), int(hidden2), int(n_actions)
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        count = match_param_count(self.hidden1, self.hidden2, self.n_actions) + (self.in_dim - MATCH_OBS_DIM) * self.hidden1
-        self.params = torch.zeros(count, dtype=torch.float32, device=self.device)
-        self.table = torch.zeros((self.n_actions, self.table_width), dtype=torch.float32, device=self.device)
-        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._eps_value = None
-        self.epsilon = epsilon
-        self._module = None
-        if table is not None:
-            self.set_table(table)
+        self._init_packed(device)
+        self._init_epsilon(epsilon)
+        self._init_table(table)
 
     @classmethod
     def from_module(cls, module, table, device=None, epsilon=0.05, obs='agent'):
         """An actor shaped like `module` (three nn.Linear layers 224 -> H1 -> H2 -> K), loaded from it, with action table
         `table` [K, 3]; obs='see': 192 -> H1 -> H2 -> K and a table [K, 5]."""
-        l1, l2, l3 = _linears(module)
+        (l1, l2, l3), _ = cls._read(module)
         dev = device if device is not None else l1.weight.device
         actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon, obs=obs)
         actor.load_from(module)
         actor.set_table(table)
         return actor
 
-    def shapes(self):
-        h1, h2, k = self.hidden1, self.hidden2, self.n_actions
-        return ((h1, self.in_dim), (h1,), (h2, h1), (h2,), (k, h2), (k,))
-
-    def load_from(self, module):
-        """Validate `module`'s shapes against this actor, remember it, and pack its parameters (sync())."""
-        got = []
-        for lin in _linears(module):
-            if lin.bias is None:
-                raise ValueError('every nn.Linear of the Q-network needs a bias')
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'Q-network shapes {got} do not match the actor {list(self.shapes())}')
-        self._module = module
-        self.sync()
-        return self
-
-    def sync(self):
-        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
-        if self._module is None:
-            raise ValueError('no module loaded (load_from)')
-        srcs = []
-        for lin in _linears(self._module):
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
-        with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
-        return self
-
-    def set_table(self, table):
-        """Write the action table (float [K, 3] = command, a, b per index; obs='see': [K, 5], with the TurnNeck moment and the
-        ChangeView code) in place."""
-        t = torch.as_tensor(table, dtype=torch.float32)
-        if tuple(t.shape) != (self.n_actions, self.table_width):
-            raise ValueError(f'action table must have shape ({self.n_actions}, {self.table_width}), got {tuple(t.shape)}')
-        self.table.copy_(t.to(self.device))
-        return self
-
-    @property
-    def epsilon(self):
-        return self._eps_value
-
-    @epsilon.setter
-    def epsilon(self, value):
-        """Written in place into the device scalar the kernel reads (stream-ordered on torch's current stream)."""
-        self._eps_value = float(value)
-        self._eps.fill_(self._eps_value)
-
-    @property
-    def epsilon_tensor(self):
-        return self._eps
-
     def snapshot(self, epsilon=0.0):
         """A frozen copy: a new actor of the same shape with its own copies of the packed parameters and the action table and
         its own epsilon -- the league member a learner plays against (MatchEngine.set_opponent_network).  It has no module:
         later sync() calls of the original do not touch it."""
-        snap = type(self)(self.hidden1, self.hidden2, self.n_actions, device=self.device, epsilon=epsilon, obs=self.obs)
-        snap.params.copy_(self.params)
-        snap.table.copy_(self.table)
-        return snap
+        return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_actions, device=self.device, epsilon=epsilon, obs=self.obs))
 
     def c_struct(self, slot_mask, vision_params=None, vision=None):
         """S2DMatchNet; obs='see': S2DMatchSeeNet, which needs the engine's vision parameters and planes."""
@@ -532,7 +506,7 @@ class MatchQNetActor:
         return net
 
 
-class MatchPolicyActor:
+class MatchPolicyActor(_ActionTable, _Deterministic, _PackedActor):
     """Packed parameters, the device deterministic word and the action table of a 224-H1-H2-K stochastic policy for the 11v11
     engine's policy slots (MatchEngine.set_network / set_opponent_network, s2d_match_set_policy_network in include/s2d_match.h):
     on-policy self-play (PPO / A2C with shared parameters) collected inside the cycle kernel.
@@ -544,6 +518,8 @@ class MatchPolicyActor:
     runs, so a captured graph acts with what they hold at replay.  The see network has no policy head: obs='see' is refused."""
 
     kind = 'policy'
+    _grid = _POLICY_GRID
+    _what = 'policy'
 
     def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None,
                  obs='agent'):
@@ -558,93 +534,28 @@ class MatchPolicyActor:
         if activation not in ('relu', 'tanh'):
             raise ValueError(f"activation must be 'relu' or 'tanh', got {activation!r}")
         self.hidden1, self.hidden2, self.n_actions, self.activation = int(hidden1), int(hidden2), int(n_actions), activation
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self.params = torch.zeros(match_param_count(self.hidden1, self.hidden2, self.n_actions), dtype=torch.float32,
-                                  device=self.device)
-        self.table = torch.zeros((self.n_actions, 3), dtype=torch.float32, device=self.device)
-        self._det = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._det_value = False
-        self.deterministic = deterministic
-        self._module = None
-        if table is not None:
-            self.set_table(table)
+        self._init_packed(device)
+        self._init_deterministic(deterministic)
+        self._init_table(table)
 
     @classmethod
     def from_module(cls, policy_net, table, device=None, deterministic=False, obs='agent'):
         """An actor shaped like `policy_net` (224 -> H1 -> H2 -> K; the module forms StochasticActor.from_module accepts, SB3's
         ``[policy.mlp_extractor.policy_net, policy.action_net]`` among them), loaded from it, with action table `table` [K, 3].
         The activation is the module's."""
-        (l1, l2, l3), act = _policy_layers(policy_net)
+        (l1, l2, l3), act = cls._read(policy_net)
         dev = device if device is not None else l1.weight.device
-        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=('relu', 'tanh')[act], device=dev,
-                    deterministic=deterministic, obs=obs)
+        actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=act, device=dev, deterministic=deterministic,
+                    obs=obs)
         actor.load_from(policy_net)
         actor.set_table(table)
         return actor
 
-    def shapes(self):
-        h1, h2, k = self.hidden1, self.hidden2, self.n_actions
-        return ((h1, MATCH_OBS_DIM), (h1,), (h2, h1), (h2,), (k, h2), (k,))
-
-    def load_from(self, policy_net):
-        """Validate `policy_net` against this actor (shapes and activation), remember it, and pack its parameters (sync())."""
-        layers, act = _policy_layers(policy_net)
-        if ('relu', 'tanh')[act] != self.activation:
-            raise ValueError(f'the policy\'s activation is {("relu", "tanh")[act]}, the actor\'s {self.activation}')
-        got = []
-        for lin in layers:
-            if lin.bias is None:
-                raise ValueError('every nn.Linear of the policy needs a bias')
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'policy shapes {got} do not match the actor {list(self.shapes())}')
-        self._module = policy_net
-        self.sync()
-        return self
-
-    def sync(self):
-        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
-        if self._module is None:
-            raise ValueError('no module loaded (load_from)')
-        srcs = []
-        for lin in _policy_layers(self._module)[0]:
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
-        with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
-        return self
-
-    def set_table(self, table):
-        """Write the action table (float [K, 3] = command, a, b per index) in place."""
-        t = torch.as_tensor(table, dtype=torch.float32)
-        if tuple(t.shape) != (self.n_actions, 3):
-            raise ValueError(f'action table must have shape ({self.n_actions}, 3), got {tuple(t.shape)}')
-        self.table.copy_(t.to(self.device))
-        return self
-
-    @property
-    def deterministic(self):
-        return self._det_value
-
-    @deterministic.setter
-    def deterministic(self, value):
-        """Written in place into the device word the kernel reads (stream-ordered on torch's current stream)."""
-        self._det_value = bool(value)
-        self._det.fill_(int(self._det_value))
-
-    @property
-    def deterministic_tensor(self):
-        return self._det
-
     def snapshot(self, deterministic=None):
         """A frozen copy: a new actor of the same shape with its own parameters, table and deterministic word -- the league
         member a learner plays against, or an evaluation copy.  It has no module: later sync() calls do not touch it."""
-        snap = type(self)(self.hidden1, self.hidden2, self.n_actions, activation=self.activation, device=self.device,
-                          deterministic=self._det_value if deterministic is None else deterministic)
-        snap.params.copy_(self.params)
-        snap.table.copy_(self.table)
-        return snap
+        return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_actions, activation=self.activation, device=self.device,
+                                       deterministic=self._det_value if deterministic is None else deterministic))
 
     def c_struct(self, slot_mask):
         """S2DMatchPolicyNet for s2d_match_set_policy_network"""

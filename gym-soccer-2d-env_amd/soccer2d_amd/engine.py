@@ -248,17 +248,18 @@ class Engine:
                 self._ro_cache[(entry, id(out))] = cached
         return out, cached[2], cached[4]
 
-    @staticmethod
-    def _is_mlp(actor):
-        """does `actor` carry the general MLP (soccer2d_amd.mlp_actor), which goes to the _mlp entry points"""
-        from .mlp_actor import MlpDeterministicActor, MlpQNetActor
-        return isinstance(actor, (MlpQNetActor, MlpDeterministicActor))
-
-    @staticmethod
-    def _is_wide(actor):
-        """does `actor` carry the streamed-weight MLP (soccer2d_amd.wide_actor), which goes to the _wide entry points"""
-        from .wide_actor import WideDeterministicActor, WideQNetActor
-        return isinstance(actor, (WideQNetActor, WideDeterministicActor))
+    def _actor_call(self, name, n_steps, actor, entries=None):
+        """what rollout_qnet / rollout_actor / rollout_policy open with: (T, the actor's C struct); entries: the family of C entry
+        points the method launches, which the actor's own (`_entry`) must belong to"""
+        if entries is not None and not str(getattr(actor, '_entry', None)).startswith(entries):
+            raise ValueError(f'{name} takes an actor of the {entries}* entry points, got a {type(actor).__name__}')
+        T = int(n_steps)
+        if T < 1:
+            raise ValueError(f'{name} needs n_steps >= 1')
+        net = actor.c_struct()
+        if actor.device != self.device:
+            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        return T, net
 
     def rollout_qnet(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False):
         """n_steps fused cycles in one launch whose actions are `actor`'s (soccer2d_amd.actor.QNetActor, or a
@@ -268,15 +269,9 @@ class Engine:
         rollout() (action int32 [T,N]); with terminal_obs=True (or a caller `out` holding 'terminal_obs') also float32 [T,N,10],
         written only where done.  The actor's buffers are read when the kernel runs: a captured graph acts with the weights and
         epsilon they hold at replay.  `out` pointer blocks are cached as in rollout()."""
-        T = int(n_steps)
-        if T < 1:
-            raise ValueError('rollout_qnet needs n_steps >= 1')
-        net = actor.c_struct()
-        if actor.device != self.device:
-            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        T, net = self._actor_call('rollout_qnet', n_steps, actor, 's2d_rollout_qnet')
         out, ro, term = self._actor_record('rollout_qnet', self._QNET_RECORD, T, out, with_obs, terminal_obs)
-        entry = ('s2d_rollout_qnet_wide' if self._is_wide(actor) else
-                 's2d_rollout_qnet_mlp' if self._is_mlp(actor) else 's2d_rollout_qnet')
+        entry = actor._entry            # the C entry point of the actor's network back end
         rc = getattr(self.lib, entry)(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
         _capi.check(self.lib, rc, entry)
         self._keep = (actor, out)
@@ -289,12 +284,7 @@ class Engine:
         the envs' own observations, with epsilon-random exploration and optional Gaussian action noise, evaluated in-kernel
         (s2d_rollout_actor; continuous and turning engines).  Returns the record dict of rollout() (action float32 [T,N,1] or
         [T,N,4]: the noisy, clipped action); terminal_obs, graph capture and `out` caching as in rollout_qnet()."""
-        T = int(n_steps)
-        if T < 1:
-            raise ValueError('rollout_actor needs n_steps >= 1')
-        net = actor.c_struct()
-        if actor.device != self.device:
-            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        T, net = self._actor_call('rollout_actor', n_steps, actor, 's2d_rollout_actor')
         t = self.cfg.task
         if not t.use_continuous_action:
             raise ValueError('rollout_actor needs a continuous-action engine (use_continuous_action=True); use rollout_qnet')
@@ -303,8 +293,7 @@ class Engine:
             raise ValueError(f'a {"turning" if t.use_turning else "continuous"} engine needs an actor with n_out = {a}, got {actor.n_out}')
         record = dict(self._QNET_RECORD, action=(torch.float32, (a,)))
         out, ro, term = self._actor_record('rollout_actor', record, T, out, with_obs, terminal_obs)
-        entry = ('s2d_rollout_actor_wide' if self._is_wide(actor) else
-                 's2d_rollout_actor_mlp' if self._is_mlp(actor) else 's2d_rollout_actor')
+        entry = actor._entry
         rc = getattr(self.lib, entry)(self._h, T, C.byref(net), C.byref(ro), term, self._stream())
         _capi.check(self.lib, rc, entry)
         self._keep = (actor, out)
@@ -318,12 +307,7 @@ class Engine:
         float32 [T,N], the log-probability of the recorded action (logp=True, or a caller `out` holding 'logp').
         actor.deterministic = True acts greedily in the same launch.  terminal_obs, graph capture and `out` caching as in
         rollout_qnet()."""
-        T = int(n_steps)
-        if T < 1:
-            raise ValueError('rollout_policy needs n_steps >= 1')
-        net = actor.c_struct()
-        if actor.device != self.device:
-            raise ValueError(f'actor lives on {actor.device}, engine on {self.device}')
+        T, net = self._actor_call('rollout_policy', n_steps, actor)
         t = self.cfg.task
         a = int(t.action_space_size) if not t.use_continuous_action else 4 if t.use_turning else 1
         if actor.n_out != a:

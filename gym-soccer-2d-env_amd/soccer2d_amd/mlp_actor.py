@@ -9,10 +9,8 @@ They are QNetActor / DeterministicActor (soccer2d_amd.actor) with another shape:
 rows, all written in place and read when the kernel runs.  The two-layer classes stay what they are; for a 10-H1-H2-A ReLU
 network with widths that are multiples of 16 both paths give the same bits.
 """
-import torch
-
 from . import _capi
-from .actor import _NO_OPS, ACTOR_OUTPUTS, MAX_ACTIONS, OBS_DIM, DeterministicActor, QNetActor
+from .actor import ACTOR_OUTPUTS, MAX_ACTIONS, OBS_DIM, DeterministicActor, QNetActor, _PackedActor
 
 MAX_HIDDEN = 4
 MLP_WIDTHS = tuple(range(8, 129, 8))
@@ -26,11 +24,10 @@ _OBS_TILE = _WAVE * OBS_DIM
 _PREP_TILE = (13 + OBS_DIM + 2) * _WAVE
 
 
-def lds_plan(hidden, n_out):
-    """(waves per workgroup, LDS bytes) of a 10-hidden...-n_out network, by the arithmetic of the C plan: the fragments of every
-    layer (ceil(h / 16) tiles of 16 rows x its k-steps, 3 for layer 1, h_(l-1) / 4 after it), the biases padded to their tiles,
-    and per wave two hidden images, the output image, the observation tile and the prepared-episode tile; as many waves of
-    4 / 2 / 1 as 160 KiB hold.  waves = None: not even one wave fits (bytes = what one wave would need)."""
+def _fragments(hidden, n_out):
+    """(fragments, bias words, widest padded layer, n_out rounded up to 16) of a 10-hidden...-n_out network, as both C plans count
+    them: ceil(h / 16) tiles of 16 rows x the layer's k-steps (3 for layer 1, h_(l-1) / 4 after it), the biases padded to their
+    tiles"""
     na16 = (n_out + 15) // 16 * 16
     nfrag = nbias = wmax = 0
     ksteps = 3
@@ -40,8 +37,15 @@ def lds_plan(hidden, n_out):
         nbias += 16 * m16
         wmax = max(wmax, 16 * m16)
         ksteps = w // 4
-    nfrag += (na16 // 16) * ksteps
-    nbias += na16
+    return nfrag + (na16 // 16) * ksteps, nbias + na16, wmax, na16
+
+
+def lds_plan(hidden, n_out):
+    """(waves per workgroup, LDS bytes) of a 10-hidden...-n_out network, by the arithmetic of the C plan: the fragments of every
+    layer (ceil(h / 16) tiles of 16 rows x its k-steps, 3 for layer 1, h_(l-1) / 4 after it), the biases padded to their tiles,
+    and per wave two hidden images, the output image, the observation tile and the prepared-episode tile; as many waves of
+    4 / 2 / 1 as 160 KiB hold.  waves = None: not even one wave fits (bytes = what one wave would need)."""
+    nfrag, nbias, wmax, na16 = _fragments(hidden, n_out)
     pitch = (wmax + 63) // 64 * 64 + 4
     shared = (nfrag * _WAVE + nbias + 3) & ~3
     wave_words = 2 * 16 * pitch + _WAVE * (na16 + 4) + _OBS_TILE + _PREP_TILE
@@ -77,111 +81,48 @@ def param_count(hidden, n_out):
     return n
 
 
-def _mlp_layers(module, tanh_head=False):
-    """(the nn.Linear layers in order, activation name) of a Linear-(F-Linear) x L module, F = ReLU or Tanh, the same throughout;
-    with tanh_head=True the module must end in one more Tanh (the deterministic actor's head).  Leaf modules are read in
-    registration order; Identity / Flatten are skipped; anything else is refused: the kernel would silently act with a
-    different function."""
-    leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
-    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else 'ReLU' if isinstance(m, torch.nn.ReLU)
-             else 'Tanh' if isinstance(m, torch.nn.Tanh) else type(m).__name__ for m in leaves]
-    what = 'actor' if tanh_head else 'Q-network'
-    form = 'Linear-(F-Linear) x L' + ('-Tanh' if tanh_head else '') + f', L = 1 .. {MAX_HIDDEN} hidden layers, F = ReLU or Tanh'
-    got = '-'.join(kinds) or 'nothing'
-    body = kinds
-    if tanh_head:
-        if not kinds or kinds[-1] != 'Tanh':
-            raise ValueError(f'the actor must end in a Tanh ({form}), got {got}')
-        body = kinds[:-1]
-    if len(body) % 2 == 0 or any(k != 'Linear' for k in body[0::2]):
-        raise ValueError(f'the {what} must be {form}, got {got}')
-    acts = set(body[1::2])
-    n_hidden = len(body) // 2
-    if not 1 <= n_hidden <= MAX_HIDDEN:
-        raise ValueError(f'the {what} must have 1 to {MAX_HIDDEN} hidden layers ({form}), got {n_hidden}: {got}')
-    if len(acts) > 1 and acts <= {'ReLU', 'Tanh'}:
-        raise ValueError(f'the {what} must use one activation throughout, ReLU or Tanh, not a mix ({form}), got {got}')
-    if not acts <= {'ReLU', 'Tanh'}:
-        raise ValueError(f'the hidden activation must be ReLU or Tanh ({form}), got {got}')
-    linears = leaves[0:len(body):2]
-    for lin in linears:
-        if lin.bias is None:
-            raise ValueError(f'every nn.Linear of the {what} needs a bias')
-    return linears, acts.pop().lower()
+class _MlpShape(_PackedActor):
+    """What the two MLP actors share beyond their two-layer base classes: the shape, the packed buffer's layout, how a module
+    is read and the C struct.  wide_actor has another grid (`_grid`, `_check_shape`, `_activations`, `_struct`)."""
 
-
-class _MlpShape:
-    """What the two MLP actors share beyond their two-layer base classes: the shape, the packed buffer's layout, loading from
-    a module and the C struct."""
-
-    _tanh_head = False
-    _what = 'Q-network'
-    _layers = staticmethod(_mlp_layers)     # how a module is read: the grid of layers and activations (wide_actor has another)
+    _grid = dict(acts=('ReLU', 'Tanh'), hidden=(1, MAX_HIDDEN))
+    _shape_error = _PackedActor._shape_error
+    _check_shape = staticmethod(_check_shape)
+    _activations = ACTIVATIONS
+    _struct = _capi.S2DMlpNet
 
     def _init_shape(self, hidden, n_out, activation, device):
-        self.hidden = _check_shape(hidden, n_out, activation)
+        self.hidden = self._check_shape(hidden, n_out, activation)
         self.activation = activation
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        # torch's device allocations are 256-byte aligned (the ABI asks for 16)
-        self.params = torch.zeros(param_count(self.hidden, n_out), dtype=torch.float32, device=self.device)
-        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._eps_value = None
-        self._module = None
+        self._init_packed(device)
 
-    @property
-    def _outputs(self):
-        return self.n_out if self._tanh_head else self.n_actions
+    @classmethod
+    def _from(cls, module, device, **kw):
+        """an actor shaped like `module`, loaded from it (from_module)"""
+        linears, act = cls._read(module)
+        dev = device if device is not None else linears[0].weight.device
+        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev, **kw)
+        return actor.load_from(module)
+
+    def _widths(self):
+        return self.hidden + (self._outputs,)
 
     @property
     def waves(self):
         """waves per workgroup of the kernel's LDS plan for this shape"""
         return lds_plan(self.hidden, self._outputs)[0]
 
-    def shapes(self):
-        out, win = [], OBS_DIM
-        for w in self.hidden + (self._outputs,):
-            out += [(w, win), (w,)]
-            win = w
-        return tuple(out)
-
-    def load_from(self, module):
-        """Validate `module`'s shapes and activation against this actor, remember it, and pack its parameters (sync())."""
-        linears, act = self._layers(module, self._tanh_head)
-        if act != self.activation:
-            raise ValueError(f'the {self._what}\'s activation is {act}, the actor\'s {self.activation}')
-        got = []
-        for lin in linears:
-            got += [tuple(lin.weight.shape), tuple(lin.bias.shape)]
-        if tuple(got) != self.shapes():
-            raise ValueError(f'{self._what} shapes {got} do not match the actor {list(self.shapes())}')
-        self._module = module
-        self.sync()
-        return self
-
-    def sync(self):
-        """Copy the loaded module's current parameters into the packed buffer: one device copy, no allocation (capturable)."""
-        if self._module is None:
-            raise ValueError('no module loaded (load_from)')
-        srcs = []
-        for lin in self._layers(self._module, self._tanh_head)[0]:
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
-        with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
-        return self
-
     def c_struct(self):
-        net = _capi.S2DMlpNet()
+        net = self._struct()
         net.n_hidden = len(self.hidden)
-        for l in range(MAX_HIDDEN):
+        for l in range(len(net.hidden)):
             net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
         net.n_out = self._outputs
-        net.activation = ACTIVATIONS.index(self.activation)
-        net.noise_kind = self.noise_kind if self._tanh_head else 0
+        net.activation = self._activations.index(self.activation)
+        net.noise_kind = self.noise_kind if self._has_noise else 0
         net.params = self.params.data_ptr()
         net.epsilon = self._eps.data_ptr()
-        net.noise = self._noise.data_ptr() if self._tanh_head else None
+        net.noise = self._noise.data_ptr() if self._has_noise else None
         return net
 
 
@@ -189,31 +130,28 @@ class MlpQNetActor(_MlpShape, QNetActor):
     """Packed parameters + device epsilon of a 10-h_1-...-h_L-A Q-network (L = 1 .. 4, ReLU or Tanh) for Engine.rollout_qnet.
     epsilon / epsilon_tensor are QNetActor's."""
 
+    _entry = 's2d_rollout_qnet_mlp'
+
     def __init__(self, hidden=(64, 64), n_actions=16, activation='relu', device='cuda:0', epsilon=0.05):
         if not 1 <= int(n_actions) <= MAX_ACTIONS:
             raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
         self.n_actions = int(n_actions)
         self._init_shape(hidden, self.n_actions, activation, device)
-        self.epsilon = epsilon
+        self._init_epsilon(epsilon)
 
     @classmethod
     def from_module(cls, module, device=None, epsilon=0.05):
         """An actor shaped like `module` (Linear-(F-Linear) x L, F = ReLU or Tanh throughout, optionally behind a Flatten or
         Identity: SB3's ``model.q_net.q_net``), loaded from it."""
-        linears, act = _mlp_layers(module)
-        dev = device if device is not None else linears[0].weight.device
-        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
-                    epsilon=epsilon)
-        actor.load_from(module)
-        return actor
+        return cls._from(module, device, epsilon=epsilon)
 
 
 class MlpDeterministicActor(_MlpShape, DeterministicActor):
     """Packed parameters, device epsilon and Gaussian action noise of a 10-h_1-...-h_L-A tanh actor (L = 1 .. 4, ReLU or Tanh
     between the layers) for Engine.rollout_actor.  epsilon and the noise properties are DeterministicActor's."""
 
-    _tanh_head = True
-    _what = 'actor'
+    _grid = dict(_MlpShape._grid, tanh_head=True)
+    _entry = 's2d_rollout_actor_mlp'
 
     def __init__(self, hidden=(64, 64), n_out=1, activation='relu', device='cuda:0', epsilon=0.0, noise_mean=None,
                  noise_sigma=None):
@@ -221,19 +159,11 @@ class MlpDeterministicActor(_MlpShape, DeterministicActor):
             raise ValueError(f'n_out must be 1 (continuous engine) or 4 (turning engine), got {n_out}')
         self.n_out = int(n_out)
         self._init_shape(hidden, self.n_out, activation, device)
-        self._noise = torch.zeros(2, self.n_out, dtype=torch.float32, device=self.device)   # [mu; sigma]
-        self._sigma = None
-        self.epsilon = epsilon
-        self.noise_mean = 0.0 if noise_mean is None else noise_mean
-        self.noise_sigma = noise_sigma
+        self._init_epsilon(epsilon)
+        self._init_noise(noise_mean, noise_sigma)
 
     @classmethod
     def from_module(cls, module, device=None, epsilon=0.0, noise_mean=None, noise_sigma=None):
         """An actor shaped like `module` (SB3's ``model.actor.mu``: Linear-(F-Linear) x L-Tanh, F = ReLU or Tanh throughout,
         optionally behind a Flatten or Identity), loaded from it."""
-        linears, act = _mlp_layers(module, tanh_head=True)
-        dev = device if device is not None else linears[0].weight.device
-        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
-                    epsilon=epsilon, noise_mean=noise_mean, noise_sigma=noise_sigma)
-        actor.load_from(module)
-        return actor
+        return cls._from(module, device, epsilon=epsilon, noise_mean=noise_mean, noise_sigma=noise_sigma)

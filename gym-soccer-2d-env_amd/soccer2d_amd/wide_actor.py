@@ -12,13 +12,12 @@ every shape the Mlp classes take both paths give the same bits.
 import torch
 
 from . import _capi
-from .actor import _NO_OPS, ACTOR_OUTPUTS, MAX_ACTIONS, OBS_DIM, DeterministicActor, QNetActor
-from .mlp_actor import _MlpShape, param_count
+from .actor import ACTOR_OUTPUTS, MAX_ACTIONS, OBS_DIM, DeterministicActor, QNetActor
+from .mlp_actor import _fragments, _MlpShape, param_count  # noqa: F401  (param_count: part of this module's interface)
 
 MAX_HIDDEN = 5
 WIDE_WIDTHS = tuple(range(8, 401, 4))
 ACTIVATIONS = ('relu', 'tanh', 'sigmoid')
-_KINDS = {torch.nn.ReLU: 'ReLU', torch.nn.Tanh: 'Tanh', torch.nn.Sigmoid: 'Sigmoid'}
 
 # the plan of csrc/s2d_wide_net.h (wide_plan_lds), in 4-byte words
 LDS_BYTES = 160 * 1024
@@ -33,17 +32,7 @@ def wide_plan(hidden, n_out):
     it, 64 words each) and the biases padded to their tiles.  The LDS holds the biases and per wave two images of `tiles` x 16 rows
     (pitch: the widest padded layer rounded up to 64, + 4), the output image, the observation tile and the prepared-episode tile.
     More waves go before more tiles: the first of (4, 4), (4, 2), (4, 1), (2, 4), ..., (1, 1) that 160 KiB hold."""
-    na16 = (n_out + 15) // 16 * 16
-    nfrag = nbias = wmax = 0
-    ksteps = 3
-    for w in hidden:
-        m16 = (w + 15) // 16
-        nfrag += m16 * ksteps
-        nbias += 16 * m16
-        wmax = max(wmax, 16 * m16)
-        ksteps = w // 4
-    nfrag += (na16 // 16) * ksteps
-    nbias += na16
+    nfrag, nbias, wmax, na16 = _fragments(hidden, n_out)
     rpitch = (wmax + 63) // 64 * 64 + 4
     shared = (nbias + 3) & ~3
     for waves in (4, 2, 1):
@@ -67,58 +56,18 @@ def _check_shape(hidden, n_out, activation):
     return hidden
 
 
-def _wide_layers(module, tanh_head=False):
-    """(the nn.Linear layers in order, activation name) of a Linear-(F-Linear) x L module, F = ReLU, Tanh or Sigmoid, the same
-    throughout; with tanh_head=True the module must end in one more Tanh (the deterministic actor's head).  Leaf modules are read
-    in registration order; Identity / Flatten are skipped; anything else is refused: the kernel would silently act with a
-    different function."""
-    leaves = [m for m in module.modules() if not any(True for _ in m.children()) and not isinstance(m, _NO_OPS)]
-    kinds = ['Linear' if isinstance(m, torch.nn.Linear) else _KINDS.get(type(m), type(m).__name__) for m in leaves]
-    what = 'actor' if tanh_head else 'Q-network'
-    form = ('Linear-(F-Linear) x L' + ('-Tanh' if tanh_head else '') +
-            f', L = 1 .. {MAX_HIDDEN} hidden layers, F = ReLU, Tanh or Sigmoid')
-    got = '-'.join(kinds) or 'nothing'
-    body = kinds
-    if tanh_head:
-        if not kinds or kinds[-1] != 'Tanh':
-            raise ValueError(f'the actor must end in a Tanh ({form}), got {got}')
-        body = kinds[:-1]
-    if len(body) % 2 == 0 or any(k != 'Linear' for k in body[0::2]):
-        raise ValueError(f'the {what} must be {form}, got {got}')
-    acts = set(body[1::2])
-    n_hidden = len(body) // 2
-    if not 1 <= n_hidden <= MAX_HIDDEN:
-        raise ValueError(f'the {what} must have 1 to {MAX_HIDDEN} hidden layers ({form}), got {n_hidden}: {got}')
-    allowed = set(_KINDS.values())
-    if len(acts) > 1 and acts <= allowed:
-        raise ValueError(f'the {what} must use one activation throughout, ReLU, Tanh or Sigmoid, not a mix ({form}), got {got}')
-    if not acts <= allowed:
-        raise ValueError(f'the hidden activation must be ReLU, Tanh or Sigmoid ({form}), got {got}')
-    linears = leaves[0:len(body):2]
-    for lin in linears:
-        if lin.bias is None:
-            raise ValueError(f'every nn.Linear of the {what} needs a bias')
-    return linears, acts.pop().lower()
-
-
 class _WideShape(_MlpShape):
     """_MlpShape on the wide grid, and the workspace the pack kernel writes"""
 
-    _layers = staticmethod(_wide_layers)
+    _grid = dict(acts=('ReLU', 'Tanh', 'Sigmoid'), hidden=(1, MAX_HIDDEN))
+    _check_shape = staticmethod(_check_shape)
+    _activations = ACTIVATIONS
+    _struct = _capi.S2DWideNet
 
     def _init_shape(self, hidden, n_out, activation, device):
-        hidden = _check_shape(hidden, n_out, activation)
-        self.activation = activation
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self.hidden = hidden
-        # torch's device allocations are 256-byte aligned (the ABI asks for 16, and for 256 of the workspace)
-        self.params = torch.zeros(param_count(hidden, n_out), dtype=torch.float32, device=self.device)
-        self.workspace = torch.zeros(wide_plan(hidden, n_out)[3] // 4, dtype=torch.float32, device=self.device)
-        self._eps = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._eps_value = None
-        self._module = None
+        super()._init_shape(hidden, n_out, activation, device)
+        # torch's device allocations are 256-byte aligned (the ABI asks for 256 of the workspace)
+        self.workspace = torch.zeros(self.plan[3] // 4, dtype=torch.float32, device=self.device)
 
     @property
     def plan(self):
@@ -130,16 +79,7 @@ class _WideShape(_MlpShape):
         return self.plan[0]
 
     def c_struct(self):
-        net = _capi.S2DWideNet()
-        net.n_hidden = len(self.hidden)
-        for l in range(MAX_HIDDEN):
-            net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
-        net.n_out = self._outputs
-        net.activation = ACTIVATIONS.index(self.activation)
-        net.noise_kind = self.noise_kind if self._tanh_head else 0
-        net.params = self.params.data_ptr()
-        net.epsilon = self._eps.data_ptr()
-        net.noise = self._noise.data_ptr() if self._tanh_head else None
+        net = super().c_struct()
         net.workspace = self.workspace.data_ptr()
         net.workspace_bytes = self.workspace.numel() * 4
         return net
@@ -149,31 +89,28 @@ class WideQNetActor(_WideShape, QNetActor):
     """Packed parameters, device epsilon and workspace of a 10-h_1-...-h_L-A Q-network (L = 1 .. 5, widths up to 400, ReLU, Tanh or
     Sigmoid) for Engine.rollout_qnet.  epsilon / epsilon_tensor are QNetActor's."""
 
+    _entry = 's2d_rollout_qnet_wide'
+
     def __init__(self, hidden=(256, 256), n_actions=16, activation='relu', device='cuda:0', epsilon=0.05):
         if not 1 <= int(n_actions) <= MAX_ACTIONS:
             raise ValueError(f'n_actions must be in [1, {MAX_ACTIONS}], got {n_actions}')
         self.n_actions = int(n_actions)
         self._init_shape(hidden, self.n_actions, activation, device)
-        self.epsilon = epsilon
+        self._init_epsilon(epsilon)
 
     @classmethod
     def from_module(cls, module, device=None, epsilon=0.05):
         """An actor shaped like `module` (Linear-(F-Linear) x L, F = ReLU, Tanh or Sigmoid throughout, optionally behind a
         Flatten or Identity: SB3's ``model.q_net.q_net``), loaded from it."""
-        linears, act = _wide_layers(module)
-        dev = device if device is not None else linears[0].weight.device
-        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
-                    epsilon=epsilon)
-        actor.load_from(module)
-        return actor
+        return cls._from(module, device, epsilon=epsilon)
 
 
 class WideDeterministicActor(_WideShape, DeterministicActor):
     """Packed parameters, device epsilon, Gaussian action noise and workspace of a 10-h_1-...-h_L-A tanh actor (L = 1 .. 5, widths
     up to 400: SB3's default [400, 300]) for Engine.rollout_actor.  epsilon and the noise properties are DeterministicActor's."""
 
-    _tanh_head = True
-    _what = 'actor'
+    _grid = dict(_WideShape._grid, tanh_head=True)
+    _entry = 's2d_rollout_actor_wide'
 
     def __init__(self, hidden=(400, 300), n_out=1, activation='relu', device='cuda:0', epsilon=0.0, noise_mean=None,
                  noise_sigma=None):
@@ -181,19 +118,11 @@ class WideDeterministicActor(_WideShape, DeterministicActor):
             raise ValueError(f'n_out must be 1 (continuous engine) or 4 (turning engine), got {n_out}')
         self.n_out = int(n_out)
         self._init_shape(hidden, self.n_out, activation, device)
-        self._noise = torch.zeros(2, self.n_out, dtype=torch.float32, device=self.device)   # [mu; sigma]
-        self._sigma = None
-        self.epsilon = epsilon
-        self.noise_mean = 0.0 if noise_mean is None else noise_mean
-        self.noise_sigma = noise_sigma
+        self._init_epsilon(epsilon)
+        self._init_noise(noise_mean, noise_sigma)
 
     @classmethod
     def from_module(cls, module, device=None, epsilon=0.0, noise_mean=None, noise_sigma=None):
         """An actor shaped like `module` (SB3's ``model.actor.mu``: Linear-(F-Linear) x L-Tanh, F = ReLU, Tanh or Sigmoid
         throughout, optionally behind a Flatten or Identity), loaded from it."""
-        linears, act = _wide_layers(module, tanh_head=True)
-        dev = device if device is not None else linears[0].weight.device
-        actor = cls([lin.out_features for lin in linears[:-1]], linears[-1].out_features, activation=act, device=dev,
-                    epsilon=epsilon, noise_mean=noise_mean, noise_sigma=noise_sigma)
-        actor.load_from(module)
-        return actor
+        return cls._from(module, device, epsilon=epsilon, noise_mean=noise_mean, noise_sigma=noise_sigma)

@@ -195,3 +195,70 @@ def test_struct_and_export_abi():
     if os.path.exists(lib):
         syms = subprocess.run(['nm', '-D', '--defined-only', lib], stdout=subprocess.PIPE, text=True).stdout
         assert re.search(r'\bs2d_rollout_actor\b', syms)
+
+
+# ------------------------------------------------------------------------------- the contract every packed-parameter actor keeps
+def _layers(widths, act=torch.nn.ReLU, tanh=False, bias=True):
+    mods = []
+    for win, w in zip(widths[:-2], widths[1:-1]):
+        mods += [torch.nn.Linear(win, w, bias=bias), act()]
+    mods.append(torch.nn.Linear(widths[-2], widths[-1], bias=bias))
+    return torch.nn.Sequential(*mods, *([torch.nn.Tanh()] if tanh else []))
+
+
+_TABLE3 = [[0.0, 0.0, 0.0]] * 3
+# class: (module widths, Tanh head, arguments of from_module after the module, does the class's own host test refuse a bias-less Linear)
+ACTOR_CLASSES = {
+    'actor.QNetActor': ((10, 16, 32, 5), False, {}, False),
+    'actor.DeterministicActor': ((10, 16, 32, 4), True, {}, False),
+    'actor.StochasticActor': ((10, 16, 32, 5), False, {}, False),
+    'actor.MatchQNetActor': ((224, 16, 32, 3), False, dict(table=_TABLE3), False),
+    'actor.MatchPolicyActor': ((224, 16, 32, 3), False, dict(table=_TABLE3), True),
+    'mlp_actor.MlpQNetActor': ((10, 24, 8, 40, 5), False, {}, True),
+    'mlp_actor.MlpDeterministicActor': ((10, 8, 1), True, {}, False),
+    'wide_actor.WideQNetActor': ((10, 300, 28, 5), False, {}, True),
+    'wide_actor.WideDeterministicActor': ((10, 12, 20, 400, 4), True, {}, False),
+}
+
+
+@pytest.mark.parametrize('name', list(ACTOR_CLASSES))
+def test_common_contract_of_the_packed_actors(name):
+    """What the nine actor classes share through their base (soccer2d_amd.actor), on device='cpu', where the class's own host
+    test does not already check it: sync() without a module raises; a bias-less nn.Linear is refused (MatchPolicyActor,
+    MlpQNetActor and WideQNetActor have that in test_match_policy_host.py, test_mlp_actor_host.py and test_wide_actor_host.py;
+    the other six, the Tanh-head readers among them, here); sync() after an in-place
+    change of the module changes `params` to the module's parameters and keeps the buffer the kernel reads (data_ptr()).
+    That from_module packs torch.cat of the parameters, and that snapshot() does not follow later sync() calls, is checked
+    for every class that has them in test_{qnet,mlp,wide}_actor_host.py, test_policy_host.py, test_match_{net,policy,two_nets}
+    _host.py and test_deterministic_actor_packing above."""
+    import importlib
+    mod, cls_name = name.split('.')
+    cls = getattr(importlib.import_module('soccer2d_amd.' + mod), cls_name)
+    widths, tanh, kw, bias_checked = ACTOR_CLASSES[name]
+    torch.manual_seed(len(name))
+    net = _layers(widths, tanh=tanh)
+    a = cls.from_module(net, device='cpu', **kw)
+    assert a.device == torch.device('cpu') and a._module is net
+    assert a.params.numel() == sum(p.numel() for p in net.parameters()) == sum(int(np.prod(s)) for s in a.shapes())
+    # a fresh actor of the same shape has no module
+    ctor = dict(device='cpu', **({} if getattr(a, 'activation', None) is None else dict(activation=a.activation)))
+    if hasattr(a, 'hidden'):
+        fresh = cls(a.hidden, widths[-1], **ctor)
+    else:
+        fresh = cls(a.hidden1, a.hidden2, widths[-1], **ctor)
+    with pytest.raises(ValueError, match='no module loaded'):
+        fresh.sync()
+    if not bias_checked:
+        with pytest.raises(ValueError, match='needs a bias'):
+            cls.from_module(_layers(widths, tanh=tanh, bias=False), device='cpu', **kw)
+        with pytest.raises(ValueError, match='needs a bias'):
+            fresh.load_from(_layers(widths, tanh=tanh, bias=False))
+    ptr, before = a.params.data_ptr(), a.params.clone()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.mul_(-0.5).add_(0.25)
+    assert torch.equal(a.params, before)                       # nothing moves before sync()
+    assert a.sync() is a
+    assert not torch.equal(a.params, before)
+    assert torch.equal(a.params, torch.cat([p.detach().reshape(-1) for p in net.parameters()]))
+    assert a.params.data_ptr() == ptr

@@ -13,6 +13,7 @@ import pytest
 
 import oracle as O
 import actor_ref as R
+from actor_refusals import refused
 from test_actor_host import chi2_phi
 
 pytestmark = pytest.mark.gpu
@@ -382,13 +383,13 @@ def test_rejections_leave_the_state_unchanged():
                              (64, 64, 1, 2), (64, 64, 1, -1)):
         net = actor.c_struct()
         net.hidden1, net.hidden2, net.n_out, net.noise_kind = h1, h2, na, kind
-        assert rc(net) == _capi.S2D_EINVAL, (h1, h2, na, kind)
+        refused(eng.lib, f's2d_rollout_actor/struct/{h1}-{h2}-{na} noise_kind {kind}', rc(net))
     for field, val in (('params', actor.params.data_ptr() + 4), ('params', None), ('epsilon', None),
                        ('epsilon', actor.epsilon_tensor.data_ptr() + 2), ('noise', None)):
         net = actor.c_struct()
         setattr(net, field, val)
-        assert rc(net) == _capi.S2D_EINVAL, field
-    assert rc(actor.c_struct(), T=0) == _capi.S2D_EINVAL
+        refused(eng.lib, f's2d_rollout_actor/struct/{field} {"NULL" if val is None else "misaligned"}', rc(net))
+    refused(eng.lib, 's2d_rollout_actor/struct/n_steps 0', rc(actor.c_struct(), T=0))
     with pytest.raises(ValueError):
         eng.rollout_actor(4, DeterministicActor(64, 64, 4))
     torch.cuda.synchronize()
@@ -405,7 +406,8 @@ def test_rejections_leave_the_state_unchanged():
     d = Engine(256, 'cuda:0', cfg=make_config(noise=False, **O.DQN_KWARGS))
     d.reset()
     dbefore = d.arena.clone()
-    assert d.lib.s2d_rollout_actor(d._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, d._stream()) == _capi.S2D_EINVAL
+    refused(d.lib, 's2d_rollout_actor/struct/discrete engine',
+            d.lib.s2d_rollout_actor(d._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, d._stream()))
     with pytest.raises(ValueError):
         d.rollout_actor(4, actor)
     q = torch.nn.Sequential(torch.nn.Linear(10, 64), torch.nn.ReLU(), torch.nn.Linear(64, 64), torch.nn.ReLU(),

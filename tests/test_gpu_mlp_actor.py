@@ -13,6 +13,7 @@ import actor_ref as R
 import mlp_ref as M
 import oracle as O
 import qnet_ref as Q
+from actor_refusals import refused
 
 pytestmark = pytest.mark.gpu
 
@@ -542,21 +543,21 @@ def test_rejections_leave_the_state_unchanged():
         for what, edit in cases:
             s = actor.c_struct()
             edit(s)
-            assert fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL, (mode, what)
+            refused(eng.lib, f'{entry}/struct/{mode}/{what}', fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()))
         s = actor.c_struct()
-        assert fn(eng._h, 0, C.byref(s), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL          # n_steps < 1
-        assert fn(eng._h, 4, None, C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+        refused(eng.lib, f'{entry}/struct/{mode}/n_steps 0', fn(eng._h, 0, C.byref(s), C.byref(ro), None, eng._stream()))
+        refused(eng.lib, f'{entry}/struct/{mode}/net NULL', fn(eng._h, 4, None, C.byref(ro), None, eng._stream()))
         # a shape that does not fit: the text says how many bytes it needs
         s = actor.c_struct()
         s.n_hidden = 3
         for l in range(3):
             s.hidden[l] = 128
-        assert fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
-        msg = eng.lib.s2d_last_error().decode()
+        msg = refused(eng.lib, f'{entry}/struct/{mode}/10-128-128-128', fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()))
         assert re.search(r'10-128-128-128-\d+ needs 1\d{5} bytes of LDS', msg), msg
         # the wrong engine mode, through both layers
         other = getattr(eng.lib, 's2d_rollout_actor_mlp' if mode == 'discrete' else 's2d_rollout_qnet_mlp')
-        assert other(eng._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+        refused(eng.lib, f'{entry}/struct/{mode}/the other entry',
+                other(eng._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, eng._stream()))
         with pytest.raises(ValueError):
             if mode == 'discrete':
                 eng.rollout_actor(4, mu1)

@@ -13,6 +13,7 @@ import pytest
 
 import oracle as O
 import policy_ref as P
+from actor_refusals import refused
 from test_policy_host import EDGE_WORDS, chi2_sf_odd, chi2_stat, edge_rows, fixed_logits, gae_case, softmax64
 
 pytestmark = pytest.mark.gpu
@@ -461,7 +462,7 @@ def test_rejections_leave_the_state_unchanged():
                               (64, 64, na, 2), (64, 64, na, -1)):
             net = actor.c_struct()
             net.hidden1, net.hidden2, net.n_out, net.activation = h1, h2, a, fn
-            assert rc(net) == _capi.S2D_EINVAL, (mode, h1, h2, a, fn)
+            refused(eng.lib, f's2d_rollout_policy/struct/{mode}/{h1}-{h2}-{a} activation {fn}', rc(net))
         fields = [('params', actor.params.data_ptr() + 4), ('params', None), ('deterministic', None),
                   ('deterministic', actor.deterministic_tensor.data_ptr() + 2)]
         if mode != 'discrete':
@@ -469,9 +470,9 @@ def test_rejections_leave_the_state_unchanged():
         for field, val in fields:
             net = actor.c_struct()
             setattr(net, field, val)
-            assert rc(net) == _capi.S2D_EINVAL, (mode, field)
-            assert b's2d_rollout_policy' in eng.lib.s2d_last_error()
-        assert rc(actor.c_struct(), T=0) == _capi.S2D_EINVAL
+            text = refused(eng.lib, f's2d_rollout_policy/struct/{mode}/{field} {"NULL" if val is None else "misaligned"}', rc(net))
+            assert 's2d_rollout_policy' in text
+        refused(eng.lib, f's2d_rollout_policy/struct/{mode}/n_steps 0', rc(actor.c_struct(), T=0))
         with pytest.raises(ValueError):
             eng.rollout_policy(4, StochasticActor(64, 64, na + 1))
         with pytest.raises(ValueError):

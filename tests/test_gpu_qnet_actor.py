@@ -9,6 +9,7 @@ import pytest
 
 import oracle as O
 import qnet_ref as Q
+from actor_refusals import refused
 
 pytestmark = pytest.mark.gpu
 
@@ -366,11 +367,11 @@ def test_rejections_leave_the_state_unchanged():
         if bad_ptr:
             net.params = actor.params.data_ptr() + 4
         rc = eng.lib.s2d_rollout_qnet(eng._h, 4, C.byref(net), C.byref(ro), None, eng._stream())
-        assert rc == _capi.S2D_EINVAL
+        refused(eng.lib, f's2d_rollout_qnet/struct/{h1}-{h2}-{na}' + '/params + 4' * bad_ptr, rc)
     net = actor.c_struct()
-    assert eng.lib.s2d_rollout_qnet(eng._h, 0, C.byref(net), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+    refused(eng.lib, 's2d_rollout_qnet/struct/n_steps 0', eng.lib.s2d_rollout_qnet(eng._h, 0, C.byref(net), C.byref(ro), None, eng._stream()))
     net.epsilon = None
-    assert eng.lib.s2d_rollout_qnet(eng._h, 4, C.byref(net), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+    refused(eng.lib, 's2d_rollout_qnet/struct/epsilon NULL', eng.lib.s2d_rollout_qnet(eng._h, 4, C.byref(net), C.byref(ro), None, eng._stream()))
     with pytest.raises(ValueError):
         eng.rollout_qnet(4, QNetActor(64, 64, 8))
     torch.cuda.synchronize()

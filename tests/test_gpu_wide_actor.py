@@ -11,8 +11,10 @@ import pytest
 import mlp_ref as M
 import oracle as O
 import qnet_ref as Q
+from actor_refusals import refused
 import wide_f64 as W64
 import wide_ref as W
+from test_gpu_qnet_actor import _StepEngine
 from wide_f64 import random_net, views
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ torch = pytest.importorskip('torch')
 nn = torch.nn
 
 F = np.float32
-NOISE = {'off': dict(noise=False), 'lattice': dict(noise=True)}
+NOISE = {'off': dict(noise=False), 'lattice': dict(noise=True), 'square': dict(noise=True, noise_model='rcssserver')}
 MODES = {'discrete': dict(), 'cont1': dict(use_continuous_action=True, use_turning=False),
          'turn4': dict(use_continuous_action=True, use_turning=True)}
 ACT_NN = {'relu': nn.ReLU, 'tanh': nn.Tanh, 'sigmoid': nn.Sigmoid}
@@ -300,7 +302,22 @@ def _engine(n, mode='discrete', noise='off', **kw):
     return Engine(n, 'cuda:0', cfg=make_config(**NOISE[noise], **_kw(mode, **kw)))
 
 
+class _StepOracle(_StepEngine):
+    """test_gpu_qnet_actor's reference for the rcssserver noise model (the per-step API with caller actions; the CPU oracle does
+    not implement that model) on an engine of any action mode"""
+
+    def __init__(self, n, mode, noise, **kw):
+        self.e = _engine(n, mode, noise, **kw)
+        self.dtype = np.int32 if mode == 'discrete' else np.float32
+
+    def step(self, a):
+        o, r, d, res = self.e.step(torch.from_numpy(np.ascontiguousarray(a, dtype=self.dtype)).to('cuda:0'))
+        return self._np(o), self._np(r), self._np(d), self._np(res)
+
+
 def _oracle(n, mode='discrete', noise='off', seed=0x5EED, **kw):
+    if noise == 'square':
+        return _StepOracle(n, mode, noise, seed=seed, **kw)
     cfg = O.make_config(seed=seed, auto_reset=1, noise=int(NOISE[noise]['noise']), **_kw(mode, **kw))
     return O.OracleEngine(cfg, n, 'f32')
 
@@ -387,7 +404,9 @@ def test_rollout_actor_equals_the_resident_path():
 
 
 # ---------------------------------------------------------------------------------------- closed loops against the CPU oracle
-def _closed_loop(refs, mode, hidden, act, n, T, eps, noise, sigma=None, **task):
+def _closed_loop(refs, mode, hidden, act, n, T, eps, noise, sigma=None, twins=(), **task):
+    """the wide actor's launch against the oracle's closed loop; twins: make(net) -> an actor of another back end on the same
+    module, launched on a twin engine: its record and arena are the wide launch's bit for bit (returns [eng, *twin engines])"""
     from soccer2d_amd.wide_actor import WideDeterministicActor, WideQNetActor
     wl, ml, ql = refs
     discrete = mode == 'discrete'
@@ -429,7 +448,52 @@ def _closed_loop(refs, mode, hidden, act, n, T, eps, noise, sigma=None, **task):
     same(eng.policy_step, ((k0 + T) & 0xFFFFFFFF).astype(np.uint32).view(np.int32), 'policy_step = k0 + T')
     same(eng.obs, orc.obs(), 'obs'); same(eng.done, orc.done(), 'done'); same(eng.result, orc.result(), 'result')
     same(eng.stats[:4], orc.stats()[:4].astype(np.int64), 'stats')
-    return eng, out
+    if not twins:
+        return eng, out
+    engs = [eng]
+    for make in twins:
+        twin = _engine(n, mode, noise, **task)
+        twin.reset()
+        twin.rollout(5)
+        tout = twin.alloc_rollout(T, terminal_obs=True)
+        tout['terminal_obs'].fill_(float('nan'))
+        tout = (twin.rollout_qnet if discrete else twin.rollout_actor)(T, make(net), out=tout)
+        torch.cuda.synchronize()
+        for k in RECORD:
+            same(tout[k], out[k].cpu().numpy(), f'{twin.kernel_name()} record.{k}')
+        assert torch.equal(twin.arena, eng.arena), twin.kernel_name()
+        engs.append(twin)
+    return engs, out
+
+
+INSTANTIATIONS = ([('discrete', nz, None) for nz in NOISE] +
+                  [(m, nz, sigma) for m in ('cont1', 'turn4') for nz in NOISE for sigma in (None, 0.2)])
+
+
+@pytest.mark.parametrize('mode,noise,sigma', INSTANTIATIONS)
+def test_every_instantiation_of_the_three_back_ends(refs, mode, noise, sigma):
+    """Each kernel of the launch tables the three back ends share -- the Q head's 3 (engine noise off / lattice / square) and the
+    tanh head's 2 x 3 x 2 (mode x engine noise x Gaussian action noise) -- once per back end: 256 envs x 8 steps on a 10-16-16-A
+    ReLU network, the wide launch against the oracle's closed loop and the MLP and two-layer launches equal to it bit for bit, so
+    that a mixed-up table entry (off for square, a swapped gauss) shows in the record; and the full kernel name of each."""
+    from soccer2d_amd.actor import DeterministicActor, QNetActor
+    from soccer2d_amd.mlp_actor import MlpDeterministicActor, MlpQNetActor, lds_plan
+    from soccer2d_amd.wide_actor import wide_plan
+    discrete = mode == 'discrete'
+    kw = dict(epsilon=0.2) if discrete else dict(epsilon=0.2, noise_sigma=sigma)
+    mlp, two = (MlpQNetActor, QNetActor) if discrete else (MlpDeterministicActor, DeterministicActor)
+    engs, out = _closed_loop(refs, mode, (16, 16), 'relu', 256, 8, 0.2, noise, sigma=sigma, max_steps=6,
+                             twins=[lambda net: mlp.from_module(net, **kw), lambda net: two.from_module(net, **kw)])
+    assert int(out['done'].sum()) >= 256
+    a = 16 if discrete else out['action'].shape[-1]
+    nk, gauss = list(NOISE).index(noise), int(sigma is not None)
+    waves, tiles = wide_plan((16, 16), a)[:2]
+    head = f'noise={nk}' if discrete else f'mode={mode},noise={nk},gauss={gauss}'
+    kind = 'qnet' if discrete else 'actor'
+    assert [e.kernel_name() for e in engs] == [
+        f's2d_wide_{kind}_rollout_kernel<{head},act=relu,h=16-16,a={a},waves={waves},tiles={tiles}>',
+        f's2d_mlp_{kind}_rollout_kernel<{head},act=relu,h=16-16,a={a},waves={lds_plan((16, 16), a)[0]}>',
+        f's2d_reach_{kind}_rollout_kernel<{head},h1=16,h2=16,a={a},waves=4>']
 
 
 @pytest.mark.parametrize('noise', ['off', 'lattice'])
@@ -580,16 +644,16 @@ def test_rejections_leave_the_state_unchanged():
         for what, edit, word in cases:
             s = actor.c_struct()
             edit(s)
-            assert fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL, (mode, what)
-            msg = eng.lib.s2d_last_error().decode()
+            msg = refused(eng.lib, f'{entry}/struct/{mode}/{what}', fn(eng._h, 4, C.byref(s), C.byref(ro), None, eng._stream()))
             assert word in msg and entry in msg, (mode, what, msg)
         s = actor.c_struct()
-        assert fn(eng._h, 0, C.byref(s), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL          # n_steps < 1
-        assert 'n_steps' in eng.lib.s2d_last_error().decode()
-        assert fn(eng._h, 4, None, C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+        assert 'n_steps' in refused(eng.lib, f'{entry}/struct/{mode}/n_steps 0',
+                                    fn(eng._h, 0, C.byref(s), C.byref(ro), None, eng._stream()))
+        refused(eng.lib, f'{entry}/struct/{mode}/net NULL', fn(eng._h, 4, None, C.byref(ro), None, eng._stream()))
         # the wrong engine mode, through both layers
         other = getattr(eng.lib, 's2d_rollout_actor_wide' if mode == 'discrete' else 's2d_rollout_qnet_wide')
-        assert other(eng._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, eng._stream()) == _capi.S2D_EINVAL
+        refused(eng.lib, f'{entry}/struct/{mode}/the other entry',
+                other(eng._h, 4, C.byref(actor.c_struct()), C.byref(ro), None, eng._stream()))
         with pytest.raises(ValueError):
             if mode == 'discrete':
                 eng.rollout_actor(4, mu1)
