@@ -103,7 +103,7 @@ static int wide_workspace(const char* who, const S2DWideNet* net, const WideDims
 // params -> workspace in fragment order, on `stream`
 static void launch_pack(const WideDims& d, const S2DWideNet* net, hipStream_t stream) {
   const int words = d.nfrag * kWave + d.nbias;
-  hipLaunchKernelGGL(s2d_wide_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, net->params,
+  hipLaunchKernelGGL(s2d_wide_pack_kernel<S2D_OBS_DIM>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, net->params,
                      static_cast<float*>(net->workspace));
 }
 

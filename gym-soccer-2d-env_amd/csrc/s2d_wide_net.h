@@ -14,6 +14,11 @@
 // weights), later layers over exactly h_(l-1) terms; a width that is no multiple of 16 pads the OUTPUT ROWS of its last tile and
 // the next layer's k-steps stop at h / 4.  h / 4 may be odd: the k-steps go in groups of four, then one group of two, then one
 // single step, in ascending order.  Neither T nor the waves per workgroup enters a chain: the bits do not depend on the plan.
+//
+// The input width is a compile-time parameter IN (S2D_OBS_DIM unless said): it is the observation tile's row stride, gives
+// layer 1 its ceil(IN / 4) k-steps and the pack kernel its first `win`.  The GoToCenter actors (s2d_gtc_actor.hip) use IN = 4:
+// layer 1 is then ONE k-step over exactly k = 0 .. 3 with no zero pad, so an accumulator of -0 stays -0 there (the padded
+// layer 1 of IN = 10 turns it into +0); a wave's LDS part ends with the observation tile of 64 x IN words and no PrepTile.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -176,30 +181,31 @@ S2D_DEV void wide_layer(const float* __restrict__ wf, const float* __restrict__ 
 }
 
 // the layers on the wave's observation tile, T env tiles per pass, ping-ponging between the wave's two images: the pass's
-// observations go into image B as 12 words a row (x_10 = x_11 = 0), layer 1 reads them and writes image A, the output layer writes
-// into the output image qv[env][j] (pitch d.qpitch)
-template <int T>
+// observations go into image B as 4 ceil(IN / 4) words a row (IN = 10: 12 words, x_10 = x_11 = 0), layer 1 reads them and writes
+// image A, the output layer writes into the output image qv[env][j] (pitch d.qpitch)
+template <int T, int IN = S2D_OBS_DIM>
 S2D_DEV void wide_layers(const WideDims& d, const float* __restrict__ bias0, float* __restrict__ ia, float* __restrict__ ib,
                          float* __restrict__ qv, const float* __restrict__ obs_tile, int lane) {
   const int g = lane >> 4, c = lane & 15;
+  constexpr int KS1 = (IN + 3) / 4;                         // layer 1's k-steps
   const int rp = d.rpitch, tstride = 16 * rp;
   for (int nt = 0; nt < 4; nt += T) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      const float* x = obs_tile + (16 * (nt + t) + c) * S2D_OBS_DIM;
+      const float* x = obs_tile + (16 * (nt + t) + c) * IN;
 #pragma unroll
-      for (int s = 0; s < 3; ++s) {
+      for (int s = 0; s < KS1; ++s) {
         const int k = 4 * s + g;
-        ib[t * tstride + c * rp + k] = k < S2D_OBS_DIM ? x[k] : 0.0f;
+        ib[t * tstride + c * rp + k] = k < IN ? x[k] : 0.0f;
       }
     }
     wave_lds_fence();
     const float* wf = d.wf;
     const float* bias = bias0;
     int hin = wide_width(d, 0), m16 = (hin + 15) >> 4;
-    wide_layer<T>(wf, bias, m16, 3, ib, rp, tstride, ia, rp, tstride, d.act, lane);
+    wide_layer<T>(wf, bias, m16, KS1, ib, rp, tstride, ia, rp, tstride, d.act, lane);
     wave_lds_fence();
-    wf += 3 * m16 * kWave;
+    wf += KS1 * m16 * kWave;
     bias += 16 * m16;
     float* in = ia;
     float* out = ib;
@@ -221,12 +227,12 @@ S2D_DEV void wide_layers(const WideDims& d, const float* __restrict__ bias0, flo
 // the network on the observation tile of the wave (lane = env): qv[env][j] = the output layer's pre-activations y_j; ARGMAX: then
 // the argmax scan of the two-layer net_forward.  `bias` = the block's LDS (net_pack); ha = the wave's images (A, then B at hb =
 // ha + 16 d.pitch).  d.tiles and d.act are wave-uniform; every form is compiled into every kernel.
-template <bool ARGMAX>
+template <bool ARGMAX, int IN = S2D_OBS_DIM>
 S2D_DEV int net_forward(const WideDims& d, const float* __restrict__ bias, float* __restrict__ ha, float* __restrict__ hb,
                         float* __restrict__ qv, const float* __restrict__ obs_tile, int lane) {
-  if (d.tiles == 4) wide_layers<4>(d, bias, ha, hb, qv, obs_tile, lane);
-  else if (d.tiles == 2) wide_layers<2>(d, bias, ha, hb, qv, obs_tile, lane);
-  else wide_layers<1>(d, bias, ha, hb, qv, obs_tile, lane);
+  if (d.tiles == 4) wide_layers<4, IN>(d, bias, ha, hb, qv, obs_tile, lane);
+  else if (d.tiles == 2) wide_layers<2, IN>(d, bias, ha, hb, qv, obs_tile, lane);
+  else wide_layers<1, IN>(d, bias, ha, hb, qv, obs_tile, lane);
   if constexpr (!ARGMAX) return 0;
   // best = 0; for a = 1 .. A-1: if (q[a] > q[best]) best = a   (ties: lowest index; a NaN never replaces the best)
   const float* q = qv + lane * d.qpitch;
@@ -247,9 +253,11 @@ S2D_DEV void net_pack(const WideDims& d, const float* __restrict__, float* __res
   for (int idx = threadIdx.x; idx < d.nbias; idx += blockDim.x) smem[idx] = bias[idx];
 }
 
-// The caller's parameters (nn.Sequential order: W_1 [h_1][10], b_1, ..., W_L [h_L][h_(L-1)], b_L, W_out [A][h_L], b_out) into the
+// The caller's parameters (nn.Sequential order: W_1 [h_1][IN], b_1, ..., W_L [h_L][h_(L-1)], b_L, W_out [A][h_L], b_out) into the
 // workspace in fragment order, then the biases, every layer's padded with zeros to its tiles' 16 rows: one word per thread.  Rows
-// past a layer's width and layer 1's k = 10, 11 are zero.  Enqueued ahead of every launch that reads the workspace.
+// past a layer's width and layer 1's k >= IN (10, 11) are zero.  Enqueued ahead of every launch that reads the workspace.  A
+// template, so that every unit that includes this header has its own.
+template <int IN = S2D_OBS_DIM>
 __global__ __launch_bounds__(256) void s2d_wide_pack_kernel(WideDims d, const float* __restrict__ params, float* __restrict__ ws) {
   const int L = d.n_hidden;
   const int nw = d.nfrag * kWave;
@@ -259,7 +267,7 @@ __global__ __launch_bounds__(256) void s2d_wide_pack_kernel(WideDims d, const fl
     const int f = idx / kWave, lw = idx & (kWave - 1);
     const int row = lw & 15, kk = lw >> 4;
     // the layer of fragment f: its first fragment, widths in and out, k-steps and the offset of its W in params
-    int f0 = 0, win = S2D_OBS_DIM, wout = wide_width(d, 0), ks = 3, ow = 0;
+    int f0 = 0, win = IN, wout = wide_width(d, 0), ks = (IN + 3) / 4, ow = 0;
 #pragma unroll
     for (int l = 1; l <= kWideMaxHidden; ++l) {
       const int next = f0 + ((wout + 15) >> 4) * ks;       // the first fragment of the layer after this one
@@ -275,7 +283,7 @@ __global__ __launch_bounds__(256) void s2d_wide_pack_kernel(WideDims d, const fl
     ws[idx] = (j < wout && k < win) ? params[ow + j * win + k] : 0.0f;
   } else {
     const int bi = idx - nw;
-    int b0 = 0, win = S2D_OBS_DIM, wout = wide_width(d, 0), ob = wout * win;     // ob: the offset of the layer's bias in params
+    int b0 = 0, win = IN, wout = wide_width(d, 0), ob = wout * win;     // ob: the offset of the layer's bias in params
 #pragma unroll
     for (int l = 1; l <= kWideMaxHidden; ++l) {
       const int pad = (wout + 15) & ~15;
@@ -302,9 +310,12 @@ static inline bool wide_shape_ok(int n_hidden, const int32_t* hidden) {
   return true;
 }
 
-// bytes of LDS of a shape's dims with `waves` waves per workgroup and `tiles` env tiles per pass
-static inline size_t wide_lds_bytes(const WideDims& d, int waves, int tiles, int* wave_words) {
-  const int ww = 2 * tiles * 16 * d.rpitch + kWave * d.qpitch + kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
+// words of a wave's LDS part behind its output image, in the rollout template: the observation tile and the PrepTile
+static constexpr int kWideTail = kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
+
+// bytes of LDS of a shape's dims with `waves` waves per workgroup and `tiles` env tiles per pass; `tail`: see kWideTail
+static inline size_t wide_lds_bytes(const WideDims& d, int waves, int tiles, int* wave_words, int tail = kWideTail) {
+  const int ww = 2 * tiles * 16 * d.rpitch + kWave * d.qpitch + tail;
   if (wave_words) *wave_words = ww;
   return ((size_t)((d.nbias + 3) & ~3) + (size_t)waves * ww) * sizeof(float);
 }
@@ -312,12 +323,14 @@ static inline size_t wide_lds_bytes(const WideDims& d, int waves, int tiles, int
 // The plan of a valid shape: the dims (wf left NULL), per-wave words, waves per workgroup, env tiles per pass and the LDS bytes.
 // More waves go before more tiles (one wave per workgroup leaves three SIMDs of the CU idle): the first of (4, 4) (4, 2) (4, 1)
 // (2, 4) ... (1, 1) that 160 KiB hold; (1, 1) always fits (width 400: 2 x 16 x 452 words of images).  force_waves / force_tiles
-// (0 = the plan's choice) are the testing override; false if the forced pair does not fit or is not in {4, 2, 1}.
+// (0 = the plan's choice) are the testing override; false if the forced pair does not fit or is not in {4, 2, 1}.  IN: the
+// input width (layer 1 has ceil(IN / 4) k-steps); tail: the words of a wave behind its output image.
+template <int IN = S2D_OBS_DIM>
 static inline bool wide_plan_lds(int n_hidden, const int32_t* hidden, int na, int act, int force_waves, int force_tiles, WideDims& d,
-                                 int& wave_words, int& waves, size_t& lds) {
+                                 int& wave_words, int& waves, size_t& lds, int tail = kWideTail) {
   d = WideDims{};
   d.n_hidden = n_hidden; d.act = act; d.na = na; d.na16 = (na + 15) / 16 * 16;
-  int nfrag = 0, nbias = 0, wmax = 0, ksteps = 3;
+  int nfrag = 0, nbias = 0, wmax = 0, ksteps = (IN + 3) / 4;
   for (int l = 0; l < n_hidden; ++l) {
     const int w = hidden[l], m16 = (w + 15) / 16;
     d.widths |= (uint64_t)(w / 4) << (7 * l);
@@ -337,7 +350,7 @@ static inline bool wide_plan_lds(int n_hidden, const int32_t* hidden, int na, in
     if (force_waves && wv != force_waves) continue;
     for (int t = 4; t >= 1; t /= 2) {
       if (force_tiles && t != force_tiles) continue;
-      lds = wide_lds_bytes(d, wv, t, &wave_words);
+      lds = wide_lds_bytes(d, wv, t, &wave_words, tail);
       if (lds <= kLdsMax) {
         waves = wv; d.tiles = t; d.pitch = t * d.rpitch;
         return true;

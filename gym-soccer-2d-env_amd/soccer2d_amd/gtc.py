@@ -31,6 +31,11 @@ GTC_PROTOTYPES = (
     ('s2d_gtc_step', C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_gtc_step_u', C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_gtc_rollout', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DGtcRollout), C.c_void_p)),
+    ('s2d_gtc_actor_workspace_bytes', C.c_size_t, (C.POINTER(_capi.S2DWideNet),)),
+    ('s2d_gtc_rollout_qnet', C.c_int, (C.c_void_p, C.c_int, C.POINTER(_capi.S2DWideNet), C.POINTER(S2DGtcRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_gtc_rollout_actor', C.c_int, (C.c_void_p, C.c_int, C.POINTER(_capi.S2DWideNet), C.POINTER(S2DGtcRollout), C.c_void_p, C.c_void_p)),
+    ('s2d_gtc_debug_forward', C.c_int, (C.POINTER(_capi.S2DWideNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p)),
+    ('s2d_gtc_kernel_name', C.c_char_p, (C.c_void_p,)),
 )
 _FIELDS = (('x', 'float32', ()), ('y', 'float32', ()), ('body', 'float32', ()), ('prev_distance', 'float32', ()),
            ('prev_angle_diff', 'float32', ()), ('step_count', 'int32', ()), ('episode', 'int32', ()),
@@ -131,20 +136,65 @@ class GoToCenterVecEnv:
             _capi.check(self.lib, self.lib.s2d_gtc_step(self._h, ptr, self._stream()), 's2d_gtc_step')
         return self.obs, self.reward, self.done, {'result': self.result, 'terminal_observation': self.terminal_obs}
 
-    def rollout(self, n_steps, with_obs=True):
+    def _alloc_rollout(self, n_steps, with_obs):
         T, n, dev = int(n_steps), self.num_envs, self.device
-        out = dict(obs=torch.empty((T, n, 4), device=dev) if with_obs else None,
+        return dict(obs=torch.empty((T, n, 4), device=dev) if with_obs else None,
                    action=(torch.empty((T, n, self.action_dim) if self.turn_mode else (T, n), dtype=torch.float32, device=dev)
                            if self.cfg.continuous else torch.empty((T, n), dtype=torch.int32, device=dev)),
                    reward=torch.empty((T, n), device=dev), done=torch.empty((T, n), dtype=torch.uint8, device=dev),
                    result=torch.empty((T, n), dtype=torch.uint8, device=dev))
+
+    @staticmethod
+    def _rollout_struct(out):
         ro = S2DGtcRollout()
-        for k, v in out.items():
-            if v is not None:
-                setattr(ro, k, v.data_ptr())
-        _capi.check(self.lib, self.lib.s2d_gtc_rollout(self._h, T, C.byref(ro), self._stream()), 's2d_gtc_rollout')
+        for k in ('obs', 'action', 'reward', 'done', 'result'):
+            if out.get(k) is not None:
+                setattr(ro, k, out[k].data_ptr())
+        return ro
+
+    def rollout(self, n_steps, with_obs=True):
+        out = self._alloc_rollout(n_steps, with_obs)
+        ro = self._rollout_struct(out)
+        _capi.check(self.lib, self.lib.s2d_gtc_rollout(self._h, int(n_steps), C.byref(ro), self._stream()), 's2d_gtc_rollout')
         self._keep = out
         return out
+
+    def _rollout_fused(self, entry, n_steps, actor, with_obs, terminal_obs, out):
+        if getattr(actor, '_entry', None) != entry:
+            raise ValueError(f'{entry} takes a soccer2d_amd.gtc_actor.'
+                             f'{"GtcQNetActor" if entry.endswith("qnet") else "GtcDeterministicActor"}, got {type(actor).__name__}')
+        if actor.device != self.device:
+            raise ValueError(f'the actor lives on {actor.device}, the env on {self.device}')
+        if out is None:
+            out = self._alloc_rollout(n_steps, with_obs)
+            if terminal_obs:
+                out['terminal_obs'] = torch.zeros((int(n_steps), self.num_envs, 4), device=self.device)
+        ro = self._rollout_struct(out)
+        term = out.get('terminal_obs')
+        net = actor.c_struct()
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, entry)(self._h, int(n_steps), C.byref(net), C.byref(ro),
+                                          C.c_void_p(term.data_ptr()) if term is not None else None, self._stream())
+        _capi.check(self.lib, rc, entry)
+        self._keep = (out, actor)
+        return out
+
+    def rollout_qnet(self, n_steps, actor, with_obs=True, terminal_obs=False, out=None):
+        """n_steps of a discrete env with the actor's Q-network evaluated in the rollout kernel, epsilon-greedy per env
+        (s2d_gtc_rollout_qnet; actor: soccer2d_amd.gtc_actor.GtcQNetActor).  Returns rollout()'s record dict, plus
+        'terminal_obs' [T, N, 4] when asked for: written only where done (zeros elsewhere in a buffer allocated here), the
+        observation the episode ended on.  out: a dict from an earlier call, written again (a captured graph replays into it)."""
+        return self._rollout_fused('s2d_gtc_rollout_qnet', n_steps, actor, with_obs, terminal_obs, out)
+
+    def rollout_actor(self, n_steps, actor, with_obs=True, terminal_obs=False, out=None):
+        """The same on a continuous or turn-mode env with the deterministic tanh actor, epsilon-random exploration and
+        optional Gaussian action noise (s2d_gtc_rollout_actor; actor: soccer2d_amd.gtc_actor.GtcDeterministicActor with n_out =
+        action_dim)."""
+        return self._rollout_fused('s2d_gtc_rollout_actor', n_steps, actor, with_obs, terminal_obs, out)
+
+    def kernel_name(self):
+        """the last fused launch: head, mode, gauss, activation, widths, outputs, waves per workgroup, env tiles per pass"""
+        return (self.lib.s2d_gtc_kernel_name(self._h) or b'').decode()
 
     def close(self):
         if getattr(self, '_h', None):

@@ -62,6 +62,38 @@ int s2d_gtc_step(S2DGtcHandle h, const void *actions_dev, void *stream);
 int s2d_gtc_step_u(S2DGtcHandle h, const void *actions_dev, const float *select_u_dev, void *stream);
 int s2d_gtc_rollout(S2DGtcHandle h, int n_steps, const S2DGtcRollout *out, void *stream);   /* random policy */
 
+/* The fused actors (DESIGN.md sections 4, 5): the caller's network evaluated inside the rollout kernel on each env's own
+ * 4-word observation -- an epsilon-greedy Q-network on a discrete engine (s2d_gtc_rollout_qnet, n_out = 16) and a
+ * deterministic tanh policy with optional Gaussian action noise on a continuous or turn-mode engine (s2d_gtc_rollout_actor,
+ * n_out = the engine's action width: actor_out_size in the turn mode, else 1).
+ *   network   S2DWideNet (s2d.h) read with "10 ->" as "4 ->": 4 -> h_1 -> ... -> h_L -> n_out, L in 1..5, widths multiples of 4 in
+ *             [8, 400], relu / tanh_spec / sigmoid_spec, linear output; params in nn.Sequential(...).parameters() order
+ *             (W_1[h_1][4], b_1, ...); every unit acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc).
+ *   layer 1   runs over exactly k = 0 .. 3: no zero pad, so an accumulator of -0 STAYS -0 (S2DWideNet's padded layer 1 on the
+ *             10-word observation turns it into +0).
+ *   draws     env g in episode j at step s = step_count: philox(g, j, (stream << 16) | s, seed), s2d_gtc_rollout's keying.
+ *             explore = (uint64)w.x < threshold(epsilon) with w from stream 9 (eps >= 1: always; eps <= 0 or NaN: never).
+ *             Exploring: the random policy's own action (stream POLICY), no action noise: epsilon = 1 IS s2d_gtc_rollout.
+ *             Else Q head: the first maximum of y (a NaN never wins); tanh head: a_j = tanh_spec(y_j), with noise_kind = 1
+ *             a_j = clip(a_j + fmaf(sigma_j, z_j, mu_j), -1, 1), z0, z1 = box_muller(w.x, w.y), z2, z3 = box_muller(w.z, w.w) of
+ *             stream 10, noise = [2][n_out] (mu, sigma).  The turn / dash uniform of use_turn stays the SELECT stream's.
+ *   records   S2DGtcRollout's, and terminal_obs [T][N][4] (may be NULL; 16-byte aligned), written only where done: the
+ *             observation the episode ended on.  State planes, per-step outputs and statistics as s2d_gtc_rollout leaves them.
+ *   workspace at least s2d_gtc_actor_workspace_bytes() bytes (0 for a shape off the grid; needs no device), 256-byte aligned:
+ *             every call first writes the fragments there (a pack kernel on `stream`), then the rollout reads them; params,
+ *             epsilon and noise are read when the kernels run.  One launch at a time per workspace.
+ * S2D_WIDE_PLAN=waves,tiles overrides the LDS plan (testing; the result does not depend on it).  Refusals return S2D_EINVAL
+ * with a text and launch nothing; n_steps = 0 is a no-op.  s2d_gtc_debug_forward: the network alone on obs [n][4] -> y [n][n_out]
+ * and the first maximum greedy [n] (name: 96 bytes or NULL).  s2d_gtc_kernel_name: the last fused launch of the handle. */
+size_t s2d_gtc_actor_workspace_bytes(const S2DWideNet *shape);
+int s2d_gtc_rollout_qnet(S2DGtcHandle h, int n_steps, const S2DWideNet *net, const S2DGtcRollout *out, float *terminal_obs,
+                         void *stream);
+int s2d_gtc_rollout_actor(S2DGtcHandle h, int n_steps, const S2DWideNet *net, const S2DGtcRollout *out, float *terminal_obs,
+                          void *stream);
+int s2d_gtc_debug_forward(const S2DWideNet *shape, const void *obs_dev, int64_t n, void *y_dev, void *greedy_dev, char *name,
+                          void *stream);
+const char *s2d_gtc_kernel_name(S2DGtcHandle h);
+
 #ifdef __cplusplus
 }
 #endif

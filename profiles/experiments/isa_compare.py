@@ -49,7 +49,7 @@ def disasm(tree, unit, out):
         since_pc = 0 if ins.startswith('s_getpc') else since_pc + 1
         if since_pc <= 2 and ins.startswith(('s_add_u32', 's_addc_u32')):      # PC-relative literal of a code-object address
             ins = re.sub(r'0x[0-9a-fA-F]+|\b-?\d+$', 'X', ins)
-        if ins and ins != 's_nop 0':
+        if ins and ins not in ('s_nop 0', '...'):                                # '...': objdump's run of zero padding
             cur.append(' '.join(ins.split()))
     for f in funcs.values():
         while f and f[-1] in ('s_code_end', 's_nop 0'):
