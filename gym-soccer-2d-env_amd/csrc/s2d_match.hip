@@ -1145,6 +1145,13 @@ struct MCtl {                          // kernel argument of the CTL instantiati
   uint32_t random_mask, script_mask;   // bit i: slot i is random / scripted; neither: the caller's row (read for those slots only)
   float* actions_out;                  // [T][N][22][3] each slot's (cmd, a, b) before the engine's gating, or NULL
 };
+// The agent reward ("Agent reward", include/s2d_match.h): the RW instantiations take an MCtlRw where the CTL ones take an MCtl
+struct MRw {
+  const float* w;                      // the caller's float[S2D_MATCH_REWARD_TERMS], read when the kernel runs
+  float* out;                          // [T][N][22]
+  int chaser_only;
+};
+struct MCtlRw { MCtl ctl; MRw rw; };   // kernel argument of the RW instantiations (s2d_match_reward.hip)
 // The scripted team's constants (documented with the rule table in include/s2d_match.h)
 constexpr float kTurnTol = S2D_SCRIPT_TURN_TOL, kArrive = S2D_SCRIPT_ARRIVE, kArrive2 = kArrive * kArrive;
 constexpr float kScriptDash = S2D_SCRIPT_DASH_POWER;
@@ -1277,6 +1284,7 @@ S2D_DEV void m_flush_counts(unsigned long long* stats, const unsigned int* lds_c
     atomicAdd(&stats[(blockIdx.x % S2D_STATS_STRIPES) * 8 + threadIdx.x], (unsigned long long)lds_cnt[threadIdx.x]);
 }
 
+#ifndef S2D_MATCH_REWARD_UNIT   // (the non-template kernels and the C ABI belong to s2d_match.hip alone: see s2d_match_reward.hip)
 __global__ __launch_bounds__(kMBlock) void s2d_match_reset_kernel(MParams p, MPtrs q, int64_t n, const uint8_t* __restrict__ mask) {
   const int l = threadIdx.x & (kHalf - 1);
   const int64_t e = (int64_t)blockIdx.x * kEnvsPerBlock + threadIdx.x / kHalf;
@@ -1286,6 +1294,7 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_reset_kernel(MParams p, MPt
   m_reset(p, q.ptab[PT_EFFORT_MAX * kHalf + l], o, g, r, l);
   m_store(q, e, l, o, g, r);
 }
+#endif
 
 // Per-agent observations (include/s2d_match.h, s2d_match_agent_obs).  Per-slot words the cycle kernels do not keep (the PT table
 // stays as it is): built on the host at create time, passed by value.
@@ -1474,6 +1483,54 @@ S2D_DEV void m_agent_row_store(float* __restrict__ dst, const float4* row, int l
   float4* d = reinterpret_cast<float4*>(dst);
   d[l] = row[l];
   if (l + kHalf < kAObsVec) d[l + kHalf] = row[l + kHalf];
+}
+
+// Agent reward (include/s2d_match.h): what lane l's reward reads of its own row -- the ball's place (field frame: the own-frame x is
+// sgn * bx, exact), ball.dist_from_self and |ball.bearing|, in m_agent_row's own expressions (its ball lane, pa = l), so that the
+// words are bitwise the row's.  Called by all 64 lanes (the ball broadcast); lanes >= 22 get words nobody reads.
+struct MRwView { float bx, by, dist, abear; };
+S2D_DEV MRwView m_reward_view(const MObj& o, int l, int half) {
+  const float bx = hbcast_c<BALL>(o.x, half), by = hbcast_c<BALL>(o.y, half);
+  const bool right = l >= 11;
+  const float sg = right ? -1.0f : 1.0f;
+  const float dx = sg * bx - sg * o.x, dy = sg * by - sg * o.y;
+  return MRwView{bx, by, hypot2(dx, dy), fabsf(norm_deg_any(atan2_deg(dy, dx) - m_own_body(o.body, right)))};
+}
+// gate of the individual terms on the start-of-cycle side: active, and with chaser_only the team's rule-5 chaser (the search of
+// m_scripted_action: the same keys, the same reduction).  chaser_only is wave-uniform; all 64 lanes call.
+S2D_DEV bool m_reward_gate(const MObj& o, const MRwView& v, int chaser_only, int l) {
+  bool gate = o.card < S2D_CARD_RED;
+  if (chaser_only) {
+    const float d2 = sq2(v.bx - o.x, v.by - o.y);
+    const bool field = l < NP && l != S2D_MATCH_GOALIE_LEFT && l != S2D_MATCH_GOALIE_RIGHT && o.card < S2D_CARD_RED;
+    unsigned long long kl = (field && l < 11) ? nearest_key(d2, l) : ~0ull;
+    unsigned long long kr = (field && l >= 11) ? nearest_key(d2, l) : ~0ull;
+    half_min_keys(kl, kr);
+    gate = gate && (int)((l < 11 ? kl : kr) & 0xFFull) == l;
+  }
+  return gate;
+}
+// The reward of lane l's agent for the cycle S -> S': v0 / mode0 / act0 (card < RED) / gate0 (m_reward_gate) of S, v1 / o / g of S'; ka2 = the
+// slot's kickable bound; w = the six weights.  Terms and their order: the table of include/s2d_match.h.
+S2D_DEV float m_agent_reward(const MRwView& v0, int mode0, bool act0, bool gate0, const MRwView& v1, const MObj& o, const MGame& g, float ka2,
+                             const float (&w)[S2D_MATCH_REWARD_TERMS], int l) {
+  const bool right = l >= 11;
+  const float sg = right ? -1.0f : 1.0f;
+  const bool play1 = g.mode == S2D_GM_PLAY_ON, live = mode0 == S2D_GM_PLAY_ON && play1;
+  const bool act1 = o.card < S2D_CARD_RED;
+  const bool indiv = live && gate0 && act1;
+  const bool kickable = act1 && sq2(v1.bx - o.x, v1.by - o.y) <= ka2;      // row(S')[self.is_kickable]
+  const float term[S2D_MATCH_REWARD_TERMS] = {
+      sg * g.reward,
+      live ? sg * v1.bx - sg * v0.bx : 0.0f,
+      indiv ? v0.dist - v1.dist : 0.0f,
+      indiv ? (v0.abear - v1.abear) * 0.005555555555555556f : 0.0f,
+      (play1 && act0 && kickable) ? 1.0f : 0.0f,
+      play1 ? m_side_word(g.last_touch, right ? SIDE_RIGHT : SIDE_LEFT) : 0.0f};
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < S2D_MATCH_REWARD_TERMS; ++k) acc = fmaf(w[k], term[k], acc);
+  return acc;
 }
 
 
@@ -1841,9 +1898,13 @@ struct MShared {                                      // the workgroup's LDS (de
 // NET (with CTL): the network slots of `nin` override the table: the action of the caller's network on the slot's agent row.
 // NA = MSeeArg (with NET): the see network -- the network acts on the slot's see row and chooses the view action too; the vision
 // state of all 22 players is stepped here, once per cycle, after the body cycle.
-template <bool CTL, bool NET = false, class P, class TY, class NA = MNetArg>
+// RW (with CTL, not SEE): the agent reward record of `rw`.  A lane's start-of-cycle words are the end-of-cycle ones of the cycle
+// before, carried in registers; the start-of-cycle mode and card are read before the cycle.
+template <bool CTL, bool NET = false, bool RW = false, class P, class TY, class NA = MNetArg>
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
-                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr) {
+                                const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr,
+                                const MRw& rw = MRw{nullptr, nullptr, 0}) {
+  static_assert(!RW || (CTL && !(NET && std::is_same<NA, MSeeArg>::value)), "the agent reward: the CTL family, not the see network");
   constexpr bool SEE = NET && std::is_same<NA, MSeeArg>::value;
   constexpr bool POL = NET && std::is_same<NA, MPolArg>::value;   // policy slots: an instantiation of its own (the NET ones keep their code)
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
@@ -1880,6 +1941,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   char* obs_row = reinterpret_cast<char*>(ro.obs) + eb * (int64_t)(kVecPerMatch * 16);
   float* reward_row = ro.reward + eb; int32_t* mode_row = ro.mode + eb; uint8_t* done_row = ro.done + eb;
   float* act_row = CTL ? ctl.actions_out + eb * (NP * 3) : nullptr;   // the action record: [T][N][22][3], same scheme
+  [[maybe_unused]] float* rw_row = RW ? rw.out + eb * NP : nullptr;   // the agent reward record: [T][N][22], same scheme
   const uint32_t lane = threadIdx.x & 63u, m_in_wg = threadIdx.x / kHalf;
   const uint32_t obs_off = ((threadIdx.x >> 6) * 2u * kVecPerMatch + lane) * 16u;
   const int64_t e0 = e - half;                             // first match of this wave (matches of a wave: e0, e0 + 1)
@@ -1919,6 +1981,13 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       }
     }
   }
+  [[maybe_unused]] MRwView rw_view{0.0f, 0.0f, 0.0f, 0.0f};      // RW: this lane's words of the current state
+  [[maybe_unused]] float rw_w[S2D_MATCH_REWARD_TERMS] = {};
+  if constexpr (RW) {
+    rw_view = m_reward_view(o, l, half);
+#pragma unroll
+    for (int k = 0; k < S2D_MATCH_REWARD_TERMS; ++k) rw_w[k] = rw.w[k];   // (uniform: scalar loads)
+  }
   for (int t = 0; t < n_steps; ++t) {
     if ((t & 3) == 0) {
       switch ((simd_slot + (t >> 2)) & 3) {
@@ -1934,6 +2003,12 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
     // the lane number and the half make them per-cycle values.
     int l = l_launch, half = half_launch;
     asm volatile("" : "+v"(l), "+v"(half));
+    [[maybe_unused]] int rw_mode0 = 0;                     // RW: the start-of-cycle mode, card and gate
+    [[maybe_unused]] bool rw_act0 = false, rw_gate0 = false;
+    if constexpr (RW) {
+      rw_mode0 = g.mode; rw_act0 = o.card < S2D_CARD_RED;
+      rw_gate0 = m_reward_gate(o, rw_view, rw.chaser_only, l);
+    }
     int cmd = S2D_MCMD_NONE; float a = 0.0f, b = 0.0f;
     float view_m = 0.0f, view_c = 0.0f;                    // SEE: this slot's view action (TurnNeck moment, ChangeView code) ...
     bool view_act = false;                                 // ... and whether it has one
@@ -2024,6 +2099,13 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       if (ro.done) done_row[m_in_wg] = (uint8_t)g.done;
     }
     reward_row += n; mode_row += n; done_row += n;         // (never dereferenced when the array is absent)
+    if constexpr (RW) {
+      const MRwView v1 = m_reward_view(o, l, half);
+      const float rwd = m_agent_reward(rw_view, rw_mode0, rw_act0, rw_gate0, v1, o, g, pt[PT_KICKABLE_AREA2][l], rw_w, l);
+      if (valid && l < NP) rw_row[m_in_wg * NP + l] = rwd;
+      rw_row += n * NP;
+      rw_view = v1;
+    }
   }
   match_nearest(o, g, l);
   if (valid) m_store(q, e, l, o, g, r);
@@ -2054,20 +2136,30 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // instantiations keep their template and kernel arguments).
 // POL: the NET instantiations whose second extra argument is an MPolArg -- policy slots, likewise a family of its own: a launch
 // takes one only when a role holds a policy network, so the NET kernels and their LDS plan are what they were.
+// RW: the CTL / NET / POL instantiations whose first extra argument is an MCtlRw -- the agent reward record, likewise a family of
+// its own, instantiated in a translation unit of its own (s2d_match_reward.hip): this unit's kernels are what they were.
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeeArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MPolArg&) { return c; }
+template <class... A> S2D_DEV MCtl m_ctl_arg(const MCtlRw& c, const A&...) { return c.ctl; }
 S2D_DEV const MNetArg* m_net_arg() { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&) { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
 S2D_DEV const MSeeArg* m_net_arg(const MCtl&, const MSeeArg& a) { return &a; }
 S2D_DEV const MPolArg* m_net_arg(const MCtl&, const MPolArg& a) { return &a; }
+S2D_DEV const MNetArg* m_net_arg(const MCtlRw&) { return nullptr; }
+template <class A> S2D_DEV const A* m_net_arg(const MCtlRw&, const A& a) { return &a; }
+template <class... A> S2D_DEV MRw m_rw_arg(const A&...) { return MRw{nullptr, nullptr, 0}; }
+template <class... A> S2D_DEV MRw m_rw_arg(const MCtlRw& c, const A&...) { return c.rw; }
 template <class... A> struct MIsSee : std::false_type {};
 template <> struct MIsSee<MCtl, MSeeArg> : std::true_type {};
 template <class... A> struct MIsPol : std::false_type {};
 template <> struct MIsPol<MCtl, MPolArg> : std::true_type {};
+template <> struct MIsPol<MCtlRw, MPolArg> : std::true_type {};
+template <class... A> struct MIsRw : std::false_type {};
+template <class... A> struct MIsRw<MCtlRw, A...> : std::true_type {};
 template <bool STOCK, bool STOCK_TYPES, bool SCHED = false, bool ILL = false, bool CTL = false, bool NET = false, class... CtlArg>
 __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel(MParams p_arg, MPtrs q, int64_t n, int n_steps,
                                                                      const float* __restrict__ actions, MRoll ro, CtlArg... ctl_arg) {
@@ -2075,7 +2167,10 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
   static_assert(!NET || CTL, "network slots come with the controller table");
   constexpr bool SEE = MIsSee<CtlArg...>::value;
   constexpr bool POL = MIsPol<CtlArg...>::value;
+  constexpr bool RW = MIsRw<CtlArg...>::value;
+  static_assert(!RW || !SEE, "the see network has no agent reward");
   const MCtl ctl = m_ctl_arg(ctl_arg...);
+  [[maybe_unused]] const MRw rw = m_rw_arg(ctl_arg...);
   const auto* const nin = m_net_arg(ctl_arg...);
   __shared__ float4 pos_tile[kEnvsPerBlock][kTileSlots];
   __shared__ PTab pt[PT_WORDS];                       // per-slot PlayerType parameters, shared by the 8 matches
@@ -2099,15 +2194,15 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
     const MStockSched p{p_arg.auto_reset, p_arg.noise, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi M_SCHEDULE_INTS(X)};
 #undef X
     const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-    match_rollout_body<CTL, NET>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin);
+    match_rollout_body<CTL, NET, RW>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin, rw);
   } else if constexpr (STOCK) {
     __syncthreads();
     const MStock p{p_arg.auto_reset, p_arg.noise, p_arg.penalty_shoot_outs, p_arg.seed_lo, p_arg.seed_hi, p_arg.gid_lo, p_arg.gid_hi};
     if constexpr (STOCK_TYPES) {
       const MStockTypes types{__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.ptab[PT_KICKABLE_AREA2 * kHalf])))};
-      match_rollout_body<CTL, NET>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin);
+      match_rollout_body<CTL, NET, RW>(p, types, sh, q, n, n_steps, actions, ro, ctl, nin, rw);
     } else {
-      match_rollout_body<CTL, NET>(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin);
+      match_rollout_body<CTL, NET, RW>(p, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin, rw);
     }
   } else {
     // The ~70 uniform parameters are read from LDS (broadcast reads) where they are used instead of
@@ -2126,10 +2221,11 @@ __global__ __launch_bounds__(kMBlock, NET ? 1 : 4) void s2d_match_rollout_kernel
     if (threadIdx.x < sizeof(MParams) / 4)
       reinterpret_cast<uint32_t*>(&p_lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&p_arg)[threadIdx.x];
     __syncthreads();
-    match_rollout_body<CTL, NET>(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin);
+    match_rollout_body<CTL, NET, RW>(p_lds, static_cast<const PTab*>(pt), sh, q, n, n_steps, actions, ro, ctl, nin, rw);
   }
 }
 
+#ifndef S2D_MATCH_REWARD_UNIT
 // Relative tables (Player.dist_from_self / angle_from_self of every agent's WorldModel): lane p scans the
 // 23 objects of its match through a broadcast-read LDS tile and writes one row of 23 values.
 __global__ __launch_bounds__(kMBlock) void s2d_match_relative_kernel(MPtrs q, int64_t n, float* __restrict__ dist,
@@ -2197,6 +2293,7 @@ __global__ __launch_bounds__(kMBlock) void s2d_match_agent_obs_kernel(MParams p,
     wave_fence();
   }
 }
+#endif
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -2222,6 +2319,8 @@ struct S2DMatchEngine {
   S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
+  bool has_rw = false;                                 // s2d_match_set_agent_reward installed the weights: the reward record may be asked for
+  MRw rw{nullptr, nullptr, 0};                         // ... the caller's weights (read at run time) and the chaser gate; out: per launch
   char* arena; size_t arena_bytes; bool owns_arena;
   S2DMatchBuffers buf; MPtrs ptrs;
 };
@@ -2235,6 +2334,14 @@ static int mfail(int code, const std::string& msg) { s2d_internal_set_error(msg.
     if (_e != hipSuccess) return mfail(S2D_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+struct MDeviceGuard {
+  int prev = -1; bool ok = false;
+  explicit MDeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess) ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess); }
+  ~MDeviceGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
+};
+static unsigned m_grid(int64_t n) { return (unsigned)((n + kEnvsPerBlock - 1) / kEnvsPerBlock); }
+
+#ifndef S2D_MATCH_REWARD_UNIT
 static size_t m_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct MLayout { size_t obj, env, reward, done, stats, ptab, total; int64_t stride; };
 static MLayout m_layout(int64_t n) {
@@ -2524,13 +2631,6 @@ S2D_API size_t s2d_match_arena_bytes(const S2DMatchConfig* cfg, int64_t n_envs) 
   return m_layout(n_envs).total;
 }
 
-struct MDeviceGuard {
-  int prev = -1; bool ok = false;
-  explicit MDeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess) ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess); }
-  ~MDeviceGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
-};
-static unsigned m_grid(int64_t n) { return (unsigned)((n + kEnvsPerBlock - 1) / kEnvsPerBlock); }
-
 S2D_API int s2d_match_reset(S2DMatchHandle h, const uint8_t* mask_dev, void* stream) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
   MDeviceGuard guard(h->device);
@@ -2647,6 +2747,7 @@ S2D_API int s2d_match_buffer_offsets(S2DMatchHandle h, int64_t* offsets, int n_o
   for (int k = 1; k < count; ++k) offsets[k] = (int64_t)(static_cast<const char*>(ptrs[k - 1]) - h->arena);
   return S2D_OK;
 }
+#endif
 
 // The five variants of the cycle kernel, in the order an engine is tried against them, and the one this engine runs.
 struct MVariant { bool stock, stock_types, sched, ill; const char* text; };
@@ -2689,8 +2790,9 @@ template <auto Kernel> static bool m_net_allow_lds(size_t dyn) {
   }
   return dyn <= limit[dev];
 }
-template <auto Kernel, class NA> static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp, const MPtrs& ptrs, int64_t n,
-                                                         int n_steps, const float* actions, const MRoll& ro, const MCtl& ctl, const NA& na) {
+template <auto Kernel, class CA, class NA>
+static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp, const MPtrs& ptrs, int64_t n, int n_steps,
+                        const float* actions, const MRoll& ro, const CA& ctl /* MCtl, or MCtlRw */, const NA& na) {
   constexpr bool SEE = std::is_same<NA, MSeeArg>::value;
   constexpr int wave_words = SEE ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
   size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
@@ -2737,6 +2839,7 @@ static int m_dispatch(S2DMatchHandle h, int n_steps, const float* actions, const
   return S2D_OK;
 }
 
+#ifndef S2D_MATCH_REWARD_UNIT
 // The caller's parameters (torch order: W1 [h1][in_dim], b1, W2 [h2][h1], b2, W3 [na][h2], b3; in_dim = 224 for the agent-row
 // network, 192 for the see network) into the engine's fragment-order copy:
 // W1's fragments [h1/16][in_dim/4][64], W2's [h2/16][h1/4][64], W3's [na16/16][h2/4][64] (rows past na zero), b1 | b2 | b3 (zero past na).
@@ -2789,9 +2892,15 @@ static S2DMatchNet m_see_as_net(const S2DMatchSeeNet& s) { return S2DMatchNet{s.
 // actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL).
 // With a network set, or a row record asked for (obs_mask), the NET instantiation runs (after the pack kernel, when there is a network).
 // With a see network set the SEE instantiation runs (agent_obs_out is then the see record, view_actions the other slots' view actions).
+// agent_reward_out != NULL (an agent reward is set: the entry point has checked): the RW instantiation of the same launch, which
+// lives in s2d_match_reward.hip -- the controller one (without a table: every slot the caller's row, or random) unless the launch
+// is a network or policy one.
+int s2d_match_internal_reward_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, const MCtlRw& ctl,
+                                     const MNetArg* na, const MPolArg* pa);
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
                     float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
-                    float* agent_obs_out = nullptr, const float* view_actions = nullptr, float* logp_out = nullptr) {
+                    float* agent_obs_out = nullptr, const float* view_actions = nullptr, float* logp_out = nullptr,
+                    float* agent_reward_out = nullptr) {
   MRoll ro{nullptr, nullptr, nullptr, nullptr};
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2802,6 +2911,7 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
   if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
     return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
   const MCtl ctl = h->has_ctl ? MCtl{h->ctl_random, h->ctl_script, actions_out} : MCtl{actions ? 0u : kAll, 0u, actions_out};
+  const MCtlRw crw{ctl, MRw{h->rw.w, agent_reward_out, h->rw.chaser_only}};
   if (h->has_see) {
     MSeeArg sa;
     std::memset(&sa, 0, sizeof sa);
@@ -2849,29 +2959,36 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       MPolArg pa;
       std::memset(&pa, 0, sizeof pa);
       pa.net = na.net; pa.tab = na.tab; pa.pol = pol;
+      if (agent_reward_out) return s2d_match_internal_reward_launch(h, n_steps, actions, ro, st, crw, nullptr, &pa);
       return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, pa);
     }
+    if (agent_reward_out) return s2d_match_internal_reward_launch(h, n_steps, actions, ro, st, crw, &na, nullptr);
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, na);
   }
+  if (agent_reward_out) return s2d_match_internal_reward_launch(h, n_steps, actions, ro, st, crw, nullptr, nullptr);
   if (h->has_ctl || actions_out) return m_dispatch<true>(h, n_steps, actions, ro, st, ctl);
   return m_dispatch<false>(h, n_steps, actions, ro, st);
 }
-// "s2d_match_rollout_kernel<" variant [", " slot kind] ">"
+// "s2d_match_rollout_kernel<" variant [", " slot kind] [", agent reward"] ">"
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
   constexpr int kKinds = 7;
   static const char* const kind_text[kKinds] = {"", ", controllers", ", network", ", two networks", ", policy network",
                                                 ", two networks, policy", ", see network"};
-  static const std::array<std::string, 5 * kKinds> names = [] {
-    std::array<std::string, 5 * kKinds> t;
+  static const std::array<std::string, 2 * 5 * kKinds> names = [] {
+    std::array<std::string, 2 * 5 * kKinds> t;
     for (int v = 0; v < 5; ++v)
-      for (int k = 0; k < kKinds; ++k) t[v * kKinds + k] = std::string("s2d_match_rollout_kernel<") + kVariant[v].text + kind_text[k] + ">";
+      for (int k = 0; k < kKinds; ++k) {
+        const std::string stem = std::string("s2d_match_rollout_kernel<") + kVariant[v].text + kind_text[k];
+        t[v * kKinds + k] = stem + ">";
+        t[(5 + v) * kKinds + k] = stem + ", agent reward>";
+      }
     return t;
   }();
   const int nets = h->role[0].set + h->role[1].set;
   const bool pol = h->role[0].pol || h->role[1].pol;
   const int kind = h->has_see ? 6 : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
-  return names[m_variant(h) * kKinds + kind].c_str();
+  return names[((h->has_rw ? 5 : 0) + m_variant(h)) * kKinds + kind].c_str();
 }
 S2D_API int s2d_match_relative(S2DMatchHandle h, float* dist_dev, float* angle_dev, void* stream) {
   if (!h || !dist_dev || !angle_dev) return mfail(S2D_EINVAL, "NULL argument");
@@ -3021,6 +3138,7 @@ S2D_API int s2d_match_set_policy_network(S2DMatchHandle h, int role, const S2DMa
 S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
   if (!h) return mfail(S2D_EINVAL, "NULL handle");
   if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+  if (h->has_rw) return mfail(S2D_EINVAL, "an agent reward is set: the see network's cycle kernel has none (clear it first)");
   if (int rc = m_net_validate("see network", m_see_as_net(*net), net->epsilon, "epsilon", true, 0u); rc != S2D_OK) return rc;
   if (!net->vis.neck || !net->vis.view_width || !net->vis.see_wait) return mfail(S2D_EINVAL, "NULL vision plane");
   if ((reinterpret_cast<uintptr_t>(net->vis.neck) | reinterpret_cast<uintptr_t>(net->vis.view_width) |
@@ -3064,6 +3182,30 @@ S2D_API int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float*
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev, nullptr,
                   logp_out_dev);
 }
+S2D_API int s2d_match_set_agent_reward(S2DMatchHandle h, const S2DMatchAgentReward* rw) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!rw) { h->has_rw = false; h->rw = MRw{nullptr, nullptr, 0}; return S2D_OK; }
+  if (!rw->weights || (reinterpret_cast<uintptr_t>(rw->weights) & 3u))
+    return mfail(S2D_EINVAL, "agent reward weights must be a non-NULL, 4-byte aligned device pointer (float[S2D_MATCH_REWARD_TERMS])");
+  if (rw->chaser_only != 0 && rw->chaser_only != 1) return mfail(S2D_EINVAL, "agent reward chaser_only must be 0 or 1");
+  if (h->has_see) return mfail(S2D_EINVAL, "a see network is set: the see network's cycle kernel has no agent reward (clear it first)");
+  h->has_rw = true; h->rw = MRw{rw->weights, nullptr, rw->chaser_only};
+  return S2D_OK;
+}
+S2D_API int s2d_match_rollout_reward(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
+                                     float* actions_out_dev, int32_t* net_index_out_dev, float* logp_out_dev, uint32_t obs_mask,
+                                     float* agent_obs_out_dev, float* agent_reward_out_dev, void* stream) {
+  if (h && h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the see network has no agent reward)");
+  if (h && agent_reward_out_dev && !h->has_rw)
+    return mfail(S2D_EINVAL, "agent_reward_out needs an agent reward (s2d_match_set_agent_reward)");
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {net_index_out_dev, "net_index_out", "int32"},
+                                             {logp_out_dev, "logp_out", "float"}, {agent_reward_out_dev, "agent_reward_out", "float"}},
+                      agent_obs_out_dev, "agent_obs_out", obs_mask))
+    return rc;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, agent_obs_out_dev, nullptr,
+                  logp_out_dev, agent_reward_out_dev);
+}
 
 // What the vision layer (s2d_see.hip, a translation unit of its own) needs of an engine beyond s2d_match_buffers(): the Philox key
 // and id words of its draws and its device.  Library-internal (hidden visibility): not part of the C ABI.
@@ -3073,3 +3215,4 @@ extern "C" int s2d_match_internal_keys(S2DMatchHandle h, uint32_t keys[4], int* 
   *device = h->device;
   return S2D_OK;
 }
+#endif

@@ -9,7 +9,10 @@ Per iteration:
      samples from its categorical distribution and records the row, the index and its log-probability.
   2. The critic stays in torch: one batched forward over the recorded [T, N, 22, 224] rows and the rows after the last cycle.
   3. The per-agent reward is the engine's left-team reward with the sign by side (+ for slots 0..10, - for 11..21); agents are
-     flattened into the env axis, [T, N * 22], for soccer2d_amd.gae.gae().
+     flattened into the env axis, [T, N * 22], for soccer2d_amd.gae.gae().  With --shaping goal=1,ball_advance=0.05,... it is
+     the cycle kernel's own per-agent shaped reward instead (rollout(..., agent_reward=True)): a launch of a
+     random policy holds next to no goals, the shaped terms are dense.  --chaser-only gives the approach and facing terms to
+     each team's chaser alone.
   4. Clipped-surrogate epochs whose logp_old is the kernel's record; sync() hands the new weights to the next launch.
   5. Every --eval-every iterations the learner plays a frozen snapshot() of an earlier self on an evaluation engine of half the
      matches (league.play_networks: learner left, snapshot right, both in-kernel), then the snapshot is renewed.
@@ -52,9 +55,21 @@ def parse(argv=None):
     ap.add_argument('--ent-coef', type=float, default=0.01)
     ap.add_argument('--eval-every', type=int, default=5, help='iterations between evaluation rounds against the snapshot')
     ap.add_argument('--eval-cycles', type=int, default=600)
+    ap.add_argument('--shaping', default=None, metavar='TERM=W,...',
+                    help='weights of the in-kernel agent reward (goal, ball_advance, approach, facing, kickable, possession); '
+                         'default: the signed team reward')
+    ap.add_argument('--chaser-only', action='store_true', help='with --shaping: approach and facing for each team\'s chaser only')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.chaser_only and not args.shaping:
+        ap.error('--chaser-only needs --shaping')
+    if args.shaping:
+        try:
+            args.shaping = {k.strip(): float(v) for k, v in (item.split('=') for item in args.shaping.split(','))}
+        except ValueError:
+            ap.error('--shaping takes TERM=WEIGHT pairs separated by commas')
+    return args
 
 
 def main(argv=None):
@@ -72,6 +87,8 @@ def main(argv=None):
     actor = MatchPolicyActor.from_module(pi, ACTION_TABLE, device=dev)
     eng = MatchEngine(N, dev, noise=True, seed=args.seed)
     eng.set_network(actor, 'all')
+    if args.shaping:
+        eng.set_agent_reward(args.shaping, args.chaser_only)
     eng.reset()
     rec = eng.alloc_rollout(T, with_obs=False)
     eval_eng = MatchEngine(max(1, N // 2), dev, noise=True, seed=args.seed + 1)
@@ -79,12 +96,15 @@ def main(argv=None):
     sign = torch.tensor([1.0] * 11 + [-1.0] * 11, device=dev)
     stats = []
     for it in range(args.iterations):
-        eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all')
+        eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all', agent_reward=bool(args.shaping))
         rows, idx, logp_old = rec['agent_obs'], rec['net_index'], rec['logp']
         with torch.no_grad():
             value = vf(rows.reshape(-1, 224)).reshape(T, N * 22)
             last_value = vf(eng.agent_observations('all').reshape(-1, 224)).reshape(N * 22)
-        reward = (rec['reward'][:, :, None] * sign).reshape(T, N * 22).contiguous()
+        if args.shaping:
+            reward = rec['agent_reward'].reshape(T, N * 22)
+        else:
+            reward = (rec['reward'][:, :, None] * sign).reshape(T, N * 22).contiguous()
         done = rec['done'][:, :, None].expand(T, N, 22).reshape(T, N * 22).contiguous()
         adv, ret = gae(reward, done, value.contiguous(), last_value.contiguous(), args.gamma, args.lam)
         obs_b, act_b = rows.reshape(-1, 224), idx.reshape(-1).long()

@@ -167,6 +167,12 @@ class S2DMatchSeeNet(C.Structure):          # include/s2d_match.h: see network
                 ('prm', S2DVisionParams), ('vis', S2DMatchVision)]
 
 
+class S2DMatchAgentReward(C.Structure):     # include/s2d_match.h: Agent reward
+    _fields_ = [('weights', C.c_void_p), ('chaser_only', C.c_int32)]
+
+
+REWARD_TERMS = ('goal', 'ball_advance', 'approach', 'facing', 'kickable', 'possession')   # S2D_MATCH_REWARD_TERMS, in term order
+
 MATCH_NET_WIDTHS = (16, 32, 48, 64)
 MATCH_NET_MAX_ACTIONS = 64
 MATCH_ST_NET = 7                           # S2D_MATCH_ST_NET: Philox stream of the network slots' exploration
@@ -208,6 +214,9 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_policy_network', C.c_int, (C.c_void_p, C.c_int, C.c_void_p)),
     ('s2d_match_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_agent_reward', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_reward', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)),
 )
 
 
@@ -244,6 +253,20 @@ def controller_codes(spec):
         if len(codes) != MATCH_PLAYERS:
             raise ValueError(f"controller spec needs {MATCH_PLAYERS} codes, got {len(codes)}")
     return bytes(codes)
+
+
+def reward_weights(weights):
+    """the six agent-reward weights (floats, in REWARD_TERMS order) from a dict by term name (missing terms are 0) or a sequence
+    of six"""
+    if isinstance(weights, dict):
+        extra = set(weights) - set(REWARD_TERMS)
+        if extra:
+            raise ValueError(f"unknown reward terms {sorted(extra)} (the terms: {', '.join(REWARD_TERMS)})")
+        return [float(weights.get(k, 0.0)) for k in REWARD_TERMS]
+    vals = [float(v) for v in weights]
+    if len(vals) != len(REWARD_TERMS):
+        raise ValueError(f"reward weights need {len(REWARD_TERMS)} values ({', '.join(REWARD_TERMS)}), got {len(vals)}")
+    return vals
 
 
 def agent_slot_mask(slots):

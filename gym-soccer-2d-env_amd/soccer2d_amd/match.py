@@ -80,6 +80,7 @@ class MatchEngine:
         self.network, self.network_mask = None, 0       # no network slots (set_network)
         self.opponent_network, self.opponent_mask = None, 0   # no second network (set_opponent_network)
         self.vision = None                              # no vision layer (enable_vision)
+        self.agent_reward_weights = None                # no agent reward (set_agent_reward)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.device = torch.device(device)
@@ -204,6 +205,22 @@ class MatchEngine:
         self._set_role(M.MATCH_ROLE_OPPONENT, actor, mask)
         self.opponent_network, self.opponent_mask = actor, mask
 
+    def set_agent_reward(self, weights, chaser_only=False):
+        """Agent reward (include/s2d_match.h): the per-agent shaped reward the cycle kernel computes for rollout(...,
+        agent_reward=True).  `weights`: a dict by term name (_capi_match.REWARD_TERMS: goal, ball_advance, approach, facing,
+        kickable, possession; missing terms are 0) or a sequence of six; None clears.  chaser_only: the individual terms
+        approach and facing go to each team's chaser only (the scripted team's rule 5).  The weights live in
+        `agent_reward_weights`, a float32 [6] device tensor the kernel reads when it runs: write it in place to anneal (a
+        captured graph replays with what it holds).  Refused while a see network is set."""
+        if weights is None:
+            _capi.check(self.lib, self.lib.s2d_match_set_agent_reward(self._h, None), 's2d_match_set_agent_reward')
+            self.agent_reward_weights = None
+            return
+        w = torch.tensor(M.reward_weights(weights), dtype=torch.float32, device=self.device)
+        rw = M.S2DMatchAgentReward(w.data_ptr(), int(bool(chaser_only)))
+        _capi.check(self.lib, self.lib.s2d_match_set_agent_reward(self._h, C.byref(rw)), 's2d_match_set_agent_reward')
+        self.agent_reward_weights = w
+
     def _record(self, out, name, T, tail_shape, dtype):
         """out[name], a rollout record [T, *tail_shape]: allocated when absent, else checked (dtype, contiguous, at least T
         steps, the tail)"""
@@ -258,7 +275,7 @@ class MatchEngine:
         return out
 
     def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None,
-                see_obs=None, view_actions=None, logp=False):
+                see_obs=None, view_actions=None, logp=False, agent_reward=False):
         """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
         each cycle, before the engine's own gating (caller slots: the caller's row).  net_index: out['net_index'] int32
         [T, N, 22] receives each network slot's index (-1 for the other slots).  agent_obs = 'all' | 'left' | 'right' | a mask:
@@ -268,7 +285,9 @@ class MatchEngine:
         beside its slots; without a network, as a record-only see network for this call.  view_actions float32 [T, N, 22, 2] =
         (TurnNeck moment, ChangeView code) of the slots the see network does not play (None: they neither turn nor change).
         logp: out['logp'] float32 [T, N, 22] receives the log-probability of the index each policy slot took (MatchPolicyActor;
-        0 for every other slot, Q-network slots included): s2d_match_rollout_policy, with net_index and agent_obs as above."""
+        0 for every other slot, Q-network slots included): s2d_match_rollout_policy, with net_index and agent_obs as above.
+        agent_reward: out['agent_reward'] float32 [T, N, 22] receives every agent's shaped reward of each cycle
+        (set_agent_reward first; s2d_match_rollout_reward); it composes with every record above but the see ones."""
         T = int(n_steps)
         keep, ptr = self._actions(actions, T)
         if out is None:
@@ -283,7 +302,21 @@ class MatchEngine:
         n, st = self.num_envs, self._stream()
         rec = self._record(out, 'actions', T, (n, M.MATCH_PLAYERS, 3), torch.float32) if record_actions else None
         va = None
-        if see_obs is not None or view_actions is not None or (net_index and self._see_network_set()):
+        if agent_reward:
+            if see_obs is not None or view_actions is not None or self._see_network_set():
+                raise ValueError("agent_reward is not offered with the see network's rollout (its cycle kernel has none)")
+            if self.agent_reward_weights is None:
+                raise ValueError("agent_reward needs set_agent_reward() first")
+            idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
+            lp = self._record(out, 'logp', T, (n, M.MATCH_PLAYERS), torch.float32) if logp else None
+            obs, mask = None, 0
+            if agent_obs is not None:
+                mask = M.agent_slot_mask(agent_obs)
+                obs = self._record(out, 'agent_obs', T, (n, bin(mask).count('1'), M.AGENT_OBS_DIM), torch.float32)
+            rwd = self._record(out, 'agent_reward', T, (n, M.MATCH_PLAYERS), torch.float32)
+            _capi.check(self.lib, self.lib.s2d_match_rollout_reward(self._h, T, ptr, C.byref(ro), _ptr(rec), _ptr(idx), _ptr(lp), mask,
+                                                                     _ptr(obs), _ptr(rwd), st), 's2d_match_rollout_reward')
+        elif see_obs is not None or view_actions is not None or (net_index and self._see_network_set()):
             if agent_obs is not None:
                 raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
             va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions)
@@ -507,6 +540,10 @@ class Soccer2DMatchVecEnv:
     With opponent = a see actor (MatchQNetActor(obs='see')) the right team plays on its own see rows and turns its necks and
     changes its view as the actor's table says; the cycle kernel then steps the vision state of all 22 players itself (the left
     team's from the caller's TurnNeck / ChangeView words), so a step is one launch plus see.  A see actor needs obs='see'.
+
+    reward = 'goals' (the default: the rewards above) | a dict by term name | six weights: the shaped per-agent reward the
+    cycle kernel computes (MatchEngine.set_agent_reward; chaser_only as there) in the place of the signed team reward, [N, 22]
+    or [N, 11], for obs 'agent' and 'see' (not while a see actor plays the opponent; obs='state' has no per-agent reward).
     """
 
     @staticmethod
@@ -528,8 +565,18 @@ class Soccer2DMatchVecEnv:
             ospace = Box(low=-200.0, high=200.0, shape=(23, 5), dtype=np.float32)
         return ospace, Box(low=-180.0, high=180.0, shape=(agents, 3), dtype=np.float32)
 
-    def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, **kwargs):
+    def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, reward='goals', chaser_only=False,
+                 **kwargs):
         self.observation_space, self.action_space = self.spaces(opponent, obs)
+        shaped = not (isinstance(reward, str) and reward == 'goals')
+        if shaped:
+            if isinstance(reward, str):
+                raise ValueError(f"reward must be 'goals', a dict by term name or six weights, got {reward!r}")
+            if obs == 'state':
+                raise ValueError("a shaped reward is per agent: it needs obs='agent' or obs='see'")
+            if _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'see':
+                raise ValueError("a shaped reward is not offered while a see network plays the opponent")
+            M.reward_weights(reward)                     # (a bad spec fails before the engine exists)
         if vision is not None and obs != 'see':
             raise ValueError("vision parameters need obs='see'")
         self.engine = MatchEngine(num_envs, device, **kwargs)
@@ -562,6 +609,9 @@ class Soccer2DMatchVecEnv:
             self._aobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
             # reward sign per agent: the left team's reward for slots 0..10, its negative for 11..21
             self._rsign = torch.tensor([1.0] * 11 + ([-1.0] * 11 if opponent is None else []), dtype=torch.float32, device=self.device)
+        self._shaped = shaped
+        if shaped:
+            self.engine.set_agent_reward(reward, chaser_only)
 
     def _obs(self):
         e = self.engine
@@ -601,12 +651,14 @@ class Soccer2DMatchVecEnv:
         if self._see_opponent:                            # one launch: the body cycle and the vision step of all 22 players
             self.engine.rollout(1, actions=a, out=self._ro, view_actions=self._view.unsqueeze(0))
         else:
-            self.engine.rollout(1, actions=a, out=self._ro)
+            self.engine.rollout(1, actions=a, out=self._ro, agent_reward=self._shaped)
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,
                 'right_team_score': e.score_right, 'cycle': e.cycle, 'nearest_left': e.nearest_left, 'nearest_right': e.nearest_right}
         if self.obs_kind == 'see' and not self._see_opponent:
             e.vision_step(self._view, done=True)
+        if self._shaped:                                  # the cycle kernel's per-agent reward, the controlled agents' columns
+            return self._obs(), self._ro['agent_reward'][0, :, :self._rsign.numel()], e.done, info
         if self.obs_kind in ('agent', 'see'):
             return self._obs(), e.reward_left[:, None] * self._rsign, e.done, info
         return self._ro['obs'][0, :, :23], e.reward_left, e.done, info

@@ -457,6 +457,57 @@ int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float *actions
                              float *actions_out_dev, int32_t *net_index_out_dev, float *logp_out_dev,
                              uint32_t obs_mask, float *agent_obs_out_dev, void *stream);
 
+/* Agent reward: an opt-in per-agent shaped reward, computed inside the cycle kernel where it writes its records.  The engine's own
+ * reward stays reward_left (+1 / -1 on a goal); this record is what a learner of sparse-goal self-play can learn from.  With no
+ * agent reward set an engine launches what it launched before, under the same names, and every record is bitwise what it was.
+ * For a cycle, S is the match's start-of-cycle state and S' the state the cycle leaves -- after the auto-reset, if the cycle
+ * ended the match: what s2d_match_buffers shows.  For agent l: sgn = +1 for slots 0..10, -1 for 11..21; row(S) is the agent's
+ * S2D_AGENT_OBS_DIM-word row of S as s2d_match_agent_obs defines it (the same device functions: the words below are bitwise the
+ * row's words).
+ *   live    mode(S) == PlayOn && mode(S') == PlayOn: a cycle that starts or ends in a restart, a halted mode, or a finished
+ *           (and reset) match is never live.
+ *   active  card(S) < S2D_CARD_RED && card(S') < S2D_CARD_RED.
+ *   chaser(S)  the scripted team's rule-5 chaser of the agent's team in S ("Controllers" above): its nearest non-goalie to the
+ *           ball by sq2, ties to the lower index, sent-off players excluded.
+ *   gate    active && (chaser_only ? chaser(S) == l : true).
+ * Terms, in this order (team terms are the same for the 11 agents of a side; individual ones are the agent's own):
+ *   0 goal          team        sgn * reward_left(S')
+ *   1 ball_advance  team        live ? row(S')[ball.x] - row(S)[ball.x] : 0     own frame: positive toward the opponents' goal
+ *   2 approach      individual  live && gate ? row(S)[ball.dist_from_self] - row(S')[ball.dist_from_self] : 0
+ *   3 facing        individual  live && gate ? (|row(S)[ball.bearing]| - |row(S')[ball.bearing]|) * (float)(1.0 / 180.0) : 0
+ *   4 kickable      individual  mode(S') == PlayOn && active ? row(S')[self.is_kickable] : 0
+ *   5 possession    team        mode(S') == PlayOn ? row(S')[ball.last_touch] : 0     the side word: +1 ours, -1 theirs, 0 none
+ * reward = acc after: acc = +0; for k ascending: acc = fmaf(w[k], term[k], acc).  Every "0" above is +0.0f.  Terms 2 + 3 with unit
+ * weights are the reference's ReachBall reward (reach_ball_env.py:130-134), per agent.
+ * w = weights: a device float[S2D_MATCH_REWARD_TERMS], read when the kernel runs (once, at its start), like epsilon: a captured
+ * graph replays with what the buffer holds, and a curriculum anneals it in place.  The engine keeps the pointer, not a copy.
+ * Mirror property: for a mirrored pair of (S, S') (teams swapped, positions and velocities negated, bodies turned by 180, sides
+ * swapped, reward_left negated) the mirrored agents' rewards are bitwise equal; between the two sides of one match the team terms
+ * 0, 1 and 5 are exact negations of each other.
+ * Lanes past the 22 agents and matches past N store nothing.
+ * Not offered: an agent reward with the see network (its cycle kernel is out of scope: setting either while the other is set is
+ * S2D_EINVAL); per-agent weights; terms that need more of the row than the words above.
+ * s2d_match_kernel_name gains the suffix ", agent reward>" in place of ">" while an agent reward is set (the instantiation a
+ * launch takes has the record only when s2d_match_rollout_reward is given one).
+ * rw == NULL clears.  Errors (S2D_EINVAL, the engine unchanged): NULL or unaligned weights; chaser_only outside {0, 1}; a see
+ * network is set (and s2d_match_set_see_network refuses while an agent reward is set). */
+#define S2D_MATCH_REWARD_TERMS 6
+typedef struct S2DMatchAgentReward {
+  const float *weights;   /* device float[S2D_MATCH_REWARD_TERMS], 4-byte aligned */
+  int32_t chaser_only;    /* 0 | 1 */
+} S2DMatchAgentReward;
+int s2d_match_set_agent_reward(S2DMatchHandle h, const S2DMatchAgentReward *rw);
+/* s2d_match_rollout_policy plus
+ *   agent_reward_out_dev  float[T][N][22] (4-byte aligned, or NULL): the agent reward of every agent for every cycle.
+ * With agent_reward_out_dev == NULL it is s2d_match_rollout_policy.  With a record the launch takes the ", agent reward"
+ * instantiation of the kernel it would have taken: the controller one (without a table: every slot the caller's row, or random,
+ * as for the action record), the network one or the policy one; every other record and the final state are bitwise those of the
+ * launch without it.
+ * Errors: as s2d_match_rollout_policy; a record while no agent reward is set; an unaligned record. */
+int s2d_match_rollout_reward(S2DMatchHandle h, int n_steps, const float *actions_dev, const S2DMatchRollout *out,
+                             float *actions_out_dev, int32_t *net_index_out_dev, float *logp_out_dev,
+                             uint32_t obs_mask, float *agent_obs_out_dev, float *agent_reward_out_dev, void *stream);
+
 /* Vision: an opt-in layer beside the engine -- view cone, neck, see-message quantisation, see timing.  Restated from the published
  * behaviour of rcssserver's synchronous see mode; like every 11v11 rule it is this project's own restatement: PARITY TO RCSSSERVER
  * UNPINNED.  The fp32 words below are the contract (the device equals tests/see_ref.c bit for bit).  The engine handle stores
