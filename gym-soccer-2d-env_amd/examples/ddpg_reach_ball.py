@@ -68,8 +68,9 @@ class DeviceReplay:
 
 class DeviceDDPG:
     def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
-                 learning_starts=2, seed=0, net_arch=None, activation='relu'):
+                 learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1):
         torch.manual_seed(seed)
+        self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.env, self.dev = env, env.device
         n_obs, self.n_act = env.observation_space.shape[0], env.action_space.shape[0]
         self.general = net_arch is not None or activation != 'relu'      # an actor only the general fused actor takes
@@ -90,11 +91,18 @@ class DeviceDDPG:
             a = (a + self.sigma * torch.randn_like(a)).clamp(-1, 1)
         return a
 
-    def optimise(self, n_updates):
+    def optimise(self, n_updates, fused=False):
+        """fused: batches of the fused path's soccer2d_amd.replay.DeviceReplay (reward = the n-step return, discount = gamma^k
+        or 0) instead of the per-step buffer's (obs, action, reward, next_obs, term)"""
         for _g in range(n_updates):
-            o, a, r, no, t = self.rb.sample(self.batch)
+            if fused:
+                b = self.frb.sample(self.batch, out=self.fbatch)
+                o, a, r, no, disc = b['obs'], b['action'], b['reward'], b['next_obs'], b['discount']
+            else:
+                o, a, r, no, t = self.rb.sample(self.batch)
+                disc = self.gamma * (1 - t)
             with torch.no_grad():
-                tgt = r + self.gamma * (1 - t) * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
+                tgt = r + disc * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
             loss_q = nn.functional.mse_loss(self.q(torch.cat([o, a], 1)).squeeze(1), tgt)
             self.opt_q.zero_grad(set_to_none=True)
             loss_q.backward()
@@ -146,17 +154,31 @@ class DeviceDDPG:
             print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
+        rb = self.fused_replay(T, eng.obs.shape[-1])
         for _ in range((vec_steps + T - 1) // T):
             self.actor.epsilon = 1.0 if self.launches < self.learning_starts else 0.0
             obs0 = eng.obs.clone()                               # the observation the first action is chosen from
             self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
-            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
-            self._store(obs_t, rec['action'], rec['obs'], rec['reward'], rec['done'], rec['result'], rec['terminal_obs'])
-            self.launches += 1
-            if self.rb.full or self.rb.pos >= self.batch:
-                self.optimise(self.grad_steps * T)
-                self.actor.sync()                                # the next launch acts with the new weights
+            rb.push(rec, obs0)                                   # T x N n-step transitions, Timeouts bootstrap (one launch)
+            self.after_fused_launch(T)
         self.obs = eng.obs.clone()
+
+    def fused_replay(self, T, n_obs):
+        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay), made at the first launch: it holds at
+        least one record"""
+        from soccer2d_amd.replay import DeviceReplay as FusedReplay
+        if not hasattr(self, 'frb'):
+            self.frb = FusedReplay(max(self.buffer, T * self.env.num_envs), n_obs, self.n_act, torch.float32, self.dev,
+                                   n_step=self.n_step, gamma=self.gamma, seed=self.seed)
+            self.fbatch, self.stored = self.frb.alloc_batch(self.batch), 0
+        return self.frb
+
+    def after_fused_launch(self, T):
+        self.launches += 1
+        self.stored += T * self.env.num_envs
+        if self.stored >= self.batch:
+            self.optimise(self.grad_steps * T, fused=True)
+            self.actor.sync()                                    # the next launch acts with the new weights
 
 
 def test(env, model, vec_steps):
@@ -185,12 +207,13 @@ def main():
     ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
                     help="the actor's hidden widths, e.g. 16,8 or 400,300 (1 to 5 multiples of 4 up to 400; default: 64,64)")
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
+    ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
-    model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation)
+    model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -11,7 +11,9 @@ feeds N transitions.
 
 --fused-actor T collects T x N transitions per launch: the engine evaluates the learner's own network in-kernel
 (Engine.rollout_qnet with a soccer2d_amd.actor.QNetActor), epsilon-greedy per env; the actor's packed weights are refreshed
-with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal observations.
+with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal observations.  The
+record goes into a soccer2d_amd.replay.DeviceReplay in one launch and a batch comes out in one; --n-step K stores
+K-step returns (targets R + discount * max Q_target(next)).
 """
 import argparse
 import copy
@@ -72,8 +74,9 @@ class DeviceReplay:
 
 class DeviceDQN:
     def __init__(self, env, lr=1e-3, gamma=0.99, buffer=1 << 20, batch=4096, target_every=50, grad_steps=4,
-                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu'):
+                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu', n_step=1):
         torch.manual_seed(seed)
+        self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.env, self.dev = env, env.device
         self.n_act = env.action_space.n
         self.general = net_arch is not None or activation != 'relu'      # a network only the general fused actor takes
@@ -135,6 +138,39 @@ class DeviceDQN:
             nn.utils.clip_grad_norm_(self.q.parameters(), 10.0)
             self.opt.step()
 
+    def fused_replay(self, T, n_obs):
+        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay), made at the first launch: it holds at
+        least one record"""
+        from soccer2d_amd.replay import DeviceReplay as FusedReplay
+        if not hasattr(self, 'frb'):
+            self.frb = FusedReplay(max(self.buffer, T * self.env.num_envs), n_obs, 1, torch.int32, self.dev, n_step=self.n_step,
+                                   gamma=self.gamma, seed=self.seed)
+            self.fbatch, self.stored = self.frb.alloc_batch(self.batch), 0
+        return self.frb
+
+    def optimise_fused(self, n_updates):
+        """optimise() on batches of the fused replay buffer: reward is the n-step return, discount gamma^k or 0"""
+        for _g in range(n_updates):
+            b = self.frb.sample(self.batch, out=self.fbatch)
+            with torch.no_grad():
+                tgt = b['reward'] + b['discount'] * self.q_target(b['next_obs']).max(dim=1).values
+            loss = nn.functional.smooth_l1_loss(self.q(b['obs']).gather(1, b['action'].long()).squeeze(1), tgt)
+            self.opt.zero_grad(set_to_none=True)
+            loss.backward()
+            nn.utils.clip_grad_norm_(self.q.parameters(), 10.0)
+            self.opt.step()
+
+    def after_fused_launch(self, T):
+        """target-network schedule, then grad_steps updates per collected vector step and the actor's new weights"""
+        for _t in range(T):
+            self.steps += 1
+            if self.steps % self.target_every == 0:
+                self.q_target.load_state_dict(self.q.state_dict())
+        self.stored += T * self.env.num_envs
+        if self.stored >= self.batch:
+            self.optimise_fused(self.grad_steps * T)
+            self.actor.sync()                                    # the next launch acts with the new weights
+
     def learn_fused(self, vec_steps, T, on_result=None):
         """The same DQN, experience collected T steps per launch by the fused actor (the learner's own network in-kernel):
         per launch T x N transitions into the replay buffer, then grad_steps updates per collected vector step, then sync()."""
@@ -153,25 +189,15 @@ class DeviceDQN:
             print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         eng, rec = self.env.engine, self.rec
+        rb = self.fused_replay(T, eng.obs.shape[-1])
         for _ in range((vec_steps + T - 1) // T):
             self.actor.epsilon = self.epsilon()
             obs0 = eng.obs.clone()                               # the observation the first action is chosen from
             self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
-            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
-            done = rec['done'].bool()
-            next_obs = torch.where(done.unsqueeze(-1), rec['terminal_obs'], rec['obs'])   # bootstrap through Timeouts
-            term = ((rec['result'] == 1) | (rec['result'] == 2)).float()                 # Goal / Out are true terminations
-            self.rb.add(obs_t.reshape(-1, obs_t.shape[-1]), rec['action'].reshape(-1).long(), rec['reward'].reshape(-1),
-                        next_obs.reshape(-1, next_obs.shape[-1]), term.reshape(-1))
+            rb.push(rec, obs0)                                   # T x N n-step transitions, Timeouts bootstrap (one launch)
             if on_result is not None:
                 on_result(rec['result'].reshape(-1))
-            for _t in range(T):
-                self.steps += 1
-                if self.steps % self.target_every == 0:
-                    self.q_target.load_state_dict(self.q.state_dict())
-            if self.rb.full or self.rb.pos >= self.batch:
-                self.optimise(self.grad_steps * T)
-                self.actor.sync()                                # the next launch acts with the new weights
+            self.after_fused_launch(T)
         self.obs = eng.obs.clone()
 
 
@@ -207,11 +233,12 @@ def main():
     ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
                     help='hidden widths, e.g. 128,64,32,16 (1 to 5 multiples of 4 up to 400; default: 64,64)')
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
+    ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
-    model = DeviceDQN(env, net_arch=net_arch, activation=args.activation)
+    model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step)
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

@@ -12,8 +12,9 @@ learners of dqn_reach_ball.py / ddpg_reach_ball.py.
 --fused-actor T collects T x N transitions per launch: the env evaluates the learner's own network in the rollout kernel
 (GoToCenterVecEnv.rollout_qnet / rollout_actor with a soccer2d_amd.gtc_actor.GtcQNetActor / GtcDeterministicActor); the actor's
 packed weights are refreshed with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal
-observations.  --net-arch / --activation: the Optuna grids of best_python_sample_soccer_env*.py (1 to 5 widths, multiples of 4 up
-to 400; relu, tanh or sigmoid).
+observations; the record goes into a soccer2d_amd.replay.DeviceReplay in one launch (--n-step K: K-step returns).
+--net-arch / --activation: the Optuna grids of best_python_sample_soccer_env*.py (1 to 5 widths, multiples of 4 up to 400; relu,
+tanh or sigmoid).
 """
 import argparse
 import copy
@@ -41,23 +42,13 @@ class GtcDQN(DeviceDQN):
             print(f'fused actor: {type(self.actor).__name__} {self.actor.hidden} {self.actor.activation}')
             self.rec = None
         env = self.env
+        rb = self.fused_replay(T, 4)
         for _ in range((vec_steps + T - 1) // T):
             self.actor.epsilon = self.epsilon()
             obs0 = env.obs.clone()                                 # the observation the first action is chosen from
             rec = self.rec = env.rollout_qnet(T, self.actor, terminal_obs=True, out=self.rec)
-            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
-            done = rec['done'].bool()
-            next_obs = torch.where(done.unsqueeze(-1), rec['terminal_obs'], rec['obs'])   # bootstrap through Timeouts
-            term = ((rec['result'] == 1) | (rec['result'] == 2)).float()                 # Goal / Out are true terminations
-            self.rb.add(obs_t.reshape(-1, 4), rec['action'].reshape(-1).long(), rec['reward'].reshape(-1), next_obs.reshape(-1, 4),
-                        term.reshape(-1))
-            for _t in range(T):
-                self.steps += 1
-                if self.steps % self.target_every == 0:
-                    self.q_target.load_state_dict(self.q.state_dict())
-            if self.rb.full or self.rb.pos >= self.batch:
-                self.optimise(self.grad_steps * T)
-                self.actor.sync()                                  # the next launch acts with the new weights
+            rb.push(rec, obs0)                                     # T x N n-step transitions, Timeouts bootstrap (one launch)
+            self.after_fused_launch(T)
         self.obs = env.obs.clone()
 
 
@@ -77,16 +68,13 @@ class GtcDDPG(DeviceDDPG):
             print(f'fused actor: {type(self.actor).__name__} {self.actor.hidden} {self.actor.activation}')
             self.rec = None
         env = self.env
+        rb = self.fused_replay(T, 4)
         for _ in range((vec_steps + T - 1) // T):
             self.actor.epsilon = 1.0 if self.launches < self.learning_starts else 0.0
             obs0 = env.obs.clone()
             rec = self.rec = env.rollout_actor(T, self.actor, terminal_obs=True, out=self.rec)
-            obs_t = torch.cat([obs0[None], rec['obs'][:-1]])
-            self._store(obs_t, rec['action'], rec['obs'], rec['reward'], rec['done'], rec['result'], rec['terminal_obs'])
-            self.launches += 1
-            if self.rb.full or self.rb.pos >= self.batch:
-                self.optimise(self.grad_steps * T)
-                self.actor.sync()
+            rb.push(rec, obs0)
+            self.after_fused_launch(T)
         self.obs = env.obs.clone()
 
 
@@ -106,6 +94,7 @@ def main():
     ap.add_argument('--net-arch', default=None, metavar='W1,W2,...',
                     help='hidden widths of the Q-network / the actor (1 to 5 multiples of 4 up to 400; default: 64,64 / 16,8)')
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
+    ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(continuous=args.continuous, turn=args.turn, use_turn=args.useturn,
@@ -113,9 +102,9 @@ def main():
     env = GoToCenterVecEnv(args.envs, args.device, **kw)
     test_env = GoToCenterVecEnv(args.envs, args.device, seed=1234, **kw)
     if args.continuous:
-        model, test = GtcDDPG(env, net_arch=net_arch, activation=args.activation), test_ddpg
+        model, test = GtcDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step), test_ddpg
     else:
-        model, test = GtcDQN(env, net_arch=net_arch, activation=args.activation), test_dqn
+        model, test = GtcDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step), test_dqn
     print('untrained:', test(test_env, model, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

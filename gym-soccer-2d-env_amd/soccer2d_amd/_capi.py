@@ -134,6 +134,12 @@ class S2DWideNet(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
+class S2DReplayRing(C.Structure):
+    """the caller-owned ring of s2d_replay_push / s2d_replay_sample (capacity in transitions; device pointers of the five arrays)"""
+    _fields_ = [('capacity', C.c_int64), ('obs', C.c_void_p), ('next_obs', C.c_void_p), ('action', C.c_void_p),
+                ('reward', C.c_void_p), ('discount', C.c_void_p)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -172,6 +178,10 @@ PROTOTYPES = (
                                      C.c_void_p)),
     ('s2d_gae', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_replay_push', C.c_int, (C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(S2DReplayRing), C.c_void_p, C.c_void_p)),
+    ('s2d_replay_sample', C.c_int, (C.c_int64, C.c_int, C.c_int, C.POINTER(S2DReplayRing), C.c_void_p, C.c_uint64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

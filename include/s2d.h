@@ -23,6 +23,9 @@
  *                              grids of best_python_sample_soccer_env*.py (up to five layers of 400, Sigmoid)
  *   s2d_rollout_policy         PPO / A2C: sampling from the policy's distribution + log_prob inside collect_rollouts
  *   s2d_gae                    RolloutBuffer.compute_returns_and_advantage
+ *   s2d_replay_push            ReplayBuffer.add with handle_timeout_termination, for a whole [T][N] record at once, in the place
+ *                              of the per-step add of OffPolicyAlgorithm.collect_rollouts (n-step returns formed on the way in)
+ *   s2d_replay_sample          ReplayBuffer.sample (uniform, with replacement)
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -428,6 +431,46 @@ int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet *net, const 
  * NULL or misaligned arrays. */
 int s2d_gae(int n_steps, int64_t n_envs, const float *reward, const uint8_t *done, const float *value, const float *last_value,
             const uint8_t *result, const float *terminal_value, float gamma, float lam, float *advantage, float *ret, void *stream);
+/* ---- device replay buffer (off-policy counterpart of s2d_gae) ------------------------------------------------------------
+ * ENGINE-INDEPENDENT like s2d_gae: no engine handle, raw device pointers, any stream of the current device; it assumes nothing
+ * of reach-ball beyond the S2D_RESULT_TIMEOUT label (GoToCenter and the 11v11 records, agents flattened into N, share it).
+ * The ring is caller-owned: `capacity` transitions, 1 <= capacity < 2^31; obs / next_obs = 32-bit words [capacity][D] and
+ * action = 32-bit words [capacity][AW] (int32 or float), all copied raw (NaN payloads survive); reward / discount = float
+ * [capacity].  D in [1, 1024], AW in [1, 8].  The learner's target is reward + discount * bootstrap(next_obs).
+ * `cursor` = device uint64[4] = {pos, size, pushes, samples}, 8-byte aligned, zero at start; both calls read it WHEN THE
+ * KERNEL RUNS, so collect -> push -> sample can sit in one captured graph. */
+typedef struct S2DReplayRing {
+  int64_t capacity;
+  void *obs, *next_obs; /* uint32[capacity][D] */
+  void *action;         /* uint32[capacity][AW] */
+  float *reward, *discount;
+} S2DReplayRing;
+#define S2D_REPLAY_STREAM 11 /* Philox stream id of the sample indices (no engine draw uses it) */
+/* Push a time-major record as n-step transitions, one launch.  first_obs[N][D] = the observation action 0 was chosen from;
+ * obs[T][N][D] = what step t returned (post-reset where done); terminal_obs[T][N][D] is read only where done; action[T][N][AW];
+ * reward[T][N]; done[T][N] (uint8); result[T][N] (uint8, S2D_RESULT_*) or NULL = every done is a termination.  Requires
+ * T * N <= capacity and n_step >= 1.  For every (t, i), fp32, in exactly this order:
+ *   R = reward[t][i]; g = gamma; s = t;
+ *   while (!done[s][i] && s + 1 < T && s + 1 - t < n_step) { s += 1; R = fmaf(g, reward[s][i], R); g = g * gamma; }
+ *   done[s][i]:  next = terminal_obs[s][i];  discount = (result && result[s][i] == S2D_RESULT_TIMEOUT) ? g : +0
+ *   else:        next = obs[s][i];           discount = g
+ * and slot (pos + t * N + i) mod capacity, pos = cursor[0], receives obs_t = (t == 0 ? first_obs[i] : obs[t - 1][i]), next,
+ * action[t][i], R, discount.  A horizon cut by the record's end is a shorter, still valid transition.  A one-thread kernel on
+ * the same stream then sets pos = (pos + T * N) mod capacity, size = min(size + T * N, capacity), pushes += 1.
+ * S2D_EINVAL without a launch: a range above violated or T * N > capacity, non-finite gamma, NULL (result excepted) or
+ * misaligned pointers (4 bytes; 16 bytes for the [.][D] arrays when D % 4 == 0; 8 bytes for the cursor), ring arrays or the
+ * cursor overlapping the record or each other. */
+int s2d_replay_push(int n_steps, int64_t n_envs, int obs_dim, int action_words, int n_step, float gamma, const void *first_obs,
+                    const void *obs, const void *terminal_obs, const void *action, const float *reward, const uint8_t *done,
+                    const uint8_t *result, const S2DReplayRing *ring, uint64_t *cursor, void *stream);
+/* Sample a batch, one launch.  size = cursor[1] and samples = cursor[3] are read when the kernel runs.  Element b takes word
+ * b & 3 of Philox4x32-10 at counter {b >> 2, samples_lo, samples_hi, S2D_REPLAY_STREAM << 16} with key `seed`, and
+ * index = ((uint64)w * size) >> 32 (uniform with replacement); the slot's five fields are copied to b_obs[B][D], b_next[B][D],
+ * b_action[B][AW], b_reward[B], b_discount[B], and b_index[B] (int32) <- index.  With size == 0: index -1, zero rows, reward
+ * and discount +0.  A one-thread kernel then sets samples += 1.  B in [1, 2^31 - 1].  S2D_EINVAL without a launch as above
+ * (the batch arrays must not overlap the ring, the cursor or each other). */
+int s2d_replay_sample(int64_t batch, int obs_dim, int action_words, const S2DReplayRing *ring, uint64_t *cursor, uint64_t seed,
+                      void *b_obs, void *b_next, void *b_action, float *b_reward, float *b_discount, int32_t *b_index, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
