@@ -68,9 +68,10 @@ class DeviceReplay:
 
 class DeviceDDPG:
     def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
-                 learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1):
+                 learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0, per_beta=0.4):
         torch.manual_seed(seed)
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
+        self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
         self.env, self.dev = env, env.device
         n_obs, self.n_act = env.observation_space.shape[0], env.action_space.shape[0]
         self.general = net_arch is not None or activation != 'relu'      # an actor only the general fused actor takes
@@ -93,7 +94,10 @@ class DeviceDDPG:
 
     def optimise(self, n_updates, fused=False):
         """fused: batches of the fused path's soccer2d_amd.replay.DeviceReplay (reward = the n-step return, discount = gamma^k
-        or 0) instead of the per-step buffer's (obs, action, reward, next_obs, term)"""
+        or 0) instead of the per-step buffer's (obs, action, reward, next_obs, term).  With --per-alpha that buffer is a
+        PrioritizedReplay: the critic's loss carries the importance weights and the batch's slots get (|TD error| + 1e-6) ** alpha
+        as their new priority."""
+        per = fused and self.per_alpha > 0
         for _g in range(n_updates):
             if fused:
                 b = self.frb.sample(self.batch, out=self.fbatch)
@@ -103,7 +107,13 @@ class DeviceDDPG:
                 disc = self.gamma * (1 - t)
             with torch.no_grad():
                 tgt = r + disc * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
-            loss_q = nn.functional.mse_loss(self.q(torch.cat([o, a], 1)).squeeze(1), tgt)
+            q_sa = self.q(torch.cat([o, a], 1)).squeeze(1)
+            if per:
+                td = q_sa - tgt
+                loss_q = (self.frb.weights(b, self.per_beta) * td * td).mean()
+                self.frb.update_priorities(b['index'], (td.detach().abs() + 1e-6) ** self.per_alpha)
+            else:
+                loss_q = nn.functional.mse_loss(q_sa, tgt)
             self.opt_q.zero_grad(set_to_none=True)
             loss_q.backward()
             self.opt_q.step()
@@ -164,9 +174,10 @@ class DeviceDDPG:
         self.obs = eng.obs.clone()
 
     def fused_replay(self, T, n_obs):
-        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay), made at the first launch: it holds at
-        least one record"""
-        from soccer2d_amd.replay import DeviceReplay as FusedReplay
+        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay, or PrioritizedReplay with --per-alpha),
+        made at the first launch: it holds at least one record"""
+        from soccer2d_amd.replay import DeviceReplay as UniformReplay, PrioritizedReplay
+        FusedReplay = PrioritizedReplay if self.per_alpha > 0 else UniformReplay
         if not hasattr(self, 'frb'):
             self.frb = FusedReplay(max(self.buffer, T * self.env.num_envs), n_obs, self.n_act, torch.float32, self.dev,
                                    n_step=self.n_step, gamma=self.gamma, seed=self.seed)
@@ -208,12 +219,16 @@ def main():
                     help="the actor's hidden widths, e.g. 16,8 or 400,300 (1 to 5 multiples of 4 up to 400; default: 64,64)")
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
+    ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
+                    help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
-    model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step)
+    model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
+                       per_beta=args.per_beta)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -74,9 +74,11 @@ class DeviceReplay:
 
 class DeviceDQN:
     def __init__(self, env, lr=1e-3, gamma=0.99, buffer=1 << 20, batch=4096, target_every=50, grad_steps=4,
-                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu', n_step=1):
+                 eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0,
+                 per_beta=0.4):
         torch.manual_seed(seed)
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
+        self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
         self.env, self.dev = env, env.device
         self.n_act = env.action_space.n
         self.general = net_arch is not None or activation != 'relu'      # a network only the general fused actor takes
@@ -139,9 +141,10 @@ class DeviceDQN:
             self.opt.step()
 
     def fused_replay(self, T, n_obs):
-        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay), made at the first launch: it holds at
-        least one record"""
-        from soccer2d_amd.replay import DeviceReplay as FusedReplay
+        """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay, or PrioritizedReplay with --per-alpha),
+        made at the first launch: it holds at least one record"""
+        from soccer2d_amd.replay import DeviceReplay, PrioritizedReplay
+        FusedReplay = PrioritizedReplay if self.per_alpha > 0 else DeviceReplay
         if not hasattr(self, 'frb'):
             self.frb = FusedReplay(max(self.buffer, T * self.env.num_envs), n_obs, 1, torch.int32, self.dev, n_step=self.n_step,
                                    gamma=self.gamma, seed=self.seed)
@@ -149,12 +152,19 @@ class DeviceDQN:
         return self.frb
 
     def optimise_fused(self, n_updates):
-        """optimise() on batches of the fused replay buffer: reward is the n-step return, discount gamma^k or 0"""
+        """optimise() on batches of the fused replay buffer: reward is the n-step return, discount gamma^k or 0.  With
+        --per-alpha the batch is drawn in proportion to priority, the loss carries the importance weights and the batch's slots
+        get (|TD error| + 1e-6) ** alpha as their new priority."""
         for _g in range(n_updates):
             b = self.frb.sample(self.batch, out=self.fbatch)
             with torch.no_grad():
                 tgt = b['reward'] + b['discount'] * self.q_target(b['next_obs']).max(dim=1).values
-            loss = nn.functional.smooth_l1_loss(self.q(b['obs']).gather(1, b['action'].long()).squeeze(1), tgt)
+            q = self.q(b['obs']).gather(1, b['action'].long()).squeeze(1)
+            if self.per_alpha > 0:
+                loss = (self.frb.weights(b, self.per_beta) * nn.functional.smooth_l1_loss(q, tgt, reduction='none')).mean()
+                self.frb.update_priorities(b['index'], ((q.detach() - tgt).abs() + 1e-6) ** self.per_alpha)
+            else:
+                loss = nn.functional.smooth_l1_loss(q, tgt)
             self.opt.zero_grad(set_to_none=True)
             loss.backward()
             nn.utils.clip_grad_norm_(self.q.parameters(), 10.0)
@@ -234,11 +244,15 @@ def main():
                     help='hidden widths, e.g. 128,64,32,16 (1 to 5 multiples of 4 up to 400; default: 64,64)')
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
+    ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
+                    help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
-    model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step)
+    model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
+                      per_beta=args.per_beta)
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

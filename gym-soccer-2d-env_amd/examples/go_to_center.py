@@ -95,16 +95,17 @@ def main():
                     help='hidden widths of the Q-network / the actor (1 to 5 multiples of 4 up to 400; default: 64,64 / 16,8)')
     ap.add_argument('--activation', choices=('relu', 'tanh', 'sigmoid'), default='relu')
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
+    ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
+                    help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(continuous=args.continuous, turn=args.turn, use_turn=args.useturn,
               actor_out_size=args.actor_out_size if (args.turn and args.continuous) else 1)
     env = GoToCenterVecEnv(args.envs, args.device, **kw)
     test_env = GoToCenterVecEnv(args.envs, args.device, seed=1234, **kw)
-    if args.continuous:
-        model, test = GtcDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step), test_ddpg
-    else:
-        model, test = GtcDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step), test_dqn
+    learner = dict(net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha, per_beta=args.per_beta)
+    model, test = (GtcDDPG(env, **learner), test_ddpg) if args.continuous else (GtcDQN(env, **learner), test_dqn)
     print('untrained:', test(test_env, model, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

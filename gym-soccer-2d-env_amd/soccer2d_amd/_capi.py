@@ -182,6 +182,12 @@ PROTOTYPES = (
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(S2DReplayRing), C.c_void_p, C.c_void_p)),
     ('s2d_replay_sample', C.c_int, (C.c_int64, C.c_int, C.c_int, C.POINTER(S2DReplayRing), C.c_void_p, C.c_uint64, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_replay_tree_words', C.c_int64, (C.c_int64,)),
+    ('s2d_replay_prio_push', C.c_int, (C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_replay_prio_update', C.c_int, (C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_replay_sample_prio', C.c_int, (C.c_int64, C.c_int, C.c_int, C.POINTER(S2DReplayRing), C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

@@ -73,6 +73,11 @@ class DeviceReplay:
         [T,N,A], 'reward', 'done' and optionally 'result' [T,N]); first_obs [N,D] is the observation action 0 was chosen from
         (a copy taken before the rollout).  Without 'result' every done is a termination.  T * N must not exceed the capacity.
         Stream-ordered on torch's current stream, capturable."""
+        T, N, ptrs = self._record(rec, first_obs)
+        self._push(T, N, ptrs)
+
+    def _record(self, rec, first_obs):
+        """push()'s argument checks: (T, N, the seven record pointers)"""
         if not isinstance(rec, dict):
             raise ValueError('DeviceReplay.push: rec must be a rollout record dict')
         for k in ('obs', 'terminal_obs', 'action', 'reward', 'done'):
@@ -97,9 +102,13 @@ class DeviceReplay:
                 self._arr('push', "rec['reward']", reward, torch.float32, (T, N)),
                 self._arr('push', "rec['done']", rec['done'], torch.uint8, (T, N)),
                 None if rec.get('result') is None else self._arr('push', "rec['result']", rec['result'], torch.uint8, (T, N))]
+        return T, N, ptrs
+
+    def _push(self, T, N, ptrs):
         lib = self._library('push')
         with torch.cuda.device(self.device):
-            rc = lib.s2d_replay_push(T, N, D, A, self.n_step, self.gamma, *ptrs, C.byref(self._ring), C.c_void_p(self.cursor.data_ptr()),
+            rc = lib.s2d_replay_push(T, N, self.obs_dim, self.action_words, self.n_step, self.gamma, *ptrs, C.byref(self._ring),
+                                     C.c_void_p(self.cursor.data_ptr()),
                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _capi.check(lib, rc, 's2d_replay_push')
 
@@ -150,3 +159,109 @@ class DeviceReplay:
     def clear(self):
         """empty the buffer and restart the push and sample counters (stream-ordered; the ring's contents stay as they are)"""
         self.cursor.zero_()
+
+
+PRIO_FIELDS = FIELDS + ('priority', 'total')
+
+
+class PrioritizedReplay(DeviceReplay):
+    """DeviceReplay with proportional prioritized sampling (Schaul et al., 2016) on a device sum tree
+    (s2d_replay_prio_push / s2d_replay_sample_prio / s2d_replay_prio_update in include/s2d.h).  Same constructor; capacity at most
+    2^30.  The tree stores priorities exactly as handed over: apply alpha before update_priorities() and beta in weights().  New
+    transitions enter with the largest priority stored so far (1.0 on a fresh buffer).  seed keys the stratified draws (Philox
+    stream S2D_REPLAY_PRIO_STREAM, counter = the number of sample() calls so far).  Sampling resolves 2^-24 of the total mass."""
+
+    def __init__(self, capacity, *args, **kw):
+        if not _is_int(capacity) or not 1 <= capacity <= 2 ** 30:
+            raise ValueError('PrioritizedReplay: capacity must be an int in [1, 2^30]')
+        super().__init__(capacity, *args, **kw)
+        self.leaves = 1 << (capacity - 1).bit_length()                   # P; s2d_replay_tree_words(capacity) = 2 * P
+        self.tree = torch.zeros((2 * self.leaves,), dtype=torch.float32, device=self.device)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def push(self, rec, first_obs):
+        """DeviceReplay.push, behind a launch that gives the T * N slots it is about to write the largest priority stored so far"""
+        T, N, ptrs = self._record(rec, first_obs)
+        lib = self._library('push')
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_replay_prio_push(T * N, self.capacity, C.c_void_p(self.tree.data_ptr()), C.c_void_p(self.cursor.data_ptr()),
+                                          self._stream())
+        _capi.check(lib, rc, 's2d_replay_prio_push')
+        self._push(T, N, ptrs)
+
+    def alloc_batch(self, batch):
+        """DeviceReplay.alloc_batch plus 'priority' float32 [B] (the leaf each element was drawn from) and 'total' float32 [1]"""
+        if not _is_int(batch) or not 1 <= batch <= 2 ** 24:
+            raise ValueError('PrioritizedReplay.sample: batch must be an int in [1, 2^24]')
+        out = super().alloc_batch(batch)
+        out['priority'] = torch.empty((batch,), dtype=torch.float32, device=self.device)
+        out['total'] = torch.empty((1,), dtype=torch.float32, device=self.device)
+        return out
+
+    def sample(self, batch, out=None):
+        """A batch drawn in proportion to priority, one stratified draw per B-th of the total mass: the dict of alloc_batch()
+        (index -1, zero rows, priority and total 0 while the buffer is empty).  out, stream order and capture as for
+        DeviceReplay.sample."""
+        if out is None:
+            out = self.alloc_batch(batch)
+        elif not _is_int(batch) or not 1 <= batch <= 2 ** 24:
+            raise ValueError('PrioritizedReplay.sample: batch must be an int in [1, 2^24]')
+        elif not isinstance(out, dict) or any(k not in out for k in PRIO_FIELDS):
+            raise ValueError(f'PrioritizedReplay.sample: out must be a dict with {PRIO_FIELDS}')
+        B, D, A, f32 = batch, self.obs_dim, self.action_words, torch.float32
+        ptrs = [self._arr('sample', "out['obs']", out['obs'], f32, (B, D)), self._arr('sample', "out['next_obs']", out['next_obs'], f32, (B, D)),
+                self._arr('sample', "out['action']", out['action'], self.action_dtype, (B, A)),
+                self._arr('sample', "out['reward']", out['reward'], f32, (B,)), self._arr('sample', "out['discount']", out['discount'], f32, (B,)),
+                self._arr('sample', "out['index']", out['index'], torch.int32, (B,)),
+                self._arr('sample', "out['priority']", out['priority'], f32, (B,)), self._arr('sample', "out['total']", out['total'], f32, (1,))]
+        lib = self._library('sample')
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_replay_sample_prio(B, D, A, C.byref(self._ring), C.c_void_p(self.tree.data_ptr()),
+                                            C.c_void_p(self.cursor.data_ptr()), self.seed, *ptrs, self._stream())
+        _capi.check(lib, rc, 's2d_replay_sample_prio')
+        return out
+
+    def update_priorities(self, index, priority):
+        """Store priority[b] (float32 [B], alpha already applied) as the new priority of slot index[b] (int32 [B], a batch's
+        'index'); entries outside [0, size) are ignored, of duplicates the largest wins, values are clamped to [2^-40, 2^40] (NaN
+        and anything <= 0 become 2^-40).  Stream-ordered on torch's current stream, capturable."""
+        if not torch.is_tensor(index) or index.dim() != 1 or not 1 <= index.numel() <= 2 ** 24:
+            raise ValueError('PrioritizedReplay.update_priorities: index must be an int32 tensor of shape [B], B in [1, 2^24]')
+        B = index.numel()
+        ptrs = [self._arr('update_priorities', 'index', index, torch.int32, (B,)),
+                self._arr('update_priorities', 'priority', priority, torch.float32, (B,))]
+        lib = self._library('update_priorities')
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_replay_prio_update(B, self.capacity, C.c_void_p(self.tree.data_ptr()), C.c_void_p(self.cursor.data_ptr()), *ptrs,
+                                            self._stream())
+        _capi.check(lib, rc, 's2d_replay_prio_update')
+
+    def weights(self, batch, beta):
+        """The importance weights of a sampled batch, float32 [B]: (size * priority / total) ** -beta divided by the batch's
+        largest weight; 0 where index is -1.  Pure torch on the buffer's device, no synchronisation."""
+        if not isinstance(beta, (int, float)) or isinstance(beta, bool) or not math.isfinite(beta) or beta < 0:
+            raise ValueError('PrioritizedReplay.weights: beta must be a finite number >= 0')
+        if not isinstance(batch, dict) or any(k not in batch for k in ('index', 'priority', 'total')):
+            raise ValueError("PrioritizedReplay.weights: batch must be a dict with 'index', 'priority' and 'total'")
+        size = self.cursor[1].clamp(max=self.capacity).to(torch.float32)
+        valid = batch['index'] >= 0
+        w = torch.where(valid, (size * batch['priority'] / batch['total']) ** -float(beta), torch.zeros_like(batch['priority']))
+        return w / w.max().clamp_min(torch.finfo(torch.float32).tiny)
+
+    @property
+    def total(self):
+        """the sum of all priorities, tree[1] (synchronises)"""
+        return float(self.tree[1].item())
+
+    @property
+    def max_priority(self):
+        """the priority the next push hands out: the largest ever stored, 1.0 before the first update (synchronises)"""
+        top = float(self.tree[0].item())
+        return top if top >= 2.0 ** -40 else 1.0
+
+    def clear(self):
+        """DeviceReplay.clear, and the tree back to its empty state (all zero)"""
+        super().clear()
+        self.tree.zero_()

@@ -26,6 +26,8 @@
  *   s2d_replay_push            ReplayBuffer.add with handle_timeout_termination, for a whole [T][N] record at once, in the place
  *                              of the per-step add of OffPolicyAlgorithm.collect_rollouts (n-step returns formed on the way in)
  *   s2d_replay_sample          ReplayBuffer.sample (uniform, with replacement)
+ *   s2d_replay_prio_push / s2d_replay_sample_prio / s2d_replay_prio_update   proportional prioritized replay (Schaul et al.,
+ *                              2016; SB3 has none) on a sum tree over the same ring
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -471,6 +473,55 @@ int s2d_replay_push(int n_steps, int64_t n_envs, int obs_dim, int action_words, 
  * (the batch arrays must not overlap the ring, the cursor or each other). */
 int s2d_replay_sample(int64_t batch, int obs_dim, int action_words, const S2DReplayRing *ring, uint64_t *cursor, uint64_t seed,
                       void *b_obs, void *b_next, void *b_action, float *b_reward, float *b_discount, int32_t *b_index, void *stream);
+/* ---- prioritized replay: proportional sampling (Schaul et al., 2016) on a sum tree over the same ring ---------------------
+ * The library stores and sums priorities exactly as handed over; the exponents alpha and beta stay with the caller, so this
+ * contract holds only +, -, /, fmaf and comparisons.  capacity in [1, 2^30]; P = the smallest power of two >= capacity.
+ * `tree` = caller-owned device float[2 * P], 8-byte aligned:
+ *   tree[P + s]            the leaf (priority) of slot s; leaves of slots >= size are +0
+ *   tree[i], 1 <= i < P    tree[2i] + tree[2i+1]: ONE fp32 add, left + right; tree[1] is the total
+ *   tree[0]                the largest priority any update has stored; a value below S2D_PRIO_MIN there reads as 1.0f
+ * An all-zero array is the valid empty state.  Every priority is clamped on its way in,
+ *   clamp(p) = p >= S2D_PRIO_MIN ? (p <= S2D_PRIO_MAX ? p : S2D_PRIO_MAX) : S2D_PRIO_MIN
+ * (NaN, zero, negatives and denormals -> MIN, +inf -> MAX), so every stored leaf is a normal positive number, no sum can
+ * overflow (2^30 * 2^40) or become denormal, and every node's value is the same whoever computes it and however the work is
+ * cut: there is no float atomic and no sum by arrival order anywhere.  Sampling resolves 2^-24 of the total mass (fp32).
+ * All calls are stream-ordered, read the cursor WHEN THE KERNEL RUNS and can be captured as a linear chain on one stream. */
+#define S2D_REPLAY_PRIO_STREAM 12 /* Philox stream id of the stratified draws (no other draw uses it) */
+#define S2D_PRIO_MIN 0x1p-40f
+#define S2D_PRIO_MAX 0x1p+40f
+/* 2 * P, the tree's length in floats; 0 if capacity is outside [1, 2^30].  Host only, needs no GPU. */
+int64_t s2d_replay_tree_words(int64_t capacity);
+/* Mark the n slots the next s2d_replay_push of n = T * N transitions will write: with pos = cursor[0] mod capacity and
+ * p0 = tree[0] >= S2D_PRIO_MIN ? tree[0] : 1.0f, the leaves of slots (pos + j) mod capacity, j in [0, n), become p0 (new
+ * transitions carry the largest priority seen) and every ancestor is made consistent again.  tree[0] and the cursor are
+ * untouched.  Requires 1 <= n <= capacity; call it BEFORE s2d_replay_push on the same stream (that call advances pos).
+ * S2D_EINVAL without a launch: a range violated, NULL or misaligned (8 bytes) tree / cursor, the tree overlapping the cursor. */
+int s2d_replay_prio_push(int64_t n, int64_t capacity, float *tree, const uint64_t *cursor, void *stream);
+/* Store new priorities.  size = min(cursor[1], capacity).  Element b is valid iff 0 <= index[b] < size, others are ignored (the
+ * -1 of an empty sample is the usual case).  Every slot named by at least one valid element gets leaf = max over those
+ * elements of clamp(priority[b]) (with duplicate indices the largest wins); tree[0] = max(tree[0] read as above, every valid
+ * element's clamped priority); ancestors are made consistent.  Nothing else changes.  batch in [1, 2^24].  A slot a push has
+ * overwritten between the sample and the update simply takes the stale priority.  S2D_EINVAL without a launch: a range
+ * violated, NULL or misaligned pointers (4 bytes; 8 for tree and cursor), the tree overlapping cursor, index or priority. */
+int s2d_replay_prio_update(int64_t batch, int64_t capacity, float *tree, const uint64_t *cursor, const int32_t *index,
+                           const float *priority, void *stream);
+/* Sample a batch in proportion to priority, stratified.  total = tree[1], size = min(cursor[1], capacity) and samples =
+ * cursor[3] are read when the kernel runs.  If size == 0 or !(total > 0): the zero batch of s2d_replay_sample (index -1, zero
+ * rows, reward and discount +0), b_priority +0 and b_total[0] = +0.  Otherwise, with seg = total / (float)B, element b does
+ *   w = word (b & 3) of Philox4x32-10 at counter {b >> 2, samples_lo, samples_hi, S2D_REPLAY_PRIO_STREAM << 16}, key seed
+ *   u = (float)(w >> 8) * 0x1p-24f
+ *   m = fmaf(u, seg, (float)b * seg)                      one draw per segment of the mass
+ *   i = 1
+ *   while (i < P) { l = tree[2i]; r = tree[2i+1]; if (m >= l && r > 0) { m = m - l; i = 2i + 1; } else i = 2i; }
+ *   index = i - P; priority = tree[i]
+ * (the r > 0 guard makes rounding drift harmless: every visited node has a positive sum, so the walk ends on a leaf with a
+ * positive priority, hence on a slot < size).  The slot's five fields are copied as s2d_replay_sample copies them,
+ * b_priority[b] <- priority, b_total[0] <- total, and a one-thread kernel then sets samples += 1.  B in [1, 2^24] ((float)b is
+ * exact); ring->capacity in [1, 2^30].  S2D_EINVAL without a launch as for s2d_replay_sample, plus: NULL or misaligned tree (8
+ * bytes), b_priority, b_total (4 bytes); the tree overlapping the ring, the cursor or the batch arrays. */
+int s2d_replay_sample_prio(int64_t batch, int obs_dim, int action_words, const S2DReplayRing *ring, const float *tree,
+                           uint64_t *cursor, uint64_t seed, void *b_obs, void *b_next, void *b_action, float *b_reward,
+                           float *b_discount, int32_t *b_index, float *b_priority, float *b_total, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
