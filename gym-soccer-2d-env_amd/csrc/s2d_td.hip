@@ -1,0 +1,484 @@
+// s2d_td.hip -- the off-policy learners' TD targets from their target networks, one launch per batch (include/s2d.h S2DTdNet,
+// s2d_td_target_q / s2d_td_target_ac): reward + discount * max_a Q'(next_obs, a) of DQN, the same with the
+// online network's argmax of Double DQN, reward + discount * Q'(next_obs, tanh(mu'(next_obs))) of DDPG and the smaller of two
+// critics of TD3.  Engine-independent, as s2d_gae and s2d_replay_*: raw device pointers, any stream of the current device,
+// everything read when the kernels run, so sample -> target sits in one captured graph.
+//
+// The network is the streamed-weight MLP of s2d_wide_net.h (wide_group / wide_layer and the fragment order are its) with a RUN-TIME
+// input width n_in in [1, 256]: layer 1 takes ceil(n_in / 4) k-steps over x_k = 0 against zero weights past n_in, so at n_in = 10 it
+// is the reach-ball actors' 12-term layer and at n_in = 4 the GoToCenter actors' single k-step.  A pack kernel per network writes
+// its parameters in fragment order into the caller's workspace on the same stream ahead of the target kernel; the biases are read
+// from there too (one float4 per output tile), so the kernel has no block-shared LDS and no barrier: a wave is on its own.
+//
+// lane = batch row, 64 rows a wave, four 16-row tiles, T = 4, 2 or 1 of them per pass.  LDS of a wave:
+//   [input image X: T x 16 x xpitch | image A: T x 16 x rpitch | image B: T x 16 x rpitch | output image: 64 x qpitch]
+// X holds the pass's padded input rows and stays as it is while the pass's networks run: the online and the target Q-network read
+// the same rows; the actor reads the observation words (its k-steps end before the action), its tanh'ed outputs are written
+// behind them and the critics read the whole row.  xpitch covers the widest padded input row of the call (n_in = 256 is wider
+// than a [8] hidden layer), rpitch the widest hidden layer, both == 4 mod 64 words (conflict-free fragment reads).  Every chain is
+// acc = b[j]; k ascending: acc = fmaf(W[j][k], in[k], acc): neither T nor the waves per workgroup enters it.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+
+#include "s2d_wide_net.h"
+
+extern "C" void s2d_internal_set_error(const char* msg);
+
+static constexpr int kTdMaxIn = 256;
+static constexpr int kTdMaxAction = 8;
+
+// one network as the kernels see it (no array indexed by the layer: see WideDims)
+struct TdNetDev {
+  int n_in;                  // 1 .. 256
+  int ks1;                   // layer 1's k-steps: ceil(n_in / 4)
+  int n_hidden;              // L, 1 .. 5
+  int act;                   // hidden activation: 0 relu, 1 tanh_spec, 2 sigmoid_spec
+  uint64_t widths;           // h_l / 4 in bits 7 (l - 1) .. 7 l - 1; 0 past L
+  int na;                    // outputs (1 .. 64)
+  int nfrag;                 // fragments in all; the bias block follows them in the workspace
+  int nbias;                 // words of the bias block: every layer's width rounded up to 16
+  const float* wf;           // the workspace
+};
+// the call's LDS plan
+struct TdPlanDev {
+  int xpitch, rpitch, qpitch;   // row pitches of the input image, the hidden images and the output image (words)
+  int tiles;                    // T: row tiles per pass, 4 | 2 | 1
+  int wave_words;               // T 16 (xpitch + 2 rpitch) + 64 qpitch
+};
+S2D_DEV int td_width(const TdNetDev& d, int l) { return 4 * (int)((d.widths >> (7 * l)) & 127u); }
+
+// wave-uniform choice between the networks of a call, field by field (a pointer into the kernel arguments would be a copy)
+S2D_DEV TdNetDev td_pick(bool first, const TdNetDev& a, const TdNetDev& b) {
+  TdNetDev r;
+  r.n_in = first ? a.n_in : b.n_in; r.ks1 = first ? a.ks1 : b.ks1; r.n_hidden = first ? a.n_hidden : b.n_hidden;
+  r.act = first ? a.act : b.act; r.widths = first ? a.widths : b.widths; r.na = first ? a.na : b.na;
+  r.nfrag = first ? a.nfrag : b.nfrag; r.nbias = first ? a.nbias : b.nbias; r.wf = first ? a.wf : b.wf;
+  return r;
+}
+
+// The network on the pass's T row tiles: x = the input image (pitch xp; layer 1 reads d.ks1 k-steps of it), ia / ib = the hidden
+// images (pitch rp), q = the pass's first row of the output image (pitch qp): q[row][j] = the output layer's pre-activations.
+// One call site of wide_layer for all layers: its code exists once per T.
+template <int T>
+S2D_DEV void td_layers(const TdNetDev& d, const float* __restrict__ x, int xp, float* __restrict__ ia, float* __restrict__ ib, int rp,
+                       float* __restrict__ q, int qp, int lane) {
+  const float* wf = d.wf;
+  const float* bias = d.wf + (size_t)d.nfrag * kWave;
+  const float* in = x;
+  int ip = xp, ks = d.ks1;
+  float* a = ia;
+  float* b = ib;
+  for (int l = 0; l <= d.n_hidden; ++l) {
+    const bool last = l == d.n_hidden;
+    const int wout = last ? d.na : td_width(d, l), m16 = (wout + 15) >> 4;
+    float* const out = last ? q : a;
+    const int op = last ? qp : rp;
+    wide_layer<T>(wf, bias, m16, ks, in, ip, 16 * ip, out, op, 16 * op, last ? (int)S2D_WIDE_LINEAR : d.act, lane);
+    wave_lds_fence();
+    wf += (size_t)m16 * ks * kWave;
+    bias += 16 * m16;
+    ks = wout >> 2;
+    in = a; ip = rp;
+    float* const swap = a; a = b; b = swap;
+  }
+}
+
+// rows row0 .. row0 + 16 T - 1 of obs[batch][D] into the input image, `kp` words a row (a multiple of 4 >= D): zeros past D and
+// in the rows past the batch.  The rows are contiguous in memory; row and column are carried, so there is one division per call.
+// Eight loads are issued before the first is stored: a word that does not exist is loaded from obs[0] (always there) and replaced
+// by zero, so no load sits behind a branch and a 256-word row costs four round trips to memory, not thirty-two.
+S2D_DEV void td_load_rows(const float* __restrict__ obs, int64_t row0, int64_t batch, int D, int kp, int rows, float* __restrict__ x,
+                          int xp, int lane) {
+  constexpr int U = 8;
+  const int total = rows * kp, q = kWave / kp, m = kWave % kp;
+  int r = lane / kp, k = lane % kp;
+  for (int f0 = lane; f0 < total + lane; f0 += U * kWave) {
+    float v[U];
+    int at[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool in = f0 + u * kWave < total, real = in && k < D && row0 + r < batch;
+      const float w = obs[real ? (row0 + r) * D + k : 0];
+      v[u] = real ? w : 0.0f;
+      at[u] = in ? r * xp + k : -1;
+      r += q; k += m;
+      if (k >= kp) { k -= kp; r += 1; }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (at[u] >= 0) x[at[u]] = v[u];
+  }
+}
+
+// target = reward + (discount * q): one fp32 multiply, then one fp32 add (what eager torch's r + d * q computes)
+S2D_DEV float td_target(float reward, float discount, float q) { return __fadd_rn(reward, __fmul_rn(discount, q)); }
+
+// s2d_td_target_q.  DOUBLE: the index is the argmax of the online network, the value the target network's at that index.
+template <bool DOUBLE>
+__global__ __launch_bounds__(kBlock) void s2d_td_target_q_kernel(TdNetDev tgt, TdNetDev onl, TdPlanDev pl, int64_t batch,
+                                                                 const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                 const float* __restrict__ discount, float* __restrict__ out_target,
+                                                                 float* __restrict__ out_q, int32_t* __restrict__ out_index) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+  if (wave_first >= batch) return;
+  const int T = pl.tiles;
+  float* const x = smem + (size_t)wv * pl.wave_words;
+  float* const ia = x + T * 16 * pl.xpitch;
+  float* const ib = ia + T * 16 * pl.rpitch;
+  float* const qv = ib + T * 16 * pl.rpitch;
+  const int kp = 4 * tgt.ks1;
+  int best = 0;
+  float qbest = 0.0f;
+  for (int nt = 0; nt < 4; nt += T) {
+    td_load_rows(next_obs, wave_first + 16 * nt, batch, tgt.n_in, kp, 16 * T, x, pl.xpitch, lane);
+    wave_lds_fence();
+    const bool mine = (lane >> 4) >= nt && (lane >> 4) < nt + T;
+    const float* const q = qv + lane * pl.qpitch;
+#pragma unroll 1
+    for (int v = DOUBLE ? 0 : 1; v < 2; ++v) {
+      const TdNetDev d = DOUBLE ? td_pick(v == 0, onl, tgt) : tgt;
+      float* const qp = qv + 16 * nt * pl.qpitch;
+      if (T == 4) td_layers<4>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else if (T == 2) td_layers<2>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else td_layers<1>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      if (mine) {
+        if (v == (DOUBLE ? 0 : 1)) {
+          // best = 0; for a = 1 .. A-1: if (y[a] > y[best]) best = a   (ties: lowest index; a NaN never replaces the best)
+          int bi = 0;
+          float bv = q[0];
+          for (int a = 1; a < d.na; ++a) {
+            const float y = q[a];
+            if (y > bv) { bv = y; bi = a; }
+          }
+          best = bi;
+        }
+        if (v == 1) qbest = q[best];
+      }
+      wave_lds_fence();
+    }
+  }
+  if (i < batch) {
+    out_target[i] = td_target(reward[i], discount[i], qbest);
+    if (out_q) out_q[i] = qbest;
+    if (out_index) out_index[i] = best;
+  }
+}
+
+// s2d_td_target_ac: the actor, its tanh head into the critics' input row, critic 1 and (TWIN) critic 2 on one row tile
+template <bool TWIN>
+__global__ __launch_bounds__(kBlock) void s2d_td_target_ac_kernel(TdNetDev actor, TdNetDev c1, TdNetDev c2, TdPlanDev pl, int64_t batch,
+                                                                  const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                  const float* __restrict__ discount, float* __restrict__ out_target,
+                                                                  float* __restrict__ out_q, float* __restrict__ out_action) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+  if (wave_first >= batch) return;
+  const int T = pl.tiles;
+  float* const x = smem + (size_t)wv * pl.wave_words;
+  float* const ia = x + T * 16 * pl.xpitch;
+  float* const ib = ia + T * 16 * pl.rpitch;
+  float* const qv = ib + T * 16 * pl.rpitch;
+  const int D = actor.n_in, A = actor.na, kp = 4 * c1.ks1;   // the critics' padded row covers the actor's
+  float qmin = 0.0f;
+  for (int nt = 0; nt < 4; nt += T) {
+    const int64_t row0 = wave_first + 16 * nt;
+    td_load_rows(next_obs, row0, batch, D, kp, 16 * T, x, pl.xpitch, lane);
+    wave_lds_fence();
+    const bool mine = (lane >> 4) >= nt && (lane >> 4) < nt + T;
+    float* const qp = qv + 16 * nt * pl.qpitch;
+#pragma unroll 1
+    for (int v = 0; v < (TWIN ? 3 : 2); ++v) {
+      const TdNetDev d = v == 0 ? actor : TWIN ? td_pick(v == 1, c1, c2) : c1;
+      if (T == 4) td_layers<4>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else if (T == 2) td_layers<2>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else td_layers<1>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      if (v == 0) {
+        // a'[i] = tanh_spec(y[i]) behind the observation words of its row (the words past D + A stay zero)
+        for (int idx = lane; idx < 16 * T * A; idx += kWave) {
+          const int r = idx / A, k = idx - r * A;
+          const float a = tanh_spec(qp[r * pl.qpitch + k]);
+          x[r * pl.xpitch + D + k] = a;
+          if (out_action && row0 + r < batch) out_action[(row0 + r) * A + k] = a;
+        }
+      } else if (mine) {
+        const float q = qv[lane * pl.qpitch];
+        qmin = (v == 1 || q < qmin) ? q : qmin;              // q2 < q1 ? q2 : q1: a NaN in q2 never replaces q1
+      }
+      wave_lds_fence();
+    }
+  }
+  if (i < batch) {
+    out_target[i] = td_target(reward[i], discount[i], qmin);
+    if (out_q) out_q[i] = qmin;
+  }
+}
+
+// The caller's parameters (nn.Sequential order: W_1 [h_1][n_in], b_1, ..., W_out [A][h_L], b_out) into the workspace in fragment
+// order, then the biases, every layer's padded with zeros to its tiles' 16 rows: one word per thread.  s2d_wide_pack_kernel with
+// a run-time input width: rows past a layer's width and layer 1's k >= n_in are zero.
+__global__ __launch_bounds__(256) void s2d_td_pack_kernel(TdNetDev d, const float* __restrict__ params, float* __restrict__ ws) {
+  const int L = d.n_hidden;
+  const int nw = d.nfrag * kWave;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nw + d.nbias) return;
+  if (idx < nw) {
+    const int f = idx / kWave, lw = idx & (kWave - 1);
+    const int row = lw & 15, kk = lw >> 4;
+    // the layer of fragment f: its first fragment, widths in and out, k-steps and the offset of its W in params
+    int f0 = 0, win = d.n_in, wout = td_width(d, 0), ks = d.ks1, ow = 0;
+#pragma unroll
+    for (int l = 1; l <= kWideMaxHidden; ++l) {
+      const int next = f0 + ((wout + 15) >> 4) * ks;         // the first fragment of the layer after this one
+      if (l <= L && f >= next) {
+        ow += wout * win + wout;
+        f0 = next;
+        win = wout;
+        wout = l < L ? td_width(d, l) : d.na;
+        ks = win >> 2;
+      }
+    }
+    const int r = f - f0, jt = r / ks, s = r - jt * ks, j = 16 * jt + row, k = 4 * s + kk;
+    ws[idx] = (j < wout && k < win) ? params[ow + j * win + k] : 0.0f;
+  } else {
+    const int bi = idx - nw;
+    int b0 = 0, win = d.n_in, wout = td_width(d, 0), ob = wout * win;   // ob: the offset of the layer's bias in params
+#pragma unroll
+    for (int l = 1; l <= kWideMaxHidden; ++l) {
+      const int pad = (wout + 15) & ~15;
+      if (l <= L && bi >= b0 + pad) {
+        b0 += pad;
+        win = wout;
+        wout = l < L ? td_width(d, l) : d.na;
+        ob += win + wout * win;
+      }
+    }
+    const int j = bi - b0;
+    ws[idx] = j < wout ? params[ob + j] : 0.0f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ host
+namespace {
+int fail(const std::string& who, const std::string& msg) {
+  s2d_internal_set_error((who + ": " + msg).c_str());
+  return S2D_EINVAL;
+}
+bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
+
+bool shape_ok(const S2DTdNet* n) {
+  return n->n_in >= 1 && n->n_in <= kTdMaxIn && wide_shape_ok(n->n_hidden, n->hidden) && n->n_out >= 1 && n->n_out <= 64;
+}
+// the kernels' view of a shape on the grid (wf left NULL) and its widest padded hidden layer
+TdNetDev net_dev(const S2DTdNet* n, int* wmax) {
+  TdNetDev d{};
+  d.n_in = n->n_in; d.ks1 = (n->n_in + 3) / 4; d.n_hidden = n->n_hidden; d.act = n->activation; d.na = n->n_out;
+  int ks = d.ks1;
+  for (int l = 0; l < n->n_hidden; ++l) {
+    const int w = n->hidden[l], m16 = (w + 15) / 16;
+    d.widths |= (uint64_t)(w / 4) << (7 * l);
+    d.nfrag += m16 * ks;
+    d.nbias += 16 * m16;
+    if (wmax && 16 * m16 > *wmax) *wmax = 16 * m16;
+    ks = w / 4;
+  }
+  const int na16 = (n->n_out + 15) / 16 * 16;
+  d.nfrag += (na16 / 16) * ks;
+  d.nbias += na16;
+  return d;
+}
+size_t workspace_bytes(const TdNetDev& d) { return ((size_t)d.nfrag * kWave + d.nbias) * sizeof(float); }
+std::string net_text(const S2DTdNet* n) {
+  std::string s = std::to_string(n->n_in);
+  for (int l = 0; l < n->n_hidden; ++l) s += "-" + std::to_string(n->hidden[l]);
+  return s + "-" + std::to_string(n->n_out);
+}
+
+// one network of a call (`name`: what the header calls it): the shape, the parameters and the workspace
+int check_net(const std::string& who, const char* name, const S2DTdNet* n, TdNetDev& d, int& wmax) {
+  const std::string nm(name);
+  if (n->n_in < 1 || n->n_in > kTdMaxIn) return fail(who, nm + ": n_in must be in [1, 256]");
+  if (n->n_hidden < 1 || n->n_hidden > kWideMaxHidden) return fail(who, nm + ": n_hidden must be in [1, 5]");
+  if (!wide_shape_ok(n->n_hidden, n->hidden)) return fail(who, nm + ": hidden widths must be multiples of 4 in [8, 400], and 0 past n_hidden");
+  if (n->n_out < 1 || n->n_out > 64) return fail(who, nm + ": n_out must be in [1, 64]");
+  if (n->activation < 0 || n->activation > 2) return fail(who, nm + ": activation must be 0 (ReLU), 1 (Tanh) or 2 (Sigmoid)");
+  if (!n->params || misaligned(n->params, 16)) return fail(who, nm + ": params must be a non-NULL, 16-byte aligned device pointer");
+  if (!n->workspace || misaligned(n->workspace, 256)) return fail(who, nm + ": workspace must be a non-NULL, 256-byte aligned device pointer");
+  d = net_dev(n, &wmax);
+  if (n->workspace_bytes < workspace_bytes(d))
+    return fail(who, nm + ": workspace_bytes is " + std::to_string(n->workspace_bytes) + ", the network " + net_text(n) + " needs " +
+                         std::to_string(workspace_bytes(d)) + " (s2d_td_workspace_bytes)");
+  d.wf = static_cast<const float*>(n->workspace);
+  return S2D_OK;
+}
+bool share(const S2DTdNet* a, const TdNetDev& da, const S2DTdNet* b, const TdNetDev& db) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(a->workspace), q = reinterpret_cast<uintptr_t>(b->workspace);
+  return p < q + workspace_bytes(db) && q < p + workspace_bytes(da);
+}
+
+// compute units of the current device (0: unknown), asked once per device
+int compute_units() {
+  static std::mutex mu;
+  static int cus[kMaxDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
+  return cus[dev];
+}
+
+// The plan of a call: pitches from the widest padded hidden layer (wmax), the widest input (n_in) and the most outputs (na) of
+// its networks; the first of (waves, tiles) = (4, 4) (4, 2) (4, 1) (2, 4) ... (1, 1) that 160 KiB hold (more waves go before more
+// tiles, as wide_plan_lds; (1, 1) always fits: 16 x (324 + 2 x 452) + 64 x 68 words).  A learner's batch is small beside a
+// rollout's env count (B = 4096 is 64 waves): the search starts at 2 waves per workgroup while the batch has fewer than 4 waves per
+// compute unit and at 1 while it has fewer than 2, so that the workgroups spread over the device instead of filling a few units.
+// S2D_TD_PLAN=waves,tiles in the environment, read at every launch, overrides the choice (testing: the results do not depend
+// on it); a pair that is not of {4, 2, 1} or does not fit is refused.
+int make_plan(const std::string& who, int64_t batch, int wmax, int n_in, int na, TdPlanDev& pl, int& waves, size_t& lds) {
+  pl.rpitch = (wmax + 63) / 64 * 64 + 4;
+  pl.xpitch = ((n_in + 3) / 4 * 4 + 63) / 64 * 64 + 4;
+  pl.qpitch = (na + 15) / 16 * 16 + 4;
+  int fw = 0, ft = 0;
+  const char* const env = std::getenv("S2D_TD_PLAN");
+  if (env && *env && std::sscanf(env, "%d,%d", &fw, &ft) != 2) fw = ft = -1;
+  const auto one_of = [](int v) { return v == 4 || v == 2 || v == 1; };
+  const int64_t batch_waves = (batch + kWave - 1) / kWave, cus = compute_units();
+  const int most = fw ? kWavesPerBlock : batch_waves >= 4 * cus ? kWavesPerBlock : batch_waves >= 2 * cus ? 2 : 1;
+  if ((!fw || one_of(fw)) && (!ft || one_of(ft))) {
+    for (int wv = most; wv >= 1; wv /= 2) {
+      if (fw && wv != fw) continue;
+      for (int t = 4; t >= 1; t /= 2) {
+        if (ft && t != ft) continue;
+        const int ww = t * 16 * (pl.xpitch + 2 * pl.rpitch) + kWave * pl.qpitch;
+        if ((size_t)wv * ww * sizeof(float) <= kLdsMax) {
+          pl.tiles = t; pl.wave_words = ww; waves = wv; lds = (size_t)wv * ww * sizeof(float);
+          return S2D_OK;
+        }
+      }
+    }
+  }
+  return fail(who, std::string("S2D_TD_PLAN=") + (env ? env : "") + " is not waves,tiles of {4, 2, 1} that fit the LDS of this call");
+}
+
+// the dynamic-LDS limit of a kernel, once per device and kernel
+bool allow_lds(const void* fn, int slot) {
+  static std::mutex mu;
+  static bool set[kMaxDevices][4] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!set[dev][slot]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
+    set[dev][slot] = true;
+  }
+  return true;
+}
+
+void launch_pack(const TdNetDev& d, const S2DTdNet* n, hipStream_t stream) {
+  const int words = d.nfrag * kWave + d.nbias;
+  hipLaunchKernelGGL(s2d_td_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, n->params,
+                     static_cast<float*>(n->workspace));
+}
+
+// what both entry points ask of the batch arrays
+int check_batch(const std::string& who, int64_t batch, const void* next_obs, const void* reward, const void* discount, const void* out_target,
+                const void* opt1, const void* opt2) {
+  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  if (!next_obs || !reward || !discount || !out_target || misaligned(next_obs, 4) || misaligned(reward, 4) || misaligned(discount, 4) ||
+      misaligned(out_target, 4))
+    return fail(who, "next_obs, reward, discount and out_target must be non-NULL, 4-byte aligned device pointers");
+  if (misaligned(opt1, 4) || misaligned(opt2, 4)) return fail(who, "the optional outputs must be 4-byte aligned device pointers (or NULL)");
+  return S2D_OK;
+}
+int launched(const std::string& who) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return S2D_OK;
+  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
+  return S2D_EHIP;
+}
+}  // namespace
+
+S2D_API size_t s2d_td_workspace_bytes(const S2DTdNet* shape) {
+  if (!shape || !shape_ok(shape)) return 0;
+  return workspace_bytes(net_dev(shape, nullptr));
+}
+
+S2D_API int s2d_td_target_q(int64_t batch, const S2DTdNet* target, const S2DTdNet* online, const float* next_obs, const float* reward,
+                            const float* discount, float* out_target, float* out_q, int32_t* out_index, void* stream) {
+  static const std::string who = "s2d_td_target_q";
+  if (!target) return fail(who, "target is NULL");
+  TdNetDev dt{}, dn{};
+  int wmax = 0;
+  if (check_net(who, "target", target, dt, wmax) != S2D_OK) return S2D_EINVAL;
+  if (online) {
+    if (check_net(who, "online", online, dn, wmax) != S2D_OK) return S2D_EINVAL;
+    if (online->n_in != target->n_in || online->n_out != target->n_out)
+      return fail(who, "online is " + net_text(online) + ", target " + net_text(target) + ": n_in and n_out must be the same");
+    if (share(target, dt, online, dn)) return fail(who, "target and online share a workspace: every network of a call needs its own");
+  }
+  if (check_batch(who, batch, next_obs, reward, discount, out_target, out_q, out_index) != S2D_OK) return S2D_EINVAL;
+  TdPlanDev pl{};
+  int waves = 0;
+  size_t lds = 0;
+  if (make_plan(who, batch, wmax, target->n_in, target->n_out, pl, waves, lds) != S2D_OK) return S2D_EINVAL;
+  using Kernel = void (*)(TdNetDev, TdNetDev, TdPlanDev, int64_t, const float*, const float*, const float*, float*, float*, int32_t*);
+  const Kernel k = online ? s2d_td_target_q_kernel<true> : s2d_td_target_q_kernel<false>;
+  if (!allow_lds(reinterpret_cast<const void*>(k), online ? 1 : 0)) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int threads = waves * kWave;
+  launch_pack(dt, target, s);
+  if (online) launch_pack(dn, online, s);
+  hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, dt, dn, pl, batch, next_obs, reward,
+                     discount, out_target, out_q, out_index);
+  return launched(who);
+}
+
+S2D_API int s2d_td_target_ac(int64_t batch, const S2DTdNet* actor, const S2DTdNet* critic1, const S2DTdNet* critic2, const float* next_obs,
+                             const float* reward, const float* discount, float* out_target, float* out_q, float* out_action, void* stream) {
+  static const std::string who = "s2d_td_target_ac";
+  if (!actor || !critic1) return fail(who, "actor and critic1 must be non-NULL");
+  TdNetDev da{}, d1{}, d2{};
+  int wmax = 0;
+  if (check_net(who, "actor", actor, da, wmax) != S2D_OK || check_net(who, "critic1", critic1, d1, wmax) != S2D_OK) return S2D_EINVAL;
+  if (critic2 && check_net(who, "critic2", critic2, d2, wmax) != S2D_OK) return S2D_EINVAL;
+  if (actor->n_out > kTdMaxAction) return fail(who, "actor: n_out must be in [1, 8]");
+  for (const S2DTdNet* c : {critic1, critic2}) {
+    if (!c) continue;
+    if (c->n_in != actor->n_in + actor->n_out || c->n_out != 1)
+      return fail(who, std::string(c == critic1 ? "critic1" : "critic2") + " is " + net_text(c) + ", the actor " + net_text(actor) +
+                           ": a critic's n_in must be the actor's n_in + n_out, its n_out 1");
+  }
+  if (share(actor, da, critic1, d1) || (critic2 && (share(actor, da, critic2, d2) || share(critic1, d1, critic2, d2))))
+    return fail(who, "two networks share a workspace: every network of a call needs its own");
+  if (check_batch(who, batch, next_obs, reward, discount, out_target, out_q, out_action) != S2D_OK) return S2D_EINVAL;
+  TdPlanDev pl{};
+  int waves = 0;
+  size_t lds = 0;
+  if (make_plan(who, batch, wmax, critic1->n_in, actor->n_out, pl, waves, lds) != S2D_OK) return S2D_EINVAL;
+  using Kernel = void (*)(TdNetDev, TdNetDev, TdNetDev, TdPlanDev, int64_t, const float*, const float*, const float*, float*, float*, float*);
+  const Kernel k = critic2 ? s2d_td_target_ac_kernel<true> : s2d_td_target_ac_kernel<false>;
+  if (!allow_lds(reinterpret_cast<const void*>(k), critic2 ? 3 : 2)) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int threads = waves * kWave;
+  launch_pack(da, actor, s);
+  launch_pack(d1, critic1, s);
+  if (critic2) launch_pack(d2, critic2, s);
+  hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, da, d1, d2, pl, batch, next_obs, reward,
+                     discount, out_target, out_q, out_action);
+  return launched(who);
+}

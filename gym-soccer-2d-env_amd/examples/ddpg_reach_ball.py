@@ -12,6 +12,8 @@ with Polyak averaging, Gaussian action noise, a replay buffer in device memory.
 (Engine.rollout_actor with a soccer2d_amd.actor.DeterministicActor), with epsilon-random exploration for the first launches
 (SB3's learning_starts) and Gaussian action noise; the actor's packed weights are refreshed with sync() after every optimiser
 phase and Timeouts bootstrap from the recorded terminal observations.  0: one torch forward per step.
+--fused-target computes the TD targets in one launch from the target actor and critic (soccer2d_amd.td.ActorCriticTarget,
+INTEGRATION 3f) instead of a chain of torch ops, and reloads its buffers after every Polyak step.
 """
 import argparse
 import copy
@@ -68,8 +70,10 @@ class DeviceReplay:
 
 class DeviceDDPG:
     def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
-                 learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0, per_beta=0.4):
+                 learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0, per_beta=0.4,
+                 fused_target=False):
         torch.manual_seed(seed)
+        self.fused_target = fused_target
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
         self.env, self.dev = env, env.device
@@ -105,8 +109,11 @@ class DeviceDDPG:
             else:
                 o, a, r, no, t = self.rb.sample(self.batch)
                 disc = self.gamma * (1 - t)
-            with torch.no_grad():
-                tgt = r + disc * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
+            if fused and self.fused_target:                      # one launch: the target actor and the target critic on the batch
+                tgt = self.td.target(b, out=self.ftgt)
+            else:
+                with torch.no_grad():
+                    tgt = r + disc * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
             q_sa = self.q(torch.cat([o, a], 1)).squeeze(1)
             if per:
                 td = q_sa - tgt
@@ -125,6 +132,8 @@ class DeviceDDPG:
                 for net, tgt_net in ((self.mu, self.mu_target), (self.q, self.q_target)):
                     for p, pt in zip(net.parameters(), tgt_net.parameters()):
                         pt.mul_(1 - self.tau).add_(p, alpha=self.tau)
+            if fused and self.fused_target:
+                self.td.sync()                                   # the next target launch reads the Polyak-averaged weights
 
     def _store(self, obs_t, act, rec_obs, rew, done, res, term_obs):
         next_obs = torch.where(done.bool().unsqueeze(-1), term_obs, rec_obs)            # bootstrap through Timeouts
@@ -163,6 +172,7 @@ class DeviceDDPG:
                     self.actor = WideDeterministicActor.from_module(self.mu, **kw)
             print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
+        self.make_fused_target()
         eng, rec = self.env.engine, self.rec
         rb = self.fused_replay(T, eng.obs.shape[-1])
         for _ in range((vec_steps + T - 1) // T):
@@ -172,6 +182,13 @@ class DeviceDDPG:
             rb.push(rec, obs0)                                   # T x N n-step transitions, Timeouts bootstrap (one launch)
             self.after_fused_launch(T)
         self.obs = eng.obs.clone()
+
+    def make_fused_target(self):
+        """--fused-target: the target launch's state (soccer2d_amd.td.ActorCriticTarget) and the tensor it writes, made once"""
+        if self.fused_target and not hasattr(self, 'td'):
+            from soccer2d_amd.td import ActorCriticTarget
+            self.td = ActorCriticTarget.from_modules(self.mu_target, self.q_target, device=self.dev)
+            self.ftgt = torch.empty((self.batch,), dtype=torch.float32, device=self.dev)
 
     def fused_replay(self, T, n_obs):
         """the device replay buffer of the fused path (soccer2d_amd.replay.DeviceReplay, or PrioritizedReplay with --per-alpha),
@@ -221,14 +238,19 @@ def main():
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
                     help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--fused-target', action='store_true',
+                    help='with --fused-actor: the TD targets in one launch from the target actor and critic '
+                         '(soccer2d_amd.td.ActorCriticTarget)')
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
+    if args.fused_target and args.fused_actor <= 0:
+        ap.error('--fused-target needs --fused-actor T')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
     model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
-                       per_beta=args.per_beta)
+                       per_beta=args.per_beta, fused_target=args.fused_target)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -13,7 +13,9 @@ feeds N transitions.
 (Engine.rollout_qnet with a soccer2d_amd.actor.QNetActor), epsilon-greedy per env; the actor's packed weights are refreshed
 with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal observations.  The
 record goes into a soccer2d_amd.replay.DeviceReplay in one launch and a batch comes out in one; --n-step K stores
-K-step returns (targets R + discount * max Q_target(next)).
+K-step returns (targets R + discount * max Q_target(next)).  --fused-target computes those targets in one launch from the target
+network (soccer2d_amd.td.QTarget) instead of a chain of torch ops; --double-q reads the target network's value at
+the online network's argmax (Double DQN), with or without --fused-target.
 """
 import argparse
 import copy
@@ -75,10 +77,11 @@ class DeviceReplay:
 class DeviceDQN:
     def __init__(self, env, lr=1e-3, gamma=0.99, buffer=1 << 20, batch=4096, target_every=50, grad_steps=4,
                  eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0,
-                 per_beta=0.4):
+                 per_beta=0.4, fused_target=False, double_q=False):
         torch.manual_seed(seed)
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
+        self.fused_target, self.double_q = fused_target, double_q
         self.env, self.dev = env, env.device
         self.n_act = env.action_space.n
         self.general = net_arch is not None or activation != 'relu'      # a network only the general fused actor takes
@@ -103,6 +106,13 @@ class DeviceDQN:
         rnd = torch.randint(0, self.n_act, greedy.shape, device=self.dev)
         return torch.where(torch.rand(greedy.shape, device=self.dev) < eps, rnd, greedy)
 
+    def bootstrap(self, next_obs):
+        """the value the target bootstraps from: max_a Q_target(next), or (--double-q) Q_target(next) at the online argmax"""
+        qn = self.q_target(next_obs)
+        if self.double_q:
+            return qn.gather(1, self.q(next_obs).argmax(dim=1, keepdim=True)).squeeze(1)
+        return qn.max(dim=1).values
+
     def learn(self, vec_steps, on_result=None):
         for _ in range(vec_steps):
             act = self.predict(self.obs, self.epsilon())
@@ -120,7 +130,7 @@ class DeviceDQN:
                 for _g in range(self.grad_steps):
                     o, a, r, no, t = self.rb.sample(self.batch)
                     with torch.no_grad():
-                        tgt = r + self.gamma * (1 - t) * self.q_target(no).max(dim=1).values
+                        tgt = r + self.gamma * (1 - t) * self.bootstrap(no)
                     loss = nn.functional.smooth_l1_loss(self.q(o).gather(1, a.unsqueeze(1)).squeeze(1), tgt)
                     self.opt.zero_grad(set_to_none=True)
                     loss.backward()
@@ -133,7 +143,7 @@ class DeviceDQN:
         for _g in range(n_updates):
             o, a, r, no, t = self.rb.sample(self.batch)
             with torch.no_grad():
-                tgt = r + self.gamma * (1 - t) * self.q_target(no).max(dim=1).values
+                tgt = r + self.gamma * (1 - t) * self.bootstrap(no)
             loss = nn.functional.smooth_l1_loss(self.q(o).gather(1, a.unsqueeze(1)).squeeze(1), tgt)
             self.opt.zero_grad(set_to_none=True)
             loss.backward()
@@ -151,14 +161,26 @@ class DeviceDQN:
             self.fbatch, self.stored = self.frb.alloc_batch(self.batch), 0
         return self.frb
 
+    def make_fused_target(self):
+        """--fused-target: the target launch's state (soccer2d_amd.td.QTarget) and the tensor it writes, made once"""
+        if self.fused_target and not hasattr(self, 'td'):
+            from soccer2d_amd.td import QTarget
+            self.td = QTarget.from_module(self.q_target, online=self.q if self.double_q else None, device=self.dev)
+            self.ftgt = torch.empty((self.batch,), dtype=torch.float32, device=self.dev)
+
     def optimise_fused(self, n_updates):
         """optimise() on batches of the fused replay buffer: reward is the n-step return, discount gamma^k or 0.  With
         --per-alpha the batch is drawn in proportion to priority, the loss carries the importance weights and the batch's slots
         get (|TD error| + 1e-6) ** alpha as their new priority."""
         for _g in range(n_updates):
             b = self.frb.sample(self.batch, out=self.fbatch)
-            with torch.no_grad():
-                tgt = b['reward'] + b['discount'] * self.q_target(b['next_obs']).max(dim=1).values
+            if self.fused_target:                                # one launch; the online network's weights as of this step
+                if self.double_q:
+                    self.td.online.sync()
+                tgt = self.td.target(b, out=self.ftgt)
+            else:
+                with torch.no_grad():
+                    tgt = b['reward'] + b['discount'] * self.bootstrap(b['next_obs'])
             q = self.q(b['obs']).gather(1, b['action'].long()).squeeze(1)
             if self.per_alpha > 0:
                 loss = (self.frb.weights(b, self.per_beta) * nn.functional.smooth_l1_loss(q, tgt, reduction='none')).mean()
@@ -176,6 +198,8 @@ class DeviceDQN:
             self.steps += 1
             if self.steps % self.target_every == 0:
                 self.q_target.load_state_dict(self.q.state_dict())
+                if self.fused_target:
+                    self.td.q_target.sync()                      # the target launch reads the new weights
         self.stored += T * self.env.num_envs
         if self.stored >= self.batch:
             self.optimise_fused(self.grad_steps * T)
@@ -198,6 +222,7 @@ class DeviceDQN:
                     self.actor = WideQNetActor.from_module(self.q, **kw)
             print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
+        self.make_fused_target()
         eng, rec = self.env.engine, self.rec
         rb = self.fused_replay(T, eng.obs.shape[-1])
         for _ in range((vec_steps + T - 1) // T):
@@ -246,13 +271,18 @@ def main():
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
                     help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--fused-target', action='store_true',
+                    help='with --fused-actor: the TD targets in one launch from the target network (soccer2d_amd.td.QTarget)')
+    ap.add_argument('--double-q', action='store_true', help="Double DQN: the target network's value at the online network's argmax")
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
+    if args.fused_target and args.fused_actor <= 0:
+        ap.error('--fused-target needs --fused-actor T')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
     model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
-                      per_beta=args.per_beta)
+                      per_beta=args.per_beta, fused_target=args.fused_target, double_q=args.double_q)
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

@@ -13,6 +13,7 @@ learners of dqn_reach_ball.py / ddpg_reach_ball.py.
 (GoToCenterVecEnv.rollout_qnet / rollout_actor with a soccer2d_amd.gtc_actor.GtcQNetActor / GtcDeterministicActor); the actor's
 packed weights are refreshed with sync() after every optimiser phase and Timeouts bootstrap from the recorded terminal
 observations; the record goes into a soccer2d_amd.replay.DeviceReplay in one launch (--n-step K: K-step returns).
+--fused-target computes the TD targets in one launch from the target network(s) (soccer2d_amd.td); --double-q: Double DQN.
 --net-arch / --activation: the Optuna grids of best_python_sample_soccer_env*.py (1 to 5 widths, multiples of 4 up to 400; relu,
 tanh or sigmoid).
 """
@@ -41,6 +42,7 @@ class GtcDQN(DeviceDQN):
             self.actor = GtcQNetActor.from_module(self.q, device=self.dev, epsilon=self.epsilon())
             print(f'fused actor: {type(self.actor).__name__} {self.actor.hidden} {self.actor.activation}')
             self.rec = None
+        self.make_fused_target()
         env = self.env
         rb = self.fused_replay(T, 4)
         for _ in range((vec_steps + T - 1) // T):
@@ -67,6 +69,7 @@ class GtcDDPG(DeviceDDPG):
             self.actor = GtcDeterministicActor.from_module(self.mu, device=self.dev, epsilon=1.0, noise_sigma=self.sigma)
             print(f'fused actor: {type(self.actor).__name__} {self.actor.hidden} {self.actor.activation}')
             self.rec = None
+        self.make_fused_target()
         env = self.env
         rb = self.fused_replay(T, 4)
         for _ in range((vec_steps + T - 1) // T):
@@ -97,15 +100,23 @@ def main():
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='with --fused-actor: K-step returns in the replay buffer')
     ap.add_argument('--per-alpha', type=float, default=0.0, metavar='A',
                     help='with --fused-actor: prioritized replay, priority = (|TD error| + 1e-6) ** A (0: uniform sampling)')
+    ap.add_argument('--fused-target', action='store_true',
+                    help='with --fused-actor: the TD targets in one launch from the target network(s) (soccer2d_amd.td)')
+    ap.add_argument('--double-q', action='store_true', help='the discrete env: Double DQN')
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     args = ap.parse_args()
+    if args.fused_target and args.fused_actor <= 0:
+        ap.error('--fused-target needs --fused-actor T')
+    if args.double_q and args.continuous:
+        ap.error('--double-q is for the discrete env (DQN)')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(continuous=args.continuous, turn=args.turn, use_turn=args.useturn,
               actor_out_size=args.actor_out_size if (args.turn and args.continuous) else 1)
     env = GoToCenterVecEnv(args.envs, args.device, **kw)
     test_env = GoToCenterVecEnv(args.envs, args.device, seed=1234, **kw)
-    learner = dict(net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha, per_beta=args.per_beta)
-    model, test = (GtcDDPG(env, **learner), test_ddpg) if args.continuous else (GtcDQN(env, **learner), test_dqn)
+    learner = dict(net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha, per_beta=args.per_beta,
+                   fused_target=args.fused_target)
+    model, test = (GtcDDPG(env, **learner), test_ddpg) if args.continuous else (GtcDQN(env, double_q=args.double_q, **learner), test_dqn)
     print('untrained:', test(test_env, model, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

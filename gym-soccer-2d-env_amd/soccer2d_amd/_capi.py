@@ -140,6 +140,13 @@ class S2DReplayRing(C.Structure):
                 ('reward', C.c_void_p), ('discount', C.c_void_p)]
 
 
+class S2DTdNet(C.Structure):
+    """one network of s2d_td_target_q / s2d_td_target_ac: S2DWideNet's MLP with a run-time input width (1 .. 256), the device
+    pointer of its packed parameters and the workspace the pack kernel writes"""
+    _fields_ = [('n_in', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 5), ('n_out', C.c_int32),
+                ('activation', C.c_int32), ('params', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
 WORLD_MODEL_FIELDS = (
     'ball_dist_from_self', 'ball_angle_from_self', 'ball_relative_x', 'ball_relative_y',
     'ball_pos_dist', 'ball_pos_angle', 'ball_vel_dist', 'ball_vel_angle',
@@ -188,6 +195,11 @@ PROTOTYPES = (
     ('s2d_replay_sample_prio', C.c_int, (C.c_int64, C.c_int, C.c_int, C.POINTER(S2DReplayRing), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p)),
+    ('s2d_td_workspace_bytes', C.c_size_t, (C.POINTER(S2DTdNet),)),
+    ('s2d_td_target_q', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_td_target_ac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

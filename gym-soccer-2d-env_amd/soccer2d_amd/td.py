@@ -1,0 +1,236 @@
+"""QTarget / ActorCriticTarget: the off-policy learners' TD targets from their target networks in one launch
+(s2d_td_target_q / s2d_td_target_ac in include/s2d.h), the step that follows DeviceReplay.sample in DQN, Double DQN, DDPG and TD3:
+
+    target = reward + discount * max_a Q'(next_obs, a)                          QTarget
+    target = reward + discount * Q'(next_obs, argmax_a Q(next_obs, a))          QTarget with online=
+    target = reward + discount * min_i Q'_i(next_obs, tanh-actor'(next_obs))    ActorCriticTarget
+
+instead of the 8 - 15 small torch ops of ``r + d * q_target(next_obs).max(dim=1).values``.  The networks are the streamed-weight
+MLP of the wide actors (Linear-(F-Linear) x L, L = 1 .. 5, widths multiples of 4 in [8, 400], F = ReLU, Tanh or Sigmoid) with any
+input width up to 256, evaluated on the project's fp32 spec: at obs_dim = 10 the value bootstrapped from is the same function of
+the weights, bit for bit, that the fused actor acts on.  Engine-independent: any batch with the replay buffer's layout.
+
+Each network keeps ONE flat fp32 parameter buffer and a workspace.  The kernels read the buffers when they run: ``sync()``
+reloads them from the modules (after ``load_state_dict`` or a Polyak step for the target networks, after every optimiser step
+for ``online``), and a captured graph computes with whatever they hold at replay.  Out of scope: the online network's forward /
+backward pass and the optimiser stay in torch, the target is not fused into the sample launch, and TD3's target-policy smoothing
+noise is not added."""
+import ctypes as C
+
+import torch
+
+from . import _capi
+from .actor import _read_layers
+from .wide_actor import _WideShape
+
+MAX_IN = 256
+MAX_OUT = 64
+MAX_ACTION = 8
+_WAVE = 64
+
+
+def td_workspace_bytes(n_in, hidden, n_out):
+    """bytes of a network's workspace, by the arithmetic of the C plan (s2d_td_workspace_bytes): every layer's fragments
+    (ceil(h / 16) tiles x its k-steps, ceil(n_in / 4) for layer 1, h_(l-1) / 4 after it, 64 words each) and the biases padded to
+    their tiles"""
+    nfrag = nbias = 0
+    ks = (n_in + 3) // 4
+    for w in tuple(hidden) + (n_out,):
+        m16 = (w + 15) // 16
+        nfrag += m16 * ks
+        nbias += 16 * m16
+        ks = w // 4
+    return (nfrag * _WAVE + nbias) * 4
+
+
+class _Net:
+    """one network of a target: its module, shape, flat parameter buffer and workspace"""
+
+    def __init__(self, who, what, module, device, tanh_head=False):
+        if not isinstance(module, torch.nn.Module):
+            raise ValueError(f'{who}: the {what} must be a torch.nn.Module')
+        # the wide actors' reader and grid: Linear-(F-Linear) x L [-Tanh], one F of ReLU / Tanh / Sigmoid throughout
+        try:
+            linears, act = _read_layers(module, **dict(_WideShape._grid, tanh_head=tanh_head))
+        except ValueError as e:
+            raise ValueError(f'{who}: {what}: {e}') from None
+        if any(lin.bias is None for lin in linears):
+            raise ValueError(f'{who}: every nn.Linear of the {what} needs a bias')
+        self.hidden = _WideShape._check_shape([lin.out_features for lin in linears[:-1]], linears[-1].out_features, act)
+        self.n_in, self.n_out, self.activation = linears[0].in_features, linears[-1].out_features, act
+        if not 1 <= self.n_in <= MAX_IN:
+            raise ValueError(f'{who}: the {what}\'s input width must be in [1, {MAX_IN}], got {self.n_in}')
+        if not 1 <= self.n_out <= MAX_OUT:
+            raise ValueError(f'{who}: the {what}\'s output width must be in [1, {MAX_OUT}], got {self.n_out}')
+        self.what, self.module, self._tanh_head = what, module, tanh_head
+        dev = torch.device(device if device is not None else linears[0].weight.device)
+        # torch's device allocations are 256-byte aligned (the ABI asks for 16 of params, 256 of the workspace)
+        self.params = torch.zeros(sum(lin.weight.numel() + lin.bias.numel() for lin in linears), dtype=torch.float32, device=dev)
+        self.device = self.params.device                                     # with its index: 'cuda' -> cuda:0
+        self.workspace = torch.zeros(td_workspace_bytes(self.n_in, self.hidden, self.n_out) // 4, dtype=torch.float32, device=self.device)
+        self.sync()
+
+    def sync(self):
+        """the module's current parameters into the flat buffer: one device copy, no allocation of what the kernel reads"""
+        linears, act = _read_layers(self.module, **dict(_WideShape._grid, tanh_head=self._tanh_head))
+        shape = ([lin.in_features for lin in linears[:1]], [lin.out_features for lin in linears])
+        if act != self.activation or shape != ([self.n_in], list(self.hidden) + [self.n_out]):
+            raise ValueError(f'the {self.what} has changed its shape since from_module')
+        srcs = []
+        for lin in linears:
+            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
+        with torch.no_grad():
+            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+
+    def text(self):
+        return '-'.join(map(str, (self.n_in,) + self.hidden + (self.n_out,)))
+
+    def c_struct(self):
+        net = _capi.S2DTdNet()
+        net.n_in, net.n_hidden, net.n_out = self.n_in, len(self.hidden), self.n_out
+        for l in range(len(net.hidden)):
+            net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
+        net.activation = ('relu', 'tanh', 'sigmoid').index(self.activation)
+        net.params = self.params.data_ptr()
+        net.workspace = self.workspace.data_ptr()
+        net.workspace_bytes = self.workspace.numel() * 4
+        return net
+
+
+class _Target:
+    """what the two targets share: the networks on one device, sync() and the checks of target()'s arguments"""
+
+    _name = '_Target'
+
+    def _init_nets(self, nets):
+        self._nets = nets
+        self.device = nets[0].device
+        for n in nets[1:]:
+            if n.device != self.device:
+                raise ValueError(f'{self._name}: the {n.what} is on {n.device}, the {nets[0].what} on {self.device}')
+        self.obs_dim = nets[0].n_in
+
+    def sync(self):
+        """Reload every network's parameter buffer from its module, in place: after ``load_state_dict`` or a Polyak step for
+        the target networks, after every optimiser step for ``online``.  Stream-ordered device copies, capturable."""
+        for n in self._nets:
+            n.sync()
+        return self
+
+    def _arr(self, name, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f'{self._name}.target: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
+        return C.c_void_p(t.data_ptr())
+
+    def _batch(self, batch, out, return_q, extra_dtype, extra_shape):
+        """target()'s argument checks: (B, the pointers of next_obs / reward / discount, the three outputs)"""
+        who = f'{self._name}.target'
+        if not isinstance(batch, dict) or any(k not in batch for k in ('next_obs', 'reward', 'discount')):
+            raise ValueError(f"{who}: batch must be a dict with 'next_obs', 'reward' and 'discount' (DeviceReplay.sample's)")
+        nxt = batch['next_obs']
+        if not torch.is_tensor(nxt) or nxt.dim() != 2 or nxt.shape[0] < 1 or nxt.shape[0] >= 2 ** 31:
+            raise ValueError(f"{who}: batch['next_obs'] must be a [B, {self.obs_dim}] tensor, 1 <= B < 2^31")
+        B, f32 = nxt.shape[0], torch.float32
+        ins = [self._arr("batch['next_obs']", nxt, f32, (B, self.obs_dim)), self._arr("batch['reward']", batch['reward'], f32, (B,)),
+               self._arr("batch['discount']", batch['discount'], f32, (B,))]
+        if out is None:
+            outs = [torch.empty((B,), dtype=f32, device=self.device)]
+            if return_q:
+                outs += [torch.empty((B,), dtype=f32, device=self.device), torch.empty((B,) + extra_shape, dtype=extra_dtype, device=self.device)]
+        else:
+            outs = list(out) if isinstance(out, (tuple, list)) else [out]
+            if len(outs) != (3 if return_q else 1):
+                raise ValueError(f'{who}: out must be ' + ('a tuple of three tensors (target, q, the index or action)' if return_q
+                                                           else 'one tensor [B]'))
+        shapes = [((B,), f32), ((B,), f32), ((B,) + extra_shape, extra_dtype)]
+        ptrs = [self._arr(f'out[{j}]' if return_q else 'out', t, shapes[j][1], shapes[j][0]) for j, t in enumerate(outs)]
+        ptrs += [None] * (3 - len(ptrs))
+        if self.device.type != 'cuda':
+            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
+        return B, ins, ptrs, (tuple(outs) if return_q else outs[0])
+
+
+class QTarget(_Target):
+    """``reward + discount * max_a q_target(next_obs)[a]`` (DQN), or with ``online`` the target network's value at the online
+    network's argmax (Double DQN), in one launch.  Both modules are Linear-(F-Linear) x L (SB3's ``q_net_target.q_net`` /
+    ``q_net.q_net``) with the same input and output widths; hidden shapes and activations may differ."""
+
+    _name = 'QTarget'
+
+    def __init__(self, q_target, online=None, device=None):
+        tgt = _Net('QTarget', 'target Q-network', q_target, device)
+        nets = [tgt]
+        if online is not None:
+            onl = _Net('QTarget', 'online Q-network', online, device if device is not None else tgt.device)
+            if (onl.n_in, onl.n_out) != (tgt.n_in, tgt.n_out):
+                raise ValueError(f'QTarget: the online Q-network is {onl.text()}, the target {tgt.text()}: input and output widths must '
+                                 'be the same')
+            nets.append(onl)
+        self.q_target, self.online = tgt, (nets[1] if online is not None else None)
+        self.n_actions = tgt.n_out
+        self._init_nets(nets)
+
+    @classmethod
+    def from_module(cls, q_target, online=None, device=None):
+        """A target shaped like the modules, loaded from them.  device: where the buffers live (default: the modules')."""
+        return cls(q_target, online=online, device=device)
+
+    def target(self, batch, out=None, return_q=False):
+        """float32 [B] targets of the dict DeviceReplay.sample / PrioritizedReplay.sample returns (its 'next_obs' [B, obs_dim],
+        'reward' and 'discount' [B]).  return_q: (target, q [B], index int32 [B]): the bootstrapped value and the action it was
+        read at.  out: the tensor (with return_q the tuple of three) of an earlier call, written again (a captured graph replays
+        into it).  Stream-ordered on torch's current stream, capturable."""
+        B, ins, outs, result = self._batch(batch, out, return_q, torch.int32, ())
+        lib = _capi.load_library()
+        net, onl = self.q_target.c_struct(), (self.online.c_struct() if self.online is not None else None)
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_td_target_q(B, C.byref(net), C.byref(onl) if onl is not None else None, *ins, *outs,
+                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, 's2d_td_target_q')
+        return result
+
+
+class ActorCriticTarget(_Target):
+    """``reward + discount * q_target(cat(next_obs, mu_target(next_obs)))`` (DDPG), with ``q_target2`` the smaller of the two
+    critics' values (TD3's clipped double-Q, without target-policy smoothing noise), in one launch.  mu_target is
+    Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs (SB3's ``actor_target.mu``); a critic is Linear-(F-Linear) x L from
+    obs_dim + A inputs to one output (SB3's ``critic_target.qf0``)."""
+
+    _name = 'ActorCriticTarget'
+
+    def __init__(self, mu_target, q_target, q_target2=None, device=None):
+        who = 'ActorCriticTarget'
+        act = _Net(who, 'target actor', mu_target, device, tanh_head=True)
+        if not 1 <= act.n_out <= MAX_ACTION:
+            raise ValueError(f'{who}: the target actor has {act.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+        dev = device if device is not None else act.device
+        critics = [_Net(who, 'target critic 1', q_target, dev)]
+        if q_target2 is not None:
+            critics.append(_Net(who, 'target critic 2', q_target2, dev))
+        for c in critics:
+            if c.n_in != act.n_in + act.n_out or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
+                                 f'{act.n_in} + {act.n_out} inputs and give one output')
+        self.mu_target, self.critics = act, tuple(critics)
+        self.action_dim = act.n_out
+        self._init_nets([act] + critics)
+
+    @classmethod
+    def from_modules(cls, mu_target, q_target, q_target2=None, device=None):
+        """A target shaped like the modules, loaded from them.  device: where the buffers live (default: the actor's)."""
+        return cls(mu_target, q_target, q_target2=q_target2, device=device)
+
+    def target(self, batch, out=None, return_q=False):
+        """float32 [B] targets of a sampled batch, as QTarget.target.  return_q: (target, q [B], action [B, A]): the bootstrapped
+        value and the target actor's action it was evaluated at."""
+        B, ins, outs, result = self._batch(batch, out, return_q, torch.float32, (self.action_dim,))
+        lib = _capi.load_library()
+        nets = [n.c_struct() for n in self._nets]
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_td_target_ac(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, *outs,
+                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, 's2d_td_target_ac')
+        return result
+
+
+__all__ = ['QTarget', 'ActorCriticTarget', 'td_workspace_bytes']

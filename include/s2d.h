@@ -522,6 +522,54 @@ int s2d_replay_prio_update(int64_t batch, int64_t capacity, float *tree, const u
 int s2d_replay_sample_prio(int64_t batch, int obs_dim, int action_words, const S2DReplayRing *ring, const float *tree,
                            uint64_t *cursor, uint64_t seed, void *b_obs, void *b_next, void *b_action, float *b_reward,
                            float *b_discount, int32_t *b_index, float *b_priority, float *b_total, void *stream);
+
+/* ---- TD targets from the target networks (s2d_td.hip) ----
+ * What follows a sampled batch in every off-policy learner and needs no gradient: reward + discount * bootstrap(next_obs), in
+ * one launch.  Engine-independent like s2d_gae and s2d_replay_*: no handle, raw device pointers, any stream of the current
+ * device; everything is read WHEN THE KERNELS RUN, so sample -> target can be captured as a linear chain on one stream.
+ *
+ * The network is S2DWideNet's MLP with a run-time input width: n_in -> h_1 -> ... -> h_L -> n_out, every unit
+ *   acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc)
+ * layer 1 over k = 0 .. 4 ceil(n_in / 4) - 1 with x_k = 0 against zero weights past n_in (n_in = 10: the reach-ball actors' 12
+ * terms; n_in = 4: the GoToCenter actors' single k-step), later layers over exactly h_(l-1) terms; relu (v > 0 ? v : +0), tanh_spec or
+ * sigmoid_spec between the layers and a linear output layer: at n_in = 10 the same function of the parameters, bit for bit, that
+ * s2d_rollout_qnet_wide / s2d_rollout_actor_wide act on.  A call first rewrites every network's params in fragment order into its
+ * workspace (a pack kernel on the caller's stream), so a captured graph computes with whatever the parameter buffers hold at
+ * replay.  A workspace belongs to one call at a time, and every network of a call needs its own.  The result does not depend on
+ * the launch plan (S2D_TD_PLAN=waves,tiles in the environment, read at every launch, overrides it for testing). */
+typedef struct S2DTdNet {
+  int32_t n_in;            /* 1 .. 256 */
+  int32_t n_hidden;        /* 1 .. 5 */
+  int32_t hidden[5];       /* multiples of 4 in [8, 400]; 0 past n_hidden */
+  int32_t n_out;           /* 1 .. 64 */
+  int32_t activation;      /* 0 relu, 1 tanh_spec, 2 sigmoid_spec */
+  const float *params;     /* nn.Sequential order, contiguous, 16-byte aligned */
+  void *workspace;         /* 256-byte aligned, >= s2d_td_workspace_bytes() */
+  size_t workspace_bytes;
+} S2DTdNet;
+/* bytes of workspace of a shape (the pointers are not read); 0 for a shape off the grid.  Host only, needs no GPU. */
+size_t s2d_td_workspace_bytes(const S2DTdNet *shape);
+/* DQN and Double DQN.  Per row b: y = target(next_obs[b]); a* = argmax(y) by the actors' scan (best = 0; for a = 1 .. A-1:
+ * if (y[a] > y[best]) best = a -- lowest index on ties, a NaN never replaces the best, an all-NaN row gives 0); with online !=
+ * NULL a* is that argmax of online(next_obs[b]) instead (same n_in and n_out; hidden shape and activation may differ).
+ * q = y[a*]; out_target[b] = reward[b] + (discount[b] * q): one fp32 multiply, then one fp32 add, never contracted -- what eager
+ * torch's r + d * q computes.  There are NO special cases: discount = 0 with q = +-inf gives NaN, as in torch.  out_q[b] <- q and
+ * out_index[b] <- a* where given.  Enqueues the pack kernel(s) and one target kernel.  S2D_EINVAL without a launch: a NULL,
+ * misaligned or too small workspace, a shape off the grid, NULL or misaligned params (16 bytes), online's n_in / n_out differing
+ * from target's, batch outside [1, 2^31 - 1], NULL or misaligned (4 bytes) next_obs / reward / discount / out_target, misaligned
+ * optional outputs, the two networks sharing a workspace. */
+int s2d_td_target_q(int64_t batch, const S2DTdNet *target, const S2DTdNet *online /* NULL: plain DQN */,
+                    const float *next_obs /* [B][n_in] */, const float *reward, const float *discount,
+                    float *out_target /* [B] */, float *out_q /* [B] or NULL */, int32_t *out_index /* [B] or NULL */, void *stream);
+/* DDPG, and TD3's clipped double-Q (without target-policy smoothing noise).  Per row b, with D = actor->n_in and A = actor->n_out
+ * in [1, 8]: a'[i] = tanh_spec(actor(next_obs[b])[i]) (the tanh actor's head without noise and without epsilon); the critics' input
+ * row is [next_obs[b] (D words) | a' (A words)], so critic->n_in == D + A and critic->n_out == 1; q = critic1(row)[0], with critic2
+ * q = q2 < q1 ? q2 : q1 (a NaN in q2 never replaces q1); out_target[b] as above; out_q[b] <- q, out_action[b][i] <- a'[i] where
+ * given.  All networks run on one row tile in one kernel: the critics' input never passes through memory.  S2D_EINVAL without a
+ * launch as above, plus: actor->n_out outside [1, 8], a critic whose n_in is not D + A or whose n_out is not 1. */
+int s2d_td_target_ac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
+                     const float *next_obs /* [B][actor->n_in] */, const float *reward, const float *discount, float *out_target,
+                     float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
