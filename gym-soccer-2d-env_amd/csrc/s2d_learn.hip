@@ -1,0 +1,425 @@
+// s2d_learn.hip -- one gradient step of a Q-network on a sampled batch (include/s2d.h S2DLearnNet / S2DLearnState, s2d_learn_q /
+// s2d_learn_q_grad): forward, TD error and its MSE / Huber derivative, backward, gradient-norm clip and Adam,
+// the link between s2d_td_target_q and the priority update.  Engine-independent, as s2d_td_* and s2d_replay_*: raw device
+// pointers, any stream of the current device, parameters, hyper-parameters and step state all read when the kernels run, a linear
+// chain of three launches on one stream.
+//
+// Every chain is the spec's (tests/learn_ref.c), on the VALU:
+//   forward    acc = b[j]; k ascending: acc = fmaf(W[j][k], in[k], acc)      -- the bits of s2d_td_target_q and the wide actors
+//   backward   s = +0; j ascending: s = fmaf(W[j][k], delta[j], s), times the activation's derivative from the stored output
+//   dW, db     per block of S2D_LEARN_BLOCK_ROWS rows: acc = +0; rows ascending: acc = fmaf(delta[row][j], in[row][k], acc)
+// so no result depends on the grid, the waves of a workgroup, where the activations live or the number of compute units, and there
+// is no float atomic anywhere: block partials go to the workspace and are added in ascending block order.
+//
+//   s2d_learn_block_kernel   one workgroup (4 waves) per block of 64 rows.  A row of the block's image holds
+//                            [x: 4 ceil(n_in / 4) | y_1: h_1 | ... | y_L: h_L | q: n_out]; a layer's delta overwrites its output once
+//                            that has been used.  The image is in LDS where 64 rows (and the rows' 64 losses) fit 160 KiB,
+//                            else in the workspace.
+//                            forward and delta: lane = row, a wave takes tiles of 8 units, the weights are wave-uniform;
+//                            dW: a thread takes 4 units x one input, the rows are the chain.
+//   s2d_learn_reduce_kernel  grad[p] = block partials in ascending order; per chunk of S2D_LEARN_NORM_CHUNK words the sum of
+//                            squares, fmaf ascending; (step) the beta products are multiplied here, once per call.
+//   s2d_learn_finish_kernel  chunks added ascending, norm, clip scale, mean loss; (step) Adam on every word.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <mutex>
+#include <string>
+
+#include "s2d_wide_net.h"
+
+extern "C" void s2d_internal_set_error(const char* msg);
+
+static constexpr int kLearnRows = S2D_LEARN_BLOCK_ROWS;
+static constexpr int kLearnChunk = S2D_LEARN_NORM_CHUNK;
+static constexpr int kLearnThreads = 256;
+static constexpr int kLearnMaxHidden = 4;
+static_assert(kLearnRows == kWave, "lane = row of the block");
+static_assert(kLearnChunk == kLearnThreads, "one thread per word of a chunk");
+
+// the network as the kernels see it (no array indexed by the layer: it would live in scratch)
+struct LearnDev {
+  int n_in, kp;        // input width and its padded row: 4 ceil(n_in / 4)
+  int n_hidden, act;   // L in 1 .. 4; 0 relu, 1 tanh_spec, 2 sigmoid_spec
+  uint32_t widths;     // h_l / 8 in bits 8 (l - 1) .. 8 l - 1
+  int na;              // outputs, 1 .. 64
+  int P;               // parameters
+  int pitch;           // words of a row of the block's image
+};
+S2D_DEV int learn_width(const LearnDev& d, int l) { return l < d.n_hidden ? 8 * (int)((d.widths >> (8 * l)) & 255u) : d.na; }
+
+S2D_DEV float learn_dact(int act, float y, float s) {
+  if (act == 0) return y > 0.0f ? s : 0.0f;
+  if (act == 1) return s * (1.0f - y * y);
+  return s * (y * (1.0f - y));
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_block_kernel(LearnDev d, int64_t batch, int loss_kind,
+                                                                        const float* __restrict__ params, float* __restrict__ part,
+                                                                        float* __restrict__ loss_part, float* __restrict__ image,
+                                                                        const float* __restrict__ obs, const int32_t* __restrict__ action,
+                                                                        const float* __restrict__ target, const float* __restrict__ weight,
+                                                                        float* __restrict__ out_td_abs, float* __restrict__ out_q,
+                                                                        int32_t* __restrict__ error) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [the rows' losses: 64 | the image, if it lives here]
+  float* const row_loss = smem;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int64_t row0 = (int64_t)blockIdx.x * kLearnRows;
+  const int rows = (int)(batch - row0 < kLearnRows ? batch - row0 : kLearnRows);
+  const int pitch = d.pitch, L = d.n_hidden, A = d.na;
+  float* const img = LDS ? smem + kLearnRows : image + (size_t)blockIdx.x * kLearnRows * pitch;
+
+  // the block's input rows, zeros past n_in and past the batch
+  for (int idx = tid; idx < kLearnRows * d.kp; idx += kLearnThreads) {
+    const int r = idx / d.kp, k = idx - r * d.kp;
+    img[r * pitch + k] = (r < rows && k < d.n_in) ? obs[(row0 + r) * d.n_in + k] : 0.0f;
+  }
+  __syncthreads();
+
+  // ---- forward
+  int in_off = 0, win = d.n_in, kk = d.kp, po = 0;
+  for (int l = 0; l <= L; ++l) {
+    const int wout = learn_width(d, l), out_off = in_off + kk;
+    const float* const W = params + po;
+    const float* const b = W + wout * win;
+    const float* const in = img + lane * pitch + in_off;
+    float* const out = img + lane * pitch + out_off;
+    const int act = l < L ? d.act : 3;
+    for (int j0 = 8 * wv; j0 < wout; j0 += 8 * (kLearnThreads / kWave)) {
+      float acc[8];
+      int jc[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        jc[u] = j0 + u < wout ? j0 + u : wout - 1;
+        acc[u] = b[jc[u]];
+      }
+      for (int k = 0; k < win; ++k) {
+        const float x = in[k];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = fmaf(W[jc[u] * win + k], x, acc[u]);
+      }
+      for (int k = win; k < kk; ++k) {            // layer 1's terms past n_in: x_k = 0 against zero weights
+        const float x = in[k];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = fmaf(0.0f, x, acc[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float v = acc[u];
+        const float y = act == 0 ? (v > 0.0f ? v : 0.0f) : act == 1 ? tanh_spec(v) : act == 2 ? sigmoid_spec(v) : v;
+        if (j0 + u < wout) out[j0 + u] = y;
+      }
+    }
+    __syncthreads();
+    po += wout * win + wout;
+    in_off = out_off; win = wout; kk = wout;
+  }
+  // in_off: the output layer's columns; po == P
+
+  // ---- the rows' outputs, TD errors, losses and output deltas
+  if (out_q)
+    for (int idx = tid; idx < rows * A; idx += kLearnThreads) {
+      const int r = idx / A, j = idx - r * A;
+      out_q[(row0 + r) * A + j] = img[r * pitch + in_off + j];
+    }
+  __syncthreads();
+  if (tid < kLearnRows) {
+    float* const q = img + tid * pitch + in_off;
+    float g = 0.0f, wl = 0.0f;
+    int a = -1;
+    if (tid < rows) {
+      const int64_t i = row0 + tid;
+      const int32_t ai = action[i];
+      const bool ok = ai >= 0 && ai < A;
+      if (!ok) atomicOr(error, 1);
+      const float e = ok ? q[ai] - target[i] : 0.0f;
+      if (out_td_abs) out_td_abs[i] = fabsf(e);
+      const float w = weight ? weight[i] : 1.0f;
+      const float sq = (0.5f * e) * e, ab = fabsf(e);
+      const float l1 = loss_kind == 0 ? sq : (ab <= 1.0f ? sq : ab - 0.5f);
+      const float dd = loss_kind == 0 ? e : (e < -1.0f ? -1.0f : (e > 1.0f ? 1.0f : e));
+      wl = ok ? w * l1 : 0.0f;
+      g = (w * dd) / (float)batch;
+      a = ok ? ai : -1;
+    }
+    for (int j = 0; j < A; ++j) q[j] = j == a ? g : 0.0f;
+    row_loss[tid] = wl;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.0f;
+    for (int r = 0; r < rows; ++r) s = s + row_loss[r];
+    loss_part[blockIdx.x] = s;
+  }
+
+  // ---- backward, layer L down to 0
+  float* const mine = part + (size_t)blockIdx.x * d.P;
+  int out_off = in_off;
+  for (int l = L; l >= 0; --l) {
+    const int wout = learn_width(d, l);
+    win = l ? learn_width(d, l - 1) : d.n_in;
+    in_off = out_off - (l ? win : d.kp);
+    po -= wout * win + wout;
+    // this block's dW: 4 units x one input per thread, rows ascending
+    const int items = ((wout + 3) >> 2) * win;
+    for (int idx = tid; idx < items; idx += kLearnThreads) {
+      const int jt = idx / win, k = idx - jt * win, j0 = 4 * jt;
+      int jc[4];
+      float acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        jc[u] = out_off + (j0 + u < wout ? j0 + u : wout - 1);
+        acc[u] = 0.0f;
+      }
+      for (int r = 0; r < rows; ++r) {
+        const float* const row = img + r * pitch;
+        const float x = row[in_off + k];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = fmaf(row[jc[u]], x, acc[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (j0 + u < wout) mine[po + (j0 + u) * win + k] = acc[u];
+    }
+    for (int j = tid; j < wout; j += kLearnThreads) {
+      float acc = 0.0f;
+      for (int r = 0; r < rows; ++r) acc = fmaf(img[r * pitch + out_off + j], 1.0f, acc);
+      mine[po + wout * win + j] = acc;
+    }
+    __syncthreads();
+    if (l) {
+      // the delta of the layer below over its stored output: lane = row, 8 units a tile (hidden widths are multiples of 8)
+      const float* const W = params + po;
+      const float* const dl = img + lane * pitch + out_off;
+      float* const y = img + lane * pitch + in_off;
+      for (int k0 = 8 * wv; k0 < win; k0 += 8 * (kLearnThreads / kWave)) {
+        float s[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s[u] = 0.0f;
+        for (int j = 0; j < wout; ++j) {
+          const float dj = dl[j];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) s[u] = fmaf(W[j * win + k0 + u], dj, s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) y[k0 + u] = learn_dact(d.act, y[k0 + u], s[u]);
+      }
+      __syncthreads();
+    }
+    out_off = in_off;
+  }
+}
+
+// grad[p] = the blocks' partials added in ascending block order; chunk_ss[c] = fmaf(g, g, .) ascending over the chunk's words
+template <bool UPDATE>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_reduce_kernel(int P, int64_t blocks, const float* __restrict__ part,
+                                                                         float* __restrict__ grad, float* __restrict__ chunk_ss,
+                                                                         float* __restrict__ hyper) {
+  __shared__ float g2[kLearnChunk];
+  const int tid = threadIdx.x, p = blockIdx.x * kLearnChunk + tid;
+  float s = 0.0f;
+  if (p < P) {
+    s = part[p];
+    for (int64_t b = 1; b < blocks; ++b) s = s + part[(size_t)b * P + p];
+    grad[p] = s;
+  }
+  g2[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    const int n = P - blockIdx.x * kLearnChunk < kLearnChunk ? P - blockIdx.x * kLearnChunk : kLearnChunk;
+    float ss = 0.0f;
+    for (int i = 0; i < n; ++i) ss = fmaf(g2[i], g2[i], ss);
+    chunk_ss[blockIdx.x] = ss;
+    if (UPDATE && blockIdx.x == 0) {                 // beta1^t, beta2^t: multiplied once per call, read by the finish kernel
+      hyper[5] = hyper[5] * hyper[1];
+      hyper[6] = hyper[6] * hyper[2];
+    }
+  }
+}
+
+// norm, clip scale and mean loss (workgroup 0 stores them); UPDATE: Adam on the chunk's words with g' = g * scale
+template <bool UPDATE>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, int64_t batch, int64_t blocks, int chunks,
+                                                                         const float* __restrict__ chunk_ss,
+                                                                         const float* __restrict__ loss_part, const float* __restrict__ grad,
+                                                                         const float* __restrict__ hyper, float* __restrict__ stats,
+                                                                         float* __restrict__ params, float* __restrict__ m,
+                                                                         float* __restrict__ v) {
+  __shared__ float sh_scale;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    float ss = chunk_ss[0];
+    for (int c = 1; c < chunks; ++c) ss = ss + chunk_ss[c];
+    const float norm = sqrtf(ss), mx = hyper[4];
+    float scale = 1.0f;
+    if (mx > 0.0f) {
+      const float c = mx / (norm + 1e-6f);
+      scale = c < 1.0f ? c : 1.0f;
+    }
+    sh_scale = scale;
+    if (blockIdx.x == 0) {
+      float ls = loss_part[0];
+      for (int64_t b = 1; b < blocks; ++b) ls = ls + loss_part[b];
+      stats[0] = ls / (float)batch;
+      stats[1] = norm;
+      stats[2] = scale;
+    }
+  }
+  if (!UPDATE) return;
+  __syncthreads();
+  const int p = blockIdx.x * kLearnChunk + tid;
+  if (p >= P) return;
+  const float scale = sh_scale;
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], b1t = hyper[5], b2t = hyper[6];
+  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+  const float bc2s = sqrtf(1.0f - b2t), step = lr / (1.0f - b1t);
+  const float gp = grad[p] * scale;
+  const float m0 = m[p];
+  const float mn = m0 + (gp - m0) * omb1;
+  const float vn = v[p] * b2 + (omb2 * gp) * gp;
+  const float den = sqrtf(vn) / bc2s + eps;
+  m[p] = mn;
+  v[p] = vn;
+  params[p] = params[p] - step * (mn / den);
+}
+
+// ------------------------------------------------------------------------------------------ host
+namespace {
+int fail(const std::string& who, const std::string& msg) {
+  s2d_internal_set_error((who + ": " + msg).c_str());
+  return S2D_EINVAL;
+}
+bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
+
+// "" if the shape is on the learner's grid, else the text naming the field
+std::string shape_error(const S2DLearnNet* n) {
+  if (n->n_in < 1 || n->n_in > 256) return "n_in must be in [1, 256]";
+  if (n->n_hidden < 1 || n->n_hidden > kLearnMaxHidden) return "n_hidden must be in [1, 4]";
+  for (int l = 0; l < 5; ++l) {
+    const int w = n->hidden[l];
+    if (l < n->n_hidden ? (w < 8 || w > 256 || w % 8) : w != 0) return "hidden widths must be multiples of 8 in [8, 256], and 0 past n_hidden";
+  }
+  if (n->n_out < 1 || n->n_out > 64) return "n_out must be in [1, 64]";
+  if (n->activation < 0 || n->activation > 2) return "activation must be 0 (ReLU), 1 (Tanh) or 2 (Sigmoid)";
+  return "";
+}
+LearnDev net_dev(const S2DLearnNet* n) {
+  LearnDev d{};
+  d.n_in = n->n_in; d.kp = (n->n_in + 3) / 4 * 4; d.n_hidden = n->n_hidden; d.act = n->activation; d.na = n->n_out;
+  int win = n->n_in, row = d.kp;
+  for (int l = 0; l <= n->n_hidden; ++l) {
+    const int w = l < n->n_hidden ? n->hidden[l] : n->n_out;
+    if (l < n->n_hidden) d.widths |= (uint32_t)(w / 8) << (8 * l);
+    d.P += w * win + w;
+    row += w;
+    win = w;
+  }
+  d.pitch = row | 1;                                  // odd: lanes that read one column of 64 rows hit 64 different banks
+  return d;
+}
+// the workspace of a shape and a batch, in words: [partials: blocks x P | chunk sums | loss partials | images, if not in LDS]
+struct LearnLayout {
+  size_t part, chunk, loss, image, words;
+  bool lds;
+};
+size_t round64(size_t w) { return (w + 63) & ~(size_t)63; }
+LearnLayout layout(const LearnDev& d, int64_t batch) {
+  LearnLayout y{};
+  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)d.P + kLearnChunk - 1) / kLearnChunk;
+  y.lds = (size_t)kLearnRows * (d.pitch + 1) * sizeof(float) <= kLdsMax;
+  y.part = 0;
+  y.chunk = round64(blocks * d.P);
+  y.loss = y.chunk + round64(chunks);
+  y.image = y.loss + round64(blocks);
+  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * d.pitch));
+  return y;
+}
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+  return p < q + nb && q < p + na;
+}
+bool allow_lds(const void* fn) {
+  static std::mutex mu;
+  static bool set[kMaxDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!set[dev]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
+    set[dev] = true;
+  }
+  return true;
+}
+
+template <bool UPDATE>
+int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S2DLearnState* st, const float* obs, const int32_t* action,
+          const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
+  if (!net || !st) return fail(who, "net and state must be non-NULL");
+  const std::string bad = shape_error(net);
+  if (!bad.empty()) return fail(who, "net: " + bad);
+  if (st->loss_kind != S2D_LEARN_MSE && st->loss_kind != S2D_LEARN_HUBER) return fail(who, "state: loss_kind must be 0 (MSE) or 1 (Huber)");
+  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  if (!net->params || misaligned(net->params, 16)) return fail(who, "net: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!net->workspace || misaligned(net->workspace, 256)) return fail(who, "net: workspace must be a non-NULL, 256-byte aligned device pointer");
+  if (!st->grad || misaligned(st->grad, 16) || !st->hyper || misaligned(st->hyper, 4) || !st->stats || misaligned(st->stats, 4) ||
+      !st->error || misaligned(st->error, 4))
+    return fail(who, "state: grad (16 bytes), hyper, stats and error (4 bytes) must be non-NULL, aligned device pointers");
+  if (UPDATE && (!st->m || !st->v || misaligned(st->m, 16) || misaligned(st->v, 16)))
+    return fail(who, "state: m and v must be non-NULL, 16-byte aligned device pointers");
+  if (!obs || !action || !target || misaligned(obs, 4) || misaligned(action, 4) || misaligned(target, 4))
+    return fail(who, "obs, action and target must be non-NULL, 4-byte aligned device pointers");
+  if (misaligned(weight, 4) || misaligned(out_td_abs, 4) || misaligned(out_q, 4))
+    return fail(who, "weight, out_td_abs and out_q must be 4-byte aligned device pointers (or NULL)");
+  const LearnDev d = net_dev(net);
+  const LearnLayout y = layout(d, batch);
+  if (net->workspace_bytes < y.words * sizeof(float))
+    return fail(who, "net: workspace_bytes is " + std::to_string(net->workspace_bytes) + ", a batch of " + std::to_string(batch) + " needs " +
+                         std::to_string(y.words * sizeof(float)) + " (s2d_learn_workspace_bytes: batch is above the workspace's max_batch)");
+  const size_t pb = (size_t)d.P * sizeof(float);
+  const void* bufs[5] = {net->params, st->grad, net->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr};
+  const size_t lens[5] = {pb, pb, y.words * sizeof(float), pb, pb};
+  for (int i = 0; i < 5; ++i)
+    for (int j = i + 1; j < 5; ++j)
+      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
+        return fail(who, "params, m, v, grad and the workspace must not overlap one another");
+  using Block = void (*)(LearnDev, int64_t, int, const float*, float*, float*, float*, const float*, const int32_t*, const float*, const float*,
+                         float*, float*, int32_t*);
+  const Block kb = y.lds ? s2d_learn_block_kernel<true> : s2d_learn_block_kernel<false>;
+  const size_t lds = (size_t)kLearnRows * ((y.lds ? d.pitch : 0) + 1) * sizeof(float);
+  if (lds > 48 * 1024 && !allow_lds(reinterpret_cast<const void*>(kb))) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  float* const ws = static_cast<float*>(net->workspace);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
+  const int chunks = (d.P + kLearnChunk - 1) / kLearnChunk;
+  hipLaunchKernelGGL(kb, dim3((unsigned)blocks), dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part,
+                     ws + y.loss, ws + y.image, obs, action, target, weight, out_td_abs, out_q, st->error);
+  hipLaunchKernelGGL(s2d_learn_reduce_kernel<UPDATE>, dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, d.P, blocks, ws + y.part, st->grad,
+                     ws + y.chunk, st->hyper);
+  hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, d.P, batch, blocks,
+                     chunks, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return S2D_OK;
+  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
+  return S2D_EHIP;
+}
+}  // namespace
+
+S2D_API size_t s2d_learn_workspace_bytes(const S2DLearnNet* shape, int64_t max_batch) {
+  if (!shape || !shape_error(shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  return layout(net_dev(shape), max_batch).words * sizeof(float);
+}
+
+S2D_API int s2d_learn_q(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, const int32_t* action,
+                        const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
+  return learn<true>("s2d_learn_q", batch, net, state, obs, action, target, weight, out_td_abs, out_q, stream);
+}
+
+S2D_API int s2d_learn_q_grad(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, const int32_t* action,
+                             const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
+  return learn<false>("s2d_learn_q_grad", batch, net, state, obs, action, target, weight, out_td_abs, out_q, stream);
+}

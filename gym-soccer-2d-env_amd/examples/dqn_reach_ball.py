@@ -15,7 +15,9 @@ with sync() after every optimiser phase and Timeouts bootstrap from the recorded
 record goes into a soccer2d_amd.replay.DeviceReplay in one launch and a batch comes out in one; --n-step K stores
 K-step returns (targets R + discount * max Q_target(next)).  --fused-target computes those targets in one launch from the target
 network (soccer2d_amd.td.QTarget) instead of a chain of torch ops; --double-q reads the target network's value at
-the online network's argmax (Double DQN), with or without --fused-target.
+the online network's argmax (Double DQN), with or without --fused-target.  --fused-learner (with --fused-actor and --fused-target)
+makes every update one call of soccer2d_amd.learn.QLearner -- forward, backward, clip and Adam in HIP -- so an
+update is sample -> target -> step (-> update_priorities with --per-alpha).
 """
 import argparse
 import copy
@@ -77,11 +79,12 @@ class DeviceReplay:
 class DeviceDQN:
     def __init__(self, env, lr=1e-3, gamma=0.99, buffer=1 << 20, batch=4096, target_every=50, grad_steps=4,
                  eps_start=1.0, eps_end=0.05, eps_decay_steps=300, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0,
-                 per_beta=0.4, fused_target=False, double_q=False):
+                 per_beta=0.4, fused_target=False, double_q=False, fused_learner=False):
         torch.manual_seed(seed)
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
         self.fused_target, self.double_q = fused_target, double_q
+        self.fused_learner, self.lr = fused_learner, lr
         self.env, self.dev = env, env.device
         self.n_act = env.action_space.n
         self.general = net_arch is not None or activation != 'relu'      # a network only the general fused actor takes
@@ -167,6 +170,10 @@ class DeviceDQN:
             from soccer2d_amd.td import QTarget
             self.td = QTarget.from_module(self.q_target, online=self.q if self.double_q else None, device=self.dev)
             self.ftgt = torch.empty((self.batch,), dtype=torch.float32, device=self.dev)
+        if self.fused_learner and not hasattr(self, 'learner'):
+            from soccer2d_amd.learn import QLearner      # self.q's parameters become views of the learner's flat buffer
+            self.learner = QLearner.from_module(self.q, lr=self.lr, max_grad_norm=10.0, loss='huber', max_batch=self.batch, device=self.dev)
+            self.fabs = torch.empty((self.batch,), dtype=torch.float32, device=self.dev)
 
     def optimise_fused(self, n_updates):
         """optimise() on batches of the fused replay buffer: reward is the n-step return, discount gamma^k or 0.  With
@@ -174,6 +181,16 @@ class DeviceDQN:
         get (|TD error| + 1e-6) ** alpha as their new priority."""
         for _g in range(n_updates):
             b = self.frb.sample(self.batch, out=self.fbatch)
+            if self.fused_learner:                               # sample -> target -> step (-> priorities): one launch chain
+                if self.double_q:
+                    self.td.online.sync()
+                tgt = self.td.target(b, out=self.ftgt)
+                if self.per_alpha > 0:
+                    self.learner.step(b, tgt, weight=self.frb.weights(b, self.per_beta), td_abs_out=self.fabs)
+                    self.frb.update_priorities(b['index'], (self.fabs + 1e-6) ** self.per_alpha)
+                else:
+                    self.learner.step(b, tgt)
+                continue
             if self.fused_target:                                # one launch; the online network's weights as of this step
                 if self.double_q:
                     self.td.online.sync()
@@ -196,7 +213,9 @@ class DeviceDQN:
         """target-network schedule, then grad_steps updates per collected vector step and the actor's new weights"""
         for _t in range(T):
             self.steps += 1
-            if self.steps % self.target_every == 0:
+            if self.steps % self.target_every == 0 and self.fused_learner:
+                self.learner.update_target(self.td)              # flat buffer to flat buffer; the target module follows
+            elif self.steps % self.target_every == 0:
                 self.q_target.load_state_dict(self.q.state_dict())
                 if self.fused_target:
                     self.td.q_target.sync()                      # the target launch reads the new weights
@@ -275,14 +294,18 @@ def main():
                     help='with --fused-actor: the TD targets in one launch from the target network (soccer2d_amd.td.QTarget)')
     ap.add_argument('--double-q', action='store_true', help="Double DQN: the target network's value at the online network's argmax")
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help='with --fused-actor and --fused-target: forward, backward, clip and Adam in one call (soccer2d_amd.learn.QLearner)')
     args = ap.parse_args()
     if args.fused_target and args.fused_actor <= 0:
         ap.error('--fused-target needs --fused-actor T')
+    if args.fused_learner and not (args.fused_actor > 0 and args.fused_target):
+        ap.error('--fused-learner needs --fused-actor T and --fused-target')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kewargs)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
     model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
-                      per_beta=args.per_beta, fused_target=args.fused_target, double_q=args.double_q)
+                      per_beta=args.per_beta, fused_target=args.fused_target, double_q=args.double_q, fused_learner=args.fused_learner)
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

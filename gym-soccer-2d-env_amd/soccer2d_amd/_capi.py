@@ -140,6 +140,20 @@ class S2DReplayRing(C.Structure):
                 ('reward', C.c_void_p), ('discount', C.c_void_p)]
 
 
+class S2DLearnNet(C.Structure):
+    """the network of s2d_learn_q / s2d_learn_q_grad: S2DTdNet's shape on the learner's grid, its READ-WRITE parameters and the
+    workspace of the blocks' partial gradients"""
+    _fields_ = [('n_in', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 5), ('n_out', C.c_int32),
+                ('activation', C.c_int32), ('params', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+class S2DLearnState(C.Structure):
+    """the optimiser's device state: Adam's moments and the summed gradient [P], hyper = (lr, beta1, beta2, eps, max_grad_norm,
+    beta1^t, beta2^t), stats = (loss, norm, scale), the error word and the loss (0 MSE, 1 Huber)"""
+    _fields_ = [('m', C.c_void_p), ('v', C.c_void_p), ('grad', C.c_void_p), ('hyper', C.c_void_p), ('stats', C.c_void_p),
+                ('error', C.c_void_p), ('loss_kind', C.c_int32)]
+
+
 class S2DTdNet(C.Structure):
     """one network of s2d_td_target_q / s2d_td_target_ac: S2DWideNet's MLP with a run-time input width (1 .. 256), the device
     pointer of its packed parameters and the workspace the pack kernel writes"""
@@ -200,6 +214,11 @@ PROTOTYPES = (
                                   C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_td_target_ac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.c_int64)),
+    ('s2d_learn_q', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_q_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

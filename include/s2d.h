@@ -570,6 +570,66 @@ int s2d_td_target_q(int64_t batch, const S2DTdNet *target, const S2DTdNet *onlin
 int s2d_td_target_ac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
                      const float *next_obs /* [B][actor->n_in] */, const float *reward, const float *discount, float *out_target,
                      float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */, void *stream);
+/* ---- the Q-learner's gradient step (s2d_learn.hip) ----
+ * What follows the TD target in DQN, Double DQN, n-step and PER: ONE gradient step of the online Q-network on a sampled batch --
+ * forward, TD error, MSE / Huber derivative, backward, gradient-norm clip and Adam -- as a linear chain of three launches on one
+ * stream.  Engine-independent like s2d_td_*: no handle, raw device pointers, any stream of the current device; the parameters, the
+ * hyper-parameters and the step state are all read WHEN THE KERNELS RUN (there is no host step counter), so sample -> target ->
+ * step can be captured and replayed, and a scheduler writes hyper[0] (lr) between replays.
+ *
+ * The network is S2DTdNet's MLP on the learner's grid: n_in 1 .. 256, 1 .. 4 hidden layers of multiples of 8 in [8, 256], n_out
+ * 1 .. 64.  The forward pass is the same fp32 chain (acc = b[j]; k ascending: acc = fmaf(W[j][k], in[k], acc); layer 1 over
+ * 4 ceil(n_in / 4) terms), so q[b][a] has the bits s2d_td_target_q and the wide actors compute from the same parameters.
+ * Per row b: a = action[b]; e = q[b][a] - target[b]; out_td_abs[b] = |e|; d = e (MSE, loss e^2 / 2) or e < -1 ? -1 : e > 1 ? 1 : e
+ * (Huber with delta 1, loss |e| <= 1 ? e^2 / 2 : |e| - 1/2: torch's smooth_l1_loss); the output delta is (weight[b] * d) / (float)B
+ * in column a and +0 elsewhere (weight NULL: 1).  An action outside [0, n_out) is never used as an index: its row has e = 0, a
+ * zero delta and no loss, and *error |= 1.  A NaN target propagates (there are no special cases).
+ * Backward: the delta of unit k of the layer below is s = +0; j ascending: s = fmaf(W[j][k], delta[j], s), times the activation's
+ * derivative from its stored output y, separate operations: relu y > 0 ? s : +0; tanh s * (1 - y * y); sigmoid s * (y * (1 - y)).
+ * Parameter gradients: rows are cut into blocks of S2D_LEARN_BLOCK_ROWS; within a block dW[j][k] = +0; rows ascending:
+ * fmaf(delta[row][j], in[row][k], .), db[j] the same with in = 1; the blocks' partials are added in ascending block order (the first
+ * block starts the sum).  No float atomics: the gradient is a function of the inputs alone, not of the grid or the device.
+ * Norm: per chunk of S2D_LEARN_NORM_CHUNK words of the flat gradient s = +0; ascending: s = fmaf(g, g, s); chunks added ascending;
+ * norm = sqrt (correctly rounded); scale = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6f)) : 1 (clip_grad_norm_).
+ * stats <- {mean loss (block partials, rows ascending, blocks ascending, / (float)B), norm, scale}; grad <- the UNCLIPPED sum.
+ * Adam (no amsgrad, no weight decay), every step one fp32 operation: beta1^t *= beta1, beta2^t *= beta2 (device words, once per
+ * call); g' = g * scale; m += (g' - m) * (1 - beta1); v = v * beta2 + ((1 - beta2) * g') * g';
+ * p -= (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)).  A fresh state has m = v = 0 and both products 1. */
+#define S2D_LEARN_BLOCK_ROWS 64
+#define S2D_LEARN_NORM_CHUNK 256
+enum { S2D_LEARN_MSE = 0, S2D_LEARN_HUBER = 1 };
+typedef struct S2DLearnNet {
+  int32_t n_in;            /* 1 .. 256 */
+  int32_t n_hidden;        /* 1 .. 4 */
+  int32_t hidden[5];       /* multiples of 8 in [8, 256]; 0 past n_hidden */
+  int32_t n_out;           /* 1 .. 64 */
+  int32_t activation;      /* 0 relu, 1 tanh_spec, 2 sigmoid_spec */
+  float *params;           /* READ-WRITE, nn.Sequential order, contiguous, 16-byte aligned */
+  void *workspace;         /* 256-byte aligned, >= s2d_learn_workspace_bytes(shape, batch) */
+  size_t workspace_bytes;
+} S2DLearnNet;
+typedef struct S2DLearnState {
+  float *m, *v, *grad;     /* [P] each, 16-byte aligned (m and v are not read by s2d_learn_q_grad) */
+  float *hyper;            /* [7]: lr, beta1, beta2, eps, max_grad_norm, beta1^t, beta2^t */
+  float *stats;            /* [3]: mean loss, gradient norm, clip scale */
+  int32_t *error;          /* |= 1: an action outside [0, n_out) */
+  int32_t loss_kind;       /* S2D_LEARN_MSE | S2D_LEARN_HUBER */
+} S2DLearnState;
+/* bytes of workspace of a shape for batches up to max_batch (the pointers are not read): the blocks' partial gradients, the
+ * chunk and loss partials and, where 64 rows of activations do not fit the LDS, the blocks' activations.  0 for a shape off the
+ * grid or max_batch outside [1, 2^31 - 1].  Host only, needs no GPU. */
+size_t s2d_learn_workspace_bytes(const S2DLearnNet *shape, int64_t max_batch);
+/* One step.  out_td_abs [B] and out_q [B][n_out] (the forward values) may be NULL.  S2D_EINVAL without a launch and with nothing
+ * written, the text naming the field: a shape off the grid, an unknown loss_kind, batch outside [1, 2^31 - 1] or above what the
+ * workspace holds, NULL or misaligned params / workspace / m / v / grad / hyper / stats / error / obs / action / target, misaligned
+ * optional arrays, params, m, v, grad or the workspace overlapping one another. */
+int s2d_learn_q(int64_t batch, const S2DLearnNet *net, const S2DLearnState *state, const float *obs /* [B][n_in] */,
+                const int32_t *action /* [B] */, const float *target /* [B] */, const float *weight /* [B] or NULL */,
+                float *out_td_abs, float *out_q, void *stream);
+/* The same up to and including grad, stats, out_td_abs and out_q, WITHOUT touching params, m, v or the beta products: for tests
+ * and for callers with their own optimiser. */
+int s2d_learn_q_grad(int64_t batch, const S2DLearnNet *net, const S2DLearnState *state, const float *obs, const int32_t *action,
+                     const float *target, const float *weight, float *out_td_abs, float *out_q, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
