@@ -15,12 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
+#include <cstdio>
 #include <new>
 #include <string>
 
 #include "s2d_actor_launch.h"
 #include "s2d_actor_net.h"
+#include "s2d_wide_host.h"
 
 // experiment build (-DS2D_QNET_STAMPS, profiles/experiments/qnet_actor_clocks.py): per wave, the shader clocks (s_memtime) of the
 // network (observation tile + three layers + argmax), of the rest of the cycle (action draw, simulation, record stores) and of the
@@ -209,26 +210,7 @@ __global__ __launch_bounds__(kBlock) void s2d_reach_actor_rollout_kernel(S2DHot 
 }
 
 // ------------------------------------------------------------------------------------------ host side
-// The dynamic-LDS limit is a per-device property of the function: set it once per (device, instantiation `slot`), under a lock
-// (engines on several devices may be driven from several threads); the caller has made the engine's device current.  One table
-// per Owner: every back end numbers its instantiations from 0 (Owner = its Dims; s2d_policy.hip has a tag of its own).
-// kLdsSlots: the most instantiations an Owner has -- a back end's 16 (the Q head's 3, the tanh head's 2 x 3 x 2, then its
-// diagnostic kernel in the last slot); s2d_policy.hip uses 9 (3 modes x 3 noise kinds)
-static constexpr int kLdsSlots = 16;
-template <typename Owner>
-static bool allow_lds_slot(const void* fn, int slot) {
-  static std::mutex attr_mu;
-  static bool attr_set[kMaxDevices][kLdsSlots] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
-  std::lock_guard<std::mutex> lock(attr_mu);
-  if (!attr_set[dev][slot]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
-    attr_set[dev][slot] = true;
-  }
-  return true;
-}
-
+// (allow_lds_slot<Owner>, the dynamic-LDS limit of an instantiation, is s2d_wide_host.h's)
 // a back end's plan for one network: its kernel argument, the LDS words of a wave, the waves of a workgroup, the LDS bytes; and
 // its place in the buffer the entry points carry
 template <typename Dims>
@@ -316,8 +298,31 @@ static int debug_forward_launch(const std::string& who, const void* kernel, cons
   }
   const int threads = pl.waves * kWave;
   enqueue((unsigned)((n + threads - 1) / threads), threads);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return S2D_OK;
-  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
-  return S2D_EHIP;
+  return launched(who);
+}
+
+// The whole of s2d_debug_wide_forward and s2d_gtc_debug_forward (`who`): the streamed-weight network (Dims = WideDims) with input
+// width n_in.  plan(who, shape, pl) is the unit's plan, `kernel` its instantiation of s2d_wide_debug_forward_kernel, kname what
+// the kernel is called in `name` (96 bytes or NULL), bytes_fn the entry point that tells the workspace's size.
+template <typename Dims, typename Plan>
+static int debug_forward_streamed(const char* who, const char* kname, int n_in, const char* bytes_fn, Plan plan,
+                                  void (*kernel)(Dims, const float*, int64_t, float*, int32_t*, int), const S2DWideNet* shape,
+                                  const void* obs_dev, int64_t n, void* y_dev, void* greedy_dev, char* name, void* stream) {
+  if (!shape) return fail(who, "shape is NULL");
+  ActorPlan<Dims> pl;
+  int rc = plan(who, shape, pl);
+  if (rc == S2D_OK) rc = debug_forward_args(who, shape->params, obs_dev, n, y_dev, greedy_dev);
+  if (rc == S2D_OK) rc = wide_net_workspace(who, shape, wide_pack_args(pl.d, n_in), bytes_fn);
+  if (rc != S2D_OK) return rc;
+  pl.d.wf = static_cast<const float*>(shape->workspace);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = debug_forward_launch(who, reinterpret_cast<const void*>(kernel), pl, n, [&](unsigned blocks, int threads) {
+    s2d_internal_wide_pack(wide_pack_args(pl.d, n_in), shape->params, shape->workspace, s);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), pl.lds, s, pl.d, static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev),
+                       static_cast<int32_t*>(greedy_dev), pl.wave_words);
+  });
+  if (rc == S2D_OK && name)
+    std::snprintf(name, 96, "%s<act=%s,h=%s,a=%d,waves=%d,tiles=%d>", kname, kActName[shape->activation], widths_text(shape).c_str(),
+                  shape->n_out, pl.waves, pl.d.tiles);
+  return rc;
 }

@@ -3,8 +3,9 @@
 // (s2d_gtc_rollout_actor, continuous and turn-mode engines), evaluated inside the rollout kernel on each env's own 4-word
 // observation.  One network back end: the streamed-weight MLP of s2d_wide_net.h with input width 4 (4 -> h_1 -> ... -> h_L -> A,
 // L = 1 .. 5, widths multiples of 4 up to 400, relu / tanh_spec / sigmoid_spec), its fragments written into the caller's workspace
-// by the pack kernel on the same stream ahead of every rollout.  The environment half is s2d_gtc_device.h's, word for word
-// what s2d_gtc_rollout runs.
+// by the pack kernel (s2d_wide_pack.hip) on the same stream ahead of every rollout; the shape's checks, the workspace's, the plan
+// and the diagnostic's host half are shared with the network's other users (s2d_wide_host.h, s2d_wide_net.h,
+// s2d_actor_rollout.h).  The environment half is s2d_gtc_device.h's, word for word what s2d_gtc_rollout runs.
 //
 // lane = env, 64 envs a wave, four 16-env tiles; waves per workgroup and env tiles per pass come from the plan.  LDS: the
 // biases (block-shared, net_pack before the one barrier), then per wave [image A | image B | q 64 x qpitch | obs tile 64 x 4].
@@ -14,7 +15,6 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 
 #include "s2d_actor_rollout.h"
@@ -159,75 +159,16 @@ __global__ __launch_bounds__(kBlock) void s2d_gtc_actor_rollout_kernel(GParams p
   }
 }
 
-// diagnostic (s2d_gtc_debug_forward): the rollout's network on caller observations [n][4]
-__global__ __launch_bounds__(kBlock) void s2d_gtc_debug_forward_kernel(WideDims d, const float* __restrict__ obs, int64_t n,
-                                                                       float* __restrict__ y, int32_t* __restrict__ greedy,
-                                                                       int wave_words) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t wave_first = i - lane;
-  net_pack(d, nullptr, smem);
-  const GtcWaveLds L = gtc_wave_lds(d, smem, wv, wave_words);
-  __syncthreads();
-  if (wave_first >= n) return;
-  const bool active = i < n;
-#pragma unroll
-  for (int k = 0; k < kGtcIn; ++k) L.tile[lane * kGtcIn + k] = active ? obs[i * kGtcIn + k] : 0.0f;
-  wave_lds_fence();
-  const int best = net_forward<true, kGtcIn>(d, smem, L.ha, L.hb, L.qv, L.tile, lane);
-  if (active) {
-    for (int a = 0; a < d.na; ++a) y[i * d.na + a] = L.qv[lane * d.qpitch + a];
-    greedy[i] = best;
-  }
-}
-
 // ------------------------------------------------------------------------------------------ host side
-static const char* const kActName[3] = {"relu", "tanh", "sigmoid"};
-static int gfail(const std::string& m) { s2d_internal_set_error(m.c_str()); return S2D_EINVAL; }
-static size_t workspace_bytes(const WideDims& d) { return ((size_t)d.nfrag * kWave + d.nbias) * sizeof(float); }
-static std::string net_text(const S2DWideNet* net) { return "4-" + widths_text(net) + "-" + std::to_string(net->n_out); }
+static const char kBytesFn[] = "s2d_gtc_actor_workspace_bytes";
 
-// The plan of `net`'s shape: S2D_OK, or S2D_EINVAL with the text set.  S2D_WIDE_PLAN=waves,tiles in the environment, read at
-// every launch, overrides the plan's choice (testing: the results do not depend on it), as for the reach-ball actors.
-static int gtc_plan(const std::string& w, const S2DWideNet* net, ActorPlan<WideDims>& pl) {
-  if (net->n_hidden < 1 || net->n_hidden > kWideMaxHidden) return gfail(w + ": n_hidden must be in [1, 5]");
-  if (!wide_shape_ok(net->n_hidden, net->hidden))
-    return gfail(w + ": hidden widths must be multiples of 4 in [8, 400], and 0 past n_hidden");
-  if (net->activation < 0 || net->activation > 2) return gfail(w + ": activation must be 0 (ReLU), 1 (Tanh) or 2 (Sigmoid)");
-  if (net->n_out < 1 || net->n_out > 64) return gfail(w + ": n_out must be in [1, 64]");
-  int fw = 0, ft = 0;
-  const char* const env = std::getenv("S2D_WIDE_PLAN");
-  if (env && *env && std::sscanf(env, "%d,%d", &fw, &ft) != 2) fw = ft = -1;
-  if (!wide_plan_lds<kGtcIn>(net->n_hidden, net->hidden, net->n_out, net->activation, fw, ft, pl.d, pl.wave_words, pl.waves, pl.lds,
-                             kGtcTail))
-    return gfail(w + ": S2D_WIDE_PLAN=" + (env ? env : "") + " is not waves,tiles of {4, 2, 1} that fit the LDS for " + net_text(net));
-  return S2D_OK;
+// The plan of `net`'s shape: wide_net_plan with the 4-word observation and its tile as the tail.  S2D_WIDE_PLAN overrides the
+// plan's choice, as for the reach-ball actors.
+static int gtc_plan(const char* who, const S2DWideNet* net, ActorPlan<WideDims>& pl) {
+  return wide_net_plan(who, net, kGtcIn, kGtcTail, pl.d, pl.wave_words, pl.waves, pl.lds);
 }
 
-static int gtc_workspace(const std::string& w, const S2DWideNet* net, const WideDims& d) {
-  if (!net->workspace || (reinterpret_cast<uintptr_t>(net->workspace) & 255u))
-    return gfail(w + ": workspace must be a non-NULL, 256-byte aligned device pointer");
-  if (net->workspace_bytes < workspace_bytes(d))
-    return gfail(w + ": workspace_bytes is " + std::to_string(net->workspace_bytes) + ", the network " + net_text(net) + " needs " +
-                 std::to_string(workspace_bytes(d)) + " (s2d_gtc_actor_workspace_bytes)");
-  return S2D_OK;
-}
-
-// params -> workspace in fragment order, on `stream`
-static void launch_pack(const WideDims& d, const S2DWideNet* net, hipStream_t stream) {
-  const int words = d.nfrag * kWave + d.nbias;
-  hipLaunchKernelGGL(s2d_wide_pack_kernel<kGtcIn>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, net->params,
-                     static_cast<float*>(net->workspace));
-}
-
-S2D_API size_t s2d_gtc_actor_workspace_bytes(const S2DWideNet* shape) {
-  if (!shape || !wide_shape_ok(shape->n_hidden, shape->hidden) || shape->n_out < 1 || shape->n_out > 64) return 0;
-  ActorPlan<WideDims> pl;
-  if (!wide_plan_lds<kGtcIn>(shape->n_hidden, shape->hidden, shape->n_out, 0, 0, 0, pl.d, pl.wave_words, pl.waves, pl.lds, kGtcTail))
-    return 0;
-  return workspace_bytes(pl.d);
-}
+S2D_API size_t s2d_gtc_actor_workspace_bytes(const S2DWideNet* shape) { return wide_net_workspace_bytes(shape, kGtcIn); }
 
 // both entry points: every check, then the pack kernel and the rollout
 static int gtc_rollout(const char* who, bool qhead, S2DGtcHandle h, int n_steps, const S2DWideNet* net, const S2DGtcRollout* out,
@@ -236,29 +177,30 @@ static int gtc_rollout(const char* who, bool qhead, S2DGtcHandle h, int n_steps,
   static const Kernel table[3] = {s2d_gtc_actor_rollout_kernel<true, false>, s2d_gtc_actor_rollout_kernel<false, false>,
                                   s2d_gtc_actor_rollout_kernel<false, true>};
   const std::string w(who);
-  if (!h) return gfail(w + ": NULL handle");
-  if (!net) return gfail(w + ": net is NULL");
-  if (n_steps < 0) return gfail(w + ": n_steps must be >= 0");
+  if (!h) return fail(w, "NULL handle");
+  if (!net) return fail(w, "net is NULL");
+  if (n_steps < 0) return fail(w, "n_steps must be >= 0");
   const GParams& gp = h->gp;
-  if (qhead && gp.continuous) return gfail(w + ": the Q head needs a discrete engine (this one is continuous): use s2d_gtc_rollout_actor");
-  if (!qhead && !gp.continuous) return gfail(w + ": the tanh head needs a continuous engine (this one is discrete): use s2d_gtc_rollout_qnet");
+  if (qhead && gp.continuous) return fail(w, "the Q head needs a discrete engine (this one is continuous): use s2d_gtc_rollout_actor");
+  if (!qhead && !gp.continuous) return fail(w, "the tanh head needs a continuous engine (this one is discrete): use s2d_gtc_rollout_qnet");
   ActorPlan<WideDims> pl;
-  if (gtc_plan(w, net, pl) != S2D_OK) return S2D_EINVAL;
+  if (gtc_plan(who, net, pl) != S2D_OK) return S2D_EINVAL;
   const int want = qhead ? 16 : gp.adim;
   if (net->n_out != want)
-    return gfail(w + ": n_out is " + std::to_string(net->n_out) + ", the engine's " + (qhead ? "action count" : "action width") + " is " +
-                 std::to_string(want));
+    return fail(w, "n_out is " + std::to_string(net->n_out) + ", the engine's " + (qhead ? "action count" : "action width") + " is " +
+                       std::to_string(want));
   if (qhead ? net->noise_kind != 0 : (net->noise_kind != 0 && net->noise_kind != 1))
-    return gfail(w + (qhead ? ": noise_kind must be 0 for the Q head" : ": noise_kind must be 0 or 1"));
+    return fail(w, qhead ? "noise_kind must be 0 for the Q head" : "noise_kind must be 0 or 1");
   if (net->noise_kind == 1 && (!net->noise || (reinterpret_cast<uintptr_t>(net->noise) & 3u)))
-    return gfail(w + ": noise_kind = 1 needs noise, a 4-byte aligned device buffer [2][n_out]");
+    return fail(w, "noise_kind = 1 needs noise, a 4-byte aligned device buffer [2][n_out]");
   if (!net->params || (reinterpret_cast<uintptr_t>(net->params) & 15u))
-    return gfail(w + ": params must be a non-NULL, 16-byte aligned device pointer");
+    return fail(w, "params must be a non-NULL, 16-byte aligned device pointer");
   if (!net->epsilon || (reinterpret_cast<uintptr_t>(net->epsilon) & 3u))
-    return gfail(w + ": epsilon must be a non-NULL, 4-byte aligned device pointer");
-  if (gtc_workspace(w, net, pl.d) != S2D_OK) return S2D_EINVAL;
+    return fail(w, "epsilon must be a non-NULL, 4-byte aligned device pointer");
+  const WidePackArgs pack = wide_pack_args(pl.d, kGtcIn);
+  if (wide_net_workspace(w, net, pack, kBytesFn) != S2D_OK) return S2D_EINVAL;
   if ((reinterpret_cast<uintptr_t>(terminal_obs) & 15u) || (out && (reinterpret_cast<uintptr_t>(out->obs) & 15u)))
-    return gfail(w + ": the obs and terminal_obs records must be 16-byte aligned");
+    return fail(w, "the obs and terminal_obs records must be 16-byte aligned");
   if (n_steps == 0) return S2D_OK;
   if (hipSetDevice(h->device) != hipSuccess) { s2d_internal_set_error((w + ": hipSetDevice failed").c_str()); return S2D_EHIP; }
   const int slot = qhead ? 0 : 1 + (net->noise_kind ? 1 : 0);
@@ -272,11 +214,10 @@ static int gtc_rollout(const char* who, bool qhead, S2DGtcHandle h, int n_steps,
   if (out) ro = GRoll{out->obs, out->action, out->reward, out->done, out->result};
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const int threads = pl.waves * kWave;
-  launch_pack(pl.d, net, s);
+  s2d_internal_wide_pack(pack, net->params, net->workspace, s);
   hipLaunchKernelGGL(k, dim3((unsigned)((h->n + threads - 1) / threads)), dim3(threads), pl.lds, s, gp, h->q, h->n, n_steps, pl.d,
                      net->epsilon, net->noise_kind ? net->noise : nullptr, ro, terminal_obs, pl.wave_words);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { s2d_internal_set_error((w + ": launch: " + hipGetErrorString(e)).c_str()); return S2D_EHIP; }
+  if (launched(w) != S2D_OK) return S2D_EHIP;
   const char* const mode = !gp.continuous ? "discrete" : !gp.turn ? "continuous" : gp.use_turn ? "useturn" : "turn";
   std::snprintf(h->name, sizeof h->name, "s2d_gtc_actor_rollout_kernel<head=%s,mode=%s,gauss=%d,act=%s,h=%s,a=%d,waves=%d,tiles=%d>",
                 qhead ? "q" : "tanh", mode, net->noise_kind ? 1 : 0, kActName[net->activation], widths_text(net).c_str(), net->n_out,
@@ -296,21 +237,6 @@ S2D_API const char* s2d_gtc_kernel_name(S2DGtcHandle h) { return h ? h->name : "
 
 S2D_API int s2d_gtc_debug_forward(const S2DWideNet* shape, const void* obs_dev, int64_t n, void* y_dev, void* greedy_dev, char* name,
                                   void* stream) {
-  static const char who[] = "s2d_gtc_debug_forward";
-  if (!shape) return gfail(std::string(who) + ": shape is NULL");
-  ActorPlan<WideDims> pl;
-  int rc = gtc_plan(who, shape, pl);
-  if (rc == S2D_OK) rc = debug_forward_args(who, shape->params, obs_dev, n, y_dev, greedy_dev);
-  if (rc == S2D_OK) rc = gtc_workspace(who, shape, pl.d);
-  if (rc != S2D_OK) return rc;
-  pl.d.wf = static_cast<const float*>(shape->workspace);
-  rc = debug_forward_launch(who, reinterpret_cast<const void*>(s2d_gtc_debug_forward_kernel), pl, n, [&](unsigned blocks, int threads) {
-    launch_pack(pl.d, shape, static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(s2d_gtc_debug_forward_kernel, dim3(blocks), dim3(threads), pl.lds, static_cast<hipStream_t>(stream), pl.d,
-                       static_cast<const float*>(obs_dev), n, static_cast<float*>(y_dev), static_cast<int32_t*>(greedy_dev), pl.wave_words);
-  });
-  if (rc == S2D_OK && name)
-    std::snprintf(name, 96, "s2d_gtc_debug_forward_kernel<act=%s,h=%s,a=%d,waves=%d,tiles=%d>", kActName[shape->activation],
-                  widths_text(shape).c_str(), shape->n_out, pl.waves, pl.d.tiles);
-  return rc;
+  return debug_forward_streamed("s2d_gtc_debug_forward", "s2d_gtc_debug_forward_kernel", kGtcIn, kBytesFn, gtc_plan,
+                                s2d_wide_debug_forward_kernel<kGtcIn>, shape, obs_dev, n, y_dev, greedy_dev, name, stream);
 }

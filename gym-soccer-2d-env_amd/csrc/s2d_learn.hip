@@ -23,12 +23,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 #include <string>
 
 #include "s2d_wide_net.h"
-
-extern "C" void s2d_internal_set_error(const char* msg);
 
 static constexpr int kLearnRows = S2D_LEARN_BLOCK_ROWS;
 static constexpr int kLearnChunk = S2D_LEARN_NORM_CHUNK;
@@ -287,11 +284,7 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
-int fail(const std::string& who, const std::string& msg) {
-  s2d_internal_set_error((who + ": " + msg).c_str());
-  return S2D_EINVAL;
-}
-bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
+struct LearnLds {};   // the owner of the block kernel's dynamic-LDS slot (allow_lds_slot); fail, misaligned and launched are s2d_wide_host.h's
 
 // "" if the shape is on the learner's grid, else the text naming the field
 std::string shape_error(const S2DLearnNet* n) {
@@ -340,19 +333,6 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
   return p < q + nb && q < p + na;
 }
-bool allow_lds(const void* fn) {
-  static std::mutex mu;
-  static bool set[kMaxDevices] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!set[dev]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
-    set[dev] = true;
-  }
-  return true;
-}
-
 template <bool UPDATE>
 int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S2DLearnState* st, const float* obs, const int32_t* action,
           const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
@@ -388,7 +368,7 @@ int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S
                          float*, float*, int32_t*);
   const Block kb = y.lds ? s2d_learn_block_kernel<true> : s2d_learn_block_kernel<false>;
   const size_t lds = (size_t)kLearnRows * ((y.lds ? d.pitch : 0) + 1) * sizeof(float);
-  if (lds > 48 * 1024 && !allow_lds(reinterpret_cast<const void*>(kb))) {
+  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 0)) {
     s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
     return S2D_EHIP;
   }
@@ -402,10 +382,7 @@ int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S
                      ws + y.chunk, st->hyper);
   hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, d.P, batch, blocks,
                      chunks, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return S2D_OK;
-  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
-  return S2D_EHIP;
+  return launched(who);
 }
 }  // namespace
 

@@ -6,8 +6,10 @@
 //
 // The network is the streamed-weight MLP of s2d_wide_net.h (wide_group / wide_layer and the fragment order are its) with a RUN-TIME
 // input width n_in in [1, 256]: layer 1 takes ceil(n_in / 4) k-steps over x_k = 0 against zero weights past n_in, so at n_in = 10 it
-// is the reach-ball actors' 12-term layer and at n_in = 4 the GoToCenter actors' single k-step.  A pack kernel per network writes
-// its parameters in fragment order into the caller's workspace on the same stream ahead of the target kernel; the biases are read
+// is the reach-ball actors' 12-term layer and at n_in = 4 the GoToCenter actors' single k-step.  The pack kernel (s2d_wide_pack.hip,
+// one launch per network) writes the parameters in fragment order into the caller's workspace on the same stream ahead of the
+// target kernel; the shape's checks, the fragment count, the workspace's check, the S2D_TD_PLAN override and the (waves, tiles)
+// search are s2d_wide_host.h's, shared with the actors.  The biases are read
 // from there too (one float4 per output tile), so the kernel has no block-shared LDS and no barrier: a wave is on its own.
 //
 // lane = batch row, 64 rows a wave, four 16-row tiles, T = 4, 2 or 1 of them per pass.  LDS of a wave:
@@ -20,14 +22,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <mutex>
 #include <string>
 
 #include "s2d_wide_net.h"
-
-extern "C" void s2d_internal_set_error(const char* msg);
 
 static constexpr int kTdMaxIn = 256;
 static constexpr int kTdMaxAction = 8;
@@ -223,100 +221,30 @@ __global__ __launch_bounds__(kBlock) void s2d_td_target_ac_kernel(TdNetDev actor
   }
 }
 
-// The caller's parameters (nn.Sequential order: W_1 [h_1][n_in], b_1, ..., W_out [A][h_L], b_out) into the workspace in fragment
-// order, then the biases, every layer's padded with zeros to its tiles' 16 rows: one word per thread.  s2d_wide_pack_kernel with
-// a run-time input width: rows past a layer's width and layer 1's k >= n_in are zero.
-__global__ __launch_bounds__(256) void s2d_td_pack_kernel(TdNetDev d, const float* __restrict__ params, float* __restrict__ ws) {
-  const int L = d.n_hidden;
-  const int nw = d.nfrag * kWave;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= nw + d.nbias) return;
-  if (idx < nw) {
-    const int f = idx / kWave, lw = idx & (kWave - 1);
-    const int row = lw & 15, kk = lw >> 4;
-    // the layer of fragment f: its first fragment, widths in and out, k-steps and the offset of its W in params
-    int f0 = 0, win = d.n_in, wout = td_width(d, 0), ks = d.ks1, ow = 0;
-#pragma unroll
-    for (int l = 1; l <= kWideMaxHidden; ++l) {
-      const int next = f0 + ((wout + 15) >> 4) * ks;         // the first fragment of the layer after this one
-      if (l <= L && f >= next) {
-        ow += wout * win + wout;
-        f0 = next;
-        win = wout;
-        wout = l < L ? td_width(d, l) : d.na;
-        ks = win >> 2;
-      }
-    }
-    const int r = f - f0, jt = r / ks, s = r - jt * ks, j = 16 * jt + row, k = 4 * s + kk;
-    ws[idx] = (j < wout && k < win) ? params[ow + j * win + k] : 0.0f;
-  } else {
-    const int bi = idx - nw;
-    int b0 = 0, win = d.n_in, wout = td_width(d, 0), ob = wout * win;   // ob: the offset of the layer's bias in params
-#pragma unroll
-    for (int l = 1; l <= kWideMaxHidden; ++l) {
-      const int pad = (wout + 15) & ~15;
-      if (l <= L && bi >= b0 + pad) {
-        b0 += pad;
-        win = wout;
-        wout = l < L ? td_width(d, l) : d.na;
-        ob += win + wout * win;
-      }
-    }
-    const int j = bi - b0;
-    ws[idx] = j < wout ? params[ob + j] : 0.0f;
-  }
-}
-
 // ------------------------------------------------------------------------------------------ host
 namespace {
-int fail(const std::string& who, const std::string& msg) {
-  s2d_internal_set_error((who + ": " + msg).c_str());
-  return S2D_EINVAL;
-}
-bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
+struct TdLds {};   // the owner of the target kernels' dynamic-LDS slots (allow_lds_slot)
 
-bool shape_ok(const S2DTdNet* n) {
-  return n->n_in >= 1 && n->n_in <= kTdMaxIn && wide_shape_ok(n->n_hidden, n->hidden) && n->n_out >= 1 && n->n_out <= 64;
-}
-// the kernels' view of a shape on the grid (wf left NULL) and its widest padded hidden layer
+// the kernels' view of a shape on the grid (wf left NULL); wmax: raised to its widest padded hidden layer
 TdNetDev net_dev(const S2DTdNet* n, int* wmax) {
+  const WideCounts c = s2d_internal_wide_counts(n->n_in, n->n_hidden, n->hidden, n->n_out);
   TdNetDev d{};
   d.n_in = n->n_in; d.ks1 = (n->n_in + 3) / 4; d.n_hidden = n->n_hidden; d.act = n->activation; d.na = n->n_out;
-  int ks = d.ks1;
-  for (int l = 0; l < n->n_hidden; ++l) {
-    const int w = n->hidden[l], m16 = (w + 15) / 16;
-    d.widths |= (uint64_t)(w / 4) << (7 * l);
-    d.nfrag += m16 * ks;
-    d.nbias += 16 * m16;
-    if (wmax && 16 * m16 > *wmax) *wmax = 16 * m16;
-    ks = w / 4;
-  }
-  const int na16 = (n->n_out + 15) / 16 * 16;
-  d.nfrag += (na16 / 16) * ks;
-  d.nbias += na16;
+  d.widths = c.widths; d.nfrag = c.nfrag; d.nbias = c.nbias;
+  if (wmax && c.wmax > *wmax) *wmax = c.wmax;
   return d;
 }
-size_t workspace_bytes(const TdNetDev& d) { return ((size_t)d.nfrag * kWave + d.nbias) * sizeof(float); }
-std::string net_text(const S2DTdNet* n) {
-  std::string s = std::to_string(n->n_in);
-  for (int l = 0; l < n->n_hidden; ++l) s += "-" + std::to_string(n->hidden[l]);
-  return s + "-" + std::to_string(n->n_out);
-}
+size_t workspace_bytes(const TdNetDev& d) { return wide_workspace_bytes(d.nfrag, d.nbias); }
+std::string net_text(const S2DTdNet* n) { return s2d_internal_wide_text(n->n_in, n->n_hidden, n->hidden, n->n_out); }
 
 // one network of a call (`name`: what the header calls it): the shape, the parameters and the workspace
 int check_net(const std::string& who, const char* name, const S2DTdNet* n, TdNetDev& d, int& wmax) {
-  const std::string nm(name);
-  if (n->n_in < 1 || n->n_in > kTdMaxIn) return fail(who, nm + ": n_in must be in [1, 256]");
-  if (n->n_hidden < 1 || n->n_hidden > kWideMaxHidden) return fail(who, nm + ": n_hidden must be in [1, 5]");
-  if (!wide_shape_ok(n->n_hidden, n->hidden)) return fail(who, nm + ": hidden widths must be multiples of 4 in [8, 400], and 0 past n_hidden");
-  if (n->n_out < 1 || n->n_out > 64) return fail(who, nm + ": n_out must be in [1, 64]");
-  if (n->activation < 0 || n->activation > 2) return fail(who, nm + ": activation must be 0 (ReLU), 1 (Tanh) or 2 (Sigmoid)");
-  if (!n->params || misaligned(n->params, 16)) return fail(who, nm + ": params must be a non-NULL, 16-byte aligned device pointer");
-  if (!n->workspace || misaligned(n->workspace, 256)) return fail(who, nm + ": workspace must be a non-NULL, 256-byte aligned device pointer");
+  const std::string nm = who + ": " + name;
+  if (s2d_internal_wide_shape(nm, &n->n_in, n->n_hidden, n->hidden, n->activation, n->n_out) != S2D_OK) return S2D_EINVAL;
+  if (!n->params || misaligned(n->params, 16)) return fail(nm, "params must be a non-NULL, 16-byte aligned device pointer");
   d = net_dev(n, &wmax);
-  if (n->workspace_bytes < workspace_bytes(d))
-    return fail(who, nm + ": workspace_bytes is " + std::to_string(n->workspace_bytes) + ", the network " + net_text(n) + " needs " +
-                         std::to_string(workspace_bytes(d)) + " (s2d_td_workspace_bytes)");
+  if (s2d_internal_wide_workspace(nm, n->workspace, n->workspace_bytes, workspace_bytes(d), net_text(n), "s2d_td_workspace_bytes") != S2D_OK)
+    return S2D_EINVAL;
   d.wf = static_cast<const float*>(n->workspace);
   return S2D_OK;
 }
@@ -347,46 +275,12 @@ int make_plan(const std::string& who, int64_t batch, int wmax, int n_in, int na,
   pl.rpitch = (wmax + 63) / 64 * 64 + 4;
   pl.xpitch = ((n_in + 3) / 4 * 4 + 63) / 64 * 64 + 4;
   pl.qpitch = (na + 15) / 16 * 16 + 4;
-  int fw = 0, ft = 0;
-  const char* const env = std::getenv("S2D_TD_PLAN");
-  if (env && *env && std::sscanf(env, "%d,%d", &fw, &ft) != 2) fw = ft = -1;
-  const auto one_of = [](int v) { return v == 4 || v == 2 || v == 1; };
+  const WidePlanOverride force = s2d_internal_plan_override("S2D_TD_PLAN");
   const int64_t batch_waves = (batch + kWave - 1) / kWave, cus = compute_units();
-  const int most = fw ? kWavesPerBlock : batch_waves >= 4 * cus ? kWavesPerBlock : batch_waves >= 2 * cus ? 2 : 1;
-  if ((!fw || one_of(fw)) && (!ft || one_of(ft))) {
-    for (int wv = most; wv >= 1; wv /= 2) {
-      if (fw && wv != fw) continue;
-      for (int t = 4; t >= 1; t /= 2) {
-        if (ft && t != ft) continue;
-        const int ww = t * 16 * (pl.xpitch + 2 * pl.rpitch) + kWave * pl.qpitch;
-        if ((size_t)wv * ww * sizeof(float) <= kLdsMax) {
-          pl.tiles = t; pl.wave_words = ww; waves = wv; lds = (size_t)wv * ww * sizeof(float);
-          return S2D_OK;
-        }
-      }
-    }
-  }
-  return fail(who, std::string("S2D_TD_PLAN=") + (env ? env : "") + " is not waves,tiles of {4, 2, 1} that fit the LDS of this call");
-}
-
-// the dynamic-LDS limit of a kernel, once per device and kernel
-bool allow_lds(const void* fn, int slot) {
-  static std::mutex mu;
-  static bool set[kMaxDevices][4] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!set[dev][slot]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
-    set[dev][slot] = true;
-  }
-  return true;
-}
-
-void launch_pack(const TdNetDev& d, const S2DTdNet* n, hipStream_t stream) {
-  const int words = d.nfrag * kWave + d.nbias;
-  hipLaunchKernelGGL(s2d_td_pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, d, n->params,
-                     static_cast<float*>(n->workspace));
+  const int most = force.waves ? kWavesPerBlock : batch_waves >= 4 * cus ? kWavesPerBlock : batch_waves >= 2 * cus ? 2 : 1;
+  const auto words = [&](int t) { return t * 16 * (pl.xpitch + 2 * pl.rpitch) + kWave * pl.qpitch; };
+  if (wide_plan_search(force, most, 0, words, waves, pl.tiles, pl.wave_words, lds)) return S2D_OK;
+  return fail(who, wide_plan_refusal(force) + " of this call");
 }
 
 // what both entry points ask of the batch arrays
@@ -399,16 +293,12 @@ int check_batch(const std::string& who, int64_t batch, const void* next_obs, con
   if (misaligned(opt1, 4) || misaligned(opt2, 4)) return fail(who, "the optional outputs must be 4-byte aligned device pointers (or NULL)");
   return S2D_OK;
 }
-int launched(const std::string& who) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return S2D_OK;
-  s2d_internal_set_error((who + ": launch: " + hipGetErrorString(e)).c_str());
-  return S2D_EHIP;
-}
 }  // namespace
 
 S2D_API size_t s2d_td_workspace_bytes(const S2DTdNet* shape) {
-  if (!shape || !shape_ok(shape)) return 0;
+  if (!shape || shape->n_in < 1 || shape->n_in > kTdMaxIn || !wide_shape_ok(shape->n_hidden, shape->hidden) || shape->n_out < 1 ||
+      shape->n_out > 64)
+    return 0;
   return workspace_bytes(net_dev(shape, nullptr));
 }
 
@@ -432,14 +322,14 @@ S2D_API int s2d_td_target_q(int64_t batch, const S2DTdNet* target, const S2DTdNe
   if (make_plan(who, batch, wmax, target->n_in, target->n_out, pl, waves, lds) != S2D_OK) return S2D_EINVAL;
   using Kernel = void (*)(TdNetDev, TdNetDev, TdPlanDev, int64_t, const float*, const float*, const float*, float*, float*, int32_t*);
   const Kernel k = online ? s2d_td_target_q_kernel<true> : s2d_td_target_q_kernel<false>;
-  if (!allow_lds(reinterpret_cast<const void*>(k), online ? 1 : 0)) {
+  if (!allow_lds_slot<TdLds>(reinterpret_cast<const void*>(k), online ? 1 : 0)) {
     s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
     return S2D_EHIP;
   }
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const int threads = waves * kWave;
-  launch_pack(dt, target, s);
-  if (online) launch_pack(dn, online, s);
+  s2d_internal_wide_pack(wide_pack_args(dt, dt.n_in), target->params, target->workspace, s);
+  if (online) s2d_internal_wide_pack(wide_pack_args(dn, dn.n_in), online->params, online->workspace, s);
   hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, dt, dn, pl, batch, next_obs, reward,
                      discount, out_target, out_q, out_index);
   return launched(who);
@@ -469,15 +359,15 @@ S2D_API int s2d_td_target_ac(int64_t batch, const S2DTdNet* actor, const S2DTdNe
   if (make_plan(who, batch, wmax, critic1->n_in, actor->n_out, pl, waves, lds) != S2D_OK) return S2D_EINVAL;
   using Kernel = void (*)(TdNetDev, TdNetDev, TdNetDev, TdPlanDev, int64_t, const float*, const float*, const float*, float*, float*, float*);
   const Kernel k = critic2 ? s2d_td_target_ac_kernel<true> : s2d_td_target_ac_kernel<false>;
-  if (!allow_lds(reinterpret_cast<const void*>(k), critic2 ? 3 : 2)) {
+  if (!allow_lds_slot<TdLds>(reinterpret_cast<const void*>(k), critic2 ? 3 : 2)) {
     s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
     return S2D_EHIP;
   }
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const int threads = waves * kWave;
-  launch_pack(da, actor, s);
-  launch_pack(d1, critic1, s);
-  if (critic2) launch_pack(d2, critic2, s);
+  s2d_internal_wide_pack(wide_pack_args(da, da.n_in), actor->params, actor->workspace, s);
+  s2d_internal_wide_pack(wide_pack_args(d1, d1.n_in), critic1->params, critic1->workspace, s);
+  if (critic2) s2d_internal_wide_pack(wide_pack_args(d2, d2.n_in), critic2->params, critic2->workspace, s);
   hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, da, d1, d2, pl, batch, next_obs, reward,
                      discount, out_target, out_q, out_action);
   return launched(who);

@@ -3,11 +3,13 @@
 // [8, 400], one hidden activation for the whole network (relu, tanh_spec or sigmoid_spec) and a linear output layer.  The second
 // network back end of the rollout template (s2d_actor_rollout.h): the spec is s2d_mlp_net.h's, the place of the weights is not.
 //
-// The weight fragments stay in GLOBAL memory (the caller's workspace, written by s2d_wide_pack_kernel ahead of every rollout),
-// in the resident path's MFMA fragment order: fragment (jt, s) = 64 words, lane l holds W[16 jt + (l & 15)][4 s + (l >> 4)], so a
-// fragment load is one coalesced 256-byte wave access that the L2 serves ([400] * 5 is 2.6 MB).  A wave loads a fragment once per
-// pass and feeds it to the MFMAs of T = 4, 2 or 1 of its four 16-env tiles (one accumulator per (output tile, env tile)), with the
-// next k-group's fragments requested ahead of the current group's MFMAs.  LDS holds only the biases (block-shared) and per wave
+// The weight fragments stay in GLOBAL memory (the caller's workspace, written by s2d_wide_pack.hip's pack kernel ahead of every
+// launch that reads it; the shape's checks, the fragment count, the workspace and the (waves, tiles) search are s2d_wide_host.h's,
+// shared with the TD targets of s2d_td.hip), in the resident path's MFMA fragment order: fragment (jt, s) = 64 words, lane l
+// holds W[16 jt + (l & 15)][4 s + (l >> 4)], so a fragment load is one coalesced 256-byte wave access that the L2 serves ([400] * 5
+// is 2.6 MB).  A wave loads a fragment once per pass and feeds it to the MFMAs of T = 4, 2 or 1 of its four 16-env tiles (one
+// accumulator per (output tile, env tile)), with the next k-group's fragments requested ahead of the current group's MFMAs.  LDS
+// holds only the biases (block-shared) and per wave
 // [image A: T x 16 x rpitch | image B: T x 16 x rpitch | q 64 x qpitch | obs tile 640 | PrepTile].
 //
 // Every unit is acc = b[j]; for k ascending: acc = fmaf(W[j][k], in[k], acc): layer 1 over k = 0 .. 11 (x_10 = x_11 = 0 against zero
@@ -15,21 +17,21 @@
 // the next layer's k-steps stop at h / 4.  h / 4 may be odd: the k-steps go in groups of four, then one group of two, then one
 // single step, in ascending order.  Neither T nor the waves per workgroup enters a chain: the bits do not depend on the plan.
 //
-// The input width is a compile-time parameter IN (S2D_OBS_DIM unless said): it is the observation tile's row stride, gives
-// layer 1 its ceil(IN / 4) k-steps and the pack kernel its first `win`.  The GoToCenter actors (s2d_gtc_actor.hip) use IN = 4:
-// layer 1 is then ONE k-step over exactly k = 0 .. 3 with no zero pad, so an accumulator of -0 stays -0 there (the padded
-// layer 1 of IN = 10 turns it into +0); a wave's LDS part ends with the observation tile of 64 x IN words and no PrepTile.
+// The input width is a compile-time parameter IN of the layers (S2D_OBS_DIM unless said): it is the observation tile's row
+// stride and gives layer 1 its ceil(IN / 4) k-steps; the host side and the pack kernel take it as a run-time n_in, the pack
+// kernel's first `win`.  The GoToCenter actors (s2d_gtc_actor.hip) use IN = 4: layer 1 is then ONE k-step over exactly
+// k = 0 .. 3 with no zero pad, so an accumulator of -0 stays -0 there (the padded layer 1 of IN = 10 turns it into +0); a wave's
+// LDS part ends with the observation tile of 64 x IN words and no PrepTile.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
-#include <cstdlib>
+#include <string>
 
 #include "s2d_actor_net.h"
+#include "s2d_wide_host.h"
 
-static constexpr int kWideMaxHidden = 5;
-static constexpr int kWideMaxWidth = 400;
 enum { S2D_WIDE_RELU = 0, S2D_WIDE_TANH = 1, S2D_WIDE_SIGMOID = 2, S2D_WIDE_LINEAR = 3 };
 
 struct WideDims {
@@ -253,109 +255,66 @@ S2D_DEV void net_pack(const WideDims& d, const float* __restrict__, float* __res
   for (int idx = threadIdx.x; idx < d.nbias; idx += blockDim.x) smem[idx] = bias[idx];
 }
 
-// The caller's parameters (nn.Sequential order: W_1 [h_1][IN], b_1, ..., W_L [h_L][h_(L-1)], b_L, W_out [A][h_L], b_out) into the
-// workspace in fragment order, then the biases, every layer's padded with zeros to its tiles' 16 rows: one word per thread.  Rows
-// past a layer's width and layer 1's k >= IN (10, 11) are zero.  Enqueued ahead of every launch that reads the workspace.  A
-// template, so that every unit that includes this header has its own.
-template <int IN = S2D_OBS_DIM>
-__global__ __launch_bounds__(256) void s2d_wide_pack_kernel(WideDims d, const float* __restrict__ params, float* __restrict__ ws) {
-  const int L = d.n_hidden;
-  const int nw = d.nfrag * kWave;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= nw + d.nbias) return;
-  if (idx < nw) {
-    const int f = idx / kWave, lw = idx & (kWave - 1);
-    const int row = lw & 15, kk = lw >> 4;
-    // the layer of fragment f: its first fragment, widths in and out, k-steps and the offset of its W in params
-    int f0 = 0, win = IN, wout = wide_width(d, 0), ks = (IN + 3) / 4, ow = 0;
+// diagnostic (s2d_debug_wide_forward: IN = 10; s2d_gtc_debug_forward: IN = 4; every unit instantiates its own): the rollouts'
+// network on caller observations obs [n][IN] -> y [n][na] and the first maximum, with the rollouts' LDS layout: the wave's
+// observation tile sits behind its output image
+template <int IN>
+__global__ __launch_bounds__(kBlock) void s2d_wide_debug_forward_kernel(WideDims d, const float* __restrict__ obs, int64_t n,
+                                                                        float* __restrict__ y, int32_t* __restrict__ greedy,
+                                                                        int wave_words) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+  net_pack(d, nullptr, smem);
+  float* const ha = smem + net_shared_words(d) + wv * wave_words;
+  float* const hb = ha + 16 * d.pitch;
+  float* const qv = hb + 16 * d.pitch;
+  float* const tile = qv + kWave * d.qpitch;
+  __syncthreads();
+  if (wave_first >= n) return;
+  const bool active = i < n;
 #pragma unroll
-    for (int l = 1; l <= kWideMaxHidden; ++l) {
-      const int next = f0 + ((wout + 15) >> 4) * ks;       // the first fragment of the layer after this one
-      if (l <= L && f >= next) {
-        ow += wout * win + wout;
-        f0 = next;
-        win = wout;
-        wout = l < L ? wide_width(d, l) : d.na;
-        ks = win >> 2;
-      }
-    }
-    const int r = f - f0, jt = r / ks, s = r - jt * ks, j = 16 * jt + row, k = 4 * s + kk;
-    ws[idx] = (j < wout && k < win) ? params[ow + j * win + k] : 0.0f;
-  } else {
-    const int bi = idx - nw;
-    int b0 = 0, win = IN, wout = wide_width(d, 0), ob = wout * win;     // ob: the offset of the layer's bias in params
-#pragma unroll
-    for (int l = 1; l <= kWideMaxHidden; ++l) {
-      const int pad = (wout + 15) & ~15;
-      if (l <= L && bi >= b0 + pad) {
-        b0 += pad;
-        win = wout;
-        wout = l < L ? wide_width(d, l) : d.na;
-        ob += win + wout * win;
-      }
-    }
-    const int j = bi - b0;
-    ws[idx] = j < wout ? params[ob + j] : 0.0f;
+  for (int k = 0; k < IN; ++k) tile[lane * IN + k] = active ? obs[i * IN + k] : 0.0f;
+  wave_lds_fence();
+  const int best = net_forward<true, IN>(d, smem, ha, hb, qv, tile, lane);
+  if (active) {
+    for (int a = 0; a < d.na; ++a) y[i * d.na + a] = qv[lane * d.qpitch + a];
+    greedy[i] = best;
   }
 }
 
-// host side
-// is (n_hidden, hidden[]) on the grid: 1 .. 5 layers, every width a multiple of 4 in [8, 400], zeros past n_hidden
-static inline bool wide_shape_ok(int n_hidden, const int32_t* hidden) {
-  if (n_hidden < 1 || n_hidden > kWideMaxHidden) return false;
-  for (int l = 0; l < kWideMaxHidden; ++l) {
-    const int w = hidden[l];
-    if (l < n_hidden ? (w < 8 || w > kWideMaxWidth || w % 4 != 0) : w != 0) return false;
-  }
-  return true;
-}
-
+// host side (the shape's grid, the fragment count, the workspace and the plan search are s2d_wide_host.h's)
 // words of a wave's LDS part behind its output image, in the rollout template: the observation tile and the PrepTile
 static constexpr int kWideTail = kObsTile + (int)(sizeof(PrepTile) / sizeof(float));
 
-// bytes of LDS of a shape's dims with `waves` waves per workgroup and `tiles` env tiles per pass; `tail`: see kWideTail
-static inline size_t wide_lds_bytes(const WideDims& d, int waves, int tiles, int* wave_words, int tail = kWideTail) {
-  const int ww = 2 * tiles * 16 * d.rpitch + kWave * d.qpitch + tail;
-  if (wave_words) *wave_words = ww;
-  return ((size_t)((d.nbias + 3) & ~3) + (size_t)waves * ww) * sizeof(float);
+// The plan of a valid shape with input width n_in (layer 1 has ceil(n_in / 4) k-steps): the dims (wf left NULL), per-wave words,
+// waves per workgroup, env tiles per pass and the LDS bytes: the first of (4, 4) (4, 2) (4, 1) (2, 4) ... (1, 1) that 160 KiB hold
+// (wide_plan_search); (1, 1) always fits (width 400: 2 x 16 x 452 words of images).  `force`: the testing override; false if the
+// forced pair does not fit or is not in {4, 2, 1}.  tail: the words of a wave behind its output image.
+static inline bool wide_plan_lds(int n_in, int n_hidden, const int32_t* hidden, int na, int act, const WidePlanOverride& force, WideDims& d,
+                                 int& wave_words, int& waves, size_t& lds, int tail = kWideTail) {
+  const WideCounts c = s2d_internal_wide_counts(n_in, n_hidden, hidden, na);
+  d = WideDims{};
+  d.n_hidden = n_hidden; d.act = act; d.na = na; d.na16 = c.na16;
+  d.widths = c.widths; d.nfrag = c.nfrag; d.nbias = c.nbias;
+  d.rpitch = (c.wmax + 63) / 64 * 64 + 4;
+  d.qpitch = d.na16 + 4;
+  const auto words = [&](int t) { return 2 * t * 16 * d.rpitch + kWave * d.qpitch + tail; };
+  if (!wide_plan_search(force, kWavesPerBlock, (size_t)((d.nbias + 3) & ~3), words, waves, d.tiles, wave_words, lds)) return false;
+  d.pitch = d.tiles * d.rpitch;
+  return true;
 }
 
-// The plan of a valid shape: the dims (wf left NULL), per-wave words, waves per workgroup, env tiles per pass and the LDS bytes.
-// More waves go before more tiles (one wave per workgroup leaves three SIMDs of the CU idle): the first of (4, 4) (4, 2) (4, 1)
-// (2, 4) ... (1, 1) that 160 KiB hold; (1, 1) always fits (width 400: 2 x 16 x 452 words of images).  force_waves / force_tiles
-// (0 = the plan's choice) are the testing override; false if the forced pair does not fit or is not in {4, 2, 1}.  IN: the
-// input width (layer 1 has ceil(IN / 4) k-steps); tail: the words of a wave behind its output image.
-template <int IN = S2D_OBS_DIM>
-static inline bool wide_plan_lds(int n_hidden, const int32_t* hidden, int na, int act, int force_waves, int force_tiles, WideDims& d,
-                                 int& wave_words, int& waves, size_t& lds, int tail = kWideTail) {
-  d = WideDims{};
-  d.n_hidden = n_hidden; d.act = act; d.na = na; d.na16 = (na + 15) / 16 * 16;
-  int nfrag = 0, nbias = 0, wmax = 0, ksteps = (IN + 3) / 4;
-  for (int l = 0; l < n_hidden; ++l) {
-    const int w = hidden[l], m16 = (w + 15) / 16;
-    d.widths |= (uint64_t)(w / 4) << (7 * l);
-    nfrag += m16 * ksteps;
-    nbias += 16 * m16;
-    if (16 * m16 > wmax) wmax = 16 * m16;
-    ksteps = w / 4;
-  }
-  nfrag += (d.na16 / 16) * ksteps;
-  nbias += d.na16;
-  d.nfrag = nfrag; d.nbias = nbias;
-  d.rpitch = (wmax + 63) / 64 * 64 + 4;
-  d.qpitch = d.na16 + 4;
-  const auto one_of = [](int v) { return v == 4 || v == 2 || v == 1; };
-  if ((force_waves && !one_of(force_waves)) || (force_tiles && !one_of(force_tiles))) return false;
-  for (int wv = kWavesPerBlock; wv >= 1; wv /= 2) {
-    if (force_waves && wv != force_waves) continue;
-    for (int t = 4; t >= 1; t /= 2) {
-      if (force_tiles && t != force_tiles) continue;
-      lds = wide_lds_bytes(d, wv, t, &wave_words, tail);
-      if (lds <= kLdsMax) {
-        waves = wv; d.tiles = t; d.pitch = t * d.rpitch;
-        return true;
-      }
-    }
-  }
-  return false;
+// The plan of `net`'s shape (everything but the engine's side of n_out and the pointers) for an actor with input width n_in: S2D_OK,
+// or S2D_EINVAL with the error text set (`who` = the entry point's name).  S2D_WIDE_PLAN=waves,tiles in the environment, read at
+// every launch, overrides the plan's choice (testing: the results do not depend on it); a pair that is not of {4, 2, 1} or does
+// not fit the LDS is refused.
+static inline int wide_net_plan(const std::string& who, const S2DWideNet* net, int n_in, int tail, WideDims& d, int& wave_words, int& waves,
+                                size_t& lds) {
+  if (s2d_internal_wide_shape(who, nullptr, net->n_hidden, net->hidden, net->activation, net->n_out) != S2D_OK) return S2D_EINVAL;
+  const WidePlanOverride force = s2d_internal_plan_override("S2D_WIDE_PLAN");
+  if (!wide_plan_lds(n_in, net->n_hidden, net->hidden, net->n_out, net->activation, force, d, wave_words, waves, lds, tail))
+    return fail(who, wide_plan_refusal(force) + " for " + s2d_internal_wide_text(n_in, net->n_hidden, net->hidden, net->n_out));
+  return S2D_OK;
 }

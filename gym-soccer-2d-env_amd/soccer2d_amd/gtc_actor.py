@@ -10,7 +10,8 @@ the pack kernel writes, all read when the kernels run.  Layer 1 runs over exactl
 """
 from .actor import DeterministicActor, QNetActor
 from .gtc import GTC_OBS_DIM
-from .wide_actor import ACTIVATIONS, LDS_BYTES, MAX_HIDDEN, WIDE_WIDTHS, _WideShape  # noqa: F401  (part of this module's interface)
+from .mlp_actor import param_count as _param_count
+from .wide_actor import ACTIVATIONS, LDS_BYTES, MAX_HIDDEN, WIDE_WIDTHS, _WideShape, wide_plan  # noqa: F401  (part of this module's interface)
 
 N_ACTIONS = 16                   # GoToCenterEnv's Discrete(16)
 ACTOR_OUTPUTS = (1, 2, 3, 4)     # continuous: 1; turn mode: actor_out_size
@@ -18,40 +19,14 @@ _WAVE = 64
 
 
 def param_count(hidden, n_out):
-    n, win = 0, GTC_OBS_DIM
-    for w in tuple(hidden) + (n_out,):
-        n += w * win + w
-        win = w
-    return n
+    return _param_count(hidden, n_out, GTC_OBS_DIM)
 
 
 def gtc_plan(hidden, n_out):
-    """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of a 4-hidden...-n_out network, by the arithmetic of
-    the C plan (csrc/s2d_wide_net.h wide_plan_lds with input width 4).  The workspace holds every layer's fragments (ceil(h / 16)
-    tiles x its k-steps, ONE for layer 1, h_(l-1) / 4 after it, 64 words each) and the biases padded to their tiles.  The LDS
-    holds the biases and per wave two images of `tiles` x 16 rows (pitch: the widest padded layer rounded up to 64, + 4), the
-    output image and the observation tile of 64 x 4 words; there is no prepared-episode tile.  More waves go before more tiles:
-    the first of (4, 4), (4, 2), (4, 1), (2, 4), ..., (1, 1) that 160 KiB hold."""
-    na16 = (n_out + 15) // 16 * 16
-    nfrag = nbias = wmax = 0
-    ksteps = (GTC_OBS_DIM + 3) // 4
-    for w in hidden:
-        m16 = (w + 15) // 16
-        nfrag += m16 * ksteps
-        nbias += 16 * m16
-        wmax = max(wmax, 16 * m16)
-        ksteps = w // 4
-    nfrag += (na16 // 16) * ksteps
-    nbias += na16
-    rpitch = (wmax + 63) // 64 * 64 + 4
-    shared = (nbias + 3) & ~3
-    for waves in (4, 2, 1):
-        for tiles in (4, 2, 1):
-            wave_words = 2 * tiles * 16 * rpitch + _WAVE * (na16 + 4) + _WAVE * GTC_OBS_DIM
-            nbytes = (shared + waves * wave_words) * 4
-            if nbytes <= LDS_BYTES:
-                return waves, tiles, nbytes, (nfrag * _WAVE + nbias) * 4
-    raise AssertionError('one wave with one tile fits for every shape on the grid')
+    """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of a 4-hidden...-n_out network: wide_plan with input
+    width 4 (ONE k-step for layer 1) and, behind a wave's output image, only the observation tile of 64 x 4 words; there is no
+    prepared-episode tile"""
+    return wide_plan(hidden, n_out, n_in=GTC_OBS_DIM, tail_words=_WAVE * GTC_OBS_DIM)
 
 
 class _GtcShape(_WideShape):

@@ -21,6 +21,8 @@ import torch
 
 from . import _capi
 from .actor import _read_layers
+from .mlp_actor import param_count
+from .td import _arr, _fill_shape, _net_text
 from .wide_actor import _WideShape
 
 MAX_IN = 256
@@ -38,11 +40,7 @@ def _round64(w):
 
 
 def learn_param_count(n_in, hidden, n_out):
-    n, win = 0, n_in
-    for w in tuple(hidden) + (n_out,):
-        n += w * win + w
-        win = w
-    return n
+    return param_count(hidden, n_out, n_in)
 
 
 def learn_workspace_bytes(n_in, hidden, n_out, max_batch):
@@ -121,14 +119,11 @@ class QLearner:
         device: where the buffers, and from then on the module's parameters, live (default: the module's)."""
         return cls(q_net, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, loss=loss, max_batch=max_batch, device=device)
 
-    def text(self):
-        return '-'.join(map(str, (self.n_in,) + self.hidden + (self.n_out,)))
+    text = _net_text
 
     # ------------------------------------------------------------------ the step
     def _arr(self, who, name, t, dtype, shape):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f'{who}: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
-        return C.c_void_p(t.data_ptr())
+        return _arr(who, self.device, name, t, dtype, shape)
 
     def _call(self, fn, batch, target, weight, td_abs_out, q_out):
         who = f'QLearner.{"step" if fn == "s2d_learn_q" else "grad"}'
@@ -157,11 +152,7 @@ class QLearner:
         _capi.check(lib, rc, fn)
 
     def c_structs(self):
-        net, st = _capi.S2DLearnNet(), _capi.S2DLearnState()
-        net.n_in, net.n_hidden, net.n_out = self.n_in, len(self.hidden), self.n_out
-        for l in range(len(net.hidden)):
-            net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
-        net.activation = ('relu', 'tanh', 'sigmoid').index(self.activation)
+        net, st = _fill_shape(_capi.S2DLearnNet(), self), _capi.S2DLearnState()
         net.params, net.workspace, net.workspace_bytes = self.params.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4
         st.m, st.v, st.grad = self.m.data_ptr(), self.v.data_ptr(), self._grad.data_ptr()
         st.hyper, st.stats, st.error, st.loss_kind = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr(), self.loss_kind

@@ -24,13 +24,13 @@ _OBS_TILE = _WAVE * OBS_DIM
 _PREP_TILE = (13 + OBS_DIM + 2) * _WAVE
 
 
-def _fragments(hidden, n_out):
-    """(fragments, bias words, widest padded layer, n_out rounded up to 16) of a 10-hidden...-n_out network, as both C plans count
-    them: ceil(h / 16) tiles of 16 rows x the layer's k-steps (3 for layer 1, h_(l-1) / 4 after it), the biases padded to their
-    tiles"""
+def _fragments(hidden, n_out, n_in=OBS_DIM):
+    """(fragments, bias words, widest padded layer, n_out rounded up to 16) of an n_in-hidden...-n_out network, as the C plans
+    count them (csrc/s2d_wide_pack.hip s2d_internal_wide_counts): ceil(h / 16) tiles of 16 rows x the layer's k-steps
+    (ceil(n_in / 4) for layer 1: 3 for the 10-word observation; h_(l-1) / 4 after it), the biases padded to their tiles"""
     na16 = (n_out + 15) // 16 * 16
     nfrag = nbias = wmax = 0
-    ksteps = 3
+    ksteps = (n_in + 3) // 4
     for w in hidden:
         m16 = (w + 15) // 16
         nfrag += m16 * ksteps
@@ -73,8 +73,9 @@ def _check_shape(hidden, n_out, activation):
     return hidden
 
 
-def param_count(hidden, n_out):
-    n, win = 0, OBS_DIM
+def param_count(hidden, n_out, n_in=OBS_DIM):
+    """parameters of an n_in-hidden...-n_out network (nn.Sequential order: every layer's weights, then its biases)"""
+    n, win = 0, n_in
     for w in tuple(hidden) + (n_out,):
         n += w * win + w
         win = w

@@ -21,7 +21,8 @@ import torch
 
 from . import _capi
 from .actor import _read_layers
-from .wide_actor import _WideShape
+from .mlp_actor import _fragments
+from .wide_actor import ACTIVATIONS, _WideShape
 
 MAX_IN = 256
 MAX_OUT = 64
@@ -33,14 +34,28 @@ def td_workspace_bytes(n_in, hidden, n_out):
     """bytes of a network's workspace, by the arithmetic of the C plan (s2d_td_workspace_bytes): every layer's fragments
     (ceil(h / 16) tiles x its k-steps, ceil(n_in / 4) for layer 1, h_(l-1) / 4 after it, 64 words each) and the biases padded to
     their tiles"""
-    nfrag = nbias = 0
-    ks = (n_in + 3) // 4
-    for w in tuple(hidden) + (n_out,):
-        m16 = (w + 15) // 16
-        nfrag += m16 * ks
-        nbias += 16 * m16
-        ks = w // 4
+    nfrag, nbias = _fragments(hidden, n_out, n_in)[:2]
     return (nfrag * _WAVE + nbias) * 4
+
+
+def _arr(who, device, name, t, dtype, shape):
+    """the pointer of an argument tensor, checked"""
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+        raise ValueError(f'{who}: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}')
+    return C.c_void_p(t.data_ptr())
+
+
+def _fill_shape(net, shape):
+    """n_in, n_hidden, hidden[], n_out and activation of a C struct from `shape` (a _Net or a learn.QLearner)"""
+    net.n_in, net.n_hidden, net.n_out = shape.n_in, len(shape.hidden), shape.n_out
+    for l in range(len(net.hidden)):
+        net.hidden[l] = shape.hidden[l] if l < len(shape.hidden) else 0
+    net.activation = ACTIVATIONS.index(shape.activation)
+    return net
+
+
+def _net_text(shape):
+    return '-'.join(map(str, (shape.n_in,) + shape.hidden + (shape.n_out,)))
 
 
 class _Net:
@@ -82,15 +97,10 @@ class _Net:
         with torch.no_grad():
             torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
 
-    def text(self):
-        return '-'.join(map(str, (self.n_in,) + self.hidden + (self.n_out,)))
+    text = _net_text
 
     def c_struct(self):
-        net = _capi.S2DTdNet()
-        net.n_in, net.n_hidden, net.n_out = self.n_in, len(self.hidden), self.n_out
-        for l in range(len(net.hidden)):
-            net.hidden[l] = self.hidden[l] if l < len(self.hidden) else 0
-        net.activation = ('relu', 'tanh', 'sigmoid').index(self.activation)
+        net = _fill_shape(_capi.S2DTdNet(), self)
         net.params = self.params.data_ptr()
         net.workspace = self.workspace.data_ptr()
         net.workspace_bytes = self.workspace.numel() * 4
@@ -118,9 +128,7 @@ class _Target:
         return self
 
     def _arr(self, name, t, dtype, shape):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f'{self._name}.target: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
-        return C.c_void_p(t.data_ptr())
+        return _arr(f'{self._name}.target', self.device, name, t, dtype, shape)
 
     def _batch(self, batch, out, return_q, extra_dtype, extra_shape):
         """target()'s argument checks: (B, the pointers of next_obs / reward / discount, the three outputs)"""

@@ -19,25 +19,26 @@ MAX_HIDDEN = 5
 WIDE_WIDTHS = tuple(range(8, 401, 4))
 ACTIVATIONS = ('relu', 'tanh', 'sigmoid')
 
-# the plan of csrc/s2d_wide_net.h (wide_plan_lds), in 4-byte words
+# the plan of csrc/s2d_wide_net.h (wide_plan_lds over s2d_wide_host.h's counts and search), in 4-byte words
 LDS_BYTES = 160 * 1024
 _WAVE = 64
 _OBS_TILE = _WAVE * OBS_DIM
 _PREP_TILE = (13 + OBS_DIM + 2) * _WAVE
 
 
-def wide_plan(hidden, n_out):
-    """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of a 10-hidden...-n_out network, by the arithmetic of
-    the C plan.  The workspace holds every layer's fragments (ceil(h / 16) tiles x its k-steps, 3 for layer 1, h_(l-1) / 4 after
-    it, 64 words each) and the biases padded to their tiles.  The LDS holds the biases and per wave two images of `tiles` x 16 rows
-    (pitch: the widest padded layer rounded up to 64, + 4), the output image, the observation tile and the prepared-episode tile.
-    More waves go before more tiles: the first of (4, 4), (4, 2), (4, 1), (2, 4), ..., (1, 1) that 160 KiB hold."""
-    nfrag, nbias, wmax, na16 = _fragments(hidden, n_out)
+def wide_plan(hidden, n_out, n_in=OBS_DIM, tail_words=_OBS_TILE + _PREP_TILE):
+    """(waves per workgroup, env tiles per pass, LDS bytes, workspace bytes) of an n_in-hidden...-n_out network, by the arithmetic
+    of the C plan.  The workspace holds every layer's fragments (ceil(h / 16) tiles x its k-steps, ceil(n_in / 4) for layer 1 --
+    3 for the 10-word observation -- and h_(l-1) / 4 after it, 64 words each) and the biases padded to their tiles.  The LDS holds
+    the biases and per wave two images of `tiles` x 16 rows (pitch: the widest padded layer rounded up to 64, + 4), the output
+    image and `tail_words` behind it (here the observation tile and the prepared-episode tile).  More waves go before more
+    tiles: the first of (4, 4), (4, 2), (4, 1), (2, 4), ..., (1, 1) that 160 KiB hold."""
+    nfrag, nbias, wmax, na16 = _fragments(hidden, n_out, n_in)
     rpitch = (wmax + 63) // 64 * 64 + 4
     shared = (nbias + 3) & ~3
     for waves in (4, 2, 1):
         for tiles in (4, 2, 1):
-            wave_words = 2 * tiles * 16 * rpitch + _WAVE * (na16 + 4) + _OBS_TILE + _PREP_TILE
+            wave_words = 2 * tiles * 16 * rpitch + _WAVE * (na16 + 4) + tail_words
             nbytes = (shared + waves * wave_words) * 4
             if nbytes <= LDS_BYTES:
                 return waves, tiles, nbytes, (nfrag * _WAVE + nbias) * 4
