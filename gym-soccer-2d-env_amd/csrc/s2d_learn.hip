@@ -2,7 +2,8 @@
 // s2d_learn_q_grad): forward, TD error and its MSE / Huber derivative, backward, gradient-norm clip and Adam,
 // the link between s2d_td_target_q and the priority update.  Engine-independent, as s2d_td_* and s2d_replay_*: raw device
 // pointers, any stream of the current device, parameters, hyper-parameters and step state all read when the kernels run, a linear
-// chain of three launches on one stream.
+// chain of three launches on one stream.  The same chain steps a DDPG / TD3 critic on [obs | action] (s2d_learn_critic) and the
+// actor through a critic whose parameters are only read (s2d_learn_actor: loss = -mean Q(obs, tanh(mu(obs)))).
 //
 // Every chain is the spec's (tests/learn_ref.c), on the VALU:
 //   forward    acc = b[j]; k ascending: acc = fmaf(W[j][k], in[k], acc)      -- the bits of s2d_td_target_q and the wide actors
@@ -17,6 +18,12 @@
 //                            else in the workspace.
 //                            forward and delta: lane = row, a wave takes tiles of 8 units, the weights are wave-uniform;
 //                            dW: a thread takes 4 units x one input, the rows are the chain.
+//   s2d_learn_critic_kernel  the same for a critic on [obs | action], the row assembled in the kernel; its loops are the device
+//                            functions learn_forward / learn_backward, which restate the block kernel's (that kernel keeps its
+//                            inlined text: through the functions it ran 3-5 % slower).
+//   s2d_learn_actor_kernel   the same workgroup and block with both networks' rows in the image: actor forward, tanh head, critic
+//                            forward, the critic's deltas down to the action columns of its input (no critic dW or db), the head's
+//                            derivative, the actor's backward pass.
 //   s2d_learn_reduce_kernel  grad[p] = block partials in ascending order; per chunk of S2D_LEARN_NORM_CHUNK words the sum of
 //                            squares, fmaf ascending; (step) the beta products are multiplied here, once per call.
 //   s2d_learn_finish_kernel  chunks added ascending, norm, clip scale, mean loss; (step) Adam on every word.
@@ -31,6 +38,8 @@ static constexpr int kLearnRows = S2D_LEARN_BLOCK_ROWS;
 static constexpr int kLearnChunk = S2D_LEARN_NORM_CHUNK;
 static constexpr int kLearnThreads = 256;
 static constexpr int kLearnMaxHidden = 4;
+static constexpr int kLearnMaxAction = 8;   // the actor's outputs, as s2d_td_target_ac
+static constexpr int kLearnMaxObs = 248;    // so that [obs | action] stays within the grid's 256 inputs
 static_assert(kLearnRows == kWave, "lane = row of the block");
 static_assert(kLearnChunk == kLearnThreads, "one thread per word of a chunk");
 
@@ -209,6 +218,235 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_block_kernel(LearnDev
   }
 }
 
+// The layers of `d` on the block's image, lane = row, a wave takes tiles of 8 units, the weights are wave-uniform.  Layer 1 reads
+// d.n_in words at column x_off (and the zeros up to d.kp against zero weights); layer l's output follows layer l - 1's from column
+// y_off on.  Returns the column of the output layer (linear).  Ends behind a barrier.
+S2D_DEV int learn_forward(const LearnDev& d, const float* __restrict__ params, float* img, int pitch, int x_off, int y_off, int lane, int wv) {
+  const int L = d.n_hidden;
+  int in_off = x_off, out_off = y_off, win = d.n_in, kk = d.kp, po = 0;
+  for (int l = 0; l <= L; ++l) {
+    const int wout = learn_width(d, l);
+    const float* const W = params + po;
+    const float* const b = W + wout * win;
+    const float* const in = img + lane * pitch + in_off;
+    float* const out = img + lane * pitch + out_off;
+    const int act = l < L ? d.act : 3;
+    for (int j0 = 8 * wv; j0 < wout; j0 += 8 * (kLearnThreads / kWave)) {
+      float acc[8];
+      int jc[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        jc[u] = j0 + u < wout ? j0 + u : wout - 1;
+        acc[u] = b[jc[u]];
+      }
+      for (int k = 0; k < win; ++k) {
+        const float x = in[k];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = fmaf(W[jc[u] * win + k], x, acc[u]);
+      }
+      for (int k = win; k < kk; ++k) {            // layer 1's terms past n_in: x_k = 0 against zero weights
+        const float x = in[k];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = fmaf(0.0f, x, acc[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float v = acc[u];
+        const float y = act == 0 ? (v > 0.0f ? v : 0.0f) : act == 1 ? tanh_spec(v) : act == 2 ? sigmoid_spec(v) : v;
+        if (j0 + u < wout) out[j0 + u] = y;
+      }
+    }
+    __syncthreads();
+    po += wout * win + wout;
+    in_off = out_off; win = wout; kk = wout;
+    if (l < L) out_off += wout;
+  }
+  return out_off;
+}
+
+// Backward from the output layer's deltas at column q_off (the layout is learn_forward's), layer L down to 0.  GRADS: this block's
+// dW and db into mine[P], 4 units x one input per thread, rows ascending.  Every hidden layer's delta overwrites its stored
+// output; !GRADS (a network whose parameters are only read) stops with layer 1's delta at column y_off.  Called behind a barrier,
+// ends behind one.
+template <bool GRADS>
+S2D_DEV void learn_backward(const LearnDev& d, const float* __restrict__ params, float* __restrict__ mine, float* img, int pitch, int rows,
+                            int x_off, int q_off, int tid, int lane, int wv) {
+  int out_off = q_off, po = d.P;
+  for (int l = d.n_hidden; l >= 0; --l) {
+    const int wout = learn_width(d, l), win = l ? learn_width(d, l - 1) : d.n_in;
+    const int in_off = l ? out_off - win : x_off;
+    po -= wout * win + wout;
+    if (GRADS) {
+      const int items = ((wout + 3) >> 2) * win;
+      for (int idx = tid; idx < items; idx += kLearnThreads) {
+        const int jt = idx / win, k = idx - jt * win, j0 = 4 * jt;
+        int jc[4];
+        float acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          jc[u] = out_off + (j0 + u < wout ? j0 + u : wout - 1);
+          acc[u] = 0.0f;
+        }
+        for (int r = 0; r < rows; ++r) {
+          const float* const row = img + r * pitch;
+          const float x = row[in_off + k];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) acc[u] = fmaf(row[jc[u]], x, acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (j0 + u < wout) mine[po + (j0 + u) * win + k] = acc[u];
+      }
+      for (int j = tid; j < wout; j += kLearnThreads) {
+        float acc = 0.0f;
+        for (int r = 0; r < rows; ++r) acc = fmaf(img[r * pitch + out_off + j], 1.0f, acc);
+        mine[po + wout * win + j] = acc;
+      }
+      __syncthreads();
+    }
+    if (l) {
+      // the delta of the layer below over its stored output: lane = row, 8 units a tile (hidden widths are multiples of 8)
+      const float* const W = params + po;
+      const float* const dl = img + lane * pitch + out_off;
+      float* const y = img + lane * pitch + in_off;
+      for (int k0 = 8 * wv; k0 < win; k0 += 8 * (kLearnThreads / kWave)) {
+        float s[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s[u] = 0.0f;
+        for (int j = 0; j < wout; ++j) {
+          const float dj = dl[j];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) s[u] = fmaf(W[j * win + k0 + u], dj, s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) y[k0 + u] = learn_dact(d.act, y[k0 + u], s[u]);
+      }
+      __syncthreads();
+    }
+    out_off = in_off;
+  }
+}
+
+// s2d_learn_critic: the row is [obs[b]: D words | act_in[b]: n_in - D words], assembled here; the one output column takes the delta.
+// The loops are learn_forward's and learn_backward's, the chains s2d_learn_block_kernel's.
+template <bool LDS>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_critic_kernel(LearnDev d, int64_t batch, int loss_kind,
+                                                                         const float* __restrict__ params, float* __restrict__ part,
+                                                                         float* __restrict__ loss_part, float* __restrict__ image,
+                                                                         const float* __restrict__ obs, int D, const float* __restrict__ act_in,
+                                                                         const float* __restrict__ target, const float* __restrict__ weight,
+                                                                         float* __restrict__ out_td_abs, float* __restrict__ out_q) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [the rows' losses: 64 | the image, if it lives here]
+  float* const row_loss = smem;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int64_t row0 = (int64_t)blockIdx.x * kLearnRows;
+  const int rows = (int)(batch - row0 < kLearnRows ? batch - row0 : kLearnRows);
+  const int pitch = d.pitch;
+  float* const img = LDS ? smem + kLearnRows : image + (size_t)blockIdx.x * kLearnRows * pitch;
+
+  for (int idx = tid; idx < kLearnRows * d.kp; idx += kLearnThreads) {
+    const int r = idx / d.kp, k = idx - r * d.kp;
+    float x = 0.0f;
+    if (r < rows && k < d.n_in) x = k < D ? obs[(row0 + r) * D + k] : act_in[(row0 + r) * (d.n_in - D) + (k - D)];
+    img[r * pitch + k] = x;
+  }
+  __syncthreads();
+  const int q_off = learn_forward(d, params, img, pitch, 0, d.kp, lane, wv);
+
+  // ---- the rows' values, TD errors, losses and output deltas
+  if (tid < kLearnRows) {
+    float g = 0.0f, wl = 0.0f;
+    if (tid < rows) {
+      const int64_t i = row0 + tid;
+      const float q = img[tid * pitch + q_off];
+      if (out_q) out_q[i] = q;
+      const float e = q - target[i];
+      if (out_td_abs) out_td_abs[i] = fabsf(e);
+      const float w = weight ? weight[i] : 1.0f;
+      const float sq = (0.5f * e) * e, ab = fabsf(e);
+      const float l1 = loss_kind == S2D_LEARN_SQUARE ? e * e : loss_kind == S2D_LEARN_MSE ? sq : (ab <= 1.0f ? sq : ab - 0.5f);
+      const float dd = loss_kind == S2D_LEARN_SQUARE ? 2.0f * e : loss_kind == S2D_LEARN_MSE ? e : (e < -1.0f ? -1.0f : (e > 1.0f ? 1.0f : e));
+      wl = w * l1;
+      g = (w * dd) / (float)batch;
+    }
+    img[tid * pitch + q_off] = g;
+    row_loss[tid] = wl;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.0f;
+    for (int r = 0; r < rows; ++r) s = s + row_loss[r];
+    loss_part[blockIdx.x] = s;
+  }
+  learn_backward<true>(d, params, part + (size_t)blockIdx.x * d.P, img, pitch, rows, 0, q_off, tid, lane, wv);
+}
+
+// s2d_learn_actor: loss = -mean_b Q(obs_b, tanh(mu(obs_b))).  A row of the image holds both networks' rows:
+// [x: c.kp = 4 ceil((D + A) / 4) | the actor's y_1 .. y_L | a: A | the critic's y_1 .. y_L | q: 1].  The actor reads the D
+// observation words (its padded terms end before the action or on the zeros behind D, as in s2d_td_target_ac), its tanh'ed outputs
+// go behind them and stay in the actor's output columns for the head's derivative; the critic reads the whole row.  The critic's
+// backward pass forms deltas only (no dW, no db) and ends with the A action columns of its input delta.
+template <bool LDS>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_actor_kernel(LearnDev a, LearnDev c, int pitch, int64_t batch,
+                                                                        const float* __restrict__ aparams, const float* __restrict__ cparams,
+                                                                        float* __restrict__ part, float* __restrict__ loss_part,
+                                                                        float* __restrict__ image, const float* __restrict__ obs,
+                                                                        float* __restrict__ out_action, float* __restrict__ out_q) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [the rows' q: 64 | the image, if it lives here]
+  float* const row_q = smem;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int64_t row0 = (int64_t)blockIdx.x * kLearnRows;
+  const int rows = (int)(batch - row0 < kLearnRows ? batch - row0 : kLearnRows);
+  const int D = a.n_in, A = a.na;
+  float* const img = LDS ? smem + kLearnRows : image + (size_t)blockIdx.x * kLearnRows * pitch;
+
+  for (int idx = tid; idx < kLearnRows * c.kp; idx += kLearnThreads) {
+    const int r = idx / c.kp, k = idx - r * c.kp;
+    img[r * pitch + k] = (r < rows && k < D) ? obs[(row0 + r) * D + k] : 0.0f;
+  }
+  __syncthreads();
+  // ---- forward: the actor, its head, the critic
+  const int a_off = learn_forward(a, aparams, img, pitch, 0, c.kp, lane, wv);
+  for (int idx = tid; idx < kLearnRows * A; idx += kLearnThreads) {
+    const int r = idx / A, i = idx - r * A;
+    const float v = tanh_spec(img[r * pitch + a_off + i]);
+    img[r * pitch + a_off + i] = v;
+    img[r * pitch + D + i] = v;
+    if (out_action && r < rows) out_action[(row0 + r) * A + i] = v;
+  }
+  __syncthreads();
+  const int cy_off = a_off + A;
+  const int q_off = learn_forward(c, cparams, img, pitch, 0, cy_off, lane, wv);
+  if (tid < kLearnRows) {
+    const float q = img[tid * pitch + q_off];
+    if (tid < rows && out_q) out_q[row0 + tid] = q;
+    row_q[tid] = q;
+    img[tid * pitch + q_off] = tid < rows ? -1.0f / (float)batch : 0.0f;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.0f;
+    for (int r = 0; r < rows; ++r) s = s + row_q[r];
+    loss_part[blockIdx.x] = s;                      // the finish kernel negates the sum
+  }
+  // ---- backward through the critic: deltas only, then the action columns D .. D + A - 1 of its input delta and the head
+  learn_backward<false>(c, cparams, nullptr, img, pitch, rows, 0, q_off, tid, lane, wv);
+  {
+    const int h1 = learn_width(c, 0), win = c.n_in;
+    const float* const d1 = img + lane * pitch + cy_off;
+    for (int i = wv; i < A; i += kLearnThreads / kWave) {
+      float s = 0.0f;
+      for (int j = 0; j < h1; ++j) s = fmaf(cparams[j * win + D + i], d1[j], s);
+      float* const y = img + lane * pitch + a_off + i;
+      *y = learn_dact(1, *y, s);
+    }
+  }
+  __syncthreads();
+  learn_backward<true>(a, aparams, part + (size_t)blockIdx.x * a.P, img, pitch, rows, 0, a_off, tid, lane, wv);
+}
+
 // grad[p] = the blocks' partials added in ascending block order; chunk_ss[c] = fmaf(g, g, .) ascending over the chunk's words
 template <bool UPDATE>
 __global__ __launch_bounds__(kLearnThreads) void s2d_learn_reduce_kernel(int P, int64_t blocks, const float* __restrict__ part,
@@ -236,9 +474,9 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_reduce_kernel(int P, 
   }
 }
 
-// norm, clip scale and mean loss (workgroup 0 stores them); UPDATE: Adam on the chunk's words with g' = g * scale
+// norm, clip scale and mean loss (workgroup 0 stores them; negate: minus the mean); UPDATE: Adam on the chunk's words with g' = g * scale
 template <bool UPDATE>
-__global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, int64_t batch, int64_t blocks, int chunks,
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, int64_t batch, int64_t blocks, int chunks, bool negate,
                                                                          const float* __restrict__ chunk_ss,
                                                                          const float* __restrict__ loss_part, const float* __restrict__ grad,
                                                                          const float* __restrict__ hyper, float* __restrict__ stats,
@@ -259,7 +497,7 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
     if (blockIdx.x == 0) {
       float ls = loss_part[0];
       for (int64_t b = 1; b < blocks; ++b) ls = ls + loss_part[b];
-      stats[0] = ls / (float)batch;
+      stats[0] = (negate ? -ls : ls) / (float)batch;   // the actor's loss is -mean q
       stats[1] = norm;
       stats[2] = scale;
     }
@@ -284,7 +522,7 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
-struct LearnLds {};   // the owner of the block kernel's dynamic-LDS slot (allow_lds_slot); fail, misaligned and launched are s2d_wide_host.h's
+struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor); fail, misaligned and launched are s2d_wide_host.h's
 
 // "" if the shape is on the learner's grid, else the text naming the field
 std::string shape_error(const S2DLearnNet* n) {
@@ -318,85 +556,202 @@ struct LearnLayout {
   bool lds;
 };
 size_t round64(size_t w) { return (w + 63) & ~(size_t)63; }
-LearnLayout layout(const LearnDev& d, int64_t batch) {
+// P parameters of the network that is stepped, rows of `pitch` words in a block's image
+LearnLayout layout(int P, int pitch, int64_t batch) {
   LearnLayout y{};
-  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)d.P + kLearnChunk - 1) / kLearnChunk;
-  y.lds = (size_t)kLearnRows * (d.pitch + 1) * sizeof(float) <= kLdsMax;
+  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
+  y.lds = (size_t)kLearnRows * (pitch + 1) * sizeof(float) <= kLdsMax;
   y.part = 0;
-  y.chunk = round64(blocks * d.P);
+  y.chunk = round64(blocks * P);
   y.loss = y.chunk + round64(chunks);
   y.image = y.loss + round64(blocks);
-  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * d.pitch));
+  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * pitch));
   return y;
 }
+// the actor step's row holds both networks: the critic's padded input row, then each network's layer outputs
+int layer_words(const S2DLearnNet* n) {
+  int w = n->n_out;
+  for (int l = 0; l < n->n_hidden; ++l) w += n->hidden[l];
+  return w;
+}
+int pair_pitch(const S2DLearnNet* a, const S2DLearnNet* c) { return ((c->n_in + 3) / 4 * 4 + layer_words(a) + layer_words(c)) | 1; }
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
   return p < q + nb && q < p + na;
 }
+// "" if the actor / critic pair is on the grid of s2d_learn_actor
+std::string pair_error(const S2DLearnNet* actor, const S2DLearnNet* critic) {
+  std::string bad = shape_error(actor);
+  if (!bad.empty()) return "actor: " + bad;
+  bad = shape_error(critic);
+  if (!bad.empty()) return "critic: " + bad;
+  if (actor->n_out > kLearnMaxAction) return "actor: n_out (the action width) must be in [1, 8]";
+  if (actor->n_in > kLearnMaxObs) return "actor: n_in must be in [1, 248]";
+  if (critic->n_in != actor->n_in + actor->n_out || critic->n_out != 1) return "critic: n_in must be the actor's n_in + n_out, its n_out 1";
+  return "";
+}
+// the pointers of a network that is stepped and of its state; "" if acceptable
 template <bool UPDATE>
-int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S2DLearnState* st, const float* obs, const int32_t* action,
+std::string buffers_error(const char* name, const S2DLearnNet* net, const S2DLearnState* st, bool error_word) {
+  const std::string nm = name;
+  if (!net->params || misaligned(net->params, 16)) return nm + ": params must be a non-NULL, 16-byte aligned device pointer";
+  if (!net->workspace || misaligned(net->workspace, 256)) return nm + ": workspace must be a non-NULL, 256-byte aligned device pointer";
+  if (!st->grad || misaligned(st->grad, 16) || !st->hyper || misaligned(st->hyper, 4) || !st->stats || misaligned(st->stats, 4) ||
+      (error_word && (!st->error || misaligned(st->error, 4))))
+    return std::string("state: grad (16 bytes), hyper, stats") + (error_word ? " and error" : "") +
+           " (4 bytes) must be non-NULL, aligned device pointers";
+  if (UPDATE && (!st->m || !st->v || misaligned(st->m, 16) || misaligned(st->v, 16)))
+    return "state: m and v must be non-NULL, 16-byte aligned device pointers";
+  return "";
+}
+// the workspace's size and the overlaps of what a call writes (and, for the actor step, the critic's parameters it reads)
+template <bool UPDATE>
+std::string layout_error(const char* name, const S2DLearnNet* net, const S2DLearnState* st, const LearnLayout& y, int P, int64_t batch,
+                         const char* bytes_fn, const float* read_only, size_t read_only_bytes) {
+  if (net->workspace_bytes < y.words * sizeof(float))
+    return std::string(name) + ": workspace_bytes is " + std::to_string(net->workspace_bytes) + ", a batch of " + std::to_string(batch) +
+           " needs " + std::to_string(y.words * sizeof(float)) + " (" + bytes_fn + ": batch is above the workspace's max_batch)";
+  const size_t pb = (size_t)P * sizeof(float);
+  const void* bufs[6] = {net->params, st->grad, net->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr, read_only};
+  const size_t lens[6] = {pb, pb, y.words * sizeof(float), pb, pb, read_only_bytes};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
+        return read_only ? "the actor's params, m, v, grad and workspace must not overlap one another or the critic's params"
+                         : "params, m, v, grad and the workspace must not overlap one another";
+  return "";
+}
+// what follows the block kernel: the reduction over the blocks, then norm, clip, stats and (UPDATE) Adam
+template <bool UPDATE>
+void reduce_and_finish(int P, int64_t batch, bool negate, const LearnLayout& y, const S2DLearnNet* net, const S2DLearnState* st, hipStream_t s) {
+  float* const ws = static_cast<float*>(net->workspace);
+  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
+  const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
+  hipLaunchKernelGGL(s2d_learn_reduce_kernel<UPDATE>, dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, blocks, ws + y.part, st->grad,
+                     ws + y.chunk, st->hyper);
+  hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, batch, blocks,
+                     chunks, negate, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
+}
+int no_lds(const std::string& who) {
+  s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+  return S2D_EHIP;
+}
+
+// s2d_learn_q[_grad] (CRITIC = false: action is int32 [B]) and s2d_learn_critic[_grad] (CRITIC = true: action is float [B][A])
+template <bool UPDATE, bool CRITIC>
+int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S2DLearnState* st, const float* obs, int A, const void* action,
           const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
   if (!net || !st) return fail(who, "net and state must be non-NULL");
   const std::string bad = shape_error(net);
   if (!bad.empty()) return fail(who, "net: " + bad);
-  if (st->loss_kind != S2D_LEARN_MSE && st->loss_kind != S2D_LEARN_HUBER) return fail(who, "state: loss_kind must be 0 (MSE) or 1 (Huber)");
+  if (CRITIC) {
+    if (A < 1 || A > kLearnMaxAction) return fail(who, "action_dim must be in [1, 8]");
+    if (net->n_out != 1) return fail(who, "net: n_out must be 1 (a critic)");
+    if (net->n_in - A < 1 || net->n_in - A > kLearnMaxObs)
+      return fail(who, "net: n_in must be obs_dim + action_dim with obs_dim in [1, 248]");
+    if (st->loss_kind < S2D_LEARN_MSE || st->loss_kind > S2D_LEARN_SQUARE)
+      return fail(who, "state: loss_kind must be 0 (MSE), 1 (Huber) or 2 (square)");
+  } else if (st->loss_kind != S2D_LEARN_MSE && st->loss_kind != S2D_LEARN_HUBER) {
+    return fail(who, "state: loss_kind must be 0 (MSE) or 1 (Huber)");
+  }
   if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
-  if (!net->params || misaligned(net->params, 16)) return fail(who, "net: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!net->workspace || misaligned(net->workspace, 256)) return fail(who, "net: workspace must be a non-NULL, 256-byte aligned device pointer");
-  if (!st->grad || misaligned(st->grad, 16) || !st->hyper || misaligned(st->hyper, 4) || !st->stats || misaligned(st->stats, 4) ||
-      !st->error || misaligned(st->error, 4))
-    return fail(who, "state: grad (16 bytes), hyper, stats and error (4 bytes) must be non-NULL, aligned device pointers");
-  if (UPDATE && (!st->m || !st->v || misaligned(st->m, 16) || misaligned(st->v, 16)))
-    return fail(who, "state: m and v must be non-NULL, 16-byte aligned device pointers");
+  std::string err = buffers_error<UPDATE>("net", net, st, true);
+  if (!err.empty()) return fail(who, err);
   if (!obs || !action || !target || misaligned(obs, 4) || misaligned(action, 4) || misaligned(target, 4))
     return fail(who, "obs, action and target must be non-NULL, 4-byte aligned device pointers");
   if (misaligned(weight, 4) || misaligned(out_td_abs, 4) || misaligned(out_q, 4))
     return fail(who, "weight, out_td_abs and out_q must be 4-byte aligned device pointers (or NULL)");
   const LearnDev d = net_dev(net);
-  const LearnLayout y = layout(d, batch);
-  if (net->workspace_bytes < y.words * sizeof(float))
-    return fail(who, "net: workspace_bytes is " + std::to_string(net->workspace_bytes) + ", a batch of " + std::to_string(batch) + " needs " +
-                         std::to_string(y.words * sizeof(float)) + " (s2d_learn_workspace_bytes: batch is above the workspace's max_batch)");
-  const size_t pb = (size_t)d.P * sizeof(float);
-  const void* bufs[5] = {net->params, st->grad, net->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr};
-  const size_t lens[5] = {pb, pb, y.words * sizeof(float), pb, pb};
-  for (int i = 0; i < 5; ++i)
-    for (int j = i + 1; j < 5; ++j)
-      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
-        return fail(who, "params, m, v, grad and the workspace must not overlap one another");
-  using Block = void (*)(LearnDev, int64_t, int, const float*, float*, float*, float*, const float*, const int32_t*, const float*, const float*,
-                         float*, float*, int32_t*);
-  const Block kb = y.lds ? s2d_learn_block_kernel<true> : s2d_learn_block_kernel<false>;
+  const LearnLayout y = layout(d.P, d.pitch, batch);
+  err = layout_error<UPDATE>("net", net, st, y, d.P, batch, "s2d_learn_workspace_bytes", nullptr, 0);
+  if (!err.empty()) return fail(who, err);
   const size_t lds = (size_t)kLearnRows * ((y.lds ? d.pitch : 0) + 1) * sizeof(float);
-  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 0)) {
-    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
-    return S2D_EHIP;
-  }
   float* const ws = static_cast<float*>(net->workspace);
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
-  const int chunks = (d.P + kLearnChunk - 1) / kLearnChunk;
-  hipLaunchKernelGGL(kb, dim3((unsigned)blocks), dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part,
-                     ws + y.loss, ws + y.image, obs, action, target, weight, out_td_abs, out_q, st->error);
-  hipLaunchKernelGGL(s2d_learn_reduce_kernel<UPDATE>, dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, d.P, blocks, ws + y.part, st->grad,
-                     ws + y.chunk, st->hyper);
-  hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, d.P, batch, blocks,
-                     chunks, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
+  const dim3 grid((unsigned)((batch + kLearnRows - 1) / kLearnRows));
+  if (CRITIC) {
+    const auto kb = y.lds ? s2d_learn_critic_kernel<true> : s2d_learn_critic_kernel<false>;
+    if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 1)) return no_lds(who);
+    hipLaunchKernelGGL(kb, grid, dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image,
+                       obs, net->n_in - A, static_cast<const float*>(action), target, weight, out_td_abs, out_q);
+  } else {
+    const auto kb = y.lds ? s2d_learn_block_kernel<true> : s2d_learn_block_kernel<false>;
+    if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 0)) return no_lds(who);
+    hipLaunchKernelGGL(kb, grid, dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image,
+                       obs, static_cast<const int32_t*>(action), target, weight, out_td_abs, out_q, st->error);
+  }
+  reduce_and_finish<UPDATE>(d.P, batch, false, y, net, st, s);
+  return launched(who);
+}
+
+template <bool UPDATE>
+int learn_actor(const std::string& who, int64_t batch, const S2DLearnNet* actor, const S2DLearnState* st, const S2DLearnNet* critic,
+                const float* obs, float* out_action, float* out_q, void* stream) {
+  if (!actor || !st || !critic) return fail(who, "actor, state and critic must be non-NULL");
+  std::string err = pair_error(actor, critic);
+  if (!err.empty()) return fail(who, err);
+  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  err = buffers_error<UPDATE>("actor", actor, st, false);
+  if (!err.empty()) return fail(who, err);
+  if (!critic->params || misaligned(critic->params, 16)) return fail(who, "critic: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!obs || misaligned(obs, 4)) return fail(who, "obs must be a non-NULL, 4-byte aligned device pointer");
+  if (misaligned(out_action, 4) || misaligned(out_q, 4)) return fail(who, "out_action and out_q must be 4-byte aligned device pointers (or NULL)");
+  const LearnDev a = net_dev(actor), c = net_dev(critic);
+  const int pitch = pair_pitch(actor, critic);
+  const LearnLayout y = layout(a.P, pitch, batch);
+  err = layout_error<UPDATE>("actor", actor, st, y, a.P, batch, "s2d_learn_actor_workspace_bytes", critic->params, (size_t)c.P * sizeof(float));
+  if (!err.empty()) return fail(who, err);
+  const auto kb = y.lds ? s2d_learn_actor_kernel<true> : s2d_learn_actor_kernel<false>;
+  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + 1) * sizeof(float);
+  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 2)) return no_lds(who);
+  float* const ws = static_cast<float*>(actor->workspace);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kb, dim3((unsigned)((batch + kLearnRows - 1) / kLearnRows)), dim3(kLearnThreads), lds, s, a, c, pitch, batch, actor->params,
+                     critic->params, ws + y.part, ws + y.loss, ws + y.image, obs, out_action, out_q);
+  reduce_and_finish<UPDATE>(a.P, batch, true, y, actor, st, s);
   return launched(who);
 }
 }  // namespace
 
 S2D_API size_t s2d_learn_workspace_bytes(const S2DLearnNet* shape, int64_t max_batch) {
   if (!shape || !shape_error(shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
-  return layout(net_dev(shape), max_batch).words * sizeof(float);
+  const LearnDev d = net_dev(shape);
+  return layout(d.P, d.pitch, max_batch).words * sizeof(float);
+}
+
+S2D_API size_t s2d_learn_actor_workspace_bytes(const S2DLearnNet* actor_shape, const S2DLearnNet* critic_shape, int64_t max_batch) {
+  if (!actor_shape || !critic_shape || !pair_error(actor_shape, critic_shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  const LearnDev a = net_dev(actor_shape);
+  return layout(a.P, pair_pitch(actor_shape, critic_shape), max_batch).words * sizeof(float);
 }
 
 S2D_API int s2d_learn_q(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, const int32_t* action,
                         const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
-  return learn<true>("s2d_learn_q", batch, net, state, obs, action, target, weight, out_td_abs, out_q, stream);
+  return learn<true, false>("s2d_learn_q", batch, net, state, obs, 0, action, target, weight, out_td_abs, out_q, stream);
 }
 
 S2D_API int s2d_learn_q_grad(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, const int32_t* action,
                              const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
-  return learn<false>("s2d_learn_q_grad", batch, net, state, obs, action, target, weight, out_td_abs, out_q, stream);
+  return learn<false, false>("s2d_learn_q_grad", batch, net, state, obs, 0, action, target, weight, out_td_abs, out_q, stream);
+}
+
+S2D_API int s2d_learn_critic(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, int32_t action_dim,
+                             const float* action, const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
+  return learn<true, true>("s2d_learn_critic", batch, net, state, obs, action_dim, action, target, weight, out_td_abs, out_q, stream);
+}
+
+S2D_API int s2d_learn_critic_grad(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, int32_t action_dim,
+                                  const float* action, const float* target, const float* weight, float* out_td_abs, float* out_q,
+                                  void* stream) {
+  return learn<false, true>("s2d_learn_critic_grad", batch, net, state, obs, action_dim, action, target, weight, out_td_abs, out_q, stream);
+}
+
+S2D_API int s2d_learn_actor(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic,
+                            const float* obs, float* out_action, float* out_q, void* stream) {
+  return learn_actor<true>("s2d_learn_actor", batch, actor, actor_state, critic, obs, out_action, out_q, stream);
+}
+
+S2D_API int s2d_learn_actor_grad(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic,
+                                 const float* obs, float* out_action, float* out_q, void* stream) {
+  return learn_actor<false>("s2d_learn_actor_grad", batch, actor, actor_state, critic, obs, out_action, out_q, stream);
 }

@@ -14,6 +14,9 @@ with Polyak averaging, Gaussian action noise, a replay buffer in device memory.
 phase and Timeouts bootstrap from the recorded terminal observations.  0: one torch forward per step.
 --fused-target computes the TD targets in one launch from the target actor and critic (soccer2d_amd.td.ActorCriticTarget,
 INTEGRATION 3f) instead of a chain of torch ops, and reloads its buffers after every Polyak step.
+--fused-learner runs the critic's and the actor's update in HIP (soccer2d_amd.learn.ActorCriticLearner): forward,
+backward through the critic and Adam, three launches each, and the Polyak step as one lerp_ per network; the networks must be on
+the learner's grid (1 to 4 hidden layers of multiples of 8 in [8, 256]), so SB3's [400, 300] stays with torch's optimisers.
 """
 import argparse
 import copy
@@ -71,9 +74,9 @@ class DeviceReplay:
 class DeviceDDPG:
     def __init__(self, env, lr=1e-3, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, grad_steps=1, sigma=0.1,
                  learning_starts=2, seed=0, net_arch=None, activation='relu', n_step=1, per_alpha=0.0, per_beta=0.4,
-                 fused_target=False):
+                 fused_target=False, fused_learner=False):
         torch.manual_seed(seed)
-        self.fused_target = fused_target
+        self.fused_target, self.fused_learner, self.lr = fused_target, fused_learner, lr
         self.buffer, self.n_step, self.seed = buffer, n_step, seed
         self.per_alpha, self.per_beta = per_alpha, per_beta             # alpha 0: the uniform DeviceReplay
         self.env, self.dev = env, env.device
@@ -102,6 +105,8 @@ class DeviceDDPG:
         PrioritizedReplay: the critic's loss carries the importance weights and the batch's slots get (|TD error| + 1e-6) ** alpha
         as their new priority."""
         per = fused and self.per_alpha > 0
+        if fused and self.fused_learner:
+            return self.optimise_fused(n_updates, per)
         for _g in range(n_updates):
             if fused:
                 b = self.frb.sample(self.batch, out=self.fbatch)
@@ -134,6 +139,42 @@ class DeviceDDPG:
                         pt.mul_(1 - self.tau).add_(p, alpha=self.tau)
             if fused and self.fused_target:
                 self.td.sync()                                   # the next target launch reads the Polyak-averaged weights
+
+    def optimise_fused(self, n_updates, per):
+        """--fused-learner: sample -> target -> the critic's step -> the actor's step -> the Polyak step, the two steps in HIP"""
+        for _g in range(n_updates):
+            b = self.frb.sample(self.batch, out=self.fbatch)
+            if self.fused_target:
+                tgt = self.td.target(b, out=self.ftgt)
+            else:
+                with torch.no_grad():
+                    no = b['next_obs']
+                    tgt = b['reward'] + b['discount'] * self.q_target(torch.cat([no, self.mu_target(no)], 1)).squeeze(1)
+            if per:
+                self.learner.step(b, tgt, weight=self.frb.weights(b, self.per_beta), td_abs_out=self.fabs)
+                self.frb.update_priorities(b['index'], (self.fabs + 1e-6) ** self.per_alpha)
+            else:
+                self.learner.step(b, tgt)
+            if self.fused_target:
+                self.learner.update_targets(self.td, self.tau)   # flat buffer to flat buffer; the target modules follow
+            else:
+                with torch.no_grad():
+                    for net, tgt_net in ((self.mu, self.mu_target), (self.q, self.q_target)):
+                        for p, pt in zip(net.parameters(), tgt_net.parameters()):
+                            pt.mul_(1 - self.tau).add_(p, alpha=self.tau)
+
+    def make_fused_learner(self):
+        """--fused-learner: the learner takes over mu's and q's parameters (they become views of its flat buffers), made once"""
+        if self.fused_learner and not hasattr(self, 'learner'):
+            from soccer2d_amd.learn import ActorCriticLearner
+            try:
+                self.learner = ActorCriticLearner.from_modules(self.mu, self.q, actor_lr=self.lr, critic_lr=self.lr,
+                                                               max_batch=self.batch, device=self.dev)
+            except ValueError as e:
+                raise SystemExit(f'--fused-learner: {e}.  The learner\'s grid is 1 to 4 hidden layers of multiples of 8 in [8, 256] '
+                                 'with ReLU, Tanh or Sigmoid, at most 248 observation words and 8 actions; run this network without '
+                                 '--fused-learner') from None
+            self.fabs = torch.empty((self.batch,), dtype=torch.float32, device=self.dev)
 
     def _store(self, obs_t, act, rec_obs, rew, done, res, term_obs):
         next_obs = torch.where(done.bool().unsqueeze(-1), term_obs, rec_obs)            # bootstrap through Timeouts
@@ -173,6 +214,7 @@ class DeviceDDPG:
             print(f'fused actor: {type(self.actor).__name__}')
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True)
         self.make_fused_target()
+        self.make_fused_learner()
         eng, rec = self.env.engine, self.rec
         rb = self.fused_replay(T, eng.obs.shape[-1])
         for _ in range((vec_steps + T - 1) // T):
@@ -242,15 +284,19 @@ def main():
                     help='with --fused-actor: the TD targets in one launch from the target actor and critic '
                          '(soccer2d_amd.td.ActorCriticTarget)')
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help="with --fused-actor: the critic's and the actor's update in HIP (soccer2d_amd.learn.ActorCriticLearner)")
     args = ap.parse_args()
     if args.fused_target and args.fused_actor <= 0:
         ap.error('--fused-target needs --fused-actor T')
+    if args.fused_learner and args.fused_actor <= 0:
+        ap.error('--fused-learner needs --fused-actor T')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
     model = DeviceDDPG(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
-                       per_beta=args.per_beta, fused_target=args.fused_target)
+                       per_beta=args.per_beta, fused_target=args.fused_target, fused_learner=args.fused_learner)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -15,6 +15,7 @@ packed weights are refreshed with sync() after every optimiser phase and Timeout
 observations; the record goes into a soccer2d_amd.replay.DeviceReplay in one launch (--n-step K: K-step returns).
 --fused-target computes the TD targets in one launch from the target network(s) (soccer2d_amd.td); --double-q: Double DQN.
 --fused-learner (the discrete env, with --fused-actor and --fused-target): every DQN update is one soccer2d_amd.learn.QLearner call.
+--fused-learner with --continuous (and --fused-actor): DDPG's critic and actor updates are soccer2d_amd.learn.ActorCriticLearner's.
 --net-arch / --activation: the Optuna grids of best_python_sample_soccer_env*.py (1 to 5 widths, multiples of 4 up to 400; relu,
 tanh or sigmoid).
 """
@@ -71,6 +72,7 @@ class GtcDDPG(DeviceDDPG):
             print(f'fused actor: {type(self.actor).__name__} {self.actor.hidden} {self.actor.activation}')
             self.rec = None
         self.make_fused_target()
+        self.make_fused_learner()
         env = self.env
         rb = self.fused_replay(T, 4)
         for _ in range((vec_steps + T - 1) // T):
@@ -106,15 +108,16 @@ def main():
     ap.add_argument('--double-q', action='store_true', help='the discrete env: Double DQN')
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     ap.add_argument('--fused-learner', action='store_true',
-                    help='the discrete env, with --fused-actor and --fused-target: forward, backward, clip and Adam in one call')
+                    help='the discrete env, with --fused-actor and --fused-target: forward, backward, clip and Adam in one call; '
+                         "--continuous, with --fused-actor: DDPG's critic and actor updates in HIP")
     args = ap.parse_args()
     if args.fused_target and args.fused_actor <= 0:
         ap.error('--fused-target needs --fused-actor T')
     if args.double_q and args.continuous:
         ap.error('--double-q is for the discrete env (DQN)')
-    if args.fused_learner and args.continuous:
-        ap.error('--fused-learner is for the discrete env (DQN)')
-    if args.fused_learner and not (args.fused_actor > 0 and args.fused_target):
+    if args.fused_learner and args.continuous and args.fused_actor <= 0:
+        ap.error('--fused-learner needs --fused-actor T')
+    if args.fused_learner and not args.continuous and not (args.fused_actor > 0 and args.fused_target):
         ap.error('--fused-learner needs --fused-actor T and --fused-target')
     net_arch = [int(w) for w in args.net_arch.split(',')] if args.net_arch else None
     kw = dict(continuous=args.continuous, turn=args.turn, use_turn=args.useturn,
@@ -123,7 +126,7 @@ def main():
     test_env = GoToCenterVecEnv(args.envs, args.device, seed=1234, **kw)
     learner = dict(net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha, per_beta=args.per_beta,
                    fused_target=args.fused_target)
-    model, test = (GtcDDPG(env, **learner), test_ddpg) if args.continuous else (GtcDQN(env, double_q=args.double_q, fused_learner=args.fused_learner, **learner), test_dqn)
+    model, test = (GtcDDPG(env, fused_learner=args.fused_learner, **learner), test_ddpg) if args.continuous else (GtcDQN(env, double_q=args.double_q, fused_learner=args.fused_learner, **learner), test_dqn)
     print('untrained:', test(test_env, model, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()

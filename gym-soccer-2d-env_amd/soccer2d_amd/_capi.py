@@ -219,6 +219,15 @@ PROTOTYPES = (
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_learn_q_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_critic', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_critic_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_actor', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.POINTER(S2DLearnNet), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_actor_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.POINTER(S2DLearnNet), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_actor_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.c_int64)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

@@ -13,8 +13,10 @@ float atomics), equal to tests/learn_ref.c.
 The learner owns ONE flat fp32 parameter buffer and REBINDS THE MODULE'S PARAMETERS AS VIEWS OF IT: the module always holds the
 learner's weights, so ``actor.sync()``, ``QTarget.sync()`` and ``state_dict()`` keep working unchanged.  Learning rate, betas,
 epsilon, the clip norm and Adam's running beta products are device words read when the kernels run: a step is a linear chain on
-torch's current stream, capturable, and ``set_lr`` between replays takes effect.  Out of scope: the DDPG / TD3 update (the
-actor's gradient through the critic)."""
+torch's current stream, capturable, and ``set_lr`` between replays takes effect.
+
+ActorCriticLearner is the same for DDPG and TD3 (s2d_learn_critic / s2d_learn_actor): the critics' step on [obs | action] and the
+actor's step on -mean Q(obs, tanh-mu(obs)), whose gradient goes through the critic inside one kernel; tests/learn_ac_ref.c."""
 import ctypes as C
 
 import torch
@@ -33,6 +35,9 @@ BLOCK_ROWS = 64      # S2D_LEARN_BLOCK_ROWS
 NORM_CHUNK = 256     # S2D_LEARN_NORM_CHUNK
 LDS_BYTES = 160 * 1024
 LOSSES = ('mse', 'huber')
+AC_LOSSES = ('mse', 'huber', 'square')   # S2D_LEARN_SQUARE: the critics' steps only
+MAX_ACTION = 8
+MAX_OBS = 248
 
 
 def _round64(w):
@@ -56,39 +61,97 @@ def learn_workspace_bytes(n_in, hidden, n_out, max_batch):
     return words * 4
 
 
+def learn_actor_workspace_bytes(obs_dim, actor_hidden, action_dim, critic_hidden, max_batch):
+    """bytes of the ACTOR's workspace for the actor step through a critic (s2d_learn_actor_workspace_bytes): the parts above for the
+    actor's parameters, and the blocks' images where 64 rows of BOTH networks ([obs | action] padded to a multiple of 4, every
+    layer's outputs of the actor and of the critic) do not fit the LDS"""
+    P = learn_param_count(obs_dim, actor_hidden, action_dim)
+    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
+    pitch = ((obs_dim + action_dim + 3) // 4 * 4 + sum(actor_hidden) + action_dim + sum(critic_hidden) + 1) | 1
+    words = _round64(blocks * P) + _round64(chunks) + _round64(blocks)
+    if BLOCK_ROWS * (pitch + 1) * 4 > LDS_BYTES:
+        words += _round64(blocks * BLOCK_ROWS * pitch)
+    return words * 4
+
+
+def _read_shape(who, what, module, tanh_head=False):
+    """(linears, hidden, n_in, n_out, activation) of `module` = Linear-(F-Linear) x L [-Tanh] on the learner's grid"""
+    if not isinstance(module, torch.nn.Module):
+        raise ValueError(f'{who}: the {what} must be a torch.nn.Module')
+    try:
+        linears, act = _read_layers(module, **dict(_WideShape._grid, tanh_head=tanh_head))
+    except ValueError as e:
+        raise ValueError(f'{who}: {what}: {e}') from None
+    if any(lin.bias is None for lin in linears):
+        raise ValueError(f'{who}: every nn.Linear of the {what} needs a bias')
+    if any(p.dtype != torch.float32 for lin in linears for p in (lin.weight, lin.bias)):
+        raise ValueError(f'{who}: the {what}\'s parameters must be float32')
+    hidden = tuple(lin.out_features for lin in linears[:-1])
+    n_in = linears[0].in_features
+    if not 1 <= len(hidden) <= MAX_HIDDEN:
+        raise ValueError(f'{who}: the learner takes 1 to {MAX_HIDDEN} hidden layers, got {len(hidden)}')
+    for w in hidden:
+        if w % 8 or not 8 <= w <= MAX_WIDTH:
+            raise ValueError(f'{who}: every hidden width must be a multiple of 8 in [8, {MAX_WIDTH}], got {w} in {list(hidden)}')
+    if not 1 <= n_in <= MAX_IN:
+        raise ValueError(f'{who}: the {what}\'s input width must be in [1, {MAX_IN}], got {n_in}')
+    return linears, hidden, n_in, linears[-1].out_features, act
+
+
+def _check_optimiser(who, max_batch, lr, betas, eps):
+    """max_batch and Adam's arguments, checked; returns the betas as floats"""
+    if not isinstance(max_batch, int) or not 1 <= max_batch < 2 ** 31:
+        raise ValueError(f'{who}: max_batch must be an int in [1, 2^31 - 1], got {max_batch!r}')
+    b1, b2 = (float(b) for b in betas)
+    if not (lr >= 0.0 and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps >= 0.0):
+        raise ValueError(f'{who}: lr and eps must be >= 0 and the betas in [0, 1), got lr={lr}, betas={betas}, eps={eps}')
+    return b1, b2
+
+
+def _rebind(params, linears):
+    """the module's parameters become views of the flat buffer (nn.Sequential order), which takes their values: the module IS the
+    learner's weights"""
+    off = 0
+    with torch.no_grad():
+        for lin in linears:
+            for p in (lin.weight, lin.bias):
+                n = p.numel()
+                params[off:off + n].copy_(p.detach().reshape(-1))
+                p.data = params[off:off + n].view_as(p)
+                off += n
+
+
+def _into_target(params, net, tau, mirror):
+    """`params` into the td._Net `net`'s flat buffer, hard (tau = 1) or as a Polyak step, and on into the mirror buffer that the
+    target MODULE's parameters are views of; returns the (net, mirror) pair to keep"""
+    with torch.no_grad():
+        if tau == 1.0:
+            net.params.copy_(params)
+        else:
+            net.params.lerp_(params, float(tau))
+        if mirror is None or mirror[0] is not net:
+            linears, _ = _read_layers(net.module, **dict(_WideShape._grid, tanh_head=net._tanh_head))
+            buf, off = torch.empty_like(net.params), 0
+            for lin in linears:
+                for p in (lin.weight, lin.bias):
+                    p.data = buf[off:off + p.numel()].view_as(p)
+                    off += p.numel()
+            mirror = (net, buf)
+        mirror[1].copy_(net.params)
+    return mirror
+
+
 class QLearner:
     """The online Q-network's optimiser step in one call.  ``q_net`` is Linear-(F-Linear) x L (SB3's ``q_net.q_net``)."""
 
     def __init__(self, q_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=10.0, loss='huber', max_batch=4096, device=None):
         who = 'QLearner'
-        if not isinstance(q_net, torch.nn.Module):
-            raise ValueError(f'{who}: the Q-network must be a torch.nn.Module')
-        try:
-            linears, act = _read_layers(q_net, **_WideShape._grid)
-        except ValueError as e:
-            raise ValueError(f'{who}: Q-network: {e}') from None
-        if any(lin.bias is None for lin in linears):
-            raise ValueError(f'{who}: every nn.Linear of the Q-network needs a bias')
-        if any(p.dtype != torch.float32 for lin in linears for p in (lin.weight, lin.bias)):
-            raise ValueError(f'{who}: the Q-network\'s parameters must be float32')
-        self.hidden = tuple(lin.out_features for lin in linears[:-1])
-        self.n_in, self.n_out, self.activation = linears[0].in_features, linears[-1].out_features, act
-        if not 1 <= len(self.hidden) <= MAX_HIDDEN:
-            raise ValueError(f'{who}: the learner takes 1 to {MAX_HIDDEN} hidden layers, got {len(self.hidden)}')
-        for w in self.hidden:
-            if w % 8 or not 8 <= w <= MAX_WIDTH:
-                raise ValueError(f'{who}: every hidden width must be a multiple of 8 in [8, {MAX_WIDTH}], got {w} in {list(self.hidden)}')
-        if not 1 <= self.n_in <= MAX_IN:
-            raise ValueError(f'{who}: the Q-network\'s input width must be in [1, {MAX_IN}], got {self.n_in}')
+        linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, 'Q-network', q_net)
         if not 1 <= self.n_out <= MAX_OUT:
             raise ValueError(f'{who}: the Q-network\'s output width must be in [1, {MAX_OUT}], got {self.n_out}')
         if loss not in LOSSES:
             raise ValueError(f"{who}: loss must be 'huber' or 'mse', got {loss!r}")
-        if not isinstance(max_batch, int) or not 1 <= max_batch < 2 ** 31:
-            raise ValueError(f'{who}: max_batch must be an int in [1, 2^31 - 1], got {max_batch!r}')
-        b1, b2 = (float(b) for b in betas)
-        if not (lr >= 0.0 and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps >= 0.0):
-            raise ValueError(f'{who}: lr and eps must be >= 0 and the betas in [0, 1), got lr={lr}, betas={betas}, eps={eps}')
+        b1, b2 = _check_optimiser(who, max_batch, lr, betas, eps)
         self.module, self.loss_kind, self.max_batch = q_net, LOSSES.index(loss), max_batch
         dev = torch.device(device if device is not None else linears[0].weight.device)
         f32 = torch.float32
@@ -101,15 +164,7 @@ class QLearner:
         self.stats = torch.zeros(3, dtype=f32, device=self.device)
         self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.workspace = torch.zeros(learn_workspace_bytes(self.n_in, self.hidden, self.n_out, max_batch) // 4, dtype=f32, device=self.device)
-        # the module's parameters become views of the flat buffer (nn.Sequential order): the module IS the learner's weights
-        off = 0
-        with torch.no_grad():
-            for lin in linears:
-                for p in (lin.weight, lin.bias):
-                    n = p.numel()
-                    self.params[off:off + n].copy_(p.detach().reshape(-1))
-                    p.data = self.params[off:off + n].view_as(p)
-                    off += n
+        _rebind(self.params, linears)
         self._mirror = None
 
     @classmethod
@@ -217,20 +272,217 @@ class QLearner:
                              f'{self.text()} on {self.device}')
         if not 0.0 <= tau <= 1.0:
             raise ValueError(f'QLearner.update_target: tau must be in [0, 1], got {tau}')
-        with torch.no_grad():
-            if tau == 1.0:
-                net.params.copy_(self.params)
-            else:
-                net.params.lerp_(self.params, float(tau))
-            if self._mirror is None or self._mirror[0] is not net:
-                linears, _ = _read_layers(net.module, **_WideShape._grid)
-                mirror, off = torch.empty_like(net.params), 0
-                for lin in linears:
-                    for p in (lin.weight, lin.bias):
-                        p.data = mirror[off:off + p.numel()].view_as(p)
-                        off += p.numel()
-                self._mirror = (net, mirror)
-            self._mirror[1].copy_(net.params)
+        self._mirror = _into_target(self.params, net, tau, self._mirror)
 
 
-__all__ = ['QLearner', 'learn_workspace_bytes', 'learn_param_count']
+class _StepNet:
+    """one network that ActorCriticLearner steps: its module (rebound to the flat buffer), shape, Adam state, device words and
+    workspace"""
+
+    def __init__(self, who, what, module, device, tanh_head, lr, b1, b2, eps, max_grad_norm):
+        linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, what, module, tanh_head)
+        self.what, self.module, self._linears = what, module, linears
+        dev = torch.device(device if device is not None else linears[0].weight.device)
+        f32 = torch.float32
+        P = learn_param_count(self.n_in, self.hidden, self.n_out)
+        self.params = torch.zeros(P, dtype=f32, device=dev)
+        self.device = self.params.device
+        self.m, self.v, self.grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
+        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0], dtype=f32).to(self.device)
+        self.stats = torch.zeros(3, dtype=f32, device=self.device)
+        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.workspace, self.mirror = None, None
+
+    def bind(self, workspace_bytes):
+        """called once every network of the learner has passed its checks: the workspace, and the module's parameters as views"""
+        self.workspace = torch.zeros(workspace_bytes // 4, dtype=torch.float32, device=self.device)
+        _rebind(self.params, self._linears)
+
+    text = _net_text
+
+    def c_structs(self, loss_kind=0):
+        net, st = _fill_shape(_capi.S2DLearnNet(), self), _capi.S2DLearnState()
+        net.params, net.workspace, net.workspace_bytes = self.params.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4
+        st.m, st.v, st.grad = self.m.data_ptr(), self.v.data_ptr(), self.grad.data_ptr()
+        st.hyper, st.stats, st.error, st.loss_kind = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr(), loss_kind
+        return net, st
+
+    def reset(self):
+        self.m.zero_()
+        self.v.zero_()
+        self.hyper[5:7].fill_(1.0)
+
+
+class ActorCriticLearner:
+    """The DDPG / TD3 update in HIP (s2d_learn_critic / s2d_learn_actor in include/s2d.h), the steps that follow
+    ActorCriticTarget.target:
+
+        critic:  e = q(cat(obs, action)) - target;  loss = mean(weight * e^2);  backward;  Adam.step()      (each critic)
+        actor:   loss = -q(cat(obs, tanh-mu(obs))).mean();  backward through the critic;  Adam.step() on mu
+
+    ``mu`` is Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs, ``q`` (and TD3's ``q2``) Linear-(F-Linear) x L from obs_dim + A
+    inputs to one output -- the forms td.ActorCriticTarget takes -- on the learner's grid (1 .. 4 hidden layers of multiples of 8
+    in [8, 256], ReLU / Tanh / Sigmoid, obs_dim <= 248); actor and critics may differ in hidden shape and activation.  SB3's default
+    [400, 300] is off this grid and stays with torch's optimisers.  Every network gets one flat fp32 buffer and its module's
+    parameters are rebound as views of it, as QLearner does.  The actor's step goes through critic 1 (SB3's ``q1_forward``) and
+    never forms or touches a critic's gradient.  Both steps are linear chains on torch's current stream, capturable; learning
+    rates are device words (``set_lr``)."""
+
+    def __init__(self, mu, q, q2=None, actor_lr=1e-3, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, loss='square',
+                 max_batch=4096, device=None):
+        who = 'ActorCriticLearner'
+        if loss not in AC_LOSSES:
+            raise ValueError(f"{who}: loss must be 'square' (F.mse_loss), 'mse' (e^2 / 2) or 'huber', got {loss!r}")
+        b1, b2 = _check_optimiser(who, max_batch, min(actor_lr, critic_lr), betas, eps)
+        self.actor = _StepNet(who, 'actor', mu, device, True, actor_lr, b1, b2, eps, max_grad_norm)
+        dev = device if device is not None else self.actor.device
+        names = ('critic',) if q2 is None else ('critic 1', 'critic 2')
+        self.critics = tuple(_StepNet(who, n, mod, dev, False, critic_lr, b1, b2, eps, max_grad_norm) for n, mod in zip(names, (q, q2)))
+        a = self.actor
+        if not 1 <= a.n_out <= MAX_ACTION:
+            raise ValueError(f'{who}: the actor has {a.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+        if a.n_in > MAX_OBS:
+            raise ValueError(f'{who}: the actor\'s input width must be in [1, {MAX_OBS}], got {a.n_in}')
+        for c in self.critics:
+            if c.n_in != a.n_in + a.n_out or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {a.text()} it must take obs_dim + A = '
+                                 f'{a.n_in} + {a.n_out} inputs and give one output')
+            if c.device != a.device:
+                raise ValueError(f'{who}: the {c.what} is on {c.device}, the actor on {a.device}')
+        self.device, self.obs_dim, self.action_dim = a.device, a.n_in, a.n_out
+        self.loss_kind, self.max_batch = AC_LOSSES.index(loss), max_batch
+        a.bind(learn_actor_workspace_bytes(a.n_in, a.hidden, a.n_out, self.critics[0].hidden, max_batch))
+        for c in self.critics:
+            c.bind(learn_workspace_bytes(c.n_in, c.hidden, 1, max_batch))
+
+    @classmethod
+    def from_modules(cls, mu, q, q2=None, actor_lr=1e-3, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, loss='square',
+                     max_batch=4096, device=None):
+        """A learner of the modules with torch.optim.Adam's arguments (one optimiser per network, as SB3), clip_grad_norm_'s
+        max_grad_norm per network (<= 0, the default: no clip, as SB3), the critic's loss ('square': F.mse_loss; 'mse': e^2 / 2;
+        'huber') and the largest batch a step will see.  device: where the buffers, and from then on the modules' parameters, live
+        (default: the actor's)."""
+        return cls(mu, q, q2=q2, actor_lr=actor_lr, critic_lr=critic_lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, loss=loss,
+                   max_batch=max_batch, device=device)
+
+    # ------------------------------------------------------------------ the steps
+    def _obs(self, who, batch, keys):
+        if not isinstance(batch, dict) or any(k not in batch for k in keys):
+            raise ValueError(f'{who}: batch must be a dict with ' + ' and '.join(repr(k) for k in keys) + " (DeviceReplay.sample's)")
+        obs = batch['obs']
+        if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
+            raise ValueError(f"{who}: batch['obs'] must be a [B, {self.obs_dim}] tensor, B >= 1")
+        B = obs.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={self.max_batch}')
+        return B, _arr(who, self.device, "batch['obs']", obs, torch.float32, (B, self.obs_dim))
+
+    def _need_gpu(self, who):
+        if self.device.type != 'cuda':
+            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
+
+    def _critic_call(self, fn, name, batch, target, weight, td_abs_out, q_out):
+        who, f32 = f'ActorCriticLearner.{name}', torch.float32
+        B, obs = self._obs(who, batch, ('obs', 'action'))
+
+        def opt(what, t):
+            return _arr(who, self.device, what, t, f32, (B,)) if t is not None else None
+        ptrs = [_arr(who, self.device, "batch['action']", batch['action'], f32, (B, self.action_dim)),
+                _arr(who, self.device, 'target', target, f32, (B,)), opt('weight', weight)]
+        outs = [opt('td_abs_out', td_abs_out), opt('q_out', q_out)]
+        self._need_gpu(who)
+        lib = _capi.load_library()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for n, c in enumerate(self.critics):
+                net, st = c.c_structs(self.loss_kind)
+                rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), obs, self.action_dim, *ptrs, *(outs if n == 0 else (None, None)), stream)
+                _capi.check(lib, rc, fn)
+
+    def _actor_call(self, fn, name, batch, action_out, q_out):
+        who, f32 = f'ActorCriticLearner.{name}', torch.float32
+        B, obs = self._obs(who, batch, ('obs',))
+        outs = [_arr(who, self.device, 'action_out', action_out, f32, (B, self.action_dim)) if action_out is not None else None,
+                _arr(who, self.device, 'q_out', q_out, f32, (B,)) if q_out is not None else None]
+        self._need_gpu(who)
+        lib = _capi.load_library()
+        net, st = self.actor.c_structs()
+        critic, _ = self.critics[0].c_structs()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), C.byref(critic), obs, *outs,
+                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, fn)
+
+    def step_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """One update of the critic (of both, where ``q2`` was given) on the dict DeviceReplay.sample returns (its 'obs' [B, obs_dim]
+        and 'action' float32 [B, A]) towards `target` float32 [B] (ActorCriticTarget.target's), with the importance weights
+        `weight` [B] where given.  td_abs_out [B] <- |q1 - target| (the new priorities' base), q_out [B] <- critic 1's forward
+        values.  Stream-ordered on torch's current stream, capturable; returns nothing."""
+        self._critic_call('s2d_learn_critic', 'step_critic', batch, target, weight, td_abs_out, q_out)
+
+    def step_actor(self, batch, action_out=None, q_out=None):
+        """One update of the actor on -mean critic_1(obs, tanh-mu(obs)) over batch['obs'].  action_out [B, A] <- the actions the
+        critic was evaluated at, q_out [B] <- its values (both before the update)."""
+        self._actor_call('s2d_learn_actor', 'step_actor', batch, action_out, q_out)
+
+    def step(self, batch, target, weight=None, td_abs_out=None, q_out=None, actor=True):
+        """The critics' step, then (actor=True) the actor's through the UPDATED critic 1, as DDPG orders them.  TD3's
+        ``policy_delay`` is the caller's: pass ``actor=(n_updates % policy_delay == 0)``; q_out is the critic step's."""
+        self.step_critic(batch, target, weight=weight, td_abs_out=td_abs_out, q_out=q_out)
+        if actor:
+            self.step_actor(batch)
+
+    def grad_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """The flat, unclipped gradient [P] of critic 1's loss (with ``q2`` the tuple of both critics'; views, written again by the
+        next call), with the critic's statistics set, without touching parameters or optimiser state."""
+        self._critic_call('s2d_learn_critic_grad', 'grad_critic', batch, target, weight, td_abs_out, q_out)
+        return self.critics[0].grad if len(self.critics) == 1 else tuple(c.grad for c in self.critics)
+
+    def grad_actor(self, batch, action_out=None, q_out=None):
+        """The flat, unclipped gradient [P] of the actor's loss, with the actor's statistics set, without touching anything else."""
+        self._actor_call('s2d_learn_actor_grad', 'grad_actor', batch, action_out, q_out)
+        return self.actor.grad
+
+    # ------------------------------------------------------------------ state
+    critic_loss = property(lambda self: self.critics[0].stats.tolist()[0], doc="critic 1's last mean loss (synchronises)")
+    critic_grad_norm = property(lambda self: self.critics[0].stats.tolist()[1], doc="critic 1's last gradient norm before the clip")
+    critic_clip_scale = property(lambda self: self.critics[0].stats.tolist()[2], doc="the factor critic 1's last gradient was scaled by")
+    actor_loss = property(lambda self: self.actor.stats.tolist()[0], doc="the actor's last loss: -mean q (synchronises)")
+    actor_grad_norm = property(lambda self: self.actor.stats.tolist()[1], doc="the actor's last gradient norm before the clip")
+    actor_clip_scale = property(lambda self: self.actor.stats.tolist()[2], doc="the factor the actor's last gradient was scaled by")
+
+    def set_lr(self, actor=None, critic=None):
+        """the learning rates of the steps enqueued from now on: device writes, also between the replays of a captured graph"""
+        if actor is not None:
+            self.actor.hyper[0:1].fill_(float(actor))
+        if critic is not None:
+            for c in self.critics:
+                c.hyper[0:1].fill_(float(critic))
+
+    def reset_optimizer(self):
+        """Adam as new for every network: m = v = 0, both beta products 1"""
+        for n in (self.actor,) + self.critics:
+            n.reset()
+
+    def update_targets(self, ac_target, tau=1.0):
+        """The learner's weights into a td.ActorCriticTarget's target networks: a hard copy (tau = 1) or a Polyak step, one
+        ``copy_`` or ``lerp_`` per network from flat buffer to flat buffer, and one more flat copy each keeps the target MODULES
+        equal (their parameters become views of mirror buffers), as QLearner.update_target."""
+        from .td import ActorCriticTarget
+        who = 'ActorCriticLearner.update_targets'
+        if not isinstance(ac_target, ActorCriticTarget):
+            raise ValueError(f'{who}: ac_target must be a td.ActorCriticTarget')
+        if len(ac_target.critics) != len(self.critics):
+            raise ValueError(f'{who}: the target has {len(ac_target.critics)} critic(s), the learner {len(self.critics)}')
+        pairs = list(zip((self.actor,) + self.critics, (ac_target.mu_target,) + ac_target.critics))
+        for mine, net in pairs:
+            if (net.n_in, net.hidden, net.n_out) != (mine.n_in, mine.hidden, mine.n_out) or net.device != mine.device:
+                raise ValueError(f'{who}: the {net.what} is {net.text()} on {net.device}, the learner\'s {mine.what} '
+                                 f'{mine.text()} on {mine.device}')
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
+        for mine, net in pairs:
+            mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
+
+
+__all__ = ['QLearner', 'ActorCriticLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes', 'learn_param_count']

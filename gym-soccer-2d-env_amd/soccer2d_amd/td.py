@@ -13,7 +13,7 @@ the weights, bit for bit, that the fused actor acts on.  Engine-independent: any
 Each network keeps ONE flat fp32 parameter buffer and a workspace.  The kernels read the buffers when they run: ``sync()``
 reloads them from the modules (after ``load_state_dict`` or a Polyak step for the target networks, after every optimiser step
 for ``online``), and a captured graph computes with whatever they hold at replay.  The online Q-network's forward / backward pass and the
-optimiser are soccer2d_amd.learn.QLearner's.  Out of scope: the target is not fused into the sample launch, and TD3's
+optimiser are soccer2d_amd.learn.QLearner's, the DDPG / TD3 update soccer2d_amd.learn.ActorCriticLearner's.  Out of scope: the target is not fused into the sample launch, and TD3's
 target-policy smoothing noise is not added."""
 import ctypes as C
 

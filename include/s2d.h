@@ -597,7 +597,7 @@ int s2d_td_target_ac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *criti
  * p -= (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)).  A fresh state has m = v = 0 and both products 1. */
 #define S2D_LEARN_BLOCK_ROWS 64
 #define S2D_LEARN_NORM_CHUNK 256
-enum { S2D_LEARN_MSE = 0, S2D_LEARN_HUBER = 1 };
+enum { S2D_LEARN_MSE = 0, S2D_LEARN_HUBER = 1, S2D_LEARN_SQUARE = 2 /* s2d_learn_critic only */ };
 typedef struct S2DLearnNet {
   int32_t n_in;            /* 1 .. 256 */
   int32_t n_hidden;        /* 1 .. 4 */
@@ -613,7 +613,7 @@ typedef struct S2DLearnState {
   float *hyper;            /* [7]: lr, beta1, beta2, eps, max_grad_norm, beta1^t, beta2^t */
   float *stats;            /* [3]: mean loss, gradient norm, clip scale */
   int32_t *error;          /* |= 1: an action outside [0, n_out) */
-  int32_t loss_kind;       /* S2D_LEARN_MSE | S2D_LEARN_HUBER */
+  int32_t loss_kind;       /* S2D_LEARN_MSE | S2D_LEARN_HUBER (| S2D_LEARN_SQUARE for s2d_learn_critic; s2d_learn_actor ignores it) */
 } S2DLearnState;
 /* bytes of workspace of a shape for batches up to max_batch (the pointers are not read): the blocks' partial gradients, the
  * chunk and loss partials and, where 64 rows of activations do not fit the LDS, the blocks' activations.  0 for a shape off the
@@ -630,6 +630,61 @@ int s2d_learn_q(int64_t batch, const S2DLearnNet *net, const S2DLearnState *stat
  * and for callers with their own optimiser. */
 int s2d_learn_q_grad(int64_t batch, const S2DLearnNet *net, const S2DLearnState *state, const float *obs, const int32_t *action,
                      const float *target, const float *weight, float *out_td_abs, float *out_q, void *stream);
+/* ---- the DDPG / TD3 update (s2d_learn.hip): the critic's step and the actor's step through the critic ----
+ * Engine-independent like s2d_learn_q: no handle, raw device pointers, any stream of the current device, everything read WHEN THE
+ * KERNELS RUN, each call a linear chain of three launches on one stream (capturable), no float atomics, no result depends on the
+ * grid.  All networks are on the learner's grid above; further D = obs width in 1 .. 248, A = action width in 1 .. 8 (D + A <= 256),
+ * a critic has n_in == D + A and n_out == 1; actor and critic may differ in hidden shape and activation.
+ *
+ * s2d_learn_critic: one step of a critic.  The input row [obs[b] (D = net->n_in - action_dim words) | action[b] (action_dim float
+ * words)], zero-padded to 4 ceil((D + A) / 4), is assembled in the kernel and never passes through memory.  Everything after that is
+ * s2d_learn_q's spec with output column 0: e = q[b] - target[b]; out_td_abs[b] = |e|; the delta (weight[b] * d) / (float)B;
+ * backward, block partials, norm, clip, Adam; out_q is [B].  One more loss kind: S2D_LEARN_SQUARE, loss e * e and d = 2.0f * e
+ * (F.mse_loss); s2d_learn_q keeps rejecting it.  The error word is required as for s2d_learn_q and never set.  Workspace:
+ * s2d_learn_workspace_bytes of the critic's shape.  TD3's second critic is a second call with a state of its own (Adam is
+ * element-wise, so two states equal one optimiser over both critics as long as nothing clips across them).  S2D_EINVAL without a
+ * launch and with nothing written: all that s2d_learn_q rejects, plus action_dim outside [1, 8], n_out != 1, n_in - action_dim
+ * outside [1, 248], loss_kind outside 0 .. 2. */
+int s2d_learn_critic(int64_t batch, const S2DLearnNet *net, const S2DLearnState *state, const float *obs /* [B][D] */,
+                     int32_t action_dim, const float *action /* [B][action_dim] */, const float *target /* [B] */,
+                     const float *weight /* [B] or NULL */, float *out_td_abs /* [B] or NULL */, float *out_q /* [B] or NULL */,
+                     void *stream);
+/* the same WITHOUT touching params, m, v or the beta products */
+int s2d_learn_critic_grad(int64_t batch, const S2DLearnNet *net, const S2DLearnState *state, const float *obs, int32_t action_dim,
+                          const float *action, const float *target, const float *weight, float *out_td_abs, float *out_q,
+                          void *stream);
+/* s2d_learn_actor: one step of the actor on loss = -mean_b Q(obs[b], tanh(mu(obs[b]))).  actor holds the linear layers of mu
+ * (n_in = D, n_out = A in 1 .. 8); the tanh head is part of the call, as in s2d_td_target_ac.  Of critic only shape and params are
+ * read (params READ-ONLY; workspace fields ignored).  actor_state->loss_kind is ignored and its error word is neither required nor
+ * written (there is no index to be wrong).  Per row b:
+ *   forward, actor   a[i] = tanh_spec(actor(obs[b])[i])
+ *   forward, critic  q = critic([obs[b] | a])[0]; both by the chain acc = b[j]; k ascending: acc = fmaf(W[j][k], in[k], acc) (layer 1
+ *                    over its padded terms), so out_action [B][A] and out_q [B] have the bits s2d_td_target_ac writes for the same
+ *                    parameters with next_obs = obs
+ *   critic's output delta   -1.0f / (float)B
+ *   critic backward  the delta spec above (s = +0; j ascending: s = fmaf(W[j][k], delta[j], s), then the activation's derivative from
+ *                    the stored output) down to the input layer, where only the A action columns k = D .. D + A - 1 are formed:
+ *                    s[i] = +0; j ascending over h_1: s[i] = fmaf(W_1[j][D + i], delta_1[j], s[i]).  No critic dW or db is computed or
+ *                    written.
+ *   tanh head        dz[i] = s[i] * (1.0f - a[i] * a[i]), separate operations
+ *   actor backward   s2d_learn_q's spec with output delta dz: block partials of S2D_LEARN_BLOCK_ROWS rows, rows ascending, blocks added
+ *                    ascending; the same norm, clip and Adam on the actor's state
+ * stats <- {-(sum of q: rows ascending per block, blocks ascending) / (float)B, norm, scale}; grad <- the UNCLIPPED sum.  The block's
+ * image holds both networks' rows (in LDS where 64 rows fit 160 KiB, else in the actor's workspace).  S2D_EINVAL without a launch and
+ * with nothing written, the text naming the field: a shape off the grid, A outside [1, 8], D above 248, a critic whose n_in != D + A
+ * or n_out != 1, batch outside [1, 2^31 - 1] or above what the workspace holds, NULL or misaligned actor params / workspace / m / v /
+ * grad / hyper / stats / obs or critic params, misaligned optional outputs, the actor's params, m, v, grad or workspace overlapping
+ * one another or the critic's params. */
+int s2d_learn_actor(int64_t batch, const S2DLearnNet *actor, const S2DLearnState *actor_state,
+                    const S2DLearnNet *critic /* params only read */, const float *obs /* [B][D] */,
+                    float *out_action /* [B][A] or NULL */, float *out_q /* [B] or NULL */, void *stream);
+/* the same WITHOUT touching the actor's params, m, v or beta products */
+int s2d_learn_actor_grad(int64_t batch, const S2DLearnNet *actor, const S2DLearnState *actor_state, const S2DLearnNet *critic,
+                         const float *obs, float *out_action, float *out_q, void *stream);
+/* bytes of the ACTOR's workspace for s2d_learn_actor with this pair of shapes (the pointers are not read) and batches up to
+ * max_batch: s2d_learn_workspace_bytes' parts for the actor's parameters and, where 64 rows of both networks do not fit the LDS,
+ * the blocks' images.  0 for a pair off the grid or max_batch outside [1, 2^31 - 1].  Host only, needs no GPU. */
+size_t s2d_learn_actor_workspace_bytes(const S2DLearnNet *actor_shape, const S2DLearnNet *critic_shape, int64_t max_batch);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
