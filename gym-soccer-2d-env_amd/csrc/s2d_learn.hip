@@ -27,6 +27,13 @@
 //   s2d_learn_reduce_kernel  grad[p] = block partials in ascending order; per chunk of S2D_LEARN_NORM_CHUNK words the sum of
 //                            squares, fmaf ascending; (step) the beta products are multiplied here, once per call.
 //   s2d_learn_finish_kernel  chunks added ascending, norm, clip scale, mean loss; (step) Adam on every word.
+// The PPO step (s2d_learn_ppo: a policy net and a value net on one observation, a categorical or Gaussian head, one flat
+// [pi | vf | log_std] buffer under one clip and one Adam; tests/learn_ppo_ref.c) adds
+//   s2d_learn_ppo_norm_kernel   the advantage's mean and standard deviation over the rows the minibatch names, a launch of its own
+//   s2d_learn_ppo_block_kernel  one workgroup per GROUP of ceil(blocks / 256) consecutive blocks: rows gathered by index, both
+//                               forwards, the head and the clipped surrogate (lane = row), both backward passes with the dW / db
+//                               chains continued across the group's blocks, so the partials are at most 256 x P words
+// and runs the reduce and finish kernels with their PPO flag (log_std's entropy term, eight statistics).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,6 +47,10 @@ static constexpr int kLearnThreads = 256;
 static constexpr int kLearnMaxHidden = 4;
 static constexpr int kLearnMaxAction = 8;   // the actor's outputs, as s2d_td_target_ac
 static constexpr int kLearnMaxObs = 248;    // so that [obs | action] stays within the grid's 256 inputs
+static constexpr int kPpoMaxGroups = S2D_LEARN_PPO_MAX_GROUPS;
+static constexpr int kPpoStatWords = 8;     // a group's partials of the five statistics, padded
+static constexpr int kPpoRowWords = 6;      // beside the image, per row of the block: its source row and its five statistics
+static constexpr int kPpoNormThreads = 1024;
 static_assert(kLearnRows == kWave, "lane = row of the block");
 static_assert(kLearnChunk == kLearnThreads, "one thread per word of a chunk");
 
@@ -268,9 +279,11 @@ S2D_DEV int learn_forward(const LearnDev& d, const float* __restrict__ params, f
 // dW and db into mine[P], 4 units x one input per thread, rows ascending.  Every hidden layer's delta overwrites its stored
 // output; !GRADS (a network whose parameters are only read) stops with layer 1's delta at column y_off.  Called behind a barrier,
 // ends behind one.
-template <bool GRADS>
+// CONT (s2d_learn_ppo: a workgroup takes several blocks): every dW / db chain starts at +0 only where `first`, else it goes on from the
+// partial stored in mine[].
+template <bool GRADS, bool CONT = false>
 S2D_DEV void learn_backward(const LearnDev& d, const float* __restrict__ params, float* __restrict__ mine, float* img, int pitch, int rows,
-                            int x_off, int q_off, int tid, int lane, int wv) {
+                            int x_off, int q_off, int tid, int lane, int wv, bool first = true) {
   int out_off = q_off, po = d.P;
   for (int l = d.n_hidden; l >= 0; --l) {
     const int wout = learn_width(d, l), win = l ? learn_width(d, l - 1) : d.n_in;
@@ -284,8 +297,9 @@ S2D_DEV void learn_backward(const LearnDev& d, const float* __restrict__ params,
         float acc[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          jc[u] = out_off + (j0 + u < wout ? j0 + u : wout - 1);
-          acc[u] = 0.0f;
+          const int j = j0 + u < wout ? j0 + u : wout - 1;
+          jc[u] = out_off + j;
+          acc[u] = CONT && !first ? mine[po + j * win + k] : 0.0f;
         }
         for (int r = 0; r < rows; ++r) {
           const float* const row = img + r * pitch;
@@ -298,7 +312,7 @@ S2D_DEV void learn_backward(const LearnDev& d, const float* __restrict__ params,
           if (j0 + u < wout) mine[po + (j0 + u) * win + k] = acc[u];
       }
       for (int j = tid; j < wout; j += kLearnThreads) {
-        float acc = 0.0f;
+        float acc = CONT && !first ? mine[po + wout * win + j] : 0.0f;
         for (int r = 0; r < rows; ++r) acc = fmaf(img[r * pitch + out_off + j], 1.0f, acc);
         mine[po + wout * win + j] = acc;
       }
@@ -447,17 +461,225 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_actor_kernel(LearnDev
   learn_backward<true>(a, aparams, part + (size_t)blockIdx.x * a.P, img, pitch, rows, 0, a_off, tid, lane, wv);
 }
 
+// ------------------------------------------------------------------------------------------ PPO (s2d_learn_ppo)
+// what the PPO kernels read of a call besides the two networks
+struct PpoArgs {
+  int head, A, normalize, pitch, P;          // 0 categorical / 1 Gaussian; outputs of pi; the pre-pass ran; the image's row; all parameters
+  int64_t batch, src_rows, blocks, per_group;   // B, R, blocks of 64 rows, blocks a group
+  const float* params;                       // [pi | vf | log_std]
+  float* part;                               // [groups][P]
+  float* stat_part;                          // [groups][kPpoStatWords]
+  float* image;                              // [groups][64][pitch], if not in LDS
+  const float* nrm;                          // mean, std of the pre-pass
+  const float* hyper;
+  const float* obs;
+  const void* action;
+  const float* logp_old;
+  const float* adv;
+  const float* ret;
+  const int32_t* index;
+  float* out_logp;
+  float* out_value;
+  int32_t* error;
+};
+
+// row b of the minibatch is row index[b] of the rollout arrays (b itself without an index); -1 if that is outside [0, R)
+S2D_DEV int64_t ppo_source(const int32_t* __restrict__ index, int64_t b, int64_t src_rows) {
+  const int64_t i = index ? (int64_t)index[b] : b;
+  return i >= 0 && i < src_rows ? i : -1;
+}
+
+// The advantage's mean and unbiased standard deviation over the rows the minibatch names: per block of 64 rows s = +0, rows
+// ascending s = s + adv; the blocks' sums added ascending; mean = S / B; then the same with s = fmaf(d, d, s), d = adv - mean;
+// std = sqrt(S2 / (B - 1)).  One workgroup, a thread per block; bsum[blocks] is its scratch.
+__global__ __launch_bounds__(kPpoNormThreads) void s2d_learn_ppo_norm_kernel(int64_t batch, int64_t src_rows, int64_t blocks,
+                                                                            const float* __restrict__ adv, const int32_t* __restrict__ index,
+                                                                            float* __restrict__ bsum, float* __restrict__ nrm) {
+  __shared__ float sh_mean;
+  float mean = 0.0f;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int64_t blk = threadIdx.x; blk < blocks; blk += kPpoNormThreads) {
+      const int64_t row0 = blk * kLearnRows;
+      const int rows = (int)(batch - row0 < kLearnRows ? batch - row0 : kLearnRows);
+      float s = 0.0f;
+      for (int r = 0; r < rows; ++r) {
+        const int64_t i = ppo_source(index, row0 + r, src_rows);
+        if (i < 0) continue;
+        const float d = adv[i] - mean;
+        s = pass ? fmaf(d, d, s) : s + adv[i];
+      }
+      bsum[blk] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = bsum[0];
+      for (int64_t blk = 1; blk < blocks; ++blk) t = t + bsum[blk];
+      if (pass == 0) {
+        sh_mean = t / (float)batch;
+      } else {
+        nrm[0] = mean;
+        nrm[1] = sqrtf(t / (float)(batch - 1));
+      }
+    }
+    __syncthreads();
+    mean = sh_mean;
+  }
+}
+
+// One workgroup per GROUP of consecutive blocks.  A row of a block's image holds both networks on one input:
+// [x: 4 ceil(D / 4) | pi's y_1 .. y_L | logits or means: A | vf's y_1 .. y_L | v: 1 | (Gaussian) the rows' d log_std terms: A].
+// Per block: the rows gathered by index, both forwards, the head (lane = row: logp, entropy, ratio, clipped surrogate, value error,
+// the output deltas of both networks), the rows' five statistics, both backward passes continuing the group's dW / db chains.
+template <bool LDS>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_ppo_block_kernel(LearnDev pi, LearnDev vf, PpoArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [the rows' sources: 64 | their statistics: 5 x 64 | the image, if it lives here]
+  int* const src = reinterpret_cast<int*>(smem);
+  float* const rstat = smem + kLearnRows;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int pitch = a.pitch, A = a.A, D = pi.n_in;
+  float* const img = LDS ? smem + kPpoRowWords * kLearnRows : a.image + (size_t)blockIdx.x * kLearnRows * pitch;
+  float* const mine = a.part + (size_t)blockIdx.x * a.P;
+  const float* const vparams = a.params + pi.P;
+  const float* const log_std = vparams + vf.P;
+  const float clip = a.hyper[7], vf_coef = a.hyper[8], ent_coef = a.hyper[9], fB = (float)a.batch;
+  const int64_t blk0 = (int64_t)blockIdx.x * a.per_group;
+  const int64_t blk1 = blk0 + a.per_group < a.blocks ? blk0 + a.per_group : a.blocks;
+  float chain = 0.0f;                                  // threads 0 .. 4: the group's sum of statistic tid, rows ascending
+
+  for (int64_t blk = blk0; blk < blk1; ++blk) {
+    const bool first = blk == blk0;
+    const int64_t row0 = blk * kLearnRows;
+    const int rows = (int)(a.batch - row0 < kLearnRows ? a.batch - row0 : kLearnRows);
+    if (tid < kLearnRows) {
+      int64_t s = -1;
+      if (tid < rows) {
+        s = ppo_source(a.index, row0 + tid, a.src_rows);
+        if (s < 0) atomicOr(a.error, 2);
+      }
+      src[tid] = (int)s;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < kLearnRows * pi.kp; idx += kLearnThreads) {
+      const int r = idx / pi.kp, k = idx - r * pi.kp, s = src[r];
+      img[r * pitch + k] = (s >= 0 && k < D) ? a.obs[(int64_t)s * D + k] : 0.0f;
+    }
+    __syncthreads();
+    const int a_off = learn_forward(pi, a.params, img, pitch, 0, pi.kp, lane, wv);
+    const int v_off = learn_forward(vf, vparams, img, pitch, 0, a_off + A, lane, wv);
+    const int ls_off = v_off + 1;
+
+    // ---- the head: lane = row
+    if (tid < kLearnRows) {
+      float* const row = img + tid * pitch;
+      float* const y = row + a_off;
+      const int s = src[tid];
+      float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f, st4 = 0.0f, o_logp = 0.0f, o_value = 0.0f;
+      bool live = s >= 0;
+      int ai = 0;
+      float logp = 0.0f, H = 0.0f, m = 0.0f, S = 1.0f, logS = 0.0f;
+      if (live && a.head == 0) {
+        ai = static_cast<const int32_t*>(a.action)[s];
+        if (ai < 0 || ai >= A) {
+          atomicOr(a.error, 1);
+          live = false;
+        }
+      }
+      if (live && a.head == 0) {
+        m = y[0];
+        for (int j = 1; j < A; ++j) m = y[j] > m ? y[j] : m;
+        S = exp_spec(y[0] - m);
+        for (int j = 1; j < A; ++j) S += exp_spec(y[j] - m);
+        logS = log_spec(S);
+        logp = (y[ai] - m) - logS;
+        float h = 0.0f;
+        for (int j = 0; j < A; ++j) {
+          const float p = exp_spec(y[j] - m) / S, lp = (y[j] - m) - logS;
+          h = fmaf(p, lp, h);
+        }
+        H = -h;
+      } else if (live) {
+        const float* const act = static_cast<const float*>(a.action) + (int64_t)s * A;
+        float hs = 0.0f;
+        for (int j = 0; j < A; ++j) {
+          const float ls = log_std[j], z = (act[j] - y[j]) / exp_spec(ls);
+          const float term = fmaf(-0.5f * z, z, -ls) - 0.91893853f;
+          logp = j ? logp + term : term;
+          hs = j ? hs + ls : ls;
+        }
+        H = hs + (float)A * 1.4189385f;
+      }
+      if (live) {
+        float adv = a.adv[s];
+        if (a.normalize) adv = (adv - a.nrm[0]) / (a.nrm[1] + 1e-8f);
+        const float d = logp - a.logp_old[s], r = exp_spec(d);
+        const float lo = 1.0f - clip, hi = 1.0f + clip;
+        const float rc = r < lo ? lo : (r > hi ? hi : r);
+        const float s1 = r * adv, s2 = rc * adv;
+        const float mn = (s1 < s2 || s1 != s1) ? s1 : s2;                 // torch.min: a NaN wins
+        const bool clipped = (r > hi && adv > 0.0f) || (r < lo && adv < 0.0f);
+        const float g = clipped ? 0.0f : -s1;                             // d(-min(s1, s2)) / d logp
+        const float v = row[v_off], e = v - a.ret[s];
+        st0 = -mn; st1 = e * e; st2 = H; st3 = (r - 1.0f) - d; st4 = fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+        o_logp = logp; o_value = v;
+        row[v_off] = (vf_coef * (2.0f * e)) / fB;
+        if (a.head == 0) {
+          for (int j = 0; j < A; ++j) {
+            const float p = exp_spec(y[j] - m) / S, lp = (y[j] - m) - logS;
+            const float t1 = g * ((j == ai ? 1.0f : 0.0f) - p), t2 = (ent_coef * p) * (lp + H);
+            y[j] = (t1 + t2) / fB;
+          }
+        } else {
+          const float* const act = static_cast<const float*>(a.action) + (int64_t)s * A;
+          for (int j = 0; j < A; ++j) {
+            const float sg = exp_spec(log_std[j]), z = (act[j] - y[j]) / sg;
+            y[j] = ((g * z) / sg) / fB;
+            row[ls_off + j] = (g * (z * z - 1.0f)) / fB;
+          }
+        }
+      } else {                                                            // past the batch, a bad index or a bad action: nothing
+        for (int j = 0; j < A; ++j) y[j] = 0.0f;
+        row[v_off] = 0.0f;
+        if (a.head) for (int j = 0; j < A; ++j) row[ls_off + j] = 0.0f;
+      }
+      if (tid < rows) {
+        if (a.out_logp) a.out_logp[row0 + tid] = o_logp;
+        if (a.out_value) a.out_value[row0 + tid] = o_value;
+      }
+      rstat[0 * kLearnRows + tid] = st0; rstat[1 * kLearnRows + tid] = st1; rstat[2 * kLearnRows + tid] = st2;
+      rstat[3 * kLearnRows + tid] = st3; rstat[4 * kLearnRows + tid] = st4;
+    }
+    __syncthreads();
+    if (tid < 5)
+      for (int r = 0; r < rows; ++r) chain = chain + rstat[tid * kLearnRows + r];
+
+    // ---- backward: both networks, then log_std's terms like a bias
+    learn_backward<true, true>(pi, a.params, mine, img, pitch, rows, 0, a_off, tid, lane, wv, first);
+    learn_backward<true, true>(vf, vparams, mine + pi.P, img, pitch, rows, 0, v_off, tid, lane, wv, first);
+    if (a.head && tid < A) {
+      float* const out = mine + pi.P + vf.P + tid;
+      float acc = first ? 0.0f : *out;
+      for (int r = 0; r < rows; ++r) acc = fmaf(img[r * pitch + ls_off + tid], 1.0f, acc);
+      *out = acc;
+    }
+    __syncthreads();                                   // the next block overwrites the sources, the statistics and the image
+  }
+  if (tid < 5) a.stat_part[(size_t)blockIdx.x * kPpoStatWords + tid] = chain;
+}
+
 // grad[p] = the blocks' partials added in ascending block order; chunk_ss[c] = fmaf(g, g, .) ascending over the chunk's words
-template <bool UPDATE>
+// PPO (s2d_learn_ppo): the partials are the groups'; the words from ent_from on are log_std's, whose sum then loses ent_coef (hyper[9])
+template <bool UPDATE, bool PPO = false>
 __global__ __launch_bounds__(kLearnThreads) void s2d_learn_reduce_kernel(int P, int64_t blocks, const float* __restrict__ part,
                                                                          float* __restrict__ grad, float* __restrict__ chunk_ss,
-                                                                         float* __restrict__ hyper) {
+                                                                         float* __restrict__ hyper, int ent_from) {
   __shared__ float g2[kLearnChunk];
   const int tid = threadIdx.x, p = blockIdx.x * kLearnChunk + tid;
   float s = 0.0f;
   if (p < P) {
     s = part[p];
     for (int64_t b = 1; b < blocks; ++b) s = s + part[(size_t)b * P + p];
+    if (PPO && p >= ent_from) s = s - hyper[9];
     grad[p] = s;
   }
   g2[tid] = s;
@@ -475,7 +697,8 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_reduce_kernel(int P, 
 }
 
 // norm, clip scale and mean loss (workgroup 0 stores them; negate: minus the mean); UPDATE: Adam on the chunk's words with g' = g * scale
-template <bool UPDATE>
+// PPO (s2d_learn_ppo): loss_part holds the groups' partials of five statistics, kPpoStatWords words a group, and stats has 8 words
+template <bool UPDATE, bool PPO = false>
 __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, int64_t batch, int64_t blocks, int chunks, bool negate,
                                                                          const float* __restrict__ chunk_ss,
                                                                          const float* __restrict__ loss_part, const float* __restrict__ grad,
@@ -494,7 +717,19 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
       scale = c < 1.0f ? c : 1.0f;
     }
     sh_scale = scale;
-    if (blockIdx.x == 0) {
+    if (blockIdx.x == 0 && PPO) {
+      float mean[5];                                   // policy loss, value loss, entropy, approx_kl, clip_fraction
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        float ls = loss_part[k];
+        for (int64_t b = 1; b < blocks; ++b) ls = ls + loss_part[b * kPpoStatWords + k];
+        mean[k] = ls / (float)batch;
+        stats[3 + k] = mean[k];
+      }
+      stats[0] = (mean[0] + hyper[8] * mean[1]) - hyper[9] * mean[2];
+      stats[1] = norm;
+      stats[2] = scale;
+    } else if (blockIdx.x == 0) {
       float ls = loss_part[0];
       for (int64_t b = 1; b < blocks; ++b) ls = ls + loss_part[b];
       stats[0] = (negate ? -ls : ls) / (float)batch;   // the actor's loss is -mean q
@@ -522,7 +757,7 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
-struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor); fail, misaligned and launched are s2d_wide_host.h's
+struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor, 3 PPO); fail, misaligned and launched are s2d_wide_host.h's
 
 // "" if the shape is on the learner's grid, else the text naming the field
 std::string shape_error(const S2DLearnNet* n) {
@@ -628,7 +863,7 @@ void reduce_and_finish(int P, int64_t batch, bool negate, const LearnLayout& y, 
   const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
   const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
   hipLaunchKernelGGL(s2d_learn_reduce_kernel<UPDATE>, dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, blocks, ws + y.part, st->grad,
-                     ws + y.chunk, st->hyper);
+                     ws + y.chunk, st->hyper, P);
   hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, batch, blocks,
                      chunks, negate, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
 }
@@ -711,7 +946,117 @@ int learn_actor(const std::string& who, int64_t batch, const S2DLearnNet* actor,
   reduce_and_finish<UPDATE>(a.P, batch, true, y, actor, st, s);
   return launched(who);
 }
+// ---- PPO
+// "" if the pair of networks and the head are on the grid of s2d_learn_ppo
+std::string ppo_error(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) {
+  std::string bad = shape_error(pi);
+  if (!bad.empty()) return "pi: " + bad;
+  bad = shape_error(vf);
+  if (!bad.empty()) return "vf: " + bad;
+  if (vf->n_out != 1 || vf->n_in != pi->n_in) return "vf: n_in must be pi's n_in, its n_out 1";
+  if (head != S2D_LEARN_PPO_CATEGORICAL && head != S2D_LEARN_PPO_GAUSSIAN) return "head must be 0 (categorical) or 1 (diagonal Gaussian)";
+  if (head == S2D_LEARN_PPO_GAUSSIAN && pi->n_out > kLearnMaxAction) return "pi: n_out (the action width) must be in [1, 8] with the Gaussian head";
+  return "";
+}
+int ppo_pitch(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) {
+  return ((pi->n_in + 3) / 4 * 4 + layer_words(pi) + layer_words(vf) + (head ? pi->n_out : 0)) | 1;
+}
+// the workspace in words: [the groups' partials: g x P | chunk sums | the groups' statistics: g x 8 | mean, std | the pre-pass's block
+// sums | the groups' images, if not in LDS], g = min(blocks, 256) -- at least the groups of every smaller batch
+struct PpoLayout {
+  size_t part, chunk, stat, nrm, bsum, image, words;
+  int64_t blocks, per_group, groups;
+  bool lds;
+};
+PpoLayout ppo_layout(int P, int pitch, int64_t batch) {
+  PpoLayout y{};
+  y.blocks = (batch + kLearnRows - 1) / kLearnRows;
+  y.per_group = (y.blocks + kPpoMaxGroups - 1) / kPpoMaxGroups;
+  y.groups = (y.blocks + y.per_group - 1) / y.per_group;
+  const size_t g = (size_t)(y.blocks < kPpoMaxGroups ? y.blocks : kPpoMaxGroups), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
+  y.lds = (size_t)kLearnRows * (pitch + kPpoRowWords) * sizeof(float) <= kLdsMax;
+  y.part = 0;
+  y.chunk = round64(g * P);
+  y.stat = y.chunk + round64(chunks);
+  y.nrm = y.stat + round64(g * kPpoStatWords);
+  y.bsum = y.nrm + 64;
+  y.image = y.bsum + round64((size_t)y.blocks);
+  y.words = y.image + (y.lds ? 0 : round64(g * kLearnRows * pitch));
+  return y;
+}
+
+template <bool UPDATE>
+int learn_ppo(const std::string& who, const S2DLearnPPO* q, const S2DLearnPPOBatch* b, void* stream) {
+  if (!q || !b) return fail(who, "learner and batch must be non-NULL");
+  std::string err = ppo_error(&q->pi, &q->vf, q->head);
+  if (!err.empty()) return fail(who, err);
+  const int64_t B = b->batch, R = b->rows;
+  if (R < 1 || R > INT32_MAX) return fail(who, "rows must be in [1, 2^31 - 1]");
+  if (B < 1 || B > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  if (!b->index && B > R) return fail(who, "batch must be at most rows where index is NULL");
+  if (!q->params || misaligned(q->params, 16)) return fail(who, "params must be a non-NULL, 16-byte aligned device pointer");
+  if (!q->workspace || misaligned(q->workspace, 256)) return fail(who, "workspace must be a non-NULL, 256-byte aligned device pointer");
+  if (!q->grad || misaligned(q->grad, 16) || !q->hyper || misaligned(q->hyper, 4) || !q->stats || misaligned(q->stats, 4) || !q->error ||
+      misaligned(q->error, 4))
+    return fail(who, "grad (16 bytes), hyper, stats and error (4 bytes) must be non-NULL, aligned device pointers");
+  if (UPDATE && (!q->m || !q->v || misaligned(q->m, 16) || misaligned(q->v, 16)))
+    return fail(who, "m and v must be non-NULL, 16-byte aligned device pointers");
+  if (!b->obs || !b->action || !b->logp_old || !b->advantage || !b->ret || misaligned(b->obs, 4) || misaligned(b->action, 4) ||
+      misaligned(b->logp_old, 4) || misaligned(b->advantage, 4) || misaligned(b->ret, 4))
+    return fail(who, "obs, action, logp_old, advantage and ret must be non-NULL, 4-byte aligned device pointers");
+  if (misaligned(b->index, 4) || misaligned(b->out_logp, 4) || misaligned(b->out_value, 4))
+    return fail(who, "index, out_logp and out_value must be 4-byte aligned device pointers (or NULL)");
+  const LearnDev pi = net_dev(&q->pi), vf = net_dev(&q->vf);
+  const int A = q->pi.n_out, P = pi.P + vf.P + (q->head ? A : 0), pitch = ppo_pitch(&q->pi, &q->vf, q->head);
+  const PpoLayout y = ppo_layout(P, pitch, B);
+  if (q->workspace_bytes < y.words * sizeof(float))
+    return fail(who, "workspace_bytes is " + std::to_string(q->workspace_bytes) + ", a batch of " + std::to_string(B) + " needs " +
+                         std::to_string(y.words * sizeof(float)) + " (s2d_learn_ppo_workspace_bytes: batch is above the workspace's max_batch)");
+  const size_t pb = (size_t)P * sizeof(float);
+  const void* bufs[5] = {q->params, q->grad, q->workspace, UPDATE ? q->m : nullptr, UPDATE ? q->v : nullptr};
+  const size_t lens[5] = {pb, pb, y.words * sizeof(float), pb, pb};
+  for (int i = 0; i < 5; ++i)
+    for (int j = i + 1; j < 5; ++j)
+      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
+        return fail(who, "params, m, v, grad and the workspace must not overlap one another");
+  const auto kb = y.lds ? s2d_learn_ppo_block_kernel<true> : s2d_learn_ppo_block_kernel<false>;
+  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + kPpoRowWords) * sizeof(float);
+  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 3)) return no_lds(who);
+  float* const ws = static_cast<float*>(q->workspace);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool normalize = q->normalize_advantage && B > 1;
+  if (normalize)
+    hipLaunchKernelGGL(s2d_learn_ppo_norm_kernel, dim3(1), dim3(kPpoNormThreads), 0, s, B, R, y.blocks, b->advantage, b->index, ws + y.bsum,
+                       ws + y.nrm);
+  PpoArgs a{};
+  a.head = q->head; a.A = A; a.normalize = normalize; a.pitch = pitch; a.P = P;
+  a.batch = B; a.src_rows = R; a.blocks = y.blocks; a.per_group = y.per_group;
+  a.params = q->params; a.part = ws + y.part; a.stat_part = ws + y.stat; a.image = ws + y.image; a.nrm = ws + y.nrm; a.hyper = q->hyper;
+  a.obs = b->obs; a.action = b->action; a.logp_old = b->logp_old; a.adv = b->advantage; a.ret = b->ret; a.index = b->index;
+  a.out_logp = b->out_logp; a.out_value = b->out_value; a.error = q->error;
+  hipLaunchKernelGGL(kb, dim3((unsigned)y.groups), dim3(kLearnThreads), lds, s, pi, vf, a);
+  const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
+  hipLaunchKernelGGL((s2d_learn_reduce_kernel<UPDATE, true>), dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, y.groups, ws + y.part, q->grad,
+                     ws + y.chunk, q->hyper, pi.P + vf.P);
+  hipLaunchKernelGGL((s2d_learn_finish_kernel<UPDATE, true>), dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, B, y.groups, chunks,
+                     false, ws + y.chunk, ws + y.stat, q->grad, q->hyper, q->stats, q->params, q->m, q->v);
+  return launched(who);
+}
 }  // namespace
+
+S2D_API size_t s2d_learn_ppo_workspace_bytes(const S2DLearnNet* pi_shape, const S2DLearnNet* vf_shape, int32_t head, int64_t max_batch) {
+  if (!pi_shape || !vf_shape || !ppo_error(pi_shape, vf_shape, head).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  const int P = net_dev(pi_shape).P + net_dev(vf_shape).P + (head ? pi_shape->n_out : 0);
+  return ppo_layout(P, ppo_pitch(pi_shape, vf_shape, head), max_batch).words * sizeof(float);
+}
+
+S2D_API int s2d_learn_ppo(const S2DLearnPPO* learner, const S2DLearnPPOBatch* batch, void* stream) {
+  return learn_ppo<true>("s2d_learn_ppo", learner, batch, stream);
+}
+
+S2D_API int s2d_learn_ppo_grad(const S2DLearnPPO* learner, const S2DLearnPPOBatch* batch, void* stream) {
+  return learn_ppo<false>("s2d_learn_ppo_grad", learner, batch, stream);
+}
 
 S2D_API size_t s2d_learn_workspace_bytes(const S2DLearnNet* shape, int64_t max_batch) {
   if (!shape || !shape_error(shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;

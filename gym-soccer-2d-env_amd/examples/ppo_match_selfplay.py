@@ -59,6 +59,8 @@ def parse(argv=None):
                     help='weights of the in-kernel agent reward (goal, ball_advance, approach, facing, kickable, possession); '
                          'default: the signed team reward')
     ap.add_argument('--chaser-only', action='store_true', help='with --shaping: approach and facing for each team\'s chaser only')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help='the minibatch epochs in HIP (soccer2d_amd.learn.PPOLearner) instead of torch autograd and Adam')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args(argv)
@@ -83,7 +85,13 @@ def main(argv=None):
     N, T, K = args.num_matches, args.steps, len(ACTION_TABLE)
     act = nn.ReLU if args.relu else nn.Tanh
     pi, vf = mlp(224, K, args.hidden, act).to(dev), mlp(224, 1, args.hidden, act).to(dev)
-    opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()), lr=args.lr)
+    learner = None
+    if args.fused_learner:                                 # torch.optim.Adam's defaults and no gradient clip, as the torch arm
+        from soccer2d_amd.learn import PPOLearner
+        learner = PPOLearner.from_modules(pi, vf, lr=args.lr, eps=1e-8, max_grad_norm=0.0, clip_range=args.clip, vf_coef=args.vf_coef,
+                                          ent_coef=args.ent_coef, max_batch=(T * N * 22 + args.minibatches - 1) // args.minibatches)
+    else:
+        opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()), lr=args.lr)
     actor = MatchPolicyActor.from_module(pi, ACTION_TABLE, device=dev)
     eng = MatchEngine(N, dev, noise=True, seed=args.seed)
     eng.set_network(actor, 'all')
@@ -111,8 +119,14 @@ def main(argv=None):
         lp_b, adv_b, ret_b = logp_old.reshape(-1), adv.reshape(-1), ret.reshape(-1)
         B = obs_b.shape[0]
         mb = (B + args.minibatches - 1) // args.minibatches
+        ro = {'obs': obs_b, 'action': idx.reshape(-1).int(), 'logp': lp_b, 'advantage': adv_b, 'return': ret_b}
         for _epoch in range(args.epochs):
             perm = torch.randperm(B, device=dev)
+            if learner is not None:                        # a minibatch step per call, the gather by perm in the kernel
+                perm = perm.int()
+                for s in range(0, B, mb):
+                    learner.step(ro, perm[s:s + mb])
+                continue
             for s in range(0, B, mb):
                 i = perm[s:s + mb]
                 d = torch.distributions.Categorical(logits=pi(obs_b[i]))
@@ -128,8 +142,12 @@ def main(argv=None):
                 loss.backward()
                 opt.step()
         actor.sync()                                       # the next launch samples from the new policy
-        row = dict(iteration=it, policy_loss=float(pg.detach()), value_loss=float(v_loss.detach()), entropy=float(ent.detach()),
-                   approx_kl=float((lp_b[i] - lp.detach()).mean()), mean_reward=float(rec['reward'].mean()))
+        if learner is not None:                            # approx_kl here is SB3's mean((r - 1) - log r), below mean(logp_old - logp)
+            row = dict(iteration=it, policy_loss=learner.policy_loss, value_loss=learner.value_loss, entropy=learner.entropy,
+                       approx_kl=learner.approx_kl, mean_reward=float(rec['reward'].mean()))
+        else:
+            row = dict(iteration=it, policy_loss=float(pg.detach()), value_loss=float(v_loss.detach()), entropy=float(ent.detach()),
+                       approx_kl=float((lp_b[i] - lp.detach()).mean()), mean_reward=float(rec['reward'].mean()))
         if (it + 1) % args.eval_every == 0:
             gl, gr = league.play_networks(eval_eng, actor, frozen, args.eval_cycles)
             row.update(eval_goals_learner=int(gl.sum()), eval_goals_snapshot=int(gr.sum()))

@@ -14,6 +14,10 @@ purpose: one batched forward over the recorded [T, N, 10] observations, the last
 Timeouts is one large GEMM, while an in-kernel value network would double the network's share of every cycle for nothing.
 Then soccer2d_amd.gae.gae() (one launch, Timeouts bootstrapped as SB3 does) and the epochs; the packed weights and log_std are
 refreshed with sync() after them.  0: one torch forward per step (Categorical / Normal in the loop).
+
+--fused-learner runs the epochs in HIP as well (soccer2d_amd.learn.PPOLearner): every minibatch step -- the gather by the
+permutation, both forward passes, log-probability, entropy, clipped surrogate, value loss, backward, clip and Adam -- is one call,
+and pi, vf and log_std stay the modules the rest of the script uses (their parameters become views of the learner's buffer).
 """
 import argparse
 import os
@@ -41,18 +45,25 @@ def mlp(n_in, n_out, act, hidden=64):
 
 class DevicePPO:
     def __init__(self, env, tanh=False, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5,
-                 ent_coef=0.0, seed=0):
+                 ent_coef=0.0, seed=0, hidden=64, fused_learner=False, max_batch=0):
         torch.manual_seed(seed)
         self.env, self.dev = env, env.device
         n_obs = env.observation_space.shape[0]
         self.discrete = hasattr(env.action_space, 'n')
         self.n_out = int(env.action_space.n) if self.discrete else env.action_space.shape[0]
         act = nn.Tanh if tanh else nn.ReLU
-        self.pi = mlp(n_obs, self.n_out, act).to(self.dev)
-        self.vf = mlp(n_obs, 1, act).to(self.dev)
+        self.pi = mlp(n_obs, self.n_out, act, hidden).to(self.dev)
+        self.vf = mlp(n_obs, 1, act, hidden).to(self.dev)
         self.log_std = nn.Parameter(torch.zeros(self.n_out, device=self.dev))
         params = list(self.pi.parameters()) + list(self.vf.parameters()) + ([] if self.discrete else [self.log_std])
-        self.opt = torch.optim.Adam(params, lr=lr)
+        self.learner = None
+        if fused_learner:                                    # torch.optim.Adam's defaults and no gradient clip, as the torch arm
+            from soccer2d_amd.learn import PPOLearner
+            self.learner = PPOLearner.from_modules(self.pi, self.vf, log_std=None if self.discrete else self.log_std, lr=lr, eps=1e-8,
+                                                   max_grad_norm=0.0, clip_range=clip, vf_coef=vf_coef, ent_coef=ent_coef,
+                                                   max_batch=(max_batch + minibatches - 1) // minibatches)
+        else:
+            self.opt = torch.optim.Adam(params, lr=lr)
         self.gamma, self.lam, self.clip, self.epochs, self.minibatches = gamma, lam, clip, epochs, minibatches
         self.vf_coef, self.ent_coef = vf_coef, ent_coef
         self.obs = env.reset().clone()
@@ -74,6 +85,14 @@ class DevicePPO:
         """clipped-surrogate epochs over the flattened batch"""
         B = obs.shape[0]
         mb = (B + self.minibatches - 1) // self.minibatches
+        if self.learner is not None:                         # the same epochs, a minibatch step per call, the gather in the kernel
+            ro = {'obs': obs, 'action': act.int() if self.discrete else act, 'logp': logp_old, 'advantage': adv, 'return': ret}
+            for _e in range(self.epochs):
+                perm = torch.randperm(B, device=self.dev).int()
+                for s in range(0, B, mb):
+                    self.learner.step(ro, perm[s:s + mb])
+            self.last_loss = self.learner.loss
+            return
         for _e in range(self.epochs):
             perm = torch.randperm(B, device=self.dev)
             for s in range(0, B, mb):
@@ -163,11 +182,16 @@ def main():
     ap.add_argument('--turning', action='store_true', help='use_turning=True: the 4-D Gaussian policy')
     ap.add_argument('--fused-actor', type=int, default=0, metavar='T',
                     help='collect T steps per launch with the in-kernel policy (0: one torch forward per step, 32 per update)')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help='the minibatch epochs in HIP (soccer2d_amd.learn.PPOLearner) instead of torch autograd and Adam')
+    ap.add_argument('--hidden', type=int, default=64, help='width of the two hidden layers of both networks (64; another width shows what --fused-learner and --fused-actor '
+                         'accept: the learner takes multiples of 8 in [8, 256] and names that grid when it refuses)')
     args = ap.parse_args()
     kw = dict(kewargs, use_continuous_action=args.continuous or args.turning, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
-    model = DevicePPO(env, tanh=args.tanh)
+    model = DevicePPO(env, tanh=args.tanh, hidden=args.hidden, fused_learner=args.fused_learner,
+                      max_batch=args.envs * (args.fused_actor if args.fused_actor > 0 else 32))
     r0 = test(test_env, model, args.test_steps)
     print('untrained policy:', r0)
     r = r0

@@ -154,6 +154,21 @@ class S2DLearnState(C.Structure):
                 ('error', C.c_void_p), ('loss_kind', C.c_int32)]
 
 
+class S2DLearnPPO(C.Structure):
+    """the learner of s2d_learn_ppo: the shapes of pi and vf, the head (0 categorical, 1 Gaussian), the flat [pi | vf | log_std]
+    parameters with their Adam state and gradient, hyper[10], stats[8], the error word and the workspace"""
+    _fields_ = [('pi', S2DLearnNet), ('vf', S2DLearnNet), ('head', C.c_int32), ('normalize_advantage', C.c_int32),
+                ('params', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('grad', C.c_void_p), ('hyper', C.c_void_p),
+                ('stats', C.c_void_p), ('error', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+class S2DLearnPPOBatch(C.Structure):
+    """the rollout arrays of R rows and the minibatch of B rows that `index` (or NULL) names in them"""
+    _fields_ = [('rows', C.c_int64), ('batch', C.c_int64), ('obs', C.c_void_p), ('action', C.c_void_p), ('logp_old', C.c_void_p),
+                ('advantage', C.c_void_p), ('ret', C.c_void_p), ('index', C.c_void_p), ('out_logp', C.c_void_p),
+                ('out_value', C.c_void_p)]
+
+
 class S2DTdNet(C.Structure):
     """one network of s2d_td_target_q / s2d_td_target_ac: S2DWideNet's MLP with a run-time input width (1 .. 256), the device
     pointer of its packed parameters and the workspace the pack kernel writes"""
@@ -228,6 +243,9 @@ PROTOTYPES = (
     ('s2d_learn_actor_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.POINTER(S2DLearnNet), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_learn_actor_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.c_int64)),
+    ('s2d_learn_ppo_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.c_int32, C.c_int64)),
+    ('s2d_learn_ppo', C.c_int, (C.POINTER(S2DLearnPPO), C.POINTER(S2DLearnPPOBatch), C.c_void_p)),
+    ('s2d_learn_ppo_grad', C.c_int, (C.POINTER(S2DLearnPPO), C.POINTER(S2DLearnPPOBatch), C.c_void_p)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

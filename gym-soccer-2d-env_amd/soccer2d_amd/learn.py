@@ -485,4 +485,202 @@ class ActorCriticLearner:
             mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
 
 
-__all__ = ['QLearner', 'ActorCriticLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes', 'learn_param_count']
+PPO_MAX_GROUPS = 256      # S2D_LEARN_PPO_MAX_GROUPS
+PPO_HEADS = ('categorical', 'gaussian')
+
+
+def learn_ppo_workspace_bytes(obs_dim, pi_hidden, n_out, vf_hidden, head, max_batch):
+    """bytes of the PPO learner's workspace, by the arithmetic of the C layout (s2d_learn_ppo_workspace_bytes): the partial gradients
+    and statistics of at most 256 groups of blocks, the chunk sums of the norm, the advantage pre-pass's two words and block sums
+    and, where 64 rows of BOTH networks do not fit the LDS, the groups' images; every part rounded up to 64 words.  head: 0 / 1."""
+    P = learn_param_count(obs_dim, pi_hidden, n_out) + learn_param_count(obs_dim, vf_hidden, 1) + (n_out if head else 0)
+    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
+    groups = min(blocks, PPO_MAX_GROUPS)
+    pitch = ((obs_dim + 3) // 4 * 4 + sum(pi_hidden) + n_out + sum(vf_hidden) + 1 + (n_out if head else 0)) | 1
+    words = _round64(groups * P) + _round64(chunks) + _round64(groups * 8) + 64 + _round64(blocks)
+    if BLOCK_ROWS * (pitch + 6) * 4 > LDS_BYTES:
+        words += _round64(groups * BLOCK_ROWS * pitch)
+    return words * 4
+
+
+class _Shape:
+    """the shape of one network of PPOLearner, as _fill_shape and _net_text read it"""
+
+    def __init__(self, who, what, module):
+        self.linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, what, module)
+        self.what, self.module = what, module
+
+    text = _net_text
+
+
+class PPOLearner:
+    """The PPO update in HIP (s2d_learn_ppo in include/s2d.h): what the examples' minibatch loop does in torch --
+
+        logp, entropy = dist(pi(obs[i])).log_prob(action[i]), .entropy();  a = normalised advantage[i]
+        ratio = exp(logp - logp_old[i]);  pg = -min(ratio a, clamp(ratio, 1 - c, 1 + c) a).mean()
+        loss = pg + vf_coef mse_loss(vf(obs[i]), return[i]) - ent_coef entropy.mean()
+        backward;  clip_grad_norm_(all parameters, max_grad_norm);  Adam.step()
+
+    -- as one call, the gather by ``index`` included.  ``pi`` and ``vf`` are separate Linear-(F-Linear) x L modules on the learner's
+    grid (1 .. 4 hidden layers of multiples of 8 in [8, 256], ReLU / Tanh / Sigmoid, at most 256 inputs) on the same observation;
+    without ``log_std`` the head is categorical (1 .. 64 logits, int32 actions), with it diagonal Gaussian (1 .. 8 means, float
+    actions as Engine.rollout_policy records them).  ONE flat buffer [pi | vf | log_std] holds every parameter, and the modules'
+    parameters and the log_std nn.Parameter are rebound as views of it: ``StochasticActor.sync()``, ``MatchPolicyActor.sync()``,
+    ``vf(obs)`` in torch for GAE and ``state_dict()`` keep working unchanged.  One Adam, one gradient norm and one clip run over
+    all of it.  Every hyper-parameter is a device word read when the kernels run: a step is a linear chain on torch's current
+    stream, capturable, and ``set_lr`` / ``set_clip_range`` / ``set_coefs`` between replays take effect.  tests/learn_ppo_ref.c."""
+
+    def __init__(self, pi, vf, log_std=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5, clip_range=0.2, vf_coef=0.5,
+                 ent_coef=0.0, normalize_advantage=True, max_batch=65536, device=None):
+        who = 'PPOLearner'
+        self.pi, self.vf = _Shape(who, 'policy network', pi), _Shape(who, 'value network', vf)
+        p, q = self.pi, self.vf
+        self.head = 0 if log_std is None else 1
+        if q.n_in != p.n_in or q.n_out != 1:
+            raise ValueError(f'{who}: the value network is {q.text()}; with the policy network {p.text()} it must take {p.n_in} inputs '
+                             f'and give one output')
+        if self.head:
+            if not isinstance(log_std, torch.nn.Parameter) or log_std.dtype != torch.float32 or log_std.numel() != p.n_out:
+                raise ValueError(f'{who}: log_std must be a float32 nn.Parameter of {p.n_out} values (or None: a categorical policy)')
+            if not 1 <= p.n_out <= MAX_ACTION:
+                raise ValueError(f'{who}: the Gaussian head takes 1 to {MAX_ACTION} means, the policy network has {p.n_out} outputs')
+        elif not 1 <= p.n_out <= MAX_OUT:
+            raise ValueError(f'{who}: the categorical head takes 1 to {MAX_OUT} logits, the policy network has {p.n_out} outputs')
+        b1, b2 = _check_optimiser(who, max_batch, lr, betas, eps)
+        if not (clip_range >= 0.0 and vf_coef >= 0.0 and ent_coef >= 0.0):
+            raise ValueError(f'{who}: clip_range, vf_coef and ent_coef must be >= 0, got {clip_range}, {vf_coef}, {ent_coef}')
+        dev = torch.device(device if device is not None else p.linears[0].weight.device)
+        f32 = torch.float32
+        self.obs_dim, self.n_out, self.max_batch, self.normalize_advantage = p.n_in, p.n_out, max_batch, bool(normalize_advantage)
+        self.P_pi, self.P_vf = learn_param_count(p.n_in, p.hidden, p.n_out), learn_param_count(q.n_in, q.hidden, 1)
+        P = self.P_pi + self.P_vf + (p.n_out if self.head else 0)
+        self.params = torch.zeros(P, dtype=f32, device=dev)
+        self.device = self.params.device
+        self.m, self.v, self._grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
+        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0, clip_range, vf_coef, ent_coef], dtype=f32).to(self.device)
+        self.stats = torch.zeros(8, dtype=f32, device=self.device)
+        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.workspace = torch.zeros(learn_ppo_workspace_bytes(p.n_in, p.hidden, p.n_out, q.hidden, self.head, max_batch) // 4, dtype=f32,
+                                     device=self.device)
+        _rebind(self.params[:self.P_pi], p.linears)
+        _rebind(self.params[self.P_pi:self.P_pi + self.P_vf], q.linears)
+        self.log_std = log_std
+        if self.head:
+            with torch.no_grad():
+                view = self.params[self.P_pi + self.P_vf:]
+                view.copy_(log_std.detach().reshape(-1))
+                log_std.data = view.view_as(log_std)
+
+    @classmethod
+    def from_modules(cls, pi, vf, log_std=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5, clip_range=0.2, vf_coef=0.5,
+                     ent_coef=0.0, normalize_advantage=True, max_batch=65536, device=None):
+        """A learner of the modules with SB3 PPO's arguments: torch.optim.Adam's (one optimiser over everything), clip_grad_norm_'s
+        max_grad_norm over everything (<= 0: no clip), the clip range, the two coefficients, per-minibatch advantage normalisation,
+        and the largest minibatch a step will see (it sizes the workspace).  device: where the buffers, and from then on the
+        modules' parameters and log_std, live (default: the policy network's)."""
+        return cls(pi, vf, log_std=log_std, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, clip_range=clip_range, vf_coef=vf_coef,
+                   ent_coef=ent_coef, normalize_advantage=normalize_advantage, max_batch=max_batch, device=device)
+
+    # ------------------------------------------------------------------ the step
+    def c_structs(self):
+        q = _capi.S2DLearnPPO()
+        _fill_shape(q.pi, self.pi), _fill_shape(q.vf, self.vf)
+        q.head, q.normalize_advantage = self.head, int(self.normalize_advantage)
+        q.params, q.m, q.v, q.grad = self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._grad.data_ptr()
+        q.hyper, q.stats, q.error = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr()
+        q.workspace, q.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel() * 4
+        return q
+
+    def _call(self, fn, rollout, index, logp_out, value_out):
+        who, f32 = f'PPOLearner.{"step" if fn == "s2d_learn_ppo" else "grad"}', torch.float32
+        keys = ('obs', 'action', 'logp', 'advantage', 'return')
+        if not isinstance(rollout, dict) or any(k not in rollout for k in keys):
+            raise ValueError(f'{who}: rollout must be a dict with ' + ', '.join(repr(k) for k in keys) + ', flattened to [R, ...]')
+        obs = rollout['obs']
+        if not torch.is_tensor(obs) or obs.dim() != 2 or not 1 <= obs.shape[0] < 2 ** 31:
+            raise ValueError(f"{who}: rollout['obs'] must be a [R, {self.obs_dim}] tensor, 1 <= R < 2^31")
+        R = obs.shape[0]
+        if index is not None and (not torch.is_tensor(index) or index.dim() != 1 or index.shape[0] < 1):
+            raise ValueError(f'{who}: index must be an int32 tensor [B], B >= 1 (or None: every row)')
+        B = index.shape[0] if index is not None else R
+        if B > self.max_batch:
+            raise ValueError(f'{who}: the minibatch has {B} rows, the learner was made with max_batch={self.max_batch}')
+
+        def arr(name, t, dtype, shape):
+            return _arr(who, self.device, name, t, dtype, shape)
+        action = (arr("rollout['action']", rollout['action'], f32, (R, self.n_out)) if self.head
+                  else arr("rollout['action']", rollout['action'], torch.int32, (R,)))
+        b = _capi.S2DLearnPPOBatch()
+        b.rows, b.batch = R, B
+        b.obs, b.action = arr("rollout['obs']", obs, f32, (R, self.obs_dim)), action
+        b.logp_old, b.advantage = arr("rollout['logp']", rollout['logp'], f32, (R,)), arr("rollout['advantage']", rollout['advantage'], f32, (R,))
+        b.ret = arr("rollout['return']", rollout['return'], f32, (R,))
+        b.index = arr('index', index, torch.int32, (B,)) if index is not None else None
+        b.out_logp = arr('logp_out', logp_out, f32, (B,)) if logp_out is not None else None
+        b.out_value = arr('value_out', value_out, f32, (B,)) if value_out is not None else None
+        if self.device.type != 'cuda':
+            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
+        lib = _capi.load_library()
+        q = self.c_structs()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, fn)(C.byref(q), C.byref(b), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, fn)
+
+    def step(self, rollout, index=None, logp_out=None, value_out=None):
+        """One update on the minibatch that `index` (int32 [B]; None: every row, in order) names in the rollout: a dict with 'obs'
+        [R, obs_dim], 'action' (int32 [R], or float32 [R, A] with log_std), 'logp', 'advantage' and 'return' [R] -- the flattened
+        record of Engine.rollout_policy and gae().  The epochs pass ``perm[s:s + mb]``: the permuted minibatch never exists in
+        memory.  logp_out / value_out [B] <- the rows' log-probabilities and values before the update.  Stream-ordered on torch's
+        current stream, capturable; returns nothing: read ``loss`` and the other statistics when they are wanted."""
+        self._call('s2d_learn_ppo', rollout, index, logp_out, value_out)
+
+    def grad(self, rollout, index=None, logp_out=None, value_out=None):
+        """The flat, unclipped gradient [P] over [pi | vf | log_std] (a view, written again by the next call) of the same loss, with
+        the statistics set, without touching the parameters or the optimiser's state."""
+        self._call('s2d_learn_ppo_grad', rollout, index, logp_out, value_out)
+        return self._grad
+
+    # ------------------------------------------------------------------ state
+    def _stat(self, i):
+        host = self.stats.tolist()                                           # synchronises
+        err = int(self.error.item())
+        if err:
+            self.error.zero_()
+            why = ([f'an action outside [0, {self.n_out})'] if err & 1 else []) + (['an index outside [0, R)'] if err & 2 else [])
+            raise ValueError(f'PPOLearner: a minibatch held {" and ".join(why)}: its rows were left out of the update')
+        return host[i]
+
+    loss = property(lambda self: self._stat(0), doc='the last call\'s loss: pg + vf_coef v_loss - ent_coef entropy (synchronises; '
+                    'raises ValueError if a minibatch since the last look held a bad action or index)')
+    grad_norm = property(lambda self: self._stat(1), doc='the last call\'s gradient norm over all parameters, before the clip')
+    clip_scale = property(lambda self: self._stat(2), doc='the factor the last call\'s gradient was scaled by')
+    policy_loss = property(lambda self: self._stat(3), doc='the last call\'s mean clipped-surrogate loss')
+    value_loss = property(lambda self: self._stat(4), doc='the last call\'s mean squared value error')
+    entropy = property(lambda self: self._stat(5), doc='the last call\'s mean entropy')
+    approx_kl = property(lambda self: self._stat(6), doc='mean((ratio - 1) - log ratio) of the last call (SB3\'s approx_kl)')
+    clip_fraction = property(lambda self: self._stat(7), doc='the share of the last call\'s rows with |ratio - 1| > clip_range')
+
+    def set_lr(self, lr):
+        """the learning rate of the steps enqueued from now on: a device write, also between the replays of a captured graph"""
+        self.hyper[0:1].fill_(float(lr))
+
+    def set_clip_range(self, clip_range):
+        """the clip range of the steps enqueued from now on (a schedule writes it as it writes lr)"""
+        self.hyper[7:8].fill_(float(clip_range))
+
+    def set_coefs(self, vf_coef=None, ent_coef=None):
+        """the value and entropy coefficients of the steps enqueued from now on"""
+        if vf_coef is not None:
+            self.hyper[8:9].fill_(float(vf_coef))
+        if ent_coef is not None:
+            self.hyper[9:10].fill_(float(ent_coef))
+
+    def reset_optimizer(self):
+        """Adam as new: m = v = 0, both beta products 1"""
+        self.m.zero_()
+        self.v.zero_()
+        self.hyper[5:7].fill_(1.0)
+
+
+__all__ = ['QLearner', 'ActorCriticLearner', 'PPOLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes',
+           'learn_ppo_workspace_bytes', 'learn_param_count']

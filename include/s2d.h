@@ -685,6 +685,79 @@ int s2d_learn_actor_grad(int64_t batch, const S2DLearnNet *actor, const S2DLearn
  * max_batch: s2d_learn_workspace_bytes' parts for the actor's parameters and, where 64 rows of both networks do not fit the LDS,
  * the blocks' images.  0 for a pair off the grid or max_batch outside [1, 2^31 - 1].  Host only, needs no GPU. */
 size_t s2d_learn_actor_workspace_bytes(const S2DLearnNet *actor_shape, const S2DLearnNet *critic_shape, int64_t max_batch);
+/* ---- the PPO update (s2d_learn.hip): clipped surrogate, value loss, entropy bonus, one clip and one Adam over both networks ----
+ * Engine-independent like s2d_learn_q: no handle, raw device pointers, any stream of the current device, everything read WHEN THE
+ * KERNELS RUN, a linear chain of launches on one stream (pre-pass if normalising, block kernel, reduce, finish; capturable), no float
+ * atomics, no result depends on the grid or the device.  tests/learn_ppo_ref.c restates every operation below.
+ *
+ * Networks: pi D -> h... -> A and vf D -> h... -> 1, both on the learner's grid above (shapes and activations may differ, D is
+ * shared).  head 0: categorical, A in 1 .. 64, action int32 [R].  head 1: diagonal Gaussian, A in 1 .. 8, action float [R][A] (the
+ * unclipped action s2d_rollout_policy records) and a parameter log_std[A].  ONE flat buffer params = [pi | vf | log_std] (log_std
+ * with head 1 only) of P words, with one m, v, grad, one norm and one clip over all of it.
+ * Rows: the rollout arrays have R rows; row b of the minibatch (b < B) is row index[b], or row b where index is NULL (then B <= R);
+ * the gather happens in the kernel.  An index outside [0, R) is never used: its row is DROPPED -- zero input, zero output deltas, no
+ * loss, no share in any statistic, out_logp = out_value = +0 -- the divisor stays B, and *error |= 2.  A categorical action outside
+ * [0, A) drops its row in the same way (but its advantage takes part in the normalisation) and *error |= 1.
+ * hyper[10]: the seven words of S2DLearnState, then clip_range c, vf_coef, ent_coef.
+ * Advantage normalisation (normalize_advantage != 0 and B > 1; a launch of its own), over the rows that are not dropped for their
+ * index: per block of 64 rows s = +0, rows ascending s = s + adv; blocks added ascending (the first starts the sum); mean = S / (float)B;
+ * the same with d = adv - mean, s = fmaf(d, d, s); std = sqrt(S2 / (float)(B - 1)); A^ = (adv - mean) / (std + 1e-8f).  Else A^ = adv.
+ * (The order is serial: the pre-pass is ONE workgroup and one lane adds the B / 64 block sums, twice: O(B / 64) on a single lane, so a
+ * normalised minibatch near the largest B is slow.)
+ * Per row, every step one fp32 operation, y = pi's outputs and v = vf's by s2d_learn_q's forward chain (layer 1 over 4 ceil(D / 4)
+ * terms: the bits s2d_rollout_policy acts on):
+ *   categorical  m = the first maximum of y; S = exp_spec(y_0 - m), j ascending: S += exp_spec(y_j - m); logS = log_spec(S);
+ *                logp = (y_a - m) - logS (categorical_head's); p_j = exp_spec(y_j - m) / S; lp_j = (y_j - m) - logS;
+ *                h = +0, j ascending: h = fmaf(p_j, lp_j, h); H = -h
+ *   Gaussian     z_j = (a_j - y_j) / exp_spec(log_std_j); term_j = fmaf(-0.5f * z_j, z_j, -log_std_j) - 0.91893853f; logp = term_0 + term_1
+ *                + ... ascending; H = (log_std_0 + log_std_1 + ...) + (float)A * 1.4189385f
+ *   surrogate    d = logp - logp_old; r = exp_spec(d); rc = r < 1 - c ? 1 - c : r > 1 + c ? 1 + c : r; s1 = r * A^; s2 = rc * A^;
+ *                policy loss -min(s1, s2) (a NaN wins); g = +0 where (r > 1 + c and A^ > 0) or (r < 1 - c and A^ < 0), else -s1
+ *   value        e = v - ret; loss e * e; delta (vf_coef * (2.0f * e)) / (float)B
+ *   deltas       categorical: (g * (1[j = a] - p_j) + (ent_coef * p_j) * (lp_j + H)) / (float)B;  Gaussian means: ((g * z_j) / sigma_j) /
+ *                (float)B, and the row's log_std term (g * (z_j * z_j - 1.0f)) / (float)B, summed over rows like a bias gradient;
+ *                grad[log_std_j] = that sum - ent_coef
+ *   statistics   policy loss, value loss, H, (r - 1.0f) - d, |r - 1.0f| > c ? 1 : 0
+ * Backward and parameter gradients are s2d_learn_q's per network, except for the order of the row sums: consecutive blocks of 64 rows
+ * are grouped G = ceil(blocks / S2D_LEARN_PPO_MAX_GROUPS) at a time; every dW / db / log_std chain and every statistic starts at +0 at
+ * the group's first row and runs over the group's rows ascending; the groups' partials are added in ascending group order (the first
+ * starts the sum).  G depends on B alone; for B <= 16 384 a group is a block.  Norm, clip scale and Adam are s2d_learn_q's over all
+ * P words.  stats[8] <- {loss = (pg + vf_coef * vl) - ent_coef * ent, norm, scale, pg, vl, ent, approx_kl, clip_fraction}, the last five
+ * the statistics' sums / (float)B.  NaN and inf propagate.  Not included: value clipping, a shared trunk, a target-KL stop. */
+#define S2D_LEARN_PPO_MAX_GROUPS 256
+enum { S2D_LEARN_PPO_CATEGORICAL = 0, S2D_LEARN_PPO_GAUSSIAN = 1 };
+typedef struct S2DLearnPPO {
+  S2DLearnNet pi, vf;      /* the shapes; their params / workspace fields are ignored */
+  int32_t head;            /* S2D_LEARN_PPO_CATEGORICAL | S2D_LEARN_PPO_GAUSSIAN */
+  int32_t normalize_advantage;
+  float *params;           /* READ-WRITE [P] = [pi | vf | log_std], 16-byte aligned */
+  float *m, *v, *grad;     /* [P] each, 16-byte aligned (m and v are not read by s2d_learn_ppo_grad) */
+  float *hyper;            /* [10]: lr, beta1, beta2, eps, max_grad_norm, beta1^t, beta2^t, clip_range, vf_coef, ent_coef */
+  float *stats;            /* [8] */
+  int32_t *error;          /* |= 1: a categorical action outside [0, A); |= 2: an index outside [0, R) */
+  void *workspace;         /* 256-byte aligned, >= s2d_learn_ppo_workspace_bytes(pi, vf, head, batch) */
+  size_t workspace_bytes;
+} S2DLearnPPO;
+typedef struct S2DLearnPPOBatch {
+  int64_t rows;            /* R: rows of the rollout arrays */
+  int64_t batch;           /* B: rows of the minibatch */
+  const float *obs;        /* [R][D] */
+  const void *action;      /* int32 [R] or float [R][A] */
+  const float *logp_old, *advantage, *ret;   /* [R] each */
+  const int32_t *index;    /* [B] or NULL */
+  float *out_logp, *out_value;               /* [B] each, or NULL */
+} S2DLearnPPOBatch;
+/* bytes of workspace for batches up to max_batch (only the shapes are read): at most 256 groups' partial gradients and statistics,
+ * the chunk sums, the pre-pass's block sums and, where 64 rows of both networks do not fit the LDS, the groups' images.  0 for a
+ * pair or head off the grid or max_batch outside [1, 2^31 - 1].  Host only, needs no GPU. */
+size_t s2d_learn_ppo_workspace_bytes(const S2DLearnNet *pi_shape, const S2DLearnNet *vf_shape, int32_t head, int64_t max_batch);
+/* One step.  S2D_EINVAL without a launch and with nothing written, the text naming the field: a shape or head off the grid, vf's n_in
+ * != pi's or n_out != 1, rows or batch outside [1, 2^31 - 1], batch above rows without an index or above what the workspace holds,
+ * NULL or misaligned params / workspace / m / v / grad / hyper / stats / error / obs / action / logp_old / advantage / ret, misaligned
+ * optional arrays, params, m, v, grad or the workspace overlapping one another. */
+int s2d_learn_ppo(const S2DLearnPPO *learner, const S2DLearnPPOBatch *batch, void *stream);
+/* The same up to and including grad, stats, out_logp and out_value, WITHOUT touching params, m, v or the beta products. */
+int s2d_learn_ppo_grad(const S2DLearnPPO *learner, const S2DLearnPPOBatch *batch, void *stream);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
