@@ -46,6 +46,10 @@ int s2d_internal_mlp_plan(const char* who, const S2DMlpNet* net, ActorPlanBuf* p
 int s2d_internal_rollout_mlp(const ActorRollout& a, const char* who, const S2DMlpNet* net, const ActorPlanBuf& pl);
 int s2d_internal_wide_plan(const char* who, const S2DWideNet* net, ActorPlanBuf* pl);
 int s2d_internal_rollout_wide(const ActorRollout& a, const char* who, const S2DWideNet* net, const ActorPlanBuf& pl);
+// s2d_wide_actor.hip: the squashed-Gaussian (SAC) rollout on a network planned by s2d_internal_wide_plan (n_out = 2A); checks the
+// workspace first, as the wide launch; 0, S2D_EINVAL with the text set, or -2
+int s2d_internal_rollout_sac(const ActorRollout& a, const char* who, const S2DWideNet* net, const ActorPlanBuf& pl, const uint32_t* det,
+                             float* logp);
 // s2d_policy.hip: the stochastic policy rollout of any action mode on a network planned by s2d_internal_net_plan (act_fn = 0 relu | 1 tanh); 0 or -2
 int s2d_internal_rollout_policy(const ActorRollout& a, const ActorPlanBuf& pl, int act_fn, const float* params, const float* log_std,
                                 const uint32_t* det, float* logp);

@@ -1513,7 +1513,7 @@ S2D_API int s2d_rollout(S2DHandle h, int n_steps, const void* actions_dev, int a
   return S2D_OK;
 }
 
-// ---- the fused actors: seven entry points on one checked prologue and epilogue.  An entry keeps what is its own: the engine
+// ---- the fused actors: eight entry points on one checked prologue and epilogue.  An entry keeps what is its own: the engine
 // modes it takes, its n_out rule, its shape check and its launcher.
 
 // S2D_EINVAL with the text `who` + `what`: built on the failing branch only, a launch that passes allocates nothing
@@ -1696,6 +1696,30 @@ S2D_API int s2d_rollout_actor_wide(S2DHandle h, int n_steps, const S2DWideNet* n
     return rc;
   return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
                       [&](const ActorRollout& a) { return s2d_internal_rollout_wide(a, who, net, pl); });
+}
+
+S2D_API int s2d_rollout_sac(S2DHandle h, int n_steps, const S2DWideNet* net, const uint32_t* deterministic, const S2DRollout* out,
+                            float* terminal_obs, float* logp, void* stream) {
+  static const char who[] = "s2d_rollout_sac";
+  RolloutOut ro;
+  int rc = actor_begin(who, h, net, kContinuousEngines,
+                       "s2d_rollout_sac needs a continuous-action engine (use_continuous_action = 1): there is no discrete SAC", n_steps, out,
+                       terminal_obs, logp, ro);
+  if (rc != S2D_OK) return rc;
+  const auto bad = [](const void* q, unsigned m) { return !q || (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  ActorPlanBuf pl;
+  if (s2d_internal_wide_plan(who, net, &pl) != S2D_OK) return S2D_EINVAL;
+  const bool turn = h->mode == S2D_MODE_TURN4;
+  if (net->n_out != (turn ? 8 : 2))
+    return actor_fail(who, turn ? ": n_out must be 8 on a turning engine (4 means, then 4 log-std rows)"
+                                : ": n_out must be 2 on a continuous (non-turning) engine (the mean, then the log-std row)");
+  if (net->noise_kind != 0) return actor_fail(who, ": noise_kind must be 0 (the policy's own noise is the only one)");
+  if (net->epsilon) return actor_fail(who, ": epsilon must be NULL (there is no epsilon in this path)");
+  if (net->noise) return actor_fail(who, ": noise must be NULL (the policy's own noise is the only one)");
+  if (bad(net->params, 15u)) return actor_fail(who, ": params must be a non-NULL, 16-byte aligned device pointer");
+  if (bad(deterministic, 3u)) return actor_fail(who, ": deterministic must be a non-NULL, 4-byte aligned device pointer");
+  return actor_launch(who, h, n_steps, ro, terminal_obs, stream,
+                      [&](const ActorRollout& a) { return s2d_internal_rollout_sac(a, who, net, pl, deterministic, logp); });
 }
 
 S2D_API int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet* net, const S2DRollout* out, float* terminal_obs,

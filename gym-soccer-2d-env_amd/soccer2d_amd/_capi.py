@@ -212,6 +212,8 @@ PROTOTYPES = (
     ('s2d_rollout_actor_wide', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DWideNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p)),
     ('s2d_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DPolicyNet), C.POINTER(S2DRollout), C.c_void_p, C.c_void_p,
                                      C.c_void_p)),
+    ('s2d_rollout_sac', C.c_int, (C.c_void_p, C.c_int, C.POINTER(S2DWideNet), C.c_void_p, C.POINTER(S2DRollout), C.c_void_p, C.c_void_p,
+                                  C.c_void_p)),
     ('s2d_gae', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_replay_push', C.c_int, (C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -229,6 +231,12 @@ PROTOTYPES = (
                                   C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_td_target_ac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_td_target_sac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p)),
+    ('s2d_debug_td_target_sac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p)),
     ('s2d_learn_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.c_int64)),
     ('s2d_learn_q', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),

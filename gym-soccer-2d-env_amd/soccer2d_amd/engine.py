@@ -323,6 +323,30 @@ class Engine:
         self._keep = (actor, out)
         return out
 
+    def rollout_sac(self, n_steps, actor, out=None, with_obs=True, terminal_obs=False, logp=True):
+        """n_steps fused cycles in one launch whose actions are SAMPLED in-kernel from `actor`'s (soccer2d_amd.wide_actor.
+        SquashedGaussianActor) squashed-Gaussian policy with a state-dependent log-std on the envs' own observations
+        (s2d_rollout_sac; continuous and turning engines: Soft Actor-Critic's collection).  Returns the record dict of rollout()
+        -- action float32 [T,N,1] / [T,N,4]: the squashed action tanh(u), what the env received and what SB3's SAC replay
+        stores -- plus 'logp' float32 [T,N] (logp=True, or a caller `out` holding 'logp').  actor.deterministic = True acts
+        with tanh(mean) in the same launch.  terminal_obs, graph capture and `out` caching as in rollout_qnet()."""
+        T, net = self._actor_call('rollout_sac', n_steps, actor, 's2d_rollout_sac')
+        t = self.cfg.task
+        if not t.use_continuous_action:
+            raise ValueError('rollout_sac needs a continuous-action engine (use_continuous_action=True): there is no discrete SAC')
+        a = 4 if t.use_turning else 1
+        if actor.action_dim != a:
+            raise ValueError(f'a {"turning" if t.use_turning else "continuous"} engine needs an actor with action_dim = {a} '
+                             f'({2 * a} outputs), got {actor.action_dim}')
+        record = dict(self._QNET_RECORD, action=(torch.float32, (a,)), logp=(torch.float32, ()))
+        out, ro, term = self._actor_record('rollout_sac', record, T, out, with_obs, terminal_obs, logp=logp)
+        lp = out.get('logp')
+        rc = self.lib.s2d_rollout_sac(self._h, T, C.byref(net), C.c_void_p(actor.deterministic_tensor.data_ptr()), C.byref(ro), term,
+                                      None if lp is None else C.c_void_p(lp.data_ptr()), self._stream())
+        _capi.check(self.lib, rc, 's2d_rollout_sac')
+        self._keep = (actor, out)
+        return out
+
     def step_k(self, k, actions=None, out=None):
         """k cycles of the per-step API in ONE launch (s2d_step_k; 1 <= k <= 64): for a learner that holds its actions for k steps
         ahead (action repeat, open-loop chunks).  actions [k, N, ...] as for rollout() (None = in-kernel random policy); returns the

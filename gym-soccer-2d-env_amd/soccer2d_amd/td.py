@@ -14,7 +14,10 @@ Each network keeps ONE flat fp32 parameter buffer and a workspace.  The kernels 
 reloads them from the modules (after ``load_state_dict`` or a Polyak step for the target networks, after every optimiser step
 for ``online``), and a captured graph computes with whatever they hold at replay.  The online Q-network's forward / backward pass and the
 optimiser are soccer2d_amd.learn.QLearner's, the DDPG / TD3 update soccer2d_amd.learn.ActorCriticLearner's.  Out of scope: the target is not fused into the sample launch, and TD3's
-target-policy smoothing noise is not added."""
+target-policy smoothing noise is not added.
+
+SacTarget is Soft Actor-Critic's: the ONLINE actor's squashed-Gaussian head draws the next action, and the target carries the
+entropy term, reward + discount * (min_i Q'_i(next_obs, a') - alpha * logp(a')) (s2d_td_target_sac)."""
 import ctypes as C
 
 import torch
@@ -62,40 +65,47 @@ class _Net:
     """one network of a target: its module, shape, flat parameter buffer and workspace"""
 
     def __init__(self, who, what, module, device, tanh_head=False):
-        if not isinstance(module, torch.nn.Module):
+        self.what, self.module, self._tanh_head = what, module, tanh_head
+        if not self._is_module():
             raise ValueError(f'{who}: the {what} must be a torch.nn.Module')
-        # the wide actors' reader and grid: Linear-(F-Linear) x L [-Tanh], one F of ReLU / Tanh / Sigmoid throughout
         try:
-            linears, act = _read_layers(module, **dict(_WideShape._grid, tanh_head=tanh_head))
+            tensors, n_in, widths, act = self._read()
         except ValueError as e:
             raise ValueError(f'{who}: {what}: {e}') from None
-        if any(lin.bias is None for lin in linears):
+        if any(t is None for t in tensors):
             raise ValueError(f'{who}: every nn.Linear of the {what} needs a bias')
-        self.hidden = _WideShape._check_shape([lin.out_features for lin in linears[:-1]], linears[-1].out_features, act)
-        self.n_in, self.n_out, self.activation = linears[0].in_features, linears[-1].out_features, act
+        self.hidden = _WideShape._check_shape(widths[:-1], widths[-1], act)
+        self.n_in, self.n_out, self.activation = n_in, widths[-1], act
         if not 1 <= self.n_in <= MAX_IN:
             raise ValueError(f'{who}: the {what}\'s input width must be in [1, {MAX_IN}], got {self.n_in}')
         if not 1 <= self.n_out <= MAX_OUT:
             raise ValueError(f'{who}: the {what}\'s output width must be in [1, {MAX_OUT}], got {self.n_out}')
-        self.what, self.module, self._tanh_head = what, module, tanh_head
-        dev = torch.device(device if device is not None else linears[0].weight.device)
+        dev = torch.device(device if device is not None else tensors[0].device)
         # torch's device allocations are 256-byte aligned (the ABI asks for 16 of params, 256 of the workspace)
-        self.params = torch.zeros(sum(lin.weight.numel() + lin.bias.numel() for lin in linears), dtype=torch.float32, device=dev)
+        self.params = torch.zeros(sum(t.numel() for t in tensors), dtype=torch.float32, device=dev)
         self.device = self.params.device                                     # with its index: 'cuda' -> cuda:0
         self.workspace = torch.zeros(td_workspace_bytes(self.n_in, self.hidden, self.n_out) // 4, dtype=torch.float32, device=self.device)
         self.sync()
 
+    def _is_module(self):
+        return isinstance(self.module, torch.nn.Module)
+
+    def _read(self):
+        """(the flat buffer's tensors in order, n_in, the layers' widths, the activation) of the module as it is now"""
+        # the wide actors' reader and grid: Linear-(F-Linear) x L [-Tanh], one F of ReLU / Tanh / Sigmoid throughout
+        linears, act = _read_layers(self.module, **dict(_WideShape._grid, tanh_head=self._tanh_head))
+        tensors = []
+        for lin in linears:
+            tensors += [lin.weight, lin.bias]
+        return tensors, linears[0].in_features, [lin.out_features for lin in linears], act
+
     def sync(self):
         """the module's current parameters into the flat buffer: one device copy, no allocation of what the kernel reads"""
-        linears, act = _read_layers(self.module, **dict(_WideShape._grid, tanh_head=self._tanh_head))
-        shape = ([lin.in_features for lin in linears[:1]], [lin.out_features for lin in linears])
-        if act != self.activation or shape != ([self.n_in], list(self.hidden) + [self.n_out]):
+        tensors, n_in, widths, act = self._read()
+        if act != self.activation or (n_in, widths) != (self.n_in, list(self.hidden) + [self.n_out]):
             raise ValueError(f'the {self.what} has changed its shape since from_module')
-        srcs = []
-        for lin in linears:
-            srcs += [lin.weight.detach().reshape(-1), lin.bias.detach().reshape(-1)]
         with torch.no_grad():
-            torch.cat([s.to(self.device, torch.float32) for s in srcs], out=self.params)
+            torch.cat([t.detach().reshape(-1).to(self.device, torch.float32) for t in tensors], out=self.params)
 
     text = _net_text
 
@@ -241,4 +251,101 @@ class ActorCriticTarget(_Target):
         return result
 
 
-__all__ = ['QTarget', 'ActorCriticTarget', 'td_workspace_bytes']
+class _SacActorNet(_Net):
+    """the online actor of SacTarget: one module ending in Linear(h_L, 2A) (A means, then A log-std rows), or SB3's triple
+    (latent_pi, mu, log_std), read into the same flat buffer: ..., [mu.weight ; log_std.weight], [mu.bias | log_std.bias]"""
+
+    def _is_module(self):
+        m = self.module
+        return isinstance(m, torch.nn.Module) or (isinstance(m, (tuple, list)) and len(m) == 3
+                                                  and all(isinstance(x, torch.nn.Module) for x in m))
+
+    def _read(self):
+        if isinstance(self.module, torch.nn.Module):
+            return super()._read()
+        latent_pi, mu, log_std = self.module
+        linears, act = _read_layers([latent_pi, mu], **dict(_WideShape._grid, many=True))
+        mu = linears[-1]
+        if not isinstance(log_std, torch.nn.Linear) or (log_std.in_features, log_std.out_features) != (mu.in_features, mu.out_features):
+            raise ValueError(f'log_std must be a Linear({mu.in_features}, {mu.out_features}) like mu, got {log_std}')
+        tensors = []
+        for lin in linears[:-1]:
+            tensors += [lin.weight, lin.bias]
+        tensors += [mu.weight, log_std.weight, mu.bias, log_std.bias]
+        return tensors, linears[0].in_features, [lin.out_features for lin in linears[:-1]] + [2 * mu.out_features], act
+
+
+class SacTarget(_Target):
+    """Soft Actor-Critic's entropy-regularised target in one launch (s2d_td_target_sac):
+
+        a', logp = squashed-Gaussian head of actor(next_obs)     the ONLINE actor, as in SB3, with fresh noise every call
+        target   = reward + discount * (min_i Q'_i(next_obs, a') - alpha * logp)
+
+    actor: Linear-(F-Linear) x L ending in Linear(h_L, 2A) (A means, then A raw log-std rows, clamped to [-20, 2]; A = 1 .. 8), or
+    SB3's triple ``(actor.latent_pi, actor.mu, actor.log_std)``; a critic is Linear-(F-Linear) x L from obs_dim + A inputs to one
+    output (SB3's ``critic_target.qf0``).  The noise is Philox with key `seed` at a device counter the target owns (``draws``):
+    every call, and every replay of a captured graph, advances it by one."""
+
+    _name = 'SacTarget'
+
+    def __init__(self, actor, q_target, q_target2=None, seed=0, device=None):
+        who = 'SacTarget'
+        act = _SacActorNet(who, 'actor', actor, device)
+        if act.n_out % 2 or not 1 <= act.n_out // 2 <= MAX_ACTION:
+            raise ValueError(f'{who}: the actor has {act.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
+                             f'1 .. {MAX_ACTION}')
+        self.action_dim = act.n_out // 2
+        dev = device if device is not None else act.device
+        critics = [_Net(who, 'target critic 1', q_target, dev)]
+        if q_target2 is not None:
+            critics.append(_Net(who, 'target critic 2', q_target2, dev))
+        for c in critics:
+            if c.n_in != act.n_in + self.action_dim or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
+                                 f'{act.n_in} + {self.action_dim} inputs and give one output')
+        self.actor, self.critics = act, tuple(critics)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self._init_nets([act] + critics)
+        self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)      # calls so far: the Philox counter's middle words
+        self._alpha = torch.zeros(1, dtype=torch.float32, device=self.device)   # where a Python float alpha is written
+
+    @classmethod
+    def from_modules(cls, actor, q_target, q_target2=None, seed=0, device=None):
+        """A target shaped like the modules, loaded from them.  device: where the buffers live (default: the actor's)."""
+        return cls(actor, q_target, q_target2=q_target2, seed=seed, device=device)
+
+    def target(self, batch, alpha, out=None, return_q=False):
+        """float32 [B] targets of a sampled batch, as QTarget.target.  alpha: the entropy coefficient, a float (written in place
+        into a device word the target owns) or a one-element float32 device tensor the kernel reads when it runs (a captured
+        graph computes with what it holds at replay).  return_q: (target, q [B], action [B, A], logp [B]): the smaller critic's
+        value, the sampled action it was evaluated at and that action's log-probability; `out` is then the tuple of four."""
+        who = 'SacTarget.target'
+        logp = None
+        if return_q and out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 4:
+                raise ValueError(f'{who}: out must be a tuple of four tensors (target, q, action, logp)')
+            out, logp = tuple(out[:3]), out[3]
+        B, ins, outs, result = self._batch(batch, out, return_q, torch.float32, (self.action_dim,))
+        if return_q:
+            if logp is None:
+                logp = torch.empty((B,), dtype=torch.float32, device=self.device)
+            lp = self._arr('out[3]', logp, torch.float32, (B,))
+            result = tuple(result) + (logp,)
+        else:
+            lp = None
+        if torch.is_tensor(alpha):
+            a = self._arr('alpha', alpha.reshape(-1) if alpha.dim() == 0 else alpha, torch.float32, (1,))
+        else:
+            self._alpha.fill_(float(alpha))
+            a = C.c_void_p(self._alpha.data_ptr())
+        lib = _capi.load_library()
+        nets = [n.c_struct() for n in self._nets]
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_td_target_sac(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, a,
+                                       C.c_void_p(self.draws.data_ptr()), self.seed, *outs, lp,
+                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, 's2d_td_target_sac')
+        return result
+
+
+__all__ = ['QTarget', 'ActorCriticTarget', 'SacTarget', 'td_workspace_bytes']

@@ -17,6 +17,7 @@ from .actor import DeterministicActor, StochasticActor
 from .engine import Engine, make_config
 from .spaces import reach_ball_spaces
 from .state_view import StateView, world_model_tensors
+from .wide_actor import SquashedGaussianActor
 
 RESULT_NAMES = _capi.RESULT_NAMES
 
@@ -59,10 +60,13 @@ class Soccer2DVecEnv:
         """T fused steps.  policy=None: `actions` (or the in-kernel random policy); policy=QNetActor: the actor's epsilon-greedy
         actions, evaluated in-kernel (Engine.rollout_qnet; terminal_obs=True records the observations episodes ended on);
         policy=DeterministicActor: its tanh policy with exploration and action noise (Engine.rollout_actor);
-        policy=StochasticActor: actions sampled from its categorical / Gaussian policy, with 'logp' (Engine.rollout_policy)."""
+        policy=StochasticActor: actions sampled from its categorical / Gaussian policy, with 'logp' (Engine.rollout_policy);
+        policy=SquashedGaussianActor: SAC's squashed actions with 'logp' (Engine.rollout_sac)."""
         if policy is not None:
             if actions is not None:
                 raise ValueError('give either actions or policy, not both')
+            if isinstance(policy, SquashedGaussianActor):
+                return self.engine.rollout_sac(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
             if isinstance(policy, StochasticActor):
                 return self.engine.rollout_policy(n_steps, policy, out=out, with_obs=with_obs, terminal_obs=terminal_obs)
             if isinstance(policy, DeterministicActor):

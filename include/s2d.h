@@ -420,6 +420,35 @@ int s2d_rollout_actor_wide(S2DHandle h, int n_steps, const S2DWideNet *net, cons
  * does not fit the LDS. */
 int s2d_rollout_policy(S2DHandle h, int n_steps, const S2DPolicyNet *net, const S2DRollout *out, float *terminal_obs, float *logp,
                        void *stream);
+/* Soft Actor-Critic's collection: n_steps >= 1 cycles fused in ONE launch (continuous or turning engines) whose action at every
+ * cycle is SAMPLED from the caller's squashed-Gaussian policy with a state-dependent log-std, and its log-probability recorded.
+ * The network is S2DWideNet's streamed-weight MLP 10 -> h_1 .. h_L -> n_out = 2A (A = 1 continuous, 4 turning; SB3's default
+ * net_arch=[256, 256] runs), the same fmaf chains, pack kernel and workspace as s2d_rollout_actor_wide.  Output rows 0 .. A-1 are
+ * the means (SB3's actor.mu), rows A .. 2A-1 the raw log-std (actor.log_std): the flat params are the hidden layers in
+ * nn.Sequential order, then W_out[2A][h_L] = [mu.weight ; log_std.weight], b_out = [mu.bias | log_std.bias].  net->epsilon and
+ * net->noise must be NULL and noise_kind 0: there is no epsilon in this path (warm-up with uniform actions is S2D_ACT_RANDOM of
+ * the plain rollout).  Per env and step at its policy_step k (advanced by one every step), every line one fixed fp32 operation:
+ *   ls_j    = v > 2 ? 2 : (v >= -20 ? v : -20), v = y[A + j]  (SB3's LOG_STD_MAX / LOG_STD_MIN; a NaN becomes -20, so exp_spec
+ *             never sees a non-finite argument);
+ *   sigma_j = exp_spec(ls_j);
+ *   z_j     from Box-Muller on Philox block 3 of stream POLICY, laid out exactly as the Gaussian head of the policy rollout above
+ *             (turning: z0..z3 of the block at counter k; continuous: z_{k & 3} of the block at counter k >> 2, cached and
+ *             refreshed at t == 0 and when k & 3 == 0);
+ *   u_j     = fmaf(sigma_j, z_j, y_j); a_j = tanh_spec(u_j).  The record and the env both get a_j (SB3's SAC replay stores the
+ *             squashed action; it is already in [-1, 1]); it then goes through the mode's action map;
+ *   logp    = t_0 (+ t_1 + t_2 + t_3 in ascending j),
+ *             t_j = (fmaf(-0.5f * z_j, z_j, -ls_j) - 0.91893853f) - log_spec(fmaf(-a_j, a_j, 1.0f) + 1e-6f)
+ *             (SB3's log(1 - tanh^2 + 1e-6) correction; at a_j = +-1 the argument is exactly 1e-6f);
+ *   *deterministic != 0   z_j = 0, u_j = y_j itself (a mean of -0 gives -0), no Philox draw.  The word is read when the kernel
+ *             runs: evaluation is the collection graph with the word set.
+ * Non-finite means are out of contract, as non-finite logits are above.  Records, terminal_obs, logp (float[T][N] or NULL),
+ * policy_step, statistics, per-step outputs and graph capture (two nodes: pack kernel and rollout) behave as the wide tanh
+ * actor's and the policy rollout's; the kernel's name carries mode, noise model, activation, widths, waves and tiles (neither of
+ * the last two enters the result).  Rejected with S2D_EINVAL, without a launch and with the state untouched, the error text
+ * naming the field: a discrete engine, n_out != 2A, a shape off S2DWideNet's grid, non-NULL epsilon / noise or noise_kind != 0,
+ * NULL or misaligned params / deterministic / workspace, a workspace too small, n_steps < 1. */
+int s2d_rollout_sac(S2DHandle h, int n_steps, const S2DWideNet *net, const uint32_t *deterministic, const S2DRollout *out,
+                    float *terminal_obs, float *logp /* [T][N] or NULL */, void *stream);
 /* Generalised advantage estimation over a time-major record, one backward scan per env (no engine handle: raw device
  * pointers, any stream of the current device).  ENGINE-INDEPENDENT: it assumes nothing of reach-ball; the 11v11 records have
  * the same [T][N] layout (N = envs, or envs x agents flattened).  Inputs: reward[T][N], done[T][N] (uint8), value[T][N] = V of
@@ -570,6 +599,28 @@ int s2d_td_target_q(int64_t batch, const S2DTdNet *target, const S2DTdNet *onlin
 int s2d_td_target_ac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
                      const float *next_obs /* [B][actor->n_in] */, const float *reward, const float *discount, float *out_target,
                      float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */, void *stream);
+#define S2D_TD_STREAM 13 /* Philox stream id of the SAC target's action noise (no other draw uses it) */
+/* Soft Actor-Critic's entropy-regularised target.  Per row b, with D = actor->n_in and A = actor->n_out / 2 in [1, 8]:
+ * y = actor(next_obs[b]) -- the ONLINE actor, as in SB3 --, rows 0 .. A-1 the means, A .. 2A-1 the raw log-std; the head of the SAC
+ * rollout above (ls_j, sigma_j, u_j, a_j, t_j, logp: the same function) with z from Philox4x32-10 with key `seed` at counter
+ * {b, draws_lo, draws_hi, (S2D_TD_STREAM << 16) | m}: m = 0 gives z0..z3, m = 1 (drawn only if A > 4) z4..z7, words x, y -> (z0, z1)
+ * and z, w -> (z2, z3) through the engine's Box-Muller.  The critics' row is [next_obs[b] | a']; q = q1, or with critic2
+ * q2 < q1 ? q2 : q1 as above; v = q - (alpha * logp): one multiply, then one subtract, never contracted; out_target[b] =
+ * reward[b] + (discount[b] * v).  out_q[b] <- q, out_action[b][j] <- a'_j, out_logp[b] <- logp where given.  *alpha (ent_coef) and
+ * *draws are device words read when the kernel runs; a one-thread kernel on the same stream then sets *draws += 1, so a replayed
+ * graph draws fresh noise and sample -> target stays one capturable linear chain.  The result does not depend on S2D_TD_PLAN.
+ * S2D_EINVAL without a launch as for the DDPG target, plus: actor->n_out odd or outside [2, 16], a critic whose n_in is not
+ * D + A, NULL or misaligned alpha (4 bytes) or draws (8 bytes), draws overlapping an output. */
+int s2d_td_target_sac(int64_t batch, const S2DTdNet *actor /* n_out = 2A */, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
+                      const float *next_obs, const float *reward, const float *discount, const float *alpha, uint64_t *draws,
+                      uint64_t seed, float *out_target, float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */,
+                      float *out_logp /* [B] or NULL */, void *stream);
+/* diagnostic: the SAC target with a `deterministic` switch, so that its head can be compared with the rollout's greedy action.
+ * deterministic = 0: the call above, bit for bit.  Non-zero: z_j = 0 and u_j = y_j, no Philox draw (the rollout's deterministic
+ * word); *draws is still advanced. */
+int s2d_debug_td_target_sac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2, const float *next_obs,
+                            const float *reward, const float *discount, const float *alpha, uint64_t *draws, uint64_t seed,
+                            int deterministic, float *out_target, float *out_q, float *out_action, float *out_logp, void *stream);
 /* ---- the Q-learner's gradient step (s2d_learn.hip) ----
  * What follows the TD target in DQN, Double DQN, n-step and PER: ONE gradient step of the online Q-network on a sampled batch --
  * forward, TD error, MSE / Huber derivative, backward, gradient-norm clip and Adam -- as a linear chain of three launches on one
