@@ -34,11 +34,22 @@
 //                               forwards, the head and the clipped surrogate (lane = row), both backward passes with the dW / db
 //                               chains continued across the group's blocks, so the partials are at most 256 x P words
 // and runs the reduce and finish kernels with their PPO flag (log_std's entropy term, eight statistics).
+// The SAC actor step (s2d_learn_sac_actor: the squashed-Gaussian actor through min(Q1, Q2), reparameterised, and the temperature;
+// tests/learn_sac_ref.c) adds
+//   s2d_learn_sac_kernel        the actor kernel's workgroup and block with three networks' rows and the head's z in the image: actor
+//                               forward, the head of s2d_sac_head.h on a Philox stream of its own (lane = row), both critics forward,
+//                               the row's minimum, both critics' delta passes, the head's derivative on the chosen critic's action
+//                               columns, the actor's backward pass; two rows of block partials (loss, logp)
+//   s2d_learn_sac_alpha_kernel  ONE THREAD, a launch of its own behind the finish kernel: the mean of logp, log_alpha's Adam step,
+//                               *alpha and *draws += 1.  (The other choice, a flag on the finish kernel as PPO took, would have
+//                               changed that kernel's text; this way its existing instantiations are the ones the other learners run.)
+// and runs the reduce and finish kernels as the DDPG actor step does, so the call stays a linear chain on one stream.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
 
+#include "s2d_sac_head.h"
 #include "s2d_wide_net.h"
 
 static constexpr int kLearnRows = S2D_LEARN_BLOCK_ROWS;
@@ -51,6 +62,7 @@ static constexpr int kPpoMaxGroups = S2D_LEARN_PPO_MAX_GROUPS;
 static constexpr int kPpoStatWords = 8;     // a group's partials of the five statistics, padded
 static constexpr int kPpoRowWords = 6;      // beside the image, per row of the block: its source row and its five statistics
 static constexpr int kPpoNormThreads = 1024;
+static constexpr int kSacRowWords = 3;     // beside the image, per row of the block: its loss, its logp and the critic it chose
 static_assert(kLearnRows == kWave, "lane = row of the block");
 static_assert(kLearnChunk == kLearnThreads, "one thread per word of a chunk");
 
@@ -461,6 +473,204 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_actor_kernel(LearnDev
   learn_backward<true>(a, aparams, part + (size_t)blockIdx.x * a.P, img, pitch, rows, 0, a_off, tid, lane, wv);
 }
 
+// ------------------------------------------------------------------------------------------ SAC (s2d_learn_sac_actor)
+// what the SAC actor kernel reads of a call besides the three networks
+struct SacArgs {
+  int pitch, z_off, twin;                    // the image's row; the column of the head's z words; critic 2 is there
+  int64_t batch;
+  const float* aparams;
+  const float* c1params;
+  const float* c2params;
+  float* part;                               // [blocks][P of the actor]
+  float* loss_part;                          // [blocks]: the rows' alpha * logp - q
+  float* logp_part;                          // [blocks]: the rows' logp
+  float* image;                              // [blocks][64][pitch], if not in LDS
+  const float* obs;
+  const float* alpha;                        // one device word: ent_coef
+  const uint64_t* draws;                     // one device word: the steps so far
+  uint32_t seed_lo, seed_hi;
+  float* out_action;
+  float* out_logp;
+  float* out_q;
+};
+
+// s2d_learn_sac_actor: loss = mean_b (alpha * logp_b - min(Q1, Q2)(obs_b, a_b)), a_b drawn by the squashed-Gaussian head.  A row of
+// the image holds all three networks' rows and the head's words:
+// [x: c1.kp = 4 ceil((D + A) / 4) | the actor's y_1 .. y_L | mean: A, v: A | critic 1's y_1 .. y_L | q1: 1 | critic 2's y_1 .. y_L | q2: 1 | z: A].
+// The head (lane = row) writes a behind the observation words, where the critics read it and the head's derivative finds it again; v
+// stays in the actor's output columns and z in its own until the derivative has been formed.  Both critics' backward passes form
+// deltas only (no dW, no db) with the output delta -1 / B; the head's derivative takes the action columns of the CHOSEN critic's
+// input delta (row_sel), so the other's words never reach a result.
+template <bool LDS>
+__global__ __launch_bounds__(kLearnThreads) void s2d_learn_sac_kernel(LearnDev a, LearnDev c1, LearnDev c2, SacArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [the rows' losses: 64 | logp: 64 | chosen critic: 64 | the image, if it lives here]
+  float* const row_loss = smem;
+  float* const row_logp = smem + kLearnRows;
+  int* const row_sel = reinterpret_cast<int*>(smem + 2 * kLearnRows);
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int64_t row0 = (int64_t)blockIdx.x * kLearnRows;
+  const int rows = (int)(g.batch - row0 < kLearnRows ? g.batch - row0 : kLearnRows);
+  const int D = a.n_in, A = a.na >> 1, pitch = g.pitch, z_off = g.z_off;
+  const bool twin = g.twin != 0;
+  float* const img = LDS ? smem + kSacRowWords * kLearnRows : g.image + (size_t)blockIdx.x * kLearnRows * pitch;
+  const float alpha = *g.alpha;
+  const uint64_t draws = *g.draws;
+
+  for (int idx = tid; idx < kLearnRows * c1.kp; idx += kLearnThreads) {
+    const int r = idx / c1.kp, k = idx - r * c1.kp;
+    img[r * pitch + k] = (r < rows && k < D) ? g.obs[(row0 + r) * D + k] : 0.0f;
+  }
+  __syncthreads();
+  // ---- forward: the actor, its head, the critics
+  const int y_off = learn_forward(a, g.aparams, img, pitch, 0, c1.kp, lane, wv);
+  if (tid < kLearnRows) {
+    float* const row = img + tid * pitch;
+    const int64_t i = row0 + tid;                      // the absolute row: nothing depends on the grid
+    float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const U4 w = philox4x32_10((uint32_t)i, (uint32_t)draws, (uint32_t)(draws >> 32), (uint32_t)S2D_LEARN_SAC_STREAM << 16, g.seed_lo,
+                               g.seed_hi);
+    box_muller(w.x, w.y, z[0], z[1]);
+    box_muller(w.z, w.w, z[2], z[3]);
+    if (A > 4) {
+      const U4 w2 = philox4x32_10((uint32_t)i, (uint32_t)draws, (uint32_t)(draws >> 32), ((uint32_t)S2D_LEARN_SAC_STREAM << 16) | 1u,
+                                  g.seed_lo, g.seed_hi);
+      box_muller(w2.x, w2.y, z[4], z[5]);
+      box_muller(w2.z, w2.w, z[6], z[7]);
+    }
+    float lp = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kLearnMaxAction; ++j) {
+      if (j < A) {
+        float act;
+        const float term = sac_head_term(row[y_off + j], row[y_off + A + j], z[j], false, act);
+        lp = j == 0 ? term : lp + term;
+        row[D + j] = act;
+        row[z_off + j] = z[j];
+        if (g.out_action && tid < rows) g.out_action[i * A + j] = act;
+      }
+    }
+    row_logp[tid] = lp;
+  }
+  __syncthreads();
+  const int c1y_off = y_off + 2 * A;
+  const int q1_off = learn_forward(c1, g.c1params, img, pitch, 0, c1y_off, lane, wv);
+  const int c2y_off = q1_off + 1;
+  const int q2_off = twin ? learn_forward(c2, g.c2params, img, pitch, 0, c2y_off, lane, wv) : q1_off;
+  if (tid < kLearnRows) {
+    float* const row = img + tid * pitch;
+    const float q1 = row[q1_off], lp = row_logp[tid];
+    float q = q1;
+    int sel = 0;
+    if (twin) {
+      const float q2 = row[q2_off];
+      if (q2 < q1) {                                   // a tie or a NaN q2 keeps critic 1
+        q = q2;
+        sel = 1;
+      }
+    }
+    if (tid < rows) {
+      if (g.out_q) g.out_q[row0 + tid] = q;
+      if (g.out_logp) g.out_logp[row0 + tid] = lp;
+    }
+    row_loss[tid] = __fsub_rn(__fmul_rn(alpha, lp), q);   // one multiply, then one subtract
+    row_sel[tid] = sel;
+    const float dq = tid < rows ? -1.0f / (float)g.batch : 0.0f;
+    row[q1_off] = dq;
+    if (twin) row[q2_off] = dq;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.0f;
+    for (int r = 0; r < rows; ++r) s = s + row_loss[r];
+    g.loss_part[blockIdx.x] = s;
+  }
+  if (tid == kWave) {                                    // another wave's lane 0
+    float s = 0.0f;
+    for (int r = 0; r < rows; ++r) s = s + row_logp[r];
+    g.logp_part[blockIdx.x] = s;
+  }
+  // ---- backward through both critics: deltas only; then the action columns of the chosen critic's input delta and the head
+  learn_backward<false>(c1, g.c1params, nullptr, img, pitch, rows, 0, q1_off, tid, lane, wv);
+  if (twin) learn_backward<false>(c2, g.c2params, nullptr, img, pitch, rows, 0, q2_off, tid, lane, wv);
+  {
+    const float w = alpha / (float)g.batch;
+    float* const row = img + lane * pitch;
+    const int win = c1.n_in;
+    for (int j = wv; j < A; j += kLearnThreads / kWave) {
+      float s = 0.0f;
+      {
+        const int h1 = learn_width(c1, 0);
+        const float* const d1 = row + c1y_off;
+        for (int k = 0; k < h1; ++k) s = fmaf(g.c1params[k * win + D + j], d1[k], s);
+      }
+      if (twin) {
+        const int h1 = learn_width(c2, 0);
+        const float* const d1 = row + c2y_off;
+        float s2 = 0.0f;
+        for (int k = 0; k < h1; ++k) s2 = fmaf(g.c2params[k * win + D + j], d1[k], s2);
+        s = row_sel[lane] ? s2 : s;
+      }
+      const float act = row[D + j], v = row[y_off + A + j], zj = row[z_off + j];
+      const float ls = v > 2.0f ? 2.0f : (v >= -20.0f ? v : -20.0f);
+      const float sigma = exp_spec(ls);
+      const float om = fmaf(-act, act, 1.0f);          // the forward's value
+      const float r = om / (om + 1e-6f);
+      const float du = ((w * (2.0f * act)) * r) + (s * om);
+      const float dls = (du * (sigma * zj)) - w;
+      row[y_off + j] = du;
+      row[y_off + A + j] = (v >= -20.0f && v <= 2.0f) ? dls : 0.0f;   // torch's clamp: inclusive bounds, a NaN gives +0
+    }
+  }
+  __syncthreads();
+  learn_backward<true>(a, g.aparams, g.part + (size_t)blockIdx.x * a.P, img, pitch, rows, 0, y_off, tid, lane, wv);
+}
+
+// what the temperature's one thread reads of a call; log_alpha == nullptr: a fixed entropy coefficient
+struct SacAlphaDev {
+  float* log_alpha;
+  float* m_v;
+  float* hyper;
+  float* stats;
+  float target_entropy;
+};
+// One thread behind the finish kernel: the mean of logp (the blocks' partials ascending), the temperature's loss and (UPDATE) its Adam
+// step with scale 1, *alpha = exp_spec(log_alpha), and *draws += 1 so that the next call draws fresh noise.
+template <bool UPDATE>
+__global__ void s2d_learn_sac_alpha_kernel(int64_t batch, int64_t blocks, const float* __restrict__ logp_part, SacAlphaDev t,
+                                           float* __restrict__ alpha, uint64_t* __restrict__ draws) {
+  if (t.log_alpha) {
+    float ls = logp_part[0];
+    for (int64_t b = 1; b < blocks; ++b) ls = ls + logp_part[b];
+    const float mean = ls / (float)batch;
+    const float la = *t.log_alpha;
+    const float gr = -(mean + t.target_entropy);
+    t.stats[0] = mean;
+    t.stats[1] = la * gr;
+    if (UPDATE) {
+      const float lr = t.hyper[0], b1 = t.hyper[1], b2 = t.hyper[2], eps = t.hyper[3];
+      const float b1t = t.hyper[5] * b1, b2t = t.hyper[6] * b2;
+      t.hyper[5] = b1t;
+      t.hyper[6] = b2t;
+      const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+      const float bc2s = sqrtf(1.0f - b2t), step = lr / (1.0f - b1t);
+      const float gp = gr * 1.0f;
+      const float m0 = t.m_v[0];
+      const float mn = m0 + (gp - m0) * omb1;
+      const float vn = t.m_v[1] * b2 + (omb2 * gp) * gp;
+      const float den = sqrtf(vn) / bc2s + eps;
+      t.m_v[0] = mn;
+      t.m_v[1] = vn;
+      const float ln = la - step * (mn / den);
+      const float an = exp_spec(ln);
+      *t.log_alpha = ln;
+      *alpha = an;
+      t.stats[2] = an;
+    }
+  }
+  if (UPDATE) *draws += 1;
+}
+
 // ------------------------------------------------------------------------------------------ PPO (s2d_learn_ppo)
 // what the PPO kernels read of a call besides the two networks
 struct PpoArgs {
@@ -757,7 +967,7 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
-struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor, 3 PPO); fail, misaligned and launched are s2d_wide_host.h's
+struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor, 3 PPO, 4 SAC); fail, misaligned and launched are s2d_wide_host.h's
 
 // "" if the shape is on the learner's grid, else the text naming the field
 std::string shape_error(const S2DLearnNet* n) {
@@ -946,6 +1156,122 @@ int learn_actor(const std::string& who, int64_t batch, const S2DLearnNet* actor,
   reduce_and_finish<UPDATE>(a.P, batch, true, y, actor, st, s);
   return launched(who);
 }
+// ---- SAC
+// "" if the actor and its critic(s) are on the grid of s2d_learn_sac_actor: s2d_learn_actor's with A = n_out / 2
+std::string sac_error(const S2DLearnNet* actor, const S2DLearnNet* critic1, const S2DLearnNet* critic2) {
+  std::string bad = shape_error(actor);
+  if (!bad.empty()) return "actor: " + bad;
+  const S2DLearnNet* const cs[2] = {critic1, critic2};
+  for (int i = 0; i < 2; ++i)
+    if (cs[i]) {
+      bad = shape_error(cs[i]);
+      if (!bad.empty()) return std::string(i ? "critic2: " : "critic1: ") + bad;
+    }
+  if (actor->n_out % 2 || actor->n_out < 2 || actor->n_out > 2 * kLearnMaxAction)
+    return "actor: n_out (means, then raw log-std) must be even and in [2, 16]";
+  if (actor->n_in > kLearnMaxObs) return "actor: n_in must be in [1, 248]";
+  for (int i = 0; i < 2; ++i)
+    if (cs[i] && (cs[i]->n_in != actor->n_in + actor->n_out / 2 || cs[i]->n_out != 1))
+      return std::string(i ? "critic2" : "critic1") + ": n_in must be the actor's n_in + n_out / 2, its n_out 1";
+  return "";
+}
+// the column of the head's z words, behind every network's layers; the row has A more words
+int sac_z_off(const S2DLearnNet* a, const S2DLearnNet* c1, const S2DLearnNet* c2) {
+  return (c1->n_in + 3) / 4 * 4 + layer_words(a) + layer_words(c1) + (c2 ? layer_words(c2) : 0);
+}
+int sac_pitch(const S2DLearnNet* a, const S2DLearnNet* c1, const S2DLearnNet* c2) { return (sac_z_off(a, c1, c2) + a->n_out / 2) | 1; }
+// the actor's workspace in words: [partials: blocks x P | chunk sums | loss partials | logp partials | images, if not in LDS]
+struct SacLayout {
+  LearnLayout y;
+  size_t logp;
+};
+SacLayout sac_layout(int P, int pitch, int64_t batch) {
+  SacLayout q{};
+  LearnLayout& y = q.y;
+  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
+  y.lds = (size_t)kLearnRows * (pitch + kSacRowWords) * sizeof(float) <= kLdsMax;
+  y.part = 0;
+  y.chunk = round64(blocks * P);
+  y.loss = y.chunk + round64(chunks);
+  q.logp = y.loss + round64(blocks);
+  y.image = q.logp + round64(blocks);
+  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * pitch));
+  return q;
+}
+
+template <bool UPDATE>
+int learn_sac(const std::string& who, int64_t batch, const S2DLearnNet* actor, const S2DLearnState* st, const S2DLearnNet* critic1,
+              const S2DLearnNet* critic2, const float* obs, float* alpha, const S2DLearnSacAlpha* as, uint64_t* draws, uint64_t seed,
+              float* out_action, float* out_logp, float* out_q, void* stream) {
+  if (!actor || !st || !critic1) return fail(who, "actor, state and critic1 must be non-NULL");
+  std::string err = sac_error(actor, critic1, critic2);
+  if (!err.empty()) return fail(who, err);
+  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  err = buffers_error<UPDATE>("actor", actor, st, false);
+  if (!err.empty()) return fail(who, err);
+  if (!critic1->params || misaligned(critic1->params, 16)) return fail(who, "critic1: params must be a non-NULL, 16-byte aligned device pointer");
+  if (critic2 && (!critic2->params || misaligned(critic2->params, 16)))
+    return fail(who, "critic2: params must be a non-NULL, 16-byte aligned device pointer");
+  if (!obs || misaligned(obs, 4)) return fail(who, "obs must be a non-NULL, 4-byte aligned device pointer");
+  if (!alpha || misaligned(alpha, 4)) return fail(who, "alpha must be a non-NULL, 4-byte aligned device pointer");
+  if (!draws || misaligned(draws, 8)) return fail(who, "draws must be a non-NULL, 8-byte aligned device pointer");
+  if (as && (!as->log_alpha || !as->m_v || !as->hyper || !as->stats || misaligned(as->log_alpha, 4) || misaligned(as->m_v, 4) ||
+             misaligned(as->hyper, 4) || misaligned(as->stats, 4)))
+    return fail(who, "alpha_state: log_alpha, m_v, hyper and stats must be non-NULL, 4-byte aligned device pointers");
+  if (misaligned(out_action, 4) || misaligned(out_logp, 4) || misaligned(out_q, 4))
+    return fail(who, "out_action, out_logp and out_q must be 4-byte aligned device pointers (or NULL)");
+  const LearnDev a = net_dev(actor), c1 = net_dev(critic1), c2 = critic2 ? net_dev(critic2) : LearnDev{};
+  const int A = actor->n_out / 2, pitch = sac_pitch(actor, critic1, critic2);
+  const SacLayout q = sac_layout(a.P, pitch, batch);
+  const LearnLayout& y = q.y;
+  err = layout_error<UPDATE>("actor", actor, st, y, a.P, batch, "s2d_learn_sac_workspace_bytes", critic1->params, (size_t)c1.P * sizeof(float));
+  if (!err.empty()) return fail(who, err);
+  {
+    // the call's new arrays against one another and against what the call writes or the critics' parameters
+    const size_t pb = (size_t)a.P * sizeof(float), fb = sizeof(float), B = (size_t)batch;
+    const void* mine[6] = {alpha, draws, as ? as->log_alpha : nullptr, as ? as->m_v : nullptr, as ? as->hyper : nullptr, as ? as->stats : nullptr};
+    const size_t mlen[6] = {fb, sizeof(uint64_t), fb, 2 * fb, 7 * fb, 3 * fb};
+    const void* other[10] = {actor->params, st->grad, actor->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr, critic1->params,
+                             critic2 ? critic2->params : nullptr, out_action, out_logp, out_q};
+    const size_t olen[10] = {pb, pb, y.words * fb, pb, pb, (size_t)c1.P * fb, (size_t)c2.P * fb, B * A * fb, B * fb, B * fb};
+    for (int i = 0; i < 6; ++i) {
+      if (!mine[i]) continue;
+      for (int j = i + 1; j < 6; ++j)
+        if (mine[j] && overlap(mine[i], mlen[i], mine[j], mlen[j]))
+          return fail(who, "alpha, draws and alpha_state's log_alpha, m_v, hyper and stats must not overlap one another");
+      for (int j = 0; j < 10; ++j)
+        if (other[j] && overlap(mine[i], mlen[i], other[j], olen[j]))
+          return fail(who, "alpha, draws and alpha_state's arrays must not overlap the actor's params, m, v, grad or workspace, a critic's "
+                           "params or an output");
+    }
+    if (critic2)
+      for (int j = 0; j < 5; ++j)
+        if (other[j] && overlap(other[j], olen[j], critic2->params, olen[6]))
+          return fail(who, "the actor's params, m, v, grad and workspace must not overlap one another or the critic's params");
+  }
+  const auto kb = y.lds ? s2d_learn_sac_kernel<true> : s2d_learn_sac_kernel<false>;
+  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + kSacRowWords) * sizeof(float);
+  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 4)) return no_lds(who);
+  float* const ws = static_cast<float*>(actor->workspace);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
+  SacArgs g{};
+  g.pitch = pitch; g.z_off = sac_z_off(actor, critic1, critic2); g.twin = critic2 ? 1 : 0; g.batch = batch;
+  g.aparams = actor->params; g.c1params = critic1->params; g.c2params = critic2 ? critic2->params : nullptr;
+  g.part = ws + y.part; g.loss_part = ws + y.loss; g.logp_part = ws + q.logp; g.image = ws + y.image;
+  g.obs = obs; g.alpha = alpha; g.draws = draws; g.seed_lo = (uint32_t)seed; g.seed_hi = (uint32_t)(seed >> 32);
+  g.out_action = out_action; g.out_logp = out_logp; g.out_q = out_q;
+  hipLaunchKernelGGL(kb, dim3((unsigned)blocks), dim3(kLearnThreads), lds, s, a, c1, c2, g);
+  reduce_and_finish<UPDATE>(a.P, batch, false, y, actor, st, s);
+  if (UPDATE || as) {
+    SacAlphaDev t{};
+    if (as) {
+      t.log_alpha = as->log_alpha; t.m_v = as->m_v; t.hyper = as->hyper; t.stats = as->stats; t.target_entropy = as->target_entropy;
+    }
+    hipLaunchKernelGGL(s2d_learn_sac_alpha_kernel<UPDATE>, dim3(1), dim3(1), 0, s, batch, blocks, ws + q.logp, t, alpha, draws);
+  }
+  return launched(who);
+}
 // ---- PPO
 // "" if the pair of networks and the head are on the grid of s2d_learn_ppo
 std::string ppo_error(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) {
@@ -1099,4 +1425,25 @@ S2D_API int s2d_learn_actor(int64_t batch, const S2DLearnNet* actor, const S2DLe
 S2D_API int s2d_learn_actor_grad(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic,
                                  const float* obs, float* out_action, float* out_q, void* stream) {
   return learn_actor<false>("s2d_learn_actor_grad", batch, actor, actor_state, critic, obs, out_action, out_q, stream);
+}
+
+S2D_API size_t s2d_learn_sac_workspace_bytes(const S2DLearnNet* actor_shape, const S2DLearnNet* critic1_shape, const S2DLearnNet* critic2_shape,
+                                             int64_t max_batch) {
+  if (!actor_shape || !critic1_shape || !sac_error(actor_shape, critic1_shape, critic2_shape).empty() || max_batch < 1 || max_batch > INT32_MAX)
+    return 0;
+  return sac_layout(net_dev(actor_shape).P, sac_pitch(actor_shape, critic1_shape, critic2_shape), max_batch).y.words * sizeof(float);
+}
+
+S2D_API int s2d_learn_sac_actor(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic1,
+                                const S2DLearnNet* critic2, const float* obs, float* alpha, const S2DLearnSacAlpha* alpha_state,
+                                uint64_t* draws, uint64_t seed, float* out_action, float* out_logp, float* out_q, void* stream) {
+  return learn_sac<true>("s2d_learn_sac_actor", batch, actor, actor_state, critic1, critic2, obs, alpha, alpha_state, draws, seed, out_action,
+                         out_logp, out_q, stream);
+}
+
+S2D_API int s2d_learn_sac_actor_grad(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic1,
+                                     const S2DLearnNet* critic2, const float* obs, float* alpha, const S2DLearnSacAlpha* alpha_state,
+                                     uint64_t* draws, uint64_t seed, float* out_action, float* out_logp, float* out_q, void* stream) {
+  return learn_sac<false>("s2d_learn_sac_actor_grad", batch, actor, actor_state, critic1, critic2, obs, alpha, alpha_state, draws, seed,
+                          out_action, out_logp, out_q, stream);
 }

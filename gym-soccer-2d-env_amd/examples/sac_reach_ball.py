@@ -15,7 +15,10 @@ sync() after every optimiser phase.  The first launches are the plain random rol
 terminal observations, so those launches store a Timeout as a termination.  0: one torch forward and one env.step per step.
 --fused-target computes reward + discount * (min Q'(s', a') - alpha logp(a')) in one launch (soccer2d_amd.td.SacTarget): the
 online actor's head draws a' with the kernel's own noise, alpha is read from a device word.
-The update itself is plain torch: the fused learner step is not part of this example yet.
+--fused-learner replaces the three torch optimiser steps and the Polyak loop by soccer2d_amd.learn.SACLearner: the critics' steps,
+the actor's reparameterised step through min(Q1, Q2) and the temperature's step in HIP, with the learner's own noise; with
+--fused-target the targets follow by SACLearner.update_targets and no sync() is needed inside the loop.  Without it the update is
+plain torch.
 """
 import argparse
 import copy
@@ -50,7 +53,7 @@ def mlp(n_in, n_out, net_arch=(64, 64)):
 
 class DeviceSAC:
     def __init__(self, env, lr=3e-4, gamma=0.99, tau=0.005, buffer=1 << 20, batch=4096, learning_starts=1, seed=0, net_arch=(64, 64),
-                 n_step=1, fused_target=False):
+                 n_step=1, fused_target=False, fused_learner=False):
         torch.manual_seed(seed)
         self.env, self.dev = env, env.device
         n_obs, self.n_act = env.observation_space.shape[0], env.action_space.shape[0]
@@ -63,6 +66,12 @@ class DeviceSAC:
         self.opt_pi = torch.optim.Adam(self.actor.parameters(), lr=lr)
         self.opt_q = torch.optim.Adam(list(self.q1.parameters()) + list(self.q2.parameters()), lr=lr)
         self.opt_alpha = torch.optim.Adam([self.log_alpha], lr=lr)
+        self.lrn = None
+        if fused_learner:                                   # the modules' parameters become views of the learner's buffers
+            from soccer2d_amd.learn import SACLearner
+            self.lrn = SACLearner.from_modules(self.actor, self.q1, self.q2, ent_coef='auto', target_entropy=self.target_entropy,
+                                               actor_lr=lr, critic_lr=lr, alpha_lr=lr, max_batch=batch, seed=seed, device=self.dev)
+            self.alpha, self.log_alpha = self.lrn.alpha, self.lrn.log_alpha
         self.gamma, self.tau, self.batch, self.learning_starts, self.launches = gamma, tau, batch, learning_starts, 0
         self.buffer, self.n_step, self.seed, self.fused_target = buffer, n_step, seed, fused_target
         self.stored, self.losses = 0, None
@@ -106,6 +115,18 @@ class DeviceSAC:
                     x = torch.cat([no, na], 1)
                     qn = torch.min(self.q1_target(x), self.q2_target(x)).squeeze(1)
                     tgt = r + disc * (qn - self.alpha * nlogp)
+            if self.lrn is not None:                             # critics, then actor and temperature, in HIP
+                self.lrn.step(b, tgt)
+                if self.fused_target:
+                    self.lrn.update_targets(self.td, self.tau)   # the Polyak step and the target's online actor: no sync()
+                else:
+                    with torch.no_grad():
+                        for net, tgt_net in ((self.q1, self.q1_target), (self.q2, self.q2_target)):
+                            for p, pt in zip(net.parameters(), tgt_net.parameters()):
+                                pt.mul_(1 - self.tau).add_(p, alpha=self.tau)
+                c1, c2 = self.lrn.critics
+                self.losses = (c1.stats[0] + c2.stats[0], self.lrn.actor.stats[0], self.lrn.alpha_stats[1])
+                continue
             x = torch.cat([o, a], 1)
             loss_q = 0.5 * (nn.functional.mse_loss(self.q1(x).squeeze(1), tgt) + nn.functional.mse_loss(self.q2(x).squeeze(1), tgt))
             self.opt_q.zero_grad(set_to_none=True)
@@ -199,6 +220,9 @@ def main():
                     help='collect T steps per launch with the in-kernel squashed-Gaussian actor (0: one torch forward per step)')
     ap.add_argument('--fused-target', action='store_true',
                     help='the entropy-regularised TD targets in one launch (soccer2d_amd.td.SacTarget)')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help='the critics\', the actor\'s and the temperature\'s steps in HIP (soccer2d_amd.learn.SACLearner: 1 to 4 hidden '
+                         'widths, multiples of 8 in [8, 256])')
     ap.add_argument('--net-arch', default='64,64', metavar='W1,W2,...',
                     help="the actor's hidden widths, e.g. 256,256 (1 to 5 multiples of 4 in [8, 400])")
     ap.add_argument('--n-step', type=int, default=1, metavar='K', help='K-step returns in the replay buffer')
@@ -207,7 +231,8 @@ def main():
     kw = dict(kewargs, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
-    model = DeviceSAC(env, batch=args.batch, net_arch=net_arch, n_step=args.n_step, fused_target=args.fused_target)
+    model = DeviceSAC(env, batch=args.batch, net_arch=net_arch, n_step=args.n_step, fused_target=args.fused_target,
+                      fused_learner=args.fused_learner)
     r0 = test(test_env, model, args.test_steps)
     print('untrained actor:', r0)
     r = r0

@@ -162,6 +162,13 @@ class S2DLearnPPO(C.Structure):
                 ('stats', C.c_void_p), ('error', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
+class S2DLearnSacAlpha(C.Structure):
+    """the temperature's state of s2d_learn_sac_actor: log_alpha [1], Adam's (m, v) [2], hyper [7] as S2DLearnState's, stats =
+    (mean logp, alpha loss, alpha after the call) and the target entropy"""
+    _fields_ = [('log_alpha', C.c_void_p), ('m_v', C.c_void_p), ('hyper', C.c_void_p), ('stats', C.c_void_p),
+                ('target_entropy', C.c_float)]
+
+
 class S2DLearnPPOBatch(C.Structure):
     """the rollout arrays of R rows and the minibatch of B rows that `index` (or NULL) names in them"""
     _fields_ = [('rows', C.c_int64), ('batch', C.c_int64), ('obs', C.c_void_p), ('action', C.c_void_p), ('logp_old', C.c_void_p),
@@ -254,6 +261,13 @@ PROTOTYPES = (
     ('s2d_learn_ppo_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.c_int32, C.c_int64)),
     ('s2d_learn_ppo', C.c_int, (C.POINTER(S2DLearnPPO), C.POINTER(S2DLearnPPOBatch), C.c_void_p)),
     ('s2d_learn_ppo_grad', C.c_int, (C.POINTER(S2DLearnPPO), C.POINTER(S2DLearnPPOBatch), C.c_void_p)),
+    ('s2d_learn_sac_actor', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.POINTER(S2DLearnNet),
+                                      C.POINTER(S2DLearnNet), C.c_void_p, C.c_void_p, C.POINTER(S2DLearnSacAlpha), C.c_void_p, C.c_uint64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_sac_actor_grad', C.c_int, (C.c_int64, C.POINTER(S2DLearnNet), C.POINTER(S2DLearnState), C.POINTER(S2DLearnNet),
+                                           C.POINTER(S2DLearnNet), C.c_void_p, C.c_void_p, C.POINTER(S2DLearnSacAlpha), C.c_void_p,
+                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_learn_sac_workspace_bytes', C.c_size_t, (C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.POINTER(S2DLearnNet), C.c_int64)),
     ('s2d_world_model', C.c_int, (C.c_void_p, C.POINTER(S2DWorldModel), C.c_void_p)),
     ('s2d_stats_reset', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_kernel_name', C.c_char_p, (C.c_void_p,)),

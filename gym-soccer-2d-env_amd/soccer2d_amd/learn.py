@@ -16,7 +16,11 @@ epsilon, the clip norm and Adam's running beta products are device words read wh
 torch's current stream, capturable, and ``set_lr`` between replays takes effect.
 
 ActorCriticLearner is the same for DDPG and TD3 (s2d_learn_critic / s2d_learn_actor): the critics' step on [obs | action] and the
-actor's step on -mean Q(obs, tanh-mu(obs)), whose gradient goes through the critic inside one kernel; tests/learn_ac_ref.c."""
+actor's step on -mean Q(obs, tanh-mu(obs)), whose gradient goes through the critic inside one kernel; tests/learn_ac_ref.c.
+
+SACLearner is Soft Actor-Critic's (s2d_learn_critic per critic, s2d_learn_sac_actor): the squashed-Gaussian actor's reparameterised
+step on mean(alpha * logp - min(Q1, Q2)(obs, a)) through the critic that gave each row's minimum, and the temperature's scalar Adam
+step; tests/learn_sac_ref.c."""
 import ctypes as C
 
 import torch
@@ -313,7 +317,46 @@ class _StepNet:
         self.hyper[5:7].fill_(1.0)
 
 
-class ActorCriticLearner:
+class _CriticSteps:
+    """what ActorCriticLearner and SACLearner share: the checks of a sampled batch and the critics' call (s2d_learn_critic or its
+    _grad twin, once per critic, the optional outputs from critic 1).  The class has ``critics`` (_StepNet), ``loss_kind``,
+    ``device``, ``obs_dim``, ``action_dim`` and ``max_batch``."""
+
+    def _obs(self, who, batch, keys):
+        if not isinstance(batch, dict) or any(k not in batch for k in keys):
+            raise ValueError(f'{who}: batch must be a dict with ' + ' and '.join(repr(k) for k in keys) + " (DeviceReplay.sample's)")
+        obs = batch['obs']
+        if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
+            raise ValueError(f"{who}: batch['obs'] must be a [B, {self.obs_dim}] tensor, B >= 1")
+        B = obs.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={self.max_batch}')
+        return B, _arr(who, self.device, "batch['obs']", obs, torch.float32, (B, self.obs_dim))
+
+    def _need_gpu(self, who):
+        if self.device.type != 'cuda':
+            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
+
+    def _critic_call(self, fn, name, batch, target, weight, td_abs_out, q_out):
+        who, f32 = f'{type(self).__name__}.{name}', torch.float32
+        B, obs = self._obs(who, batch, ('obs', 'action'))
+
+        def opt(what, t):
+            return _arr(who, self.device, what, t, f32, (B,)) if t is not None else None
+        ptrs = [_arr(who, self.device, "batch['action']", batch['action'], f32, (B, self.action_dim)),
+                _arr(who, self.device, 'target', target, f32, (B,)), opt('weight', weight)]
+        outs = [opt('td_abs_out', td_abs_out), opt('q_out', q_out)]
+        self._need_gpu(who)
+        lib = _capi.load_library()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for n, c in enumerate(self.critics):
+                net, st = c.c_structs(self.loss_kind)
+                rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), obs, self.action_dim, *ptrs, *(outs if n == 0 else (None, None)), stream)
+                _capi.check(lib, rc, fn)
+
+
+class ActorCriticLearner(_CriticSteps):
     """The DDPG / TD3 update in HIP (s2d_learn_critic / s2d_learn_actor in include/s2d.h), the steps that follow
     ActorCriticTarget.target:
 
@@ -366,39 +409,6 @@ class ActorCriticLearner:
                    max_batch=max_batch, device=device)
 
     # ------------------------------------------------------------------ the steps
-    def _obs(self, who, batch, keys):
-        if not isinstance(batch, dict) or any(k not in batch for k in keys):
-            raise ValueError(f'{who}: batch must be a dict with ' + ' and '.join(repr(k) for k in keys) + " (DeviceReplay.sample's)")
-        obs = batch['obs']
-        if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
-            raise ValueError(f"{who}: batch['obs'] must be a [B, {self.obs_dim}] tensor, B >= 1")
-        B = obs.shape[0]
-        if B > self.max_batch:
-            raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={self.max_batch}')
-        return B, _arr(who, self.device, "batch['obs']", obs, torch.float32, (B, self.obs_dim))
-
-    def _need_gpu(self, who):
-        if self.device.type != 'cuda':
-            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
-
-    def _critic_call(self, fn, name, batch, target, weight, td_abs_out, q_out):
-        who, f32 = f'ActorCriticLearner.{name}', torch.float32
-        B, obs = self._obs(who, batch, ('obs', 'action'))
-
-        def opt(what, t):
-            return _arr(who, self.device, what, t, f32, (B,)) if t is not None else None
-        ptrs = [_arr(who, self.device, "batch['action']", batch['action'], f32, (B, self.action_dim)),
-                _arr(who, self.device, 'target', target, f32, (B,)), opt('weight', weight)]
-        outs = [opt('td_abs_out', td_abs_out), opt('q_out', q_out)]
-        self._need_gpu(who)
-        lib = _capi.load_library()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for n, c in enumerate(self.critics):
-                net, st = c.c_structs(self.loss_kind)
-                rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), obs, self.action_dim, *ptrs, *(outs if n == 0 else (None, None)), stream)
-                _capi.check(lib, rc, fn)
-
     def _actor_call(self, fn, name, batch, action_out, q_out):
         who, f32 = f'ActorCriticLearner.{name}', torch.float32
         B, obs = self._obs(who, batch, ('obs',))
@@ -483,6 +493,213 @@ class ActorCriticLearner:
             raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
         for mine, net in pairs:
             mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
+
+
+def learn_sac_workspace_bytes(obs_dim, actor_hidden, action_dim, critic1_hidden, critic2_hidden, max_batch):
+    """bytes of the ACTOR's workspace for the SAC actor step (s2d_learn_sac_workspace_bytes): learn_actor_workspace_bytes' parts for
+    the actor's parameters (D -> ... -> 2A), a second row of block partials (the rows' logp), and the blocks' images where 64 rows of
+    ALL the networks ([obs | action] padded to a multiple of 4, every layer's outputs of the actor and of each critic, the head's A
+    noise words) and three words a row do not fit the LDS.  critic2_hidden: None for one critic."""
+    P = learn_param_count(obs_dim, actor_hidden, 2 * action_dim)
+    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
+    pitch = ((obs_dim + action_dim + 3) // 4 * 4 + sum(actor_hidden) + 2 * action_dim + sum(critic1_hidden) + 1
+             + (sum(critic2_hidden) + 1 if critic2_hidden is not None else 0) + action_dim) | 1
+    words = _round64(blocks * P) + _round64(chunks) + 2 * _round64(blocks)
+    if BLOCK_ROWS * (pitch + 3) * 4 > LDS_BYTES:
+        words += _round64(blocks * BLOCK_ROWS * pitch)
+    return words * 4
+
+
+class SACLearner(_CriticSteps):
+    """The Soft Actor-Critic update in HIP (s2d_learn_critic with the 'mse' loss per critic, s2d_learn_sac_actor in include/s2d.h),
+    the steps that follow SacTarget.target:
+
+        critics: loss = 0.5 * (mse(q1(cat(obs, action)), target) + mse(q2(...), target));  backward;  Adam.step()
+        actor:   a, logp = squashed-Gaussian head of actor(obs), reparameterised, with the kernel's own noise
+                 loss = (alpha * logp - min(q1, q2)(cat(obs, a))).mean();  backward through the critic that gave the minimum;  Adam.step()
+        alpha:   loss = -(log_alpha * (logp + target_entropy).mean());  Adam.step();  alpha = exp(log_alpha)
+
+    ``actor`` is ONE module Linear-(F-Linear) x L ending in Linear(h_L, 2A) (A means, then A raw log-std rows clamped to [-20, 2];
+    A = 1 .. 8), ``q1`` (and ``q2``) Linear-(F-Linear) x L from obs_dim + A inputs to one output -- the forms td.SacTarget and
+    wide_actor.SquashedGaussianActor take -- on the learner's grid (1 .. 4 hidden layers of multiples of 8 in [8, 256], ReLU / Tanh /
+    Sigmoid, obs_dim <= 248); the three may differ in hidden shape and activation.  SB3's default [256, 256] is on this grid; its
+    module triple (latent_pi, mu, log_std) is not taken.  Every network gets one flat fp32 buffer and its module's parameters are
+    rebound as views of it, as QLearner does.  The actor's step never forms or touches a critic's gradient.  ``alpha`` is the [1]
+    device tensor SacTarget.target takes; every step is a linear chain on torch's current stream, capturable; learning rates are
+    device words (``set_lr``).  tests/learn_sac_ref.c."""
+
+    def __init__(self, actor, q1, q2=None, ent_coef='auto', target_entropy=None, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4,
+                 betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, max_batch=4096, seed=0, device=None):
+        who = 'SACLearner'
+        if isinstance(actor, (tuple, list)):
+            raise ValueError(f'{who}: the actor must be ONE nn.Module ending in Linear(h_L, 2A); SB3\'s (latent_pi, mu, log_std) triple '
+                             'is not taken by the learner (stack mu and log_std into one Linear)')
+        if ent_coef != 'auto' and (isinstance(ent_coef, (str, bool)) or not isinstance(ent_coef, (int, float)) or not ent_coef >= 0.0
+                                   or ent_coef == float('inf')):
+            raise ValueError(f"{who}: ent_coef must be 'auto' or a finite float >= 0, got {ent_coef!r}")
+        if not (alpha_lr >= 0.0):
+            raise ValueError(f'{who}: alpha_lr must be >= 0, got {alpha_lr}')
+        b1, b2 = _check_optimiser(who, max_batch, min(actor_lr, critic_lr), betas, eps)
+        self.actor = _StepNet(who, 'actor', actor, device, False, actor_lr, b1, b2, eps, max_grad_norm)
+        dev = device if device is not None else self.actor.device
+        names = ('critic',) if q2 is None else ('critic 1', 'critic 2')
+        self.critics = tuple(_StepNet(who, n, mod, dev, False, critic_lr, b1, b2, eps, max_grad_norm) for n, mod in zip(names, (q1, q2)))
+        a = self.actor
+        if a.n_out % 2 or not 1 <= a.n_out // 2 <= MAX_ACTION:
+            raise ValueError(f'{who}: the actor has {a.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
+                             f'1 .. {MAX_ACTION}')
+        A = a.n_out // 2
+        if a.n_in > MAX_OBS:
+            raise ValueError(f'{who}: the actor\'s input width must be in [1, {MAX_OBS}], got {a.n_in}')
+        for c in self.critics:
+            if c.n_in != a.n_in + A or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {a.text()} it must take obs_dim + A = '
+                                 f'{a.n_in} + {A} inputs and give one output')
+            if c.device != a.device:
+                raise ValueError(f'{who}: the {c.what} is on {c.device}, the actor on {a.device}')
+        if target_entropy is not None and not isinstance(target_entropy, (int, float)):
+            raise ValueError(f'{who}: target_entropy must be a float (or None: -A), got {target_entropy!r}')
+        self.device, self.obs_dim, self.action_dim = a.device, a.n_in, A
+        self.loss_kind, self.max_batch = AC_LOSSES.index('mse'), max_batch
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.auto = ent_coef == 'auto'
+        self.target_entropy = float(-A if target_entropy is None else target_entropy)
+        f32 = torch.float32
+        self.alpha = torch.full((1,), 1.0 if self.auto else float(ent_coef), dtype=f32, device=self.device)
+        self.log_alpha = torch.zeros(1, dtype=f32, device=self.device) if self.auto else None
+        self.alpha_m_v = torch.zeros(2, dtype=f32, device=self.device)
+        self.alpha_hyper = torch.tensor([alpha_lr, b1, b2, eps, 0.0, 1.0, 1.0], dtype=f32).to(self.device)
+        self.alpha_stats = torch.tensor([0.0, 0.0, float(self.alpha[0])], dtype=f32).to(self.device)
+        self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)       # steps so far: the Philox counter's middle words
+        hc = [c.hidden for c in self.critics]
+        a.bind(learn_sac_workspace_bytes(a.n_in, a.hidden, A, hc[0], hc[1] if len(hc) > 1 else None, max_batch))
+        for c in self.critics:
+            c.bind(learn_workspace_bytes(c.n_in, c.hidden, 1, max_batch))
+
+    @classmethod
+    def from_modules(cls, actor, q1, q2=None, ent_coef='auto', target_entropy=None, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4,
+                     betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, max_batch=4096, seed=0, device=None):
+        """A learner of the modules with SB3 SAC's arguments: ent_coef 'auto' (log_alpha = 0, learned towards target_entropy, default
+        -A) or a float (fixed), torch.optim.Adam's arguments (one optimiser per network and one for log_alpha), clip_grad_norm_'s
+        max_grad_norm per network (<= 0, the default: no clip, as SB3), the largest batch a step will see and the seed of the actor
+        step's noise.  device: where the buffers, and from then on the modules' parameters, live (default: the actor's)."""
+        return cls(actor, q1, q2=q2, ent_coef=ent_coef, target_entropy=target_entropy, actor_lr=actor_lr, critic_lr=critic_lr,
+                   alpha_lr=alpha_lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, max_batch=max_batch, seed=seed, device=device)
+
+    # ------------------------------------------------------------------ the steps
+    def alpha_struct(self):
+        """the S2DLearnSacAlpha of a learned temperature, or None"""
+        if not self.auto:
+            return None
+        t = _capi.S2DLearnSacAlpha()
+        t.log_alpha, t.m_v, t.hyper, t.stats = (x.data_ptr() for x in (self.log_alpha, self.alpha_m_v, self.alpha_hyper, self.alpha_stats))
+        t.target_entropy = self.target_entropy
+        return t
+
+    def _actor_call(self, fn, name, batch, action_out, logp_out, q_out):
+        who, f32 = f'SACLearner.{name}', torch.float32
+        B, obs = self._obs(who, batch, ('obs',))
+        outs = [_arr(who, self.device, 'action_out', action_out, f32, (B, self.action_dim)) if action_out is not None else None,
+                _arr(who, self.device, 'logp_out', logp_out, f32, (B,)) if logp_out is not None else None,
+                _arr(who, self.device, 'q_out', q_out, f32, (B,)) if q_out is not None else None]
+        self._need_gpu(who)
+        lib = _capi.load_library()
+        net, st = self.actor.c_structs()
+        cs = [c.c_structs()[0] for c in self.critics]
+        t = self.alpha_struct()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), C.byref(cs[0]), C.byref(cs[1]) if len(cs) > 1 else None, obs,
+                                  C.c_void_p(self.alpha.data_ptr()), C.byref(t) if t is not None else None,
+                                  C.c_void_p(self.draws.data_ptr()), self.seed, *outs,
+                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, fn)
+
+    def step_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """One update of the critic (of both, where ``q2`` was given) with the loss e^2 / 2 on the dict DeviceReplay.sample returns
+        (its 'obs' [B, obs_dim] and 'action' float32 [B, A]) towards `target` float32 [B] (SacTarget.target's), with the importance
+        weights `weight` [B] where given.  td_abs_out [B] <- |q1 - target|, q_out [B] <- critic 1's forward values.  Stream-ordered
+        on torch's current stream, capturable; returns nothing."""
+        self._critic_call('s2d_learn_critic', 'step_critic', batch, target, weight, td_abs_out, q_out)
+
+    def step_actor(self, batch, action_out=None, logp_out=None, q_out=None):
+        """One update of the actor on (alpha * logp - min Q(obs, a)).mean() over batch['obs'] and, with ent_coef='auto', of log_alpha;
+        ``alpha`` then holds exp(log_alpha) and ``draws`` is one more.  action_out [B, A] <- the sampled actions, logp_out [B] <-
+        their log-probabilities, q_out [B] <- the smaller critic's values (all before the update)."""
+        self._actor_call('s2d_learn_sac_actor', 'step_actor', batch, action_out, logp_out, q_out)
+
+    def step(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """The critics' step, then the actor's (and the temperature's) through the UPDATED critics, as SB3 orders them; q_out is the
+        critic step's."""
+        self.step_critic(batch, target, weight=weight, td_abs_out=td_abs_out, q_out=q_out)
+        self.step_actor(batch)
+
+    def grad_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """The flat, unclipped gradient [P] of critic 1's loss (with ``q2`` the tuple of both critics'; views, written again by the
+        next call), with the critic's statistics set, without touching parameters or optimiser state."""
+        self._critic_call('s2d_learn_critic_grad', 'grad_critic', batch, target, weight, td_abs_out, q_out)
+        return self.critics[0].grad if len(self.critics) == 1 else tuple(c.grad for c in self.critics)
+
+    def grad_actor(self, batch, action_out=None, logp_out=None, q_out=None):
+        """The flat, unclipped gradient [P] of the actor's loss at the noise the next step will draw, with the actor's statistics,
+        ``entropy`` and ``alpha_loss`` set, without touching anything else (``draws`` included)."""
+        self._actor_call('s2d_learn_sac_actor_grad', 'grad_actor', batch, action_out, logp_out, q_out)
+        return self.actor.grad
+
+    # ------------------------------------------------------------------ state
+    critic_loss = property(lambda self: self.critics[0].stats.tolist()[0], doc="critic 1's last mean loss e^2 / 2 (synchronises)")
+    actor_loss = property(lambda self: self.actor.stats.tolist()[0], doc="the actor's last loss: mean(alpha logp - min q) (synchronises)")
+    actor_grad_norm = property(lambda self: self.actor.stats.tolist()[1], doc="the actor's last gradient norm before the clip")
+    actor_clip_scale = property(lambda self: self.actor.stats.tolist()[2], doc="the factor the actor's last gradient was scaled by")
+
+    def _alpha_stat(self, i):
+        if not self.auto:
+            raise ValueError('SACLearner: the entropy coefficient is fixed: the temperature has no statistics (ent_coef=\'auto\')')
+        return self.alpha_stats.tolist()[i]
+
+    entropy = property(lambda self: -self._alpha_stat(0), doc="minus the last actor call's mean logp (ent_coef='auto'; synchronises)")
+    alpha_loss = property(lambda self: self._alpha_stat(1), doc="the last actor call's log_alpha * -(mean logp + target_entropy)")
+    ent_coef = property(lambda self: float(self.alpha.item()), doc='the entropy coefficient now (synchronises)')
+
+    def set_lr(self, actor=None, critic=None, alpha=None):
+        """the learning rates of the steps enqueued from now on: device writes, also between the replays of a captured graph"""
+        if actor is not None:
+            self.actor.hyper[0:1].fill_(float(actor))
+        if critic is not None:
+            for c in self.critics:
+                c.hyper[0:1].fill_(float(critic))
+        if alpha is not None:
+            self.alpha_hyper[0:1].fill_(float(alpha))
+
+    def reset_optimizer(self):
+        """Adam as new for every network and for log_alpha: m = v = 0, both beta products 1"""
+        for n in (self.actor,) + self.critics:
+            n.reset()
+        self.alpha_m_v.zero_()
+        self.alpha_hyper[5:7].fill_(1.0)
+
+    def update_targets(self, sac_target, tau=1.0):
+        """The learner's weights into a td.SacTarget: the critics into its target critics, a hard copy (tau = 1) or a Polyak step,
+        one ``copy_`` or ``lerp_`` per critic from flat buffer to flat buffer with one more flat copy each that keeps the target
+        MODULES equal (as ActorCriticLearner.update_targets), and ONE flat ``copy_`` of the actor into the buffer the target reads its
+        ONLINE actor from.  Capturable: a loop that calls this needs no ``sac_target.sync()``."""
+        from .td import SacTarget
+        who = 'SACLearner.update_targets'
+        if not isinstance(sac_target, SacTarget):
+            raise ValueError(f'{who}: sac_target must be a td.SacTarget')
+        if len(sac_target.critics) != len(self.critics):
+            raise ValueError(f'{who}: the target has {len(sac_target.critics)} critic(s), the learner {len(self.critics)}')
+        pairs = list(zip((self.actor,) + self.critics, (sac_target.actor,) + sac_target.critics))
+        for mine, net in pairs:
+            if (net.n_in, net.hidden, net.n_out, net.activation) != (mine.n_in, mine.hidden, mine.n_out, mine.activation) \
+                    or net.device != mine.device:
+                raise ValueError(f'{who}: the {net.what} is {net.text()} ({net.activation}) on {net.device}, the learner\'s {mine.what} '
+                                 f'{mine.text()} ({mine.activation}) on {mine.device}')
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
+        for mine, net in pairs[1:]:
+            mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
+        with torch.no_grad():
+            sac_target.actor.params.copy_(self.actor.params)
 
 
 PPO_MAX_GROUPS = 256      # S2D_LEARN_PPO_MAX_GROUPS
@@ -682,5 +899,5 @@ class PPOLearner:
         self.hyper[5:7].fill_(1.0)
 
 
-__all__ = ['QLearner', 'ActorCriticLearner', 'PPOLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes',
-           'learn_ppo_workspace_bytes', 'learn_param_count']
+__all__ = ['QLearner', 'ActorCriticLearner', 'SACLearner', 'PPOLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes',
+           'learn_sac_workspace_bytes', 'learn_ppo_workspace_bytes', 'learn_param_count']

@@ -809,6 +809,76 @@ size_t s2d_learn_ppo_workspace_bytes(const S2DLearnNet *pi_shape, const S2DLearn
 int s2d_learn_ppo(const S2DLearnPPO *learner, const S2DLearnPPOBatch *batch, void *stream);
 /* The same up to and including grad, stats, out_logp and out_value, WITHOUT touching params, m, v or the beta products. */
 int s2d_learn_ppo_grad(const S2DLearnPPO *learner, const S2DLearnPPOBatch *batch, void *stream);
+/* ---- the Soft Actor-Critic update (s2d_learn.hip): the actor's step through min(Q1, Q2) and the temperature's step ----
+ * SAC's critic loss 0.5 * (mse(q1, t) + mse(q2, t)) is, per critic, s2d_learn_critic with S2D_LEARN_MSE (loss e^2 / 2, delta e / B),
+ * called once per critic: there is no SAC critic call.  s2d_learn_sac_actor is one step of the squashed-Gaussian actor on
+ * loss = mean_b (alpha * logp_b - min(Q1, Q2)(obs_b, a_b)), reparameterised, and (with alpha_state) one Adam step of log_alpha.
+ * Engine-independent like s2d_learn_q: no handle, raw device pointers, any stream of the current device, everything read WHEN THE
+ * KERNELS RUN; a linear chain of four launches on one stream (block kernel, reduce, finish, then ONE THREAD for the mean of logp,
+ * the temperature and the draw counter; the _grad twin with a fixed coefficient has nothing for it to do and stops at three), capturable, no float atomics, no result depends on the grid.  tests/learn_sac_ref.c
+ * restates every operation below.
+ *
+ * Networks, all on the learner's grid above: the actor D -> h... -> 2A (D in 1 .. 248, A in 1 .. 8: n_out even, in [2, 16]), each
+ * critic (D + A) -> h... -> 1; the three may differ in hidden shape and activation; critic2 may be NULL.  Of the critics only shape
+ * and params are read (READ-ONLY; workspace fields ignored): no critic dW or db is formed or written.  actor_state->loss_kind is
+ * ignored, its error word neither required nor written.
+ * Per row b (b the absolute row of the batch), every step one fp32 operation unless an fmaf is written:
+ *   forward, actor   y = actor(obs[b]) by s2d_learn_q's forward chain; mean_j = y[j], v_j = y[A + j]
+ *   head             the head of s2d_rollout_sac and s2d_td_target_sac, the same function, never deterministic: ls_j = v_j > 2 ? 2 :
+ *                    (v_j >= -20 ? v_j : -20) (a NaN gives -20); sigma_j = exp_spec(ls_j); u_j = fmaf(sigma_j, z_j, mean_j);
+ *                    a_j = tanh_spec(u_j); t_j = (fmaf(-0.5f * z_j, z_j, -ls_j) - 0.91893853f) - log_spec(fmaf(-a_j, a_j, 1.0f) + 1e-6f);
+ *                    logp = t_0 (+ t_1 ... in ascending j).  z from Philox4x32-10 with key `seed` at counter
+ *                    {b, draws_lo, draws_hi, (S2D_LEARN_SAC_STREAM << 16) | m}: m = 0 gives z0..z3, m = 1 (drawn only if A > 4) z4..z7,
+ *                    words x, y -> (z0, z1) and z, w -> (z2, z3) through the engine's Box-Muller, as in s2d_td_target_sac
+ *   forward, critics q_i = critic_i([obs[b] | a])[0]; q = q1, or with critic2 q2 < q1 ? q2 : q1 (a tie or a NaN q2 keeps critic 1)
+ *   row loss         l_b = (alpha * logp) - q: one multiply, then one subtract, never contracted
+ *   critic backward  only the CHOSEN critic's: output delta -1.0f / (float)B, s2d_learn_actor's delta chain down to the A action
+ *                    columns of its input: s_j = +0; k ascending over h_1: s_j = fmaf(W_1[k][D + j], delta_1[k], s_j).  (The kernel runs
+ *                    both critics' chains and takes the chosen one's words; the other's bits never reach a result.)
+ *   head backward    w = alpha / (float)B; om = fmaf(-a_j, a_j, 1.0f); r = om / (om + 1e-6f); du = ((w * (2.0f * a_j)) * r) + (s_j * om);
+ *                    dmean_j = du; dls = (du * (sigma_j * z_j)) - w; dv_j = (v_j >= -20.0f && v_j <= 2.0f) ? dls : +0 (torch's clamp,
+ *                    inclusive at both bounds; a NaN v gives +0); a saturated a_j = +-1 has om = 0, so du = 0 and dls = -w
+ *   actor backward   s2d_learn_q's spec with the 2A words [dmean | dv] as the output delta; the same block partials, norm, clip and Adam on
+ *                    actor_state
+ * actor_state->stats <- {(sum of l_b) / (float)B, norm, scale}; alpha_state->stats[0] <- (sum of logp_b) / (float)B; both sums per block
+ * of S2D_LEARN_BLOCK_ROWS rows s = +0, rows ascending s = s + x, then the blocks' sums added ascending (the first block starts the sum).
+ * Temperature (only with alpha_state): g = -(mean_logp + target_entropy); stats[1] = log_alpha * g (the pre-step log_alpha); its own
+ * beta products hyper[5] *= hyper[1], hyper[6] *= hyper[2], once; s2d_learn_q's Adam formula on the one word with scale 1 and m = m_v[0],
+ * v = m_v[1] (hyper[4] is ignored: one scalar is never clipped); *alpha = exp_spec(log_alpha_new), and stats[2] the same.  The actor's
+ * rows read *alpha BEFORE any of this; the next target launch reads the new value.  alpha_state NULL: a fixed entropy coefficient,
+ * *alpha is only read.
+ * The step then sets *draws += 1 (after its rows have read it), so a replayed graph draws fresh noise.
+ * out_action [B][A] <- a, out_logp [B] <- logp, out_q [B] <- q where given (all before the update).
+ * S2D_EINVAL without a launch and with nothing written, the text naming the field: all that s2d_learn_actor rejects (for both critics),
+ * plus the actor's n_out odd or outside [2, 16], NULL or misaligned alpha (4 bytes) or draws (8 bytes), NULL or misaligned members of a
+ * non-NULL alpha_state, and alpha, draws or alpha_state's arrays overlapping one another, the actor's params, m, v, grad or workspace,
+ * a critic's params or an output. */
+#define S2D_LEARN_SAC_STREAM 14 /* Philox stream id of the SAC actor step's action noise (no other draw uses it) */
+typedef struct S2DLearnSacAlpha {
+  float *log_alpha;        /* [1] READ-WRITE */
+  float *m_v;              /* [2] Adam's m and v of log_alpha */
+  float *hyper;            /* [7] as S2DLearnState.hyper; word 4 (max_grad_norm) ignored */
+  float *stats;            /* [3]: mean logp, alpha loss, alpha after the call */
+  float target_entropy;    /* SB3: -A */
+} S2DLearnSacAlpha;
+int s2d_learn_sac_actor(int64_t batch, const S2DLearnNet *actor /* n_out = 2A */, const S2DLearnState *actor_state,
+                        const S2DLearnNet *critic1 /* params only read */, const S2DLearnNet *critic2 /* the same, or NULL */,
+                        const float *obs /* [B][D] */, float *alpha /* [1]; READ, and with alpha_state WRITTEN after the step */,
+                        const S2DLearnSacAlpha *alpha_state /* or NULL */, uint64_t *draws, uint64_t seed,
+                        float *out_action /* [B][A] or NULL */, float *out_logp /* [B] or NULL */, float *out_q /* [B] or NULL */,
+                        void *stream);
+/* The same up to and including the actor's grad and stats, alpha_state->stats[0..1] and the optional outputs, WITHOUT touching the
+ * actor's params, m, v or beta products, log_alpha, m_v, the temperature's beta products, alpha_state->stats[2], *alpha or *draws: two
+ * calls in a row see the same noise. */
+int s2d_learn_sac_actor_grad(int64_t batch, const S2DLearnNet *actor, const S2DLearnState *actor_state, const S2DLearnNet *critic1,
+                             const S2DLearnNet *critic2, const float *obs, float *alpha, const S2DLearnSacAlpha *alpha_state,
+                             uint64_t *draws, uint64_t seed, float *out_action, float *out_logp, float *out_q, void *stream);
+/* bytes of the ACTOR's workspace for s2d_learn_sac_actor with these shapes (the pointers are not read; critic2_shape may be NULL) and
+ * batches up to max_batch: s2d_learn_actor_workspace_bytes' parts, a second row of block partials (the rows' logp) and, where 64 rows of
+ * all the networks and the head's words do not fit the LDS, the blocks' images.  0 for shapes off the grid or max_batch outside
+ * [1, 2^31 - 1].  Host only, needs no GPU. */
+size_t s2d_learn_sac_workspace_bytes(const S2DLearnNet *actor_shape, const S2DLearnNet *critic1_shape,
+                                     const S2DLearnNet *critic2_shape /* or NULL */, int64_t max_batch);
 /* fill derived protobuf-mirroring fields from the current state */
 int s2d_world_model(S2DHandle h, const S2DWorldModel *out, void *stream);
 /* zero the statistics counters */
