@@ -372,7 +372,7 @@ static int pen_over(const MP *p, int w) {
   const int nr = p->pen_nr_kicks;
   if (kl <= nr && kr <= nr) {                            /* the regular kicks: over as soon as one side cannot catch up */
     if (gl > gr + (nr - kr) || gr > gl + (nr - kl)) return 1;
-    if (kl == nr && kr == nr) return gl != gr || p->pen_max_extra_kicks <= 0;
+    if (kl == nr && kr == nr) return p->pen_max_extra_kicks <= 0;   /* (level: a lead was decided by the line above) */
     return 0;
   }
   if (kl == kr) return gl != gr || kl >= nr + p->pen_max_extra_kicks;   /* pairs of extra kicks */
@@ -484,7 +484,7 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
   if (foul_by >= 0) {                                      /* the victim goes down; a foul the referee saw is a card */
     Obj *v = &m->o[foul_victim];
     if (v->tackle < p->foul_cycles + 1) v->tackle = p->foul_cycles + 1;
-    if (foul_seen && m->o[foul_by].card < S2D_CARD_RED) m->o[foul_by].card += 1;
+    if (foul_seen) m->o[foul_by].card += 1;                /* (he tackled in this cycle: he had not been sent off) */
   }
   /* 2. ball: accelerations summed in player order */
   REAL bax = R(0.0), bay = R(0.0);
@@ -763,7 +763,7 @@ static void match_step(const MP *p, Match *m, uint64_t gid, const float *act, Ma
     } else if (pen) {
     } else if (advanced && m->cycle < total) {
       if (p->half_time_cycles > 0 && m->cycle % p->half_time_cycles == 0) period = m->cycle / p->half_time_cycles;
-    } else if (advanced && p->nr_extra_halfs > 0) {
+    } else if (advanced) {                               /* cycle >= total and not over: extra halves are being played */
       if ((m->cycle - total) % p->extra_half_cycles == 0) period = p->nr_normal_halfs + (m->cycle - total) / p->extra_half_cycles;
     }
     if (period >= 0) {

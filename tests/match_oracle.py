@@ -76,14 +76,8 @@ EV_KICK, EV_TACKLE, EV_CATCH, EV_COLLIDE, EV_BALL_COLLIDE, EV_GOAL = 1, 2, 4, 8,
 _libs = {}
 
 
-def lib(precision='f32'):
-    """the fp32 spec build ('f32': the kernels' parity target) or the fp64 libm build ('f64') of s2d_match_oracle.c"""
-    if precision in _libs:
-        return _libs[precision]
-    if precision not in ('f32', 'f64'):
-        raise ValueError(precision)
-    O.build_oracle()                       # rebuilds when s2d_match_oracle.c, the common header or the headers changed
-    L = C.CDLL(os.path.join(O.ORACLE_DIR, '_build', f'libs2d_match_oracle_{precision}.so'))
+def bind(L):
+    """the argument and result types of every s2dmo_* entry point of a loaded build of s2d_match_oracle.c"""
     cfgp = C.POINTER(M.S2DMatchConfig)
     L.s2dmo_create.argtypes = [cfgp, C.c_int64]; L.s2dmo_create.restype = C.c_void_p
     L.s2dmo_destroy.argtypes = [C.c_void_p]; L.s2dmo_destroy.restype = None
@@ -100,8 +94,24 @@ def lib(precision='f32'):
     L.s2dmo_load.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]; L.s2dmo_load.restype = C.c_int
     L.s2dmo_set_env_ids.argtypes = [C.c_void_p, C.c_void_p]; L.s2dmo_set_env_ids.restype = None
     L.s2dmo_events.argtypes = [C.c_void_p]; L.s2dmo_events.restype = C.POINTER(C.c_uint32)
-    _libs[precision] = L
     return L
+
+
+def lib(precision='f32'):
+    """the fp32 spec build ('f32': the kernels' parity target) or the fp64 libm build ('f64') of s2d_match_oracle.c"""
+    if precision in _libs:
+        return _libs[precision]
+    if precision not in ('f32', 'f64'):
+        raise ValueError(precision)
+    O.build_oracle()                       # rebuilds when s2d_match_oracle.c, the common header or the headers changed
+    _libs[precision] = bind(C.CDLL(os.path.join(O.ORACLE_DIR, '_build', f'libs2d_match_oracle_{precision}.so')))
+    return _libs[precision]
+
+
+def use_library(path, precision='f32'):
+    """serve another build of s2d_match_oracle.c (a coverage-instrumented one) as the `precision` oracle of this process"""
+    _libs[precision] = bind(C.CDLL(path))
+    return _libs[precision]
 
 
 class MatchOracle:

@@ -468,13 +468,11 @@ def test_illegal_defense():
     count starts again when the defenders play the ball or leave.  rcssserver's IllegalDefenseRef restated: parity unpinned."""
     from soccer2d_amd._capi_match import GM_FREE_KICK, GM_ILLEGAL_DEFENSE
     def scene(**kw):
-        m = fresh(auto_reset=0, announce_wait=3, **kw); play_on(m)
-        for i in range(22):                                             # everybody far from the ball and from both goal mouths
-            m.set_obj(0, i, x=(-20.0 if i < 11 else 20.0) - (i % 11), y=-25.0 + 2.0 * (i % 11), vx=0.0, vy=0.0)
-        for k, i in enumerate((1, 2, 3, 4)):                            # four left defenders inside their own strip
-            m.set_obj(0, i, x=-45.0 - k, y=-6.0 + 4.0 * k)
-        m.set_obj(0, 22, x=0.0, y=30.0, vx=0.0, vy=0.0)
-        m.set_game(0, last_touch_side=RIGHT)
+        import match_scenes as MS
+        m = fresh(auto_reset=0, announce_wait=3, **kw)
+        # play on; everybody far from the ball and from both goal mouths, but four left defenders inside their own strip; the right
+        # team was the last to play the ball
+        MS.apply_edits(m, MS.ILLEGAL_DEFENSE_SCENE)
         return m
     m = scene()                                                         # stock: the rule is off
     for _ in range(30):
@@ -767,11 +765,9 @@ def test_back_pass_to_the_goalie_is_an_indirect_free_kick():
 
 # ---- round 3: fouls and cards (Tackle.foul, idl/service.proto:399-402; FoulCharge_ :282) -- rcssserver's rule restated, parity unpinned
 def _foul_scene(**kw):
-    from soccer2d_amd._capi_match import GM_PLAY_ON
-    m = fresh(**kw); play_on(m)
-    m.set_obj(0, 5, x=0.0, y=0.0, body=0.0)                 # left #6 faces +x ...
-    m.set_obj(0, 15, x=1.0, y=0.2, body=180.0)              # ... a right player stands 1 m in front of him with the ball at his feet
-    m.set_obj(0, 22, x=0.7, y=0.1, vx=0.0, vy=0.0)
+    import match_scenes as MS
+    m = fresh(**kw)
+    MS.apply_edits(m, MS.FOUL_SCENE)                        # play on; left #6 faces +x, a right player 1 m in front of him, the ball at his feet
     return m
 
 
