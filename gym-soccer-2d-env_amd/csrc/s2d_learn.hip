@@ -44,6 +44,14 @@
 //                               *alpha and *draws += 1.  (The other choice, a flag on the finish kernel as PPO took, would have
 //                               changed that kernel's text; this way its existing instantiations are the ones the other learners run.)
 // and runs the reduce and finish kernels as the DDPG actor step does, so the call stays a linear chain on one stream.
+//
+// The host path is one for the four learners.  layout() places every workspace from the stepped parameter count, the image's pitch,
+// the words a row keeps beside the image, the rows of partials and the learner's extra parts.  An entry point reads what it steps
+// into a Stepped view (from S2DLearnNet + S2DLearnState, or from S2DLearnPPO), on which buffers_error checks the pointers and
+// layout_error the workspace's size and, through a Spans list, the overlaps; pair_error checks an actor with its critic(s).
+// launch_block picks the block kernel's instantiation, sizes its LDS, takes the 48 KiB attribute step and launches;
+// reduce_and_finish enqueues the two kernels behind it.  The order of the checks is the order of the refusals, which
+// tests/test_learn_refusals_host.py pins sentence by sentence.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -969,6 +977,8 @@ __global__ __launch_bounds__(kLearnThreads) void s2d_learn_finish_kernel(int P, 
 namespace {
 struct LearnLds {};   // the owner of the block kernels' dynamic-LDS slots (allow_lds_slot: 0 Q, 1 critic, 2 actor, 3 PPO, 4 SAC); fail, misaligned and launched are s2d_wide_host.h's
 
+bool in_range(int64_t n) { return n >= 1 && n <= INT32_MAX; }   // a batch, a max_batch, the rows of a rollout
+const char* const kBatchText = "batch must be in [1, 2^31 - 1]";
 // "" if the shape is on the learner's grid, else the text naming the field
 std::string shape_error(const S2DLearnNet* n) {
   if (n->n_in < 1 || n->n_in > 256) return "n_in must be in [1, 256]";
@@ -979,6 +989,18 @@ std::string shape_error(const S2DLearnNet* n) {
   }
   if (n->n_out < 1 || n->n_out > 64) return "n_out must be in [1, 64]";
   if (n->activation < 0 || n->activation > 2) return "activation must be 0 (ReLU), 1 (Tanh) or 2 (Sigmoid)";
+  return "";
+}
+// the first shape_error of the networks of a call (a NULL one is skipped), behind its name and ": "
+struct NamedNet {
+  const char* name;
+  const S2DLearnNet* net;
+};
+std::string shapes_error(std::initializer_list<NamedNet> nets) {
+  for (const NamedNet& n : nets) {
+    const std::string bad = n.net ? shape_error(n.net) : "";
+    if (!bad.empty()) return std::string(n.name) + ": " + bad;
+  }
   return "";
 }
 LearnDev net_dev(const S2DLearnNet* n) {
@@ -995,91 +1017,162 @@ LearnDev net_dev(const S2DLearnNet* n) {
   d.pitch = row | 1;                                  // odd: lanes that read one column of 64 rows hit 64 different banks
   return d;
 }
-// the workspace of a shape and a batch, in words: [partials: blocks x P | chunk sums | loss partials | images, if not in LDS]
+// the workspace in words: [partials: rows x P | chunk sums | loss partials: rows x loss_words | the learner's extra parts | images,
+// if not in LDS], every part rounded up to 64 words.  P parameters are stepped; `rows` is the batch's blocks, or PPO's groups
 struct LearnLayout {
-  size_t part, chunk, loss, image, words;
-  bool lds;
+  size_t part, chunk, loss, extra[2], image, words;
+  bool lds;   // 64 rows of `pitch` words of the image and of the row_words beside it fit the LDS
 };
 size_t round64(size_t w) { return (w + 63) & ~(size_t)63; }
-// P parameters of the network that is stepped, rows of `pitch` words in a block's image
-LearnLayout layout(int P, int pitch, int64_t batch) {
+int64_t blocks_of(int64_t batch) { return (batch + kLearnRows - 1) / kLearnRows; }
+LearnLayout layout(int P, int pitch, int row_words, size_t rows, size_t loss_words, size_t extra0 = 0, size_t extra1 = 0) {
   LearnLayout y{};
-  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
-  y.lds = (size_t)kLearnRows * (pitch + 1) * sizeof(float) <= kLdsMax;
+  const size_t chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
+  y.lds = (size_t)kLearnRows * (pitch + row_words) * sizeof(float) <= kLdsMax;
   y.part = 0;
-  y.chunk = round64(blocks * P);
+  y.chunk = round64(rows * P);
   y.loss = y.chunk + round64(chunks);
-  y.image = y.loss + round64(blocks);
-  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * pitch));
+  y.extra[0] = y.loss + round64(rows * loss_words);
+  y.extra[1] = y.extra[0] + round64(extra0);
+  y.image = y.extra[1] + round64(extra1);
+  y.words = y.image + (y.lds ? 0 : round64(rows * kLearnRows * pitch));
   return y;
 }
-// the actor step's row holds both networks: the critic's padded input row, then each network's layer outputs
-int layer_words(const S2DLearnNet* n) {
-  int w = n->n_out;
-  for (int l = 0; l < n->n_hidden; ++l) w += n->hidden[l];
+// the Q, critic and DDPG actor steps: a loss word per block
+LearnLayout block_layout(int P, int pitch, int64_t batch) { return layout(P, pitch, 1, (size_t)blocks_of(batch), 1); }
+// the words of an image's row up to the last network's outputs: the padded input row, then each network's layers (none of a NULL one)
+int row_words(int n_in, std::initializer_list<const S2DLearnNet*> nets) {
+  int w = (n_in + 3) / 4 * 4;
+  for (const S2DLearnNet* n : nets)
+    for (int l = 0; n && l <= n->n_hidden; ++l) w += l < n->n_hidden ? n->hidden[l] : n->n_out;
   return w;
 }
-int pair_pitch(const S2DLearnNet* a, const S2DLearnNet* c) { return ((c->n_in + 3) / 4 * 4 + layer_words(a) + layer_words(c)) | 1; }
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p < q + nb && q < p + na;
-}
-// "" if the actor / critic pair is on the grid of s2d_learn_actor
-std::string pair_error(const S2DLearnNet* actor, const S2DLearnNet* critic) {
-  std::string bad = shape_error(actor);
-  if (!bad.empty()) return "actor: " + bad;
-  bad = shape_error(critic);
-  if (!bad.empty()) return "critic: " + bad;
-  if (actor->n_out > kLearnMaxAction) return "actor: n_out (the action width) must be in [1, 8]";
+int pair_pitch(const S2DLearnNet* a, const S2DLearnNet* c) { return row_words(c->n_in, {a, c}) | 1; }
+// "" if an actor with A actions and its critic(s) on n_in + A inputs, one output, are on the grid: s2d_learn_actor's pair (A = n_out,
+// one critic) or s2d_learn_sac_actor's (sac: A = n_out / 2, critic2 may be NULL)
+std::string pair_error(const S2DLearnNet* actor, bool sac, const S2DLearnNet* critic1, const S2DLearnNet* critic2) {
+  const NamedNet critics[2] = {{sac ? "critic1" : "critic", critic1}, {"critic2", critic2}};
+  const std::string bad = shapes_error({{"actor", actor}, critics[0], critics[1]});
+  if (!bad.empty()) return bad;
+  const int A = sac ? actor->n_out / 2 : actor->n_out;
+  if (A < 1 || A > kLearnMaxAction || (sac && actor->n_out % 2))
+    return sac ? "actor: n_out (means, then raw log-std) must be even and in [2, 16]" : "actor: n_out (the action width) must be in [1, 8]";
   if (actor->n_in > kLearnMaxObs) return "actor: n_in must be in [1, 248]";
-  if (critic->n_in != actor->n_in + actor->n_out || critic->n_out != 1) return "critic: n_in must be the actor's n_in + n_out, its n_out 1";
+  for (const NamedNet& c : critics)
+    if (c.net && (c.net->n_in != actor->n_in + A || c.net->n_out != 1))
+      return std::string(c.name) + ": n_in must be the actor's n_in + n_out" + (sac ? " / 2" : "") + ", its n_out 1";
   return "";
 }
-// the pointers of a network that is stepped and of its state; "" if acceptable
+// what a call steps and how its refusals name it: filled from (S2DLearnNet, S2DLearnState) or from S2DLearnPPO
+struct Stepped {
+  const char *net, *state;   // "net: " / "actor: " and "state: ", or "" twice for PPO's one struct
+  float *params, *m, *v, *grad, *hyper, *stats;
+  int32_t* error;
+  bool error_word;           // the call has one (the actor steps have not)
+  void* workspace;
+  size_t workspace_bytes;
+};
+Stepped stepped(const char* name, const S2DLearnNet* n, const S2DLearnState* st, bool error_word) {
+  return Stepped{name, "state: ", n->params, st->m, st->v, st->grad, st->hyper, st->stats, st->error, error_word, n->workspace, n->workspace_bytes};
+}
+Stepped stepped(const S2DLearnPPO* q) {
+  return Stepped{"", "", q->params, q->m, q->v, q->grad, q->hyper, q->stats, q->error, true, q->workspace, q->workspace_bytes};
+}
+// "" or the refusal of a parameter pointer, the stepped network's or a critic's that is only read (`net`: "critic: ", ...)
+std::string params_error(const char* net, const float* params) {
+  if (params && !misaligned(params, 16)) return "";
+  return std::string(net) + "params must be a non-NULL, 16-byte aligned device pointer";
+}
+// the pointers of what is stepped; "" if acceptable
 template <bool UPDATE>
-std::string buffers_error(const char* name, const S2DLearnNet* net, const S2DLearnState* st, bool error_word) {
-  const std::string nm = name;
-  if (!net->params || misaligned(net->params, 16)) return nm + ": params must be a non-NULL, 16-byte aligned device pointer";
-  if (!net->workspace || misaligned(net->workspace, 256)) return nm + ": workspace must be a non-NULL, 256-byte aligned device pointer";
-  if (!st->grad || misaligned(st->grad, 16) || !st->hyper || misaligned(st->hyper, 4) || !st->stats || misaligned(st->stats, 4) ||
-      (error_word && (!st->error || misaligned(st->error, 4))))
-    return std::string("state: grad (16 bytes), hyper, stats") + (error_word ? " and error" : "") +
+std::string buffers_error(const Stepped& b) {
+  const std::string bad = params_error(b.net, b.params);
+  if (!bad.empty()) return bad;
+  if (!b.workspace || misaligned(b.workspace, 256)) return std::string(b.net) + "workspace must be a non-NULL, 256-byte aligned device pointer";
+  if (!b.grad || misaligned(b.grad, 16) || !b.hyper || misaligned(b.hyper, 4) || !b.stats || misaligned(b.stats, 4) ||
+      (b.error_word && (!b.error || misaligned(b.error, 4))))
+    return std::string(b.state) + "grad (16 bytes), hyper, stats" + (b.error_word ? " and error" : "") +
            " (4 bytes) must be non-NULL, aligned device pointers";
-  if (UPDATE && (!st->m || !st->v || misaligned(st->m, 16) || misaligned(st->v, 16)))
-    return "state: m and v must be non-NULL, 16-byte aligned device pointers";
+  if (UPDATE && (!b.m || !b.v || misaligned(b.m, 16) || misaligned(b.v, 16)))
+    return std::string(b.state) + "m and v must be non-NULL, 16-byte aligned device pointers";
   return "";
 }
-// the workspace's size and the overlaps of what a call writes (and, for the actor step, the critic's parameters it reads)
+// what the two actor steps check alike, in their order: the pair, the batch, the actor's buffers, the critics' parameters, obs
 template <bool UPDATE>
-std::string layout_error(const char* name, const S2DLearnNet* net, const S2DLearnState* st, const LearnLayout& y, int P, int64_t batch,
-                         const char* bytes_fn, const float* read_only, size_t read_only_bytes) {
-  if (net->workspace_bytes < y.words * sizeof(float))
-    return std::string(name) + ": workspace_bytes is " + std::to_string(net->workspace_bytes) + ", a batch of " + std::to_string(batch) +
+std::string actor_error(const Stepped& b, int64_t batch, const S2DLearnNet* actor, bool sac, const S2DLearnNet* critic1,
+                        const S2DLearnNet* critic2, const float* obs) {
+  std::string err = pair_error(actor, sac, critic1, critic2);
+  if (err.empty() && !in_range(batch)) err = kBatchText;
+  if (err.empty()) err = buffers_error<UPDATE>(b);
+  if (err.empty()) err = params_error(sac ? "critic1: " : "critic: ", critic1->params);
+  if (err.empty() && critic2) err = params_error("critic2: ", critic2->params);
+  if (err.empty() && (!obs || misaligned(obs, 4))) err = "obs must be a non-NULL, 4-byte aligned device pointer";
+  return err;
+}
+// The device arrays of a call that must not overlap.  An array of group 0 must overlap nothing behind it in the list; arrays of
+// another group are checked against those of group 0 alone.  NULL arrays are skipped
+struct Spans {
+  uintptr_t p[16];
+  size_t bytes[16];
+  int group[16], n = 0;
+  Spans& add(const void* q, size_t b, int g = 0) {
+    p[n] = reinterpret_cast<uintptr_t>(q), bytes[n] = b, group[n++] = g;
+    return *this;
+  }
+  // what a call writes of the stepped network: params, grad, the workspace and (UPDATE) m and v
+  template <bool UPDATE>
+  Spans& add_stepped(const Stepped& b, int P, const LearnLayout& y, int g = 0) {
+    const size_t pb = (size_t)P * sizeof(float);
+    return add(b.params, pb, g).add(b.grad, pb, g).add(b.workspace, y.words * sizeof(float), g).add(UPDATE ? b.m : nullptr, pb, g)
+        .add(UPDATE ? b.v : nullptr, pb, g);
+  }
+  // -1, or the group of the later array of the first pair that overlaps: the list's order, the earlier array counting first
+  int clash() const {
+    for (int i = 0; i < n; ++i)
+      for (int j = i + 1; p[i] && group[i] == 0 && j < n; ++j)
+        if (p[j] && p[i] < p[j] + bytes[j] && p[j] < p[i] + bytes[i]) return group[j];
+    return -1;
+  }
+};
+const char* const kActorOverlapText = "the actor's params, m, v, grad and workspace must not overlap one another or the critic's params";
+// the workspace's size and the overlaps of what a call writes (and, for the actor steps, the first critic's parameters it reads)
+template <bool UPDATE>
+std::string layout_error(const Stepped& b, const LearnLayout& y, int P, int64_t batch, const char* bytes_fn, const float* read_only = nullptr,
+                         size_t read_only_bytes = 0) {
+  if (b.workspace_bytes < y.words * sizeof(float))
+    return std::string(b.net) + "workspace_bytes is " + std::to_string(b.workspace_bytes) + ", a batch of " + std::to_string(batch) +
            " needs " + std::to_string(y.words * sizeof(float)) + " (" + bytes_fn + ": batch is above the workspace's max_batch)";
-  const size_t pb = (size_t)P * sizeof(float);
-  const void* bufs[6] = {net->params, st->grad, net->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr, read_only};
-  const size_t lens[6] = {pb, pb, y.words * sizeof(float), pb, pb, read_only_bytes};
-  for (int i = 0; i < 6; ++i)
-    for (int j = i + 1; j < 6; ++j)
-      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
-        return read_only ? "the actor's params, m, v, grad and workspace must not overlap one another or the critic's params"
-                         : "params, m, v, grad and the workspace must not overlap one another";
+  if (Spans().add_stepped<UPDATE>(b, P, y).add(read_only, read_only_bytes).clash() >= 0)
+    return read_only ? kActorOverlapText : "params, m, v, grad and the workspace must not overlap one another";
   return "";
 }
-// what follows the block kernel: the reduction over the blocks, then norm, clip, stats and (UPDATE) Adam
-template <bool UPDATE>
-void reduce_and_finish(int P, int64_t batch, bool negate, const LearnLayout& y, const S2DLearnNet* net, const S2DLearnState* st, hipStream_t s) {
-  float* const ws = static_cast<float*>(net->workspace);
-  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
-  const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
-  hipLaunchKernelGGL(s2d_learn_reduce_kernel<UPDATE>, dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, blocks, ws + y.part, st->grad,
-                     ws + y.chunk, st->hyper, P);
-  hipLaunchKernelGGL(s2d_learn_finish_kernel<UPDATE>, dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, batch, blocks,
-                     chunks, negate, ws + y.chunk, ws + y.loss, st->grad, st->hyper, st->stats, net->params, st->m, st->v);
+// A learner's block kernel on `grid` workgroups: the instantiation for where the image lives, its dynamic LDS (64 rows of `beside`
+// words, then the image if it lives there), above 48 KiB the attribute step under the kernel's `slot` of LearnLds, before() (what
+// the call enqueues ahead of the kernel) and the launch.  S2D_OK, or S2D_EHIP with the text set and nothing enqueued
+template <typename... Params, typename Before, typename... Args>
+int launch_block(const std::string& who, void (*in_lds)(Params...), void (*in_workspace)(Params...), int slot, const LearnLayout& y, int beside,
+                 int pitch, int64_t grid, hipStream_t s, Before before, Args... args) {
+  const auto kb = y.lds ? in_lds : in_workspace;
+  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + beside) * sizeof(float);
+  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), slot)) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  before();
+  hipLaunchKernelGGL(kb, dim3((unsigned)grid), dim3(kLearnThreads), lds, s, args...);
+  return S2D_OK;
 }
-int no_lds(const std::string& who) {
-  s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
-  return S2D_EHIP;
+const auto nothing_before = [] {};
+// what follows the block kernel: the reduction over the `rows` rows of partials, then norm, clip, stats and (UPDATE) Adam.
+// PPO: the words from ent_from on are log_std's, and the loss partials are the groups' statistics; else ent_from = P
+template <bool UPDATE, bool PPO = false>
+void reduce_and_finish(const Stepped& b, int P, int64_t batch, int64_t rows, int ent_from, bool negate, const LearnLayout& y, hipStream_t s) {
+  float* const ws = static_cast<float*>(b.workspace);
+  const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
+  hipLaunchKernelGGL((s2d_learn_reduce_kernel<UPDATE, PPO>), dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, rows, ws + y.part, b.grad,
+                     ws + y.chunk, b.hyper, ent_from);
+  hipLaunchKernelGGL((s2d_learn_finish_kernel<UPDATE, PPO>), dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, batch, rows,
+                     chunks, negate, ws + y.chunk, ws + y.loss, b.grad, b.hyper, b.stats, b.params, b.m, b.v);
 }
 
 // s2d_learn_q[_grad] (CRITIC = false: action is int32 [B]) and s2d_learn_critic[_grad] (CRITIC = true: action is float [B][A])
@@ -1087,8 +1180,8 @@ template <bool UPDATE, bool CRITIC>
 int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S2DLearnState* st, const float* obs, int A, const void* action,
           const float* target, const float* weight, float* out_td_abs, float* out_q, void* stream) {
   if (!net || !st) return fail(who, "net and state must be non-NULL");
-  const std::string bad = shape_error(net);
-  if (!bad.empty()) return fail(who, "net: " + bad);
+  std::string err = shapes_error({{"net", net}});
+  if (!err.empty()) return fail(who, err);
   if (CRITIC) {
     if (A < 1 || A > kLearnMaxAction) return fail(who, "action_dim must be in [1, 8]");
     if (net->n_out != 1) return fail(who, "net: n_out must be 1 (a critic)");
@@ -1099,33 +1192,30 @@ int learn(const std::string& who, int64_t batch, const S2DLearnNet* net, const S
   } else if (st->loss_kind != S2D_LEARN_MSE && st->loss_kind != S2D_LEARN_HUBER) {
     return fail(who, "state: loss_kind must be 0 (MSE) or 1 (Huber)");
   }
-  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
-  std::string err = buffers_error<UPDATE>("net", net, st, true);
+  if (!in_range(batch)) return fail(who, kBatchText);
+  const Stepped b = stepped("net: ", net, st, true);
+  err = buffers_error<UPDATE>(b);
   if (!err.empty()) return fail(who, err);
   if (!obs || !action || !target || misaligned(obs, 4) || misaligned(action, 4) || misaligned(target, 4))
     return fail(who, "obs, action and target must be non-NULL, 4-byte aligned device pointers");
   if (misaligned(weight, 4) || misaligned(out_td_abs, 4) || misaligned(out_q, 4))
     return fail(who, "weight, out_td_abs and out_q must be 4-byte aligned device pointers (or NULL)");
   const LearnDev d = net_dev(net);
-  const LearnLayout y = layout(d.P, d.pitch, batch);
-  err = layout_error<UPDATE>("net", net, st, y, d.P, batch, "s2d_learn_workspace_bytes", nullptr, 0);
+  const LearnLayout y = block_layout(d.P, d.pitch, batch);
+  err = layout_error<UPDATE>(b, y, d.P, batch, "s2d_learn_workspace_bytes");
   if (!err.empty()) return fail(who, err);
-  const size_t lds = (size_t)kLearnRows * ((y.lds ? d.pitch : 0) + 1) * sizeof(float);
   float* const ws = static_cast<float*>(net->workspace);
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((batch + kLearnRows - 1) / kLearnRows));
-  if (CRITIC) {
-    const auto kb = y.lds ? s2d_learn_critic_kernel<true> : s2d_learn_critic_kernel<false>;
-    if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 1)) return no_lds(who);
-    hipLaunchKernelGGL(kb, grid, dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image,
-                       obs, net->n_in - A, static_cast<const float*>(action), target, weight, out_td_abs, out_q);
-  } else {
-    const auto kb = y.lds ? s2d_learn_block_kernel<true> : s2d_learn_block_kernel<false>;
-    if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 0)) return no_lds(who);
-    hipLaunchKernelGGL(kb, grid, dim3(kLearnThreads), lds, s, d, batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image,
-                       obs, static_cast<const int32_t*>(action), target, weight, out_td_abs, out_q, st->error);
-  }
-  reduce_and_finish<UPDATE>(d.P, batch, false, y, net, st, s);
+  const int64_t blocks = blocks_of(batch);
+  const int rc =
+      CRITIC ? launch_block(who, s2d_learn_critic_kernel<true>, s2d_learn_critic_kernel<false>, 1, y, 1, d.pitch, blocks, s, nothing_before, d,
+                            batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image, obs, net->n_in - A,
+                            static_cast<const float*>(action), target, weight, out_td_abs, out_q)
+             : launch_block(who, s2d_learn_block_kernel<true>, s2d_learn_block_kernel<false>, 0, y, 1, d.pitch, blocks, s, nothing_before, d,
+                            batch, (int)st->loss_kind, net->params, ws + y.part, ws + y.loss, ws + y.image, obs,
+                            static_cast<const int32_t*>(action), target, weight, out_td_abs, out_q, st->error);
+  if (rc != S2D_OK) return rc;
+  reduce_and_finish<UPDATE>(b, d.P, batch, blocks, d.P, false, y, s);
   return launched(who);
 }
 
@@ -1133,70 +1223,32 @@ template <bool UPDATE>
 int learn_actor(const std::string& who, int64_t batch, const S2DLearnNet* actor, const S2DLearnState* st, const S2DLearnNet* critic,
                 const float* obs, float* out_action, float* out_q, void* stream) {
   if (!actor || !st || !critic) return fail(who, "actor, state and critic must be non-NULL");
-  std::string err = pair_error(actor, critic);
+  const Stepped b = stepped("actor: ", actor, st, false);
+  std::string err = actor_error<UPDATE>(b, batch, actor, false, critic, nullptr, obs);
   if (!err.empty()) return fail(who, err);
-  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
-  err = buffers_error<UPDATE>("actor", actor, st, false);
-  if (!err.empty()) return fail(who, err);
-  if (!critic->params || misaligned(critic->params, 16)) return fail(who, "critic: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!obs || misaligned(obs, 4)) return fail(who, "obs must be a non-NULL, 4-byte aligned device pointer");
   if (misaligned(out_action, 4) || misaligned(out_q, 4)) return fail(who, "out_action and out_q must be 4-byte aligned device pointers (or NULL)");
   const LearnDev a = net_dev(actor), c = net_dev(critic);
   const int pitch = pair_pitch(actor, critic);
-  const LearnLayout y = layout(a.P, pitch, batch);
-  err = layout_error<UPDATE>("actor", actor, st, y, a.P, batch, "s2d_learn_actor_workspace_bytes", critic->params, (size_t)c.P * sizeof(float));
+  const LearnLayout y = block_layout(a.P, pitch, batch);
+  err = layout_error<UPDATE>(b, y, a.P, batch, "s2d_learn_actor_workspace_bytes", critic->params, (size_t)c.P * sizeof(float));
   if (!err.empty()) return fail(who, err);
-  const auto kb = y.lds ? s2d_learn_actor_kernel<true> : s2d_learn_actor_kernel<false>;
-  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + 1) * sizeof(float);
-  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 2)) return no_lds(who);
   float* const ws = static_cast<float*>(actor->workspace);
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(kb, dim3((unsigned)((batch + kLearnRows - 1) / kLearnRows)), dim3(kLearnThreads), lds, s, a, c, pitch, batch, actor->params,
-                     critic->params, ws + y.part, ws + y.loss, ws + y.image, obs, out_action, out_q);
-  reduce_and_finish<UPDATE>(a.P, batch, true, y, actor, st, s);
+  const int64_t blocks = blocks_of(batch);
+  if (const int rc = launch_block(who, s2d_learn_actor_kernel<true>, s2d_learn_actor_kernel<false>, 2, y, 1, pitch, blocks, s, nothing_before, a, c,
+                                  pitch, batch, actor->params, critic->params, ws + y.part, ws + y.loss, ws + y.image, obs, out_action, out_q))
+    return rc;
+  reduce_and_finish<UPDATE>(b, a.P, batch, blocks, a.P, true, y, s);
   return launched(who);
 }
 // ---- SAC
-// "" if the actor and its critic(s) are on the grid of s2d_learn_sac_actor: s2d_learn_actor's with A = n_out / 2
-std::string sac_error(const S2DLearnNet* actor, const S2DLearnNet* critic1, const S2DLearnNet* critic2) {
-  std::string bad = shape_error(actor);
-  if (!bad.empty()) return "actor: " + bad;
-  const S2DLearnNet* const cs[2] = {critic1, critic2};
-  for (int i = 0; i < 2; ++i)
-    if (cs[i]) {
-      bad = shape_error(cs[i]);
-      if (!bad.empty()) return std::string(i ? "critic2: " : "critic1: ") + bad;
-    }
-  if (actor->n_out % 2 || actor->n_out < 2 || actor->n_out > 2 * kLearnMaxAction)
-    return "actor: n_out (means, then raw log-std) must be even and in [2, 16]";
-  if (actor->n_in > kLearnMaxObs) return "actor: n_in must be in [1, 248]";
-  for (int i = 0; i < 2; ++i)
-    if (cs[i] && (cs[i]->n_in != actor->n_in + actor->n_out / 2 || cs[i]->n_out != 1))
-      return std::string(i ? "critic2" : "critic1") + ": n_in must be the actor's n_in + n_out / 2, its n_out 1";
-  return "";
-}
 // the column of the head's z words, behind every network's layers; the row has A more words
-int sac_z_off(const S2DLearnNet* a, const S2DLearnNet* c1, const S2DLearnNet* c2) {
-  return (c1->n_in + 3) / 4 * 4 + layer_words(a) + layer_words(c1) + (c2 ? layer_words(c2) : 0);
-}
+int sac_z_off(const S2DLearnNet* a, const S2DLearnNet* c1, const S2DLearnNet* c2) { return row_words(c1->n_in, {a, c1, c2}); }
 int sac_pitch(const S2DLearnNet* a, const S2DLearnNet* c1, const S2DLearnNet* c2) { return (sac_z_off(a, c1, c2) + a->n_out / 2) | 1; }
-// the actor's workspace in words: [partials: blocks x P | chunk sums | loss partials | logp partials | images, if not in LDS]
-struct SacLayout {
-  LearnLayout y;
-  size_t logp;
-};
-SacLayout sac_layout(int P, int pitch, int64_t batch) {
-  SacLayout q{};
-  LearnLayout& y = q.y;
-  const size_t blocks = (size_t)((batch + kLearnRows - 1) / kLearnRows), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
-  y.lds = (size_t)kLearnRows * (pitch + kSacRowWords) * sizeof(float) <= kLdsMax;
-  y.part = 0;
-  y.chunk = round64(blocks * P);
-  y.loss = y.chunk + round64(chunks);
-  q.logp = y.loss + round64(blocks);
-  y.image = q.logp + round64(blocks);
-  y.words = y.image + (y.lds ? 0 : round64(blocks * kLearnRows * pitch));
-  return q;
+// the actor's workspace: the actor step's, with the blocks' logp partials (extra[0]) behind their loss partials
+LearnLayout sac_layout(int P, int pitch, int64_t batch) {
+  const size_t blocks = (size_t)blocks_of(batch);
+  return layout(P, pitch, kSacRowWords, blocks, 1, blocks);
 }
 
 template <bool UPDATE>
@@ -1204,15 +1256,9 @@ int learn_sac(const std::string& who, int64_t batch, const S2DLearnNet* actor, c
               const S2DLearnNet* critic2, const float* obs, float* alpha, const S2DLearnSacAlpha* as, uint64_t* draws, uint64_t seed,
               float* out_action, float* out_logp, float* out_q, void* stream) {
   if (!actor || !st || !critic1) return fail(who, "actor, state and critic1 must be non-NULL");
-  std::string err = sac_error(actor, critic1, critic2);
+  const Stepped b = stepped("actor: ", actor, st, false);
+  std::string err = actor_error<UPDATE>(b, batch, actor, true, critic1, critic2, obs);
   if (!err.empty()) return fail(who, err);
-  if (batch < 1 || batch > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
-  err = buffers_error<UPDATE>("actor", actor, st, false);
-  if (!err.empty()) return fail(who, err);
-  if (!critic1->params || misaligned(critic1->params, 16)) return fail(who, "critic1: params must be a non-NULL, 16-byte aligned device pointer");
-  if (critic2 && (!critic2->params || misaligned(critic2->params, 16)))
-    return fail(who, "critic2: params must be a non-NULL, 16-byte aligned device pointer");
-  if (!obs || misaligned(obs, 4)) return fail(who, "obs must be a non-NULL, 4-byte aligned device pointer");
   if (!alpha || misaligned(alpha, 4)) return fail(who, "alpha must be a non-NULL, 4-byte aligned device pointer");
   if (!draws || misaligned(draws, 8)) return fail(who, "draws must be a non-NULL, 8-byte aligned device pointer");
   if (as && (!as->log_alpha || !as->m_v || !as->hyper || !as->stats || misaligned(as->log_alpha, 4) || misaligned(as->m_v, 4) ||
@@ -1222,93 +1268,64 @@ int learn_sac(const std::string& who, int64_t batch, const S2DLearnNet* actor, c
     return fail(who, "out_action, out_logp and out_q must be 4-byte aligned device pointers (or NULL)");
   const LearnDev a = net_dev(actor), c1 = net_dev(critic1), c2 = critic2 ? net_dev(critic2) : LearnDev{};
   const int A = actor->n_out / 2, pitch = sac_pitch(actor, critic1, critic2);
-  const SacLayout q = sac_layout(a.P, pitch, batch);
-  const LearnLayout& y = q.y;
-  err = layout_error<UPDATE>("actor", actor, st, y, a.P, batch, "s2d_learn_sac_workspace_bytes", critic1->params, (size_t)c1.P * sizeof(float));
+  const LearnLayout y = sac_layout(a.P, pitch, batch);
+  err = layout_error<UPDATE>(b, y, a.P, batch, "s2d_learn_sac_workspace_bytes", critic1->params, (size_t)c1.P * sizeof(float));
   if (!err.empty()) return fail(who, err);
   {
-    // the call's new arrays against one another and against what the call writes or the critics' parameters
-    const size_t pb = (size_t)a.P * sizeof(float), fb = sizeof(float), B = (size_t)batch;
-    const void* mine[6] = {alpha, draws, as ? as->log_alpha : nullptr, as ? as->m_v : nullptr, as ? as->hyper : nullptr, as ? as->stats : nullptr};
-    const size_t mlen[6] = {fb, sizeof(uint64_t), fb, 2 * fb, 7 * fb, 3 * fb};
-    const void* other[10] = {actor->params, st->grad, actor->workspace, UPDATE ? st->m : nullptr, UPDATE ? st->v : nullptr, critic1->params,
-                             critic2 ? critic2->params : nullptr, out_action, out_logp, out_q};
-    const size_t olen[10] = {pb, pb, y.words * fb, pb, pb, (size_t)c1.P * fb, (size_t)c2.P * fb, B * A * fb, B * fb, B * fb};
-    for (int i = 0; i < 6; ++i) {
-      if (!mine[i]) continue;
-      for (int j = i + 1; j < 6; ++j)
-        if (mine[j] && overlap(mine[i], mlen[i], mine[j], mlen[j]))
-          return fail(who, "alpha, draws and alpha_state's log_alpha, m_v, hyper and stats must not overlap one another");
-      for (int j = 0; j < 10; ++j)
-        if (other[j] && overlap(mine[i], mlen[i], other[j], olen[j]))
-          return fail(who, "alpha, draws and alpha_state's arrays must not overlap the actor's params, m, v, grad or workspace, a critic's "
-                           "params or an output");
-    }
-    if (critic2)
-      for (int j = 0; j < 5; ++j)
-        if (other[j] && overlap(other[j], olen[j], critic2->params, olen[6]))
-          return fail(who, "the actor's params, m, v, grad and workspace must not overlap one another or the critic's params");
+    // the call's new arrays (group 0) against one another, then against what the call writes, the critics' parameters and the
+    // outputs (group 1); last the second critic's parameters against what the call writes, as layout_error did the first's
+    const size_t fb = sizeof(float), B = (size_t)batch, c2b = (size_t)c2.P * fb;
+    const float* const c2p = critic2 ? critic2->params : nullptr;
+    Spans z;
+    z.add(alpha, fb).add(draws, sizeof(uint64_t)).add(as ? as->log_alpha : nullptr, fb).add(as ? as->m_v : nullptr, 2 * fb)
+        .add(as ? as->hyper : nullptr, 7 * fb).add(as ? as->stats : nullptr, 3 * fb);
+    z.add_stepped<UPDATE>(b, a.P, y, 1).add(critic1->params, (size_t)c1.P * fb, 1).add(c2p, c2b, 1).add(out_action, B * A * fb, 1)
+        .add(out_logp, B * fb, 1).add(out_q, B * fb, 1);
+    const int group = z.clash();
+    if (group == 0) return fail(who, "alpha, draws and alpha_state's log_alpha, m_v, hyper and stats must not overlap one another");
+    if (group == 1)
+      return fail(who, "alpha, draws and alpha_state's arrays must not overlap the actor's params, m, v, grad or workspace, a critic's "
+                       "params or an output");
+    if (Spans().add(c2p, c2b).add_stepped<UPDATE>(b, a.P, y, 1).clash() >= 0) return fail(who, kActorOverlapText);
   }
-  const auto kb = y.lds ? s2d_learn_sac_kernel<true> : s2d_learn_sac_kernel<false>;
-  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + kSacRowWords) * sizeof(float);
-  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 4)) return no_lds(who);
   float* const ws = static_cast<float*>(actor->workspace);
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t blocks = (batch + kLearnRows - 1) / kLearnRows;
+  const int64_t blocks = blocks_of(batch);
   SacArgs g{};
   g.pitch = pitch; g.z_off = sac_z_off(actor, critic1, critic2); g.twin = critic2 ? 1 : 0; g.batch = batch;
   g.aparams = actor->params; g.c1params = critic1->params; g.c2params = critic2 ? critic2->params : nullptr;
-  g.part = ws + y.part; g.loss_part = ws + y.loss; g.logp_part = ws + q.logp; g.image = ws + y.image;
+  g.part = ws + y.part; g.loss_part = ws + y.loss; g.logp_part = ws + y.extra[0]; g.image = ws + y.image;
   g.obs = obs; g.alpha = alpha; g.draws = draws; g.seed_lo = (uint32_t)seed; g.seed_hi = (uint32_t)(seed >> 32);
   g.out_action = out_action; g.out_logp = out_logp; g.out_q = out_q;
-  hipLaunchKernelGGL(kb, dim3((unsigned)blocks), dim3(kLearnThreads), lds, s, a, c1, c2, g);
-  reduce_and_finish<UPDATE>(a.P, batch, false, y, actor, st, s);
+  if (const int rc = launch_block(who, s2d_learn_sac_kernel<true>, s2d_learn_sac_kernel<false>, 4, y, kSacRowWords, pitch, blocks, s,
+                                  nothing_before, a, c1, c2, g))
+    return rc;
+  reduce_and_finish<UPDATE>(b, a.P, batch, blocks, a.P, false, y, s);
   if (UPDATE || as) {
     SacAlphaDev t{};
     if (as) {
       t.log_alpha = as->log_alpha; t.m_v = as->m_v; t.hyper = as->hyper; t.stats = as->stats; t.target_entropy = as->target_entropy;
     }
-    hipLaunchKernelGGL(s2d_learn_sac_alpha_kernel<UPDATE>, dim3(1), dim3(1), 0, s, batch, blocks, ws + q.logp, t, alpha, draws);
+    hipLaunchKernelGGL(s2d_learn_sac_alpha_kernel<UPDATE>, dim3(1), dim3(1), 0, s, batch, blocks, ws + y.extra[0], t, alpha, draws);
   }
   return launched(who);
 }
 // ---- PPO
 // "" if the pair of networks and the head are on the grid of s2d_learn_ppo
 std::string ppo_error(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) {
-  std::string bad = shape_error(pi);
-  if (!bad.empty()) return "pi: " + bad;
-  bad = shape_error(vf);
-  if (!bad.empty()) return "vf: " + bad;
+  const std::string bad = shapes_error({{"pi", pi}, {"vf", vf}});
+  if (!bad.empty()) return bad;
   if (vf->n_out != 1 || vf->n_in != pi->n_in) return "vf: n_in must be pi's n_in, its n_out 1";
   if (head != S2D_LEARN_PPO_CATEGORICAL && head != S2D_LEARN_PPO_GAUSSIAN) return "head must be 0 (categorical) or 1 (diagonal Gaussian)";
   if (head == S2D_LEARN_PPO_GAUSSIAN && pi->n_out > kLearnMaxAction) return "pi: n_out (the action width) must be in [1, 8] with the Gaussian head";
   return "";
 }
-int ppo_pitch(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) {
-  return ((pi->n_in + 3) / 4 * 4 + layer_words(pi) + layer_words(vf) + (head ? pi->n_out : 0)) | 1;
-}
-// the workspace in words: [the groups' partials: g x P | chunk sums | the groups' statistics: g x 8 | mean, std | the pre-pass's block
-// sums | the groups' images, if not in LDS], g = min(blocks, 256) -- at least the groups of every smaller batch
-struct PpoLayout {
-  size_t part, chunk, stat, nrm, bsum, image, words;
-  int64_t blocks, per_group, groups;
-  bool lds;
-};
-PpoLayout ppo_layout(int P, int pitch, int64_t batch) {
-  PpoLayout y{};
-  y.blocks = (batch + kLearnRows - 1) / kLearnRows;
-  y.per_group = (y.blocks + kPpoMaxGroups - 1) / kPpoMaxGroups;
-  y.groups = (y.blocks + y.per_group - 1) / y.per_group;
-  const size_t g = (size_t)(y.blocks < kPpoMaxGroups ? y.blocks : kPpoMaxGroups), chunks = ((size_t)P + kLearnChunk - 1) / kLearnChunk;
-  y.lds = (size_t)kLearnRows * (pitch + kPpoRowWords) * sizeof(float) <= kLdsMax;
-  y.part = 0;
-  y.chunk = round64(g * P);
-  y.stat = y.chunk + round64(chunks);
-  y.nrm = y.stat + round64(g * kPpoStatWords);
-  y.bsum = y.nrm + 64;
-  y.image = y.bsum + round64((size_t)y.blocks);
-  y.words = y.image + (y.lds ? 0 : round64(g * kLearnRows * pitch));
-  return y;
+int ppo_pitch(const S2DLearnNet* pi, const S2DLearnNet* vf, int head) { return (row_words(pi->n_in, {pi, vf}) + (head ? pi->n_out : 0)) | 1; }
+// the workspace: g = min(blocks, 256) rows of partials -- at least the groups of every smaller batch -- with the groups' statistics
+// (8 words each) as their loss partials, then [mean, std] (extra[0]) and the pre-pass's block sums (extra[1])
+LearnLayout ppo_layout(int P, int pitch, int64_t batch) {
+  const size_t blocks = (size_t)blocks_of(batch), most = kPpoMaxGroups;
+  return layout(P, pitch, kPpoRowWords, blocks < most ? blocks : most, kPpoStatWords, 2, blocks);
 }
 
 template <bool UPDATE>
@@ -1317,16 +1334,12 @@ int learn_ppo(const std::string& who, const S2DLearnPPO* q, const S2DLearnPPOBat
   std::string err = ppo_error(&q->pi, &q->vf, q->head);
   if (!err.empty()) return fail(who, err);
   const int64_t B = b->batch, R = b->rows;
-  if (R < 1 || R > INT32_MAX) return fail(who, "rows must be in [1, 2^31 - 1]");
-  if (B < 1 || B > INT32_MAX) return fail(who, "batch must be in [1, 2^31 - 1]");
+  if (!in_range(R)) return fail(who, "rows must be in [1, 2^31 - 1]");
+  if (!in_range(B)) return fail(who, kBatchText);
   if (!b->index && B > R) return fail(who, "batch must be at most rows where index is NULL");
-  if (!q->params || misaligned(q->params, 16)) return fail(who, "params must be a non-NULL, 16-byte aligned device pointer");
-  if (!q->workspace || misaligned(q->workspace, 256)) return fail(who, "workspace must be a non-NULL, 256-byte aligned device pointer");
-  if (!q->grad || misaligned(q->grad, 16) || !q->hyper || misaligned(q->hyper, 4) || !q->stats || misaligned(q->stats, 4) || !q->error ||
-      misaligned(q->error, 4))
-    return fail(who, "grad (16 bytes), hyper, stats and error (4 bytes) must be non-NULL, aligned device pointers");
-  if (UPDATE && (!q->m || !q->v || misaligned(q->m, 16) || misaligned(q->v, 16)))
-    return fail(who, "m and v must be non-NULL, 16-byte aligned device pointers");
+  const Stepped st = stepped(q);
+  err = buffers_error<UPDATE>(st);
+  if (!err.empty()) return fail(who, err);
   if (!b->obs || !b->action || !b->logp_old || !b->advantage || !b->ret || misaligned(b->obs, 4) || misaligned(b->action, 4) ||
       misaligned(b->logp_old, 4) || misaligned(b->advantage, 4) || misaligned(b->ret, 4))
     return fail(who, "obs, action, logp_old, advantage and ret must be non-NULL, 4-byte aligned device pointers");
@@ -1334,44 +1347,35 @@ int learn_ppo(const std::string& who, const S2DLearnPPO* q, const S2DLearnPPOBat
     return fail(who, "index, out_logp and out_value must be 4-byte aligned device pointers (or NULL)");
   const LearnDev pi = net_dev(&q->pi), vf = net_dev(&q->vf);
   const int A = q->pi.n_out, P = pi.P + vf.P + (q->head ? A : 0), pitch = ppo_pitch(&q->pi, &q->vf, q->head);
-  const PpoLayout y = ppo_layout(P, pitch, B);
-  if (q->workspace_bytes < y.words * sizeof(float))
-    return fail(who, "workspace_bytes is " + std::to_string(q->workspace_bytes) + ", a batch of " + std::to_string(B) + " needs " +
-                         std::to_string(y.words * sizeof(float)) + " (s2d_learn_ppo_workspace_bytes: batch is above the workspace's max_batch)");
-  const size_t pb = (size_t)P * sizeof(float);
-  const void* bufs[5] = {q->params, q->grad, q->workspace, UPDATE ? q->m : nullptr, UPDATE ? q->v : nullptr};
-  const size_t lens[5] = {pb, pb, y.words * sizeof(float), pb, pb};
-  for (int i = 0; i < 5; ++i)
-    for (int j = i + 1; j < 5; ++j)
-      if (bufs[i] && bufs[j] && overlap(bufs[i], lens[i], bufs[j], lens[j]))
-        return fail(who, "params, m, v, grad and the workspace must not overlap one another");
-  const auto kb = y.lds ? s2d_learn_ppo_block_kernel<true> : s2d_learn_ppo_block_kernel<false>;
-  const size_t lds = (size_t)kLearnRows * ((y.lds ? pitch : 0) + kPpoRowWords) * sizeof(float);
-  if (lds > 48 * 1024 && !allow_lds_slot<LearnLds>(reinterpret_cast<const void*>(kb), 3)) return no_lds(who);
+  const LearnLayout y = ppo_layout(P, pitch, B);
+  err = layout_error<UPDATE>(st, y, P, B, "s2d_learn_ppo_workspace_bytes");
+  if (!err.empty()) return fail(who, err);
+  // one workgroup per group of per_group consecutive blocks
+  const int64_t blocks = blocks_of(B), per_group = (blocks + kPpoMaxGroups - 1) / kPpoMaxGroups, groups = (blocks + per_group - 1) / per_group;
   float* const ws = static_cast<float*>(q->workspace);
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const bool normalize = q->normalize_advantage && B > 1;
-  if (normalize)
-    hipLaunchKernelGGL(s2d_learn_ppo_norm_kernel, dim3(1), dim3(kPpoNormThreads), 0, s, B, R, y.blocks, b->advantage, b->index, ws + y.bsum,
-                       ws + y.nrm);
   PpoArgs a{};
   a.head = q->head; a.A = A; a.normalize = normalize; a.pitch = pitch; a.P = P;
-  a.batch = B; a.src_rows = R; a.blocks = y.blocks; a.per_group = y.per_group;
-  a.params = q->params; a.part = ws + y.part; a.stat_part = ws + y.stat; a.image = ws + y.image; a.nrm = ws + y.nrm; a.hyper = q->hyper;
+  a.batch = B; a.src_rows = R; a.blocks = blocks; a.per_group = per_group;
+  a.params = q->params; a.part = ws + y.part; a.stat_part = ws + y.loss; a.image = ws + y.image; a.nrm = ws + y.extra[0]; a.hyper = q->hyper;
   a.obs = b->obs; a.action = b->action; a.logp_old = b->logp_old; a.adv = b->advantage; a.ret = b->ret; a.index = b->index;
   a.out_logp = b->out_logp; a.out_value = b->out_value; a.error = q->error;
-  hipLaunchKernelGGL(kb, dim3((unsigned)y.groups), dim3(kLearnThreads), lds, s, pi, vf, a);
-  const int chunks = (P + kLearnChunk - 1) / kLearnChunk;
-  hipLaunchKernelGGL((s2d_learn_reduce_kernel<UPDATE, true>), dim3((unsigned)chunks), dim3(kLearnThreads), 0, s, P, y.groups, ws + y.part, q->grad,
-                     ws + y.chunk, q->hyper, pi.P + vf.P);
-  hipLaunchKernelGGL((s2d_learn_finish_kernel<UPDATE, true>), dim3(UPDATE ? (unsigned)chunks : 1u), dim3(kLearnThreads), 0, s, P, B, y.groups, chunks,
-                     false, ws + y.chunk, ws + y.stat, q->grad, q->hyper, q->stats, q->params, q->m, q->v);
+  const auto advantage_pre_pass = [&] {
+    if (normalize)
+      hipLaunchKernelGGL(s2d_learn_ppo_norm_kernel, dim3(1), dim3(kPpoNormThreads), 0, s, B, R, blocks, b->advantage, b->index, ws + y.extra[1],
+                         ws + y.extra[0]);
+  };
+  if (const int rc = launch_block(who, s2d_learn_ppo_block_kernel<true>, s2d_learn_ppo_block_kernel<false>, 3, y, kPpoRowWords, pitch, groups, s,
+                                  advantage_pre_pass, pi, vf, a))
+    return rc;
+  reduce_and_finish<UPDATE, true>(st, P, B, groups, pi.P + vf.P, false, y, s);
   return launched(who);
 }
 }  // namespace
 
 S2D_API size_t s2d_learn_ppo_workspace_bytes(const S2DLearnNet* pi_shape, const S2DLearnNet* vf_shape, int32_t head, int64_t max_batch) {
-  if (!pi_shape || !vf_shape || !ppo_error(pi_shape, vf_shape, head).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  if (!pi_shape || !vf_shape || !ppo_error(pi_shape, vf_shape, head).empty() || !in_range(max_batch)) return 0;
   const int P = net_dev(pi_shape).P + net_dev(vf_shape).P + (head ? pi_shape->n_out : 0);
   return ppo_layout(P, ppo_pitch(pi_shape, vf_shape, head), max_batch).words * sizeof(float);
 }
@@ -1385,15 +1389,15 @@ S2D_API int s2d_learn_ppo_grad(const S2DLearnPPO* learner, const S2DLearnPPOBatc
 }
 
 S2D_API size_t s2d_learn_workspace_bytes(const S2DLearnNet* shape, int64_t max_batch) {
-  if (!shape || !shape_error(shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  if (!shape || !shape_error(shape).empty() || !in_range(max_batch)) return 0;
   const LearnDev d = net_dev(shape);
-  return layout(d.P, d.pitch, max_batch).words * sizeof(float);
+  return block_layout(d.P, d.pitch, max_batch).words * sizeof(float);
 }
 
 S2D_API size_t s2d_learn_actor_workspace_bytes(const S2DLearnNet* actor_shape, const S2DLearnNet* critic_shape, int64_t max_batch) {
-  if (!actor_shape || !critic_shape || !pair_error(actor_shape, critic_shape).empty() || max_batch < 1 || max_batch > INT32_MAX) return 0;
+  if (!actor_shape || !critic_shape || !pair_error(actor_shape, false, critic_shape, nullptr).empty() || !in_range(max_batch)) return 0;
   const LearnDev a = net_dev(actor_shape);
-  return layout(a.P, pair_pitch(actor_shape, critic_shape), max_batch).words * sizeof(float);
+  return block_layout(a.P, pair_pitch(actor_shape, critic_shape), max_batch).words * sizeof(float);
 }
 
 S2D_API int s2d_learn_q(int64_t batch, const S2DLearnNet* net, const S2DLearnState* state, const float* obs, const int32_t* action,
@@ -1429,9 +1433,8 @@ S2D_API int s2d_learn_actor_grad(int64_t batch, const S2DLearnNet* actor, const 
 
 S2D_API size_t s2d_learn_sac_workspace_bytes(const S2DLearnNet* actor_shape, const S2DLearnNet* critic1_shape, const S2DLearnNet* critic2_shape,
                                              int64_t max_batch) {
-  if (!actor_shape || !critic1_shape || !sac_error(actor_shape, critic1_shape, critic2_shape).empty() || max_batch < 1 || max_batch > INT32_MAX)
-    return 0;
-  return sac_layout(net_dev(actor_shape).P, sac_pitch(actor_shape, critic1_shape, critic2_shape), max_batch).y.words * sizeof(float);
+  if (!actor_shape || !critic1_shape || !pair_error(actor_shape, true, critic1_shape, critic2_shape).empty() || !in_range(max_batch)) return 0;
+  return sac_layout(net_dev(actor_shape).P, sac_pitch(actor_shape, critic1_shape, critic2_shape), max_batch).words * sizeof(float);
 }
 
 S2D_API int s2d_learn_sac_actor(int64_t batch, const S2DLearnNet* actor, const S2DLearnState* actor_state, const S2DLearnNet* critic1,

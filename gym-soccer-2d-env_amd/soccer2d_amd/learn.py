@@ -20,7 +20,11 @@ actor's step on -mean Q(obs, tanh-mu(obs)), whose gradient goes through the crit
 
 SACLearner is Soft Actor-Critic's (s2d_learn_critic per critic, s2d_learn_sac_actor): the squashed-Gaussian actor's reparameterised
 step on mean(alpha * logp - min(Q1, Q2)(obs, a)) through the critic that gave each row's minimum, and the temperature's scalar Adam
-step; tests/learn_sac_ref.c."""
+step; tests/learn_sac_ref.c.
+
+PPOLearner is the PPO minibatch update (s2d_learn_ppo); tests/learn_ppo_ref.c.  The four share one host path: _Stepped owns the
+flat buffers one optimiser steps, _StepNet is one stepped network, _workspace_bytes the one workspace formula and _launch the
+one way into the library."""
 import ctypes as C
 
 import torch
@@ -42,6 +46,8 @@ LOSSES = ('mse', 'huber')
 AC_LOSSES = ('mse', 'huber', 'square')   # S2D_LEARN_SQUARE: the critics' steps only
 MAX_ACTION = 8
 MAX_OBS = 248
+PPO_MAX_GROUPS = 256      # S2D_LEARN_PPO_MAX_GROUPS
+PPO_HEADS = ('categorical', 'gaussian')
 
 
 def _round64(w):
@@ -52,30 +58,55 @@ def learn_param_count(n_in, hidden, n_out):
     return param_count(hidden, n_out, n_in)
 
 
+def _blocks(batch):
+    return (batch + BLOCK_ROWS - 1) // BLOCK_ROWS
+
+
+def _workspace_bytes(P, pitch, row_words, rows, loss_words=1, extras=()):
+    """bytes of a learner's workspace, by the arithmetic of the C layout(): `rows` rows of partial gradients of P words, the chunk
+    sums of the norm, `loss_words` loss partials per row, the learner's extra parts and, where 64 rows of an image of `pitch` words
+    and of the `row_words` beside it do not fit the LDS, the rows' images; every part rounded up to 64 words"""
+    words = _round64(rows * P) + _round64((P + NORM_CHUNK - 1) // NORM_CHUNK) + sum(map(_round64, (rows * loss_words, *extras)))
+    if BLOCK_ROWS * (pitch + row_words) * 4 > LDS_BYTES:
+        words += _round64(rows * BLOCK_ROWS * pitch)
+    return words * 4
+
+
 def learn_workspace_bytes(n_in, hidden, n_out, max_batch):
     """bytes of the learner's workspace, by the arithmetic of the C layout (s2d_learn_workspace_bytes): the blocks' partial
     gradients, the chunk sums of the norm, the blocks' loss partials and, where 64 rows of activations do not fit the LDS, the
     blocks' activations; every part rounded up to 64 words"""
-    P = learn_param_count(n_in, hidden, n_out)
-    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
     pitch = ((n_in + 3) // 4 * 4 + sum(hidden) + n_out) | 1
-    words = _round64(blocks * P) + _round64(chunks) + _round64(blocks)
-    if BLOCK_ROWS * (pitch + 1) * 4 > LDS_BYTES:
-        words += _round64(blocks * BLOCK_ROWS * pitch)
-    return words * 4
+    return _workspace_bytes(learn_param_count(n_in, hidden, n_out), pitch, 1, _blocks(max_batch))
 
 
 def learn_actor_workspace_bytes(obs_dim, actor_hidden, action_dim, critic_hidden, max_batch):
     """bytes of the ACTOR's workspace for the actor step through a critic (s2d_learn_actor_workspace_bytes): the parts above for the
     actor's parameters, and the blocks' images where 64 rows of BOTH networks ([obs | action] padded to a multiple of 4, every
     layer's outputs of the actor and of the critic) do not fit the LDS"""
-    P = learn_param_count(obs_dim, actor_hidden, action_dim)
-    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
     pitch = ((obs_dim + action_dim + 3) // 4 * 4 + sum(actor_hidden) + action_dim + sum(critic_hidden) + 1) | 1
-    words = _round64(blocks * P) + _round64(chunks) + _round64(blocks)
-    if BLOCK_ROWS * (pitch + 1) * 4 > LDS_BYTES:
-        words += _round64(blocks * BLOCK_ROWS * pitch)
-    return words * 4
+    return _workspace_bytes(learn_param_count(obs_dim, actor_hidden, action_dim), pitch, 1, _blocks(max_batch))
+
+
+def learn_sac_workspace_bytes(obs_dim, actor_hidden, action_dim, critic1_hidden, critic2_hidden, max_batch):
+    """bytes of the ACTOR's workspace for the SAC actor step (s2d_learn_sac_workspace_bytes): learn_actor_workspace_bytes' parts for
+    the actor's parameters (D -> ... -> 2A), a second row of block partials (the rows' logp), and the blocks' images where 64 rows of
+    ALL the networks ([obs | action] padded to a multiple of 4, every layer's outputs of the actor and of each critic, the head's A
+    noise words) and three words a row do not fit the LDS.  critic2_hidden: None for one critic."""
+    pitch = ((obs_dim + action_dim + 3) // 4 * 4 + sum(actor_hidden) + 2 * action_dim + sum(critic1_hidden) + 1
+             + (sum(critic2_hidden) + 1 if critic2_hidden is not None else 0) + action_dim) | 1
+    blocks = _blocks(max_batch)
+    return _workspace_bytes(learn_param_count(obs_dim, actor_hidden, 2 * action_dim), pitch, 3, blocks, 1, (blocks,))
+
+
+def learn_ppo_workspace_bytes(obs_dim, pi_hidden, n_out, vf_hidden, head, max_batch):
+    """bytes of the PPO learner's workspace, by the arithmetic of the C layout (s2d_learn_ppo_workspace_bytes): the partial gradients
+    and statistics of at most 256 groups of blocks, the chunk sums of the norm, the advantage pre-pass's two words and block sums
+    and, where 64 rows of BOTH networks do not fit the LDS, the groups' images; every part rounded up to 64 words.  head: 0 / 1."""
+    P = learn_param_count(obs_dim, pi_hidden, n_out) + learn_param_count(obs_dim, vf_hidden, 1) + (n_out if head else 0)
+    pitch = ((obs_dim + 3) // 4 * 4 + sum(pi_hidden) + n_out + sum(vf_hidden) + 1 + (n_out if head else 0)) | 1
+    blocks = _blocks(max_batch)
+    return _workspace_bytes(P, pitch, 6, min(blocks, PPO_MAX_GROUPS), 8, (2, blocks))
 
 
 def _read_shape(who, what, module, tanh_head=False):
@@ -145,31 +176,110 @@ def _into_target(params, net, tau, mirror):
     return mirror
 
 
-class QLearner:
+# ---------------------------------------------------------------------------------------------- what every learner's call does
+def _batch_obs(who, lrn, batch, keys):
+    """the checks of a sampled batch (`lrn` has ``device``, ``obs_dim`` and ``max_batch``); returns B and the pointer of batch['obs']"""
+    if not isinstance(batch, dict) or any(k not in batch for k in keys):
+        raise ValueError(f'{who}: batch must be a dict with ' + ' and '.join(repr(k) for k in keys) + " (DeviceReplay.sample's)")
+    obs = batch['obs']
+    if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
+        raise ValueError(f"{who}: batch['obs'] must be a [B, {lrn.obs_dim}] tensor, B >= 1")
+    B = obs.shape[0]
+    if B > lrn.max_batch:
+        raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={lrn.max_batch}')
+    return B, _arr(who, lrn.device, "batch['obs']", obs, torch.float32, (B, lrn.obs_dim))
+
+
+def _opt(who, device, name, t, shape, dtype=torch.float32):
+    """the pointer of an optional argument tensor, checked, or None"""
+    return _arr(who, device, name, t, dtype, shape) if t is not None else None
+
+
+def _launch(who, device, fn, calls):
+    """the library's `fn` once per argument list of `calls`, each with torch's current stream of `device` behind it and its return
+    code through _capi.check; ValueError where the learner is not on a GPU"""
+    if device.type != 'cuda':
+        raise ValueError(f'{who}: the networks are on {device}; the kernels need a GPU (there is no CPU path)')
+    lib = _capi.load_library()
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        for args in calls:
+            _capi.check(lib, getattr(lib, fn)(*args, stream), fn)
+
+
+class _Stepped:
+    """the flat fp32 device buffers that one optimiser steps: ``params``, Adam's ``m`` and ``v``, the gradient ``_grad``, the
+    ``hyper`` words (lr, beta1, beta2, eps, max_grad_norm, beta1^t, beta2^t and the learner's own behind them), ``stats``, the
+    ``error`` word and the ``workspace``"""
+
+    def _alloc(self, P, device, lr, b1, b2, eps, max_grad_norm, more_hyper=(), n_stats=3):
+        # torch's device allocations are 256-byte aligned (the ABI asks for 16 of the [P] arrays, 256 of the workspace)
+        f32 = torch.float32
+        self.params = torch.zeros(P, dtype=f32, device=torch.device(device))
+        self.device = self.params.device                                     # with its index: 'cuda' -> cuda:0
+        self.m, self.v, self._grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
+        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0, *more_hyper], dtype=f32).to(self.device)
+        self.stats = torch.zeros(n_stats, dtype=f32, device=self.device)
+        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _alloc_workspace(self, workspace_bytes):
+        self.workspace = torch.zeros(workspace_bytes // 4, dtype=torch.float32, device=self.device)
+
+    def set_lr(self, lr):
+        """the learning rate of the steps enqueued from now on: a device write, also between the replays of a captured graph"""
+        self.hyper[0:1].fill_(float(lr))
+
+    def reset_optimizer(self):
+        """Adam as new: m = v = 0, both beta products 1"""
+        self.m.zero_()
+        self.v.zero_()
+        self.hyper[5:7].fill_(1.0)
+
+
+class _StepNet(_Stepped):
+    """one network that a learner steps: its module (rebound to the flat buffer by ``bind``), shape, Adam state, device words and
+    workspace.  PPOLearner reads its two networks' shapes with it and steps them in a buffer of its own."""
+    loss_kind = 0             # S2DLearnState.loss_kind, where the call reads it
+    grad = property(lambda self: self._grad)
+
+    def __init__(self, who, what, module, tanh_head=False):
+        self._linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, what, module, tanh_head)
+        self.what, self.module, self.mirror = what, module, None
+
+    def alloc(self, device, lr, b1, b2, eps, max_grad_norm):
+        """the buffers, on `device` (default: the module's); the workspace waits for ``bind``"""
+        self._alloc(learn_param_count(self.n_in, self.hidden, self.n_out), device if device is not None else self._linears[0].weight.device,
+                    lr, b1, b2, eps, max_grad_norm)
+        return self
+
+    def bind(self, workspace_bytes):
+        """called once every network of the learner has passed its checks: the workspace, and the module's parameters as views"""
+        self._alloc_workspace(workspace_bytes)
+        _rebind(self.params, self._linears)
+
+    text = _net_text
+
+    def c_structs(self):
+        net, st = _fill_shape(_capi.S2DLearnNet(), self), _capi.S2DLearnState()
+        net.params, net.workspace, net.workspace_bytes = self.params.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4
+        st.m, st.v, st.grad = self.m.data_ptr(), self.v.data_ptr(), self._grad.data_ptr()
+        st.hyper, st.stats, st.error, st.loss_kind = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr(), self.loss_kind
+        return net, st
+
+
+class QLearner(_StepNet):
     """The online Q-network's optimiser step in one call.  ``q_net`` is Linear-(F-Linear) x L (SB3's ``q_net.q_net``)."""
 
     def __init__(self, q_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=10.0, loss='huber', max_batch=4096, device=None):
         who = 'QLearner'
-        linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, 'Q-network', q_net)
+        _StepNet.__init__(self, who, 'Q-network', q_net)
         if not 1 <= self.n_out <= MAX_OUT:
             raise ValueError(f'{who}: the Q-network\'s output width must be in [1, {MAX_OUT}], got {self.n_out}')
         if loss not in LOSSES:
             raise ValueError(f"{who}: loss must be 'huber' or 'mse', got {loss!r}")
         b1, b2 = _check_optimiser(who, max_batch, lr, betas, eps)
-        self.module, self.loss_kind, self.max_batch = q_net, LOSSES.index(loss), max_batch
-        dev = torch.device(device if device is not None else linears[0].weight.device)
-        f32 = torch.float32
-        P = learn_param_count(self.n_in, self.hidden, self.n_out)
-        # torch's device allocations are 256-byte aligned (the ABI asks for 16 of the [P] arrays, 256 of the workspace)
-        self.params = torch.zeros(P, dtype=f32, device=dev)
-        self.device = self.params.device                                     # with its index: 'cuda' -> cuda:0
-        self.m, self.v, self._grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
-        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0], dtype=f32).to(self.device)
-        self.stats = torch.zeros(3, dtype=f32, device=self.device)
-        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.workspace = torch.zeros(learn_workspace_bytes(self.n_in, self.hidden, self.n_out, max_batch) // 4, dtype=f32, device=self.device)
-        _rebind(self.params, linears)
-        self._mirror = None
+        self.loss_kind, self.max_batch, self.obs_dim = LOSSES.index(loss), max_batch, self.n_in
+        self.alloc(device, lr, b1, b2, eps, max_grad_norm).bind(learn_workspace_bytes(self.n_in, self.hidden, self.n_out, max_batch))
 
     @classmethod
     def from_module(cls, q_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=10.0, loss='huber', max_batch=4096, device=None):
@@ -178,44 +288,17 @@ class QLearner:
         device: where the buffers, and from then on the module's parameters, live (default: the module's)."""
         return cls(q_net, lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, loss=loss, max_batch=max_batch, device=device)
 
-    text = _net_text
-
     # ------------------------------------------------------------------ the step
-    def _arr(self, who, name, t, dtype, shape):
-        return _arr(who, self.device, name, t, dtype, shape)
-
     def _call(self, fn, batch, target, weight, td_abs_out, q_out):
-        who = f'QLearner.{"step" if fn == "s2d_learn_q" else "grad"}'
-        if not isinstance(batch, dict) or any(k not in batch for k in ('obs', 'action')):
-            raise ValueError(f"{who}: batch must be a dict with 'obs' and 'action' (DeviceReplay.sample's)")
-        obs, action = batch['obs'], batch['action']
-        if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
-            raise ValueError(f"{who}: batch['obs'] must be a [B, {self.n_in}] tensor, B >= 1")
-        B, f32 = obs.shape[0], torch.float32
-        if B > self.max_batch:
-            raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={self.max_batch}')
+        who, dev = f'QLearner.{"step" if fn == "s2d_learn_q" else "grad"}', self.device
+        B, obs = _batch_obs(who, self, batch, ('obs', 'action'))
+        action = batch['action']
         if torch.is_tensor(action) and tuple(action.shape) == (B, 1):
             action = action.view(B) if action.is_contiguous() else action
-        ptrs = [self._arr(who, "batch['obs']", obs, f32, (B, self.n_in)),
-                self._arr(who, "batch['action'] ([B] or [B, 1])", action, torch.int32, (B,)),
-                self._arr(who, 'target', target, f32, (B,)),
-                self._arr(who, 'weight', weight, f32, (B,)) if weight is not None else None,
-                self._arr(who, 'td_abs_out', td_abs_out, f32, (B,)) if td_abs_out is not None else None,
-                self._arr(who, 'q_out', q_out, f32, (B, self.n_out)) if q_out is not None else None]
-        if self.device.type != 'cuda':
-            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
-        lib = _capi.load_library()
-        net, st = self.c_structs()
-        with torch.cuda.device(self.device):
-            rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), *ptrs, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, fn)
-
-    def c_structs(self):
-        net, st = _fill_shape(_capi.S2DLearnNet(), self), _capi.S2DLearnState()
-        net.params, net.workspace, net.workspace_bytes = self.params.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4
-        st.m, st.v, st.grad = self.m.data_ptr(), self.v.data_ptr(), self._grad.data_ptr()
-        st.hyper, st.stats, st.error, st.loss_kind = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr(), self.loss_kind
-        return net, st
+        ptrs = [obs, _arr(who, dev, "batch['action'] ([B] or [B, 1])", action, torch.int32, (B,)),
+                _arr(who, dev, 'target', target, torch.float32, (B,)), _opt(who, dev, 'weight', weight, (B,)),
+                _opt(who, dev, 'td_abs_out', td_abs_out, (B,)), _opt(who, dev, 'q_out', q_out, (B, self.n_out))]
+        _launch(who, dev, fn, [(B, *map(C.byref, self.c_structs()), *ptrs)])
 
     def step(self, batch, target, weight=None, td_abs_out=None, q_out=None):
         """One update on the dict DeviceReplay.sample / PrioritizedReplay.sample returns (its 'obs' [B, obs_dim] and 'action' int32
@@ -253,16 +336,6 @@ class QLearner:
         """the factor the last call's gradient was scaled by: min(1, max_grad_norm / (norm + 1e-6)) (synchronises)"""
         return self._stat(2)
 
-    def set_lr(self, lr):
-        """the learning rate of the steps enqueued from now on: a device write, also between the replays of a captured graph"""
-        self.hyper[0:1].fill_(float(lr))
-
-    def reset_optimizer(self):
-        """Adam as new: m = v = 0, both beta products 1"""
-        self.m.zero_()
-        self.v.zero_()
-        self.hyper[5:7].fill_(1.0)
-
     def update_target(self, q_target, tau=1.0):
         """The learner's weights into a td.QTarget's target network: a hard copy (tau = 1) or a Polyak step target += tau (online
         - target), one ``copy_`` or ``lerp_`` from the learner's flat buffer straight into the target's (the layouts are the
@@ -276,87 +349,114 @@ class QLearner:
                              f'{self.text()} on {self.device}')
         if not 0.0 <= tau <= 1.0:
             raise ValueError(f'QLearner.update_target: tau must be in [0, 1], got {tau}')
-        self._mirror = _into_target(self.params, net, tau, self._mirror)
+        self.mirror = _into_target(self.params, net, tau, self.mirror)
 
 
-class _StepNet:
-    """one network that ActorCriticLearner steps: its module (rebound to the flat buffer), shape, Adam state, device words and
-    workspace"""
+class _ActorCritic:
+    """what ActorCriticLearner and SACLearner share: an actor with A actions and one or two critics on [obs | action] as _StepNets,
+    built and checked as a pair; the critics' call (s2d_learn_critic or its _grad twin, once per critic, the optional outputs from
+    critic 1); learning rates, Adam's reset, the statistics and the pair check of ``update_targets``.  ``_sac``: the actor has 2 A
+    outputs and no Tanh behind them, and a target's networks must agree in the activation too."""
+    _sac = False
 
-    def __init__(self, who, what, module, device, tanh_head, lr, b1, b2, eps, max_grad_norm):
-        linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, what, module, tanh_head)
-        self.what, self.module, self._linears = what, module, linears
-        dev = torch.device(device if device is not None else linears[0].weight.device)
-        f32 = torch.float32
-        P = learn_param_count(self.n_in, self.hidden, self.n_out)
-        self.params = torch.zeros(P, dtype=f32, device=dev)
-        self.device = self.params.device
-        self.m, self.v, self.grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
-        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0], dtype=f32).to(self.device)
-        self.stats = torch.zeros(3, dtype=f32, device=self.device)
-        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.workspace, self.mirror = None, None
+    def _networks(self, who, actor, q, q2, device, actor_lr, critic_lr, b1, b2, eps, max_grad_norm, max_batch):
+        """the networks with their buffers, the pair's checks; nothing of a module is touched before ``_bind``"""
+        a = self.actor = _StepNet(who, 'actor', actor, not self._sac).alloc(device, actor_lr, b1, b2, eps, max_grad_norm)
+        dev = device if device is not None else a.device
+        names = ('critic',) if q2 is None else ('critic 1', 'critic 2')
+        self.critics = tuple(_StepNet(who, n, mod).alloc(dev, critic_lr, b1, b2, eps, max_grad_norm) for n, mod in zip(names, (q, q2)))
+        A = a.n_out // 2 if self._sac else a.n_out
+        if self._sac and (a.n_out % 2 or not 1 <= A <= MAX_ACTION):
+            raise ValueError(f'{who}: the actor has {a.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
+                             f'1 .. {MAX_ACTION}')
+        if not 1 <= A <= MAX_ACTION:
+            raise ValueError(f'{who}: the actor has {a.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+        if a.n_in > MAX_OBS:
+            raise ValueError(f'{who}: the actor\'s input width must be in [1, {MAX_OBS}], got {a.n_in}')
+        for c in self.critics:
+            if c.n_in != a.n_in + A or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {a.text()} it must take obs_dim + A = '
+                                 f'{a.n_in} + {A} inputs and give one output')
+            if c.device != a.device:
+                raise ValueError(f'{who}: the {c.what} is on {c.device}, the actor on {a.device}')
+        self.device, self.obs_dim, self.action_dim, self.max_batch = a.device, a.n_in, A, max_batch
 
-    def bind(self, workspace_bytes):
-        """called once every network of the learner has passed its checks: the workspace, and the module's parameters as views"""
-        self.workspace = torch.zeros(workspace_bytes // 4, dtype=torch.float32, device=self.device)
-        _rebind(self.params, self._linears)
+    def _bind(self, loss, actor_workspace_bytes):
+        self.loss_kind = AC_LOSSES.index(loss)
+        self.actor.bind(actor_workspace_bytes)
+        for c in self.critics:
+            c.loss_kind = self.loss_kind
+            c.bind(learn_workspace_bytes(c.n_in, c.hidden, 1, self.max_batch))
 
-    text = _net_text
-
-    def c_structs(self, loss_kind=0):
-        net, st = _fill_shape(_capi.S2DLearnNet(), self), _capi.S2DLearnState()
-        net.params, net.workspace, net.workspace_bytes = self.params.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4
-        st.m, st.v, st.grad = self.m.data_ptr(), self.v.data_ptr(), self.grad.data_ptr()
-        st.hyper, st.stats, st.error, st.loss_kind = self.hyper.data_ptr(), self.stats.data_ptr(), self.error.data_ptr(), loss_kind
-        return net, st
-
-    def reset(self):
-        self.m.zero_()
-        self.v.zero_()
-        self.hyper[5:7].fill_(1.0)
-
-
-class _CriticSteps:
-    """what ActorCriticLearner and SACLearner share: the checks of a sampled batch and the critics' call (s2d_learn_critic or its
-    _grad twin, once per critic, the optional outputs from critic 1).  The class has ``critics`` (_StepNet), ``loss_kind``,
-    ``device``, ``obs_dim``, ``action_dim`` and ``max_batch``."""
-
-    def _obs(self, who, batch, keys):
-        if not isinstance(batch, dict) or any(k not in batch for k in keys):
-            raise ValueError(f'{who}: batch must be a dict with ' + ' and '.join(repr(k) for k in keys) + " (DeviceReplay.sample's)")
-        obs = batch['obs']
-        if not torch.is_tensor(obs) or obs.dim() != 2 or obs.shape[0] < 1:
-            raise ValueError(f"{who}: batch['obs'] must be a [B, {self.obs_dim}] tensor, B >= 1")
-        B = obs.shape[0]
-        if B > self.max_batch:
-            raise ValueError(f'{who}: the batch has {B} rows, the learner was made with max_batch={self.max_batch}')
-        return B, _arr(who, self.device, "batch['obs']", obs, torch.float32, (B, self.obs_dim))
-
-    def _need_gpu(self, who):
-        if self.device.type != 'cuda':
-            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
-
+    # ------------------------------------------------------------------ the critics' steps
     def _critic_call(self, fn, name, batch, target, weight, td_abs_out, q_out):
-        who, f32 = f'{type(self).__name__}.{name}', torch.float32
-        B, obs = self._obs(who, batch, ('obs', 'action'))
+        who, dev, f32 = f'{type(self).__name__}.{name}', self.device, torch.float32
+        B, obs = _batch_obs(who, self, batch, ('obs', 'action'))
+        ptrs = [_arr(who, dev, "batch['action']", batch['action'], f32, (B, self.action_dim)), _arr(who, dev, 'target', target, f32, (B,)),
+                _opt(who, dev, 'weight', weight, (B,))]
+        outs = [_opt(who, dev, 'td_abs_out', td_abs_out, (B,)), _opt(who, dev, 'q_out', q_out, (B,))]
+        _launch(who, dev, fn, ((B, *map(C.byref, c.c_structs()), obs, self.action_dim, *ptrs, *(outs if n == 0 else (None, None)))
+                               for n, c in enumerate(self.critics)))
 
-        def opt(what, t):
-            return _arr(who, self.device, what, t, f32, (B,)) if t is not None else None
-        ptrs = [_arr(who, self.device, "batch['action']", batch['action'], f32, (B, self.action_dim)),
-                _arr(who, self.device, 'target', target, f32, (B,)), opt('weight', weight)]
-        outs = [opt('td_abs_out', td_abs_out), opt('q_out', q_out)]
-        self._need_gpu(who)
-        lib = _capi.load_library()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for n, c in enumerate(self.critics):
-                net, st = c.c_structs(self.loss_kind)
-                rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), obs, self.action_dim, *ptrs, *(outs if n == 0 else (None, None)), stream)
-                _capi.check(lib, rc, fn)
+    def step_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """One update of the critic (of both, where ``q2`` was given) on the dict DeviceReplay.sample returns (its 'obs' [B, obs_dim]
+        and 'action' float32 [B, A]) towards `target` float32 [B] (ActorCriticTarget.target's; SACLearner: SacTarget.target's, with
+        the loss e^2 / 2), with the importance weights `weight` [B] where given.  td_abs_out [B] <- |q1 - target| (the new
+        priorities' base), q_out [B] <- critic 1's forward values.  Stream-ordered on torch's current stream, capturable; returns
+        nothing."""
+        self._critic_call('s2d_learn_critic', 'step_critic', batch, target, weight, td_abs_out, q_out)
+
+    def grad_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
+        """The flat, unclipped gradient [P] of critic 1's loss (with ``q2`` the tuple of both critics'; views, written again by the
+        next call), with the critic's statistics set, without touching parameters or optimiser state."""
+        self._critic_call('s2d_learn_critic_grad', 'grad_critic', batch, target, weight, td_abs_out, q_out)
+        return self.critics[0].grad if len(self.critics) == 1 else tuple(c.grad for c in self.critics)
+
+    # ------------------------------------------------------------------ state
+    critic_loss = property(lambda self: self.critics[0].stats.tolist()[0],
+                           doc="critic 1's last mean loss (SACLearner: of e^2 / 2; synchronises)")
+    critic_grad_norm = property(lambda self: self.critics[0].stats.tolist()[1], doc="critic 1's last gradient norm before the clip")
+    critic_clip_scale = property(lambda self: self.critics[0].stats.tolist()[2], doc="the factor critic 1's last gradient was scaled by")
+    actor_loss = property(lambda self: self.actor.stats.tolist()[0],
+                          doc="the actor's last loss: -mean q (SACLearner: mean(alpha logp - min q)) (synchronises)")
+    actor_grad_norm = property(lambda self: self.actor.stats.tolist()[1], doc="the actor's last gradient norm before the clip")
+    actor_clip_scale = property(lambda self: self.actor.stats.tolist()[2], doc="the factor the actor's last gradient was scaled by")
+
+    def set_lr(self, actor=None, critic=None):
+        """the learning rates of the steps enqueued from now on: device writes, also between the replays of a captured graph"""
+        if actor is not None:
+            self.actor.set_lr(actor)
+        if critic is not None:
+            for c in self.critics:
+                c.set_lr(critic)
+
+    def reset_optimizer(self):
+        """Adam as new for every network: m = v = 0, both beta products 1"""
+        for n in (self.actor,) + self.critics:
+            n.reset_optimizer()
+
+    def _target_pairs(self, who, target, actor_net, tau):
+        """update_targets' checks -- the critic count, every network's shape and device against the target's, tau -- and the
+        (learner's, target's) pairs, the actor's first"""
+        if len(target.critics) != len(self.critics):
+            raise ValueError(f'{who}: the target has {len(target.critics)} critic(s), the learner {len(self.critics)}')
+        pairs = list(zip((self.actor,) + self.critics, (actor_net,) + target.critics))
+
+        def shape(n):
+            return (n.n_in, n.hidden, n.n_out) + ((n.activation,) if self._sac else ())
+
+        def text(n):
+            return n.text() + (f' ({n.activation})' if self._sac else '')
+        for mine, net in pairs:
+            if shape(net) != shape(mine) or net.device != mine.device:
+                raise ValueError(f'{who}: the {net.what} is {text(net)} on {net.device}, the learner\'s {mine.what} {text(mine)} on '
+                                 f'{mine.device}')
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
+        return pairs
 
 
-class ActorCriticLearner(_CriticSteps):
+class ActorCriticLearner(_ActorCritic):
     """The DDPG / TD3 update in HIP (s2d_learn_critic / s2d_learn_actor in include/s2d.h), the steps that follow
     ActorCriticTarget.target:
 
@@ -377,26 +477,9 @@ class ActorCriticLearner(_CriticSteps):
         if loss not in AC_LOSSES:
             raise ValueError(f"{who}: loss must be 'square' (F.mse_loss), 'mse' (e^2 / 2) or 'huber', got {loss!r}")
         b1, b2 = _check_optimiser(who, max_batch, min(actor_lr, critic_lr), betas, eps)
-        self.actor = _StepNet(who, 'actor', mu, device, True, actor_lr, b1, b2, eps, max_grad_norm)
-        dev = device if device is not None else self.actor.device
-        names = ('critic',) if q2 is None else ('critic 1', 'critic 2')
-        self.critics = tuple(_StepNet(who, n, mod, dev, False, critic_lr, b1, b2, eps, max_grad_norm) for n, mod in zip(names, (q, q2)))
+        self._networks(who, mu, q, q2, device, actor_lr, critic_lr, b1, b2, eps, max_grad_norm, max_batch)
         a = self.actor
-        if not 1 <= a.n_out <= MAX_ACTION:
-            raise ValueError(f'{who}: the actor has {a.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
-        if a.n_in > MAX_OBS:
-            raise ValueError(f'{who}: the actor\'s input width must be in [1, {MAX_OBS}], got {a.n_in}')
-        for c in self.critics:
-            if c.n_in != a.n_in + a.n_out or c.n_out != 1:
-                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {a.text()} it must take obs_dim + A = '
-                                 f'{a.n_in} + {a.n_out} inputs and give one output')
-            if c.device != a.device:
-                raise ValueError(f'{who}: the {c.what} is on {c.device}, the actor on {a.device}')
-        self.device, self.obs_dim, self.action_dim = a.device, a.n_in, a.n_out
-        self.loss_kind, self.max_batch = AC_LOSSES.index(loss), max_batch
-        a.bind(learn_actor_workspace_bytes(a.n_in, a.hidden, a.n_out, self.critics[0].hidden, max_batch))
-        for c in self.critics:
-            c.bind(learn_workspace_bytes(c.n_in, c.hidden, 1, max_batch))
+        self._bind(loss, learn_actor_workspace_bytes(a.n_in, a.hidden, a.n_out, self.critics[0].hidden, max_batch))
 
     @classmethod
     def from_modules(cls, mu, q, q2=None, actor_lr=1e-3, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, loss='square',
@@ -410,25 +493,10 @@ class ActorCriticLearner(_CriticSteps):
 
     # ------------------------------------------------------------------ the steps
     def _actor_call(self, fn, name, batch, action_out, q_out):
-        who, f32 = f'ActorCriticLearner.{name}', torch.float32
-        B, obs = self._obs(who, batch, ('obs',))
-        outs = [_arr(who, self.device, 'action_out', action_out, f32, (B, self.action_dim)) if action_out is not None else None,
-                _arr(who, self.device, 'q_out', q_out, f32, (B,)) if q_out is not None else None]
-        self._need_gpu(who)
-        lib = _capi.load_library()
-        net, st = self.actor.c_structs()
-        critic, _ = self.critics[0].c_structs()
-        with torch.cuda.device(self.device):
-            rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), C.byref(critic), obs, *outs,
-                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, fn)
-
-    def step_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
-        """One update of the critic (of both, where ``q2`` was given) on the dict DeviceReplay.sample returns (its 'obs' [B, obs_dim]
-        and 'action' float32 [B, A]) towards `target` float32 [B] (ActorCriticTarget.target's), with the importance weights
-        `weight` [B] where given.  td_abs_out [B] <- |q1 - target| (the new priorities' base), q_out [B] <- critic 1's forward
-        values.  Stream-ordered on torch's current stream, capturable; returns nothing."""
-        self._critic_call('s2d_learn_critic', 'step_critic', batch, target, weight, td_abs_out, q_out)
+        who, dev = f'ActorCriticLearner.{name}', self.device
+        B, obs = _batch_obs(who, self, batch, ('obs',))
+        outs = [_opt(who, dev, 'action_out', action_out, (B, self.action_dim)), _opt(who, dev, 'q_out', q_out, (B,))]
+        _launch(who, dev, fn, [(B, *map(C.byref, self.actor.c_structs()), C.byref(self.critics[0].c_structs()[0]), obs, *outs)])
 
     def step_actor(self, batch, action_out=None, q_out=None):
         """One update of the actor on -mean critic_1(obs, tanh-mu(obs)) over batch['obs'].  action_out [B, A] <- the actions the
@@ -442,37 +510,10 @@ class ActorCriticLearner(_CriticSteps):
         if actor:
             self.step_actor(batch)
 
-    def grad_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
-        """The flat, unclipped gradient [P] of critic 1's loss (with ``q2`` the tuple of both critics'; views, written again by the
-        next call), with the critic's statistics set, without touching parameters or optimiser state."""
-        self._critic_call('s2d_learn_critic_grad', 'grad_critic', batch, target, weight, td_abs_out, q_out)
-        return self.critics[0].grad if len(self.critics) == 1 else tuple(c.grad for c in self.critics)
-
     def grad_actor(self, batch, action_out=None, q_out=None):
         """The flat, unclipped gradient [P] of the actor's loss, with the actor's statistics set, without touching anything else."""
         self._actor_call('s2d_learn_actor_grad', 'grad_actor', batch, action_out, q_out)
         return self.actor.grad
-
-    # ------------------------------------------------------------------ state
-    critic_loss = property(lambda self: self.critics[0].stats.tolist()[0], doc="critic 1's last mean loss (synchronises)")
-    critic_grad_norm = property(lambda self: self.critics[0].stats.tolist()[1], doc="critic 1's last gradient norm before the clip")
-    critic_clip_scale = property(lambda self: self.critics[0].stats.tolist()[2], doc="the factor critic 1's last gradient was scaled by")
-    actor_loss = property(lambda self: self.actor.stats.tolist()[0], doc="the actor's last loss: -mean q (synchronises)")
-    actor_grad_norm = property(lambda self: self.actor.stats.tolist()[1], doc="the actor's last gradient norm before the clip")
-    actor_clip_scale = property(lambda self: self.actor.stats.tolist()[2], doc="the factor the actor's last gradient was scaled by")
-
-    def set_lr(self, actor=None, critic=None):
-        """the learning rates of the steps enqueued from now on: device writes, also between the replays of a captured graph"""
-        if actor is not None:
-            self.actor.hyper[0:1].fill_(float(actor))
-        if critic is not None:
-            for c in self.critics:
-                c.hyper[0:1].fill_(float(critic))
-
-    def reset_optimizer(self):
-        """Adam as new for every network: m = v = 0, both beta products 1"""
-        for n in (self.actor,) + self.critics:
-            n.reset()
 
     def update_targets(self, ac_target, tau=1.0):
         """The learner's weights into a td.ActorCriticTarget's target networks: a hard copy (tau = 1) or a Polyak step, one
@@ -482,35 +523,11 @@ class ActorCriticLearner(_CriticSteps):
         who = 'ActorCriticLearner.update_targets'
         if not isinstance(ac_target, ActorCriticTarget):
             raise ValueError(f'{who}: ac_target must be a td.ActorCriticTarget')
-        if len(ac_target.critics) != len(self.critics):
-            raise ValueError(f'{who}: the target has {len(ac_target.critics)} critic(s), the learner {len(self.critics)}')
-        pairs = list(zip((self.actor,) + self.critics, (ac_target.mu_target,) + ac_target.critics))
-        for mine, net in pairs:
-            if (net.n_in, net.hidden, net.n_out) != (mine.n_in, mine.hidden, mine.n_out) or net.device != mine.device:
-                raise ValueError(f'{who}: the {net.what} is {net.text()} on {net.device}, the learner\'s {mine.what} '
-                                 f'{mine.text()} on {mine.device}')
-        if not 0.0 <= tau <= 1.0:
-            raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
-        for mine, net in pairs:
+        for mine, net in self._target_pairs(who, ac_target, ac_target.mu_target, tau):
             mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
 
 
-def learn_sac_workspace_bytes(obs_dim, actor_hidden, action_dim, critic1_hidden, critic2_hidden, max_batch):
-    """bytes of the ACTOR's workspace for the SAC actor step (s2d_learn_sac_workspace_bytes): learn_actor_workspace_bytes' parts for
-    the actor's parameters (D -> ... -> 2A), a second row of block partials (the rows' logp), and the blocks' images where 64 rows of
-    ALL the networks ([obs | action] padded to a multiple of 4, every layer's outputs of the actor and of each critic, the head's A
-    noise words) and three words a row do not fit the LDS.  critic2_hidden: None for one critic."""
-    P = learn_param_count(obs_dim, actor_hidden, 2 * action_dim)
-    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
-    pitch = ((obs_dim + action_dim + 3) // 4 * 4 + sum(actor_hidden) + 2 * action_dim + sum(critic1_hidden) + 1
-             + (sum(critic2_hidden) + 1 if critic2_hidden is not None else 0) + action_dim) | 1
-    words = _round64(blocks * P) + _round64(chunks) + 2 * _round64(blocks)
-    if BLOCK_ROWS * (pitch + 3) * 4 > LDS_BYTES:
-        words += _round64(blocks * BLOCK_ROWS * pitch)
-    return words * 4
-
-
-class SACLearner(_CriticSteps):
+class SACLearner(_ActorCritic):
     """The Soft Actor-Critic update in HIP (s2d_learn_critic with the 'mse' loss per critic, s2d_learn_sac_actor in include/s2d.h),
     the steps that follow SacTarget.target:
 
@@ -527,6 +544,7 @@ class SACLearner(_CriticSteps):
     rebound as views of it, as QLearner does.  The actor's step never forms or touches a critic's gradient.  ``alpha`` is the [1]
     device tensor SacTarget.target takes; every step is a linear chain on torch's current stream, capturable; learning rates are
     device words (``set_lr``).  tests/learn_sac_ref.c."""
+    _sac = True
 
     def __init__(self, actor, q1, q2=None, ent_coef='auto', target_entropy=None, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4,
                  betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, max_batch=4096, seed=0, device=None):
@@ -540,27 +558,10 @@ class SACLearner(_CriticSteps):
         if not (alpha_lr >= 0.0):
             raise ValueError(f'{who}: alpha_lr must be >= 0, got {alpha_lr}')
         b1, b2 = _check_optimiser(who, max_batch, min(actor_lr, critic_lr), betas, eps)
-        self.actor = _StepNet(who, 'actor', actor, device, False, actor_lr, b1, b2, eps, max_grad_norm)
-        dev = device if device is not None else self.actor.device
-        names = ('critic',) if q2 is None else ('critic 1', 'critic 2')
-        self.critics = tuple(_StepNet(who, n, mod, dev, False, critic_lr, b1, b2, eps, max_grad_norm) for n, mod in zip(names, (q1, q2)))
-        a = self.actor
-        if a.n_out % 2 or not 1 <= a.n_out // 2 <= MAX_ACTION:
-            raise ValueError(f'{who}: the actor has {a.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
-                             f'1 .. {MAX_ACTION}')
-        A = a.n_out // 2
-        if a.n_in > MAX_OBS:
-            raise ValueError(f'{who}: the actor\'s input width must be in [1, {MAX_OBS}], got {a.n_in}')
-        for c in self.critics:
-            if c.n_in != a.n_in + A or c.n_out != 1:
-                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {a.text()} it must take obs_dim + A = '
-                                 f'{a.n_in} + {A} inputs and give one output')
-            if c.device != a.device:
-                raise ValueError(f'{who}: the {c.what} is on {c.device}, the actor on {a.device}')
+        self._networks(who, actor, q1, q2, device, actor_lr, critic_lr, b1, b2, eps, max_grad_norm, max_batch)
         if target_entropy is not None and not isinstance(target_entropy, (int, float)):
             raise ValueError(f'{who}: target_entropy must be a float (or None: -A), got {target_entropy!r}')
-        self.device, self.obs_dim, self.action_dim = a.device, a.n_in, A
-        self.loss_kind, self.max_batch = AC_LOSSES.index('mse'), max_batch
+        a, A = self.actor, self.action_dim
         self.seed = int(seed) & (2 ** 64 - 1)
         self.auto = ent_coef == 'auto'
         self.target_entropy = float(-A if target_entropy is None else target_entropy)
@@ -572,9 +573,7 @@ class SACLearner(_CriticSteps):
         self.alpha_stats = torch.tensor([0.0, 0.0, float(self.alpha[0])], dtype=f32).to(self.device)
         self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)       # steps so far: the Philox counter's middle words
         hc = [c.hidden for c in self.critics]
-        a.bind(learn_sac_workspace_bytes(a.n_in, a.hidden, A, hc[0], hc[1] if len(hc) > 1 else None, max_batch))
-        for c in self.critics:
-            c.bind(learn_workspace_bytes(c.n_in, c.hidden, 1, max_batch))
+        self._bind('mse', learn_sac_workspace_bytes(a.n_in, a.hidden, A, hc[0], hc[1] if len(hc) > 1 else None, max_batch))
 
     @classmethod
     def from_modules(cls, actor, q1, q2=None, ent_coef='auto', target_entropy=None, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4,
@@ -597,29 +596,15 @@ class SACLearner(_CriticSteps):
         return t
 
     def _actor_call(self, fn, name, batch, action_out, logp_out, q_out):
-        who, f32 = f'SACLearner.{name}', torch.float32
-        B, obs = self._obs(who, batch, ('obs',))
-        outs = [_arr(who, self.device, 'action_out', action_out, f32, (B, self.action_dim)) if action_out is not None else None,
-                _arr(who, self.device, 'logp_out', logp_out, f32, (B,)) if logp_out is not None else None,
-                _arr(who, self.device, 'q_out', q_out, f32, (B,)) if q_out is not None else None]
-        self._need_gpu(who)
-        lib = _capi.load_library()
-        net, st = self.actor.c_structs()
-        cs = [c.c_structs()[0] for c in self.critics]
+        who, dev = f'SACLearner.{name}', self.device
+        B, obs = _batch_obs(who, self, batch, ('obs',))
+        outs = [_opt(who, dev, 'action_out', action_out, (B, self.action_dim)), _opt(who, dev, 'logp_out', logp_out, (B,)),
+                _opt(who, dev, 'q_out', q_out, (B,))]
+        cs = [C.byref(c.c_structs()[0]) for c in self.critics]
         t = self.alpha_struct()
-        with torch.cuda.device(self.device):
-            rc = getattr(lib, fn)(B, C.byref(net), C.byref(st), C.byref(cs[0]), C.byref(cs[1]) if len(cs) > 1 else None, obs,
-                                  C.c_void_p(self.alpha.data_ptr()), C.byref(t) if t is not None else None,
-                                  C.c_void_p(self.draws.data_ptr()), self.seed, *outs,
-                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, fn)
-
-    def step_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
-        """One update of the critic (of both, where ``q2`` was given) with the loss e^2 / 2 on the dict DeviceReplay.sample returns
-        (its 'obs' [B, obs_dim] and 'action' float32 [B, A]) towards `target` float32 [B] (SacTarget.target's), with the importance
-        weights `weight` [B] where given.  td_abs_out [B] <- |q1 - target|, q_out [B] <- critic 1's forward values.  Stream-ordered
-        on torch's current stream, capturable; returns nothing."""
-        self._critic_call('s2d_learn_critic', 'step_critic', batch, target, weight, td_abs_out, q_out)
+        _launch(who, dev, fn, [(B, *map(C.byref, self.actor.c_structs()), cs[0], cs[1] if len(cs) > 1 else None, obs,
+                                C.c_void_p(self.alpha.data_ptr()), C.byref(t) if t is not None else None, C.c_void_p(self.draws.data_ptr()),
+                                self.seed, *outs)])
 
     def step_actor(self, batch, action_out=None, logp_out=None, q_out=None):
         """One update of the actor on (alpha * logp - min Q(obs, a)).mean() over batch['obs'] and, with ent_coef='auto', of log_alpha;
@@ -633,12 +618,6 @@ class SACLearner(_CriticSteps):
         self.step_critic(batch, target, weight=weight, td_abs_out=td_abs_out, q_out=q_out)
         self.step_actor(batch)
 
-    def grad_critic(self, batch, target, weight=None, td_abs_out=None, q_out=None):
-        """The flat, unclipped gradient [P] of critic 1's loss (with ``q2`` the tuple of both critics'; views, written again by the
-        next call), with the critic's statistics set, without touching parameters or optimiser state."""
-        self._critic_call('s2d_learn_critic_grad', 'grad_critic', batch, target, weight, td_abs_out, q_out)
-        return self.critics[0].grad if len(self.critics) == 1 else tuple(c.grad for c in self.critics)
-
     def grad_actor(self, batch, action_out=None, logp_out=None, q_out=None):
         """The flat, unclipped gradient [P] of the actor's loss at the noise the next step will draw, with the actor's statistics,
         ``entropy`` and ``alpha_loss`` set, without touching anything else (``draws`` included)."""
@@ -646,11 +625,6 @@ class SACLearner(_CriticSteps):
         return self.actor.grad
 
     # ------------------------------------------------------------------ state
-    critic_loss = property(lambda self: self.critics[0].stats.tolist()[0], doc="critic 1's last mean loss e^2 / 2 (synchronises)")
-    actor_loss = property(lambda self: self.actor.stats.tolist()[0], doc="the actor's last loss: mean(alpha logp - min q) (synchronises)")
-    actor_grad_norm = property(lambda self: self.actor.stats.tolist()[1], doc="the actor's last gradient norm before the clip")
-    actor_clip_scale = property(lambda self: self.actor.stats.tolist()[2], doc="the factor the actor's last gradient was scaled by")
-
     def _alpha_stat(self, i):
         if not self.auto:
             raise ValueError('SACLearner: the entropy coefficient is fixed: the temperature has no statistics (ent_coef=\'auto\')')
@@ -662,18 +636,13 @@ class SACLearner(_CriticSteps):
 
     def set_lr(self, actor=None, critic=None, alpha=None):
         """the learning rates of the steps enqueued from now on: device writes, also between the replays of a captured graph"""
-        if actor is not None:
-            self.actor.hyper[0:1].fill_(float(actor))
-        if critic is not None:
-            for c in self.critics:
-                c.hyper[0:1].fill_(float(critic))
+        _ActorCritic.set_lr(self, actor, critic)
         if alpha is not None:
             self.alpha_hyper[0:1].fill_(float(alpha))
 
     def reset_optimizer(self):
         """Adam as new for every network and for log_alpha: m = v = 0, both beta products 1"""
-        for n in (self.actor,) + self.critics:
-            n.reset()
+        _ActorCritic.reset_optimizer(self)
         self.alpha_m_v.zero_()
         self.alpha_hyper[5:7].fill_(1.0)
 
@@ -686,51 +655,13 @@ class SACLearner(_CriticSteps):
         who = 'SACLearner.update_targets'
         if not isinstance(sac_target, SacTarget):
             raise ValueError(f'{who}: sac_target must be a td.SacTarget')
-        if len(sac_target.critics) != len(self.critics):
-            raise ValueError(f'{who}: the target has {len(sac_target.critics)} critic(s), the learner {len(self.critics)}')
-        pairs = list(zip((self.actor,) + self.critics, (sac_target.actor,) + sac_target.critics))
-        for mine, net in pairs:
-            if (net.n_in, net.hidden, net.n_out, net.activation) != (mine.n_in, mine.hidden, mine.n_out, mine.activation) \
-                    or net.device != mine.device:
-                raise ValueError(f'{who}: the {net.what} is {net.text()} ({net.activation}) on {net.device}, the learner\'s {mine.what} '
-                                 f'{mine.text()} ({mine.activation}) on {mine.device}')
-        if not 0.0 <= tau <= 1.0:
-            raise ValueError(f'{who}: tau must be in [0, 1], got {tau}')
-        for mine, net in pairs[1:]:
+        for mine, net in self._target_pairs(who, sac_target, sac_target.actor, tau)[1:]:
             mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
         with torch.no_grad():
             sac_target.actor.params.copy_(self.actor.params)
 
 
-PPO_MAX_GROUPS = 256      # S2D_LEARN_PPO_MAX_GROUPS
-PPO_HEADS = ('categorical', 'gaussian')
-
-
-def learn_ppo_workspace_bytes(obs_dim, pi_hidden, n_out, vf_hidden, head, max_batch):
-    """bytes of the PPO learner's workspace, by the arithmetic of the C layout (s2d_learn_ppo_workspace_bytes): the partial gradients
-    and statistics of at most 256 groups of blocks, the chunk sums of the norm, the advantage pre-pass's two words and block sums
-    and, where 64 rows of BOTH networks do not fit the LDS, the groups' images; every part rounded up to 64 words.  head: 0 / 1."""
-    P = learn_param_count(obs_dim, pi_hidden, n_out) + learn_param_count(obs_dim, vf_hidden, 1) + (n_out if head else 0)
-    blocks, chunks = (max_batch + BLOCK_ROWS - 1) // BLOCK_ROWS, (P + NORM_CHUNK - 1) // NORM_CHUNK
-    groups = min(blocks, PPO_MAX_GROUPS)
-    pitch = ((obs_dim + 3) // 4 * 4 + sum(pi_hidden) + n_out + sum(vf_hidden) + 1 + (n_out if head else 0)) | 1
-    words = _round64(groups * P) + _round64(chunks) + _round64(groups * 8) + 64 + _round64(blocks)
-    if BLOCK_ROWS * (pitch + 6) * 4 > LDS_BYTES:
-        words += _round64(groups * BLOCK_ROWS * pitch)
-    return words * 4
-
-
-class _Shape:
-    """the shape of one network of PPOLearner, as _fill_shape and _net_text read it"""
-
-    def __init__(self, who, what, module):
-        self.linears, self.hidden, self.n_in, self.n_out, self.activation = _read_shape(who, what, module)
-        self.what, self.module = what, module
-
-    text = _net_text
-
-
-class PPOLearner:
+class PPOLearner(_Stepped):
     """The PPO update in HIP (s2d_learn_ppo in include/s2d.h): what the examples' minibatch loop does in torch --
 
         logp, entropy = dist(pi(obs[i])).log_prob(action[i]), .entropy();  a = normalised advantage[i]
@@ -750,7 +681,7 @@ class PPOLearner:
     def __init__(self, pi, vf, log_std=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5, clip_range=0.2, vf_coef=0.5,
                  ent_coef=0.0, normalize_advantage=True, max_batch=65536, device=None):
         who = 'PPOLearner'
-        self.pi, self.vf = _Shape(who, 'policy network', pi), _Shape(who, 'value network', vf)
+        self.pi, self.vf = _StepNet(who, 'policy network', pi), _StepNet(who, 'value network', vf)   # their shapes: the buffers are the learner's
         p, q = self.pi, self.vf
         self.head = 0 if log_std is None else 1
         if q.n_in != p.n_in or q.n_out != 1:
@@ -766,21 +697,13 @@ class PPOLearner:
         b1, b2 = _check_optimiser(who, max_batch, lr, betas, eps)
         if not (clip_range >= 0.0 and vf_coef >= 0.0 and ent_coef >= 0.0):
             raise ValueError(f'{who}: clip_range, vf_coef and ent_coef must be >= 0, got {clip_range}, {vf_coef}, {ent_coef}')
-        dev = torch.device(device if device is not None else p.linears[0].weight.device)
-        f32 = torch.float32
         self.obs_dim, self.n_out, self.max_batch, self.normalize_advantage = p.n_in, p.n_out, max_batch, bool(normalize_advantage)
         self.P_pi, self.P_vf = learn_param_count(p.n_in, p.hidden, p.n_out), learn_param_count(q.n_in, q.hidden, 1)
-        P = self.P_pi + self.P_vf + (p.n_out if self.head else 0)
-        self.params = torch.zeros(P, dtype=f32, device=dev)
-        self.device = self.params.device
-        self.m, self.v, self._grad = (torch.zeros(P, dtype=f32, device=self.device) for _ in range(3))
-        self.hyper = torch.tensor([lr, b1, b2, eps, max_grad_norm, 1.0, 1.0, clip_range, vf_coef, ent_coef], dtype=f32).to(self.device)
-        self.stats = torch.zeros(8, dtype=f32, device=self.device)
-        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.workspace = torch.zeros(learn_ppo_workspace_bytes(p.n_in, p.hidden, p.n_out, q.hidden, self.head, max_batch) // 4, dtype=f32,
-                                     device=self.device)
-        _rebind(self.params[:self.P_pi], p.linears)
-        _rebind(self.params[self.P_pi:self.P_pi + self.P_vf], q.linears)
+        self._alloc(self.P_pi + self.P_vf + (p.n_out if self.head else 0), device if device is not None else p._linears[0].weight.device,
+                    lr, b1, b2, eps, max_grad_norm, (clip_range, vf_coef, ent_coef), 8)
+        self._alloc_workspace(learn_ppo_workspace_bytes(p.n_in, p.hidden, p.n_out, q.hidden, self.head, max_batch))
+        _rebind(self.params[:self.P_pi], p._linears)
+        _rebind(self.params[self.P_pi:self.P_pi + self.P_vf], q._linears)
         self.log_std = log_std
         if self.head:
             with torch.no_grad():
@@ -832,16 +755,9 @@ class PPOLearner:
         b.obs, b.action = arr("rollout['obs']", obs, f32, (R, self.obs_dim)), action
         b.logp_old, b.advantage = arr("rollout['logp']", rollout['logp'], f32, (R,)), arr("rollout['advantage']", rollout['advantage'], f32, (R,))
         b.ret = arr("rollout['return']", rollout['return'], f32, (R,))
-        b.index = arr('index', index, torch.int32, (B,)) if index is not None else None
-        b.out_logp = arr('logp_out', logp_out, f32, (B,)) if logp_out is not None else None
-        b.out_value = arr('value_out', value_out, f32, (B,)) if value_out is not None else None
-        if self.device.type != 'cuda':
-            raise ValueError(f'{who}: the networks are on {self.device}; the kernels need a GPU (there is no CPU path)')
-        lib = _capi.load_library()
-        q = self.c_structs()
-        with torch.cuda.device(self.device):
-            rc = getattr(lib, fn)(C.byref(q), C.byref(b), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, fn)
+        b.index = _opt(who, self.device, 'index', index, (B,), torch.int32)
+        b.out_logp, b.out_value = _opt(who, self.device, 'logp_out', logp_out, (B,)), _opt(who, self.device, 'value_out', value_out, (B,))
+        _launch(who, self.device, fn, [(C.byref(self.c_structs()), C.byref(b))])
 
     def step(self, rollout, index=None, logp_out=None, value_out=None):
         """One update on the minibatch that `index` (int32 [B]; None: every row, in order) names in the rollout: a dict with 'obs'
@@ -877,10 +793,6 @@ class PPOLearner:
     approx_kl = property(lambda self: self._stat(6), doc='mean((ratio - 1) - log ratio) of the last call (SB3\'s approx_kl)')
     clip_fraction = property(lambda self: self._stat(7), doc='the share of the last call\'s rows with |ratio - 1| > clip_range')
 
-    def set_lr(self, lr):
-        """the learning rate of the steps enqueued from now on: a device write, also between the replays of a captured graph"""
-        self.hyper[0:1].fill_(float(lr))
-
     def set_clip_range(self, clip_range):
         """the clip range of the steps enqueued from now on (a schedule writes it as it writes lr)"""
         self.hyper[7:8].fill_(float(clip_range))
@@ -891,12 +803,6 @@ class PPOLearner:
             self.hyper[8:9].fill_(float(vf_coef))
         if ent_coef is not None:
             self.hyper[9:10].fill_(float(ent_coef))
-
-    def reset_optimizer(self):
-        """Adam as new: m = v = 0, both beta products 1"""
-        self.m.zero_()
-        self.v.zero_()
-        self.hyper[5:7].fill_(1.0)
 
 
 __all__ = ['QLearner', 'ActorCriticLearner', 'SACLearner', 'PPOLearner', 'learn_workspace_bytes', 'learn_actor_workspace_bytes',
