@@ -5,6 +5,8 @@
 // everything read when the kernels run, so sample -> target sits in one captured graph.
 // s2d_td_target_sac is Soft Actor-Critic's: the ONLINE actor's squashed-Gaussian head (s2d_sac_head.h) draws the next action with
 // a Philox stream of its own, and the target carries the entropy term, reward + discount * (min Q' - alpha * logp).
+// s2d_td_target_td3 is TD3's whole target: the DDPG / twin target with clipped Gaussian noise on the target actor's action
+// (target-policy smoothing), drawn from a third Philox stream.
 //
 // The network is the streamed-weight MLP of s2d_wide_net.h (wide_group / wide_layer and the fragment order are its) with a RUN-TIME
 // input width n_in in [1, 256]: layer 1 takes ceil(n_in / 4) k-steps over x_k = 0 against zero weights past n_in, so at n_in = 10 it
@@ -314,6 +316,92 @@ __global__ __launch_bounds__(kBlock) void s2d_td_target_sac_kernel(TdNetDev acto
   }
 }
 
+// s2d_td_target_td3: the target actor's tanh head with TD3's target-policy smoothing, a' = clamp(tanh_spec(y) + clamp(sigma z, -c, c),
+// -1, 1), into the critics' input row, critic 1 and (TWIN) critic 2 on one row tile.  As in the SAC target a lane runs the head of
+// its own batch row, so a row's one or two Philox blocks are drawn once.  z: Philox4x32-10 with key seed at counter {row, draws_lo,
+// draws_hi, (S2D_TD3_STREAM << 16) | blk}, blk = 0 for z0..z3, blk = 1 (A > 4 only) for z4..z7.
+struct TdTd3Args {
+  const float* noise;          // two device words: sigma (target_policy_noise), clip (target_noise_clip)
+  const uint64_t* draws;       // one device word: the calls so far
+  uint32_t seed_lo, seed_hi;
+};
+// one action word: a multiply, a clamp, an add, a clamp; a NaN passes through both clamps (torch.clamp)
+S2D_DEV float td3_smooth(float m, float sigma, float clip, float z) {
+  float n = __fmul_rn(sigma, z);
+  n = n < -clip ? -clip : (n > clip ? clip : n);
+  const float s = __fadd_rn(m, n);
+  return s < -1.0f ? -1.0f : (s > 1.0f ? 1.0f : s);
+}
+template <bool TWIN>
+__global__ __launch_bounds__(kBlock) void s2d_td_target_td3_kernel(TdNetDev actor, TdNetDev c1, TdNetDev c2, TdPlanDev pl, int64_t batch,
+                                                                   const float* __restrict__ next_obs, const float* __restrict__ reward,
+                                                                   const float* __restrict__ discount, TdTd3Args ta,
+                                                                   float* __restrict__ out_target, float* __restrict__ out_q,
+                                                                   float* __restrict__ out_action) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t wave_first = i - lane;
+  if (wave_first >= batch) return;
+  const int T = pl.tiles;
+  float* const x = smem + (size_t)wv * pl.wave_words;
+  float* const ia = x + T * 16 * pl.xpitch;
+  float* const ib = ia + T * 16 * pl.rpitch;
+  float* const qv = ib + T * 16 * pl.rpitch;
+  const int D = actor.n_in, A = actor.na, kp = 4 * c1.ks1;   // the critics' padded row covers the actor's
+  const float sigma = ta.noise[0], clip = ta.noise[1];
+  const uint64_t draws = *ta.draws;
+  float qmin = 0.0f;
+  for (int nt = 0; nt < 4; nt += T) {
+    const int64_t row0 = wave_first + 16 * nt;
+    td_load_rows(next_obs, row0, batch, D, kp, 16 * T, x, pl.xpitch, lane);
+    wave_lds_fence();
+    const bool mine = (lane >> 4) >= nt && (lane >> 4) < nt + T;
+    float* const qp = qv + 16 * nt * pl.qpitch;
+#pragma unroll 1
+    for (int v = 0; v < (TWIN ? 3 : 2); ++v) {
+      const TdNetDev d = v == 0 ? actor : TWIN ? td_pick(v == 1, c1, c2) : c1;
+      if (T == 4) td_layers<4>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else if (T == 2) td_layers<2>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      else td_layers<1>(d, x, pl.xpitch, ia, ib, pl.rpitch, qp, pl.qpitch, lane);
+      if (v == 0) {
+        if (mine) {
+          // the head of row i: a' behind the observation words of its row (the words past D + A stay zero)
+          const float* const y = qv + lane * pl.qpitch;
+          float* const xa = x + (lane - 16 * nt) * pl.xpitch + D;
+          float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+          const U4 w = philox4x32_10((uint32_t)i, (uint32_t)draws, (uint32_t)(draws >> 32), (uint32_t)S2D_TD3_STREAM << 16, ta.seed_lo,
+                                     ta.seed_hi);
+          box_muller(w.x, w.y, z[0], z[1]);
+          box_muller(w.z, w.w, z[2], z[3]);
+          if (A > 4) {
+            const U4 w2 = philox4x32_10((uint32_t)i, (uint32_t)draws, (uint32_t)(draws >> 32), ((uint32_t)S2D_TD3_STREAM << 16) | 1u,
+                                        ta.seed_lo, ta.seed_hi);
+            box_muller(w2.x, w2.y, z[4], z[5]);
+            box_muller(w2.z, w2.w, z[6], z[7]);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if (j < A) {
+              const float a = td3_smooth(tanh_spec(y[j]), sigma, clip, z[j]);
+              xa[j] = a;
+              if (out_action && i < batch) out_action[i * A + j] = a;
+            }
+          }
+        }
+      } else if (mine) {
+        const float q = qv[lane * pl.qpitch];
+        qmin = (v == 1 || q < qmin) ? q : qmin;              // q2 < q1 ? q2 : q1: a NaN in q2 never replaces q1
+      }
+      wave_lds_fence();
+    }
+  }
+  if (i < batch) {
+    out_target[i] = td_target(reward[i], discount[i], qmin);
+    if (out_q) out_q[i] = qmin;
+  }
+}
+
 // what follows the target kernel on the same stream: the next call (the next replay of a captured graph) draws fresh noise
 __global__ void s2d_td_draws_kernel(uint64_t* __restrict__ draws) { *draws += 1; }
 
@@ -466,6 +554,61 @@ S2D_API int s2d_td_target_ac(int64_t batch, const S2DTdNet* actor, const S2DTdNe
   if (critic2) s2d_internal_wide_pack(wide_pack_args(d2, d2.n_in), critic2->params, critic2->workspace, s);
   hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, da, d1, d2, pl, batch, next_obs, reward,
                      discount, out_target, out_q, out_action);
+  return launched(who);
+}
+
+S2D_API int s2d_td_target_td3(int64_t batch, const S2DTdNet* actor, const S2DTdNet* critic1, const S2DTdNet* critic2, const float* next_obs,
+                              const float* reward, const float* discount, const float* noise, uint64_t* draws, uint64_t seed,
+                              float* out_target, float* out_q, float* out_action, void* stream) {
+  static const std::string who = "s2d_td_target_td3";
+  if (!actor || !critic1) return fail(who, "actor and critic1 must be non-NULL");
+  TdNetDev da{}, d1{}, d2{};
+  int wmax = 0;
+  if (check_net(who, "actor", actor, da, wmax) != S2D_OK || check_net(who, "critic1", critic1, d1, wmax) != S2D_OK) return S2D_EINVAL;
+  if (critic2 && check_net(who, "critic2", critic2, d2, wmax) != S2D_OK) return S2D_EINVAL;
+  if (actor->n_out > kTdMaxAction) return fail(who, "actor: n_out must be in [1, 8]");
+  const int A = actor->n_out;
+  for (const S2DTdNet* c : {critic1, critic2}) {
+    if (!c) continue;
+    if (c->n_in != actor->n_in + A || c->n_out != 1)
+      return fail(who, std::string(c == critic1 ? "critic1" : "critic2") + " is " + net_text(c) + ", the actor " + net_text(actor) +
+                           ": a critic's n_in must be the actor's n_in + n_out, its n_out 1");
+  }
+  if (share(actor, da, critic1, d1) || (critic2 && (share(actor, da, critic2, d2) || share(critic1, d1, critic2, d2))))
+    return fail(who, "two networks share a workspace: every network of a call needs its own");
+  if (check_batch(who, batch, next_obs, reward, discount, out_target, out_q, out_action) != S2D_OK) return S2D_EINVAL;
+  if (!noise || misaligned(noise, 4)) return fail(who, "noise must be a non-NULL, 4-byte aligned device pointer (sigma, clip)");
+  if (!draws || misaligned(draws, 8)) return fail(who, "draws must be a non-NULL, 8-byte aligned device pointer");
+  const struct { const void* p; size_t bytes; } outs[3] = {{out_target, (size_t)batch * 4}, {out_q, (size_t)batch * 4},
+                                                            {out_action, (size_t)batch * A * 4}};
+  const struct { const void* p; size_t bytes; const char* name; } words[2] = {{draws, sizeof(uint64_t), "draws"}, {noise, 2 * sizeof(float), "noise"}};
+  for (const auto& w : words) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(w.p);
+    for (const auto& o : outs) {
+      const uintptr_t q = reinterpret_cast<uintptr_t>(o.p);
+      if (o.p && p < q + o.bytes && q < p + w.bytes) return fail(who, std::string(w.name) + " must not overlap an output");
+    }
+  }
+  TdPlanDev pl{};
+  int waves = 0;
+  size_t lds = 0;
+  if (make_plan(who, batch, wmax, critic1->n_in, actor->n_out, pl, waves, lds) != S2D_OK) return S2D_EINVAL;
+  using Kernel = void (*)(TdNetDev, TdNetDev, TdNetDev, TdPlanDev, int64_t, const float*, const float*, const float*, TdTd3Args, float*, float*,
+                          float*);
+  const Kernel k = critic2 ? s2d_td_target_td3_kernel<true> : s2d_td_target_td3_kernel<false>;
+  if (!allow_lds_slot<TdLds>(reinterpret_cast<const void*>(k), critic2 ? 7 : 6)) {
+    s2d_internal_set_error((who + ": hipGetDevice or hipFuncSetAttribute failed").c_str());
+    return S2D_EHIP;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int threads = waves * kWave;
+  const TdTd3Args ta{noise, draws, (uint32_t)seed, (uint32_t)(seed >> 32)};
+  s2d_internal_wide_pack(wide_pack_args(da, da.n_in), actor->params, actor->workspace, s);
+  s2d_internal_wide_pack(wide_pack_args(d1, d1.n_in), critic1->params, critic1->workspace, s);
+  if (critic2) s2d_internal_wide_pack(wide_pack_args(d2, d2.n_in), critic2->params, critic2->workspace, s);
+  hipLaunchKernelGGL(k, dim3((unsigned)((batch + threads - 1) / threads)), dim3(threads), lds, s, da, d1, d2, pl, batch, next_obs, reward,
+                     discount, ta, out_target, out_q, out_action);
+  hipLaunchKernelGGL(s2d_td_draws_kernel, dim3(1), dim3(1), 0, s, draws);
   return launched(who);
 }
 

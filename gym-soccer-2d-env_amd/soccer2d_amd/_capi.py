@@ -238,6 +238,8 @@ PROTOTYPES = (
                                   C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_td_target_ac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
+    ('s2d_td_target_td3', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_td_target_sac', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p)),

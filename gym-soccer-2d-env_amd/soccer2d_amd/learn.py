@@ -516,13 +516,13 @@ class ActorCriticLearner(_ActorCritic):
         return self.actor.grad
 
     def update_targets(self, ac_target, tau=1.0):
-        """The learner's weights into a td.ActorCriticTarget's target networks: a hard copy (tau = 1) or a Polyak step, one
-        ``copy_`` or ``lerp_`` per network from flat buffer to flat buffer, and one more flat copy each keeps the target MODULES
-        equal (their parameters become views of mirror buffers), as QLearner.update_target."""
-        from .td import ActorCriticTarget
+        """The learner's weights into a td.ActorCriticTarget's (or a td.Td3Target's) target networks: a hard copy (tau = 1) or a
+        Polyak step, one ``copy_`` or ``lerp_`` per network from flat buffer to flat buffer, and one more flat copy each keeps the
+        target MODULES equal (their parameters become views of mirror buffers), as QLearner.update_target."""
+        from .td import ActorCriticTarget, Td3Target
         who = 'ActorCriticLearner.update_targets'
-        if not isinstance(ac_target, ActorCriticTarget):
-            raise ValueError(f'{who}: ac_target must be a td.ActorCriticTarget')
+        if not isinstance(ac_target, (ActorCriticTarget, Td3Target)):
+            raise ValueError(f'{who}: ac_target must be a td.ActorCriticTarget or a td.Td3Target')
         for mine, net in self._target_pairs(who, ac_target, ac_target.mu_target, tau):
             mine.mirror = _into_target(mine.params, net, tau, mine.mirror)
 

@@ -1,9 +1,10 @@
-"""QTarget / ActorCriticTarget: the off-policy learners' TD targets from their target networks in one launch
+"""QTarget / ActorCriticTarget / Td3Target: the off-policy learners' TD targets from their target networks in one launch
 (s2d_td_target_q / s2d_td_target_ac in include/s2d.h), the step that follows DeviceReplay.sample in DQN, Double DQN, DDPG and TD3:
 
     target = reward + discount * max_a Q'(next_obs, a)                          QTarget
     target = reward + discount * Q'(next_obs, argmax_a Q(next_obs, a))          QTarget with online=
     target = reward + discount * min_i Q'_i(next_obs, tanh-actor'(next_obs))    ActorCriticTarget
+    target = reward + discount * min_i Q'_i(next_obs, that action, smoothed)    Td3Target
 
 instead of the 8 - 15 small torch ops of ``r + d * q_target(next_obs).max(dim=1).values``.  The networks are the streamed-weight
 MLP of the wide actors (Linear-(F-Linear) x L, L = 1 .. 5, widths multiples of 4 in [8, 400], F = ReLU, Tanh or Sigmoid) with any
@@ -13,8 +14,9 @@ the weights, bit for bit, that the fused actor acts on.  Engine-independent: any
 Each network keeps ONE flat fp32 parameter buffer and a workspace.  The kernels read the buffers when they run: ``sync()``
 reloads them from the modules (after ``load_state_dict`` or a Polyak step for the target networks, after every optimiser step
 for ``online``), and a captured graph computes with whatever they hold at replay.  The online Q-network's forward / backward pass and the
-optimiser are soccer2d_amd.learn.QLearner's, the DDPG / TD3 update soccer2d_amd.learn.ActorCriticLearner's.  Out of scope: the target is not fused into the sample launch, and TD3's
-target-policy smoothing noise is not added.
+optimiser are soccer2d_amd.learn.QLearner's, the DDPG / TD3 update soccer2d_amd.learn.ActorCriticLearner's.  Out of scope: the target is not fused into the sample launch.
+TD3's target-policy smoothing noise is Td3Target's (s2d_td_target_td3): ActorCriticTarget's launch with clipped Gaussian noise on
+the target actor's action, from a Philox stream and a device counter of its own.
 
 SacTarget is Soft Actor-Critic's: the ONLINE actor's squashed-Gaussian head draws the next action, and the target carries the
 entropy term, reward + discount * (min_i Q'_i(next_obs, a') - alpha * logp(a')) (s2d_td_target_sac)."""
@@ -210,7 +212,7 @@ class QTarget(_Target):
 
 class ActorCriticTarget(_Target):
     """``reward + discount * q_target(cat(next_obs, mu_target(next_obs)))`` (DDPG), with ``q_target2`` the smaller of the two
-    critics' values (TD3's clipped double-Q, without target-policy smoothing noise), in one launch.  mu_target is
+    critics' values (TD3's clipped double-Q; with target-policy smoothing noise: Td3Target), in one launch.  mu_target is
     Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs (SB3's ``actor_target.mu``); a critic is Linear-(F-Linear) x L from
     obs_dim + A inputs to one output (SB3's ``critic_target.qf0``)."""
 
@@ -248,6 +250,70 @@ class ActorCriticTarget(_Target):
             rc = lib.s2d_td_target_ac(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, *outs,
                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _capi.check(lib, rc, 's2d_td_target_ac')
+        return result
+
+
+class Td3Target(_Target):
+    """TD3's target in one launch (s2d_td_target_td3): ActorCriticTarget's with target-policy smoothing,
+
+        a'     = (mu_target(next_obs) + (sigma * z).clamp(-clip, clip)).clamp(-1, 1)     z ~ N(0, 1), fresh every call
+        target = reward + discount * min_i Q'_i(next_obs, a')
+
+    The networks are ActorCriticTarget's: mu_target Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs, a critic Linear-(F-Linear) x L
+    from obs_dim + A inputs to one output.  sigma (SB3's ``target_policy_noise``) and clip (``target_noise_clip``) are two device
+    words the target owns (``noise``, written by ``set_noise``); z is Philox with key `seed` at a device counter the target owns
+    (``draws``): every call, and every replay of a captured graph, advances it by one."""
+
+    _name = 'Td3Target'
+
+    def __init__(self, mu_target, q_target, q_target2=None, target_policy_noise=0.2, target_noise_clip=0.5, seed=0, device=None):
+        who = 'Td3Target'
+        act = _Net(who, 'target actor', mu_target, device, tanh_head=True)
+        if not 1 <= act.n_out <= MAX_ACTION:
+            raise ValueError(f'{who}: the target actor has {act.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+        dev = device if device is not None else act.device
+        critics = [_Net(who, 'target critic 1', q_target, dev)]
+        if q_target2 is not None:
+            critics.append(_Net(who, 'target critic 2', q_target2, dev))
+        for c in critics:
+            if c.n_in != act.n_in + act.n_out or c.n_out != 1:
+                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
+                                 f'{act.n_in} + {act.n_out} inputs and give one output')
+        self.mu_target, self.critics = act, tuple(critics)
+        self.action_dim = act.n_out
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self._init_nets([act] + critics)
+        self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)      # calls so far: the Philox counter's middle words
+        self.noise = torch.zeros(2, dtype=torch.float32, device=self.device)    # sigma, clip: read when the kernel runs
+        self.set_noise(target_policy_noise, target_noise_clip)
+
+    @classmethod
+    def from_modules(cls, mu_target, q_target, q_target2=None, target_policy_noise=0.2, target_noise_clip=0.5, seed=0, device=None):
+        """A target shaped like the modules, loaded from them.  device: where the buffers live (default: the actor's)."""
+        return cls(mu_target, q_target, q_target2=q_target2, target_policy_noise=target_policy_noise, target_noise_clip=target_noise_clip,
+                   seed=seed, device=device)
+
+    def set_noise(self, sigma, clip):
+        """sigma (target_policy_noise) and clip (target_noise_clip) into the device words the kernel reads, in place: legal
+        between the replays of a captured graph.  Both are floats >= 0 (clip may be inf: no clipping)."""
+        for name, v in (('sigma', sigma), ('clip', clip)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0.0:
+                raise ValueError(f'Td3Target.set_noise: {name} must be a float >= 0, got {v!r}')
+        self.noise[0].fill_(float(sigma))
+        self.noise[1].fill_(float(clip))
+        return self
+
+    def target(self, batch, out=None, return_q=False):
+        """float32 [B] targets of a sampled batch, as ActorCriticTarget.target.  return_q: (target, q [B], action [B, A]): the
+        bootstrapped value and the smoothed, clamped action it was evaluated at."""
+        B, ins, outs, result = self._batch(batch, out, return_q, torch.float32, (self.action_dim,))
+        lib = _capi.load_library()
+        nets = [n.c_struct() for n in self._nets]
+        with torch.cuda.device(self.device):
+            rc = lib.s2d_td_target_td3(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins,
+                                       C.c_void_p(self.noise.data_ptr()), C.c_void_p(self.draws.data_ptr()), self.seed, *outs,
+                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, 's2d_td_target_td3')
         return result
 
 
@@ -348,4 +414,4 @@ class SacTarget(_Target):
         return result
 
 
-__all__ = ['QTarget', 'ActorCriticTarget', 'SacTarget', 'td_workspace_bytes']
+__all__ = ['QTarget', 'ActorCriticTarget', 'Td3Target', 'SacTarget', 'td_workspace_bytes']

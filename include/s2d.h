@@ -590,7 +590,7 @@ size_t s2d_td_workspace_bytes(const S2DTdNet *shape);
 int s2d_td_target_q(int64_t batch, const S2DTdNet *target, const S2DTdNet *online /* NULL: plain DQN */,
                     const float *next_obs /* [B][n_in] */, const float *reward, const float *discount,
                     float *out_target /* [B] */, float *out_q /* [B] or NULL */, int32_t *out_index /* [B] or NULL */, void *stream);
-/* DDPG, and TD3's clipped double-Q (without target-policy smoothing noise).  Per row b, with D = actor->n_in and A = actor->n_out
+/* DDPG, and TD3's clipped double-Q (with smoothing noise: s2d_td_target_td3).  Per row b, with D = actor->n_in and A = actor->n_out
  * in [1, 8]: a'[i] = tanh_spec(actor(next_obs[b])[i]) (the tanh actor's head without noise and without epsilon); the critics' input
  * row is [next_obs[b] (D words) | a' (A words)], so critic->n_in == D + A and critic->n_out == 1; q = critic1(row)[0], with critic2
  * q = q2 < q1 ? q2 : q1 (a NaN in q2 never replaces q1); out_target[b] as above; out_q[b] <- q, out_action[b][i] <- a'[i] where
@@ -599,6 +599,29 @@ int s2d_td_target_q(int64_t batch, const S2DTdNet *target, const S2DTdNet *onlin
 int s2d_td_target_ac(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
                      const float *next_obs /* [B][actor->n_in] */, const float *reward, const float *discount, float *out_target,
                      float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */, void *stream);
+#define S2D_TD3_STREAM 15 /* Philox stream id of the TD3 target's smoothing noise (no other draw uses it) */
+/* TD3's target: the call above with target-policy smoothing, SB3's (actor_target(next_obs) + noise.clamp(-c, c)).clamp(-1, 1).  Per
+ * row b, with D = actor->n_in and A = actor->n_out in [1, 8]: y = actor(next_obs[b]), m_i = tanh_spec(y_i) (s2d_td_target_ac's
+ * action); z_0 .. z_7 from Philox4x32-10 with key `seed` at counter {b, draws_lo, draws_hi, (S2D_TD3_STREAM << 16) | blk}: blk = 0
+ * gives z0..z3, blk = 1 (drawn only if A > 4) z4..z7, words x, y -> (z0, z1) and z, w -> (z2, z3) through the engine's Box-Muller, as
+ * in the SAC target below.  With sigma = noise[0] (target_policy_noise) and clip = noise[1] (target_noise_clip):
+ *   n_i  = sigma * z_i                                    one fp32 multiply
+ *   n_i  = n_i < -clip ? -clip : (n_i > clip ? clip : n_i)
+ *   s_i  = m_i + n_i                                      one fp32 add, never contracted with the multiply
+ *   a'_i = s_i < -1 ? -1 : (s_i > 1 ? 1 : s_i)
+ * so a NaN passes through both clamps, as in torch.clamp.  The critics' row is [next_obs[b] | a']; q = q1, with critic2
+ * q2 < q1 ? q2 : q1; out_target[b] = reward[b] + (discount[b] * q) as above; out_q[b] <- q, out_action[b][i] <- a'_i (the smoothed,
+ * clamped action) where given.  noise[0], noise[1] and *draws are device words read when the kernel runs; a one-thread kernel on
+ * the same stream then sets *draws += 1, so every call and every replay of a captured graph draws fresh noise and sample -> target
+ * stays one capturable linear chain.  The counter is keyed by the global row: the result does not depend on S2D_TD_PLAN.
+ * sigma = 0: n_i = +-0, so out_target and out_q have s2d_td_target_ac's bits wherever no action word is -0; an action of -0 may come
+ * out as +0 (-0 + +0 = +0).  S2D_EINVAL without a launch as for s2d_td_target_ac, plus: NULL or misaligned noise (4 bytes) or draws
+ * (8 bytes), draws or noise overlapping an output. */
+int s2d_td_target_td3(int64_t batch, const S2DTdNet *actor, const S2DTdNet *critic1, const S2DTdNet *critic2 /* or NULL */,
+                      const float *next_obs, const float *reward, const float *discount,
+                      const float *noise /* device float[2]: sigma (target_policy_noise), clip (target_noise_clip) */,
+                      uint64_t *draws, uint64_t seed,
+                      float *out_target, float *out_q /* or NULL */, float *out_action /* [B][A] or NULL */, void *stream);
 #define S2D_TD_STREAM 13 /* Philox stream id of the SAC target's action noise (no other draw uses it) */
 /* Soft Actor-Critic's entropy-regularised target.  Per row b, with D = actor->n_in and A = actor->n_out / 2 in [1, 8]:
  * y = actor(next_obs[b]) -- the ONLINE actor, as in SB3 --, rows 0 .. A-1 the means, A .. 2A-1 the raw log-std; the head of the SAC
