@@ -68,11 +68,31 @@ static REAL rnd_u01(uint32_t w) { return (REAL)(w >> 8) * R(5.9604644775390625e-
  * Elementary functions.  F64: libm, as pyrusgeom / numpy do.  F32: DESIGN.md section 4.
  * ==================================================================================== */
 #ifdef S2DO_F64
+#ifdef S2DO_SINCOS_QUADRANT
+/* The match oracle's fp64 build (oracle/Makefile): the quadrant is taken out first, as the fp32 spec does below -- r = deg - 90 q is
+ * exact, so the result is exact at every multiple of 90 degrees and odd / even in deg to the last bit.  libm alone gives
+ * sin(180 deg) = 1.2e-16: a back dash straight behind (m_dash: dir += 180) then moved a player sideways by 1e-17 with the same
+ * sign whichever way the pitch is mirrored, and the fp64 reference broke a symmetry that the spec and the kernel keep
+ * (tests/match_symmetry.py).  The reach-ball and GoToCenter builds stay on libm alone, as the reference's Python. */
+static void sincos_deg(REAL deg, REAL *s, REAL *c) {
+  const double DEG2RAD = 3.14159265358979323846 / 180.0;
+  const double q = rint(deg / 90.0);
+  const double r = fma(-q, 90.0, deg);           /* exact: r in [-45, 45] */
+  const double sr = sin(r * DEG2RAD), cr = cos(r * DEG2RAD);
+  switch ((int)((long long)q & 3)) {
+    case 0: *s = sr; *c = cr; break;
+    case 1: *s = cr; *c = -sr; break;
+    case 2: *s = -sr; *c = -cr; break;
+    default: *s = -cr; *c = sr; break;
+  }
+}
+#else
 static void sincos_deg(REAL deg, REAL *s, REAL *c) {
   const double DEG2RAD = 3.14159265358979323846 / 180.0;
   *s = sin(deg * DEG2RAD);
   *c = cos(deg * DEG2RAD);
 }
+#endif
 /* pyrusgeom AngleDeg.atan2_deg: 0 for the zero vector */
 static REAL atan2_deg(REAL y, REAL x) {
   const double RAD2DEG = 180.0 / 3.14159265358979323846;
