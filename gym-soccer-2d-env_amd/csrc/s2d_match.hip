@@ -1807,6 +1807,16 @@ constexpr int kSeeWaveWords = 16 * kSeeRowPitch + 16 * kNetHidPitch + 2 * (int)(
 static_assert((2 * sizeof(s2d_see::SeeFacts)) % 16 == 0 && (16 * kSeeRowPitch + 16 * kNetHidPitch) % 4 == 0 && kSeeRowPitch % 4 == 0,
               "16-byte aligned LDS parts");
 static_assert(16 * kSeeRowPitch >= 16 * kNetHidPitch, "layer 2's image fits where the rows were");
+// See policy slots (s2d_match_set_see_policy_network): the kernel argument of the SEEPOL instantiations, an MSeeArg (epsilon NULL)
+// and then the policy words; one log-probability word beside each index word of the wave (768 B more per workgroup).
+struct MSeePolArg {
+  MSee net; s2d_see::SeeParams sp; S2DMatchVision vis;
+  int act;                                 // hidden activation: 0 relu, 1 tanh_spec
+  const uint32_t* det;                     // the policy's device word (read once per launch): != 0 -> greedy
+  float* logp;                             // [T][N][22] or NULL
+};
+constexpr int kSeePolWaveWords = kSeeWaveWords + kNetMaxRows;
+static_assert(kSeeWaveWords % 4 == 0 && kSeePolWaveWords % 4 == 0, "a wave's part starts 16-byte aligned");
 
 // the block-shared part of the network into LDS (every thread of the block; the kernel's barrier follows)
 S2D_DEV void m_see_stage(const MSee& net) {
@@ -1815,18 +1825,43 @@ S2D_DEV void m_see_stage(const MSee& net) {
   for (int i = threadIdx.x; i < net.shared_words / 4; i += kMBlock) dst[i] = src[i];
 }
 
+// A see-row tile through the three layers of a SEEPOL instantiation, hidden activation ACT (both are compiled in, the launch says
+// which); the logits stay in `hid`.  ACT relu is m_see_greedy's forward word for word.
+template <int ACT>
+S2D_DEV void m_see_pol_tile_layers(const MSee& net, const float* shared, float* tile, float* hid, int lane) {
+  const int gq = lane >> 4, c = lane & 15;
+  const float* const w2 = shared;
+  const float* const w3 = w2 + (net.h2 / 16) * (net.h1 / 4) * 64;
+  const float* const b1 = w3 + (net.na16 / 16) * (net.h2 / 4) * 64;
+  const float* const b2 = b1 + net.h1;
+  const float* const b3 = b2 + net.h2;
+  const float* const x = tile + c * kSeeRowPitch;
+  layer_tile<ACT, 4>(net.frags, b1, net.h1 / 16, kSeeK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<ACT, 4>(w2, b2, net.h2 / 16, net.h1 / 4, [&](int s) { return hid[c * kNetHidPitch + 4 * s + gq]; }, tile, kNetHidPitch, lane);
+  wave_fence();
+  layer_tile<S2D_ACT_FN_NONE, 4>(w3, b3, net.na16 / 16, net.h2 / 4, [&](int s) { return tile[c * kNetHidPitch + 4 * s + gq]; }, hid,
+                                 kNetHidPitch, lane);
+  wave_fence();
+}
+
 // One cycle's see-network step of the wave, from the start-of-cycle state (o, g), the lane's vision words and the match's tick: the
 // see rows, their record, the forward pass and the argmax.  Returns the greedy index of this lane's slot (meaningful for network
 // slots).  All 64 lanes, uniform control flow.
-S2D_DEV int m_see_greedy(const MSeeArg& sa, const MObj& o, const MGame& g, float vneck, int vwidth, int vwait, int l, int half,
-                         bool valid, uint64_t gid, int64_t rec_row) {
+// SEEPOL (SA = MSeePolArg): the policy's forward and the categorical head of the policy slots (m_pol_tile_head; `det`: the
+// launch's deterministic bit); returns an MPick: the index and its log-probability (0 for a slot outside the mask).
+template <class P, class SA>
+S2D_DEV auto m_see_greedy(const P& p, const SA& sa, const MObj& o, const MGame& g, float vneck, int vwidth, int vwait, int l, int half,
+                          bool valid, uint64_t gid, int64_t rec_row, bool det = false) {
+  constexpr bool SEEPOL = std::is_same<SA, MSeePolArg>::value;
   const MSee& net = sa.net;
   const int lane = threadIdx.x & 63, gq = lane >> 4, c = lane & 15;
   float* const shared = m_net_lds();
-  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * kSeeWaveWords;
+  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * (SEEPOL ? kSeePolWaveWords : kSeeWaveWords);
   float* const hid = tile + 16 * kSeeRowPitch;
   s2d_see::SeeFacts* const facts = reinterpret_cast<s2d_see::SeeFacts*>(hid + 16 * kNetHidPitch);
   int* const gidx = reinterpret_cast<int*>(facts + 2);
+  [[maybe_unused]] float* const glp = reinterpret_cast<float*>(gidx + kNetMaxRows);   // (SEEPOL only: the words kSeePolWaveWords adds)
   s2d_see::SeeIn in{};
   if (l <= BALL) { in.x = o.x; in.y = o.y; in.vx = o.vx; in.vy = o.vy; }
   if (l < NP) {
@@ -1845,6 +1880,7 @@ S2D_DEV int m_see_greedy(const MSeeArg& sa, const MObj& o, const MGame& g, float
   uint32_t rest = net.row_mask;
   for (int nt = 0; 8 * nt < nrows; ++nt) {
     const int rn = nrows - 8 * nt < 8 ? nrows - 8 * nt : 8;
+    [[maybe_unused]] const uint32_t tile_mask = rest;      // (SEEPOL: its lowest rn bits are this tile's slots)
     for (int i = lane; i < (16 - 2 * rn) * (kSeeRowPitch / 4); i += 64)   // pad rows of the last tile
       reinterpret_cast<float4*>(tile + 2 * rn * kSeeRowPitch)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (int j = 0; j < rn; ++j) {
@@ -1858,7 +1894,12 @@ S2D_DEV int m_see_greedy(const MSeeArg& sa, const MObj& o, const MGame& g, float
       }
     }
     wave_fence();
-    if (net.net_mask != 0u) {
+    if constexpr (SEEPOL) {                              // (a see policy always has slots: no record-only launch here)
+      if (sa.act) m_see_pol_tile_layers<S2D_ACT_FN_TANH>(net, shared, tile, hid, lane);
+      else m_see_pol_tile_layers<S2D_ACT_FN_RELU>(net, shared, tile, hid, lane);
+      m_pol_tile_head(p, net.na, hid, gidx + 16 * nt, glp + 16 * nt, lane, true, det, tile_mask, rn, (uint32_t)gid,
+                      (uint32_t)(gid >> 32), (uint32_t)g.tick);
+    } else if (net.net_mask != 0u) {
       const float* const x = tile + c * kSeeRowPitch;
       layer_tile<true, 4>(net.frags, b1, net.h1 / 16, kSeeK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
       wave_fence();
@@ -1883,8 +1924,15 @@ S2D_DEV int m_see_greedy(const MSeeArg& sa, const MObj& o, const MGame& g, float
   }
   int greedy = 0;
   if (l < NP && ((net.net_mask >> l) & 1u)) greedy = gidx[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
-  wave_fence();
-  return greedy;
+  if constexpr (SEEPOL) {
+    float lp = 0.0f;
+    if (l < NP && ((net.net_mask >> l) & 1u)) lp = glp[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+    wave_fence();
+    return MPick{greedy, lp};
+  } else {
+    wave_fence();
+    return greedy;
+  }
 }
 
 struct MRoll { float* obs; float* reward; int32_t* mode; uint8_t* done; };
@@ -1904,8 +1952,10 @@ template <bool CTL, bool NET = false, bool RW = false, class P, class TY, class 
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
                                 const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr,
                                 const MRw& rw = MRw{nullptr, nullptr, 0}) {
-  static_assert(!RW || (CTL && !(NET && std::is_same<NA, MSeeArg>::value)), "the agent reward: the CTL family, not the see network");
-  constexpr bool SEE = NET && std::is_same<NA, MSeeArg>::value;
+  static_assert(!RW || (CTL && !(NET && (std::is_same<NA, MSeeArg>::value || std::is_same<NA, MSeePolArg>::value))),
+                "the agent reward: the CTL family, not the see network");
+  constexpr bool SEEPOL = NET && std::is_same<NA, MSeePolArg>::value;   // see policy slots: SEE with the policy's head and record
+  constexpr bool SEE = NET && (std::is_same<NA, MSeeArg>::value || SEEPOL);
   constexpr bool POL = NET && std::is_same<NA, MPolArg>::value;   // policy slots: an instantiation of its own (the NET ones keep their code)
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
@@ -1957,7 +2007,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
   uint64_t net_thr = 0;
   uint32_t net_slots = 0u, net_k = 0u;                     // NET: the slots on a network; this lane's network: its K and table
   const float* net_tab = nullptr;
-  [[maybe_unused]] uint32_t pol_det = 0u;                  // POL: the passes' deterministic words, read once per launch like epsilon
+  [[maybe_unused]] uint32_t pol_det = 0u;                  // POL, SEEPOL: the passes' deterministic words, read once per launch like epsilon
   if constexpr (POL) {
     const MPol& pl = nin->pol;
     if (pl.kind[0]) pol_det |= *pl.det[0] != 0u ? 1u : 0u;
@@ -1970,6 +2020,9 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       net_slots |= nin->net.opp.mask;
       if ((nin->net.opp.mask >> l) & 1u) { net_thr = thr2; net_k = (uint32_t)nin->net.opp.na; net_tab = nin->net.opp.table; }
     }
+  } else if constexpr (SEEPOL) {                           // (no epsilon: its pointer is NULL)
+    pol_det = *nin->det != 0u ? 1u : 0u;
+    net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
   } else if constexpr (NET) {
     net_thr = nin->net.net_mask ? explore_threshold(*nin->net.epsilon) : 0;   // (records only: no network)
     net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
@@ -2019,7 +2072,11 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       if constexpr (NET) {
         int greedy;
         [[maybe_unused]] float lp = 0.0f;
-        if constexpr (SEE) greedy = m_see_greedy(*nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec);
+        if constexpr (SEEPOL) {
+          const MPick pick = m_see_greedy(p, *nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec, pol_det != 0u);
+          greedy = pick.idx; lp = pick.logp;
+        }
+        else if constexpr (SEE) greedy = m_see_greedy(p, *nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec);
         else if constexpr (POL) {
           const MPick pick = m_net_greedy(p, *nin, o, g, r, l, half, valid, (int64_t)t * n + ec, pol_det, gl, gh);
           greedy = pick.idx; lp = pick.logp;
@@ -2029,6 +2086,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
           bool pol_lane = false;                           // POL: the slot is on a policy: its head has sampled (word z of this block)
           if constexpr (POL)
             pol_lane = (nin->pol.kind[0] && ((nin->net.net_mask >> l) & 1u)) || (nin->pol.kind[1] && ((nin->net.opp.mask >> l) & 1u));
+          if constexpr (SEEPOL) pol_lane = true;           // (every network slot is the policy's)
           if (pol_lane) {
             nidx = greedy;
           } else {
@@ -2039,6 +2097,9 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
         if constexpr (POL) {
           // (wave-uniform pointer; 0.0f for every slot that is not on a policy)
           if (nin->pol.logp && valid && l < NP) nin->pol.logp[((int64_t)t * n + e) * NP + l] = lp;
+        }
+        if constexpr (SEEPOL) {
+          if (nin->logp && valid && l < NP) nin->logp[((int64_t)t * n + e) * NP + l] = lp;
         }
         if (nin->net.net_index && valid && l < NP) nin->net.net_index[((int64_t)t * n + e) * NP + l] = nidx;
       }
@@ -2136,6 +2197,8 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // instantiations keep their template and kernel arguments).
 // POL: the NET instantiations whose second extra argument is an MPolArg -- policy slots, likewise a family of its own: a launch
 // takes one only when a role holds a policy network, so the NET kernels and their LDS plan are what they were.
+// SEEPOL: the SEE instantiations whose second extra argument is an MSeePolArg -- see policy slots, a family of its own as well,
+// instantiated in a translation unit of its own (s2d_match_see_policy.hip): the SEE kernels are what they were.
 // RW: the CTL / NET / POL instantiations whose first extra argument is an MCtlRw -- the agent reward record, likewise a family of
 // its own, instantiated in a translation unit of its own (s2d_match_reward.hip): this unit's kernels are what they were.
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
@@ -2143,18 +2206,21 @@ S2D_DEV MCtl m_ctl_arg(const MCtl& c) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeeArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MPolArg&) { return c; }
+S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeePolArg&) { return c; }
 template <class... A> S2D_DEV MCtl m_ctl_arg(const MCtlRw& c, const A&...) { return c.ctl; }
 S2D_DEV const MNetArg* m_net_arg() { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&) { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
 S2D_DEV const MSeeArg* m_net_arg(const MCtl&, const MSeeArg& a) { return &a; }
 S2D_DEV const MPolArg* m_net_arg(const MCtl&, const MPolArg& a) { return &a; }
+S2D_DEV const MSeePolArg* m_net_arg(const MCtl&, const MSeePolArg& a) { return &a; }
 S2D_DEV const MNetArg* m_net_arg(const MCtlRw&) { return nullptr; }
 template <class A> S2D_DEV const A* m_net_arg(const MCtlRw&, const A& a) { return &a; }
 template <class... A> S2D_DEV MRw m_rw_arg(const A&...) { return MRw{nullptr, nullptr, 0}; }
 template <class... A> S2D_DEV MRw m_rw_arg(const MCtlRw& c, const A&...) { return c.rw; }
 template <class... A> struct MIsSee : std::false_type {};
 template <> struct MIsSee<MCtl, MSeeArg> : std::true_type {};
+template <> struct MIsSee<MCtl, MSeePolArg> : std::true_type {};
 template <class... A> struct MIsPol : std::false_type {};
 template <> struct MIsPol<MCtl, MPolArg> : std::true_type {};
 template <> struct MIsPol<MCtlRw, MPolArg> : std::true_type {};
@@ -2317,6 +2383,9 @@ struct S2DMatchEngine {
   float* net_frags = nullptr;                          // the fragment-order copies the pack kernel writes (2 x kNetFragsMax words, one half per role)
   bool has_see = false;                                // s2d_match_set_see_network installed a see network: launches use the SEE kernels
   S2DMatchSeeNet see{};                                // ... its pointers and planes (the caller's buffers), its parameters (a copy)
+  bool see_pol = false;                                // s2d_match_set_see_policy_network: `see` holds a policy (epsilon NULL), launches use the SEEPOL kernels
+  int see_act = 0;                                     // ... its hidden activation (0 relu, 1 tanh)
+  const uint32_t* see_det = nullptr;                   // ... its deterministic word (the caller's, read at run time)
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
   bool has_rw = false;                                 // s2d_match_set_agent_reward installed the weights: the reward record may be asked for
@@ -2793,8 +2862,8 @@ template <auto Kernel> static bool m_net_allow_lds(size_t dyn) {
 template <auto Kernel, class CA, class NA>
 static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp, const MPtrs& ptrs, int64_t n, int n_steps,
                         const float* actions, const MRoll& ro, const CA& ctl /* MCtl, or MCtlRw */, const NA& na) {
-  constexpr bool SEE = std::is_same<NA, MSeeArg>::value;
-  constexpr int wave_words = SEE ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
+  constexpr bool SEEPOL = std::is_same<NA, MSeePolArg>::value, SEE = std::is_same<NA, MSeeArg>::value || SEEPOL;
+  constexpr int wave_words = SEEPOL ? kSeePolWaveWords : SEE ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
   size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
   if constexpr (!SEE) {
     // The budget: a 64-64-64 network's W2 .. b3 are 33 536 B, a wave's tile, facts and index words 20 784 B, so two widest
@@ -2897,6 +2966,9 @@ static S2DMatchNet m_see_as_net(const S2DMatchSeeNet& s) { return S2DMatchNet{s.
 // is a network or policy one.
 int s2d_match_internal_reward_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, const MCtlRw& ctl,
                                      const MNetArg* na, const MPolArg* pa);
+// With a see policy set the SEEPOL instantiation runs, which lives in s2d_match_see_policy.hip (logp_out: its record, or NULL).
+int s2d_match_internal_see_policy_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st,
+                                         const MCtl& ctl, const MSeePolArg& pa);
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
                     float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
                     float* agent_obs_out = nullptr, const float* view_actions = nullptr, float* logp_out = nullptr,
@@ -2925,6 +2997,17 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       MDeviceGuard guard(h->device);
       m_net_pass(nt, m_see_as_net(h->see), S2D_SEE_DIM, h->net_frags, st);
       MHIP_TRY(hipGetLastError());
+    }
+    if (h->see_pol) {                                      // the SEEPOL instantiation: the same MSeeArg plus the policy words
+      MSeePolArg pa;
+      std::memset(&pa, 0, sizeof pa);
+      pa.net = sa.net; pa.sp = sa.sp; pa.vis = sa.vis;
+      pa.act = h->see_act; pa.det = h->see_det; pa.logp = logp_out;
+      return s2d_match_internal_see_policy_launch(h, n_steps, actions, ro, st, ctl, pa);
+    }
+    if (logp_out) {                                        // no see policy: the record is all zero
+      MDeviceGuard guard(h->device);
+      MHIP_TRY(hipMemsetAsync(logp_out, 0, (size_t)n_steps * (size_t)h->n * NP * sizeof(float), st));
     }
     return m_dispatch<true, true>(h, n_steps, actions, ro, st, ctl, sa);
   }
@@ -2972,9 +3055,9 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
 // "s2d_match_rollout_kernel<" variant [", " slot kind] [", agent reward"] ">"
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
-  constexpr int kKinds = 7;
+  constexpr int kKinds = 8;
   static const char* const kind_text[kKinds] = {"", ", controllers", ", network", ", two networks", ", policy network",
-                                                ", two networks, policy", ", see network"};
+                                                ", two networks, policy", ", see network", ", see policy network"};
   static const std::array<std::string, 2 * 5 * kKinds> names = [] {
     std::array<std::string, 2 * 5 * kKinds> t;
     for (int v = 0; v < 5; ++v)
@@ -2987,7 +3070,7 @@ S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   }();
   const int nets = h->role[0].set + h->role[1].set;
   const bool pol = h->role[0].pol || h->role[1].pol;
-  const int kind = h->has_see ? 6 : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
+  const int kind = h->has_see ? (h->see_pol ? 7 : 6) : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
   return names[((h->has_rw ? 5 : 0) + m_variant(h)) * kKinds + kind].c_str();
 }
 S2D_API int s2d_match_relative(S2DMatchHandle h, float* dist_dev, float* angle_dev, void* stream) {
@@ -3086,7 +3169,7 @@ static int m_net_validate(const std::string& what, const S2DMatchNet& net, const
     return mfail(S2D_EINVAL, what + " " + word_name + " and table must be non-NULL, 4-byte aligned device pointers");
   return S2D_OK;
 }
-// Who excludes whom, for all four setters.  `slot`: a role, or kSlotSee.  The see network is the engine's only one: the opponent role
+// Who excludes whom, for all five setters.  `slot`: a role, or kSlotSee (a see network of either kind).  The see network is the engine's only one: the opponent role
 // refuses beside it, the network role replaces it, and setting it clears both roles (policy networks too).
 static constexpr int kSlotSee = 2;
 static int m_slot_admit(S2DMatchHandle h, int slot) {
@@ -3095,7 +3178,7 @@ static int m_slot_admit(S2DMatchHandle h, int slot) {
   return S2D_OK;
 }
 static void m_slot_clear(S2DMatchHandle h, int slot) {   // a slot without a network, whatever kind it held
-  if (slot == kSlotSee) { h->has_see = false; h->see = S2DMatchSeeNet{}; }
+  if (slot == kSlotSee) { h->has_see = false; h->see = S2DMatchSeeNet{}; h->see_pol = false; h->see_act = 0; h->see_det = nullptr; }
   else h->role[slot] = MRole{};
 }
 static void m_slot_displace(S2DMatchHandle h, int slot) {
@@ -3135,11 +3218,12 @@ S2D_API int s2d_match_set_policy_network(S2DMatchHandle h, int role, const S2DMa
   const S2DMatchNet as_net{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, nullptr, net->table};
   return m_role_set(h, role, MRole{true, as_net, true, net->activation, net->deterministic});
 }
-S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
-  if (!h) return mfail(S2D_EINVAL, "NULL handle");
-  if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+// a see network of either kind into the see slot: word / word_name as for m_net_validate; pol: a policy (act, det: its words)
+static int m_see_set(S2DMatchHandle h, const S2DMatchSeeNet* net, const std::string& what, const void* word, const char* word_name,
+                     bool pol, int act, const uint32_t* det) {
   if (h->has_rw) return mfail(S2D_EINVAL, "an agent reward is set: the see network's cycle kernel has none (clear it first)");
-  if (int rc = m_net_validate("see network", m_see_as_net(*net), net->epsilon, "epsilon", true, 0u); rc != S2D_OK) return rc;
+  if (pol && act != 0 && act != 1) return mfail(S2D_EINVAL, what + " activation must be 0 (relu) or 1 (tanh)");
+  if (int rc = m_net_validate(what, m_see_as_net(*net), word, word_name, !pol, 0u); rc != S2D_OK) return rc;
   if (!net->vis.neck || !net->vis.view_width || !net->vis.see_wait) return mfail(S2D_EINVAL, "NULL vision plane");
   if ((reinterpret_cast<uintptr_t>(net->vis.neck) | reinterpret_cast<uintptr_t>(net->vis.view_width) |
        reinterpret_cast<uintptr_t>(net->vis.see_wait)) & 3u)
@@ -3148,8 +3232,21 @@ S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* ne
   if (net->slot_mask != 0u)
     if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
   h->see = *net; h->has_see = true;
+  h->see_pol = pol; h->see_act = pol ? act : 0; h->see_det = pol ? det : nullptr;
   m_slot_displace(h, kSlotSee);
   return S2D_OK;
+}
+S2D_API int s2d_match_set_see_network(S2DMatchHandle h, const S2DMatchSeeNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+  return m_see_set(h, net, "see network", net->epsilon, "epsilon", false, 0, nullptr);
+}
+S2D_API int s2d_match_set_see_policy_network(S2DMatchHandle h, const S2DMatchSeePolicyNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+  // a see policy keeps its words in the same S2DMatchSeeNet, epsilon NULL
+  const S2DMatchSeeNet as_see{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, nullptr, net->table, net->prm, net->vis};
+  return m_see_set(h, &as_see, "see policy network", net->deterministic, "deterministic", true, net->activation, net->deterministic);
 }
 S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
                                   const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask,
@@ -3160,6 +3257,19 @@ S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* ac
                                              {net_index_out_dev, "net_index_out", "int32"}}, see_out_dev, "see_out", obs_mask))
     return rc;
   return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, see_out_dev, view_actions_dev);
+}
+S2D_API int s2d_match_rollout_see_policy(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
+                                         const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev,
+                                         float* logp_out_dev, uint32_t obs_mask, float* see_out_dev, void* stream) {
+  if (h && !h->has_see)
+    return mfail(S2D_EINVAL, "s2d_match_rollout_see_policy needs a see network (s2d_match_set_see_policy_network, s2d_match_set_see_network)");
+  int rc;
+  if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {view_actions_dev, "view_actions", "float"},
+                                             {net_index_out_dev, "net_index_out", "int32"}, {logp_out_dev, "logp_out", "float"}},
+                      see_out_dev, "see_out", obs_mask))
+    return rc;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, see_out_dev, view_actions_dev,
+                  logp_out_dev);
 }
 S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                   float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask, float* agent_obs_out_dev,
@@ -3174,7 +3284,7 @@ S2D_API int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float* ac
 S2D_API int s2d_match_rollout_policy(S2DMatchHandle h, int n_steps, const float* actions_dev, const S2DMatchRollout* out,
                                      float* actions_out_dev, int32_t* net_index_out_dev, float* logp_out_dev, uint32_t obs_mask,
                                      float* agent_obs_out_dev, void* stream) {
-  if (h && h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see (the see network has no policy head)");
+  if (h && h->has_see) return mfail(S2D_EINVAL, "a see network is set: use s2d_match_rollout_see, or s2d_match_rollout_see_policy for a see policy's log-probabilities");
   int rc;
   if (!m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {net_index_out_dev, "net_index_out", "int32"},
                                              {logp_out_dev, "logp_out", "float"}}, agent_obs_out_dev, "agent_obs_out", obs_mask))

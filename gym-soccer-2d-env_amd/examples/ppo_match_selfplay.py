@@ -17,6 +17,11 @@ Per iteration:
   5. Every --eval-every iterations the learner plays a frozen snapshot() of an earlier self on an evaluation engine of half the
      matches (league.play_networks: learner left, snapshot right, both in-kernel), then the snapshot is renewed.
 
+--obs see is the same loop under partial observability: a MatchSeePolicyActor on every slot's 192-word see row,
+a [K, 5] table whose rows also turn the neck or change the view width, the vision state stepped in the cycle kernel, the critic on
+the recorded see rows, the signed team reward (the see families have no agent reward: --shaping is refused).  No snapshot
+opponent exists for see networks, so evaluation plays the deterministic learner's left team against the in-kernel scripted team.
+
 stable-baselines3 cannot be installed offline; the PPO here is a small plain-torch one of the same shape (Tanh MlpPolicy)."""
 import argparse
 import os
@@ -32,6 +37,12 @@ DASH, TURN, KICK, TACKLE = 1.0, 2.0, 3.0, 4.0   # S2D_MCMD_* (include/s2d_match.
 ACTION_TABLE = ([[DASH, 100.0, float(d)] for d in (0, 45, 90, 135, 180, -135, -90, -45)] +
                 [[TURN, float(m), 0.0] for m in (-60, -15, 15, 60)] +
                 [[KICK, 100.0, float(d)] for d in (-45, 0, 45)] + [[TACKLE, 0.0, 0.0]])
+NONE = 0.0                                      # S2D_MCMD_NONE
+# --obs see, (command, a, b, TurnNeck moment, ChangeView code): the 16 body actions with no view action, then four rows that only
+# turn the neck and three that only change the view width (1 narrow, 2 normal, 3 wide)
+SEE_ACTION_TABLE = ([row + [0.0, 0.0] for row in ACTION_TABLE] +
+                    [[NONE, 0.0, 0.0, float(m), 0.0] for m in (-60, -20, 20, 60)] +
+                    [[NONE, 0.0, 0.0, 0.0, float(c)] for c in (1, 2, 3)])
 
 
 def mlp(n_in, n_out, hidden, act):
@@ -61,11 +72,15 @@ def parse(argv=None):
     ap.add_argument('--chaser-only', action='store_true', help='with --shaping: approach and facing for each team\'s chaser only')
     ap.add_argument('--fused-learner', action='store_true',
                     help='the minibatch epochs in HIP (soccer2d_amd.learn.PPOLearner) instead of torch autograd and Adam')
+    ap.add_argument('--obs', default='agent', choices=('agent', 'see'),
+                    help="'see': partial observability -- the policy on see rows (MatchSeePolicyActor), vision stepped in the kernel")
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args(argv)
     if args.chaser_only and not args.shaping:
         ap.error('--chaser-only needs --shaping')
+    if args.shaping and args.obs == 'see':
+        ap.error('--shaping needs --obs agent: the see families of the cycle kernel have no agent reward')
     if args.shaping:
         try:
             args.shaping = {k.strip(): float(v) for k, v in (item.split('=') for item in args.shaping.split(','))}
@@ -77,14 +92,16 @@ def parse(argv=None):
 def main(argv=None):
     args = parse(argv)
     from soccer2d_amd import league
-    from soccer2d_amd.actor import MatchPolicyActor
+    from soccer2d_amd.actor import MatchPolicyActor, MatchSeePolicyActor
     from soccer2d_amd.gae import gae
     from soccer2d_amd.match import MatchEngine
     torch.manual_seed(args.seed)
     dev = torch.device(args.device)
-    N, T, K = args.num_matches, args.steps, len(ACTION_TABLE)
+    see = args.obs == 'see'
+    table = SEE_ACTION_TABLE if see else ACTION_TABLE
+    N, T, K, D = args.num_matches, args.steps, len(table), 192 if see else 224
     act = nn.ReLU if args.relu else nn.Tanh
-    pi, vf = mlp(224, K, args.hidden, act).to(dev), mlp(224, 1, args.hidden, act).to(dev)
+    pi, vf = mlp(D, K, args.hidden, act).to(dev), mlp(D, 1, args.hidden, act).to(dev)
     learner = None
     if args.fused_learner:                                 # torch.optim.Adam's defaults and no gradient clip, as the torch arm
         from soccer2d_amd.learn import PPOLearner
@@ -92,30 +109,41 @@ def main(argv=None):
                                           ent_coef=args.ent_coef, max_batch=(T * N * 22 + args.minibatches - 1) // args.minibatches)
     else:
         opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()), lr=args.lr)
-    actor = MatchPolicyActor.from_module(pi, ACTION_TABLE, device=dev)
+    actor = (MatchSeePolicyActor if see else MatchPolicyActor).from_module(pi, table, device=dev)
     eng = MatchEngine(N, dev, noise=True, seed=args.seed)
+    if see:
+        eng.enable_vision()
     eng.set_network(actor, 'all')
     if args.shaping:
         eng.set_agent_reward(args.shaping, args.chaser_only)
     eng.reset()
     rec = eng.alloc_rollout(T, with_obs=False)
     eval_eng = MatchEngine(max(1, N // 2), dev, noise=True, seed=args.seed + 1)
+    if see:                                                # the learner's left team, greedy, against the scripted right team
+        eval_eng.enable_vision()
+        eval_eng.set_controllers({'left': 'external', 'right': 'scripted'})
+        eval_actor = actor.snapshot(deterministic=True)
+        eval_eng.set_network(eval_actor, 'left')
     frozen = actor.snapshot()
     sign = torch.tensor([1.0] * 11 + [-1.0] * 11, device=dev)
     stats = []
     for it in range(args.iterations):
-        eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all', agent_reward=bool(args.shaping))
-        rows, idx, logp_old = rec['agent_obs'], rec['net_index'], rec['logp']
+        if see:
+            eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, see_obs='all')
+        else:
+            eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all', agent_reward=bool(args.shaping))
+        rows, idx, logp_old = rec['see' if see else 'agent_obs'], rec['net_index'], rec['logp']
         with torch.no_grad():
-            value = vf(rows.reshape(-1, 224)).reshape(T, N * 22)
-            last_value = vf(eng.agent_observations('all').reshape(-1, 224)).reshape(N * 22)
+            value = vf(rows.reshape(-1, D)).reshape(T, N * 22)
+            last_rows = eng.see('all') if see else eng.agent_observations('all')
+            last_value = vf(last_rows.reshape(-1, D)).reshape(N * 22)
         if args.shaping:
             reward = rec['agent_reward'].reshape(T, N * 22)
         else:
             reward = (rec['reward'][:, :, None] * sign).reshape(T, N * 22).contiguous()
         done = rec['done'][:, :, None].expand(T, N, 22).reshape(T, N * 22).contiguous()
         adv, ret = gae(reward, done, value.contiguous(), last_value.contiguous(), args.gamma, args.lam)
-        obs_b, act_b = rows.reshape(-1, 224), idx.reshape(-1).long()
+        obs_b, act_b = rows.reshape(-1, D), idx.reshape(-1).long()
         lp_b, adv_b, ret_b = logp_old.reshape(-1), adv.reshape(-1), ret.reshape(-1)
         B = obs_b.shape[0]
         mb = (B + args.minibatches - 1) // args.minibatches
@@ -148,7 +176,15 @@ def main(argv=None):
         else:
             row = dict(iteration=it, policy_loss=float(pg.detach()), value_loss=float(v_loss.detach()), entropy=float(ent.detach()),
                        approx_kl=float((lp_b[i] - lp.detach()).mean()), mean_reward=float(rec['reward'].mean()))
-        if (it + 1) % args.eval_every == 0:
+        if (it + 1) % args.eval_every == 0 and see:
+            eval_actor.params.copy_(actor.params)          # the learner as it is now, on the first maximum
+            eval_eng.reset()
+            left0, right0 = eval_eng.score_left.clone(), eval_eng.score_right.clone()
+            for c in range(0, args.eval_cycles, 64):
+                eval_eng.rollout(min(64, args.eval_cycles - c), with_obs=False)
+            row.update(eval_goals_learner=int((eval_eng.score_left - left0).sum()),
+                       eval_goals_scripted=int((eval_eng.score_right - right0).sum()))
+        elif (it + 1) % args.eval_every == 0:
             gl, gr = league.play_networks(eval_eng, actor, frozen, args.eval_cycles)
             row.update(eval_goals_learner=int(gl.sum()), eval_goals_snapshot=int(gr.sum()))
             frozen = actor.snapshot()                      # the next rounds' opponent: the learner as it is now

@@ -167,6 +167,12 @@ class S2DMatchSeeNet(C.Structure):          # include/s2d_match.h: see network
                 ('prm', S2DVisionParams), ('vis', S2DMatchVision)]
 
 
+class S2DMatchSeePolicyNet(C.Structure):    # include/s2d_match.h: see policy slots
+    _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
+                ('params', C.c_void_p), ('deterministic', C.c_void_p), ('table', C.c_void_p),
+                ('prm', S2DVisionParams), ('vis', S2DMatchVision), ('activation', C.c_int32)]
+
+
 class S2DMatchAgentReward(C.Structure):     # include/s2d_match.h: Agent reward
     _fields_ = [('weights', C.c_void_p), ('chaser_only', C.c_int32)]
 
@@ -211,6 +217,9 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_see_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_see', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_see_policy_network', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_see_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
     ('s2d_match_set_policy_network', C.c_int, (C.c_void_p, C.c_int, C.c_void_p)),
     ('s2d_match_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),

@@ -506,26 +506,15 @@ class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
         return net
 
 
-class MatchPolicyActor(_ActionTable, _Deterministic, _PackedActor):
-    """Packed parameters, the device deterministic word and the action table of a 224-H1-H2-K stochastic policy for the 11v11
-    engine's policy slots (MatchEngine.set_network / set_opponent_network, s2d_match_set_policy_network in include/s2d_match.h):
-    on-policy self-play (PPO / A2C with shared parameters) collected inside the cycle kernel.
-
-    y = W3 f(W2 f(W1 x + b1) + b2) + b3 with f = ReLU or Tanh (``activation``; Tanh is SB3's default for PPO's MlpPolicy) are the
-    logits of a categorical policy over the K rows of `table`, float32 [K, 3] = (command, a, b).  The kernel samples the index,
-    records it (``net_index``) and its log-probability (``MatchEngine.rollout(logp=True)``); ``deterministic = True`` switches to
-    the first maximum.  params, the deterministic word and table are device buffers written in place and read when the kernel
-    runs, so a captured graph acts with what they hold at replay.  The see network has no policy head: obs='see' is refused."""
+class _MatchPolicy(_ActionTable, _Deterministic, _PackedActor):
+    """what the 11v11 engine's two stochastic policies share: the row width and table width are the class's (`in_dim`,
+    `table_width`); widths, K, the activation, the deterministic word and the table are checked and built alike"""
 
     kind = 'policy'
     _grid = _POLICY_GRID
     _what = 'policy'
 
-    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None,
-                 obs='agent'):
-        if obs != 'agent':
-            raise ValueError(f"a policy actor acts on agent rows only (obs='agent'): the see network has no policy head, got obs={obs!r}")
-        self.obs, self.in_dim, self.table_width = 'agent', MATCH_OBS_DIM, 3
+    def _init_policy(self, hidden1, hidden2, n_actions, activation, device, deterministic, table):
         for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
             if int(w) not in MATCH_WIDTHS:
                 raise ValueError(f'{name} must be one of {MATCH_WIDTHS}, got {w}')
@@ -539,14 +528,11 @@ class MatchPolicyActor(_ActionTable, _Deterministic, _PackedActor):
         self._init_table(table)
 
     @classmethod
-    def from_module(cls, policy_net, table, device=None, deterministic=False, obs='agent'):
-        """An actor shaped like `policy_net` (224 -> H1 -> H2 -> K; the module forms StochasticActor.from_module accepts, SB3's
-        ``[policy.mlp_extractor.policy_net, policy.action_net]`` among them), loaded from it, with action table `table` [K, 3].
-        The activation is the module's."""
+    def _from_module(cls, policy_net, table, device, deterministic, **kwargs):
         (l1, l2, l3), act = cls._read(policy_net)
         dev = device if device is not None else l1.weight.device
         actor = cls(l1.out_features, l2.out_features, l3.out_features, activation=act, device=dev, deterministic=deterministic,
-                    obs=obs)
+                    **kwargs)
         actor.load_from(policy_net)
         actor.set_table(table)
         return actor
@@ -557,11 +543,73 @@ class MatchPolicyActor(_ActionTable, _Deterministic, _PackedActor):
         return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_actions, activation=self.activation, device=self.device,
                                        deterministic=self._det_value if deterministic is None else deterministic))
 
-    def c_struct(self, slot_mask):
-        """S2DMatchPolicyNet for s2d_match_set_policy_network"""
-        from . import _capi_match as M
-        net = M.S2DMatchPolicyNet()
+    def _fill(self, net, slot_mask):
+        """the words S2DMatchPolicyNet and S2DMatchSeePolicyNet share"""
         net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
         net.activation = 1 if self.activation == 'tanh' else 0
         net.params, net.deterministic, net.table = self.params.data_ptr(), self._det.data_ptr(), self.table.data_ptr()
+        return net
+
+
+class MatchPolicyActor(_MatchPolicy):
+    """Packed parameters, the device deterministic word and the action table of a 224-H1-H2-K stochastic policy for the 11v11
+    engine's policy slots (MatchEngine.set_network / set_opponent_network, s2d_match_set_policy_network in include/s2d_match.h):
+    on-policy self-play (PPO / A2C with shared parameters) collected inside the cycle kernel.
+
+    y = W3 f(W2 f(W1 x + b1) + b2) + b3 with f = ReLU or Tanh (``activation``; Tanh is SB3's default for PPO's MlpPolicy) are the
+    logits of a categorical policy over the K rows of `table`, float32 [K, 3] = (command, a, b).  The kernel samples the index,
+    records it (``net_index``) and its log-probability (``MatchEngine.rollout(logp=True)``); ``deterministic = True`` switches to
+    the first maximum.  params, the deterministic word and table are device buffers written in place and read when the kernel
+    runs, so a captured graph acts with what they hold at replay.  obs='see' is refused: the policy on see rows is a class of
+    its own, MatchSeePolicyActor."""
+
+    obs, in_dim, table_width = 'agent', MATCH_OBS_DIM, 3
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None,
+                 obs='agent'):
+        if obs != 'agent':
+            raise ValueError(f"a MatchPolicyActor acts on agent rows only (obs='agent'), got obs={obs!r}: the policy on see rows "
+                             f"is MatchSeePolicyActor")
+        self._init_policy(hidden1, hidden2, n_actions, activation, device, deterministic, table)
+
+    @classmethod
+    def from_module(cls, policy_net, table, device=None, deterministic=False, obs='agent'):
+        """An actor shaped like `policy_net` (224 -> H1 -> H2 -> K; the module forms StochasticActor.from_module accepts, SB3's
+        ``[policy.mlp_extractor.policy_net, policy.action_net]`` among them), loaded from it, with action table `table` [K, 3].
+        The activation is the module's."""
+        return cls._from_module(policy_net, table, device, deterministic, obs=obs)
+
+    def c_struct(self, slot_mask):
+        """S2DMatchPolicyNet for s2d_match_set_policy_network"""
+        from . import _capi_match as M
+        return self._fill(M.S2DMatchPolicyNet(), slot_mask)
+
+
+class MatchSeePolicyActor(_MatchPolicy):
+    """MatchPolicyActor under partial observability: a 192-H1-H2-K stochastic policy on each slot's see row (MatchEngine.see)
+    for the 11v11 engine's see policy slots (MatchEngine.set_network, s2d_match_set_see_policy_network in include/s2d_match.h).
+
+    The logits are MatchPolicyActor's with 192 inputs; the sampled index chooses a row of `table`, float32 [K, 5] = (command, a,
+    b, TurnNeck moment, ChangeView code), so the policy also turns the neck and changes the view width, and the cycle kernel
+    steps the vision state of all 22 players.  ``MatchEngine.rollout(logp=True, see_obs=..., net_index=True)`` records what a
+    PPO / A2C learner needs.  It is the engine's only network (no opponent beside it) and needs enable_vision() first."""
+
+    obs, in_dim, table_width = 'see', MATCH_SEE_DIM, 5
+
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None):
+        self._init_policy(hidden1, hidden2, n_actions, activation, device, deterministic, table)
+
+    @classmethod
+    def from_module(cls, policy_net, table, device=None, deterministic=False):
+        """An actor shaped like `policy_net` (192 -> H1 -> H2 -> K, the module forms MatchPolicyActor.from_module accepts), loaded
+        from it, with action table `table` [K, 5].  The activation is the module's."""
+        return cls._from_module(policy_net, table, device, deterministic)
+
+    def c_struct(self, slot_mask, vision_params=None, vision=None):
+        """S2DMatchSeePolicyNet for s2d_match_set_see_policy_network; it needs the engine's vision parameters and planes"""
+        from . import _capi_match as M
+        if vision_params is None or vision is None:
+            raise ValueError("a see actor's struct needs the engine's vision parameters and planes (enable_vision)")
+        net = self._fill(M.S2DMatchSeePolicyNet(), slot_mask)
+        net.prm, net.vis = vision_params, vision
         return net

@@ -150,7 +150,8 @@ class MatchEngine:
         A see actor (MatchQNetActor(obs='see')) is the see network: it acts on the slot's see row, its table also chooses the
         slot's TurnNeck / ChangeView, and from now on the cycle kernel steps the vision state itself -- do not call vision_step()
         for cycles it runs.  It needs enable_vision() first.  Either kind replaces the other, and the see network also clears
-        the opponent network: it stays the engine's only one."""
+        the opponent network: it stays the engine's only one.  A MatchSeePolicyActor is the see network's stochastic
+        counterpart (s2d_match_set_see_policy_network), under the same rules."""
         if actor is None:
             _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, None), 's2d_match_set_network')
             _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, None), 's2d_match_set_opponent_network')
@@ -164,7 +165,11 @@ class MatchEngine:
         if getattr(actor, 'obs', 'agent') == 'see':
             self._need_vision()
             net = actor.c_struct(mask, self.vision_params, self.vision)
-            _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
+            if _is_policy(actor):
+                _capi.check(self.lib, self.lib.s2d_match_set_see_policy_network(self._h, C.byref(net)),
+                            's2d_match_set_see_policy_network')
+            else:
+                _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
             self.opponent_network, self.opponent_mask = None, 0
         else:
             if mask & self.opponent_mask:
@@ -286,6 +291,8 @@ class MatchEngine:
         (TurnNeck moment, ChangeView code) of the slots the see network does not play (None: they neither turn nor change).
         logp: out['logp'] float32 [T, N, 22] receives the log-probability of the index each policy slot took (MatchPolicyActor;
         0 for every other slot, Q-network slots included): s2d_match_rollout_policy, with net_index and agent_obs as above.
+        With a MatchSeePolicyActor set it is the see policy's record (s2d_match_rollout_see_policy), with net_index, see_obs and
+        view_actions as above; a see Q-network has none and logp is refused.
         agent_reward: out['agent_reward'] float32 [T, N, 22] receives every agent's shaped reward of each cycle
         (set_agent_reward first; s2d_match_rollout_reward); it composes with every record above but the see ones."""
         T = int(n_steps)
@@ -316,12 +323,12 @@ class MatchEngine:
             rwd = self._record(out, 'agent_reward', T, (n, M.MATCH_PLAYERS), torch.float32)
             _capi.check(self.lib, self.lib.s2d_match_rollout_reward(self._h, T, ptr, C.byref(ro), _ptr(rec), _ptr(idx), _ptr(lp), mask,
                                                                      _ptr(obs), _ptr(rwd), st), 's2d_match_rollout_reward')
-        elif see_obs is not None or view_actions is not None or (net_index and self._see_network_set()):
+        elif logp and self._see_network_set() and not _is_policy(self.network):
+            raise ValueError("logp is the policy slots' record: the see Q-network has no policy head (MatchSeePolicyActor has)")
+        elif see_obs is not None or view_actions is not None or ((net_index or logp) and self._see_network_set()):
             if agent_obs is not None:
                 raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
-            va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions)
-        elif logp and self._see_network_set():
-            raise ValueError("logp is the policy slots' record: the see network has no policy head")
+            va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp)
         elif net_index or agent_obs is not None or logp:
             idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
             obs, mask = None, 0
@@ -342,14 +349,16 @@ class MatchEngine:
         self._keep = (keep, out, va)
         return out
 
-    def _rollout_see(self, T, ptr, ro, rec, out, net_index, see_obs, view_actions):
-        """the see network's rollout, or the record-only one; returns the view actions' tensor (for the caller to keep alive)"""
+    def _rollout_see(self, T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp=False):
+        """the see network's rollout, the see policy's (logp: with its log-probability record), or the record-only one; returns
+        the view actions' tensor (for the caller to keep alive)"""
         n, dev = self.num_envs, self.device
         self._need_vision()
         record_only = not self._see_network_set()
         if record_only and (self.network is not None or self.opponent_network is not None):
             raise ValueError("see_obs / view_actions need a see network or no network (the engine has an agent-row network set)")
         idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
+        lp = self._record(out, 'logp', T, (n, M.MATCH_PLAYERS), torch.float32) if logp else None
         va = None
         if view_actions is not None:
             va = torch.as_tensor(view_actions, device=dev).to(torch.float32).contiguous()
@@ -365,8 +374,13 @@ class MatchEngine:
             net.prm, net.vis = self.vision_params, self.vision
             _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, C.byref(net)), 's2d_match_set_see_network')
         try:
-            _capi.check(self.lib, self.lib.s2d_match_rollout_see(self._h, T, ptr, _ptr(va), C.byref(ro), _ptr(rec), _ptr(idx), mask,
-                                                                  _ptr(see), self._stream()), 's2d_match_rollout_see')
+            if logp:
+                _capi.check(self.lib, self.lib.s2d_match_rollout_see_policy(self._h, T, ptr, _ptr(va), C.byref(ro), _ptr(rec), _ptr(idx),
+                                                                             _ptr(lp), mask, _ptr(see), self._stream()),
+                            's2d_match_rollout_see_policy')
+            else:
+                _capi.check(self.lib, self.lib.s2d_match_rollout_see(self._h, T, ptr, _ptr(va), C.byref(ro), _ptr(rec), _ptr(idx), mask,
+                                                                      _ptr(see), self._stream()), 's2d_match_rollout_see')
         finally:
             if record_only:
                 _capi.check(self.lib, self.lib.s2d_match_set_see_network(self._h, None), 's2d_match_set_see_network')
@@ -505,8 +519,8 @@ class MatchEngine:
 
 
 def _is_match_actor(obj):
-    from .actor import MatchPolicyActor, MatchQNetActor
-    return isinstance(obj, (MatchQNetActor, MatchPolicyActor))
+    from .actor import MatchPolicyActor, MatchQNetActor, MatchSeePolicyActor
+    return isinstance(obj, (MatchQNetActor, MatchPolicyActor, MatchSeePolicyActor))
 
 
 class Soccer2DMatchVecEnv:
@@ -537,7 +551,7 @@ class Soccer2DMatchVecEnv:
     actions float32 [N, 22 or 11, 5] = (command, a, b, TurnNeck moment, ChangeView code).  A step is the body step, then
     vision_step with the engine's done (a restarted match restarts its vision state), then see.  `vision` = a dict of
     S2DVisionParams fields.  The row returned by reset() is not fresh (self and game words only); the first step's is.
-    With opponent = a see actor (MatchQNetActor(obs='see')) the right team plays on its own see rows and turns its necks and
+    With opponent = a see actor (MatchQNetActor(obs='see') or a MatchSeePolicyActor) the right team plays on its own see rows and turns its necks and
     changes its view as the actor's table says; the cycle kernel then steps the vision state of all 22 players itself (the left
     team's from the caller's TurnNeck / ChangeView words), so a step is one launch plus see.  A see actor needs obs='see'.
 

@@ -428,8 +428,9 @@ int s2d_match_rollout_net(S2DMatchHandle h, int n_steps, const float *actions_de
  * does net == NULL here.  All four combinations of kinds are legal; the two masks must be disjoint whatever the kinds; the symmetry
  * of the opponent network holds: (A in role 0 on mask a, B in role 1 on b) is bitwise the launch (B in role 0 on b, A in role 1 on
  * a).  Setting role 0 clears a see network (as s2d_match_set_network does), setting role 1 while a see network is set is
- * S2D_EINVAL, and s2d_match_set_see_network clears policy networks too.  Not offered: a policy head for the see network, a
- * Gaussian head (11v11 actions go through the table), a value head (the critic runs on the recorded rows), action masking.
+ * S2D_EINVAL, and s2d_match_set_see_network clears policy networks too.  Not offered: a Gaussian head (11v11 actions go
+ * through the table), a value head (the critic runs on the recorded rows), action masking.  A policy on see rows is the see
+ * network's counterpart of this one ("See policy slots" below, s2d_match_set_see_policy_network), not a role here.
  * The engine keeps the pointers, not copies, as for S2DMatchNet.
  * Errors (S2D_EINVAL, the engine unchanged): a role other than 0 or 1; an activation other than 0 or 1; h1 / h2 not in {16, 32, 48,
  * 64}; n_actions outside [1, 64]; an empty slot_mask or bits above 21; NULL or unaligned pointers (params 16 bytes, deterministic
@@ -665,11 +666,57 @@ int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float *actions_de
                           const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev, uint32_t obs_mask,
                           float *see_out_dev, void *stream);
 
+/* See policy slots: "Policy slots" under partial observability -- a stochastic policy (PPO / A2C with shared parameters) in the
+ * place of the epsilon-greedy Q-network of "See network".  It occupies the see network's place: one per engine, no agent-row
+ * network beside it (it clears both roles and is cleared by s2d_match_set_network and s2d_match_set_policy_network(h, 0, ..),
+ * exactly as the see network is; role 1 refuses beside it; refused while an agent reward is set).  For every cycle of a launch
+ * and every match:
+ *   1. The see rows are step 1 of "See network", unchanged, and are recorded for obs_mask as there.
+ *   2. For every slot l of slot_mask: logits y = W3 f(W2 f(W1 x + b1) + b2) + b3 on the 192 words, params in the S2DMatchSeeNet
+ *      layout, the k-ascending fmaf order of step 2 of "Policy slots"; f = relu (NaN and -0 -> +0) or tanh_spec (include/s2d.h),
+ *      the same on both hidden layers; the output layer is linear.
+ *   3. The head is step 3 of "Policy slots" (the categorical head; *deterministic != 0, read once when the kernel runs: the first
+ *      maximum) on word z of the block of its step 4: counter = the match's tick, stream S2D_MATCH_ST_NET, block = l.  There is no
+ *      epsilon.  logp = (y[index] - m) - log_spec(S).
+ *   4. (cmd, a, b) = table[index][0..2] (device float[K][5]), the engine's usual gating and the body cycle; then the vision step of
+ *      step 4 of "See network", the slot's view action being table[index][3..4].  Slots outside slot_mask take the caller's rows,
+ *      the controllers and view_actions_dev, exactly as there.
+ * A finished match's or a sent-off player's row is built and acted on as "Policy slots" and "See network" treat theirs (the
+ * engine's gating discards the command).  The engine keeps the pointers, not copies; prm is copied at the call.
+ * Not offered: a second see role (no frozen see opponent in the same launch), the agent reward in the see families, a value head
+ * or a Gaussian head (the critic runs on the recorded see rows), agent rows recorded beside see rows (an asymmetric critic),
+ * action masking.
+ * s2d_match_kernel_name ends in "see policy network>" while one is set. */
+typedef struct S2DMatchSeePolicyNet {
+  int32_t h1, h2, n_actions;      /* h1, h2 in {16, 32, 48, 64}; 1 <= K <= 64 */
+  uint32_t slot_mask;             /* bits 0..21, not empty (a policy with no slots is not the record-only network) */
+  const float *params;            /* W1[h1][192], b1, W2[h2][h1], b2, W3[K][h2], b3; device, 16-byte aligned */
+  const uint32_t *deterministic;  /* device word, read when the kernel runs: != 0 -> greedy */
+  const float *table;             /* device float[K][5]: command, a, b, TurnNeck moment, ChangeView code */
+  S2DVisionParams prm;            /* copied at the call */
+  S2DMatchVision vis;             /* the caller's three planes; the engine keeps the pointers */
+  int32_t activation;             /* 0 relu, 1 tanh (tanh_spec) on both hidden layers */
+} S2DMatchSeePolicyNet;
+/* net == NULL: clears the see network, whichever kind is set.  Errors (S2D_EINVAL, the engine unchanged): everything
+ * s2d_match_set_see_network rejects; an activation other than 0 or 1; a NULL or unaligned deterministic word (4 bytes); an empty
+ * slot_mask; an agent reward is set.  s2d_match_step, s2d_match_rollout, s2d_match_rollout_ex and s2d_match_rollout_see use the
+ * see policy when one is set (no log-probability is recorded there); s2d_match_rollout_net, s2d_match_rollout_policy and
+ * s2d_match_rollout_reward return S2D_EINVAL as beside the see network. */
+int s2d_match_set_see_policy_network(S2DMatchHandle h, const S2DMatchSeePolicyNet *net);
+/* s2d_match_rollout_see plus
+ *   logp_out_dev  float[T][N][22] (4-byte aligned, or NULL): a policy slot receives the log-probability of the index it took (in
+ *                 deterministic mode: of the greedy index); every other slot receives 0.0f.
+ * With a see Q-network or the record-only see network set it behaves as s2d_match_rollout_see and logp_out_dev is all zeros.
+ * Errors: as s2d_match_rollout_see; an unaligned logp_out_dev. */
+int s2d_match_rollout_see_policy(S2DMatchHandle h, int n_steps, const float *actions_dev, const float *view_actions_dev,
+                                 const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev,
+                                 float *logp_out_dev, uint32_t obs_mask, float *see_out_dev, void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
- * env_id_offset, auto_reset, noise and the PlayerTypes do not matter for the choice.  With a controller table, a network or a see
- * network set the name ends in "controllers>", "network>" or "see network>". */
+ * env_id_offset, auto_reset, noise and the PlayerTypes do not matter for the choice.  With a controller table, a network, a see
+ * network or a see policy set the name ends in "controllers>", "network>", "see network>" or "see policy network>". */
 const char *s2d_match_kernel_name(S2DMatchHandle h);
 
 #ifdef __cplusplus
