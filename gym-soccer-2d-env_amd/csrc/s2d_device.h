@@ -267,6 +267,19 @@ S2D_DEV void box_muller(uint32_t wa, uint32_t wb, float& zc, float& zs) {
   sincos_deg((float)(wb >> 8) * 2.1457672119140625e-5f, s, c);
   zc = r * c; zs = r * s;
 }
+// The learners' row-keyed normals: z0 .. z(A - 1), A <= 8, of batch row `row` in the call that finds `draws` in its counter word.
+// Philox with key seed at counter {row, draws_lo, draws_hi, (stream << 16) | blk}: blk = 0 gives z0..z3, blk = 1 (drawn only when
+// A > 4) z4..z7, words x, y -> (z0, z1) and z, w -> (z2, z3).  What is not drawn is left as the caller set it.
+S2D_DEV void row_normals(int64_t row, uint64_t draws, uint32_t stream, uint32_t seed_lo, uint32_t seed_hi, int A, float (&z)[8]) {
+  const U4 w = philox4x32_10((uint32_t)row, (uint32_t)draws, (uint32_t)(draws >> 32), stream << 16, seed_lo, seed_hi);
+  box_muller(w.x, w.y, z[0], z[1]);
+  box_muller(w.z, w.w, z[2], z[3]);
+  if (A > 4) {
+    const U4 w2 = philox4x32_10((uint32_t)row, (uint32_t)draws, (uint32_t)(draws >> 32), (stream << 16) | 1u, seed_lo, seed_hi);
+    box_muller(w2.x, w2.y, z[4], z[5]);
+    box_muller(w2.z, w2.w, z[6], z[7]);
+  }
+}
 // pyrusgeom AngleDeg normalisation for |d| <= 540 (every angle the engine forms: sums and
 // differences of two angles in [-180,180], plus 180 for a back dash); general form with
 // fmod kept for the diagnostic entry point.

@@ -1,5 +1,6 @@
 // s2d_sac_head.h -- the squashed-Gaussian head of Soft Actor-Critic, shared by the SAC rollout (s2d_wide_actor.hip,
-// s2d_rollout_sac) and the entropy-regularised TD target (s2d_td.hip, s2d_td_target_sac).  include/s2d.h has the spec, and
+// s2d_rollout_sac), the entropy-regularised TD target (s2d_td.hip: TdSacHead, the head of s2d_td_target_ac_kernel behind
+// s2d_td_target_sac) and the SAC actor step (s2d_learn.hip).  include/s2d.h has the spec, and
 // tests/sac_ref.c::sac_term restates it on the host.
 #pragma once
 #include <hip/hip_runtime.h>

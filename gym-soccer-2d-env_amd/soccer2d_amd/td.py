@@ -120,7 +120,7 @@ class _Net:
 
 
 class _Target:
-    """what the two targets share: the networks on one device, sync() and the checks of target()'s arguments"""
+    """what the targets share: the networks on one device, sync() and the checks of target()'s arguments"""
 
     _name = '_Target'
 
@@ -210,30 +210,59 @@ class QTarget(_Target):
         return result
 
 
-class ActorCriticTarget(_Target):
-    """``reward + discount * q_target(cat(next_obs, mu_target(next_obs)))`` (DDPG), with ``q_target2`` the smaller of the two
-    critics' values (TD3's clipped double-Q; with target-policy smoothing noise: Td3Target), in one launch.  mu_target is
-    Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs (SB3's ``actor_target.mu``); a critic is Linear-(F-Linear) x L from
-    obs_dim + A inputs to one output (SB3's ``critic_target.qf0``)."""
+class _ActorCriticTarget(_Target):
+    """what ActorCriticTarget, Td3Target and SacTarget share: an actor and one or two critics on obs_dim + A inputs, and the
+    launch of their entry point"""
 
-    _name = 'ActorCriticTarget'
+    _entry = None                              # the C entry point
+    _actor = (_Net, 'target actor', True)      # the actor's reader, what the errors call it, whether the module ends in a Tanh
 
-    def __init__(self, mu_target, q_target, q_target2=None, device=None):
-        who = 'ActorCriticTarget'
-        act = _Net(who, 'target actor', mu_target, device, tanh_head=True)
-        if not 1 <= act.n_out <= MAX_ACTION:
-            raise ValueError(f'{who}: the target actor has {act.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+    def __init__(self, actor, q_target, q_target2, device, seed=None):
+        who = self._name
+        net, what, tanh_head = self._actor
+        act = net(who, what, actor, device, tanh_head=tanh_head)
+        self.action_dim = A = self._actions(act)
         dev = device if device is not None else act.device
         critics = [_Net(who, 'target critic 1', q_target, dev)]
         if q_target2 is not None:
             critics.append(_Net(who, 'target critic 2', q_target2, dev))
         for c in critics:
-            if c.n_in != act.n_in + act.n_out or c.n_out != 1:
+            if c.n_in != act.n_in + A or c.n_out != 1:
                 raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
-                                 f'{act.n_in} + {act.n_out} inputs and give one output')
-        self.mu_target, self.critics = act, tuple(critics)
-        self.action_dim = act.n_out
+                                 f'{act.n_in} + {A} inputs and give one output')
+        self.critics = tuple(critics)
         self._init_nets([act] + critics)
+        if seed is not None:
+            self.seed = int(seed) & (2 ** 64 - 1)
+            self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)  # calls so far: the Philox counter's middle words
+
+    def _actions(self, act):
+        """A of the actor's n_out: here n_out itself, 1 .. 8"""
+        if not 1 <= act.n_out <= MAX_ACTION:
+            raise ValueError(f'{self._name}: the target actor has {act.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
+        return act.n_out
+
+    def _launch(self, B, ins, words, outs):
+        """the entry point on torch's current stream: the networks, the batch arrays, the target's own `words`, the outputs"""
+        lib = _capi.load_library()
+        nets = [n.c_struct() for n in self._nets]
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, self._entry)(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, *words,
+                                           *outs, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _capi.check(lib, rc, self._entry)
+
+
+class ActorCriticTarget(_ActorCriticTarget):
+    """``reward + discount * q_target(cat(next_obs, mu_target(next_obs)))`` (DDPG), with ``q_target2`` the smaller of the two
+    critics' values (TD3's clipped double-Q; with target-policy smoothing noise: Td3Target), in one launch.  mu_target is
+    Linear-(F-Linear) x L-Tanh with 1 .. 8 outputs (SB3's ``actor_target.mu``); a critic is Linear-(F-Linear) x L from
+    obs_dim + A inputs to one output (SB3's ``critic_target.qf0``)."""
+
+    _name, _entry = 'ActorCriticTarget', 's2d_td_target_ac'
+
+    def __init__(self, mu_target, q_target, q_target2=None, device=None):
+        super().__init__(mu_target, q_target, q_target2, device)
+        self.mu_target = self._nets[0]
 
     @classmethod
     def from_modules(cls, mu_target, q_target, q_target2=None, device=None):
@@ -244,16 +273,11 @@ class ActorCriticTarget(_Target):
         """float32 [B] targets of a sampled batch, as QTarget.target.  return_q: (target, q [B], action [B, A]): the bootstrapped
         value and the target actor's action it was evaluated at."""
         B, ins, outs, result = self._batch(batch, out, return_q, torch.float32, (self.action_dim,))
-        lib = _capi.load_library()
-        nets = [n.c_struct() for n in self._nets]
-        with torch.cuda.device(self.device):
-            rc = lib.s2d_td_target_ac(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, *outs,
-                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, 's2d_td_target_ac')
+        self._launch(B, ins, (), outs)
         return result
 
 
-class Td3Target(_Target):
+class Td3Target(_ActorCriticTarget):
     """TD3's target in one launch (s2d_td_target_td3): ActorCriticTarget's with target-policy smoothing,
 
         a'     = (mu_target(next_obs) + (sigma * z).clamp(-clip, clip)).clamp(-1, 1)     z ~ N(0, 1), fresh every call
@@ -264,26 +288,11 @@ class Td3Target(_Target):
     words the target owns (``noise``, written by ``set_noise``); z is Philox with key `seed` at a device counter the target owns
     (``draws``): every call, and every replay of a captured graph, advances it by one."""
 
-    _name = 'Td3Target'
+    _name, _entry = 'Td3Target', 's2d_td_target_td3'
 
     def __init__(self, mu_target, q_target, q_target2=None, target_policy_noise=0.2, target_noise_clip=0.5, seed=0, device=None):
-        who = 'Td3Target'
-        act = _Net(who, 'target actor', mu_target, device, tanh_head=True)
-        if not 1 <= act.n_out <= MAX_ACTION:
-            raise ValueError(f'{who}: the target actor has {act.n_out} outputs, the kernel takes 1 to {MAX_ACTION}')
-        dev = device if device is not None else act.device
-        critics = [_Net(who, 'target critic 1', q_target, dev)]
-        if q_target2 is not None:
-            critics.append(_Net(who, 'target critic 2', q_target2, dev))
-        for c in critics:
-            if c.n_in != act.n_in + act.n_out or c.n_out != 1:
-                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
-                                 f'{act.n_in} + {act.n_out} inputs and give one output')
-        self.mu_target, self.critics = act, tuple(critics)
-        self.action_dim = act.n_out
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self._init_nets([act] + critics)
-        self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)      # calls so far: the Philox counter's middle words
+        super().__init__(mu_target, q_target, q_target2, device, seed=seed)
+        self.mu_target = self._nets[0]
         self.noise = torch.zeros(2, dtype=torch.float32, device=self.device)    # sigma, clip: read when the kernel runs
         self.set_noise(target_policy_noise, target_noise_clip)
 
@@ -307,13 +316,7 @@ class Td3Target(_Target):
         """float32 [B] targets of a sampled batch, as ActorCriticTarget.target.  return_q: (target, q [B], action [B, A]): the
         bootstrapped value and the smoothed, clamped action it was evaluated at."""
         B, ins, outs, result = self._batch(batch, out, return_q, torch.float32, (self.action_dim,))
-        lib = _capi.load_library()
-        nets = [n.c_struct() for n in self._nets]
-        with torch.cuda.device(self.device):
-            rc = lib.s2d_td_target_td3(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins,
-                                       C.c_void_p(self.noise.data_ptr()), C.c_void_p(self.draws.data_ptr()), self.seed, *outs,
-                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, 's2d_td_target_td3')
+        self._launch(B, ins, (C.c_void_p(self.noise.data_ptr()), C.c_void_p(self.draws.data_ptr()), self.seed), outs)
         return result
 
 
@@ -341,7 +344,7 @@ class _SacActorNet(_Net):
         return tensors, linears[0].in_features, [lin.out_features for lin in linears[:-1]] + [2 * mu.out_features], act
 
 
-class SacTarget(_Target):
+class SacTarget(_ActorCriticTarget):
     """Soft Actor-Critic's entropy-regularised target in one launch (s2d_td_target_sac):
 
         a', logp = squashed-Gaussian head of actor(next_obs)     the ONLINE actor, as in SB3, with fresh noise every call
@@ -352,28 +355,20 @@ class SacTarget(_Target):
     output (SB3's ``critic_target.qf0``).  The noise is Philox with key `seed` at a device counter the target owns (``draws``):
     every call, and every replay of a captured graph, advances it by one."""
 
-    _name = 'SacTarget'
+    _name, _entry = 'SacTarget', 's2d_td_target_sac'
+    _actor = (_SacActorNet, 'actor', False)
 
     def __init__(self, actor, q_target, q_target2=None, seed=0, device=None):
-        who = 'SacTarget'
-        act = _SacActorNet(who, 'actor', actor, device)
-        if act.n_out % 2 or not 1 <= act.n_out // 2 <= MAX_ACTION:
-            raise ValueError(f'{who}: the actor has {act.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
-                             f'1 .. {MAX_ACTION}')
-        self.action_dim = act.n_out // 2
-        dev = device if device is not None else act.device
-        critics = [_Net(who, 'target critic 1', q_target, dev)]
-        if q_target2 is not None:
-            critics.append(_Net(who, 'target critic 2', q_target2, dev))
-        for c in critics:
-            if c.n_in != act.n_in + self.action_dim or c.n_out != 1:
-                raise ValueError(f'{who}: the {c.what} is {c.text()}; with the actor {act.text()} it must take obs_dim + A = '
-                                 f'{act.n_in} + {self.action_dim} inputs and give one output')
-        self.actor, self.critics = act, tuple(critics)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self._init_nets([act] + critics)
-        self.draws = torch.zeros(1, dtype=torch.int64, device=self.device)      # calls so far: the Philox counter's middle words
+        super().__init__(actor, q_target, q_target2, device, seed=seed)
+        self.actor = self._nets[0]
         self._alpha = torch.zeros(1, dtype=torch.float32, device=self.device)   # where a Python float alpha is written
+
+    def _actions(self, act):
+        """A of the actor's n_out = 2 A"""
+        if act.n_out % 2 or not 1 <= act.n_out // 2 <= MAX_ACTION:
+            raise ValueError(f'{self._name}: the actor has {act.n_out} outputs; the kernel takes 2 A (A means, then A log-std rows) with A in '
+                             f'1 .. {MAX_ACTION}')
+        return act.n_out // 2
 
     @classmethod
     def from_modules(cls, actor, q_target, q_target2=None, seed=0, device=None):
@@ -404,13 +399,7 @@ class SacTarget(_Target):
         else:
             self._alpha.fill_(float(alpha))
             a = C.c_void_p(self._alpha.data_ptr())
-        lib = _capi.load_library()
-        nets = [n.c_struct() for n in self._nets]
-        with torch.cuda.device(self.device):
-            rc = lib.s2d_td_target_sac(B, C.byref(nets[0]), C.byref(nets[1]), C.byref(nets[2]) if len(nets) > 2 else None, *ins, a,
-                                       C.c_void_p(self.draws.data_ptr()), self.seed, *outs, lp,
-                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _capi.check(lib, rc, 's2d_td_target_sac')
+        self._launch(B, ins, (a, C.c_void_p(self.draws.data_ptr()), self.seed), outs + [lp])
         return result
 
 
