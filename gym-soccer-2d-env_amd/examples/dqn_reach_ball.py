@@ -18,6 +18,9 @@ network (soccer2d_amd.td.QTarget) instead of a chain of torch op
 the online network's argmax (Double DQN), with or without --fused-target.  --fused-learner (with --fused-actor and --fused-target)
 makes every update one call of soccer2d_amd.learn.QLearner -- forward, backward, clip and Adam in HIP -- so an
 update is sample -> target -> step (-> update_priorities with --per-alpha).
+
+--episode-stats (with --fused-actor) hands every collected record to soccer2d_amd.episodes.EpisodeStats and prints SB3's
+ep_rew_mean / ep_len_mean of the training episodes after each iteration.
 """
 import argparse
 import copy
@@ -96,6 +99,7 @@ class DeviceDQN:
         self.eps_start, self.eps_end, self.eps_decay = eps_start, eps_end, eps_decay_steps
         self.steps = 0
         self.obs = env.reset().clone()
+        self.episode_stats = None                                        # --episode-stats: the collected records go through it
 
     def epsilon(self):
         f = min(1.0, self.steps / self.eps_decay)
@@ -249,6 +253,8 @@ class DeviceDQN:
             obs0 = eng.obs.clone()                               # the observation the first action is chosen from
             self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
             rb.push(rec, obs0)                                   # T x N n-step transitions, Timeouts bootstrap (one launch)
+            if self.episode_stats is not None:
+                self.episode_stats.update_record(rec)
             if on_result is not None:
                 on_result(rec['result'].reshape(-1))
             self.after_fused_launch(T)
@@ -296,7 +302,12 @@ def main():
     ap.add_argument('--per-beta', type=float, default=0.4, metavar='B', help='with --per-alpha: the importance-weight exponent')
     ap.add_argument('--fused-learner', action='store_true',
                     help='with --fused-actor and --fused-target: forward, backward, clip and Adam in one call (soccer2d_amd.learn.QLearner)')
+    ap.add_argument('--episode-stats', action='store_true',
+                    help='with --fused-actor: episode returns / lengths / results of the collected records on the device '
+                         '(soccer2d_amd.episodes.EpisodeStats), one more line per iteration')
     args = ap.parse_args()
+    if args.episode_stats and args.fused_actor <= 0:
+        ap.error('--episode-stats needs --fused-actor T')
     if args.fused_target and args.fused_actor <= 0:
         ap.error('--fused-target needs --fused-actor T')
     if args.fused_learner and not (args.fused_actor > 0 and args.fused_target):
@@ -306,6 +317,9 @@ def main():
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kewargs)
     model = DeviceDQN(env, net_arch=net_arch, activation=args.activation, n_step=args.n_step, per_alpha=args.per_alpha,
                       per_beta=args.per_beta, fused_target=args.fused_target, double_q=args.double_q, fused_learner=args.fused_learner)
+    if args.episode_stats:
+        from soccer2d_amd.episodes import EpisodeStats
+        model.episode_stats = EpisodeStats(args.envs, device=env.device)      # SB3's window of 100 episodes
     print('random policy:', test(test_env, None, args.test_steps))
     for i in range(args.iters):
         t0 = time.time()
@@ -317,6 +331,10 @@ def main():
         dt = time.time() - t0
         r = test(test_env, model, args.test_steps)
         print(f'iter {i}: {args.train_steps * args.envs / dt / 1e6:.2f} M env-steps/s incl. learning  eps={model.epsilon():.2f}  {r}')
+        if model.episode_stats is not None:
+            s = model.episode_stats.summary()
+            print(f"iter {i}: ep_rew_mean {s['ep_rew_mean']:.4f}  ep_len_mean {s['ep_len_mean']:.2f}  Goal {s['window_goal']:.4f} over the "
+                  f"last {s['window']} of {s['episodes']} training episodes")
     env.close(); test_env.close()
 
 

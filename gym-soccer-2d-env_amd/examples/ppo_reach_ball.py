@@ -18,6 +18,11 @@ refreshed with sync() after them.  0: one torch forward per ste
 --fused-learner runs the epochs in HIP as well (soccer2d_amd.learn.PPOLearner): every minibatch step -- the gather by the
 permutation, both forward passes, log-probability, entropy, clipped surrogate, value loss, backward, clip and Adam -- is one call,
 and pi, vf and log_std stay the modules the rest of the script uses (their parameters become views of the learner's buffer).
+
+--episode-stats (with --fused-actor) hands every collected record to soccer2d_amd.episodes.EpisodeStats (one more call per
+launch, no host loop) and prints SB3's ep_rew_mean / ep_len_mean of the training episodes after each iteration.  --fused-eval T
+evaluates with the same machinery instead of one torch forward and one env.step per vector step: the greedy policy in-kernel
+(the learner's StochasticActor with deterministic = True) on the test env, T steps per launch, episodes counted on the device.
 """
 import argparse
 import os
@@ -68,6 +73,7 @@ class DevicePPO:
         self.vf_coef, self.ent_coef = vf_coef, ent_coef
         self.obs = env.reset().clone()
         self.last_loss = float('nan')
+        self.episode_stats = None                            # --episode-stats: an EpisodeStats the collected records go through
 
     def dist(self, obs):
         y = self.pi(obs)
@@ -139,18 +145,26 @@ class DevicePPO:
                 self.obs = nobs.clone()
             self._finish(obs_t, act, logp, rew, done, res, term, self.obs)
 
-    def learn_fused(self, vec_steps, T):
-        """The same PPO, experience collected T steps per launch by the fused stochastic policy (the learner's own policy net
-        in-kernel, with the log-probabilities recorded)."""
+    def fused_actor(self):
+        """the in-kernel policy (the learner's own policy net), made once"""
         from soccer2d_amd.actor import StochasticActor
         if not hasattr(self, 'actor'):
             self.actor = StochasticActor.from_module(self.pi, log_std=None if self.discrete else self.log_std, device=self.dev)
+        return self.actor
+
+    def learn_fused(self, vec_steps, T):
+        """The same PPO, experience collected T steps per launch by the fused stochastic policy (the learner's own policy net
+        in-kernel, with the log-probabilities recorded)."""
+        if not hasattr(self, 'rec'):
+            self.fused_actor()
             self.rec = self.env.engine.alloc_rollout(T, terminal_obs=True, logp=True)
             self.rec['terminal_obs'].zero_()
         eng, rec = self.env.engine, self.rec
         for _ in range((vec_steps + T - 1) // T):
             obs0 = eng.obs.clone()                               # the observation the first action is chosen from
             self.env.rollout(T, out=rec, policy=self.actor, terminal_obs=True)
+            if self.episode_stats is not None:
+                self.episode_stats.update_record(rec)            # returns, lengths and results of the episodes that ended
             obs_t = torch.cat([obs0[None], rec['obs'][:-1]])       # action t was chosen from the observation of step t - 1
             self._finish(obs_t, rec['action'].long() if self.discrete else rec['action'], rec['logp'], rec['reward'], rec['done'],
                          rec['result'], rec['terminal_obs'], eng.obs)
@@ -170,6 +184,28 @@ def test(env, model, vec_steps):
     return {'Goal': c[1] / n, 'Out': c[2] / n, 'Timeout': c[3] / n, 'episodes': n}
 
 
+def test_fused(env, model, vec_steps, T):
+    """test() without the per-step loop: the greedy policy in-kernel on the test env, T steps per launch, and the finished
+    episodes counted by an EpisodeStats that keeps every one of them; test()'s keys plus ep_rew_mean / ep_len_mean"""
+    from soccer2d_amd.episodes import EpisodeStats
+    env.reset()
+    eng, actor = env.engine, model.fused_actor()
+    actor.sync()                                             # the weights as they are now
+    stats = EpisodeStats(env.num_envs, capacity=vec_steps * env.num_envs, device=env.device)
+    rec = eng.alloc_rollout(T, with_obs=False)
+    was, actor.deterministic = actor.deterministic, True
+    try:
+        for t in range(0, vec_steps, T):
+            n = min(T, vec_steps - t)
+            eng.rollout_policy(n, actor, out=rec, with_obs=False, logp=False)
+            stats.update(rec['reward'][:n], rec['done'][:n], rec['result'][:n])
+    finally:
+        actor.deterministic = was
+    s = stats.summary()
+    return {'Goal': s['Goal'], 'Out': s['Out'], 'Timeout': s['Timeout'], 'episodes': max(1, s['episodes']),
+            'ep_rew_mean': s['ep_rew_mean'], 'ep_len_mean': s['ep_len_mean']}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=4096)
@@ -186,13 +222,26 @@ def main():
                     help='the minibatch epochs in HIP (soccer2d_amd.learn.PPOLearner) instead of torch autograd and Adam')
     ap.add_argument('--hidden', type=int, default=64, help='width of the two hidden layers of both networks (64; another width shows what --fused-learner and --fused-actor '
                          'accept: the learner takes multiples of 8 in [8, 256] and names that grid when it refuses)')
+    ap.add_argument('--episode-stats', action='store_true',
+                    help='with --fused-actor: episode returns / lengths / results of the collected records on the device '
+                         '(soccer2d_amd.episodes.EpisodeStats), one more line per iteration')
+    ap.add_argument('--fused-eval', type=int, default=0, metavar='T',
+                    help='evaluate with the in-kernel greedy policy, T steps per launch, episodes counted on the device '
+                         '(0: one torch forward and one env.step per vector step)')
     args = ap.parse_args()
+    if args.episode_stats and args.fused_actor <= 0:
+        ap.error('--episode-stats needs --fused-actor T')
     kw = dict(kewargs, use_continuous_action=args.continuous or args.turning, use_turning=args.turning)
     env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, **kw)
     test_env = EnvironmentFactory().create_vec('reachball', args.envs, device=args.device, seed=1234, **kw)
     model = DevicePPO(env, tanh=args.tanh, hidden=args.hidden, fused_learner=args.fused_learner,
                       max_batch=args.envs * (args.fused_actor if args.fused_actor > 0 else 32))
-    r0 = test(test_env, model, args.test_steps)
+    if args.episode_stats:
+        from soccer2d_amd.episodes import EpisodeStats
+        model.episode_stats = EpisodeStats(args.envs, device=env.device)      # SB3's window of 100 episodes
+    evaluate = (lambda: test_fused(test_env, model, args.test_steps, args.fused_eval)) if args.fused_eval > 0 else \
+        (lambda: test(test_env, model, args.test_steps))
+    r0 = evaluate()
     print('untrained policy:', r0)
     r = r0
     for i in range(args.iters):
@@ -203,8 +252,12 @@ def main():
             model.learn(args.train_steps, 32)
         torch.cuda.synchronize()
         dt = time.time() - t0
-        r = test(test_env, model, args.test_steps)
+        r = evaluate()
         print(f'iter {i}: loss {model.last_loss:.5f}  {args.train_steps * args.envs / dt / 1e6:.2f} M env-steps/s incl. learning  {r}')
+        if model.episode_stats is not None:
+            s = model.episode_stats.summary()
+            print(f"iter {i}: ep_rew_mean {s['ep_rew_mean']:.4f}  ep_len_mean {s['ep_len_mean']:.2f}  Goal {s['window_goal']:.4f} over the "
+                  f"last {s['window']} of {s['episodes']} training episodes")
     print(f"goal share: {r0['Goal']:.4f} before, {r['Goal']:.4f} after {args.iters} iterations")
     env.close(); test_env.close()
 

@@ -140,6 +140,12 @@ class S2DReplayRing(C.Structure):
                 ('reward', C.c_void_p), ('discount', C.c_void_p)]
 
 
+class S2DEpisodeRing(C.Structure):
+    """the caller-owned ring of s2d_episode_stats (device pointers of the five arrays, capacity in episodes)"""
+    _fields_ = [('ret', C.c_void_p), ('length', C.c_void_p), ('result', C.c_void_p), ('env', C.c_void_p), ('step', C.c_void_p),
+                ('capacity', C.c_int64)]
+
+
 class S2DLearnNet(C.Structure):
     """the network of s2d_learn_q / s2d_learn_q_grad: S2DTdNet's shape on the learner's grid, its READ-WRITE parameters and the
     workspace of the blocks' partial gradients"""
@@ -233,6 +239,9 @@ PROTOTYPES = (
     ('s2d_replay_sample_prio', C.c_int, (C.c_int64, C.c_int, C.c_int, C.POINTER(S2DReplayRing), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p)),
+    ('s2d_episode_stats_workspace', C.c_size_t, (C.c_int, C.c_int64)),
+    ('s2d_episode_stats', C.c_int, (C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(S2DEpisodeRing), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)),
     ('s2d_td_workspace_bytes', C.c_size_t, (C.POINTER(S2DTdNet),)),
     ('s2d_td_target_q', C.c_int, (C.c_int64, C.POINTER(S2DTdNet), C.POINTER(S2DTdNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p)),

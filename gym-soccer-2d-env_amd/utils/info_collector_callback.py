@@ -38,6 +38,13 @@ class InfoCollectorCallback(_Base):
         names = (None,) + RESULT_TYPES
         self.infos.extend({'result': names[x]} for x in c)
 
+    def on_episode_stats(self, stats):
+        """Fused-collection variant: `stats` is a soccer2d_amd.episodes.EpisodeStats the records went through.  Takes the results
+        of the episodes finished since the previous call (one byte per EPISODE crosses to the host, in the order
+        on_result_codes would have met them); unlabelled episodes are skipped as on_infos skips them."""
+        names = (None,) + RESULT_TYPES
+        self.infos.extend({'result': names[x]} for x in stats.new_result_codes().tolist() if 0 < x < len(names))
+
     def reset(self):
         self.infos = []
         self.results = {}

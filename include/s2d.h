@@ -28,6 +28,8 @@
  *   s2d_replay_sample          ReplayBuffer.sample (uniform, with replacement)
  *   s2d_replay_prio_push / s2d_replay_sample_prio / s2d_replay_prio_update   proportional prioritized replay (Schaul et al.,
  *                              2016; SB3 has none) on a sum tree over the same ring
+ *   s2d_episode_stats          Monitor's episode returns / lengths (ep_info_buffer: ep_rew_mean, ep_len_mean) and the results
+ *                              InfoCollectorCallback tallies, for a whole [T][N] record at once
  *   s2d_world_model            protobuf State/WorldModel fields  idl/service.proto:22-27, 68-86,
  *                              144-223, 306-349 (returned as device arrays, not wire bytes)
  *   S2DConfig                  ReachBallEnv kwargs               reach_ball_env.py:26-36
@@ -551,6 +553,44 @@ int s2d_replay_prio_update(int64_t batch, int64_t capacity, float *tree, const u
 int s2d_replay_sample_prio(int64_t batch, int obs_dim, int action_words, const S2DReplayRing *ring, const float *tree,
                            uint64_t *cursor, uint64_t seed, void *b_obs, void *b_next, void *b_action, float *b_reward,
                            float *b_discount, int32_t *b_index, float *b_priority, float *b_total, void *stream);
+
+/* ---- episode statistics of a record (s2d_episodes.hip): what the person watching the run reads ----
+ * The third consumer of a [T][N] record beside s2d_gae and s2d_replay_push, ENGINE-INDEPENDENT like them: no handle, raw device
+ * pointers, any stream of the current device; everything is read WHEN THE KERNELS RUN, so it can be captured behind a rollout
+ * launch as a linear chain on one stream.  An episode usually spans several records: the caller owns each env's running
+ * return and length (acc_return / acc_length [N], zero at start) and hands them to every call.  Finished episodes go to a
+ * caller-owned ring of `capacity` episodes, 1 <= capacity < 2^31 (the five arrays [capacity]; step 8-byte aligned), exact
+ * counts to `totals` = device uint64[8], 8-byte aligned, zero at start:
+ *   {episodes, vector steps, episodes by result 0 (unlabelled) / 1 / 2 / 3, sum of episode lengths, episodes not kept}.
+ * With e0 = totals[0] and s0 = totals[1] before the call, for every env i, t ascending:
+ *   R = acc_return[i] + (reward ? reward[t][i] : +0.0f);                one fp32 add, in this order
+ *   L = acc_length[i] + 1;
+ *   if (done[t][i]) { emit(R, L, r = result ? result[t][i] : 0, i, s0 + t); acc_return[i] = +0.0f; acc_length[i] = 0; }
+ *   else            { acc_return[i] = R; acc_length[i] = L; }
+ * (result is read only where done is set).  The emitted episode's rank k is the number of set done[t'][i'] with (t', i')
+ * lexicographically before (t, i): row-major order, the order a per-step loop over the envs meets them.  With n = the number
+ * of set done bytes of the record and C = capacity, the episode of rank k is written to slot (e0 + k) mod C of all five
+ * arrays if and only if k >= n - C; earlier episodes of the call are not written at all, so a slot has at most one writer.
+ * A one-thread kernel queued behind the others then sets totals[0] = e0 + n, totals[1] = s0 + T,
+ * totals[2 + (r <= 3 ? r : 0)] += 1 per episode, totals[6] += the sum of L, totals[7] += max(0, n - C); no wave of the call sees
+ * the new values.  Slots the call does not own and the inputs are untouched; the workspace belongs to one call at a time and
+ * holds nothing between calls.  There is no float atomic and no sum by arrival order: every output is the same bits whatever
+ * the launch geometry.  S2D_EINVAL without a launch: n_steps < 1, n_envs outside [1, 2^31 - 1], T * N >= 2^40, capacity outside
+ * [1, 2^31 - 1], a NULL pointer other than reward / result, totals or step not 8-byte aligned (4 bytes for the 4-byte arrays),
+ * workspace_bytes below s2d_episode_stats_workspace(n_steps, n_envs). */
+typedef struct S2DEpisodeRing {
+  float *ret;
+  int32_t *length;
+  uint8_t *result;
+  int32_t *env;
+  int64_t *step;
+  int64_t capacity;
+} S2DEpisodeRing;
+/* bytes of workspace of a shape; 0 for a shape the call rejects.  Host only, needs no GPU. */
+size_t s2d_episode_stats_workspace(int n_steps, int64_t n_envs);
+int s2d_episode_stats(int n_steps, int64_t n_envs, const float *reward /* [T][N] or NULL */, const uint8_t *done /* [T][N] */,
+                      const uint8_t *result /* [T][N] or NULL */, float *acc_return /* [N] */, int32_t *acc_length /* [N] */,
+                      const S2DEpisodeRing *ring, uint64_t *totals /* [8] */, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- TD targets from the target networks (s2d_td.hip) ----
  * What follows a sampled batch in every off-policy learner and needs no gradient: reward + discount * bootstrap(next_obs), in
