@@ -1,5 +1,5 @@
 // s2d_head.h -- the categorical head of the stochastic policies, shared by the reach-ball policy rollout (s2d_policy.hip) and the
-// 11v11 engine's policy slots (s2d_match.hip).  (Moved out of s2d_policy.hip unchanged; include/s2d.h has the spec, and
+// 11v11 engine's policy slots (s2d_match_slots.h).  (Moved out of s2d_policy.hip unchanged; include/s2d.h has the spec, and
 // tests/policy_ref.c::categorical restates it on the host.)
 #pragma once
 #include <hip/hip_runtime.h>

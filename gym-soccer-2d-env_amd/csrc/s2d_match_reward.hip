@@ -2,13 +2,12 @@
 //
 // A translation unit of its own, for two reasons.  The RW family is 15 more instantiations of the library's largest kernel: built
 // beside s2d_match.hip they compile in parallel with it.  And nothing instantiated here can reach the code of s2d_match.hip's
-// kernels: helpers that two families share have been optimised differently before (see MParamsCtl there).
+// kernels: helpers that two families share have been optimised differently before (see MParamsCtl in s2d_match_rules.h).
 //
-// The cycle kernel, its device functions and the launch plumbing are s2d_match.hip's, included with S2D_MATCH_REWARD_UNIT set:
-// that leaves out what may exist only once in the library -- the non-template kernels and the C ABI.  This unit defines one
+// The cycle kernel, its device functions and the launch plumbing come from s2d_match_host.h and the headers under it; what may
+// exist only once in the library -- the non-template kernels and the C ABI -- is in s2d_match.hip.  This unit defines one
 // function, the launch s2d_match.hip's m_launch calls when a reward record is asked for.
-#define S2D_MATCH_REWARD_UNIT 1
-#include "s2d_match.hip"
+#include "s2d_match_host.h"
 
 // na: the network launch (one or two Q-networks, or records only); pa: the policy launch; neither: the controller launch.
 int s2d_match_internal_reward_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st, const MCtlRw& ctl,

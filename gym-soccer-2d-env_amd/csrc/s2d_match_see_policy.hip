@@ -4,11 +4,10 @@
 // the library's largest kernel, which compile beside s2d_match.hip instead of after it, and nothing instantiated here can reach
 // the code of the SEE kernels it was derived from.
 //
-// The cycle kernel, its device functions and the launch plumbing are s2d_match.hip's, included with S2D_MATCH_REWARD_UNIT set
-// (the switch that leaves out what may exist only once in the library: the non-template kernels and the C ABI).  This unit
-// defines one function, the launch s2d_match.hip's m_launch calls when the engine's see network holds a policy.
-#define S2D_MATCH_REWARD_UNIT 1
-#include "s2d_match.hip"
+// The cycle kernel, its device functions and the launch plumbing come from s2d_match_host.h and the headers under it; what may
+// exist only once in the library -- the non-template kernels and the C ABI -- is in s2d_match.hip.  This unit defines one
+// function, the launch s2d_match.hip's m_launch calls when the engine's see network holds a policy.
+#include "s2d_match_host.h"
 
 int s2d_match_internal_see_policy_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st,
                                          const MCtl& ctl, const MSeePolArg& pa) {

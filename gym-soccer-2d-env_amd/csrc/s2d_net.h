@@ -1,5 +1,5 @@
 // s2d_net.h -- the building blocks of the fused networks, shared by the reach-ball actors (s2d_actor.hip) and the 11v11
-// engine's network slots (s2d_match.hip): one layer on v_mfma_f32_16x16x4_f32 in the k-ordered fmaf spec, and the exploration
+// engine's network slots (s2d_match_slots.h): one layer on v_mfma_f32_16x16x4_f32 in the k-ordered fmaf spec, and the exploration
 // threshold of a device epsilon.  (Moved out of s2d_actor.hip unchanged.)
 //
 // v_mfma_f32_16x16x4_f32 is bit for bit the k-ordered fmaf chain acc = fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1,

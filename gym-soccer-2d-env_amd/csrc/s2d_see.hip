@@ -3,12 +3,12 @@
 // (EXT: parity to rcssserver unpinned); tests/see_ref.c is an independent CPU restatement this file matches bit for bit.
 //
 // A unit of its own: it reads an engine through the public s2d_match_buffers() and one library-internal accessor for the
-// Philox keys; the engine holds no vision state, so nothing in s2d_match.hip's kernels knows of this file
+// Philox keys; the engine holds no vision state, so nothing in the match engine's kernels knows of this file
 // (a see network, s2d_match_set_see_network, is the cycle kernel's own use of s2d_see_row.h).
 //
 // Mapping of the see kernel, as s2d_match_agent_obs_kernel: ONE MATCH PER HALF-WAVE, lane = object (0..21 players, 22 the ball).
 // The loop over the mask's agents is uniform.  The row itself -- and one player's vision step -- are device functions in
-// s2d_see_row.h, which the cycle kernel's SEE instantiations (s2d_match.hip) execute too; here the row is assembled in LDS and
+// s2d_see_row.h, which the cycle kernel's SEE instantiations (s2d_match_cycle.h) execute too; here the row is assembled in LDS and
 // leaves as whole 64-byte lines, one float4 per lane and store instruction.
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // s2d_see_row.h -- the see row and the vision step of the 11v11 vision layer (include/s2d_match.h, "Vision") as device functions.
 // Two kernels execute this source: s2d_match_see_kernel / s2d_match_vision_step_kernel (s2d_see.hip: state from memory, one launch
-// per call) and the SEE instantiations of the cycle kernel (s2d_match.hip: state from registers, every cycle of a launch).  A see
+// per call) and the SEE instantiations of the cycle kernel (s2d_match_cycle.h: state from registers, every cycle of a launch).  A see
 // row recorded by the cycle kernel is therefore bitwise the row s2d_match_see returns at that moment.
 //
 // Mapping (both callers): ONE MATCH PER HALF-WAVE, lane = object (0..21 players, 22 the ball).  Per agent every lane derives the

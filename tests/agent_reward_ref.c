@@ -1,4 +1,4 @@
-/* Host restatement of the agent reward (include/s2d_match.h, "Agent reward"; device: m_agent_reward in s2d_match.hip).
+/* Host restatement of the agent reward (include/s2d_match.h, "Agent reward"; device: m_agent_reward in s2d_match_slots.h).
  * TEST INFRASTRUCTURE: compiled by the tests with -ffp-contract=off and bound with ctypes.  Written from the header's table: the
  * row words come from the rows of tests/agent_obs_ref.c (row(S), row(S')), everything else from the two states' planes. */
 #include "../oracle/s2d_oracle_common.h"

@@ -1,4 +1,4 @@
-/* Host restatement of the scripted team (include/s2d_match.h, rules 1-8; device: m_scripted_action in s2d_match.hip).
+/* Host restatement of the scripted team (include/s2d_match.h, rules 1-8; device: m_scripted_action in s2d_match_rules.h).
  * TEST INFRASTRUCTURE: compiled by the tests with -ffp-contract=off and bound with ctypes.  atan2_deg / norm_deg / sq2 are the
  * fp32 spec functions of oracle/s2d_oracle_common.h, so the result is comparable with the device bit for bit. */
 #include "../oracle/s2d_oracle_common.h"

@@ -364,7 +364,7 @@ def test_header_constants_and_struct_sizes(tmp_path):
     got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
     assert got == [C.sizeof(M.S2DVisionParams), C.sizeof(M.S2DMatchVision), M.SEE_DIM, M.MATCH_ST_SEE, 0, 16, 24, 8]
     # streams 0..7 belong to the engine
-    src = open(os.path.join(ROOT, 'gym-soccer-2d-env_amd', 'csrc', 's2d_match.hip')).read()
+    src = open(os.path.join(ROOT, 'gym-soccer-2d-env_amd', 'csrc', 's2d_match_rules.h')).read()
     assert 'S2D_ST_NET = S2D_MATCH_ST_NET' in src and M.MATCH_ST_NET == 7
 
 
