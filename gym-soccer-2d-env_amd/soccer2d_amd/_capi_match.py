@@ -62,6 +62,27 @@ for _i, _n in enumerate(('level', 'dist', 'dir', 'dist_chg', 'dir_chg', 'game_mo
 for _i, _n in enumerate(SEE_ROW_FIELDS):
     SEE_FIELDS['players.' + _n] = slice(24 + _i, 192, 8)
 
+# the belief layer (s2d_match_belief_scan; the words are specified in include/s2d_match.h, "Belief")
+BELIEF_DIM, BELIEF_COUNT_LIMIT = 192, 16777216.0
+BELIEF_BLOCKS = {'self': slice(0, 16), 'ball': slice(16, 24), 'players': slice(24, 192)}
+BELIEF_ROW_FIELDS = ('x', 'y', 'vx', 'vy', 'body', 'pos_count', 'vel_count', 'body_count')     # one player row
+BELIEF_FIELDS = {k: v for k, v in SEE_FIELDS.items() if k.startswith('self.')}   # every word 0..191 exactly once, as SEE_FIELDS
+for _i, _n in enumerate(('x', 'y', 'vx', 'vy', 'pos_count', 'game_mode_type', 'mode_side', 'cycle')):
+    BELIEF_FIELDS['ball.' + _n] = 16 + _i
+for _i, _n in enumerate(BELIEF_ROW_FIELDS):
+    BELIEF_FIELDS['players.' + _n] = slice(24 + _i, 192, 8)
+
+
+def belief_row_of(slot, other):
+    """the player row (0..20) of raw slot `other` in the belief of the agent in raw slot `slot`: teammates first by own index
+    with the agent itself left out, then the opponents by unum"""
+    if slot == other or not (0 <= slot < MATCH_PLAYERS and 0 <= other < MATCH_PLAYERS):
+        raise ValueError(f"no belief row of slot {other} for the agent in slot {slot}")
+    u, i = slot % 11, other % 11
+    if (slot < 11) == (other < 11):
+        return i if i < u else i - 1
+    return 10 + i
+
 
 class S2DMatchParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
@@ -161,6 +182,14 @@ class S2DMatchVision(C.Structure):          # the caller-owned vision planes, [N
     _fields_ = [('neck', C.c_void_p), ('view_width', C.c_void_p), ('see_wait', C.c_void_p)]
 
 
+BELIEF_PARAM_FIELDS = ('ball_decay', 'player_decay', 'match_dist', 'match_rate', 'ghost_margin', 'count_max')
+
+
+class S2DBeliefParams(C.Structure):         # include/s2d_match.h: Belief
+    _fields_ = [('ball_decay', C.c_double), ('player_decay', C.c_double), ('view_angle', C.c_double * 3),
+                ('match_dist', C.c_double), ('match_rate', C.c_double), ('ghost_margin', C.c_double), ('count_max', C.c_double)]
+
+
 class S2DMatchSeeNet(C.Structure):          # include/s2d_match.h: see network
     _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
                 ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p),
@@ -214,6 +243,11 @@ MATCH_PROTOTYPES = (
                                         C.c_void_p)),
     ('s2d_match_see', C.c_int, (C.c_void_p, C.POINTER(S2DVisionParams), C.POINTER(S2DMatchVision), C.c_uint32, C.c_void_p,
                                 C.c_void_p)),
+    ('s2d_match_belief_default_params', None, (C.POINTER(S2DBeliefParams),)),
+    ('s2d_match_belief_validate', C.c_int, (C.POINTER(S2DBeliefParams),)),
+    ('s2d_match_belief_reset', C.c_int, (C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_belief_scan', C.c_int, (C.POINTER(S2DBeliefParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_int64, C.c_uint32, C.c_void_p)),
     ('s2d_match_set_see_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_see', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
@@ -307,4 +341,24 @@ def vision_params(lib, **params):
         else:
             raise ValueError(f"unknown vision parameter {k!r}")
     _capi.check(lib, lib.s2d_match_vision_validate(C.byref(prm)), 's2d_match_vision_validate')
+    return prm
+
+
+def belief_params(lib, **params):
+    """S2DBeliefParams: the defaults of s2d_match_belief_default_params with `params` written over them (view_angle: three
+    values, narrow / normal / wide), validated by s2d_match_belief_validate."""
+    prm = S2DBeliefParams()
+    lib.s2d_match_belief_default_params(C.byref(prm))
+    for k, v in params.items():
+        if k == 'view_angle':
+            vals = [float(x) for x in v]
+            if len(vals) != 3:
+                raise ValueError("view_angle needs three values (narrow, normal, wide)")
+            for i, x in enumerate(vals):
+                prm.view_angle[i] = x
+        elif k in BELIEF_PARAM_FIELDS:
+            setattr(prm, k, float(v))
+        else:
+            raise ValueError(f"unknown belief parameter {k!r}")
+    _capi.check(lib, lib.s2d_match_belief_validate(C.byref(prm)), 's2d_match_belief_validate')
     return prm

@@ -80,6 +80,7 @@ class MatchEngine:
         self.network, self.network_mask = None, 0       # no network slots (set_network)
         self.opponent_network, self.opponent_mask = None, 0   # no second network (set_opponent_network)
         self.vision = None                              # no vision layer (enable_vision)
+        self.belief = None                              # no belief layer (enable_belief)
         self.agent_reward_weights = None                # no agent reward (set_agent_reward)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -260,6 +261,9 @@ class MatchEngine:
         if self.vision is not None:
             _capi.check(self.lib, self.lib.s2d_match_vision_reset(self._h, C.byref(self.vision), ptr, self._stream()),
                         's2d_match_vision_reset')
+        if self.belief is not None:
+            _capi.check(self.lib, self.lib.s2d_match_belief_reset(_ptr(self.belief), self.num_envs, self.belief_mask, ptr,
+                                                                  self._stream()), 's2d_match_belief_reset')
         self._keep = mask
 
     def step(self, actions=None):
@@ -491,6 +495,78 @@ class MatchEngine:
                                                       C.c_void_p(out.data_ptr()), self._stream()), 's2d_match_see')
         return out
 
+    def enable_belief(self, slots='all', **params):
+        """Switch the belief layer on (include/s2d_match.h, "Belief"): each selected agent's memory of what it has seen, a row of
+        192 words as wide as its see row (the words: _capi_match.BELIEF_FIELDS).  Needs the vision layer.  Allocates `belief`
+        float32 [N, k, 192] (rows in ascending slot order; slots as for see) and resets it; from now on reset() resets the
+        masked matches' rows.  `params`: S2DBeliefParams fields; ball_decay and player_decay default to the engine's
+        ServerParam, view_angle to the vision parameters'.  The layer reads see rows only: the engine does not change."""
+        self._need_vision()
+        params.setdefault('ball_decay', self.cfg.sp.ball_decay)
+        params.setdefault('player_decay', self.cfg.sp.player_decay)
+        params.setdefault('view_angle', tuple(self.vision_params.view_angle))
+        self.belief_params = M.belief_params(self.lib, **params)
+        self.belief_mask = M.agent_slot_mask(slots)
+        self.belief_slots = slots
+        self.belief = torch.empty((self.num_envs, bin(self.belief_mask).count('1'), M.BELIEF_DIM), dtype=torch.float32,
+                                  device=self.device)
+        _capi.check(self.lib, self.lib.s2d_match_belief_reset(_ptr(self.belief), self.num_envs, self.belief_mask, None,
+                                                              self._stream()), 's2d_match_belief_reset')
+
+    def _need_belief(self):
+        if self.belief is None:
+            raise RuntimeError("the belief layer is off: call enable_belief() first")
+
+    def _belief_rows(self, t, name, lead, dtype=torch.float32, tail=None):
+        """a contiguous device tensor [*lead, N, k, 192] (or [*lead, N] with tail=()) of the belief's shape"""
+        tail = tuple(self.belief.shape[1:]) if tail is None else tail
+        t = torch.as_tensor(t, device=self.device)
+        want = tuple(lead) + (self.num_envs,) + tail
+        if t.dtype != dtype:
+            if dtype == torch.float32:
+                raise ValueError(f"{name} must be float32")
+            t = t.to(dtype)
+        if tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape {want}, got {tuple(t.shape)}")
+        return t
+
+    def belief_step(self, see=None, done=None):
+        """One update of the belief with one see row per agent; call it once per cycle, after vision_step.  see: float32
+        [N, k, 192] for the belief's slots, None = self.see(slots).  done: None, True (the engine's own `done` of the last step) or
+        a uint8 [N] tensor: those matches' beliefs are reset before the row is taken in.  Returns `belief` (updated in place)."""
+        self._need_belief()
+        s = self.see(self.belief_slots) if see is None else self._belief_rows(see, 'see', ())
+        d = None
+        if done is not None and done is not False:
+            d = self.done if done is True else self._belief_rows(done, 'done', (), torch.uint8, ())
+        rc = self.lib.s2d_match_belief_scan(C.byref(self.belief_params), _ptr(s), _ptr(d), _ptr(self.belief), None, 1,
+                                            self.num_envs, self.belief_mask, self._stream())
+        _capi.check(self.lib, rc, 's2d_match_belief_scan')
+        self._keep_belief = (s, d)
+        return self.belief
+
+    def belief_scan(self, see_record, reset=None, out=None):
+        """T updates in one launch over a recorded see_record float32 [T, N, k, 192] (a rollout's see record of the belief's
+        slots).  reset: uint8 [T, N] or None, a set flag = that match's beliefs are reset before row t is taken in (the record's
+        done, shifted by one row, when the rows are start-of-cycle rows).  out: float32 [T, N, k, 192] or True (allocate it) or
+        None: the belief after each row.  `belief` is updated in place to the state after the last row; returns out or belief."""
+        self._need_belief()
+        s = torch.as_tensor(see_record, device=self.device)
+        if s.dim() != 4 or s.shape[0] < 1:
+            raise ValueError(f"see_record must have shape (T, {self.num_envs}, {self.belief.shape[1]}, {M.SEE_DIM}) with T >= 1")
+        T = int(s.shape[0])
+        s = self._belief_rows(s, 'see_record', (T,))
+        r = None if reset is None else self._belief_rows(reset, 'reset', (T,), torch.uint8, ())
+        if out is True:
+            out = torch.empty_like(s)
+        elif out is not None:
+            out = self._belief_rows(out, 'out', (T,))
+        rc = self.lib.s2d_match_belief_scan(C.byref(self.belief_params), _ptr(s), _ptr(r), _ptr(self.belief), _ptr(out), T,
+                                            self.num_envs, self.belief_mask, self._stream())
+        _capi.check(self.lib, rc, 's2d_match_belief_scan')
+        self._keep_belief = (s, r)
+        return self.belief if out is None else out
+
     def world_model(self):
         """dict proto-path -> device tensor (left team's point of view = absolute coordinates)."""
         P = M.MATCH_PLAYERS
@@ -553,7 +629,15 @@ class Soccer2DMatchVecEnv:
     S2DVisionParams fields.  The row returned by reset() is not fresh (self and game words only); the first step's is.
     With opponent = a see actor (MatchQNetActor(obs='see') or a MatchSeePolicyActor) the right team plays on its own see rows and turns its necks and
     changes its view as the actor's table says; the cycle kernel then steps the vision state of all 22 players itself (the left
-    team's from the caller's TurnNeck / ChangeView words), so a step is one launch plus see.  A see actor needs obs='see'.
+    team's from the caller's TurnNeck / ChangeView words), so a step is one launch plus see.  A see actor needs obs='see' or
+    obs='belief'.
+
+    obs = 'belief': partial observability with a memory -- every controlled agent gets its belief row (MatchEngine.belief: the
+    layer of include/s2d_match.h, "Belief", over its see rows: identified players in fixed rows, positions predicted while
+    unseen, counts of how old each word is).  Actions, shapes and rewards as for 'see'.  A step is the body step, vision_step,
+    see, then belief_step with the engine's done (a restarted match forgets); with a see actor as the opponent the one launch,
+    then see, then the belief step.  `belief` = a dict of S2DBeliefParams fields.  The obs tensor is the engine's `belief`
+    buffer, updated in place; reset(mask) leaves the masked matches' rows unknown.
 
     reward = 'goals' (the default: the rewards above) | a dict by term name | six weights: the shaped per-agent reward the
     cycle kernel computes (MatchEngine.set_agent_reward; chaser_only as there) in the place of the signed team reward, [N, 22]
@@ -567,11 +651,11 @@ class Soccer2DMatchVecEnv:
         from .spaces import Box
         if not (opponent in (None, 'random', 'scripted') or _is_match_actor(opponent)):
             raise ValueError(f"opponent must be None, 'random', 'scripted' a MatchQNetActor or a MatchPolicyActor, got {opponent!r}")
-        if obs not in ('state', 'agent', 'see'):
-            raise ValueError(f"obs must be 'state', 'agent' or 'see', got {obs!r}")
+        if obs not in ('state', 'agent', 'see', 'belief'):
+            raise ValueError(f"obs must be 'state', 'agent', 'see' or 'belief', got {obs!r}")
         agents = 22 if opponent is None else 11
-        if obs == 'see':
-            return (Box(low=-1.0e6, high=1.0e6, shape=(agents, M.SEE_DIM), dtype=np.float32),
+        if obs in ('see', 'belief'):               # (a freshly reset belief row holds BELIEF_COUNT_LIMIT in its counts)
+            return (Box(low=-1.0e6, high=1.0e6 if obs == 'see' else M.BELIEF_COUNT_LIMIT, shape=(agents, M.SEE_DIM), dtype=np.float32),
                     Box(low=-180.0, high=180.0, shape=(agents, 5), dtype=np.float32))
         if obs == 'agent':
             ospace = Box(low=-1.0e6, high=1.0e6, shape=(agents, M.AGENT_OBS_DIM), dtype=np.float32)
@@ -580,27 +664,30 @@ class Soccer2DMatchVecEnv:
         return ospace, Box(low=-180.0, high=180.0, shape=(agents, 3), dtype=np.float32)
 
     def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, reward='goals', chaser_only=False,
-                 **kwargs):
+                 belief=None, **kwargs):
         self.observation_space, self.action_space = self.spaces(opponent, obs)
         shaped = not (isinstance(reward, str) and reward == 'goals')
         if shaped:
             if isinstance(reward, str):
                 raise ValueError(f"reward must be 'goals', a dict by term name or six weights, got {reward!r}")
             if obs == 'state':
-                raise ValueError("a shaped reward is per agent: it needs obs='agent' or obs='see'")
+                raise ValueError("a shaped reward is per agent: it needs obs='agent', obs='see' or obs='belief'")
             if _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'see':
                 raise ValueError("a shaped reward is not offered while a see network plays the opponent")
             M.reward_weights(reward)                     # (a bad spec fails before the engine exists)
-        if vision is not None and obs != 'see':
-            raise ValueError("vision parameters need obs='see'")
+        sees = obs in ('see', 'belief')                  # the agents act under the vision model
+        if vision is not None and not sees:
+            raise ValueError("vision parameters need obs='see' or obs='belief'")
+        if belief is not None and obs != 'belief':
+            raise ValueError("belief parameters need obs='belief'")
         self.engine = MatchEngine(num_envs, device, **kwargs)
         self.num_envs, self.device = self.engine.num_envs, self.engine.device
         self.opponent, self.obs_kind = opponent, obs
         self._ro = self.engine.alloc_rollout(1)
         self._see_opponent = _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'see'
         if self._see_opponent:
-            if obs != 'see':
-                raise ValueError("a see actor as the opponent needs obs='see'")
+            if not sees:
+                raise ValueError("a see actor as the opponent needs obs='see' or obs='belief'")
             self.engine.set_controllers({'left': 'external', 'right': 'random'})
             self.engine.enable_vision(**(vision or {}))
             self.engine.set_network(opponent, 'right')
@@ -613,16 +700,18 @@ class Soccer2DMatchVecEnv:
         if opponent is not None:
             # the caller's half of the action rows; the right team's rows are never read
             self._act = torch.zeros((1, self.num_envs, M.MATCH_PLAYERS, 3), dtype=torch.float32, device=self.device)
-        if obs == 'see':
+        if sees:
             if not self._see_opponent:
                 self.engine.enable_vision(**(vision or {}))
             # the view half of the action rows; an in-kernel opponent's players never turn their necks or change their view
             self._view = torch.zeros((self.num_envs, M.MATCH_PLAYERS, 2), dtype=torch.float32, device=self.device)
-        if obs in ('agent', 'see'):
+        if obs in ('agent', 'see', 'belief'):
             self._slots = 'all' if opponent is None else 'left'
             self._aobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
             # reward sign per agent: the left team's reward for slots 0..10, its negative for 11..21
             self._rsign = torch.tensor([1.0] * 11 + ([-1.0] * 11 if opponent is None else []), dtype=torch.float32, device=self.device)
+        if obs == 'belief':                              # _aobs takes the see rows, the layer's input; the obs is engine.belief
+            self.engine.enable_belief(self._slots, **(belief or {}))
         self._shaped = shaped
         if shaped:
             self.engine.set_agent_reward(reward, chaser_only)
@@ -633,6 +722,8 @@ class Soccer2DMatchVecEnv:
             return e.agent_observations(self._slots, out=self._aobs)
         if self.obs_kind == 'see':
             return e.see(self._slots, out=self._aobs)
+        if self.obs_kind == 'belief':
+            return e.belief
         return torch.stack([e.x[:, :23], e.y[:, :23], e.vx[:, :23], e.vy[:, :23], e.body[:, :23]], dim=2)
 
     def reset(self, mask=None):
@@ -642,7 +733,7 @@ class Soccer2DMatchVecEnv:
     def _step_see(self, actions):
         agents = 22 if self.opponent is None else 11
         if actions is None:
-            raise ValueError(f"with obs='see', step() needs actions [N, {agents}, 5]")
+            raise ValueError(f"with obs={self.obs_kind!r}, step() needs actions [N, {agents}, 5]")
         a = torch.as_tensor(actions, device=self.device).to(torch.float32)
         if tuple(a.shape) != (self.num_envs, agents, 5):
             raise ValueError(f"actions must have shape ({self.num_envs}, {agents}, 5), got {tuple(a.shape)}")
@@ -650,7 +741,7 @@ class Soccer2DMatchVecEnv:
         return a[..., :3].contiguous()
 
     def step(self, actions=None):
-        if self.obs_kind == 'see':
+        if self.obs_kind in ('see', 'belief'):
             actions = self._step_see(actions)
         if self.opponent is None:
             a = None if actions is None else torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(1, self.num_envs, 22, 3)
@@ -669,11 +760,13 @@ class Soccer2DMatchVecEnv:
         e = self.engine
         info = {'game_mode_type': e.mode, 'game_mode_side': e.mode_side, 'left_team_score': e.score_left,
                 'right_team_score': e.score_right, 'cycle': e.cycle, 'nearest_left': e.nearest_left, 'nearest_right': e.nearest_right}
-        if self.obs_kind == 'see' and not self._see_opponent:
+        if self.obs_kind in ('see', 'belief') and not self._see_opponent:
             e.vision_step(self._view, done=True)
+        if self.obs_kind == 'belief':                     # this cycle's see rows into the memory; a restarted match forgets
+            e.belief_step(e.see(self._slots, out=self._aobs), done=True)
         if self._shaped:                                  # the cycle kernel's per-agent reward, the controlled agents' columns
             return self._obs(), self._ro['agent_reward'][0, :, :self._rsign.numel()], e.done, info
-        if self.obs_kind in ('agent', 'see'):
+        if self.obs_kind in ('agent', 'see', 'belief'):
             return self._obs(), e.reward_left[:, None] * self._rsign, e.done, info
         return self._ro['obs'][0, :, :23], e.reward_left, e.done, info
 

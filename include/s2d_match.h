@@ -712,6 +712,102 @@ int s2d_match_rollout_see_policy(S2DMatchHandle h, int n_steps, const float *act
                                  const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev,
                                  float *logp_out_dev, uint32_t obs_mask, float *see_out_dev, void *stream);
 
+/* Belief: each agent's memory of what it has seen -- an opt-in layer beside the vision layer, the counterpart of the world model
+ * every real client keeps over its see messages (idl/service.proto:71-83, 146-168: seen_position, pos_count, vel_count,
+ * body_direction_count, ghost_count).  It reads NOTHING but see rows: no engine handle, no state plane -- it cannot leak ground
+ * truth.  The fp32 words below are the contract (the device, csrc/s2d_belief.hip, equals tests/belief_ref.c bit for bit).
+ * Deviations: this is the project's own filter and claims NO PARITY TO LIBRCSC (its WorldModel localises, matches and forgets by
+ * other rules); players beyond identification range enter the belief only once they have been identified (a level 1-3 sighting
+ * can move a known entry, it never creates one); the ball has no vel_count word (its eight words are full: its velocity is as old
+ * as the last level-4 ball sighting, which the row does not say); self-localisation is the see row's (exact).
+ *
+ * A belief row is S2D_BELIEF_DIM float32 words per agent, in the agent's own-team frame (the see row's frame).  The row is both the
+ * memory and the observation: belief' = f(belief, see row, parameters), there is no hidden state.  It is as wide as a see row, so
+ * every 192-input network, learner and target of the see path takes it unchanged.
+ *   self [0, 16)      the see row's self words, copied
+ *   ball [16, 24)     x, y, vx, vy, pos_count | game_mode_type, mode side, cycle (the see row's three game words, copied)
+ *   players [24, 192) 21 rows of 8 words in FIXED IDENTITY ORDER: with u = the agent's own index (raw slot % 11), row j < 10 is the
+ *                     teammate with own index (j < u ? j : j + 1), row j >= 10 the opponent with unum j - 9.
+ *                     Words: x, y, vx, vy, body, pos_count, vel_count, body_count.
+ * The 22 ENTRIES are the ball and the 21 player rows.  Positions and velocities are absolute, in the own frame.  A count is the
+ * number of updates since the word group was last seen: a whole number stored as a float, saturating at count_max.  An UNKNOWN
+ * entry is all +0 with every count equal to count_max; an entry is KNOWN while pos_count < count_max.
+ *
+ * Parameters (doubles, each rounded to fp32 once, as S2DVisionParams):
+ *   ball_decay 0.94, player_decay 0.4   ServerParam's; one player_decay for everybody (PlayerTypes are not visible)
+ *   view_angle[3] 60 / 120 / 180        the vision parameters' (narrow, normal, wide)
+ *   match_dist 3.0, match_rate 0.1      a level 1-3 sighting matches an entry within tol = match_dist + match_rate * dist
+ *   ghost_margin 5.0                    degrees kept clear of the cone's edge when an unseen entry is forgotten
+ *   count_max 1000                      a whole number in [1, 16777216]
+ * match_dist, match_rate and ghost_margin are this project's own choice and are measured against nothing.
+ *
+ * One update of agent p's row B with its see row S (S2D_SEE_* words), in this order; "entry := unknown" writes the +0 words and
+ * count_max into every count:
+ *   1. Reset.  If the reset flag of p's match is set: every entry := unknown.
+ *   2. Predict.  For every entry with pos_count < count_max:  x = x + vx; y = y + vy;  then vx = vx * decay; vy = vy * decay
+ *      (ball_decay for the ball, player_decay for a player).  Then for EVERY entry each count c becomes
+ *      (c + 1 < count_max ? c + 1 : count_max) -- a count above count_max, or NaN, becomes count_max -- and an entry whose pos_count
+ *      is now count_max := unknown (a belief too old to keep is forgotten, so that every unknown entry is the canonical one).
+ *   3. Copy.  B[0, 16) = S[0, 16); B[21, 24) = S[21, 24).
+ *   4. Correct, only if S[self.fresh] == 1 and S[self.card] < S2D_CARD_RED.  With face, (sx, sy), (svx, svy) the self words of S, a
+ *      SIGHTING (level, dist, dir, dist_chg, dir_chg) with level >= 1 gives
+ *        th = norm_deg_any(face + dir);  (s, c) = sincos_deg(th);  X = fmaf(dist, c, sx);  Y = fmaf(dist, s, sy)
+ *        level 4, dist != 0:  vr = dist_chg;  vt = (dir_chg * 0.017453292519943295f) * dist;
+ *                             VX = fmaf(vr, c, -(vt * s)) + svx;  VY = fmaf(vr, s, vt * c) + svy
+ *        level 4, dist == 0:  VX = svx;  VY = svy
+ *      Ball (its five see words): level >= 1 sets x = X, y = Y, pos_count = 0 and marks it updated; level 4 also vx = VX, vy = VY.
+ *      Players, first pass: the see rows of level 4, in row order.  The identity names the entry: team > 0 and unum n in 1..11,
+ *        n - 1 != u: row j = (n - 1 < u ? n - 1 : n - 2);  team < 0 and n in 1..11: row j = n + 9;  any other identity (team 0, a
+ *        unum outside 1..11 or not whole, the agent itself) is dropped.  Set x, y, vx, vy = X, Y, VX, VY and body =
+ *        norm_deg_any(body_rel + face); all three counts = 0; mark the entry updated.  (Two rows naming one entry: the later wins.)
+ *      Players, second pass: the see rows of level 1, 2 or 3, in row order, one after the other.  Candidates are the player rows
+ *        compatible with the team word (> 0: rows 0..9; < 0: rows 10..20; otherwise all 21) that are not marked updated and have
+ *        pos_count < count_max.  tol = fmaf(match_rate, dist, match_dist); of the candidates with q = sq2(X - x, Y - y) <= tol * tol
+ *        the one with the smallest q is taken, ties to the lowest row: x = X, y = Y, pos_count = 0, marked updated; velocity, body
+ *        and their counts stay.  Without such a candidate the sighting is dropped.
+ *   5. Ghosts, under the condition of step 4.  wi = the view width of S (code 1 -> 0, 3 -> 2, anything else 1);
+ *      cone = 0.5f * view_angle[wi] - ghost_margin.  An entry (the ball included) that is not marked updated and has pos_count <
+ *      count_max := unknown when, with dx = x - sx, dy = y - sy, d = hypot2(dx, dy):
+ *        d > 0  and  fabsf(norm_deg_any(atan2_deg(dy, dx) - face)) <= cone.
+ *      The see model reports everything inside the cone, so the object is not where the belief put it.
+ * The marks live for one update only. */
+#define S2D_BELIEF_DIM 192         /* float32 words per agent: a see row's width */
+#define S2D_BELIEF_SELF 0
+#define S2D_BELIEF_BALL 16
+#define S2D_BELIEF_PLAYERS 24
+#define S2D_BELIEF_ROW_WORDS 8     /* words of one player row */
+#define S2D_BELIEF_COUNT_LIMIT 16777216.0f   /* 2^24: the largest count_max (every smaller whole number is an exact float) */
+typedef struct S2DBeliefParams {
+  double ball_decay, player_decay;
+  double view_angle[3];
+  double match_dist, match_rate, ghost_margin;
+  double count_max;
+} S2DBeliefParams;
+void s2d_match_belief_default_params(S2DBeliefParams *prm);
+/* Errors: non-finite values; a decay outside (0, 1]; view angles outside (0, 360]; match_dist, match_rate or ghost_margin < 0;
+ * count_max < 1, above S2D_BELIEF_COUNT_LIMIT or not whole. */
+int s2d_match_belief_validate(const S2DBeliefParams *prm);
+/* Engine-free, on the current device, as s2d_gae: raw device pointers, any stream of that device; no atomics, no host reads,
+ * capturable.  k = popcount(slot_mask); the rows of a match are those of the mask's slots in ascending order, as s2d_match_see
+ * writes them (the slot gives u).  All row buffers 16-byte aligned.
+ *
+ * s2d_match_belief_reset: every row of the masked matches (mask_dev uint8[N], NULL = all) becomes +0 in every word but the
+ * counts, which become S2D_BELIEF_COUNT_LIMIT: the call takes no parameters, so it writes the one value that is not below any
+ * count_max.  Such a row is unknown in every entry for any parameters (pos_count >= count_max), and step 2 of the first update
+ * stores count_max in its place.
+ * Errors: a NULL or unaligned belief_dev; n_matches < 1 (or above 2^24); a mask that is empty or has bits above 21. */
+int s2d_match_belief_reset(float *belief_dev, int64_t n_matches, uint32_t slot_mask, const uint8_t *mask_dev, void *stream);
+/* s2d_match_belief_scan: T = n_steps updates in one launch.
+ *   see_dev     float[T][N][k][S2D_SEE_DIM]
+ *   reset_dev   uint8[T][N] or NULL: a set flag = step 1 of that match's agents before row t is taken in
+ *   belief_dev  float[N][k][S2D_BELIEF_DIM], updated in place to the state after row T - 1
+ *   out_dev     float[T][N][k][S2D_BELIEF_DIM] or NULL: the belief after each row
+ * n_steps = 1 is the per-cycle step.  Errors (S2D_EINVAL, before any HIP call): NULL prm, see_dev or belief_dev; a mask that is
+ * empty or has bits above 21; see_dev, belief_dev or out_dev not 16-byte aligned; parameters s2d_match_belief_validate rejects;
+ * n_steps < 1 or n_matches < 1 (or above 2^24); out_dev overlapping belief_dev or see_dev (or belief_dev overlapping see_dev). */
+int s2d_match_belief_scan(const S2DBeliefParams *prm, const float *see_dev, const uint8_t *reset_dev, float *belief_dev,
+                          float *out_dev, int n_steps, int64_t n_matches, uint32_t slot_mask, void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
