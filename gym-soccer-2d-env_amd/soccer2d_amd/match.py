@@ -547,8 +547,9 @@ class MatchEngine:
 
     def belief_scan(self, see_record, reset=None, out=None):
         """T updates in one launch over a recorded see_record float32 [T, N, k, 192] (a rollout's see record of the belief's
-        slots).  reset: uint8 [T, N] or None, a set flag = that match's beliefs are reset before row t is taken in (the record's
-        done, shifted by one row, when the rows are start-of-cycle rows).  out: float32 [T, N, k, 192] or True (allocate it) or
+        slots).  reset: uint8 [T, N] or None, a set flag = that match's beliefs are reset before row t is taken in.  A rollout's see
+        rows are start-of-cycle rows, so there it is the record's done shifted by one row: reset[0] = 0, reset[t] = done[t - 1];
+        for see_record[1:] it is done[:T - 1] as it stands.  out: float32 [T, N, k, 192] or True (allocate it) or
         None: the belief after each row.  `belief` is updated in place to the state after the last row; returns out or belief."""
         self._need_belief()
         s = torch.as_tensor(see_record, device=self.device)

@@ -1,6 +1,7 @@
 """The belief layer on the GPU (s2d_match_belief_scan, s2d_match_belief_reset; include/s2d_match.h, "Belief"): bit-exact to the host
 restatement (tests/belief_ref.c) fed the same see rows -- in a closed loop with the engine under every kind of slot mask, as a scan
-against single steps, replayed from a captured graph -- and Soccer2DMatchVecEnv(obs='belief')."""
+against single steps, replayed from a captured graph, scanned over a fused rollout's see record against the per-cycle steps -- and
+Soccer2DMatchVecEnv(obs='belief')."""
 import numpy as np
 import pytest
 
@@ -249,3 +250,43 @@ def test_surface_errors():
     with pytest.raises(ValueError):
         eng.enable_belief(count_max=0)
     eng.close()
+
+
+@pytest.mark.parametrize('slots', ['all', 'left'])
+def test_record_path_equals_the_per_cycle_path(slots):
+    """INTEGRATION.md section 5i's learner path: the beliefs scanned over a fused rollout's see record equal, bit for bit, the ones
+    belief_step builds cycle by cycle (what Soccer2DMatchVecEnv(obs='belief') shows a policy).  out['see'][t] is the START-of-cycle
+    row of cycle t and out['done'][t] the done of cycle t, so the row AFTER cycle t is out['see'][t + 1] and its reset flag is
+    out['done'][t]."""
+    n, T = 9, 24
+    g = torch.Generator(device='cuda:0').manual_seed(12)
+    view = torch.stack([_view_actions(g, n) for _ in range(T + 1)])
+    a, online, b = (_engine(n, slots, seed=7) for _ in range(3))
+    # A: per cycle.  `online` also takes in the row it sees before its first action, as an agent acting from its belief does
+    held = [online.belief_step().clone()]
+    beliefs, rows = [], []
+    for t in range(T):
+        for eng in (a, online):
+            eng.step(None)
+            eng.vision_step(view[t], done=True)
+        rows.append(a.see(slots).clone())
+        beliefs.append(a.belief_step(rows[-1], done=True).clone())
+        held.append(online.belief_step(done=True).clone())
+    # B: one fused rollout, then one scan
+    out = b.rollout(T + 1, with_obs=False, see_obs=slots, view_actions=view)
+    see, done = out['see'], out['done']
+    assert done[:T].any() and not done[:T].all()           # matches restarted inside the record
+    for t in range(T):
+        assert torch.equal(see[t + 1].view(torch.int32), rows[t].view(torch.int32)), f'see row after cycle {t}'
+    got = b.belief_scan(see[1:], reset=done[:T], out=True)
+    assert torch.equal(got.view(torch.int32), torch.stack(beliefs).view(torch.int32))
+    assert torch.equal(b.belief.view(torch.int32), a.belief.view(torch.int32))
+    # the learner's form: from row 0, flags shifted by one row -> the belief an online agent holds when it chooses action t
+    b.reset()
+    flags = torch.cat([torch.zeros_like(done[:1]), done[:T]])
+    got = b.belief_scan(see, reset=flags, out=True)
+    assert tuple(got.shape) == (T + 1, n, B.popcount(M.agent_slot_mask(slots)), 192)
+    assert torch.equal(got.view(torch.int32), torch.stack(held).view(torch.int32))
+    assert (got[..., 29::8] < 1000).any() and (got[1:][done[:T].bool()][..., 29::8] == 1000).any()
+    for eng in (a, online, b):
+        eng.close()
