@@ -553,6 +553,10 @@ template <class D> static void m_net_pass(D& d, const S2DMatchNet& net, int in_d
 // the fields the see network shares with the agent-row ones
 static S2DMatchNet m_see_as_net(const S2DMatchSeeNet& s) { return S2DMatchNet{s.h1, s.h2, s.n_actions, s.slot_mask, s.params, s.epsilon, s.table}; }
 
+static bool m_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
 // actions_out != NULL without a table records today's controllers: every slot the caller's row, or every slot random (actions NULL).
 // With a network set, or a row record asked for (obs_mask), the NET instantiation runs (after the pack kernel, when there is a network).
 // With a see network set the SEE instantiation runs (agent_obs_out is then the see record, view_actions the other slots' view actions).
@@ -560,22 +564,36 @@ static S2DMatchNet m_see_as_net(const S2DMatchSeeNet& s) { return S2DMatchNet{s.
 // lives in s2d_match_reward.hip -- the controller one (without a table: every slot the caller's row, or random) unless the launch
 // is a network or policy one.
 // With a see policy set the SEEPOL instantiation runs, which lives in s2d_match_see_policy.hip (logp_out: its record, or NULL).
+// With a belief network set the BEL instantiation runs, which lives in s2d_match_belief_net.hip (belief_out: its row record, or
+// NULL; obs_mask names the slots of both row records).
 static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S2DMatchRollout* out, void* stream,
                     float* actions_out = nullptr, int32_t* net_index_out = nullptr, uint32_t obs_mask = 0u,
                     float* agent_obs_out = nullptr, const float* view_actions = nullptr, float* logp_out = nullptr,
-                    float* agent_reward_out = nullptr) {
+                    float* agent_reward_out = nullptr, float* belief_out = nullptr) {
   MRoll ro{nullptr, nullptr, nullptr, nullptr};
   if (out) ro = MRoll{out->obs, out->reward, out->mode, out->done};
   const hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr uint32_t kAll = (1u << NP) - 1u;
   const MRole* const role = h->role;
   const uint32_t net_mask = h->has_see ? h->see.slot_mask : role[0].net.slot_mask | role[1].net.slot_mask;
-  if (!agent_obs_out) obs_mask = 0u;
+  if (!agent_obs_out && !belief_out) obs_mask = 0u;
   if (h->has_ctl && !actions && ((h->ctl_random | h->ctl_script | net_mask) & kAll) != kAll)
     return mfail(S2D_EINVAL, "the controller table has external slots (S2D_CTL_EXTERNAL) but actions_dev is NULL");
   const MCtl ctl = h->has_ctl ? MCtl{h->ctl_random, h->ctl_script, actions_out} : MCtl{actions ? 0u : kAll, 0u, actions_out};
   const MCtlRw crw{ctl, MRw{h->rw.w, agent_reward_out, h->rw.chaser_only}};
   if (h->has_see) {
+    if (h->has_bel) {                                      // refused before anything is launched, whichever entry point came here
+      if ((net_mask | obs_mask) & ~h->bel_mask)            // (the kernel addresses a slot's row by its rank in belief_mask)
+        return mfail(S2D_EINVAL, "a belief network is set: obs_mask must lie inside its belief_mask");
+      // no record may lie over the state the kernel updates every cycle
+      const size_t N = (size_t)h->n, T = (size_t)n_steps, k = (size_t)__builtin_popcount(obs_mask);
+      const size_t state = N * (size_t)__builtin_popcount(h->bel_mask) * S2D_BELIEF_DIM * sizeof(float);
+      const size_t rows = T * N * k * S2D_BELIEF_DIM * sizeof(float), slots = T * N * NP * sizeof(float);
+      if (m_overlap(h->bel_rows, state, agent_obs_out, rows) || m_overlap(h->bel_rows, state, belief_out, rows) ||
+          m_overlap(agent_obs_out, rows, belief_out, rows) || m_overlap(h->bel_rows, state, actions_out, 3 * slots) ||
+          m_overlap(h->bel_rows, state, net_index_out, slots) || m_overlap(h->bel_rows, state, logp_out, slots))
+        return mfail(S2D_EINVAL, "a record overlaps the belief state buffer (or see_out overlaps belief_out)");
+    }
     MSeeArg sa;
     std::memset(&sa, 0, sizeof sa);
     MSee& nt = sa.net;
@@ -588,6 +606,15 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
       MDeviceGuard guard(h->device);
       m_net_pass(nt, m_see_as_net(h->see), S2D_SEE_DIM, h->net_frags, st);
       MHIP_TRY(hipGetLastError());
+    }
+    if (h->has_bel) {                                      // the BEL instantiation: the same MSeeArg, the policy words, the belief words
+      MBelArg ba;
+      std::memset(&ba, 0, sizeof ba);
+      ba.net = sa.net; ba.sp = sa.sp; ba.vis = sa.vis;
+      ba.act = h->see_act; ba.det = h->see_det; ba.logp = logp_out;
+      ba.head = h->bel_head; ba.bp = s2d_belief::belief_params(h->bel_prm);
+      ba.belief = h->bel_rows; ba.belief_mask = h->bel_mask; ba.belief_out = belief_out; ba.done0 = h->buf.done;
+      return s2d_match_internal_belief_net_launch(h, n_steps, actions, ro, st, ctl, ba);
     }
     if (h->see_pol) {                                      // the SEEPOL instantiation: the same MSeeArg plus the policy words
       MSeePolArg pa;
@@ -646,9 +673,9 @@ static int m_launch(S2DMatchHandle h, int n_steps, const float* actions, const S
 // "s2d_match_rollout_kernel<" variant [", " slot kind] [", agent reward"] ">"
 S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   if (!h) return "";
-  constexpr int kKinds = 8;
+  constexpr int kKinds = 9;
   static const char* const kind_text[kKinds] = {"", ", controllers", ", network", ", two networks", ", policy network",
-                                                ", two networks, policy", ", see network", ", see policy network"};
+                                                ", two networks, policy", ", see network", ", see policy network", ", belief network"};
   static const std::array<std::string, 2 * 5 * kKinds> names = [] {
     std::array<std::string, 2 * 5 * kKinds> t;
     for (int v = 0; v < 5; ++v)
@@ -661,7 +688,7 @@ S2D_API const char* s2d_match_kernel_name(S2DMatchHandle h) {
   }();
   const int nets = h->role[0].set + h->role[1].set;
   const bool pol = h->role[0].pol || h->role[1].pol;
-  const int kind = h->has_see ? (h->see_pol ? 7 : 6) : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
+  const int kind = h->has_see ? (h->has_bel ? 8 : h->see_pol ? 7 : 6) : nets == 2 ? (pol ? 5 : 3) : nets == 1 ? (pol ? 4 : 2) : h->has_ctl ? 1 : 0;
   return names[((h->has_rw ? 5 : 0) + m_variant(h)) * kKinds + kind].c_str();
 }
 S2D_API int s2d_match_relative(S2DMatchHandle h, float* dist_dev, float* angle_dev, void* stream) {
@@ -769,7 +796,10 @@ static int m_slot_admit(S2DMatchHandle h, int slot) {
   return S2D_OK;
 }
 static void m_slot_clear(S2DMatchHandle h, int slot) {   // a slot without a network, whatever kind it held
-  if (slot == kSlotSee) { h->has_see = false; h->see = S2DMatchSeeNet{}; h->see_pol = false; h->see_act = 0; h->see_det = nullptr; }
+  if (slot == kSlotSee) {
+    h->has_see = false; h->see = S2DMatchSeeNet{}; h->see_pol = false; h->see_act = 0; h->see_det = nullptr;
+    h->has_bel = false; h->bel_head = 0; h->bel_prm = S2DBeliefParams{}; h->bel_rows = nullptr; h->bel_mask = 0u;
+  }
   else h->role[slot] = MRole{};
 }
 static void m_slot_displace(S2DMatchHandle h, int slot) {
@@ -822,6 +852,7 @@ static int m_see_set(S2DMatchHandle h, const S2DMatchSeeNet* net, const std::str
   if (int rc = s2d_match_vision_validate(&net->prm); rc != S2D_OK) return rc;
   if (net->slot_mask != 0u)
     if (int rc = m_net_frags_alloc(h); rc != S2D_OK) return rc;
+  m_slot_clear(h, kSlotSee);                            // (a belief network's words go with whatever the slot held)
   h->see = *net; h->has_see = true;
   h->see_pol = pol; h->see_act = pol ? act : 0; h->see_det = pol ? det : nullptr;
   m_slot_displace(h, kSlotSee);
@@ -838,6 +869,48 @@ S2D_API int s2d_match_set_see_policy_network(S2DMatchHandle h, const S2DMatchSee
   // a see policy keeps its words in the same S2DMatchSeeNet, epsilon NULL
   const S2DMatchSeeNet as_see{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, nullptr, net->table, net->prm, net->vis};
   return m_see_set(h, &as_see, "see policy network", net->deterministic, "deterministic", true, net->activation, net->deterministic);
+}
+// The belief network: the see slot's words through m_see_set (every check of the see policy's setter, with the head's own device
+// word), then the belief words.  All checks come first: a refusal leaves the engine as it was.
+S2D_API int s2d_match_set_belief_network(S2DMatchHandle h, const S2DMatchBeliefNet* net) {
+  if (!h) return mfail(S2D_EINVAL, "NULL handle");
+  if (!net) { m_slot_clear(h, kSlotSee); return S2D_OK; }
+  const std::string what = "belief network";
+  if (net->head != 0 && net->head != 1) return mfail(S2D_EINVAL, what + " head must be 0 (epsilon-greedy Q-network) or 1 (categorical policy)");
+  if (net->head == 0 && net->activation != 0) return mfail(S2D_EINVAL, what + " head 0 (the Q-network) takes activation 0 (relu) only");
+  if (!net->belief || (reinterpret_cast<uintptr_t>(net->belief) & 15u))
+    return mfail(S2D_EINVAL, what + " belief must be a non-NULL, 16-byte aligned device pointer");
+  if (net->belief_mask == 0u || (net->belief_mask >> NP) != 0u)
+    return mfail(S2D_EINVAL, what + " belief_mask must be a non-empty set of bits 0..21");
+  if ((net->slot_mask >> NP) == 0u && (net->slot_mask & ~net->belief_mask))
+    return mfail(S2D_EINVAL, what + " slot_mask must lie inside belief_mask (a slot's row is its rank in belief_mask)");
+  if (int rc = s2d_match_belief_validate(&net->belief_prm); rc != S2D_OK) return rc;
+  const void* const word = net->head ? static_cast<const void*>(net->deterministic) : static_cast<const void*>(net->epsilon);
+  const S2DMatchSeeNet as_see{net->h1, net->h2, net->n_actions, net->slot_mask, net->params, net->head ? nullptr : net->epsilon,
+                              net->table, net->prm, net->vis};
+  if (int rc = m_see_set(h, &as_see, what, word, net->head ? "deterministic" : "epsilon", true, net->activation,
+                         net->head ? net->deterministic : nullptr);
+      rc != S2D_OK)
+    return rc;
+  h->see_pol = false;                                    // (the see slot holds a belief network: its launches are the BEL kernels')
+  h->has_bel = true; h->bel_head = net->head; h->bel_prm = net->belief_prm; h->bel_rows = net->belief; h->bel_mask = net->belief_mask;
+  return S2D_OK;
+}
+S2D_API int s2d_match_rollout_belief(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
+                                     const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev,
+                                     float* logp_out_dev, uint32_t obs_mask, float* see_out_dev, float* belief_out_dev, void* stream) {
+  if (h && !h->has_bel) return mfail(S2D_EINVAL, "s2d_match_rollout_belief needs a belief network (s2d_match_set_belief_network)");
+  if (reinterpret_cast<uintptr_t>(belief_out_dev) & 15u) return mfail(S2D_EINVAL, "belief_out must be 16-byte aligned");
+  int rc;
+  const bool go = m_rollout_args(&rc, h, n_steps, out, {{actions_out_dev, "actions_out", "float"}, {view_actions_dev, "view_actions", "float"},
+                                                        {net_index_out_dev, "net_index_out", "int32"}, {logp_out_dev, "logp_out", "float"}},
+                                 see_out_dev ? see_out_dev : belief_out_dev, see_out_dev ? "see_out" : "belief_out", obs_mask);
+  if (rc != S2D_OK) return rc;
+  if ((see_out_dev || belief_out_dev) && (obs_mask & ~h->bel_mask))
+    return mfail(S2D_EINVAL, "obs_mask must lie inside the belief network's belief_mask");
+  if (!go) return rc;
+  return m_launch(h, n_steps, actions_dev, out, stream, actions_out_dev, net_index_out_dev, obs_mask, see_out_dev, view_actions_dev,
+                  logp_out_dev, nullptr, belief_out_dev);
 }
 S2D_API int s2d_match_rollout_see(S2DMatchHandle h, int n_steps, const float* actions_dev, const float* view_actions_dev,
                                   const S2DMatchRollout* out, float* actions_out_dev, int32_t* net_index_out_dev, uint32_t obs_mask,

@@ -1,7 +1,7 @@
 // s2d_match_cycle.h -- 11v11: the cycle kernel.
 //
 // Holds: MRoll, MShared, match_rollout_body, the argument pickers and the template s2d_match_rollout_kernel, whose instantiations
-// the three match units divide among themselves (s2d_match.hip, s2d_match_reward.hip, s2d_match_see_policy.hip).
+// the match units divide among themselves (s2d_match.hip, s2d_match_reward.hip, s2d_match_see_policy.hip, s2d_match_belief_net.hip).
 // Included by s2d_match_host.h (and through it by those units).
 #pragma once
 #include "s2d_match_slots.h"
@@ -23,10 +23,12 @@ template <bool CTL, bool NET = false, bool RW = false, class P, class TY, class 
 S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, const MPtrs& q, int64_t n, int n_steps,
                                 const float* __restrict__ actions, const MRoll& ro, const MCtl& ctl, const NA* nin = nullptr,
                                 const MRw& rw = MRw{nullptr, nullptr, 0}) {
-  static_assert(!RW || (CTL && !(NET && (std::is_same<NA, MSeeArg>::value || std::is_same<NA, MSeePolArg>::value))),
+  static_assert(!RW || (CTL && !(NET && (std::is_same<NA, MSeeArg>::value || std::is_same<NA, MSeePolArg>::value ||
+                                         std::is_same<NA, MBelArg>::value))),
                 "the agent reward: the CTL family, not the see network");
   constexpr bool SEEPOL = NET && std::is_same<NA, MSeePolArg>::value;   // see policy slots: SEE with the policy's head and record
-  constexpr bool SEE = NET && (std::is_same<NA, MSeeArg>::value || SEEPOL);
+  constexpr bool BEL = NET && std::is_same<NA, MBelArg>::value;   // belief network: SEE on belief rows, either head, the policy's record
+  constexpr bool SEE = NET && (std::is_same<NA, MSeeArg>::value || SEEPOL || BEL);
   constexpr bool POL = NET && std::is_same<NA, MPolArg>::value;   // policy slots: an instantiation of its own (the NET ones keep their code)
   const int l = threadIdx.x & (kHalf - 1), l_launch = l;
   const int half = (threadIdx.x >> 5) & 1, half_launch = half;
@@ -91,6 +93,10 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       net_slots |= nin->net.opp.mask;
       if ((nin->net.opp.mask >> l) & 1u) { net_thr = thr2; net_k = (uint32_t)nin->net.opp.na; net_tab = nin->net.opp.table; }
     }
+  } else if constexpr (BEL) {                              // (the launch's head reads its own word; the other's pointer is NULL)
+    if (nin->head != 0) pol_det = *nin->det != 0u ? 1u : 0u;
+    else net_thr = explore_threshold(*nin->net.epsilon);
+    net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
   } else if constexpr (SEEPOL) {                           // (no epsilon: its pointer is NULL)
     pol_det = *nin->det != 0u ? 1u : 0u;
     net_slots = nin->net.net_mask; net_k = (uint32_t)nin->net.na; net_tab = nin->net.table;
@@ -105,6 +111,8 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       }
     }
   }
+  [[maybe_unused]] bool bel_reset = false;                 // BEL: the match's done of the cycle before (first cycle: the engine's plane)
+  if constexpr (BEL) bel_reset = nin->done0[ec] != 0;
   [[maybe_unused]] MRwView rw_view{0.0f, 0.0f, 0.0f, 0.0f};      // RW: this lane's words of the current state
   [[maybe_unused]] float rw_w[S2D_MATCH_REWARD_TERMS] = {};
   if constexpr (RW) {
@@ -143,7 +151,12 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
       if constexpr (NET) {
         int greedy;
         [[maybe_unused]] float lp = 0.0f;
-        if constexpr (SEEPOL) {
+        if constexpr (BEL) {
+          const MPick pick = m_see_greedy(p, *nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec, pol_det != 0u,
+                                          ec, bel_reset);
+          greedy = pick.idx; lp = pick.logp;
+        }
+        else if constexpr (SEEPOL) {
           const MPick pick = m_see_greedy(p, *nin, o, g, vneck, vwidth, vwait, l, half, valid, gid, (int64_t)t * n + ec, pol_det != 0u);
           greedy = pick.idx; lp = pick.logp;
         }
@@ -158,6 +171,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
           if constexpr (POL)
             pol_lane = (nin->pol.kind[0] && ((nin->net.net_mask >> l) & 1u)) || (nin->pol.kind[1] && ((nin->net.opp.mask >> l) & 1u));
           if constexpr (SEEPOL) pol_lane = true;           // (every network slot is the policy's)
+          if constexpr (BEL) pol_lane = nin->head != 0;    // (... or the Q-network's: the draw below)
           if (pol_lane) {
             nidx = greedy;
           } else {
@@ -169,7 +183,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
           // (wave-uniform pointer; 0.0f for every slot that is not on a policy)
           if (nin->pol.logp && valid && l < NP) nin->pol.logp[((int64_t)t * n + e) * NP + l] = lp;
         }
-        if constexpr (SEEPOL) {
+        if constexpr (SEEPOL || BEL) {
           if (nin->logp && valid && l < NP) nin->logp[((int64_t)t * n + e) * NP + l] = lp;
         }
         if (nin->net.net_index && valid && l < NP) nin->net.net_index[((int64_t)t * n + e) * NP + l] = nidx;
@@ -218,6 +232,7 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
     if constexpr (SEE) {                                   // the vision step: this cycle's done, the card after the body cycle
       if (l < NP) s2d_see::vision_advance(nin->sp, vneck, vwidth, vwait, g.done != 0, o.card >= S2D_CARD_RED, view_act, view_m, view_c);
     }
+    if constexpr (BEL) bel_reset = g.done != 0;            // a finished match's rows are forgotten at the next row
     if (ro.obs) {                                          // wave-uniform
       if (l < SLOTS) { obs_slot[0] = o.x; obs_slot[1] = o.y; obs_slot[2] = o.vx; obs_slot[3] = o.vy; obs_slot[4] = o.body; }
       wave_fence();
@@ -270,6 +285,8 @@ S2D_DEV void match_rollout_body(const P& p, const TY& pt, const MShared& sh, con
 // takes one only when a role holds a policy network, so the NET kernels and their LDS plan are what they were.
 // SEEPOL: the SEE instantiations whose second extra argument is an MSeePolArg -- see policy slots, a family of its own as well,
 // instantiated in a translation unit of its own (s2d_match_see_policy.hip): the SEE kernels are what they were.
+// BEL: the SEE instantiations whose second extra argument is an MBelArg -- the belief network, a family of its own too,
+// instantiated in a translation unit of its own (s2d_match_belief_net.hip): the SEE and SEEPOL kernels are what they were.
 // RW: the CTL / NET / POL instantiations whose first extra argument is an MCtlRw -- the agent reward record, likewise a family of
 // its own, instantiated in a translation unit of its own (s2d_match_reward.hip): this unit's kernels are what they were.
 S2D_DEV MCtl m_ctl_arg() { return MCtl{0u, 0u, nullptr}; }
@@ -278,6 +295,7 @@ S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MNetArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeeArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MPolArg&) { return c; }
 S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MSeePolArg&) { return c; }
+S2D_DEV MCtl m_ctl_arg(const MCtl& c, const MBelArg&) { return c; }
 template <class... A> S2D_DEV MCtl m_ctl_arg(const MCtlRw& c, const A&...) { return c.ctl; }
 S2D_DEV const MNetArg* m_net_arg() { return nullptr; }
 S2D_DEV const MNetArg* m_net_arg(const MCtl&) { return nullptr; }
@@ -285,6 +303,7 @@ S2D_DEV const MNetArg* m_net_arg(const MCtl&, const MNetArg& a) { return &a; }
 S2D_DEV const MSeeArg* m_net_arg(const MCtl&, const MSeeArg& a) { return &a; }
 S2D_DEV const MPolArg* m_net_arg(const MCtl&, const MPolArg& a) { return &a; }
 S2D_DEV const MSeePolArg* m_net_arg(const MCtl&, const MSeePolArg& a) { return &a; }
+S2D_DEV const MBelArg* m_net_arg(const MCtl&, const MBelArg& a) { return &a; }
 S2D_DEV const MNetArg* m_net_arg(const MCtlRw&) { return nullptr; }
 template <class A> S2D_DEV const A* m_net_arg(const MCtlRw&, const A& a) { return &a; }
 template <class... A> S2D_DEV MRw m_rw_arg(const A&...) { return MRw{nullptr, nullptr, 0}; }
@@ -292,6 +311,7 @@ template <class... A> S2D_DEV MRw m_rw_arg(const MCtlRw& c, const A&...) { retur
 template <class... A> struct MIsSee : std::false_type {};
 template <> struct MIsSee<MCtl, MSeeArg> : std::true_type {};
 template <> struct MIsSee<MCtl, MSeePolArg> : std::true_type {};
+template <> struct MIsSee<MCtl, MBelArg> : std::true_type {};
 template <class... A> struct MIsPol : std::false_type {};
 template <> struct MIsPol<MCtl, MPolArg> : std::true_type {};
 template <> struct MIsPol<MCtlRw, MPolArg> : std::true_type {};

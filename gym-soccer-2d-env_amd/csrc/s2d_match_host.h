@@ -1,9 +1,9 @@
 // s2d_match_host.h -- 11v11: the host side that every unit launching the cycle kernel needs.
 //
 // Holds: MRole, S2DMatchEngine, mfail, MHIP_TRY, MDeviceGuard, m_grid, the variant table, m_net_allow_lds, m_net_launch and
-// m_dispatch, and the prototypes of the two launches that live in units of their own.  What exists once in the library (the
+// m_dispatch, and the prototypes of the three launches that live in units of their own.  What exists once in the library (the
 // non-template kernels, the arena layout, the C ABI) is s2d_match.hip's.
-// Included by s2d_match.hip, s2d_match_reward.hip and s2d_match_see_policy.hip.
+// Included by s2d_match.hip, s2d_match_reward.hip, s2d_match_see_policy.hip and s2d_match_belief_net.hip.
 #pragma once
 #include "s2d_match_cycle.h"
 
@@ -32,6 +32,12 @@ struct S2DMatchEngine {
   bool see_pol = false;                                // s2d_match_set_see_policy_network: `see` holds a policy (epsilon NULL), launches use the SEEPOL kernels
   int see_act = 0;                                     // ... its hidden activation (0 relu, 1 tanh)
   const uint32_t* see_det = nullptr;                   // ... its deterministic word (the caller's, read at run time)
+  bool has_bel = false;                                // s2d_match_set_belief_network: `see` holds a belief network (see_act, see_det: its words;
+                                                       // see.epsilon: head 0's), launches use the BEL kernels
+  int bel_head = 0;                                    // ... its head: 0 epsilon-greedy Q-network, 1 categorical policy
+  S2DBeliefParams bel_prm{};                           // ... the belief parameters (a copy)
+  float* bel_rows = nullptr;                           // ... the caller's state buffer [N][popcount(bel_mask)][192]
+  uint32_t bel_mask = 0;                               // ... and its layout
   uint32_t ctl_random = 0, ctl_script = 0;             // its slot masks (S2D_CTL_RANDOM, S2D_CTL_SCRIPTED)
   MAgentTab atab;                                      // per-slot words of s2d_match_agent_obs
   bool has_rw = false;                                 // s2d_match_set_agent_reward installed the weights: the reward record may be asked for
@@ -100,8 +106,13 @@ template <auto Kernel> static bool m_net_allow_lds(size_t dyn) {
 template <auto Kernel, class CA, class NA>
 static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp, const MPtrs& ptrs, int64_t n, int n_steps,
                         const float* actions, const MRoll& ro, const CA& ctl /* MCtl, or MCtlRw */, const NA& na) {
-  constexpr bool SEEPOL = std::is_same<NA, MSeePolArg>::value, SEE = std::is_same<NA, MSeeArg>::value || SEEPOL;
-  constexpr int wave_words = SEEPOL ? kSeePolWaveWords : SEE ? kSeeWaveWords : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
+  constexpr bool BEL = std::is_same<NA, MBelArg>::value, SEEPOL = std::is_same<NA, MSeePolArg>::value;
+  constexpr bool SEE = std::is_same<NA, MSeeArg>::value || SEEPOL || BEL;
+  // The belief network's budget: W2 .. b3 of a 192-64-64-64 network are 33 536 B, a wave's tile, facts, index and log-probability
+  // words 20 096 B and its two staging rows with their scratch 3 072 B: 33 536 + 4 x 23 168 = 126 208 B beside at most 14 576 B.
+  constexpr int wave_words = BEL ? kBelWaveWords : SEEPOL ? kSeePolWaveWords : SEE ? kSeeWaveWords
+                             : std::is_same<NA, MPolArg>::value ? kPolWaveWords : kNetWaveWords;
+  constexpr const char* what = BEL ? "the belief network's LDS (its weights, tiles and staging rows: " : "the network's LDS (";
   size_t dyn = ((size_t)na.net.shared_words + (size_t)(kMBlock / 64) * wave_words) * sizeof(float);
   if constexpr (!SEE) {
     // The budget: a 64-64-64 network's W2 .. b3 are 33 536 B, a wave's tile, facts and index words 20 784 B, so two widest
@@ -123,7 +134,7 @@ static int m_net_launch(dim3 grid, dim3 block, hipStream_t st, const MParams& mp
     }
   }
   if (!m_net_allow_lds<Kernel>(dyn))
-    return mfail(S2D_EHIP, "the network's LDS (" + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
+    return mfail(S2D_EHIP, std::string(what) + std::to_string(dyn) + " B) does not fit beside the cycle kernel's");
   hipLaunchKernelGGL(Kernel, grid, block, dyn, st, mp, ptrs, n, n_steps, actions, ro, ctl, na);
   return S2D_OK;
 }
@@ -153,3 +164,6 @@ int s2d_match_internal_reward_launch(S2DMatchHandle h, int n_steps, const float*
 // s2d_match_see_policy.hip, the SEEPOL instantiations.
 int s2d_match_internal_see_policy_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st,
                                          const MCtl& ctl, const MSeePolArg& pa);
+// s2d_match_belief_net.hip, the BEL instantiations.
+int s2d_match_internal_belief_net_launch(S2DMatchHandle h, int n_steps, const float* actions, const MRoll& ro, hipStream_t st,
+                                         const MCtl& ctl, const MBelArg& ba);

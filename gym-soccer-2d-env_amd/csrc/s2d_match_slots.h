@@ -1,10 +1,11 @@
 // s2d_match_slots.h -- 11v11: what a slot of the cycle kernel can be driven by and what it reports.
 //
 // Holds: the agent observations (facts and rows) and the agent reward, the network slots, the policy slots, the see network and
-// the see policy -- device code only, on top of the rule book of s2d_match_rules.h.
-// Included by s2d_match_cycle.h (and through it by the three match units).
+// the see policy, the belief network -- device code only, on top of the rule book of s2d_match_rules.h.
+// Included by s2d_match_cycle.h (and through it by the match units).
 #pragma once
 #include "s2d_match_rules.h"
+#include "s2d_belief_row.h"
 
 // Per-agent observations (include/s2d_match.h, s2d_match_agent_obs).  Per-slot words the cycle kernels do not keep (the PT table
 // stays as it is): built on the host at create time, passed by value.
@@ -527,6 +528,26 @@ struct MSeePolArg {
 };
 constexpr int kSeePolWaveWords = kSeeWaveWords + kNetMaxRows;
 static_assert(kSeeWaveWords % 4 == 0 && kSeePolWaveWords % 4 == 0, "a wave's part starts 16-byte aligned");
+// Belief network (s2d_match_set_belief_network): the kernel argument of the BELIEF instantiations, an MSeePolArg (net.epsilon: the
+// Q head's) and then the belief words.  The network reads the slot's BELIEF row: per cycle and agent the see row is built into a
+// staging row of the half-wave, the belief row comes from memory into the tile row, s2d_belief_row.h's belief_update() takes the
+// see row into it there, and it goes back to memory.  A wave's part: a see policy wave's, then per half-wave the staging row and
+// belief_update's scratch (2 x 768 B each half, 3 KB more per wave).
+struct MBelArg {
+  MSee net; s2d_see::SeeParams sp; S2DMatchVision vis;
+  int act;                                 // hidden activation: 0 relu, 1 tanh_spec (head 0: relu)
+  const uint32_t* det;                     // head 1: the policy's device word (read once per launch): != 0 -> greedy
+  float* logp;                             // [T][N][22] or NULL
+  int head;                                // 0: epsilon-greedy Q-network (net.epsilon), 1: categorical policy (det)
+  s2d_belief::BeliefParams bp;
+  float* belief;                           // the state: [N][popcount(belief_mask)][192], a slot's row = its rank in belief_mask
+  uint32_t belief_mask;                    // (net.row_mask lies inside it)
+  float* belief_out;                       // [T][N][popcount(obs_mask)][192] or NULL: the rows the network acted on
+  const uint8_t* done0;                    // the engine's done plane as the launch finds it: the first cycle's reset flags
+};
+struct MBelStage { float4 see[s2d_see::kSeeVec]; s2d_belief::BeliefScratch scratch; };   // one half-wave
+constexpr int kBelWaveWords = kSeePolWaveWords + 2 * (int)(sizeof(MBelStage) / 4);
+static_assert(sizeof(MBelStage) % 16 == 0 && kBelWaveWords % 4 == 0, "16-byte aligned LDS parts");
 
 // the block-shared part of the network into LDS (every thread of the block; the kernel's barrier follows)
 S2D_DEV void m_see_stage(const MSee& net) {
@@ -560,18 +581,24 @@ S2D_DEV void m_see_pol_tile_layers(const MSee& net, const float* shared, float* 
 // slots).  All 64 lanes, uniform control flow.
 // SEEPOL (SA = MSeePolArg): the policy's forward and the categorical head of the policy slots (m_pol_tile_head; `det`: the
 // launch's deterministic bit); returns an MPick: the index and its log-probability (0 for a slot outside the mask).
+// BEL (SA = MBelArg): SEEPOL on the slot's BELIEF row -- the see row goes into the half-wave's staging row, the slot's belief row
+// (match ec, the slot's rank in belief_mask) comes from memory into the tile row, belief_update() takes the see row into it (reset:
+// the match's flag), it is stored back and recorded (valid matches only).  The head is the launch's: the categorical one, or the
+// first maximum (the exploration draw is the body's), whose log-probability is 0.
 template <class P, class SA>
 S2D_DEV auto m_see_greedy(const P& p, const SA& sa, const MObj& o, const MGame& g, float vneck, int vwidth, int vwait, int l, int half,
-                          bool valid, uint64_t gid, int64_t rec_row, bool det = false) {
-  constexpr bool SEEPOL = std::is_same<SA, MSeePolArg>::value;
+                          bool valid, uint64_t gid, int64_t rec_row, bool det = false, int64_t ec = 0, bool reset = false) {
+  constexpr bool BEL = std::is_same<SA, MBelArg>::value;
+  constexpr bool SEEPOL = std::is_same<SA, MSeePolArg>::value || BEL;
   const MSee& net = sa.net;
   const int lane = threadIdx.x & 63, gq = lane >> 4, c = lane & 15;
   float* const shared = m_net_lds();
-  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * (SEEPOL ? kSeePolWaveWords : kSeeWaveWords);
+  float* const tile = shared + net.shared_words + (threadIdx.x >> 6) * (BEL ? kBelWaveWords : SEEPOL ? kSeePolWaveWords : kSeeWaveWords);
   float* const hid = tile + 16 * kSeeRowPitch;
   s2d_see::SeeFacts* const facts = reinterpret_cast<s2d_see::SeeFacts*>(hid + 16 * kNetHidPitch);
   int* const gidx = reinterpret_cast<int*>(facts + 2);
   [[maybe_unused]] float* const glp = reinterpret_cast<float*>(gidx + kNetMaxRows);   // (SEEPOL only: the words kSeePolWaveWords adds)
+  [[maybe_unused]] MBelStage* const stage = reinterpret_cast<MBelStage*>(glp + kNetMaxRows) + half;   // (BEL only: kBelWaveWords' words)
   s2d_see::SeeIn in{};
   if (l <= BALL) { in.x = o.x; in.y = o.y; in.vx = o.vx; in.vy = o.vy; }
   if (l < NP) {
@@ -597,18 +624,42 @@ S2D_DEV auto m_see_greedy(const P& p, const SA& sa, const MObj& o, const MGame& 
       const int pa = __builtin_ctz(rest);              // the agent (uniform: the mask is a kernel argument)
       rest &= rest - 1u;
       float4* const row = reinterpret_cast<float4*>(tile + (2 * j + half) * kSeeRowPitch);
-      s2d_see::see_row(sa.sp, fs, in, l, half, pa, gid, row);   // (ends with a wave fence: the row is whole)
-      if (net.see_out && ((net.obs_mask >> pa) & 1u)) {
-        const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
-        if (valid) s2d_see::see_row_store(net.see_out + (rec_row * nobs + k) * S2D_SEE_DIM, row, l);
+      if constexpr (BEL) {
+        // the belief row is in flight while the see row is built (the same lanes wrote these words in the cycle before)
+        float4* const brow = reinterpret_cast<float4*>(sa.belief) +
+                             (ec * __builtin_popcount(sa.belief_mask) + __builtin_popcount(sa.belief_mask & ((1u << pa) - 1u))) *
+                                 (int64_t)s2d_belief::kVec;
+        const bool has2 = l + kHalf < s2d_belief::kVec;
+        const float4 b0 = brow[l], b1 = has2 ? brow[l + kHalf] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        s2d_see::see_row(sa.sp, fs, in, l, half, pa, gid, stage->see);   // (ends with a wave fence: the row is whole)
+        row[l] = b0;
+        if (has2) row[l + kHalf] = b1;
+        wave_fence();
+        s2d_belief::belief_update(sa.bp, row, stage->see, stage->scratch, l, half, pa % 11, reset);   // (ends with a fence)
+        if (valid) { brow[l] = row[l]; if (has2) brow[l + kHalf] = row[l + kHalf]; }
+        if ((net.obs_mask >> pa) & 1u) {
+          const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
+          if (net.see_out && valid) s2d_see::see_row_store(net.see_out + (rec_row * nobs + k) * S2D_SEE_DIM, stage->see, l);
+          if (sa.belief_out && valid) s2d_see::see_row_store(sa.belief_out + (rec_row * nobs + k) * S2D_BELIEF_DIM, row, l);
+        }
+      } else {
+        s2d_see::see_row(sa.sp, fs, in, l, half, pa, gid, row);   // (ends with a wave fence: the row is whole)
+        if (net.see_out && ((net.obs_mask >> pa) & 1u)) {
+          const int k = __builtin_popcount(net.obs_mask & ((1u << pa) - 1u));
+          if (valid) s2d_see::see_row_store(net.see_out + (rec_row * nobs + k) * S2D_SEE_DIM, row, l);
+        }
       }
     }
     wave_fence();
     if constexpr (SEEPOL) {                              // (a see policy always has slots: no record-only launch here)
       if (sa.act) m_see_pol_tile_layers<S2D_ACT_FN_TANH>(net, shared, tile, hid, lane);
       else m_see_pol_tile_layers<S2D_ACT_FN_RELU>(net, shared, tile, hid, lane);
-      m_pol_tile_head(p, net.na, hid, gidx + 16 * nt, glp + 16 * nt, lane, true, det, tile_mask, rn, (uint32_t)gid,
-                      (uint32_t)(gid >> 32), (uint32_t)g.tick);
+      if constexpr (BEL)                                   // (head 0: the first maximum; no log-probability word is written)
+        m_pol_tile_head(p, net.na, hid, gidx + 16 * nt, glp + 16 * nt, lane, sa.head != 0, det, tile_mask, rn, (uint32_t)gid,
+                        (uint32_t)(gid >> 32), (uint32_t)g.tick);
+      else
+        m_pol_tile_head(p, net.na, hid, gidx + 16 * nt, glp + 16 * nt, lane, true, det, tile_mask, rn, (uint32_t)gid,
+                        (uint32_t)(gid >> 32), (uint32_t)g.tick);
     } else if (net.net_mask != 0u) {
       const float* const x = tile + c * kSeeRowPitch;
       layer_tile<true, 4>(net.frags, b1, net.h1 / 16, kSeeK1, [&](int s) { return x[4 * s + gq]; }, hid, kNetHidPitch, lane);
@@ -636,7 +687,11 @@ S2D_DEV auto m_see_greedy(const P& p, const SA& sa, const MObj& o, const MGame& 
   if (l < NP && ((net.net_mask >> l) & 1u)) greedy = gidx[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
   if constexpr (SEEPOL) {
     float lp = 0.0f;
-    if (l < NP && ((net.net_mask >> l) & 1u)) lp = glp[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+    if constexpr (BEL) {
+      if (l < NP && ((net.net_mask >> l) & 1u) && sa.head != 0) lp = glp[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+    } else {
+      if (l < NP && ((net.net_mask >> l) & 1u)) lp = glp[2 * __builtin_popcount(net.row_mask & ((1u << l) - 1u)) + half];
+    }
     wave_fence();
     return MPick{greedy, lp};
   } else {

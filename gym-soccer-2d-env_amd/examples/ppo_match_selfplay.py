@@ -22,6 +22,10 @@ a [K, 5] table whose rows also turn the neck or change the view width, the visio
 the recorded see rows, the signed team reward (the see families have no agent reward: --shaping is refused).  No snapshot
 opponent exists for see networks, so evaluation plays the deterministic learner's left team against the in-kernel scripted team.
 
+--obs belief is --obs see with a memory: enable_belief(), a MatchSeePolicyActor(obs='belief') on every slot's
+192-word belief row -- the cycle kernel builds the see row, takes it into the slot's belief and acts on that -- the critic on the
+recorded belief rows (rec['belief']) and belief_peek() for the rows after the last cycle.  --shaping is refused as for see.
+
 stable-baselines3 cannot be installed offline; the PPO here is a small plain-torch one of the same shape (Tanh MlpPolicy)."""
 import argparse
 import os
@@ -72,15 +76,16 @@ def parse(argv=None):
     ap.add_argument('--chaser-only', action='store_true', help='with --shaping: approach and facing for each team\'s chaser only')
     ap.add_argument('--fused-learner', action='store_true',
                     help='the minibatch epochs in HIP (soccer2d_amd.learn.PPOLearner) instead of torch autograd and Adam')
-    ap.add_argument('--obs', default='agent', choices=('agent', 'see'),
-                    help="'see': partial observability -- the policy on see rows (MatchSeePolicyActor), vision stepped in the kernel")
+    ap.add_argument('--obs', default='agent', choices=('agent', 'see', 'belief'),
+                    help="'see': partial observability -- the policy on see rows (MatchSeePolicyActor), vision stepped in the kernel; "
+                         "'belief': the same on belief rows, the belief updated in the kernel too")
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args(argv)
     if args.chaser_only and not args.shaping:
         ap.error('--chaser-only needs --shaping')
-    if args.shaping and args.obs == 'see':
-        ap.error('--shaping needs --obs agent: the see families of the cycle kernel have no agent reward')
+    if args.shaping and args.obs in ('see', 'belief'):
+        ap.error('--shaping needs --obs agent: the see and belief families of the cycle kernel have no agent reward')
     if args.shaping:
         try:
             args.shaping = {k.strip(): float(v) for k, v in (item.split('=') for item in args.shaping.split(','))}
@@ -97,7 +102,8 @@ def main(argv=None):
     from soccer2d_amd.match import MatchEngine
     torch.manual_seed(args.seed)
     dev = torch.device(args.device)
-    see = args.obs == 'see'
+    belief = args.obs == 'belief'
+    see = args.obs == 'see' or belief                      # the see path: 192 words, the [K, 5] table, vision in the kernel
     table = SEE_ACTION_TABLE if see else ACTION_TABLE
     N, T, K, D = args.num_matches, args.steps, len(table), 192 if see else 224
     act = nn.ReLU if args.relu else nn.Tanh
@@ -109,10 +115,15 @@ def main(argv=None):
                                           ent_coef=args.ent_coef, max_batch=(T * N * 22 + args.minibatches - 1) // args.minibatches)
     else:
         opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()), lr=args.lr)
-    actor = (MatchSeePolicyActor if see else MatchPolicyActor).from_module(pi, table, device=dev)
+    if see:
+        actor = MatchSeePolicyActor.from_module(pi, table, device=dev, obs=args.obs)
+    else:
+        actor = MatchPolicyActor.from_module(pi, table, device=dev)
     eng = MatchEngine(N, dev, noise=True, seed=args.seed)
     if see:
         eng.enable_vision()
+    if belief:
+        eng.enable_belief('all')
     eng.set_network(actor, 'all')
     if args.shaping:
         eng.set_agent_reward(args.shaping, args.chaser_only)
@@ -121,6 +132,8 @@ def main(argv=None):
     eval_eng = MatchEngine(max(1, N // 2), dev, noise=True, seed=args.seed + 1)
     if see:                                                # the learner's left team, greedy, against the scripted right team
         eval_eng.enable_vision()
+        if belief:
+            eval_eng.enable_belief('left')
         eval_eng.set_controllers({'left': 'external', 'right': 'scripted'})
         eval_actor = actor.snapshot(deterministic=True)
         eval_eng.set_network(eval_actor, 'left')
@@ -128,14 +141,16 @@ def main(argv=None):
     sign = torch.tensor([1.0] * 11 + [-1.0] * 11, device=dev)
     stats = []
     for it in range(args.iterations):
-        if see:
+        if belief:
+            eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, belief_obs='all')
+        elif see:
             eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, see_obs='all')
         else:
             eng.rollout(T, out=rec, with_obs=False, logp=True, net_index=True, agent_obs='all', agent_reward=bool(args.shaping))
-        rows, idx, logp_old = rec['see' if see else 'agent_obs'], rec['net_index'], rec['logp']
+        rows, idx, logp_old = rec['belief' if belief else 'see' if see else 'agent_obs'], rec['net_index'], rec['logp']
         with torch.no_grad():
             value = vf(rows.reshape(-1, D)).reshape(T, N * 22)
-            last_rows = eng.see('all') if see else eng.agent_observations('all')
+            last_rows = eng.belief_peek() if belief else eng.see('all') if see else eng.agent_observations('all')
             last_value = vf(last_rows.reshape(-1, D)).reshape(N * 22)
         if args.shaping:
             reward = rec['agent_reward'].reshape(T, N * 22)

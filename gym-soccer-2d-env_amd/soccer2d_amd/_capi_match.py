@@ -202,6 +202,13 @@ class S2DMatchSeePolicyNet(C.Structure):    # include/s2d_match.h: see policy sl
                 ('prm', S2DVisionParams), ('vis', S2DMatchVision), ('activation', C.c_int32)]
 
 
+class S2DMatchBeliefNet(C.Structure):       # include/s2d_match.h: Belief network
+    _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
+                ('params', C.c_void_p), ('table', C.c_void_p), ('prm', S2DVisionParams), ('vis', S2DMatchVision),
+                ('head', C.c_int32), ('activation', C.c_int32), ('epsilon', C.c_void_p), ('deterministic', C.c_void_p),
+                ('belief_prm', S2DBeliefParams), ('belief', C.c_void_p), ('belief_mask', C.c_uint32)]
+
+
 class S2DMatchAgentReward(C.Structure):     # include/s2d_match.h: Agent reward
     _fields_ = [('weights', C.c_void_p), ('chaser_only', C.c_int32)]
 
@@ -254,6 +261,9 @@ MATCH_PROTOTYPES = (
     ('s2d_match_set_see_policy_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_see_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
+    ('s2d_match_set_belief_network', C.c_int, (C.c_void_p, C.c_void_p)),
+    ('s2d_match_rollout_belief', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)),
     ('s2d_match_set_policy_network', C.c_int, (C.c_void_p, C.c_int, C.c_void_p)),
     ('s2d_match_rollout_policy', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),

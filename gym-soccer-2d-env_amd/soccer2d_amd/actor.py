@@ -456,14 +456,18 @@ class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
 
     obs='see': a 192-H1-H2-K network on the agent's see row (MatchEngine.see: partial observability) with a table float32
     [K, 5] = (command, a, b, TurnNeck moment, ChangeView code) -- the see network of include/s2d_match.h
-    (s2d_match_set_see_network): the index chooses the body command and the view action."""
+    (s2d_match_set_see_network): the index chooses the body command and the view action.
+
+    obs='belief': the same network and table on the agent's belief row (MatchEngine.belief: the memory over its see rows) -- head
+    0 of the belief network of include/s2d_match.h (s2d_match_set_belief_network): the cycle kernel builds the see row, takes
+    it into the belief row and acts on that."""
 
     def __init__(self, hidden1=64, hidden2=64, n_actions=16, device='cuda:0', epsilon=0.05, table=None, obs='agent'):
-        if obs not in ('agent', 'see'):
-            raise ValueError(f"obs must be 'agent' or 'see', got {obs!r}")
+        if obs not in ('agent', 'see', 'belief'):
+            raise ValueError(f"obs must be 'agent', 'see' or 'belief', got {obs!r}")
         self.obs = obs
-        self.in_dim = MATCH_SEE_DIM if obs == 'see' else MATCH_OBS_DIM
-        self.table_width = 5 if obs == 'see' else 3
+        self.in_dim = MATCH_OBS_DIM if obs == 'agent' else MATCH_SEE_DIM
+        self.table_width = 3 if obs == 'agent' else 5
         for name, w in (('hidden1', hidden1), ('hidden2', hidden2)):
             if int(w) not in MATCH_WIDTHS:
                 raise ValueError(f'{name} must be one of {MATCH_WIDTHS}, got {w}')
@@ -477,7 +481,7 @@ class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
     @classmethod
     def from_module(cls, module, table, device=None, epsilon=0.05, obs='agent'):
         """An actor shaped like `module` (three nn.Linear layers 224 -> H1 -> H2 -> K), loaded from it, with action table
-        `table` [K, 3]; obs='see': 192 -> H1 -> H2 -> K and a table [K, 5]."""
+        `table` [K, 3]; obs='see' or 'belief': 192 -> H1 -> H2 -> K and a table [K, 5]."""
         (l1, l2, l3), _ = cls._read(module)
         dev = device if device is not None else l1.weight.device
         actor = cls(l1.out_features, l2.out_features, l3.out_features, device=dev, epsilon=epsilon, obs=obs)
@@ -491,9 +495,14 @@ class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
         later sync() calls of the original do not touch it."""
         return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_actions, device=self.device, epsilon=epsilon, obs=self.obs))
 
-    def c_struct(self, slot_mask, vision_params=None, vision=None):
-        """S2DMatchNet; obs='see': S2DMatchSeeNet, which needs the engine's vision parameters and planes."""
+    def c_struct(self, slot_mask, vision_params=None, vision=None, belief_params=None, belief=None, belief_mask=0):
+        """S2DMatchNet; obs='see': S2DMatchSeeNet, which needs the engine's vision parameters and planes; obs='belief':
+        S2DMatchBeliefNet (head 0), which also needs the engine's belief parameters, buffer and mask."""
         from . import _capi_match as M
+        if self.obs == 'belief':
+            net = _belief_struct(self, slot_mask, vision_params, vision, belief_params, belief, belief_mask)
+            net.head, net.activation, net.epsilon = 0, 0, self._eps.data_ptr()
+            return net
         if self.obs == 'see':
             if vision_params is None or vision is None:
                 raise ValueError("a see actor's struct needs the engine's vision parameters and planes (enable_vision)")
@@ -504,6 +513,21 @@ class MatchQNetActor(_ActionTable, _Epsilon, _PackedActor):
         net.h1, net.h2, net.n_actions, net.slot_mask = self.hidden1, self.hidden2, self.n_actions, int(slot_mask)
         net.params, net.epsilon, net.table = self.params.data_ptr(), self._eps.data_ptr(), self.table.data_ptr()
         return net
+
+
+def _belief_struct(actor, slot_mask, vision_params, vision, belief_params, belief, belief_mask):
+    """the words of S2DMatchBeliefNet both heads share: the network, the table, the engine's vision and belief layers"""
+    from . import _capi_match as M
+    if vision_params is None or vision is None:
+        raise ValueError("a belief actor's struct needs the engine's vision parameters and planes (enable_vision)")
+    if belief_params is None or belief is None:
+        raise ValueError("a belief actor's struct needs the engine's belief parameters, buffer and mask (enable_belief)")
+    net = M.S2DMatchBeliefNet()
+    net.h1, net.h2, net.n_actions, net.slot_mask = actor.hidden1, actor.hidden2, actor.n_actions, int(slot_mask)
+    net.params, net.table = actor.params.data_ptr(), actor.table.data_ptr()
+    net.prm, net.vis = vision_params, vision
+    net.belief_prm, net.belief, net.belief_mask = belief_params, belief.data_ptr(), int(belief_mask)
+    return net
 
 
 class _MatchPolicy(_ActionTable, _Deterministic, _PackedActor):
@@ -541,7 +565,7 @@ class _MatchPolicy(_ActionTable, _Deterministic, _PackedActor):
         """A frozen copy: a new actor of the same shape with its own parameters, table and deterministic word -- the league
         member a learner plays against, or an evaluation copy.  It has no module: later sync() calls do not touch it."""
         return self._frozen(type(self)(self.hidden1, self.hidden2, self.n_actions, activation=self.activation, device=self.device,
-                                       deterministic=self._det_value if deterministic is None else deterministic))
+                                       deterministic=self._det_value if deterministic is None else deterministic, obs=self.obs))
 
     def _fill(self, net, slot_mask):
         """the words S2DMatchPolicyNet and S2DMatchSeePolicyNet share"""
@@ -592,22 +616,36 @@ class MatchSeePolicyActor(_MatchPolicy):
     The logits are MatchPolicyActor's with 192 inputs; the sampled index chooses a row of `table`, float32 [K, 5] = (command, a,
     b, TurnNeck moment, ChangeView code), so the policy also turns the neck and changes the view width, and the cycle kernel
     steps the vision state of all 22 players.  ``MatchEngine.rollout(logp=True, see_obs=..., net_index=True)`` records what a
-    PPO / A2C learner needs.  It is the engine's only network (no opponent beside it) and needs enable_vision() first."""
+    PPO / A2C learner needs.  It is the engine's only network (no opponent beside it) and needs enable_vision() first.
+
+    obs='belief': the same policy and table on each slot's belief row (MatchEngine.belief) -- head 1 of the belief network of
+    include/s2d_match.h (s2d_match_set_belief_network); ``rollout(logp=True, belief_obs=..., net_index=True)`` records the rows
+    it acted on.  It needs enable_belief() too."""
 
     obs, in_dim, table_width = 'see', MATCH_SEE_DIM, 5
 
-    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None):
+    def __init__(self, hidden1=64, hidden2=64, n_actions=16, activation='tanh', device='cuda:0', deterministic=False, table=None,
+                 obs='see'):
+        if obs not in ('see', 'belief'):
+            raise ValueError(f"a MatchSeePolicyActor acts on see rows or belief rows (obs='see' or 'belief'), got obs={obs!r}: the "
+                             f"policy on agent rows is MatchPolicyActor")
+        self.obs = obs
         self._init_policy(hidden1, hidden2, n_actions, activation, device, deterministic, table)
 
     @classmethod
-    def from_module(cls, policy_net, table, device=None, deterministic=False):
+    def from_module(cls, policy_net, table, device=None, deterministic=False, obs='see'):
         """An actor shaped like `policy_net` (192 -> H1 -> H2 -> K, the module forms MatchPolicyActor.from_module accepts), loaded
         from it, with action table `table` [K, 5].  The activation is the module's."""
-        return cls._from_module(policy_net, table, device, deterministic)
+        return cls._from_module(policy_net, table, device, deterministic, obs=obs)
 
-    def c_struct(self, slot_mask, vision_params=None, vision=None):
-        """S2DMatchSeePolicyNet for s2d_match_set_see_policy_network; it needs the engine's vision parameters and planes"""
+    def c_struct(self, slot_mask, vision_params=None, vision=None, belief_params=None, belief=None, belief_mask=0):
+        """S2DMatchSeePolicyNet for s2d_match_set_see_policy_network; it needs the engine's vision parameters and planes.
+        obs='belief': S2DMatchBeliefNet (head 1), which also needs the engine's belief parameters, buffer and mask."""
         from . import _capi_match as M
+        if self.obs == 'belief':
+            net = _belief_struct(self, slot_mask, vision_params, vision, belief_params, belief, belief_mask)
+            net.head, net.activation, net.deterministic = 1, 1 if self.activation == 'tanh' else 0, self._det.data_ptr()
+            return net
         if vision_params is None or vision is None:
             raise ValueError("a see actor's struct needs the engine's vision parameters and planes (enable_vision)")
         net = self._fill(M.S2DMatchSeePolicyNet(), slot_mask)

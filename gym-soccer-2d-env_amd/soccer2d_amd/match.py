@@ -152,7 +152,16 @@ class MatchEngine:
         slot's TurnNeck / ChangeView, and from now on the cycle kernel steps the vision state itself -- do not call vision_step()
         for cycles it runs.  It needs enable_vision() first.  Either kind replaces the other, and the see network also clears
         the opponent network: it stays the engine's only one.  A MatchSeePolicyActor is the see network's stochastic
-        counterpart (s2d_match_set_see_policy_network), under the same rules."""
+        counterpart (s2d_match_set_see_policy_network), under the same rules.
+
+        A belief actor (MatchQNetActor(obs='belief') or MatchSeePolicyActor(obs='belief')) is the belief network
+        (s2d_match_set_belief_network): a see network that acts on the slot's belief row.  The cycle kernel then also owns the
+        belief update of its slots -- it takes each cycle's see row into `belief` before it acts -- so do not call belief_step()
+        for cycles it runs.  It needs enable_vision() and enable_belief(...) with the belief's slots containing `slots`.  The
+        engine keeps the address of the `belief` tensor, as it does of the vision planes: while a belief network is set, change
+        `belief` in place only (belief.copy_(...), belief_step, belief_scan) and never rebind the attribute to another tensor --
+        the kernel would go on reading and writing the old one.  enable_belief() is the one call that replaces the tensor, and it
+        sets the network again on the new one."""
         if actor is None:
             _capi.check(self.lib, self.lib.s2d_match_set_network(self._h, None), 's2d_match_set_network')
             _capi.check(self.lib, self.lib.s2d_match_set_opponent_network(self._h, None), 's2d_match_set_opponent_network')
@@ -163,7 +172,15 @@ class MatchEngine:
         mask = M.agent_slot_mask(slots)
         if actor.device != self.device:
             raise ValueError(f"the actor's buffers are on {actor.device}, the engine on {self.device}")
-        if getattr(actor, 'obs', 'agent') == 'see':
+        if getattr(actor, 'obs', 'agent') == 'belief':
+            self._need_vision()
+            self._need_belief()
+            if mask & ~self.belief_mask:
+                raise ValueError(f"network slots {mask:#x} are not inside the belief's slots {self.belief_mask:#x} (enable_belief)")
+            net = actor.c_struct(mask, self.vision_params, self.vision, self.belief_params, self.belief, self.belief_mask)
+            _capi.check(self.lib, self.lib.s2d_match_set_belief_network(self._h, C.byref(net)), 's2d_match_set_belief_network')
+            self.opponent_network, self.opponent_mask = None, 0
+        elif getattr(actor, 'obs', 'agent') == 'see':
             self._need_vision()
             net = actor.c_struct(mask, self.vision_params, self.vision)
             if _is_policy(actor):
@@ -200,7 +217,7 @@ class MatchEngine:
             self.opponent_network, self.opponent_mask = None, 0
             return
         mask = M.agent_slot_mask(slots)
-        if getattr(actor, 'obs', 'agent') == 'see':
+        if getattr(actor, 'obs', 'agent') in ('see', 'belief'):
             raise ValueError("the opponent network acts on agent rows: a see actor cannot be one (the see network stays single)")
         if actor.device != self.device:
             raise ValueError(f"the actor's buffers are on {actor.device}, the engine on {self.device}")
@@ -239,7 +256,11 @@ class MatchEngine:
         return t
 
     def _see_network_set(self):
-        return self.network is not None and getattr(self.network, 'obs', 'agent') == 'see'
+        """a see network of any kind is set: a see actor, or a belief actor (a see network on belief rows)"""
+        return self.network is not None and getattr(self.network, 'obs', 'agent') in ('see', 'belief')
+
+    def _belief_network_set(self):
+        return self.network is not None and getattr(self.network, 'obs', 'agent') == 'belief'
 
     def _actions(self, actions, T=None):
         if actions is None:
@@ -284,7 +305,7 @@ class MatchEngine:
         return out
 
     def rollout(self, n_steps, actions=None, out=None, with_obs=True, record_actions=False, net_index=False, agent_obs=None,
-                see_obs=None, view_actions=None, logp=False, agent_reward=False):
+                see_obs=None, view_actions=None, logp=False, agent_reward=False, belief_obs=None):
         """record_actions: out['actions'] float32 [T, N, 22, 3] receives the (command, a, b) each slot's controller chose in
         each cycle, before the engine's own gating (caller slots: the caller's row).  net_index: out['net_index'] int32
         [T, N, 22] receives each network slot's index (-1 for the other slots).  agent_obs = 'all' | 'left' | 'right' | a mask:
@@ -298,8 +319,19 @@ class MatchEngine:
         With a MatchSeePolicyActor set it is the see policy's record (s2d_match_rollout_see_policy), with net_index, see_obs and
         view_actions as above; a see Q-network has none and logp is refused.
         agent_reward: out['agent_reward'] float32 [T, N, 22] receives every agent's shaped reward of each cycle
-        (set_agent_reward first; s2d_match_rollout_reward); it composes with every record above but the see ones."""
+        (set_agent_reward first; s2d_match_rollout_reward); it composes with every record above but the see ones.
+        belief_obs = 'all' | 'left' | 'right' | a mask (a belief actor set; inside the belief's slots): out['belief'] float32
+        [T, N, k, 192] receives the belief rows the network acted on in each cycle -- the belief after that cycle's see row
+        (s2d_match_rollout_belief).  It shares its mask with see_obs: giving two different ones raises.  While a belief actor is
+        set every launch updates `belief` itself: do not call belief_step() for those cycles."""
         T = int(n_steps)
+        if belief_obs is not None:
+            if not self._belief_network_set():
+                raise ValueError("belief_obs needs a belief network (set_network with a belief actor)")
+            if see_obs is not None and M.agent_slot_mask(see_obs) != M.agent_slot_mask(belief_obs):
+                raise ValueError("see_obs and belief_obs share one mask: give the same slots for both (or only one of them)")
+            if agent_obs is not None or agent_reward:
+                raise ValueError("belief_obs excludes agent_obs and agent_reward (the belief network's cycle kernel has neither)")
         keep, ptr = self._actions(actions, T)
         if out is None:
             out = self.alloc_rollout(T, with_obs, record_actions)
@@ -329,10 +361,11 @@ class MatchEngine:
                                                                      _ptr(obs), _ptr(rwd), st), 's2d_match_rollout_reward')
         elif logp and self._see_network_set() and not _is_policy(self.network):
             raise ValueError("logp is the policy slots' record: the see Q-network has no policy head (MatchSeePolicyActor has)")
-        elif see_obs is not None or view_actions is not None or ((net_index or logp) and self._see_network_set()):
+        elif (see_obs is not None or view_actions is not None or belief_obs is not None or
+              ((net_index or logp) and self._see_network_set())):
             if agent_obs is not None:
                 raise ValueError("agent_obs and the see network's rollout exclude each other (one network per engine)")
-            va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp)
+            va = self._rollout_see(T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp, belief_obs)
         elif net_index or agent_obs is not None or logp:
             idx = self._record(out, 'net_index', T, (n, M.MATCH_PLAYERS), torch.int32) if net_index else None
             obs, mask = None, 0
@@ -353,9 +386,9 @@ class MatchEngine:
         self._keep = (keep, out, va)
         return out
 
-    def _rollout_see(self, T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp=False):
-        """the see network's rollout, the see policy's (logp: with its log-probability record), or the record-only one; returns
-        the view actions' tensor (for the caller to keep alive)"""
+    def _rollout_see(self, T, ptr, ro, rec, out, net_index, see_obs, view_actions, logp=False, belief_obs=None):
+        """the see network's rollout, the see policy's (logp: with its log-probability record), the belief network's (belief_obs:
+        with its row record), or the record-only one; returns the view actions' tensor (for the caller to keep alive)"""
         n, dev = self.num_envs, self.device
         self._need_vision()
         record_only = not self._see_network_set()
@@ -372,6 +405,17 @@ class MatchEngine:
         if see_obs is not None:
             mask = M.agent_slot_mask(see_obs)
             see = self._record(out, 'see', T, (n, bin(mask).count('1'), M.SEE_DIM), torch.float32)
+        if self._belief_network_set():
+            bel = None
+            if belief_obs is not None:
+                mask = M.agent_slot_mask(belief_obs)
+                bel = self._record(out, 'belief', T, (n, bin(mask).count('1'), M.BELIEF_DIM), torch.float32)
+            if mask & ~self.belief_mask:
+                raise ValueError(f"recorded slots {mask:#x} are not inside the belief's slots {self.belief_mask:#x}")
+            _capi.check(self.lib, self.lib.s2d_match_rollout_belief(self._h, T, ptr, _ptr(va), C.byref(ro), _ptr(rec), _ptr(idx), _ptr(lp),
+                                                                     mask, _ptr(see), _ptr(bel), self._stream()),
+                        's2d_match_rollout_belief')
+            return va
         if record_only:                                  # no network: the vision state stepped and recorded in-kernel for this call
             net = M.S2DMatchSeeNet()
             net.h1, net.h2, net.n_actions, net.slot_mask = 16, 16, 1, 0
@@ -500,8 +544,12 @@ class MatchEngine:
         192 words as wide as its see row (the words: _capi_match.BELIEF_FIELDS).  Needs the vision layer.  Allocates `belief`
         float32 [N, k, 192] (rows in ascending slot order; slots as for see) and resets it; from now on reset() resets the
         masked matches' rows.  `params`: S2DBeliefParams fields; ball_decay and player_decay default to the engine's
-        ServerParam, view_angle to the vision parameters'.  The layer reads see rows only: the engine does not change."""
+        ServerParam, view_angle to the vision parameters'.  The layer reads see rows only: the engine does not change -- unless a
+        belief network is set (set_network with a belief actor), whose cycle kernel updates `belief`; a second enable_belief()
+        then sets that network again on the new buffer and parameters, and refuses slots that no longer contain the network's."""
         self._need_vision()
+        if self._belief_network_set() and self.network_mask & ~M.agent_slot_mask(slots):
+            raise ValueError(f"a belief network plays slots {self.network_mask:#x}: the belief's slots must contain them")
         params.setdefault('ball_decay', self.cfg.sp.ball_decay)
         params.setdefault('player_decay', self.cfg.sp.player_decay)
         params.setdefault('view_angle', tuple(self.vision_params.view_angle))
@@ -512,6 +560,8 @@ class MatchEngine:
                                   device=self.device)
         _capi.check(self.lib, self.lib.s2d_match_belief_reset(_ptr(self.belief), self.num_envs, self.belief_mask, None,
                                                               self._stream()), 's2d_match_belief_reset')
+        if self._belief_network_set():                   # the engine kept the old buffer's address and the old parameters
+            self.set_network(self.network, self.network_mask)
 
     def _need_belief(self):
         if self.belief is None:
@@ -533,7 +583,8 @@ class MatchEngine:
     def belief_step(self, see=None, done=None):
         """One update of the belief with one see row per agent; call it once per cycle, after vision_step.  see: float32
         [N, k, 192] for the belief's slots, None = self.see(slots).  done: None, True (the engine's own `done` of the last step) or
-        a uint8 [N] tensor: those matches' beliefs are reset before the row is taken in.  Returns `belief` (updated in place)."""
+        a uint8 [N] tensor: those matches' beliefs are reset before the row is taken in.  Returns `belief` (updated in place).
+        Not for cycles a belief network runs (set_network with a belief actor): its cycle kernel takes each cycle's row in itself."""
         self._need_belief()
         s = self.see(self.belief_slots) if see is None else self._belief_rows(see, 'see', ())
         d = None
@@ -567,6 +618,19 @@ class MatchEngine:
         _capi.check(self.lib, rc, 's2d_match_belief_scan')
         self._keep_belief = (s, r)
         return self.belief if out is None else out
+
+    def belief_peek(self):
+        """float32 [N, k, 192]: the belief rows the next launch of a belief network will act on in its first cycle -- `belief`
+        after the see rows of the current state, with the engine's done plane as the reset flags -- without changing `belief`.
+        One s2d_match_belief_scan of T = 1 on a clone.  What a PPO loop needs for the value of the state after the last cycle."""
+        self._need_belief()
+        s = self.see(self.belief_slots)
+        b = self.belief.clone()
+        rc = self.lib.s2d_match_belief_scan(C.byref(self.belief_params), _ptr(s), _ptr(self.done), _ptr(b), None, 1,
+                                            self.num_envs, self.belief_mask, self._stream())
+        _capi.check(self.lib, rc, 's2d_match_belief_scan')
+        self._keep_peek = s
+        return b
 
     def world_model(self):
         """dict proto-path -> device tensor (left team's point of view = absolute coordinates)."""
@@ -667,6 +731,9 @@ class Soccer2DMatchVecEnv:
     def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, reward='goals', chaser_only=False,
                  belief=None, **kwargs):
         self.observation_space, self.action_space = self.spaces(opponent, obs)
+        if _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'belief':
+            raise ValueError("a belief actor is not offered as the in-kernel opponent (the env updates its belief after the cycle, "
+                             "the kernel before it); use a see actor with obs='belief'")
         shaped = not (isinstance(reward, str) and reward == 'goals')
         if shaped:
             if isinstance(reward, str):

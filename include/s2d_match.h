@@ -808,11 +808,75 @@ int s2d_match_belief_reset(float *belief_dev, int64_t n_matches, uint32_t slot_m
 int s2d_match_belief_scan(const S2DBeliefParams *prm, const float *see_dev, const uint8_t *reset_dev, float *belief_dev,
                           float *out_dev, int n_steps, int64_t n_matches, uint32_t slot_mask, void *stream);
 
+/* Belief network: the network slots of "See network" / "See policy slots" on each slot's BELIEF row -- the see row is built, taken
+ * into the slot's belief row, and the network acts on that row, all inside the cycle kernel: T cycles of collection under partial
+ * observability with a memory are one launch.  It occupies the see network's place: one per engine, no agent-row network beside it
+ * (it clears both roles and is cleared by the calls that clear a see network; role 1 refuses beside it; refused while an agent
+ * reward is set).  For every cycle of a launch, every match and slot:
+ *   1. See row.  For every slot of row_mask = slot_mask | obs_mask: its see row from the start-of-cycle state, the vision state and
+ *      the tick, as step 1 of "See network".  row_mask must lie inside belief_mask, the layout of the state buffer
+ *      belief[N][popcount(belief_mask)][S2D_BELIEF_DIM] (what s2d_match_belief_reset / _scan take with slot_mask = belief_mask): a
+ *      slot's row index in a match is its rank in belief_mask, and its own index u is slot % 11.
+ *   2. Belief update.  One update of that slot's row with that see row, exactly as "Belief" specifies for one row (bitwise the row
+ *      s2d_match_belief_scan writes for the same see row and flag).  The reset flag is the match's done of the previous cycle; for the first
+ *      cycle of a launch it is the engine's done plane (S2DMatchBuffers.done) as the launch finds it.  Slots of belief_mask outside
+ *      row_mask are not touched.  After a launch the state buffer holds every row_mask slot's belief after the start-of-cycle see
+ *      row of the launch's last cycle; it is read and written in every cycle, for valid matches only.
+ *   3. Network.  For every slot of slot_mask, on the slot's belief row (192 words): the logits of step 2 of "See policy slots"
+ *      (same layout of params, same k-ascending fmaf order, f = relu or tanh_spec).  head 1: step 3 of "See policy slots" (the
+ *      categorical head, *deterministic, logp) on the same Philox words.  head 0: the first-maximum argmax and the epsilon
+ *      exploration of "See network" (stream S2D_MATCH_ST_NET, block = slot, *epsilon read when the kernel runs); activation 0 only;
+ *      its logp is 0.
+ *   4. Act.  (cmd, a, b) = table[index][0..2] into the body cycle, table[index][3..4] into the vision step of step 4 of "See
+ *      network"; every other slot as there.
+ * The kernel OWNS the belief update of its row_mask slots as it owns the vision step: the caller must not also call
+ * s2d_match_belief_scan on those rows for cycles it runs.  Note the order: the kernel updates the belief BEFORE the body cycle (with
+ * the start-of-cycle row, the row the network acts on); a per-step loop that calls s2d_match_belief_scan after each step holds the
+ * same rows one call later.  The engine keeps the pointers (params, the head's word, table, planes, belief), not copies; prm and
+ * belief_prm are copied at the call.
+ * Not offered: a belief network as the in-kernel opponent of an environment that updates the same buffer after the cycle (two
+ * conventions on one buffer); a record-only belief network (slot_mask == 0: a see record and s2d_match_belief_scan give that); a
+ * second belief role; the agent reward.
+ * s2d_match_kernel_name ends in "belief network>" while one is set. */
+typedef struct S2DMatchBeliefNet {
+  int32_t h1, h2, n_actions;      /* h1, h2 in {16, 32, 48, 64}; 1 <= K <= 64 */
+  uint32_t slot_mask;             /* bits 0..21, not empty, inside belief_mask */
+  const float *params;            /* W1[h1][192], b1, W2[h2][h1], b2, W3[K][h2], b3; device, 16-byte aligned */
+  const float *table;             /* device float[K][5]: command, a, b, TurnNeck moment, ChangeView code */
+  S2DVisionParams prm;            /* copied at the call */
+  S2DMatchVision vis;             /* the caller's three planes; the engine keeps the pointers */
+  int32_t head;                   /* 0 epsilon-greedy Q-network, 1 categorical policy */
+  int32_t activation;             /* 0 relu, 1 tanh (tanh_spec) on both hidden layers; head 0: 0 */
+  const float *epsilon;           /* head 0: device float, read when the kernel runs (head 1: not read) */
+  const uint32_t *deterministic;  /* head 1: device word, read when the kernel runs: != 0 -> greedy (head 0: not read) */
+  S2DBeliefParams belief_prm;     /* copied at the call */
+  float *belief;                  /* device float[N][popcount(belief_mask)][S2D_BELIEF_DIM], 16-byte aligned; the engine keeps the pointer */
+  uint32_t belief_mask;           /* bits 0..21, not empty: the buffer's slots */
+} S2DMatchBeliefNet;
+/* net == NULL: clears the see network, whichever kind is set.  Errors (S2D_EINVAL, the engine unchanged): everything
+ * s2d_match_set_see_policy_network rejects (the device word being the head's: epsilon or deterministic); head outside {0, 1}; head 0
+ * with activation 1; a NULL or not 16-byte aligned belief; an empty belief_mask or bits above 21 in it; slot_mask not inside
+ * belief_mask; parameters s2d_match_belief_validate rejects; an agent reward is set.  s2d_match_step, s2d_match_rollout,
+ * s2d_match_rollout_ex, s2d_match_rollout_see and s2d_match_rollout_see_policy use the belief network when one is set (no belief
+ * record; an obs_mask outside belief_mask, or a record overlapping the state buffer, is refused); s2d_match_rollout_net, s2d_match_rollout_policy and s2d_match_rollout_reward
+ * return S2D_EINVAL as beside the see network. */
+int s2d_match_set_belief_network(S2DMatchHandle h, const S2DMatchBeliefNet *net);
+/* s2d_match_rollout_see_policy plus
+ *   belief_out_dev  float[T][N][popcount(obs_mask)][S2D_BELIEF_DIM] or NULL (16-byte aligned), written as whole 64-byte lines: the
+ *                   row the network acted on at cycle t, i.e. the belief after see row t.  see_out_dev and belief_out_dev share
+ *                   obs_mask; either may be NULL.
+ * Errors: as s2d_match_rollout_see_policy; no belief network set; obs_mask not inside belief_mask; an unaligned belief_out_dev; a
+ * record overlapping the state buffer. */
+int s2d_match_rollout_belief(S2DMatchHandle h, int n_steps, const float *actions_dev, const float *view_actions_dev,
+                             const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev, float *logp_out_dev,
+                             uint32_t obs_mask, float *see_out_dev, float *belief_out_dev, void *stream);
+
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
  * (same arithmetic, parameters read at run time; S2D_MATCH_GENERAL_KERNEL=1 in the environment selects it regardless).  Seed,
  * env_id_offset, auto_reset, noise and the PlayerTypes do not matter for the choice.  With a controller table, a network, a see
- * network or a see policy set the name ends in "controllers>", "network>", "see network>" or "see policy network>". */
+ * network, a see policy or a belief network set the name ends in "controllers>", "network>", "see network>", "see policy network>"
+ * or "belief network>". */
 const char *s2d_match_kernel_name(S2DMatchHandle h);
 
 #ifdef __cplusplus
