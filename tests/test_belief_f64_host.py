@@ -17,6 +17,15 @@ max over well-conditioned rows of (|f32 - f64| - 2 spread) / UNIT; `raw` is max 
     played, 60 cycles    5280    0  (0.000 %)     0.04  raw 1.60   0.02  raw 1.20   0.00  raw 1.00
     scenes                242   15  (6.198 %)     0.00  raw 0.00   0.00  raw 0.00   0.00  raw 0.00
 
+The cycle kernel's copy of the rule (belief_update() in csrc/s2d_belief_row.h), on the records of its own launches
+(tests/test_gpu_match_belief_net_edges.py; the same launches replayed on the host in tests/test_belief_state_scenes_host.py give
+these rows bit for bit):
+
+    cycle kernel, played 12 x 33     8712    0  (0.000 %)     0.34  raw 1.59   0.00  raw 1.49   0.00  raw 1.00
+    cycle kernel, priors, default    3168    1  (0.032 %)     0.31  raw 1.46   0.00  raw 1.28   0.00  raw 1.00
+    cycle kernel, priors, other      3168    0  (0.000 %)     0.23  raw 1.41   0.00  raw 1.01   0.00  raw 1.00
+    state scenes                      189   13  (6.878 %)     0.00  raw 0.00   0.00  raw 0.00   0.00  raw 0.00
+
 (body reaches its bound: body_rel + face is a tie in [256, 512) whenever face has an odd last bit in [128, 256), and where two probe
 moves cancel the spread is 0.  The errors are whole multiples of 2^-16 there, so the comparison with T = 1 is exact.)
 (The scenes are exact: every deviation is 0, so nothing exceeds twice the spread.)"""
