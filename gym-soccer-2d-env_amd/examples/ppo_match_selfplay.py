@@ -26,6 +26,11 @@ opponent exists for see networks, so evaluation plays the deterministic learner'
 192-word belief row -- the cycle kernel builds the see row, takes it into the slot's belief and acts on that -- the critic on the
 recorded belief rows (rec['belief']) and belief_peek() for the rows after the last cycle.  --shaping is refused as for see.
 
+--hear (with --obs see or belief) is the talking variant, on the unfused loop: the cycle kernel has no audio yet, so collection
+goes cycle by cycle through Soccer2DMatchVecEnv(obs=..., hear=True).  The policy's 224 inputs are [row | hear
+row], a second, small Gaussian head produces the 10 payload words, and every agent speaks every cycle; the log-probability of a
+step is the categorical one plus the Gaussian one.  No evaluation rounds; --fused-learner and --shaping are refused.
+
 stable-baselines3 cannot be installed offline; the PPO here is a small plain-torch one of the same shape (Tanh MlpPolicy)."""
 import argparse
 import os
@@ -79,6 +84,9 @@ def parse(argv=None):
     ap.add_argument('--obs', default='agent', choices=('agent', 'see', 'belief'),
                     help="'see': partial observability -- the policy on see rows (MatchSeePolicyActor), vision stepped in the kernel; "
                          "'belief': the same on belief rows, the belief updated in the kernel too")
+    ap.add_argument('--hear', action='store_true',
+                    help='the agents talk: [row | hear row] in, a Gaussian head for the 10 payload words; the unfused loop '
+                         '(needs --obs see or belief)')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args(argv)
@@ -86,6 +94,8 @@ def parse(argv=None):
         ap.error('--chaser-only needs --shaping')
     if args.shaping and args.obs in ('see', 'belief'):
         ap.error('--shaping needs --obs agent: the see and belief families of the cycle kernel have no agent reward')
+    if args.hear and (args.obs == 'agent' or args.fused_learner or args.shaping):
+        ap.error('--hear needs --obs see or belief and goes with neither --fused-learner nor --shaping')
     if args.shaping:
         try:
             args.shaping = {k.strip(): float(v) for k, v in (item.split('=') for item in args.shaping.split(','))}
@@ -94,8 +104,79 @@ def parse(argv=None):
     return args
 
 
+def main_hear(args):
+    """the talking variant: collection cycle by cycle through the env, the policy with a second head for what it says"""
+    from soccer2d_amd.gae import gae
+    from soccer2d_amd.match import Soccer2DMatchVecEnv
+    torch.manual_seed(args.seed)
+    dev = torch.device(args.device)
+    N, T, K, D, W = args.num_matches, args.steps, len(SEE_ACTION_TABLE), 224, 10
+    act = nn.ReLU if args.relu else nn.Tanh
+    table = torch.tensor(SEE_ACTION_TABLE, device=dev)
+    pi, vf = mlp(D, K, args.hidden, act).to(dev), mlp(D, 1, args.hidden, act).to(dev)
+    say_mu = mlp(D, W, 16, act).to(dev)                    # the second head: the mean of the payload words
+    say_logstd = nn.Parameter(torch.full((W,), -0.5, device=dev))
+    opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()) + list(say_mu.parameters()) + [say_logstd], lr=args.lr)
+    env = Soccer2DMatchVecEnv(N, dev, obs=args.obs, hear=True, noise=True, seed=args.seed)
+
+    def dists(o):
+        return torch.distributions.Categorical(logits=pi(o)), torch.distributions.Normal(say_mu(o), say_logstd.exp())
+
+    obs = env.reset()
+    rows = torch.empty((T, N, 22, D), device=dev)
+    idx = torch.empty((T, N, 22), dtype=torch.long, device=dev)
+    words = torch.empty((T, N, 22, W), device=dev)
+    logp_old, value = torch.empty((T, N, 22), device=dev), torch.empty((T, N, 22), device=dev)
+    reward, done = torch.empty((T, N, 22), device=dev), torch.empty((T, N, 22), dtype=torch.uint8, device=dev)
+    a = torch.zeros((N, 22, 17), device=dev)
+    a[..., 5] = 1.0                                        # said: every agent speaks every cycle; no attention command
+    stats = []
+    for it in range(args.iterations):
+        with torch.no_grad():
+            for t in range(T):
+                dc, dn = dists(obs)
+                k, w = dc.sample(), dn.sample()
+                rows[t], idx[t], words[t], value[t] = obs, k, w, vf(obs).squeeze(-1)
+                logp_old[t] = dc.log_prob(k) + dn.log_prob(w).sum(-1)
+                a[..., :5], a[..., 7:] = table[k], w       # the payload is clamped to [-1, 1] and quantised by the hear step
+                obs, r, d, _info = env.step(a)
+                reward[t], done[t] = r, d[:, None]
+            last_value = vf(obs).squeeze(-1)
+        adv, ret = gae(reward.reshape(T, N * 22).contiguous(), done.reshape(T, N * 22).contiguous(),
+                       value.reshape(T, N * 22).contiguous(), last_value.reshape(N * 22).contiguous(), args.gamma, args.lam)
+        obs_b, act_b, w_b = rows.reshape(-1, D), idx.reshape(-1), words.reshape(-1, W)
+        lp_b, adv_b, ret_b = logp_old.reshape(-1), adv.reshape(-1), ret.reshape(-1)
+        B = obs_b.shape[0]
+        mb = (B + args.minibatches - 1) // args.minibatches
+        for _epoch in range(args.epochs):
+            perm = torch.randperm(B, device=dev)
+            for s in range(0, B, mb):
+                i = perm[s:s + mb]
+                dc, dn = dists(obs_b[i])
+                lp = dc.log_prob(act_b[i]) + dn.log_prob(w_b[i]).sum(-1)
+                adv_i = adv_b[i]
+                adv_i = (adv_i - adv_i.mean()) / (adv_i.std() + 1e-8)
+                ratio = (lp - lp_b[i]).exp()
+                pg = -torch.min(ratio * adv_i, ratio.clamp(1 - args.clip, 1 + args.clip) * adv_i).mean()
+                v_loss = nn.functional.mse_loss(vf(obs_b[i]).squeeze(-1), ret_b[i])
+                ent = dc.entropy().mean() + dn.entropy().sum(-1).mean()
+                loss = pg + args.vf_coef * v_loss - args.ent_coef * ent
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+        row = dict(iteration=it, policy_loss=float(pg.detach()), value_loss=float(v_loss.detach()), entropy=float(ent.detach()),
+                   approx_kl=float((lp_b[i] - lp.detach()).mean()), mean_reward=float(reward[:, :, 0].mean()),
+                   heard_share=float(rows[..., 192].mean()))
+        stats.append(row)
+        print('  '.join(f'{k} {v:.4g}' if isinstance(v, float) else f'{k} {v}' for k, v in row.items()))
+    env.close()
+    return stats
+
+
 def main(argv=None):
     args = parse(argv)
+    if args.hear:
+        return main_hear(args)
     from soccer2d_amd import league
     from soccer2d_amd.actor import MatchPolicyActor, MatchSeePolicyActor
     from soccer2d_amd.gae import gae

@@ -72,6 +72,16 @@ for _i, _n in enumerate(('x', 'y', 'vx', 'vy', 'pos_count', 'game_mode_type', 'm
 for _i, _n in enumerate(BELIEF_ROW_FIELDS):
     BELIEF_FIELDS['players.' + _n] = slice(24 + _i, 192, 8)
 
+# the audio layer (s2d_match_hear_step; the words are specified in include/s2d_match.h, "Hearing")
+HEAR_DIM, HEAR_RECORD, SAY_WORDS, SAY_ROW, MATCH_ST_HEAR = 32, 16, 10, 12, 9
+HEAR_BLOCKS = {'ours': slice(0, 16), 'theirs': slice(16, 32)}
+HEAR_FIELDS = {}                                       # every word 0..31 exactly once: name -> index, or the payload's slice
+for _r, _base in (('ours', 0), ('theirs', 16)):
+    for _i, _n in enumerate(('heard', 'sender', 'dir', 'missed', 'capacity', 'attention')):
+        HEAR_FIELDS[f'{_r}.{_n}'] = _base + _i
+    HEAR_FIELDS[f'{_r}.payload'] = slice(_base + 6, _base + 16)
+SAY_FIELDS = {'said': 0, 'attention': 1, 'payload': slice(2, 12)}   # one say row (MatchEngine.hear_step)
+
 
 def belief_row_of(slot, other):
     """the player row (0..20) of raw slot `other` in the belief of the agent in raw slot `slot`: teammates first by own index
@@ -190,6 +200,17 @@ class S2DBeliefParams(C.Structure):         # include/s2d_match.h: Belief
                 ('match_dist', C.c_double), ('match_rate', C.c_double), ('ghost_margin', C.c_double), ('count_max', C.c_double)]
 
 
+HEAR_PARAM_FIELDS = ('audio_cut_dist', 'hear_max', 'hear_inc', 'hear_decay', 'say_msg_size', 'say_levels')
+
+
+class S2DHearParams(C.Structure):           # include/s2d_match.h: Hearing
+    _fields_ = [(n, C.c_double) for n in HEAR_PARAM_FIELDS]
+
+
+class S2DMatchHear(C.Structure):            # the caller-owned hear planes: three [N][24], the rows [N][22][32]
+    _fields_ = [('cap_our', C.c_void_p), ('cap_opp', C.c_void_p), ('attention', C.c_void_p), ('hear', C.c_void_p)]
+
+
 class S2DMatchSeeNet(C.Structure):          # include/s2d_match.h: see network
     _fields_ = [('h1', C.c_int32), ('h2', C.c_int32), ('n_actions', C.c_int32), ('slot_mask', C.c_uint32),
                 ('params', C.c_void_p), ('epsilon', C.c_void_p), ('table', C.c_void_p),
@@ -255,6 +276,11 @@ MATCH_PROTOTYPES = (
     ('s2d_match_belief_reset', C.c_int, (C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p)),
     ('s2d_match_belief_scan', C.c_int, (C.POINTER(S2DBeliefParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int64, C.c_uint32, C.c_void_p)),
+    ('s2d_match_hear_default_params', None, (C.POINTER(S2DHearParams),)),
+    ('s2d_match_hear_validate', C.c_int, (C.POINTER(S2DHearParams),)),
+    ('s2d_match_hear_reset', C.c_int, (C.c_void_p, C.POINTER(S2DHearParams), C.POINTER(S2DMatchHear), C.c_void_p, C.c_void_p)),
+    ('s2d_match_hear_step', C.c_int, (C.c_void_p, C.POINTER(S2DHearParams), C.POINTER(S2DMatchHear), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p)),
     ('s2d_match_set_see_network', C.c_int, (C.c_void_p, C.c_void_p)),
     ('s2d_match_rollout_see', C.c_int, (C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(S2DMatchRollout), C.c_void_p,
                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)),
@@ -371,4 +397,17 @@ def belief_params(lib, **params):
         else:
             raise ValueError(f"unknown belief parameter {k!r}")
     _capi.check(lib, lib.s2d_match_belief_validate(C.byref(prm)), 's2d_match_belief_validate')
+    return prm
+
+
+def hear_params(lib, **params):
+    """S2DHearParams: the defaults of s2d_match_hear_default_params with `params` written over them, validated by
+    s2d_match_hear_validate."""
+    prm = S2DHearParams()
+    lib.s2d_match_hear_default_params(C.byref(prm))
+    for k, v in params.items():
+        if k not in HEAR_PARAM_FIELDS:
+            raise ValueError(f"unknown hear parameter {k!r}")
+        setattr(prm, k, float(v))
+    _capi.check(lib, lib.s2d_match_hear_validate(C.byref(prm)), 's2d_match_hear_validate')
     return prm

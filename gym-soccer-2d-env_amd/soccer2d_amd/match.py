@@ -81,6 +81,7 @@ class MatchEngine:
         self.opponent_network, self.opponent_mask = None, 0   # no second network (set_opponent_network)
         self.vision = None                              # no vision layer (enable_vision)
         self.belief = None                              # no belief layer (enable_belief)
+        self.hearing = None                             # no audio layer (enable_hearing)
         self.agent_reward_weights = None                # no agent reward (set_agent_reward)
         if not torch.cuda.is_available():
             raise RuntimeError("the s2d HIP engine needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -285,6 +286,9 @@ class MatchEngine:
         if self.belief is not None:
             _capi.check(self.lib, self.lib.s2d_match_belief_reset(_ptr(self.belief), self.num_envs, self.belief_mask, ptr,
                                                                   self._stream()), 's2d_match_belief_reset')
+        if self.hearing is not None:
+            _capi.check(self.lib, self.lib.s2d_match_hear_reset(self._h, C.byref(self.hear_params), C.byref(self.hearing), ptr,
+                                                                self._stream()), 's2d_match_hear_reset')
         self._keep = mask
 
     def step(self, actions=None):
@@ -539,6 +543,62 @@ class MatchEngine:
                                                       C.c_void_p(out.data_ptr()), self._stream()), 's2d_match_see')
         return out
 
+    def enable_hearing(self, **params):
+        """Switch the audio layer on (include/s2d_match.h, "Hearing"): allocates the hear capacities `cap_our`, `cap_opp` and
+        `attention`, int32 [N, 24] each, and the hear rows `hear` float32 [N, 22, 32] (the words: _capi_match.HEAR_FIELDS), and
+        resets them; from now on reset() resets them with the engine.  `params`: S2DHearParams fields over the defaults.  The
+        engine itself does not change: no kernel of it reads or writes these planes."""
+        self.hear_params = M.hear_params(self.lib, **params)
+        shape = (self.num_envs, M.MATCH_SLOTS)
+        self.cap_our = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.cap_opp = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.attention = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.hear = torch.zeros((self.num_envs, M.MATCH_PLAYERS, M.HEAR_DIM), dtype=torch.float32, device=self.device)
+        self.hearing = M.S2DMatchHear(self.cap_our.data_ptr(), self.cap_opp.data_ptr(), self.attention.data_ptr(), self.hear.data_ptr())
+        _capi.check(self.lib, self.lib.s2d_match_hear_reset(self._h, C.byref(self.hear_params), C.byref(self.hearing), None,
+                                                            self._stream()), 's2d_match_hear_reset')
+
+    def _need_hearing(self):
+        if self.hearing is None:
+            raise RuntimeError("the audio layer is off: call enable_hearing() first")
+
+    def hear_step(self, say=None, done=None):
+        """One cycle of hearing; call it once after each body step, beside vision_step.  say float32 [N, 22, 12] = (said,
+        attention command, 10 payload words) per player in raw slot order (_capi_match.SAY_FIELDS), None = nobody speaks or changes
+        attention.  done: None, True (the engine's own `done` of the last step) or a uint8 [N] tensor: those matches' hear state
+        is reset instead.  The neck plane is passed when the vision layer is on.  Returns `hear` (rewritten in place)."""
+        self._need_hearing()
+        a, aptr = None, None
+        if say is not None:
+            a = torch.as_tensor(say, device=self.device).to(torch.float32).contiguous()
+            if tuple(a.shape) != (self.num_envs, M.MATCH_PLAYERS, M.SAY_ROW):
+                raise ValueError(f"say must have shape ({self.num_envs}, {M.MATCH_PLAYERS}, {M.SAY_ROW}), got {tuple(a.shape)}")
+            aptr = C.c_void_p(a.data_ptr())
+        d, dptr = None, None
+        if done is not None and done is not False:
+            d = self.done if done is True else torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
+            if tuple(d.shape) != (self.num_envs,):
+                raise ValueError(f"done must have shape ({self.num_envs},)")
+            dptr = C.c_void_p(d.data_ptr())
+        nptr = None if self.vision is None else C.c_void_p(self.neck.data_ptr())
+        _capi.check(self.lib, self.lib.s2d_match_hear_step(self._h, C.byref(self.hear_params), C.byref(self.hearing), nptr, aptr, dptr,
+                                                            self._stream()), 's2d_match_hear_step')
+        self._keep_hear = (a, d)
+        return self.hear
+
+    def hear_rows(self, slots='all'):
+        """float32 [N, k, 32]: the selected agents' hear rows in ascending slot order (slots as for see): a view of `hear` for
+        'all' / 'left' / 'right', a gather for any other mask."""
+        self._need_hearing()
+        mask = M.agent_slot_mask(slots)
+        if mask == M.AGENT_SLOT_MASKS['all']:
+            return self.hear
+        if mask == M.AGENT_SLOT_MASKS['left']:
+            return self.hear[:, :11]
+        if mask == M.AGENT_SLOT_MASKS['right']:
+            return self.hear[:, 11:]
+        return self.hear[:, [i for i in range(M.MATCH_PLAYERS) if (mask >> i) & 1]]
+
     def enable_belief(self, slots='all', **params):
         """Switch the belief layer on (include/s2d_match.h, "Belief"): each selected agent's memory of what it has seen, a row of
         192 words as wide as its see row (the words: _capi_match.BELIEF_FIELDS).  Needs the vision layer.  Allocates `belief`
@@ -704,13 +764,19 @@ class Soccer2DMatchVecEnv:
     then see, then the belief step.  `belief` = a dict of S2DBeliefParams fields.  The obs tensor is the engine's `belief`
     buffer, updated in place; reset(mask) leaves the masked matches' rows unknown.
 
+    hear = True (obs 'see' or 'belief'): the agents talk (MatchEngine.hear_step: the layer of include/s2d_match.h, "Hearing").
+    Observations are float32 [N, agents, 224] = [row | hear row] -- the width of an agent row -- and actions [N, agents, 17] =
+    the five see words, then the 12 say words (said, attention command, 10 payload words).  A step ends with hear_step on the
+    engine's done: what an agent says with its command is in the listeners' next observation.  `hear_params` = a dict of
+    S2DHearParams fields.  Not offered while a see actor plays the opponent (that opponent cannot speak yet).
+
     reward = 'goals' (the default: the rewards above) | a dict by term name | six weights: the shaped per-agent reward the
     cycle kernel computes (MatchEngine.set_agent_reward; chaser_only as there) in the place of the signed team reward, [N, 22]
     or [N, 11], for obs 'agent' and 'see' (not while a see actor plays the opponent; obs='state' has no per-agent reward).
     """
 
     @staticmethod
-    def spaces(opponent=None, obs='state'):
+    def spaces(opponent=None, obs='state', hear=False):
         """(observation_space, action_space) of an env with this opponent and observation (no engine needed)."""
         import numpy as np
         from .spaces import Box
@@ -719,6 +785,15 @@ class Soccer2DMatchVecEnv:
         if obs not in ('state', 'agent', 'see', 'belief'):
             raise ValueError(f"obs must be 'state', 'agent', 'see' or 'belief', got {obs!r}")
         agents = 22 if opponent is None else 11
+        if hear:
+            if obs not in ('see', 'belief'):
+                raise ValueError("hear=True needs obs='see' or obs='belief'")
+            if _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'see':
+                raise ValueError("hear=True is not offered while a see actor plays the opponent (that opponent cannot speak yet)")
+            # [row | hear row]: 192 + 32 words; actions = the five see words, then the 12 say words
+            return (Box(low=-1.0e6, high=1.0e6 if obs == 'see' else M.BELIEF_COUNT_LIMIT, shape=(agents, M.SEE_DIM + M.HEAR_DIM),
+                        dtype=np.float32),
+                    Box(low=-180.0, high=180.0, shape=(agents, 5 + M.SAY_ROW), dtype=np.float32))
         if obs in ('see', 'belief'):               # (a freshly reset belief row holds BELIEF_COUNT_LIMIT in its counts)
             return (Box(low=-1.0e6, high=1.0e6 if obs == 'see' else M.BELIEF_COUNT_LIMIT, shape=(agents, M.SEE_DIM), dtype=np.float32),
                     Box(low=-180.0, high=180.0, shape=(agents, 5), dtype=np.float32))
@@ -729,8 +804,11 @@ class Soccer2DMatchVecEnv:
         return ospace, Box(low=-180.0, high=180.0, shape=(agents, 3), dtype=np.float32)
 
     def __init__(self, num_envs, device='cuda:0', opponent=None, obs='state', vision=None, reward='goals', chaser_only=False,
-                 belief=None, **kwargs):
-        self.observation_space, self.action_space = self.spaces(opponent, obs)
+                 belief=None, hear=False, hear_params=None, **kwargs):
+        self.observation_space, self.action_space = self.spaces(opponent, obs, hear)
+        if hear_params is not None and not hear:
+            raise ValueError("hear parameters need hear=True")
+        self.hears = bool(hear)
         if _is_match_actor(opponent) and getattr(opponent, 'obs', 'agent') == 'belief':
             raise ValueError("a belief actor is not offered as the in-kernel opponent (the env updates its belief after the cycle, "
                              "the kernel before it); use a see actor with obs='belief'")
@@ -775,17 +853,27 @@ class Soccer2DMatchVecEnv:
             self._view = torch.zeros((self.num_envs, M.MATCH_PLAYERS, 2), dtype=torch.float32, device=self.device)
         if obs in ('agent', 'see', 'belief'):
             self._slots = 'all' if opponent is None else 'left'
-            self._aobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
+            self._aobs = torch.empty((self.num_envs, self.observation_space.shape[0], M.SEE_DIM if self.hears else
+                                      self.observation_space.shape[1]), dtype=torch.float32, device=self.device)
             # reward sign per agent: the left team's reward for slots 0..10, its negative for 11..21
             self._rsign = torch.tensor([1.0] * 11 + ([-1.0] * 11 if opponent is None else []), dtype=torch.float32, device=self.device)
         if obs == 'belief':                              # _aobs takes the see rows, the layer's input; the obs is engine.belief
             self.engine.enable_belief(self._slots, **(belief or {}))
+        if self.hears:                                   # the say rows of all 22 players; an in-kernel opponent's never speak
+            self.engine.enable_hearing(**(hear_params or {}))
+            self._say = torch.zeros((self.num_envs, M.MATCH_PLAYERS, M.SAY_ROW), dtype=torch.float32, device=self.device)
+            self._hobs = torch.empty((self.num_envs,) + tuple(self.observation_space.shape), dtype=torch.float32, device=self.device)
         self._shaped = shaped
         if shaped:
             self.engine.set_agent_reward(reward, chaser_only)
 
     def _obs(self):
         e = self.engine
+        if self.hears:                                   # [row | hear row] into one buffer
+            row = e.see(self._slots, out=self._aobs) if self.obs_kind == 'see' else e.belief
+            self._hobs[..., :M.SEE_DIM] = row
+            self._hobs[..., M.SEE_DIM:] = e.hear_rows(self._slots)
+            return self._hobs
         if self.obs_kind == 'agent':
             return e.agent_observations(self._slots, out=self._aobs)
         if self.obs_kind == 'see':
@@ -803,9 +891,12 @@ class Soccer2DMatchVecEnv:
         if actions is None:
             raise ValueError(f"with obs={self.obs_kind!r}, step() needs actions [N, {agents}, 5]")
         a = torch.as_tensor(actions, device=self.device).to(torch.float32)
-        if tuple(a.shape) != (self.num_envs, agents, 5):
-            raise ValueError(f"actions must have shape ({self.num_envs}, {agents}, 5), got {tuple(a.shape)}")
-        self._view[:, :agents] = a[..., 3:]
+        width = 5 + M.SAY_ROW if self.hears else 5
+        if tuple(a.shape) != (self.num_envs, agents, width):
+            raise ValueError(f"actions must have shape ({self.num_envs}, {agents}, {width}), got {tuple(a.shape)}")
+        self._view[:, :agents] = a[..., 3:5]
+        if self.hears:
+            self._say[:, :agents] = a[..., 5:]
         return a[..., :3].contiguous()
 
     def step(self, actions=None):
@@ -832,6 +923,8 @@ class Soccer2DMatchVecEnv:
             e.vision_step(self._view, done=True)
         if self.obs_kind == 'belief':                     # this cycle's see rows into the memory; a restarted match forgets
             e.belief_step(e.see(self._slots, out=self._aobs), done=True)
+        if self.hears:                                    # what was said with this cycle's commands; a restarted match is silent
+            e.hear_step(self._say, done=True)
         if self._shaped:                                  # the cycle kernel's per-agent reward, the controlled agents' columns
             return self._obs(), self._ro['agent_reward'][0, :, :self._rsign.numel()], e.done, info
         if self.obs_kind in ('agent', 'see', 'belief'):

@@ -515,7 +515,7 @@ int s2d_match_rollout_reward(S2DMatchHandle h, int n_steps, const float *actions
  * nothing of it: the three state planes are the caller's, an engine that never calls these functions is byte for byte the engine
  * without them.  Deviations: the self words are exact (self-localisation from flags and lines is not modelled: they are what
  * sense_body plus a perfect localiser would give); no landmark flags or lines; no gaussian_see; nothing is heard but the referee
- * (the game words); synchronous timing only.
+ * (the game words; what players say is the opt-in "Hearing" layer below, a row of its own); synchronous timing only.
  *
  * Parameters (ServerParam names; doubles, each rounded to fp32 once; a reciprocal inv(v) is the float of the double 1 / v):
  *   view_angle[3]       60, 120, 180 degrees for narrow, normal, wide (rcssserver: visible_angle 90 scaled by 2/3, 4/3 and 2 in
@@ -870,6 +870,92 @@ int s2d_match_set_belief_network(S2DMatchHandle h, const S2DMatchBeliefNet *net)
 int s2d_match_rollout_belief(S2DMatchHandle h, int n_steps, const float *actions_dev, const float *view_actions_dev,
                              const S2DMatchRollout *out, float *actions_out_dev, int32_t *net_index_out_dev, float *logp_out_dev,
                              uint32_t obs_mask, float *see_out_dev, float *belief_out_dev, void *stream);
+
+/* Hearing: say and hear, an opt-in audio layer beside the vision and belief layers -- Say (idl/service.proto:549-574), AttentionTo /
+ * AttentionToOf (:585-592), ServerParam player_say_msg_size, player_hear_max, player_hear_inc, player_hear_decay (:1511-1514) and
+ * audio_cut_dist (:1520).  Restated from the published behaviour of rcssserver; like every 11v11 rule it is this project's own
+ * restatement: PARITY TO RCSSSERVER UNPINNED.  The fp32 words below are the contract (the device equals tests/hear_ref.c bit for
+ * bit).  The engine handle stores nothing of it: all state is in caller-owned planes, an engine that never calls these functions is
+ * byte for byte the engine without them.  Deviations: at most ONE message per side and cycle is delivered, even where hear_max /
+ * hear_decay would allow more (the capacity still tallies); the draw among several speakers is per listener, not one shuffle per
+ * cycle; a player does not hear itself; no coach; a message reaches the listener one step after it was said (the step that follows
+ * the body step it was given with) and is never kept longer.  A message is say_msg_size symbols, each one of say_levels levels on
+ * [-1, 1]: rcssserver's 10 characters of a 73-character alphabet kept as numbers -- the same channel capacity, no string codec.
+ *
+ * Parameters (doubles, each rounded to fp32 or to int once):
+ *   audio_cut_dist  50   finite, >= 0: a speaker further away is not heard
+ *   hear_max        1    whole, 1 .. 1e6: the largest hear capacity
+ *   hear_inc        1    whole, 0 .. 1e6: what a capacity gains per cycle
+ *   hear_decay      1    whole, 1 .. 1e6: what a delivered message costs
+ *   say_msg_size    10   whole, 1 .. S2D_SAY_WORDS: payload words delivered; the others arrive as +0
+ *   say_levels      73   odd whole, 3 .. 4097: half = the float of (say_levels - 1) / 2, inv_half = the float of the double 1 / half */
+#define S2D_HEAR_DIM 32            /* float32 words per listener: 128 B, two lines of 64 B; see row + hear row = 224 words */
+#define S2D_HEAR_RECORD 16         /* words of one record: ours at [0, 16), theirs at [16, 32) */
+#define S2D_SAY_WORDS 10           /* payload words of a message */
+#define S2D_SAY_ROW 12             /* words of a say row: said, attention command, payload */
+#define S2D_MATCH_ST_HEAR 9        /* Philox stream id of the hear draws */
+typedef struct S2DHearParams {
+  double audio_cut_dist, hear_max, hear_inc, hear_decay, say_msg_size, say_levels;
+} S2DHearParams;
+void s2d_match_hear_default_params(S2DHearParams *prm);
+/* Errors: NULL; a value outside the rule above (non-finite values included). */
+int s2d_match_hear_validate(const S2DHearParams *prm);
+
+/* The hear state: caller-owned device planes.  The three int32 planes are [N][24] (slot = player; slots 22, 23 are padding), 4-byte
+ * aligned.  Own-frame slots are the see rows': the listener's team is 0..10, the other team 11..21 (the raw slot for the left
+ * team, (slot + 11) % 22 for the right team).
+ * A hear row is two records of S2D_HEAR_RECORD words, ours (the listener's team) then theirs; integers and flags as float values:
+ *   0       heard (0 / 1)
+ *   1       sender: own index + 1 (1..11) for a teammate; +0 in the theirs record -- opponents' numbers are not heard
+ *   2       dir: the direction the message came from, relative to the face, whole degrees
+ *   3       missed: the count of candidates not delivered
+ *   4       the side's capacity after the step
+ *   5       attention, ours record only: 0 for none, else own-frame slot + 1; +0 in the theirs record
+ *   6..15   payload */
+typedef struct S2DMatchHear {
+  int32_t *cap_our, *cap_opp;   /* hear capacities for the listener's team and for the other team */
+  int32_t *attention;           /* -1 for none, otherwise an own-frame slot 0..21; any other value reads as -1 */
+  float *hear;                  /* float[N][22][S2D_HEAR_DIM], 16-byte aligned */
+} S2DMatchHear;
+/* For the masked matches (mask_dev uint8[N], NULL = all): caps = hear_max and attention = -1 in every slot of the three planes; every
+ * word of the 22 hear rows +0, then word 4 of both records = hear_max (the reset row).
+ * Errors (S2D_EINVAL, nothing written): invalid parameters, NULL or unaligned planes, a hear plane overlapping another plane. */
+int s2d_match_hear_reset(S2DMatchHandle h, const S2DHearParams *prm, const S2DMatchHear *hear, const uint8_t *mask_dev, void *stream);
+/* One cycle of hearing; call it once after each body step, beside s2d_match_vision_step.
+ *   say_dev   float[N][22][S2D_SAY_ROW] (raw slots), 16-byte aligned, or NULL = nobody speaks or changes attention.  It holds what
+ *             the players said with the body step just taken.
+ *               word 0       said: nonzero and not NaN means said (-0 is zero)
+ *               word 1       attention command: -1 switches attention off; a whole k in 1..22 attends own-frame slot k - 1, except
+ *                            that the listener's own slot keeps; 0, NaN and every other value keep
+ *               words 2..11  payload
+ *   neck_dev  the vision layer's neck plane float[N][24], 4-byte aligned, or NULL = every neck +0
+ *   done_dev  uint8[N] or NULL
+ * Listener p of match e, on the current (post-step) engine state, in this order:
+ *   1. done_dev[e] != 0: p's three plane words and row become the reset state and nothing below happens (a message does not cross
+ *      a restart).
+ *   2. otherwise, p sent off (card == S2D_CARD_RED): the three plane words are kept as they are, the row is all +0, and nothing
+ *      below happens.
+ *   3. p's attention command is applied (a stored attention outside -1..21 first reads as -1).
+ *   4. for both sides: a cap outside [0, hear_max] reads as hear_max; cap = min(cap + hear_inc, hear_max).
+ *   5. candidates of side s (ours: p's team; theirs: the other): every j != p of that side with card < S2D_CARD_RED who said, with
+ *      d = hypot2(dx, dy) <= audio_cut_dist; dx = x_j - x_p, dy = y_j - y_p on the own-frame values (positions times sgn), so that
+ *      mirrored states give the mirrored listener bitwise the same row whenever no draw decides.
+ *   6. if cap_s >= hear_decay and side s has a candidate, the listener hears one:
+ *        the winner is the attended slot if it is a candidate of this side; otherwise the candidate with the smallest
+ *        (u_j, own-frame slot), u_j = w.x >> 8 of the Philox block with counter = the match's tick as the state holds it, stream
+ *        S2D_MATCH_ST_HEAR, block = p * 24 + j (raw slots), the random policy's keys;
+ *        cap_s -= hear_decay; heard = 1; sender as above; missed = candidates - 1;
+ *        dir = d == 0 ? 0 : rintf(norm_deg_any(atan2_deg(dy, dx) - face)), face = norm_deg_any(body + neck) with the own-frame body;
+ *        payload word i < say_msg_size: v NaN: +0; otherwise rintf(clamp(v, -1, 1) * half) * inv_half (clamp as in
+ *        s2d_match_vision_step; a quantised word may be -0); payload word i >= say_msg_size: +0.
+ *      otherwise (no capacity or no candidate): heard = 0, missed = the candidate count, sender, dir and payload +0.
+ *   7. words 4 and 5 of both records are written and the three plane words stored.
+ * The row is a pure function of state, planes, say rows and tick.  Reads x, y, body, card and tick of the engine; writes the four
+ * planes of `hear` only.
+ * Errors (S2D_EINVAL, nothing written): invalid parameters; NULL or unaligned planes; an unaligned say_dev or neck_dev; a plane of
+ * `hear` overlapping another plane of it, say_dev, neck_dev or done_dev. */
+int s2d_match_hear_step(S2DMatchHandle h, const S2DHearParams *prm, const S2DMatchHear *hear, const float *neck_dev,
+                        const float *say_dev, const uint8_t *done_dev, void *stream);
 
 /* Which instantiation of the cycle kernel this engine launches: "...<stock>" when its configuration equals
  * s2d_match_default_config() in every rule / physics word (those are compile-time constants there), "...<general>" otherwise
